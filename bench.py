@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- env-steps/sec of the MI355X-native PPO actor-learner (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -183,6 +183,10 @@ def parse():
     p.add_argument("--inject-host-stall-ms", type=float, default=0.0,
                    help="DIAGNOSTIC: sleep this long on the host before the 6th minibatch of every update (what a descheduled "
                         "thread / page-in / garbage collection does on a busy box); compare with and without --sync-metrics")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed (rank 0: parameters and Adam state after its update, "
+                        "its logged scalars, its rollout's actions / log-probs / values / rewards / advantages / returns) as DIR/<name>.npy, "
+                        "f32 / f64, at most 64 MB in all; inputs are seeded, so two builds run with the same arguments compare output for output")
     cli = p.parse_args()
     cfg = CONFIGS[cli.config]
     if cli.local_num_envs is None:
@@ -401,6 +405,36 @@ def preflight(rank: int, world: int, device, backend: str, verbose: bool) -> dic
     return info
 
 
+DUMP_SCALARS = ("loss", "policy_loss", "value_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac", "explained_variance", "num_updates")
+DUMP_MAX_ELEMENTS = 1_750_000      # per array (7 MB of f32; nine arrays stay under 64 MB): the agent's 1,686,693 parameters fit whole
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, learner, metrics) -> dict:
+    """``--dump-outputs DIR``: what the last timed step handed its caller, one ``DIR/<name>.npy`` each -- the flat parameters and the Adam
+    moments after its update, the logged scalars of that update (float64, in DUMP_SCALARS order), and its rollout's storage
+    (actions, log-probs, values, rewards, advantages, returns; f32, flattened).  An array longer than DUMP_MAX_ELEMENTS is written as a
+    fixed sample of its elements (seeded: the same positions for the same shape), so the dump stays under DUMP_MAX_BYTES.
+    Returns {name: number of elements written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"params": learner.flat.params, "adam_exp_avg": learner.flat.exp_avg, "adam_exp_avg_sq": learner.flat.exp_avg_sq}
+    for name in ("actions", "logprobs", "values", "rewards", "advantages", "returns"):
+        arrays[name] = getattr(learner, name)
+    written, total = {}, 0
+    for name, t in arrays.items():
+        a = t.detach().reshape(-1).to(torch.float32).cpu().numpy()
+        if a.size > DUMP_MAX_ELEMENTS:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name], total = a.size, total + a.nbytes
+    s = np.array([float(metrics[k]) for k in DUMP_SCALARS], dtype=np.float64)
+    np.save(os.path.join(out_dir, "scalars.npy"), s)
+    written["scalars"], total = s.size, total + s.nbytes
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs wrote {total} bytes"
+    print(f"[bench] outputs of the last timed step: {total / 2**20:.1f} MB in {out_dir}", file=sys.stderr, flush=True)
+    return written
+
+
 def self_launch(cli) -> int:
     """``python bench.py --gpus N`` with N > 1 and no launcher around it: start the N ranks ourselves (one process per GPU,
     the launch line of the module docstring) and hand their output through.  Refuses -- loudly, non-zero -- when the box
@@ -408,7 +442,11 @@ def self_launch(cli) -> int:
     import socket
     import subprocess
 
-    have = torch.cuda.device_count() if torch.cuda.is_available() else 0
+    # counted in a child that exits before the ranks start: the launcher itself never opens the GPU, so a --gpus N run has the N ranks
+    # (and the launcher of torch.distributed.run) on the device, not one process more
+    probe = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count() if torch.cuda.is_available() else 0)"],
+                           capture_output=True, text=True)
+    have = int(probe.stdout.split()[-1]) if probe.returncode == 0 and probe.stdout.split() else 0
     if cli.same_device and have >= 1:
         have = cli.gpus                              # plumbing smoke: every rank on cuda:0
     if have < cli.gpus:
@@ -666,6 +704,7 @@ def main():
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+    dumped = dump_outputs(cli.dump_outputs, learner, metrics) if cli.dump_outputs and rank == 0 else None      # (before the event-bracket iterations below)
     timing_iters = cli.steps
     if not cli.no_kernel_timing:
         # the per-launch durations: one more iteration issued launch by launch with event brackets (outside the timed region; the
@@ -721,6 +760,8 @@ def main():
         }
         if cli.collective_preflight:
             out["collective_preflight"] = cli.collective_preflight
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": cli.dump_outputs, "elements": dumped}
         if learner.fused_cnn:
             out["config"]["cnn"], out["matrix_arithmetic"] = describe_cnn(kernel_of, M)
         timed = phase_events[cli.warmup:cli.warmup + cli.steps]
@@ -1017,6 +1058,7 @@ def main_continuous(cli, rank, world, device):
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+    dumped = dump_outputs(cli.dump_outputs, learner, metrics) if cli.dump_outputs and rank == 0 else None      # (before the event-bracket iterations below)
     if not cli.no_kernel_timing:
         graphs, learner._update_graphs = learner._update_graphs, None
         install_timing_hooks()
@@ -1045,6 +1087,8 @@ def main_continuous(cli, rank, world, device):
                                   else "two 64-64 tanh MLPs as torch Linear layers (library GEMMs; MI355PPO_MLP=torch)"},
             "final_loss": metrics["loss"],
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": cli.dump_outputs, "elements": dumped}
         timed = phase_events[cli.warmup:cli.warmup + cli.steps]
         out["phases_ms"] = {"rollout_incl_gae": float(np.mean([e[0].elapsed_time(e[1]) for e in timed])),
                             "update": float(np.mean([e[1].elapsed_time(e[2]) for e in timed])),

@@ -955,6 +955,49 @@ def mint_continuous_iteration():
     _save("continuous_iteration", cases)
 
 
+CLI_SCRIPTS = ["ppo", "ppo_atari", "ppo_atari_envpool", "ppo_atari_multigpu", "ppo_continuous_action", "ppo_atari_lstm", "ppo_procgen",
+               "ppo_rnd_envpool", "ppg_procgen"]
+
+
+def mint_cli_surface():
+    """tests/golden/cli_surface.json: the reference's command-line surface as data -- every field of each script's ``Args`` with its
+    default (``exp_name`` left out), and every ``parser.add_argument`` of ppo_pettingzoo_ma_atari.py with its default (``exp_name``:
+    computed from the file name, left out).  tests/test_cli_scripts.py and tests/test_ma_atari_script.py check against it."""
+    import ast
+    import json
+
+    args = {}
+    for script in CLI_SCRIPTS:
+        tree = ast.parse("\n".join(R._read(script + ".py")))
+        (cls,) = [n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == "Args"]
+        ref = {}
+        for b in cls.body:
+            if isinstance(b, ast.AnnAssign) and b.target.id != "exp_name":
+                try:
+                    ref[b.target.id] = ast.literal_eval(b.value)
+                except ValueError:
+                    v = b.value
+                    if isinstance(v, ast.Call) and getattr(v.func, "id", "") == "int" and len(v.args) == 1:
+                        ref[b.target.id] = int(ast.literal_eval(v.args[0]))      # `int(25e6)` (ppo_procgen.py)
+                    else:
+                        ref[b.target.id] = []          # field(default_factory=lambda: [])
+        args[script] = ref
+    argparse_defaults = {}
+    for node in ast.walk(ast.parse("\n".join(R._read("ppo_pettingzoo_ma_atari.py")))):
+        if isinstance(node, ast.Call) and getattr(node.func, "attr", "") == "add_argument":
+            flag = ast.literal_eval(node.args[0])
+            default = [k.value for k in node.keywords if k.arg == "default"][0]
+            try:
+                argparse_defaults[flag.lstrip("-").replace("-", "_")] = ast.literal_eval(default)
+            except ValueError:
+                pass                                                   # exp_name: os.path.basename(__file__).rstrip(".py")
+    path = os.path.join(OUT, "cli_surface.json")
+    with open(path, "w") as fh:
+        json.dump({"args": args, "ppo_pettingzoo_ma_atari_argparse": argparse_defaults}, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print(f"cli_surface: {len(args)} Args classes, {len(argparse_defaults)} argparse flags")
+
+
 def main():
     assert R.available(), "needs /root/reference (build container only)"
     os.makedirs(OUT, exist_ok=True)
@@ -979,6 +1022,7 @@ def main():
     mint_ma_atari_update()
     mint_continuous_iteration()
     mint_ppo_iteration()
+    mint_cli_surface()
 
 
 if __name__ == "__main__":

@@ -162,3 +162,29 @@ def test_round_6_measurement_switches_exist(monkeypatch):
     assert pc["rollout_steps_timed"] == 3 and pc["minibatch_rows"] == 32 and pc["minibatch_updates_per_iteration"] == 4
     want = 8 * pc["rollout_step_s"] + pc["gae_s"] + 4 * pc["minibatch_s"]
     assert abs(s["seconds"] - want) < 1e-9 and abs(s["sps"] - 64 / want) < 1e-6 and np.isfinite(s["final_loss"])
+
+
+def test_dump_outputs_writes_the_last_steps_arrays_within_the_budget(monkeypatch, tmp_path):
+    """``--dump-outputs DIR``: one f32 / f64 ``.npy`` per output of the timed path, the same fixed sample of an array too long to keep whole
+    from run to run, 64 MB at most in all."""
+    from types import SimpleNamespace
+
+    bench = _load_bench(monkeypatch)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--dump-outputs", str(tmp_path / "a")])
+    assert bench.parse().dump_outputs == str(tmp_path / "a")
+    g = torch.Generator().manual_seed(0)
+    T, N, P = 128, 16384, 1686693                     # 2,097,152 rollout rows: more than one array may hold whole
+    flat = SimpleNamespace(params=torch.randn(P, generator=g), exp_avg=torch.randn(P, generator=g), exp_avg_sq=torch.rand(P, generator=g))
+    learner = SimpleNamespace(flat=flat, **{k: torch.randn(T, N, generator=g) for k in ("actions", "logprobs", "values", "rewards", "advantages", "returns")})
+    metrics = dict(zip(bench.DUMP_SCALARS, [0.5, -0.1, 0.2, 1.38, 0.01, 0.02, 0.1, float("nan"), 16]))
+    got = bench.dump_outputs(str(tmp_path / "a"), learner, metrics)
+    bench.dump_outputs(str(tmp_path / "b"), learner, metrics)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(n + ".npy" for n in got) and sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    p = np.load(tmp_path / "a" / "params.npy")
+    assert p.dtype == np.float32 and np.array_equal(p, flat.params.numpy())                  # whole
+    v = np.load(tmp_path / "a" / "values.npy")
+    assert v.dtype == np.float32 and v.size == bench.DUMP_MAX_ELEMENTS and np.isin(v, learner.values.numpy()).all()
+    assert np.array_equal(v, np.load(tmp_path / "b" / "values.npy"))                          # the same sample every time
+    s = np.load(tmp_path / "a" / "scalars.npy")
+    assert s.dtype == np.float64 and s[0] == 0.5 and s[-1] == 16 and np.isnan(s[7])

@@ -1,9 +1,9 @@
 """Drop-in CLI surface: every flag of the reference's Args exists with the same default, both spellings
 parse, and each script runs end-to-end on CPU (the reference's own tests are exit-code smoke tests of
 exactly this kind: tests/test_classic_control.py:4-9, test_envpool.py:4-9, test_atari_multigpu.py:4-9)."""
-import ast
 import dataclasses
 import importlib
+import json
 import os
 import subprocess
 import re
@@ -12,11 +12,10 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/cleanrl"
 SCRIPTS = ["ppo", "ppo_atari", "ppo_atari_envpool", "ppo_atari_multigpu", "ppo_continuous_action", "ppo_atari_lstm", "ppo_procgen", "ppo_rnd_envpool", "ppg_procgen"]
 
-# the reference's flag surface (cleanrl/<script>.py Args), recorded so that this test also runs where
-# /root/reference is absent; test_recorded_surface_matches_reference re-derives it when it is present
+# the reference's flag surface (cleanrl/<script>.py Args), restated here; test_recorded_surface_matches_reference checks it against
+# tests/golden/cli_surface.json (the reference's Args fields and defaults as data, minted by oracle/mint_goldens.py)
 REF_DEFAULTS = {
     "ppo": dict(seed=1, torch_deterministic=True, cuda=True, track=False, wandb_project_name="cleanRL", wandb_entity=None,
                 capture_video=False, env_id="CartPole-v1", total_timesteps=500000, learning_rate=2.5e-4, num_envs=4,
@@ -61,22 +60,10 @@ def test_flag_surface_matches_reference(script):
         assert mine[name] == default, f"{script}.py --{name}: default {mine[name]!r} != reference {default!r}"
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present on this box")
 @pytest.mark.parametrize("script", SCRIPTS)
 def test_recorded_surface_matches_reference(script):
-    tree = ast.parse(open(os.path.join(REF, script + ".py")).read())
-    (cls,) = [n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == "Args"]
-    ref = {}
-    for b in cls.body:
-        if isinstance(b, ast.AnnAssign) and b.target.id != "exp_name":
-            try:
-                ref[b.target.id] = ast.literal_eval(b.value)
-            except ValueError:
-                v = b.value
-                if isinstance(v, ast.Call) and getattr(v.func, "id", "") == "int" and len(v.args) == 1:
-                    ref[b.target.id] = int(ast.literal_eval(v.args[0]))      # `int(25e6)` (ppo_procgen.py:40)
-                else:
-                    ref[b.target.id] = []          # field(default_factory=lambda: [])
+    with open(os.path.join(ROOT, "tests", "golden", "cli_surface.json")) as fh:
+        ref = json.load(fh)["args"][script]
     assert ref == REF_DEFAULTS[script]
 
 

@@ -96,14 +96,14 @@ def test_env_wise_minibatch_indices_are_time_major():
         assert np.array_equal(got, want)
 
 
-def test_ppo_atari_lstm_cli_runs_on_cpu():
+def test_ppo_atari_lstm_cli_runs_on_cpu(tmp_path):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "cleanrl_amd", "ppo_atari_lstm.py"), "--no-cuda", "--num-envs", "4",
                           "--num_steps", "8", "--total-timesteps", "64", "--num-minibatches", "2", "--update-epochs", "1",
-                          "--seed", "3"], capture_output=True, text=True, cwd="/tmp", timeout=600)
+                          "--seed", "3"], capture_output=True, text=True, cwd=tmp_path, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     sps = [ln for ln in out.stdout.splitlines() if ln.startswith("SPS:")]
     assert len(sps) == 2 and all(int(ln.split()[1]) > 0 for ln in sps)
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "cleanrl_amd", "ppo_atari_lstm.py"), "--no-cuda", "--num-envs", "3",
                           "--num-steps", "4", "--total-timesteps", "12", "--num-minibatches", "2"], capture_output=True,
-                         text=True, cwd="/tmp", timeout=600)
+                         text=True, cwd=tmp_path, timeout=600)
     assert bad.returncode != 0 and "divisible" in bad.stderr                               # :296 assert

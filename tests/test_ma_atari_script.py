@@ -2,7 +2,7 @@
 four frame channels divided by 255) against the reference's own lines (tests/golden/ma_atari_update.npz, minted by
 oracle/mint_goldens.py::mint_ma_atari_update from cleanrl/ppo_pettingzoo_ma_atari.py:86-118 Agent and :250-290 update),
 the argparse flag surface of the reference (strtobool flags included), the stand-in env and the CLI."""
-import ast
+import json
 import os
 import subprocess
 import sys
@@ -19,7 +19,6 @@ from cleanrl_amd.learner import PPOLearner
 from cleanrl_amd.learner_smoke import default_args
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/cleanrl/ppo_pettingzoo_ma_atari.py"
 
 
 @pytest.fixture
@@ -60,21 +59,13 @@ def test_ma_atari_host_minibatch_steps_match_the_reference_lines(one_thread):
     assert torch.equal(b_obs, keep)                                   # the stored observations are never scaled in place
 
 
-@pytest.mark.skipif(not os.path.isfile(REF), reason="reference tree not present on this box")
 def test_flag_surface_matches_the_reference_argparse():
-    """Every ``parser.add_argument`` of the reference exists as a field with the same default, under both spellings."""
+    """Every ``parser.add_argument`` of the reference (tests/golden/cli_surface.json, minted by oracle/mint_goldens.py) exists as a field
+    with the same default, under both spellings."""
     from cleanrl_amd.ppo_pettingzoo_ma_atari import Args
 
-    tree = ast.parse(open(REF).read())
-    ref = {}
-    for node in ast.walk(tree):
-        if isinstance(node, ast.Call) and getattr(node.func, "attr", "") == "add_argument":
-            flag = ast.literal_eval(node.args[0])
-            default = [k.value for k in node.keywords if k.arg == "default"][0]
-            try:
-                ref[flag.lstrip("-").replace("-", "_")] = ast.literal_eval(default)
-            except ValueError:
-                pass                                                   # exp_name: os.path.basename(__file__).rstrip(".py")
+    with open(os.path.join(ROOT, "tests", "golden", "cli_surface.json")) as fh:
+        ref = json.load(fh)["ppo_pettingzoo_ma_atari_argparse"]
     assert len(ref) == 24
     a = cli.parse(Args, [])
     for name, default in ref.items():
@@ -98,9 +89,9 @@ def test_synthetic_two_player_env_contract():
     assert ends >= 2
 
 
-def test_ppo_pettingzoo_ma_atari_cli_runs_on_cpu():
+def test_ppo_pettingzoo_ma_atari_cli_runs_on_cpu(tmp_path):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "cleanrl_amd", "ppo_pettingzoo_ma_atari.py"), "--cuda", "False",
                           "--num-envs", "4", "--num-steps", "8", "--total-timesteps", "64", "--num-minibatches", "2",
-                          "--update-epochs", "1"], capture_output=True, text=True, cwd="/tmp", timeout=900)
+                          "--update-epochs", "1"], capture_output=True, text=True, cwd=tmp_path, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     assert out.stdout.count("SPS:") == 2

@@ -80,9 +80,9 @@ def test_flatten_unflatten_roundtrip():
     assert torch.equal(unflatten01(flatten01(a), a.shape[:2]), a)
 
 
-def test_ppg_procgen_cli_runs_on_cpu():
+def test_ppg_procgen_cli_runs_on_cpu(tmp_path):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "cleanrl_amd", "ppg_procgen.py"), "--no-cuda", "--num-envs", "4",
                           "--num_steps", "8", "--total-timesteps", "128", "--num-minibatches", "2", "--n-iteration", "2",
-                          "--e-auxiliary", "1", "--num-aux-rollouts", "4"], capture_output=True, text=True, cwd="/tmp", timeout=900)
+                          "--e-auxiliary", "1", "--num-aux-rollouts", "4"], capture_output=True, text=True, cwd=tmp_path, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     assert out.stdout.count("SPS:") == 4 and out.stdout.count("aux epoch 1") == 2      # 2 phases x 2 policy iterations

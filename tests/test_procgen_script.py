@@ -78,10 +78,10 @@ def test_synthetic_procgen_env_contract():
     assert ends > 3 and a.ret_rms.count > 2000
 
 
-def test_ppo_procgen_cli_runs_on_cpu():
+def test_ppo_procgen_cli_runs_on_cpu(tmp_path):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "cleanrl_amd", "ppo_procgen.py"), "--no-cuda", "--num-envs", "4",
                           "--num_steps", "8", "--total-timesteps", "64", "--num-minibatches", "2", "--update-epochs", "1"],
-                         capture_output=True, text=True, cwd="/tmp", timeout=900)
+                         capture_output=True, text=True, cwd=tmp_path, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     sps = [ln for ln in out.stdout.splitlines() if ln.startswith("SPS:")]
     assert len(sps) == 2 and all(int(ln.split()[1]) > 0 for ln in sps)

@@ -88,10 +88,10 @@ def test_running_mean_std_is_the_batch_parallel_update():
     assert np.allclose(rms.mean, x.mean(0), atol=1e-5) and np.allclose(rms.var, x.var(0), atol=1e-4) and abs(rms.count - 1000) < 1e-3
 
 
-def test_ppo_rnd_envpool_cli_runs_on_cpu():
+def test_ppo_rnd_envpool_cli_runs_on_cpu(tmp_path):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "cleanrl_amd", "ppo_rnd_envpool.py"), "--no-cuda", "--num-envs", "4",
                           "--num_steps", "8", "--total-timesteps", "64", "--num-minibatches", "2", "--update-epochs", "1",
-                          "--num-iterations-obs-norm-init", "2"], capture_output=True, text=True, cwd="/tmp", timeout=900)
+                          "--num-iterations-obs-norm-init", "2"], capture_output=True, text=True, cwd=tmp_path, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     assert "Start to initialize observation normalization parameter" in out.stdout
     sps = [ln for ln in out.stdout.splitlines() if ln.startswith("SPS:")]
