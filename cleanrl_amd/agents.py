@@ -13,6 +13,8 @@ fused loss kernel (``heads``/``dist_params`` below are the seam).
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -305,11 +307,25 @@ class ContinuousAgent(nn.Module):
         return action, probs.log_prob(action).sum(1), probs.entropy().sum(1), value
 
 
+LSTM_BACKENDS = ("torch", "fused")
+
+
+def lstm_backend_from_env() -> str:
+    """``MI355PPO_LSTM``: ``torch`` (default: the reference's per-step ``nn.LSTM`` loop) or ``fused`` (the sequence scans of
+    csrc/lstm.hip, ``ops.lstm_seq``)."""
+    v = os.environ.get("MI355PPO_LSTM", "torch")
+    if v not in LSTM_BACKENDS:
+        raise ValueError(f"MI355PPO_LSTM={v!r}: expected torch or fused")
+    return v
+
+
 class AtariLSTMAgent(_DiscreteMixin, nn.Module):
     """ppo_atari_lstm.py:117-165: NatureCNN on ONE 84x84 frame -> Linear(3136,512) -> LSTM(512,128) -> actor / critic.
     Same construction order as the reference (network layers, ``nn.LSTM`` default init, then bias := 0 and orthogonal
     weights in ``named_parameters`` order, then actor, critic), hence the same weights for the same torch seed.
-    The recurrent state is reset where ``done`` is 1, one time step at a time, exactly as ``get_states`` (:138-156)."""
+    The recurrent state is reset where ``done`` is 1, one time step at a time, exactly as ``get_states`` (:138-156).
+    ``lstm_backend`` (from ``MI355PPO_LSTM`` at construction; tests may set the attribute): ``torch`` runs that loop, ``fused``
+    runs all T steps as one scan (``ops.lstm_seq``: HIP kernels on the GPU, their host twins on CPU)."""
 
     obs_is_image = True
     recurrent = True
@@ -337,6 +353,7 @@ class AtariLSTMAgent(_DiscreteMixin, nn.Module):
         self.critic = layer_init(nn.Linear(128, 1), std=1)
         self.n_actions = envs.single_action_space.n
         self.rng = _SampleCounter()
+        self.lstm_backend = lstm_backend_from_env()
 
     def _normalise(self, x):
         if x.dtype == torch.uint8:
@@ -351,6 +368,8 @@ class AtariLSTMAgent(_DiscreteMixin, nn.Module):
     def states_from_features(self, hidden, lstm_state, done):
         """The LSTM logic of ``get_states`` (:141-156) on the (T*B, 512) features of T time-major steps of B envs."""
         batch_size = lstm_state[0].shape[1]
+        if self.lstm_backend == "fused":
+            return self._states_fused(hidden, lstm_state, done, batch_size)
         hidden = hidden.reshape((-1, batch_size, self.lstm.input_size))
         done = done.reshape((-1, batch_size))
         new_hidden = []
@@ -359,6 +378,13 @@ class AtariLSTMAgent(_DiscreteMixin, nn.Module):
             h, lstm_state = self.lstm(h.unsqueeze(0), (keep * lstm_state[0], keep * lstm_state[1]))
             new_hidden += [h]
         return torch.flatten(torch.cat(new_hidden), 0, 1), lstm_state
+
+    def _states_fused(self, hidden, lstm_state, done, batch_size):
+        """The same recurrence as one scan: gx = x W_ih^T + (b_ih + b_hh) for all T steps, then ``ops.lstm_seq``."""
+        lstm, H = self.lstm, self.lstm.hidden_size
+        gx = nn.functional.linear(hidden, lstm.weight_ih_l0, lstm.bias_ih_l0 + lstm.bias_hh_l0).reshape(-1, batch_size, 4 * H)
+        h, hT, cT = ops.lstm_seq(gx, lstm.weight_hh_l0, lstm_state[0][0], lstm_state[1][0], done.reshape(-1, batch_size))
+        return h.reshape(-1, H), (hT.unsqueeze(0), cT.unsqueeze(0))
 
     def heads_seq(self, xn, lstm_state, done):
         """xn: already-normalised f32 frames, time-major (T*B, 1, 84, 84) -> (logits, value, new state): the seam the

@@ -8,13 +8,14 @@
 // pointer here; a CUDA device always runs the HIP kernels and raises when they are missing (cleanrl_amd/_lib.py).
 //
 // Same math by construction: the row / element functions (gae_step, categorical_row, ppo_row_terms, mean_den_from_sums,
-// adam_elem, the Philox stream) are the device kernels' own, compiled for the host from the same headers (ppo_rows.h,
-// catrow.h, common.h), without FMA contraction.  Differences to the device results can come only from libm vs the device
+// adam_elem, the Philox stream, the LSTM cell and its 128-column products) are the device kernels' own, compiled for the host
+// from the same headers (ppo_rows.h, catrow.h, lstm_rows.h, common.h), without FMA contraction.  Differences to the device results can come only from libm vs the device
 // math library (expf / logf / sincosf: a few ulp) and from the order of the f64 reductions (row order here, fixed tree there).
 // Serial, single-threaded: sizes of config A are a few hundred rows.
 #include "common.h"
 #include "catrow.h"
 #include "ppo_rows.h"
+#include "lstm_rows.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -421,6 +422,104 @@ extern "C" MI355PPO_API int mi355ppo_obs_u8_to_f32_cpu(const uint8_t* src_u8, co
         const uint8_t* s = src_u8 + (size_t)(inds ? inds[r] : r) * row_bytes;
         float* d = dst_f32 + (size_t)r * row_bytes;
         for (int64_t k = 0; k < row_bytes; ++k) d[k] = scale_255 ? (float)s[k] / 255.0f : (float)s[k];
+    }
+    return MI355PPO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ LSTM
+namespace {
+
+// Column k of gate block q of W_hh (512, 128): the backward's operand, read in the device thread (q, k)'s order.
+struct LstmColumn {
+    const float* p;
+    MI355_HD float operator[](int r) const { return p[(size_t)r * kLstmH]; }
+};
+
+}  // namespace
+
+extern "C" MI355PPO_API int mi355ppo_lstm_seq_fwd_f32_cpu(const float* gx, const float* w_hh, const float* h0, const float* c0,
+                                                          const float* done, float* h, float* hT, float* cT, float* record, int T,
+                                                          int B, int H) {
+    const char* fn = "mi355ppo_lstm_seq_fwd_f32_cpu";
+    MI355_REQUIRE(gx && w_hh && h0 && c0 && done && h && hT && cT, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(H == kLstmH, MI355PPO_EINVAL, "%s: H=%d (only %d)", fn, H, kLstmH);
+    MI355_REQUIRE(T > 0 && B > 0, MI355PPO_EINVAL, "%s: T=%d B=%d must be positive", fn, T, B);
+    const size_t TB = (size_t)T * B;
+    for (int b = 0; b < B; ++b) {
+        float hk[kLstmH], ck[kLstmH], a[kLstmG];
+        const float keep0 = 1.0f - done[b];
+        for (int u = 0; u < kLstmH; ++u) {
+            hk[u] = keep0 * h0[(size_t)b * kLstmH + u];
+            ck[u] = keep0 * c0[(size_t)b * kLstmH + u];
+        }
+        for (int t = 0; t < T; ++t) {
+            const size_t row = (size_t)t * B + b;
+            for (int j = 0; j < kLstmG; ++j) a[j] = gx[row * kLstmG + j] + lstm_dot128(w_hh + (size_t)j * kLstmH, hk);
+            const float keep = t + 1 < T ? 1.0f - done[row + B] : 0.0f;
+            for (int u = 0; u < kLstmH; ++u) {
+                const LstmCell s = lstm_cell_fwd(a[u], a[kLstmH + u], a[2 * kLstmH + u], a[3 * kLstmH + u], ck[u]);
+                h[row * kLstmH + u] = s.h;
+                if (record) {
+                    float* g = record + row * kLstmG + u;
+                    g[0] = s.i;
+                    g[kLstmH] = s.f;
+                    g[2 * kLstmH] = s.g;
+                    g[3 * kLstmH] = s.o;
+                    record[TB * 4 * kLstmH + row * kLstmH + u] = s.c;
+                    record[TB * 5 * kLstmH + row * kLstmH + u] = hk[u];
+                    record[TB * 6 * kLstmH + row * kLstmH + u] = ck[u];
+                }
+                if (t + 1 == T) {
+                    hT[(size_t)b * kLstmH + u] = s.h;
+                    cT[(size_t)b * kLstmH + u] = s.c;
+                }
+                hk[u] = keep * s.h;
+                ck[u] = keep * s.c;
+            }
+        }
+    }
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_lstm_seq_bwd_f32_cpu(const float* dh, const float* dhT, const float* dcT, const float* record,
+                                                          const float* w_hh, const float* done, float* dgx, float* dh0, float* dc0,
+                                                          int T, int B, int H) {
+    const char* fn = "mi355ppo_lstm_seq_bwd_f32_cpu";
+    MI355_REQUIRE(dh && record && w_hh && done && dgx, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(H == kLstmH, MI355PPO_EINVAL, "%s: H=%d (only %d)", fn, H, kLstmH);
+    MI355_REQUIRE(T > 0 && B > 0, MI355PPO_EINVAL, "%s: T=%d B=%d must be positive", fn, T, B);
+    const size_t TB = (size_t)T * B;
+    for (int b = 0; b < B; ++b) {
+        float dhk[kLstmH], dc[kLstmH], part[4][kLstmH], dg[kLstmG];
+        float keep_next = 0.0f;
+        for (int u = 0; u < kLstmH; ++u) {
+            dhk[u] = dhT ? dhT[(size_t)b * kLstmH + u] : 0.0f;
+            dc[u] = dcT ? dcT[(size_t)b * kLstmH + u] : 0.0f;
+        }
+        for (int t = T - 1; t >= 0; --t) {
+            const size_t row = (size_t)t * B + b;
+            const float keep = 1.0f - done[row];
+            for (int u = 0; u < kLstmH; ++u) {
+                const float carry = t == T - 1 ? dhk[u] : keep_next * lstm_fold4(part[0][u], part[1][u], part[2][u], part[3][u]);
+                const float* g = record + row * kLstmG + u;
+                const LstmCellGrad d = lstm_cell_bwd(g[0], g[kLstmH], g[2 * kLstmH], g[3 * kLstmH], record[TB * 4 * kLstmH + row * kLstmH + u],
+                                                     record[TB * 6 * kLstmH + row * kLstmH + u], dh[row * kLstmH + u] + carry, dc[u]);
+                dg[u] = d.dai;
+                dg[kLstmH + u] = d.daf;
+                dg[2 * kLstmH + u] = d.dag;
+                dg[3 * kLstmH + u] = d.dao;
+                dc[u] = keep * d.dck;
+            }
+            for (int j = 0; j < kLstmG; ++j) dgx[row * kLstmG + j] = dg[j];
+            for (int q = 0; q < 4; ++q)
+                for (int k = 0; k < kLstmH; ++k)
+                    part[q][k] = lstm_dot128(LstmColumn{w_hh + (size_t)q * kLstmH * kLstmH + k}, dg + q * kLstmH);
+            keep_next = keep;
+        }
+        for (int u = 0; u < kLstmH; ++u) {
+            if (dh0) dh0[(size_t)b * kLstmH + u] = keep_next * lstm_fold4(part[0][u], part[1][u], part[2][u], part[3][u]);
+            if (dc0) dc0[(size_t)b * kLstmH + u] = dc[u];
+        }
     }
     return MI355PPO_OK;
 }

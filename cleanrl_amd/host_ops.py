@@ -5,8 +5,8 @@ plumbing", and the world_size-2 ``gloo`` tests of the data-parallel logic).  It 
 CUDA device always runs the HIP kernels and raises if ``libmi355ppo.so`` is missing, and these functions
 refuse CUDA tensors.  The twins (csrc/host_twins.hip, declared in include/mi355ppo.h) are the device
 kernels' own row / element functions compiled for the host, so the CPU loop crosses the SAME C ABI seams
-as the GPU loop: GAE (ppo.py:218-231), the fused loss forward + backward (ppo.py:250-285 and its autograd)
-and, for tests, sampling and clip + Adam.  The learners whose loss has extra terms (LSTM state, RND's second value
+as the GPU loop: GAE (ppo.py:218-231), the fused loss forward + backward (ppo.py:250-285 and its autograd),
+the LSTM sequence scans of ppo_atari_lstm.py (opt-in: ``MI355PPO_LSTM=fused``) and, for tests, sampling and clip + Adam.  The learners whose loss has extra terms (LSTM state, RND's second value
 head and distillation loss) cross the same twin on their logits / value and add their terms outside.
 """
 from __future__ import annotations
@@ -208,3 +208,38 @@ def obs_u8_to_f32(src_u8, inds=None, scale_255=True):
     _lib.check(lib.mi355ppo_obs_u8_to_f32_cpu(_p(src), _p(idx), _p(out), rows, row_bytes, int(bool(scale_255))),
                "mi355ppo_obs_u8_to_f32_cpu")
     return out
+
+
+def _lstm_dims(gx, done):
+    T, B, G = gx.shape
+    assert G % 4 == 0 and tuple(done.shape) == (T, B), "gx (T,B,4H), done (T,B)"
+    return T, B, G // 4
+
+
+def lstm_seq_forward(gx, w_hh, h0, c0, done, record: bool = False):
+    """The done-masked LSTM scan (ppo_atari_lstm.py:140-158) through ``mi355ppo_lstm_seq_fwd_f32_cpu`` -> (h, hT, cT, record | None);
+    gx (T,B,4H), w_hh (4H,H), h0 / c0 (B,H), done (T,B).  Same arithmetic as the device scan (csrc/lstm_rows.h)."""
+    lib = _lib.load()
+    T, B, H = _lstm_dims(gx, done)
+    g, w, h0, c0, d = _f32(gx), _f32(w_hh), _f32(h0), _f32(c0), _f32(done)
+    h, hT, cT = torch.empty((T, B, H)), torch.empty((B, H)), torch.empty((B, H))
+    rec = torch.empty(7 * T * B * H) if record else None
+    _lib.check(lib.mi355ppo_lstm_seq_fwd_f32_cpu(_p(g), _p(w), _p(h0), _p(c0), _p(d), _p(h), _p(hT), _p(cT), _p(rec), T, B, H),
+               "mi355ppo_lstm_seq_fwd_f32_cpu")
+    return h, hT, cT, rec
+
+
+def lstm_seq_backward(dh, dhT, dcT, record, w_hh, done, want_dh0: bool = True, want_dc0: bool = True):
+    """Backward of ``lstm_seq_forward`` through ``mi355ppo_lstm_seq_bwd_f32_cpu`` -> (dgx (T,B,4H), dh0 | None, dc0 | None);
+    dhT / dcT may be None (= zeros)."""
+    lib = _lib.load()
+    T, B, H = dh.shape
+    d, w, g = _f32(done), _f32(w_hh), _f32(dh)
+    dhT = None if dhT is None else _f32(dhT)
+    dcT = None if dcT is None else _f32(dcT)
+    dgx = torch.empty((T, B, 4 * H))
+    dh0 = torch.empty((B, H)) if want_dh0 else None
+    dc0 = torch.empty((B, H)) if want_dc0 else None
+    _lib.check(lib.mi355ppo_lstm_seq_bwd_f32_cpu(_p(g), _p(dhT), _p(dcT), _p(record), _p(w), _p(d), _p(dgx), _p(dh0), _p(dc0), T, B, H),
+               "mi355ppo_lstm_seq_bwd_f32_cpu")
+    return dgx, dh0, dc0

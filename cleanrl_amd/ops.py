@@ -2,7 +2,9 @@
 
 Each function mirrors one seam of the reference's inline PPO code (cited per function) and takes
 CUDA (=HIP) ``torch`` tensors only: torch is plumbing here (device memory + the current stream), the
-computation is the HIP kernels.  Passing a CPU tensor raises; there is no CPU fallback in this module.
+computation is the HIP kernels.  Passing a CPU tensor raises; there is no CPU fallback in this module.  The one exception is
+``LSTMSeq`` / ``lstm_seq``, which take CPU tensors to the LSTM scans' host twins (cleanrl_amd/host_ops.py) on purpose: the
+agent's host path and the tests run the same arithmetic as the device scan.
 """
 from __future__ import annotations
 
@@ -16,7 +18,8 @@ from . import _lib
 __all__ = [
     "gae", "categorical_sample", "categorical_logprob_entropy", "normal_sample", "normal_logprob_entropy",
     "ppo_loss_categorical", "ppo_loss_normal", "obs_u8_to_f32", "obs_nchw_to_nhwc_u8", "clip_adam_", "PPOLossCategorical", "PPOLossNormal",
-    "CategoricalLogProbEntropy", "NormalLogProbEntropy", "LOSS_SCALAR_NAMES",
+    "CategoricalLogProbEntropy", "NormalLogProbEntropy", "LOSS_SCALAR_NAMES", "lstm_seq_forward", "lstm_seq_backward", "LSTMSeq",
+    "lstm_seq", "lstm_seq_dw_hh",
 ]
 
 LOSS_SCALAR_NAMES = ("loss", "pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac")
@@ -759,6 +762,118 @@ def mlp_ppo_fwd_bwd(b_obs, mb_inds, actor: MlpNetPtrs, critic: MlpNetPtrs, b_act
                 _ptr(adv_mean_den), actor.grads(), critic.grads(), _ptr(sc), int(rows_per_block), _ptr(ws), ws.numel(), _stream(dev))
     _lib.check(st, "mi355ppo_mlp_ppo_fwd_bwd_f32")
     return sc
+
+
+# ------------------------------------------------------------------------------------------- LSTM
+def _lstm_dims(gx, done):
+    if gx.dim() != 3 or gx.shape[2] % 4:
+        raise ValueError(f"gx: expected (T, B, 4H), got {tuple(gx.shape)}")
+    T, B, G = gx.shape
+    return T, B, G // 4
+
+
+def lstm_seq_forward(gx, w_hh, h0, c0, done, record: bool = False):
+    """The done-masked LSTM scan of ppo_atari_lstm.py:140-158 (``get_states``) in one launch: ``gx`` (T,B,4H) = x W_ih^T + b_ih +
+    b_hh, ``w_hh`` (4H,H), ``h0`` / ``c0`` (B,H), ``done`` (T,B); H = 128.  Returns ``(h (T,B,H), hT, cT, record | None)``; the
+    record (7 T B H floats, layout in include/mi355ppo.h) feeds ``lstm_seq_backward``."""
+    lib = _lib.load()
+    T, B, H = _lstm_dims(gx, done)
+    _chk(gx, torch.float32, "gx", (T, B, 4 * H))
+    _chk(w_hh, torch.float32, "w_hh", (4 * H, H))
+    _chk(h0, torch.float32, "h0", (B, H))
+    _chk(c0, torch.float32, "c0", (B, H))
+    _chk(done, torch.float32, "done", (T, B))
+    dev = gx.device
+    h = torch.empty((T, B, H), device=dev)
+    hT, cT = torch.empty((B, H), device=dev), torch.empty((B, H), device=dev)
+    rec = torch.empty(7 * T * B * H, device=dev) if record else None
+    with _on(dev):
+        st = lib.mi355ppo_lstm_seq_fwd_f32(_ptr(gx), _ptr(w_hh), _ptr(h0), _ptr(c0), _ptr(done), _ptr(h), _ptr(hT), _ptr(cT), _ptr(rec),
+                                           T, B, H, _stream(dev))
+    _lib.check(st, "mi355ppo_lstm_seq_fwd_f32")
+    return h, hT, cT, rec
+
+
+def lstm_seq_backward(dh, dhT, dcT, record, w_hh, done, want_dh0: bool = True, want_dc0: bool = True):
+    """Backward of ``lstm_seq_forward`` (BPTT with the state gradient masked by keep_t): ``dh`` (T,B,H) from the heads, ``dhT`` /
+    ``dcT`` (B,H) or None.  Returns ``(dgx (T,B,4H), dh0 | None, dc0 | None)``; dW_hh = dgx^T hk is the caller's GEMM."""
+    lib = _lib.load()
+    T, B, H = dh.shape
+    _chk(dh, torch.float32, "dh", (T, B, H))
+    if dhT is not None:
+        _chk(dhT, torch.float32, "dhT", (B, H))
+    if dcT is not None:
+        _chk(dcT, torch.float32, "dcT", (B, H))
+    _chk(record, torch.float32, "record", (7 * T * B * H,))
+    _chk(w_hh, torch.float32, "w_hh", (4 * H, H))
+    _chk(done, torch.float32, "done", (T, B))
+    dev = dh.device
+    dgx = torch.empty((T, B, 4 * H), device=dev)
+    dh0 = torch.empty((B, H), device=dev) if want_dh0 else None
+    dc0 = torch.empty((B, H), device=dev) if want_dc0 else None
+    with _on(dev):
+        st = lib.mi355ppo_lstm_seq_bwd_f32(_ptr(dh), _ptr(dhT), _ptr(dcT), _ptr(record), _ptr(w_hh), _ptr(done), _ptr(dgx), _ptr(dh0),
+                                           _ptr(dc0), T, B, H, _stream(dev))
+    _lib.check(st, "mi355ppo_lstm_seq_bwd_f32")
+    return dgx, dh0, dc0
+
+
+def lstm_seq_dw_hh(dgx, record):
+    """d W_hh = sum_t dgx[t]^T hk_t (hk: the record's plane 5), as the reference's per-step graphs accumulate it: one product of
+    B rows per step (one batched GEMM), then the sum over T -- not one GEMM over T*B rows, whose single accumulation chain is
+    several times less accurate at update sizes (T*B = 8,192: 1.5e-6 against float64 on the device, the loop's 2.5e-7)."""
+    T, B, G = dgx.shape
+    H = G // 4
+    hk = record[5 * T * B * H:6 * T * B * H].view(T, B, H)
+    return torch.bmm(dgx.transpose(1, 2), hk).sum(0)
+
+
+def _lstm_impl(t):
+    """The scans for ``t``'s device: the HIP kernels for CUDA tensors, the ``*_cpu`` twins (cleanrl_amd/host_ops.py) for CPU ones."""
+    if t.is_cuda:
+        return lstm_seq_forward, lstm_seq_backward
+    from . import host_ops
+
+    return host_ops.lstm_seq_forward, host_ops.lstm_seq_backward
+
+
+class LSTMSeq(torch.autograd.Function):
+    """Differentiable ``(gx, w_hh, h0, c0, done) -> (h, hT, cT)``: the scan forward records its activations, the backward scan
+    returns d gx and d (h0, c0), and d w_hh is one GEMM over the record's hk plane.  The HIP kernels run for CUDA tensors, the
+    host twins for CPU ones (same arithmetic), so the plumbing is testable without a GPU.  ``lstm_seq`` picks the record-free
+    forward when no gradient is wanted."""
+
+    @staticmethod
+    def forward(ctx, gx, w_hh, h0, c0, done):
+        fwd, _ = _lstm_impl(gx)
+        w = w_hh.detach().contiguous()
+        d = done.detach().to(torch.float32).contiguous()
+        h, hT, cT, rec = fwd(gx.detach().contiguous(), w, h0.detach().contiguous(), c0.detach().contiguous(), d, record=True)
+        ctx.save_for_backward(rec, w, d)
+        return h, hT, cT
+
+    @staticmethod
+    def backward(ctx, dh, dhT, dcT):
+        rec, w, d = ctx.saved_tensors
+        _, bwd = _lstm_impl(w)
+        T, B = d.shape
+        H = w.shape[1]
+        dh = torch.zeros((T, B, H), device=w.device) if dh is None else dh.contiguous()
+        dhT = None if dhT is None else dhT.contiguous()
+        dcT = None if dcT is None else dcT.contiguous()
+        dgx, dh0, dc0 = bwd(dh, dhT, dcT, rec, w, d, want_dh0=ctx.needs_input_grad[2], want_dc0=ctx.needs_input_grad[3])
+        dw = lstm_seq_dw_hh(dgx, rec) if ctx.needs_input_grad[1] else None
+        return dgx, dw, dh0, dc0, None
+
+
+def lstm_seq(gx, w_hh, h0, c0, done):
+    """``LSTMSeq.apply`` when a gradient is wanted, else the inference scan without a record (the rollout step, the bootstrap)."""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (gx, w_hh, h0, c0)):
+        return LSTMSeq.apply(gx, w_hh, h0, c0, done)
+    fwd, _ = _lstm_impl(gx)
+    h, hT, cT, _ = fwd(gx.contiguous(), w_hh.detach().contiguous(), h0.contiguous(), c0.contiguous(),
+                       done.to(torch.float32).contiguous())
+    return h, hT, cT
 
 
 def synth_continuous_step(state, reset_state, At, Bm, w, noise, k: int, steps, horizon: float, action, obs_out, reward, done, k_base=None):

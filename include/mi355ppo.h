@@ -32,13 +32,14 @@
 extern "C" {
 #endif
 
-#define MI355PPO_VERSION 210 /* major*100 + minor*10 + patch.  The minor moves whenever an exported signature changes or an entry
+#define MI355PPO_VERSION 220 /* major*100 + minor*10 + patch.  The minor moves whenever an exported signature changes or an entry
                                   point is added (1.1: adv_mean_den / conv1_variant arguments of round 2; 1.2, 1.3: round 3;
                                   1.4: the *_cpu host-pointer twins; 1.5: mi355ppo_init; 1.6: round 4 -- the fused MLP family K7,
                                   mi355ppo_clip_adam_sched_f32; 1.7: mi355ppo_fc_heads_act_categorical_f32, mi355ppo_nature_packs_f32,
                                   mi355ppo_synth_atari_step_hwc_ctr_u8; 1.8: round 5 -- the *_f16x2 / *_amax entry points and mi355ppo_absmax_f32;
                                   1.9: round 6 -- the kernel queries mi355ppo_fc_packed_kernel_f16x2, mi355ppo_fc_wgrad_kernel_f16x2, mi355ppo_cnn_conv_wgrad_kernel_f16x2;
-                                  heads of up to 18 actions, a 4-byte-aligned critic row; 2.0: the peer-memory gradient exchange mi355ppo_dp_*; 2.1: the fused MLP family takes obs_dim <= 512, n_out <= 20);
+                                  heads of up to 18 actions, a 4-byte-aligned critic row; 2.0: the peer-memory gradient exchange mi355ppo_dp_*; 2.1: the fused MLP family takes obs_dim <= 512, n_out <= 20;
+                                  2.2: the done-masked LSTM sequence scans mi355ppo_lstm_seq_fwd_f32 / _bwd_f32 and their *_cpu twins);
                                   a binding must check major AND minor (cleanrl_amd/_lib.py does) */
 
 #if defined(__GNUC__)
@@ -363,6 +364,36 @@ MI355PPO_API int mi355ppo_mlp_ppo_normal_fwd_bwd_f32(
     size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * LSTM  The recurrence of ppo_atari_lstm.py's get_states (cleanrl/ppo_atari_lstm.py:140-158): one layer of nn.LSTM(512, 128)
+ * run over T time-major steps of B envs, the state multiplied by keep_t = 1 - done[t] before step t (a multiply: a non-binary
+ * done scales the state as the reference's does).  Replaces T x (two masking multiplies + a length-1 nn.LSTM call) and, in the
+ * update, the backward through T per-step autograd graphs.  Gate order i, f, g, o; H must be 128.  Math: csrc/lstm_rows.h.
+ *   gx        : (T,B,4H) f32  x W_ih^T + b_ih + b_hh, formed by the caller                      [in]
+ *   w_hh      : (4H,H)   f32  nn.LSTM's weight_hh_l0 (row-major, any 4-byte offset)             [in]
+ *   h0, c0    : (B,H)    f32  state before step 0                                              [in]
+ *   done      : (T,B)    f32                                                                   [in]
+ *   h         : (T,B,H)  f32  h_t                                                              [out]
+ *   hT, cT    : (B,H)    f32  h_{T-1}, c_{T-1} (not masked: the state the reference returns)   [out]
+ *   record    : 7 T B H  f32 activation record for the backward, or NULL (inference: the rollout step and the bootstrap
+ *               value).  Planes: post-activation gates (T,B,4,H) | c_t (T,B,H) | hk_t = keep_t h_{t-1} (T,B,H) |
+ *               ck_t = keep_t c_{t-1} (T,B,H)                                                  [out]
+ * One workgroup walks one env's chain in a fixed order: deterministic, and env b's results do not depend on B or on b.
+ */
+MI355PPO_API int mi355ppo_lstm_seq_fwd_f32(const float* gx, const float* w_hh, const float* h0, const float* c0, const float* done,
+                                           float* h, float* hT, float* cT, float* record, int T, int B, int H, void* stream);
+/* Backward through the scan (BPTT):
+ *   dh        : (T,B,H)  d loss / d h_t from the heads                                         [in]
+ *   dhT, dcT  : (B,H)    d loss / d (hT, cT), or NULL (= zeros)                                [in]
+ *   record    : as written by the forward of the same inputs                                   [in]
+ *   dgx       : (T,B,4H) d loss / d pre-activation gates (= d gx)                               [out]
+ *   dh0, dc0  : (B,H)    d loss / d (h0, c0), or NULL                                          [out]
+ * The dense products stay with the caller: dW_hh = dgx^T hk (the record's hk plane), dW_ih = dgx^T x, dx = dgx W_ih,
+ * d b_ih = d b_hh = column sums of dgx. */
+MI355PPO_API int mi355ppo_lstm_seq_bwd_f32(const float* dh, const float* dhT, const float* dcT, const float* record,
+                                           const float* w_hh, const float* done, float* dgx, float* dh0, float* dc0, int T, int B,
+                                           int H, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Host-pointer twins (csrc/host_twins.hip) of the PPO-path entry points above: the same arguments minus `stream` and
  * `workspace`, every pointer a HOST pointer, the call returns when the result is written.  Same math by construction: the
  * row / element functions (GAE step, Categorical row, loss row terms, advantage statistics fold, Adam element, Philox stream)
@@ -410,6 +441,12 @@ MI355PPO_API int mi355ppo_clip_adam_f32_cpu(float* params, float* grads, float* 
                                             double eps, int64_t step, float* total_norm_out);
 MI355PPO_API int mi355ppo_obs_u8_to_f32_cpu(const uint8_t* src_u8, const int64_t* inds, float* dst_f32, int64_t rows,
                                             int64_t row_bytes, int scale_255);
+MI355PPO_API int mi355ppo_lstm_seq_fwd_f32_cpu(const float* gx, const float* w_hh, const float* h0, const float* c0,
+                                               const float* done, float* h, float* hT, float* cT, float* record, int T, int B,
+                                               int H);
+MI355PPO_API int mi355ppo_lstm_seq_bwd_f32_cpu(const float* dh, const float* dhT, const float* dcT, const float* record,
+                                               const float* w_hh, const float* done, float* dgx, float* dh0, float* dc0, int T,
+                                               int B, int H);
 
 /* ---------------------------------------------------------------------------------------------
  * FC   Linear(3136, 512) + ReLU of the NatureCNN (cleanrl/ppo_atari_multigpu.py:144-145) on the bf16 matrix pipe
