@@ -131,6 +131,11 @@ SIGNATURES = {
     # the done-masked LSTM sequence scans (csrc/lstm.hip)
     "mi355ppo_lstm_seq_fwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "mi355ppo_lstm_seq_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    # the TrXL episodic-memory attention (csrc/trxl_attn.hip)
+    "mi355ppo_trxl_attn_fwd_f32": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P,
+                                           c_int, c_int, c_int, c_int, _P]),
+    "mi355ppo_trxl_attn_bwd_f32": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P,
+                                           _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     # host-pointer twins (csrc/host_twins.hip): the device signatures minus stream / workspace
     "mi355ppo_gae_f32_cpu": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_double, c_double]),
     "mi355ppo_categorical_sample_f32_cpu": (c_int, [_P, _P, c_uint64, c_uint64, _P, _P, _P, _P, c_int, c_int]),
@@ -148,9 +153,13 @@ SIGNATURES = {
     "mi355ppo_obs_u8_to_f32_cpu": (c_int, [_P, _P, _P, c_int64, c_int64, c_int]),
     "mi355ppo_lstm_seq_fwd_f32_cpu": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int]),
     "mi355ppo_lstm_seq_bwd_f32_cpu": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int]),
+    "mi355ppo_trxl_attn_fwd_f32_cpu": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P,
+                                               c_int, c_int, c_int, c_int]),
+    "mi355ppo_trxl_attn_bwd_f32_cpu": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P,
+                                               _P, _P, _P, _P, c_int, c_int, c_int, c_int]),
 }
 
-ABI_VERSION = 220       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)
+ABI_VERSION = 230       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)
 
 _lib = None
 

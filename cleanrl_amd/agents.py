@@ -768,3 +768,263 @@ class MAAtariAgent(_DiscreteMixin, nn.Module):
         logits, value = self.heads(self._normalise(x))
         action, lp, ent = self._dist(logits, action)
         return action, lp, ent, value
+
+
+# ------------------------------------------------------------------------------------------- TrXL (ppo_trxl.py)
+TRXL_BACKENDS = ("torch", "fused")
+
+
+def trxl_backend_from_env() -> str:
+    """``MI355PPO_TRXL``: ``torch`` (default: the reference's window gather and attention ops) or ``fused`` (the episodic-memory
+    attention of csrc/trxl_attn.hip, ``ops.TrXLMemoryAttention``)."""
+    v = os.environ.get("MI355PPO_TRXL", "torch")
+    if v not in TRXL_BACKENDS:
+        raise ValueError(f"MI355PPO_TRXL={v!r}: expected torch or fused")
+    return v
+
+
+def _trxl_init(layer, std=np.sqrt(2)):
+    """ppo_trxl.py's ``layer_init``: orthogonal weight only -- the bias keeps nn.Linear's default init."""
+    torch.nn.init.orthogonal_(layer.weight, std)
+    return layer
+
+
+def batched_index_select(input, dim, index):
+    """ppo_trxl.py's gather of per-sample rows along ``dim``."""
+    for ii in range(1, len(input.shape)):
+        if ii != dim:
+            index = index.unsqueeze(ii)
+    expanse = list(input.shape)
+    expanse[0] = -1
+    expanse[dim] = -1
+    index = index.expand(expanse)
+    return torch.gather(input, dim, index)
+
+
+class MemoryWindow:
+    """A memory window given as indices into an episode pool instead of a gathered tensor: sample b's rows are
+    ``pool[ep[b], rows[b, :]]``.  ``pool`` is (E, T_ep, layers, D); the ``fused`` backend streams the rows from it, the ``torch``
+    backend gathers them as the reference does (``batched_index_select(pool[ep], 1, rows)``)."""
+
+    def __init__(self, pool, ep, rows):
+        self.pool, self.ep, self.rows = pool, ep, rows
+
+    def gather(self):
+        return batched_index_select(self.pool[self.ep], 1, self.rows)
+
+
+class TrXLPositionalEncoding(nn.Module):
+    """ppo_trxl.py ``PositionalEncoding``: sinusoids of reversed positions, (seq_len, dim)."""
+
+    def __init__(self, dim, min_timescale=2.0, max_timescale=1e4):
+        super().__init__()
+        freqs = torch.arange(0, dim, min_timescale)
+        inv_freqs = max_timescale ** (-freqs / dim)
+        self.register_buffer("inv_freqs", inv_freqs)
+
+    def forward(self, seq_len):
+        seq = torch.arange(seq_len - 1, -1, -1.0, device=self.inv_freqs.device)
+        sinusoidal_inp = seq.reshape(-1, 1) * self.inv_freqs.reshape(1, -1)
+        return torch.cat((sinusoidal_inp.sin(), sinusoidal_inp.cos()), dim=-1)
+
+
+class TrXLMultiHeadAttention(nn.Module):
+    """ppo_trxl.py ``MultiHeadAttention`` (no dropout): per-head (d, d) values / keys / queries, ``fc_out``."""
+
+    def __init__(self, embed_dim, num_heads):
+        super().__init__()
+        self.embed_dim = embed_dim
+        self.num_heads = num_heads
+        self.head_size = embed_dim // num_heads
+        assert self.head_size * num_heads == embed_dim, "Embedding dimension needs to be divisible by the number of heads"
+        self.values = nn.Linear(self.head_size, self.head_size, bias=False)
+        self.keys = nn.Linear(self.head_size, self.head_size, bias=False)
+        self.queries = nn.Linear(self.head_size, self.head_size, bias=False)
+        self.fc_out = nn.Linear(self.num_heads * self.head_size, embed_dim)
+
+    def forward(self, values, keys, query, mask):
+        N = query.shape[0]
+        value_len, key_len, query_len = values.shape[1], keys.shape[1], query.shape[1]
+        values = self.values(values.reshape(N, value_len, self.num_heads, self.head_size))
+        keys = self.keys(keys.reshape(N, key_len, self.num_heads, self.head_size))
+        queries = self.queries(query.reshape(N, query_len, self.num_heads, self.head_size))
+        energy = torch.einsum("nqhd,nkhd->nhqk", [queries, keys])
+        if mask is not None:
+            energy = energy.masked_fill(mask.unsqueeze(1).unsqueeze(1) == 0, float("-1e20"))
+        attention = torch.softmax(energy / (self.embed_dim ** (1 / 2)), dim=3)
+        out = torch.einsum("nhql,nlhd->nqhd", [attention, values]).reshape(N, query_len, self.num_heads * self.head_size)
+        return self.fc_out(out), attention
+
+
+class TrXLTransformerLayer(nn.Module):
+    """ppo_trxl.py ``TransformerLayer``: pre-LN attention over the memory window (K = V), skip, pre-LN ReLU projection, skip."""
+
+    def __init__(self, dim, num_heads):
+        super().__init__()
+        self.attention = TrXLMultiHeadAttention(dim, num_heads)
+        self.layer_norm_q = nn.LayerNorm(dim)
+        self.norm_kv = nn.LayerNorm(dim)
+        self.layer_norm_attn = nn.LayerNorm(dim)
+        self.fc_projection = nn.Sequential(nn.Linear(dim, dim), nn.ReLU())
+
+    def forward(self, value, key, query, mask):
+        query_ = self.layer_norm_q(query)
+        value = self.norm_kv(value)
+        key = value
+        attention, attention_weights = self.attention(value, key, query_, mask)
+        x = attention + query
+        x_ = self.layer_norm_attn(x)
+        forward = self.fc_projection(x_)
+        return forward + x, attention_weights
+
+    def forward_fused(self, x, window, layer, pos, mask, pe):
+        """The same layer with the window path (gather, pe, norm_kv, keys, softmax, weighted sum) in one kernel:
+        q~ = queries(LN_q(x)) @ keys.weight, u = sum_j att_j norm_kv(row_j), then ``values`` and ``fc_out`` on u."""
+        att = self.attention
+        B = x.shape[0]
+        q = att.queries(self.layer_norm_q(x).reshape(B, att.num_heads, att.head_size))
+        u = ops.trxl_memory_attention(q @ att.keys.weight, self.norm_kv.weight, self.norm_kv.bias, window.pool, layer, window.ep,
+                                      window.rows, pos, mask, pe)
+        x = att.fc_out(att.values(u).reshape(B, att.embed_dim)) + x
+        return self.fc_projection(self.layer_norm_attn(x)) + x
+
+
+class TrXLTransformer(nn.Module):
+    """ppo_trxl.py ``Transformer``: positional encoding (``absolute``, ``learned`` or none) added to the memory window, then the
+    layers; returns the output and the per-layer inputs (detached: the next episodic-memory row)."""
+
+    def __init__(self, num_layers, dim, num_heads, max_episode_steps, positional_encoding, backend="torch"):
+        super().__init__()
+        self.max_episode_steps = max_episode_steps
+        self.positional_encoding = positional_encoding
+        if positional_encoding == "absolute":
+            self.pos_embedding = TrXLPositionalEncoding(dim)
+        elif positional_encoding == "learned":
+            self.pos_embedding = nn.Parameter(torch.randn(max_episode_steps, dim))
+        self.transformer_layers = nn.ModuleList([TrXLTransformerLayer(dim, num_heads) for _ in range(num_layers)])
+        self.backend = backend
+
+    def forward(self, x, memories, mask, memory_indices):
+        if self.backend == "fused":
+            return self._forward_fused(x, memories, mask, memory_indices)
+        if isinstance(memories, MemoryWindow):
+            memories = memories.gather()
+        if self.positional_encoding == "absolute":
+            pos_embedding = self.pos_embedding(self.max_episode_steps)[memory_indices]
+            memories = memories + pos_embedding.unsqueeze(2)
+        elif self.positional_encoding == "learned":
+            memories = memories + self.pos_embedding[memory_indices].unsqueeze(2)
+        out_memories = []
+        for i, layer in enumerate(self.transformer_layers):
+            out_memories.append(x.detach())
+            x, attention_weights = layer(memories[:, :, i], memories[:, :, i], x.unsqueeze(1), mask)
+            x = x.squeeze()
+            if len(x.shape) == 1:
+                x = x.unsqueeze(0)
+        return x, torch.stack(out_memories, dim=1)
+
+    def _forward_fused(self, x, memories, mask, memory_indices):
+        if not isinstance(memories, MemoryWindow):              # an already gathered (B, L, layers, D) window
+            B, L = memories.shape[:2]
+            memories = MemoryWindow(memories, torch.arange(B, device=memories.device),
+                                    torch.arange(L, device=memories.device).expand(B, L))
+        pe = self.pos_embedding(self.max_episode_steps) if self.positional_encoding == "absolute" else None
+        out_memories = []
+        for i, layer in enumerate(self.transformer_layers):
+            out_memories.append(x.detach())
+            x = layer.forward_fused(x, memories, i, memory_indices, mask, pe)
+        return x, torch.stack(out_memories, dim=1)
+
+
+class TrXLAgent(nn.Module):
+    """ppo_trxl.py ``Agent``: encoder (Linear for vector observations, NatureCNN on (84, 84, 3) images / 255), Transformer-XL over
+    the episodic memory window, ``hidden_post_trxl``, one Categorical branch per MultiDiscrete component, the critic, and the
+    optional transposed-CNN observation reconstruction.  Same modules, parameter order and initialisation as the reference, so a
+    seeded construction gives the reference's weights.
+
+    ``trxl_backend`` (from ``MI355PPO_TRXL`` at construction): ``torch`` runs the reference's ops; ``fused`` routes each layer's
+    window path through ``ops.TrXLMemoryAttention`` (HIP kernels on the GPU, their host twins on CPU).  ``fused`` refuses a
+    ``learned`` positional encoding, whose gradient would be a scatter-add into the table.  The ``memory`` argument of the methods
+    is a gathered window (B, L, layers, D), as in the reference, or a ``MemoryWindow`` into an episode pool."""
+
+    def __init__(self, args, observation_space, action_space_shape, max_episode_steps):
+        super().__init__()
+        self.obs_shape = observation_space.shape
+        self.max_episode_steps = max_episode_steps
+        self.trxl_backend = trxl_backend_from_env()
+        if self.trxl_backend == "fused" and args.trxl_positional_encoding == "learned":
+            raise ValueError("MI355PPO_TRXL=fused does not support --trxl-positional-encoding learned (use torch)")
+
+        if len(self.obs_shape) > 1:
+            self.encoder = nn.Sequential(
+                _trxl_init(nn.Conv2d(3, 32, 8, stride=4)),
+                nn.ReLU(),
+                _trxl_init(nn.Conv2d(32, 64, 4, stride=2)),
+                nn.ReLU(),
+                _trxl_init(nn.Conv2d(64, 64, 3, stride=1)),
+                nn.ReLU(),
+                nn.Flatten(),
+                _trxl_init(nn.Linear(64 * 7 * 7, args.trxl_dim)),
+                nn.ReLU(),
+            )
+        else:
+            self.encoder = _trxl_init(nn.Linear(observation_space.shape[0], args.trxl_dim))
+
+        self.transformer = TrXLTransformer(args.trxl_num_layers, args.trxl_dim, args.trxl_num_heads, self.max_episode_steps,
+                                           args.trxl_positional_encoding, backend=self.trxl_backend)
+        self.hidden_post_trxl = nn.Sequential(_trxl_init(nn.Linear(args.trxl_dim, args.trxl_dim)), nn.ReLU())
+        self.actor_branches = nn.ModuleList(
+            [_trxl_init(nn.Linear(args.trxl_dim, out_features=num_actions), np.sqrt(0.01)) for num_actions in action_space_shape])
+        self.critic = _trxl_init(nn.Linear(args.trxl_dim, 1), 1)
+
+        if args.reconstruction_coef > 0.0:
+            self.transposed_cnn = nn.Sequential(
+                _trxl_init(nn.Linear(args.trxl_dim, 64 * 7 * 7)),
+                nn.ReLU(),
+                nn.Unflatten(1, (64, 7, 7)),
+                _trxl_init(nn.ConvTranspose2d(64, 64, 3, stride=1)),
+                nn.ReLU(),
+                _trxl_init(nn.ConvTranspose2d(64, 32, 4, stride=2)),
+                nn.ReLU(),
+                _trxl_init(nn.ConvTranspose2d(32, 3, 8, stride=4)),
+                nn.Sigmoid(),
+            )
+
+    @property
+    def trxl_backend(self):
+        return self._trxl_backend
+
+    @trxl_backend.setter
+    def trxl_backend(self, v):
+        if v not in TRXL_BACKENDS:
+            raise ValueError(f"trxl_backend={v!r}: expected torch or fused")
+        self._trxl_backend = v
+        if "transformer" in self._modules:
+            self.transformer.backend = v
+
+    def _encode(self, x):
+        if len(self.obs_shape) > 1:
+            return self.encoder(x.permute((0, 3, 1, 2)) / 255.0)
+        return self.encoder(x)
+
+    def get_value(self, x, memory, memory_mask, memory_indices):
+        x, _ = self.transformer(self._encode(x), memory, memory_mask, memory_indices)
+        x = self.hidden_post_trxl(x)
+        return self.critic(x).flatten()
+
+    def get_action_and_value(self, x, memory, memory_mask, memory_indices, action=None):
+        x, memory = self.transformer(self._encode(x), memory, memory_mask, memory_indices)
+        x = self.hidden_post_trxl(x)
+        self.x = x
+        probs = [Categorical(logits=branch(x)) for branch in self.actor_branches]
+        if action is None:
+            action = torch.stack([dist.sample() for dist in probs], dim=1)
+        log_probs = []
+        for i, dist in enumerate(probs):
+            log_probs.append(dist.log_prob(action[:, i]))
+        entropies = torch.stack([dist.entropy() for dist in probs], dim=1).sum(1).reshape(-1)
+        return action, torch.stack(log_probs, dim=1), entropies, self.critic(x).flatten(), memory
+
+    def reconstruct_observation(self):
+        x = self.transposed_cnn(self.x)
+        return x.permute((0, 2, 3, 1))

@@ -9,13 +9,14 @@
 //
 // Same math by construction: the row / element functions (gae_step, categorical_row, ppo_row_terms, mean_den_from_sums,
 // adam_elem, the Philox stream, the LSTM cell and its 128-column products) are the device kernels' own, compiled for the host
-// from the same headers (ppo_rows.h, catrow.h, lstm_rows.h, common.h), without FMA contraction.  Differences to the device results can come only from libm vs the device
+// from the same headers (ppo_rows.h, catrow.h, lstm_rows.h, trxl_rows.h, common.h), without FMA contraction.  Differences to the device results can come only from libm vs the device
 // math library (expf / logf / sincosf: a few ulp) and from the order of the f64 reductions (row order here, fixed tree there).
 // Serial, single-threaded: sizes of config A are a few hundred rows.
 #include "common.h"
 #include "catrow.h"
 #include "ppo_rows.h"
 #include "lstm_rows.h"
+#include "trxl_rows.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -520,6 +521,208 @@ extern "C" MI355PPO_API int mi355ppo_lstm_seq_bwd_f32_cpu(const float* dh, const
             if (dh0) dh0[(size_t)b * kLstmH + u] = keep_next * lstm_fold4(part[0][u], part[1][u], part[2][u], part[3][u]);
             if (dc0) dc0[(size_t)b * kLstmH + u] = dc[u];
         }
+    }
+    return MI355PPO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ TrXL
+// The episodic-memory attention core (trxl_attn.hip): the 64 lanes and 4 waves of the device layout emulated in order, so the
+// sums are folded exactly as the kernels fold them (trxl_rows.h).  Out-of-range indices are refused (the device clamps them and
+// raises its error word).
+namespace {
+
+struct TwinTrxl {
+    const float* mem;
+    const int64_t* ep;
+    const int64_t* rows;
+    const int64_t* pos;
+    const uint8_t* mask;
+    const float* pe;
+    const float* gamma;
+    const float* beta;
+    const float* q;
+    int E, T, layers, layer, P, B, L, D, H;
+};
+
+constexpr int kLanes = MI355_WAVE;
+
+// v[i] += v[i ^ off] for off = n/2 .. 1 within groups of n lanes: __shfl_xor's butterfly.
+void twin_butterfly(float (&v)[kLanes], int n) {
+    for (int off = n >> 1; off >= 1; off >>= 1) {
+        float t[kLanes];
+        for (int i = 0; i < kLanes; ++i) t[i] = v[i] + v[i ^ off];
+        for (int i = 0; i < kLanes; ++i) v[i] = t[i];
+    }
+}
+
+float twin_wave_sum(const float* x, int C) {
+    float v[kLanes];
+    for (int l = 0; l < kLanes; ++l) {
+        float s = 0.0f;
+        for (int c = 0; c < C; ++c) s = s + x[l * C + c];
+        v[l] = s;
+    }
+    twin_butterfly(v, kLanes);
+    return v[0];
+}
+
+// Per-head dots a . b over the row: out[h] for every head.
+void twin_head_dots(const float* a, const float* b, int C, int H, float* out) {
+    float v[kLanes];
+    for (int l = 0; l < kLanes; ++l) {
+        float s = 0.0f;
+        for (int c = 0; c < C; ++c) s = s + a[l * C + c] * b[l * C + c];
+        v[l] = s;
+    }
+    const int G = kLanes / H;
+    twin_butterfly(v, G);
+    for (int h = 0; h < H; ++h) out[h] = v[h * G];
+}
+
+// Window row j of sample b -> xhat, y.
+void twin_norm_row(const TwinTrxl& a, int b, int j, float* xh, float* y) {
+    const int C = a.D / kLanes;
+    const int64_t r = a.rows[(size_t)b * a.L + j];
+    const float* src = a.mem + (((size_t)a.ep[b] * a.T + (size_t)r) * a.layers + a.layer) * a.D;
+    float x[kTrxlMaxD];
+    for (int k = 0; k < a.D; ++k) x[k] = a.pe ? src[k] + a.pe[(size_t)a.pos[(size_t)b * a.L + j] * a.D + k] : src[k];
+    const float mean = twin_wave_sum(x, C) / (float)a.D;
+    for (int k = 0; k < a.D; ++k) xh[k] = x[k] - mean;
+    float sq[kTrxlMaxD];
+    for (int k = 0; k < a.D; ++k) sq[k] = xh[k] * xh[k];
+    const float rstd = trxl_rstd(twin_wave_sum(sq, C) / (float)a.D);
+    for (int k = 0; k < a.D; ++k) {
+        xh[k] = xh[k] * rstd;
+        y[k] = xh[k] * a.gamma[k] + a.beta[k];
+    }
+}
+
+int twin_trxl_check(const char* fn, const TwinTrxl& a) {
+    MI355_REQUIRE(a.mem && a.ep && a.rows && a.mask && a.gamma && a.beta && a.q, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(trxl_shape_ok(a.D, a.H, a.L), MI355PPO_EINVAL,
+                  "%s: D=%d H=%d L=%d (need D %% 64 == 0, D <= 512, H dividing 64, 1 <= L <= 1024)", fn, a.D, a.H, a.L);
+    MI355_REQUIRE(a.B > 0 && a.E > 0 && a.T > 0 && a.layers > 0 && a.layer >= 0 && a.layer < a.layers, MI355PPO_EINVAL,
+                  "%s: B=%d E=%d T_ep=%d layers=%d layer=%d", fn, a.B, a.E, a.T, a.layers, a.layer);
+    MI355_REQUIRE(!a.pe || (a.pos && a.P > 0), MI355PPO_EINVAL, "%s: pe needs pos and P > 0 (P=%d)", fn, a.P);
+    for (int b = 0; b < a.B; ++b) {
+        MI355_REQUIRE(a.ep[b] >= 0 && a.ep[b] < a.E, MI355PPO_EINVAL, "%s: ep[%d]=%lld outside [0, %d)", fn, b, (long long)a.ep[b], a.E);
+        for (int j = 0; j < a.L; ++j) {
+            const size_t i = (size_t)b * a.L + j;
+            MI355_REQUIRE(a.rows[i] >= 0 && a.rows[i] < a.T, MI355PPO_EINVAL, "%s: rows[%d, %d]=%lld outside [0, %d)", fn, b, j,
+                          (long long)a.rows[i], a.T);
+            MI355_REQUIRE(!a.pe || (a.pos[i] >= 0 && a.pos[i] < a.P), MI355PPO_EINVAL, "%s: pos[%d, %d]=%lld outside [0, %d)", fn, b,
+                          j, (long long)a.pos[i], a.P);
+        }
+    }
+    return MI355PPO_OK;
+}
+
+}  // namespace
+
+extern "C" MI355PPO_API int mi355ppo_trxl_attn_fwd_f32_cpu(const float* memory, int E, int T_ep, int layers, int layer, const int64_t* ep,
+                                                           const int64_t* rows, const int64_t* pos, const uint8_t* mask, const float* pe,
+                                                           int P, const float* gamma, const float* beta, const float* q, float* u,
+                                                           float* stats, int B, int L, int D, int H) {
+    const char* fn = "mi355ppo_trxl_attn_fwd_f32_cpu";
+    const TwinTrxl a{memory, ep, rows, pos, mask, pe, gamma, beta, q, E, T_ep, layers, layer, pe ? P : 0, B, L, D, H};
+    if (int r = twin_trxl_check(fn, a)) return r;
+    MI355_REQUIRE(u && stats, MI355PPO_EINVAL, "%s: null pointer", fn);
+    const float sqrt_d = trxl_sqrt_d(D);
+    const int d = D / H;
+    float xh[kTrxlMaxD], y[kTrxlMaxD], acc[kTrxlWaves][kTrxlMaxD], e[64];
+    TrxlOnline st[kTrxlWaves][64];
+    for (int b = 0; b < B; ++b) {
+        const float* qb = q + (size_t)b * D;
+        for (int w = 0; w < kTrxlWaves; ++w) {
+            for (int h = 0; h < H; ++h) st[w][h] = TrxlOnline{-INFINITY, 0.0f};
+            for (int k = 0; k < D; ++k) acc[w][k] = 0.0f;
+            for (int j = w; j < L; j += kTrxlWaves) {
+                twin_norm_row(a, b, j, xh, y);
+                twin_head_dots(qb, y, D / kLanes, H, e);
+                const bool keep = mask[(size_t)b * L + j] != 0;
+                for (int h = 0; h < H; ++h) {
+                    float p;
+                    const float f = trxl_online_step(st[w][h], trxl_score(keep, e[h], sqrt_d), p);
+                    for (int k = h * d; k < (h + 1) * d; ++k) acc[w][k] = acc[w][k] * f + p * y[k];
+                }
+            }
+        }
+        for (int h = 0; h < H; ++h) {
+            float m[kTrxlWaves], f[kTrxlWaves], l[kTrxlWaves], v[kTrxlWaves];
+            for (int w = 0; w < kTrxlWaves; ++w) m[w] = st[w][h].m;
+            const float M = trxl_merge_max(m);
+            for (int w = 0; w < kTrxlWaves; ++w) {
+                f[w] = expf(m[w] - M);
+                l[w] = st[w][h].l;
+            }
+            const float lsum = trxl_merge_sum(l, f);
+            for (int k = h * d; k < (h + 1) * d; ++k) {
+                for (int w = 0; w < kTrxlWaves; ++w) v[w] = acc[w][k];
+                u[(size_t)b * D + k] = trxl_merge_sum(v, f) / lsum;
+            }
+            stats[((size_t)b * H + h) * 2] = M;
+            stats[((size_t)b * H + h) * 2 + 1] = lsum;
+        }
+    }
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_trxl_attn_bwd_f32_cpu(const float* memory, int E, int T_ep, int layers, int layer, const int64_t* ep,
+                                                           const int64_t* rows, const int64_t* pos, const uint8_t* mask, const float* pe,
+                                                           int P, const float* gamma, const float* beta, const float* q, const float* u,
+                                                           const float* stats, const float* du, float* dq, float* dln_rows,
+                                                           float* dgamma, float* dbeta, int B, int L, int D, int H) {
+    const char* fn = "mi355ppo_trxl_attn_bwd_f32_cpu";
+    const TwinTrxl a{memory, ep, rows, pos, mask, pe, gamma, beta, q, E, T_ep, layers, layer, pe ? P : 0, B, L, D, H};
+    if (int r = twin_trxl_check(fn, a)) return r;
+    MI355_REQUIRE(u && stats && du && dq && dln_rows && dgamma && dbeta, MI355PPO_EINVAL, "%s: null pointer", fn);
+    const float sqrt_d = trxl_sqrt_d(D);
+    const int d = D / H, C = D / kLanes;
+    const size_t BD = (size_t)B * D;
+    float xh[kTrxlMaxD], y[kTrxlMaxD], e[64], dyu[64], duu[64];
+    static thread_local float z[kTrxlWaves][kTrxlMaxD], dg[kTrxlWaves][kTrxlMaxD], db[kTrxlWaves][kTrxlMaxD];
+    for (int b = 0; b < B; ++b) {
+        const float *qb = q + (size_t)b * D, *dub = du + (size_t)b * D;
+        twin_head_dots(dub, u + (size_t)b * D, C, H, duu);
+        for (int w = 0; w < kTrxlWaves; ++w) {
+            for (int k = 0; k < D; ++k) z[w][k] = dg[w][k] = db[w][k] = 0.0f;
+            for (int j = w; j < L; j += kTrxlWaves) {
+                twin_norm_row(a, b, j, xh, y);
+                twin_head_dots(qb, y, C, H, e);
+                twin_head_dots(dub, y, C, H, dyu);
+                const bool keep = mask[(size_t)b * L + j] != 0;
+                for (int h = 0; h < H; ++h) {
+                    const float s = trxl_score(keep, e[h], sqrt_d);
+                    const float att = trxl_att(s, stats[((size_t)b * H + h) * 2], stats[((size_t)b * H + h) * 2 + 1]);
+                    const float ds = att * (dyu[h] - duu[h]);
+                    const float gs = keep ? ds / sqrt_d : 0.0f;
+                    for (int k = h * d; k < (h + 1) * d; ++k) {
+                        z[w][k] = z[w][k] + gs * y[k];
+                        const float dyk = gs * qb[k] + att * dub[k];
+                        dg[w][k] = dg[w][k] + dyk * xh[k];
+                        db[w][k] = db[w][k] + dyk;
+                    }
+                }
+            }
+        }
+        for (int k = 0; k < D; ++k) {
+            const size_t o = (size_t)b * D + k;
+            dq[o] = ((z[0][k] + z[1][k]) + z[2][k]) + z[3][k];
+            dln_rows[o] = ((dg[0][k] + dg[1][k]) + dg[2][k]) + dg[3][k];
+            dln_rows[BD + o] = ((db[0][k] + db[1][k]) + db[2][k]) + db[3][k];
+        }
+    }
+    for (int k = 0; k < D; ++k) {                            // trxl_ln_fold_kernel's order: wave w sums b = w, w + 4, ...
+        float sg[kTrxlWaves], sb[kTrxlWaves];
+        for (int w = 0; w < kTrxlWaves; ++w) {
+            sg[w] = sb[w] = 0.0f;
+            for (int b = w; b < B; b += kTrxlWaves) {
+                sg[w] = sg[w] + dln_rows[(size_t)b * D + k];
+                sb[w] = sb[w] + dln_rows[BD + (size_t)b * D + k];
+            }
+        }
+        dgamma[k] = ((sg[0] + sg[1]) + sg[2]) + sg[3];
+        dbeta[k] = ((sb[0] + sb[1]) + sb[2]) + sb[3];
     }
     return MI355PPO_OK;
 }

@@ -14,6 +14,9 @@ packages (used when importable) this module provides self-contained vector envs 
 * ``SyntheticContinuousVecEnv`` -- (N,17) observations / (N,6) actions (HalfCheetah-v4 shapes).
 * ``DeviceSyntheticAtariVecEnv``-- the Atari byte streams generated directly in HBM (bench.py's
                                    "inputs already resident in HBM" mode; no PCIe in the timed region).
+* ``SyntheticMemoryVecEnv``     -- a cue-recall memory task for ppo_trxl.py (vector or (84,84,3) image
+                                   observations, Discrete or MultiDiscrete actions, episodes ended by
+                                   termination and by truncation).
 
 All follow gymnasium 0.29's vector API (5-tuple ``step``, autoreset, ``final_info``); ``api="gym"``
 switches to the old 4-tuple + ``info["lives"]/["r"]/["l"]`` layout that ``ppo_atari_envpool.py`` consumes.
@@ -538,6 +541,115 @@ class SyntheticMAAtariVecEnv:
         r, l = self.stats.update(reward.astype(np.float32), done)
         info = [{"episode": {"r": r[i], "l": l[i]}} if done[i] else {} for i in range(self.num_envs)]
         return self._obs(), reward, done, info
+
+    def close(self):
+        pass
+
+
+class MultiDiscrete:
+    def __init__(self, nvec):
+        self.nvec = np.asarray(nvec, dtype=np.int64)
+        self.shape = self.nvec.shape
+        self.dtype = np.int64
+
+    def __repr__(self):
+        return f"MultiDiscrete({self.nvec.tolist()})"
+
+
+class _Spec:
+    def __init__(self, env_id: str, max_episode_steps):
+        self.id, self.max_episode_steps = env_id, max_episode_steps
+
+
+class _MemoryEnvHandle:
+    """``envs.envs[i]`` of the memory stand-in: what ppo_trxl.py reads from it -- ``spec.max_episode_steps`` (a TimeLimit env) or,
+    for Memory Gym ids (no TimeLimit), ``max_episode_steps`` after ``reset()``."""
+
+    def __init__(self, vec, i, spec_steps):
+        self._vec, self._i = vec, i
+        self.spec = _Spec(vec.env_id, spec_steps)
+        self.max_episode_steps = -1
+
+    def reset(self, seed=None):
+        self.max_episode_steps = self._vec.max_episode_steps
+        return None, {}
+
+
+class SyntheticMemoryVecEnv:
+    """A memory task in the gymnasium 0.29 vector API (autoreset, ``final_info``) for ppo_trxl.py where ``gymnasium`` /
+    ``memory_gym`` are absent.  Each episode shows a cue (one of ``n_cues``) at its first step only; at a random later step it
+    shows a query flag, and the action that names the cue earns 1 and terminates the episode.  Episodes reach the query at step
+    ``min_len - 1 .. max_len - 1``; an episode that reaches ``max_episode_steps`` first is truncated.  By env id:
+
+    * ``...Vector...``: (obs_dim,) float32 observations; otherwise (84, 84, 3) uint8 images (the cue a colour block, the query a bar);
+    * ``...MultiDiscrete...``: MultiDiscrete([n_cues, 2]) actions (the first component names the cue); otherwise Discrete(n_cues);
+    * ``MiniGrid...`` ids carry a TimeLimit (``spec.max_episode_steps``), the others behave as Memory Gym envs (``spec`` without a
+      limit; ``max_episode_steps`` after ``reset()``).
+    """
+
+    def __init__(self, env_id: str, num_envs: int, max_episode_steps: int = 64, min_len: int = 2, max_len: int = None,
+                 n_cues: int = 4, obs_dim: int = 8):
+        self.env_id, self.num_envs = env_id, int(num_envs)
+        self.max_episode_steps = int(max_episode_steps)
+        self.min_len, self.max_len = int(min_len), int(max_len if max_len is not None else max_episode_steps + 4)
+        self.n_cues, self.obs_dim = int(n_cues), int(obs_dim)
+        self.image = "Vector" not in env_id
+        self.single_observation_space = (Box(0, 255, (84, 84, 3), np.uint8) if self.image else
+                                         Box(-np.inf, np.inf, (self.obs_dim,), np.float32))
+        self.single_action_space = MultiDiscrete([self.n_cues, 2]) if "MultiDiscrete" in env_id else Discrete(self.n_cues)
+        spec_steps = self.max_episode_steps if env_id.startswith("MiniGrid") else None
+        self.envs = [_MemoryEnvHandle(self, i, spec_steps) for i in range(self.num_envs)]
+        self._rng = np.random.default_rng(0)
+        self._stats = _EpisodeStats(self.num_envs)
+        self.cue = np.zeros(self.num_envs, np.int64)
+        self.query = np.zeros(self.num_envs, np.int64)
+        self.t = np.zeros(self.num_envs, np.int64)
+
+    def _new_episodes(self, rows):
+        k = len(rows)
+        self.cue[rows] = self._rng.integers(0, self.n_cues, k)
+        self.query[rows] = self._rng.integers(self.min_len - 1, self.max_len, k)
+        self.t[rows] = 0
+
+    def _obs(self):
+        n = self.num_envs
+        first, asked = self.t == 0, self.t == self.query
+        if self.image:
+            o = np.zeros((n, 84, 84, 3), np.uint8)
+            for i in range(n):
+                if first[i]:
+                    o[i, 20:64, 20:64, self.cue[i] % 3] = 60 * (1 + self.cue[i] // 3)
+                if asked[i]:
+                    o[i, 76:80, :, :] = 255
+                o[i, 0, self.t[i] % 84, :] = 128
+            return o
+        o = np.zeros((n, self.obs_dim), np.float32)
+        o[np.flatnonzero(first), self.cue[first]] = 1.0
+        o[:, self.n_cues] = asked
+        o[:, self.n_cues + 1] = self.t / float(self.max_episode_steps)
+        o[:, self.n_cues + 2:] = self._rng.standard_normal((n, self.obs_dim - self.n_cues - 2)).astype(np.float32) * 0.1
+        return o
+
+    def reset(self, seed: Optional[int] = None):
+        if seed is not None:
+            self._rng = np.random.default_rng(seed)
+        self._stats = _EpisodeStats(self.num_envs)
+        self._new_episodes(np.arange(self.num_envs))
+        return self._obs(), {}
+
+    def step(self, action):
+        a = np.asarray(action).reshape(self.num_envs, -1)[:, 0]
+        asked = self.t == self.query
+        terminated = asked.copy()
+        reward = np.where(asked & (a == self.cue), 1.0, 0.0)
+        self.t += 1
+        truncated = ~terminated & (self.t >= self.max_episode_steps)
+        done = terminated | truncated
+        r, l = self._stats.update(reward.astype(np.float32), done.astype(np.int32))
+        infos = _final_info(done, r, l)
+        if done.any():
+            self._new_episodes(np.flatnonzero(done))
+        return self._obs(), reward, terminated, truncated, infos
 
     def close(self):
         pass

@@ -6,7 +6,8 @@ CUDA device always runs the HIP kernels and raises if ``libmi355ppo.so`` is miss
 refuse CUDA tensors.  The twins (csrc/host_twins.hip, declared in include/mi355ppo.h) are the device
 kernels' own row / element functions compiled for the host, so the CPU loop crosses the SAME C ABI seams
 as the GPU loop: GAE (ppo.py:218-231), the fused loss forward + backward (ppo.py:250-285 and its autograd),
-the LSTM sequence scans of ppo_atari_lstm.py (opt-in: ``MI355PPO_LSTM=fused``) and, for tests, sampling and clip + Adam.  The learners whose loss has extra terms (LSTM state, RND's second value
+the LSTM sequence scans of ppo_atari_lstm.py (opt-in: ``MI355PPO_LSTM=fused``), the TrXL memory attention of ppo_trxl.py
+(opt-in: ``MI355PPO_TRXL=fused``) and, for tests, sampling and clip + Adam.  The learners whose loss has extra terms (LSTM state, RND's second value
 head and distillation loss) cross the same twin on their logits / value and add their terms outside.
 """
 from __future__ import annotations
@@ -243,3 +244,40 @@ def lstm_seq_backward(dh, dhT, dcT, record, w_hh, done, want_dh0: bool = True, w
     _lib.check(lib.mi355ppo_lstm_seq_bwd_f32_cpu(_p(g), _p(dhT), _p(dcT), _p(record), _p(w), _p(d), _p(dgx), _p(dh0), _p(dc0), T, B, H),
                "mi355ppo_lstm_seq_bwd_f32_cpu")
     return dgx, dh0, dc0
+
+
+def _trxl_args(memory, ep, rows, pos, mask, pe, gamma, beta, q):
+    from .ops import trxl_dims
+
+    E, T, layers, D, B, L, H = trxl_dims(memory, rows, q)
+    m, g, b, qq = _f32(memory), _f32(gamma), _f32(beta), _f32(q)
+    e, r = ep.to(torch.int64).contiguous(), rows.to(torch.int64).contiguous()
+    k = (mask != 0).to(torch.uint8).contiguous()
+    p = None if pe is None else _f32(pe)
+    ps = None if pe is None else pos.to(torch.int64).contiguous()
+    return (E, T, layers, D, B, L, H), (m, e, r, ps, k, p, g, b, qq)
+
+
+def trxl_attn_forward(memory, layer, ep, rows, pos, mask, pe, gamma, beta, q):
+    """The TrXL memory attention of one layer through ``mi355ppo_trxl_attn_fwd_f32_cpu`` -> (u (B,H,d), stats (B,H,2)); same
+    arithmetic as the device kernel (csrc/trxl_rows.h).  An out-of-range index raises."""
+    lib = _lib.load()
+    (E, T, layers, D, B, L, H), (m, e, r, ps, k, p, g, b, qq) = _trxl_args(memory, ep, rows, pos, mask, pe, gamma, beta, q)
+    u, stats = torch.empty((B, H, D // H)), torch.empty((B, H, 2))
+    _lib.check(lib.mi355ppo_trxl_attn_fwd_f32_cpu(_p(m), E, T, layers, int(layer), _p(e), _p(r), _p(ps), _p(k), _p(p),
+                                                  0 if p is None else p.shape[0], _p(g), _p(b), _p(qq), _p(u), _p(stats), B, L, D, H),
+               "mi355ppo_trxl_attn_fwd_f32_cpu")
+    return u, stats
+
+
+def trxl_attn_backward(memory, layer, ep, rows, pos, mask, pe, gamma, beta, q, u, stats, du):
+    """Backward of ``trxl_attn_forward`` through ``mi355ppo_trxl_attn_bwd_f32_cpu`` -> (dq (B,H,d), dgamma (D), dbeta (D))."""
+    lib = _lib.load()
+    (E, T, layers, D, B, L, H), (m, e, r, ps, k, p, g, b, qq) = _trxl_args(memory, ep, rows, pos, mask, pe, gamma, beta, q)
+    dq, rows_ws = torch.empty((B, H, D // H)), torch.empty((2, B, D))
+    dgamma, dbeta = torch.empty(D), torch.empty(D)
+    _lib.check(lib.mi355ppo_trxl_attn_bwd_f32_cpu(_p(m), E, T, layers, int(layer), _p(e), _p(r), _p(ps), _p(k), _p(p),
+                                                  0 if p is None else p.shape[0], _p(g), _p(b), _p(qq), _p(_f32(u)), _p(_f32(stats)),
+                                                  _p(_f32(du)), _p(dq), _p(rows_ws), _p(dgamma), _p(dbeta), B, L, D, H),
+               "mi355ppo_trxl_attn_bwd_f32_cpu")
+    return dq, dgamma, dbeta

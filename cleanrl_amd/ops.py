@@ -3,8 +3,8 @@
 Each function mirrors one seam of the reference's inline PPO code (cited per function) and takes
 CUDA (=HIP) ``torch`` tensors only: torch is plumbing here (device memory + the current stream), the
 computation is the HIP kernels.  Passing a CPU tensor raises; there is no CPU fallback in this module.  The one exception is
-``LSTMSeq`` / ``lstm_seq``, which take CPU tensors to the LSTM scans' host twins (cleanrl_amd/host_ops.py) on purpose: the
-agent's host path and the tests run the same arithmetic as the device scan.
+``LSTMSeq`` / ``lstm_seq`` and ``TrXLMemoryAttention``, which take CPU tensors to the host twins (cleanrl_amd/host_ops.py) on
+purpose: the agent's host path and the tests run the same arithmetic as the device kernels.
 """
 from __future__ import annotations
 
@@ -19,7 +19,7 @@ __all__ = [
     "gae", "categorical_sample", "categorical_logprob_entropy", "normal_sample", "normal_logprob_entropy",
     "ppo_loss_categorical", "ppo_loss_normal", "obs_u8_to_f32", "obs_nchw_to_nhwc_u8", "clip_adam_", "PPOLossCategorical", "PPOLossNormal",
     "CategoricalLogProbEntropy", "NormalLogProbEntropy", "LOSS_SCALAR_NAMES", "lstm_seq_forward", "lstm_seq_backward", "LSTMSeq",
-    "lstm_seq", "lstm_seq_dw_hh",
+    "lstm_seq", "lstm_seq_dw_hh", "trxl_attn_forward", "trxl_attn_backward", "TrXLMemoryAttention", "trxl_memory_attention",
 ]
 
 LOSS_SCALAR_NAMES = ("loss", "pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac")
@@ -874,6 +874,144 @@ def lstm_seq(gx, w_hh, h0, c0, done):
     h, hT, cT, _ = fwd(gx.contiguous(), w_hh.detach().contiguous(), h0.contiguous(), c0.contiguous(),
                        done.to(torch.float32).contiguous())
     return h, hT, cT
+
+
+# ------------------------------------------------------------------------------------------- TrXL
+def trxl_dims(memory, rows, q):
+    """(E, T_ep, layers, D, B, L, H) of one attention call; shapes as in include/mi355ppo.h (TRXL)."""
+    if memory.dim() != 4:
+        raise ValueError(f"memory: expected (E, T_ep, layers, D), got {tuple(memory.shape)}")
+    if rows.dim() != 2 or q.dim() != 3:
+        raise ValueError(f"rows: expected (B, L), q: expected (B, H, d); got {tuple(rows.shape)}, {tuple(q.shape)}")
+    E, T, layers, D = memory.shape
+    B, L = rows.shape
+    H = q.shape[1]
+    if tuple(q.shape) != (B, H, D // max(H, 1)) or H * q.shape[2] != D:
+        raise ValueError(f"q: expected (B={B}, H, D/H) with D={D}, got {tuple(q.shape)}")
+    return E, T, layers, D, B, L, H
+
+
+def _trxl_checked(memory, layer, ep, rows, pos, mask, pe, gamma, beta, q):
+    E, T, layers, D, B, L, H = trxl_dims(memory, rows, q)
+    _chk(memory, torch.float32, "memory")
+    _chk(ep, torch.int64, "ep", (B,))
+    _chk(rows, torch.int64, "rows", (B, L))
+    _chk(mask, torch.uint8, "mask", (B, L))
+    if pe is not None:
+        _chk(pe, torch.float32, "pe")
+        _chk(pos, torch.int64, "pos", (B, L))
+    _chk(gamma, torch.float32, "gamma", (D,))
+    _chk(beta, torch.float32, "beta", (D,))
+    _chk(q, torch.float32, "q", (B, H, D // H))
+    return E, T, layers, D, B, L, H
+
+
+def _trxl_report(err, fn: str) -> None:
+    """The error word of one call: read back (one sync) unless the stream is being captured into a graph."""
+    if not torch.cuda.is_current_stream_capturing() and int(err.item()) != 0:
+        raise IndexError(f"{fn}: an episode, row or position index was outside the memory / pe table (clamped on the device)")
+
+
+def trxl_attn_forward(memory, layer: int, ep, rows, pos, mask, pe, gamma, beta, q, err=None):
+    """The episodic-memory attention of one TrXL layer (ppo_trxl.py: MultiHeadAttention.forward over norm_kv of the window
+    rows): ``u`` (B,H,d) = sum_j softmax(s)_j LN(mem[ep, rows_j, layer] + pe[pos_j])_h and ``stats`` (B,H,2) (max, sum) for the
+    backward.  ``q`` is q~ = W_k^T q (``q @ keys.weight``); ``pe`` may be None.  ``err`` (int32, 1 element): a caller-owned
+    error word (zeroed here, left unread); with None one is allocated and checked after the launch."""
+    lib = _lib.load()
+    E, T, layers, D, B, L, H = _trxl_checked(memory, layer, ep, rows, pos, mask, pe, gamma, beta, q)
+    dev = q.device
+    u = torch.empty((B, H, D // H), device=dev)
+    stats = torch.empty((B, H, 2), device=dev)
+    own = err is None
+    if own:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    else:
+        err.zero_()
+    P = 0 if pe is None else pe.shape[0]
+    with _on(dev):
+        st = lib.mi355ppo_trxl_attn_fwd_f32(_ptr(memory), E, T, layers, int(layer), _ptr(ep), _ptr(rows), _ptr(pos), _ptr(mask), _ptr(pe),
+                                            P, _ptr(gamma), _ptr(beta), _ptr(q), _ptr(u), _ptr(stats), _ptr(err), B, L, D, H, _stream(dev))
+    _lib.check(st, "mi355ppo_trxl_attn_fwd_f32")
+    if own:
+        _trxl_report(err, "mi355ppo_trxl_attn_fwd_f32")
+    return u, stats
+
+
+def trxl_attn_backward(memory, layer: int, ep, rows, pos, mask, pe, gamma, beta, q, u, stats, du, err=None):
+    """Backward of ``trxl_attn_forward`` -> (dq (B,H,d), dgamma (D), dbeta (D)); no gradient reaches the memory."""
+    lib = _lib.load()
+    E, T, layers, D, B, L, H = _trxl_checked(memory, layer, ep, rows, pos, mask, pe, gamma, beta, q)
+    _chk(u, torch.float32, "u", (B, H, D // H))
+    _chk(stats, torch.float32, "stats", (B, H, 2))
+    _chk(du, torch.float32, "du", (B, H, D // H))
+    dev = q.device
+    dq = torch.empty((B, H, D // H), device=dev)
+    rows_ws = torch.empty((2, B, D), device=dev)
+    dgamma, dbeta = torch.empty(D, device=dev), torch.empty(D, device=dev)
+    own = err is None
+    if own:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    else:
+        err.zero_()
+    P = 0 if pe is None else pe.shape[0]
+    with _on(dev):
+        st = lib.mi355ppo_trxl_attn_bwd_f32(_ptr(memory), E, T, layers, int(layer), _ptr(ep), _ptr(rows), _ptr(pos), _ptr(mask), _ptr(pe),
+                                            P, _ptr(gamma), _ptr(beta), _ptr(q), _ptr(u), _ptr(stats), _ptr(du), _ptr(dq), _ptr(rows_ws),
+                                            _ptr(dgamma), _ptr(dbeta), _ptr(err), B, L, D, H, _stream(dev))
+    _lib.check(st, "mi355ppo_trxl_attn_bwd_f32")
+    if own:
+        _trxl_report(err, "mi355ppo_trxl_attn_bwd_f32")
+    return dq, dgamma, dbeta
+
+
+def _trxl_impl(t):
+    """The attention for ``t``'s device: the HIP kernels for CUDA tensors, the ``*_cpu`` twins (cleanrl_amd/host_ops.py) for CPU ones."""
+    if t.is_cuda:
+        return trxl_attn_forward, trxl_attn_backward
+    from . import host_ops
+
+    return host_ops.trxl_attn_forward, host_ops.trxl_attn_backward
+
+
+def _trxl_inputs(memory, ep, rows, pos, mask, pe):
+    """The non-differentiable inputs in the kernels' dtypes: int64 indices, uint8 mask (any nonzero keeps a row)."""
+    pe = None if pe is None else pe.detach().to(torch.float32).contiguous()
+    pos = None if pe is None else pos.to(torch.int64).contiguous()
+    return (memory.detach().contiguous(), ep.to(torch.int64).contiguous(), rows.to(torch.int64).contiguous(), pos,
+            (mask != 0).to(torch.uint8).contiguous(), pe)
+
+
+class TrXLMemoryAttention(torch.autograd.Function):
+    """Differentiable ``(q~, gamma, beta; memory, layer, ep, rows, pos, mask, pe) -> u`` (B,H,d): the window gather, positional
+    encoding, norm_kv, scores, masked softmax and weighted sum of one TrXL layer in one streaming pass (csrc/trxl_attn.hip).
+    The memory, indices, mask and pe get no gradient.  The HIP kernels run for CUDA tensors, the host twins for CPU ones."""
+
+    @staticmethod
+    def forward(ctx, q, gamma, beta, memory, layer, ep, rows, pos, mask, pe):
+        fwd, _ = _trxl_impl(q)
+        memory, ep, rows, pos, mask, pe = _trxl_inputs(memory, ep, rows, pos, mask, pe)
+        q, gamma, beta = q.detach().contiguous(), gamma.detach().contiguous(), beta.detach().contiguous()
+        u, stats = fwd(memory, layer, ep, rows, pos, mask, pe, gamma, beta, q)
+        ctx.layer = layer
+        ctx.save_for_backward(q, gamma, beta, memory, ep, rows, pos, mask, pe, u, stats)
+        return u
+
+    @staticmethod
+    def backward(ctx, du):
+        q, gamma, beta, memory, ep, rows, pos, mask, pe, u, stats = ctx.saved_tensors
+        _, bwd = _trxl_impl(q)
+        dq, dgamma, dbeta = bwd(memory, ctx.layer, ep, rows, pos, mask, pe, gamma, beta, q, u, stats, du.contiguous())
+        return dq, dgamma, dbeta, None, None, None, None, None, None, None
+
+
+def trxl_memory_attention(q, gamma, beta, memory, layer: int, ep, rows, pos, mask, pe):
+    """``TrXLMemoryAttention.apply`` when a gradient is wanted, else the forward alone (the rollout step, the bootstrap)."""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, gamma, beta)):
+        return TrXLMemoryAttention.apply(q, gamma, beta, memory, layer, ep, rows, pos, mask, pe)
+    fwd, _ = _trxl_impl(q)
+    memory, ep, rows, pos, mask, pe = _trxl_inputs(memory, ep, rows, pos, mask, pe)
+    u, _ = fwd(memory, layer, ep, rows, pos, mask, pe, gamma.detach().contiguous(), beta.detach().contiguous(), q.detach().contiguous())
+    return u
 
 
 def synth_continuous_step(state, reset_state, At, Bm, w, noise, k: int, steps, horizon: float, action, obs_out, reward, done, k_base=None):

@@ -32,14 +32,15 @@
 extern "C" {
 #endif
 
-#define MI355PPO_VERSION 220 /* major*100 + minor*10 + patch.  The minor moves whenever an exported signature changes or an entry
+#define MI355PPO_VERSION 230 /* major*100 + minor*10 + patch.  The minor moves whenever an exported signature changes or an entry
                                   point is added (1.1: adv_mean_den / conv1_variant arguments of round 2; 1.2, 1.3: round 3;
                                   1.4: the *_cpu host-pointer twins; 1.5: mi355ppo_init; 1.6: round 4 -- the fused MLP family K7,
                                   mi355ppo_clip_adam_sched_f32; 1.7: mi355ppo_fc_heads_act_categorical_f32, mi355ppo_nature_packs_f32,
                                   mi355ppo_synth_atari_step_hwc_ctr_u8; 1.8: round 5 -- the *_f16x2 / *_amax entry points and mi355ppo_absmax_f32;
                                   1.9: round 6 -- the kernel queries mi355ppo_fc_packed_kernel_f16x2, mi355ppo_fc_wgrad_kernel_f16x2, mi355ppo_cnn_conv_wgrad_kernel_f16x2;
                                   heads of up to 18 actions, a 4-byte-aligned critic row; 2.0: the peer-memory gradient exchange mi355ppo_dp_*; 2.1: the fused MLP family takes obs_dim <= 512, n_out <= 20;
-                                  2.2: the done-masked LSTM sequence scans mi355ppo_lstm_seq_fwd_f32 / _bwd_f32 and their *_cpu twins);
+                                  2.2: the done-masked LSTM sequence scans mi355ppo_lstm_seq_fwd_f32 / _bwd_f32 and their *_cpu twins;
+                                  2.3: the TrXL episodic-memory attention mi355ppo_trxl_attn_fwd_f32 / _bwd_f32 and their *_cpu twins);
                                   a binding must check major AND minor (cleanrl_amd/_lib.py does) */
 
 #if defined(__GNUC__)
@@ -394,6 +395,41 @@ MI355PPO_API int mi355ppo_lstm_seq_bwd_f32(const float* dh, const float* dhT, co
                                            int H, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * TRXL  The episodic-memory attention core of ppo_trxl.py (cleanrl/ppo_trxl/ppo_trxl.py: batched_index_select of the
+ * window, Transformer.forward's positional encoding, TransformerLayer.forward's norm_kv, MultiHeadAttention.forward's keys,
+ * masked softmax and weighted sum) for one layer, reassociated so that no matrix is applied per row.  Per sample b, window
+ * row j < L and head h (d = D / H):
+ *   y_j  = LayerNorm(mem[ep[b], rows[b,j], layer, :] + pe[pos[b,j]])   (eps 1e-5, biased variance; no pe term if pe == NULL)
+ *   s_j  = (mask[b,j] ? q[b,h] . y_j,h : -1e20) / sqrt(D)             (q = q~ = W_k^T q_h: the caller's `q @ keys.weight`)
+ *   u[b,h] = sum_j softmax(s)_j y_j,h                                  (the caller applies `values` and `fc_out` to u)
+ * A fully masked window is a uniform softmax over its L rows, as in the reference (the fill precedes the scale).
+ *   memory     : (E, T_ep, layers, D) f32, the episode pool                                   [in]
+ *   ep         : (B) int64 episode of each sample;  rows, pos : (B, L) int64 window rows / pe rows  [in]
+ *   mask       : (B, L) uint8;  pe : (P, D) f32 or NULL;  gamma, beta : (D) f32 of norm_kv   [in]
+ *   q          : (B, H, d) f32                                                                [in]
+ *   u          : (B, H, d) f32;  stats : (B, H, 2) f32 softmax max and sum, for the backward  [out]
+ *   err        : int32 error word or NULL: an index outside [0, E) / [0, T_ep) / [0, P) is clamped (never read out of bounds)
+ *                and 1 is stored to *err; the caller zeroes it before and reads it after       [out]
+ * Shapes: D % 64 == 0, D <= 512, H divides 64, 1 <= L <= 1024 (else MI355PPO_EINVAL).  One workgroup per sample folds every
+ * sum in a fixed order: deterministic, and sample b's bits do not depend on B or on b.  Math: csrc/trxl_rows.h.
+ */
+MI355PPO_API int mi355ppo_trxl_attn_fwd_f32(const float* memory, int E, int T_ep, int layers, int layer, const int64_t* ep,
+                                            const int64_t* rows, const int64_t* pos, const uint8_t* mask, const float* pe, int P,
+                                            const float* gamma, const float* beta, const float* q, float* u, float* stats, int* err,
+                                            int B, int L, int D, int H, void* stream);
+/* Backward, re-streaming the window with the forward's u and stats:
+ *   du         : (B, H, d) f32 d loss / d u                                                   [in]
+ *   dq         : (B, H, d) f32 d loss / d q                                                   [out]
+ *   dln_rows   : (2, B, D) f32 per-sample d gamma and d beta rows (caller scratch, also a result) [out]
+ *   dgamma, dbeta : (D) f32 the rows folded over b in a fixed order (no atomics)               [out]
+ * No gradient reaches the memory: the reference stores detached layer inputs. */
+MI355PPO_API int mi355ppo_trxl_attn_bwd_f32(const float* memory, int E, int T_ep, int layers, int layer, const int64_t* ep,
+                                            const int64_t* rows, const int64_t* pos, const uint8_t* mask, const float* pe, int P,
+                                            const float* gamma, const float* beta, const float* q, const float* u, const float* stats,
+                                            const float* du, float* dq, float* dln_rows, float* dgamma, float* dbeta, int* err, int B,
+                                            int L, int D, int H, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Host-pointer twins (csrc/host_twins.hip) of the PPO-path entry points above: the same arguments minus `stream` and
  * `workspace`, every pointer a HOST pointer, the call returns when the result is written.  Same math by construction: the
  * row / element functions (GAE step, Categorical row, loss row terms, advantage statistics fold, Adam element, Philox stream)
@@ -447,6 +483,16 @@ MI355PPO_API int mi355ppo_lstm_seq_fwd_f32_cpu(const float* gx, const float* w_h
 MI355PPO_API int mi355ppo_lstm_seq_bwd_f32_cpu(const float* dh, const float* dhT, const float* dcT, const float* record,
                                                const float* w_hh, const float* done, float* dgx, float* dh0, float* dc0, int T,
                                                int B, int H);
+/* The TrXL twins refuse (MI355PPO_EINVAL) an out-of-range ep / rows / pos instead of clamping it. */
+MI355PPO_API int mi355ppo_trxl_attn_fwd_f32_cpu(const float* memory, int E, int T_ep, int layers, int layer, const int64_t* ep,
+                                                const int64_t* rows, const int64_t* pos, const uint8_t* mask, const float* pe, int P,
+                                                const float* gamma, const float* beta, const float* q, float* u, float* stats, int B,
+                                                int L, int D, int H);
+MI355PPO_API int mi355ppo_trxl_attn_bwd_f32_cpu(const float* memory, int E, int T_ep, int layers, int layer, const int64_t* ep,
+                                                const int64_t* rows, const int64_t* pos, const uint8_t* mask, const float* pe, int P,
+                                                const float* gamma, const float* beta, const float* q, const float* u,
+                                                const float* stats, const float* du, float* dq, float* dln_rows, float* dgamma,
+                                                float* dbeta, int B, int L, int D, int H);
 
 /* ---------------------------------------------------------------------------------------------
  * FC   Linear(3136, 512) + ReLU of the NatureCNN (cleanrl/ppo_atari_multigpu.py:144-145) on the bf16 matrix pipe
