@@ -136,6 +136,14 @@ SIGNATURES = {
                                            c_int, c_int, c_int, c_int, _P]),
     "mi355ppo_trxl_attn_bwd_f32": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P,
                                            _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    # the IMPALA-CNN trunk (csrc/impala.hip)
+    "mi355ppo_impala_saved_floats": (c_int64, [c_int]),
+    "mi355ppo_impala_argmax_bytes": (c_int64, [c_int]),
+    "mi355ppo_impala_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "mi355ppo_impala_fwd_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "mi355ppo_impala_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "mi355ppo_impala_maxpool_fwd_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "mi355ppo_impala_maxpool_bwd_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     # host-pointer twins (csrc/host_twins.hip): the device signatures minus stream / workspace
     "mi355ppo_gae_f32_cpu": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_double, c_double]),
     "mi355ppo_categorical_sample_f32_cpu": (c_int, [_P, _P, c_uint64, c_uint64, _P, _P, _P, _P, c_int, c_int]),
@@ -157,9 +165,13 @@ SIGNATURES = {
                                                c_int, c_int, c_int, c_int]),
     "mi355ppo_trxl_attn_bwd_f32_cpu": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P,
                                                _P, _P, _P, _P, c_int, c_int, c_int, c_int]),
+    "mi355ppo_impala_fwd_f32_cpu": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "mi355ppo_impala_bwd_f32_cpu": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "mi355ppo_impala_maxpool_fwd_f32_cpu": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int]),
+    "mi355ppo_impala_maxpool_bwd_f32_cpu": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int]),
 }
 
-ABI_VERSION = 230       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)
+ABI_VERSION = 240       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)
 
 _lib = None
 

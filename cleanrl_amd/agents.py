@@ -406,6 +406,31 @@ class AtariLSTMAgent(_DiscreteMixin, nn.Module):
         return action, lp, ent, self.critic(hidden), lstm_state
 
 
+IMPALA_BACKENDS = ("torch", "fused")
+
+
+def impala_backend_from_env() -> str:
+    """``MI355PPO_IMPALA``: ``torch`` (default: the reference's ConvSequence modules) or ``fused`` (the trunk kernels of
+    csrc/impala.hip, ``ops.impala_trunk``)."""
+    v = os.environ.get("MI355PPO_IMPALA", "torch")
+    if v not in IMPALA_BACKENDS:
+        raise ValueError(f"MI355PPO_IMPALA={v!r}: expected torch or fused")
+    return v
+
+
+def _impala_features(agent, xn):
+    """The IMPALA network (conv sequences, then Flatten -> ReLU -> Linear -> ReLU) on normalised (B, C, H, W) frames.  With the
+    ``fused`` backend the three conv sequences run as ``ops.impala_trunk`` on the channels-last frames (``xn`` is a permuted
+    view of them, so the permute back is free) and the tail runs on the NCHW view of the trunk's output, so ``Flatten`` sees
+    the reference's (C, H, W) order."""
+    if agent.impala_backend != "fused":
+        return agent.network(xn)
+    net = agent.network
+    params = [p for i in range(3) for p in net[i].parameters()]
+    y = ops.impala_trunk(xn.permute(0, 2, 3, 1), params)
+    return net[3:](y.permute(0, 3, 1, 2))
+
+
 class ResidualBlock(nn.Module):
     """ppo_procgen.py:86-98 (IMPALA-CNN residual block): x + conv1(relu(conv0(relu(x))))."""
 
@@ -475,6 +500,7 @@ class ProcgenAgent(_DiscreteMixin, nn.Module):
         self.critic = layer_init(nn.Linear(256, 1), std=1)
         self.n_actions = envs.single_action_space.n
         self.rng = _SampleCounter()
+        self.impala_backend = impala_backend_from_env()
 
     def _normalise(self, x):
         """(B, H, W, C) frames -> normalised (B, C, H, W) view ("bhwc" -> "bchw", :147,150)."""
@@ -486,11 +512,11 @@ class ProcgenAgent(_DiscreteMixin, nn.Module):
 
     def heads(self, xn):
         """xn: normalised f32 frames as (B, C, H, W) (any strides) -> (logits, value)."""
-        hidden = self.network(xn)
+        hidden = _impala_features(self, xn)
         return self.actor(hidden), self.critic(hidden)
 
     def get_value(self, x):
-        return self.critic(self.network(self._normalise(x)))
+        return self.critic(_impala_features(self, self._normalise(x)))
 
     def get_action_and_value(self, x, action=None):
         logits, value = self.heads(self._normalise(x))
@@ -683,6 +709,7 @@ class PPGAgent(_DiscreteMixin, nn.Module):
         self.aux_critic = layer_init_normed(nn.Linear(256, 1), norm_dim=1, scale=0.1)
         self.n_actions = envs.single_action_space.n
         self.rng = _SampleCounter()
+        self.impala_backend = impala_backend_from_env()
 
     def _normalise(self, x):
         """(B, H, W, C) frames -> normalised (B, C, H, W) view ("bhwc" -> "bchw")."""
@@ -694,12 +721,12 @@ class PPGAgent(_DiscreteMixin, nn.Module):
 
     def heads(self, xn):
         """xn: normalised (B, C, H, W) frames -> (logits, value on the detached features): the policy-phase seam."""
-        hidden = self.network(xn)
+        hidden = _impala_features(self, xn)
         return self.actor(hidden), self.critic(hidden.detach())
 
     def heads_aux(self, xn):
         """-> (logits, value on detached features, auxiliary value on live features): the auxiliary-phase seam."""
-        hidden = self.network(xn)
+        hidden = _impala_features(self, xn)
         return self.actor(hidden), self.critic(hidden.detach()), self.aux_critic(hidden)
 
     def get_action_and_value(self, x, action=None):
@@ -708,14 +735,14 @@ class PPGAgent(_DiscreteMixin, nn.Module):
         return action, lp, ent, value
 
     def get_value(self, x):
-        return self.critic(self.network(self._normalise(x)))
+        return self.critic(_impala_features(self, self._normalise(x)))
 
     def get_pi_value_and_aux_value(self, x):
         logits, value, aux = self.heads_aux(self._normalise(x))
         return Categorical(logits=logits), value, aux
 
     def get_pi(self, x):
-        return Categorical(logits=self.actor(self.network(self._normalise(x))))
+        return Categorical(logits=self.actor(_impala_features(self, self._normalise(x))))
 
 
 class MAAtariAgent(_DiscreteMixin, nn.Module):

@@ -9,7 +9,7 @@
 //
 // Same math by construction: the row / element functions (gae_step, categorical_row, ppo_row_terms, mean_den_from_sums,
 // adam_elem, the Philox stream, the LSTM cell and its 128-column products) are the device kernels' own, compiled for the host
-// from the same headers (ppo_rows.h, catrow.h, lstm_rows.h, trxl_rows.h, common.h), without FMA contraction.  Differences to the device results can come only from libm vs the device
+// from the same headers (ppo_rows.h, catrow.h, lstm_rows.h, trxl_rows.h, impala_rows.h, common.h), without FMA contraction.  Differences to the device results can come only from libm vs the device
 // math library (expf / logf / sincosf: a few ulp) and from the order of the f64 reductions (row order here, fixed tree there).
 // Serial, single-threaded: sizes of config A are a few hundred rows.
 #include "common.h"
@@ -17,10 +17,13 @@
 #include "ppo_rows.h"
 #include "lstm_rows.h"
 #include "trxl_rows.h"
+#include "impala_rows.h"
 
 #include <math.h>
 #include <stddef.h>
 #include <string.h>
+
+#include <vector>
 
 #pragma clang fp contract(off)
 
@@ -724,5 +727,277 @@ extern "C" MI355PPO_API int mi355ppo_trxl_attn_bwd_f32_cpu(const float* memory, 
         dgamma[k] = ((sg[0] + sg[1]) + sg[2]) + sg[3];
         dbeta[k] = ((sb[0] + sb[1]) + sb[2]) + sb[3];
     }
+    return MI355PPO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ IMPALA-CNN trunk twins
+// The device launches of impala.hip restated serially: every conv output an fmaf chain in the kernel's k order, every weight
+// gradient one chain per part in pixel order plus the fold in part order, the max pool through the same window functions
+// (impala_rows.h).  The hot loops are compiled twice, with the x86 FMA instructions and without (libm's fmaf); both round
+// each fused multiply-add once, so the bits are the same, and the first only runs where the CPU has the instructions.
+namespace {
+
+struct ImpConvHost {
+    const float* in;
+    int ci, co, h;
+    bool relu;
+    const float* wt;            // Wt[k][n], k < 9 cp (forward: cp = ci rounded up to 4), n < co
+    const float* bias;          // forward: bias (+ res); data gradient (bias NULL): mask / res epilogue
+    const float* mask;
+    const float* res;
+    float* out;
+    int B;
+};
+
+template <int V>
+__attribute__((always_inline)) inline void imp_conv_host_impl(const ImpConvHost& a) {
+    const int cp = imp_cpad(a.ci), hp = a.h + 2, kp = 9 * cp;
+    std::vector<float> pad((size_t)hp * hp * cp);
+    float acc[32];
+    for (int img = 0; img < a.B; ++img) {
+        for (int y = 0; y < hp; ++y)
+            for (int x = 0; x < hp; ++x)
+                for (int c = 0; c < cp; ++c) {
+                    const int yy = y - 1, xx = x - 1;
+                    float v = 0.0f;
+                    if (yy >= 0 && yy < a.h && xx >= 0 && xx < a.h && c < a.ci) {
+                        v = a.in[(((size_t)img * a.h + yy) * a.h + xx) * a.ci + c];
+                        if (a.relu) v = imp_relu(v);
+                    }
+                    pad[((size_t)y * hp + x) * cp + c] = v;
+                }
+        for (int y = 0; y < a.h; ++y)
+            for (int x = 0; x < a.h; ++x) {
+                for (int n = 0; n < a.co; ++n) acc[n] = 0.0f;
+                for (int k = 0; k < kp; ++k) {
+                    const int tap = k / cp;
+                    const float v = pad[((size_t)(y + tap / 3) * hp + x + tap % 3) * cp + k % cp];
+                    const float* w = a.wt + (size_t)k * a.co;
+                    for (int n = 0; n < a.co; ++n) acc[n] = fmaf(v, w[n], acc[n]);
+                }
+                const size_t o = (((size_t)img * a.h + y) * a.h + x) * a.co;
+                for (int n = 0; n < a.co; ++n)
+                    a.out[o + n] = a.bias ? imp_epi_fwd(acc[n], a.bias[n], a.res ? a.res + o + n : nullptr)
+                                          : imp_epi_dgrad(acc[n], a.mask ? a.mask + o + n : nullptr, a.res ? a.res + o + n : nullptr);
+            }
+    }
+}
+
+struct ImpWgradHost {
+    const float* in;
+    int ci, co, h;
+    bool relu;
+    const float* dy;
+    float* gw;
+    float* gb;
+    int B;
+};
+
+template <int V>
+__attribute__((always_inline)) inline void imp_wgrad_host_impl(const ImpWgradHost& a) {
+    const ImpGeom g = imp_geom(a.ci, a.co, a.h);
+    const int64_t bands = imp_bands(g, a.h, a.B);
+    const int parts = imp_parts(bands), jp = g.JP;
+    std::vector<float> part((size_t)parts * a.co * jp), row(jp);
+    for (int q = 0; q < parts; ++q) {
+        float* acc = part.data() + (size_t)q * a.co * jp;
+        for (int i = 0; i < a.co * jp; ++i) acc[i] = 0.0f;
+        int64_t b0, b1;
+        imp_part_range(bands, parts, q, &b0, &b1);
+        for (int64_t b = b0; b < b1; ++b) {
+            int64_t img0;
+            int y0;
+            imp_band(g, a.h, b, &img0, &y0);
+            for (int64_t img = img0; img < img0 + g.NI && img < a.B; ++img)
+                for (int y = y0; y < y0 + g.R; ++y)
+                    for (int x = 0; x < a.h; ++x) {
+                        for (int j = 0; j < jp; ++j) {
+                            float v = j == g.KP ? 1.0f : 0.0f;
+                            if (j < g.KP) {
+                                const int tap = j / g.CP, c = j % g.CP, yy = y + tap / 3 - 1, xx = x + tap % 3 - 1;
+                                if (yy >= 0 && yy < a.h && xx >= 0 && xx < a.h && c < a.ci) {
+                                    v = a.in[(((size_t)img * a.h + yy) * a.h + xx) * a.ci + c];
+                                    if (a.relu) v = imp_relu(v);
+                                }
+                            }
+                            row[j] = v;
+                        }
+                        const float* d = a.dy + (((size_t)img * a.h + y) * a.h + x) * a.co;
+                        for (int n = 0; n < a.co; ++n) {
+                            float* r = acc + (size_t)n * jp;
+                            for (int j = 0; j < jp; ++j) r[j] = fmaf(d[n], row[j], r[j]);
+                        }
+                    }
+        }
+    }
+    for (int n = 0; n < a.co; ++n)
+        for (int j = 0; j <= g.KP; ++j) {
+            if (j < g.KP && j % g.CP >= a.ci) continue;
+            float s = 0.0f;
+            for (int f = 0; f < kImpFoldGroups; ++f) {                 // imp_fold_kernel's order
+                int q0, q1;
+                imp_fold_range(parts, f, &q0, &q1);
+                float r = 0.0f;
+                for (int q = q0; q < q1; ++q) r = r + part[((size_t)q * a.co + n) * jp + j];
+                s = s + r;
+            }
+            if (j == g.KP)
+                a.gb[n] = s;
+            else
+                a.gw[((size_t)n * a.ci + j % g.CP) * 9 + j / g.CP] = s;
+        }
+}
+
+__attribute__((target("avx2,fma"))) void imp_conv_host_fma(const ImpConvHost& a) { imp_conv_host_impl<1>(a); }
+void imp_conv_host_plain(const ImpConvHost& a) { imp_conv_host_impl<0>(a); }
+__attribute__((target("avx2,fma"))) void imp_wgrad_host_fma(const ImpWgradHost& a) { imp_wgrad_host_impl<1>(a); }
+void imp_wgrad_host_plain(const ImpWgradHost& a) { imp_wgrad_host_impl<0>(a); }
+
+bool imp_host_has_fma() {
+    static const bool has = __builtin_cpu_supports("avx2") && __builtin_cpu_supports("fma");
+    return has;
+}
+void imp_conv_host(const ImpConvHost& a) { imp_host_has_fma() ? imp_conv_host_fma(a) : imp_conv_host_plain(a); }
+void imp_wgrad_host(const ImpWgradHost& a) { imp_host_has_fma() ? imp_wgrad_host_fma(a) : imp_wgrad_host_plain(a); }
+
+// Dense Wt[k][n] of layer l: the forward's (dgrad = false) or the data gradient's.
+std::vector<float> imp_wt_host(const float* w, int l, bool dgrad) {
+    const int ci = imp_layer_cin(l), co = imp_layer_cout(l);
+    const int kp = dgrad ? 9 * co : 9 * imp_cpad(ci), nn = dgrad ? ci : co;
+    std::vector<float> wt((size_t)kp * nn);
+    for (int k = 0; k < kp; ++k)
+        for (int n = 0; n < nn; ++n) wt[(size_t)k * nn + n] = dgrad ? imp_wt_dgrad(w, ci, co, k, n) : imp_wt_fwd(w, ci, k, n);
+    return wt;
+}
+
+void imp_pool_fwd_host(const float* x, float* y, uint8_t* arg, int B, int h, int c) {
+    const int ho = h / 2;
+    for (int64_t img = 0; img < B; ++img)
+        for (int oy = 0; oy < ho; ++oy)
+            for (int ox = 0; ox < ho; ++ox)
+                for (int ch = 0; ch < c; ++ch) {
+                    const int64_t i = ((img * ho + oy) * ho + ox) * c + ch;
+                    y[i] = imp_pool_window(x + img * h * h * c + ch, h, c, oy, ox, arg + i);
+                }
+}
+
+void imp_pool_bwd_host(const float* g, const uint8_t* arg, float* dx, int B, int h, int c) {
+    const int ho = h / 2;
+    for (int64_t img = 0; img < B; ++img)
+        for (int iy = 0; iy < h; ++iy)
+            for (int ix = 0; ix < h; ++ix)
+                for (int ch = 0; ch < c; ++ch) {
+                    const int64_t base = img * ho * ho * c + ch;
+                    dx[((img * h + iy) * h + ix) * c + ch] = imp_pool_grad(g + base, arg + base, ho, c, iy, ix);
+                }
+}
+
+int imp_check_host(const char* fn, int B, int H, int W, int C, int ch0, int ch1, int ch2) {
+    MI355_REQUIRE(B > 0, MI355PPO_EINVAL, "%s: B=%d must be positive", fn, B);
+    MI355_REQUIRE(H == kImpH && W == kImpH && C == kImpC, MI355PPO_EINVAL, "%s: frames %dx%dx%d (only 64x64x3)", fn, H, W, C);
+    MI355_REQUIRE(ch0 == 16 && ch1 == 32 && ch2 == 32, MI355PPO_EINVAL, "%s: channels [%d, %d, %d] (only [16, 32, 32])", fn, ch0, ch1,
+                  ch2);
+    return MI355PPO_OK;
+}
+
+bool imp_pool_shape_ok(int B, int H, int W, int C) {
+    return B > 0 && H == W && ((H == 64 && C == 16) || (H == 32 && C == 32) || (H == 16 && C == 32));
+}
+
+}  // namespace
+
+extern "C" MI355PPO_API int mi355ppo_impala_fwd_f32_cpu(const float* x, const float* const* params, float* y, float* saved,
+                                                        uint8_t* argmax, int B, int H, int W, int C, int ch0, int ch1, int ch2) {
+    const char* fn = "mi355ppo_impala_fwd_f32_cpu";
+    MI355_REQUIRE(x && params && y && saved && argmax, MI355PPO_EINVAL, "%s: null pointer", fn);
+    if (int st = imp_check_host(fn, B, H, W, C, ch0, ch1, ch2)) return st;
+    for (int i = 0; i < kImpParams; ++i) MI355_REQUIRE(params[i], MI355PPO_EINVAL, "%s: null pointer (params[%d])", fn, i);
+    std::vector<float> big((size_t)B * kImpH * kImpH * 16);
+    const float* xin = x;
+    for (int s = 0; s < kImpSeqs; ++s) {
+        const int ci = imp_seq_cin(s), c = imp_seq_cout(s), h = imp_seq_h(s), hp = h / 2, L = 5 * s;
+        float* P = saved + imp_saved_offset(B, s, 0);
+        float* h0 = saved + imp_saved_offset(B, s, 1);
+        float* x1 = saved + imp_saved_offset(B, s, 2);
+        float* h1 = saved + imp_saved_offset(B, s, 3);
+        float* yo = s < 2 ? saved + imp_saved_offset(B, s, 4) : y;
+        std::vector<float> wt = imp_wt_host(params[2 * L], L, false);
+        imp_conv_host({xin, ci, c, h, false, wt.data(), params[2 * L + 1], nullptr, nullptr, big.data(), B});
+        imp_pool_fwd_host(big.data(), P, argmax + imp_argmax_offset(B, s), B, h, c);
+        const float* ins[4] = {P, h0, x1, h1};
+        float* outs[4] = {h0, x1, h1, yo};
+        const float* ress[4] = {nullptr, P, nullptr, x1};
+        for (int i = 0; i < 4; ++i) {
+            wt = imp_wt_host(params[2 * (L + 1 + i)], L + 1 + i, false);
+            imp_conv_host({ins[i], c, c, hp, true, wt.data(), params[2 * (L + 1 + i) + 1], nullptr, ress[i], outs[i], B});
+        }
+        xin = yo;
+    }
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_impala_bwd_f32_cpu(const float* x, const float* const* params, const float* saved,
+                                                        const uint8_t* argmax, const float* dy, float* const* grads, int B, int H, int W,
+                                                        int C, int ch0, int ch1, int ch2) {
+    const char* fn = "mi355ppo_impala_bwd_f32_cpu";
+    MI355_REQUIRE(x && params && saved && argmax && dy && grads, MI355PPO_EINVAL, "%s: null pointer", fn);
+    if (int st = imp_check_host(fn, B, H, W, C, ch0, ch1, ch2)) return st;
+    for (int i = 0; i < kImpParams; ++i)
+        MI355_REQUIRE(params[i] && grads[i], MI355PPO_EINVAL, "%s: null pointer (params / grads[%d])", fn, i);
+    const size_t plane = (size_t)B * 32 * 32 * 16;
+    std::vector<float> ga(plane), gb(plane), t(plane), big((size_t)B * kImpH * kImpH * 16);
+    const float* g_in = dy;
+    for (int s = kImpSeqs - 1; s >= 0; --s) {
+        const int ci = imp_seq_cin(s), c = imp_seq_cout(s), h = imp_seq_h(s), hp = h / 2, L = 5 * s;
+        const float* P = saved + imp_saved_offset(B, s, 0);
+        const float* h0 = saved + imp_saved_offset(B, s, 1);
+        const float* x1 = saved + imp_saved_offset(B, s, 2);
+        const float* h1 = saved + imp_saved_offset(B, s, 3);
+        const float* xin = s == 0 ? x : saved + imp_saved_offset(B, s - 1, 4);
+        auto other = [&](const float* g) { return g == ga.data() ? gb.data() : ga.data(); };
+        float* g1 = other(g_in);
+        float* g2 = other(g1);
+        std::vector<float> wt;
+        // res_block1, then res_block0 (the order of bwd_seq in impala.hip)
+        imp_wgrad_host({h1, c, c, hp, true, g_in, grads[2 * L + 8], grads[2 * L + 9], B});
+        wt = imp_wt_host(params[2 * (L + 4)], L + 4, true);
+        imp_conv_host({g_in, c, c, hp, false, wt.data(), nullptr, h1, nullptr, t.data(), B});
+        imp_wgrad_host({x1, c, c, hp, true, t.data(), grads[2 * L + 6], grads[2 * L + 7], B});
+        wt = imp_wt_host(params[2 * (L + 3)], L + 3, true);
+        imp_conv_host({t.data(), c, c, hp, false, wt.data(), nullptr, x1, g_in, g1, B});
+        imp_wgrad_host({h0, c, c, hp, true, g1, grads[2 * L + 4], grads[2 * L + 5], B});
+        wt = imp_wt_host(params[2 * (L + 2)], L + 2, true);
+        imp_conv_host({g1, c, c, hp, false, wt.data(), nullptr, h0, nullptr, t.data(), B});
+        imp_wgrad_host({P, c, c, hp, true, t.data(), grads[2 * L + 2], grads[2 * L + 3], B});
+        wt = imp_wt_host(params[2 * (L + 1)], L + 1, true);
+        imp_conv_host({t.data(), c, c, hp, false, wt.data(), nullptr, P, g1, g2, B});
+        imp_pool_bwd_host(g2, argmax + imp_argmax_offset(B, s), big.data(), B, h, c);
+        imp_wgrad_host({xin, ci, c, h, false, big.data(), grads[2 * L], grads[2 * L + 1], B});
+        if (s > 0) {
+            float* gx = other(g2);
+            wt = imp_wt_host(params[2 * L], L, true);
+            imp_conv_host({big.data(), c, ci, h, false, wt.data(), nullptr, nullptr, nullptr, gx, B});
+            g_in = gx;
+        }
+    }
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_impala_maxpool_fwd_f32_cpu(const float* x, float* y, uint8_t* argmax, int B, int H, int W, int C) {
+    const char* fn = "mi355ppo_impala_maxpool_fwd_f32_cpu";
+    MI355_REQUIRE(x && y && argmax, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(imp_pool_shape_ok(B, H, W, C), MI355PPO_EINVAL, "%s: B=%d %dx%dx%d (only the trunk's 64x64x16, 32x32x32, 16x16x32)",
+                  fn, B, H, W, C);
+    imp_pool_fwd_host(x, y, argmax, B, H, C);
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_impala_maxpool_bwd_f32_cpu(const float* dy, const uint8_t* argmax, float* dx, int B, int H, int W,
+                                                                int C) {
+    const char* fn = "mi355ppo_impala_maxpool_bwd_f32_cpu";
+    MI355_REQUIRE(dy && argmax && dx, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(imp_pool_shape_ok(B, H, W, C), MI355PPO_EINVAL, "%s: B=%d %dx%dx%d (only the trunk's 64x64x16, 32x32x32, 16x16x32)",
+                  fn, B, H, W, C);
+    imp_pool_bwd_host(dy, argmax, dx, B, H, C);
     return MI355PPO_OK;
 }

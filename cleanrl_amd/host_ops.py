@@ -281,3 +281,64 @@ def trxl_attn_backward(memory, layer, ep, rows, pos, mask, pe, gamma, beta, q, u
                                                   _p(_f32(du)), _p(dq), _p(rows_ws), _p(dgamma), _p(dbeta), B, L, D, H),
                "mi355ppo_trxl_attn_bwd_f32_cpu")
     return dq, dgamma, dbeta
+
+
+IMPALA_CHANNELS = (16, 32, 32)
+
+
+def _ptrs(ts):
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def impala_forward(x, params):
+    """The IMPALA-CNN trunk through ``mi355ppo_impala_fwd_f32_cpu``: x (B,64,64,3) channels-last frames, params the 30 conv
+    weights / biases in state_dict order -> (y (B,8,8,32) channels-last, saved, argmax).  Same arithmetic as the device kernels
+    (csrc/impala_rows.h)."""
+    lib = _lib.load()
+    B, H, W, C = x.shape
+    xs, ps = _f32(x), [_f32(p) for p in params]
+    y = torch.empty((B, 8, 8, 32))
+    saved = torch.empty(max(int(lib.mi355ppo_impala_saved_floats(B)), 1))
+    arg = torch.empty(max(int(lib.mi355ppo_impala_argmax_bytes(B)), 1), dtype=torch.uint8)
+    _lib.check(lib.mi355ppo_impala_fwd_f32_cpu(_p(xs), _ptrs([_p_t(p) for p in ps]), _p(y), _p(saved), _p(arg), B, H, W, C,
+                                               *IMPALA_CHANNELS), "mi355ppo_impala_fwd_f32_cpu")
+    return y, saved, arg
+
+
+def impala_backward(x, params, saved, arg, dy):
+    """Backward of ``impala_forward`` through ``mi355ppo_impala_bwd_f32_cpu`` -> the 30 parameter gradients (no input gradient)."""
+    lib = _lib.load()
+    B, H, W, C = x.shape
+    xs, ps, g = _f32(x), [_f32(p) for p in params], _f32(dy)
+    grads = [torch.empty(p.shape) for p in ps]
+    _lib.check(lib.mi355ppo_impala_bwd_f32_cpu(_p(xs), _ptrs([_p_t(p) for p in ps]), _p(saved), _p(arg), _p(g),
+                                               _ptrs([_p_t(t) for t in grads]), B, H, W, C, *IMPALA_CHANNELS),
+               "mi355ppo_impala_bwd_f32_cpu")
+    return grads
+
+
+def impala_maxpool_forward(x):
+    """The trunk's max pool (3, stride 2, pad 1) on channels-last x (B,H,W,C) -> (y (B,H/2,W/2,C), argmax bytes)."""
+    lib = _lib.load()
+    B, H, W, C = x.shape
+    xs = _f32(x)
+    y = torch.empty((B, H // 2, W // 2, C))
+    arg = torch.empty((B, H // 2, W // 2, C), dtype=torch.uint8)
+    _lib.check(lib.mi355ppo_impala_maxpool_fwd_f32_cpu(_p(xs), _p(y), _p(arg), B, H, W, C), "mi355ppo_impala_maxpool_fwd_f32_cpu")
+    return y, arg
+
+
+def impala_maxpool_backward(dy, arg):
+    """Backward of ``impala_maxpool_forward``: dx (B,H,W,C) from dy and the argmax."""
+    lib = _lib.load()
+    B, Ho, Wo, C = dy.shape
+    g = _f32(dy)
+    dx = torch.empty((B, 2 * Ho, 2 * Wo, C))
+    _lib.check(lib.mi355ppo_impala_maxpool_bwd_f32_cpu(_p(g), _p(arg.contiguous()), _p(dx), B, 2 * Ho, 2 * Wo, C),
+               "mi355ppo_impala_maxpool_bwd_f32_cpu")
+    return dx
+
+
+def _p_t(t):
+    _p(t)                       # the CPU / contiguity checks
+    return t

@@ -3,7 +3,7 @@
 Each function mirrors one seam of the reference's inline PPO code (cited per function) and takes
 CUDA (=HIP) ``torch`` tensors only: torch is plumbing here (device memory + the current stream), the
 computation is the HIP kernels.  Passing a CPU tensor raises; there is no CPU fallback in this module.  The one exception is
-``LSTMSeq`` / ``lstm_seq`` and ``TrXLMemoryAttention``, which take CPU tensors to the host twins (cleanrl_amd/host_ops.py) on
+``LSTMSeq`` / ``lstm_seq``, ``TrXLMemoryAttention`` and ``ImpalaTrunk`` / ``impala_trunk``, which take CPU tensors to the host twins (cleanrl_amd/host_ops.py) on
 purpose: the agent's host path and the tests run the same arithmetic as the device kernels.
 """
 from __future__ import annotations
@@ -19,7 +19,8 @@ __all__ = [
     "gae", "categorical_sample", "categorical_logprob_entropy", "normal_sample", "normal_logprob_entropy",
     "ppo_loss_categorical", "ppo_loss_normal", "obs_u8_to_f32", "obs_nchw_to_nhwc_u8", "clip_adam_", "PPOLossCategorical", "PPOLossNormal",
     "CategoricalLogProbEntropy", "NormalLogProbEntropy", "LOSS_SCALAR_NAMES", "lstm_seq_forward", "lstm_seq_backward", "LSTMSeq",
-    "lstm_seq", "lstm_seq_dw_hh", "trxl_attn_forward", "trxl_attn_backward", "TrXLMemoryAttention", "trxl_memory_attention",
+    "lstm_seq", "lstm_seq_dw_hh", "impala_forward", "impala_backward", "impala_maxpool_forward", "impala_maxpool_backward",
+    "ImpalaTrunk", "impala_trunk", "impala_param_shapes", "trxl_attn_forward", "trxl_attn_backward", "TrXLMemoryAttention", "trxl_memory_attention",
 ]
 
 LOSS_SCALAR_NAMES = ("loss", "pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac")
@@ -1012,6 +1013,150 @@ def trxl_memory_attention(q, gamma, beta, memory, layer: int, ep, rows, pos, mas
     memory, ep, rows, pos, mask, pe = _trxl_inputs(memory, ep, rows, pos, mask, pe)
     u, _ = fwd(memory, layer, ep, rows, pos, mask, pe, gamma.detach().contiguous(), beta.detach().contiguous(), q.detach().contiguous())
     return u
+
+
+# ------------------------------------------------------------------------------------------- IMPALA-CNN trunk
+IMPALA_CHANNELS = (16, 32, 32)
+IMPALA_FRAME = (64, 64, 3)
+
+
+def impala_param_shapes():
+    """The 30 trunk parameters' shapes in state_dict order (per sequence: conv, res_block0.conv0 / conv1, res_block1.conv0 / conv1;
+    weight then bias)."""
+    shapes, cin = [], IMPALA_FRAME[2]
+    for c in IMPALA_CHANNELS:
+        for i in range(5):
+            ci = cin if i == 0 else c
+            shapes += [(c, ci, 3, 3), (c,)]
+        cin = c
+    return shapes
+
+
+def _impala_check(x, params):
+    if x.dim() != 4 or tuple(x.shape[1:]) != IMPALA_FRAME or x.shape[0] < 1:
+        raise ValueError(f"x: expected channels-last frames (B, 64, 64, 3), got {tuple(x.shape)}")
+    if len(params) != 30:
+        raise ValueError(f"params: expected the trunk's 30 weights and biases, got {len(params)}")
+    for i, (p, shp) in enumerate(zip(params, impala_param_shapes())):
+        if tuple(p.shape) != shp:
+            raise ValueError(f"params[{i}]: expected shape {shp}, got {tuple(p.shape)} (channels must be {list(IMPALA_CHANNELS)})")
+
+
+def _ptr_array(ts):
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def impala_forward(x, params):
+    """The IMPALA-CNN trunk (ppo_procgen.py:86-124 / ppg_procgen.py:123-165, three ConvSequences) on the HIP kernels of
+    csrc/impala.hip: x (B,64,64,3) f32 channels-last frames, params the 30 conv weights / biases in state_dict order.
+    Returns ``(y (B,8,8,32) channels-last, saved, argmax)``; the last two feed ``impala_backward``."""
+    lib = _lib.load()
+    _impala_check(x, params)
+    _chk(x, torch.float32, "x")
+    for i, p in enumerate(params):
+        _chk(p, torch.float32, f"params[{i}]")
+    B, dev = x.shape[0], x.device
+    y = torch.empty((B, 8, 8, 32), device=dev)
+    saved = torch.empty(int(lib.mi355ppo_impala_saved_floats(B)), device=dev)
+    arg = torch.empty(int(lib.mi355ppo_impala_argmax_bytes(B)), dtype=torch.uint8, device=dev)
+    nws = int(lib.mi355ppo_impala_workspace_bytes(B, 0))
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    with _on(dev):
+        st = lib.mi355ppo_impala_fwd_f32(_ptr(x), _ptr_array(params), _ptr(y), _ptr(saved), _ptr(arg), B, *IMPALA_FRAME, *IMPALA_CHANNELS,
+                                         _ptr(ws), nws, _stream(dev))
+    _lib.check(st, "mi355ppo_impala_fwd_f32")
+    return y, saved, arg
+
+
+def impala_backward(x, params, saved, arg, dy):
+    """Backward of ``impala_forward``: dy (B,8,8,32) channels-last -> the 30 parameter gradients (one flat buffer's views, written
+    by deterministic fixed-order folds); no input gradient."""
+    lib = _lib.load()
+    _impala_check(x, params)
+    B, dev = x.shape[0], x.device
+    _chk(dy, torch.float32, "dy", (B, 8, 8, 32))
+    _chk(saved, torch.float32, "saved", (int(lib.mi355ppo_impala_saved_floats(B)),))
+    _chk(arg, torch.uint8, "argmax", (int(lib.mi355ppo_impala_argmax_bytes(B)),))
+    flat = torch.empty(sum(p.numel() for p in params), device=dev)
+    grads, o = [], 0
+    for p in params:
+        grads.append(flat[o:o + p.numel()].view(p.shape))
+        o += p.numel()
+    nws = int(lib.mi355ppo_impala_workspace_bytes(B, 1))
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    with _on(dev):
+        st = lib.mi355ppo_impala_bwd_f32(_ptr(x), _ptr_array(params), _ptr(saved), _ptr(arg), _ptr(dy), _ptr_array(grads), B,
+                                         *IMPALA_FRAME, *IMPALA_CHANNELS, _ptr(ws), nws, _stream(dev))
+    _lib.check(st, "mi355ppo_impala_bwd_f32")
+    return grads
+
+
+def impala_maxpool_forward(x):
+    """The trunk's max pool (3, stride 2, pad 1) alone on channels-last x (B,H,W,C) -> (y, argmax bytes (B,H/2,W/2,C))."""
+    lib = _lib.load()
+    _chk(x, torch.float32, "x")
+    B, H, W, C = x.shape
+    y = torch.empty((B, H // 2, W // 2, C), device=x.device)
+    arg = torch.empty((B, H // 2, W // 2, C), dtype=torch.uint8, device=x.device)
+    with _on(x.device):
+        st = lib.mi355ppo_impala_maxpool_fwd_f32(_ptr(x), _ptr(y), _ptr(arg), B, H, W, C, _stream(x.device))
+    _lib.check(st, "mi355ppo_impala_maxpool_fwd_f32")
+    return y, arg
+
+
+def impala_maxpool_backward(dy, arg):
+    """Backward of ``impala_maxpool_forward``: dx (B,2Ho,2Wo,C)."""
+    lib = _lib.load()
+    _chk(dy, torch.float32, "dy")
+    B, Ho, Wo, C = dy.shape
+    _chk(arg, torch.uint8, "argmax", tuple(dy.shape))
+    dx = torch.empty((B, 2 * Ho, 2 * Wo, C), device=dy.device)
+    with _on(dy.device):
+        st = lib.mi355ppo_impala_maxpool_bwd_f32(_ptr(dy), _ptr(arg), _ptr(dx), B, 2 * Ho, 2 * Wo, C, _stream(dy.device))
+    _lib.check(st, "mi355ppo_impala_maxpool_bwd_f32")
+    return dx
+
+
+def _impala_impl(t):
+    """The trunk for ``t``'s device: the HIP kernels for CUDA tensors, the ``*_cpu`` twins (cleanrl_amd/host_ops.py) for CPU ones."""
+    if t.is_cuda:
+        return impala_forward, impala_backward
+    from . import host_ops
+
+    return host_ops.impala_forward, host_ops.impala_backward
+
+
+class ImpalaTrunk(torch.autograd.Function):
+    """Differentiable ``(x, *params) -> y``: the three ConvSequences of the IMPALA-CNN on channels-last frames x (B,64,64,3),
+    y (B,8,8,32) channels-last.  The backward returns the 30 parameter gradients and None for the frames (no input gradient
+    is computed).  The HIP kernels run for CUDA tensors, the host twins for CPU ones (same arithmetic)."""
+
+    @staticmethod
+    def forward(ctx, x, *params):
+        fwd, _ = _impala_impl(x)
+        xs = x.detach().contiguous()
+        ps = [p.detach().contiguous() for p in params]
+        _impala_check(xs, ps)
+        y, saved, arg = fwd(xs, ps)
+        ctx.save_for_backward(xs, saved, arg, *ps)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xs, saved, arg, *ps = ctx.saved_tensors
+        _, bwd = _impala_impl(xs)
+        grads = bwd(xs, ps, saved, arg, dy.contiguous())
+        return (None, *grads)
+
+
+def impala_trunk(x, params):
+    """``ImpalaTrunk.apply`` when a gradient is wanted, else the forward alone (the rollout step, the old-policy pass)."""
+    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        return ImpalaTrunk.apply(x, *params)
+    fwd, _ = _impala_impl(x)
+    ps = [p.detach().contiguous() for p in params]
+    _impala_check(x, ps)
+    return fwd(x.contiguous(), ps)[0]
 
 
 def synth_continuous_step(state, reset_state, At, Bm, w, noise, k: int, steps, horizon: float, action, obs_out, reward, done, k_base=None):

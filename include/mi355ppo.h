@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MI355PPO_VERSION 230 /* major*100 + minor*10 + patch.  The minor moves whenever an exported signature changes or an entry
+#define MI355PPO_VERSION 240 /* major*100 + minor*10 + patch.  The minor moves whenever an exported signature changes or an entry
                                   point is added (1.1: adv_mean_den / conv1_variant arguments of round 2; 1.2, 1.3: round 3;
                                   1.4: the *_cpu host-pointer twins; 1.5: mi355ppo_init; 1.6: round 4 -- the fused MLP family K7,
                                   mi355ppo_clip_adam_sched_f32; 1.7: mi355ppo_fc_heads_act_categorical_f32, mi355ppo_nature_packs_f32,
@@ -40,7 +40,8 @@ extern "C" {
                                   1.9: round 6 -- the kernel queries mi355ppo_fc_packed_kernel_f16x2, mi355ppo_fc_wgrad_kernel_f16x2, mi355ppo_cnn_conv_wgrad_kernel_f16x2;
                                   heads of up to 18 actions, a 4-byte-aligned critic row; 2.0: the peer-memory gradient exchange mi355ppo_dp_*; 2.1: the fused MLP family takes obs_dim <= 512, n_out <= 20;
                                   2.2: the done-masked LSTM sequence scans mi355ppo_lstm_seq_fwd_f32 / _bwd_f32 and their *_cpu twins;
-                                  2.3: the TrXL episodic-memory attention mi355ppo_trxl_attn_fwd_f32 / _bwd_f32 and their *_cpu twins);
+                                  2.3: the TrXL episodic-memory attention mi355ppo_trxl_attn_fwd_f32 / _bwd_f32 and their *_cpu twins;
+                                  2.4: the IMPALA-CNN trunk mi355ppo_impala_* (forward, backward, max pool, sizes) and the *_cpu twins);
                                   a binding must check major AND minor (cleanrl_amd/_lib.py does) */
 
 #if defined(__GNUC__)
@@ -430,6 +431,39 @@ MI355PPO_API int mi355ppo_trxl_attn_bwd_f32(const float* memory, int E, int T_ep
                                             int L, int D, int H, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * IMPALA  The IMPALA-CNN trunk of ppo_procgen.py / ppg_procgen.py (cleanrl/ppo_procgen.py:86-124, cleanrl/ppg_procgen.py:123-165):
+ * 3 x [conv3x3 -> max_pool2d(3, 2, 1) -> 2 residual blocks], channels [16, 32, 32], on 64x64x3 frames; the Flatten -> ReLU ->
+ * Linear tail stays with the caller.  Activations are channels-last f32 (B, H, W, C): x is the frames as K5
+ * (mi355ppo_obs_u8_to_f32) writes them, y the (B, 8, 8, 32) output -- NCHW order is y.permute(0, 3, 1, 2).  Exact f32 on
+ * v_mfma_f32_16x16x4_f32; orders, tie rule and layouts: csrc/impala_rows.h.
+ *   params    : host array of 30 pointers, the trunk's conv weights (C_out, C_in, 3, 3) and biases in state_dict order
+ *               (network.0.conv.weight, network.0.conv.bias, network.0.res_block0.conv0.weight, ...), any 4-byte offset  [in]
+ *   saved     : mi355ppo_impala_saved_floats(B) f32, the activations the backward reads (16-byte aligned)      [out / in]
+ *   argmax    : mi355ppo_impala_argmax_bytes(B) bytes, the pools' window-relative argmax                        [out / in]
+ *   workspace : mi355ppo_impala_workspace_bytes(B, backward) bytes, 256-byte aligned (packed weights, scratch planes,
+ *               weight-gradient partials)
+ * Only B > 0, H = W = 64, C = 3 and channels (ch0, ch1, ch2) = (16, 32, 32); anything else returns MI355PPO_EINVAL before
+ * any launch, with the outputs untouched.  The backward writes all 30 parameter gradients (grads: host array of 30 device
+ * pointers, written, not accumulated) and no input gradient.  Deterministic (weight gradients: fixed-order partials and a
+ * fixed-order fold, no atomics); forward results of one image do not depend on the batch.  No host synchronisation and no
+ * allocation: capturable.
+ */
+MI355PPO_API int64_t mi355ppo_impala_saved_floats(int B);
+MI355PPO_API int64_t mi355ppo_impala_argmax_bytes(int B);
+MI355PPO_API size_t mi355ppo_impala_workspace_bytes(int B, int backward);
+MI355PPO_API int mi355ppo_impala_fwd_f32(const float* x, const float* const* params, float* y, float* saved, uint8_t* argmax, int B,
+                                         int H, int W, int C, int ch0, int ch1, int ch2, void* workspace, size_t workspace_bytes,
+                                         void* stream);
+MI355PPO_API int mi355ppo_impala_bwd_f32(const float* x, const float* const* params, const float* saved, const uint8_t* argmax,
+                                         const float* dy, float* const* grads, int B, int H, int W, int C, int ch0, int ch1, int ch2,
+                                         void* workspace, size_t workspace_bytes, void* stream);
+/* The trunk's max pool alone (channels-last; only its three shapes: 64x64x16, 32x32x32, 16x16x32): y (B, H/2, W/2, C) and the
+ * argmax byte per output; the backward writes dx (B, H, W, C) from dy and the argmax. */
+MI355PPO_API int mi355ppo_impala_maxpool_fwd_f32(const float* x, float* y, uint8_t* argmax, int B, int H, int W, int C, void* stream);
+MI355PPO_API int mi355ppo_impala_maxpool_bwd_f32(const float* dy, const uint8_t* argmax, float* dx, int B, int H, int W, int C,
+                                                 void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Host-pointer twins (csrc/host_twins.hip) of the PPO-path entry points above: the same arguments minus `stream` and
  * `workspace`, every pointer a HOST pointer, the call returns when the result is written.  Same math by construction: the
  * row / element functions (GAE step, Categorical row, loss row terms, advantage statistics fold, Adam element, Philox stream)
@@ -493,6 +527,13 @@ MI355PPO_API int mi355ppo_trxl_attn_bwd_f32_cpu(const float* memory, int E, int 
                                                 const float* gamma, const float* beta, const float* q, const float* u,
                                                 const float* stats, const float* du, float* dq, float* dln_rows, float* dgamma,
                                                 float* dbeta, int B, int L, int D, int H);
+MI355PPO_API int mi355ppo_impala_fwd_f32_cpu(const float* x, const float* const* params, float* y, float* saved, uint8_t* argmax,
+                                             int B, int H, int W, int C, int ch0, int ch1, int ch2);
+MI355PPO_API int mi355ppo_impala_bwd_f32_cpu(const float* x, const float* const* params, const float* saved, const uint8_t* argmax,
+                                             const float* dy, float* const* grads, int B, int H, int W, int C, int ch0, int ch1,
+                                             int ch2);
+MI355PPO_API int mi355ppo_impala_maxpool_fwd_f32_cpu(const float* x, float* y, uint8_t* argmax, int B, int H, int W, int C);
+MI355PPO_API int mi355ppo_impala_maxpool_bwd_f32_cpu(const float* dy, const uint8_t* argmax, float* dx, int B, int H, int W, int C);
 
 /* ---------------------------------------------------------------------------------------------
  * FC   Linear(3136, 512) + ReLU of the NatureCNN (cleanrl/ppo_atari_multigpu.py:144-145) on the bf16 matrix pipe
