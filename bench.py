@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- env-steps/sec of the MI355X-native PPO actor-learner (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -16,7 +16,10 @@ device-resident generator, so inputs are already in HBM when the timed region st
 Weak scaling: every rank (one process per GPU, RCCL over xGMI) keeps 1024 envs; ``value`` is the whole-job
 env-steps/sec = N * 1024 * 128 * K / max-over-ranks(time).
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps, writes ``--dump-outputs`` and prints the line: ``value``, ``ms_per_step``, the
+GPU-timeline split ``phases_ms``, the configuration, the last step's loss and, for N > 1, the preflight every multi-rank run starts with.
+Everything else the line can carry is measured after the timed region and only with ``--full`` (each leg still switched off by its
+``--no-*`` option there); it never touches ``value``:
   ``roofline``      for the dominant HIP kernel of the path = the convolution / FC launch with the largest total time in
                     the timed region (KERNEL_INFO below names them; the uint8 gather + /255 of K5, bias, ReLU and
                     ReLU-backward passes are fused into them), timed live with HIP events on the learner's stream around each
@@ -31,7 +34,8 @@ The JSON line also carries
   ``kernels``       the same accounting for every conv launch shape, and GB/s for the GAE and fused-loss kernels
                     (latency-bound at this size);
   ``cpu_baseline``  the oracle's CPU port of the reference loop (oracle/cpu_ppo_port.py), rank 0, N=1 only,
-                    on a bounded sample (64 envs x 128 steps, >=1 iteration), on the box's host cores.
+                    on a bounded sample (64 envs x 128 steps, >=1 iteration), on the box's host cores;
+  ``pcie_inclusive``  the same learner fed by host envs (tools/host_env_bench.py), rank 0, N=1 only.
 """
 from __future__ import annotations
 
@@ -154,7 +158,11 @@ def parse():
                         "two ranks on one device).  Exercises the launcher, barrier, max-over-ranks timing and rank-0 JSON line")
     p.add_argument("--n-actions", type=int, default=4)
     p.add_argument("--seed", type=int, default=1)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed region, also measure what the headline figure does not need: the per-launch event brackets (roofline, "
+                        "kernels, hbm_frac, matrix_arithmetic, the HBM-regime K1 / K3 points, the stream probe), cpu_baseline and the PCIe-inclusive "
+                        "leg.  Without it a run sets up, warms up, times --steps, writes --dump-outputs and prints the line")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
     p.add_argument("--cpu-baseline-envs", type=int, default=64)
     p.add_argument("--cpu-baseline-full", choices=["auto", "on", "off"], default="auto",
                    help="how cpu_baseline.value is taken at the METRIC's configuration (1,024 envs x 128 steps, 16 updates of 32,768 rows) on this box's own "
@@ -162,12 +170,12 @@ def parse():
                         "minibatch update after one untimed), times its count: ~1 minute of CPU work.  on: ONE whole iteration (~5 minutes on the GPU box's "
                         "256 threads, ~3 on 8 cores; abandoned for the sample if the rollout alone exceeds 2 minutes).  off: whole iterations at "
                         "--cpu-baseline-envs envs (the rounds 1-5 sample; NOT the metric's configuration)")
-    p.add_argument("--no-kernel-timing", action="store_true", help="skip the HIP-event brackets (pure SPS run)")
+    p.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the HIP-event brackets")
     p.add_argument("--no-rollout-graphs", action="store_true", help="issue the rollout kernel by kernel instead of one hipGraph per step")
     p.add_argument("--rollout-steps-per-graph", type=int, default=0,
                    help="consecutive env steps captured into one hipGraph (0 = the whole rollout in one graph, the default: a replay "
                         "boundary costs ~8 us of GPU idle; 1 = a graph per step)")
-    p.add_argument("--no-pcie-inclusive", action="store_true", help="skip the host-env (PCIe-inclusive) leg after the timed region")
+    p.add_argument("--no-pcie-inclusive", action="store_true", help="with --full: skip the host-env (PCIe-inclusive) leg after the timed region")
     p.add_argument("--pcie-env-groups", type=int, default=4)
     p.add_argument("--update-graphs", action="store_true", help="(the default on one GPU; kept for old command lines)")
     p.add_argument("--no-update-graphs", action="store_true",
@@ -195,6 +203,8 @@ def parse():
         cli.num_steps = cfg["num_steps"]
     if cli.same_device and cli.backend != "gloo":
         p.error("--same-device needs --backend gloo (RCCL refuses two ranks on one device)")
+    if not cli.full:              # a plain run: nothing after the timed region but --dump-outputs and the line
+        cli.no_kernel_timing = cli.no_cpu_baseline = cli.no_pcie_inclusive = True
     return cli
 
 
@@ -754,7 +764,8 @@ def main():
                 "update": update_mode,
                 "diagnostics": "synchronous (one device synchronisation per iteration)" if cli.sync_metrics
                                else "read one iteration late (PPOLearner.update_async): the host runs an iteration ahead of the GPU",
-                "cnn": "(filled in below from the kernels that ran)" if learner.fused_cnn else "torch Conv2d (MIOpen)",
+                "cnn": ("fused HIP convolution / FC kernels (--full names the kernel of every launch)" if learner.fused_cnn
+                        else "torch Conv2d (MIOpen)"),
             },
             "final_loss": metrics["loss"],
         }
@@ -762,7 +773,7 @@ def main():
             out["collective_preflight"] = cli.collective_preflight
         if dumped is not None:
             out["dumped_outputs"] = {"dir": cli.dump_outputs, "elements": dumped}
-        if learner.fused_cnn:
+        if learner.fused_cnn and kernel_of:          # (filled by the event-bracket iterations)
             out["config"]["cnn"], out["matrix_arithmetic"] = describe_cnn(kernel_of, M)
         timed = phase_events[cli.warmup:cli.warmup + cli.steps]
         out["phases_ms"] = {"rollout_incl_gae": float(np.mean([e[0].elapsed_time(e[1]) for e in timed])),

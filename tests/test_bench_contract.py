@@ -164,6 +164,22 @@ def test_round_6_measurement_switches_exist(monkeypatch):
     assert abs(s["seconds"] - want) < 1e-9 and abs(s["sps"] - 64 / want) < 1e-6 and np.isfinite(s["final_loss"])
 
 
+def test_legs_after_the_timed_region_run_only_with_full(monkeypatch):
+    """A plain run does only what the headline figure needs: the event brackets, the CPU baseline and the host-env leg are off unless ``--full``
+    is given, and under ``--full`` each of them still follows its own ``--no-*`` option."""
+    bench = _load_bench(monkeypatch)
+    legs = lambda c: (c.no_kernel_timing, c.no_cpu_baseline, c.no_pcie_inclusive)          # noqa: E731
+    cli = bench.parse()
+    assert not cli.full and legs(cli) == (True, True, True)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    cli = bench.parse()
+    assert cli.full and legs(cli) == (False, False, False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline", "--no-pcie-inclusive"])
+    assert legs(bench.parse()) == (False, True, True)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-kernel-timing"])
+    assert legs(bench.parse()) == (True, False, False)
+
+
 def test_dump_outputs_writes_the_last_steps_arrays_within_the_budget(monkeypatch, tmp_path):
     """``--dump-outputs DIR``: one f32 / f64 ``.npy`` per output of the timed path, the same fixed sample of an array too long to keep whole
     from run to run, 64 MB at most in all."""

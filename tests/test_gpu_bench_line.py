@@ -14,8 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_line_says_what_ran_at_the_size_it_claims():
     env = {k: v for k, v in os.environ.items() if not k.startswith("MI355PPO_")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "B", "--steps", "1", "--warmup", "1", "--no-pcie-inclusive", "--cpu-baseline-envs", "4",
-           "--cpu-baseline-full", "off"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "B", "--steps", "1", "--warmup", "1", "--full", "--no-pcie-inclusive",
+           "--cpu-baseline-envs", "4", "--cpu-baseline-full", "off"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stdout[-3000:] + "\n" + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -39,3 +39,23 @@ def test_bench_line_says_what_ran_at_the_size_it_claims():
     cb = j["cpu_baseline"]
     # (config B, --cpu-baseline-full off: the small whole-iteration sample; the default line -- config C -- takes the bounded sample at the metric's shapes)
     assert cb["kind"] == "port" and cb["at_metric_config"] is False and cb["value"] > 0 and "cross_check_8_cores_port_value" in cb
+
+
+def test_plain_bench_line_carries_the_headline_alone():
+    """Without ``--full`` the run stops after the timed steps: the line has the headline fields and ``phases_ms``, and none of the legs that are
+    measured after the timed region (event brackets, HBM-regime points, stream probe, CPU baseline, host envs)."""
+    env = {k: v for k, v in os.environ.items() if not k.startswith("MI355PPO_")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "B", "--steps", "1", "--warmup", "1"]
+    out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
+    assert out.returncode == 0, out.stdout[-3000:] + "\n" + out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "phases_ms", "final_loss"):
+        assert k in j, k
+    assert j["dtype"] == "f32" and j["higher_is_better"] is True and j["unit"] == "env-steps/s" and j["value"] > 0
+    assert abs(j["value"] - 128 * 128 / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+    for k in ("roofline", "kernels", "hbm_frac", "matrix_arithmetic", "iteration_f32_equiv_TFLOPs", "hbm_stream_probe", "cpu_baseline",
+              "pcie_inclusive", "pcie_inclusive_sps"):
+        assert k not in j, k
+    assert "--full" in j["config"]["cnn"]

@@ -9,11 +9,11 @@ rm -rf $O; mkdir -p $O
 cd $R
 T0=$SECONDS
 (time timeout 600 python -m pytest tests/test_gpu_cnn.py tests/test_gpu_kernels.py -q) > $O/pytest_gpu_kernels.log 2>&1; echo "pytest rc=$? t=$((SECONDS-T0))"; tail -3 $O/pytest_gpu_kernels.log | cut -c1-200
-timeout 600 python bench.py > $O/bench_cfgC.json 2> $O/bench_cfgC.err; echo "bench C rc=$? t=$((SECONDS-T0))"; cut -c1-300 $O/bench_cfgC.json
+timeout 600 python bench.py --full > $O/bench_cfgC.json 2> $O/bench_cfgC.err; echo "bench C rc=$? t=$((SECONDS-T0))"; cut -c1-300 $O/bench_cfgC.json
 prof() {   # config
   c=$1
   cd /tmp; rm -rf /tmp/prof_$c
-  timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_$c -o bench -- python $R/bench.py --config $c --steps 3 --warmup 2 --no-cpu-baseline --no-pcie-inclusive > $O/prof_$c.log 2>&1; echo "prof $c rc=$? t=$((SECONDS-T0))"
+  timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/prof_$c -o bench -- python $R/bench.py --full --config $c --steps 3 --warmup 2 --no-cpu-baseline --no-pcie-inclusive > $O/prof_$c.log 2>&1; echo "prof $c rc=$? t=$((SECONDS-T0))"
   db=$(find /tmp/prof_$c -name '*.db' | head -1); [ -n "$db" ] && python $R/tools/rocpd_stats.py "$db" 80 > $O/kernel_stats_cfg$c.csv
   grep '^{' $O/prof_$c.log | tail -1 > $O/bench_cfg${c}_profiled.json
   rm -rf /tmp/prof_$c; cd $R
@@ -38,6 +38,6 @@ pmc_pass mem SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_VALU SQ_INSTS_S
 pmc_pass lds SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_INSTS_VALU_MFMA_MOPS_BF16 GRBM_GUI_ACTIVE
 rm -f $O/pmc_*.log
 for c in B D; do
-  timeout 300 python bench.py --config $c --no-cpu-baseline --no-pcie-inclusive > $O/bench_cfg$c.json 2> $O/bench_cfg$c.err; echo "bench $c rc=$? t=$((SECONDS-T0))"; cut -c1-200 $O/bench_cfg$c.json
+  timeout 300 python bench.py --full --config $c --no-cpu-baseline --no-pcie-inclusive > $O/bench_cfg$c.json 2> $O/bench_cfg$c.err; echo "bench $c rc=$? t=$((SECONDS-T0))"; cut -c1-200 $O/bench_cfg$c.json
   prof $c
 done

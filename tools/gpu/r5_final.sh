@@ -12,12 +12,12 @@ T0=$SECONDS
 if [ "${SKIP_TESTS:-0}" != 1 ]; then
 (time timeout 1500 python -m pytest tests -m gpu -q -p no:cacheprovider) > $O/pytest_gpu.log 2>&1; echo "pytest rc=$? t=$((SECONDS-T0))"; tail -6 $O/pytest_gpu.log | cut -c1-300
 fi
-(time timeout 900 python bench.py) > $O/bench_cfgC.json 2> $O/bench_cfgC.err; echo "bench C (default command) rc=$? t=$((SECONDS-T0))"; grep '^{' $O/bench_cfgC.json | cut -c1-400; grep real $O/bench_cfgC.err
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-pcie-inclusive > $O/bench_cfgC_driver_counts.json 2>/dev/null; grep '^{' $O/bench_cfgC_driver_counts.json | cut -c1-200
+(time timeout 900 python bench.py --full) > $O/bench_cfgC.json 2> $O/bench_cfgC.err; echo "bench C (all legs) rc=$? t=$((SECONDS-T0))"; grep '^{' $O/bench_cfgC.json | cut -c1-400; grep real $O/bench_cfgC.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-pcie-inclusive > $O/bench_cfgC_driver_counts.json 2>/dev/null; grep '^{' $O/bench_cfgC_driver_counts.json | cut -c1-200
 prof() {   # config
   c=$1
   cd /tmp; rm -rf /tmp/prof_$c
-  timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/prof_$c -o bench -- python $R/bench.py --config $c --steps 3 --warmup 2 --no-cpu-baseline --no-pcie-inclusive > $O/prof_$c.log 2>&1; echo "prof $c rc=$? t=$((SECONDS-T0))"
+  timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/prof_$c -o bench -- python $R/bench.py --full --config $c --steps 3 --warmup 2 --no-cpu-baseline --no-pcie-inclusive > $O/prof_$c.log 2>&1; echo "prof $c rc=$? t=$((SECONDS-T0))"
   db=$(find /tmp/prof_$c -name '*.db' | head -1); [ -n "$db" ] && python $R/tools/rocpd_stats.py "$db" 80 > $O/kernel_stats_cfg$c.csv
   grep '^{' $O/prof_$c.log | tail -1 > $O/bench_cfg${c}_profiled.json
   rm -rf /tmp/prof_$c; cd $R
@@ -56,7 +56,7 @@ pmc_pass mem SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_VALU SQ_INSTS_S
 pmc_pass lds SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_INSTS_VALU_MFMA_MOPS_F16 GRBM_GUI_ACTIVE
 rm -f $O/pmc_*.log
 for c in B D E; do
-  timeout 300 python bench.py --config $c --no-cpu-baseline --no-pcie-inclusive > $O/bench_cfg$c.json 2> $O/bench_cfg$c.err; echo "bench $c rc=$? t=$((SECONDS-T0))"; grep '^{' $O/bench_cfg$c.json | cut -c1-240
+  timeout 300 python bench.py --full --config $c --no-cpu-baseline --no-pcie-inclusive > $O/bench_cfg$c.json 2> $O/bench_cfg$c.err; echo "bench $c rc=$? t=$((SECONDS-T0))"; grep '^{' $O/bench_cfg$c.json | cut -c1-240
 done
 prof E
 for N in 1024 256; do

@@ -23,7 +23,7 @@ timeout 60 tools/conv_traffic 1024 4 2>&1 | grep '^{' | cut -c1-420
 (timeout 900 python -m pytest tests/test_gpu_cnn.py tests/test_gpu_kernels.py -q -p no:cacheprovider) > $O/pytest_cnn.log 2>&1; echo "pytest cnn rc=$? t=$((SECONDS-T0))"; tail -8 $O/pytest_cnn.log | cut -c1-300
 (timeout 1200 python -m pytest tests/test_gpu_learner.py -q -p no:cacheprovider -s) > $O/pytest_learner.log 2>&1; echo "pytest learner rc=$? t=$((SECONDS-T0))"; grep -E "passed|failed|config C|update [0-9]+:|values |capture" $O/pytest_learner.log | tail -30 | cut -c1-400
 for sp in bf16x3 f16x2 bf16x3 f16x2; do
-  MI355PPO_SPLIT=$sp timeout 300 python bench.py --steps 6 --warmup 3 --no-cpu-baseline --no-pcie-inclusive 2> $O/bench_$sp.err | grep '^{' | python -c "
+  MI355PPO_SPLIT=$sp timeout 300 python bench.py --full --steps 6 --warmup 3 --no-cpu-baseline --no-pcie-inclusive 2> $O/bench_$sp.err | grep '^{' | python -c "
 import sys, json
 for l in sys.stdin:
     d = json.loads(l); r = d.get('roofline', {})
