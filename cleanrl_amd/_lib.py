@@ -169,9 +169,29 @@ SIGNATURES = {
     "mi355ppo_impala_bwd_f32_cpu": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "mi355ppo_impala_maxpool_fwd_f32_cpu": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int]),
     "mi355ppo_impala_maxpool_bwd_f32_cpu": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int]),
+    # PQN (ABI 2.5)
+    "mi355ppo_pqn_egreedy_f32": (c_int, [_P, _P, _P, c_double, _P, _P, _P, c_int, c_int, _P]),
+    "mi355ppo_pqn_egreedy_f32_cpu": (c_int, [_P, _P, _P, c_double, _P, _P, _P, c_int, c_int]),
+    "mi355ppo_pqn_qlambda_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_double, c_double, _P]),
+    "mi355ppo_pqn_qlambda_f32_cpu": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_double, c_double]),
+    "mi355ppo_pqn_td_loss_fwd_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int64, _P]),
+    "mi355ppo_pqn_td_loss_fwd_bwd_f32_cpu": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int64]),
+    "mi355ppo_pqn_mlp_fwd_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
+    "mi355ppo_pqn_mlp_fwd_f32_cpu": (c_int, [_P, _P, _P, c_int, c_int, c_int]),
+    "mi355ppo_pqn_mlp_act_f32": (c_int, [_P, _P, _P, _P, c_double, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "mi355ppo_pqn_mlp_act_f32_cpu": (c_int, [_P, _P, _P, _P, c_double, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int]),
+    "mi355ppo_pqn_mlp_td_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mi355ppo_pqn_mlp_td_fwd_bwd_f32": (c_int, [_P, c_int64, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "mi355ppo_pqn_mlp_td_fwd_bwd_f32_cpu": (c_int, [_P, c_int64, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int]),
+    "mi355ppo_radam_schedule_f32": (c_int, [c_double, c_double, c_double, c_int64, _P]),
+    "mi355ppo_clip_radam_workspace_bytes": (c_size_t, [c_int64]),
+    "mi355ppo_clip_radam_f32": (c_int, [_P, _P, _P, _P, c_int64, c_double, c_double, c_double, c_double, c_double, c_int64, _P, _P, c_size_t,
+                                        _P]),
+    "mi355ppo_clip_radam_sched_f32": (c_int, [_P, _P, _P, _P, c_int64, c_double, c_double, c_double, c_double, _P, _P, _P, c_size_t, _P]),
+    "mi355ppo_clip_radam_f32_cpu": (c_int, [_P, _P, _P, _P, c_int64, c_double, c_double, c_double, c_double, c_double, c_int64, _P]),
 }
 
-ABI_VERSION = 240       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)
+ABI_VERSION = 250       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)
 
 _lib = None
 

@@ -1055,3 +1055,52 @@ class TrXLAgent(nn.Module):
     def reconstruct_observation(self):
         x = self.transposed_cnn(self.x)
         return x.permute((0, 2, 3, 1))
+
+
+# ------------------------------------------------------------------------------------------- PQN (pqn.py, pqn_atari_envpool.py)
+class QNetwork(nn.Module):
+    """pqn.py's ``QNetwork``: Linear -> LayerNorm(120) -> ReLU -> Linear -> LayerNorm(84) -> ReLU -> Linear, built in the reference's
+    order (``layer_init``: orthogonal std sqrt(2), bias 0), so a seed gives the reference's weights and ``parameters()`` order.  The
+    learner runs it through the fused kernels on the flat parameters (``MI355PPO_PQN=fused``) or as this module (``torch``)."""
+
+    def __init__(self, env):
+        super().__init__()
+        self.network = nn.Sequential(
+            layer_init(nn.Linear(np.array(env.single_observation_space.shape).prod(), 120)),
+            nn.LayerNorm(120),
+            nn.ReLU(),
+            layer_init(nn.Linear(120, 84)),
+            nn.LayerNorm(84),
+            nn.ReLU(),
+            layer_init(nn.Linear(84, env.single_action_space.n)),
+        )
+
+    def forward(self, x):
+        return self.network(x)
+
+
+class AtariQNetwork(nn.Module):
+    """pqn_atari_envpool.py's ``QNetwork``: the NatureCNN with LayerNorm after every layer, on ``x / 255.0``, built in the
+    reference's order.  It stays torch on every backend (MIOpen convolutions, ATen LayerNorm); the fused backend takes its ``q``."""
+
+    def __init__(self, env):
+        super().__init__()
+        self.network = nn.Sequential(
+            layer_init(nn.Conv2d(4, 32, 8, stride=4)),
+            nn.LayerNorm([32, 20, 20]),
+            nn.ReLU(),
+            layer_init(nn.Conv2d(32, 64, 4, stride=2)),
+            nn.LayerNorm([64, 9, 9]),
+            nn.ReLU(),
+            layer_init(nn.Conv2d(64, 64, 3, stride=1)),
+            nn.LayerNorm([64, 7, 7]),
+            nn.ReLU(),
+            nn.Flatten(),
+            layer_init(nn.Linear(3136, 512)),
+            nn.LayerNorm(512),
+            nn.ReLU(),
+            layer_init(nn.Linear(512, env.single_action_space.n)),
+        )
+
+    def forward(self, x):
+        return self.network(x / 255.0)

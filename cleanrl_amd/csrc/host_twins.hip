@@ -18,6 +18,7 @@
 #include "lstm_rows.h"
 #include "trxl_rows.h"
 #include "impala_rows.h"
+#include "pqn_rows.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -999,5 +1000,208 @@ extern "C" MI355PPO_API int mi355ppo_impala_maxpool_bwd_f32_cpu(const float* dy,
     MI355_REQUIRE(imp_pool_shape_ok(B, H, W, C), MI355PPO_EINVAL, "%s: B=%d %dx%dx%d (only the trunk's 64x64x16, 32x32x32, 16x16x32)",
                   fn, B, H, W, C);
     imp_pool_bwd_host(dy, argmax, dx, B, H, C);
+    return MI355PPO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ PQN (pqn.hip)
+// The device's row functions (pqn_rows.h) and its fold orders (kPqnFold slots, kPqnRows-row partials, the sum-of-squares
+// workgroups), run serially: every output equals the device's bit for bit.
+namespace {
+
+void pqn_td_scalars_cpu(const std::vector<float>& old, const std::vector<float>& sq, int M, float* scalars) {
+    double to = 0.0, ts = 0.0;
+    for (int t = 0; t < kPqnFold; ++t) {
+        double so = 0.0, ss = 0.0;
+        for (int k = t; k < M; k += kPqnFold) {
+            so += (double)old[k];
+            ss += (double)sq[k];
+        }
+        to += so;
+        ts += ss;
+    }
+    scalars[0] = (float)(ts / (double)M);
+    scalars[1] = (float)(to / (double)M);
+}
+
+inline int64_t pqn_clamp_index_cpu(int64_t i, int64_t B) { return i < 0 ? 0 : (i >= B ? B - 1 : i); }
+
+}  // namespace
+
+extern "C" MI355PPO_API int mi355ppo_pqn_egreedy_f32_cpu(const float* q, const int64_t* random_actions, const float* u, double epsilon,
+                                                        float* actions_out, float* values_out, int64_t* action_i64_out, int N, int A) {
+    const char* fn = "mi355ppo_pqn_egreedy_f32_cpu";
+    MI355_REQUIRE(q && random_actions && u && actions_out && values_out, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(N > 0 && A > 0, MI355PPO_EINVAL, "%s: N=%d A=%d must be positive", fn, N, A);
+    const float eps = (float)epsilon;
+    for (int r = 0; r < N; ++r) {
+        float v;
+        const int64_t a = pqn_egreedy(q + (int64_t)r * A, 1, A, random_actions[r], u[r], eps, &v);
+        actions_out[r] = (float)a;
+        values_out[r] = v;
+        if (action_i64_out) action_i64_out[r] = a;
+    }
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_pqn_qlambda_f32_cpu(const float* rewards, const float* dones, const float* values, const float* next_done,
+                                                        const float* next_q, float* returns, int T, int N, int A, double gamma, double q_lambda) {
+    const char* fn = "mi355ppo_pqn_qlambda_f32_cpu";
+    MI355_REQUIRE(rewards && dones && values && next_done && next_q && returns, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(T > 0 && N > 0 && A > 0, MI355PPO_EINVAL, "%s: T=%d N=%d A=%d must be positive", fn, T, N, A);
+    const float g = (float)gamma, lam = (float)q_lambda, oml = (float)(1.0 - q_lambda);
+    for (int n = 0; n < N; ++n) {
+        const float* nq = next_q + (int64_t)n * A;
+        int64_t off = (int64_t)(T - 1) * N + n;
+        float ret = pqn_qlambda_last(rewards[off], nq[pqn_argmax(nq, 1, A)], next_done[n], g);
+        returns[off] = ret;
+        for (int t = T - 2; t >= 0; --t) {
+            const int64_t o1 = off;
+            off -= N;
+            ret = pqn_qlambda_step(rewards[off], ret, values[o1], dones[o1], g, lam, oml);
+            returns[off] = ret;
+        }
+    }
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_pqn_td_loss_fwd_bwd_f32_cpu(const float* q, const int64_t* mb_inds, const float* b_actions,
+                                                                const float* b_returns, float* dq, float* scalars_out, int M, int A, int64_t B) {
+    const char* fn = "mi355ppo_pqn_td_loss_fwd_bwd_f32_cpu";
+    MI355_REQUIRE(q && mb_inds && b_actions && b_returns && dq && scalars_out, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(M > 0 && A > 0 && B > 0, MI355PPO_EINVAL, "%s: M=%d A=%d B=%lld must be positive", fn, M, A, (long long)B);
+    const float norm = (float)(2.0 / (double)M);
+    std::vector<float> old(M), sq(M);
+    for (int r = 0; r < M; ++r) {
+        const int64_t i = pqn_clamp_index_cpu(mb_inds[r], B);
+        old[r] = pqn_td_row(q + (int64_t)r * A, 1, A, b_actions[i], b_returns[i], norm, dq + (int64_t)r * A, 1, &sq[r]);
+    }
+    pqn_td_scalars_cpu(old, sq, M, scalars_out);
+    return MI355PPO_OK;
+}
+
+static int pqn_mlp_shape_cpu(const char* fn, int N, int O, int A) {
+    MI355_REQUIRE(N > 0 && O > 0 && O <= kPqnMaxObs && A > 0 && A <= kPqnMaxA, MI355PPO_EINVAL,
+                  "%s: rows=%d obs_dim=%d n_actions=%d: the PQN MLP takes 1 <= obs_dim <= %d, 1 <= n_actions <= %d", fn, N, O, A, kPqnMaxObs,
+                  kPqnMaxA);
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_pqn_mlp_fwd_f32_cpu(const float* obs, const float* params, float* q_out, int N, int O, int A) {
+    const char* fn = "mi355ppo_pqn_mlp_fwd_f32_cpu";
+    MI355_REQUIRE(obs && params && q_out, MI355PPO_EINVAL, "%s: null pointer", fn);
+    if (int rc = pqn_mlp_shape_cpu(fn, N, O, A)) return rc;
+    const PqnNet net = pqn_net(params, O, A);
+    float h1[kPqnH1], h2[kPqnH2], rstd[2];
+    for (int r = 0; r < N; ++r) pqn_row_forward(net, obs + (int64_t)r * O, 1, h1, h1, h2, h2, 1, q_out + (int64_t)r * A, 1, rstd);
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_pqn_mlp_act_f32_cpu(const float* obs, const float* params, const int64_t* random_actions, const float* u,
+                                                        double epsilon, float* actions_out, float* values_out, int64_t* action_i64_out,
+                                                        float* obs_row_out, const float* done_in, float* done_row_out, int N, int O, int A) {
+    const char* fn = "mi355ppo_pqn_mlp_act_f32_cpu";
+    MI355_REQUIRE(obs && params && random_actions && u && actions_out && values_out && (!done_row_out || done_in), MI355PPO_EINVAL,
+                  "%s: null pointer", fn);
+    if (int rc = pqn_mlp_shape_cpu(fn, N, O, A)) return rc;
+    const PqnNet net = pqn_net(params, O, A);
+    const float eps = (float)epsilon;
+    float h1[kPqnH1], h2[kPqnH2], q[kPqnMaxA], rstd[2];
+    for (int r = 0; r < N; ++r) {
+        const float* x = obs + (int64_t)r * O;
+        pqn_row_forward(net, x, 1, h1, h1, h2, h2, 1, q, 1, rstd);
+        float v;
+        const int64_t a = pqn_egreedy(q, 1, A, random_actions[r], u[r], eps, &v);
+        actions_out[r] = (float)a;
+        values_out[r] = v;
+        if (action_i64_out) action_i64_out[r] = a;
+        if (obs_row_out) memcpy(obs_row_out + (int64_t)r * O, x, sizeof(float) * O);
+        if (done_row_out) done_row_out[r] = done_in[r];
+    }
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_pqn_mlp_td_fwd_bwd_f32_cpu(const float* b_obs, int64_t B, const int64_t* mb_inds, const float* params,
+                                                               const float* b_actions, const float* b_returns, float* grads, float* scalars_out,
+                                                               int M, int O, int A) {
+    const char* fn = "mi355ppo_pqn_mlp_td_fwd_bwd_f32_cpu";
+    MI355_REQUIRE(b_obs && mb_inds && params && b_actions && b_returns && grads && scalars_out, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(B > 0, MI355PPO_EINVAL, "%s: B=%lld must be positive", fn, (long long)B);
+    if (int rc = pqn_mlp_shape_cpu(fn, M, O, A)) return rc;
+    const PqnNet net = pqn_net(params, O, A);
+    const PqnUnits U = pqn_units(O, A);
+    const int64_t P = pqn_param_count(O, A);
+    const float norm = (float)(2.0 / (double)M);
+    // the device's row-interleaved workspace, unit-major with stride M (the layout does not change any value)
+    std::vector<float> ws((size_t)U.total * M);
+    std::vector<float> old(M), sq(M);
+    for (int r = 0; r < M; ++r) {
+        const int64_t i = pqn_clamp_index_cpu(mb_inds[r], B);
+        float* w = ws.data() + r;
+        for (int k = 0; k < O; ++k) w[(int64_t)(U.x + k) * M] = b_obs[i * O + k];
+        float rstd[2];
+        float* xh1 = w + (int64_t)U.xh1 * M;
+        float* a1 = w + (int64_t)U.a1 * M;
+        float* xh2 = w + (int64_t)U.xh2 * M;
+        float* a2 = w + (int64_t)U.a2 * M;
+        float* dq = w + (int64_t)U.dq * M;
+        pqn_row_forward(net, w + (int64_t)U.x * M, M, xh1, a1, xh2, a2, M, dq, M, rstd);
+        old[r] = pqn_td_row(dq, M, A, b_actions[i], b_returns[i], norm, dq, M, &sq[r]);
+        pqn_row_backward(net, dq, M, xh1, a1, xh2, a2, rstd, w + (int64_t)U.dy1 * M, w + (int64_t)U.dz1 * M, w + (int64_t)U.dy2 * M,
+                         w + (int64_t)U.dz2 * M, M);
+    }
+    const int nblk = (M + kPqnRows - 1) / kPqnRows;
+    for (int64_t e = 0; e < P; ++e) {
+        int u1, u2;
+        pqn_grad_units(e, O, A, &u1, &u2);
+        const float* p1 = ws.data() + (int64_t)u1 * M;
+        const float* p2 = u2 < 0 ? nullptr : ws.data() + (int64_t)u2 * M;
+        float g = 0.0f;
+        for (int b = 0; b < nblk; ++b) {
+            const int r0 = b * kPqnRows, r1 = (r0 + kPqnRows < M) ? r0 + kPqnRows : M;
+            float acc = 0.0f;
+            if (p2)
+                for (int k = r0; k < r1; ++k) acc = acc + p1[k] * p2[k];
+            else
+                for (int k = r0; k < r1; ++k) acc = acc + p1[k];
+            g = g + acc;
+        }
+        grads[e] = g;
+    }
+    pqn_td_scalars_cpu(old, sq, M, scalars_out);
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_clip_radam_f32_cpu(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                                       double max_grad_norm, double lr, double beta1, double beta2, double eps, int64_t step,
+                                                       float* total_norm_out) {
+    const char* fn = "mi355ppo_clip_radam_f32_cpu";
+    MI355_REQUIRE(params && grads && exp_avg && exp_avg_sq, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(n > 0, MI355PPO_EINVAL, "%s: n=%lld must be > 0", fn, (long long)n);
+    float c[kPqnSched];
+    if (int rc = mi355ppo_radam_schedule_f32(lr, beta1, beta2, step, c)) return rc;
+    const int G = pqn_sumsq_blocks(n);
+    double s = 0.0;
+    for (int b = 0; b < G; ++b) {
+        double part = 0.0;
+        for (int t = 0; t < kPqnFold; ++t) {
+            double slot = 0.0;
+            for (int64_t i = (int64_t)b * 256 + t; i < n; i += (int64_t)G * 256) {
+                const double a = (double)grads[i];
+                slot += a * a;
+            }
+            part += slot;
+        }
+        s += part;
+    }
+    if (total_norm_out) *total_norm_out = (float)sqrt(s);
+    RAdamParams R;
+    R.max_norm = (float)max_grad_norm;
+    R.w1 = (float)(1.0 - beta1);
+    R.beta2 = (float)beta2;
+    R.w2 = (float)(1.0 - beta2);
+    R.eps = (float)eps;
+    R.nblocks = G;
+    const float coef = pqn_clip_coef(s, R.max_norm);
+    for (int64_t i = 0; i < n; ++i) pqn_radam_elem(params[i], grads[i], exp_avg[i], exp_avg_sq[i], coef, R, c);
     return MI355PPO_OK;
 }

@@ -342,3 +342,88 @@ def impala_maxpool_backward(dy, arg):
 def _p_t(t):
     _p(t)                       # the CPU / contiguity checks
     return t
+
+
+# ------------------------------------------------------------------------------------------- PQN twins (csrc/pqn.hip)
+def _i64(t):
+    return t.detach().to(torch.int64).contiguous()
+
+
+def pqn_param_count(obs_dim: int, n_actions: int) -> int:
+    return 120 * obs_dim + 360 + 84 * 120 + 252 + 85 * n_actions
+
+
+def pqn_egreedy(q, random_actions, u, epsilon, actions_out, values_out, action_i64_out=None):
+    """``mi355ppo_pqn_egreedy_f32_cpu``: the e-greedy row of pqn.py's rollout (see ops.pqn_egreedy); writes the storage rows in place."""
+    N, A = q.shape
+    q, rnd, uu = _f32(q), _i64(random_actions), _f32(u)
+    _lib.check(_lib.load().mi355ppo_pqn_egreedy_f32_cpu(_p(q), _p(rnd), _p(uu), float(epsilon), _p(actions_out), _p(values_out),
+                                                        _p(action_i64_out), N, A), "mi355ppo_pqn_egreedy_f32_cpu")
+    return actions_out, values_out
+
+
+def pqn_qlambda(rewards, dones, values, next_done, next_q, gamma, q_lambda, returns=None):
+    T, N = rewards.shape
+    A = next_q.shape[-1]
+    r, d, v, nd, nq = _f32(rewards), _f32(dones), _f32(values), _f32(next_done).reshape(-1), _f32(next_q)
+    returns = torch.empty_like(r) if returns is None else returns
+    _lib.check(_lib.load().mi355ppo_pqn_qlambda_f32_cpu(_p(r), _p(d), _p(v), _p(nd), _p(nq), _p(returns), T, N, A, float(gamma),
+                                                        float(q_lambda)), "mi355ppo_pqn_qlambda_f32_cpu")
+    return returns
+
+
+def pqn_td_loss(q, mb_inds, b_actions, b_returns, dq=None, scalars=None):
+    M, A = q.shape
+    qq, inds, ba, br = _f32(q), _i64(mb_inds), _f32(b_actions).reshape(-1), _f32(b_returns).reshape(-1)
+    dq = torch.empty_like(qq) if dq is None else dq
+    scalars = torch.empty(2) if scalars is None else scalars
+    _lib.check(_lib.load().mi355ppo_pqn_td_loss_fwd_bwd_f32_cpu(_p(qq), _p(inds), _p(ba), _p(br), _p(dq), _p(scalars), M, A, ba.numel()),
+               "mi355ppo_pqn_td_loss_fwd_bwd_f32_cpu")
+    return dq, scalars
+
+
+def pqn_mlp_forward(obs, params, n_actions, q_out=None):
+    N, O = obs.shape
+    x, p = _f32(obs), _f32(params)
+    assert p.numel() == pqn_param_count(O, n_actions), "flat parameters of another shape"
+    q_out = torch.empty((N, n_actions)) if q_out is None else q_out
+    _lib.check(_lib.load().mi355ppo_pqn_mlp_fwd_f32_cpu(_p(x), _p(p), _p(q_out), N, O, int(n_actions)), "mi355ppo_pqn_mlp_fwd_f32_cpu")
+    return q_out
+
+
+def pqn_mlp_act(obs, params, n_actions, random_actions, u, epsilon, actions_out, values_out, action_i64_out=None, obs_row_out=None,
+                done_in=None, done_row_out=None):
+    N, O = obs.shape
+    x, p, rnd, uu = _f32(obs), _f32(params), _i64(random_actions), _f32(u)
+    assert p.numel() == pqn_param_count(O, n_actions), "flat parameters of another shape"
+    din = None if done_in is None else _f32(done_in)
+    _lib.check(_lib.load().mi355ppo_pqn_mlp_act_f32_cpu(_p(x), _p(p), _p(rnd), _p(uu), float(epsilon), _p(actions_out), _p(values_out),
+                                                        _p(action_i64_out), _p(obs_row_out), _p(din), _p(done_row_out), N, O, int(n_actions)),
+               "mi355ppo_pqn_mlp_act_f32_cpu")
+    return actions_out, values_out
+
+
+def pqn_mlp_td_fwd_bwd(b_obs, mb_inds, params, b_actions, b_returns, grads, n_actions, scalars=None):
+    B, O = b_obs.shape
+    x, p, inds = _f32(b_obs), _f32(params), _i64(mb_inds)
+    assert p.numel() == pqn_param_count(O, n_actions), "flat parameters of another shape"
+    ba, br = _f32(b_actions).reshape(-1), _f32(b_returns).reshape(-1)
+    scalars = torch.empty(2) if scalars is None else scalars
+    _lib.check(_lib.load().mi355ppo_pqn_mlp_td_fwd_bwd_f32_cpu(_p(x), B, _p(inds), _p(p), _p(ba), _p(br), _p(grads), _p(scalars),
+                                                               inds.numel(), O, int(n_actions)), "mi355ppo_pqn_mlp_td_fwd_bwd_f32_cpu")
+    return scalars
+
+
+def radam_schedule(lr, step, beta1=0.9, beta2=0.999):
+    out = (ctypes.c_float * 8)()
+    _lib.check(_lib.load().mi355ppo_radam_schedule_f32(float(lr), float(beta1), float(beta2), int(step), out), "mi355ppo_radam_schedule_f32")
+    return [float(x) for x in out]
+
+
+def clip_radam_(params, grads, exp_avg, exp_avg_sq, step, lr, max_grad_norm, beta1=0.9, beta2=0.999, eps=1e-8, total_norm_out=None):
+    """``mi355ppo_clip_radam_f32_cpu``: clip_grad_norm_ + RAdam step ``step`` on flat CPU buffers (in place; zeroes grads)."""
+    total = torch.empty(1) if total_norm_out is None else total_norm_out
+    _lib.check(_lib.load().mi355ppo_clip_radam_f32_cpu(_p(params), _p(grads), _p(exp_avg), _p(exp_avg_sq), params.numel(), float(max_grad_norm),
+                                                       float(lr), float(beta1), float(beta2), float(eps), int(step), _p(total)),
+               "mi355ppo_clip_radam_f32_cpu")
+    return total

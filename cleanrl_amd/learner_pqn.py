@@ -1,0 +1,224 @@
+"""The rollout, Q(lambda) targets and Q-network update of ``pqn.py`` and ``pqn_atari_envpool.py`` (reference: cleanrl/pqn.py and
+cleanrl/pqn_atari_envpool.py, the main loop after ``QNetwork``).
+
+====================================================  ==============================================================
+reference                                              here
+====================================================  ==============================================================
+``optim.RAdam``, storage setup, ``next_obs`` /         ``PQNLearner.__init__`` / ``reset``
+``next_done``
+learning-rate annealing                                ``start_iteration``
+``global_step``, ``obs`` / ``dones`` stores,           ``act``: ``torch`` -- the reference's ops; ``fused`` -- one launch
+``linear_schedule``, ``randint``, ``q_network``,       (``mi355ppo_pqn_mlp_act_f32``) for pqn.py, the torch network +
+argmax, ``values``, ``rand < epsilon``, ``where``,     ``mi355ppo_pqn_egreedy_f32`` for the Atari network
+``actions`` store
+``envs.step`` results -> ``rewards``, ``next_obs``,    ``observe``
+``next_done``
+``# Compute Q(lambda) targets``                        ``finish_rollout``: ``mi355ppo_pqn_qlambda_f32`` on ``fused``
+flatten, ``np.random.shuffle``, minibatch gather,      ``update``: ``fused`` -- ``mi355ppo_pqn_mlp_td_fwd_bwd_f32`` (pqn.py) or
+``mse_loss``, ``backward``, ``clip_grad_norm_``,       the torch network + ``mi355ppo_pqn_td_loss_fwd_bwd_f32`` +
+``RAdam.step``                                         ``q.backward(dq)`` (Atari), then ``mi355ppo_clip_radam_f32`` on the
+                                                       flat buffers (``FlatParams``)
+``losses/td_loss``, ``losses/q_values``                the dict ``update`` returns (last minibatch)
+====================================================  ==============================================================
+
+Backend: ``MI355PPO_PQN=torch|fused``; the default is ``fused`` on a CUDA device and ``torch`` on the CPU, where ``fused`` runs the
+host twins (cleanrl_amd/host_ops.py).  Both draw the reference's random stream: ``torch.randint(0, A, (N,))`` and then
+``torch.rand((N,))`` on the CPU default generator every step, and ``np.random.shuffle`` for the minibatches, so a fused run takes
+the reference's actions for a seed as long as the greedy actions agree.
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+import torch.optim as optim
+
+from . import host_ops, ops
+from .flat import FlatParams
+
+BACKENDS = ("torch", "fused")
+
+
+def pqn_backend(device) -> str:
+    b = os.environ.get("MI355PPO_PQN", "").strip().lower()
+    if not b:
+        return "fused" if torch.device(device).type == "cuda" else "torch"
+    if b not in BACKENDS:
+        raise ValueError(f"MI355PPO_PQN={b!r}: expected one of {BACKENDS}")
+    return b
+
+
+def linear_schedule(start_e: float, end_e: float, duration: int, t: int):
+    """pqn.py's epsilon schedule (Python doubles)."""
+    slope = (end_e - start_e) / duration
+    return max(slope * t + start_e, end_e)
+
+
+class PQNLearner:
+    def __init__(self, q_network: nn.Module, args, obs_shape, n_actions: int, num_envs: int, device, mlp: bool = True, backend=None):
+        self.net, self.args, self.device = q_network, args, torch.device(device)
+        self.backend = pqn_backend(self.device) if backend is None else backend
+        if self.backend not in BACKENDS:
+            raise ValueError(f"PQN backend {self.backend!r}: expected one of {BACKENDS}")
+        self.N, self.T, self.A = int(num_envs), int(args.num_steps), int(n_actions)
+        self.obs_shape, self.mlp = tuple(obs_shape), bool(mlp)
+        self.fused = self.backend == "fused"
+        self.g = ops if self.device.type == "cuda" else host_ops
+        if self.fused and self.mlp:
+            O = int(np.prod(self.obs_shape))
+            if not (1 <= O <= ops.PQN_MAX_OBS and 1 <= self.A <= ops.PQN_MAX_ACTIONS):
+                raise ValueError(f"MI355PPO_PQN=fused: the fused QNetwork takes obs_dim <= {ops.PQN_MAX_OBS} and <= {ops.PQN_MAX_ACTIONS} "
+                                 f"actions, not {O} / {self.A}; use MI355PPO_PQN=torch")
+        if self.fused:
+            self.flat = FlatParams(q_network)
+            self.optimizer = None
+        else:
+            self.flat = None
+            self.optimizer = optim.RAdam(q_network.parameters(), lr=args.learning_rate)
+        dev, T, N = self.device, self.T, self.N
+        self.obs = torch.zeros((T, N) + self.obs_shape).to(dev)
+        self.actions = torch.zeros((T, N)).to(dev)
+        self.rewards = torch.zeros((T, N)).to(dev)
+        self.dones = torch.zeros((T, N)).to(dev)
+        self.values = torch.zeros((T, N)).to(dev)
+        self.returns = None
+        self.global_step = 0
+        self.lr = float(args.learning_rate)
+        self.epsilon = float(args.start_e)
+        self.next_obs = self.next_done = None
+        if self.fused:
+            pin = dev.type == "cuda"
+            self._rnd_host = torch.zeros(N, dtype=torch.int64)
+            self._u_host = torch.zeros(N, dtype=torch.float32)
+            if pin:                                             # the step's draws reach the device through pinned staging
+                self._rnd_host, self._u_host = self._rnd_host.pin_memory(), self._u_host.pin_memory()
+            self._rnd = torch.zeros(N, dtype=torch.int64, device=dev)
+            self._u = torch.zeros(N, dtype=torch.float32, device=dev)
+            self._act = torch.zeros(N, dtype=torch.int64, device=dev)
+
+    # ------------------------------------------------------------------ rollout
+    def reset(self, next_obs):
+        self.next_obs = torch.Tensor(next_obs).to(self.device)
+        self.next_done = torch.zeros(self.N).to(self.device)
+
+    def start_iteration(self, iteration: int):
+        a = self.args
+        if a.anneal_lr:
+            frac = 1.0 - (iteration - 1.0) / a.num_iterations
+            self.lr = frac * a.learning_rate
+            if self.optimizer is not None:
+                self.optimizer.param_groups[0]["lr"] = self.lr
+
+    def _epsilon(self):
+        a = self.args
+        return linear_schedule(a.start_e, a.end_e, a.exploration_fraction * a.total_timesteps, self.global_step)
+
+    def act(self, step: int, force_action=None):
+        """One step's action logic; returns the (N,) int64 action on the learner's device.  ``force_action`` (N,) replaces the
+        chosen action in storage and in the result (teacher forcing); ``values`` keeps q at the greedy index."""
+        self.global_step += self.N
+        self.epsilon = epsilon = self._epsilon()
+        if not self.fused:
+            self.obs[step] = self.next_obs
+            self.dones[step] = self.next_done
+            random_actions = torch.randint(0, self.A, (self.N,)).to(self.device)
+            with torch.no_grad():
+                q_values = self.net(self.next_obs)
+                max_actions = torch.argmax(q_values, dim=1)
+                self.values[step] = q_values[torch.arange(self.N), max_actions].flatten()
+            explore = torch.rand((self.N,)).to(self.device) < epsilon
+            action = torch.where(explore, random_actions, max_actions)
+            if force_action is not None:
+                action = force_action.to(self.device, torch.int64)
+            self.actions[step] = action
+            return action
+        self._rnd_host.copy_(torch.randint(0, self.A, (self.N,)))     # the reference's draws, in its order
+        self._u_host.copy_(torch.rand((self.N,)))
+        rnd, u = self._rnd_host, self._u_host
+        if self.device.type == "cuda":
+            self._rnd.copy_(self._rnd_host, non_blocking=True)
+            self._u.copy_(self._u_host, non_blocking=True)
+            rnd, u = self._rnd, self._u
+        if self.mlp:
+            self.g.pqn_mlp_act(self.next_obs, self.flat.params, self.A, rnd, u, epsilon, self.actions[step], self.values[step], self._act,
+                               obs_row_out=self.obs[step].view(self.N, -1), done_in=self.next_done, done_row_out=self.dones[step])
+        else:
+            self.obs[step] = self.next_obs
+            self.dones[step] = self.next_done
+            with torch.no_grad():
+                q = self.net(self.next_obs)
+            self.g.pqn_egreedy(q, rnd, u, epsilon, self.actions[step], self.values[step], self._act)
+        if force_action is not None:
+            self._act.copy_(force_action.to(torch.int64))
+            self.actions[step] = self._act
+        return self._act
+
+    def observe(self, step: int, next_obs, reward, next_done):
+        self.rewards[step] = torch.tensor(reward).to(self.device).view(-1)
+        self.next_obs, self.next_done = torch.Tensor(next_obs).to(self.device), torch.Tensor(next_done).to(self.device)
+
+    @torch.no_grad()
+    def finish_rollout(self):
+        """``# Compute Q(lambda) targets``."""
+        a = self.args
+        if self.fused:
+            if self.mlp:
+                next_q = self.g.pqn_mlp_forward(self.next_obs, self.flat.params, self.A)
+            else:
+                next_q = self.net(self.next_obs).contiguous()
+            self.returns = self.g.pqn_qlambda(self.rewards, self.dones, self.values, self.next_done, next_q, a.gamma, a.q_lambda)
+            return self.returns
+        returns = torch.zeros_like(self.rewards).to(self.device)
+        for t in reversed(range(self.T)):
+            if t == self.T - 1:
+                next_value, _ = torch.max(self.net(self.next_obs), dim=-1)
+                nextnonterminal = 1.0 - self.next_done
+                returns[t] = self.rewards[t] + a.gamma * next_value * nextnonterminal
+            else:
+                nextnonterminal = 1.0 - self.dones[t + 1]
+                next_value = self.values[t + 1]
+                returns[t] = self.rewards[t] + a.gamma * (a.q_lambda * returns[t + 1] + (1 - a.q_lambda) * next_value) * nextnonterminal
+        self.returns = returns
+        return returns
+
+    # ------------------------------------------------------------------ update
+    def update(self):
+        a = self.args
+        batch_size = self.T * self.N
+        minibatch_size = batch_size // int(a.num_minibatches)
+        b_obs = self.obs.reshape((-1,) + self.obs_shape)
+        b_actions = self.actions.reshape(-1)
+        b_returns = self.returns.reshape(-1)
+        b_inds = np.arange(batch_size)
+        scalars = None
+        for epoch in range(a.update_epochs):
+            np.random.shuffle(b_inds)
+            for start in range(0, batch_size, minibatch_size):
+                end = start + minibatch_size
+                mb_inds = b_inds[start:end]
+                if not self.fused:
+                    old_val = self.net(b_obs[mb_inds]).gather(1, b_actions[mb_inds].unsqueeze(-1).long()).squeeze()
+                    loss = F.mse_loss(b_returns[mb_inds], old_val)
+                    self.optimizer.zero_grad()
+                    loss.backward()
+                    nn.utils.clip_grad_norm_(self.net.parameters(), a.max_grad_norm)
+                    self.optimizer.step()
+                    continue
+                mb = torch.from_numpy(mb_inds).to(self.device)
+                if self.mlp:
+                    scalars = self.g.pqn_mlp_td_fwd_bwd(b_obs.view(batch_size, -1), mb, self.flat.params, b_actions, b_returns,
+                                                        self.flat.grads, self.A, scalars)
+                else:
+                    q = self.net(b_obs[mb])
+                    dq, scalars = self.g.pqn_td_loss(q.detach().contiguous(), mb, b_actions, b_returns, scalars=scalars)
+                    q.backward(dq)
+                self.flat.step += 1
+                self.g.clip_radam_(self.flat.params, self.flat.grads, self.flat.exp_avg, self.flat.exp_avg_sq, self.flat.step, self.lr,
+                                   a.max_grad_norm)
+        if not self.fused:
+            return {"td_loss": loss.item(), "q_values": old_val.mean().item()}
+        td_loss, q_values = scalars.tolist()
+        return {"td_loss": td_loss, "q_values": q_values}

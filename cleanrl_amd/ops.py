@@ -21,6 +21,8 @@ __all__ = [
     "CategoricalLogProbEntropy", "NormalLogProbEntropy", "LOSS_SCALAR_NAMES", "lstm_seq_forward", "lstm_seq_backward", "LSTMSeq",
     "lstm_seq", "lstm_seq_dw_hh", "impala_forward", "impala_backward", "impala_maxpool_forward", "impala_maxpool_backward",
     "ImpalaTrunk", "impala_trunk", "impala_param_shapes", "trxl_attn_forward", "trxl_attn_backward", "TrXLMemoryAttention", "trxl_memory_attention",
+    "pqn_param_count", "pqn_egreedy", "pqn_qlambda", "pqn_td_loss", "pqn_mlp_forward", "pqn_mlp_act", "pqn_mlp_td_fwd_bwd", "radam_schedule",
+    "clip_radam_", "clip_radam_sched_",
 ]
 
 LOSS_SCALAR_NAMES = ("loss", "pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac")
@@ -1177,3 +1179,177 @@ def synth_continuous_step(state, reset_state, At, Bm, w, noise, k: int, steps, h
                                                     int(k) & (2**64 - 1), _ptr(k_base), _ptr(steps), float(horizon), _ptr(action),
                                                     _ptr(obs_out), _ptr(reward), _ptr(done), N, O, D, _stream(dev))
     _lib.check(st, "mi355ppo_synth_continuous_step_f32")
+
+
+# ------------------------------------------------------------------------------------------- PQN (csrc/pqn.hip)
+PQN_MAX_OBS, PQN_MAX_ACTIONS, PQN_HIDDEN = 64, 18, (120, 84)
+
+
+def pqn_param_count(obs_dim: int, n_actions: int) -> int:
+    """Parameters of pqn.py's QNetwork (Linear -> LayerNorm(120) -> ReLU -> Linear -> LayerNorm(84) -> ReLU -> Linear)."""
+    return 120 * obs_dim + 360 + 84 * 120 + 252 + 85 * n_actions
+
+
+def pqn_egreedy(q, random_actions, u, epsilon: float, actions_out, values_out, action_i64_out=None):
+    """pqn.py's action logic on a computed ``q`` (N, A): argmax (torch's tie / NaN rule), ``values[step]`` = q at the greedy index,
+    ``rand < epsilon`` and ``where``.  ``actions_out`` / ``values_out`` are the step's storage rows (N,) f32."""
+    N, A = q.shape
+    _chk(q, torch.float32, "q")
+    _chk(random_actions, torch.int64, "random_actions", (N,))
+    _chk(u, torch.float32, "u", (N,))
+    _chk(actions_out, torch.float32, "actions_out", (N,))
+    _chk(values_out, torch.float32, "values_out", (N,))
+    if action_i64_out is not None:
+        _chk(action_i64_out, torch.int64, "action_i64_out", (N,))
+    with _on(q.device):
+        st = _lib.load().mi355ppo_pqn_egreedy_f32(_ptr(q), _ptr(random_actions), _ptr(u), float(epsilon), _ptr(actions_out), _ptr(values_out),
+                                                  _ptr(action_i64_out), N, A, _stream(q.device))
+    _lib.check(st, "mi355ppo_pqn_egreedy_f32")
+    return actions_out, values_out
+
+
+def pqn_qlambda(rewards, dones, values, next_done, next_q, gamma: float, q_lambda: float, returns=None):
+    """The ``# Compute Q(lambda) targets`` block (bootstrap ``torch.max(next_q, dim=-1)`` included) -> returns (T, N)."""
+    T, N = rewards.shape
+    A = next_q.shape[-1]
+    for t, nm in ((rewards, "rewards"), (dones, "dones"), (values, "values")):
+        _chk(t, torch.float32, nm, (T, N))
+    next_done = _chk(next_done.reshape(-1), torch.float32, "next_done", (N,))
+    _chk(next_q, torch.float32, "next_q", (N, A))
+    if returns is None:
+        returns = torch.empty_like(rewards)
+    _chk(returns, torch.float32, "returns", (T, N))
+    with _on(rewards.device):
+        st = _lib.load().mi355ppo_pqn_qlambda_f32(_ptr(rewards), _ptr(dones), _ptr(values), _ptr(next_done), _ptr(next_q), _ptr(returns),
+                                                  T, N, A, float(gamma), float(q_lambda), _stream(rewards.device))
+    _lib.check(st, "mi355ppo_pqn_qlambda_f32")
+    return returns
+
+
+def pqn_td_loss(q, mb_inds, b_actions, b_returns, dq=None, scalars=None):
+    """``q.gather(1, b_actions[mb_inds].long())`` + ``F.mse_loss(b_returns[mb_inds], old_val)`` and its gradient -> (dq (M, A),
+    scalars (2,) = {td_loss, mean(old_val)})."""
+    M, A = q.shape
+    _chk(q, torch.float32, "q")
+    _chk(mb_inds, torch.int64, "mb_inds", (M,))
+    B = b_actions.numel()
+    b_actions = _chk(b_actions.reshape(-1), torch.float32, "b_actions", (B,))
+    b_returns = _chk(b_returns.reshape(-1), torch.float32, "b_returns", (B,))
+    dq = torch.empty_like(q) if dq is None else _chk(dq, torch.float32, "dq", (M, A))
+    scalars = torch.empty(2, dtype=torch.float32, device=q.device) if scalars is None else _chk(scalars, torch.float32, "scalars", (2,))
+    with _on(q.device):
+        st = _lib.load().mi355ppo_pqn_td_loss_fwd_bwd_f32(_ptr(q), _ptr(mb_inds), _ptr(b_actions), _ptr(b_returns), _ptr(dq), _ptr(scalars),
+                                                          M, A, B, _stream(q.device))
+    _lib.check(st, "mi355ppo_pqn_td_loss_fwd_bwd_f32")
+    return dq, scalars
+
+
+def _pqn_net(obs, params, n_actions):
+    N, O = obs.shape
+    _chk(obs, torch.float32, "obs")
+    _chk(params, torch.float32, "params", (pqn_param_count(O, n_actions),))
+    return N, O
+
+
+def pqn_mlp_forward(obs, params, n_actions: int, q_out=None):
+    """``QNetwork.forward`` of pqn.py on the flat parameters (``agent.parameters()`` order) -> q (N, A)."""
+    N, O = _pqn_net(obs, params, n_actions)
+    q_out = torch.empty((N, n_actions), dtype=torch.float32, device=obs.device) if q_out is None else _chk(q_out, torch.float32, "q_out",
+                                                                                                            (N, n_actions))
+    with _on(obs.device):
+        st = _lib.load().mi355ppo_pqn_mlp_fwd_f32(_ptr(obs), _ptr(params), _ptr(q_out), N, O, int(n_actions), _stream(obs.device))
+    _lib.check(st, "mi355ppo_pqn_mlp_fwd_f32")
+    return q_out
+
+
+def pqn_mlp_act(obs, params, n_actions: int, random_actions, u, epsilon: float, actions_out, values_out, action_i64_out=None,
+                obs_row_out=None, done_in=None, done_row_out=None):
+    """One rollout step of pqn.py in one launch: forward, e-greedy, the ``actions`` / ``values`` (and optionally ``obs`` /
+    ``dones``) storage rows."""
+    N, O = _pqn_net(obs, params, n_actions)
+    _chk(random_actions, torch.int64, "random_actions", (N,))
+    _chk(u, torch.float32, "u", (N,))
+    _chk(actions_out, torch.float32, "actions_out", (N,))
+    _chk(values_out, torch.float32, "values_out", (N,))
+    if action_i64_out is not None:
+        _chk(action_i64_out, torch.int64, "action_i64_out", (N,))
+    if obs_row_out is not None:
+        _chk(obs_row_out, torch.float32, "obs_row_out", (N, O))
+    if done_row_out is not None:
+        _chk(done_in, torch.float32, "done_in", (N,))
+        _chk(done_row_out, torch.float32, "done_row_out", (N,))
+    with _on(obs.device):
+        st = _lib.load().mi355ppo_pqn_mlp_act_f32(_ptr(obs), _ptr(params), _ptr(random_actions), _ptr(u), float(epsilon), _ptr(actions_out),
+                                                  _ptr(values_out), _ptr(action_i64_out), _ptr(obs_row_out), _ptr(done_in), _ptr(done_row_out), N,
+                                                  O, int(n_actions), _stream(obs.device))
+    _lib.check(st, "mi355ppo_pqn_mlp_act_f32")
+    return actions_out, values_out
+
+
+def pqn_mlp_td_fwd_bwd(b_obs, mb_inds, params, b_actions, b_returns, grads, n_actions: int, scalars=None):
+    """One minibatch of pqn.py: gather, forward, TD loss, backward.  OVERWRITES ``grads`` (flat) with d loss / d params and returns
+    scalars (2,) = {td_loss, mean(old_val)}."""
+    B, O = _pqn_net(b_obs, params, n_actions)
+    (M,) = mb_inds.shape
+    _chk(mb_inds, torch.int64, "mb_inds", (M,))
+    b_actions = _chk(b_actions.reshape(-1), torch.float32, "b_actions", (B,))
+    b_returns = _chk(b_returns.reshape(-1), torch.float32, "b_returns", (B,))
+    _chk(grads, torch.float32, "grads", params.shape)
+    dev = b_obs.device
+    scalars = torch.empty(2, dtype=torch.float32, device=dev) if scalars is None else _chk(scalars, torch.float32, "scalars", (2,))
+    lib = _lib.load()
+    ws = _workspace(dev, lib.mi355ppo_pqn_mlp_td_workspace_bytes(M, O, int(n_actions)))
+    with _on(dev):
+        st = lib.mi355ppo_pqn_mlp_td_fwd_bwd_f32(_ptr(b_obs), B, _ptr(mb_inds), _ptr(params), _ptr(b_actions), _ptr(b_returns), _ptr(grads),
+                                                 _ptr(scalars), M, O, int(n_actions), _ptr(ws), ws.numel(), _stream(dev))
+    _lib.check(st, "mi355ppo_pqn_mlp_td_fwd_bwd_f32")
+    return scalars
+
+
+def radam_schedule(lr: float, step: int, beta1: float = 0.9, beta2: float = 0.999):
+    """The 8-float schedule slot of RAdam step ``step`` (1-based), as the library forms it (host floats)."""
+    out = (ctypes.c_float * 8)()
+    _lib.check(_lib.load().mi355ppo_radam_schedule_f32(float(lr), float(beta1), float(beta2), int(step), out), "mi355ppo_radam_schedule_f32")
+    return [float(x) for x in out]
+
+
+def _flat4(params, grads, exp_avg, exp_avg_sq):
+    n = params.numel()
+    for t, nm in ((params, "params"), (grads, "grads"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        _chk(t, torch.float32, nm, (n,))
+    return n
+
+
+def clip_radam_(params, grads, exp_avg, exp_avg_sq, step: int, lr: float, max_grad_norm: float, beta1: float = 0.9, beta2: float = 0.999,
+                eps: float = 1e-8, total_norm_out=None):
+    """In-place ``clip_grad_norm_`` + ``optim.RAdam`` step ``step`` (1-based) on flat f32 buffers; zeroes ``grads``."""
+    lib = _lib.load()
+    n = _flat4(params, grads, exp_avg, exp_avg_sq)
+    dev = params.device
+    if total_norm_out is None:
+        total_norm_out = torch.empty(1, dtype=torch.float32, device=dev)
+    ws = _workspace(dev, lib.mi355ppo_clip_radam_workspace_bytes(n))
+    with _on(dev):
+        st = lib.mi355ppo_clip_radam_f32(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), n, float(max_grad_norm), float(lr),
+                                         float(beta1), float(beta2), float(eps), int(step), _ptr(total_norm_out), _ptr(ws), ws.numel(),
+                                         _stream(dev))
+    _lib.check(st, "mi355ppo_clip_radam_f32")
+    return total_norm_out
+
+
+def clip_radam_sched_(params, grads, exp_avg, exp_avg_sq, sched8, max_grad_norm: float, beta1: float = 0.9, beta2: float = 0.999,
+                      eps: float = 1e-8, total_norm_out=None):
+    """``clip_radam_`` with the step's slot (``radam_schedule`` values) read from the 8-float DEVICE tensor ``sched8``: capturable."""
+    lib = _lib.load()
+    n = _flat4(params, grads, exp_avg, exp_avg_sq)
+    _chk(sched8, torch.float32, "sched8", (8,))
+    dev = params.device
+    if total_norm_out is None:
+        total_norm_out = torch.empty(1, dtype=torch.float32, device=dev)
+    ws = _workspace(dev, lib.mi355ppo_clip_radam_workspace_bytes(n))
+    with _on(dev):
+        st = lib.mi355ppo_clip_radam_sched_f32(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), n, float(max_grad_norm),
+                                               float(beta1), float(beta2), float(eps), _ptr(sched8), _ptr(total_norm_out), _ptr(ws),
+                                               ws.numel(), _stream(dev))
+    _lib.check(st, "mi355ppo_clip_radam_sched_f32")
+    return total_norm_out

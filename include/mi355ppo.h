@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MI355PPO_VERSION 240 /* major*100 + minor*10 + patch.  The minor moves whenever an exported signature changes or an entry
+#define MI355PPO_VERSION 250 /* major*100 + minor*10 + patch.  The minor moves whenever an exported signature changes or an entry
                                   point is added (1.1: adv_mean_den / conv1_variant arguments of round 2; 1.2, 1.3: round 3;
                                   1.4: the *_cpu host-pointer twins; 1.5: mi355ppo_init; 1.6: round 4 -- the fused MLP family K7,
                                   mi355ppo_clip_adam_sched_f32; 1.7: mi355ppo_fc_heads_act_categorical_f32, mi355ppo_nature_packs_f32,
@@ -41,7 +41,8 @@ extern "C" {
                                   heads of up to 18 actions, a 4-byte-aligned critic row; 2.0: the peer-memory gradient exchange mi355ppo_dp_*; 2.1: the fused MLP family takes obs_dim <= 512, n_out <= 20;
                                   2.2: the done-masked LSTM sequence scans mi355ppo_lstm_seq_fwd_f32 / _bwd_f32 and their *_cpu twins;
                                   2.3: the TrXL episodic-memory attention mi355ppo_trxl_attn_fwd_f32 / _bwd_f32 and their *_cpu twins;
-                                  2.4: the IMPALA-CNN trunk mi355ppo_impala_* (forward, backward, max pool, sizes) and the *_cpu twins);
+                                  2.4: the IMPALA-CNN trunk mi355ppo_impala_* (forward, backward, max pool, sizes) and the *_cpu twins;
+                                  2.5: PQN -- mi355ppo_pqn_* (e-greedy, Q(lambda), TD loss, the LayerNorm MLP), clip + RAdam, the *_cpu twins);
                                   a binding must check major AND minor (cleanrl_amd/_lib.py does) */
 
 #if defined(__GNUC__)
@@ -828,6 +829,67 @@ MI355PPO_API int mi355ppo_synth_continuous_step_f32(float* state, const float* r
                                                     const float* noise, int bank, uint64_t k, const uint64_t* k_base, float* steps,
                                                     double horizon, const float* action, float* obs_out, float* reward, float* done, int N,
                                                     int O, int D, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * PQN (cleanrl/pqn.py, cleanrl/pqn_atari_envpool.py; csrc/pqn.hip, row math in csrc/pqn_rows.h).  All f32, row-major; every
+ * *_cpu twin takes host pointers and returns the device's bits.  No entry point allocates or synchronises (all are capturable).
+ *
+ * e-greedy (the rollout's action logic): per env n, g = argmax q[n, :] (torch's rule: the first maximum wins, a NaN is the maximum
+ * and the first NaN wins), values_out[n] = q[n, g], a = (u[n] < (float)epsilon) ? random_actions[n] : g; actions_out[n] = (float)a
+ * and, when non-NULL, action_i64_out[n] = a.  actions_out / values_out point at the storage row of the step. */
+MI355PPO_API int mi355ppo_pqn_egreedy_f32(const float* q, const int64_t* random_actions, const float* u, double epsilon, float* actions_out,
+                                          float* values_out, int64_t* action_i64_out, int N, int A, void* stream);
+MI355PPO_API int mi355ppo_pqn_egreedy_f32_cpu(const float* q, const int64_t* random_actions, const float* u, double epsilon,
+                                              float* actions_out, float* values_out, int64_t* action_i64_out, int N, int A);
+/* Q(lambda) targets: returns (T, N) from rewards, dones, values (T, N), next_done (N) and next_q (N, A) (the bootstrap is
+ * torch.max(next_q, dim=-1), NaN-propagating), in the reference loop's operation order with gamma, q_lambda and 1 - q_lambda (formed
+ * in double) rounded to f32: bit-equal to the loop run by torch on the CPU. */
+MI355PPO_API int mi355ppo_pqn_qlambda_f32(const float* rewards, const float* dones, const float* values, const float* next_done,
+                                          const float* next_q, float* returns, int T, int N, int A, double gamma, double q_lambda, void* stream);
+MI355PPO_API int mi355ppo_pqn_qlambda_f32_cpu(const float* rewards, const float* dones, const float* values, const float* next_done,
+                                              const float* next_q, float* returns, int T, int N, int A, double gamma, double q_lambda);
+/* TD loss of a minibatch: old[r] = q[r, (long)b_actions[i]], loss = F.mse_loss(b_returns[i], old) with i = mb_inds[r] (B = rows of
+ * b_actions / b_returns; an index or action out of range is clamped).  dq (M, A) = d loss / d q (non-zero only in the action's
+ * column); scalars_out = {loss, mean(old)}, summed in f64 in a fixed order. */
+MI355PPO_API int mi355ppo_pqn_td_loss_fwd_bwd_f32(const float* q, const int64_t* mb_inds, const float* b_actions, const float* b_returns,
+                                                  float* dq, float* scalars_out, int M, int A, int64_t B, void* stream);
+MI355PPO_API int mi355ppo_pqn_td_loss_fwd_bwd_f32_cpu(const float* q, const int64_t* mb_inds, const float* b_actions, const float* b_returns,
+                                                      float* dq, float* scalars_out, int M, int A, int64_t B);
+/* pqn.py's QNetwork: Linear(O, 120) -> LayerNorm(120) -> ReLU -> Linear(120, 84) -> LayerNorm(84) -> ReLU -> Linear(84, A), its
+ * parameters flat in agent.parameters() order (params, mi355ppo_pqn_* count: 120 O + 360 + 10080 + 252 + 85 A).  1 <= O <= 64,
+ * 1 <= A <= 18, else MI355PPO_EINVAL.  fwd: q_out (N, A).  act: one rollout step in one launch -- the forward, e-greedy as above and,
+ * when non-NULL, obs_row_out[n] = obs[n] and done_row_out[n] = done_in[n] (the step's storage rows). */
+MI355PPO_API int mi355ppo_pqn_mlp_fwd_f32(const float* obs, const float* params, float* q_out, int N, int O, int A, void* stream);
+MI355PPO_API int mi355ppo_pqn_mlp_fwd_f32_cpu(const float* obs, const float* params, float* q_out, int N, int O, int A);
+MI355PPO_API int mi355ppo_pqn_mlp_act_f32(const float* obs, const float* params, const int64_t* random_actions, const float* u, double epsilon,
+                                          float* actions_out, float* values_out, int64_t* action_i64_out, float* obs_row_out, const float* done_in,
+                                          float* done_row_out, int N, int O, int A, void* stream);
+MI355PPO_API int mi355ppo_pqn_mlp_act_f32_cpu(const float* obs, const float* params, const int64_t* random_actions, const float* u,
+                                              double epsilon, float* actions_out, float* values_out, int64_t* action_i64_out, float* obs_row_out,
+                                              const float* done_in, float* done_row_out, int N, int O, int A);
+/* One minibatch of pqn.py: gather b_obs[mb_inds] (B rows), forward, the TD loss as above, backward through both LayerNorm + ReLU
+ * layers; grads (flat, agent.parameters() order) is OVERWRITTEN with d loss / d params; scalars_out = {td_loss, mean(old)}.  Two
+ * launches: per-workgroup (256 rows) partials, then their fold in a fixed order. */
+MI355PPO_API size_t mi355ppo_pqn_mlp_td_workspace_bytes(int M, int O, int A);
+MI355PPO_API int mi355ppo_pqn_mlp_td_fwd_bwd_f32(const float* b_obs, int64_t B, const int64_t* mb_inds, const float* params,
+                                                 const float* b_actions, const float* b_returns, float* grads, float* scalars_out, int M, int O,
+                                                 int A, void* workspace, size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_pqn_mlp_td_fwd_bwd_f32_cpu(const float* b_obs, int64_t B, const int64_t* mb_inds, const float* params,
+                                                     const float* b_actions, const float* b_returns, float* grads, float* scalars_out, int M,
+                                                     int O, int A);
+/* clip_grad_norm_(max_grad_norm) + torch.optim.RAdam(lr, (beta1, beta2), eps) step `step` (1-based) on flat buffers, in torch's
+ * single-tensor operation order; zeroes grads.  mi355ppo_radam_schedule_f32 writes the step's 8-float slot {1 - beta1^step, lr,
+ * (1 - beta2^step)^0.5, rect, rho_t > 5, 0, 0, 0} (double, rounded to f32); the _sched form reads such a slot from DEVICE memory. */
+MI355PPO_API int mi355ppo_radam_schedule_f32(double lr, double beta1, double beta2, int64_t step, float* out8_host);
+MI355PPO_API size_t mi355ppo_clip_radam_workspace_bytes(int64_t n);
+MI355PPO_API int mi355ppo_clip_radam_f32(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, double max_grad_norm,
+                                         double lr, double beta1, double beta2, double eps, int64_t step, float* total_norm_out, void* workspace,
+                                         size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_clip_radam_sched_f32(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, double max_grad_norm,
+                                               double beta1, double beta2, double eps, const float* sched8, float* total_norm_out,
+                                               void* workspace, size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_clip_radam_f32_cpu(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, double max_grad_norm,
+                                             double lr, double beta1, double beta2, double eps, int64_t step, float* total_norm_out);
 
 #ifdef __cplusplus
 }
