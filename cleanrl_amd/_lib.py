@@ -251,3 +251,9 @@ def check(status: int, fn: str) -> None:
     if status != 0:
         msg = load().mi355ppo_last_error()
         raise Mi355PpoError(f"{fn} failed with status {status}: {msg.decode() if msg else ''}")
+
+
+def call(name: str, *args) -> None:
+    """Call the status-returning entry point ``name``; a non-zero status raises ``Mi355PpoError`` naming that symbol.  The helpers
+    that return a value (``*_workspace_bytes``, ``*_pack_bytes``, ``*_kernel*``, ...) are called on ``load()`` directly."""
+    check(getattr(_lib or load(), name)(*args), name)

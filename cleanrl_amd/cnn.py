@@ -18,7 +18,7 @@ import weakref
 import torch
 
 from . import _lib
-from .ops import _chk, _on, _ptr, _stream, _workspace
+from .ops import _chk, _launch, _ptr, _workspace
 
 # layer -> (Cin, Cout, K, stride, Hin, Hout)
 LAYERS = {1: (4, 32, 8, 4, 84, 20), 2: (32, 64, 4, 2, 20, 9), 3: (64, 64, 3, 1, 9, 7)}
@@ -48,13 +48,10 @@ def new_amax(n: int, device) -> torch.Tensor:
 
 def absmax(x: torch.Tensor, rec: torch.Tensor) -> torch.Tensor:
     """Fold ``max |x|`` into the amax record ``rec`` (one row of ``new_amax``; zero it first unless it already holds part of x)."""
-    lib = _lib.load()
     _chk(rec, torch.int32, "amax record", (AMAX_WORDS,))
     if x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous():
         raise ValueError(f"absmax: expected a contiguous f32 device tensor, got {tuple(x.shape)} {x.dtype} on {x.device}")
-    with _on(x.device):
-        st = lib.mi355ppo_absmax_f32(_ptr(x), x.numel(), _ptr(rec), _stream(x.device))
-    _lib.check(st, "mi355ppo_absmax_f32")
+    _launch("mi355ppo_absmax_f32", x.device, _ptr(x), x.numel(), _ptr(rec))
     return rec
 
 
@@ -78,7 +75,6 @@ def warm_forward_packs(bufs, net) -> None:
 
 
 def repack_weights(W: torch.Tensor, layer: int, mode: int = MODE_FWD, out: torch.Tensor | None = None) -> torch.Tensor:
-    lib = _lib.load()
     cin, cout, k, _, _, _ = LAYERS[layer]
     _chk(W, torch.float32, f"W{layer}", (cout, cin, k, k))
     numel = (BT_CLASSES_NUMEL if mode == MODE_DGRAD_S1_CLASSES else QPACK_NUMEL if mode == MODE_FWD_Q
@@ -86,16 +82,13 @@ def repack_weights(W: torch.Tensor, layer: int, mode: int = MODE_FWD, out: torch
     if out is None:
         out = torch.empty(numel, dtype=torch.float32, device=W.device)
     _chk(out, torch.float32, "Bt", (numel,))
-    with _on(W.device):
-        st = lib.mi355ppo_cnn_repack_weights_f32(_ptr(W), _ptr(out), layer, mode, _stream(W.device))
-    _lib.check(st, "mi355ppo_cnn_repack_weights_f32")
+    _launch("mi355ppo_cnn_repack_weights_f32", W.device, _ptr(W), _ptr(out), layer, mode)
     return out
 
 
 def conv_fwd(src: torch.Tensor, Bt: torch.Tensor, bias: torch.Tensor, layer: int, inds: torch.Tensor | None = None,
              out: torch.Tensor | None = None, variant: int = 0) -> torch.Tensor:
     """``relu(conv(src) + bias)``; layer 1 takes the uint8 rollout rows (+ optional int64 row gather)."""
-    lib = _lib.load()
     cin, cout, k, _, hin, hout = LAYERS[layer]
     if layer == 1:
         _chk(src, torch.uint8, "src")
@@ -112,17 +105,14 @@ def conv_fwd(src: torch.Tensor, Bt: torch.Tensor, bias: torch.Tensor, layer: int
     if out is None:
         out = torch.empty((images, hout, hout, cout), dtype=torch.float32, device=src.device)
     _chk(out, torch.float32, "out", (images, hout, hout, cout))
-    with _on(src.device):
-        st = lib.mi355ppo_cnn_conv_fwd_f32_variant(_ptr(src), _ptr(inds), _ptr(Bt), _ptr(bias), _ptr(out), images, layer,
-                                                   int(variant), _stream(src.device))
-    _lib.check(st, "mi355ppo_cnn_conv_fwd_f32")
+    _launch("mi355ppo_cnn_conv_fwd_f32_variant", src.device, _ptr(src), _ptr(inds), _ptr(Bt), _ptr(bias), _ptr(out), images, layer,
+            int(variant))
     return out
 
 
 def conv_dgrad(dz: torch.Tensor, Bt: torch.Tensor, act_in: torch.Tensor, layer: int,
                out: torch.Tensor | None = None, variant: int = 0) -> torch.Tensor:
     """Gradient w.r.t. the layer's input activation, masked by ``act_in > 0`` (ReLU backward fused)."""
-    lib = _lib.load()
     cin, cout, k, _, hin, hout = LAYERS[layer]
     images = dz.shape[0]
     _chk(dz, torch.float32, "dz", (images, hout, hout, cout))
@@ -132,10 +122,7 @@ def conv_dgrad(dz: torch.Tensor, Bt: torch.Tensor, act_in: torch.Tensor, layer: 
     if out is None:
         out = torch.empty_like(act_in)
     _chk(out, torch.float32, "out", (images, hin, hin, cin))
-    with _on(dz.device):
-        st = lib.mi355ppo_cnn_conv_dgrad_f32_variant(_ptr(dz), _ptr(Bt), _ptr(act_in), _ptr(out), images, layer, int(variant),
-                                                     _stream(dz.device))
-    _lib.check(st, "mi355ppo_cnn_conv_dgrad_f32")
+    _launch("mi355ppo_cnn_conv_dgrad_f32_variant", dz.device, _ptr(dz), _ptr(Bt), _ptr(act_in), _ptr(out), images, layer, int(variant))
     return out
 
 
@@ -164,35 +151,25 @@ def conv_wgrad(src: torch.Tensor, dz: torch.Tensor, layer: int, inds: torch.Tens
         db = torch.empty(cout, dtype=torch.float32, device=dev)
     ws = _workspace(dev, lib.mi355ppo_cnn_conv_wgrad_workspace_bytes(images, layer))
     if amax is not None and layer == 1:          # kernel P with dz in two f16 terms: ``amax = (None, dz_rec)`` (the uint8 frames are exact)
-        with _on(dev):
-            st = lib.mi355ppo_cnn_conv1_wgrad_f16x2(_ptr(src), _ptr(inds), _ptr(dz), _ptr(dW), _ptr(db), images, _ptr(ws), ws.numel(),
-                                                    _rec(amax[1], "dz_amax"), _stream(dev))
-        _lib.check(st, "mi355ppo_cnn_conv1_wgrad_f16x2")
+        _launch("mi355ppo_cnn_conv1_wgrad_f16x2", dev, _ptr(src), _ptr(inds), _ptr(dz), _ptr(dW), _ptr(db), images, _ptr(ws), ws.numel(),
+                _rec(amax[1], "dz_amax"))
         return dW, db
     if amax is not None:
-        with _on(dev):
-            st = lib.mi355ppo_cnn_conv_wgrad_f16x2_f32(_ptr(src), _ptr(dz), _ptr(dW), _ptr(db), images, layer, _ptr(ws), ws.numel(),
-                                                       _rec(amax[0], "src_amax"), _rec(amax[1], "dz_amax"), _stream(dev))
-        _lib.check(st, "mi355ppo_cnn_conv_wgrad_f16x2_f32")
+        _launch("mi355ppo_cnn_conv_wgrad_f16x2_f32", dev, _ptr(src), _ptr(dz), _ptr(dW), _ptr(db), images, layer, _ptr(ws), ws.numel(),
+                _rec(amax[0], "src_amax"), _rec(amax[1], "dz_amax"))
         return dW, db
-    with _on(dev):
-        st = lib.mi355ppo_cnn_conv_wgrad_f32(_ptr(src), _ptr(inds), _ptr(dz), _ptr(dW), _ptr(db), images, layer, _ptr(ws),
-                                             ws.numel(), _stream(dev))
-    _lib.check(st, "mi355ppo_cnn_conv_wgrad_f32")
+    _launch("mi355ppo_cnn_conv_wgrad_f32", dev, _ptr(src), _ptr(inds), _ptr(dz), _ptr(dW), _ptr(db), images, layer, _ptr(ws), ws.numel())
     return dW, db
 
 
 def trunk_fwd(obs_u8, inds, bt1, b1, bt2, b2, bt3, b3, a1, a2, a3, conv1_variant: int = 0):
     """conv1 -> conv2 -> conv3 (each with bias + ReLU) in one library call; buffers as produced by ``_Buffers``.
     ``conv1_variant=VARIANT_Q``: ``bt1`` is the mode-4 pack."""
-    lib = _lib.load()
     _chk(obs_u8, torch.uint8, "obs_u8")
     images = a1.shape[0]
     dev = obs_u8.device
-    with _on(dev):
-        st = lib.mi355ppo_cnn_trunk_fwd_f32(_ptr(obs_u8), _ptr(inds), _ptr(bt1), _ptr(b1), _ptr(bt2), _ptr(b2), _ptr(bt3), _ptr(b3),
-                                            _ptr(a1), _ptr(a2), _ptr(a3), images, int(conv1_variant), _stream(dev))
-    _lib.check(st, "mi355ppo_cnn_trunk_fwd_f32")
+    _launch("mi355ppo_cnn_trunk_fwd_f32", dev, _ptr(obs_u8), _ptr(inds), _ptr(bt1), _ptr(b1), _ptr(bt2), _ptr(b2), _ptr(bt3), _ptr(b3),
+            _ptr(a1), _ptr(a2), _ptr(a3), images, int(conv1_variant))
     return a3
 
 
@@ -208,9 +185,7 @@ def fc_pack(B: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     if out is None:
         out = torch.empty(nbytes, dtype=torch.uint8, device=B.device)
     _chk(out, torch.uint8, "pack", (nbytes,))
-    with _on(B.device):
-        st = lib.mi355ppo_fc_pack_f32(_ptr(B), B.stride(0), N, K, _ptr(out), _stream(B.device))
-    _lib.check(st, "mi355ppo_fc_pack_f32")
+    _launch("mi355ppo_fc_pack_f32", B.device, _ptr(B), B.stride(0), N, K, _ptr(out))
     return out
 
 
@@ -233,9 +208,7 @@ def fc_pack_f16x2(B: torch.Tensor, b_amax: torch.Tensor | None = None, out: torc
     if out is None:
         out = torch.empty(nbytes, dtype=torch.uint8, device=B.device)
     _chk(out, torch.uint8, "pack", (nbytes,))
-    with _on(B.device):
-        st = lib.mi355ppo_fc_pack_f16x2_f32(_ptr(B), B.stride(0), N, K, _rec(b_amax, "b_amax"), _ptr(out), _stream(B.device))
-    _lib.check(st, "mi355ppo_fc_pack_f16x2_f32")
+    _launch("mi355ppo_fc_pack_f16x2_f32", B.device, _ptr(B), B.stride(0), N, K, _rec(b_amax, "b_amax"), _ptr(out))
     return out
 
 
@@ -254,18 +227,14 @@ def fc_fwd_relu_packed(a: torch.Tensor, pack: torch.Tensor, bias: torch.Tensor, 
     nws = lib.mi355ppo_fc_fwd_workspace_bytes(M, N, K)       # rollout-sized batches: K split over the grid, partials in a workspace
     if amax is not None:
         ws = _workspace(a.device, nws) if nws else None
-        with _on(a.device):
-            st = lib.mi355ppo_fc_fwd_relu_packed_f16x2_f32(_ptr(a), lda, _ptr(pack), _ptr(bias), _ptr(out), M, N, K, _ptr(ws), ws.numel() if nws else 0,
-                                                           _rec(amax[0], "a_amax"), None if nws else _rec(amax[1], "h_amax"), _stream(a.device))
-        _lib.check(st, "mi355ppo_fc_fwd_relu_packed_f16x2_f32")
+        _launch("mi355ppo_fc_fwd_relu_packed_f16x2_f32", a.device, _ptr(a), lda, _ptr(pack), _ptr(bias), _ptr(out), M, N, K, _ptr(ws),
+                ws.numel() if nws else 0, _rec(amax[0], "a_amax"), None if nws else _rec(amax[1], "h_amax"))
         return out
-    with _on(a.device):
-        if nws:
-            ws = _workspace(a.device, nws)
-            st = lib.mi355ppo_fc_fwd_relu_packed_ws_f32(_ptr(a), lda, _ptr(pack), _ptr(bias), _ptr(out), M, N, K, _ptr(ws), ws.numel(), _stream(a.device))
-        else:
-            st = lib.mi355ppo_fc_fwd_relu_packed_f32(_ptr(a), lda, _ptr(pack), _ptr(bias), _ptr(out), M, N, K, _stream(a.device))
-    _lib.check(st, "mi355ppo_fc_fwd_relu_packed_f32")
+    if nws:
+        ws = _workspace(a.device, nws)
+        _launch("mi355ppo_fc_fwd_relu_packed_ws_f32", a.device, _ptr(a), lda, _ptr(pack), _ptr(bias), _ptr(out), M, N, K, _ptr(ws), ws.numel())
+    else:
+        _launch("mi355ppo_fc_fwd_relu_packed_f32", a.device, _ptr(a), lda, _ptr(pack), _ptr(bias), _ptr(out), M, N, K)
     return out
 
 
@@ -304,17 +273,13 @@ def fc_heads_act_categorical(a: torch.Tensor, pack: torch.Tensor, fc_bias: torch
     if noise_exp1 is not None:
         _chk(noise_exp1, torch.float32, "noise_exp1", (M, A))
     ws = _workspace(dev, lib.mi355ppo_fc_fwd_workspace_bytes(M, H, K))
-    with _on(dev):
-        if amax is not None:        # ``amax`` = a's amax record, ``pack`` an f16x2 pack
-            st = lib.mi355ppo_fc_heads_act_categorical_f16x2_f32(_ptr(a), lda, _ptr(pack), _ptr(fc_bias), _ptr(Wa), _ptr(ba), _ptr(Wc), _ptr(bc), M, A,
-                                                                 H, K, _ptr(noise_exp1), int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
-                                                                 _ptr(offset_base), _ptr(a64), _ptr(af), _ptr(lp), _ptr(val), None, _ptr(ws),
-                                                                 ws.numel(), _rec(amax, "a_amax"), _stream(dev))
-        else:
-            st = lib.mi355ppo_fc_heads_act_categorical_f32(_ptr(a), lda, _ptr(pack), _ptr(fc_bias), _ptr(Wa), _ptr(ba), _ptr(Wc), _ptr(bc), M, A, H, K,
-                                                           _ptr(noise_exp1), int(seed) & (2**64 - 1), int(offset) & (2**64 - 1), _ptr(offset_base),
-                                                           _ptr(a64), _ptr(af), _ptr(lp), _ptr(val), None, _ptr(ws), ws.numel(), _stream(dev))
-    _lib.check(st, "mi355ppo_fc_heads_act_categorical_f32")
+    args = (_ptr(a), lda, _ptr(pack), _ptr(fc_bias), _ptr(Wa), _ptr(ba), _ptr(Wc), _ptr(bc), M, A, H, K, _ptr(noise_exp1),
+            int(seed) & (2**64 - 1), int(offset) & (2**64 - 1), _ptr(offset_base), _ptr(a64), _ptr(af), _ptr(lp), _ptr(val), None, _ptr(ws),
+            ws.numel())
+    if amax is not None:        # ``amax`` = a's amax record, ``pack`` an f16x2 pack
+        _launch("mi355ppo_fc_heads_act_categorical_f16x2_f32", dev, *args, _rec(amax, "a_amax"))
+    else:
+        _launch("mi355ppo_fc_heads_act_categorical_f32", dev, *args)
     return a64, af, lp, val
 
 
@@ -334,18 +299,14 @@ def fc_dgrad_mask_packed(dz: torch.Tensor, pack: torch.Tensor, act_in: torch.Ten
     if amax is not None:            # the f16 split: ``amax = (dz_rec, out_rec | None)``, ``pack = fc_pack_f16x2(B)``
         if bits is not None:
             _chk(bits, torch.int32, "bits", (mask_words(M * N),))
-        with _on(dz.device):
-            st = lib.mi355ppo_fc_dgrad_packed_f16x2_f32(_ptr(dz), lddz, _ptr(pack), _ptr(act_in), _ptr(bits), _ptr(out), M, N, K,
-                                                        _rec(amax[0], "dz_amax"), _rec(amax[1], "da_amax"), _stream(dz.device))
-        _lib.check(st, "mi355ppo_fc_dgrad_packed_f16x2_f32")
+        _launch("mi355ppo_fc_dgrad_packed_f16x2_f32", dz.device, _ptr(dz), lddz, _ptr(pack), _ptr(act_in), _ptr(bits), _ptr(out), M, N, K,
+                _rec(amax[0], "dz_amax"), _rec(amax[1], "da_amax"))
         return out
-    with _on(dz.device):
-        if bits is not None:
-            _chk(bits, torch.int32, "bits", (mask_words(M * N),))
-            st = lib.mi355ppo_fc_dgrad_maskbits_packed_f32(_ptr(dz), lddz, _ptr(pack), _ptr(bits), _ptr(out), M, N, K, _stream(dz.device))
-        else:
-            st = lib.mi355ppo_fc_dgrad_mask_packed_f32(_ptr(dz), lddz, _ptr(pack), _ptr(act_in), _ptr(out), M, N, K, _stream(dz.device))
-    _lib.check(st, "mi355ppo_fc_dgrad_mask_packed_f32")
+    if bits is not None:
+        _chk(bits, torch.int32, "bits", (mask_words(M * N),))
+        _launch("mi355ppo_fc_dgrad_maskbits_packed_f32", dz.device, _ptr(dz), lddz, _ptr(pack), _ptr(bits), _ptr(out), M, N, K)
+    else:
+        _launch("mi355ppo_fc_dgrad_mask_packed_f32", dz.device, _ptr(dz), lddz, _ptr(pack), _ptr(act_in), _ptr(out), M, N, K)
     return out
 
 
@@ -380,7 +341,6 @@ def unpack_mask_bits(bits: torch.Tensor, shape) -> torch.Tensor:
 def conv1q_fwd_amax(obs_u8: torch.Tensor, pack: torch.Tensor, bias: torch.Tensor, inds: torch.Tensor | None, out: torch.Tensor,
                     bits: torch.Tensor | None, dst_amax: torch.Tensor) -> torch.Tensor:
     """Layer-1 forward on kernel Q that also folds ``max(out)`` into the amax record ``dst_amax`` (and writes the mask bits when given)."""
-    lib = _lib.load()
     _chk(obs_u8, torch.uint8, "src")
     images = obs_u8.shape[0] if inds is None else inds.numel()
     if inds is not None:
@@ -390,17 +350,14 @@ def conv1q_fwd_amax(obs_u8: torch.Tensor, pack: torch.Tensor, bias: torch.Tensor
     _chk(out, torch.float32, "out", (images, 20, 20, 32))
     if bits is not None:
         _chk(bits, torch.int32, "bits", (mask_words(out.numel()),))
-    with _on(obs_u8.device):
-        st = lib.mi355ppo_cnn_conv1q_fwd_amax(_ptr(obs_u8), _ptr(inds), _ptr(pack), _ptr(bias), _ptr(out), _ptr(bits), images,
-                                              _rec(dst_amax, "dst_amax"), _stream(obs_u8.device))
-    _lib.check(st, "mi355ppo_cnn_conv1q_fwd_amax")
+    _launch("mi355ppo_cnn_conv1q_fwd_amax", obs_u8.device, _ptr(obs_u8), _ptr(inds), _ptr(pack), _ptr(bias), _ptr(out), _ptr(bits), images,
+            _rec(dst_amax, "dst_amax"))
     return out
 
 
 def conv1q_fwd_bits(obs_u8: torch.Tensor, pack: torch.Tensor, bias: torch.Tensor, inds: torch.Tensor | None, out: torch.Tensor,
                     bits: torch.Tensor) -> torch.Tensor:
     """Layer-1 forward on kernel Q that also writes ``(out > 0)`` as bits (``bits``: int32, ``out.numel() // 32`` words)."""
-    lib = _lib.load()
     _chk(obs_u8, torch.uint8, "src")
     images = obs_u8.shape[0] if inds is None else inds.numel()
     if inds is not None:
@@ -409,9 +366,7 @@ def conv1q_fwd_bits(obs_u8: torch.Tensor, pack: torch.Tensor, bias: torch.Tensor
     _chk(bias, torch.float32, "bias", (32,))
     _chk(out, torch.float32, "out", (images, 20, 20, 32))
     _chk(bits, torch.int32, "bits", (mask_words(out.numel()),))
-    with _on(obs_u8.device):
-        st = lib.mi355ppo_cnn_conv1q_fwd_bits(_ptr(obs_u8), _ptr(inds), _ptr(pack), _ptr(bias), _ptr(out), _ptr(bits), images, _stream(obs_u8.device))
-    _lib.check(st, "mi355ppo_cnn_conv1q_fwd_bits")
+    _launch("mi355ppo_cnn_conv1q_fwd_bits", obs_u8.device, _ptr(obs_u8), _ptr(inds), _ptr(pack), _ptr(bias), _ptr(out), _ptr(bits), images)
     return out
 
 
@@ -431,18 +386,14 @@ def conv_fwd_packed(src: torch.Tensor, pack: torch.Tensor, bias: torch.Tensor, l
     if amax is not None:            # the f16 split: ``amax = (src_rec, out_rec | None)``, ``pack = conv_zpack_f16x2(W, layer, MODE_FWD)``
         if bits is not None:
             _chk(bits, torch.int32, "bits", (mask_words(out.numel()),))
-        with _on(src.device):
-            st = lib.mi355ppo_cnn_conv_fwd_packed_f16x2_f32(_ptr(src), _ptr(pack), _ptr(bias), _ptr(out), _ptr(bits), images, layer,
-                                                            _rec(amax[0], "src_amax"), _rec(amax[1], "dst_amax"), _stream(src.device))
-        _lib.check(st, "mi355ppo_cnn_conv_fwd_packed_f16x2_f32")
+        _launch("mi355ppo_cnn_conv_fwd_packed_f16x2_f32", src.device, _ptr(src), _ptr(pack), _ptr(bias), _ptr(out), _ptr(bits), images,
+                layer, _rec(amax[0], "src_amax"), _rec(amax[1], "dst_amax"))
         return out
-    with _on(src.device):
-        if bits is not None:
-            _chk(bits, torch.int32, "bits", (mask_words(out.numel()),))
-            st = lib.mi355ppo_cnn_conv_fwd_packed_bits_f32(_ptr(src), _ptr(pack), _ptr(bias), _ptr(out), _ptr(bits), images, layer, _stream(src.device))
-        else:
-            st = lib.mi355ppo_cnn_conv_fwd_packed_f32(_ptr(src), _ptr(pack), _ptr(bias), _ptr(out), images, layer, _stream(src.device))
-    _lib.check(st, "mi355ppo_cnn_conv_fwd_packed_f32")
+    if bits is not None:
+        _chk(bits, torch.int32, "bits", (mask_words(out.numel()),))
+        _launch("mi355ppo_cnn_conv_fwd_packed_bits_f32", src.device, _ptr(src), _ptr(pack), _ptr(bias), _ptr(out), _ptr(bits), images, layer)
+    else:
+        _launch("mi355ppo_cnn_conv_fwd_packed_f32", src.device, _ptr(src), _ptr(pack), _ptr(bias), _ptr(out), images, layer)
     return out
 
 
@@ -464,18 +415,14 @@ def conv_dgrad_packed(dz: torch.Tensor, pack: torch.Tensor, act_in: torch.Tensor
     if amax is not None:            # the f16 split: ``amax = (dz_rec, out_rec | None)``
         if bits is not None:
             _chk(bits, torch.int32, "bits", (mask_words(out.numel()),))
-        with _on(dz.device):
-            st = lib.mi355ppo_cnn_conv_dgrad_packed_f16x2_f32(_ptr(dz), _ptr(pack), _ptr(act_in), _ptr(bits), _ptr(out), images, layer,
-                                                              _rec(amax[0], "dz_amax"), _rec(amax[1], "dsrc_amax"), _stream(dz.device))
-        _lib.check(st, "mi355ppo_cnn_conv_dgrad_packed_f16x2_f32")
+        _launch("mi355ppo_cnn_conv_dgrad_packed_f16x2_f32", dz.device, _ptr(dz), _ptr(pack), _ptr(act_in), _ptr(bits), _ptr(out), images,
+                layer, _rec(amax[0], "dz_amax"), _rec(amax[1], "dsrc_amax"))
         return out
-    with _on(dz.device):
-        if bits is not None:
-            _chk(bits, torch.int32, "bits", (mask_words(out.numel()),))
-            st = lib.mi355ppo_cnn_conv_dgrad_packed_bits_f32(_ptr(dz), _ptr(pack), _ptr(bits), _ptr(out), images, layer, _stream(dz.device))
-        else:
-            st = lib.mi355ppo_cnn_conv_dgrad_packed_f32(_ptr(dz), _ptr(pack), _ptr(act_in), _ptr(out), images, layer, _stream(dz.device))
-    _lib.check(st, "mi355ppo_cnn_conv_dgrad_packed_f32")
+    if bits is not None:
+        _chk(bits, torch.int32, "bits", (mask_words(out.numel()),))
+        _launch("mi355ppo_cnn_conv_dgrad_packed_bits_f32", dz.device, _ptr(dz), _ptr(pack), _ptr(bits), _ptr(out), images, layer)
+    else:
+        _launch("mi355ppo_cnn_conv_dgrad_packed_f32", dz.device, _ptr(dz), _ptr(pack), _ptr(act_in), _ptr(out), images, layer)
     return out
 
 
@@ -511,14 +458,10 @@ def fc_wgrad(dz: torch.Tensor, a: torch.Tensor, hwc_channels: int = 0, out: torc
     _chk(out, torch.float32, "out", (N, K))
     ws = _workspace(dz.device, lib.mi355ppo_fc_wgrad_workspace_bytes(M, N, K))
     if amax is not None:            # kernel W on the f16 split: ``amax = (dz_rec, a_rec)``
-        with _on(dz.device):
-            st = lib.mi355ppo_fc_wgrad_f16x2_f32(_ptr(dz), lddz, _ptr(a), _ptr(out), M, N, K, int(hwc_channels), _ptr(ws), ws.numel(),
-                                                 _rec(amax[0], "dz_amax"), _rec(amax[1], "a_amax"), _stream(dz.device))
-        _lib.check(st, "mi355ppo_fc_wgrad_f16x2_f32")
+        _launch("mi355ppo_fc_wgrad_f16x2_f32", dz.device, _ptr(dz), lddz, _ptr(a), _ptr(out), M, N, K, int(hwc_channels), _ptr(ws),
+                ws.numel(), _rec(amax[0], "dz_amax"), _rec(amax[1], "a_amax"))
         return out
-    with _on(dz.device):
-        st = lib.mi355ppo_fc_wgrad_f32(_ptr(dz), lddz, _ptr(a), _ptr(out), M, N, K, int(hwc_channels), _ptr(ws), ws.numel(), _stream(dz.device))
-    _lib.check(st, "mi355ppo_fc_wgrad_f32")
+    _launch("mi355ppo_fc_wgrad_f32", dz.device, _ptr(dz), lddz, _ptr(a), _ptr(out), M, N, K, int(hwc_channels), _ptr(ws), ws.numel())
     return out
 
 
@@ -630,14 +573,12 @@ class _Buffers:
                 buf = hit[1]
             outs.append(buf)
         W1, W2, W3, Wfc = (w.detach() for w in self.pack_params)
-        with _on(dev):
-            if f16:
-                if self.w_amax is None:
-                    self.w_amax = new_amax(3, dev)
-                st = lib.mi355ppo_nature_packs_f16x2_f32(_ptr(W1), _ptr(W2), _ptr(W3), _ptr(Wfc), *[_ptr(o) for o in outs], _ptr(self.w_amax), _stream(dev))
-            else:
-                st = lib.mi355ppo_nature_packs_f32(_ptr(W1), _ptr(W2), _ptr(W3), _ptr(Wfc), *[_ptr(o) for o in outs], _stream(dev))
-        _lib.check(st, "mi355ppo_nature_packs_f16x2_f32" if f16 else "mi355ppo_nature_packs_f32")
+        if f16:
+            if self.w_amax is None:
+                self.w_amax = new_amax(3, dev)
+            _launch("mi355ppo_nature_packs_f16x2_f32", dev, _ptr(W1), _ptr(W2), _ptr(W3), _ptr(Wfc), *[_ptr(o) for o in outs], _ptr(self.w_amax))
+        else:
+            _launch("mi355ppo_nature_packs_f32", dev, _ptr(W1), _ptr(W2), _ptr(W3), _ptr(Wfc), *[_ptr(o) for o in outs])
         for (k, w, _), buf in zip(keys, outs):
             self._bt[k] = ((self.weights_version, w._version, w.data_ptr()), buf)
         return True
@@ -954,7 +895,6 @@ class HeadsFn(torch.autograd.Function):
         """``relu_bufs``: the trunk's ``_Buffers`` when ``h`` is the output of ``LinearReLUHwcFn`` -- backward then returns the
         gradient with respect to that layer's PRE-activation (its ReLU mask applied here, where h and dh are in registers) and
         leaves its bias gradient in ``relu_bufs.fc_dz_from_heads``."""
-        lib = _lib.load()
         ctx.relu_bufs = relu_bufs
         M, H = h.shape
         A = Wa.shape[0]
@@ -963,10 +903,7 @@ class HeadsFn(torch.autograd.Function):
         _chk(Wc, torch.float32, "critic.weight", (1, H))
         logits = torch.empty((M, A), dtype=torch.float32, device=h.device)
         value = torch.empty((M, 1), dtype=torch.float32, device=h.device)
-        with _on(h.device):
-            st = lib.mi355ppo_heads_fwd_f32(_ptr(h), _ptr(Wa), _ptr(ba), _ptr(Wc), _ptr(bc), _ptr(logits), _ptr(value), M, A, H,
-                                            _stream(h.device))
-        _lib.check(st, "mi355ppo_heads_fwd_f32")
+        _launch("mi355ppo_heads_fwd_f32", h.device, _ptr(h), _ptr(Wa), _ptr(ba), _ptr(Wc), _ptr(bc), _ptr(logits), _ptr(value), M, A, H)
         ctx.save_for_backward(h, Wa, Wc)
         ctx.biases = (ba, bc)
         return logits, value
@@ -991,23 +928,18 @@ class HeadsFn(torch.autograd.Function):
             dWa, dba = torch.empty_like(Wa), torch.empty(A, dtype=torch.float32, device=dev)
             dWc, dbc = torch.empty_like(Wc), torch.empty(1, dtype=torch.float32, device=dev)
         ws = _workspace(dev, lib.mi355ppo_heads_bwd_workspace_bytes(M, A))
-        with _on(dev):
-            if bufs is not None and bufs.f16(h) and bufs.has_pass(M, dev):      # the FC layer's gradients will split dz: record max |dz| here
-                dbh = torch.empty(H, dtype=torch.float32, device=dev)
-                st = lib.mi355ppo_heads_bwd_relu_amax_f32(_ptr(h), _ptr(Wa), _ptr(Wc), _ptr(dlogits), _ptr(dvalue), _ptr(dh), dh.stride(0),
-                                                          _ptr(dWa), _ptr(dba), _ptr(dWc), _ptr(dbc), _ptr(dbh), M, A, H, _ptr(ws), ws.numel(),
-                                                          _ptr(bufs.owns(REC_DH, dh)), _stream(dev))
-                bufs.fc_dz_from_heads = (dh.data_ptr(), dbh)
-            elif bufs is not None:
-                dbh = torch.empty(H, dtype=torch.float32, device=dev)
-                st = lib.mi355ppo_heads_bwd_relu_f32(_ptr(h), _ptr(Wa), _ptr(Wc), _ptr(dlogits), _ptr(dvalue), _ptr(dh), dh.stride(0),
-                                                     _ptr(dWa), _ptr(dba), _ptr(dWc), _ptr(dbc), _ptr(dbh), M, A, H, _ptr(ws), ws.numel(),
-                                                     _stream(dev))
-                bufs.fc_dz_from_heads = (dh.data_ptr(), dbh)
+        if bufs is not None:
+            dbh = torch.empty(H, dtype=torch.float32, device=dev)
+            args = (_ptr(h), _ptr(Wa), _ptr(Wc), _ptr(dlogits), _ptr(dvalue), _ptr(dh), dh.stride(0), _ptr(dWa), _ptr(dba), _ptr(dWc), _ptr(dbc),
+                    _ptr(dbh), M, A, H, _ptr(ws), ws.numel())
+            if bufs.f16(h) and bufs.has_pass(M, dev):      # the FC layer's gradients will split dz: record max |dz| here
+                _launch("mi355ppo_heads_bwd_relu_amax_f32", dev, *args, _ptr(bufs.owns(REC_DH, dh)))
             else:
-                st = lib.mi355ppo_heads_bwd_f32(_ptr(h), _ptr(Wa), _ptr(Wc), _ptr(dlogits), _ptr(dvalue), _ptr(dh), _ptr(dWa),
-                                                _ptr(dba), _ptr(dWc), _ptr(dbc), M, A, H, _ptr(ws), ws.numel(), _stream(dev))
-        _lib.check(st, "mi355ppo_heads_bwd_relu_f32" if bufs is not None else "mi355ppo_heads_bwd_f32")
+                _launch("mi355ppo_heads_bwd_relu_f32", dev, *args)
+            bufs.fc_dz_from_heads = (dh.data_ptr(), dbh)
+        else:
+            _launch("mi355ppo_heads_bwd_f32", dev, _ptr(h), _ptr(Wa), _ptr(Wc), _ptr(dlogits), _ptr(dvalue), _ptr(dh), _ptr(dWa), _ptr(dba),
+                    _ptr(dWc), _ptr(dbc), M, A, H, _ptr(ws), ws.numel())
         if direct:
             return dh, None, None, None, None, None
         return dh, dWa, dba, dWc, dbc, None

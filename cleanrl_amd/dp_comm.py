@@ -18,6 +18,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
+from .ops import _launch
 
 MAX_WORLD = 8           # MI355PPO_DP_MAX_WORLD
 HANDLE_BYTES = 64       # MI355PPO_DP_HANDLE_BYTES
@@ -61,24 +62,21 @@ class PeerAllReduce:
             timeout_s = _setting()[1]
         self._comm = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.mi355ppo_dp_comm_create(self.world, self.rank, self.numel, float(timeout_s) * 1e3, ctypes.byref(self._comm)),
-                       "mi355ppo_dp_comm_create")
+            _lib.call("mi355ppo_dp_comm_create", self.world, self.rank, self.numel, float(timeout_s) * 1e3, ctypes.byref(self._comm))
             buf = ctypes.create_string_buffer(HANDLE_BYTES)
-            _lib.check(self.lib.mi355ppo_dp_comm_handle(self._comm, buf), "mi355ppo_dp_comm_handle")
+            _lib.call("mi355ppo_dp_comm_handle", self._comm, buf)
             handles = [None] * self.world
             dist.all_gather_object(handles, buf.raw, group=group)
             assert all(isinstance(h, bytes) and len(h) == HANDLE_BYTES for h in handles)
             if self.world > 1:
-                _lib.check(self.lib.mi355ppo_dp_comm_connect(self._comm, b"".join(handles)), "mi355ppo_dp_comm_connect")
+                _lib.call("mi355ppo_dp_comm_connect", self._comm, b"".join(handles))
         dist.barrier(group=group)           # every rank has mapped every segment before anybody's first flag arrives
 
     def all_reduce_sum_(self, flat: torch.Tensor) -> torch.Tensor:
         """``flat`` (f32, contiguous, on this communicator's device, 16-byte aligned) summed over the ranks in place, enqueued on the
         current stream.  Every rank must issue the same calls in the same order."""
         assert flat.dtype == torch.float32 and flat.is_contiguous() and flat.device == self.device and flat.numel() <= self.numel
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(self.lib.mi355ppo_dp_allreduce_sum_f32(self._comm, ctypes.c_void_p(flat.data_ptr()), flat.numel(), stream),
-                   "mi355ppo_dp_allreduce_sum_f32")
+        _launch("mi355ppo_dp_allreduce_sum_f32", self.device, self._comm, ctypes.c_void_p(flat.data_ptr()), flat.numel())
         return flat
 
     def status(self):

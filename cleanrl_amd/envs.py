@@ -279,22 +279,19 @@ class DeviceSyntheticAtariVecEnv:
     def _call(self, out, reward, done, advance, hwc=False):
         """Two launches per env step (csrc/synth_env.hip) instead of ~14 torch kernels: the rollout is short enough for
         the stand-in env's own launches to show up in env-steps/sec."""
-        from . import _lib
+        from .ops import _launch
 
-        lib = _lib.load()
         t = self.torch
         assert out.dtype == t.uint8 and out.is_contiguous() and tuple(out.shape) == (self.num_envs,) + ((84, 84, 4) if hwc else (4, 84, 84))
         if advance:
             assert reward.dtype == t.float32 and done.dtype == t.float32 and reward.is_contiguous() and done.is_contiguous()
             self._step += 1
         rel = self._step_rel if (advance and self._step_rel is not None) else None
-        fn = lib.mi355ppo_synth_atari_step_hwc_ctr_u8 if hwc else lib.mi355ppo_synth_atari_step_ctr_u8
-        st = fn(
-            self.planes.data_ptr(), self.pool, self.cursor.data_ptr(), self._seed, self._step if rel is None else rel,
-            self.step_base.data_ptr() if rel is not None else None, out.data_ptr(),
-            reward.data_ptr() if advance else None, done.data_ptr() if advance else None, self.num_envs, float(self.done_p),
-            int(advance), t.cuda.current_stream(self.device).cuda_stream)
-        _lib.check(st, "mi355ppo_synth_atari_step_u8")
+        _launch("mi355ppo_synth_atari_step_hwc_ctr_u8" if hwc else "mi355ppo_synth_atari_step_ctr_u8", self.planes.device,
+                self.planes.data_ptr(), self.pool, self.cursor.data_ptr(), self._seed, self._step if rel is None else rel,
+                self.step_base.data_ptr() if rel is not None else None, out.data_ptr(),
+                reward.data_ptr() if advance else None, done.data_ptr() if advance else None, self.num_envs, float(self.done_p),
+                int(advance))
         return out
 
     def obs_into(self, out):

@@ -17,6 +17,7 @@ import ctypes
 import torch
 
 from . import _lib
+from .ops import IMPALA_CHANNELS, _lstm_dims, _ptr_array, pqn_param_count, radam_schedule, trxl_dims  # noqa: F401  (one definition for both modules)
 
 LOSS_SCALARS = 7
 
@@ -26,23 +27,37 @@ def _p(t):
         return None
     if t.device.type != "cpu":
         raise TypeError("cleanrl_amd.host_ops works on CPU tensors only (CUDA tensors run the HIP kernels: cleanrl_amd.ops)")
-    assert t.is_contiguous(), "host twins take contiguous tensors"
+    if not t.is_contiguous():
+        raise ValueError("host twins take contiguous tensors")
     return ctypes.c_void_p(t.data_ptr())
+
+
+def _out(t, dtype, numel, name):
+    """Pointer of a caller-owned tensor that a twin WRITES ``numel`` elements of ``dtype`` through: unlike an input it cannot be
+    coerced into a copy, so a wrong dtype or a short tensor is refused here instead of overrunning host memory."""
+    ptr = _p(t)
+    if t is not None and t.dtype != dtype:
+        raise TypeError(f"{name}: expected dtype {dtype}, got {t.dtype}")
+    if t is not None and t.numel() < numel:
+        raise ValueError(f"{name}: expected {numel} elements, got {t.numel()}")
+    return ptr
 
 
 def _f32(t):
     return t.detach().to(torch.float32).contiguous()
 
 
+def _i64(t):
+    return t.detach().to(torch.int64).contiguous()
+
+
 def gae(rewards, dones, values, next_done, next_value, gamma, gae_lambda):
     """ppo.py:218-231 through ``mi355ppo_gae_f32_cpu`` -> (advantages, returns); bit-equal to the reference's loop."""
-    lib = _lib.load()
     T, N = rewards.shape
     r, d, v = _f32(rewards), _f32(dones), _f32(values)
     nd, nv = _f32(next_done).reshape(-1), _f32(next_value).reshape(-1)
     adv, ret = torch.empty_like(r), torch.empty_like(r)
-    _lib.check(lib.mi355ppo_gae_f32_cpu(_p(r), _p(d), _p(v), _p(nd), _p(nv), _p(adv), _p(ret), T, N, float(gamma),
-                                        float(gae_lambda)), "mi355ppo_gae_f32_cpu")
+    _lib.call("mi355ppo_gae_f32_cpu", _p(r), _p(d), _p(v), _p(nd), _p(nv), _p(adv), _p(ret), T, N, float(gamma), float(gae_lambda))
     return adv, ret
 
 
@@ -52,16 +67,14 @@ class _CategoricalLossTwin(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, value, mb_inds, b_actions, b_logprobs, b_advantages, b_returns, b_values, hp):
-        lib = _lib.load()
         M, A = logits.shape
         lg, vl = _f32(logits), _f32(value).reshape(-1)
         inds = mb_inds.to(torch.int64).contiguous()
         scalars = torch.empty(LOSS_SCALARS)
         dlogits, dvalue = torch.empty_like(lg), torch.empty_like(vl)
-        _lib.check(lib.mi355ppo_loss_categorical_fwd_bwd_f32_cpu(
-            _p(lg), _p(vl), _p(inds), _p(_f32(b_actions)), _p(_f32(b_logprobs)), _p(_f32(b_advantages)), _p(_f32(b_returns)),
-            _p(_f32(b_values)), M, A, hp["clip_coef"], hp["ent_coef"], hp["vf_coef"], int(hp["norm_adv"]), int(hp["clip_vloss"]),
-            None, _p(scalars), _p(dlogits), _p(dvalue)), "mi355ppo_loss_categorical_fwd_bwd_f32_cpu")
+        _lib.call("mi355ppo_loss_categorical_fwd_bwd_f32_cpu", _p(lg), _p(vl), _p(inds), _p(_f32(b_actions)), _p(_f32(b_logprobs)),
+                  _p(_f32(b_advantages)), _p(_f32(b_returns)), _p(_f32(b_values)), M, A, hp["clip_coef"], hp["ent_coef"], hp["vf_coef"],
+                  int(hp["norm_adv"]), int(hp["clip_vloss"]), None, _p(scalars), _p(dlogits), _p(dvalue))
         ctx.save_for_backward(dlogits, dvalue.reshape(value.shape))
         ctx.mark_non_differentiable(scalars)
         return scalars[0].clone(), scalars
@@ -77,16 +90,14 @@ class _NormalLossTwin(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, mean, logstd, value, mb_inds, b_actions, b_logprobs, b_advantages, b_returns, b_values, hp):
-        lib = _lib.load()
         M, D = mean.shape
         mu, ls, vl = _f32(mean), _f32(logstd).reshape(-1), _f32(value).reshape(-1)
         inds = mb_inds.to(torch.int64).contiguous()
         scalars = torch.empty(LOSS_SCALARS)
         dmean, dlogstd, dvalue = torch.empty_like(mu), torch.empty_like(ls), torch.empty_like(vl)
-        _lib.check(lib.mi355ppo_loss_normal_fwd_bwd_f32_cpu(
-            _p(mu), _p(ls), _p(vl), _p(inds), _p(_f32(b_actions)), _p(_f32(b_logprobs)), _p(_f32(b_advantages)), _p(_f32(b_returns)),
-            _p(_f32(b_values)), M, D, hp["clip_coef"], hp["ent_coef"], hp["vf_coef"], int(hp["norm_adv"]), int(hp["clip_vloss"]),
-            None, _p(scalars), _p(dmean), _p(dlogstd), _p(dvalue)), "mi355ppo_loss_normal_fwd_bwd_f32_cpu")
+        _lib.call("mi355ppo_loss_normal_fwd_bwd_f32_cpu", _p(mu), _p(ls), _p(vl), _p(inds), _p(_f32(b_actions)), _p(_f32(b_logprobs)),
+                  _p(_f32(b_advantages)), _p(_f32(b_returns)), _p(_f32(b_values)), M, D, hp["clip_coef"], hp["ent_coef"], hp["vf_coef"],
+                  int(hp["norm_adv"]), int(hp["clip_vloss"]), None, _p(scalars), _p(dmean), _p(dlogstd), _p(dvalue))
         ctx.save_for_backward(dmean, dlogstd.reshape(logstd.shape), dvalue.reshape(value.shape))
         ctx.mark_non_differentiable(scalars)
         return scalars[0].clone(), scalars
@@ -120,120 +131,98 @@ def ppo_loss_normal(mean, logstd, newvalue, mb_inds, b_actions, b_logprobs, b_ad
 def categorical_sample(logits, noise_exp1=None, seed=0, offset=0):
     """``mi355ppo_categorical_sample_f32_cpu`` -> (action int64, logprob, entropy).  With ``noise_exp1`` None the draws come from
     the device kernel's Philox stream (same words for the same (seed, offset, row))."""
-    lib = _lib.load()
     lg = _f32(logits)
     B, A = lg.shape
     act, lp, ent = torch.empty(B, dtype=torch.int64), torch.empty(B), torch.empty(B)
     nz = _f32(noise_exp1) if noise_exp1 is not None else None
-    _lib.check(lib.mi355ppo_categorical_sample_f32_cpu(_p(lg), _p(nz), int(seed), int(offset), _p(act), None, _p(lp), _p(ent), B, A),
-               "mi355ppo_categorical_sample_f32_cpu")
+    _lib.call("mi355ppo_categorical_sample_f32_cpu", _p(lg), _p(nz), int(seed), int(offset), _p(act), None, _p(lp), _p(ent), B, A)
     return act, lp, ent
 
 
 def categorical_logprob_entropy(logits, action):
-    lib = _lib.load()
     lg = _f32(logits)
     B, A = lg.shape
     act = action.to(torch.int64).contiguous()
     lp, ent = torch.empty(B), torch.empty(B)
-    _lib.check(lib.mi355ppo_categorical_logprob_entropy_f32_cpu(_p(lg), _p(act), None, _p(lp), _p(ent), B, A),
-               "mi355ppo_categorical_logprob_entropy_f32_cpu")
+    _lib.call("mi355ppo_categorical_logprob_entropy_f32_cpu", _p(lg), _p(act), None, _p(lp), _p(ent), B, A)
     return lp, ent
 
 
 def categorical_logprob_entropy_bwd(logits, action, g_logprob, g_entropy):
-    lib = _lib.load()
     lg = _f32(logits)
     B, A = lg.shape
     act = action.to(torch.int64).contiguous()
     out = torch.empty_like(lg)
-    _lib.check(lib.mi355ppo_categorical_logprob_entropy_bwd_f32_cpu(
-        _p(lg), _p(act), None, _p(_f32(g_logprob)) if g_logprob is not None else None,
-        _p(_f32(g_entropy)) if g_entropy is not None else None, _p(out), B, A), "mi355ppo_categorical_logprob_entropy_bwd_f32_cpu")
+    _lib.call("mi355ppo_categorical_logprob_entropy_bwd_f32_cpu", _p(lg), _p(act), None,
+              _p(_f32(g_logprob)) if g_logprob is not None else None, _p(_f32(g_entropy)) if g_entropy is not None else None, _p(out), B, A)
     return out
 
 
 def normal_sample(mean, logstd, noise=None, seed=0, offset=0):
-    lib = _lib.load()
     mu, ls = _f32(mean), _f32(logstd).reshape(-1)
     B, D = mu.shape
     act, lp, ent = torch.empty_like(mu), torch.empty(B), torch.empty(B)
     nz = _f32(noise) if noise is not None else None
-    _lib.check(lib.mi355ppo_normal_sample_f32_cpu(_p(mu), _p(ls), _p(nz), int(seed), int(offset), _p(act), _p(lp), _p(ent), B, D),
-               "mi355ppo_normal_sample_f32_cpu")
+    _lib.call("mi355ppo_normal_sample_f32_cpu", _p(mu), _p(ls), _p(nz), int(seed), int(offset), _p(act), _p(lp), _p(ent), B, D)
     return act, lp, ent
 
 
 def normal_logprob_entropy(mean, logstd, action):
-    lib = _lib.load()
     mu, ls, ac = _f32(mean), _f32(logstd).reshape(-1), _f32(action)
     B, D = mu.shape
     lp, ent = torch.empty(B), torch.empty(B)
-    _lib.check(lib.mi355ppo_normal_logprob_entropy_f32_cpu(_p(mu), _p(ls), _p(ac), _p(lp), _p(ent), B, D),
-               "mi355ppo_normal_logprob_entropy_f32_cpu")
+    _lib.call("mi355ppo_normal_logprob_entropy_f32_cpu", _p(mu), _p(ls), _p(ac), _p(lp), _p(ent), B, D)
     return lp, ent
 
 
 def normal_logprob_entropy_bwd(mean, logstd, action, g_logprob, g_entropy):
-    lib = _lib.load()
     mu, ls, ac = _f32(mean), _f32(logstd).reshape(-1), _f32(action)
     B, D = mu.shape
     dmean, dls = torch.empty_like(mu), torch.empty_like(mu)
-    _lib.check(lib.mi355ppo_normal_logprob_entropy_bwd_f32_cpu(
-        _p(mu), _p(ls), _p(ac), _p(_f32(g_logprob)) if g_logprob is not None else None,
-        _p(_f32(g_entropy)) if g_entropy is not None else None, _p(dmean), _p(dls), B, D), "mi355ppo_normal_logprob_entropy_bwd_f32_cpu")
+    _lib.call("mi355ppo_normal_logprob_entropy_bwd_f32_cpu", _p(mu), _p(ls), _p(ac), _p(_f32(g_logprob)) if g_logprob is not None else None,
+              _p(_f32(g_entropy)) if g_entropy is not None else None, _p(dmean), _p(dls), B, D)
     return dmean, dls
+
+
+def _flat4(params, grads, exp_avg, exp_avg_sq):
+    n = params.numel()
+    return [_out(t, torch.float32, n, nm) for t, nm in ((params, "params"), (grads, "grads"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq"))]
 
 
 def clip_adam_(params, grads, exp_avg, exp_avg_sq, step, lr, max_grad_norm, grad_scale=1.0, beta1=0.9, beta2=0.999, eps=1e-5):
     """In place on flat f32 CPU buffers (``mi355ppo_clip_adam_f32_cpu``): grads * grad_scale -> global-norm clip -> Adam; the
     gradient buffer is zeroed.  Returns the pre-clip norm."""
-    lib = _lib.load()
-    for t in (params, grads, exp_avg, exp_avg_sq):
-        assert t.dtype == torch.float32 and t.dim() == 1
     norm = torch.empty(1)
-    _lib.check(lib.mi355ppo_clip_adam_f32_cpu(_p(params), _p(grads), _p(exp_avg), _p(exp_avg_sq), params.numel(), float(grad_scale),
-                                              float(max_grad_norm), float(lr), beta1, beta2, eps, int(step), _p(norm)),
-               "mi355ppo_clip_adam_f32_cpu")
+    _lib.call("mi355ppo_clip_adam_f32_cpu", *_flat4(params, grads, exp_avg, exp_avg_sq), params.numel(), float(grad_scale),
+              float(max_grad_norm), float(lr), beta1, beta2, eps, int(step), _p(norm))
     return norm
 
 
 def obs_u8_to_f32(src_u8, inds=None, scale_255=True):
-    lib = _lib.load()
     src = src_u8.contiguous()
     rows_total = src.shape[0]
     row_bytes = src.numel() // max(rows_total, 1)
     idx = inds.to(torch.int64).contiguous() if inds is not None else None
     rows = idx.numel() if idx is not None else rows_total
     out = torch.empty((rows,) + tuple(src.shape[1:]), dtype=torch.float32)
-    _lib.check(lib.mi355ppo_obs_u8_to_f32_cpu(_p(src), _p(idx), _p(out), rows, row_bytes, int(bool(scale_255))),
-               "mi355ppo_obs_u8_to_f32_cpu")
+    _lib.call("mi355ppo_obs_u8_to_f32_cpu", _p(src), _p(idx), _p(out), rows, row_bytes, int(bool(scale_255)))
     return out
-
-
-def _lstm_dims(gx, done):
-    T, B, G = gx.shape
-    assert G % 4 == 0 and tuple(done.shape) == (T, B), "gx (T,B,4H), done (T,B)"
-    return T, B, G // 4
 
 
 def lstm_seq_forward(gx, w_hh, h0, c0, done, record: bool = False):
     """The done-masked LSTM scan (ppo_atari_lstm.py:140-158) through ``mi355ppo_lstm_seq_fwd_f32_cpu`` -> (h, hT, cT, record | None);
     gx (T,B,4H), w_hh (4H,H), h0 / c0 (B,H), done (T,B).  Same arithmetic as the device scan (csrc/lstm_rows.h)."""
-    lib = _lib.load()
     T, B, H = _lstm_dims(gx, done)
     g, w, h0, c0, d = _f32(gx), _f32(w_hh), _f32(h0), _f32(c0), _f32(done)
     h, hT, cT = torch.empty((T, B, H)), torch.empty((B, H)), torch.empty((B, H))
     rec = torch.empty(7 * T * B * H) if record else None
-    _lib.check(lib.mi355ppo_lstm_seq_fwd_f32_cpu(_p(g), _p(w), _p(h0), _p(c0), _p(d), _p(h), _p(hT), _p(cT), _p(rec), T, B, H),
-               "mi355ppo_lstm_seq_fwd_f32_cpu")
+    _lib.call("mi355ppo_lstm_seq_fwd_f32_cpu", _p(g), _p(w), _p(h0), _p(c0), _p(d), _p(h), _p(hT), _p(cT), _p(rec), T, B, H)
     return h, hT, cT, rec
 
 
 def lstm_seq_backward(dh, dhT, dcT, record, w_hh, done, want_dh0: bool = True, want_dc0: bool = True):
     """Backward of ``lstm_seq_forward`` through ``mi355ppo_lstm_seq_bwd_f32_cpu`` -> (dgx (T,B,4H), dh0 | None, dc0 | None);
     dhT / dcT may be None (= zeros)."""
-    lib = _lib.load()
     T, B, H = dh.shape
     d, w, g = _f32(done), _f32(w_hh), _f32(dh)
     dhT = None if dhT is None else _f32(dhT)
@@ -241,14 +230,11 @@ def lstm_seq_backward(dh, dhT, dcT, record, w_hh, done, want_dh0: bool = True, w
     dgx = torch.empty((T, B, 4 * H))
     dh0 = torch.empty((B, H)) if want_dh0 else None
     dc0 = torch.empty((B, H)) if want_dc0 else None
-    _lib.check(lib.mi355ppo_lstm_seq_bwd_f32_cpu(_p(g), _p(dhT), _p(dcT), _p(record), _p(w), _p(d), _p(dgx), _p(dh0), _p(dc0), T, B, H),
-               "mi355ppo_lstm_seq_bwd_f32_cpu")
+    _lib.call("mi355ppo_lstm_seq_bwd_f32_cpu", _p(g), _p(dhT), _p(dcT), _p(record), _p(w), _p(d), _p(dgx), _p(dh0), _p(dc0), T, B, H)
     return dgx, dh0, dc0
 
 
 def _trxl_args(memory, ep, rows, pos, mask, pe, gamma, beta, q):
-    from .ops import trxl_dims
-
     E, T, layers, D, B, L, H = trxl_dims(memory, rows, q)
     m, g, b, qq = _f32(memory), _f32(gamma), _f32(beta), _f32(q)
     e, r = ep.to(torch.int64).contiguous(), rows.to(torch.int64).contiguous()
@@ -261,33 +247,22 @@ def _trxl_args(memory, ep, rows, pos, mask, pe, gamma, beta, q):
 def trxl_attn_forward(memory, layer, ep, rows, pos, mask, pe, gamma, beta, q):
     """The TrXL memory attention of one layer through ``mi355ppo_trxl_attn_fwd_f32_cpu`` -> (u (B,H,d), stats (B,H,2)); same
     arithmetic as the device kernel (csrc/trxl_rows.h).  An out-of-range index raises."""
-    lib = _lib.load()
     (E, T, layers, D, B, L, H), (m, e, r, ps, k, p, g, b, qq) = _trxl_args(memory, ep, rows, pos, mask, pe, gamma, beta, q)
     u, stats = torch.empty((B, H, D // H)), torch.empty((B, H, 2))
-    _lib.check(lib.mi355ppo_trxl_attn_fwd_f32_cpu(_p(m), E, T, layers, int(layer), _p(e), _p(r), _p(ps), _p(k), _p(p),
-                                                  0 if p is None else p.shape[0], _p(g), _p(b), _p(qq), _p(u), _p(stats), B, L, D, H),
-               "mi355ppo_trxl_attn_fwd_f32_cpu")
+    _lib.call("mi355ppo_trxl_attn_fwd_f32_cpu", _p(m), E, T, layers, int(layer), _p(e), _p(r), _p(ps), _p(k), _p(p),
+              0 if p is None else p.shape[0], _p(g), _p(b), _p(qq), _p(u), _p(stats), B, L, D, H)
     return u, stats
 
 
 def trxl_attn_backward(memory, layer, ep, rows, pos, mask, pe, gamma, beta, q, u, stats, du):
     """Backward of ``trxl_attn_forward`` through ``mi355ppo_trxl_attn_bwd_f32_cpu`` -> (dq (B,H,d), dgamma (D), dbeta (D))."""
-    lib = _lib.load()
     (E, T, layers, D, B, L, H), (m, e, r, ps, k, p, g, b, qq) = _trxl_args(memory, ep, rows, pos, mask, pe, gamma, beta, q)
     dq, rows_ws = torch.empty((B, H, D // H)), torch.empty((2, B, D))
     dgamma, dbeta = torch.empty(D), torch.empty(D)
-    _lib.check(lib.mi355ppo_trxl_attn_bwd_f32_cpu(_p(m), E, T, layers, int(layer), _p(e), _p(r), _p(ps), _p(k), _p(p),
-                                                  0 if p is None else p.shape[0], _p(g), _p(b), _p(qq), _p(_f32(u)), _p(_f32(stats)),
-                                                  _p(_f32(du)), _p(dq), _p(rows_ws), _p(dgamma), _p(dbeta), B, L, D, H),
-               "mi355ppo_trxl_attn_bwd_f32_cpu")
+    _lib.call("mi355ppo_trxl_attn_bwd_f32_cpu", _p(m), E, T, layers, int(layer), _p(e), _p(r), _p(ps), _p(k), _p(p),
+              0 if p is None else p.shape[0], _p(g), _p(b), _p(qq), _p(_f32(u)), _p(_f32(stats)), _p(_f32(du)), _p(dq), _p(rows_ws),
+              _p(dgamma), _p(dbeta), B, L, D, H)
     return dq, dgamma, dbeta
-
-
-IMPALA_CHANNELS = (16, 32, 32)
-
-
-def _ptrs(ts):
-    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
 
 
 def impala_forward(x, params):
@@ -300,42 +275,36 @@ def impala_forward(x, params):
     y = torch.empty((B, 8, 8, 32))
     saved = torch.empty(max(int(lib.mi355ppo_impala_saved_floats(B)), 1))
     arg = torch.empty(max(int(lib.mi355ppo_impala_argmax_bytes(B)), 1), dtype=torch.uint8)
-    _lib.check(lib.mi355ppo_impala_fwd_f32_cpu(_p(xs), _ptrs([_p_t(p) for p in ps]), _p(y), _p(saved), _p(arg), B, H, W, C,
-                                               *IMPALA_CHANNELS), "mi355ppo_impala_fwd_f32_cpu")
+    _lib.call("mi355ppo_impala_fwd_f32_cpu", _p(xs), _ptr_array([_p_t(p) for p in ps]), _p(y), _p(saved), _p(arg), B, H, W, C, *IMPALA_CHANNELS)
     return y, saved, arg
 
 
 def impala_backward(x, params, saved, arg, dy):
     """Backward of ``impala_forward`` through ``mi355ppo_impala_bwd_f32_cpu`` -> the 30 parameter gradients (no input gradient)."""
-    lib = _lib.load()
     B, H, W, C = x.shape
     xs, ps, g = _f32(x), [_f32(p) for p in params], _f32(dy)
     grads = [torch.empty(p.shape) for p in ps]
-    _lib.check(lib.mi355ppo_impala_bwd_f32_cpu(_p(xs), _ptrs([_p_t(p) for p in ps]), _p(saved), _p(arg), _p(g),
-                                               _ptrs([_p_t(t) for t in grads]), B, H, W, C, *IMPALA_CHANNELS),
-               "mi355ppo_impala_bwd_f32_cpu")
+    _lib.call("mi355ppo_impala_bwd_f32_cpu", _p(xs), _ptr_array([_p_t(p) for p in ps]), _p(saved), _p(arg), _p(g),
+              _ptr_array([_p_t(t) for t in grads]), B, H, W, C, *IMPALA_CHANNELS)
     return grads
 
 
 def impala_maxpool_forward(x):
     """The trunk's max pool (3, stride 2, pad 1) on channels-last x (B,H,W,C) -> (y (B,H/2,W/2,C), argmax bytes)."""
-    lib = _lib.load()
     B, H, W, C = x.shape
     xs = _f32(x)
     y = torch.empty((B, H // 2, W // 2, C))
     arg = torch.empty((B, H // 2, W // 2, C), dtype=torch.uint8)
-    _lib.check(lib.mi355ppo_impala_maxpool_fwd_f32_cpu(_p(xs), _p(y), _p(arg), B, H, W, C), "mi355ppo_impala_maxpool_fwd_f32_cpu")
+    _lib.call("mi355ppo_impala_maxpool_fwd_f32_cpu", _p(xs), _p(y), _p(arg), B, H, W, C)
     return y, arg
 
 
 def impala_maxpool_backward(dy, arg):
     """Backward of ``impala_maxpool_forward``: dx (B,H,W,C) from dy and the argmax."""
-    lib = _lib.load()
     B, Ho, Wo, C = dy.shape
     g = _f32(dy)
     dx = torch.empty((B, 2 * Ho, 2 * Wo, C))
-    _lib.check(lib.mi355ppo_impala_maxpool_bwd_f32_cpu(_p(g), _p(arg.contiguous()), _p(dx), B, 2 * Ho, 2 * Wo, C),
-               "mi355ppo_impala_maxpool_bwd_f32_cpu")
+    _lib.call("mi355ppo_impala_maxpool_bwd_f32_cpu", _p(g), _p(arg.contiguous()), _p(dx), B, 2 * Ho, 2 * Wo, C)
     return dx
 
 
@@ -345,20 +314,20 @@ def _p_t(t):
 
 
 # ------------------------------------------------------------------------------------------- PQN twins (csrc/pqn.hip)
-def _i64(t):
-    return t.detach().to(torch.int64).contiguous()
-
-
-def pqn_param_count(obs_dim: int, n_actions: int) -> int:
-    return 120 * obs_dim + 360 + 84 * 120 + 252 + 85 * n_actions
+def _pqn_params(params, obs_dim, n_actions):
+    p = _f32(params)
+    if p.numel() != pqn_param_count(obs_dim, n_actions):
+        raise ValueError(f"params: expected the {pqn_param_count(obs_dim, n_actions)} flat parameters of a ({obs_dim}, {n_actions}) QNetwork, "
+                         f"got {p.numel()}")
+    return p
 
 
 def pqn_egreedy(q, random_actions, u, epsilon, actions_out, values_out, action_i64_out=None):
     """``mi355ppo_pqn_egreedy_f32_cpu``: the e-greedy row of pqn.py's rollout (see ops.pqn_egreedy); writes the storage rows in place."""
     N, A = q.shape
     q, rnd, uu = _f32(q), _i64(random_actions), _f32(u)
-    _lib.check(_lib.load().mi355ppo_pqn_egreedy_f32_cpu(_p(q), _p(rnd), _p(uu), float(epsilon), _p(actions_out), _p(values_out),
-                                                        _p(action_i64_out), N, A), "mi355ppo_pqn_egreedy_f32_cpu")
+    _lib.call("mi355ppo_pqn_egreedy_f32_cpu", _p(q), _p(rnd), _p(uu), float(epsilon), _out(actions_out, torch.float32, N, "actions_out"),
+              _out(values_out, torch.float32, N, "values_out"), _out(action_i64_out, torch.int64, N, "action_i64_out"), N, A)
     return actions_out, values_out
 
 
@@ -367,8 +336,8 @@ def pqn_qlambda(rewards, dones, values, next_done, next_q, gamma, q_lambda, retu
     A = next_q.shape[-1]
     r, d, v, nd, nq = _f32(rewards), _f32(dones), _f32(values), _f32(next_done).reshape(-1), _f32(next_q)
     returns = torch.empty_like(r) if returns is None else returns
-    _lib.check(_lib.load().mi355ppo_pqn_qlambda_f32_cpu(_p(r), _p(d), _p(v), _p(nd), _p(nq), _p(returns), T, N, A, float(gamma),
-                                                        float(q_lambda)), "mi355ppo_pqn_qlambda_f32_cpu")
+    _lib.call("mi355ppo_pqn_qlambda_f32_cpu", _p(r), _p(d), _p(v), _p(nd), _p(nq), _out(returns, torch.float32, T * N, "returns"), T, N, A,
+              float(gamma), float(q_lambda))
     return returns
 
 
@@ -377,53 +346,44 @@ def pqn_td_loss(q, mb_inds, b_actions, b_returns, dq=None, scalars=None):
     qq, inds, ba, br = _f32(q), _i64(mb_inds), _f32(b_actions).reshape(-1), _f32(b_returns).reshape(-1)
     dq = torch.empty_like(qq) if dq is None else dq
     scalars = torch.empty(2) if scalars is None else scalars
-    _lib.check(_lib.load().mi355ppo_pqn_td_loss_fwd_bwd_f32_cpu(_p(qq), _p(inds), _p(ba), _p(br), _p(dq), _p(scalars), M, A, ba.numel()),
-               "mi355ppo_pqn_td_loss_fwd_bwd_f32_cpu")
+    _lib.call("mi355ppo_pqn_td_loss_fwd_bwd_f32_cpu", _p(qq), _p(inds), _p(ba), _p(br), _out(dq, torch.float32, M * A, "dq"),
+              _out(scalars, torch.float32, 2, "scalars"), M, A, ba.numel())
     return dq, scalars
 
 
 def pqn_mlp_forward(obs, params, n_actions, q_out=None):
     N, O = obs.shape
-    x, p = _f32(obs), _f32(params)
-    assert p.numel() == pqn_param_count(O, n_actions), "flat parameters of another shape"
+    x, p = _f32(obs), _pqn_params(params, O, n_actions)
     q_out = torch.empty((N, n_actions)) if q_out is None else q_out
-    _lib.check(_lib.load().mi355ppo_pqn_mlp_fwd_f32_cpu(_p(x), _p(p), _p(q_out), N, O, int(n_actions)), "mi355ppo_pqn_mlp_fwd_f32_cpu")
+    _lib.call("mi355ppo_pqn_mlp_fwd_f32_cpu", _p(x), _p(p), _out(q_out, torch.float32, N * n_actions, "q_out"), N, O, int(n_actions))
     return q_out
 
 
 def pqn_mlp_act(obs, params, n_actions, random_actions, u, epsilon, actions_out, values_out, action_i64_out=None, obs_row_out=None,
                 done_in=None, done_row_out=None):
     N, O = obs.shape
-    x, p, rnd, uu = _f32(obs), _f32(params), _i64(random_actions), _f32(u)
-    assert p.numel() == pqn_param_count(O, n_actions), "flat parameters of another shape"
+    x, p, rnd, uu = _f32(obs), _pqn_params(params, O, n_actions), _i64(random_actions), _f32(u)
     din = None if done_in is None else _f32(done_in)
-    _lib.check(_lib.load().mi355ppo_pqn_mlp_act_f32_cpu(_p(x), _p(p), _p(rnd), _p(uu), float(epsilon), _p(actions_out), _p(values_out),
-                                                        _p(action_i64_out), _p(obs_row_out), _p(din), _p(done_row_out), N, O, int(n_actions)),
-               "mi355ppo_pqn_mlp_act_f32_cpu")
+    _lib.call("mi355ppo_pqn_mlp_act_f32_cpu", _p(x), _p(p), _p(rnd), _p(uu), float(epsilon), _out(actions_out, torch.float32, N, "actions_out"),
+              _out(values_out, torch.float32, N, "values_out"), _out(action_i64_out, torch.int64, N, "action_i64_out"),
+              _out(obs_row_out, torch.float32, N * O, "obs_row_out"), _p(din), _out(done_row_out, torch.float32, N, "done_row_out"), N, O,
+              int(n_actions))
     return actions_out, values_out
 
 
 def pqn_mlp_td_fwd_bwd(b_obs, mb_inds, params, b_actions, b_returns, grads, n_actions, scalars=None):
     B, O = b_obs.shape
-    x, p, inds = _f32(b_obs), _f32(params), _i64(mb_inds)
-    assert p.numel() == pqn_param_count(O, n_actions), "flat parameters of another shape"
+    x, p, inds = _f32(b_obs), _pqn_params(params, O, n_actions), _i64(mb_inds)
     ba, br = _f32(b_actions).reshape(-1), _f32(b_returns).reshape(-1)
     scalars = torch.empty(2) if scalars is None else scalars
-    _lib.check(_lib.load().mi355ppo_pqn_mlp_td_fwd_bwd_f32_cpu(_p(x), B, _p(inds), _p(p), _p(ba), _p(br), _p(grads), _p(scalars),
-                                                               inds.numel(), O, int(n_actions)), "mi355ppo_pqn_mlp_td_fwd_bwd_f32_cpu")
+    _lib.call("mi355ppo_pqn_mlp_td_fwd_bwd_f32_cpu", _p(x), B, _p(inds), _p(p), _p(ba), _p(br), _out(grads, torch.float32, p.numel(), "grads"),
+              _out(scalars, torch.float32, 2, "scalars"), inds.numel(), O, int(n_actions))
     return scalars
-
-
-def radam_schedule(lr, step, beta1=0.9, beta2=0.999):
-    out = (ctypes.c_float * 8)()
-    _lib.check(_lib.load().mi355ppo_radam_schedule_f32(float(lr), float(beta1), float(beta2), int(step), out), "mi355ppo_radam_schedule_f32")
-    return [float(x) for x in out]
 
 
 def clip_radam_(params, grads, exp_avg, exp_avg_sq, step, lr, max_grad_norm, beta1=0.9, beta2=0.999, eps=1e-8, total_norm_out=None):
     """``mi355ppo_clip_radam_f32_cpu``: clip_grad_norm_ + RAdam step ``step`` on flat CPU buffers (in place; zeroes grads)."""
     total = torch.empty(1) if total_norm_out is None else total_norm_out
-    _lib.check(_lib.load().mi355ppo_clip_radam_f32_cpu(_p(params), _p(grads), _p(exp_avg), _p(exp_avg_sq), params.numel(), float(max_grad_norm),
-                                                       float(lr), float(beta1), float(beta2), float(eps), int(step), _p(total)),
-               "mi355ppo_clip_radam_f32_cpu")
+    _lib.call("mi355ppo_clip_radam_f32_cpu", *_flat4(params, grads, exp_avg, exp_avg_sq), params.numel(), float(max_grad_norm), float(lr),
+              float(beta1), float(beta2), float(eps), int(step), _out(total, torch.float32, 1, "total_norm_out"))
     return total

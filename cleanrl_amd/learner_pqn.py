@@ -36,7 +36,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 import torch.optim as optim
 
-from . import host_ops, ops
+from . import ops
 from .flat import FlatParams
 
 BACKENDS = ("torch", "fused")
@@ -66,7 +66,7 @@ class PQNLearner:
         self.N, self.T, self.A = int(num_envs), int(args.num_steps), int(n_actions)
         self.obs_shape, self.mlp = tuple(obs_shape), bool(mlp)
         self.fused = self.backend == "fused"
-        self.g = ops if self.device.type == "cuda" else host_ops
+        self.g = ops.twins(self.device)
         if self.fused and self.mlp:
             O = int(np.prod(self.obs_shape))
             if not (1 <= O <= ops.PQN_MAX_OBS and 1 <= self.A <= ops.PQN_MAX_ACTIONS):

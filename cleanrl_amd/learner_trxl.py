@@ -31,7 +31,7 @@ import torch
 import torch.nn as nn
 import torch.optim as optim
 
-from . import host_ops, ops
+from . import ops
 from .agents import MemoryWindow, batched_index_select
 
 
@@ -156,8 +156,7 @@ class TrXLLearner:
         next_value = self.agent.get_value(self.next_obs, self._window(self.next_memory, indices),
                                           self.memory_mask[torch.clip(self.env_current_episode_step, 0, L - 1)],
                                           self.stored_memory_indices[-1])
-        g = ops if self.device.type == "cuda" else host_ops
-        self.advantages, self.returns = g.gae(self.rewards, self.dones, self.values, self.next_done, next_value, a.gamma, a.gae_lambda)
+        self.advantages, self.returns = ops.twins(self.device).gae(self.rewards, self.dones, self.values, self.next_done, next_value, a.gamma, a.gae_lambda)
 
     # ------------------------------------------------------------------ update
     def update(self):

@@ -2,13 +2,17 @@
 
 Each function mirrors one seam of the reference's inline PPO code (cited per function) and takes
 CUDA (=HIP) ``torch`` tensors only: torch is plumbing here (device memory + the current stream), the
-computation is the HIP kernels.  Passing a CPU tensor raises; there is no CPU fallback in this module.  The one exception is
-``LSTMSeq`` / ``lstm_seq``, ``TrXLMemoryAttention`` and ``ImpalaTrunk`` / ``impala_trunk``, which take CPU tensors to the host twins (cleanrl_amd/host_ops.py) on
-purpose: the agent's host path and the tests run the same arithmetic as the device kernels.
+computation is the HIP kernels.  Every wrapper ends in ``_launch(symbol, device, *args)``: the entry point on the device's current
+stream, a non-zero status raised as ``Mi355PpoError`` naming that symbol.  Passing a CPU tensor raises; there is no CPU fallback in
+this module.  The one exception is ``twins``: the autograd nodes ``LSTMSeq`` / ``lstm_seq``, ``TrXLMemoryAttention`` /
+``trxl_memory_attention`` and ``ImpalaTrunk`` / ``impala_trunk`` (and the TrXL / PQN learners, for their whole device) take CPU tensors
+to the host twins (cleanrl_amd/host_ops.py) on purpose: the agent's host path and the tests run the same arithmetic as the device
+kernels.
 """
 from __future__ import annotations
 
 import ctypes
+import sys
 from typing import Optional
 
 import torch
@@ -50,10 +54,17 @@ _NO_SWITCH = _NoSwitch()
 
 
 def _on(dev: torch.device):
-    """``with _on(dev):`` == ``with _on(dev):`` without the get/set-device round trips when ``dev`` is
+    """``with _on(dev):`` == ``with torch.cuda.device(dev):`` without the get/set-device round trips when ``dev`` is
     already current -- the normal case (one process per GPU); the wrappers sit on the rollout's per-step critical path,
     which is host-bound."""
     return _NO_SWITCH if dev.index is None or torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
+
+
+def _launch(name: str, dev: torch.device, *args) -> None:
+    """Enqueue the device entry point ``name`` on ``dev``'s current stream (every entry point that takes a stream takes it as its last
+    argument) and raise ``Mi355PpoError`` naming it on a non-zero status."""
+    with _on(dev):
+        _lib.call(name, *args, _stream(dev))
 
 
 def _chk(t: torch.Tensor, dtype, name: str, shape=None) -> torch.Tensor:
@@ -67,6 +78,21 @@ def _chk(t: torch.Tensor, dtype, name: str, shape=None) -> torch.Tensor:
     if shape is not None and tuple(t.shape) != tuple(shape):
         raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
     return t
+
+
+def _ptr_array(ts):
+    """A host array of the tensors' data pointers (a network's parameters / gradients as the C ABI takes them)."""
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def twins(where, *names):
+    """The functions ``names`` for ``where`` (a tensor or a device): this module's HIP wrappers for CUDA, the ``*_cpu`` host twins
+    of the same names (cleanrl_amd/host_ops.py) otherwise.  Without names: the module itself."""
+    if (where.device if isinstance(where, torch.Tensor) else where).type == "cuda":
+        mod = sys.modules[__name__]
+    else:
+        from . import host_ops as mod
+    return tuple(getattr(mod, n) for n in names) if names else mod
 
 
 _workspaces: dict = {}
@@ -89,7 +115,6 @@ def _workspace(dev: torch.device, nbytes: int) -> torch.Tensor:
 def gae(rewards, dones, values, next_done, next_value, gamma: float, gae_lambda: float, advantages=None, returns=None,
         variant: int = 0):
     """Fused GAE (reference: ppo_atari_multigpu.py:290-301).  Returns ``(advantages, returns)`` (T,N)."""
-    lib = _lib.load()
     T, N = rewards.shape
     _chk(rewards, torch.float32, "rewards", (T, N))
     _chk(dones, torch.float32, "dones", (T, N))
@@ -102,11 +127,8 @@ def gae(rewards, dones, values, next_done, next_value, gamma: float, gae_lambda:
         returns = torch.empty_like(rewards)
     _chk(advantages, torch.float32, "advantages", (T, N))
     _chk(returns, torch.float32, "returns", (T, N))
-    with _on(rewards.device):
-        st = lib.mi355ppo_gae_f32_variant(_ptr(rewards), _ptr(dones), _ptr(values), _ptr(next_done), _ptr(next_value),
-                                          _ptr(advantages), _ptr(returns), T, N, float(gamma), float(gae_lambda),
-                                          int(variant), _stream(rewards.device))
-    _lib.check(st, "mi355ppo_gae_f32")
+    _launch("mi355ppo_gae_f32_variant", rewards.device, _ptr(rewards), _ptr(dones), _ptr(values), _ptr(next_done), _ptr(next_value),
+            _ptr(advantages), _ptr(returns), T, N, float(gamma), float(gae_lambda), int(variant))
     return advantages, returns
 
 
@@ -120,7 +142,6 @@ def categorical_sample(logits, noise_exp1=None, seed: int = 0, offset: int = 0, 
     tensor) is added to ``offset`` on the device, so a captured launch can be replayed at a new stream position.
     Returns ``(action_i64 | None, action_f32 | None, logprob, entropy | None)``.
     """
-    lib = _lib.load()
     B, A = logits.shape
     _chk(logits, torch.float32, "logits", (B, A))
     if noise_exp1 is not None:
@@ -137,17 +158,13 @@ def categorical_sample(logits, noise_exp1=None, seed: int = 0, offset: int = 0, 
     ent = torch.empty(B, dtype=torch.float32, device=dev) if want_entropy else None
     if offset_base is not None:
         _chk(offset_base, torch.int64, "offset_base", (1,))
-    with _on(dev):
-        st = lib.mi355ppo_categorical_sample_ctr_f32(_ptr(logits), _ptr(noise_exp1), int(seed) & (2**64 - 1),
-                                                     int(offset) & (2**64 - 1), _ptr(offset_base), _ptr(a64), _ptr(af), _ptr(lp),
-                                                     _ptr(ent), B, A, _stream(dev))
-    _lib.check(st, "mi355ppo_categorical_sample_f32")
+    _launch("mi355ppo_categorical_sample_ctr_f32", dev, _ptr(logits), _ptr(noise_exp1), int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
+            _ptr(offset_base), _ptr(a64), _ptr(af), _ptr(lp), _ptr(ent), B, A)
     return a64, af, lp, ent
 
 
 def categorical_logprob_entropy(logits, action):
     """log_prob / entropy of given actions (int64 or the reference's f32 storage)."""
-    lib = _lib.load()
     B, A = logits.shape
     _chk(logits, torch.float32, "logits", (B, A))
     dev = logits.device
@@ -157,16 +174,12 @@ def categorical_logprob_entropy(logits, action):
         a64, af = None, _chk(action, torch.float32, "action", (B,))
     lp = torch.empty(B, dtype=torch.float32, device=dev)
     ent = torch.empty(B, dtype=torch.float32, device=dev)
-    with _on(dev):
-        st = lib.mi355ppo_categorical_logprob_entropy_f32(_ptr(logits), _ptr(a64), _ptr(af), _ptr(lp), _ptr(ent), B, A,
-                                                          _stream(dev))
-    _lib.check(st, "mi355ppo_categorical_logprob_entropy_f32")
+    _launch("mi355ppo_categorical_logprob_entropy_f32", dev, _ptr(logits), _ptr(a64), _ptr(af), _ptr(lp), _ptr(ent), B, A)
     return lp, ent
 
 
 def normal_sample(mean, logstd, noise=None, seed: int = 0, offset: int = 0, action_out=None, logprob_out=None):
     """``Normal(mean, exp(logstd))`` sample + summed log_prob/entropy (ppo_continuous_action.py:134-141)."""
-    lib = _lib.load()
     B, D = mean.shape
     _chk(mean, torch.float32, "mean", (B, D))
     logstd = _chk(logstd.reshape(-1), torch.float32, "logstd", (D,))
@@ -177,16 +190,12 @@ def normal_sample(mean, logstd, noise=None, seed: int = 0, offset: int = 0, acti
     _chk(act, torch.float32, "action_out", (B, D))
     lp = logprob_out if logprob_out is not None else torch.empty(B, dtype=torch.float32, device=dev)
     ent = torch.empty(B, dtype=torch.float32, device=dev)
-    with _on(dev):
-        st = lib.mi355ppo_normal_sample_f32(_ptr(mean), _ptr(logstd), _ptr(noise), int(seed) & (2**64 - 1),
-                                            int(offset) & (2**64 - 1), _ptr(act), _ptr(lp), _ptr(ent), B, D,
-                                            _stream(dev))
-    _lib.check(st, "mi355ppo_normal_sample_f32")
+    _launch("mi355ppo_normal_sample_f32", dev, _ptr(mean), _ptr(logstd), _ptr(noise), int(seed) & (2**64 - 1), int(offset) & (2**64 - 1),
+            _ptr(act), _ptr(lp), _ptr(ent), B, D)
     return act, lp, ent
 
 
 def normal_logprob_entropy(mean, logstd, action):
-    lib = _lib.load()
     B, D = mean.shape
     _chk(mean, torch.float32, "mean", (B, D))
     logstd = _chk(logstd.reshape(-1), torch.float32, "logstd", (D,))
@@ -194,10 +203,7 @@ def normal_logprob_entropy(mean, logstd, action):
     dev = mean.device
     lp = torch.empty(B, dtype=torch.float32, device=dev)
     ent = torch.empty(B, dtype=torch.float32, device=dev)
-    with _on(dev):
-        st = lib.mi355ppo_normal_logprob_entropy_f32(_ptr(mean), _ptr(logstd), _ptr(action), _ptr(lp), _ptr(ent), B, D,
-                                                     _stream(dev))
-    _lib.check(st, "mi355ppo_normal_logprob_entropy_f32")
+    _launch("mi355ppo_normal_logprob_entropy_f32", dev, _ptr(mean), _ptr(logstd), _ptr(action), _ptr(lp), _ptr(ent), B, D)
     return lp, ent
 
 
@@ -215,17 +221,13 @@ class CategoricalLogProbEntropy(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_lp, g_ent):
         logits, action = ctx.saved_tensors
-        lib = _lib.load()
         B, A = logits.shape
         dlogits = torch.empty_like(logits)
         a64, af = (action, None) if action.dtype == torch.int64 else (None, action)
         g_lp = None if g_lp is None else _chk(g_lp.contiguous(), torch.float32, "g_logprob", (B,))
         g_ent = None if g_ent is None else _chk(g_ent.contiguous(), torch.float32, "g_entropy", (B,))
-        with _on(logits.device):
-            st = lib.mi355ppo_categorical_logprob_entropy_bwd_f32(_ptr(logits), _ptr(a64), _ptr(af), _ptr(g_lp),
-                                                                  _ptr(g_ent), _ptr(dlogits), B, A,
-                                                                  _stream(logits.device))
-        _lib.check(st, "mi355ppo_categorical_logprob_entropy_bwd_f32")
+        _launch("mi355ppo_categorical_logprob_entropy_bwd_f32", logits.device, _ptr(logits), _ptr(a64), _ptr(af), _ptr(g_lp), _ptr(g_ent),
+                _ptr(dlogits), B, A)
         return dlogits, None
 
 
@@ -242,15 +244,12 @@ class NormalLogProbEntropy(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_lp, g_ent):
         mean, ls, action = ctx.saved_tensors
-        lib = _lib.load()
         B, D = mean.shape
         dmean, drows = torch.empty_like(mean), torch.empty_like(mean)
         g_lp = None if g_lp is None else _chk(g_lp.contiguous(), torch.float32, "g_logprob", (B,))
         g_ent = None if g_ent is None else _chk(g_ent.contiguous(), torch.float32, "g_entropy", (B,))
-        with _on(mean.device):
-            st = lib.mi355ppo_normal_logprob_entropy_bwd_f32(_ptr(mean), _ptr(ls), _ptr(action), _ptr(g_lp), _ptr(g_ent),
-                                                             _ptr(dmean), _ptr(drows), B, D, _stream(mean.device))
-        _lib.check(st, "mi355ppo_normal_logprob_entropy_bwd_f32")
+        _launch("mi355ppo_normal_logprob_entropy_bwd_f32", mean.device, _ptr(mean), _ptr(ls), _ptr(action), _ptr(g_lp), _ptr(g_ent),
+                _ptr(dmean), _ptr(drows), B, D)
         return dmean, drows.sum(0).reshape(ctx.logstd_shape), None
 
 
@@ -281,14 +280,11 @@ class LossSlots:
 
     def fold(self, n: int, out: torch.Tensor, first: int = 0) -> torch.Tensor:
         """rows first..first+n-1 of ``out`` (>= first+n, 7) <- slots first..first+n-1."""
-        lib = _lib.load()
         _chk(out, torch.float32, "out")
         if out.dim() != 2 or out.shape[1] != 7 or out.shape[0] < first + n or first + n > self.n:
             raise ValueError(f"fold: out {tuple(out.shape)} / slots {self.n} cannot hold rows {first}..{first + n - 1}")
-        with _on(self.device):
-            st = lib.mi355ppo_loss_scalars_f32(self.ptr(first), self.stride, int(n), ctypes.c_void_p(out.data_ptr() + 28 * first),
-                                               _stream(self.device))
-        _lib.check(st, "mi355ppo_loss_scalars_f32")
+        _launch("mi355ppo_loss_scalars_f32", self.device, self.ptr(first), self.stride, int(n),
+                ctypes.c_void_p(out.data_ptr() + 28 * first))
         return out
 
 
@@ -305,10 +301,7 @@ def adv_stats(b_advantages, inds, minibatch_size: int, out=None):
     out = out if out is not None else torch.empty(nseg, 2, dtype=torch.float32, device=flat.device)
     _chk(out, torch.float32, "out", (nseg, 2))
     ws = _workspace(flat.device, lib.mi355ppo_adv_stats_workspace_bytes(total, int(minibatch_size)))
-    with _on(flat.device):
-        st = lib.mi355ppo_adv_stats_f32(_ptr(flat), _ptr(inds), total, int(minibatch_size), _ptr(out), _ptr(ws), ws.numel(),
-                                        _stream(flat.device))
-    _lib.check(st, "mi355ppo_adv_stats_f32")
+    _launch("mi355ppo_adv_stats_f32", flat.device, _ptr(flat), _ptr(inds), total, int(minibatch_size), _ptr(out), _ptr(ws), ws.numel())
     return out
 
 
@@ -318,16 +311,13 @@ PACK_FLOATS = 8       # floats per packed behaviour row: {action, old log-prob, 
 def batch_pack(b_actions, b_logprobs, b_advantages, b_returns, b_values, out=None):
     """The five per-row behaviour arrays of the flat batch -> ``(B, 8)`` packed rows (one 32-byte gather per minibatch row in
     K3 instead of five 4-byte gathers; ppo_atari_multigpu.py:320-352).  Once per iteration, after GAE."""
-    lib = _lib.load()
     Bf, b_logprobs, b_advantages, b_returns, b_values = _flat_batch(b_logprobs, b_advantages, b_returns, b_values)
     b_actions = _chk(b_actions.reshape(-1), torch.float32, "b_actions (f32 storage, as the reference)", (Bf,))
     dev = b_logprobs.device
     out = out if out is not None else torch.empty((Bf, PACK_FLOATS), dtype=torch.float32, device=dev)
     _chk(out, torch.float32, "pack", (Bf, PACK_FLOATS))
-    with _on(dev):
-        st = lib.mi355ppo_batch_pack_f32(_ptr(b_actions), _ptr(b_logprobs), _ptr(b_advantages), _ptr(b_returns), _ptr(b_values),
-                                         _ptr(out), Bf, _stream(dev))
-    _lib.check(st, "mi355ppo_batch_pack_f32")
+    _launch("mi355ppo_batch_pack_f32", dev, _ptr(b_actions), _ptr(b_logprobs), _ptr(b_advantages), _ptr(b_returns), _ptr(b_values),
+            _ptr(out), Bf)
     return out
 
 
@@ -344,10 +334,8 @@ def adv_stats_packed(pack, inds, minibatch_size: int, out=None):
     out = out if out is not None else torch.empty(nseg, 2, dtype=torch.float32, device=pack.device)
     _chk(out, torch.float32, "out", (nseg, 2))
     ws = _workspace(pack.device, lib.mi355ppo_adv_stats_workspace_bytes(total, int(minibatch_size)))
-    with _on(pack.device):
-        st = lib.mi355ppo_adv_stats_packed_f32(_ptr(pack), _ptr(inds), total, int(minibatch_size), _ptr(out), _ptr(ws), ws.numel(),
-                                               _stream(pack.device))
-    _lib.check(st, "mi355ppo_adv_stats_packed_f32")
+    _launch("mi355ppo_adv_stats_packed_f32", pack.device, _ptr(pack), _ptr(inds), total, int(minibatch_size), _ptr(out), _ptr(ws),
+            ws.numel())
     return out
 
 
@@ -379,12 +367,9 @@ def ppo_loss_categorical_packed(new_logits, new_value, mb_inds, pack, clip_coef:
         scalars = scalars_out if scalars_out is not None else torch.empty(7, dtype=torch.float32, device=dev)
         ws = _workspace(dev, lib.mi355ppo_loss_workspace_bytes(M, 0))
         ws_ptr, ws_bytes = _ptr(ws), ws.numel()
-    with _on(dev):
-        st = lib.mi355ppo_loss_categorical_packed_fwd_bwd_f32(
-            _ptr(new_logits), _ptr(new_value), _ptr(mb_inds), _ptr(pack), M, A, float(clip_coef), float(ent_coef), float(vf_coef),
-            int(bool(norm_adv)), int(bool(clip_vloss)), _ptr(adv_mean_den), _ptr(scalars), _ptr(dlogits), _ptr(dvalue), ws_ptr,
-            ws_bytes, _stream(dev))
-    _lib.check(st, "mi355ppo_loss_categorical_packed_fwd_bwd_f32")
+    _launch("mi355ppo_loss_categorical_packed_fwd_bwd_f32", dev, _ptr(new_logits), _ptr(new_value), _ptr(mb_inds), _ptr(pack), M, A,
+            float(clip_coef), float(ent_coef), float(vf_coef), int(bool(norm_adv)), int(bool(clip_vloss)), _ptr(adv_mean_den),
+            _ptr(scalars), _ptr(dlogits), _ptr(dvalue), ws_ptr, ws_bytes)
     return scalars, dlogits, dvalue
 
 
@@ -418,13 +403,9 @@ def ppo_loss_categorical(new_logits, new_value, mb_inds, b_actions, b_logprobs, 
         scalars = scalars_out if scalars_out is not None else torch.empty(7, dtype=torch.float32, device=dev)
         ws = _workspace(dev, lib.mi355ppo_loss_workspace_bytes(M, 0))
         ws_ptr, ws_bytes = _ptr(ws), ws.numel()
-    with _on(dev):
-        st = lib.mi355ppo_loss_categorical_fwd_bwd_f32(
-            _ptr(new_logits), _ptr(new_value), _ptr(mb_inds), _ptr(b_actions), _ptr(b_logprobs), _ptr(b_advantages),
-            _ptr(b_returns), _ptr(b_values), M, A, float(clip_coef), float(ent_coef), float(vf_coef), int(bool(norm_adv)),
-            int(bool(clip_vloss)), _ptr(adv_mean_den), _ptr(scalars), _ptr(dlogits), _ptr(dvalue), ws_ptr, ws_bytes,
-            _stream(dev))
-    _lib.check(st, "mi355ppo_loss_categorical_fwd_bwd_f32")
+    _launch("mi355ppo_loss_categorical_fwd_bwd_f32", dev, _ptr(new_logits), _ptr(new_value), _ptr(mb_inds), _ptr(b_actions),
+            _ptr(b_logprobs), _ptr(b_advantages), _ptr(b_returns), _ptr(b_values), M, A, float(clip_coef), float(ent_coef), float(vf_coef),
+            int(bool(norm_adv)), int(bool(clip_vloss)), _ptr(adv_mean_den), _ptr(scalars), _ptr(dlogits), _ptr(dvalue), ws_ptr, ws_bytes)
     return scalars, dlogits, dvalue
 
 
@@ -450,13 +431,10 @@ def ppo_loss_normal(new_mean, logstd, new_value, mb_inds, b_actions, b_logprobs,
     dlogstd = torch.empty(D, dtype=torch.float32, device=dev)
     dvalue = torch.empty(M, dtype=torch.float32, device=dev)
     ws = _workspace(dev, lib.mi355ppo_loss_workspace_bytes(M, D))
-    with _on(dev):
-        st = lib.mi355ppo_loss_normal_fwd_bwd_f32(
-            _ptr(new_mean), _ptr(logstd_flat), _ptr(new_value), _ptr(mb_inds), _ptr(b_actions), _ptr(b_logprobs),
-            _ptr(b_advantages), _ptr(b_returns), _ptr(b_values), M, D, float(clip_coef), float(ent_coef), float(vf_coef),
-            int(bool(norm_adv)), int(bool(clip_vloss)), _ptr(adv_mean_den), _ptr(scalars), _ptr(dmean), _ptr(dlogstd),
-            _ptr(dvalue), _ptr(ws), ws.numel(), _stream(dev))
-    _lib.check(st, "mi355ppo_loss_normal_fwd_bwd_f32")
+    _launch("mi355ppo_loss_normal_fwd_bwd_f32", dev, _ptr(new_mean), _ptr(logstd_flat), _ptr(new_value), _ptr(mb_inds), _ptr(b_actions),
+            _ptr(b_logprobs), _ptr(b_advantages), _ptr(b_returns), _ptr(b_values), M, D, float(clip_coef), float(ent_coef), float(vf_coef),
+            int(bool(norm_adv)), int(bool(clip_vloss)), _ptr(adv_mean_den), _ptr(scalars), _ptr(dmean), _ptr(dlogstd), _ptr(dvalue),
+            _ptr(ws), ws.numel())
     return scalars, dmean, dlogstd, dvalue
 
 
@@ -505,7 +483,6 @@ class PPOLossNormal(torch.autograd.Function):
 def obs_u8_to_f32(src_u8, inds=None, out=None, scale_255: bool = True):
     """Gather rows of a uint8 observation buffer and convert to f32 (``b_obs[mb_inds]`` then ``x / 255.0``,
     ppo_atari_multigpu.py:320,154).  ``src_u8``: (R, ...) uint8; ``inds``: (rows,) int64 or None."""
-    lib = _lib.load()
     _chk(src_u8, torch.uint8, "src_u8")
     dev = src_u8.device
     row_shape = tuple(src_u8.shape[1:])
@@ -520,39 +497,30 @@ def obs_u8_to_f32(src_u8, inds=None, out=None, scale_255: bool = True):
     if out is None:
         out = torch.empty((rows,) + row_shape, dtype=torch.float32, device=dev)
     _chk(out, torch.float32, "out", (rows,) + row_shape)
-    with _on(dev):
-        st = lib.mi355ppo_obs_u8_to_f32(_ptr(src_u8), _ptr(inds), _ptr(out), rows, row_bytes, int(bool(scale_255)),
-                                        _stream(dev))
-    _lib.check(st, "mi355ppo_obs_u8_to_f32")
+    _launch("mi355ppo_obs_u8_to_f32", dev, _ptr(src_u8), _ptr(inds), _ptr(out), rows, row_bytes, int(bool(scale_255)))
     return out
 
 
 def obs_nchw_to_nhwc_u8(src, out=None):
     """(rows, C, H, W) uint8 -> (rows, H, W, C) uint8, the rollout buffer's pixel-interleaved layout."""
-    lib = _lib.load()
     _chk(src, torch.uint8, "src")
     rows, C, H, W = src.shape
     if out is None:
         out = torch.empty((rows, H, W, C), dtype=torch.uint8, device=src.device)
     _chk(out, torch.uint8, "out", (rows, H, W, C))
-    with _on(src.device):
-        st = lib.mi355ppo_obs_nchw_to_nhwc_u8(_ptr(src), _ptr(out), rows, C, H * W, _stream(src.device))
-    _lib.check(st, "mi355ppo_obs_nchw_to_nhwc_u8")
+    _launch("mi355ppo_obs_nchw_to_nhwc_u8", src.device, _ptr(src), _ptr(out), rows, C, H * W)
     return out
 
 
 def obs_shift_append_u8(prev_rows, newest, out):
     """FrameStack(4) delta store: ``out[r] = concat(prev_rows[r][..., 1:4], newest[r][..., None])`` on (rows, H, W, 4) uint8
     rows and (rows, H, W) uint8 planes -- the next observation of envs that were not reset."""
-    lib = _lib.load()
     rows, H, W, C = prev_rows.shape
     assert C == 4, "the delta store is defined for 4-frame stacks"
     _chk(prev_rows, torch.uint8, "prev_rows", (rows, H, W, 4))
     _chk(newest, torch.uint8, "newest", (rows, H, W))
     _chk(out, torch.uint8, "out", (rows, H, W, 4))
-    with _on(out.device):
-        st = lib.mi355ppo_obs_shift_append_u8_c4(_ptr(prev_rows), _ptr(newest), _ptr(out), rows, H * W, _stream(out.device))
-    _lib.check(st, "mi355ppo_obs_shift_append_u8_c4")
+    _launch("mi355ppo_obs_shift_append_u8_c4", out.device, _ptr(prev_rows), _ptr(newest), _ptr(out), rows, H * W)
     return out
 
 
@@ -569,11 +537,8 @@ def clip_adam_(params, grads, exp_avg, exp_avg_sq, step: int, lr: float, max_gra
     if total_norm_out is None:
         total_norm_out = torch.empty(1, dtype=torch.float32, device=dev)
     ws = _workspace(dev, lib.mi355ppo_clip_adam_workspace_bytes(n))
-    with _on(dev):
-        st = lib.mi355ppo_clip_adam_f32(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), n, float(grad_scale),
-                                        float(max_grad_norm), float(lr), float(beta1), float(beta2), float(eps),
-                                        int(step), _ptr(total_norm_out), _ptr(ws), ws.numel(), _stream(dev))
-    _lib.check(st, "mi355ppo_clip_adam_f32")
+    _launch("mi355ppo_clip_adam_f32", dev, _ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), n, float(grad_scale),
+            float(max_grad_norm), float(lr), float(beta1), float(beta2), float(eps), int(step), _ptr(total_norm_out), _ptr(ws), ws.numel())
     return total_norm_out
 
 
@@ -582,7 +547,7 @@ def adam_schedule(lr: float, step: int, beta1: float = 0.9, beta2: float = 0.999
     ``(-(lr / (1 - beta1^step)), sqrt(1 - beta2^step))`` -- computed by the library, so that eager and captured steps agree bit
     for bit."""
     out = (ctypes.c_float * 2)()
-    _lib.check(_lib.load().mi355ppo_adam_schedule_f32(float(lr), float(beta1), float(beta2), int(step), out), "mi355ppo_adam_schedule_f32")
+    _lib.call("mi355ppo_adam_schedule_f32", float(lr), float(beta1), float(beta2), int(step), out)
     return float(out[0]), float(out[1])
 
 
@@ -599,11 +564,8 @@ def clip_adam_sched_(params, grads, exp_avg, exp_avg_sq, sched2, max_grad_norm: 
     if total_norm_out is None:
         total_norm_out = torch.empty(1, dtype=torch.float32, device=dev)
     ws = _workspace(dev, lib.mi355ppo_clip_adam_workspace_bytes(n))
-    with _on(dev):
-        st = lib.mi355ppo_clip_adam_sched_f32(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), n, float(grad_scale),
-                                              float(max_grad_norm), float(beta1), float(beta2), float(eps), _ptr(sched2),
-                                              _ptr(total_norm_out), _ptr(ws), ws.numel(), _stream(dev))
-    _lib.check(st, "mi355ppo_clip_adam_sched_f32")
+    _launch("mi355ppo_clip_adam_sched_f32", dev, _ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), n, float(grad_scale),
+            float(max_grad_norm), float(beta1), float(beta2), float(eps), _ptr(sched2), _ptr(total_norm_out), _ptr(ws), ws.numel())
     return total_norm_out
 
 
@@ -646,7 +608,6 @@ def mlp_supported(obs_dim: int, n_out: int) -> bool:
 
 def mlp_forward(obs, actor: MlpNetPtrs, critic: MlpNetPtrs, actor_out=None, value_out=None):
     """Both networks' forward in one launch -> ``(actor_out (B, n_out), value (B))``."""
-    lib = _lib.load()
     B, O = obs.shape
     _chk(obs, torch.float32, "obs", (B, actor.obs_dim))
     dev = obs.device
@@ -654,9 +615,7 @@ def mlp_forward(obs, actor: MlpNetPtrs, critic: MlpNetPtrs, actor_out=None, valu
     val = value_out if value_out is not None else torch.empty(B, dtype=torch.float32, device=dev)
     _chk(out, torch.float32, "actor_out", (B, actor.n_out))
     _chk(val, torch.float32, "value_out", (B,))
-    with _on(dev):
-        st = lib.mi355ppo_mlp_fwd_f32(_ptr(obs), B, O, actor.params, critic.params, actor.n_out, _ptr(out), _ptr(val), _stream(dev))
-    _lib.check(st, "mi355ppo_mlp_fwd_f32")
+    _launch("mi355ppo_mlp_fwd_f32", dev, _ptr(obs), B, O, actor.params, critic.params, actor.n_out, _ptr(out), _ptr(val))
     return out, val
 
 
@@ -665,7 +624,6 @@ def mlp_act_categorical(obs, actor: MlpNetPtrs, critic: MlpNetPtrs, noise_exp1=N
                         want_logits: bool = False):
     """One rollout step of the Categorical MLP agent (ppo.py:205-210): both forwards + sample + log_prob (+ entropy) in one launch.
     -> ``(action_i64 | None, action_f32 | None, logprob, entropy | None, value, logits | None)``."""
-    lib = _lib.load()
     B, O = obs.shape
     _chk(obs, torch.float32, "obs", (B, actor.obs_dim))
     dev, A = obs.device, actor.n_out
@@ -682,11 +640,9 @@ def mlp_act_categorical(obs, actor: MlpNetPtrs, critic: MlpNetPtrs, noise_exp1=N
     logits = torch.empty((B, A), dtype=torch.float32, device=dev) if want_logits else None
     if offset_base is not None:
         _chk(offset_base, torch.int64, "offset_base", (1,))
-    with _on(dev):
-        st = lib.mi355ppo_mlp_act_categorical_f32(_ptr(obs), B, O, actor.params, critic.params, A, _ptr(noise_exp1), int(seed) & (2**64 - 1),
-                                                  int(offset) & (2**64 - 1), _ptr(offset_base), _ptr(a64), _ptr(af), _ptr(lp), _ptr(ent),
-                                                  _ptr(val), _ptr(logits), _stream(dev))
-    _lib.check(st, "mi355ppo_mlp_act_categorical_f32")
+    _launch("mi355ppo_mlp_act_categorical_f32", dev, _ptr(obs), B, O, actor.params, critic.params, A, _ptr(noise_exp1),
+            int(seed) & (2**64 - 1), int(offset) & (2**64 - 1), _ptr(offset_base), _ptr(a64), _ptr(af), _ptr(lp), _ptr(ent), _ptr(val),
+            _ptr(logits))
     return a64, af, lp, ent, val, logits
 
 
@@ -694,7 +650,6 @@ def mlp_act_normal(obs, actor: MlpNetPtrs, critic: MlpNetPtrs, logstd, noise=Non
                    action_out=None, logprob_out=None, value_out=None, want_entropy: bool = False, want_mean: bool = False):
     """One rollout step of the continuous-action agent (ppo_continuous_action.py:221-226) in one launch.
     -> ``(action (B, D), logprob, entropy | None, value, mean | None)``."""
-    lib = _lib.load()
     B, O = obs.shape
     _chk(obs, torch.float32, "obs", (B, actor.obs_dim))
     dev, D = obs.device, actor.n_out
@@ -711,11 +666,8 @@ def mlp_act_normal(obs, actor: MlpNetPtrs, critic: MlpNetPtrs, logstd, noise=Non
     mean = torch.empty((B, D), dtype=torch.float32, device=dev) if want_mean else None
     if offset_base is not None:
         _chk(offset_base, torch.int64, "offset_base", (1,))
-    with _on(dev):
-        st = lib.mi355ppo_mlp_act_normal_f32(_ptr(obs), B, O, actor.params, critic.params, _ptr(logstd), D, _ptr(noise),
-                                             int(seed) & (2**64 - 1), int(offset) & (2**64 - 1), _ptr(offset_base), _ptr(act), _ptr(lp),
-                                             _ptr(ent), _ptr(val), _ptr(mean), _stream(dev))
-    _lib.check(st, "mi355ppo_mlp_act_normal_f32")
+    _launch("mi355ppo_mlp_act_normal_f32", dev, _ptr(obs), B, O, actor.params, critic.params, _ptr(logstd), D, _ptr(noise),
+            int(seed) & (2**64 - 1), int(offset) & (2**64 - 1), _ptr(offset_base), _ptr(act), _ptr(lp), _ptr(ent), _ptr(val), _ptr(mean))
     return act, lp, ent, val, mean
 
 
@@ -747,23 +699,20 @@ def mlp_ppo_fwd_bwd(b_obs, mb_inds, actor: MlpNetPtrs, critic: MlpNetPtrs, b_act
     if nbytes == 0:
         raise ValueError(f"mlp_ppo_fwd_bwd: unsupported shape (obs_dim={O} <= {MLP_MAX_OBS}, n_out={nout} <= {MLP_MAX_OUT})")
     ws = _workspace(dev, nbytes)
-    with _on(dev):
-        if normal:
-            ls = _chk(logstd.reshape(-1), torch.float32, "logstd", (nout,))
-            lg = _chk(logstd_grad.reshape(-1), torch.float32, "logstd_grad", (nout,))
-            if mean_shift is not None:
-                _chk(mean_shift, torch.float32, "mean_shift", (M, nout))
-            st = lib.mi355ppo_mlp_ppo_normal_fwd_bwd_f32(
-                _ptr(b_obs), _ptr(mb_inds), M, O, actor.params, critic.params, _ptr(ls), nout, _ptr(mean_shift), _ptr(b_actions), _ptr(lpv),
-                _ptr(advv), _ptr(retv), _ptr(valv), float(clip_coef), float(ent_coef), float(vf_coef), int(bool(norm_adv)),
-                int(bool(clip_vloss)), _ptr(adv_mean_den), actor.grads(), critic.grads(), _ptr(lg), _ptr(sc), int(rows_per_block), _ptr(ws),
-                ws.numel(), _stream(dev))
-        else:
-            st = lib.mi355ppo_mlp_ppo_categorical_fwd_bwd_f32(
-                _ptr(b_obs), _ptr(mb_inds), M, O, actor.params, critic.params, nout, _ptr(b_actions), _ptr(lpv), _ptr(advv), _ptr(retv),
-                _ptr(valv), float(clip_coef), float(ent_coef), float(vf_coef), int(bool(norm_adv)), int(bool(clip_vloss)),
-                _ptr(adv_mean_den), actor.grads(), critic.grads(), _ptr(sc), int(rows_per_block), _ptr(ws), ws.numel(), _stream(dev))
-    _lib.check(st, "mi355ppo_mlp_ppo_fwd_bwd_f32")
+    if normal:
+        ls = _chk(logstd.reshape(-1), torch.float32, "logstd", (nout,))
+        lg = _chk(logstd_grad.reshape(-1), torch.float32, "logstd_grad", (nout,))
+        if mean_shift is not None:
+            _chk(mean_shift, torch.float32, "mean_shift", (M, nout))
+        _launch("mi355ppo_mlp_ppo_normal_fwd_bwd_f32", dev, _ptr(b_obs), _ptr(mb_inds), M, O, actor.params, critic.params, _ptr(ls), nout,
+                _ptr(mean_shift), _ptr(b_actions), _ptr(lpv), _ptr(advv), _ptr(retv), _ptr(valv), float(clip_coef), float(ent_coef),
+                float(vf_coef), int(bool(norm_adv)), int(bool(clip_vloss)), _ptr(adv_mean_den), actor.grads(), critic.grads(), _ptr(lg),
+                _ptr(sc), int(rows_per_block), _ptr(ws), ws.numel())
+    else:
+        _launch("mi355ppo_mlp_ppo_categorical_fwd_bwd_f32", dev, _ptr(b_obs), _ptr(mb_inds), M, O, actor.params, critic.params, nout,
+                _ptr(b_actions), _ptr(lpv), _ptr(advv), _ptr(retv), _ptr(valv), float(clip_coef), float(ent_coef), float(vf_coef),
+                int(bool(norm_adv)), int(bool(clip_vloss)), _ptr(adv_mean_den), actor.grads(), critic.grads(), _ptr(sc),
+                int(rows_per_block), _ptr(ws), ws.numel())
     return sc
 
 
@@ -772,6 +721,8 @@ def _lstm_dims(gx, done):
     if gx.dim() != 3 or gx.shape[2] % 4:
         raise ValueError(f"gx: expected (T, B, 4H), got {tuple(gx.shape)}")
     T, B, G = gx.shape
+    if tuple(done.shape) != (T, B):
+        raise ValueError(f"done: expected (T, B) = {(T, B)}, got {tuple(done.shape)}")
     return T, B, G // 4
 
 
@@ -779,7 +730,6 @@ def lstm_seq_forward(gx, w_hh, h0, c0, done, record: bool = False):
     """The done-masked LSTM scan of ppo_atari_lstm.py:140-158 (``get_states``) in one launch: ``gx`` (T,B,4H) = x W_ih^T + b_ih +
     b_hh, ``w_hh`` (4H,H), ``h0`` / ``c0`` (B,H), ``done`` (T,B); H = 128.  Returns ``(h (T,B,H), hT, cT, record | None)``; the
     record (7 T B H floats, layout in include/mi355ppo.h) feeds ``lstm_seq_backward``."""
-    lib = _lib.load()
     T, B, H = _lstm_dims(gx, done)
     _chk(gx, torch.float32, "gx", (T, B, 4 * H))
     _chk(w_hh, torch.float32, "w_hh", (4 * H, H))
@@ -790,17 +740,14 @@ def lstm_seq_forward(gx, w_hh, h0, c0, done, record: bool = False):
     h = torch.empty((T, B, H), device=dev)
     hT, cT = torch.empty((B, H), device=dev), torch.empty((B, H), device=dev)
     rec = torch.empty(7 * T * B * H, device=dev) if record else None
-    with _on(dev):
-        st = lib.mi355ppo_lstm_seq_fwd_f32(_ptr(gx), _ptr(w_hh), _ptr(h0), _ptr(c0), _ptr(done), _ptr(h), _ptr(hT), _ptr(cT), _ptr(rec),
-                                           T, B, H, _stream(dev))
-    _lib.check(st, "mi355ppo_lstm_seq_fwd_f32")
+    _launch("mi355ppo_lstm_seq_fwd_f32", dev, _ptr(gx), _ptr(w_hh), _ptr(h0), _ptr(c0), _ptr(done), _ptr(h), _ptr(hT), _ptr(cT), _ptr(rec),
+            T, B, H)
     return h, hT, cT, rec
 
 
 def lstm_seq_backward(dh, dhT, dcT, record, w_hh, done, want_dh0: bool = True, want_dc0: bool = True):
     """Backward of ``lstm_seq_forward`` (BPTT with the state gradient masked by keep_t): ``dh`` (T,B,H) from the heads, ``dhT`` /
     ``dcT`` (B,H) or None.  Returns ``(dgx (T,B,4H), dh0 | None, dc0 | None)``; dW_hh = dgx^T hk is the caller's GEMM."""
-    lib = _lib.load()
     T, B, H = dh.shape
     _chk(dh, torch.float32, "dh", (T, B, H))
     if dhT is not None:
@@ -814,10 +761,8 @@ def lstm_seq_backward(dh, dhT, dcT, record, w_hh, done, want_dh0: bool = True, w
     dgx = torch.empty((T, B, 4 * H), device=dev)
     dh0 = torch.empty((B, H), device=dev) if want_dh0 else None
     dc0 = torch.empty((B, H), device=dev) if want_dc0 else None
-    with _on(dev):
-        st = lib.mi355ppo_lstm_seq_bwd_f32(_ptr(dh), _ptr(dhT), _ptr(dcT), _ptr(record), _ptr(w_hh), _ptr(done), _ptr(dgx), _ptr(dh0),
-                                           _ptr(dc0), T, B, H, _stream(dev))
-    _lib.check(st, "mi355ppo_lstm_seq_bwd_f32")
+    _launch("mi355ppo_lstm_seq_bwd_f32", dev, _ptr(dh), _ptr(dhT), _ptr(dcT), _ptr(record), _ptr(w_hh), _ptr(done), _ptr(dgx), _ptr(dh0),
+            _ptr(dc0), T, B, H)
     return dgx, dh0, dc0
 
 
@@ -831,13 +776,7 @@ def lstm_seq_dw_hh(dgx, record):
     return torch.bmm(dgx.transpose(1, 2), hk).sum(0)
 
 
-def _lstm_impl(t):
-    """The scans for ``t``'s device: the HIP kernels for CUDA tensors, the ``*_cpu`` twins (cleanrl_amd/host_ops.py) for CPU ones."""
-    if t.is_cuda:
-        return lstm_seq_forward, lstm_seq_backward
-    from . import host_ops
-
-    return host_ops.lstm_seq_forward, host_ops.lstm_seq_backward
+_LSTM = ("lstm_seq_forward", "lstm_seq_backward")
 
 
 class LSTMSeq(torch.autograd.Function):
@@ -848,7 +787,7 @@ class LSTMSeq(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, gx, w_hh, h0, c0, done):
-        fwd, _ = _lstm_impl(gx)
+        fwd, _ = twins(gx, *_LSTM)
         w = w_hh.detach().contiguous()
         d = done.detach().to(torch.float32).contiguous()
         h, hT, cT, rec = fwd(gx.detach().contiguous(), w, h0.detach().contiguous(), c0.detach().contiguous(), d, record=True)
@@ -858,7 +797,7 @@ class LSTMSeq(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dh, dhT, dcT):
         rec, w, d = ctx.saved_tensors
-        _, bwd = _lstm_impl(w)
+        _, bwd = twins(w, *_LSTM)
         T, B = d.shape
         H = w.shape[1]
         dh = torch.zeros((T, B, H), device=w.device) if dh is None else dh.contiguous()
@@ -873,7 +812,7 @@ def lstm_seq(gx, w_hh, h0, c0, done):
     """``LSTMSeq.apply`` when a gradient is wanted, else the inference scan without a record (the rollout step, the bootstrap)."""
     if torch.is_grad_enabled() and any(t.requires_grad for t in (gx, w_hh, h0, c0)):
         return LSTMSeq.apply(gx, w_hh, h0, c0, done)
-    fwd, _ = _lstm_impl(gx)
+    fwd, _ = twins(gx, *_LSTM)
     h, hT, cT, _ = fwd(gx.contiguous(), w_hh.detach().contiguous(), h0.contiguous(), c0.contiguous(),
                        done.to(torch.float32).contiguous())
     return h, hT, cT
@@ -909,10 +848,14 @@ def _trxl_checked(memory, layer, ep, rows, pos, mask, pe, gamma, beta, q):
     return E, T, layers, D, B, L, H
 
 
-def _trxl_report(err, fn: str) -> None:
-    """The error word of one call: read back (one sync) unless the stream is being captured into a graph."""
-    if not torch.cuda.is_current_stream_capturing() and int(err.item()) != 0:
-        raise IndexError(f"{fn}: an episode, row or position index was outside the memory / pe table (clamped on the device)")
+def _trxl_launch(name: str, dev, err, *args) -> None:
+    """``_launch`` with the call's error word between ``args`` and the four sizes: a caller-owned ``err`` is zeroed and left unread;
+    with None one is allocated and read back (one sync) unless the stream is being captured into a graph."""
+    own = err is None
+    err = torch.zeros(1, dtype=torch.int32, device=dev) if own else err.zero_()
+    _launch(name, dev, *args[:-4], _ptr(err), *args[-4:])
+    if own and not torch.cuda.is_current_stream_capturing() and int(err.item()) != 0:
+        raise IndexError(f"{name}: an episode, row or position index was outside the memory / pe table (clamped on the device)")
 
 
 def trxl_attn_forward(memory, layer: int, ep, rows, pos, mask, pe, gamma, beta, q, err=None):
@@ -920,29 +863,18 @@ def trxl_attn_forward(memory, layer: int, ep, rows, pos, mask, pe, gamma, beta, 
     rows): ``u`` (B,H,d) = sum_j softmax(s)_j LN(mem[ep, rows_j, layer] + pe[pos_j])_h and ``stats`` (B,H,2) (max, sum) for the
     backward.  ``q`` is q~ = W_k^T q (``q @ keys.weight``); ``pe`` may be None.  ``err`` (int32, 1 element): a caller-owned
     error word (zeroed here, left unread); with None one is allocated and checked after the launch."""
-    lib = _lib.load()
     E, T, layers, D, B, L, H = _trxl_checked(memory, layer, ep, rows, pos, mask, pe, gamma, beta, q)
     dev = q.device
     u = torch.empty((B, H, D // H), device=dev)
     stats = torch.empty((B, H, 2), device=dev)
-    own = err is None
-    if own:
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
-    else:
-        err.zero_()
     P = 0 if pe is None else pe.shape[0]
-    with _on(dev):
-        st = lib.mi355ppo_trxl_attn_fwd_f32(_ptr(memory), E, T, layers, int(layer), _ptr(ep), _ptr(rows), _ptr(pos), _ptr(mask), _ptr(pe),
-                                            P, _ptr(gamma), _ptr(beta), _ptr(q), _ptr(u), _ptr(stats), _ptr(err), B, L, D, H, _stream(dev))
-    _lib.check(st, "mi355ppo_trxl_attn_fwd_f32")
-    if own:
-        _trxl_report(err, "mi355ppo_trxl_attn_fwd_f32")
+    _trxl_launch("mi355ppo_trxl_attn_fwd_f32", dev, err, _ptr(memory), E, T, layers, int(layer), _ptr(ep), _ptr(rows), _ptr(pos),
+                 _ptr(mask), _ptr(pe), P, _ptr(gamma), _ptr(beta), _ptr(q), _ptr(u), _ptr(stats), B, L, D, H)
     return u, stats
 
 
 def trxl_attn_backward(memory, layer: int, ep, rows, pos, mask, pe, gamma, beta, q, u, stats, du, err=None):
     """Backward of ``trxl_attn_forward`` -> (dq (B,H,d), dgamma (D), dbeta (D)); no gradient reaches the memory."""
-    lib = _lib.load()
     E, T, layers, D, B, L, H = _trxl_checked(memory, layer, ep, rows, pos, mask, pe, gamma, beta, q)
     _chk(u, torch.float32, "u", (B, H, D // H))
     _chk(stats, torch.float32, "stats", (B, H, 2))
@@ -951,29 +883,14 @@ def trxl_attn_backward(memory, layer: int, ep, rows, pos, mask, pe, gamma, beta,
     dq = torch.empty((B, H, D // H), device=dev)
     rows_ws = torch.empty((2, B, D), device=dev)
     dgamma, dbeta = torch.empty(D, device=dev), torch.empty(D, device=dev)
-    own = err is None
-    if own:
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
-    else:
-        err.zero_()
     P = 0 if pe is None else pe.shape[0]
-    with _on(dev):
-        st = lib.mi355ppo_trxl_attn_bwd_f32(_ptr(memory), E, T, layers, int(layer), _ptr(ep), _ptr(rows), _ptr(pos), _ptr(mask), _ptr(pe),
-                                            P, _ptr(gamma), _ptr(beta), _ptr(q), _ptr(u), _ptr(stats), _ptr(du), _ptr(dq), _ptr(rows_ws),
-                                            _ptr(dgamma), _ptr(dbeta), _ptr(err), B, L, D, H, _stream(dev))
-    _lib.check(st, "mi355ppo_trxl_attn_bwd_f32")
-    if own:
-        _trxl_report(err, "mi355ppo_trxl_attn_bwd_f32")
+    _trxl_launch("mi355ppo_trxl_attn_bwd_f32", dev, err, _ptr(memory), E, T, layers, int(layer), _ptr(ep), _ptr(rows), _ptr(pos),
+                 _ptr(mask), _ptr(pe), P, _ptr(gamma), _ptr(beta), _ptr(q), _ptr(u), _ptr(stats), _ptr(du), _ptr(dq), _ptr(rows_ws),
+                 _ptr(dgamma), _ptr(dbeta), B, L, D, H)
     return dq, dgamma, dbeta
 
 
-def _trxl_impl(t):
-    """The attention for ``t``'s device: the HIP kernels for CUDA tensors, the ``*_cpu`` twins (cleanrl_amd/host_ops.py) for CPU ones."""
-    if t.is_cuda:
-        return trxl_attn_forward, trxl_attn_backward
-    from . import host_ops
-
-    return host_ops.trxl_attn_forward, host_ops.trxl_attn_backward
+_TRXL = ("trxl_attn_forward", "trxl_attn_backward")
 
 
 def _trxl_inputs(memory, ep, rows, pos, mask, pe):
@@ -991,7 +908,7 @@ class TrXLMemoryAttention(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, gamma, beta, memory, layer, ep, rows, pos, mask, pe):
-        fwd, _ = _trxl_impl(q)
+        fwd, _ = twins(q, *_TRXL)
         memory, ep, rows, pos, mask, pe = _trxl_inputs(memory, ep, rows, pos, mask, pe)
         q, gamma, beta = q.detach().contiguous(), gamma.detach().contiguous(), beta.detach().contiguous()
         u, stats = fwd(memory, layer, ep, rows, pos, mask, pe, gamma, beta, q)
@@ -1002,7 +919,7 @@ class TrXLMemoryAttention(torch.autograd.Function):
     @staticmethod
     def backward(ctx, du):
         q, gamma, beta, memory, ep, rows, pos, mask, pe, u, stats = ctx.saved_tensors
-        _, bwd = _trxl_impl(q)
+        _, bwd = twins(q, *_TRXL)
         dq, dgamma, dbeta = bwd(memory, ctx.layer, ep, rows, pos, mask, pe, gamma, beta, q, u, stats, du.contiguous())
         return dq, dgamma, dbeta, None, None, None, None, None, None, None
 
@@ -1011,7 +928,7 @@ def trxl_memory_attention(q, gamma, beta, memory, layer: int, ep, rows, pos, mas
     """``TrXLMemoryAttention.apply`` when a gradient is wanted, else the forward alone (the rollout step, the bootstrap)."""
     if torch.is_grad_enabled() and any(t.requires_grad for t in (q, gamma, beta)):
         return TrXLMemoryAttention.apply(q, gamma, beta, memory, layer, ep, rows, pos, mask, pe)
-    fwd, _ = _trxl_impl(q)
+    fwd, _ = twins(q, *_TRXL)
     memory, ep, rows, pos, mask, pe = _trxl_inputs(memory, ep, rows, pos, mask, pe)
     u, _ = fwd(memory, layer, ep, rows, pos, mask, pe, gamma.detach().contiguous(), beta.detach().contiguous(), q.detach().contiguous())
     return u
@@ -1044,10 +961,6 @@ def _impala_check(x, params):
             raise ValueError(f"params[{i}]: expected shape {shp}, got {tuple(p.shape)} (channels must be {list(IMPALA_CHANNELS)})")
 
 
-def _ptr_array(ts):
-    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-
-
 def impala_forward(x, params):
     """The IMPALA-CNN trunk (ppo_procgen.py:86-124 / ppg_procgen.py:123-165, three ConvSequences) on the HIP kernels of
     csrc/impala.hip: x (B,64,64,3) f32 channels-last frames, params the 30 conv weights / biases in state_dict order.
@@ -1063,10 +976,8 @@ def impala_forward(x, params):
     arg = torch.empty(int(lib.mi355ppo_impala_argmax_bytes(B)), dtype=torch.uint8, device=dev)
     nws = int(lib.mi355ppo_impala_workspace_bytes(B, 0))
     ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-    with _on(dev):
-        st = lib.mi355ppo_impala_fwd_f32(_ptr(x), _ptr_array(params), _ptr(y), _ptr(saved), _ptr(arg), B, *IMPALA_FRAME, *IMPALA_CHANNELS,
-                                         _ptr(ws), nws, _stream(dev))
-    _lib.check(st, "mi355ppo_impala_fwd_f32")
+    _launch("mi355ppo_impala_fwd_f32", dev, _ptr(x), _ptr_array(params), _ptr(y), _ptr(saved), _ptr(arg), B, *IMPALA_FRAME,
+            *IMPALA_CHANNELS, _ptr(ws), nws)
     return y, saved, arg
 
 
@@ -1086,46 +997,32 @@ def impala_backward(x, params, saved, arg, dy):
         o += p.numel()
     nws = int(lib.mi355ppo_impala_workspace_bytes(B, 1))
     ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-    with _on(dev):
-        st = lib.mi355ppo_impala_bwd_f32(_ptr(x), _ptr_array(params), _ptr(saved), _ptr(arg), _ptr(dy), _ptr_array(grads), B,
-                                         *IMPALA_FRAME, *IMPALA_CHANNELS, _ptr(ws), nws, _stream(dev))
-    _lib.check(st, "mi355ppo_impala_bwd_f32")
+    _launch("mi355ppo_impala_bwd_f32", dev, _ptr(x), _ptr_array(params), _ptr(saved), _ptr(arg), _ptr(dy), _ptr_array(grads), B,
+            *IMPALA_FRAME, *IMPALA_CHANNELS, _ptr(ws), nws)
     return grads
 
 
 def impala_maxpool_forward(x):
     """The trunk's max pool (3, stride 2, pad 1) alone on channels-last x (B,H,W,C) -> (y, argmax bytes (B,H/2,W/2,C))."""
-    lib = _lib.load()
     _chk(x, torch.float32, "x")
     B, H, W, C = x.shape
     y = torch.empty((B, H // 2, W // 2, C), device=x.device)
     arg = torch.empty((B, H // 2, W // 2, C), dtype=torch.uint8, device=x.device)
-    with _on(x.device):
-        st = lib.mi355ppo_impala_maxpool_fwd_f32(_ptr(x), _ptr(y), _ptr(arg), B, H, W, C, _stream(x.device))
-    _lib.check(st, "mi355ppo_impala_maxpool_fwd_f32")
+    _launch("mi355ppo_impala_maxpool_fwd_f32", x.device, _ptr(x), _ptr(y), _ptr(arg), B, H, W, C)
     return y, arg
 
 
 def impala_maxpool_backward(dy, arg):
     """Backward of ``impala_maxpool_forward``: dx (B,2Ho,2Wo,C)."""
-    lib = _lib.load()
     _chk(dy, torch.float32, "dy")
     B, Ho, Wo, C = dy.shape
     _chk(arg, torch.uint8, "argmax", tuple(dy.shape))
     dx = torch.empty((B, 2 * Ho, 2 * Wo, C), device=dy.device)
-    with _on(dy.device):
-        st = lib.mi355ppo_impala_maxpool_bwd_f32(_ptr(dy), _ptr(arg), _ptr(dx), B, 2 * Ho, 2 * Wo, C, _stream(dy.device))
-    _lib.check(st, "mi355ppo_impala_maxpool_bwd_f32")
+    _launch("mi355ppo_impala_maxpool_bwd_f32", dy.device, _ptr(dy), _ptr(arg), _ptr(dx), B, 2 * Ho, 2 * Wo, C)
     return dx
 
 
-def _impala_impl(t):
-    """The trunk for ``t``'s device: the HIP kernels for CUDA tensors, the ``*_cpu`` twins (cleanrl_amd/host_ops.py) for CPU ones."""
-    if t.is_cuda:
-        return impala_forward, impala_backward
-    from . import host_ops
-
-    return host_ops.impala_forward, host_ops.impala_backward
+_IMPALA = ("impala_forward", "impala_backward")
 
 
 class ImpalaTrunk(torch.autograd.Function):
@@ -1135,7 +1032,7 @@ class ImpalaTrunk(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, *params):
-        fwd, _ = _impala_impl(x)
+        fwd, _ = twins(x, *_IMPALA)
         xs = x.detach().contiguous()
         ps = [p.detach().contiguous() for p in params]
         _impala_check(xs, ps)
@@ -1146,7 +1043,7 @@ class ImpalaTrunk(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         xs, saved, arg, *ps = ctx.saved_tensors
-        _, bwd = _impala_impl(xs)
+        _, bwd = twins(xs, *_IMPALA)
         grads = bwd(xs, ps, saved, arg, dy.contiguous())
         return (None, *grads)
 
@@ -1155,7 +1052,7 @@ def impala_trunk(x, params):
     """``ImpalaTrunk.apply`` when a gradient is wanted, else the forward alone (the rollout step, the old-policy pass)."""
     if torch.is_grad_enabled() and any(p.requires_grad for p in params):
         return ImpalaTrunk.apply(x, *params)
-    fwd, _ = _impala_impl(x)
+    fwd, _ = twins(x, *_IMPALA)
     ps = [p.detach().contiguous() for p in params]
     _impala_check(x, ps)
     return fwd(x.contiguous(), ps)[0]
@@ -1163,7 +1060,6 @@ def impala_trunk(x, params):
 
 def synth_continuous_step(state, reset_state, At, Bm, w, noise, k: int, steps, horizon: float, action, obs_out, reward, done, k_base=None):
     """One step of the device-resident continuous-control stand-in env (test / bench support, not the reference path)."""
-    lib = _lib.load()
     N, O = state.shape
     D = action.shape[1]
     bank = noise.shape[0]
@@ -1174,11 +1070,8 @@ def synth_continuous_step(state, reset_state, At, Bm, w, noise, k: int, steps, h
     if k_base is not None:
         _chk(k_base, torch.int64, "k_base", (1,))
     dev = state.device
-    with _on(dev):
-        st = lib.mi355ppo_synth_continuous_step_f32(_ptr(state), _ptr(reset_state), _ptr(At), _ptr(Bm), _ptr(w), _ptr(noise), bank,
-                                                    int(k) & (2**64 - 1), _ptr(k_base), _ptr(steps), float(horizon), _ptr(action),
-                                                    _ptr(obs_out), _ptr(reward), _ptr(done), N, O, D, _stream(dev))
-    _lib.check(st, "mi355ppo_synth_continuous_step_f32")
+    _launch("mi355ppo_synth_continuous_step_f32", dev, _ptr(state), _ptr(reset_state), _ptr(At), _ptr(Bm), _ptr(w), _ptr(noise), bank,
+            int(k) & (2**64 - 1), _ptr(k_base), _ptr(steps), float(horizon), _ptr(action), _ptr(obs_out), _ptr(reward), _ptr(done), N, O, D)
 
 
 # ------------------------------------------------------------------------------------------- PQN (csrc/pqn.hip)
@@ -1201,10 +1094,8 @@ def pqn_egreedy(q, random_actions, u, epsilon: float, actions_out, values_out, a
     _chk(values_out, torch.float32, "values_out", (N,))
     if action_i64_out is not None:
         _chk(action_i64_out, torch.int64, "action_i64_out", (N,))
-    with _on(q.device):
-        st = _lib.load().mi355ppo_pqn_egreedy_f32(_ptr(q), _ptr(random_actions), _ptr(u), float(epsilon), _ptr(actions_out), _ptr(values_out),
-                                                  _ptr(action_i64_out), N, A, _stream(q.device))
-    _lib.check(st, "mi355ppo_pqn_egreedy_f32")
+    _launch("mi355ppo_pqn_egreedy_f32", q.device, _ptr(q), _ptr(random_actions), _ptr(u), float(epsilon), _ptr(actions_out),
+            _ptr(values_out), _ptr(action_i64_out), N, A)
     return actions_out, values_out
 
 
@@ -1219,10 +1110,8 @@ def pqn_qlambda(rewards, dones, values, next_done, next_q, gamma: float, q_lambd
     if returns is None:
         returns = torch.empty_like(rewards)
     _chk(returns, torch.float32, "returns", (T, N))
-    with _on(rewards.device):
-        st = _lib.load().mi355ppo_pqn_qlambda_f32(_ptr(rewards), _ptr(dones), _ptr(values), _ptr(next_done), _ptr(next_q), _ptr(returns),
-                                                  T, N, A, float(gamma), float(q_lambda), _stream(rewards.device))
-    _lib.check(st, "mi355ppo_pqn_qlambda_f32")
+    _launch("mi355ppo_pqn_qlambda_f32", rewards.device, _ptr(rewards), _ptr(dones), _ptr(values), _ptr(next_done), _ptr(next_q),
+            _ptr(returns), T, N, A, float(gamma), float(q_lambda))
     return returns
 
 
@@ -1237,10 +1126,8 @@ def pqn_td_loss(q, mb_inds, b_actions, b_returns, dq=None, scalars=None):
     b_returns = _chk(b_returns.reshape(-1), torch.float32, "b_returns", (B,))
     dq = torch.empty_like(q) if dq is None else _chk(dq, torch.float32, "dq", (M, A))
     scalars = torch.empty(2, dtype=torch.float32, device=q.device) if scalars is None else _chk(scalars, torch.float32, "scalars", (2,))
-    with _on(q.device):
-        st = _lib.load().mi355ppo_pqn_td_loss_fwd_bwd_f32(_ptr(q), _ptr(mb_inds), _ptr(b_actions), _ptr(b_returns), _ptr(dq), _ptr(scalars),
-                                                          M, A, B, _stream(q.device))
-    _lib.check(st, "mi355ppo_pqn_td_loss_fwd_bwd_f32")
+    _launch("mi355ppo_pqn_td_loss_fwd_bwd_f32", q.device, _ptr(q), _ptr(mb_inds), _ptr(b_actions), _ptr(b_returns), _ptr(dq), _ptr(scalars),
+            M, A, B)
     return dq, scalars
 
 
@@ -1256,9 +1143,7 @@ def pqn_mlp_forward(obs, params, n_actions: int, q_out=None):
     N, O = _pqn_net(obs, params, n_actions)
     q_out = torch.empty((N, n_actions), dtype=torch.float32, device=obs.device) if q_out is None else _chk(q_out, torch.float32, "q_out",
                                                                                                             (N, n_actions))
-    with _on(obs.device):
-        st = _lib.load().mi355ppo_pqn_mlp_fwd_f32(_ptr(obs), _ptr(params), _ptr(q_out), N, O, int(n_actions), _stream(obs.device))
-    _lib.check(st, "mi355ppo_pqn_mlp_fwd_f32")
+    _launch("mi355ppo_pqn_mlp_fwd_f32", obs.device, _ptr(obs), _ptr(params), _ptr(q_out), N, O, int(n_actions))
     return q_out
 
 
@@ -1278,11 +1163,9 @@ def pqn_mlp_act(obs, params, n_actions: int, random_actions, u, epsilon: float, 
     if done_row_out is not None:
         _chk(done_in, torch.float32, "done_in", (N,))
         _chk(done_row_out, torch.float32, "done_row_out", (N,))
-    with _on(obs.device):
-        st = _lib.load().mi355ppo_pqn_mlp_act_f32(_ptr(obs), _ptr(params), _ptr(random_actions), _ptr(u), float(epsilon), _ptr(actions_out),
-                                                  _ptr(values_out), _ptr(action_i64_out), _ptr(obs_row_out), _ptr(done_in), _ptr(done_row_out), N,
-                                                  O, int(n_actions), _stream(obs.device))
-    _lib.check(st, "mi355ppo_pqn_mlp_act_f32")
+    _launch("mi355ppo_pqn_mlp_act_f32", obs.device, _ptr(obs), _ptr(params), _ptr(random_actions), _ptr(u), float(epsilon),
+            _ptr(actions_out), _ptr(values_out), _ptr(action_i64_out), _ptr(obs_row_out), _ptr(done_in), _ptr(done_row_out), N, O,
+            int(n_actions))
     return actions_out, values_out
 
 
@@ -1299,17 +1182,15 @@ def pqn_mlp_td_fwd_bwd(b_obs, mb_inds, params, b_actions, b_returns, grads, n_ac
     scalars = torch.empty(2, dtype=torch.float32, device=dev) if scalars is None else _chk(scalars, torch.float32, "scalars", (2,))
     lib = _lib.load()
     ws = _workspace(dev, lib.mi355ppo_pqn_mlp_td_workspace_bytes(M, O, int(n_actions)))
-    with _on(dev):
-        st = lib.mi355ppo_pqn_mlp_td_fwd_bwd_f32(_ptr(b_obs), B, _ptr(mb_inds), _ptr(params), _ptr(b_actions), _ptr(b_returns), _ptr(grads),
-                                                 _ptr(scalars), M, O, int(n_actions), _ptr(ws), ws.numel(), _stream(dev))
-    _lib.check(st, "mi355ppo_pqn_mlp_td_fwd_bwd_f32")
+    _launch("mi355ppo_pqn_mlp_td_fwd_bwd_f32", dev, _ptr(b_obs), B, _ptr(mb_inds), _ptr(params), _ptr(b_actions), _ptr(b_returns),
+            _ptr(grads), _ptr(scalars), M, O, int(n_actions), _ptr(ws), ws.numel())
     return scalars
 
 
 def radam_schedule(lr: float, step: int, beta1: float = 0.9, beta2: float = 0.999):
     """The 8-float schedule slot of RAdam step ``step`` (1-based), as the library forms it (host floats)."""
     out = (ctypes.c_float * 8)()
-    _lib.check(_lib.load().mi355ppo_radam_schedule_f32(float(lr), float(beta1), float(beta2), int(step), out), "mi355ppo_radam_schedule_f32")
+    _lib.call("mi355ppo_radam_schedule_f32", float(lr), float(beta1), float(beta2), int(step), out)
     return [float(x) for x in out]
 
 
@@ -1329,11 +1210,8 @@ def clip_radam_(params, grads, exp_avg, exp_avg_sq, step: int, lr: float, max_gr
     if total_norm_out is None:
         total_norm_out = torch.empty(1, dtype=torch.float32, device=dev)
     ws = _workspace(dev, lib.mi355ppo_clip_radam_workspace_bytes(n))
-    with _on(dev):
-        st = lib.mi355ppo_clip_radam_f32(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), n, float(max_grad_norm), float(lr),
-                                         float(beta1), float(beta2), float(eps), int(step), _ptr(total_norm_out), _ptr(ws), ws.numel(),
-                                         _stream(dev))
-    _lib.check(st, "mi355ppo_clip_radam_f32")
+    _launch("mi355ppo_clip_radam_f32", dev, _ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), n, float(max_grad_norm), float(lr),
+            float(beta1), float(beta2), float(eps), int(step), _ptr(total_norm_out), _ptr(ws), ws.numel())
     return total_norm_out
 
 
@@ -1347,9 +1225,6 @@ def clip_radam_sched_(params, grads, exp_avg, exp_avg_sq, sched8, max_grad_norm:
     if total_norm_out is None:
         total_norm_out = torch.empty(1, dtype=torch.float32, device=dev)
     ws = _workspace(dev, lib.mi355ppo_clip_radam_workspace_bytes(n))
-    with _on(dev):
-        st = lib.mi355ppo_clip_radam_sched_f32(_ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), n, float(max_grad_norm),
-                                               float(beta1), float(beta2), float(eps), _ptr(sched8), _ptr(total_norm_out), _ptr(ws),
-                                               ws.numel(), _stream(dev))
-    _lib.check(st, "mi355ppo_clip_radam_sched_f32")
+    _launch("mi355ppo_clip_radam_sched_f32", dev, _ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), n, float(max_grad_norm),
+            float(beta1), float(beta2), float(eps), _ptr(sched8), _ptr(total_norm_out), _ptr(ws), ws.numel())
     return total_norm_out

@@ -29,9 +29,10 @@ def test_gae_goldens_bit_exact(case, variant):
     if variant == 3 and N % 4 != 0:
         # the float4 variant needs N % 4 == 0: the library refuses it before any launch and leaves the outputs alone
         adv, ret = (torch.full((T_, N), 7.0, device=DEV) for _ in range(2))
-        with pytest.raises(_lib.Mi355PpoError, match="variant 3 needs N%4==0"):
+        with pytest.raises(_lib.Mi355PpoError, match="variant 3 needs N%4==0") as e:
             ops.gae(G(g["rewards"]), G(g["dones"]), G(g["values"]), G(g["next_done"]), G(g["next_value"]), float(g["gamma"]),
                     float(g["gae_lambda"]), adv, ret, variant=3)
+        assert str(e.value).startswith("mi355ppo_gae_f32_variant failed"), "the message names the symbol that was called"
         torch.cuda.synchronize()
         assert (adv == 7.0).all() and (ret == 7.0).all()
         return

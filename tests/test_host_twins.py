@@ -191,3 +191,67 @@ def test_twins_validate_and_refuse_device_tensors():
     meta = torch.zeros(4, 4, device="meta")
     with pytest.raises(TypeError, match="CPU tensors only"):
         H.gae(meta, meta, meta, meta[0], meta[0], 0.99, 0.95)
+
+
+def test_a_failing_status_call_names_the_symbol_that_was_called():
+    """``step = 0`` is MI355PPO_EINVAL in the twin before any memory is touched (see the ctypes line above); the wrapper's message
+    must BEGIN with the symbol it called (the library's own last_error text names a function too, so a substring proves nothing)."""
+    p, g, m, v = torch.ones(16), torch.ones(16), torch.zeros(16), torch.zeros(16)
+    with pytest.raises(_lib.Mi355PpoError) as e:
+        H.clip_adam_(p, g, m, v, step=0, lr=1e-3, max_grad_norm=0.5)
+    assert str(e.value).startswith("mi355ppo_clip_adam_f32_cpu failed with status -1: ")
+    assert len(str(e.value)) > len("mi355ppo_clip_adam_f32_cpu failed with status -1: ")      # the last_error part is still there
+    assert torch.equal(p, torch.ones(16)) and torch.equal(g, torch.ones(16))
+
+
+def test_lib_call_names_its_symbol_and_leaves_value_helpers_alone():
+    with pytest.raises(_lib.Mi355PpoError) as e:
+        _lib.call("mi355ppo_gae_f32_cpu", None, None, None, None, None, None, None, 4, 4, 0.99, 0.95)
+    assert str(e.value).startswith("mi355ppo_gae_f32_cpu failed with status -1: ")
+    assert _lib.call("mi355ppo_radam_schedule_f32", 1e-3, 0.9, 0.999, 1, (ctypes.c_float * 8)()) is None
+
+
+def test_clip_adam_twin_refuses_buffers_it_would_overrun():
+    """The four flat buffers are written through raw pointers: float64, non-contiguous or one element short is refused, untouched."""
+    n = 16
+    good = lambda: [torch.ones(n), torch.ones(n), torch.zeros(n), torch.zeros(n)]      # noqa: E731
+    bad = {"float64": (lambda: torch.ones(n, dtype=torch.float64), TypeError), "view": (lambda: torch.ones(2 * n)[::2], ValueError),
+           "short": (lambda: torch.ones(n - 1), ValueError)}
+    for which in (1, 2, 3):                    # (params itself defines n)
+        for name, (make, exc) in bad.items():
+            bufs = good()
+            bufs[which] = make()
+            before = [b.clone() for b in bufs]
+            with pytest.raises(exc):
+                H.clip_adam_(*bufs, step=1, lr=1e-3, max_grad_norm=0.5)
+            assert all(torch.equal(a, b) for a, b in zip(bufs, before)), (which, name)
+    for name in ("float64", "view"):
+        bufs = good()
+        bufs[0] = bad[name][0]()
+        with pytest.raises(bad[name][1]):
+            H.clip_adam_(*bufs, step=1, lr=1e-3, max_grad_norm=0.5)
+
+
+def test_host_pointer_checks_survive_python_O():
+    """The contiguity / dtype / length guards are raises, not asserts: ``python -O`` keeps them."""
+    code = ("import torch\n"
+            "from cleanrl_amd import host_ops as H\n"
+            "assert False, 'asserts are off under -O'\n"
+            "x = torch.zeros((4, 4))\n"
+            "for bad, exc in ((torch.zeros(7), ValueError), (torch.zeros(8, dtype=torch.float64), TypeError), (torch.zeros(16)[::2], ValueError)):\n"
+            "    try:\n"
+            "        H.pqn_mlp_forward(x, torch.zeros(H.pqn_param_count(4, 2)), 2, q_out=bad)\n"
+            "    except exc:\n"
+            "        continue\n"
+            "    raise SystemExit('no refusal for %r' % (bad,))\n"
+            "try:\n"
+            "    H.gae(x.t(), x, x, x[0], x[0], 0.99, 0.95)\n"            # inputs are coerced, as before
+            "    H._p(x.t())\n"
+            "except ValueError:\n"
+            "    print('refused')\n")
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, "-O", "-c", code], capture_output=True, text=True, cwd=root, timeout=600)
+    assert out.returncode == 0 and out.stdout.strip() == "refused", out.stdout[-2000:] + out.stderr[-2000:]

@@ -179,3 +179,51 @@ def test_clip_radam_twin_against_torch():
     assert float(tn) < 10.0  # the last steps are not clipped; step 7 was
     sched = [H.radam_schedule(2.5e-4, s)[4] for s in range(1, 8)]
     assert sched == [0.0] * 5 + [1.0, 1.0]
+
+
+# ------------------------------------------------------------------------------------------- caller-owned outputs
+def _bad_outputs(good):
+    """``good`` (a contiguous CPU tensor a twin writes) -> its float64 copy, a non-contiguous view of the same shape and a tensor one
+    element short, each with the exception the wrapper owes."""
+    wide = torch.zeros(tuple(good.shape[:-1]) + (2 * good.shape[-1],), dtype=good.dtype)[..., ::2]
+    assert wide.shape == good.shape and (good.numel() == 1 or not wide.is_contiguous())      # (one element is always contiguous)
+    other = torch.float64 if good.dtype == torch.float32 else torch.int32
+    return [(torch.zeros(good.shape, dtype=other), TypeError), (torch.zeros(good.numel() - 1, dtype=good.dtype), ValueError)] + \
+        [(wide, ValueError)] * (good.numel() > 1)
+
+
+def _refuses(call, outputs):
+    """``call(**outputs)`` is fine; with any one output swapped for a bad one it raises and no output is written."""
+    call(**{k: v.clone() for k, v in outputs.items()})
+    for name, good in outputs.items():
+        for bad, exc in _bad_outputs(good):
+            kw = {k: torch.full(v.shape, 7, dtype=v.dtype) for k, v in outputs.items()}
+            kw[name] = bad.fill_(7) if bad.is_contiguous() else bad.copy_(torch.full(bad.shape, 7, dtype=bad.dtype))
+            with pytest.raises(exc):
+                call(**kw)
+            assert all(bool((v == 7).all()) for v in kw.values()), (name, exc)
+
+
+def test_twins_refuse_caller_owned_outputs_they_would_overrun():
+    N, O, A, T = 5, 4, 3, 6
+    g = torch.Generator().manual_seed(3)
+    obs, q = torch.randn((N, O), generator=g), torch.randn((N, A), generator=g)
+    params = torch.randn(H.pqn_param_count(O, A), generator=g) * 0.1
+    rnd, u = torch.randint(0, A, (N,), generator=g), torch.rand(N, generator=g)
+    f, i64 = (lambda *s: torch.zeros(s)), (lambda *s: torch.zeros(s, dtype=torch.int64))
+    _refuses(lambda **o: H.pqn_egreedy(q, rnd, u, 0.1, **o), dict(actions_out=f(N), values_out=f(N), action_i64_out=i64(N)))
+    _refuses(lambda **o: H.pqn_mlp_act(obs, params, A, rnd, u, 0.1, done_in=torch.zeros(N), **o),
+             dict(actions_out=f(N), values_out=f(N), action_i64_out=i64(N), obs_row_out=f(N, O), done_row_out=f(N)))
+    r, d, v, nd, nq = _qlambda_inputs(T, N, A, seed=5)
+    _refuses(lambda **o: H.pqn_qlambda(r, d, v, nd, nq, 0.99, 0.65, **o), dict(returns=f(T, N)))
+    inds, ba, br = torch.tensor([3, 0, 4, 1, 2]), torch.randint(0, A, (N,)).float(), torch.randn(N, generator=g)
+    _refuses(lambda **o: H.pqn_td_loss(q, inds, ba, br, **o), dict(dq=f(N, A), scalars=f(2)))
+    _refuses(lambda **o: H.pqn_mlp_forward(obs, params, A, **o), dict(q_out=f(N, A)))
+    _refuses(lambda **o: H.pqn_mlp_td_fwd_bwd(obs, inds, params, ba, br, n_actions=A, **o), dict(grads=f(params.numel()), scalars=f(2)))
+    n = 16
+    # (params defines n: a shorter one is a smaller update, so it is tried for dtype and layout only)
+    _refuses(lambda **o: H.clip_radam_(torch.ones(n), step=1, lr=1e-3, max_grad_norm=0.5, **o),
+             dict(grads=torch.ones(n), exp_avg=f(n), exp_avg_sq=f(n), total_norm_out=f(1)))
+    for bad, exc in _bad_outputs(torch.ones(n))[::2]:
+        with pytest.raises(exc):
+            H.clip_radam_(bad, torch.ones(n), f(n), f(n), step=1, lr=1e-3, max_grad_norm=0.5)
