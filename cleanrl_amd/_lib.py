@@ -189,9 +189,15 @@ SIGNATURES = {
                                         _P]),
     "mi355ppo_clip_radam_sched_f32": (c_int, [_P, _P, _P, _P, c_int64, c_double, c_double, c_double, c_double, _P, _P, _P, c_size_t, _P]),
     "mi355ppo_clip_radam_f32_cpu": (c_int, [_P, _P, _P, _P, c_int64, c_double, c_double, c_double, c_double, c_double, c_int64, _P]),
+    # the recurrent PQN tail (ABI 2.6, csrc/pqn_lstm.hip)
+    "mi355ppo_pqn_lstm_act_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_double, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "mi355ppo_pqn_lstm_act_f32_cpu": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_double, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int]),
+    "mi355ppo_pqn_lstm_td_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "mi355ppo_pqn_lstm_td_fwd_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int64, _P, c_size_t, _P]),
+    "mi355ppo_pqn_lstm_td_fwd_bwd_f32_cpu": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int64]),
 }
 
-ABI_VERSION = 250       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)
+ABI_VERSION = 260       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)
 
 _lib = None
 

@@ -1104,3 +1104,79 @@ class AtariQNetwork(nn.Module):
 
     def forward(self, x):
         return self.network(x / 255.0)
+
+
+class AtariLSTMQNetwork(nn.Module):
+    """pqn_atari_envpool_lstm.py's ``QNetwork``: the LayerNorm NatureCNN on ONE frame -> ``nn.LSTM(512, 128)`` (zero biases,
+    orthogonal weights) with the done reset of ``get_states`` -> ``q_func = Linear(128, A)``, built in the reference's order, so a
+    torch seed gives the reference's weights.  ``forward`` / ``get_states`` are the reference's per-step loop (the ``torch``
+    backend).  The fused backend of ``LSTMPQNLearner`` uses the seams below: ``gates`` (trunk + the gx GEMM, both torch) and
+    ``states_fused`` (``ops.lstm_seq``: all T steps in one scan, HIP kernels on the GPU and their host twins on the CPU); the cell of
+    a rollout step, ``q_func``, e-greedy and the TD loss run in csrc/pqn_lstm.hip on this module's parameters."""
+
+    def __init__(self, env):
+        super().__init__()
+        self.network = nn.Sequential(
+            layer_init(nn.Conv2d(1, 32, 8, stride=4)),
+            nn.LayerNorm([32, 20, 20]),
+            nn.ReLU(),
+            layer_init(nn.Conv2d(32, 64, 4, stride=2)),
+            nn.LayerNorm([64, 9, 9]),
+            nn.ReLU(),
+            layer_init(nn.Conv2d(64, 64, 3, stride=1)),
+            nn.LayerNorm([64, 7, 7]),
+            nn.ReLU(),
+            nn.Flatten(),
+            layer_init(nn.Linear(3136, 512)),
+            nn.LayerNorm(512),
+            nn.ReLU(),
+        )
+        self.lstm = nn.LSTM(512, 128)
+        for name, param in self.lstm.named_parameters():
+            if "bias" in name:
+                nn.init.constant_(param, 0)
+            elif "weight" in name:
+                nn.init.orthogonal_(param, 1.0)
+        self.q_func = layer_init(nn.Linear(128, env.single_action_space.n))
+
+    def initial_state(self, num_envs: int, device):
+        shape = (self.lstm.num_layers, num_envs, self.lstm.hidden_size)
+        return torch.zeros(shape).to(device), torch.zeros(shape).to(device)
+
+    def get_states(self, x, lstm_state, done):
+        hidden = self.network(x / 255.0)
+
+        # LSTM logic
+        batch_size = lstm_state[0].shape[1]
+        hidden = hidden.reshape((-1, batch_size, self.lstm.input_size))
+        done = done.reshape((-1, batch_size))
+        new_hidden = []
+        for h, d in zip(hidden, done):
+            h, lstm_state = self.lstm(
+                h.unsqueeze(0),
+                (
+                    (1.0 - d).view(1, -1, 1) * lstm_state[0],
+                    (1.0 - d).view(1, -1, 1) * lstm_state[1],
+                ),
+            )
+            new_hidden += [h]
+        new_hidden = torch.flatten(torch.cat(new_hidden), 0, 1)
+        return new_hidden, lstm_state
+
+    def forward(self, x, lstm_state, done):
+        hidden, lstm_state = self.get_states(x, lstm_state, done)
+        return self.q_func(hidden), lstm_state
+
+    # ---- the fused seams
+    def gates(self, x):
+        """gx (rows, 4H) = trunk(x / 255) W_ih^T + (b_ih + b_hh): the input half of every gate pre-activation, as the scan and the
+        act kernel take it."""
+        lstm = self.lstm
+        return nn.functional.linear(self.network(x / 255.0), lstm.weight_ih_l0, lstm.bias_ih_l0 + lstm.bias_hh_l0)
+
+    def states_fused(self, x, lstm_state, done):
+        """``get_states`` as one scan over the T time-major steps of the B envs of ``lstm_state`` -> (h (T*B, H), new state)."""
+        batch_size, H = lstm_state[0].shape[1], self.lstm.hidden_size
+        gx = self.gates(x).reshape(-1, batch_size, 4 * H)
+        h, hT, cT = ops.lstm_seq(gx, self.lstm.weight_hh_l0, lstm_state[0][0], lstm_state[1][0], done.reshape(-1, batch_size))
+        return h.reshape(-1, H), (hT.unsqueeze(0), cT.unsqueeze(0))

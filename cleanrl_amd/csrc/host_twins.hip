@@ -19,6 +19,7 @@
 #include "trxl_rows.h"
 #include "impala_rows.h"
 #include "pqn_rows.h"
+#include "pqn_lstm_rows.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -1203,5 +1204,97 @@ extern "C" MI355PPO_API int mi355ppo_clip_radam_f32_cpu(float* params, float* gr
     R.nblocks = G;
     const float coef = pqn_clip_coef(s, R.max_norm);
     for (int64_t i = 0; i < n; ++i) pqn_radam_elem(params[i], grads[i], exp_avg[i], exp_avg_sq[i], coef, R, c);
+    return MI355PPO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ recurrent PQN (pqn_lstm.hip)
+// act: every FMA is the device's (lstm_dot128, the cell's products, pqn_lstm_q), expf / tanhf are libm's -- as for the scans, the
+// state and q agree with the device to the last bits, not bit for bit.  h_out / c_out of env b are bit-equal to
+// mi355ppo_lstm_seq_fwd_f32_cpu at T = 1.
+extern "C" MI355PPO_API int mi355ppo_pqn_lstm_act_f32_cpu(const float* gx, const float* w_hh, const float* h_in, const float* c_in,
+                                                         const float* done_in, const float* wq, const float* bq,
+                                                         const int64_t* random_actions, const float* u, double epsilon, float* h_out,
+                                                         float* c_out, float* q_out, float* actions_out, float* values_out,
+                                                         int64_t* action_i64_out, float* done_row_out, int N, int H, int A) {
+    const char* fn = "mi355ppo_pqn_lstm_act_f32_cpu";
+    MI355_REQUIRE(gx && w_hh && h_in && c_in && done_in && wq && bq, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(!h_out == !c_out, MI355PPO_EINVAL, "%s: h_out and c_out are both given or both NULL", fn);
+    MI355_REQUIRE(!actions_out == !values_out && (!actions_out || (random_actions && u)) && (actions_out || !action_i64_out),
+                  MI355PPO_EINVAL, "%s: actions_out, values_out, random_actions and u go together (all NULL: the bootstrap form)", fn);
+    MI355_REQUIRE(h_out || q_out || actions_out, MI355PPO_EINVAL, "%s: null pointer (no output)", fn);
+    MI355_REQUIRE(H == kLstmH, MI355PPO_EINVAL, "%s: H=%d (only %d)", fn, H, kLstmH);
+    MI355_REQUIRE(N > 0 && A > 0 && A <= kPqnMaxA, MI355PPO_EINVAL, "%s: N=%d A=%d: N must be positive, 1 <= A <= %d", fn, N, A, kPqnMaxA);
+    const float eps = (float)epsilon;
+    for (int b = 0; b < N; ++b) {
+        float hk[kLstmH], ck[kLstmH], a[kLstmG], hn[kLstmH], q[kPqnMaxA];
+        const float keep = 1.0f - done_in[b];
+        for (int k = 0; k < kLstmH; ++k) {
+            hk[k] = keep * h_in[(size_t)b * kLstmH + k];
+            ck[k] = keep * c_in[(size_t)b * kLstmH + k];
+        }
+        for (int j = 0; j < kLstmG; ++j) a[j] = gx[(size_t)b * kLstmG + j] + lstm_dot128(w_hh + (size_t)j * kLstmH, hk);
+        for (int k = 0; k < kLstmH; ++k) {
+            const LstmCell s = lstm_cell_fwd(a[k], a[kLstmH + k], a[2 * kLstmH + k], a[3 * kLstmH + k], ck[k]);
+            hn[k] = s.h;
+            if (h_out) {
+                h_out[(size_t)b * kLstmH + k] = s.h;
+                c_out[(size_t)b * kLstmH + k] = s.c;
+            }
+        }
+        for (int c = 0; c < A; ++c) {
+            q[c] = pqn_lstm_q(wq + (size_t)c * kLstmH, hn, bq[c]);
+            if (q_out) q_out[(size_t)b * A + c] = q[c];
+        }
+        if (actions_out) {
+            float v;
+            const int64_t act = pqn_egreedy(q, 1, A, random_actions[b], u[b], eps, &v);
+            actions_out[b] = (float)act;
+            values_out[b] = v;
+            if (action_i64_out) action_i64_out[b] = act;
+        }
+        if (done_row_out) done_row_out[b] = done_in[b];
+    }
+    return MI355PPO_OK;
+}
+
+// td: the device's row function, its kPqnRows-row partials and their fold, run serially: every output equals the device's bits.
+extern "C" MI355PPO_API int mi355ppo_pqn_lstm_td_fwd_bwd_f32_cpu(const float* h, const int64_t* mb_inds, const float* b_actions,
+                                                                const float* b_returns, const float* wq, const float* bq, float* dh,
+                                                                float* dwq, float* dbq, float* scalars_out, int M, int H, int A,
+                                                                int64_t B) {
+    const char* fn = "mi355ppo_pqn_lstm_td_fwd_bwd_f32_cpu";
+    MI355_REQUIRE(h && mb_inds && b_actions && b_returns && wq && bq && dh && dwq && dbq && scalars_out, MI355PPO_EINVAL,
+                  "%s: null pointer", fn);
+    MI355_REQUIRE(H == kLstmH, MI355PPO_EINVAL, "%s: H=%d (only %d)", fn, H, kLstmH);
+    MI355_REQUIRE(M > 0 && B > 0 && A > 0 && A <= kPqnMaxA, MI355PPO_EINVAL, "%s: M=%d B=%lld A=%d: M, B must be positive, 1 <= A <= %d",
+                  fn, M, (long long)B, A, kPqnMaxA);
+    const float norm = (float)(2.0 / (double)M);
+    std::vector<float> old(M), sq(M), g(M);
+    std::vector<int> act(M);
+    for (int r = 0; r < M; ++r) {
+        const int64_t i = pqn_clamp_index(mb_inds[r], B);
+        const PqnLstmTd t = pqn_lstm_td_row(h + (size_t)r * kLstmH, wq, bq, A, b_actions[i], b_returns[i], norm);
+        old[r] = t.old;
+        sq[r] = t.sq;
+        g[r] = t.g;
+        act[r] = t.a;
+        for (int k = 0; k < kLstmH; ++k) dh[(size_t)r * kLstmH + k] = t.g * wq[(size_t)t.a * kLstmH + k];
+    }
+    const int nblk = (M + kPqnRows - 1) / kPqnRows;
+    const int AH = A * kLstmH;
+    for (int e = 0; e < AH + A; ++e) {
+        float acc = 0.0f;
+        for (int b = 0; b < nblk; ++b) {
+            const int r0 = b * kPqnRows, r1 = (r0 + kPqnRows < M) ? r0 + kPqnRows : M;
+            const float part = e < AH ? pqn_lstm_grad_partial(e, h, g.data() + r0, act.data() + r0, r0, r1)
+                                      : pqn_lstm_bias_partial(e - AH, g.data() + r0, act.data() + r0, r1 - r0);
+            acc = acc + part;
+        }
+        if (e < AH)
+            dwq[e] = acc;
+        else
+            dbq[e - AH] = acc;
+    }
+    pqn_td_scalars_cpu(old, sq, M, scalars_out);
     return MI355PPO_OK;
 }

@@ -18,18 +18,11 @@
 namespace mi355ppo {
 namespace {
 
-constexpr int kThreads = 512;
-constexpr int kCus = 256;
-
-inline int lstm_envs_per_group(int B) {
-    for (int e = 1; e < 8; e *= 2)
-        if ((B + e - 1) / e <= kCus) return e;
-    return 8;
-}
+constexpr int kThreads = kLstmThreads;            // launch shape and the E rule: lstm_rows.h
 
 // Unit pairs (env e, unit u) owned by thread tid: p = tid + 512 r, e = p / 128, u = p % 128.
 template <int E>
-constexpr int kPairs = (E * kLstmH + kThreads - 1) / kThreads;
+constexpr int kPairs = kLstmPairs<E>;
 
 template <int E>
 __global__ __launch_bounds__(kThreads) void lstm_fwd_kernel(const float* __restrict__ gx, const float* __restrict__ w_hh,

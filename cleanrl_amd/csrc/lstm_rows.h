@@ -28,6 +28,21 @@ constexpr int kLstmRec = 7 * kLstmH;      // record floats per (t, b)
 
 inline size_t lstm_record_floats(int T, int B) { return (size_t)T * (size_t)B * kLstmRec; }
 
+// Launch shape of the scans and of the kernels that walk the same chain (pqn_lstm.hip): workgroups of kLstmThreads threads own
+// E envs each, E in {1, 2, 4, 8} the smallest that keeps ceil(B / E) workgroups within one per CU.  Thread tid owns the unit
+// pairs (env e, unit u) p = tid + kLstmThreads r, e = p / kLstmH, u = p % kLstmH, r < kLstmPairs<E>.
+constexpr int kLstmThreads = 512;
+constexpr int kLstmCus = 256;
+
+inline int lstm_envs_per_group(int B) {
+    for (int e = 1; e < 8; e *= 2)
+        if ((B + e - 1) / e <= kLstmCus) return e;
+    return 8;
+}
+
+template <int E>
+constexpr int kLstmPairs = (E * kLstmH + kLstmThreads - 1) / kLstmThreads;
+
 // sum_k w[k] v[k] over the 128 columns: four interleaved fused multiply-add chains, folded (s0 + s1) + (s2 + s3).  The
 // order is fixed, so a device thread (w in registers, v broadcast from LDS) and the host twin produce the same bits.
 template <class W, class V>

@@ -58,25 +58,6 @@ __global__ __launch_bounds__(64) void pqn_qlambda_kernel(const float* __restrict
     }
 }
 
-// Workgroup 0's part of the TD scalars: slot t = threadIdx.x adds rows t, t + 256, ... in f64; thread 0 adds the slots in order.
-__device__ void pqn_fold_scalars(double so, double ss, int M, float* __restrict__ scalars) {
-    __shared__ double s_old[kPqnFold], s_sq[kPqnFold];
-    s_old[threadIdx.x] = so;
-    s_sq[threadIdx.x] = ss;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double to = 0.0, ts = 0.0;
-        for (int t = 0; t < kPqnFold; ++t) {
-            to += s_old[t];
-            ts += s_sq[t];
-        }
-        scalars[0] = (float)(ts / (double)M);                        // losses/td_loss
-        scalars[1] = (float)(to / (double)M);                        // losses/q_values: old_val.mean()
-    }
-}
-
-__device__ __forceinline__ int64_t pqn_clamp_index(int64_t i, int64_t B) { return i < 0 ? 0 : (i >= B ? B - 1 : i); }
-
 __global__ __launch_bounds__(256) void pqn_td_loss_kernel(const float* __restrict__ q, const int64_t* __restrict__ inds,
                                                           const float* __restrict__ b_actions, const float* __restrict__ b_returns,
                                                           float* __restrict__ dq, float* __restrict__ scalars, int M, int A, int64_t B,

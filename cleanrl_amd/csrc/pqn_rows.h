@@ -213,6 +213,26 @@ MI355_HD float pqn_td_row(const float* q, int qs, int A, float action_f, float r
 // in f64, then the slots are added in order.  The device runs slot t on thread t of one workgroup; the twins run the same loops.
 constexpr int kPqnFold = 256;
 
+// Workgroup 0's part of the TD scalars (a workgroup of kPqnFold threads): slot t = threadIdx.x adds rows t, t + 256, ... in f64;
+// thread 0 adds the slots in order.
+__device__ inline void pqn_fold_scalars(double so, double ss, int M, float* __restrict__ scalars) {
+    __shared__ double s_old[kPqnFold], s_sq[kPqnFold];
+    s_old[threadIdx.x] = so;
+    s_sq[threadIdx.x] = ss;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double to = 0.0, ts = 0.0;
+        for (int t = 0; t < kPqnFold; ++t) {
+            to += s_old[t];
+            ts += s_sq[t];
+        }
+        scalars[0] = (float)(ts / (double)M);                        // losses/td_loss
+        scalars[1] = (float)(to / (double)M);                        // losses/q_values: old_val.mean()
+    }
+}
+
+MI355_HD int64_t pqn_clamp_index(int64_t i, int64_t B) { return i < 0 ? 0 : (i >= B ? B - 1 : i); }
+
 // Workgroups of the clip's sum-of-squares pass over n elements (each adds its kPqnFold slots in order into one partial).
 MI355_HD int pqn_sumsq_blocks(int64_t n) {
     const int64_t b = (n + 2047) / 2048;

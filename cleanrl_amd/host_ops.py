@@ -387,3 +387,41 @@ def clip_radam_(params, grads, exp_avg, exp_avg_sq, step, lr, max_grad_norm, bet
     _lib.call("mi355ppo_clip_radam_f32_cpu", *_flat4(params, grads, exp_avg, exp_avg_sq), params.numel(), float(max_grad_norm), float(lr),
               float(beta1), float(beta2), float(eps), int(step), _out(total, torch.float32, 1, "total_norm_out"))
     return total
+
+
+# ------------------------------------------------------------------------------------------- recurrent PQN twins (csrc/pqn_lstm.hip)
+def pqn_lstm_act(gx, w_hh, h_in, c_in, done_in, wq, bq, random_actions=None, u=None, epsilon=0.0, h_out=None, c_out=None, q_out=None,
+                 actions_out=None, values_out=None, action_i64_out=None, done_row_out=None):
+    """``mi355ppo_pqn_lstm_act_f32_cpu`` (see ops.pqn_lstm_act): writes the given outputs in place; ``h_out`` / ``c_out`` may be
+    ``h_in`` / ``c_in``."""
+    N, G = gx.shape
+    H, A = G // 4, wq.shape[0]
+    for t, nm in ((h_in, "h_in"), (c_in, "c_in")):          # possibly aliased by an output: taken as they are, never copied
+        if t.dtype != torch.float32 or tuple(t.shape) != (N, H):
+            raise ValueError(f"{nm}: expected f32 {(N, H)}, got {t.dtype} {tuple(t.shape)}")
+    g, w, d, q_w, q_b = _f32(gx), _f32(w_hh), _f32(done_in).reshape(-1), _f32(wq), _f32(bq)
+    if w.shape != (4 * H, H) or d.numel() != N or q_w.shape != (A, H) or q_b.numel() != A:
+        raise ValueError("pqn_lstm_act: w_hh (4H, H), done_in (N,), wq (A, H), bq (A,) expected")
+    rnd = None if random_actions is None else _i64(random_actions)
+    uu = None if u is None else _f32(u)
+    _lib.call("mi355ppo_pqn_lstm_act_f32_cpu", _p(g), _p(w), _p(h_in), _p(c_in), _p(d), _p(q_w), _p(q_b), _p(rnd), _p(uu), float(epsilon),
+              _out(h_out, torch.float32, N * H, "h_out"), _out(c_out, torch.float32, N * H, "c_out"),
+              _out(q_out, torch.float32, N * A, "q_out"), _out(actions_out, torch.float32, N, "actions_out"),
+              _out(values_out, torch.float32, N, "values_out"), _out(action_i64_out, torch.int64, N, "action_i64_out"),
+              _out(done_row_out, torch.float32, N, "done_row_out"), N, H, A)
+    return q_out
+
+
+def pqn_lstm_td_fwd_bwd(h, mb_inds, b_actions, b_returns, wq, bq, dwq, dbq, dh=None, scalars=None):
+    """``mi355ppo_pqn_lstm_td_fwd_bwd_f32_cpu`` (see ops.pqn_lstm_td_fwd_bwd): the device's bits."""
+    M, H = h.shape
+    A = wq.shape[0]
+    hh, inds, ba, br, q_w, q_b = _f32(h), _i64(mb_inds), _f32(b_actions).reshape(-1), _f32(b_returns).reshape(-1), _f32(wq), _f32(bq)
+    if inds.numel() != M or q_w.shape != (A, H) or q_b.numel() != A or br.numel() != ba.numel():
+        raise ValueError("pqn_lstm_td_fwd_bwd: mb_inds (M,), wq (A, H), bq (A,), b_actions / b_returns of one length expected")
+    dh = torch.empty((M, H)) if dh is None else dh
+    scalars = torch.empty(2) if scalars is None else scalars
+    _lib.call("mi355ppo_pqn_lstm_td_fwd_bwd_f32_cpu", _p(hh), _p(inds), _p(ba), _p(br), _p(q_w), _p(q_b), _out(dh, torch.float32, M * H, "dh"),
+              _out(dwq, torch.float32, A * H, "dwq"), _out(dbq, torch.float32, A, "dbq"), _out(scalars, torch.float32, 2, "scalars"), M, H, A,
+              ba.numel())
+    return dh, scalars

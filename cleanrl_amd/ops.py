@@ -26,7 +26,7 @@ __all__ = [
     "lstm_seq", "lstm_seq_dw_hh", "impala_forward", "impala_backward", "impala_maxpool_forward", "impala_maxpool_backward",
     "ImpalaTrunk", "impala_trunk", "impala_param_shapes", "trxl_attn_forward", "trxl_attn_backward", "TrXLMemoryAttention", "trxl_memory_attention",
     "pqn_param_count", "pqn_egreedy", "pqn_qlambda", "pqn_td_loss", "pqn_mlp_forward", "pqn_mlp_act", "pqn_mlp_td_fwd_bwd", "radam_schedule",
-    "clip_radam_", "clip_radam_sched_",
+    "clip_radam_", "clip_radam_sched_", "pqn_lstm_act", "pqn_lstm_td_fwd_bwd",
 ]
 
 LOSS_SCALAR_NAMES = ("loss", "pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac")
@@ -1228,3 +1228,57 @@ def clip_radam_sched_(params, grads, exp_avg, exp_avg_sq, sched8, max_grad_norm:
     _launch("mi355ppo_clip_radam_sched_f32", dev, _ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), n, float(max_grad_norm),
             float(beta1), float(beta2), float(eps), _ptr(sched8), _ptr(total_norm_out), _ptr(ws), ws.numel())
     return total_norm_out
+
+
+# ------------------------------------------------------------------------------------------- recurrent PQN (csrc/pqn_lstm.hip)
+def pqn_lstm_act(gx, w_hh, h_in, c_in, done_in, wq, bq, random_actions=None, u=None, epsilon: float = 0.0, h_out=None, c_out=None,
+                 q_out=None, actions_out=None, values_out=None, action_i64_out=None, done_row_out=None):
+    """The recurrent tail of one rollout step of pqn_atari_envpool_lstm.py in one launch: the done reset, ONE LSTM cell on ``gx``
+    (N, 4H) = x W_ih^T + b_ih + b_hh (bit-equal to ``lstm_seq_forward`` at T = 1), ``q_func`` and e-greedy into the step's storage
+    rows.  ``h_out`` / ``c_out`` (N, H) may be ``h_in`` / ``c_in``.  Every output is optional: with only ``q_out`` it is the
+    bootstrap's ``q_network(next_obs, ...)``.  Returns ``q_out``."""
+    N, G = gx.shape
+    H = G // 4
+    A = wq.shape[0]
+    _chk(gx, torch.float32, "gx", (N, 4 * H))
+    _chk(w_hh, torch.float32, "w_hh", (4 * H, H))
+    _chk(h_in, torch.float32, "h_in", (N, H))
+    _chk(c_in, torch.float32, "c_in", (N, H))
+    _chk(done_in, torch.float32, "done_in", (N,))
+    _chk(wq, torch.float32, "wq", (A, H))
+    _chk(bq, torch.float32, "bq", (A,))
+    for t, dt, nm, shape in ((random_actions, torch.int64, "random_actions", (N,)), (u, torch.float32, "u", (N,)),
+                             (h_out, torch.float32, "h_out", (N, H)), (c_out, torch.float32, "c_out", (N, H)),
+                             (q_out, torch.float32, "q_out", (N, A)), (actions_out, torch.float32, "actions_out", (N,)),
+                             (values_out, torch.float32, "values_out", (N,)), (action_i64_out, torch.int64, "action_i64_out", (N,)),
+                             (done_row_out, torch.float32, "done_row_out", (N,))):
+        if t is not None:
+            _chk(t, dt, nm, shape)
+    _launch("mi355ppo_pqn_lstm_act_f32", gx.device, _ptr(gx), _ptr(w_hh), _ptr(h_in), _ptr(c_in), _ptr(done_in), _ptr(wq), _ptr(bq),
+            _ptr(random_actions), _ptr(u), float(epsilon), _ptr(h_out), _ptr(c_out), _ptr(q_out), _ptr(actions_out), _ptr(values_out),
+            _ptr(action_i64_out), _ptr(done_row_out), N, H, A)
+    return q_out
+
+
+def pqn_lstm_td_fwd_bwd(h, mb_inds, b_actions, b_returns, wq, bq, dwq, dbq, dh=None, scalars=None):
+    """``q_func(h).gather(1, b_actions[mb_inds].long())`` + ``F.mse_loss(b_returns[mb_inds], old_val)`` of one minibatch, forward and
+    backward: ``h`` (M, H) are the scan's rows in minibatch order.  OVERWRITES ``dwq`` (A, H) / ``dbq`` (A) (views of the flat
+    gradient) and returns ``(dh (M, H), scalars (2,) = {td_loss, mean(old_val)})``."""
+    M, H = h.shape
+    A = wq.shape[0]
+    _chk(h, torch.float32, "h")
+    _chk(mb_inds, torch.int64, "mb_inds", (M,))
+    B = b_actions.numel()
+    b_actions = _chk(b_actions.reshape(-1), torch.float32, "b_actions", (B,))
+    b_returns = _chk(b_returns.reshape(-1), torch.float32, "b_returns", (B,))
+    _chk(wq, torch.float32, "wq", (A, H))
+    _chk(bq, torch.float32, "bq", (A,))
+    _chk(dwq, torch.float32, "dwq", (A, H))
+    _chk(dbq, torch.float32, "dbq", (A,))
+    dev = h.device
+    dh = torch.empty_like(h) if dh is None else _chk(dh, torch.float32, "dh", (M, H))
+    scalars = torch.empty(2, dtype=torch.float32, device=dev) if scalars is None else _chk(scalars, torch.float32, "scalars", (2,))
+    ws = _workspace(dev, _lib.load().mi355ppo_pqn_lstm_td_workspace_bytes(M, A))
+    _launch("mi355ppo_pqn_lstm_td_fwd_bwd_f32", dev, _ptr(h), _ptr(mb_inds), _ptr(b_actions), _ptr(b_returns), _ptr(wq), _ptr(bq), _ptr(dh),
+            _ptr(dwq), _ptr(dbq), _ptr(scalars), M, H, A, B, _ptr(ws), ws.numel())
+    return dh, scalars

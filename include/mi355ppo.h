@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MI355PPO_VERSION 250 /* major*100 + minor*10 + patch.  The minor moves whenever an exported signature changes or an entry
+#define MI355PPO_VERSION 260 /* major*100 + minor*10 + patch.  The minor moves whenever an exported signature changes or an entry
                                   point is added (1.1: adv_mean_den / conv1_variant arguments of round 2; 1.2, 1.3: round 3;
                                   1.4: the *_cpu host-pointer twins; 1.5: mi355ppo_init; 1.6: round 4 -- the fused MLP family K7,
                                   mi355ppo_clip_adam_sched_f32; 1.7: mi355ppo_fc_heads_act_categorical_f32, mi355ppo_nature_packs_f32,
@@ -42,7 +42,8 @@ extern "C" {
                                   2.2: the done-masked LSTM sequence scans mi355ppo_lstm_seq_fwd_f32 / _bwd_f32 and their *_cpu twins;
                                   2.3: the TrXL episodic-memory attention mi355ppo_trxl_attn_fwd_f32 / _bwd_f32 and their *_cpu twins;
                                   2.4: the IMPALA-CNN trunk mi355ppo_impala_* (forward, backward, max pool, sizes) and the *_cpu twins;
-                                  2.5: PQN -- mi355ppo_pqn_* (e-greedy, Q(lambda), TD loss, the LayerNorm MLP), clip + RAdam, the *_cpu twins);
+                                  2.5: PQN -- mi355ppo_pqn_* (e-greedy, Q(lambda), TD loss, the LayerNorm MLP), clip + RAdam, the *_cpu twins;
+                                  2.6: the recurrent PQN tail mi355ppo_pqn_lstm_act_f32, mi355ppo_pqn_lstm_td_fwd_bwd_f32 (+ workspace size) and their *_cpu twins);
                                   a binding must check major AND minor (cleanrl_amd/_lib.py does) */
 
 #if defined(__GNUC__)
@@ -890,6 +891,42 @@ MI355PPO_API int mi355ppo_clip_radam_sched_f32(float* params, float* grads, floa
                                                void* workspace, size_t workspace_bytes, void* stream);
 MI355PPO_API int mi355ppo_clip_radam_f32_cpu(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, double max_grad_norm,
                                              double lr, double beta1, double beta2, double eps, int64_t step, float* total_norm_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * The recurrent PQN tail (cleanrl/pqn_atari_envpool_lstm.py; csrc/pqn_lstm.hip, row math in csrc/pqn_lstm_rows.h).  All f32,
+ * row-major; H must be 128 and 1 <= A <= 18, else MI355PPO_EINVAL.  No entry point allocates or synchronises (all are capturable).
+ *
+ * act -- one rollout step after the gx GEMM, in one launch.  gx (N, 4H) = x W_ih^T + b_ih + b_hh, w_hh (4H, H), h_in / c_in (N, H),
+ * done_in (N), wq (A, H), bq (A).  keep = 1 - done_in; one LSTM cell on (keep h_in, keep c_in): h_out / c_out (N, H) are bit-equal to
+ * mi355ppo_lstm_seq_fwd_f32 at T = 1 on the same device, and may alias h_in / c_in.  q[n, a] = dot(wq[a, :], h_out[n, :]) + bq[a]
+ * (four interleaved fmaf chains over k, folded (s0 + s1) + (s2 + s3), then the bias).  Then e-greedy on q exactly as
+ * mi355ppo_pqn_egreedy_f32 (first maximum wins, a NaN is the maximum, u < (float)epsilon) into actions_out / values_out (the step's
+ * storage rows) and, when non-NULL, action_i64_out; done_row_out[n] = done_in[n] when non-NULL.  q_out (N, A) is written when
+ * non-NULL.  h_out and c_out are both given or both NULL (NULL: the state is discarded); actions_out, values_out, random_actions
+ * and u go together.  The bootstrap form q(next_obs) passes only q_out.  The *_cpu twin shares every FMA with the device; expf /
+ * tanhf come from libm, so it agrees to the last bits, not bit for bit. */
+MI355PPO_API int mi355ppo_pqn_lstm_act_f32(const float* gx, const float* w_hh, const float* h_in, const float* c_in, const float* done_in,
+                                           const float* wq, const float* bq, const int64_t* random_actions, const float* u, double epsilon,
+                                           float* h_out, float* c_out, float* q_out, float* actions_out, float* values_out,
+                                           int64_t* action_i64_out, float* done_row_out, int N, int H, int A, void* stream);
+MI355PPO_API int mi355ppo_pqn_lstm_act_f32_cpu(const float* gx, const float* w_hh, const float* h_in, const float* c_in, const float* done_in,
+                                               const float* wq, const float* bq, const int64_t* random_actions, const float* u,
+                                               double epsilon, float* h_out, float* c_out, float* q_out, float* actions_out,
+                                               float* values_out, int64_t* action_i64_out, float* done_row_out, int N, int H, int A);
+/* td -- q_func + gather + F.mse_loss of one minibatch, forward and backward.  h (M, H): the scan's output rows in minibatch order;
+ * i = mb_inds[r] indexes b_actions / b_returns (B rows; an index or action out of range is clamped).  a = (long)b_actions[i],
+ * old[r] = dot(wq[a, :], h[r, :]) + bq[a] (the act kernel's q), loss = mean((ret - old)^2), g_r = -((float)(2 / M) * (ret - old)).
+ * dh (M, H): dh[r, :] = g_r wq[a, :]; dwq (A, H) and dbq (A) are OVERWRITTEN with sum over the rows of that action of g_r h[r, :]
+ * and g_r (rows in ascending order within workgroups of 256 rows, then the workgroups in order; an action that never occurs gets
+ * exact zeros); scalars_out = {loss, mean(old)}, summed in f64 in a fixed order.  Two launches.  The *_cpu twin returns the
+ * device's bits. */
+MI355PPO_API size_t mi355ppo_pqn_lstm_td_workspace_bytes(int M, int A);
+MI355PPO_API int mi355ppo_pqn_lstm_td_fwd_bwd_f32(const float* h, const int64_t* mb_inds, const float* b_actions, const float* b_returns,
+                                                  const float* wq, const float* bq, float* dh, float* dwq, float* dbq, float* scalars_out,
+                                                  int M, int H, int A, int64_t B, void* workspace, size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_pqn_lstm_td_fwd_bwd_f32_cpu(const float* h, const int64_t* mb_inds, const float* b_actions, const float* b_returns,
+                                                      const float* wq, const float* bq, float* dh, float* dwq, float* dbq,
+                                                      float* scalars_out, int M, int H, int A, int64_t B);
 
 #ifdef __cplusplus
 }
