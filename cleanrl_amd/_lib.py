@@ -195,9 +195,24 @@ SIGNATURES = {
     "mi355ppo_pqn_lstm_td_workspace_bytes": (c_size_t, [c_int, c_int]),
     "mi355ppo_pqn_lstm_td_fwd_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int64, _P, c_size_t, _P]),
     "mi355ppo_pqn_lstm_td_fwd_bwd_f32_cpu": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int64]),
+    # DDPG / TD3 (ABI 2.7, csrc/offpolicy.hip)
+    "mi355ppo_replay_add_f32": (c_int, [_P] * 10 + [c_int64, c_int64, c_int, c_int, c_int, _P]),
+    "mi355ppo_replay_add_f32_cpu": (c_int, [_P] * 10 + [c_int64, c_int64, c_int, c_int, c_int]),
+    "mi355ppo_ddpg_act_f32": (c_int, [_P] * 8 + [c_int, c_int, c_int, _P]),
+    "mi355ppo_ddpg_act_f32_cpu": (c_int, [_P] * 8 + [c_int, c_int, c_int]),
+    "mi355ppo_td3_target_f32": (c_int, [_P] * 5 + [c_int64, c_int, _P, _P, c_int, _P, _P, _P] + [c_double] * 5 + [_P, _P, c_int, c_int, c_int, _P]),
+    "mi355ppo_td3_target_f32_cpu": (c_int, [_P] * 5 + [c_int64, c_int, _P, _P, c_int, _P, _P, _P] + [c_double] * 5 + [_P, _P, c_int, c_int, c_int]),
+    "mi355ppo_td3_critic_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "mi355ppo_td3_critic_fwd_bwd_f32": (c_int, [_P] * 4 + [c_int64, c_int, _P, c_int, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "mi355ppo_td3_critic_fwd_bwd_f32_cpu": (c_int, [_P] * 4 + [c_int64, c_int, _P, c_int, _P, _P, _P, c_int, c_int, c_int]),
+    "mi355ppo_td3_actor_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mi355ppo_td3_actor_fwd_bwd_f32": (c_int, [_P] * 3 + [c_int64, c_int] + [_P] * 7 + [c_int, c_int, c_int, _P, c_size_t, _P]),
+    "mi355ppo_td3_actor_fwd_bwd_f32_cpu": (c_int, [_P] * 3 + [c_int64, c_int] + [_P] * 7 + [c_int, c_int, c_int]),
+    "mi355ppo_polyak_f32": (c_int, [_P, _P, c_int64, c_double, _P]),
+    "mi355ppo_polyak_f32_cpu": (c_int, [_P, _P, c_int64, c_double]),
 }
 
-ABI_VERSION = 260       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)
+ABI_VERSION = 270       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)
 
 _lib = None
 

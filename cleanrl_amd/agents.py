@@ -1180,3 +1180,43 @@ class AtariLSTMQNetwork(nn.Module):
         gx = self.gates(x).reshape(-1, batch_size, 4 * H)
         h, hT, cT = ops.lstm_seq(gx, self.lstm.weight_hh_l0, lstm_state[0][0], lstm_state[1][0], done.reshape(-1, batch_size))
         return h.reshape(-1, H), (hT.unsqueeze(0), cT.unsqueeze(0))
+
+
+# ------------------------------------------------------------------------------------------- DDPG / TD3 (ddpg_continuous_action.py, td3_continuous_action.py)
+class ActionValueNetwork(nn.Module):
+    """The two scripts' ``QNetwork`` (named apart from the PQN ``QNetwork`` above): Linear(obs + act, 256) -> ReLU -> Linear(256, 256)
+    -> ReLU -> Linear(256, 1) on ``cat([x, a], 1)``, torch's default initialisation in the reference's construction order, so a seed
+    gives the reference's weights."""
+
+    def __init__(self, env):
+        super().__init__()
+        self.fc1 = nn.Linear(np.array(env.single_observation_space.shape).prod() + np.prod(env.single_action_space.shape), 256)
+        self.fc2 = nn.Linear(256, 256)
+        self.fc3 = nn.Linear(256, 1)
+
+    def forward(self, x, a):
+        x = torch.cat([x, a], 1)
+        x = torch.relu(self.fc1(x))
+        x = torch.relu(self.fc2(x))
+        return self.fc3(x)
+
+
+class Actor(nn.Module):
+    """The two scripts' ``Actor``: Linear(obs, 256) -> ReLU -> Linear(256, 256) -> ReLU -> Linear(256, act) -> tanh, rescaled by the
+    ``action_scale`` / ``action_bias`` buffers.  ``batched_space``: ddpg_continuous_action.py forms the buffers from the vector
+    env's batched ``action_space`` (shape (1, act)), td3_continuous_action.py from ``single_action_space`` (shape (act,))."""
+
+    def __init__(self, env, batched_space: bool = False):
+        super().__init__()
+        self.fc1 = nn.Linear(np.array(env.single_observation_space.shape).prod(), 256)
+        self.fc2 = nn.Linear(256, 256)
+        self.fc_mu = nn.Linear(256, np.prod(env.single_action_space.shape))
+        space = env.action_space if batched_space else env.single_action_space
+        self.register_buffer("action_scale", torch.tensor((space.high - space.low) / 2.0, dtype=torch.float32))
+        self.register_buffer("action_bias", torch.tensor((space.high + space.low) / 2.0, dtype=torch.float32))
+
+    def forward(self, x):
+        x = torch.relu(self.fc1(x))
+        x = torch.relu(self.fc2(x))
+        x = torch.tanh(self.fc_mu(x))
+        return x * self.action_scale + self.action_bias

@@ -20,6 +20,7 @@
 #include "impala_rows.h"
 #include "pqn_rows.h"
 #include "pqn_lstm_rows.h"
+#include "offpolicy_rows.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -1296,5 +1297,298 @@ extern "C" MI355PPO_API int mi355ppo_pqn_lstm_td_fwd_bwd_f32_cpu(const float* h,
             dbq[e - AH] = acc;
     }
     pqn_td_scalars_cpu(old, sq, M, scalars_out);
+    return MI355PPO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ DDPG / TD3 (offpolicy.hip)
+// The device's element functions (offpolicy_rows.h) in the device's orders: dot products ascending from 0.0f, weight gradients per
+// tile of kOpRows rows, tiles into their group's partial, groups ascending into the flat gradient, f64 slot folds for the scalars.
+// Every output equals the device's bit for bit (op_tanh uses no libm function).
+namespace {
+
+constexpr int kOpXSh = kOpMaxObs + kOpMaxAct;
+
+template <bool RELU>
+void op_fwd_host(const float* xin, int xs, int K, const float* W, const float* b, float* out, int os) {
+    for (int j = 0; j < kOpH; ++j)
+        for (int r = 0; r < kOpRows; ++r) {
+            float acc = 0.0f;
+            for (int k = 0; k < K; ++k) acc = op_mac(acc, xin[r * xs + k], W[(int64_t)j * K + k]);
+            const float v = acc + b[j];
+            out[r * os + j] = RELU ? op_relu(v) : v;
+        }
+}
+
+void op_head_host(const float* h, int hs, const float* W, const float* b, int J, float* out) {
+    for (int r = 0; r < kOpRows; ++r)
+        for (int j = 0; j < J; ++j) {
+            float acc = 0.0f;
+            for (int k = 0; k < kOpH; ++k) acc = op_mac(acc, h[r * hs + k], W[j * kOpH + k]);
+            out[r * J + j] = acc + b[j];
+        }
+}
+
+void op_dgrad_host(const float* dz, int ds, int J, const float* W, int ldw, float* io, int ios) {
+    for (int k = 0; k < kOpH; ++k)
+        for (int r = 0; r < kOpRows; ++r) {
+            float acc = 0.0f;
+            for (int j = 0; j < J; ++j) acc = op_mac(acc, dz[r * ds + j], W[(int64_t)j * ldw + k]);
+            io[r * ios + k] = op_relu_bwd(io[r * ios + k], acc);
+        }
+}
+
+void op_wgrad_host(const float* dz, int ds, const float* in, int is, int J, int K, float* part_w, float* part_b, bool first, int nr) {
+    for (int j = 0; j < J; ++j) {
+        for (int k = 0; k < K; ++k) {
+            float acc = 0.0f;
+            for (int r = 0; r < nr; ++r) acc = op_mac(acc, dz[r * ds + j], in[r * is + k]);
+            float& p = part_w[(int64_t)j * K + k];
+            p = first ? acc : p + acc;
+        }
+        float acc = 0.0f;
+        for (int r = 0; r < nr; ++r) acc = acc + dz[r * ds + j];
+        part_b[j] = first ? acc : part_b[j] + acc;
+    }
+}
+
+float op_fold_mean_host(const float* v, int M) {
+    double tot = 0.0;
+    for (int t = 0; t < kOpFold; ++t) {
+        double s = 0.0;
+        for (int k = t; k < M; k += kOpFold) s += (double)v[k];
+        tot += s;
+    }
+    return (float)(tot / (double)M);
+}
+
+void op_fold_host(const float* part, int G, int64_t P, float* grads) {
+    for (int64_t e = 0; e < P; ++e) {
+        float acc = 0.0f;
+        for (int b = 0; b < G; ++b) acc = acc + part[(int64_t)b * P + e];
+        grads[e] = acc;
+    }
+}
+
+struct OpTile {
+    std::vector<float> x, a1, a2, c1, c2;
+    float mu[kOpRows * kOpMaxAct], tv[kOpRows * kOpMaxAct], qv[2 * kOpRows], dq[kOpRows];
+    OpTile() : x(kOpRows * kOpXSh), a1(kOpRows * kOpH), a2(kOpRows * kOpH), c1(kOpRows * kOpH), c2(kOpRows * kOpH) {}
+};
+
+void op_actor_host(const OpNet& an, const float* scale, const float* bias, OpTile& T) {
+    op_fwd_host<true>(T.x.data(), kOpXSh, an.K, an.w1, an.b1, T.a1.data(), kOpH);
+    op_fwd_host<true>(T.a1.data(), kOpH, kOpH, an.w2, an.b2, T.a2.data(), kOpH);
+    op_head_host(T.a2.data(), kOpH, an.w3, an.b3, an.J, T.mu);
+    for (int r = 0; r < kOpRows; ++r)
+        for (int a = 0; a < an.J; ++a) {
+            const float th = op_tanh(T.mu[r * an.J + a]);
+            T.tv[r * an.J + a] = th;
+            T.x[r * kOpXSh + an.K + a] = op_action(th, scale[a], bias[a]);
+        }
+}
+
+int op_shape_cpu(const char* fn, int M, int O, int A) {
+    MI355_REQUIRE(M > 0 && O > 0 && O <= kOpMaxObs && A > 0 && A <= kOpMaxAct, MI355PPO_EINVAL,
+                  "%s: rows=%d obs_dim=%d act_dim=%d: the off-policy networks take 1 <= obs_dim <= %d, 1 <= act_dim <= %d", fn, M, O, A,
+                  kOpMaxObs, kOpMaxAct);
+    return MI355PPO_OK;
+}
+
+inline int64_t op_row_cpu(const int64_t* bi, const int64_t* ei, int m, int64_t slots, int N) {
+    return op_clamp(bi[m], slots) * N + op_clamp(ei[m], N);
+}
+
+}  // namespace
+
+extern "C" MI355PPO_API int mi355ppo_replay_add_f32_cpu(const float* obs, const float* next_obs, const float* actions, const float* rewards,
+                                                       const float* dones, float* ring_obs, float* ring_next_obs, float* ring_actions,
+                                                       float* ring_rewards, float* ring_dones, int64_t pos, int64_t slots, int N, int O, int A) {
+    const char* fn = "mi355ppo_replay_add_f32_cpu";
+    MI355_REQUIRE(obs && next_obs && actions && rewards && dones && ring_obs && ring_next_obs && ring_actions && ring_rewards && ring_dones,
+                  MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(N > 0 && O > 0 && A > 0 && slots > 0 && pos >= 0 && pos < slots, MI355PPO_EINVAL,
+                  "%s: N=%d O=%d A=%d slots=%lld pos=%lld: sizes must be positive and 0 <= pos < slots", fn, N, O, A, (long long)slots,
+                  (long long)pos);
+    const size_t no = (size_t)N * O, na = (size_t)N * A;
+    memcpy(ring_obs + pos * no, obs, no * sizeof(float));
+    memcpy(ring_next_obs + pos * no, next_obs, no * sizeof(float));
+    memcpy(ring_actions + pos * na, actions, na * sizeof(float));
+    memcpy(ring_rewards + pos * N, rewards, (size_t)N * sizeof(float));
+    memcpy(ring_dones + pos * N, dones, (size_t)N * sizeof(float));
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_ddpg_act_f32_cpu(const float* obs, const float* actor_params, const float* action_scale,
+                                                     const float* action_bias, const float* noise_row, const float* low, const float* high,
+                                                     float* actions_out, int N, int O, int A) {
+    const char* fn = "mi355ppo_ddpg_act_f32_cpu";
+    MI355_REQUIRE(obs && actor_params && action_scale && action_bias && low && high && actions_out, MI355PPO_EINVAL, "%s: null pointer", fn);
+    if (int rc = op_shape_cpu(fn, N, O, A)) return rc;
+    const OpNet an = op_net(actor_params, O, A);
+    OpTile T;
+    for (int r0 = 0; r0 < N; r0 += kOpRows) {
+        for (int r = 0; r < kOpRows; ++r)
+            for (int k = 0; k < O; ++k) T.x[r * kOpXSh + k] = (r0 + r < N) ? obs[(int64_t)(r0 + r) * O + k] : 0.0f;
+        op_actor_host(an, action_scale, action_bias, T);
+        for (int r = 0; r < kOpRows && r0 + r < N; ++r)
+            for (int a = 0; a < A; ++a)
+                actions_out[(int64_t)(r0 + r) * A + a] = op_explore(T.x[r * kOpXSh + O + a], noise_row ? noise_row[a] : 0.0f, low[a], high[a]);
+    }
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_td3_target_f32_cpu(const float* ring_next_obs, const float* ring_rewards, const float* ring_dones,
+                                                       const int64_t* batch_inds, const int64_t* env_inds, int64_t slots, int n_envs,
+                                                       const float* target_actor, const float* target_critics, int n_critics,
+                                                       const float* action_scale, const float* action_bias, const float* noise,
+                                                       double policy_noise, double noise_clip, double low0, double high0, double gamma,
+                                                       float* next_q_value, float* next_actions_out, int M, int O, int A) {
+    const char* fn = "mi355ppo_td3_target_f32_cpu";
+    MI355_REQUIRE(ring_next_obs && ring_rewards && ring_dones && target_actor && target_critics && action_scale && action_bias && next_q_value &&
+                      batch_inds && env_inds,
+                  MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE((n_critics == 1 || n_critics == 2) && slots > 0 && n_envs > 0, MI355PPO_EINVAL,
+                  "%s: n_critics=%d must be 1 or 2, slots=%lld and n_envs=%d positive", fn, n_critics, (long long)slots, n_envs);
+    if (int rc = op_shape_cpu(fn, M, O, A)) return rc;
+    const OpNet an = op_net(target_actor, O, A);
+    const int64_t Pq = op_critic_count(O, A);
+    const float pn = (float)policy_noise, nc = (float)noise_clip, lo0 = (float)low0, hi0 = (float)high0, g = (float)gamma;
+    OpTile T;
+    for (int r0 = 0; r0 < M; r0 += kOpRows) {
+        for (int r = 0; r < kOpRows; ++r)
+            for (int k = 0; k < O; ++k)
+                T.x[r * kOpXSh + k] = (r0 + r < M) ? ring_next_obs[op_row_cpu(batch_inds, env_inds, r0 + r, slots, n_envs) * O + k] : 0.0f;
+        op_actor_host(an, action_scale, action_bias, T);
+        for (int r = 0; r < kOpRows && r0 + r < M; ++r)
+            for (int a = 0; a < A; ++a) {
+                float& v = T.x[r * kOpXSh + O + a];
+                if (noise) v = op_smooth(v, noise[(int64_t)(r0 + r) * A + a], pn, nc, action_scale[a], lo0, hi0);
+                if (next_actions_out) next_actions_out[(int64_t)(r0 + r) * A + a] = v;
+            }
+        for (int c = 0; c < n_critics; ++c) {
+            const OpNet qn = op_net(target_critics + c * Pq, O + A, 1);
+            op_fwd_host<true>(T.x.data(), kOpXSh, O + A, qn.w1, qn.b1, T.a1.data(), kOpH);
+            op_fwd_host<true>(T.a1.data(), kOpH, kOpH, qn.w2, qn.b2, T.a2.data(), kOpH);
+            op_head_host(T.a2.data(), kOpH, qn.w3, qn.b3, 1, T.qv + c * kOpRows);
+        }
+        for (int r = 0; r < kOpRows && r0 + r < M; ++r) {
+            const int64_t row = op_row_cpu(batch_inds, env_inds, r0 + r, slots, n_envs);
+            const float q = (n_critics == 2) ? op_min(T.qv[r], T.qv[kOpRows + r]) : T.qv[r];
+            next_q_value[r0 + r] = op_td_target(ring_rewards[row], ring_dones[row], g, q);
+        }
+    }
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_td3_critic_fwd_bwd_f32_cpu(const float* ring_obs, const float* ring_actions, const int64_t* batch_inds,
+                                                               const int64_t* env_inds, int64_t slots, int n_envs, const float* critics,
+                                                               int n_critics, const float* next_q_value, float* grads, float* scalars_out, int M,
+                                                               int O, int A) {
+    const char* fn = "mi355ppo_td3_critic_fwd_bwd_f32_cpu";
+    MI355_REQUIRE(ring_obs && ring_actions && critics && next_q_value && grads && scalars_out && batch_inds && env_inds, MI355PPO_EINVAL,
+                  "%s: null pointer", fn);
+    MI355_REQUIRE((n_critics == 1 || n_critics == 2) && slots > 0 && n_envs > 0, MI355PPO_EINVAL,
+                  "%s: n_critics=%d must be 1 or 2, slots=%lld and n_envs=%d positive", fn, n_critics, (long long)slots, n_envs);
+    if (int rc = op_shape_cpu(fn, M, O, A)) return rc;
+    const int K = O + A, G = op_groups(M), ntiles = op_tiles(M);
+    const int64_t Pq = op_critic_count(O, A), P = n_critics * Pq;
+    const OpOff off = op_off(K, 1);
+    const float norm = (float)(2.0 / (double)M);
+    std::vector<float> part((size_t)G * P), rows((size_t)4 * M);
+    OpTile T;
+    for (int c = 0; c < n_critics; ++c) {
+        const OpNet qn = op_net(critics + c * Pq, K, 1);
+        for (int tl = 0; tl < ntiles; ++tl) {
+            const int g = tl % G, r0 = tl * kOpRows, nr = (M - r0 < kOpRows) ? M - r0 : kOpRows;
+            const bool first = tl == g;
+            float* p = part.data() + ((int64_t)g * n_critics + c) * Pq;
+            for (int r = 0; r < kOpRows; ++r) {
+                const int64_t row = r < nr ? op_row_cpu(batch_inds, env_inds, r0 + r, slots, n_envs) : 0;
+                for (int k = 0; k < K; ++k)
+                    T.x[r * kOpXSh + k] = r < nr ? (k < O ? ring_obs[row * O + k] : ring_actions[row * A + (k - O)]) : 0.0f;
+            }
+            op_fwd_host<true>(T.x.data(), kOpXSh, K, qn.w1, qn.b1, T.a1.data(), kOpH);
+            op_fwd_host<true>(T.a1.data(), kOpH, kOpH, qn.w2, qn.b2, T.a2.data(), kOpH);
+            op_head_host(T.a2.data(), kOpH, qn.w3, qn.b3, 1, T.qv);
+            for (int r = 0; r < kOpRows; ++r) {
+                float d = 0.0f;
+                if (r < nr) {
+                    float sq;
+                    d = op_mse_row(T.qv[r], next_q_value[r0 + r], norm, &sq);
+                    rows[(size_t)(2 * c) * M + r0 + r] = T.qv[r];
+                    rows[(size_t)(2 * c + 1) * M + r0 + r] = sq;
+                }
+                T.dq[r] = d;
+            }
+            op_wgrad_host(T.dq, 1, T.a2.data(), kOpH, 1, kOpH, p + off.w3, p + off.b3, first, nr);
+            op_dgrad_host(T.dq, 1, 1, qn.w3, kOpH, T.a2.data(), kOpH);
+            op_wgrad_host(T.a2.data(), kOpH, T.a1.data(), kOpH, kOpH, kOpH, p + off.w2, p + off.b2, first, nr);
+            op_dgrad_host(T.a2.data(), kOpH, kOpH, qn.w2, kOpH, T.a1.data(), kOpH);
+            op_wgrad_host(T.a1.data(), kOpH, T.x.data(), kOpXSh, kOpH, K, p + off.w1, p + off.b1, first, nr);
+        }
+    }
+    op_fold_host(part.data(), G, P, grads);
+    for (int s = 0; s < 2 * n_critics; ++s) scalars_out[s] = 1.0f * op_fold_mean_host(rows.data() + (size_t)s * M, M);
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_td3_actor_fwd_bwd_f32_cpu(const float* ring_obs, const int64_t* batch_inds, const int64_t* env_inds,
+                                                              int64_t slots, int n_envs, const float* actor, const float* qf1,
+                                                              const float* action_scale, const float* action_bias, float* grads,
+                                                              float* actor_loss_out, float* dq_daction_out, int M, int O, int A) {
+    const char* fn = "mi355ppo_td3_actor_fwd_bwd_f32_cpu";
+    MI355_REQUIRE(ring_obs && actor && qf1 && action_scale && action_bias && grads && actor_loss_out && batch_inds && env_inds, MI355PPO_EINVAL,
+                  "%s: null pointer", fn);
+    MI355_REQUIRE(slots > 0 && n_envs > 0, MI355PPO_EINVAL, "%s: slots=%lld n_envs=%d must be positive", fn, (long long)slots, n_envs);
+    if (int rc = op_shape_cpu(fn, M, O, A)) return rc;
+    const int K = O + A, G = op_groups(M), ntiles = op_tiles(M);
+    const int64_t Pa = op_actor_count(O, A);
+    const OpNet an = op_net(actor, O, A), qn = op_net(qf1, K, 1);
+    const OpOff off = op_off(O, A);
+    const float dqv = (float)(-1.0 / (double)M);
+    std::vector<float> part((size_t)G * Pa), rows(M);
+    OpTile T;
+    for (int tl = 0; tl < ntiles; ++tl) {
+        const int g = tl % G, r0 = tl * kOpRows, nr = (M - r0 < kOpRows) ? M - r0 : kOpRows;
+        const bool first = tl == g;
+        float* p = part.data() + (int64_t)g * Pa;
+        for (int r = 0; r < kOpRows; ++r) {
+            const int64_t row = r < nr ? op_row_cpu(batch_inds, env_inds, r0 + r, slots, n_envs) : 0;
+            for (int k = 0; k < O; ++k) T.x[r * kOpXSh + k] = r < nr ? ring_obs[row * O + k] : 0.0f;
+        }
+        op_actor_host(an, action_scale, action_bias, T);
+        op_fwd_host<true>(T.x.data(), kOpXSh, K, qn.w1, qn.b1, T.c1.data(), kOpH);
+        op_fwd_host<true>(T.c1.data(), kOpH, kOpH, qn.w2, qn.b2, T.c2.data(), kOpH);
+        op_head_host(T.c2.data(), kOpH, qn.w3, qn.b3, 1, T.qv);
+        for (int r = 0; r < kOpRows; ++r) {
+            if (r < nr) rows[r0 + r] = T.qv[r];
+            T.dq[r] = r < nr ? dqv : 0.0f;
+        }
+        op_dgrad_host(T.dq, 1, 1, qn.w3, kOpH, T.c2.data(), kOpH);
+        op_dgrad_host(T.c2.data(), kOpH, kOpH, qn.w2, kOpH, T.c1.data(), kOpH);
+        for (int r = 0; r < kOpRows; ++r)
+            for (int a = 0; a < A; ++a) {
+                float acc = 0.0f;
+                for (int j = 0; j < kOpH; ++j) acc = op_mac(acc, T.c1[r * kOpH + j], qn.w1[(int64_t)j * K + O + a]);
+                if (dq_daction_out && r < nr) dq_daction_out[(int64_t)(r0 + r) * A + a] = acc;
+                T.mu[r * A + a] = op_dmu(acc, action_scale[a], T.tv[r * A + a]);
+            }
+        op_wgrad_host(T.mu, A, T.a2.data(), kOpH, A, kOpH, p + off.w3, p + off.b3, first, nr);
+        op_dgrad_host(T.mu, A, A, an.w3, kOpH, T.a2.data(), kOpH);
+        op_wgrad_host(T.a2.data(), kOpH, T.a1.data(), kOpH, kOpH, kOpH, p + off.w2, p + off.b2, first, nr);
+        op_dgrad_host(T.a2.data(), kOpH, kOpH, an.w2, kOpH, T.a1.data(), kOpH);
+        op_wgrad_host(T.a1.data(), kOpH, T.x.data(), kOpXSh, kOpH, O, p + off.w1, p + off.b1, first, nr);
+    }
+    op_fold_host(part.data(), G, Pa, grads);
+    *actor_loss_out = -1.0f * op_fold_mean_host(rows.data(), M);
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_polyak_f32_cpu(const float* params, float* target_params, int64_t n, double tau) {
+    const char* fn = "mi355ppo_polyak_f32_cpu";
+    MI355_REQUIRE(params && target_params, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(n > 0, MI355PPO_EINVAL, "%s: n=%lld must be > 0", fn, (long long)n);
+    const float t = (float)tau, omt = (float)(1.0 - tau);
+    for (int64_t i = 0; i < n; ++i) target_params[i] = op_polyak(params[i], target_params[i], t, omt);
     return MI355PPO_OK;
 }

@@ -1,0 +1,158 @@
+"""Drop-in for ``cleanrl/ddpg_continuous_action.py``: DDPG (one critic, a deterministic actor, delayed policy updates).
+
+    python cleanrl_amd/ddpg_continuous_action.py --env-id Hopper-v4 --seed 1 [--no-cuda]
+
+Same flags, defaults, stdout lines and scalar tags as the reference.  ``Actor`` / ``ActionValueNetwork`` (cleanrl_amd/agents.py) are
+the reference's networks; ``OffPolicyLearner`` (cleanrl_amd/learner_offpolicy.py) holds the replay buffer and runs the action logic
+and the training step.  ``MI355PPO_OFFPOLICY=fused`` keeps the buffer in device memory and runs a step in at most 12 launches (one critic, no target noise)
+(csrc/offpolicy.hip); ``torch`` runs the reference's ops.  Without gymnasium the built-in continuous stand-in is used.
+"""
+from __future__ import annotations
+
+import os
+import sys
+import time
+from dataclasses import dataclass
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from cleanrl_amd import cli, envs as E, runner  # noqa: E402
+from cleanrl_amd.agents import ActionValueNetwork as QNetwork, Actor  # noqa: E402
+from cleanrl_amd.learner_offpolicy import OffPolicyLearner  # noqa: E402
+
+
+@dataclass
+class Args:
+    exp_name: str = os.path.basename(__file__)[: -len(".py")]
+    """the name of this experiment"""
+    seed: int = 1
+    """seed of the experiment"""
+    torch_deterministic: bool = True
+    """if toggled, `torch.backends.cudnn.deterministic=False`"""
+    cuda: bool = True
+    """if toggled, cuda will be enabled by default"""
+    track: bool = False
+    """if toggled, this experiment will be tracked with Weights and Biases"""
+    wandb_project_name: str = "cleanRL"
+    """the wandb's project name"""
+    wandb_entity: str = None
+    """the entity (team) of wandb's project"""
+    capture_video: bool = False
+    """whether to capture videos of the agent performances (check out `videos` folder)"""
+    save_model: bool = False
+    """whether to save model into the `runs/{run_name}` folder"""
+    upload_model: bool = False
+    """whether to upload the saved model to huggingface"""
+    hf_entity: str = ""
+    """the user or org name of the model repository from the Hugging Face Hub"""
+
+    # Algorithm specific arguments
+    env_id: str = "Hopper-v4"
+    """the environment id of the Atari game"""
+    total_timesteps: int = 1000000
+    """total timesteps of the experiments"""
+    learning_rate: float = 3e-4
+    """the learning rate of the optimizer"""
+    buffer_size: int = int(1e6)
+    """the replay memory buffer size"""
+    gamma: float = 0.99
+    """the discount factor gamma"""
+    tau: float = 0.005
+    """target smoothing coefficient (default: 0.005)"""
+    batch_size: int = 256
+    """the batch size of sample from the reply memory"""
+    exploration_noise: float = 0.1
+    """the scale of exploration noise"""
+    learning_starts: int = 25e3
+    """timestep to start learning"""
+    policy_frequency: int = 2
+    """the frequency of training policy (delayed)"""
+
+
+def make_envs(args, run_name, seeds):
+    if E.have_gymnasium():
+        import gymnasium as gym
+
+        def make_env(env_id, seed, idx, capture_video):
+            def thunk():
+                if capture_video and idx == 0:
+                    env = gym.make(env_id, render_mode="rgb_array")
+                    env = gym.wrappers.RecordVideo(env, f"videos/{run_name}")
+                else:
+                    env = gym.make(env_id)
+                env = gym.wrappers.RecordEpisodeStatistics(env)
+                env.action_space.seed(seed)
+                return env
+
+            return thunk
+
+        envs = gym.vector.SyncVectorEnv([make_env(args.env_id, s, i, args.capture_video) for i, s in enumerate(seeds)])
+        assert isinstance(envs.single_action_space, gym.spaces.Box), "only continuous action space is supported"
+        return envs
+    print(f"[cleanrl_amd] gymnasium not installed: using the built-in continuous stand-in for {args.env_id}", file=sys.stderr)
+    return E.SyntheticReplayVecEnv(len(seeds), seed=args.seed, horizon=int(os.environ.get("MI355PPO_STANDIN_HORIZON", "1000")))
+
+
+def main(argv=None):
+    args = cli.parse(Args, argv)
+    run_name = f"{args.env_id}__{args.exp_name}__{args.seed}__{int(time.time())}"
+    writer = runner.open_writer(args, run_name)
+    runner.seed_everything(args)
+    device = runner.select_device(args)
+
+    envs = make_envs(args, run_name, [args.seed])
+    actor = Actor(envs, batched_space=True).to(device)
+    qf1 = QNetwork(envs).to(device)
+    qf1_target = QNetwork(envs).to(device)
+    target_actor = Actor(envs, batched_space=True).to(device)
+    target_actor.load_state_dict(actor.state_dict())
+    qf1_target.load_state_dict(qf1.state_dict())
+    learner = OffPolicyLearner(actor, [qf1], target_actor, [qf1_target], args, envs, device, td3=False)
+    start_time = time.time()
+
+    obs, _ = envs.reset(seed=args.seed)
+    for global_step in range(args.total_timesteps):
+        actions = learner.act(obs, global_step)
+        next_obs, rewards, terminations, truncations, infos = envs.step(actions)
+
+        if "final_info" in infos:
+            for info in infos["final_info"]:
+                print(f"global_step={global_step}, episodic_return={info['episode']['r']}")
+                writer.add_scalar("charts/episodic_return", info["episode"]["r"], global_step)
+                writer.add_scalar("charts/episodic_length", info["episode"]["l"], global_step)
+                break
+
+        real_next_obs = next_obs.copy()
+        for idx, trunc in enumerate(truncations):
+            if trunc:
+                real_next_obs[idx] = infos["final_observation"][idx]
+        learner.store(obs, real_next_obs, actions, rewards, terminations)
+        obs = next_obs
+
+        if global_step > args.learning_starts:
+            learner.train_step(policy_update=global_step % args.policy_frequency == 0)
+            if global_step % 100 == 0:
+                m = learner.metrics()
+                writer.add_scalar("losses/qf1_values", m["qf1_values"], global_step)
+                writer.add_scalar("losses/qf1_loss", m["qf1_loss"], global_step)
+                writer.add_scalar("losses/actor_loss", m["actor_loss"], global_step)
+                print("SPS:", int(global_step / (time.time() - start_time)))
+                writer.add_scalar("charts/SPS", int(global_step / (time.time() - start_time)), global_step)
+
+    if args.save_model:
+        model_path = f"runs/{run_name}/{args.exp_name}.cleanrl_model"
+        torch.save((actor.state_dict(), qf1.state_dict()), model_path)
+        print(f"model saved to {model_path}")
+        if args.upload_model:
+            raise SystemExit("--upload-model needs network access and cleanrl_utils.huggingface; not available here")
+        print("[cleanrl_amd] the evaluation leg needs cleanrl_utils.evals; not available here", file=sys.stderr)
+
+    envs.close()
+    writer.close()
+    return learner
+
+
+if __name__ == "__main__":
+    main()

@@ -650,3 +650,55 @@ class SyntheticMemoryVecEnv:
 
     def close(self):
         pass
+
+
+class ArrayBox(Box):
+    """A ``Box`` with array bounds, a ``seed()`` and a ``sample()`` (uniform between the bounds), as the replay-buffer scripts use
+    their action space (``low[0]``, ``high - low``, ``sample()`` before ``learning_starts``)."""
+
+    def __init__(self, low, high, shape, dtype=np.float32):
+        shape = tuple(shape)
+        super().__init__(np.full(shape, low, dtype=dtype), np.full(shape, high, dtype=dtype), shape, dtype)
+        self._rng = np.random.RandomState(0)
+
+    def seed(self, seed=None):
+        self._rng = np.random.RandomState(seed)
+        return [seed]
+
+    def sample(self):
+        return self._rng.uniform(self.low, self.high).astype(self.dtype)
+
+
+class SyntheticReplayVecEnv(SyntheticContinuousVecEnv):
+    """The continuous stand-in of ddpg_continuous_action.py / td3_continuous_action.py: ``SyntheticContinuousVecEnv``'s dynamics
+    with array-bounded action spaces (``single_action_space`` and the batched ``action_space``), float32 observations, a
+    configurable truncation ``horizon`` and gymnasium's ``final_observation`` / ``final_info`` in ``infos`` when an episode is
+    truncated (the returned observation is then the next episode's first)."""
+
+    def __init__(self, num_envs: int, seed: int = 0, obs_dim: int = 17, act_dim: int = 6, horizon: int = 1000):
+        super().__init__(num_envs, seed=seed, obs_dim=obs_dim, act_dim=act_dim)
+        self.horizon = int(horizon)
+        self.single_observation_space = Box(-np.inf, np.inf, (obs_dim,), np.float32)
+        self.single_action_space = ArrayBox(-1.0, 1.0, (act_dim,))
+        self.action_space = ArrayBox(-1.0, 1.0, (num_envs, act_dim))
+        self.single_action_space.seed(seed)
+
+    def step(self, action):
+        a = np.clip(np.asarray(action, np.float64).reshape(self.num_envs, self.act_dim), -1, 1)
+        self.state = self.state @ self.A.T + a @ self.B + 0.01 * self.rng.standard_normal(self.state.shape)
+        reward = self.state @ self.w - 0.1 * (a**2).sum(1)
+        self.steps += 1
+        truncated = self.steps >= self.horizon
+        terminated = np.zeros(self.num_envs, bool)
+        r, l = self.stats.update(reward.astype(np.float32), truncated)
+        infos = _final_info(truncated, r, l)
+        if truncated.any():
+            final = np.empty(self.num_envs, dtype=object)
+            rows = np.flatnonzero(truncated)
+            for i in rows:
+                final[i] = self.state[i].astype(np.float32)
+            infos["final_observation"] = final
+            infos["_final_observation"] = truncated.copy()
+            self.state[rows] = self.rng.standard_normal((len(rows), self.obs_dim)) * 0.1
+            self.steps[rows] = 0
+        return self.state.astype(np.float32), reward, terminated, truncated, infos

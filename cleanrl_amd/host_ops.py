@@ -17,7 +17,7 @@ import ctypes
 import torch
 
 from . import _lib
-from .ops import IMPALA_CHANNELS, _lstm_dims, _ptr_array, pqn_param_count, radam_schedule, trxl_dims  # noqa: F401  (one definition for both modules)
+from .ops import IMPALA_CHANNELS, _lstm_dims, _ptr_array, offpolicy_counts, pqn_param_count, radam_schedule, trxl_dims  # noqa: F401  (one definition for both modules)
 
 LOSS_SCALARS = 7
 
@@ -425,3 +425,85 @@ def pqn_lstm_td_fwd_bwd(h, mb_inds, b_actions, b_returns, wq, bq, dwq, dbq, dh=N
               _out(dwq, torch.float32, A * H, "dwq"), _out(dbq, torch.float32, A, "dbq"), _out(scalars, torch.float32, 2, "scalars"), M, H, A,
               ba.numel())
     return dh, scalars
+
+
+# ------------------------------------------------------------------------------------------- DDPG / TD3 twins (csrc/offpolicy.hip)
+def _in(t, dtype, shape, name):
+    """An input the twin reads ``prod(shape)`` elements of: taken as it is (the ring is never copied)."""
+    _p(t)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected {dtype} {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _ring_dims(ring):
+    obs, nxt, act, rew, done = ring
+    slots, N, O = obs.shape
+    A = act.shape[-1]
+    ptrs = [_in(t, torch.float32, shape, nm) for t, nm, shape in (
+        (obs, "ring obs", (slots, N, O)), (nxt, "ring next_obs", (slots, N, O)), (act, "ring actions", (slots, N, A)),
+        (rew, "ring rewards", (slots, N)), (done, "ring dones", (slots, N)))]
+    return slots, N, O, A, ptrs
+
+
+def replay_add(ring, pos, obs, next_obs, actions, rewards, dones):
+    slots, N, O, A, rp = _ring_dims(ring)
+    _lib.call("mi355ppo_replay_add_f32_cpu", _in(obs, torch.float32, (N, O), "obs"), _in(next_obs, torch.float32, (N, O), "next_obs"),
+              _in(actions, torch.float32, (N, A), "actions"), _in(rewards, torch.float32, (N,), "rewards"),
+              _in(dones, torch.float32, (N,), "dones"), *rp, int(pos), slots, N, O, A)
+
+
+def ddpg_act(obs, actor_params, action_scale, action_bias, noise_row, low, high, actions_out):
+    N, O = obs.shape
+    (A,) = action_scale.shape
+    nz = None if noise_row is None else _in(noise_row, torch.float32, (A,), "noise_row")
+    _lib.call("mi355ppo_ddpg_act_f32_cpu", _in(obs, torch.float32, (N, O), "obs"),
+              _in(actor_params, torch.float32, (offpolicy_counts(O, A)[0],), "actor_params"), _in(action_scale, torch.float32, (A,), "action_scale"),
+              _in(action_bias, torch.float32, (A,), "action_bias"), nz, _in(low, torch.float32, (A,), "low"), _in(high, torch.float32, (A,), "high"),
+              _out(actions_out, torch.float32, N * A, "actions_out"), N, O, A)
+    return actions_out
+
+
+def td3_target(ring, batch_inds, env_inds, target_actor, target_critics, n_critics, action_scale, action_bias, noise, policy_noise,
+               noise_clip, low0, high0, gamma, next_q_value, next_actions_out=None):
+    slots, N, O, A, rp = _ring_dims(ring)
+    (M,) = batch_inds.shape
+    pa, pq = offpolicy_counts(O, A)
+    nz = None if noise is None else _in(noise, torch.float32, (M, A), "noise")
+    _lib.call("mi355ppo_td3_target_f32_cpu", rp[1], rp[3], rp[4], _in(batch_inds, torch.int64, (M,), "batch_inds"),
+              _in(env_inds, torch.int64, (M,), "env_inds"), slots, N, _in(target_actor, torch.float32, (pa,), "target_actor"),
+              _in(target_critics, torch.float32, (int(n_critics) * pq,), "target_critics"), int(n_critics),
+              _in(action_scale, torch.float32, (A,), "action_scale"), _in(action_bias, torch.float32, (A,), "action_bias"), nz,
+              float(policy_noise), float(noise_clip), float(low0), float(high0), float(gamma),
+              _out(next_q_value, torch.float32, M, "next_q_value"), _out(next_actions_out, torch.float32, M * A, "next_actions_out"), M, O, A)
+    return next_q_value
+
+
+def td3_critic_fwd_bwd(ring, batch_inds, env_inds, critics, n_critics, next_q_value, grads, scalars):
+    slots, N, O, A, rp = _ring_dims(ring)
+    (M,) = batch_inds.shape
+    P = int(n_critics) * offpolicy_counts(O, A)[1]
+    _lib.call("mi355ppo_td3_critic_fwd_bwd_f32_cpu", rp[0], rp[2], _in(batch_inds, torch.int64, (M,), "batch_inds"),
+              _in(env_inds, torch.int64, (M,), "env_inds"), slots, N, _in(critics, torch.float32, (P,), "critics"), int(n_critics),
+              _in(next_q_value, torch.float32, (M,), "next_q_value"), _out(grads, torch.float32, P, "grads"),
+              _out(scalars, torch.float32, 2 * int(n_critics), "scalars"), M, O, A)
+    return scalars
+
+
+def td3_actor_fwd_bwd(ring, batch_inds, env_inds, actor, qf1, action_scale, action_bias, grads, actor_loss, dq_daction_out=None):
+    slots, N, O, A, rp = _ring_dims(ring)
+    (M,) = batch_inds.shape
+    pa, pq = offpolicy_counts(O, A)
+    _lib.call("mi355ppo_td3_actor_fwd_bwd_f32_cpu", rp[0], _in(batch_inds, torch.int64, (M,), "batch_inds"),
+              _in(env_inds, torch.int64, (M,), "env_inds"), slots, N, _in(actor, torch.float32, (pa,), "actor"),
+              _in(qf1, torch.float32, (pq,), "qf1"), _in(action_scale, torch.float32, (A,), "action_scale"),
+              _in(action_bias, torch.float32, (A,), "action_bias"), _out(grads, torch.float32, pa, "grads"),
+              _out(actor_loss, torch.float32, 1, "actor_loss"), _out(dq_daction_out, torch.float32, M * A, "dq_daction_out"), M, O, A)
+    return actor_loss
+
+
+def polyak_(params, target_params, tau):
+    n = params.numel()
+    _lib.call("mi355ppo_polyak_f32_cpu", _in(params, torch.float32, (n,), "params"), _out(target_params, torch.float32, n, "target_params"),
+              n, float(tau))
+    return target_params

@@ -26,7 +26,8 @@ __all__ = [
     "lstm_seq", "lstm_seq_dw_hh", "impala_forward", "impala_backward", "impala_maxpool_forward", "impala_maxpool_backward",
     "ImpalaTrunk", "impala_trunk", "impala_param_shapes", "trxl_attn_forward", "trxl_attn_backward", "TrXLMemoryAttention", "trxl_memory_attention",
     "pqn_param_count", "pqn_egreedy", "pqn_qlambda", "pqn_td_loss", "pqn_mlp_forward", "pqn_mlp_act", "pqn_mlp_td_fwd_bwd", "radam_schedule",
-    "clip_radam_", "clip_radam_sched_", "pqn_lstm_act", "pqn_lstm_td_fwd_bwd",
+    "clip_radam_", "clip_radam_sched_", "pqn_lstm_act", "pqn_lstm_td_fwd_bwd", "offpolicy_counts", "replay_add", "ddpg_act", "td3_target",
+    "td3_critic_fwd_bwd", "td3_actor_fwd_bwd", "polyak_",
 ]
 
 LOSS_SCALAR_NAMES = ("loss", "pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac")
@@ -1282,3 +1283,127 @@ def pqn_lstm_td_fwd_bwd(h, mb_inds, b_actions, b_returns, wq, bq, dwq, dbq, dh=N
     _launch("mi355ppo_pqn_lstm_td_fwd_bwd_f32", dev, _ptr(h), _ptr(mb_inds), _ptr(b_actions), _ptr(b_returns), _ptr(wq), _ptr(bq), _ptr(dh),
             _ptr(dwq), _ptr(dbq), _ptr(scalars), M, H, A, B, _ptr(ws), ws.numel())
     return dh, scalars
+
+
+# ------------------------------------------------------------------------------------------- DDPG / TD3 (csrc/offpolicy.hip)
+OFFPOLICY_MAX_OBS, OFFPOLICY_MAX_ACT, OFFPOLICY_HIDDEN = 512, 20, 256
+
+
+def offpolicy_counts(obs_dim: int, act_dim: int):
+    """(actor, critic) parameter counts of the two scripts' ``Actor`` / ``QNetwork`` (hidden width 256)."""
+    h = OFFPOLICY_HIDDEN
+    return h * obs_dim + h + h * h + h + act_dim * h + act_dim, h * (obs_dim + act_dim) + h + h * h + h + h + 1
+
+
+def _ring_dims(ring):
+    """ring = (obs, next_obs, actions, rewards, dones), each (slots, n_envs, .) f32 -> (slots, N, O, A)."""
+    obs, nxt, act, rew, done = ring
+    slots, N, O = obs.shape
+    A = act.shape[-1]
+    for t, nm, shape in ((obs, "ring obs", (slots, N, O)), (nxt, "ring next_obs", (slots, N, O)), (act, "ring actions", (slots, N, A)),
+                         (rew, "ring rewards", (slots, N)), (done, "ring dones", (slots, N))):
+        _chk(t, torch.float32, nm, shape)
+    return slots, N, O, A
+
+
+def _batch_inds(batch_inds, env_inds):
+    (M,) = batch_inds.shape
+    _chk(batch_inds, torch.int64, "batch_inds", (M,))
+    _chk(env_inds, torch.int64, "env_inds", (M,))
+    return M
+
+
+def replay_add(ring, pos: int, obs, next_obs, actions, rewards, dones):
+    """``ReplayBuffer.add``: one step's N transitions into slot ``pos`` of the device ring (one launch)."""
+    slots, N, O, A = _ring_dims(ring)
+    _chk(obs, torch.float32, "obs", (N, O))
+    _chk(next_obs, torch.float32, "next_obs", (N, O))
+    _chk(actions, torch.float32, "actions", (N, A))
+    _chk(rewards, torch.float32, "rewards", (N,))
+    _chk(dones, torch.float32, "dones", (N,))
+    _launch("mi355ppo_replay_add_f32", obs.device, _ptr(obs), _ptr(next_obs), _ptr(actions), _ptr(rewards), _ptr(dones),
+            *[_ptr(t) for t in ring], int(pos), slots, N, O, A)
+
+
+def ddpg_act(obs, actor_params, action_scale, action_bias, noise_row, low, high, actions_out):
+    """The rollout's action in one launch: ``actor(obs) + noise_row`` clipped to ``low`` / ``high`` -> actions_out (N, A)."""
+    N, O = obs.shape
+    (A,) = action_scale.shape
+    _chk(obs, torch.float32, "obs")
+    _chk(actor_params, torch.float32, "actor_params", (offpolicy_counts(O, A)[0],))
+    for t, nm in ((action_scale, "action_scale"), (action_bias, "action_bias"), (low, "low"), (high, "high")):
+        _chk(t, torch.float32, nm, (A,))
+    if noise_row is not None:
+        _chk(noise_row, torch.float32, "noise_row", (A,))
+    _chk(actions_out, torch.float32, "actions_out", (N, A))
+    _launch("mi355ppo_ddpg_act_f32", obs.device, _ptr(obs), _ptr(actor_params), _ptr(action_scale), _ptr(action_bias), _ptr(noise_row),
+            _ptr(low), _ptr(high), _ptr(actions_out), N, O, A)
+    return actions_out
+
+
+def td3_target(ring, batch_inds, env_inds, target_actor, target_critics, n_critics: int, action_scale, action_bias, noise,
+               policy_noise: float, noise_clip: float, low0: float, high0: float, gamma: float, next_q_value, next_actions_out=None):
+    """The ``with torch.no_grad()`` block of the training step in one launch -> next_q_value (M,).  ``noise`` None: DDPG."""
+    slots, N, O, A = _ring_dims(ring)
+    M = _batch_inds(batch_inds, env_inds)
+    pa, pq = offpolicy_counts(O, A)
+    _chk(target_actor, torch.float32, "target_actor", (pa,))
+    _chk(target_critics, torch.float32, "target_critics", (int(n_critics) * pq,))
+    _chk(action_scale, torch.float32, "action_scale", (A,))
+    _chk(action_bias, torch.float32, "action_bias", (A,))
+    if noise is not None:
+        _chk(noise, torch.float32, "noise", (M, A))
+    _chk(next_q_value, torch.float32, "next_q_value", (M,))
+    if next_actions_out is not None:
+        _chk(next_actions_out, torch.float32, "next_actions_out", (M, A))
+    _launch("mi355ppo_td3_target_f32", batch_inds.device, _ptr(ring[1]), _ptr(ring[3]), _ptr(ring[4]), _ptr(batch_inds), _ptr(env_inds), slots,
+            N, _ptr(target_actor), _ptr(target_critics), int(n_critics), _ptr(action_scale), _ptr(action_bias), _ptr(noise),
+            float(policy_noise), float(noise_clip), float(low0), float(high0), float(gamma), _ptr(next_q_value), _ptr(next_actions_out),
+            M, O, A)
+    return next_q_value
+
+
+def td3_critic_fwd_bwd(ring, batch_inds, env_inds, critics, n_critics: int, next_q_value, grads, scalars):
+    """Critic forward, ``mse_loss`` and backward in two launches.  OVERWRITES ``grads`` (flat, ``list(qf1.parameters()) +
+    list(qf2.parameters())`` order); scalars (2 * n_critics,) = {mean q1, qf1_loss, mean q2, qf2_loss}."""
+    slots, N, O, A = _ring_dims(ring)
+    M = _batch_inds(batch_inds, env_inds)
+    P = int(n_critics) * offpolicy_counts(O, A)[1]
+    _chk(critics, torch.float32, "critics", (P,))
+    _chk(next_q_value, torch.float32, "next_q_value", (M,))
+    _chk(grads, torch.float32, "grads", (P,))
+    _chk(scalars, torch.float32, "scalars", (2 * int(n_critics),))
+    dev = batch_inds.device
+    ws = _workspace(dev, _lib.load().mi355ppo_td3_critic_workspace_bytes(M, O, A, int(n_critics)))
+    _launch("mi355ppo_td3_critic_fwd_bwd_f32", dev, _ptr(ring[0]), _ptr(ring[2]), _ptr(batch_inds), _ptr(env_inds), slots, N, _ptr(critics),
+            int(n_critics), _ptr(next_q_value), _ptr(grads), _ptr(scalars), M, O, A, _ptr(ws), ws.numel())
+    return scalars
+
+
+def td3_actor_fwd_bwd(ring, batch_inds, env_inds, actor, qf1, action_scale, action_bias, grads, actor_loss, dq_daction_out=None):
+    """``actor_loss = -qf1(obs, actor(obs)).mean()`` and its gradient w.r.t. the actor in two launches.  OVERWRITES ``grads``."""
+    slots, N, O, A = _ring_dims(ring)
+    M = _batch_inds(batch_inds, env_inds)
+    pa, pq = offpolicy_counts(O, A)
+    _chk(actor, torch.float32, "actor", (pa,))
+    _chk(qf1, torch.float32, "qf1", (pq,))
+    _chk(action_scale, torch.float32, "action_scale", (A,))
+    _chk(action_bias, torch.float32, "action_bias", (A,))
+    _chk(grads, torch.float32, "grads", (pa,))
+    _chk(actor_loss, torch.float32, "actor_loss", (1,))
+    if dq_daction_out is not None:
+        _chk(dq_daction_out, torch.float32, "dq_daction_out", (M, A))
+    dev = batch_inds.device
+    ws = _workspace(dev, _lib.load().mi355ppo_td3_actor_workspace_bytes(M, O, A))
+    _launch("mi355ppo_td3_actor_fwd_bwd_f32", dev, _ptr(ring[0]), _ptr(batch_inds), _ptr(env_inds), slots, N, _ptr(actor), _ptr(qf1),
+            _ptr(action_scale), _ptr(action_bias), _ptr(grads), _ptr(actor_loss), _ptr(dq_daction_out), M, O, A, _ptr(ws), ws.numel())
+    return actor_loss
+
+
+def polyak_(params, target_params, tau: float):
+    """``target = tau * param + (1 - tau) * target`` over flat buffers, in place on ``target_params`` (one launch)."""
+    n = params.numel()
+    _chk(params, torch.float32, "params", (n,))
+    _chk(target_params, torch.float32, "target_params", (n,))
+    _launch("mi355ppo_polyak_f32", params.device, _ptr(params), _ptr(target_params), n, float(tau))
+    return target_params

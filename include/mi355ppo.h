@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MI355PPO_VERSION 260 /* major*100 + minor*10 + patch.  The minor moves whenever an exported signature changes or an entry
+#define MI355PPO_VERSION 270 /* major*100 + minor*10 + patch.  The minor moves whenever an exported signature changes or an entry
                                   point is added (1.1: adv_mean_den / conv1_variant arguments of round 2; 1.2, 1.3: round 3;
                                   1.4: the *_cpu host-pointer twins; 1.5: mi355ppo_init; 1.6: round 4 -- the fused MLP family K7,
                                   mi355ppo_clip_adam_sched_f32; 1.7: mi355ppo_fc_heads_act_categorical_f32, mi355ppo_nature_packs_f32,
@@ -927,6 +927,75 @@ MI355PPO_API int mi355ppo_pqn_lstm_td_fwd_bwd_f32(const float* h, const int64_t*
 MI355PPO_API int mi355ppo_pqn_lstm_td_fwd_bwd_f32_cpu(const float* h, const int64_t* mb_inds, const float* b_actions, const float* b_returns,
                                                       const float* wq, const float* bq, float* dh, float* dwq, float* dbq,
                                                       float* scalars_out, int M, int H, int A, int64_t B);
+
+/* ---- DDPG / TD3 (ABI 2.7, csrc/offpolicy.hip; reference: cleanrl/ddpg_continuous_action.py, cleanrl/td3_continuous_action.py) ----
+ * Actor and QNetwork are Linear(K, 256) - ReLU - Linear(256, 256) - ReLU - Linear(256, J) (K = obs_dim, J = act_dim; K = obs_dim +
+ * act_dim, J = 1 on cat(obs, action)); a network is its flat f32 parameters in .parameters() order.  1 <= obs_dim <= 512,
+ * 1 <= act_dim <= 20, anything else is MI355PPO_EINVAL.  The replay ring is five f32 arrays (slots, n_envs, .): obs, next_obs,
+ * actions, rewards, dones; a batch row m is ring row batch_inds[m] * n_envs + env_inds[m] (int64; an index out of range is
+ * clamped).  No entry point allocates or synchronises, none uses atomics, all can be captured.  Every *_cpu twin (host pointers, no
+ * workspace, no stream) returns the device's bits: the accumulation orders are those of csrc/offpolicy_rows.h.
+ *
+ * replay_add: one step's N transitions into slot pos (0 <= pos < slots).  One launch. */
+MI355PPO_API int mi355ppo_replay_add_f32(const float* obs, const float* next_obs, const float* actions, const float* rewards,
+                                         const float* dones, float* ring_obs, float* ring_next_obs, float* ring_actions,
+                                         float* ring_rewards, float* ring_dones, int64_t pos, int64_t slots, int N, int O, int A,
+                                         void* stream);
+MI355PPO_API int mi355ppo_replay_add_f32_cpu(const float* obs, const float* next_obs, const float* actions, const float* rewards,
+                                             const float* dones, float* ring_obs, float* ring_next_obs, float* ring_actions,
+                                             float* ring_rewards, float* ring_dones, int64_t pos, int64_t slots, int N, int O, int A);
+/* act: actions_out (N, A) = clip(tanh(actor(obs)) * action_scale + action_bias + noise_row, low, high); noise_row (A) may be NULL.
+ * One launch. */
+MI355PPO_API int mi355ppo_ddpg_act_f32(const float* obs, const float* actor_params, const float* action_scale, const float* action_bias,
+                                       const float* noise_row, const float* low, const float* high, float* actions_out, int N, int O,
+                                       int A, void* stream);
+MI355PPO_API int mi355ppo_ddpg_act_f32_cpu(const float* obs, const float* actor_params, const float* action_scale,
+                                           const float* action_bias, const float* noise_row, const float* low, const float* high,
+                                           float* actions_out, int N, int O, int A);
+/* target: next_q_value (M) = rewards + (1 - dones) * gamma * min_c q_c(next_obs, a'), a' = target_actor(next_obs) and, with noise (M, A)
+ * non-NULL, + (noise * policy_noise).clamp(+-noise_clip) * action_scale clamped to [low0, high0] (TD3); noise NULL: neither (DDPG).
+ * target_critics holds n_critics (1 or 2) networks back to back.  next_actions_out (M, A) may be NULL.  One launch. */
+MI355PPO_API int mi355ppo_td3_target_f32(const float* ring_next_obs, const float* ring_rewards, const float* ring_dones,
+                                         const int64_t* batch_inds, const int64_t* env_inds, int64_t slots, int n_envs,
+                                         const float* target_actor, const float* target_critics, int n_critics,
+                                         const float* action_scale, const float* action_bias, const float* noise, double policy_noise,
+                                         double noise_clip, double low0, double high0, double gamma, float* next_q_value,
+                                         float* next_actions_out, int M, int O, int A, void* stream);
+MI355PPO_API int mi355ppo_td3_target_f32_cpu(const float* ring_next_obs, const float* ring_rewards, const float* ring_dones,
+                                             const int64_t* batch_inds, const int64_t* env_inds, int64_t slots, int n_envs,
+                                             const float* target_actor, const float* target_critics, int n_critics,
+                                             const float* action_scale, const float* action_bias, const float* noise,
+                                             double policy_noise, double noise_clip, double low0, double high0, double gamma,
+                                             float* next_q_value, float* next_actions_out, int M, int O, int A);
+/* critic: q_c = critic_c(obs, actions), loss = sum_c F.mse_loss(q_c, next_q_value); grads (n_critics * critic parameters, the order of
+ * list(qf1.parameters()) + list(qf2.parameters())) is OVERWRITTEN; scalars_out (2 * n_critics) = {mean q1, qf1_loss, mean q2, qf2_loss}.
+ * Two launches: per-workgroup partials, then the fold in workgroup order. */
+MI355PPO_API size_t mi355ppo_td3_critic_workspace_bytes(int M, int O, int A, int n_critics);
+MI355PPO_API int mi355ppo_td3_critic_fwd_bwd_f32(const float* ring_obs, const float* ring_actions, const int64_t* batch_inds,
+                                                 const int64_t* env_inds, int64_t slots, int n_envs, const float* critics, int n_critics,
+                                                 const float* next_q_value, float* grads, float* scalars_out, int M, int O, int A,
+                                                 void* workspace, size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_td3_critic_fwd_bwd_f32_cpu(const float* ring_obs, const float* ring_actions, const int64_t* batch_inds,
+                                                     const int64_t* env_inds, int64_t slots, int n_envs, const float* critics,
+                                                     int n_critics, const float* next_q_value, float* grads, float* scalars_out, int M,
+                                                     int O, int A);
+/* actor: actor_loss = -mean(qf1(obs, actor(obs))); grads (actor parameters) is OVERWRITTEN (qf1 gets no gradient: the backward runs
+ * through its first layer to the action columns only); dq_daction_out (M, A), the gradient of the loss w.r.t. the action, may be
+ * NULL.  Two launches. */
+MI355PPO_API size_t mi355ppo_td3_actor_workspace_bytes(int M, int O, int A);
+MI355PPO_API int mi355ppo_td3_actor_fwd_bwd_f32(const float* ring_obs, const int64_t* batch_inds, const int64_t* env_inds, int64_t slots,
+                                                int n_envs, const float* actor, const float* qf1, const float* action_scale,
+                                                const float* action_bias, float* grads, float* actor_loss_out, float* dq_daction_out,
+                                                int M, int O, int A, void* workspace, size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_td3_actor_fwd_bwd_f32_cpu(const float* ring_obs, const int64_t* batch_inds, const int64_t* env_inds,
+                                                    int64_t slots, int n_envs, const float* actor, const float* qf1,
+                                                    const float* action_scale, const float* action_bias, float* grads,
+                                                    float* actor_loss_out, float* dq_daction_out, int M, int O, int A);
+/* polyak: target = (float)tau * param + (float)(1 - tau) * target over flat buffers (1 - tau formed in double, as Python does).
+ * One launch; bit-equal to the reference's per-parameter loop.  Adam for these scripts is mi355ppo_clip_adam_f32 with
+ * grad_scale = 1 and max_grad_norm = +inf (coefficient min(inf, 1) = exactly 1) and eps = 1e-8. */
+MI355PPO_API int mi355ppo_polyak_f32(const float* params, float* target_params, int64_t n, double tau, void* stream);
+MI355PPO_API int mi355ppo_polyak_f32_cpu(const float* params, float* target_params, int64_t n, double tau);
 
 #ifdef __cplusplus
 }

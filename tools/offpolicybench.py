@@ -1,0 +1,92 @@
+"""ddpg_continuous_action.py / td3_continuous_action.py with both ``MI355PPO_OFFPOLICY`` backends, in one process, alternating.
+
+    python tools/offpolicybench.py [--reps 20] [--scripts td3 ddpg]
+
+Times, at each script's defaults (batch 256) on a HalfCheetah-shaped (obs 17 / act 6) and a Humanoid-shaped (376 / 17) task:
+one rollout step including the action's copy to the host, one critic-only training step and one step with the delayed policy
+update.  The comparison is the ``torch`` backend on the same box in the same process; medians of ``--reps`` after a warm-up.
+Prints one JSON line per (script, shape).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from cleanrl_amd import envs as E  # noqa: E402
+from cleanrl_amd.agents import ActionValueNetwork, Actor  # noqa: E402
+from cleanrl_amd.learner_offpolicy import OffPolicyLearner  # noqa: E402
+
+SHAPES = {"halfcheetah": (17, 6), "humanoid": (376, 17)}
+
+
+def make(script, O, A, backend, dev, fill=4096):
+    td3 = script == "td3"
+    torch.manual_seed(1)
+    np.random.seed(1)
+    envs = E.SyntheticReplayVecEnv(1, seed=1, obs_dim=O, act_dim=A)
+    nets = [Actor(envs, batched_space=not td3).to(dev)] + [ActionValueNetwork(envs).to(dev) for _ in range(2 if td3 else 1)]
+    tgts = [Actor(envs, batched_space=not td3).to(dev)] + [ActionValueNetwork(envs).to(dev) for _ in range(2 if td3 else 1)]
+    for n, t in zip(nets, tgts):
+        t.load_state_dict(n.state_dict())
+    args = SimpleNamespace(buffer_size=fill * 2, batch_size=256, learning_rate=3e-4, gamma=0.99, tau=0.005, policy_noise=0.2, noise_clip=0.5,
+                           exploration_noise=0.1, learning_starts=0)
+    L = OffPolicyLearner(nets[0], nets[1:], tgts[0], tgts[1:], args, envs, dev, td3=td3, backend=backend)
+    obs, _ = envs.reset(seed=1)
+    for _ in range(fill):
+        a = np.array([envs.single_action_space.sample()])
+        nxt, r, term, trunc, _ = envs.step(a)
+        L.store(obs, nxt, a, r, term)
+        obs = nxt
+    return L, obs
+
+
+def timed(fn, dev):
+    if dev.type == "cuda":
+        torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    if dev.type == "cuda":
+        torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e6
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--scripts", nargs="+", default=["td3", "ddpg"])
+    ap.add_argument("--no-cuda", action="store_true")
+    a = ap.parse_args()
+    dev = torch.device("cuda" if torch.cuda.is_available() and not a.no_cuda else "cpu")
+    for script in a.scripts:
+        for shape, (O, A) in SHAPES.items():
+            learners = {b: make(script, O, A, b, dev) for b in ("torch", "fused")}
+            legs = {"rollout_step": lambda L, obs: L.act(obs, 1), "critic_step": lambda L, obs: L.train_step(False),
+                    "policy_step": lambda L, obs: L.train_step(True)}
+            times = {leg: {b: [] for b in learners} for leg in legs}
+            for rep in range(a.warmup + a.reps):
+                for leg, fn in legs.items():
+                    for b, (L, obs) in learners.items():                 # alternating: both backends see the same box state
+                        us = timed(lambda: fn(L, obs), dev)
+                        if rep >= a.warmup:
+                            times[leg][b].append(us)
+            row = {"script": script, "shape": shape, "obs_dim": O, "act_dim": A, "batch": 256, "device": str(dev), "reps": a.reps}
+            for leg in legs:
+                for b in learners:
+                    row[f"{leg}_{b}_us"] = round(statistics.median(times[leg][b]), 1)
+                row[f"{leg}_speedup"] = round(row[f"{leg}_torch_us"] / row[f"{leg}_fused_us"], 2)
+            print(json.dumps(row), flush=True)
+
+
+if __name__ == "__main__":
+    main()
