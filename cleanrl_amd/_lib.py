@@ -210,9 +210,20 @@ SIGNATURES = {
     "mi355ppo_td3_actor_fwd_bwd_f32_cpu": (c_int, [_P] * 3 + [c_int64, c_int] + [_P] * 7 + [c_int, c_int, c_int]),
     "mi355ppo_polyak_f32": (c_int, [_P, _P, c_int64, c_double, _P]),
     "mi355ppo_polyak_f32_cpu": (c_int, [_P, _P, c_int64, c_double]),
+    # SAC (ABI 2.7.1, csrc/sac.hip)
+    "mi355ppo_sac_policy_f32": (c_int, [_P] * 3 + [c_int64, c_int] + [_P] * 6 + [c_int, c_int, c_int, _P]),
+    "mi355ppo_sac_policy_f32_cpu": (c_int, [_P] * 3 + [c_int64, c_int] + [_P] * 6 + [c_int, c_int, c_int]),
+    "mi355ppo_sac_target_f32": (c_int, [_P] * 5 + [c_int64, c_int] + [_P] * 6 + [c_double, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "mi355ppo_sac_target_f32_cpu": (c_int, [_P] * 5 + [c_int64, c_int] + [_P] * 6 + [c_double, _P, _P, _P, c_int, c_int, c_int]),
+    "mi355ppo_sac_actor_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mi355ppo_sac_actor_fwd_bwd_f32": (c_int, [_P] * 3 + [c_int64, c_int] + [_P] * 11 + [c_int, c_int, c_int, _P, c_size_t, _P]),
+    "mi355ppo_sac_actor_fwd_bwd_f32_cpu": (c_int, [_P] * 3 + [c_int64, c_int] + [_P] * 11 + [c_int, c_int, c_int]),
+    "mi355ppo_sac_alpha_f32": (c_int, [_P, c_int, c_double, _P, _P, _P] + [c_double] * 4 + [c_int64, _P, _P, _P, _P]),
+    "mi355ppo_sac_alpha_f32_cpu": (c_int, [_P, c_int, c_double, _P, _P, _P] + [c_double] * 4 + [c_int64, _P, _P]),
+    "mi355ppo_sac_exp_log_f32_cpu": (c_int, [_P, _P, _P, c_int64]),
 }
 
-ABI_VERSION = 270       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)
+ABI_VERSION = 271       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)
 
 _lib = None
 

@@ -1220,3 +1220,48 @@ class Actor(nn.Module):
         x = torch.relu(self.fc2(x))
         x = torch.tanh(self.fc_mu(x))
         return x * self.action_scale + self.action_bias
+
+
+# ------------------------------------------------------------------------------------------- SAC (sac_continuous_action.py)
+SoftQNetwork = ActionValueNetwork           # the script's critic is the same network under another name
+LOG_STD_MAX = 2
+LOG_STD_MIN = -5
+
+
+class SoftActor(nn.Module):
+    """sac_continuous_action.py's ``Actor``: Linear(obs, 256) -> ReLU -> Linear(256, 256) -> ReLU, then ``fc_mean`` and ``fc_logstd``
+    (Linear(256, act) each, in that construction order, so a seed gives the reference's weights); ``log_std`` is squashed into
+    [LOG_STD_MIN, LOG_STD_MAX] through tanh.  ``get_action`` draws ``Normal.rsample`` (one standard normal of the mean's shape from
+    the global stream) unless ``eps`` is given."""
+
+    def __init__(self, env):
+        super().__init__()
+        self.fc1 = nn.Linear(np.array(env.single_observation_space.shape).prod(), 256)
+        self.fc2 = nn.Linear(256, 256)
+        self.fc_mean = nn.Linear(256, np.prod(env.single_action_space.shape))
+        self.fc_logstd = nn.Linear(256, np.prod(env.single_action_space.shape))
+        space = env.single_action_space
+        self.register_buffer("action_scale", torch.tensor((space.high - space.low) / 2.0, dtype=torch.float32))
+        self.register_buffer("action_bias", torch.tensor((space.high + space.low) / 2.0, dtype=torch.float32))
+
+    def forward(self, x):
+        x = torch.relu(self.fc1(x))
+        x = torch.relu(self.fc2(x))
+        mean = self.fc_mean(x)
+        log_std = self.fc_logstd(x)
+        log_std = torch.tanh(log_std)
+        log_std = LOG_STD_MIN + 0.5 * (LOG_STD_MAX - LOG_STD_MIN) * (log_std + 1)
+        return mean, log_std
+
+    def get_action(self, x, eps=None):
+        mean, log_std = self(x)
+        std = log_std.exp()
+        normal = torch.distributions.Normal(mean, std)
+        x_t = normal.rsample() if eps is None else mean + eps * std
+        y_t = torch.tanh(x_t)
+        action = y_t * self.action_scale + self.action_bias
+        log_prob = normal.log_prob(x_t)
+        log_prob -= torch.log(self.action_scale * (1 - y_t.pow(2)) + 1e-6)
+        log_prob = log_prob.sum(1, keepdim=True)
+        mean = torch.tanh(mean) * self.action_scale + self.action_bias
+        return action, log_prob, mean

@@ -21,6 +21,7 @@
 #include "pqn_rows.h"
 #include "pqn_lstm_rows.h"
 #include "offpolicy_rows.h"
+#include "sac_rows.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -1590,5 +1591,247 @@ extern "C" MI355PPO_API int mi355ppo_polyak_f32_cpu(const float* params, float* 
     MI355_REQUIRE(n > 0, MI355PPO_EINVAL, "%s: n=%lld must be > 0", fn, (long long)n);
     const float t = (float)tau, omt = (float)(1.0 - tau);
     for (int64_t i = 0; i < n; ++i) target_params[i] = op_polyak(params[i], target_params[i], t, omt);
+    return MI355PPO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ SAC (sac.hip)
+// The device's element functions (sac_rows.h over offpolicy_rows.h) in the device's orders; every output equals the device's bit for
+// bit (op_exp / op_log / op_tanh use no libm function).
+namespace {
+
+struct SacTileH {
+    float mu[kOpRows * kOpMaxAct], us[kOpRows * kOpMaxAct], y[kOpRows * kOpMaxAct], std[kOpRows * kOpMaxAct], th[kOpRows * kOpMaxAct],
+        arg[kOpRows * kOpMaxAct], g1[kOpRows * kOpMaxAct], g2[kOpRows * kOpMaxAct], lpr[kOpRows];
+};
+
+// get_action of one tile (wg_sac_policy): T.x's rows hold the observations
+void sac_policy_host(const SacNet& an, const float* scale, const float* bias, const float* eps, int r0, int rows, OpTile& T, SacTileH& S) {
+    const int A = an.A;
+    op_fwd_host<true>(T.x.data(), kOpXSh, an.K, an.w1, an.b1, T.a1.data(), kOpH);
+    op_fwd_host<true>(T.a1.data(), kOpH, kOpH, an.w2, an.b2, T.a2.data(), kOpH);
+    op_head_host(T.a2.data(), kOpH, an.wm, an.bm, A, S.mu);
+    op_head_host(T.a2.data(), kOpH, an.ws, an.bs, A, S.us);
+    for (int r = 0; r < kOpRows; ++r) {
+        float acc = 0.0f;
+        for (int a = 0; a < A; ++a) {
+            const int t = r * A + a;
+            const float ev = (r0 + r < rows) ? eps[(int64_t)(r0 + r) * A + a] : 0.0f;
+            const SacElem e = sac_elem(S.mu[t], S.us[t], ev, scale[a], bias[a]);
+            S.y[t] = e.y;
+            S.std[t] = e.std;
+            S.th[t] = e.th;
+            S.arg[t] = e.arg;
+            T.x[r * kOpXSh + an.K + a] = e.action;
+            acc = acc + e.lp;
+        }
+        S.lpr[r] = acc;
+    }
+}
+
+void sac_dgrad2_host(const float* dza, const float* Wa, const float* dzb, const float* Wb, int J, float* io) {
+    for (int k = 0; k < kOpH; ++k)
+        for (int r = 0; r < kOpRows; ++r) {
+            float acc = 0.0f;
+            for (int j = 0; j < J; ++j) acc = op_mac(acc, dza[r * J + j], Wa[j * kOpH + k]);
+            for (int j = 0; j < J; ++j) acc = op_mac(acc, dzb[r * J + j], Wb[j * kOpH + k]);
+            io[r * kOpH + k] = op_relu_bwd(io[r * kOpH + k], acc);
+        }
+}
+
+}  // namespace
+
+extern "C" MI355PPO_API int mi355ppo_sac_exp_log_f32_cpu(const float* x, float* exp_out, float* log_out, int64_t n) {
+    const char* fn = "mi355ppo_sac_exp_log_f32_cpu";
+    MI355_REQUIRE(x && (exp_out || log_out), MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(n > 0, MI355PPO_EINVAL, "%s: n=%lld must be > 0", fn, (long long)n);
+    for (int64_t i = 0; i < n; ++i) {
+        if (exp_out) exp_out[i] = op_exp(x[i]);
+        if (log_out) log_out[i] = op_log(x[i]);
+    }
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_sac_policy_f32_cpu(const float* obs, const int64_t* batch_inds, const int64_t* env_inds, int64_t slots,
+                                                       int n_envs, const float* actor, const float* action_scale, const float* action_bias,
+                                                       const float* eps, float* actions_out, float* log_pi_out, int rows, int O, int A) {
+    const char* fn = "mi355ppo_sac_policy_f32_cpu";
+    MI355_REQUIRE(obs && actor && action_scale && action_bias && eps && (actions_out || log_pi_out), MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE((batch_inds == nullptr) == (env_inds == nullptr), MI355PPO_EINVAL, "%s: batch_inds and env_inds come together", fn);
+    MI355_REQUIRE(!batch_inds || (slots > 0 && n_envs > 0), MI355PPO_EINVAL, "%s: slots=%lld n_envs=%d must be positive", fn, (long long)slots,
+                  n_envs);
+    if (int rc = op_shape_cpu(fn, rows, O, A)) return rc;
+    const SacNet an = sac_net(actor, O, A);
+    OpTile T;
+    SacTileH S;
+    for (int r0 = 0; r0 < rows; r0 += kOpRows) {
+        for (int r = 0; r < kOpRows; ++r) {
+            const int64_t row = (r0 + r < rows) ? (batch_inds ? op_row_cpu(batch_inds, env_inds, r0 + r, slots, n_envs) : (int64_t)(r0 + r)) : 0;
+            for (int k = 0; k < O; ++k) T.x[r * kOpXSh + k] = (r0 + r < rows) ? obs[row * O + k] : 0.0f;
+        }
+        sac_policy_host(an, action_scale, action_bias, eps, r0, rows, T, S);
+        for (int r = 0; r < kOpRows && r0 + r < rows; ++r) {
+            if (actions_out)
+                for (int a = 0; a < A; ++a) actions_out[(int64_t)(r0 + r) * A + a] = T.x[r * kOpXSh + O + a];
+            if (log_pi_out) log_pi_out[r0 + r] = S.lpr[r];
+        }
+    }
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_sac_target_f32_cpu(const float* ring_next_obs, const float* ring_rewards, const float* ring_dones,
+                                                       const int64_t* batch_inds, const int64_t* env_inds, int64_t slots, int n_envs,
+                                                       const float* actor, const float* target_critics, const float* action_scale,
+                                                       const float* action_bias, const float* eps, const float* alpha, double gamma,
+                                                       float* next_q_value, float* next_actions_out, float* log_pi_out, int M, int O, int A) {
+    const char* fn = "mi355ppo_sac_target_f32_cpu";
+    MI355_REQUIRE(ring_next_obs && ring_rewards && ring_dones && actor && target_critics && action_scale && action_bias && eps && alpha &&
+                      next_q_value && batch_inds && env_inds,
+                  MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(slots > 0 && n_envs > 0, MI355PPO_EINVAL, "%s: slots=%lld n_envs=%d must be positive", fn, (long long)slots, n_envs);
+    if (int rc = op_shape_cpu(fn, M, O, A)) return rc;
+    const SacNet an = sac_net(actor, O, A);
+    const int64_t Pq = op_critic_count(O, A);
+    const float g = (float)gamma;
+    OpTile T;
+    SacTileH S;
+    for (int r0 = 0; r0 < M; r0 += kOpRows) {
+        for (int r = 0; r < kOpRows; ++r)
+            for (int k = 0; k < O; ++k)
+                T.x[r * kOpXSh + k] = (r0 + r < M) ? ring_next_obs[op_row_cpu(batch_inds, env_inds, r0 + r, slots, n_envs) * O + k] : 0.0f;
+        sac_policy_host(an, action_scale, action_bias, eps, r0, M, T, S);
+        if (next_actions_out)
+            for (int r = 0; r < kOpRows && r0 + r < M; ++r)
+                for (int a = 0; a < A; ++a) next_actions_out[(int64_t)(r0 + r) * A + a] = T.x[r * kOpXSh + O + a];
+        for (int c = 0; c < 2; ++c) {
+            const OpNet qn = op_net(target_critics + c * Pq, O + A, 1);
+            op_fwd_host<true>(T.x.data(), kOpXSh, O + A, qn.w1, qn.b1, T.a1.data(), kOpH);
+            op_fwd_host<true>(T.a1.data(), kOpH, kOpH, qn.w2, qn.b2, T.a2.data(), kOpH);
+            op_head_host(T.a2.data(), kOpH, qn.w3, qn.b3, 1, T.qv + c * kOpRows);
+        }
+        for (int r = 0; r < kOpRows && r0 + r < M; ++r) {
+            const int64_t row = op_row_cpu(batch_inds, env_inds, r0 + r, slots, n_envs);
+            next_q_value[r0 + r] = op_td_target(ring_rewards[row], ring_dones[row], g, sac_soft_q(T.qv[r], T.qv[kOpRows + r], alpha[0], S.lpr[r]));
+            if (log_pi_out) log_pi_out[r0 + r] = S.lpr[r];
+        }
+    }
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_sac_actor_fwd_bwd_f32_cpu(const float* ring_obs, const int64_t* batch_inds, const int64_t* env_inds,
+                                                              int64_t slots, int n_envs, const float* actor, const float* critics,
+                                                              const float* action_scale, const float* action_bias, const float* eps,
+                                                              const float* alpha, float* grads, float* actor_loss_out, float* log_pi_out,
+                                                              float* dmean_out, float* du_out, int M, int O, int A) {
+    const char* fn = "mi355ppo_sac_actor_fwd_bwd_f32_cpu";
+    MI355_REQUIRE(ring_obs && actor && critics && action_scale && action_bias && eps && alpha && grads && actor_loss_out && batch_inds && env_inds,
+                  MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(slots > 0 && n_envs > 0, MI355PPO_EINVAL, "%s: slots=%lld n_envs=%d must be positive", fn, (long long)slots, n_envs);
+    if (int rc = op_shape_cpu(fn, M, O, A)) return rc;
+    const int K = O + A, G = op_groups(M), ntiles = op_tiles(M);
+    const int64_t Pa = sac_actor_count(O, A), Pq = op_critic_count(O, A);
+    const SacNet an = sac_net(actor, O, A);
+    const SacOff off = sac_off(O, A);
+    const float inv_m = (float)(1.0 / (double)M), al = alpha[0];
+    const float one[kOpRows] = {1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f};
+    std::vector<float> part((size_t)G * Pa), rows(M);
+    OpTile T;
+    SacTileH S;
+    for (int tl = 0; tl < ntiles; ++tl) {
+        const int g = tl % G, r0 = tl * kOpRows, nr = (M - r0 < kOpRows) ? M - r0 : kOpRows;
+        const bool first = tl == g;
+        float* p = part.data() + (int64_t)g * Pa;
+        for (int r = 0; r < kOpRows; ++r) {
+            const int64_t row = r < nr ? op_row_cpu(batch_inds, env_inds, r0 + r, slots, n_envs) : 0;
+            for (int k = 0; k < O; ++k) T.x[r * kOpXSh + k] = r < nr ? ring_obs[row * O + k] : 0.0f;
+        }
+        sac_policy_host(an, action_scale, action_bias, eps, r0, M, T, S);
+        for (int c = 0; c < 2; ++c) {
+            const OpNet qn = op_net(critics + c * Pq, K, 1);
+            op_fwd_host<true>(T.x.data(), kOpXSh, K, qn.w1, qn.b1, T.c1.data(), kOpH);
+            op_fwd_host<true>(T.c1.data(), kOpH, kOpH, qn.w2, qn.b2, T.c2.data(), kOpH);
+            op_head_host(T.c2.data(), kOpH, qn.w3, qn.b3, 1, T.qv + c * kOpRows);
+            op_dgrad_host(one, 1, 1, qn.w3, kOpH, T.c2.data(), kOpH);
+            op_dgrad_host(T.c2.data(), kOpH, kOpH, qn.w2, kOpH, T.c1.data(), kOpH);
+            float* gq = c == 0 ? S.g1 : S.g2;
+            for (int r = 0; r < kOpRows; ++r)
+                for (int a = 0; a < A; ++a) {
+                    float acc = 0.0f;
+                    for (int j = 0; j < kOpH; ++j) acc = op_mac(acc, T.c1[r * kOpH + j], qn.w1[(int64_t)j * K + O + a]);
+                    gq[r * A + a] = acc;
+                }
+        }
+        for (int r = 0; r < kOpRows; ++r) {
+            const float q1 = T.qv[r], q2 = T.qv[kOpRows + r];
+            if (r < nr) {
+                rows[r0 + r] = sac_actor_row(al, S.lpr[r], q1, q2);
+                if (log_pi_out) log_pi_out[r0 + r] = S.lpr[r];
+            }
+            for (int a = 0; a < A; ++a) {
+                const int t = r * A + a;
+                float dm = 0.0f, du = 0.0f;
+                if (r < nr) {
+                    const float dact = (-inv_m) * (sac_min_w(q1, q2) * S.g1[t] + sac_min_w(q2, q1) * S.g2[t]);
+                    SacElem e;
+                    e.y = S.y[t];
+                    e.std = S.std[t];
+                    e.th = S.th[t];
+                    e.arg = S.arg[t];
+                    e.action = 0.0f;
+                    e.lp = 0.0f;
+                    sac_elem_bwd(e, eps[(int64_t)(r0 + r) * A + a], action_scale[a], dact, al * inv_m, &dm, &du);
+                    if (dmean_out) dmean_out[(int64_t)(r0 + r) * A + a] = dm;
+                    if (du_out) du_out[(int64_t)(r0 + r) * A + a] = du;
+                }
+                S.mu[t] = dm;
+                S.us[t] = du;
+            }
+        }
+        op_wgrad_host(S.mu, A, T.a2.data(), kOpH, A, kOpH, p + off.wm, p + off.bm, first, nr);
+        op_wgrad_host(S.us, A, T.a2.data(), kOpH, A, kOpH, p + off.ws, p + off.bs, first, nr);
+        sac_dgrad2_host(S.mu, an.wm, S.us, an.ws, A, T.a2.data());
+        op_wgrad_host(T.a2.data(), kOpH, T.a1.data(), kOpH, kOpH, kOpH, p + off.w2, p + off.b2, first, nr);
+        op_dgrad_host(T.a2.data(), kOpH, kOpH, an.w2, kOpH, T.a1.data(), kOpH);
+        op_wgrad_host(T.a1.data(), kOpH, T.x.data(), kOpXSh, kOpH, O, p + off.w1, p + off.b1, first, nr);
+    }
+    op_fold_host(part.data(), G, Pa, grads);
+    *actor_loss_out = 1.0f * op_fold_mean_host(rows.data(), M);
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_sac_alpha_f32_cpu(const float* log_pi, int M, double target_entropy, float* log_alpha, float* exp_avg,
+                                                      float* exp_avg_sq, double lr, double beta1, double beta2, double eps, int64_t step,
+                                                      float* alpha_out, float* alpha_loss_out) {
+    const char* fn = "mi355ppo_sac_alpha_f32_cpu";
+    MI355_REQUIRE(log_pi && log_alpha && exp_avg && exp_avg_sq && alpha_out && alpha_loss_out, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(M > 0 && step >= 1, MI355PPO_EINVAL, "%s: rows=%d must be > 0 and step=%lld >= 1", fn, M, (long long)step);
+    AdamParams P;
+    P.scale = 1.0f;
+    P.max_norm = 0.0f;
+    P.w1 = (float)(1.0 - beta1);
+    P.beta2 = (float)beta2;
+    P.w2 = (float)(1.0 - beta2);
+    float sc[2];
+    mi355ppo_adam_schedule_f32(lr, beta1, beta2, step, sc);
+    P.neg_step = sc[0];
+    P.bc2_sqrt = sc[1];
+    P.eps = (float)eps;
+    P.nblocks = 0;
+    P.zero_grads = 1;
+    const float te = (float)target_entropy;
+    double tot = 0.0;
+    for (int t = 0; t < kOpFold; ++t) {
+        double s = 0.0;
+        for (int k = t; k < M; k += kOpFold) s += (double)(log_pi[k] + te);
+        tot += s;
+    }
+    float la = log_alpha[0], m = exp_avg[0], v = exp_avg_sq[0];
+    const float loss = sac_alpha_loss(op_exp(la), tot / (double)M);
+    float gr = loss;
+    adam_elem(la, gr, m, v, 1.0f, P);
+    log_alpha[0] = la;
+    exp_avg[0] = m;
+    exp_avg_sq[0] = v;
+    alpha_out[0] = op_exp(la);
+    alpha_loss_out[0] = loss;
     return MI355PPO_OK;
 }

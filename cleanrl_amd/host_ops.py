@@ -17,7 +17,7 @@ import ctypes
 import torch
 
 from . import _lib
-from .ops import IMPALA_CHANNELS, _lstm_dims, _ptr_array, offpolicy_counts, pqn_param_count, radam_schedule, trxl_dims  # noqa: F401  (one definition for both modules)
+from .ops import IMPALA_CHANNELS, _lstm_dims, _ptr_array, offpolicy_counts, pqn_param_count, radam_schedule, sac_actor_count, trxl_dims  # noqa: F401  (one definition for both modules)
 
 LOSS_SCALARS = 7
 
@@ -507,3 +507,70 @@ def polyak_(params, target_params, tau):
     _lib.call("mi355ppo_polyak_f32_cpu", _in(params, torch.float32, (n,), "params"), _out(target_params, torch.float32, n, "target_params"),
               n, float(tau))
     return target_params
+
+
+# ------------------------------------------------------------------------------------------- SAC twins (csrc/sac.hip)
+def sac_exp_log(x):
+    """The library's own exp and log (csrc/sac_rows.h) on a float32 CPU tensor -> (exp, log)."""
+    x = _f32(x).reshape(-1)
+    e, l = torch.empty_like(x), torch.empty_like(x)
+    _lib.call("mi355ppo_sac_exp_log_f32_cpu", _p(x), _p(e), _p(l), x.numel())
+    return e, l
+
+
+def sac_policy(obs, actor, action_scale, action_bias, eps, actions_out=None, log_pi_out=None, batch_inds=None, env_inds=None):
+    rows, A = eps.shape
+    if batch_inds is None:
+        slots, N, O = 0, 0, obs.shape[-1]
+        op, bi, ei = _in(obs, torch.float32, (rows, O), "obs"), None, None
+    else:
+        slots, N, O = obs.shape
+        op = _in(obs, torch.float32, (slots, N, O), "obs")
+        bi, ei = _in(batch_inds, torch.int64, (rows,), "batch_inds"), _in(env_inds, torch.int64, (rows,), "env_inds")
+    _lib.call("mi355ppo_sac_policy_f32_cpu", op, bi, ei, slots, N, _in(actor, torch.float32, (sac_actor_count(O, A),), "actor"),
+              _in(action_scale, torch.float32, (A,), "action_scale"), _in(action_bias, torch.float32, (A,), "action_bias"),
+              _in(eps, torch.float32, (rows, A), "eps"), _out(actions_out, torch.float32, rows * A, "actions_out"),
+              _out(log_pi_out, torch.float32, rows, "log_pi_out"), rows, O, A)
+    return actions_out, log_pi_out
+
+
+def sac_target(ring, batch_inds, env_inds, actor, target_critics, action_scale, action_bias, eps, alpha, gamma, next_q_value,
+               next_actions_out=None, log_pi_out=None):
+    slots, N, O, A, rp = _ring_dims(ring)
+    (M,) = batch_inds.shape
+    _lib.call("mi355ppo_sac_target_f32_cpu", rp[1], rp[3], rp[4], _in(batch_inds, torch.int64, (M,), "batch_inds"),
+              _in(env_inds, torch.int64, (M,), "env_inds"), slots, N, _in(actor, torch.float32, (sac_actor_count(O, A),), "actor"),
+              _in(target_critics, torch.float32, (2 * offpolicy_counts(O, A)[1],), "target_critics"),
+              _in(action_scale, torch.float32, (A,), "action_scale"), _in(action_bias, torch.float32, (A,), "action_bias"),
+              _in(eps, torch.float32, (M, A), "eps"), _in(alpha, torch.float32, (1,), "alpha"), float(gamma),
+              _out(next_q_value, torch.float32, M, "next_q_value"), _out(next_actions_out, torch.float32, M * A, "next_actions_out"),
+              _out(log_pi_out, torch.float32, M, "log_pi_out"), M, O, A)
+    return next_q_value
+
+
+def sac_actor_fwd_bwd(ring, batch_inds, env_inds, actor, critics, action_scale, action_bias, eps, alpha, grads, actor_loss,
+                      log_pi_out=None, dmean_out=None, du_out=None):
+    slots, N, O, A, rp = _ring_dims(ring)
+    (M,) = batch_inds.shape
+    pa = sac_actor_count(O, A)
+    _lib.call("mi355ppo_sac_actor_fwd_bwd_f32_cpu", rp[0], _in(batch_inds, torch.int64, (M,), "batch_inds"),
+              _in(env_inds, torch.int64, (M,), "env_inds"), slots, N, _in(actor, torch.float32, (pa,), "actor"),
+              _in(critics, torch.float32, (2 * offpolicy_counts(O, A)[1],), "critics"), _in(action_scale, torch.float32, (A,), "action_scale"),
+              _in(action_bias, torch.float32, (A,), "action_bias"), _in(eps, torch.float32, (M, A), "eps"),
+              _in(alpha, torch.float32, (1,), "alpha"), _out(grads, torch.float32, pa, "grads"), _out(actor_loss, torch.float32, 1, "actor_loss"),
+              _out(log_pi_out, torch.float32, M, "log_pi_out"), _out(dmean_out, torch.float32, M * A, "dmean_out"),
+              _out(du_out, torch.float32, M * A, "du_out"), M, O, A)
+    return actor_loss
+
+
+def sac_alpha_(log_pi, target_entropy, log_alpha, exp_avg, exp_avg_sq, step, lr, alpha_out, alpha_loss_out, sched2=None, beta1=0.9,
+               beta2=0.999, eps=1e-8):
+    """The twin takes the Adam step count by value; ``sched2`` (the device path's schedule in device memory) is refused."""
+    if sched2 is not None:
+        raise ValueError("sac_alpha_: the host twin takes `step` and `lr`; a schedule tensor is the device path's (cleanrl_amd.ops)")
+    (M,) = log_pi.shape
+    _lib.call("mi355ppo_sac_alpha_f32_cpu", _in(log_pi, torch.float32, (M,), "log_pi"), M, float(target_entropy),
+              _out(log_alpha, torch.float32, 1, "log_alpha"), _out(exp_avg, torch.float32, 1, "exp_avg"),
+              _out(exp_avg_sq, torch.float32, 1, "exp_avg_sq"), float(lr), float(beta1), float(beta2), float(eps), int(step),
+              _out(alpha_out, torch.float32, 1, "alpha_out"), _out(alpha_loss_out, torch.float32, 1, "alpha_loss_out"))
+    return alpha_out

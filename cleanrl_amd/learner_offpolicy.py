@@ -82,7 +82,76 @@ def advance(ring):
         ring.full, ring.pos = True, 0
 
 
-class OffPolicyLearner:
+class DeviceRing:
+    """The part of a ``fused`` learner that is the replay ring: the five device arrays, the pinned staging of a step's transitions,
+    indices and observations, ``store`` and ``sample_indices``.  The learner sets ``device``, ``fused``, ``g`` (``ops.twins``),
+    ``N`` / ``O`` / ``A``, ``slots``, ``pos`` / ``full`` and, on ``torch``, ``rb`` (a ``HostReplayBuffer``) before it calls
+    ``_alloc_ring``.  Shared by ``OffPolicyLearner`` and ``learner_sac.SACLearner``."""
+
+    def _alloc_ring(self, M: int):
+        dev, N, O, A = self.device, self.N, self.O, self.A
+        self.ring = (torch.zeros((self.slots, N, O), device=dev), torch.zeros((self.slots, N, O), device=dev),
+                     torch.zeros((self.slots, N, A), device=dev), torch.zeros((self.slots, N), device=dev),
+                     torch.zeros((self.slots, N), device=dev))
+        pin = dev.type == "cuda"
+        width = 2 * O + A + 2
+        self._stage_host = torch.zeros(N * width, dtype=torch.float32)
+        self._idx_host = torch.zeros((2, M), dtype=torch.int64)
+        self._obs_host = torch.zeros((N, O), dtype=torch.float32)
+        if pin:                                                  # the step's data and draws reach the device through pinned staging
+            self._stage_host, self._idx_host, self._obs_host = (t.pin_memory() for t in (self._stage_host, self._idx_host, self._obs_host))
+        self._stage = torch.zeros(N * width, dtype=torch.float32, device=dev)
+        self._idx = torch.zeros((2, M), dtype=torch.int64, device=dev)
+        self._obs = torch.zeros((N, O), dtype=torch.float32, device=dev)
+        self._act = torch.zeros((N, A), dtype=torch.float32, device=dev)
+
+    def _stage_obs(self, obs):
+        """The rollout's observations (N, O) where the action kernel reads them."""
+        self._obs_host.copy_(torch.from_numpy(np.ascontiguousarray(obs, np.float32)).reshape(self.N, self.O))
+        if self.device.type != "cuda":
+            return self._obs_host
+        self._obs.copy_(self._obs_host, non_blocking=True)
+        return self._obs
+
+    def _stage_indices(self, bi, ei):
+        """The batch's (batch_inds, env_inds) as two int64 rows on the learner's device."""
+        self._idx_host[0].copy_(torch.from_numpy(np.asarray(bi, np.int64)))
+        self._idx_host[1].copy_(torch.from_numpy(np.asarray(ei, np.int64)))
+        if self.device.type != "cuda":
+            return self._idx_host
+        self._idx.copy_(self._idx_host, non_blocking=True)
+        return self._idx
+
+    def store(self, obs, real_next_obs, actions, rewards, terminations):
+        """``rb.add(obs, real_next_obs, actions, rewards, terminations, infos)``."""
+        if not self.fused:
+            self.rb.add(obs, real_next_obs, actions, rewards, terminations)
+            self.pos, self.full = self.rb.pos, self.rb.full
+            return
+        N, O, A = self.N, self.O, self.A
+        h = self._stage_host
+        parts, off = [], 0
+        for src, n in ((obs, N * O), (real_next_obs, N * O), (actions, N * A), (rewards, N), (terminations, N)):
+            h[off:off + n].copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(src).reshape(-1).astype(np.float32))))
+            parts.append((off, n))
+            off += n
+        buf = h
+        if self.device.type == "cuda":
+            self._stage.copy_(h, non_blocking=True)
+            buf = self._stage
+        v = [buf[o:o + n] for o, n in parts]
+        self.g.replay_add(self.ring, self.pos, v[0].view(N, O), v[1].view(N, O), v[2].view(N, A), v[3], v[4])
+        advance(self)
+
+    def sample_indices(self, batch_size: int):
+        """``ReplayBuffer.sample`` / ``_get_samples``: ``batch_inds`` and then ``env_indices`` from ``np.random``."""
+        upper_bound = self.slots if self.full else self.pos
+        batch_inds = np.random.randint(0, upper_bound, size=batch_size)
+        env_indices = np.random.randint(0, high=self.N, size=(len(batch_inds),))
+        return batch_inds, env_indices
+
+
+class OffPolicyLearner(DeviceRing):
     """``qfs`` / ``qf_targets``: one network (DDPG) or two (TD3).  ``td3``: target policy smoothing and the delayed update."""
 
     def __init__(self, actor, qfs, target_actor, qf_targets, args, envs, device, td3: bool, backend=None):
@@ -132,21 +201,8 @@ class OffPolicyLearner:
         self.scale = actor.action_scale.detach().reshape(-1).to(dev).contiguous()
         self.bias = actor.action_bias.detach().reshape(-1).to(dev).contiguous()
         self.low_t, self.high_t = torch.from_numpy(self.low.copy()).to(dev), torch.from_numpy(self.high.copy()).to(dev)
-        self.ring = (torch.zeros((self.slots, N, O), device=dev), torch.zeros((self.slots, N, O), device=dev),
-                     torch.zeros((self.slots, N, A), device=dev), torch.zeros((self.slots, N), device=dev),
-                     torch.zeros((self.slots, N), device=dev))
         M = int(args.batch_size)
-        pin = dev.type == "cuda"
-        width = 2 * O + A + 2
-        self._stage_host = torch.zeros(N * width, dtype=torch.float32)
-        self._idx_host = torch.zeros((2, M), dtype=torch.int64)
-        self._obs_host = torch.zeros((N, O), dtype=torch.float32)
-        if pin:                                                  # the step's data and draws reach the device through pinned staging
-            self._stage_host, self._idx_host, self._obs_host = (t.pin_memory() for t in (self._stage_host, self._idx_host, self._obs_host))
-        self._stage = torch.zeros(N * width, dtype=torch.float32, device=dev)
-        self._idx = torch.zeros((2, M), dtype=torch.int64, device=dev)
-        self._obs = torch.zeros((N, O), dtype=torch.float32, device=dev)
-        self._act = torch.zeros((N, A), dtype=torch.float32, device=dev)
+        self._alloc_ring(M)
         self._y = torch.zeros(M, dtype=torch.float32, device=dev)
         self._qsc = torch.zeros(2 * self.ncrit, dtype=torch.float32, device=dev)
         self._asc = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -172,42 +228,9 @@ class OffPolicyLearner:
                 actions += torch.normal(0, self.actor.action_scale * a.exploration_noise)
                 return actions.cpu().numpy().clip(self.space.low, self.space.high)
             noise = torch.normal(0, self.actor.action_scale * a.exploration_noise).reshape(-1)
-            self._obs_host.copy_(torch.from_numpy(np.ascontiguousarray(obs, np.float32)).reshape(self.N, self.O))
-            x = self._obs_host
-            if self.device.type == "cuda":
-                self._obs.copy_(self._obs_host, non_blocking=True)
-                x = self._obs
-            self.g.ddpg_act(x, self._seg(self.online, "actor"), self.scale, self.bias, noise, self.low_t, self.high_t, self._act)
+            self.g.ddpg_act(self._stage_obs(obs), self._seg(self.online, "actor"), self.scale, self.bias, noise, self.low_t, self.high_t, self._act)
             out = self._act.cpu().numpy()
             return out if self.device.type == "cuda" else out.copy()      # on the CPU .cpu() aliases the reused buffer
-
-    def store(self, obs, real_next_obs, actions, rewards, terminations):
-        """``rb.add(obs, real_next_obs, actions, rewards, terminations, infos)``."""
-        if not self.fused:
-            self.rb.add(obs, real_next_obs, actions, rewards, terminations)
-            self.pos, self.full = self.rb.pos, self.rb.full
-            return
-        N, O, A = self.N, self.O, self.A
-        h = self._stage_host
-        parts, off = [], 0
-        for src, n in ((obs, N * O), (real_next_obs, N * O), (actions, N * A), (rewards, N), (terminations, N)):
-            h[off:off + n].copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(src).reshape(-1).astype(np.float32))))
-            parts.append((off, n))
-            off += n
-        buf = h
-        if self.device.type == "cuda":
-            self._stage.copy_(h, non_blocking=True)
-            buf = self._stage
-        v = [buf[o:o + n] for o, n in parts]
-        self.g.replay_add(self.ring, self.pos, v[0].view(N, O), v[1].view(N, O), v[2].view(N, A), v[3], v[4])
-        advance(self)
-
-    def sample_indices(self, batch_size: int):
-        """``ReplayBuffer.sample`` / ``_get_samples``: ``batch_inds`` and then ``env_indices`` from ``np.random``."""
-        upper_bound = self.slots if self.full else self.pos
-        batch_inds = np.random.randint(0, upper_bound, size=batch_size)
-        env_indices = np.random.randint(0, high=self.N, size=(len(batch_inds),))
-        return batch_inds, env_indices
 
     # ------------------------------------------------------------------ training
     def train_step(self, policy_update: bool, indices=None, noise=None):
@@ -220,12 +243,7 @@ class OffPolicyLearner:
         dev = self.device
         if self.td3 and noise is None:
             noise = torch.randn((M, self.A), dtype=torch.float32, device=dev)     # torch.randn_like(data.actions)
-        self._idx_host[0].copy_(torch.from_numpy(np.asarray(bi, np.int64)))
-        self._idx_host[1].copy_(torch.from_numpy(np.asarray(ei, np.int64)))
-        idx = self._idx_host
-        if dev.type == "cuda":
-            self._idx.copy_(self._idx_host, non_blocking=True)
-            idx = self._idx
+        idx = self._stage_indices(bi, ei)
         self.update_kernels(idx[0], idx[1], noise, policy_update)
         self.last = ("fused", policy_update)
         return self

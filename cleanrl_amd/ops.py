@@ -27,7 +27,7 @@ __all__ = [
     "ImpalaTrunk", "impala_trunk", "impala_param_shapes", "trxl_attn_forward", "trxl_attn_backward", "TrXLMemoryAttention", "trxl_memory_attention",
     "pqn_param_count", "pqn_egreedy", "pqn_qlambda", "pqn_td_loss", "pqn_mlp_forward", "pqn_mlp_act", "pqn_mlp_td_fwd_bwd", "radam_schedule",
     "clip_radam_", "clip_radam_sched_", "pqn_lstm_act", "pqn_lstm_td_fwd_bwd", "offpolicy_counts", "replay_add", "ddpg_act", "td3_target",
-    "td3_critic_fwd_bwd", "td3_actor_fwd_bwd", "polyak_",
+    "td3_critic_fwd_bwd", "td3_actor_fwd_bwd", "polyak_", "sac_actor_count", "sac_policy", "sac_target", "sac_actor_fwd_bwd", "sac_alpha_",
 ]
 
 LOSS_SCALAR_NAMES = ("loss", "pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac")
@@ -1407,3 +1407,100 @@ def polyak_(params, target_params, tau: float):
     _chk(target_params, torch.float32, "target_params", (n,))
     _launch("mi355ppo_polyak_f32", params.device, _ptr(params), _ptr(target_params), n, float(tau))
     return target_params
+
+
+# ------------------------------------------------------------------------------------------- SAC (csrc/sac.hip)
+def sac_actor_count(obs_dim: int, act_dim: int) -> int:
+    """Parameter count of sac_continuous_action.py's ``Actor`` (fc1, fc2, fc_mean, fc_logstd; hidden width 256)."""
+    h = OFFPOLICY_HIDDEN
+    return h * obs_dim + h + h * h + h + 2 * (act_dim * h + act_dim)
+
+
+def sac_policy(obs, actor, action_scale, action_bias, eps, actions_out=None, log_pi_out=None, batch_inds=None, env_inds=None):
+    """``actor.get_action`` forward in one launch.  ``obs`` is a dense (rows, O) array, or with ``batch_inds`` / ``env_inds`` a ring
+    array (slots, n_envs, O) gathered through them; ``eps`` (rows, A) is the standard normal draw."""
+    rows, A = eps.shape
+    _chk(eps, torch.float32, "eps", (rows, A))
+    if batch_inds is None:
+        slots, N, O = 0, 0, obs.shape[-1]
+        _chk(obs, torch.float32, "obs", (rows, O))
+    else:
+        slots, N, O = obs.shape
+        _chk(obs, torch.float32, "obs", (slots, N, O))
+        assert _batch_inds(batch_inds, env_inds) == rows
+    _chk(actor, torch.float32, "actor", (sac_actor_count(O, A),))
+    _chk(action_scale, torch.float32, "action_scale", (A,))
+    _chk(action_bias, torch.float32, "action_bias", (A,))
+    if actions_out is not None:
+        _chk(actions_out, torch.float32, "actions_out", (rows, A))
+    if log_pi_out is not None:
+        _chk(log_pi_out, torch.float32, "log_pi_out", (rows,))
+    _launch("mi355ppo_sac_policy_f32", eps.device, _ptr(obs), _ptr(batch_inds), _ptr(env_inds), slots, N, _ptr(actor), _ptr(action_scale),
+            _ptr(action_bias), _ptr(eps), _ptr(actions_out), _ptr(log_pi_out), rows, O, A)
+    return actions_out, log_pi_out
+
+
+def sac_target(ring, batch_inds, env_inds, actor, target_critics, action_scale, action_bias, eps, alpha, gamma: float, next_q_value,
+               next_actions_out=None, log_pi_out=None):
+    """The ``with torch.no_grad()`` block of SAC's training step in one launch -> next_q_value (M,).  ``alpha``: one device float."""
+    slots, N, O, A = _ring_dims(ring)
+    M = _batch_inds(batch_inds, env_inds)
+    _chk(actor, torch.float32, "actor", (sac_actor_count(O, A),))
+    _chk(target_critics, torch.float32, "target_critics", (2 * offpolicy_counts(O, A)[1],))
+    _chk(action_scale, torch.float32, "action_scale", (A,))
+    _chk(action_bias, torch.float32, "action_bias", (A,))
+    _chk(eps, torch.float32, "eps", (M, A))
+    _chk(alpha, torch.float32, "alpha", (1,))
+    _chk(next_q_value, torch.float32, "next_q_value", (M,))
+    if next_actions_out is not None:
+        _chk(next_actions_out, torch.float32, "next_actions_out", (M, A))
+    if log_pi_out is not None:
+        _chk(log_pi_out, torch.float32, "log_pi_out", (M,))
+    _launch("mi355ppo_sac_target_f32", batch_inds.device, _ptr(ring[1]), _ptr(ring[3]), _ptr(ring[4]), _ptr(batch_inds), _ptr(env_inds), slots,
+            N, _ptr(actor), _ptr(target_critics), _ptr(action_scale), _ptr(action_bias), _ptr(eps), _ptr(alpha), float(gamma),
+            _ptr(next_q_value), _ptr(next_actions_out), _ptr(log_pi_out), M, O, A)
+    return next_q_value
+
+
+def sac_actor_fwd_bwd(ring, batch_inds, env_inds, actor, critics, action_scale, action_bias, eps, alpha, grads, actor_loss,
+                      log_pi_out=None, dmean_out=None, du_out=None):
+    """``actor_loss = ((alpha * log_pi) - min(qf1_pi, qf2_pi)).mean()`` and its gradient w.r.t. the actor in two launches.
+    OVERWRITES ``grads``."""
+    slots, N, O, A = _ring_dims(ring)
+    M = _batch_inds(batch_inds, env_inds)
+    pa = sac_actor_count(O, A)
+    _chk(actor, torch.float32, "actor", (pa,))
+    _chk(critics, torch.float32, "critics", (2 * offpolicy_counts(O, A)[1],))
+    _chk(action_scale, torch.float32, "action_scale", (A,))
+    _chk(action_bias, torch.float32, "action_bias", (A,))
+    _chk(eps, torch.float32, "eps", (M, A))
+    _chk(alpha, torch.float32, "alpha", (1,))
+    _chk(grads, torch.float32, "grads", (pa,))
+    _chk(actor_loss, torch.float32, "actor_loss", (1,))
+    if log_pi_out is not None:
+        _chk(log_pi_out, torch.float32, "log_pi_out", (M,))
+    for t, nm in ((dmean_out, "dmean_out"), (du_out, "du_out")):
+        if t is not None:
+            _chk(t, torch.float32, nm, (M, A))
+    dev = batch_inds.device
+    ws = _workspace(dev, _lib.load().mi355ppo_sac_actor_workspace_bytes(M, O, A))
+    _launch("mi355ppo_sac_actor_fwd_bwd_f32", dev, _ptr(ring[0]), _ptr(batch_inds), _ptr(env_inds), slots, N, _ptr(actor), _ptr(critics),
+            _ptr(action_scale), _ptr(action_bias), _ptr(eps), _ptr(alpha), _ptr(grads), _ptr(actor_loss), _ptr(log_pi_out), _ptr(dmean_out),
+            _ptr(du_out), M, O, A, _ptr(ws), ws.numel())
+    return actor_loss
+
+
+def sac_alpha_(log_pi, target_entropy: float, log_alpha, exp_avg, exp_avg_sq, step: int, lr: float, alpha_out, alpha_loss_out, sched2=None,
+               beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8):
+    """``alpha_loss``, its gradient and the Adam step on ``log_alpha`` in one launch; writes ``alpha_out = exp(log_alpha)``.  With
+    ``sched2`` (2 device floats, ``adam_schedule`` values) the step is read from device memory: capturable."""
+    (M,) = log_pi.shape
+    _chk(log_pi, torch.float32, "log_pi", (M,))
+    for t, nm in ((log_alpha, "log_alpha"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq"), (alpha_out, "alpha_out"),
+                  (alpha_loss_out, "alpha_loss_out")):
+        _chk(t, torch.float32, nm, (1,))
+    if sched2 is not None:
+        _chk(sched2, torch.float32, "sched2", (2,))
+    _launch("mi355ppo_sac_alpha_f32", log_pi.device, _ptr(log_pi), M, float(target_entropy), _ptr(log_alpha), _ptr(exp_avg), _ptr(exp_avg_sq),
+            float(lr), float(beta1), float(beta2), float(eps), int(step), _ptr(sched2), _ptr(alpha_out), _ptr(alpha_loss_out))
+    return alpha_out

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MI355PPO_VERSION 270 /* major*100 + minor*10 + patch.  The minor moves whenever an exported signature changes or an entry
+#define MI355PPO_VERSION 271 /* major*100 + minor*10 + patch.  The minor moves whenever an exported signature changes or an entry
                                   point is added (1.1: adv_mean_den / conv1_variant arguments of round 2; 1.2, 1.3: round 3;
                                   1.4: the *_cpu host-pointer twins; 1.5: mi355ppo_init; 1.6: round 4 -- the fused MLP family K7,
                                   mi355ppo_clip_adam_sched_f32; 1.7: mi355ppo_fc_heads_act_categorical_f32, mi355ppo_nature_packs_f32,
@@ -44,6 +44,10 @@ extern "C" {
                                   2.4: the IMPALA-CNN trunk mi355ppo_impala_* (forward, backward, max pool, sizes) and the *_cpu twins;
                                   2.5: PQN -- mi355ppo_pqn_* (e-greedy, Q(lambda), TD loss, the LayerNorm MLP), clip + RAdam, the *_cpu twins;
                                   2.6: the recurrent PQN tail mi355ppo_pqn_lstm_act_f32, mi355ppo_pqn_lstm_td_fwd_bwd_f32 (+ workspace size) and their *_cpu twins);
+                                  2.7: DDPG / TD3 -- the device replay ring and mi355ppo_td3_* / mi355ppo_polyak_f32 and their *_cpu twins;
+                                  2.7.1: SAC -- mi355ppo_sac_* (policy, target, actor, alpha) and their *_cpu twins.  Entry points were only
+                                  added and no existing signature moved, so a 2.7 binding keeps working against this library: the patch
+                                  moves, the minor stays;
                                   a binding must check major AND minor (cleanrl_amd/_lib.py does) */
 
 #if defined(__GNUC__)
@@ -996,6 +1000,63 @@ MI355PPO_API int mi355ppo_td3_actor_fwd_bwd_f32_cpu(const float* ring_obs, const
  * grad_scale = 1 and max_grad_norm = +inf (coefficient min(inf, 1) = exactly 1) and eps = 1e-8. */
 MI355PPO_API int mi355ppo_polyak_f32(const float* params, float* target_params, int64_t n, double tau, void* stream);
 MI355PPO_API int mi355ppo_polyak_f32_cpu(const float* params, float* target_params, int64_t n, double tau);
+
+/* ---- SAC (ABI 2.7.1, csrc/sac.hip; reference: cleanrl/sac_continuous_action.py) ----
+ * The critics are the QNetwork of the section above.  The actor is Linear(obs_dim, 256) - ReLU - Linear(256, 256) - ReLU and two heads
+ * Linear(256, act_dim), flat in .parameters() order: fc1.w, fc1.b, fc2.w, fc2.b, fc_mean.w, fc_mean.b, fc_logstd.w, fc_logstd.b.
+ * get_action(obs, eps): log_std = -5 + 3.5 * (tanh(u) + 1), x = mean + exp(log_std) * eps, y = tanh(x), action = y * action_scale +
+ * action_bias, log_pi = sum_a [Normal(mean, std).log_prob(x) - log(action_scale * (1 - y^2) + 1e-6)]; eps (rows, act_dim) is the
+ * caller's standard normal draw.  exp, log and tanh are the library's own (csrc/sac_rows.h), identical on host and device.  alpha is
+ * read from one float in device memory (host memory for the twins).  Limits, ring, indices and the twins' bit equality as above.
+ *
+ * policy: get_action forward.  batch_inds / env_inds both NULL: obs is a dense (rows, obs_dim) array; both given: obs is a ring array
+ * gathered through them.  actions_out (rows, act_dim) and log_pi_out (rows) may be NULL, not both.  One launch. */
+MI355PPO_API int mi355ppo_sac_policy_f32(const float* obs, const int64_t* batch_inds, const int64_t* env_inds, int64_t slots, int n_envs,
+                                         const float* actor, const float* action_scale, const float* action_bias, const float* eps,
+                                         float* actions_out, float* log_pi_out, int rows, int O, int A, void* stream);
+MI355PPO_API int mi355ppo_sac_policy_f32_cpu(const float* obs, const int64_t* batch_inds, const int64_t* env_inds, int64_t slots, int n_envs,
+                                             const float* actor, const float* action_scale, const float* action_bias, const float* eps,
+                                             float* actions_out, float* log_pi_out, int rows, int O, int A);
+/* target: next_q_value (M) = rewards + (1 - dones) * gamma * (min(q1', q2') - alpha * log_pi'), (a', log_pi') = get_action of the ONLINE
+ * actor on next_obs, q_c' the two target critics (back to back) on (next_obs, a').  next_actions_out (M, A) and log_pi_out (M) may be
+ * NULL.  One launch. */
+MI355PPO_API int mi355ppo_sac_target_f32(const float* ring_next_obs, const float* ring_rewards, const float* ring_dones,
+                                         const int64_t* batch_inds, const int64_t* env_inds, int64_t slots, int n_envs, const float* actor,
+                                         const float* target_critics, const float* action_scale, const float* action_bias, const float* eps,
+                                         const float* alpha, double gamma, float* next_q_value, float* next_actions_out, float* log_pi_out,
+                                         int M, int O, int A, void* stream);
+MI355PPO_API int mi355ppo_sac_target_f32_cpu(const float* ring_next_obs, const float* ring_rewards, const float* ring_dones,
+                                             const int64_t* batch_inds, const int64_t* env_inds, int64_t slots, int n_envs,
+                                             const float* actor, const float* target_critics, const float* action_scale,
+                                             const float* action_bias, const float* eps, const float* alpha, double gamma,
+                                             float* next_q_value, float* next_actions_out, float* log_pi_out, int M, int O, int A);
+/* actor: actor_loss = mean(alpha * log_pi - min(qf1(obs, pi), qf2(obs, pi))), (pi, log_pi) = get_action(obs, eps); critics holds the two
+ * online critics back to back and gets no gradient.  grads (actor parameters) is OVERWRITTEN.  torch.min's backward: 1 to the smaller
+ * q, 0.5 to each on a tie.  log_pi_out (M), dmean_out and du_out (M, A: d loss / d fc_mean's and fc_logstd's outputs) may be NULL.
+ * Two launches. */
+MI355PPO_API size_t mi355ppo_sac_actor_workspace_bytes(int M, int O, int A);
+MI355PPO_API int mi355ppo_sac_actor_fwd_bwd_f32(const float* ring_obs, const int64_t* batch_inds, const int64_t* env_inds, int64_t slots,
+                                                int n_envs, const float* actor, const float* critics, const float* action_scale,
+                                                const float* action_bias, const float* eps, const float* alpha, float* grads,
+                                                float* actor_loss_out, float* log_pi_out, float* dmean_out, float* du_out, int M, int O,
+                                                int A, void* workspace, size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_sac_actor_fwd_bwd_f32_cpu(const float* ring_obs, const int64_t* batch_inds, const int64_t* env_inds,
+                                                    int64_t slots, int n_envs, const float* actor, const float* critics,
+                                                    const float* action_scale, const float* action_bias, const float* eps,
+                                                    const float* alpha, float* grads, float* actor_loss_out, float* log_pi_out,
+                                                    float* dmean_out, float* du_out, int M, int O, int A);
+/* alpha: alpha_loss = mean(-exp(log_alpha) * (log_pi + target_entropy)) (f64 fold), its gradient w.r.t. log_alpha (the same value) and
+ * one torch Adam step on that scalar; exp_avg / exp_avg_sq are its one-float moments.  sched2 NULL: the step size and bias correction
+ * are mi355ppo_adam_schedule_f32(lr, beta1, beta2, step); otherwise they are read from the two device floats sched2 (capturable) and
+ * lr / step are ignored.  Writes log_alpha, alpha_out = exp(log_alpha) and alpha_loss_out.  One launch of one workgroup. */
+MI355PPO_API int mi355ppo_sac_alpha_f32(const float* log_pi, int M, double target_entropy, float* log_alpha, float* exp_avg,
+                                        float* exp_avg_sq, double lr, double beta1, double beta2, double eps, int64_t step,
+                                        const float* sched2, float* alpha_out, float* alpha_loss_out, void* stream);
+MI355PPO_API int mi355ppo_sac_alpha_f32_cpu(const float* log_pi, int M, double target_entropy, float* log_alpha, float* exp_avg,
+                                            float* exp_avg_sq, double lr, double beta1, double beta2, double eps, int64_t step,
+                                            float* alpha_out, float* alpha_loss_out);
+/* the library's exp and log on host arrays (tests): exp_out[i] = exp(x[i]), log_out[i] = log(x[i]); either output may be NULL. */
+MI355PPO_API int mi355ppo_sac_exp_log_f32_cpu(const float* x, float* exp_out, float* log_out, int64_t n);
 
 #ifdef __cplusplus
 }

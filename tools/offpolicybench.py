@@ -1,6 +1,7 @@
-"""ddpg_continuous_action.py / td3_continuous_action.py with both ``MI355PPO_OFFPOLICY`` backends, in one process, alternating.
+"""ddpg_continuous_action.py / td3_continuous_action.py / sac_continuous_action.py with both ``MI355PPO_OFFPOLICY`` backends, in one
+process, alternating.
 
-    python tools/offpolicybench.py [--reps 20] [--scripts td3 ddpg]
+    python tools/offpolicybench.py [--reps 20] [--scripts td3 ddpg sac]
 
 Times, at each script's defaults (batch 256) on a HalfCheetah-shaped (obs 17 / act 6) and a Humanoid-shaped (376 / 17) task:
 one rollout step including the action's copy to the host, one critic-only training step and one step with the delayed policy
@@ -23,8 +24,9 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from cleanrl_amd import envs as E  # noqa: E402
-from cleanrl_amd.agents import ActionValueNetwork, Actor  # noqa: E402
+from cleanrl_amd.agents import ActionValueNetwork, Actor, SoftActor  # noqa: E402
 from cleanrl_amd.learner_offpolicy import OffPolicyLearner  # noqa: E402
+from cleanrl_amd.learner_sac import SACLearner  # noqa: E402
 
 SHAPES = {"halfcheetah": (17, 6), "humanoid": (376, 17)}
 
@@ -34,13 +36,22 @@ def make(script, O, A, backend, dev, fill=4096):
     torch.manual_seed(1)
     np.random.seed(1)
     envs = E.SyntheticReplayVecEnv(1, seed=1, obs_dim=O, act_dim=A)
+    if script == "sac":
+        qs = [ActionValueNetwork(envs).to(dev) for _ in range(4)]
+        qs[2].load_state_dict(qs[0].state_dict()), qs[3].load_state_dict(qs[1].state_dict())
+        args = SimpleNamespace(buffer_size=fill * 2, batch_size=256, q_lr=1e-3, policy_lr=3e-4, gamma=0.99, tau=0.005, learning_starts=0,
+                               policy_frequency=2, target_network_frequency=1, alpha=0.2, autotune=True)
+        return fill_ring(SACLearner(SoftActor(envs).to(dev), *qs, args, envs, dev, backend=backend), envs, fill)
     nets = [Actor(envs, batched_space=not td3).to(dev)] + [ActionValueNetwork(envs).to(dev) for _ in range(2 if td3 else 1)]
     tgts = [Actor(envs, batched_space=not td3).to(dev)] + [ActionValueNetwork(envs).to(dev) for _ in range(2 if td3 else 1)]
     for n, t in zip(nets, tgts):
         t.load_state_dict(n.state_dict())
     args = SimpleNamespace(buffer_size=fill * 2, batch_size=256, learning_rate=3e-4, gamma=0.99, tau=0.005, policy_noise=0.2, noise_clip=0.5,
                            exploration_noise=0.1, learning_starts=0)
-    L = OffPolicyLearner(nets[0], nets[1:], tgts[0], tgts[1:], args, envs, dev, td3=td3, backend=backend)
+    return fill_ring(OffPolicyLearner(nets[0], nets[1:], tgts[0], tgts[1:], args, envs, dev, td3=td3, backend=backend), envs, fill)
+
+
+def fill_ring(L, envs, fill):
     obs, _ = envs.reset(seed=1)
     for _ in range(fill):
         a = np.array([envs.single_action_space.sample()])
@@ -71,8 +82,9 @@ def main():
     for script in a.scripts:
         for shape, (O, A) in SHAPES.items():
             learners = {b: make(script, O, A, b, dev) for b in ("torch", "fused")}
-            legs = {"rollout_step": lambda L, obs: L.act(obs, 1), "critic_step": lambda L, obs: L.train_step(False),
-                    "policy_step": lambda L, obs: L.train_step(True)}
+            extra = (True,) if script == "sac" else ()          # SAC's target update runs every step (target_network_frequency 1)
+            legs = {"rollout_step": lambda L, obs: L.act(obs, 1), "critic_step": lambda L, obs: L.train_step(False, *extra),
+                    "policy_step": lambda L, obs: L.train_step(True, *extra)}
             times = {leg: {b: [] for b in learners} for leg in legs}
             for rep in range(a.warmup + a.reps):
                 for leg, fn in legs.items():
