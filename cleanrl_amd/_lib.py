@@ -221,6 +221,15 @@ SIGNATURES = {
     "mi355ppo_sac_alpha_f32": (c_int, [_P, c_int, c_double, _P, _P, _P] + [c_double] * 4 + [c_int64, _P, _P, _P, _P]),
     "mi355ppo_sac_alpha_f32_cpu": (c_int, [_P, c_int, c_double, _P, _P, _P] + [c_double] * 4 + [c_int64, _P, _P]),
     "mi355ppo_sac_exp_log_f32_cpu": (c_int, [_P, _P, _P, c_int64]),
+    # DQN / C51 (added under ABI 2.7.1, csrc/dqn.hip)
+    "mi355ppo_dqn_act_f32": (c_int, [_P] * 5 + [c_int] * 4 + [_P]),
+    "mi355ppo_dqn_act_f32_cpu": (c_int, [_P] * 5 + [c_int] * 4),
+    "mi355ppo_dqn_td_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mi355ppo_dqn_td_fwd_bwd_f32": (c_int, [_P] * 7 + [c_int64, c_int, _P, _P, c_double] + [_P] * 4 + [c_int] * 3 + [_P, c_size_t, _P]),
+    "mi355ppo_dqn_td_fwd_bwd_f32_cpu": (c_int, [_P] * 7 + [c_int64, c_int, _P, _P, c_double] + [_P] * 4 + [c_int] * 3),
+    "mi355ppo_c51_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "mi355ppo_c51_fwd_bwd_f32": (c_int, [_P] * 7 + [c_int64, c_int, _P, _P, _P] + [c_double] * 3 + [_P] * 4 + [c_int] * 4 + [_P, c_size_t, _P]),
+    "mi355ppo_c51_fwd_bwd_f32_cpu": (c_int, [_P] * 7 + [c_int64, c_int, _P, _P, _P] + [c_double] * 3 + [_P] * 4 + [c_int] * 4),
 }
 
 ABI_VERSION = 271       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)

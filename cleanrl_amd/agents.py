@@ -1265,3 +1265,48 @@ class SoftActor(nn.Module):
         log_prob = log_prob.sum(1, keepdim=True)
         mean = torch.tanh(mean) * self.action_scale + self.action_bias
         return action, log_prob, mean
+
+
+# ------------------------------------------------------------------------------------------- DQN / C51 (dqn.py, c51.py)
+class DQNNetwork(nn.Module):
+    """dqn.py's ``QNetwork`` (named apart from the PQN ``QNetwork`` above): Linear(obs, 120) -> ReLU -> Linear(120, 84) -> ReLU ->
+    Linear(84, n), torch's default initialisation in the reference's construction order, so a seed gives the reference's weights."""
+
+    def __init__(self, env):
+        super().__init__()
+        self.network = nn.Sequential(
+            nn.Linear(np.array(env.single_observation_space.shape).prod(), 120),
+            nn.ReLU(),
+            nn.Linear(120, 84),
+            nn.ReLU(),
+            nn.Linear(84, env.single_action_space.n),
+        )
+
+    def forward(self, x):
+        return self.network(x)
+
+
+class C51Network(nn.Module):
+    """c51.py's ``QNetwork``: the same trunk with ``n * n_atoms`` outputs, the ``atoms`` buffer and ``get_action``."""
+
+    def __init__(self, env, n_atoms=101, v_min=-100, v_max=100):
+        super().__init__()
+        self.env = env
+        self.n_atoms = n_atoms
+        self.register_buffer("atoms", torch.linspace(v_min, v_max, steps=n_atoms))
+        self.n = env.single_action_space.n
+        self.network = nn.Sequential(
+            nn.Linear(np.array(env.single_observation_space.shape).prod(), 120),
+            nn.ReLU(),
+            nn.Linear(120, 84),
+            nn.ReLU(),
+            nn.Linear(84, self.n * n_atoms),
+        )
+
+    def get_action(self, x, action=None):
+        logits = self.network(x)
+        pmfs = torch.softmax(logits.view(len(x), self.n, self.n_atoms), dim=2)
+        q_values = (pmfs * self.atoms).sum(2)
+        if action is None:
+            action = torch.argmax(q_values, 1)
+        return action, pmfs[torch.arange(len(x)), action]

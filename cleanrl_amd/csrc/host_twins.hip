@@ -21,6 +21,7 @@
 #include "pqn_rows.h"
 #include "pqn_lstm_rows.h"
 #include "offpolicy_rows.h"
+#include "dqn_rows.h"
 #include "sac_rows.h"
 
 #include <math.h>
@@ -1834,4 +1835,228 @@ extern "C" MI355PPO_API int mi355ppo_sac_alpha_f32_cpu(const float* log_pi, int 
     alpha_out[0] = op_exp(la);
     alpha_loss_out[0] = loss;
     return MI355PPO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ DQN / C51 (dqn.hip)
+// The device's element functions (dqn_rows.h over sac_rows.h / offpolicy_rows.h) in the device's orders: tiles of kOpRows rows, dot
+// products ascending from 0.0f, the softmax and the projection per atom in ascending order, weight gradients per tile into their
+// group's partial, groups ascending into the flat gradient, f64 slot folds for the scalars.  Every output equals the device's bit
+// for bit.
+namespace {
+
+struct DqTile {
+    std::vector<float> x, h1, h2, z, pl, pu, pdl, pdu, tp;
+    float qv[kOpRows * kDqMaxAct], yv[kOpRows], dq[kOpRows];
+    int act[kOpRows];
+    DqTile()
+        : x(kOpRows * kDqMaxObs), h1(kOpRows * kDqH1), h2(kOpRows * kDqH2), z(kOpRows * kDqMaxOut), pl(kOpRows * kDqMaxAtoms),
+          pu(kOpRows * kDqMaxAtoms), pdl(kOpRows * kDqMaxAtoms), pdu(kOpRows * kDqMaxAtoms), tp(kOpRows * kDqMaxAtoms) {}
+};
+
+template <bool RELU>
+void dq_layer_host(const float* xin, int xs, int K, const float* W, const float* b, int J, float* out, int os) {
+    for (int r = 0; r < kOpRows; ++r)
+        for (int j = 0; j < J; ++j) {
+            float acc = 0.0f;
+            for (int k = 0; k < K; ++k) acc = op_mac(acc, xin[r * xs + k], W[(int64_t)j * K + k]);
+            const float v = acc + b[j];
+            out[r * os + j] = RELU ? op_relu(v) : v;
+        }
+}
+
+void dq_forward_host(const DqNet& n, DqTile& T) {
+    dq_layer_host<true>(T.x.data(), kDqMaxObs, n.O, n.w1, n.b1, kDqH1, T.h1.data(), kDqH1);
+    dq_layer_host<true>(T.h1.data(), kDqH1, kDqH1, n.w2, n.b2, kDqH2, T.h2.data(), kDqH2);
+    dq_layer_host<false>(T.h2.data(), kDqH2, kDqH2, n.w3, n.b3, n.J, T.z.data(), kDqMaxOut);
+}
+
+void dq_qvalues_host(DqTile& T, int n, int na, const float* atoms) {
+    for (int r = 0; r < kOpRows; ++r)
+        for (int a = 0; a < n; ++a) {
+            float* za = T.z.data() + r * kDqMaxOut + a * na;
+            T.qv[r * kDqMaxAct + a] = (na > 1) ? dq_softmax_q(za, na, atoms, za) : za[0];
+        }
+}
+
+void dq_dgrad_host(const float* dz, int ds, int J, const float* W, int K, float* io, int ios) {
+    for (int r = 0; r < kOpRows; ++r)
+        for (int k = 0; k < K; ++k) {
+            float acc = 0.0f;
+            for (int j = 0; j < J; ++j) acc = op_mac(acc, dz[r * ds + j], W[(int64_t)j * K + k]);
+            io[r * ios + k] = op_relu_bwd(io[r * ios + k], acc);
+        }
+}
+
+int dq_shape_cpu(const char* fn, int M, int O, int n, int na) {
+    MI355_REQUIRE(M > 0 && dq_limits(O, n, na), MI355PPO_EINVAL,
+                  "%s: rows=%d obs_dim=%d n_actions=%d n_atoms=%d: the fused Q networks take 1 <= obs_dim <= %d, 2 <= n_actions <= %d, "
+                  "1 <= n_atoms <= %d, n_actions * n_atoms <= %d", fn, M, O, n, na, kDqMaxObs, kDqMaxAct, kDqMaxAtoms, kDqMaxOut);
+    return MI355PPO_OK;
+}
+
+void dq_gather_host(const float* src, const int64_t* bi, const int64_t* ei, int64_t slots, int N, int r0, int nr, int O, DqTile& T) {
+    for (int r = 0; r < kOpRows; ++r) {
+        const int64_t row = r < nr ? op_row_cpu(bi, ei, r0 + r, slots, N) : 0;
+        for (int k = 0; k < O; ++k) T.x[r * kDqMaxObs + k] = r < nr ? src[row * O + k] : 0.0f;
+    }
+}
+
+// dq_update_kernel<C51> on the host
+template <bool C51>
+int dq_update_cpu(const float* ring_obs, const float* ring_next_obs, const float* ring_actions, const float* ring_rewards,
+                  const float* ring_dones, const int64_t* bi, const int64_t* ei, int64_t slots, int N, const float* online, const float* target,
+                  const float* atoms, float gamma, float vmin, float vmax, float norm, float* grads, float* scalars_out, float* aux_a,
+                  float* aux_b, int M, int O, int n, int na) {
+    const int J = n * na, G = op_groups(M), ntiles = op_tiles(M);
+    const int64_t P = dq_count(O, J);
+    const DqNet tn = dq_net(target, O, J), qn = dq_net(online, O, J);
+    const DqOff off = dq_off(O, J);
+    std::vector<float> part((size_t)G * P), rows((size_t)2 * M);
+    DqTile T;
+    const int PS = kDqMaxAtoms, ZS = kDqMaxOut;
+    for (int tl = 0; tl < ntiles; ++tl) {
+        const int g = tl % G, r0 = tl * kOpRows, nr = (M - r0 < kOpRows) ? M - r0 : kOpRows;
+        const bool first = tl == g;
+        float* p = part.data() + (int64_t)g * P;
+        dq_gather_host(ring_next_obs, bi, ei, slots, N, r0, nr, O, T);
+        dq_forward_host(tn, T);
+        dq_qvalues_host(T, n, na, atoms);
+        if constexpr (C51) {
+            const float delta_z = atoms[1] - atoms[0];
+            for (int r = 0; r < kOpRows; ++r) {
+                const int a = dq_argmax(T.qv + r * kDqMaxAct, n);
+                for (int j = 0; j < na; ++j) {
+                    C51Proj e;
+                    e.l = e.u = -1.0f;
+                    e.dml = e.dmu = 0.0f;
+                    if (r < nr) {
+                        const int64_t row = op_row_cpu(bi, ei, r0 + r, slots, N);
+                        const float pj = T.z[r * ZS + a * na + j];
+                        e = c51_proj_elem(ring_rewards[row], ring_dones[row], gamma, atoms[j], vmin, vmax, delta_z, na, pj);
+                        if (aux_a) aux_a[(int64_t)(r0 + r) * na + j] = pj;
+                    }
+                    T.pl[r * PS + j] = e.l;
+                    T.pu[r * PS + j] = e.u;
+                    T.pdl[r * PS + j] = e.dml;
+                    T.pdu[r * PS + j] = e.dmu;
+                }
+                for (int k = 0; k < na; ++k) {
+                    const float v = c51_proj_atom(k, &T.pl[r * PS], &T.pu[r * PS], &T.pdl[r * PS], &T.pdu[r * PS], na);
+                    T.tp[r * PS + k] = v;
+                    if (aux_b && r < nr) aux_b[(int64_t)(r0 + r) * na + k] = v;
+                }
+            }
+        } else {
+            for (int r = 0; r < kOpRows; ++r) {
+                float y = 0.0f;
+                if (r < nr) {
+                    const int64_t row = op_row_cpu(bi, ei, r0 + r, slots, N);
+                    if (aux_a)
+                        for (int a = 0; a < n; ++a) aux_a[(int64_t)(r0 + r) * n + a] = T.qv[r * kDqMaxAct + a];
+                    y = dq_td_target(ring_rewards[row], ring_dones[row], gamma, T.qv[r * kDqMaxAct + dq_argmax(T.qv + r * kDqMaxAct, n)]);
+                    if (aux_b) aux_b[r0 + r] = y;
+                }
+                T.yv[r] = y;
+            }
+        }
+        for (int r = 0; r < kOpRows; ++r) T.act[r] = r < nr ? dq_action_index(ring_actions[op_row_cpu(bi, ei, r0 + r, slots, N)], n) : 0;
+        dq_gather_host(ring_obs, bi, ei, slots, N, r0, nr, O, T);
+        dq_forward_host(qn, T);
+        dq_qvalues_host(T, n, na, atoms);
+        if constexpr (C51) {
+            for (int r = 0; r < kOpRows; ++r) {
+                float s = 0.0f, dot = 0.0f;
+                for (int k = 0; k < na; ++k) {
+                    const C51Loss e = c51_loss_elem(T.tp[r * PS + k], T.z[r * ZS + T.act[r] * na + k], norm);
+                    T.pdl[r * PS + k] = e.g;
+                    s = s + e.term;
+                    dot = dot + e.gp;
+                }
+                if (r < nr) {
+                    rows[r0 + r] = -s;
+                    rows[(size_t)M + r0 + r] = T.qv[r * kDqMaxAct + T.act[r]];
+                }
+                for (int j = 0; j < J; ++j) {
+                    const int a = j / na, k = j - a * na;
+                    T.z[r * ZS + j] = (r < nr && a == T.act[r]) ? c51_dlogit(T.z[r * ZS + j], T.pdl[r * PS + k], dot) : 0.0f;
+                }
+            }
+        } else {
+            for (int r = 0; r < kOpRows; ++r) {
+                float d = 0.0f;
+                if (r < nr) {
+                    float sq;
+                    const float q = T.qv[r * kDqMaxAct + T.act[r]];
+                    d = op_mse_row(q, T.yv[r], norm, &sq);
+                    rows[r0 + r] = sq;
+                    rows[(size_t)M + r0 + r] = q;
+                }
+                for (int j = 0; j < J; ++j) T.z[r * ZS + j] = (j == T.act[r]) ? d : 0.0f;
+            }
+        }
+        op_wgrad_host(T.z.data(), ZS, T.h2.data(), kDqH2, J, kDqH2, p + off.w3, p + off.b3, first, nr);
+        dq_dgrad_host(T.z.data(), ZS, J, qn.w3, kDqH2, T.h2.data(), kDqH2);
+        op_wgrad_host(T.h2.data(), kDqH2, T.h1.data(), kDqH1, kDqH2, kDqH1, p + off.w2, p + off.b2, first, nr);
+        dq_dgrad_host(T.h2.data(), kDqH2, kDqH2, qn.w2, kDqH1, T.h1.data(), kDqH1);
+        op_wgrad_host(T.h1.data(), kDqH1, T.x.data(), kDqMaxObs, kDqH1, O, p + off.w1, p + off.b1, first, nr);
+    }
+    op_fold_host(part.data(), G, P, grads);
+    for (int s = 0; s < 2; ++s) scalars_out[s] = 1.0f * op_fold_mean_host(rows.data() + (size_t)s * M, M);
+    return MI355PPO_OK;
+}
+
+}  // namespace
+
+extern "C" MI355PPO_API int mi355ppo_dqn_act_f32_cpu(const float* obs, const float* params, const float* atoms, int64_t* actions_out,
+                                                    float* q_out, int N, int O, int n_actions, int n_atoms) {
+    const char* fn = "mi355ppo_dqn_act_f32_cpu";
+    MI355_REQUIRE(obs && params && actions_out, MI355PPO_EINVAL, "%s: null pointer", fn);
+    if (int rc = dq_shape_cpu(fn, N, O, n_actions, n_atoms)) return rc;
+    MI355_REQUIRE(n_atoms == 1 || atoms, MI355PPO_EINVAL, "%s: n_atoms=%d needs the atoms", fn, n_atoms);
+    const DqNet qn = dq_net(params, O, n_actions * n_atoms);
+    DqTile T;
+    for (int r0 = 0; r0 < N; r0 += kOpRows) {
+        for (int r = 0; r < kOpRows; ++r)
+            for (int k = 0; k < O; ++k) T.x[r * kDqMaxObs + k] = (r0 + r < N) ? obs[(int64_t)(r0 + r) * O + k] : 0.0f;
+        dq_forward_host(qn, T);
+        dq_qvalues_host(T, n_actions, n_atoms, atoms);
+        for (int r = 0; r < kOpRows && r0 + r < N; ++r) {
+            if (q_out)
+                for (int a = 0; a < n_actions; ++a) q_out[(int64_t)(r0 + r) * n_actions + a] = T.qv[r * kDqMaxAct + a];
+            actions_out[r0 + r] = (int64_t)dq_argmax(T.qv + r * kDqMaxAct, n_actions);
+        }
+    }
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_dqn_td_fwd_bwd_f32_cpu(const float* ring_obs, const float* ring_next_obs, const float* ring_actions,
+                                                           const float* ring_rewards, const float* ring_dones, const int64_t* batch_inds,
+                                                           const int64_t* env_inds, int64_t slots, int n_envs, const float* online,
+                                                           const float* target, double gamma, float* grads, float* scalars_out,
+                                                           float* target_q_out, float* td_target_out, int M, int O, int n_actions) {
+    const char* fn = "mi355ppo_dqn_td_fwd_bwd_f32_cpu";
+    MI355_REQUIRE(ring_obs && ring_next_obs && ring_actions && ring_rewards && ring_dones && online && target && grads && scalars_out &&
+                      batch_inds && env_inds, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(slots > 0 && n_envs > 0, MI355PPO_EINVAL, "%s: slots=%lld n_envs=%d must be positive", fn, (long long)slots, n_envs);
+    if (int rc = dq_shape_cpu(fn, M, O, n_actions, 1)) return rc;
+    return dq_update_cpu<false>(ring_obs, ring_next_obs, ring_actions, ring_rewards, ring_dones, batch_inds, env_inds, slots, n_envs, online,
+                                target, nullptr, (float)gamma, 0.0f, 0.0f, (float)(2.0 / (double)M), grads, scalars_out, target_q_out,
+                                td_target_out, M, O, n_actions, 1);
+}
+
+extern "C" MI355PPO_API int mi355ppo_c51_fwd_bwd_f32_cpu(const float* ring_obs, const float* ring_next_obs, const float* ring_actions,
+                                                        const float* ring_rewards, const float* ring_dones, const int64_t* batch_inds,
+                                                        const int64_t* env_inds, int64_t slots, int n_envs, const float* online,
+                                                        const float* target, const float* atoms, double gamma, double v_min, double v_max,
+                                                        float* grads, float* scalars_out, float* next_pmfs_out, float* target_pmfs_out, int M,
+                                                        int O, int n_actions, int n_atoms) {
+    const char* fn = "mi355ppo_c51_fwd_bwd_f32_cpu";
+    MI355_REQUIRE(ring_obs && ring_next_obs && ring_actions && ring_rewards && ring_dones && online && target && atoms && grads &&
+                      scalars_out && batch_inds && env_inds, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(slots > 0 && n_envs > 0, MI355PPO_EINVAL, "%s: slots=%lld n_envs=%d must be positive", fn, (long long)slots, n_envs);
+    if (int rc = dq_shape_cpu(fn, M, O, n_actions, n_atoms)) return rc;
+    MI355_REQUIRE(n_atoms >= 2, MI355PPO_EINVAL, "%s: n_atoms=%d: the projection needs two atoms (delta_z = atoms[1] - atoms[0])", fn, n_atoms);
+    return dq_update_cpu<true>(ring_obs, ring_next_obs, ring_actions, ring_rewards, ring_dones, batch_inds, env_inds, slots, n_envs, online,
+                               target, atoms, (float)gamma, (float)v_min, (float)v_max, (float)(1.0 / (double)M), grads, scalars_out,
+                               next_pmfs_out, target_pmfs_out, M, O, n_actions, n_atoms);
 }

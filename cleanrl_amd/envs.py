@@ -702,3 +702,50 @@ class SyntheticReplayVecEnv(SyntheticContinuousVecEnv):
             self.state[rows] = self.rng.standard_normal((len(rows), self.obs_dim)) * 0.1
             self.steps[rows] = 0
         return self.state.astype(np.float32), reward, terminated, truncated, infos
+
+
+class SamplingDiscrete(Discrete):
+    """A ``Discrete`` with a ``seed()`` and a ``sample()``, as dqn.py / c51.py use their action space for the random branch of the
+    epsilon-greedy action."""
+
+    def __init__(self, n: int):
+        super().__init__(n)
+        self._rng = np.random.RandomState(0)
+
+    def seed(self, seed=None):
+        self._rng = np.random.RandomState(seed)
+        return [seed]
+
+    def sample(self):
+        return np.int64(self._rng.randint(self.n))
+
+
+class CartPoleReplayVecEnv(CartPoleVecEnv):
+    """The CartPole stand-in of dqn.py / c51.py: ``CartPoleVecEnv``'s dynamics and reset stream with float32 observations, a seeded
+    ``single_action_space.sample()``, an optional shorter truncation ``horizon`` and gymnasium's ``final_observation`` in ``infos``
+    when an episode ends (the returned observation is then the next episode's first)."""
+
+    def __init__(self, num_envs: int, seed: int = 0, horizon=None):
+        super().__init__(num_envs, seed=seed)
+        self._final = {}
+        if horizon is not None:
+            self.max_episode_steps = int(horizon)
+        self.single_observation_space = Box(-np.inf, np.inf, (4,), np.float32)
+        self.single_action_space = SamplingDiscrete(2)
+        self.single_action_space.seed(seed)
+
+    def _reset_rows(self, rows):
+        if len(rows) and self.steps[rows].any():                  # an episode just ended: keep its last state for final_observation
+            self._final = {int(i): self.state[i].astype(np.float32) for i in rows}
+        super()._reset_rows(rows)
+
+    def step(self, action):
+        self._final = {}
+        obs, reward, terminated, truncated, infos = super().step(action)
+        if self._final:
+            final = np.empty(self.num_envs, dtype=object)
+            for i, v in self._final.items():
+                final[i] = v
+            infos["final_observation"] = final
+            infos["_final_observation"] = terminated | truncated
+        return obs, reward, terminated, truncated, infos

@@ -17,7 +17,7 @@ import ctypes
 import torch
 
 from . import _lib
-from .ops import IMPALA_CHANNELS, _lstm_dims, _ptr_array, offpolicy_counts, pqn_param_count, radam_schedule, sac_actor_count, trxl_dims  # noqa: F401  (one definition for both modules)
+from .ops import IMPALA_CHANNELS, _lstm_dims, _ptr_array, dqn_counts, dqn_limits_ok, offpolicy_counts, pqn_param_count, radam_schedule, sac_actor_count, trxl_dims  # noqa: F401  (one definition for both modules)
 
 LOSS_SCALARS = 7
 
@@ -574,3 +574,51 @@ def sac_alpha_(log_pi, target_entropy, log_alpha, exp_avg, exp_avg_sq, step, lr,
               _out(exp_avg_sq, torch.float32, 1, "exp_avg_sq"), float(lr), float(beta1), float(beta2), float(eps), int(step),
               _out(alpha_out, torch.float32, 1, "alpha_out"), _out(alpha_loss_out, torch.float32, 1, "alpha_loss_out"))
     return alpha_out
+
+
+# ------------------------------------------------------------------------------------------- DQN / C51 twins (csrc/dqn.hip)
+def _opt_out(t, numel, name):
+    return None if t is None else _out(t, torch.float32, numel, name)
+
+
+def dqn_act(obs, params, n_actions, actions_out, atoms=None, q_out=None):
+    N, O = obs.shape
+    na = 1 if atoms is None else atoms.numel()
+    _lib.call("mi355ppo_dqn_act_f32_cpu", _in(obs, torch.float32, (N, O), "obs"),
+              _in(params, torch.float32, (dqn_counts(O, n_actions, na),), "params"),
+              None if atoms is None else _in(atoms, torch.float32, (na,), "atoms"), _out(actions_out, torch.int64, N, "actions_out"),
+              _opt_out(q_out, N * n_actions, "q_out"), N, O, int(n_actions), na)
+    return actions_out
+
+
+def _dqn_ring(ring):
+    slots, N, O, A, rp = _ring_dims(ring)
+    if A != 1:
+        raise ValueError(f"ring actions: the DQN / C51 ring stores one action index per env, got width {A}")
+    return slots, N, O, rp
+
+
+def dqn_td_fwd_bwd(ring, batch_inds, env_inds, online, target, n_actions, gamma, grads, scalars, target_q_out=None, td_target_out=None):
+    slots, N, O, rp = _dqn_ring(ring)
+    (M,) = batch_inds.shape
+    P = dqn_counts(O, n_actions)
+    _lib.call("mi355ppo_dqn_td_fwd_bwd_f32_cpu", *rp, _in(batch_inds, torch.int64, (M,), "batch_inds"),
+              _in(env_inds, torch.int64, (M,), "env_inds"), slots, N, _in(online, torch.float32, (P,), "online"),
+              _in(target, torch.float32, (P,), "target"), float(gamma), _out(grads, torch.float32, P, "grads"),
+              _out(scalars, torch.float32, 2, "scalars"), _opt_out(target_q_out, M * n_actions, "target_q_out"),
+              _opt_out(td_target_out, M, "td_target_out"), M, O, int(n_actions))
+    return scalars
+
+
+def c51_fwd_bwd(ring, batch_inds, env_inds, online, target, atoms, n_actions, gamma, v_min, v_max, grads, scalars, next_pmfs_out=None,
+                target_pmfs_out=None):
+    slots, N, O, rp = _dqn_ring(ring)
+    (M,) = batch_inds.shape
+    na = atoms.numel()
+    P = dqn_counts(O, n_actions, na)
+    _lib.call("mi355ppo_c51_fwd_bwd_f32_cpu", *rp, _in(batch_inds, torch.int64, (M,), "batch_inds"),
+              _in(env_inds, torch.int64, (M,), "env_inds"), slots, N, _in(online, torch.float32, (P,), "online"),
+              _in(target, torch.float32, (P,), "target"), _in(atoms, torch.float32, (na,), "atoms"), float(gamma), float(v_min), float(v_max),
+              _out(grads, torch.float32, P, "grads"), _out(scalars, torch.float32, 2, "scalars"),
+              _opt_out(next_pmfs_out, M * na, "next_pmfs_out"), _opt_out(target_pmfs_out, M * na, "target_pmfs_out"), M, O, int(n_actions), na)
+    return scalars

@@ -1,0 +1,205 @@
+"""The replay buffer, action logic and training step of ``dqn.py`` and ``c51.py`` (reference: cleanrl/dqn.py, cleanrl/c51.py and
+``ReplayBuffer`` of cleanrl_utils/buffers.py).
+
+====================================================  ==============================================================
+reference                                              here
+====================================================  ==============================================================
+``optim.Adam(q_network.parameters(), ...)``,           ``DQNLearner.__init__``: ``torch`` -- ``HostReplayBuffer`` (int64 actions) + the torch
+``ReplayBuffer(..., handle_timeout_termination=        optimizer; ``fused`` -- the ring in device memory with an action width of 1 (the index
+False)``                                               as f32), flat parameter / gradient / Adam buffers the modules' parameters are views of
+``random.random() < epsilon``, then                    ``act``: the same two draws in the same order; the greedy branch on ``fused`` is one
+``single_action_space.sample()`` per env or            launch (``mi355ppo_dqn_act_f32``) on the staged obs
+``argmax(q_network(obs))`` / ``get_action(obs)``
+``real_next_obs`` / ``rb.add(...)``                    ``store`` (``DeviceRing``): one staged copy + ``mi355ppo_replay_add_f32``
+``rb.sample`` (``np.random.randint`` twice)            ``sample_indices`` (``DeviceRing``)
+dqn.py: ``target_max`` / ``td_target`` /               ``train_step``: ``mi355ppo_dqn_td_fwd_bwd_f32`` (2 launches) + ``mi355ppo_clip_adam_f32``
+``old_val`` / ``mse_loss`` / ``backward`` /            (grad_scale 1, max_grad_norm inf, eps 1e-8: 2 launches)
+``optimizer.step``
+c51.py: target ``get_action``, the projection          ``train_step``: ``mi355ppo_c51_fwd_bwd_f32`` (2 launches) + ``mi355ppo_clip_adam_f32``
+loop, ``old_pmfs``, the loss, ``backward``,            with eps ``0.01 / batch_size``
+``optimizer.step``
+dqn.py: the ``tau`` Polyak loop                        ``sync_target``: ``mi355ppo_polyak_f32`` over the flat buffers (1 launch)
+c51.py: ``target_network.load_state_dict``             ``sync_target``: one flat ``target.copy_(online)`` (a copy keeps ``-0.0`` and does not
+                                                       read the old target, which ``polyak_(tau=1)`` would)
+``losses/*``                                           ``metrics`` (one device -> host copy when the script logs)
+====================================================  ==============================================================
+
+Backend: ``MI355PPO_OFFPOLICY=torch|fused``, default ``torch``.  Both backends draw the reference's random
+streams in its order.  A fused step is 6 library launches (act 1, add 1, update 2, Adam 2), 7 on a target-update step of dqn.py.
+"""
+from __future__ import annotations
+
+import math
+import random
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+import torch.optim as optim
+
+from . import ops
+from .learner_offpolicy import BACKENDS, DeviceRing, HostReplayBuffer, offpolicy_backend
+
+
+class DQNLearner(DeviceRing):
+    """``c51``: the networks are ``C51Network`` (atoms, ``get_action``) and the update is the categorical one."""
+
+    def __init__(self, q_network, target_network, args, envs, device, c51: bool, backend=None):
+        self.q_network, self.target_network = q_network, target_network
+        self.args, self.device, self.c51 = args, torch.device(device), bool(c51)
+        self.backend = offpolicy_backend(self.device) if backend is None else backend
+        if self.backend not in BACKENDS:
+            raise ValueError(f"off-policy backend {self.backend!r}: expected one of {BACKENDS}")
+        self.fused = self.backend == "fused"
+        self.space = envs.single_action_space
+        self.N = int(envs.num_envs)
+        self.O = int(np.array(envs.single_observation_space.shape).prod())
+        self.A = 1
+        self.n = int(self.space.n)
+        self.n_atoms = int(args.n_atoms) if self.c51 else 1
+        self.eps = 0.01 / args.batch_size if self.c51 else 1e-8
+        self.g = ops.twins(self.device)
+        self.pos, self.full = 0, False
+        self.slots = max(int(args.buffer_size) // self.N, 1)
+        self.step = 0
+        self.last = None
+        if not self.fused:
+            self.rb = HostReplayBuffer(args.buffer_size, self.O, 1, self.device, n_envs=self.N, act_dtype=np.int64)
+            self.optimizer = optim.Adam(q_network.parameters(), lr=args.learning_rate, eps=self.eps)
+            return
+        if not ops.dqn_limits_ok(self.O, self.n, self.n_atoms) or (self.c51 and self.n_atoms < 2):
+            raise ValueError(f"MI355PPO_OFFPOLICY=fused: the fused Q networks take obs_dim <= {ops.DQN_MAX_OBS}, 2 <= n_actions <= "
+                             f"{ops.DQN_MAX_ACT}, n_atoms <= {ops.DQN_MAX_ATOMS} (at least 2 for c51) and n_actions * n_atoms <= "
+                             f"{ops.DQN_MAX_OUT}, not {self.O} / {self.n} / {self.n_atoms}; use MI355PPO_OFFPOLICY=torch")
+        dev = self.device
+        total = ops.dqn_counts(self.O, self.n, self.n_atoms)
+        self.online = torch.zeros(total, dtype=torch.float32, device=dev)
+        self.target = torch.zeros(total, dtype=torch.float32, device=dev)
+        self.grads, self.exp_avg, self.exp_avg_sq = (torch.zeros(total, dtype=torch.float32, device=dev) for _ in range(3))
+        for flat, net in ((self.online, q_network), (self.target, target_network)):
+            off = 0
+            with torch.no_grad():
+                for p in net.parameters():                       # the modules keep working: their parameters are views of the flat buffer
+                    n = p.numel()
+                    flat[off:off + n].copy_(p.reshape(-1))
+                    p.data = flat[off:off + n].view(p.shape)
+                    off += n
+        self.atoms = q_network.atoms.detach().to(dev).contiguous() if self.c51 else None
+        M = int(args.batch_size)
+        self._alloc_ring(M)
+        self._greedy = torch.zeros(self.N, dtype=torch.int64, device=dev)
+        self._sc = torch.zeros(2, dtype=torch.float32, device=dev)
+        self._norm = torch.zeros(1, dtype=torch.float32, device=dev)
+
+    # ------------------------------------------------------------------ rollout
+    def act(self, obs, global_step: int, epsilon: float):
+        """The step's actions (N,) int64: ``random.random() < epsilon`` first, then ``sample()`` per env or the greedy action."""
+        if random.random() < epsilon:
+            return np.array([self.space.sample() for _ in range(self.N)])
+        with torch.no_grad():
+            if not self.fused:
+                x = torch.Tensor(obs).to(self.device)
+                if self.c51:
+                    actions, _ = self.q_network.get_action(x)
+                else:
+                    actions = torch.argmax(self.q_network(x), dim=1)
+                return actions.cpu().numpy()
+            self.g.dqn_act(self._stage_obs(obs), self.online, self.n, self._greedy, atoms=self.atoms)
+            out = self._greedy.cpu().numpy()
+            return out if self.device.type == "cuda" else out.copy()      # on the CPU .cpu() aliases the reused buffer
+
+    # ------------------------------------------------------------------ training
+    def train_step(self, indices=None):
+        """One ``# ALGO LOGIC: training.`` block up to the optimizer step.  ``indices`` replaces the draws (teacher forcing)."""
+        M = int(self.args.batch_size)
+        bi, ei = self.sample_indices(M) if indices is None else indices
+        if not self.fused:
+            return self._train_torch(bi, ei)
+        idx = self._stage_indices(bi, ei)
+        self.update_kernels(idx[0], idx[1])
+        self.last = ("fused",)
+        return self
+
+    def update_kernels(self, bi, ei, adam: bool = True, sched=None):
+        """The update's library launches on device-resident indices (what a graph capture records).  With ``sched``, a (2,) float32
+        device tensor holding ``adam_schedule()``, Adam reads its step size and bias correction from it (``clip_adam_sched_``) and
+        the caller advances ``step``."""
+        a, g = self.args, self.g
+        if self.c51:
+            g.c51_fwd_bwd(self.ring, bi, ei, self.online, self.target, self.atoms, self.n, a.gamma, a.v_min, a.v_max, self.grads, self._sc)
+        else:
+            g.dqn_td_fwd_bwd(self.ring, bi, ei, self.online, self.target, self.n, a.gamma, self.grads, self._sc)
+        if adam and sched is not None:
+            ops.clip_adam_sched_(self.online, self.grads, self.exp_avg, self.exp_avg_sq, sched, math.inf, 1.0, eps=self.eps,
+                                 total_norm_out=self._norm)
+        elif adam:
+            self.step += 1
+            kw = {"total_norm_out": self._norm} if self.device.type == "cuda" else {}
+            g.clip_adam_(self.online, self.grads, self.exp_avg, self.exp_avg_sq, self.step, a.learning_rate, math.inf, 1.0, eps=self.eps, **kw)
+
+    def adam_schedule(self):
+        """(2,) host tensor: the library's (step size, bias correction) of the NEXT Adam step."""
+        return torch.tensor(ops.adam_schedule(self.args.learning_rate, self.step + 1), dtype=torch.float32)
+
+    def _train_torch(self, bi, ei):
+        a = self.args
+        observations, actions, next_observations, dones, rewards = self.rb.gather(bi, ei)
+        q_network, target_network = self.q_network, self.target_network
+        if self.c51:
+            with torch.no_grad():
+                _, next_pmfs = target_network.get_action(next_observations)
+                next_atoms = rewards + a.gamma * target_network.atoms * (1 - dones)
+                delta_z = target_network.atoms[1] - target_network.atoms[0]
+                tz = next_atoms.clamp(a.v_min, a.v_max)
+                b = (tz - a.v_min) / delta_z
+                l = b.floor().clamp(0, a.n_atoms - 1)  # noqa: E741
+                u = b.ceil().clamp(0, a.n_atoms - 1)
+                d_m_l = (u + (l == u).float() - b) * next_pmfs
+                d_m_u = (b - l) * next_pmfs
+                target_pmfs = torch.zeros_like(next_pmfs)
+                for i in range(target_pmfs.size(0)):
+                    target_pmfs[i].index_add_(0, l[i].long(), d_m_l[i])
+                    target_pmfs[i].index_add_(0, u[i].long(), d_m_u[i])
+            _, old_pmfs = q_network.get_action(observations, actions.flatten())
+            loss = (-(target_pmfs * old_pmfs.clamp(min=1e-5, max=1 - 1e-5).log()).sum(-1)).mean()
+            old_val = (old_pmfs * q_network.atoms).sum(1)
+        else:
+            with torch.no_grad():
+                target_max, _ = target_network(next_observations).max(dim=1)
+                td_target = rewards.flatten() + a.gamma * target_max * (1 - dones.flatten())
+            old_val = q_network(observations).gather(1, actions).squeeze()
+            loss = F.mse_loss(td_target, old_val)
+        self.optimizer.zero_grad()
+        loss.backward()
+        self.optimizer.step()
+        self.step += 1
+        self.last = ("torch", loss.detach(), old_val.detach())
+        return self
+
+    def sync_target(self):
+        """The target update: dqn.py's ``tau`` loop, c51.py's ``load_state_dict``."""
+        if self.c51:
+            if self.fused:
+                self.target.copy_(self.online)
+            else:
+                self.target_network.load_state_dict(self.q_network.state_dict())
+            return
+        tau = self.args.tau
+        if self.fused:
+            self.g.polyak_(self.online, self.target, tau)
+            return
+        for target_network_param, q_network_param in zip(self.target_network.parameters(), self.q_network.parameters()):
+            target_network_param.data.copy_(tau * q_network_param.data + (1.0 - tau) * target_network_param.data)
+
+    def metrics(self) -> dict:
+        """The last update's scalars as Python floats: ``loss`` (``losses/td_loss`` or ``losses/loss``) and ``q_values``."""
+        if self.last[0] == "torch":
+            return {"loss": self.last[1].item(), "q_values": self.last[2].mean().item()}
+        sc = self._sc.tolist()
+        return {"loss": sc[0], "q_values": sc[1]}
+
+    def flat_params(self):
+        """(online, target) flat parameters, detached copies (tests)."""
+        fo = torch.cat([p.detach().reshape(-1) for p in self.q_network.parameters()])
+        ft = torch.cat([p.detach().reshape(-1) for p in self.target_network.parameters()])
+        return fo.clone(), ft.clone()

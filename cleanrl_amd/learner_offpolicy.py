@@ -53,11 +53,11 @@ class HostReplayBuffer:
     """``ReplayBuffer(buffer_size, ..., n_envs, handle_timeout_termination=False)``: numpy arrays of ``buffer_size // n_envs`` slots,
     ``pos`` / ``full``; ``sample`` draws ``batch_inds`` and then ``env_indices`` from ``np.random``."""
 
-    def __init__(self, buffer_size: int, obs_dim: int, act_dim: int, device, n_envs: int = 1):
+    def __init__(self, buffer_size: int, obs_dim: int, act_dim: int, device, n_envs: int = 1, act_dtype=np.float32):
         self.slots, self.n_envs, self.device = max(int(buffer_size) // n_envs, 1), n_envs, device
         self.observations = np.zeros((self.slots, n_envs, obs_dim), np.float32)
         self.next_observations = np.zeros((self.slots, n_envs, obs_dim), np.float32)
-        self.actions = np.zeros((self.slots, n_envs, act_dim), np.float32)
+        self.actions = np.zeros((self.slots, n_envs, act_dim), act_dtype)     # int64 for a Discrete space (dqn.py, c51.py)
         self.rewards = np.zeros((self.slots, n_envs), np.float32)
         self.dones = np.zeros((self.slots, n_envs), np.float32)
         self.pos, self.full = 0, False

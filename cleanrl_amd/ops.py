@@ -28,6 +28,7 @@ __all__ = [
     "pqn_param_count", "pqn_egreedy", "pqn_qlambda", "pqn_td_loss", "pqn_mlp_forward", "pqn_mlp_act", "pqn_mlp_td_fwd_bwd", "radam_schedule",
     "clip_radam_", "clip_radam_sched_", "pqn_lstm_act", "pqn_lstm_td_fwd_bwd", "offpolicy_counts", "replay_add", "ddpg_act", "td3_target",
     "td3_critic_fwd_bwd", "td3_actor_fwd_bwd", "polyak_", "sac_actor_count", "sac_policy", "sac_target", "sac_actor_fwd_bwd", "sac_alpha_",
+    "dqn_counts", "dqn_limits_ok", "dqn_act", "dqn_td_fwd_bwd", "c51_fwd_bwd",
 ]
 
 LOSS_SCALAR_NAMES = ("loss", "pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac")
@@ -1504,3 +1505,88 @@ def sac_alpha_(log_pi, target_entropy: float, log_alpha, exp_avg, exp_avg_sq, st
     _launch("mi355ppo_sac_alpha_f32", log_pi.device, _ptr(log_pi), M, float(target_entropy), _ptr(log_alpha), _ptr(exp_avg), _ptr(exp_avg_sq),
             float(lr), float(beta1), float(beta2), float(eps), int(step), _ptr(sched2), _ptr(alpha_out), _ptr(alpha_loss_out))
     return alpha_out
+
+
+# ------------------------------------------------------------------------------------------- DQN / C51 (csrc/dqn.hip)
+DQN_MAX_OBS, DQN_MAX_ACT, DQN_MAX_ATOMS, DQN_MAX_OUT, DQN_HIDDEN = 512, 18, 101, 512, (120, 84)
+
+
+def dqn_counts(obs_dim: int, n_actions: int, n_atoms: int = 1) -> int:
+    """Parameter count of dqn.py's / c51.py's ``QNetwork`` (120 - 84 - n_actions * n_atoms)."""
+    h1, h2 = DQN_HIDDEN
+    J = n_actions * n_atoms
+    return h1 * obs_dim + h1 + h2 * h1 + h2 + J * h2 + J
+
+
+def dqn_limits_ok(obs_dim: int, n_actions: int, n_atoms: int = 1) -> bool:
+    """What the fused Q networks take (anything else is ``MI355PPO_EINVAL`` from the C ABI)."""
+    return (1 <= obs_dim <= DQN_MAX_OBS and 2 <= n_actions <= DQN_MAX_ACT and 1 <= n_atoms <= DQN_MAX_ATOMS
+            and n_actions * n_atoms <= DQN_MAX_OUT)
+
+
+def _dqn_ring(ring):
+    slots, N, O, A = _ring_dims(ring)
+    if A != 1:
+        raise ValueError(f"ring actions: the DQN / C51 ring stores one action index per env, got width {A}")
+    return slots, N, O
+
+
+def dqn_act(obs, params, n_actions: int, actions_out, atoms=None, q_out=None):
+    """The greedy action in one launch: ``argmax(q_network(obs), dim=1)`` or, with ``atoms`` (n_atoms,), C51's ``get_action`` ->
+    actions_out (N,) int64.  ``q_out`` (N, n_actions) optionally receives the q values."""
+    N, O = obs.shape
+    na = 1 if atoms is None else atoms.numel()
+    _chk(obs, torch.float32, "obs")
+    _chk(params, torch.float32, "params", (dqn_counts(O, n_actions, na),))
+    if atoms is not None:
+        _chk(atoms, torch.float32, "atoms", (na,))
+    _chk(actions_out, torch.int64, "actions_out", (N,))
+    if q_out is not None:
+        _chk(q_out, torch.float32, "q_out", (N, n_actions))
+    _launch("mi355ppo_dqn_act_f32", obs.device, _ptr(obs), _ptr(params), _ptr(atoms), _ptr(actions_out), _ptr(q_out), N, O, int(n_actions), na)
+    return actions_out
+
+
+def dqn_td_fwd_bwd(ring, batch_inds, env_inds, online, target, n_actions: int, gamma: float, grads, scalars, target_q_out=None,
+                   td_target_out=None):
+    """dqn.py's update up to the optimizer in two launches.  OVERWRITES ``grads`` (flat, ``q_network.parameters()`` order);
+    scalars (2,) = {td_loss, mean old_val}."""
+    slots, N, O = _dqn_ring(ring)
+    M = _batch_inds(batch_inds, env_inds)
+    P = dqn_counts(O, n_actions)
+    for t, nm in ((online, "online"), (target, "target"), (grads, "grads")):
+        _chk(t, torch.float32, nm, (P,))
+    _chk(scalars, torch.float32, "scalars", (2,))
+    if target_q_out is not None:
+        _chk(target_q_out, torch.float32, "target_q_out", (M, n_actions))
+    if td_target_out is not None:
+        _chk(td_target_out, torch.float32, "td_target_out", (M,))
+    dev = batch_inds.device
+    ws = _workspace(dev, _lib.load().mi355ppo_dqn_td_workspace_bytes(M, O, int(n_actions)))
+    _launch("mi355ppo_dqn_td_fwd_bwd_f32", dev, *[_ptr(t) for t in ring], _ptr(batch_inds), _ptr(env_inds), slots, N, _ptr(online),
+            _ptr(target), float(gamma), _ptr(grads), _ptr(scalars), _ptr(target_q_out), _ptr(td_target_out), M, O, int(n_actions), _ptr(ws),
+            ws.numel())
+    return scalars
+
+
+def c51_fwd_bwd(ring, batch_inds, env_inds, online, target, atoms, n_actions: int, gamma: float, v_min: float, v_max: float, grads, scalars,
+                next_pmfs_out=None, target_pmfs_out=None):
+    """c51.py's update up to the optimizer in two launches (target ``get_action``, projection, loss, backward).  OVERWRITES
+    ``grads``; scalars (2,) = {loss, mean (old_pmfs * atoms).sum(1)}."""
+    slots, N, O = _dqn_ring(ring)
+    M = _batch_inds(batch_inds, env_inds)
+    na = atoms.numel()
+    P = dqn_counts(O, n_actions, na)
+    for t, nm in ((online, "online"), (target, "target"), (grads, "grads")):
+        _chk(t, torch.float32, nm, (P,))
+    _chk(atoms, torch.float32, "atoms", (na,))
+    _chk(scalars, torch.float32, "scalars", (2,))
+    for t, nm in ((next_pmfs_out, "next_pmfs_out"), (target_pmfs_out, "target_pmfs_out")):
+        if t is not None:
+            _chk(t, torch.float32, nm, (M, na))
+    dev = batch_inds.device
+    ws = _workspace(dev, _lib.load().mi355ppo_c51_workspace_bytes(M, O, int(n_actions), na))
+    _launch("mi355ppo_c51_fwd_bwd_f32", dev, *[_ptr(t) for t in ring], _ptr(batch_inds), _ptr(env_inds), slots, N, _ptr(online), _ptr(target),
+            _ptr(atoms), float(gamma), float(v_min), float(v_max), _ptr(grads), _ptr(scalars), _ptr(next_pmfs_out), _ptr(target_pmfs_out), M, O,
+            int(n_actions), na, _ptr(ws), ws.numel())
+    return scalars

@@ -48,6 +48,9 @@ extern "C" {
                                   2.7.1: SAC -- mi355ppo_sac_* (policy, target, actor, alpha) and their *_cpu twins.  Entry points were only
                                   added and no existing signature moved, so a 2.7 binding keeps working against this library: the patch
                                   moves, the minor stays;
+                                  DQN / C51 -- mi355ppo_dqn_act_f32, mi355ppo_dqn_td_fwd_bwd_f32, mi355ppo_c51_fwd_bwd_f32 (+ workspace sizes) and
+                                  their *_cpu twins were added the same way: no existing signature moved, and the number stays at 2.7.1 (a
+                                  binding finds out whether they are there by looking the symbols up);
                                   a binding must check major AND minor (cleanrl_amd/_lib.py does) */
 
 #if defined(__GNUC__)
@@ -1057,6 +1060,55 @@ MI355PPO_API int mi355ppo_sac_alpha_f32_cpu(const float* log_pi, int M, double t
                                             float* alpha_out, float* alpha_loss_out);
 /* the library's exp and log on host arrays (tests): exp_out[i] = exp(x[i]), log_out[i] = log(x[i]); either output may be NULL. */
 MI355PPO_API int mi355ppo_sac_exp_log_f32_cpu(const float* x, float* exp_out, float* log_out, int64_t n);
+
+/* ---- DQN / C51 (added under ABI 2.7.1, csrc/dqn.hip; reference: cleanrl/dqn.py, cleanrl/c51.py) ----
+ * QNetwork is Linear(obs_dim, 120) - ReLU - Linear(120, 84) - ReLU - Linear(84, n_actions * n_atoms), flat f32 parameters in
+ * .parameters() order; n_atoms = 1 is dqn.py's network.  1 <= obs_dim <= 512, 2 <= n_actions <= 18, 1 <= n_atoms <= 101,
+ * n_actions * n_atoms <= 512 (the C51 update needs n_atoms >= 2); anything else is MI355PPO_EINVAL before any launch.  The ring is
+ * the one of the section above with an action width of 1: the action index stored as f32.  atoms (n_atoms) is the network's own
+ * torch.linspace buffer; it is read, never recomputed.  exp and log are the library's own (csrc/sac_rows.h).  No entry point allocates
+ * or synchronises, none uses atomics, all can be captured; every *_cpu twin returns the device's bits (csrc/dqn_rows.h).
+ *
+ * act: actions_out (N, int64) = argmax_a q(obs)[a], a tie to the lowest index.  n_atoms == 1: q = q_network(obs) and atoms may be
+ * NULL; n_atoms > 1: C51's get_action -- softmax over each action's atoms, q = (pmfs * atoms).sum in ascending atom order.  q_out
+ * (N, n_actions) may be NULL.  One launch. */
+MI355PPO_API int mi355ppo_dqn_act_f32(const float* obs, const float* params, const float* atoms, int64_t* actions_out, float* q_out, int N,
+                                      int O, int n_actions, int n_atoms, void* stream);
+MI355PPO_API int mi355ppo_dqn_act_f32_cpu(const float* obs, const float* params, const float* atoms, int64_t* actions_out, float* q_out, int N,
+                                          int O, int n_actions, int n_atoms);
+/* dqn.py's update: td_target = rewards + gamma * target(next_obs).max(1) * (1 - dones), old_val = online(obs)[action],
+ * loss = F.mse_loss(td_target, old_val).  grads (the online network's parameters) is OVERWRITTEN; scalars_out (2) = {td_loss,
+ * mean old_val}; target_q_out (M, n_actions) and td_target_out (M) may be NULL.  Two launches: per-workgroup partials, then the fold
+ * in workgroup order. */
+MI355PPO_API size_t mi355ppo_dqn_td_workspace_bytes(int M, int O, int n_actions);
+MI355PPO_API int mi355ppo_dqn_td_fwd_bwd_f32(const float* ring_obs, const float* ring_next_obs, const float* ring_actions,
+                                             const float* ring_rewards, const float* ring_dones, const int64_t* batch_inds,
+                                             const int64_t* env_inds, int64_t slots, int n_envs, const float* online, const float* target,
+                                             double gamma, float* grads, float* scalars_out, float* target_q_out, float* td_target_out, int M,
+                                             int O, int n_actions, void* workspace, size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_dqn_td_fwd_bwd_f32_cpu(const float* ring_obs, const float* ring_next_obs, const float* ring_actions,
+                                                 const float* ring_rewards, const float* ring_dones, const int64_t* batch_inds,
+                                                 const int64_t* env_inds, int64_t slots, int n_envs, const float* online,
+                                                 const float* target, double gamma, float* grads, float* scalars_out, float* target_q_out,
+                                                 float* td_target_out, int M, int O, int n_actions);
+/* c51.py's update: next_pmfs = target.get_action(next_obs), the categorical projection onto atoms (each target atom adds its d_m_l
+ * terms and then its d_m_u terms in ascending source order, as the reference's two index_add_ calls per row do), old_pmfs =
+ * online.get_action(obs, action), loss = mean(-(target_pmfs * old_pmfs.clamp(1e-5, 1 - 1e-5).log()).sum(-1)); the backward passes no
+ * gradient where the clamp is active.  grads is OVERWRITTEN; scalars_out (2) = {loss, mean (old_pmfs * atoms).sum(1)};
+ * next_pmfs_out and target_pmfs_out (M, n_atoms) may be NULL.  Two launches. */
+MI355PPO_API size_t mi355ppo_c51_workspace_bytes(int M, int O, int n_actions, int n_atoms);
+MI355PPO_API int mi355ppo_c51_fwd_bwd_f32(const float* ring_obs, const float* ring_next_obs, const float* ring_actions,
+                                          const float* ring_rewards, const float* ring_dones, const int64_t* batch_inds,
+                                          const int64_t* env_inds, int64_t slots, int n_envs, const float* online, const float* target,
+                                          const float* atoms, double gamma, double v_min, double v_max, float* grads, float* scalars_out,
+                                          float* next_pmfs_out, float* target_pmfs_out, int M, int O, int n_actions, int n_atoms,
+                                          void* workspace, size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_c51_fwd_bwd_f32_cpu(const float* ring_obs, const float* ring_next_obs, const float* ring_actions,
+                                              const float* ring_rewards, const float* ring_dones, const int64_t* batch_inds,
+                                              const int64_t* env_inds, int64_t slots, int n_envs, const float* online, const float* target,
+                                              const float* atoms, double gamma, double v_min, double v_max, float* grads,
+                                              float* scalars_out, float* next_pmfs_out, float* target_pmfs_out, int M, int O, int n_actions,
+                                              int n_atoms);
 
 #ifdef __cplusplus
 }

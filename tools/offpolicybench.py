@@ -1,12 +1,13 @@
 """ddpg_continuous_action.py / td3_continuous_action.py / sac_continuous_action.py with both ``MI355PPO_OFFPOLICY`` backends, in one
 process, alternating.
 
-    python tools/offpolicybench.py [--reps 20] [--scripts td3 ddpg sac]
+    python tools/offpolicybench.py [--reps 20] [--scripts td3 ddpg sac dqn]
 
 Times, at each script's defaults (batch 256) on a HalfCheetah-shaped (obs 17 / act 6) and a Humanoid-shaped (376 / 17) task:
 one rollout step including the action's copy to the host, one critic-only training step and one step with the delayed policy
 update.  The comparison is the ``torch`` backend on the same box in the same process; medians of ``--reps`` after a warm-up.
-Prints one JSON line per (script, shape).
+Prints one JSON line per (script, shape).  ``--scripts dqn`` times dqn.py and c51.py (batch 128) at a CartPole-shaped (obs 4 / 2
+actions) and a LunarLander-shaped (8 / 4) task: one greedy rollout step, one DQN update and one C51 update (101 atoms).
 """
 from __future__ import annotations
 
@@ -29,6 +30,49 @@ from cleanrl_amd.learner_offpolicy import OffPolicyLearner  # noqa: E402
 from cleanrl_amd.learner_sac import SACLearner  # noqa: E402
 
 SHAPES = {"halfcheetah": (17, 6), "humanoid": (376, 17)}
+DQN_SHAPES = {"cartpole": (4, 2), "lunarlander": (8, 4)}
+
+
+def make_dqn(c51, O, n, backend, dev, fill=4096):
+    from cleanrl_amd.agents import C51Network, DQNNetwork
+    from cleanrl_amd.learner_dqn import DQNLearner
+
+    torch.manual_seed(1)
+    np.random.seed(1)
+    rng = np.random.RandomState(1)
+    env = SimpleNamespace(single_observation_space=SimpleNamespace(shape=(O,)), single_action_space=E.SamplingDiscrete(n), num_envs=1)
+    mk = (lambda: C51Network(env).to(dev)) if c51 else (lambda: DQNNetwork(env).to(dev))
+    q, t = mk(), mk()
+    t.load_state_dict(q.state_dict())
+    args = SimpleNamespace(buffer_size=fill * 2, batch_size=128, learning_rate=2.5e-4, gamma=0.99, tau=1.0, n_atoms=101, v_min=-100, v_max=100)
+    L = DQNLearner(q, t, args, env, dev, c51=c51, backend=backend)
+    obs = rng.standard_normal((1, O)).astype(np.float32)
+    for i in range(fill):
+        nxt = rng.standard_normal((1, O)).astype(np.float32)
+        L.store(obs, nxt, np.array([env.single_action_space.sample()]), np.ones(1), np.array([i % 20 == 19]))
+        obs = nxt
+    return L, obs
+
+
+def bench_dqn(a, dev):
+    for shape, (O, n) in DQN_SHAPES.items():
+        learners = {(alg, b): make_dqn(alg == "c51", O, n, b, dev) for alg in ("dqn", "c51") for b in ("torch", "fused")}
+        legs = {"rollout_step": ("dqn", lambda L, obs: L.act(obs, 1, 0.0)), "dqn_update": ("dqn", lambda L, obs: L.train_step()),
+                "c51_update": ("c51", lambda L, obs: L.train_step())}
+        times = {leg: {b: [] for b in ("torch", "fused")} for leg in legs}
+        for rep in range(a.warmup + a.reps):
+            for leg, (alg, fn) in legs.items():
+                for b in ("torch", "fused"):                             # alternating: both backends see the same box state
+                    L, obs = learners[(alg, b)]
+                    us = timed(lambda: fn(L, obs), dev)
+                    if rep >= a.warmup:
+                        times[leg][b].append(us)
+        row = {"script": "dqn", "shape": shape, "obs_dim": O, "n_actions": n, "n_atoms": 101, "batch": 128, "device": str(dev), "reps": a.reps}
+        for leg in legs:
+            for b in ("torch", "fused"):
+                row[f"{leg}_{b}_us"] = round(statistics.median(times[leg][b]), 1)
+            row[f"{leg}_speedup"] = round(row[f"{leg}_torch_us"] / row[f"{leg}_fused_us"], 2)
+        print(json.dumps(row), flush=True)
 
 
 def make(script, O, A, backend, dev, fill=4096):
@@ -80,6 +124,9 @@ def main():
     a = ap.parse_args()
     dev = torch.device("cuda" if torch.cuda.is_available() and not a.no_cuda else "cpu")
     for script in a.scripts:
+        if script == "dqn":
+            bench_dqn(a, dev)
+            continue
         for shape, (O, A) in SHAPES.items():
             learners = {b: make(script, O, A, b, dev) for b in ("torch", "fused")}
             extra = (True,) if script == "sac" else ()          # SAC's target update runs every step (target_network_frequency 1)
