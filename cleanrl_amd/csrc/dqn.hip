@@ -254,13 +254,6 @@ __global__ __launch_bounds__(256) void dq_update_kernel(OpRing R, const float* _
     }
 }
 
-static int dq_shape(const char* fn, int M, int O, int n, int na) {
-    MI355_REQUIRE(M > 0 && dq_limits(O, n, na), MI355PPO_EINVAL,
-                  "%s: rows=%d obs_dim=%d n_actions=%d n_atoms=%d: the fused Q networks take 1 <= obs_dim <= %d, 2 <= n_actions <= %d, "
-                  "1 <= n_atoms <= %d, n_actions * n_atoms <= %d", fn, M, O, n, na, kDqMaxObs, kDqMaxAct, kDqMaxAtoms, kDqMaxOut);
-    return MI355PPO_OK;
-}
-
 static size_t dq_workspace(int M, int O, int n, int na) {
     if (M <= 0 || !dq_limits(O, n, na)) return 0;
     return (size_t)(2 * op_mp(M) + (int64_t)op_groups(M) * dq_count(O, n * na)) * sizeof(float);
@@ -296,10 +289,7 @@ extern "C" MI355PPO_API int mi355ppo_dqn_td_fwd_bwd_f32(const float* ring_obs, c
     if (int rc = dq_shape(fn, M, O, n_actions, 1)) return rc;
     OpRing R;
     if (int rc = op_ring_args(fn, R, ring_obs, ring_next_obs, ring_actions, ring_rewards, ring_dones, batch_inds, env_inds, slots, n_envs)) return rc;
-    const size_t need = dq_workspace(M, O, n_actions, 1);
-    MI355_REQUIRE(workspace && workspace_bytes >= need, MI355PPO_EWORKSPACE, "%s: workspace %zu bytes < required %zu", fn,
-                  workspace ? workspace_bytes : (size_t)0, need);
-    MI355_REQUIRE(aligned(workspace, 16), MI355PPO_EALIGN, "%s: workspace must be 16-byte aligned", fn);
+    if (int rc = op_workspace_ok(fn, workspace, workspace_bytes, dq_workspace(M, O, n_actions, 1))) return rc;
     hipStream_t s = as_stream(stream);
     const int Mp = (int)op_mp(M), G = op_groups(M);
     const int64_t P = dq_count(O, n_actions);
@@ -328,10 +318,7 @@ extern "C" MI355PPO_API int mi355ppo_c51_fwd_bwd_f32(const float* ring_obs, cons
     MI355_REQUIRE(n_atoms >= 2, MI355PPO_EINVAL, "%s: n_atoms=%d: the projection needs two atoms (delta_z = atoms[1] - atoms[0])", fn, n_atoms);
     OpRing R;
     if (int rc = op_ring_args(fn, R, ring_obs, ring_next_obs, ring_actions, ring_rewards, ring_dones, batch_inds, env_inds, slots, n_envs)) return rc;
-    const size_t need = dq_workspace(M, O, n_actions, n_atoms);
-    MI355_REQUIRE(workspace && workspace_bytes >= need, MI355PPO_EWORKSPACE, "%s: workspace %zu bytes < required %zu", fn,
-                  workspace ? workspace_bytes : (size_t)0, need);
-    MI355_REQUIRE(aligned(workspace, 16), MI355PPO_EALIGN, "%s: workspace must be 16-byte aligned", fn);
+    if (int rc = op_workspace_ok(fn, workspace, workspace_bytes, dq_workspace(M, O, n_actions, n_atoms))) return rc;
     hipStream_t s = as_stream(stream);
     const int Mp = (int)op_mp(M), G = op_groups(M);
     const int64_t P = dq_count(O, n_actions * n_atoms);

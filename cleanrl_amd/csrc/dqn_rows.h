@@ -23,6 +23,13 @@ constexpr int kDqMaxOut = 512;       // n * n_atoms
 MI355_HD bool dq_limits(int O, int n, int na) {
     return O >= 1 && O <= kDqMaxObs && n >= 2 && n <= kDqMaxAct && na >= 1 && na <= kDqMaxAtoms && n * na <= kDqMaxOut;
 }
+// host-side argument check of the device entry points and of their twins
+inline int dq_shape(const char* fn, int M, int O, int n, int na) {
+    MI355_REQUIRE(M > 0 && dq_limits(O, n, na), MI355PPO_EINVAL,
+                  "%s: rows=%d obs_dim=%d n_actions=%d n_atoms=%d: the fused Q networks take 1 <= obs_dim <= %d, 2 <= n_actions <= %d, "
+                  "1 <= n_atoms <= %d, n_actions * n_atoms <= %d", fn, M, O, n, na, kDqMaxObs, kDqMaxAct, kDqMaxAtoms, kDqMaxOut);
+    return MI355PPO_OK;
+}
 MI355_HD int64_t dq_count(int O, int J) { return (int64_t)kDqH1 * O + kDqH1 + kDqH2 * kDqH1 + kDqH2 + (int64_t)J * kDqH2 + J; }
 
 struct DqNet {

@@ -1305,15 +1305,17 @@ extern "C" MI355PPO_API int mi355ppo_pqn_lstm_td_fwd_bwd_f32_cpu(const float* h,
 // ------------------------------------------------------------------------------------------------ DDPG / TD3 (offpolicy.hip)
 // The device's element functions (offpolicy_rows.h) in the device's orders: dot products ascending from 0.0f, weight gradients per
 // tile of kOpRows rows, tiles into their group's partial, groups ascending into the flat gradient, f64 slot folds for the scalars.
-// Every output equals the device's bit for bit (op_tanh uses no libm function).
+// Every output equals the device's bit for bit (op_tanh uses no libm function).  The tile helpers up to tile_backward_host serve
+// the SAC and DQN / C51 twins below as well: the three families run the same three-layer network at different widths.
 namespace {
 
 constexpr int kOpXSh = kOpMaxObs + kOpMaxAct;
 
+// out[r, j] = act(b[j] + sum_k xin[r, k] * W[j, k]) for the tile's kOpRows rows and j < J
 template <bool RELU>
-void op_fwd_host(const float* xin, int xs, int K, const float* W, const float* b, float* out, int os) {
-    for (int j = 0; j < kOpH; ++j)
-        for (int r = 0; r < kOpRows; ++r) {
+void tile_layer_host(const float* xin, int xs, int K, const float* W, const float* b, int J, float* out, int os) {
+    for (int r = 0; r < kOpRows; ++r)
+        for (int j = 0; j < J; ++j) {
             float acc = 0.0f;
             for (int k = 0; k < K; ++k) acc = op_mac(acc, xin[r * xs + k], W[(int64_t)j * K + k]);
             const float v = acc + b[j];
@@ -1321,20 +1323,12 @@ void op_fwd_host(const float* xin, int xs, int K, const float* W, const float* b
         }
 }
 
-void op_head_host(const float* h, int hs, const float* W, const float* b, int J, float* out) {
+// io[r, k] = relu'(io[r, k]) * sum_{j < J} dz[r * ds + j] * W[j * K + k] for k < K (in place over the layer's ReLU output)
+void tile_dgrad_host(const float* dz, int ds, int J, const float* W, int K, float* io, int ios) {
     for (int r = 0; r < kOpRows; ++r)
-        for (int j = 0; j < J; ++j) {
+        for (int k = 0; k < K; ++k) {
             float acc = 0.0f;
-            for (int k = 0; k < kOpH; ++k) acc = op_mac(acc, h[r * hs + k], W[j * kOpH + k]);
-            out[r * J + j] = acc + b[j];
-        }
-}
-
-void op_dgrad_host(const float* dz, int ds, int J, const float* W, int ldw, float* io, int ios) {
-    for (int k = 0; k < kOpH; ++k)
-        for (int r = 0; r < kOpRows; ++r) {
-            float acc = 0.0f;
-            for (int j = 0; j < J; ++j) acc = op_mac(acc, dz[r * ds + j], W[(int64_t)j * ldw + k]);
+            for (int j = 0; j < J; ++j) acc = op_mac(acc, dz[r * ds + j], W[(int64_t)j * K + k]);
             io[r * ios + k] = op_relu_bwd(io[r * ios + k], acc);
         }
 }
@@ -1371,16 +1365,75 @@ void op_fold_host(const float* part, int G, int64_t P, float* grads) {
     }
 }
 
+// The batch's rows: the ring's (batch_inds[m], env_inds[m]), both clamped into range as the kernels' ring_row clamps them
+// (offpolicy_wg.h), or, without indices (the rollout's observations), m itself.
+struct TileRows {
+    const int64_t *bi, *ei;
+    int64_t slots;
+    int N;
+    int64_t operator()(int m) const { return bi ? op_clamp(bi[m], slots) * N + op_clamp(ei[m], N) : (int64_t)m; }
+};
+
+// x[r, k] = src[row(r0 + r), k] for k < O and the tile's kOpRows rows, zero past the batch's `rows`
+void tile_gather_host(const float* src, const TileRows& row, int r0, int rows, int O, float* x, int xs) {
+    for (int r = 0; r < kOpRows; ++r) {
+        const bool in = r0 + r < rows;
+        const float* s = src + (in ? row(r0 + r) : 0) * O;
+        for (int k = 0; k < O; ++k) x[r * xs + k] = in ? s[k] : 0.0f;
+    }
+}
+
+// One tile of a three-layer network: the input rows (stride xs) and the two hidden layers' outputs (widths H1 / H2, their strides).
+struct TileNet {
+    float* x;
+    int xs;
+    float* h1;
+    int H1;
+    float* h2;
+    int H2;
+};
+
+// Linear(K, H1) - ReLU - Linear(H1, H2) - ReLU: what every network of the three families starts with
+template <class Net>
+void tile_hidden_host(const Net& n, int K, const TileNet& B) {
+    tile_layer_host<true>(B.x, B.xs, K, n.w1, n.b1, B.H1, B.h1, B.H1);
+    tile_layer_host<true>(B.h1, B.H1, B.H1, n.w2, n.b2, B.H2, B.h2, B.H2);
+}
+
+// ... - Linear(H2, n.J) into out (row stride os): the whole forward of an OpNet or a DqNet
+template <class Net>
+void tile_forward_host(const Net& n, int K, const TileNet& B, float* out, int os) {
+    tile_hidden_host(n, K, B);
+    tile_layer_host<false>(B.h2, B.H2, B.H2, n.w3, n.b3, n.J, out, os);
+}
+
+// The backward below h2, which holds d loss / d (layer 2's output), masked: layer 2's weight gradient, the masked data gradient
+// into h1, layer 1's weight gradient -- into the group's partial p at the offsets off.
+template <class Net, class Off>
+void tile_backward_lower_host(const Net& n, const Off& off, int K, const TileNet& B, float* p, bool first, int nr) {
+    op_wgrad_host(B.h2, B.H2, B.h1, B.H1, B.H2, B.H1, p + off.w2, p + off.b2, first, nr);
+    tile_dgrad_host(B.h2, B.H2, B.H2, n.w2, B.H1, B.h1, B.H1);
+    op_wgrad_host(B.h1, B.H1, B.x, B.xs, B.H1, K, p + off.w1, p + off.b1, first, nr);
+}
+
+// The whole chain from dz = d loss / d (layer 3's output), row stride ds: wgrad, dgrad, wgrad, dgrad, wgrad.
+template <class Net, class Off>
+void tile_backward_host(const Net& n, const Off& off, int K, const float* dz, int ds, const TileNet& B, float* p, bool first, int nr) {
+    op_wgrad_host(dz, ds, B.h2, B.H2, n.J, B.H2, p + off.w3, p + off.b3, first, nr);
+    tile_dgrad_host(dz, ds, n.J, n.w3, B.H2, B.h2, B.H2);
+    tile_backward_lower_host(n, off, K, B, p, first, nr);
+}
+
 struct OpTile {
     std::vector<float> x, a1, a2, c1, c2;
     float mu[kOpRows * kOpMaxAct], tv[kOpRows * kOpMaxAct], qv[2 * kOpRows], dq[kOpRows];
     OpTile() : x(kOpRows * kOpXSh), a1(kOpRows * kOpH), a2(kOpRows * kOpH), c1(kOpRows * kOpH), c2(kOpRows * kOpH) {}
+    TileNet a() { return TileNet{x.data(), kOpXSh, a1.data(), kOpH, a2.data(), kOpH}; }       // the actor's hidden layers (or a lone critic's)
+    TileNet c() { return TileNet{x.data(), kOpXSh, c1.data(), kOpH, c2.data(), kOpH}; }       // a critic's next to the actor's
 };
 
 void op_actor_host(const OpNet& an, const float* scale, const float* bias, OpTile& T) {
-    op_fwd_host<true>(T.x.data(), kOpXSh, an.K, an.w1, an.b1, T.a1.data(), kOpH);
-    op_fwd_host<true>(T.a1.data(), kOpH, kOpH, an.w2, an.b2, T.a2.data(), kOpH);
-    op_head_host(T.a2.data(), kOpH, an.w3, an.b3, an.J, T.mu);
+    tile_forward_host(an, an.K, T.a(), T.mu, an.J);
     for (int r = 0; r < kOpRows; ++r)
         for (int a = 0; a < an.J; ++a) {
             const float th = op_tanh(T.mu[r * an.J + a]);
@@ -1389,15 +1442,26 @@ void op_actor_host(const OpNet& an, const float* scale, const float* bias, OpTil
         }
 }
 
-int op_shape_cpu(const char* fn, int M, int O, int A) {
-    MI355_REQUIRE(M > 0 && O > 0 && O <= kOpMaxObs && A > 0 && A <= kOpMaxAct, MI355PPO_EINVAL,
-                  "%s: rows=%d obs_dim=%d act_dim=%d: the off-policy networks take 1 <= obs_dim <= %d, 1 <= act_dim <= %d", fn, M, O, A,
-                  kOpMaxObs, kOpMaxAct);
-    return MI355PPO_OK;
+// q of the tile's (obs | action) rows through the n_critics target critics into T.qv (critic c at c * kOpRows)
+void op_target_q_host(const float* target_critics, int n_critics, int O, int A, OpTile& T) {
+    for (int c = 0; c < n_critics; ++c) {
+        const OpNet qn = op_net(target_critics + c * op_critic_count(O, A), O + A, 1);
+        tile_forward_host(qn, qn.K, T.a(), T.qv + c * kOpRows, 1);
+    }
 }
 
-inline int64_t op_row_cpu(const int64_t* bi, const int64_t* ei, int m, int64_t slots, int N) {
-    return op_clamp(bi[m], slots) * N + op_clamp(ei[m], N);
+// One critic over the tile's (obs | action) rows, forward into q and back to the action: out[r * A + a] = dq[r] * d q / d action[r, a].
+void op_critic_daction_host(const OpNet& qn, const float* dq, int O, int A, OpTile& T, float* q, float* out) {
+    const TileNet B = T.c();
+    tile_forward_host(qn, qn.K, B, q, 1);
+    tile_dgrad_host(dq, 1, 1, qn.w3, kOpH, B.h2, kOpH);
+    tile_dgrad_host(B.h2, kOpH, kOpH, qn.w2, kOpH, B.h1, kOpH);
+    for (int r = 0; r < kOpRows; ++r)
+        for (int a = 0; a < A; ++a) {
+            float acc = 0.0f;
+            for (int j = 0; j < kOpH; ++j) acc = op_mac(acc, B.h1[r * kOpH + j], qn.w1[(int64_t)j * qn.K + O + a]);
+            out[r * A + a] = acc;
+        }
 }
 
 }  // namespace
@@ -1425,12 +1489,12 @@ extern "C" MI355PPO_API int mi355ppo_ddpg_act_f32_cpu(const float* obs, const fl
                                                      float* actions_out, int N, int O, int A) {
     const char* fn = "mi355ppo_ddpg_act_f32_cpu";
     MI355_REQUIRE(obs && actor_params && action_scale && action_bias && low && high && actions_out, MI355PPO_EINVAL, "%s: null pointer", fn);
-    if (int rc = op_shape_cpu(fn, N, O, A)) return rc;
+    if (int rc = op_shape(fn, N, O, A)) return rc;
     const OpNet an = op_net(actor_params, O, A);
+    const TileRows plain{nullptr, nullptr, 0, 0};
     OpTile T;
     for (int r0 = 0; r0 < N; r0 += kOpRows) {
-        for (int r = 0; r < kOpRows; ++r)
-            for (int k = 0; k < O; ++k) T.x[r * kOpXSh + k] = (r0 + r < N) ? obs[(int64_t)(r0 + r) * O + k] : 0.0f;
+        tile_gather_host(obs, plain, r0, N, O, T.x.data(), kOpXSh);
         op_actor_host(an, action_scale, action_bias, T);
         for (int r = 0; r < kOpRows && r0 + r < N; ++r)
             for (int a = 0; a < A; ++a)
@@ -1451,15 +1515,13 @@ extern "C" MI355PPO_API int mi355ppo_td3_target_f32_cpu(const float* ring_next_o
                   MI355PPO_EINVAL, "%s: null pointer", fn);
     MI355_REQUIRE((n_critics == 1 || n_critics == 2) && slots > 0 && n_envs > 0, MI355PPO_EINVAL,
                   "%s: n_critics=%d must be 1 or 2, slots=%lld and n_envs=%d positive", fn, n_critics, (long long)slots, n_envs);
-    if (int rc = op_shape_cpu(fn, M, O, A)) return rc;
+    if (int rc = op_shape(fn, M, O, A)) return rc;
     const OpNet an = op_net(target_actor, O, A);
-    const int64_t Pq = op_critic_count(O, A);
+    const TileRows ring{batch_inds, env_inds, slots, n_envs};
     const float pn = (float)policy_noise, nc = (float)noise_clip, lo0 = (float)low0, hi0 = (float)high0, g = (float)gamma;
     OpTile T;
     for (int r0 = 0; r0 < M; r0 += kOpRows) {
-        for (int r = 0; r < kOpRows; ++r)
-            for (int k = 0; k < O; ++k)
-                T.x[r * kOpXSh + k] = (r0 + r < M) ? ring_next_obs[op_row_cpu(batch_inds, env_inds, r0 + r, slots, n_envs) * O + k] : 0.0f;
+        tile_gather_host(ring_next_obs, ring, r0, M, O, T.x.data(), kOpXSh);
         op_actor_host(an, action_scale, action_bias, T);
         for (int r = 0; r < kOpRows && r0 + r < M; ++r)
             for (int a = 0; a < A; ++a) {
@@ -1467,14 +1529,9 @@ extern "C" MI355PPO_API int mi355ppo_td3_target_f32_cpu(const float* ring_next_o
                 if (noise) v = op_smooth(v, noise[(int64_t)(r0 + r) * A + a], pn, nc, action_scale[a], lo0, hi0);
                 if (next_actions_out) next_actions_out[(int64_t)(r0 + r) * A + a] = v;
             }
-        for (int c = 0; c < n_critics; ++c) {
-            const OpNet qn = op_net(target_critics + c * Pq, O + A, 1);
-            op_fwd_host<true>(T.x.data(), kOpXSh, O + A, qn.w1, qn.b1, T.a1.data(), kOpH);
-            op_fwd_host<true>(T.a1.data(), kOpH, kOpH, qn.w2, qn.b2, T.a2.data(), kOpH);
-            op_head_host(T.a2.data(), kOpH, qn.w3, qn.b3, 1, T.qv + c * kOpRows);
-        }
+        op_target_q_host(target_critics, n_critics, O, A, T);
         for (int r = 0; r < kOpRows && r0 + r < M; ++r) {
-            const int64_t row = op_row_cpu(batch_inds, env_inds, r0 + r, slots, n_envs);
+            const int64_t row = ring(r0 + r);
             const float q = (n_critics == 2) ? op_min(T.qv[r], T.qv[kOpRows + r]) : T.qv[r];
             next_q_value[r0 + r] = op_td_target(ring_rewards[row], ring_dones[row], g, q);
         }
@@ -1491,10 +1548,11 @@ extern "C" MI355PPO_API int mi355ppo_td3_critic_fwd_bwd_f32_cpu(const float* rin
                   "%s: null pointer", fn);
     MI355_REQUIRE((n_critics == 1 || n_critics == 2) && slots > 0 && n_envs > 0, MI355PPO_EINVAL,
                   "%s: n_critics=%d must be 1 or 2, slots=%lld and n_envs=%d positive", fn, n_critics, (long long)slots, n_envs);
-    if (int rc = op_shape_cpu(fn, M, O, A)) return rc;
+    if (int rc = op_shape(fn, M, O, A)) return rc;
     const int K = O + A, G = op_groups(M), ntiles = op_tiles(M);
     const int64_t Pq = op_critic_count(O, A), P = n_critics * Pq;
     const OpOff off = op_off(K, 1);
+    const TileRows ring{batch_inds, env_inds, slots, n_envs};
     const float norm = (float)(2.0 / (double)M);
     std::vector<float> part((size_t)G * P), rows((size_t)4 * M);
     OpTile T;
@@ -1504,14 +1562,9 @@ extern "C" MI355PPO_API int mi355ppo_td3_critic_fwd_bwd_f32_cpu(const float* rin
             const int g = tl % G, r0 = tl * kOpRows, nr = (M - r0 < kOpRows) ? M - r0 : kOpRows;
             const bool first = tl == g;
             float* p = part.data() + ((int64_t)g * n_critics + c) * Pq;
-            for (int r = 0; r < kOpRows; ++r) {
-                const int64_t row = r < nr ? op_row_cpu(batch_inds, env_inds, r0 + r, slots, n_envs) : 0;
-                for (int k = 0; k < K; ++k)
-                    T.x[r * kOpXSh + k] = r < nr ? (k < O ? ring_obs[row * O + k] : ring_actions[row * A + (k - O)]) : 0.0f;
-            }
-            op_fwd_host<true>(T.x.data(), kOpXSh, K, qn.w1, qn.b1, T.a1.data(), kOpH);
-            op_fwd_host<true>(T.a1.data(), kOpH, kOpH, qn.w2, qn.b2, T.a2.data(), kOpH);
-            op_head_host(T.a2.data(), kOpH, qn.w3, qn.b3, 1, T.qv);
+            tile_gather_host(ring_obs, ring, r0, M, O, T.x.data(), kOpXSh);
+            tile_gather_host(ring_actions, ring, r0, M, A, T.x.data() + O, kOpXSh);
+            tile_forward_host(qn, K, T.a(), T.qv, 1);
             for (int r = 0; r < kOpRows; ++r) {
                 float d = 0.0f;
                 if (r < nr) {
@@ -1522,11 +1575,7 @@ extern "C" MI355PPO_API int mi355ppo_td3_critic_fwd_bwd_f32_cpu(const float* rin
                 }
                 T.dq[r] = d;
             }
-            op_wgrad_host(T.dq, 1, T.a2.data(), kOpH, 1, kOpH, p + off.w3, p + off.b3, first, nr);
-            op_dgrad_host(T.dq, 1, 1, qn.w3, kOpH, T.a2.data(), kOpH);
-            op_wgrad_host(T.a2.data(), kOpH, T.a1.data(), kOpH, kOpH, kOpH, p + off.w2, p + off.b2, first, nr);
-            op_dgrad_host(T.a2.data(), kOpH, kOpH, qn.w2, kOpH, T.a1.data(), kOpH);
-            op_wgrad_host(T.a1.data(), kOpH, T.x.data(), kOpXSh, kOpH, K, p + off.w1, p + off.b1, first, nr);
+            tile_backward_host(qn, off, K, T.dq, 1, T.a(), p, first, nr);
         }
     }
     op_fold_host(part.data(), G, P, grads);
@@ -1542,11 +1591,12 @@ extern "C" MI355PPO_API int mi355ppo_td3_actor_fwd_bwd_f32_cpu(const float* ring
     MI355_REQUIRE(ring_obs && actor && qf1 && action_scale && action_bias && grads && actor_loss_out && batch_inds && env_inds, MI355PPO_EINVAL,
                   "%s: null pointer", fn);
     MI355_REQUIRE(slots > 0 && n_envs > 0, MI355PPO_EINVAL, "%s: slots=%lld n_envs=%d must be positive", fn, (long long)slots, n_envs);
-    if (int rc = op_shape_cpu(fn, M, O, A)) return rc;
-    const int K = O + A, G = op_groups(M), ntiles = op_tiles(M);
+    if (int rc = op_shape(fn, M, O, A)) return rc;
+    const int G = op_groups(M), ntiles = op_tiles(M);
     const int64_t Pa = op_actor_count(O, A);
-    const OpNet an = op_net(actor, O, A), qn = op_net(qf1, K, 1);
+    const OpNet an = op_net(actor, O, A), qn = op_net(qf1, O + A, 1);
     const OpOff off = op_off(O, A);
+    const TileRows ring{batch_inds, env_inds, slots, n_envs};
     const float dqv = (float)(-1.0 / (double)M);
     std::vector<float> part((size_t)G * Pa), rows(M);
     OpTile T;
@@ -1554,32 +1604,19 @@ extern "C" MI355PPO_API int mi355ppo_td3_actor_fwd_bwd_f32_cpu(const float* ring
         const int g = tl % G, r0 = tl * kOpRows, nr = (M - r0 < kOpRows) ? M - r0 : kOpRows;
         const bool first = tl == g;
         float* p = part.data() + (int64_t)g * Pa;
-        for (int r = 0; r < kOpRows; ++r) {
-            const int64_t row = r < nr ? op_row_cpu(batch_inds, env_inds, r0 + r, slots, n_envs) : 0;
-            for (int k = 0; k < O; ++k) T.x[r * kOpXSh + k] = r < nr ? ring_obs[row * O + k] : 0.0f;
-        }
+        tile_gather_host(ring_obs, ring, r0, M, O, T.x.data(), kOpXSh);
         op_actor_host(an, action_scale, action_bias, T);
-        op_fwd_host<true>(T.x.data(), kOpXSh, K, qn.w1, qn.b1, T.c1.data(), kOpH);
-        op_fwd_host<true>(T.c1.data(), kOpH, kOpH, qn.w2, qn.b2, T.c2.data(), kOpH);
-        op_head_host(T.c2.data(), kOpH, qn.w3, qn.b3, 1, T.qv);
+        for (int r = 0; r < kOpRows; ++r) T.dq[r] = r < nr ? dqv : 0.0f;
+        op_critic_daction_host(qn, T.dq, O, A, T, T.qv, T.mu);
         for (int r = 0; r < kOpRows; ++r) {
             if (r < nr) rows[r0 + r] = T.qv[r];
-            T.dq[r] = r < nr ? dqv : 0.0f;
-        }
-        op_dgrad_host(T.dq, 1, 1, qn.w3, kOpH, T.c2.data(), kOpH);
-        op_dgrad_host(T.c2.data(), kOpH, kOpH, qn.w2, kOpH, T.c1.data(), kOpH);
-        for (int r = 0; r < kOpRows; ++r)
             for (int a = 0; a < A; ++a) {
-                float acc = 0.0f;
-                for (int j = 0; j < kOpH; ++j) acc = op_mac(acc, T.c1[r * kOpH + j], qn.w1[(int64_t)j * K + O + a]);
-                if (dq_daction_out && r < nr) dq_daction_out[(int64_t)(r0 + r) * A + a] = acc;
-                T.mu[r * A + a] = op_dmu(acc, action_scale[a], T.tv[r * A + a]);
+                float& v = T.mu[r * A + a];
+                if (dq_daction_out && r < nr) dq_daction_out[(int64_t)(r0 + r) * A + a] = v;
+                v = op_dmu(v, action_scale[a], T.tv[r * A + a]);
             }
-        op_wgrad_host(T.mu, A, T.a2.data(), kOpH, A, kOpH, p + off.w3, p + off.b3, first, nr);
-        op_dgrad_host(T.mu, A, A, an.w3, kOpH, T.a2.data(), kOpH);
-        op_wgrad_host(T.a2.data(), kOpH, T.a1.data(), kOpH, kOpH, kOpH, p + off.w2, p + off.b2, first, nr);
-        op_dgrad_host(T.a2.data(), kOpH, kOpH, an.w2, kOpH, T.a1.data(), kOpH);
-        op_wgrad_host(T.a1.data(), kOpH, T.x.data(), kOpXSh, kOpH, O, p + off.w1, p + off.b1, first, nr);
+        }
+        tile_backward_host(an, off, O, T.mu, A, T.a(), p, first, nr);
     }
     op_fold_host(part.data(), G, Pa, grads);
     *actor_loss_out = -1.0f * op_fold_mean_host(rows.data(), M);
@@ -1597,7 +1634,7 @@ extern "C" MI355PPO_API int mi355ppo_polyak_f32_cpu(const float* params, float* 
 
 // ------------------------------------------------------------------------------------------------ SAC (sac.hip)
 // The device's element functions (sac_rows.h over offpolicy_rows.h) in the device's orders; every output equals the device's bit for
-// bit (op_exp / op_log / op_tanh use no libm function).
+// bit (op_exp / op_log / op_tanh use no libm function).  The tile helpers are the DDPG / TD3 section's.
 namespace {
 
 struct SacTileH {
@@ -1608,10 +1645,9 @@ struct SacTileH {
 // get_action of one tile (wg_sac_policy): T.x's rows hold the observations
 void sac_policy_host(const SacNet& an, const float* scale, const float* bias, const float* eps, int r0, int rows, OpTile& T, SacTileH& S) {
     const int A = an.A;
-    op_fwd_host<true>(T.x.data(), kOpXSh, an.K, an.w1, an.b1, T.a1.data(), kOpH);
-    op_fwd_host<true>(T.a1.data(), kOpH, kOpH, an.w2, an.b2, T.a2.data(), kOpH);
-    op_head_host(T.a2.data(), kOpH, an.wm, an.bm, A, S.mu);
-    op_head_host(T.a2.data(), kOpH, an.ws, an.bs, A, S.us);
+    tile_hidden_host(an, an.K, T.a());
+    tile_layer_host<false>(T.a2.data(), kOpH, kOpH, an.wm, an.bm, A, S.mu, A);
+    tile_layer_host<false>(T.a2.data(), kOpH, kOpH, an.ws, an.bs, A, S.us, A);
     for (int r = 0; r < kOpRows; ++r) {
         float acc = 0.0f;
         for (int a = 0; a < A; ++a) {
@@ -1660,15 +1696,13 @@ extern "C" MI355PPO_API int mi355ppo_sac_policy_f32_cpu(const float* obs, const 
     MI355_REQUIRE((batch_inds == nullptr) == (env_inds == nullptr), MI355PPO_EINVAL, "%s: batch_inds and env_inds come together", fn);
     MI355_REQUIRE(!batch_inds || (slots > 0 && n_envs > 0), MI355PPO_EINVAL, "%s: slots=%lld n_envs=%d must be positive", fn, (long long)slots,
                   n_envs);
-    if (int rc = op_shape_cpu(fn, rows, O, A)) return rc;
+    if (int rc = op_shape(fn, rows, O, A)) return rc;
     const SacNet an = sac_net(actor, O, A);
+    const TileRows ring{batch_inds, env_inds, slots, n_envs};
     OpTile T;
     SacTileH S;
     for (int r0 = 0; r0 < rows; r0 += kOpRows) {
-        for (int r = 0; r < kOpRows; ++r) {
-            const int64_t row = (r0 + r < rows) ? (batch_inds ? op_row_cpu(batch_inds, env_inds, r0 + r, slots, n_envs) : (int64_t)(r0 + r)) : 0;
-            for (int k = 0; k < O; ++k) T.x[r * kOpXSh + k] = (r0 + r < rows) ? obs[row * O + k] : 0.0f;
-        }
+        tile_gather_host(obs, ring, r0, rows, O, T.x.data(), kOpXSh);
         sac_policy_host(an, action_scale, action_bias, eps, r0, rows, T, S);
         for (int r = 0; r < kOpRows && r0 + r < rows; ++r) {
             if (actions_out)
@@ -1689,28 +1723,21 @@ extern "C" MI355PPO_API int mi355ppo_sac_target_f32_cpu(const float* ring_next_o
                       next_q_value && batch_inds && env_inds,
                   MI355PPO_EINVAL, "%s: null pointer", fn);
     MI355_REQUIRE(slots > 0 && n_envs > 0, MI355PPO_EINVAL, "%s: slots=%lld n_envs=%d must be positive", fn, (long long)slots, n_envs);
-    if (int rc = op_shape_cpu(fn, M, O, A)) return rc;
+    if (int rc = op_shape(fn, M, O, A)) return rc;
     const SacNet an = sac_net(actor, O, A);
-    const int64_t Pq = op_critic_count(O, A);
+    const TileRows ring{batch_inds, env_inds, slots, n_envs};
     const float g = (float)gamma;
     OpTile T;
     SacTileH S;
     for (int r0 = 0; r0 < M; r0 += kOpRows) {
-        for (int r = 0; r < kOpRows; ++r)
-            for (int k = 0; k < O; ++k)
-                T.x[r * kOpXSh + k] = (r0 + r < M) ? ring_next_obs[op_row_cpu(batch_inds, env_inds, r0 + r, slots, n_envs) * O + k] : 0.0f;
+        tile_gather_host(ring_next_obs, ring, r0, M, O, T.x.data(), kOpXSh);
         sac_policy_host(an, action_scale, action_bias, eps, r0, M, T, S);
         if (next_actions_out)
             for (int r = 0; r < kOpRows && r0 + r < M; ++r)
                 for (int a = 0; a < A; ++a) next_actions_out[(int64_t)(r0 + r) * A + a] = T.x[r * kOpXSh + O + a];
-        for (int c = 0; c < 2; ++c) {
-            const OpNet qn = op_net(target_critics + c * Pq, O + A, 1);
-            op_fwd_host<true>(T.x.data(), kOpXSh, O + A, qn.w1, qn.b1, T.a1.data(), kOpH);
-            op_fwd_host<true>(T.a1.data(), kOpH, kOpH, qn.w2, qn.b2, T.a2.data(), kOpH);
-            op_head_host(T.a2.data(), kOpH, qn.w3, qn.b3, 1, T.qv + c * kOpRows);
-        }
+        op_target_q_host(target_critics, 2, O, A, T);
         for (int r = 0; r < kOpRows && r0 + r < M; ++r) {
-            const int64_t row = op_row_cpu(batch_inds, env_inds, r0 + r, slots, n_envs);
+            const int64_t row = ring(r0 + r);
             next_q_value[r0 + r] = op_td_target(ring_rewards[row], ring_dones[row], g, sac_soft_q(T.qv[r], T.qv[kOpRows + r], alpha[0], S.lpr[r]));
             if (log_pi_out) log_pi_out[r0 + r] = S.lpr[r];
         }
@@ -1727,11 +1754,12 @@ extern "C" MI355PPO_API int mi355ppo_sac_actor_fwd_bwd_f32_cpu(const float* ring
     MI355_REQUIRE(ring_obs && actor && critics && action_scale && action_bias && eps && alpha && grads && actor_loss_out && batch_inds && env_inds,
                   MI355PPO_EINVAL, "%s: null pointer", fn);
     MI355_REQUIRE(slots > 0 && n_envs > 0, MI355PPO_EINVAL, "%s: slots=%lld n_envs=%d must be positive", fn, (long long)slots, n_envs);
-    if (int rc = op_shape_cpu(fn, M, O, A)) return rc;
+    if (int rc = op_shape(fn, M, O, A)) return rc;
     const int K = O + A, G = op_groups(M), ntiles = op_tiles(M);
     const int64_t Pa = sac_actor_count(O, A), Pq = op_critic_count(O, A);
     const SacNet an = sac_net(actor, O, A);
     const SacOff off = sac_off(O, A);
+    const TileRows ring{batch_inds, env_inds, slots, n_envs};
     const float inv_m = (float)(1.0 / (double)M), al = alpha[0];
     const float one[kOpRows] = {1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f};
     std::vector<float> part((size_t)G * Pa), rows(M);
@@ -1741,26 +1769,10 @@ extern "C" MI355PPO_API int mi355ppo_sac_actor_fwd_bwd_f32_cpu(const float* ring
         const int g = tl % G, r0 = tl * kOpRows, nr = (M - r0 < kOpRows) ? M - r0 : kOpRows;
         const bool first = tl == g;
         float* p = part.data() + (int64_t)g * Pa;
-        for (int r = 0; r < kOpRows; ++r) {
-            const int64_t row = r < nr ? op_row_cpu(batch_inds, env_inds, r0 + r, slots, n_envs) : 0;
-            for (int k = 0; k < O; ++k) T.x[r * kOpXSh + k] = r < nr ? ring_obs[row * O + k] : 0.0f;
-        }
+        tile_gather_host(ring_obs, ring, r0, M, O, T.x.data(), kOpXSh);
         sac_policy_host(an, action_scale, action_bias, eps, r0, M, T, S);
-        for (int c = 0; c < 2; ++c) {
-            const OpNet qn = op_net(critics + c * Pq, K, 1);
-            op_fwd_host<true>(T.x.data(), kOpXSh, K, qn.w1, qn.b1, T.c1.data(), kOpH);
-            op_fwd_host<true>(T.c1.data(), kOpH, kOpH, qn.w2, qn.b2, T.c2.data(), kOpH);
-            op_head_host(T.c2.data(), kOpH, qn.w3, qn.b3, 1, T.qv + c * kOpRows);
-            op_dgrad_host(one, 1, 1, qn.w3, kOpH, T.c2.data(), kOpH);
-            op_dgrad_host(T.c2.data(), kOpH, kOpH, qn.w2, kOpH, T.c1.data(), kOpH);
-            float* gq = c == 0 ? S.g1 : S.g2;
-            for (int r = 0; r < kOpRows; ++r)
-                for (int a = 0; a < A; ++a) {
-                    float acc = 0.0f;
-                    for (int j = 0; j < kOpH; ++j) acc = op_mac(acc, T.c1[r * kOpH + j], qn.w1[(int64_t)j * K + O + a]);
-                    gq[r * A + a] = acc;
-                }
-        }
+        for (int c = 0; c < 2; ++c)
+            op_critic_daction_host(op_net(critics + c * Pq, K, 1), one, O, A, T, T.qv + c * kOpRows, c == 0 ? S.g1 : S.g2);
         for (int r = 0; r < kOpRows; ++r) {
             const float q1 = T.qv[r], q2 = T.qv[kOpRows + r];
             if (r < nr) {
@@ -1790,9 +1802,7 @@ extern "C" MI355PPO_API int mi355ppo_sac_actor_fwd_bwd_f32_cpu(const float* ring
         op_wgrad_host(S.mu, A, T.a2.data(), kOpH, A, kOpH, p + off.wm, p + off.bm, first, nr);
         op_wgrad_host(S.us, A, T.a2.data(), kOpH, A, kOpH, p + off.ws, p + off.bs, first, nr);
         sac_dgrad2_host(S.mu, an.wm, S.us, an.ws, A, T.a2.data());
-        op_wgrad_host(T.a2.data(), kOpH, T.a1.data(), kOpH, kOpH, kOpH, p + off.w2, p + off.b2, first, nr);
-        op_dgrad_host(T.a2.data(), kOpH, kOpH, an.w2, kOpH, T.a1.data(), kOpH);
-        op_wgrad_host(T.a1.data(), kOpH, T.x.data(), kOpXSh, kOpH, O, p + off.w1, p + off.b1, first, nr);
+        tile_backward_lower_host(an, off, O, T.a(), p, first, nr);
     }
     op_fold_host(part.data(), G, Pa, grads);
     *actor_loss_out = 1.0f * op_fold_mean_host(rows.data(), M);
@@ -1841,7 +1851,7 @@ extern "C" MI355PPO_API int mi355ppo_sac_alpha_f32_cpu(const float* log_pi, int 
 // The device's element functions (dqn_rows.h over sac_rows.h / offpolicy_rows.h) in the device's orders: tiles of kOpRows rows, dot
 // products ascending from 0.0f, the softmax and the projection per atom in ascending order, weight gradients per tile into their
 // group's partial, groups ascending into the flat gradient, f64 slot folds for the scalars.  Every output equals the device's bit
-// for bit.
+// for bit.  The tile helpers are the DDPG / TD3 section's, at QNetwork's widths.
 namespace {
 
 struct DqTile {
@@ -1851,26 +1861,12 @@ struct DqTile {
     DqTile()
         : x(kOpRows * kDqMaxObs), h1(kOpRows * kDqH1), h2(kOpRows * kDqH2), z(kOpRows * kDqMaxOut), pl(kOpRows * kDqMaxAtoms),
           pu(kOpRows * kDqMaxAtoms), pdl(kOpRows * kDqMaxAtoms), pdu(kOpRows * kDqMaxAtoms), tp(kOpRows * kDqMaxAtoms) {}
+    TileNet net() { return TileNet{x.data(), kDqMaxObs, h1.data(), kDqH1, h2.data(), kDqH2}; }
 };
 
-template <bool RELU>
-void dq_layer_host(const float* xin, int xs, int K, const float* W, const float* b, int J, float* out, int os) {
-    for (int r = 0; r < kOpRows; ++r)
-        for (int j = 0; j < J; ++j) {
-            float acc = 0.0f;
-            for (int k = 0; k < K; ++k) acc = op_mac(acc, xin[r * xs + k], W[(int64_t)j * K + k]);
-            const float v = acc + b[j];
-            out[r * os + j] = RELU ? op_relu(v) : v;
-        }
-}
-
-void dq_forward_host(const DqNet& n, DqTile& T) {
-    dq_layer_host<true>(T.x.data(), kDqMaxObs, n.O, n.w1, n.b1, kDqH1, T.h1.data(), kDqH1);
-    dq_layer_host<true>(T.h1.data(), kDqH1, kDqH1, n.w2, n.b2, kDqH2, T.h2.data(), kDqH2);
-    dq_layer_host<false>(T.h2.data(), kDqH2, kDqH2, n.w3, n.b3, n.J, T.z.data(), kDqMaxOut);
-}
-
-void dq_qvalues_host(DqTile& T, int n, int na, const float* atoms) {
+// the network over the tile's rows into T.z, then per action the Q value (C51: the softmax in place and its expectation) into T.qv
+void dq_qvalues_host(const DqNet& net, DqTile& T, int n, int na, const float* atoms) {
+    tile_forward_host(net, net.O, T.net(), T.z.data(), kDqMaxOut);
     for (int r = 0; r < kOpRows; ++r)
         for (int a = 0; a < n; ++a) {
             float* za = T.z.data() + r * kDqMaxOut + a * na;
@@ -1878,35 +1874,11 @@ void dq_qvalues_host(DqTile& T, int n, int na, const float* atoms) {
         }
 }
 
-void dq_dgrad_host(const float* dz, int ds, int J, const float* W, int K, float* io, int ios) {
-    for (int r = 0; r < kOpRows; ++r)
-        for (int k = 0; k < K; ++k) {
-            float acc = 0.0f;
-            for (int j = 0; j < J; ++j) acc = op_mac(acc, dz[r * ds + j], W[(int64_t)j * K + k]);
-            io[r * ios + k] = op_relu_bwd(io[r * ios + k], acc);
-        }
-}
-
-int dq_shape_cpu(const char* fn, int M, int O, int n, int na) {
-    MI355_REQUIRE(M > 0 && dq_limits(O, n, na), MI355PPO_EINVAL,
-                  "%s: rows=%d obs_dim=%d n_actions=%d n_atoms=%d: the fused Q networks take 1 <= obs_dim <= %d, 2 <= n_actions <= %d, "
-                  "1 <= n_atoms <= %d, n_actions * n_atoms <= %d", fn, M, O, n, na, kDqMaxObs, kDqMaxAct, kDqMaxAtoms, kDqMaxOut);
-    return MI355PPO_OK;
-}
-
-void dq_gather_host(const float* src, const int64_t* bi, const int64_t* ei, int64_t slots, int N, int r0, int nr, int O, DqTile& T) {
-    for (int r = 0; r < kOpRows; ++r) {
-        const int64_t row = r < nr ? op_row_cpu(bi, ei, r0 + r, slots, N) : 0;
-        for (int k = 0; k < O; ++k) T.x[r * kDqMaxObs + k] = r < nr ? src[row * O + k] : 0.0f;
-    }
-}
-
 // dq_update_kernel<C51> on the host
 template <bool C51>
 int dq_update_cpu(const float* ring_obs, const float* ring_next_obs, const float* ring_actions, const float* ring_rewards,
-                  const float* ring_dones, const int64_t* bi, const int64_t* ei, int64_t slots, int N, const float* online, const float* target,
-                  const float* atoms, float gamma, float vmin, float vmax, float norm, float* grads, float* scalars_out, float* aux_a,
-                  float* aux_b, int M, int O, int n, int na) {
+                  const float* ring_dones, const TileRows& ring, const float* online, const float* target, const float* atoms, float gamma,
+                  float vmin, float vmax, float norm, float* grads, float* scalars_out, float* aux_a, float* aux_b, int M, int O, int n, int na) {
     const int J = n * na, G = op_groups(M), ntiles = op_tiles(M);
     const int64_t P = dq_count(O, J);
     const DqNet tn = dq_net(target, O, J), qn = dq_net(online, O, J);
@@ -1918,9 +1890,8 @@ int dq_update_cpu(const float* ring_obs, const float* ring_next_obs, const float
         const int g = tl % G, r0 = tl * kOpRows, nr = (M - r0 < kOpRows) ? M - r0 : kOpRows;
         const bool first = tl == g;
         float* p = part.data() + (int64_t)g * P;
-        dq_gather_host(ring_next_obs, bi, ei, slots, N, r0, nr, O, T);
-        dq_forward_host(tn, T);
-        dq_qvalues_host(T, n, na, atoms);
+        tile_gather_host(ring_next_obs, ring, r0, M, O, T.x.data(), kDqMaxObs);
+        dq_qvalues_host(tn, T, n, na, atoms);
         if constexpr (C51) {
             const float delta_z = atoms[1] - atoms[0];
             for (int r = 0; r < kOpRows; ++r) {
@@ -1930,7 +1901,7 @@ int dq_update_cpu(const float* ring_obs, const float* ring_next_obs, const float
                     e.l = e.u = -1.0f;
                     e.dml = e.dmu = 0.0f;
                     if (r < nr) {
-                        const int64_t row = op_row_cpu(bi, ei, r0 + r, slots, N);
+                        const int64_t row = ring(r0 + r);
                         const float pj = T.z[r * ZS + a * na + j];
                         e = c51_proj_elem(ring_rewards[row], ring_dones[row], gamma, atoms[j], vmin, vmax, delta_z, na, pj);
                         if (aux_a) aux_a[(int64_t)(r0 + r) * na + j] = pj;
@@ -1950,7 +1921,7 @@ int dq_update_cpu(const float* ring_obs, const float* ring_next_obs, const float
             for (int r = 0; r < kOpRows; ++r) {
                 float y = 0.0f;
                 if (r < nr) {
-                    const int64_t row = op_row_cpu(bi, ei, r0 + r, slots, N);
+                    const int64_t row = ring(r0 + r);
                     if (aux_a)
                         for (int a = 0; a < n; ++a) aux_a[(int64_t)(r0 + r) * n + a] = T.qv[r * kDqMaxAct + a];
                     y = dq_td_target(ring_rewards[row], ring_dones[row], gamma, T.qv[r * kDqMaxAct + dq_argmax(T.qv + r * kDqMaxAct, n)]);
@@ -1959,10 +1930,9 @@ int dq_update_cpu(const float* ring_obs, const float* ring_next_obs, const float
                 T.yv[r] = y;
             }
         }
-        for (int r = 0; r < kOpRows; ++r) T.act[r] = r < nr ? dq_action_index(ring_actions[op_row_cpu(bi, ei, r0 + r, slots, N)], n) : 0;
-        dq_gather_host(ring_obs, bi, ei, slots, N, r0, nr, O, T);
-        dq_forward_host(qn, T);
-        dq_qvalues_host(T, n, na, atoms);
+        for (int r = 0; r < kOpRows; ++r) T.act[r] = r < nr ? dq_action_index(ring_actions[ring(r0 + r)], n) : 0;
+        tile_gather_host(ring_obs, ring, r0, M, O, T.x.data(), kDqMaxObs);
+        dq_qvalues_host(qn, T, n, na, atoms);
         if constexpr (C51) {
             for (int r = 0; r < kOpRows; ++r) {
                 float s = 0.0f, dot = 0.0f;
@@ -1994,11 +1964,7 @@ int dq_update_cpu(const float* ring_obs, const float* ring_next_obs, const float
                 for (int j = 0; j < J; ++j) T.z[r * ZS + j] = (j == T.act[r]) ? d : 0.0f;
             }
         }
-        op_wgrad_host(T.z.data(), ZS, T.h2.data(), kDqH2, J, kDqH2, p + off.w3, p + off.b3, first, nr);
-        dq_dgrad_host(T.z.data(), ZS, J, qn.w3, kDqH2, T.h2.data(), kDqH2);
-        op_wgrad_host(T.h2.data(), kDqH2, T.h1.data(), kDqH1, kDqH2, kDqH1, p + off.w2, p + off.b2, first, nr);
-        dq_dgrad_host(T.h2.data(), kDqH2, kDqH2, qn.w2, kDqH1, T.h1.data(), kDqH1);
-        op_wgrad_host(T.h1.data(), kDqH1, T.x.data(), kDqMaxObs, kDqH1, O, p + off.w1, p + off.b1, first, nr);
+        tile_backward_host(qn, off, O, T.z.data(), ZS, T.net(), p, first, nr);
     }
     op_fold_host(part.data(), G, P, grads);
     for (int s = 0; s < 2; ++s) scalars_out[s] = 1.0f * op_fold_mean_host(rows.data() + (size_t)s * M, M);
@@ -2011,15 +1977,14 @@ extern "C" MI355PPO_API int mi355ppo_dqn_act_f32_cpu(const float* obs, const flo
                                                     float* q_out, int N, int O, int n_actions, int n_atoms) {
     const char* fn = "mi355ppo_dqn_act_f32_cpu";
     MI355_REQUIRE(obs && params && actions_out, MI355PPO_EINVAL, "%s: null pointer", fn);
-    if (int rc = dq_shape_cpu(fn, N, O, n_actions, n_atoms)) return rc;
+    if (int rc = dq_shape(fn, N, O, n_actions, n_atoms)) return rc;
     MI355_REQUIRE(n_atoms == 1 || atoms, MI355PPO_EINVAL, "%s: n_atoms=%d needs the atoms", fn, n_atoms);
     const DqNet qn = dq_net(params, O, n_actions * n_atoms);
+    const TileRows plain{nullptr, nullptr, 0, 0};
     DqTile T;
     for (int r0 = 0; r0 < N; r0 += kOpRows) {
-        for (int r = 0; r < kOpRows; ++r)
-            for (int k = 0; k < O; ++k) T.x[r * kDqMaxObs + k] = (r0 + r < N) ? obs[(int64_t)(r0 + r) * O + k] : 0.0f;
-        dq_forward_host(qn, T);
-        dq_qvalues_host(T, n_actions, n_atoms, atoms);
+        tile_gather_host(obs, plain, r0, N, O, T.x.data(), kDqMaxObs);
+        dq_qvalues_host(qn, T, n_actions, n_atoms, atoms);
         for (int r = 0; r < kOpRows && r0 + r < N; ++r) {
             if (q_out)
                 for (int a = 0; a < n_actions; ++a) q_out[(int64_t)(r0 + r) * n_actions + a] = T.qv[r * kDqMaxAct + a];
@@ -2038,9 +2003,9 @@ extern "C" MI355PPO_API int mi355ppo_dqn_td_fwd_bwd_f32_cpu(const float* ring_ob
     MI355_REQUIRE(ring_obs && ring_next_obs && ring_actions && ring_rewards && ring_dones && online && target && grads && scalars_out &&
                       batch_inds && env_inds, MI355PPO_EINVAL, "%s: null pointer", fn);
     MI355_REQUIRE(slots > 0 && n_envs > 0, MI355PPO_EINVAL, "%s: slots=%lld n_envs=%d must be positive", fn, (long long)slots, n_envs);
-    if (int rc = dq_shape_cpu(fn, M, O, n_actions, 1)) return rc;
-    return dq_update_cpu<false>(ring_obs, ring_next_obs, ring_actions, ring_rewards, ring_dones, batch_inds, env_inds, slots, n_envs, online,
-                                target, nullptr, (float)gamma, 0.0f, 0.0f, (float)(2.0 / (double)M), grads, scalars_out, target_q_out,
+    if (int rc = dq_shape(fn, M, O, n_actions, 1)) return rc;
+    return dq_update_cpu<false>(ring_obs, ring_next_obs, ring_actions, ring_rewards, ring_dones, TileRows{batch_inds, env_inds, slots, n_envs},
+                                online, target, nullptr, (float)gamma, 0.0f, 0.0f, (float)(2.0 / (double)M), grads, scalars_out, target_q_out,
                                 td_target_out, M, O, n_actions, 1);
 }
 
@@ -2054,9 +2019,9 @@ extern "C" MI355PPO_API int mi355ppo_c51_fwd_bwd_f32_cpu(const float* ring_obs, 
     MI355_REQUIRE(ring_obs && ring_next_obs && ring_actions && ring_rewards && ring_dones && online && target && atoms && grads &&
                       scalars_out && batch_inds && env_inds, MI355PPO_EINVAL, "%s: null pointer", fn);
     MI355_REQUIRE(slots > 0 && n_envs > 0, MI355PPO_EINVAL, "%s: slots=%lld n_envs=%d must be positive", fn, (long long)slots, n_envs);
-    if (int rc = dq_shape_cpu(fn, M, O, n_actions, n_atoms)) return rc;
+    if (int rc = dq_shape(fn, M, O, n_actions, n_atoms)) return rc;
     MI355_REQUIRE(n_atoms >= 2, MI355PPO_EINVAL, "%s: n_atoms=%d: the projection needs two atoms (delta_z = atoms[1] - atoms[0])", fn, n_atoms);
-    return dq_update_cpu<true>(ring_obs, ring_next_obs, ring_actions, ring_rewards, ring_dones, batch_inds, env_inds, slots, n_envs, online,
-                               target, atoms, (float)gamma, (float)v_min, (float)v_max, (float)(1.0 / (double)M), grads, scalars_out,
+    return dq_update_cpu<true>(ring_obs, ring_next_obs, ring_actions, ring_rewards, ring_dones, TileRows{batch_inds, env_inds, slots, n_envs},
+                               online, target, atoms, (float)gamma, (float)v_min, (float)v_max, (float)(1.0 / (double)M), grads, scalars_out,
                                next_pmfs_out, target_pmfs_out, M, O, n_actions, n_atoms);
 }

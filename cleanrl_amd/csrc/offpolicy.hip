@@ -323,10 +323,7 @@ extern "C" MI355PPO_API int mi355ppo_td3_critic_fwd_bwd_f32(const float* ring_ob
     if (int rc = op_shape(fn, M, O, A)) return rc;
     OpRing R;
     if (int rc = op_ring_args(fn, R, ring_obs, nullptr, ring_actions, nullptr, nullptr, batch_inds, env_inds, slots, n_envs)) return rc;
-    const size_t need = mi355ppo_td3_critic_workspace_bytes(M, O, A, n_critics);
-    MI355_REQUIRE(workspace && workspace_bytes >= need, MI355PPO_EWORKSPACE, "%s: workspace %zu bytes < required %zu", fn,
-                  workspace ? workspace_bytes : (size_t)0, need);
-    MI355_REQUIRE(aligned(workspace, 16), MI355PPO_EALIGN, "%s: workspace must be 16-byte aligned", fn);
+    if (int rc = op_workspace_ok(fn, workspace, workspace_bytes, mi355ppo_td3_critic_workspace_bytes(M, O, A, n_critics))) return rc;
     hipStream_t s = as_stream(stream);
     const int Mp = (int)op_mp(M), G = op_groups(M);
     const int64_t P = (int64_t)n_critics * op_critic_count(O, A);
@@ -335,9 +332,7 @@ extern "C" MI355PPO_API int mi355ppo_td3_critic_fwd_bwd_f32(const float* ring_ob
                        (float)(2.0 / (double)M));
     if (int rc = check_launch("op_critic_kernel")) return rc;
     // rows: q1 | sq1 | q2 | sq2 -> scalars {mean q1, qf1_loss, mean q2, qf2_loss}
-    hipLaunchKernelGGL(op_fold_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, ws + (int64_t)4 * Mp, G, P, grads, ws, Mp, M,
-                       2 * n_critics, 1.0f, scalars_out);
-    return check_launch("op_fold_kernel");
+    return op_fold_launch(s, ws + (int64_t)4 * Mp, G, P, grads, ws, Mp, M, 2 * n_critics, 1.0f, scalars_out);
 }
 
 extern "C" MI355PPO_API size_t mi355ppo_td3_actor_workspace_bytes(int M, int O, int A) {
@@ -354,10 +349,7 @@ extern "C" MI355PPO_API int mi355ppo_td3_actor_fwd_bwd_f32(const float* ring_obs
     if (int rc = op_shape(fn, M, O, A)) return rc;
     OpRing R;
     if (int rc = op_ring_args(fn, R, ring_obs, nullptr, nullptr, nullptr, nullptr, batch_inds, env_inds, slots, n_envs)) return rc;
-    const size_t need = mi355ppo_td3_actor_workspace_bytes(M, O, A);
-    MI355_REQUIRE(workspace && workspace_bytes >= need, MI355PPO_EWORKSPACE, "%s: workspace %zu bytes < required %zu", fn,
-                  workspace ? workspace_bytes : (size_t)0, need);
-    MI355_REQUIRE(aligned(workspace, 16), MI355PPO_EALIGN, "%s: workspace must be 16-byte aligned", fn);
+    if (int rc = op_workspace_ok(fn, workspace, workspace_bytes, mi355ppo_td3_actor_workspace_bytes(M, O, A))) return rc;
     hipStream_t s = as_stream(stream);
     const int Mp = (int)op_mp(M), G = op_groups(M);
     const int64_t P = op_actor_count(O, A);
@@ -365,9 +357,7 @@ extern "C" MI355PPO_API int mi355ppo_td3_actor_fwd_bwd_f32(const float* ring_obs
     hipLaunchKernelGGL(op_actor_kernel, dim3(G), dim3(256), 0, s, R, actor, qf1, action_scale, action_bias, ws, dq_daction_out, M, Mp, O, A, G,
                        (float)(-1.0 / (double)M));
     if (int rc = check_launch("op_actor_kernel")) return rc;
-    hipLaunchKernelGGL(op_fold_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, ws + Mp, G, P, grads, ws, Mp, M, 1, -1.0f,
-                       actor_loss_out);
-    return check_launch("op_fold_kernel");
+    return op_fold_launch(s, ws + Mp, G, P, grads, ws, Mp, M, 1, -1.0f, actor_loss_out);
 }
 
 extern "C" MI355PPO_API int mi355ppo_polyak_f32(const float* params, float* target_params, int64_t n, double tau, void* stream) {

@@ -127,4 +127,12 @@ MI355_HD float op_dmu(float dact, float scale, float t) { return (dact * scale) 
 // args.tau * param + (1 - args.tau) * target_param
 MI355_HD float op_polyak(float p, float t, float tau, float omt) { return tau * p + omt * t; }
 
+// host-side argument check of the device entry points and of their twins
+inline int op_shape(const char* fn, int M, int O, int A) {
+    MI355_REQUIRE(M > 0 && O > 0 && O <= kOpMaxObs && A > 0 && A <= kOpMaxAct, MI355PPO_EINVAL,
+                  "%s: rows=%d obs_dim=%d act_dim=%d: the off-policy networks take 1 <= obs_dim <= %d, 1 <= act_dim <= %d", fn, M, O, A,
+                  kOpMaxObs, kOpMaxAct);
+    return MI355PPO_OK;
+}
+
 }  // namespace mi355ppo

@@ -1,6 +1,7 @@
 // Workgroup-level device helpers of the off-policy kernels (offpolicy.hip: DDPG / TD3, sac.hip: SAC): one tile of kOpRows rows
 // through a 256-wide layer (forward, head, masked data gradient, weight gradient), the f64 slot fold, the ring gather and the
-// host-side argument checks.  Included by the kernel files only; the row math both sides share is in offpolicy_rows.h.
+// host-side argument checks of the device entry points.  Included by the kernel files only; the row math and the shape check both
+// sides share are in offpolicy_rows.h.
 #pragma once
 #include "common.h"
 #include "offpolicy_rows.h"
@@ -139,13 +140,6 @@ struct OpRing {
 __device__ __forceinline__ int64_t ring_row(const OpRing& R, int m) { return op_clamp(R.bi[m], R.slots) * R.N + op_clamp(R.ei[m], R.N); }
 
 // ------------------------------------------------------------------------------------------------ host-side argument checks
-static int op_shape(const char* fn, int M, int O, int A) {
-    MI355_REQUIRE(M > 0 && O > 0 && O <= kOpMaxObs && A > 0 && A <= kOpMaxAct, MI355PPO_EINVAL,
-                  "%s: rows=%d obs_dim=%d act_dim=%d: the off-policy networks take 1 <= obs_dim <= %d, 1 <= act_dim <= %d", fn, M, O, A,
-                  kOpMaxObs, kOpMaxAct);
-    return MI355PPO_OK;
-}
-
 static int64_t op_mp(int M) { return ((int64_t)M + 63) / 64 * 64; }
 
 static int op_ring_args(const char* fn, OpRing& R, const float* obs, const float* next_obs, const float* actions, const float* rewards,
@@ -161,6 +155,14 @@ static int op_ring_args(const char* fn, OpRing& R, const float* obs, const float
     R.ei = ei;
     R.slots = slots;
     R.N = N;
+    return MI355PPO_OK;
+}
+
+// the workspace of a *_fwd_bwd entry point: present, at least `need` bytes, 16-byte aligned
+static int op_workspace_ok(const char* fn, const void* workspace, size_t workspace_bytes, size_t need) {
+    MI355_REQUIRE(workspace && workspace_bytes >= need, MI355PPO_EWORKSPACE, "%s: workspace %zu bytes < required %zu", fn,
+                  workspace ? workspace_bytes : (size_t)0, need);
+    MI355_REQUIRE(aligned(workspace, 16), MI355PPO_EALIGN, "%s: workspace must be 16-byte aligned", fn);
     return MI355PPO_OK;
 }
 

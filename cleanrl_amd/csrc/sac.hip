@@ -367,10 +367,7 @@ extern "C" MI355PPO_API int mi355ppo_sac_actor_fwd_bwd_f32(const float* ring_obs
     if (int rc = op_shape(fn, M, O, A)) return rc;
     OpRing R;
     if (int rc = op_ring_args(fn, R, ring_obs, nullptr, nullptr, nullptr, nullptr, batch_inds, env_inds, slots, n_envs)) return rc;
-    const size_t need = mi355ppo_sac_actor_workspace_bytes(M, O, A);
-    MI355_REQUIRE(workspace && workspace_bytes >= need, MI355PPO_EWORKSPACE, "%s: workspace %zu bytes < required %zu", fn,
-                  workspace ? workspace_bytes : (size_t)0, need);
-    MI355_REQUIRE(aligned(workspace, 16), MI355PPO_EALIGN, "%s: workspace must be 16-byte aligned", fn);
+    if (int rc = op_workspace_ok(fn, workspace, workspace_bytes, mi355ppo_sac_actor_workspace_bytes(M, O, A))) return rc;
     hipStream_t s = as_stream(stream);
     const int Mp = (int)op_mp(M), G = op_groups(M);
     float* ws = static_cast<float*>(workspace);

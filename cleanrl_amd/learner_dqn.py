@@ -25,11 +25,11 @@ c51.py: ``target_network.load_state_dict``             ``sync_target``: one flat
 ====================================================  ==============================================================
 
 Backend: ``MI355PPO_OFFPOLICY=torch|fused``, default ``torch``.  Both backends draw the reference's random
-streams in its order.  A fused step is 6 library launches (act 1, add 1, update 2, Adam 2), 7 on a target-update step of dqn.py.
+streams in its order.  The backend switch, the ring, the flat-buffer helpers and the Adam helper are the base class's (``DeviceRing``,
+cleanrl_amd/learner_offpolicy.py).  A fused step is 6 library launches (act 1, add 1, update 2, Adam 2), 7 on a target-update step of dqn.py.
 """
 from __future__ import annotations
 
-import math
 import random
 
 import numpy as np
@@ -38,58 +38,38 @@ import torch.nn.functional as F
 import torch.optim as optim
 
 from . import ops
-from .learner_offpolicy import BACKENDS, DeviceRing, HostReplayBuffer, offpolicy_backend
+from .learner_offpolicy import DeviceRing
 
 
 class DQNLearner(DeviceRing):
     """``c51``: the networks are ``C51Network`` (atoms, ``get_action``) and the update is the categorical one."""
 
     def __init__(self, q_network, target_network, args, envs, device, c51: bool, backend=None):
-        self.q_network, self.target_network = q_network, target_network
-        self.args, self.device, self.c51 = args, torch.device(device), bool(c51)
-        self.backend = offpolicy_backend(self.device) if backend is None else backend
-        if self.backend not in BACKENDS:
-            raise ValueError(f"off-policy backend {self.backend!r}: expected one of {BACKENDS}")
-        self.fused = self.backend == "fused"
-        self.space = envs.single_action_space
-        self.N = int(envs.num_envs)
-        self.O = int(np.array(envs.single_observation_space.shape).prod())
-        self.A = 1
-        self.n = int(self.space.n)
+        self.c51 = bool(c51)
+        self.n = int(envs.single_action_space.n)
         self.n_atoms = int(args.n_atoms) if self.c51 else 1
+        super().__init__(args, envs, device, backend, 1, act_dtype=np.int64)
+        self.q_network, self.target_network = q_network, target_network
         self.eps = 0.01 / args.batch_size if self.c51 else 1e-8
-        self.g = ops.twins(self.device)
-        self.pos, self.full = 0, False
-        self.slots = max(int(args.buffer_size) // self.N, 1)
         self.step = 0
-        self.last = None
         if not self.fused:
-            self.rb = HostReplayBuffer(args.buffer_size, self.O, 1, self.device, n_envs=self.N, act_dtype=np.int64)
             self.optimizer = optim.Adam(q_network.parameters(), lr=args.learning_rate, eps=self.eps)
             return
+        dev = self.device
+        total = ops.dqn_counts(self.O, self.n, self.n_atoms)
+        self._alloc_flat(total)
+        self.target = torch.zeros(total, dtype=torch.float32, device=dev)
+        self._adopt([q_network], self.online)
+        self._adopt([target_network], self.target)
+        self.atoms = q_network.atoms.detach().to(dev).contiguous() if self.c51 else None
+        self._greedy = torch.zeros(self.N, dtype=torch.int64, device=dev)
+        self._sc = torch.zeros(2, dtype=torch.float32, device=dev)
+
+    def _check_sizes(self):
         if not ops.dqn_limits_ok(self.O, self.n, self.n_atoms) or (self.c51 and self.n_atoms < 2):
             raise ValueError(f"MI355PPO_OFFPOLICY=fused: the fused Q networks take obs_dim <= {ops.DQN_MAX_OBS}, 2 <= n_actions <= "
                              f"{ops.DQN_MAX_ACT}, n_atoms <= {ops.DQN_MAX_ATOMS} (at least 2 for c51) and n_actions * n_atoms <= "
                              f"{ops.DQN_MAX_OUT}, not {self.O} / {self.n} / {self.n_atoms}; use MI355PPO_OFFPOLICY=torch")
-        dev = self.device
-        total = ops.dqn_counts(self.O, self.n, self.n_atoms)
-        self.online = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.target = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.grads, self.exp_avg, self.exp_avg_sq = (torch.zeros(total, dtype=torch.float32, device=dev) for _ in range(3))
-        for flat, net in ((self.online, q_network), (self.target, target_network)):
-            off = 0
-            with torch.no_grad():
-                for p in net.parameters():                       # the modules keep working: their parameters are views of the flat buffer
-                    n = p.numel()
-                    flat[off:off + n].copy_(p.reshape(-1))
-                    p.data = flat[off:off + n].view(p.shape)
-                    off += n
-        self.atoms = q_network.atoms.detach().to(dev).contiguous() if self.c51 else None
-        M = int(args.batch_size)
-        self._alloc_ring(M)
-        self._greedy = torch.zeros(self.N, dtype=torch.int64, device=dev)
-        self._sc = torch.zeros(2, dtype=torch.float32, device=dev)
-        self._norm = torch.zeros(1, dtype=torch.float32, device=dev)
 
     # ------------------------------------------------------------------ rollout
     def act(self, obs, global_step: int, epsilon: float):
@@ -105,8 +85,7 @@ class DQNLearner(DeviceRing):
                     actions = torch.argmax(self.q_network(x), dim=1)
                 return actions.cpu().numpy()
             self.g.dqn_act(self._stage_obs(obs), self.online, self.n, self._greedy, atoms=self.atoms)
-            out = self._greedy.cpu().numpy()
-            return out if self.device.type == "cuda" else out.copy()      # on the CPU .cpu() aliases the reused buffer
+            return self._copy_out(self._greedy)
 
     # ------------------------------------------------------------------ training
     def train_step(self, indices=None):
@@ -129,13 +108,10 @@ class DQNLearner(DeviceRing):
             g.c51_fwd_bwd(self.ring, bi, ei, self.online, self.target, self.atoms, self.n, a.gamma, a.v_min, a.v_max, self.grads, self._sc)
         else:
             g.dqn_td_fwd_bwd(self.ring, bi, ei, self.online, self.target, self.n, a.gamma, self.grads, self._sc)
-        if adam and sched is not None:
-            ops.clip_adam_sched_(self.online, self.grads, self.exp_avg, self.exp_avg_sq, sched, math.inf, 1.0, eps=self.eps,
-                                 total_norm_out=self._norm)
-        elif adam:
-            self.step += 1
-            kw = {"total_norm_out": self._norm} if self.device.type == "cuda" else {}
-            g.clip_adam_(self.online, self.grads, self.exp_avg, self.exp_avg_sq, self.step, a.learning_rate, math.inf, 1.0, eps=self.eps, **kw)
+        if adam:
+            if sched is None:
+                self.step += 1
+            self._adam(self._flats, self.step if sched is None else sched, a.learning_rate, self.eps)
 
     def adam_schedule(self):
         """(2,) host tensor: the library's (step size, bias correction) of the NEXT Adam step."""
@@ -200,6 +176,4 @@ class DQNLearner(DeviceRing):
 
     def flat_params(self):
         """(online, target) flat parameters, detached copies (tests)."""
-        fo = torch.cat([p.detach().reshape(-1) for p in self.q_network.parameters()])
-        ft = torch.cat([p.detach().reshape(-1) for p in self.target_network.parameters()])
-        return fo.clone(), ft.clone()
+        return self._flat([self.q_network]), self._flat([self.target_network])

@@ -24,6 +24,7 @@ the three Polyak loops                                 ``mi355ppo_polyak_f32`` o
 Backend: ``MI355PPO_OFFPOLICY=torch|fused``.  The default is ``torch`` on the CPU (``fused`` runs the host twins there) and on a GPU
 (see DESIGN.md section 3.13 for why).  Both backends draw the reference's random streams in its order, so a fused run follows the
 reference's trajectory for a seed up to rounding.  A TD3 step with the delayed update is 12 library launches on ``fused``.
+``DeviceRing`` is the base class this learner shares with ``learner_sac.SACLearner`` and ``learner_dqn.DQNLearner``.
 """
 from __future__ import annotations
 
@@ -83,10 +84,39 @@ def advance(ring):
 
 
 class DeviceRing:
-    """The part of a ``fused`` learner that is the replay ring: the five device arrays, the pinned staging of a step's transitions,
-    indices and observations, ``store`` and ``sample_indices``.  The learner sets ``device``, ``fused``, ``g`` (``ops.twins``),
-    ``N`` / ``O`` / ``A``, ``slots``, ``pos`` / ``full`` and, on ``torch``, ``rb`` (a ``HostReplayBuffer``) before it calls
-    ``_alloc_ring``.  Shared by ``OffPolicyLearner`` and ``learner_sac.SACLearner``."""
+    """What the learners on the replay ring share.  ``__init__`` resolves the backend (``fused``), reads ``N`` / ``O`` from ``envs`` and
+    sets ``space``, ``g`` (``ops.twins``), ``slots`` and ``pos`` / ``full``; then ``torch`` gets ``rb`` (a ``HostReplayBuffer``) and
+    ``fused`` the ring: the five device arrays and the pinned staging of a step's transitions, indices and observations.  ``act_width``
+    is the ring's action width ``A`` and ``act_dtype`` the host buffer's action dtype: ``prod(space.shape)`` / float32 for the
+    continuous families, ``1`` / int64 for a Discrete space.  ``store``, ``sample_indices`` and the helpers of the flat parameter
+    buffers (``_alloc_flat``, ``_adopt``, ``_adam``, ``_copy_out``, ``_flat``) are here once.  Base of ``OffPolicyLearner``,
+    ``learner_sac.SACLearner`` and ``learner_dqn.DQNLearner``."""
+
+    def __init__(self, args, envs, device, backend, act_width: int, act_dtype=np.float32):
+        self.args, self.device = args, torch.device(device)
+        self.backend = offpolicy_backend(self.device) if backend is None else backend
+        if self.backend not in BACKENDS:
+            raise ValueError(f"off-policy backend {self.backend!r}: expected one of {BACKENDS}")
+        self.fused = self.backend == "fused"
+        self.space = envs.single_action_space
+        self.N = int(envs.num_envs)
+        self.O = int(np.array(envs.single_observation_space.shape).prod())
+        self.A = int(act_width)
+        self.g = ops.twins(self.device)
+        self.pos, self.full = 0, False
+        self.slots = max(int(args.buffer_size) // self.N, 1)
+        self.last = None
+        if not self.fused:
+            self.rb = HostReplayBuffer(args.buffer_size, self.O, self.A, self.device, n_envs=self.N, act_dtype=act_dtype)
+            return
+        self._check_sizes()                                      # before anything of the ring's size is allocated
+        self._alloc_ring(int(args.batch_size))
+
+    def _check_sizes(self):
+        """The refusal of sizes the fused networks do not take: the continuous families' (``DQNLearner`` has its own limits)."""
+        if not (1 <= self.O <= ops.OFFPOLICY_MAX_OBS and 1 <= self.A <= ops.OFFPOLICY_MAX_ACT):
+            raise ValueError(f"MI355PPO_OFFPOLICY=fused: the fused networks take obs_dim <= {ops.OFFPOLICY_MAX_OBS} and act_dim <= "
+                             f"{ops.OFFPOLICY_MAX_ACT}, not {self.O} / {self.A}; use MI355PPO_OFFPOLICY=torch")
 
     def _alloc_ring(self, M: int):
         dev, N, O, A = self.device, self.N, self.O, self.A
@@ -104,6 +134,46 @@ class DeviceRing:
         self._idx = torch.zeros((2, M), dtype=torch.int64, device=dev)
         self._obs = torch.zeros((N, O), dtype=torch.float32, device=dev)
         self._act = torch.zeros((N, A), dtype=torch.float32, device=dev)
+        self._norm = torch.zeros(1, dtype=torch.float32, device=dev)
+
+    # ------------------------------------------------------------------ the flat parameter / gradient / Adam buffers
+    def _alloc_flat(self, total: int):
+        """``online`` | ``grads`` | ``exp_avg`` | ``exp_avg_sq``, ``total`` floats each (``_flats``: the order ``_adam`` takes them in)."""
+        self._flats = tuple(torch.zeros(total, dtype=torch.float32, device=self.device) for _ in range(4))
+        self.online, self.grads, self.exp_avg, self.exp_avg_sq = self._flats
+
+    @staticmethod
+    def _adopt(nets, flat, off: int = 0) -> int:
+        """The modules keep working: their parameters become views of ``flat`` from ``off`` on, in ``.parameters()`` order.  Returns
+        the offset behind the last one."""
+        with torch.no_grad():
+            for net in nets:
+                for p in net.parameters():
+                    n = p.numel()
+                    flat[off:off + n].copy_(p.reshape(-1))
+                    p.data = flat[off:off + n].view(p.shape)
+                    off += n
+        return off
+
+    def _adam(self, segs, step, lr, eps=1e-8):
+        """One clip + Adam launch pair (grad_scale 1, max_grad_norm inf) over ``segs``, the four flat segments in ``_flats`` order.
+        ``step`` is the step number or a device row of a schedule tensor (``clip_adam_sched_``; a device only: the host twins take
+        the step as an argument)."""
+        if torch.is_tensor(step):
+            ops.clip_adam_sched_(*segs, step, math.inf, 1.0, eps=eps, total_norm_out=self._norm)
+            return
+        kw = {"total_norm_out": self._norm} if self.device.type == "cuda" else {}
+        self.g.clip_adam_(*segs, step, lr, math.inf, 1.0, eps=eps, **kw)
+
+    def _copy_out(self, buf):
+        """The action kernel's reused output buffer as a numpy array the caller owns."""
+        out = buf.cpu().numpy()
+        return out if self.device.type == "cuda" else out.copy()          # on the CPU .cpu() aliases the reused buffer
+
+    @staticmethod
+    def _flat(nets):
+        """The modules' parameters as one flat detached copy (``flat_params``)."""
+        return torch.cat([p.detach().reshape(-1) for n in nets for p in n.parameters()]).clone()
 
     def _stage_obs(self, obs):
         """The rollout's observations (N, O) where the action kernel reads them."""
@@ -155,58 +225,33 @@ class OffPolicyLearner(DeviceRing):
     """``qfs`` / ``qf_targets``: one network (DDPG) or two (TD3).  ``td3``: target policy smoothing and the delayed update."""
 
     def __init__(self, actor, qfs, target_actor, qf_targets, args, envs, device, td3: bool, backend=None):
+        super().__init__(args, envs, device, backend, int(np.prod(envs.single_action_space.shape)))
         self.actor, self.qfs, self.target_actor, self.qf_targets = actor, list(qfs), target_actor, list(qf_targets)
-        self.args, self.device, self.td3 = args, torch.device(device), bool(td3)
-        self.backend = offpolicy_backend(self.device) if backend is None else backend
-        if self.backend not in BACKENDS:
-            raise ValueError(f"off-policy backend {self.backend!r}: expected one of {BACKENDS}")
-        self.fused = self.backend == "fused"
-        self.space = envs.single_action_space
-        self.N = int(envs.num_envs)
-        self.O = int(np.array(envs.single_observation_space.shape).prod())
-        self.A = int(np.prod(self.space.shape))
+        self.td3 = bool(td3)
         self.ncrit = len(self.qfs)
         self.low = np.asarray(self.space.low, np.float32).reshape(-1)
         self.high = np.asarray(self.space.high, np.float32).reshape(-1)
-        self.g = ops.twins(self.device)
-        self.pos, self.full = 0, False
-        self.slots = max(int(args.buffer_size) // self.N, 1)
         self.q_step = self.actor_step = 0
-        self.last = None
         if not self.fused:
-            self.rb = HostReplayBuffer(args.buffer_size, self.O, self.A, self.device, n_envs=self.N)
             self.q_optimizer = optim.Adam([p for q in self.qfs for p in q.parameters()], lr=args.learning_rate)
             self.actor_optimizer = optim.Adam(list(actor.parameters()), lr=args.learning_rate)
             return
-        if not (1 <= self.O <= ops.OFFPOLICY_MAX_OBS and 1 <= self.A <= ops.OFFPOLICY_MAX_ACT):
-            raise ValueError(f"MI355PPO_OFFPOLICY=fused: the fused networks take obs_dim <= {ops.OFFPOLICY_MAX_OBS} and act_dim <= "
-                             f"{ops.OFFPOLICY_MAX_ACT}, not {self.O} / {self.A}; use MI355PPO_OFFPOLICY=torch")
-        dev, N, O, A = self.device, self.N, self.O, self.A
-        self.pa, self.pq = ops.offpolicy_counts(O, A)
+        dev = self.device
+        self.pa, self.pq = ops.offpolicy_counts(self.O, self.A)
         self.q_off = (self.pa + 3) // 4 * 4                      # the critics start 16-byte aligned (the Adam kernel's float4s)
         total = self.q_off + self.ncrit * self.pq
-        self.online = torch.zeros(total, dtype=torch.float32, device=dev)
+        self._alloc_flat(total)
         self.target = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.grads, self.exp_avg, self.exp_avg_sq = (torch.zeros(total, dtype=torch.float32, device=dev) for _ in range(3))
-        for flat, nets in ((self.online, [actor] + self.qfs), (self.target, [target_actor] + self.qf_targets)):
-            off = 0
-            for i, net in enumerate(nets):
-                off = 0 if i == 0 else self.q_off + (i - 1) * self.pq
-                with torch.no_grad():
-                    for p in net.parameters():                   # the modules keep working: their parameters are views of the flat buffer
-                        n = p.numel()
-                        flat[off:off + n].copy_(p.reshape(-1))
-                        p.data = flat[off:off + n].view(p.shape)
-                        off += n
+        for flat, a_net, q_nets in ((self.online, actor, self.qfs), (self.target, target_actor, self.qf_targets)):
+            self._adopt([a_net], flat)
+            self._adopt(q_nets, flat, self.q_off)
         self.scale = actor.action_scale.detach().reshape(-1).to(dev).contiguous()
         self.bias = actor.action_bias.detach().reshape(-1).to(dev).contiguous()
         self.low_t, self.high_t = torch.from_numpy(self.low.copy()).to(dev), torch.from_numpy(self.high.copy()).to(dev)
         M = int(args.batch_size)
-        self._alloc_ring(M)
         self._y = torch.zeros(M, dtype=torch.float32, device=dev)
         self._qsc = torch.zeros(2 * self.ncrit, dtype=torch.float32, device=dev)
         self._asc = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._norm = torch.zeros(1, dtype=torch.float32, device=dev)
 
     # ------------------------------------------------------------------ views of the flat buffers
     def _seg(self, flat, which):
@@ -229,8 +274,7 @@ class OffPolicyLearner(DeviceRing):
                 return actions.cpu().numpy().clip(self.space.low, self.space.high)
             noise = torch.normal(0, self.actor.action_scale * a.exploration_noise).reshape(-1)
             self.g.ddpg_act(self._stage_obs(obs), self._seg(self.online, "actor"), self.scale, self.bias, noise, self.low_t, self.high_t, self._act)
-            out = self._act.cpu().numpy()
-            return out if self.device.type == "cuda" else out.copy()      # on the CPU .cpu() aliases the reused buffer
+            return self._copy_out(self._act)
 
     # ------------------------------------------------------------------ training
     def train_step(self, policy_update: bool, indices=None, noise=None):
@@ -258,34 +302,26 @@ class OffPolicyLearner(DeviceRing):
                      noise if self.td3 else None, getattr(a, "policy_noise", 0.0), getattr(a, "noise_clip", 0.0), lo0, hi0, a.gamma, self._y)
         g.td3_critic_fwd_bwd(self.ring, bi, ei, self._seg(self.online, "critics"), self.ncrit, self._y, self._seg(self.grads, "critics"),
                              self._qsc)
-        if adam and sched is not None:
-            self._adam_sched("critics", sched[0])
-        elif adam:
-            self.q_step += 1
-            self._adam("critics", self.q_step)
+        if adam:
+            if sched is None:
+                self.q_step += 1
+            self._adam_seg("critics", self.q_step if sched is None else sched[0])
         if policy_update:
             g.td3_actor_fwd_bwd(self.ring, bi, ei, self._seg(self.online, "actor"), self._seg(self.online, "qf1"), self.scale, self.bias,
                                 self._seg(self.grads, "actor"), self._asc)
-            if adam and sched is not None:
-                self._adam_sched("actor", sched[1])
-            elif adam:
-                self.actor_step += 1
-                self._adam("actor", self.actor_step)
+            if adam:
+                if sched is None:
+                    self.actor_step += 1
+                self._adam_seg("actor", self.actor_step if sched is None else sched[1])
             g.polyak_(self.online, self.target, a.tau)
 
-    def _adam(self, which, step):
-        kw = {"total_norm_out": self._norm} if self.device.type == "cuda" else {}
-        self.g.clip_adam_(self._seg(self.online, which), self._seg(self.grads, which), self._seg(self.exp_avg, which),
-                          self._seg(self.exp_avg_sq, which), step, self.args.learning_rate, math.inf, 1.0, eps=1e-8, **kw)
+    def _adam_seg(self, which, step):
+        self._adam([self._seg(f, which) for f in self._flats], step, self.args.learning_rate)
 
     def adam_schedules(self):
         """(2, 2) host tensor: the library's (step size, bias correction) of the NEXT critic and actor Adam steps."""
         lr = self.args.learning_rate
         return torch.tensor([ops.adam_schedule(lr, self.q_step + 1), ops.adam_schedule(lr, self.actor_step + 1)], dtype=torch.float32)
-
-    def _adam_sched(self, which, sched2):                        # device only: the host twins take the step as an argument
-        ops.clip_adam_sched_(self._seg(self.online, which), self._seg(self.grads, which), self._seg(self.exp_avg, which),
-                             self._seg(self.exp_avg_sq, which), sched2, math.inf, 1.0, eps=1e-8, total_norm_out=self._norm)
 
     def _train_torch(self, bi, ei, policy_update, noise):
         a, dev = self.args, self.device
@@ -346,6 +382,4 @@ class OffPolicyLearner(DeviceRing):
 
     def flat_params(self):
         """(actor, critics) flat parameters, detached copies (tests)."""
-        fa = torch.cat([p.detach().reshape(-1) for p in self.actor.parameters()])
-        fq = torch.cat([p.detach().reshape(-1) for q in self.qfs for p in q.parameters()])
-        return fa.clone(), fq.clone()
+        return self._flat([self.actor]), self._flat(self.qfs)

@@ -1,6 +1,6 @@
 """The replay buffer, action logic and training step of ``sac_continuous_action.py`` (reference: cleanrl/sac_continuous_action.py and
-``ReplayBuffer`` of cleanrl_utils/buffers.py).  The ring, its staging, ``HostReplayBuffer`` and the backend switch are
-cleanrl_amd/learner_offpolicy.py's.
+``ReplayBuffer`` of cleanrl_utils/buffers.py).  The backend switch, ``HostReplayBuffer``, the ring with its staging and the helpers
+of the flat parameter buffers are the base class's (``DeviceRing``, cleanrl_amd/learner_offpolicy.py).
 
 ====================================================  ==============================================================
 reference                                              here
@@ -35,34 +35,21 @@ import torch.nn.functional as F
 import torch.optim as optim
 
 from . import ops
-from .learner_offpolicy import BACKENDS, DeviceRing, HostReplayBuffer, offpolicy_backend
+from .learner_offpolicy import DeviceRing
 
 
 class SACLearner(DeviceRing):
-    """``store`` (``rb.add``) and ``sample_indices`` (``rb.sample``'s two ``np.random`` draws) are ``DeviceRing``'s."""
+    """``store`` (``rb.add``) and ``sample_indices`` (``rb.sample``'s two ``np.random`` draws) are the base class's."""
 
     def __init__(self, actor, qf1, qf2, qf1_target, qf2_target, args, envs, device, backend=None):
+        super().__init__(args, envs, device, backend, int(np.prod(envs.single_action_space.shape)))
         self.actor, self.qfs, self.qf_targets = actor, [qf1, qf2], [qf1_target, qf2_target]
-        self.args, self.device = args, torch.device(device)
-        self.backend = offpolicy_backend(self.device) if backend is None else backend
-        if self.backend not in BACKENDS:
-            raise ValueError(f"off-policy backend {self.backend!r}: expected one of {BACKENDS}")
-        self.fused = self.backend == "fused"
-        self.space = envs.single_action_space
-        self.N = int(envs.num_envs)
-        self.O = int(np.array(envs.single_observation_space.shape).prod())
-        self.A = int(np.prod(self.space.shape))
-        self.g = ops.twins(self.device)
-        self.pos, self.full = 0, False
-        self.slots = max(int(args.buffer_size) // self.N, 1)
         self.q_step = self.actor_step = self.alpha_step = 0
         self.autotune = bool(args.autotune)
-        self.last = None
         dev = self.device
         if self.autotune:
             self.target_entropy = -torch.prod(torch.Tensor(self.space.shape).to(dev)).item()
         if not self.fused:
-            self.rb = HostReplayBuffer(args.buffer_size, self.O, self.A, dev, n_envs=self.N)
             self.q_optimizer = optim.Adam(list(qf1.parameters()) + list(qf2.parameters()), lr=args.q_lr)
             self.actor_optimizer = optim.Adam(list(actor.parameters()), lr=args.policy_lr)
             if self.autotune:
@@ -72,34 +59,20 @@ class SACLearner(DeviceRing):
             else:
                 self.alpha = args.alpha
             return
-        if not (1 <= self.O <= ops.OFFPOLICY_MAX_OBS and 1 <= self.A <= ops.OFFPOLICY_MAX_ACT):
-            raise ValueError(f"MI355PPO_OFFPOLICY=fused: the fused networks take obs_dim <= {ops.OFFPOLICY_MAX_OBS} and act_dim <= "
-                             f"{ops.OFFPOLICY_MAX_ACT}, not {self.O} / {self.A}; use MI355PPO_OFFPOLICY=torch")
-        N, O, A = self.N, self.O, self.A
-        self.pa, self.pq = ops.sac_actor_count(O, A), ops.offpolicy_counts(O, A)[1]
+        self.pa, self.pq = ops.sac_actor_count(self.O, self.A), ops.offpolicy_counts(self.O, self.A)[1]
         self.q_off = (self.pa + 3) // 4 * 4                      # the critics start 16-byte aligned (the Adam kernel's float4s)
-        total = self.q_off + 2 * self.pq
-        self.online = torch.zeros(total, dtype=torch.float32, device=dev)
+        self._alloc_flat(self.q_off + 2 * self.pq)
         self.target = torch.zeros(2 * self.pq, dtype=torch.float32, device=dev)          # SAC has no target actor
-        self.grads, self.exp_avg, self.exp_avg_sq = (torch.zeros(total, dtype=torch.float32, device=dev) for _ in range(3))
-        with torch.no_grad():
-            for flat, nets, base in ((self.online, [actor], 0), (self.online, self.qfs, self.q_off), (self.target, self.qf_targets, 0)):
-                off = base
-                for net in nets:
-                    for p in net.parameters():                   # the modules keep working: their parameters are views of the flat buffer
-                        n = p.numel()
-                        flat[off:off + n].copy_(p.reshape(-1))
-                        p.data = flat[off:off + n].view(p.shape)
-                        off += n
+        self._adopt([actor], self.online)
+        self._adopt(self.qfs, self.online, self.q_off)
+        self._adopt(self.qf_targets, self.target)
         self.scale = actor.action_scale.detach().reshape(-1).to(dev).contiguous()
         self.bias = actor.action_bias.detach().reshape(-1).to(dev).contiguous()
         M = int(args.batch_size)
-        self._alloc_ring(M)
         self._y = torch.zeros(M, dtype=torch.float32, device=dev)
         self._lp = torch.zeros(M, dtype=torch.float32, device=dev)
         self._qsc = torch.zeros(4, dtype=torch.float32, device=dev)
         self._asc = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._norm = torch.zeros(1, dtype=torch.float32, device=dev)
         # log_alpha | exp_avg | exp_avg_sq | alpha | alpha_loss: --no-autotune leaves args.alpha in the alpha slot and never launches the step
         self.alpha_state = torch.tensor([0.0, 0.0, 0.0, 1.0 if self.autotune else float(args.alpha), 0.0], dtype=torch.float32, device=dev)
         self.log_alpha_t, self._am, self._av, self.alpha_t, self._alsc = (self.alpha_state[i:i + 1] for i in range(5))
@@ -123,8 +96,7 @@ class SACLearner(DeviceRing):
                 return actions.detach().cpu().numpy()
             eps = torch.randn((self.N, self.A), dtype=torch.float32, device=self.device)
             self.g.sac_policy(self._stage_obs(obs), self._seg(self.online, "actor"), self.scale, self.bias, eps, actions_out=self._act)
-            out = self._act.cpu().numpy()
-            return out if self.device.type == "cuda" else out.copy()      # on the CPU .cpu() aliases the reused buffer
+            return self._copy_out(self._act)
 
     # ------------------------------------------------------------------ training
     def train_step(self, policy_update: bool, target_update: bool, indices=None, noise=None):
@@ -151,22 +123,20 @@ class SACLearner(DeviceRing):
         actor, critics = self._seg(self.online, "actor"), self._seg(self.online, "critics")
         g.sac_target(self.ring, bi, ei, actor, self.target, self.scale, self.bias, noise[0], self.alpha_t, a.gamma, self._y)
         g.td3_critic_fwd_bwd(self.ring, bi, ei, critics, 2, self._y, self._seg(self.grads, "critics"), self._qsc)
-        if adam and sched is not None:
-            self._adam_sched("critics", sched[0])
-        elif adam:
-            self.q_step += 1
-            self._adam("critics", self.q_step, a.q_lr)
+        if adam:
+            if sched is None:
+                self.q_step += 1
+            self._adam_seg("critics", self.q_step if sched is None else sched[0], a.q_lr)
         if policy_update:
             k = 1
             for i in range(int(a.policy_frequency)):
                 g.sac_actor_fwd_bwd(self.ring, bi, ei, actor, critics, self.scale, self.bias, noise[k], self.alpha_t,
                                     self._seg(self.grads, "actor"), self._asc)
                 k += 1
-                if adam and sched is not None:
-                    self._adam_sched("actor", sched[1 + 2 * i])
-                elif adam:
-                    self.actor_step += 1
-                    self._adam("actor", self.actor_step, a.policy_lr)
+                if adam:
+                    if sched is None:
+                        self.actor_step += 1
+                    self._adam_seg("actor", self.actor_step if sched is None else sched[1 + 2 * i], a.policy_lr)
                 if self.autotune:
                     g.sac_policy(self.ring[0], actor, self.scale, self.bias, noise[k], log_pi_out=self._lp, batch_inds=bi, env_inds=ei)
                     k += 1
@@ -177,10 +147,8 @@ class SACLearner(DeviceRing):
         if target_update:
             g.polyak_(critics, self.target, a.tau)
 
-    def _adam(self, which, step, lr):
-        kw = {"total_norm_out": self._norm} if self.device.type == "cuda" else {}
-        self.g.clip_adam_(self._seg(self.online, which), self._seg(self.grads, which), self._seg(self.exp_avg, which),
-                          self._seg(self.exp_avg_sq, which), step, lr, math.inf, 1.0, eps=1e-8, **kw)
+    def _adam_seg(self, which, step, lr):
+        self._adam([self._seg(f, which) for f in self._flats], step, lr)
 
     def adam_schedules(self):
         """(1 + 2 * policy_frequency, 2) host tensor: the library's (step size, bias correction) of the NEXT critic step and, per policy
@@ -190,10 +158,6 @@ class SACLearner(DeviceRing):
         for i in range(int(a.policy_frequency)):
             rows += [ops.adam_schedule(a.policy_lr, self.actor_step + 1 + i), ops.adam_schedule(a.q_lr, self.alpha_step + 1 + i)]
         return torch.tensor(rows, dtype=torch.float32)
-
-    def _adam_sched(self, which, sched2):                        # device only: the host twins take the step as an argument
-        ops.clip_adam_sched_(self._seg(self.online, which), self._seg(self.grads, which), self._seg(self.exp_avg, which),
-                             self._seg(self.exp_avg_sq, which), sched2, math.inf, 1.0, eps=1e-8, total_norm_out=self._norm)
 
     def _train_torch(self, bi, ei, policy_update, target_update, noise):
         a = self.args
@@ -277,5 +241,4 @@ class SACLearner(DeviceRing):
 
     def flat_params(self):
         """(actor, critics, critic targets) flat parameters, detached copies (tests)."""
-        f = lambda nets: torch.cat([p.detach().reshape(-1) for n in nets for p in n.parameters()]).clone()  # noqa: E731
-        return f([self.actor]), f(self.qfs), f(self.qf_targets)
+        return self._flat([self.actor]), self._flat(self.qfs), self._flat(self.qf_targets)

@@ -1,58 +1,36 @@
 """Replay of the minted DQN / C51 runs (tests/golden/dqn_iteration.npz, tools/mint_dqn_goldens.py) through the drop-ins' own classes:
 free-running for the ``torch`` backend (it must meet the reference's random streams), teacher-forced (the golden actions and indices)
-for ``fused``."""
-import json
-import os
-import random
-
+for ``fused``.  The loop and the comparison are tests/replay_harness.py's."""
 import numpy as np
 import torch
 
+import replay_harness as H
 from cleanrl_amd import envs as E
 from cleanrl_amd.agents import C51Network, DQNNetwork
 from cleanrl_amd.learner_dqn import DQNLearner
 
-GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CASES = ("dqn", "dqn_tau", "c51", "c51_small")
 SCALARS = ("loss", "q_values")
 FINAL = ("online", "target")
-
-
-def golden_case(name):
-    z = np.load(os.path.join(GOLDEN_DIR, "dqn_iteration.npz"))
-    return {k.split("/", 1)[1]: z[k] for k in z.files if k.startswith(name + "/")}
-
-
-def sensitivity(name):
-    with open(os.path.join(GOLDEN_DIR, "dqn_iteration_ref_sensitivity.json")) as fh:
-        return json.load(fh)[name]
-
-
-def surface():
-    with open(os.path.join(GOLDEN_DIR, "dqn_cli_surface.json")) as fh:
-        return json.load(fh)
-
-
-def _flat(net):
-    return torch.cat([p.detach().reshape(-1) for p in net.parameters()]).cpu()
+_G = H.Goldens("dqn", SCALARS, FINAL)
+golden_case, sensitivity, surface, deviations, assert_within_sensitivity = (
+    _G.golden_case, _G.sensitivity, _G.surface, _G.deviations, _G.assert_within_sensitivity)
 
 
 def build(name, backend, device=torch.device("cpu")):
     """The case's seeded environment, networks and learner, as the script's ``main`` builds them."""
     g = golden_case(name)
-    cfg = json.loads(bytes(g["config"]).decode())
+    cfg = H.case_config(g)
     c51 = cfg["script"].startswith("c51")
     mod = __import__("cleanrl_amd." + cfg["script"][: -len(".py")], fromlist=["Args"])
     args = mod.Args(**cfg["args"])
     args.total_timesteps = cfg["steps"]
-    random.seed(args.seed)
-    np.random.seed(args.seed)
-    torch.manual_seed(args.seed)
+    H.seed_all(args.seed)
     envs = E.CartPoleReplayVecEnv(1, seed=args.seed, horizon=cfg["horizon"])
     mk = (lambda: C51Network(envs, n_atoms=args.n_atoms, v_min=args.v_min, v_max=args.v_max).to(device)) if c51 else (lambda: DQNNetwork(envs).to(device))
     q_network = mk()
     target_network = mk()
-    init_checksum = _flat(q_network).double().sum().item()
+    init_checksum = H.flat(q_network).double().sum().item()
     target_network.load_state_dict(q_network.state_dict())
     L = DQNLearner(q_network, target_network, args, envs, device, c51=c51, backend=backend)
     return g, mod, args, envs, L, init_checksum
@@ -62,52 +40,22 @@ def replay(name, backend, device=torch.device("cpu"), forced=None):
     """Runs the case's steps as the script's main loop does -> dict of per-step arrays and final flat parameters."""
     g, mod, args, envs, L, init_checksum = build(name, backend, device)
     forced = backend == "fused" if forced is None else forced
-    out = {k: [] for k in ("actions",) + SCALARS}
-    obs, _ = envs.reset(seed=args.seed)
-    for global_step in range(args.total_timesteps):
+
+    def choose_action(obs, global_step):
         epsilon = mod.linear_schedule(args.start_e, args.end_e, args.exploration_fraction * args.total_timesteps, global_step)
-        actions = g["actions"][global_step].copy() if forced else L.act(obs, global_step, epsilon)
-        out["actions"].append(np.asarray(actions, np.int64).reshape(1))
-        next_obs, rewards, terminations, truncations, infos = envs.step(actions)
-        real_next_obs = next_obs.copy()
-        for idx, trunc in enumerate(truncations):
-            if trunc:
-                real_next_obs[idx] = infos["final_observation"][idx]
-        L.store(obs, real_next_obs, actions, rewards, terminations)
-        obs = next_obs
-        sc = {k: np.nan for k in SCALARS}
-        if global_step > args.learning_starts:
-            if global_step % args.train_frequency == 0:
-                L.train_step(indices=(g["batch_inds"][global_step], g["env_inds"][global_step]) if forced else None)
-                sc.update(L.metrics())
-            if global_step % args.target_network_frequency == 0:
-                L.sync_target()
-        for k in SCALARS:
-            out[k].append(sc[k])
-    out = {k: np.asarray(v) for k, v in out.items()}
-    out["final_online"], out["final_target"] = _flat(L.q_network), _flat(L.target_network)
+        return L.act(obs, global_step, epsilon)
+
+    def train(global_step):
+        sc = {}
+        if global_step % args.train_frequency == 0:
+            L.train_step(indices=(g["batch_inds"][global_step], g["env_inds"][global_step]) if forced else None)
+            sc = L.metrics()
+        if global_step % args.target_network_frequency == 0:
+            L.sync_target()
+        return sc
+
+    out = H.run_loop(g, args, envs, L, SCALARS, forced, choose_action, train, action_dtype=np.int64, action_shape=(1,))
+    out["final_online"], out["final_target"] = H.flat(L.q_network), H.flat(L.target_network)
     out["init_checksum"] = init_checksum
     out["learner"] = L
     return out
-
-
-def deviations(name, rec):
-    g = golden_case(name)
-    dev = {}
-    for k in SCALARS:
-        a, b = rec[k], g[k]
-        m = ~np.isnan(b)
-        assert np.array_equal(np.isnan(a), np.isnan(b)), k
-        dev[k] = float(np.abs(a[m] - b[m]).max())
-    s = int(g["stride"])
-    for k in FINAL:
-        dev["final_" + k] = float((rec["final_" + k][::s] - torch.from_numpy(g[f"final_{k}_sub"])).abs().max())
-    return dev
-
-
-def assert_within_sensitivity(name, rec):
-    """Every compared quantity within twice the float32 reference's own recorded deviation from float64, plus 2e-6."""
-    dev, sens = deviations(name, rec), sensitivity(name)
-    print(name, {k: f"{v:.3e} (bar {2 * sens[k] + 2e-6:.3e})" for k, v in dev.items()})
-    bad = {k: (v, 2 * sens[k] + 2e-6) for k, v in dev.items() if not v <= 2 * sens[k] + 2e-6}
-    assert not bad, bad

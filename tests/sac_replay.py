@@ -1,40 +1,32 @@
 """Replay of the minted SAC runs (tests/golden/sac_iteration.npz, tools/mint_sac_goldens.py) through the drop-in's own classes:
 free-running for the ``torch`` backend (it must meet the reference's random streams), teacher-forced (the golden actions, indices
-and every noise draw) for ``fused``."""
-import json
-import os
-import random
-
+and every noise draw) for ``fused``.  The loop and the comparison are tests/replay_harness.py's."""
 import numpy as np
 import torch
 
+import replay_harness as H
 from cleanrl_amd import envs as E
 from cleanrl_amd.agents import SoftActor, SoftQNetwork
 from cleanrl_amd.learner_sac import SACLearner
 from cleanrl_amd.sac_continuous_action import Args
 
-GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CASES = ("sac", "sac_n2", "sac_fixed", "sac_tnf2")
 SCALARS = ("qf1_values", "qf1_loss", "qf2_values", "qf2_loss", "qf_loss", "actor_loss", "alpha_loss", "alpha")
 FINAL = ("actor", "critics", "targets")
-_cache = {}
-
-
-def golden_case(name):
-    if "z" not in _cache:
-        z = np.load(os.path.join(GOLDEN_DIR, "sac_iteration.npz"))
-        _cache["z"] = {k: z[k] for k in z.files}
-    return {k.split("/", 1)[1]: v for k, v in _cache["z"].items() if k.startswith(name + "/")}
+_G = H.Goldens("sac", SCALARS, FINAL,
+               extra=lambda rec, g: {"final_log_alpha": abs(rec["final_log_alpha"] - float(g["final_log_alpha"]))})
+golden_case, sensitivity, surface, deviations, assert_within_sensitivity = (
+    _G.golden_case, _G.sensitivity, _G.surface, _G.deviations, _G.assert_within_sensitivity)
 
 
 def golden_noise(name):
     """Every standard normal draw of the minted run, regenerated from the recorded generator state in the run's order (per step:
     the rollout's (N, A) from ``learning_starts`` on, then the training step's (B, A) draws) and checked against the recorded
     checksums -> list over steps of lists of (B, A) float32 CPU tensors."""
-    if ("noise", name) in _cache:
-        return _cache["noise", name]
+    if ("sac_noise", name) in H._cache:
+        return H._cache["sac_noise", name]
     g = golden_case(name)
-    cfg = json.loads(bytes(g["config"]).decode())
+    cfg = H.case_config(g)
     args = Args(**cfg["args"])
     gen = torch.Generator()
     gen.set_state(torch.from_numpy(g["rng_state"].copy()))
@@ -46,36 +38,20 @@ def golden_noise(name):
         per_step.append([torch.randn((args.batch_size, A), generator=gen) for _ in range(int(off[step + 1] - off[step]))])
     sums = np.asarray([d.double().sum().item() for ds in per_step for d in ds])
     assert np.array_equal(sums, g["noise_checksums"]), "the regenerated draws are not the minted run's"
-    _cache["noise", name] = per_step
+    H._cache["sac_noise", name] = per_step
     return per_step
-
-
-def sensitivity(name):
-    with open(os.path.join(GOLDEN_DIR, "sac_iteration_ref_sensitivity.json")) as fh:
-        return json.load(fh)[name]
-
-
-def surface():
-    with open(os.path.join(GOLDEN_DIR, "sac_cli_surface.json")) as fh:
-        return json.load(fh)
-
-
-def _flat(*nets):
-    return torch.cat([p.detach().reshape(-1) for n in nets for p in n.parameters()]).cpu()
 
 
 def build(name, backend, device=torch.device("cpu")):
     g = golden_case(name)
-    cfg = json.loads(bytes(g["config"]).decode())
+    cfg = H.case_config(g)
     args = Args(**cfg["args"])
     args.total_timesteps = cfg["steps"]
-    random.seed(args.seed)
-    np.random.seed(args.seed)
-    torch.manual_seed(args.seed)
+    H.seed_all(args.seed)
     envs = E.SyntheticReplayVecEnv(args.num_envs, seed=args.seed, horizon=cfg["horizon"])
     actor = SoftActor(envs).to(device)
     nets = [SoftQNetwork(envs).to(device) for _ in range(4)]
-    init_checksum = _flat(actor, *nets[:2]).double().sum().item()
+    init_checksum = H.flat(actor, *nets[:2]).double().sum().item()
     nets[2].load_state_dict(nets[0].state_dict())
     nets[3].load_state_dict(nets[1].state_dict())
     return g, args, envs, actor, nets, SACLearner(actor, *nets, args, envs, device, backend=backend), init_checksum
@@ -84,59 +60,22 @@ def build(name, backend, device=torch.device("cpu")):
 def replay(name, backend, device=torch.device("cpu"), forced=None):
     """Runs the case's steps as the script's main loop does -> dict of per-step arrays and final flat parameters."""
     g, args, envs, actor, nets, L, init_checksum = build(name, backend, device)
-    N = args.num_envs
     forced = backend == "fused" if forced is None else forced
-    out = {k: [] for k in ("actions",) + SCALARS}
-    obs, _ = envs.reset(seed=args.seed)
-    for global_step in range(args.total_timesteps):
-        actions = g["actions"][global_step].copy() if forced else L.act(obs, global_step)
-        out["actions"].append(np.asarray(actions, np.float32).reshape(N, -1))
-        next_obs, rewards, terminations, truncations, infos = envs.step(actions)
-        real_next_obs = next_obs.copy()
-        for idx, trunc in enumerate(truncations):
-            if trunc:
-                real_next_obs[idx] = infos["final_observation"][idx]
-        L.store(obs, real_next_obs, actions, rewards, terminations)
-        obs = next_obs
-        sc = {k: np.nan for k in SCALARS}
-        if global_step > args.learning_starts:
-            pu, tu = global_step % args.policy_frequency == 0, global_step % args.target_network_frequency == 0
-            assert (pu, tu) == (bool(g["policy_update"][global_step]), bool(g["target_update"][global_step]))
-            if forced:
-                nz = [t.to(device) for t in golden_noise(name)[global_step]]
-                assert len(nz) == L.noise_count(pu)
-                L.train_step(pu, tu, indices=(g["batch_inds"][global_step], g["env_inds"][global_step]), noise=nz)
-            else:
-                L.train_step(pu, tu)
-            sc.update(L.metrics())
-        for k in SCALARS:
-            out[k].append(sc.get(k, np.nan))
-    out = {k: np.asarray(v) for k, v in out.items()}
-    out["final_actor"], out["final_critics"], out["final_targets"] = _flat(actor), _flat(*nets[:2]), _flat(*nets[2:])
+
+    def train(global_step):
+        pu, tu = global_step % args.policy_frequency == 0, global_step % args.target_network_frequency == 0
+        assert (pu, tu) == (bool(g["policy_update"][global_step]), bool(g["target_update"][global_step]))
+        if forced:
+            nz = [t.to(device) for t in golden_noise(name)[global_step]]
+            assert len(nz) == L.noise_count(pu)
+            L.train_step(pu, tu, indices=(g["batch_inds"][global_step], g["env_inds"][global_step]), noise=nz)
+        else:
+            L.train_step(pu, tu)
+        return L.metrics()
+
+    out = H.run_loop(g, args, envs, L, SCALARS, forced, L.act, train)
+    out["final_actor"], out["final_critics"], out["final_targets"] = H.flat(actor), H.flat(*nets[:2]), H.flat(*nets[2:])
     out["final_log_alpha"] = L.log_alpha_value()
     out["init_checksum"] = init_checksum
     out["learner"] = L
     return out
-
-
-def deviations(name, rec):
-    g = golden_case(name)
-    dev = {}
-    for k in SCALARS:
-        a, b = rec[k], g[k]
-        m = ~np.isnan(b)
-        assert np.array_equal(np.isnan(a), np.isnan(b)), k
-        dev[k] = float(np.abs(a[m] - b[m]).max()) if m.any() else 0.0
-    s = int(g["stride"])
-    for k in FINAL:
-        dev["final_" + k] = float((rec["final_" + k][::s] - torch.from_numpy(g[f"final_{k}_sub"])).abs().max())
-    dev["final_log_alpha"] = abs(rec["final_log_alpha"] - float(g["final_log_alpha"]))
-    return dev
-
-
-def assert_within_sensitivity(name, rec):
-    """Every compared quantity within twice the float32 reference's own recorded deviation from float64, plus 2e-6."""
-    dev, sens = deviations(name, rec), sensitivity(name)
-    print(name, {k: f"{v:.3e} (bar {2 * sens[k] + 2e-6:.3e})" for k, v in dev.items()})
-    bad = {k: (v, 2 * sens[k] + 2e-6) for k, v in dev.items() if not v <= 2 * sens[k] + 2e-6}
-    assert not bad, bad

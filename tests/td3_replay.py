@@ -1,116 +1,54 @@
 """Replay of the minted DDPG / TD3 runs (tests/golden/td3_iteration.npz, tools/mint_td3_goldens.py) through the drop-ins' own
 classes: free-running for the ``torch`` backend (it must meet the reference's random streams), teacher-forced (the golden actions,
-indices and target noise) for ``fused``."""
-import json
-import os
-import random
-from types import SimpleNamespace
-
-import numpy as np
+indices and target noise) for ``fused``.  The loop and the comparison are tests/replay_harness.py's."""
 import torch
 
+import replay_harness as H
 from cleanrl_amd import envs as E
 from cleanrl_amd.agents import ActionValueNetwork, Actor
 from cleanrl_amd.learner_offpolicy import OffPolicyLearner
 
-GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SCALARS = ("qf1_values", "qf1_loss", "qf2_values", "qf2_loss", "actor_loss")
 FINAL = ("actor", "critics", "targets")
-
-
-def golden_case(name):
-    z = np.load(os.path.join(GOLDEN_DIR, "td3_iteration.npz"))
-    return {k.split("/", 1)[1]: z[k] for k in z.files if k.startswith(name + "/")}
-
-
-def sensitivity(name):
-    with open(os.path.join(GOLDEN_DIR, "td3_iteration_ref_sensitivity.json")) as fh:
-        return json.load(fh)[name]
-
-
-def surface():
-    with open(os.path.join(GOLDEN_DIR, "td3_cli_surface.json")) as fh:
-        return json.load(fh)
-
-
-def _flat(*nets):
-    return torch.cat([p.detach().reshape(-1) for n in nets for p in n.parameters()]).cpu()
+_G = H.Goldens("td3", SCALARS, FINAL)
+golden_case, sensitivity, surface, deviations, assert_within_sensitivity = (
+    _G.golden_case, _G.sensitivity, _G.surface, _G.deviations, _G.assert_within_sensitivity)
 
 
 def replay(name, backend, device=torch.device("cpu")):
     """Runs the case's steps as the script's main loop does -> dict of per-step arrays and final flat parameters."""
     g = golden_case(name)
-    cfg = json.loads(bytes(g["config"]).decode())
+    cfg = H.case_config(g)
     td3 = cfg["script"].startswith("td3")
     mod = __import__("cleanrl_amd." + cfg["script"][: -len(".py")], fromlist=["Args"])
     args = mod.Args(**cfg["args"])
     args.total_timesteps = cfg["steps"]
     N = getattr(args, "num_envs", 1)
     forced = backend == "fused"
-    random.seed(args.seed)
-    np.random.seed(args.seed)
-    torch.manual_seed(args.seed)
+    H.seed_all(args.seed)
     envs = E.SyntheticReplayVecEnv(N, seed=args.seed, horizon=cfg["horizon"])
     mk = lambda: Actor(envs, batched_space=not td3).to(device)  # noqa: E731
     actor = mk()
     qfs = [ActionValueNetwork(envs).to(device) for _ in range(2 if td3 else 1)]
     qts = [ActionValueNetwork(envs).to(device) for _ in qfs]
     target_actor = mk()                                         # both scripts build the target actor last
-    init_checksum = _flat(actor, *qfs).double().sum().item()
+    init_checksum = H.flat(actor, *qfs).double().sum().item()
     target_actor.load_state_dict(actor.state_dict())
     for q, t in zip(qfs, qts):
         t.load_state_dict(q.state_dict())
     L = OffPolicyLearner(actor, qfs, target_actor, qts, args, envs, device, td3=td3, backend=backend)
-    out = {k: [] for k in ("actions",) + SCALARS}
-    obs, _ = envs.reset(seed=args.seed)
-    for global_step in range(args.total_timesteps):
+
+    def train(global_step):
+        pu = global_step % args.policy_frequency == 0
         if forced:
-            actions = g["actions"][global_step].copy()
+            nz = torch.from_numpy(g["noise"][global_step]).to(device) if td3 else None
+            L.train_step(pu, indices=(g["batch_inds"][global_step], g["env_inds"][global_step]), noise=nz)
         else:
-            actions = L.act(obs, global_step)
-        out["actions"].append(np.asarray(actions, np.float32).reshape(N, -1))
-        next_obs, rewards, terminations, truncations, infos = envs.step(actions)
-        real_next_obs = next_obs.copy()
-        for idx, trunc in enumerate(truncations):
-            if trunc:
-                real_next_obs[idx] = infos["final_observation"][idx]
-        L.store(obs, real_next_obs, actions, rewards, terminations)
-        obs = next_obs
-        sc = {k: np.nan for k in SCALARS}
-        if global_step > args.learning_starts:
-            pu = global_step % args.policy_frequency == 0
-            if forced:
-                nz = torch.from_numpy(g["noise"][global_step]).to(device) if td3 else None
-                L.train_step(pu, indices=(g["batch_inds"][global_step], g["env_inds"][global_step]), noise=nz)
-            else:
-                L.train_step(pu)
-            sc.update(L.metrics())
-        for k in SCALARS:
-            out[k].append(sc.get(k, np.nan))
-    out = {k: np.asarray(v) for k, v in out.items()}
-    out["final_actor"], out["final_critics"], out["final_targets"] = _flat(actor), _flat(*qfs), _flat(target_actor, *qts)
+            L.train_step(pu)
+        return L.metrics()
+
+    out = H.run_loop(g, args, envs, L, SCALARS, forced, L.act, train)
+    out["final_actor"], out["final_critics"], out["final_targets"] = H.flat(actor), H.flat(*qfs), H.flat(target_actor, *qts)
     out["init_checksum"] = init_checksum
     out["learner"] = L
     return out
-
-
-def deviations(name, rec):
-    g = golden_case(name)
-    dev = {}
-    for k in SCALARS:
-        a, b = rec[k], g[k]
-        m = ~np.isnan(b)
-        assert np.array_equal(np.isnan(a), np.isnan(b)) or not m.any(), k
-        dev[k] = float(np.abs(a[m] - b[m]).max()) if m.any() else 0.0
-    s = int(g["stride"])
-    for k in FINAL:
-        dev["final_" + k] = float((rec["final_" + k][::s] - torch.from_numpy(g[f"final_{k}_sub"])).abs().max())
-    return dev
-
-
-def assert_within_sensitivity(name, rec):
-    """Every compared quantity within twice the float32 reference's own recorded deviation from float64, plus 2e-6."""
-    dev, sens = deviations(name, rec), sensitivity(name)
-    print(name, {k: f"{v:.3e} (bar {2 * sens[k] + 2e-6:.3e})" for k, v in dev.items()})
-    bad = {k: (v, 2 * sens[k] + 2e-6) for k, v in dev.items() if not v <= 2 * sens[k] + 2e-6}
-    assert not bad, bad
