@@ -230,6 +230,19 @@ SIGNATURES = {
     "mi355ppo_c51_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "mi355ppo_c51_fwd_bwd_f32": (c_int, [_P] * 7 + [c_int64, c_int, _P, _P, _P] + [c_double] * 3 + [_P] * 4 + [c_int] * 4 + [_P, c_size_t, _P]),
     "mi355ppo_c51_fwd_bwd_f32_cpu": (c_int, [_P] * 7 + [c_int64, c_int, _P, _P, _P] + [c_double] * 3 + [_P] * 4 + [c_int] * 4),
+    # Atari DQN / C51 (added under ABI 2.7.1, csrc/dqn_atari.hip)
+    "mi355ppo_replay_add_u8": (c_int, [_P] * 9 + [c_int64, c_int64, c_int, _P]),
+    "mi355ppo_replay_add_u8_cpu": (c_int, [_P] * 9 + [c_int64, c_int64, c_int]),
+    "mi355ppo_replay_gather_u8": (c_int, [_P] * 6 + [c_int64, c_int] + [_P] * 4 + [c_int, _P]),
+    "mi355ppo_replay_gather_u8_cpu": (c_int, [_P] * 6 + [c_int64, c_int] + [_P] * 4 + [c_int]),
+    "mi355ppo_dqn_head_act_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mi355ppo_dqn_head_act_f32": (c_int, [_P] * 6 + [c_int] * 4 + [_P, c_size_t, _P]),
+    "mi355ppo_dqn_head_act_f32_cpu": (c_int, [_P] * 6 + [c_int] * 4),
+    "mi355ppo_dqn_head_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mi355ppo_dqn_head_td_fwd_bwd_f32": (c_int, [_P] * 9 + [c_double] + [_P] * 6 + [c_int] * 3 + [_P, c_size_t, _P]),
+    "mi355ppo_dqn_head_td_fwd_bwd_f32_cpu": (c_int, [_P] * 9 + [c_double] + [_P] * 6 + [c_int] * 3),
+    "mi355ppo_c51_head_fwd_bwd_f32": (c_int, [_P] * 10 + [c_double] * 3 + [_P] * 6 + [c_int] * 4 + [_P, c_size_t, _P]),
+    "mi355ppo_c51_head_fwd_bwd_f32_cpu": (c_int, [_P] * 10 + [c_double] * 3 + [_P] * 6 + [c_int] * 4),
 }
 
 ABI_VERSION = 271       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)

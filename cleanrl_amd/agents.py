@@ -1310,3 +1310,52 @@ class C51Network(nn.Module):
         if action is None:
             action = torch.argmax(q_values, 1)
         return action, pmfs[torch.arange(len(x)), action]
+
+
+def _nature_q(outputs):
+    """The NatureCNN trunk, ``Linear(3136, 512)`` and the head of dqn_atari.py / c51_atari.py: torch's default initialisation (these
+    scripts have no ``layer_init``) in the reference's construction order."""
+    return nn.Sequential(
+        nn.Conv2d(4, 32, 8, stride=4),
+        nn.ReLU(),
+        nn.Conv2d(32, 64, 4, stride=2),
+        nn.ReLU(),
+        nn.Conv2d(64, 64, 3, stride=1),
+        nn.ReLU(),
+        nn.Flatten(),
+        nn.Linear(3136, 512),
+        nn.ReLU(),
+        nn.Linear(512, outputs),
+    )
+
+
+class AtariDQNNetwork(nn.Module):
+    """dqn_atari.py's ``QNetwork``; ``x / 255.0`` is part of the network."""
+
+    def __init__(self, env):
+        super().__init__()
+        self.n = env.single_action_space.n
+        self.network = _nature_q(self.n)
+
+    def forward(self, x):
+        return self.network(x / 255.0)
+
+
+class AtariC51Network(nn.Module):
+    """c51_atari.py's ``QNetwork``: ``n * n_atoms`` outputs, the ``atoms`` buffer and ``get_action``."""
+
+    def __init__(self, env, n_atoms=51, v_min=-10, v_max=10):
+        super().__init__()
+        self.env = env
+        self.n_atoms = n_atoms
+        self.register_buffer("atoms", torch.linspace(v_min, v_max, steps=n_atoms))
+        self.n = env.single_action_space.n
+        self.network = _nature_q(self.n * n_atoms)
+
+    def get_action(self, x, action=None):
+        logits = self.network(x / 255.0)
+        pmfs = torch.softmax(logits.view(len(x), self.n, self.n_atoms), dim=2)
+        q_values = (pmfs * self.atoms).sum(2)
+        if action is None:
+            action = torch.argmax(q_values, 1)
+        return action, pmfs[torch.arange(len(x)), action]

@@ -22,6 +22,7 @@
 #include "pqn_lstm_rows.h"
 #include "offpolicy_rows.h"
 #include "dqn_rows.h"
+#include "dqn_atari_rows.h"
 #include "sac_rows.h"
 
 #include <math.h>
@@ -2024,4 +2025,179 @@ extern "C" MI355PPO_API int mi355ppo_c51_fwd_bwd_f32_cpu(const float* ring_obs, 
     return dq_update_cpu<true>(ring_obs, ring_next_obs, ring_actions, ring_rewards, ring_dones, TileRows{batch_inds, env_inds, slots, n_envs},
                                online, target, atoms, (float)gamma, (float)v_min, (float)v_max, (float)(1.0 / (double)M), grads, scalars_out,
                                next_pmfs_out, target_pmfs_out, M, O, n_actions, n_atoms);
+}
+
+// ------------------------------------------------------------------------------------------------ Atari DQN / C51 (dqn_atari.hip)
+// The frame ring's two copies and the wide heads, from dqn_atari_rows.h / dqn_rows.h in the device's orders: dot products ascending
+// from 0.0f, the softmax, the projection and the loss sums per atom in ascending order, dh over the taken action's atoms, dW / db over
+// the rows that took the action, the scalars through the f64 slot fold.  Every output equals the device's bit for bit.
+namespace {
+
+// z (N, J) = h W^T + b
+void da_forward_host(const float* h, const float* w, const float* b, int N, int J, float* z) {
+    for (int r = 0; r < N; ++r)
+        for (int j = 0; j < J; ++j) z[(int64_t)r * J + j] = da_dot(h + (int64_t)r * kDaH, w + (int64_t)j * kDaH, b[j]);
+}
+
+// q[a] of one row; with atoms, the pmfs replace the logits
+void da_qvalues_host(float* z, int n, int na, const float* atoms, float* q) {
+    for (int a = 0; a < n; ++a) q[a] = (na > 1) ? dq_softmax_q(z + a * na, na, atoms, z + a * na) : z[a];
+}
+
+// da_fwd_kernel, da_row_kernel<C51> and da_wgrad_kernel on the host
+template <bool C51>
+int da_update_cpu(const float* h, const float* h_next, const float* w, const float* b, const float* w_target, const float* b_target,
+                  const float* atoms, const int64_t* actions, const float* rewards, const float* dones, float gamma, float vmin, float vmax,
+                  float norm, float* dh, float* dw, float* db, float* scalars_out, float* aux_a, float* aux_b, int M, int n, int na) {
+    const int J = n * na;
+    std::vector<float> zo((size_t)M * J), zt((size_t)M * J), dz((size_t)M * na), rows((size_t)2 * M), tmp((size_t)5 * na);
+    std::vector<int> act(M);
+    float qt[kDqMaxAct], qo[kDqMaxAct];
+    da_forward_host(h, w, b, M, J, zo.data());
+    da_forward_host(h_next, w_target, b_target, M, J, zt.data());
+    for (int r = 0; r < M; ++r) {
+        float *t = zt.data() + (size_t)r * J, *o = zo.data() + (size_t)r * J, *d = dz.data() + (size_t)r * na;
+        da_qvalues_host(t, n, na, atoms, qt);
+        da_qvalues_host(o, n, na, atoms, qo);
+        const int best = dq_argmax(qt, n), a = (int)op_clamp(actions[r], n);
+        act[r] = a;
+        if constexpr (C51) {
+            float *pl = tmp.data(), *pu = pl + na, *pdl = pu + na, *pdu = pdl + na, *tp = pdu + na;
+            const float delta_z = atoms[1] - atoms[0];
+            for (int j = 0; j < na; ++j) {
+                const float p = t[best * na + j];
+                const C51Proj e = c51_proj_elem(rewards[r], dones[r], gamma, atoms[j], vmin, vmax, delta_z, na, p);
+                pl[j] = e.l, pu[j] = e.u, pdl[j] = e.dml, pdu[j] = e.dmu;
+                if (aux_a) aux_a[(int64_t)r * na + j] = p;
+            }
+            for (int k = 0; k < na; ++k) {
+                tp[k] = c51_proj_atom(k, pl, pu, pdl, pdu, na);
+                if (aux_b) aux_b[(int64_t)r * na + k] = tp[k];
+            }
+            float s = 0.0f, dot = 0.0f;
+            for (int k = 0; k < na; ++k) {
+                const C51Loss e = c51_loss_elem(tp[k], o[a * na + k], norm);
+                pdl[k] = e.g;
+                s = s + e.term;
+                dot = dot + e.gp;
+            }
+            for (int k = 0; k < na; ++k) d[k] = c51_dlogit(o[a * na + k], pdl[k], dot);
+            rows[r] = -s;
+        } else {
+            if (aux_a)
+                for (int k = 0; k < n; ++k) aux_a[(int64_t)r * n + k] = qt[k];
+            const float y = dq_td_target(rewards[r], dones[r], gamma, qt[best]);
+            if (aux_b) aux_b[r] = y;
+            float sq;
+            d[0] = op_mse_row(qo[a], y, norm, &sq);
+            rows[r] = sq;
+        }
+        rows[(size_t)M + r] = qo[a];
+        for (int k = 0; k < kDaH; ++k) dh[(int64_t)r * kDaH + k] = da_dh(d, na, w + (int64_t)a * na * kDaH, k);
+    }
+    for (int j = 0; j < J; ++j) {
+        const int a = j / na, k0 = j - a * na;
+        for (int k = 0; k < kDaH; ++k) dw[(int64_t)j * kDaH + k] = da_wgrad(act.data(), dz.data(), na, M, a, k0, h, k);
+        db[j] = da_wgrad(act.data(), dz.data(), na, M, a, k0, nullptr, 0);
+    }
+    for (int s = 0; s < 2; ++s) scalars_out[s] = op_fold_mean_host(rows.data() + (size_t)s * M, M);
+    return MI355PPO_OK;
+}
+
+}  // namespace
+
+extern "C" MI355PPO_API int mi355ppo_replay_add_u8_cpu(const uint8_t* obs, const uint8_t* next_obs, const int64_t* actions, const float* rewards,
+                                                      const float* dones, uint8_t* ring_frames, int64_t* ring_actions, float* ring_rewards,
+                                                      float* ring_dones, int64_t pos, int64_t slots, int n_envs) {
+    const char* fn = "mi355ppo_replay_add_u8_cpu";
+    MI355_REQUIRE(obs && next_obs && actions && rewards && dones && ring_frames && ring_actions && ring_rewards && ring_dones, MI355PPO_EINVAL,
+                  "%s: null pointer", fn);
+    if (int rc = da_ring_shape(fn, slots, n_envs)) return rc;
+    MI355_REQUIRE(pos >= 0 && pos < slots && n_envs <= (1 << 16), MI355PPO_EINVAL, "%s: pos=%lld slots=%lld n_envs=%d: 0 <= pos < slots, n_envs <= 65536",
+                  fn, (long long)pos, (long long)slots, n_envs);
+    for (int which = (slots == 1 ? 1 : 0); which < 2; ++which)
+        for (int e = 0; e < n_envs; ++e) {
+            const uint8_t* stack = (which ? next_obs : obs) + (int64_t)e * (kDaPlanes * kDaPix);
+            uint8_t* dst = ring_frames + 4 * da_frame(which ? da_next_slot(pos, slots) : pos, e, n_envs);
+            for (int p = 0; p < kDaPix; ++p) {
+                const uint32_t v = da_pack(stack, p);
+                memcpy(dst + 4 * (int64_t)p, &v, 4);
+            }
+        }
+    for (int e = 0; e < n_envs; ++e) {
+        ring_actions[pos * n_envs + e] = actions[e];
+        ring_rewards[pos * n_envs + e] = rewards[e];
+        ring_dones[pos * n_envs + e] = dones[e];
+    }
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_replay_gather_u8_cpu(const uint8_t* ring_frames, const int64_t* ring_actions, const float* ring_rewards,
+                                                         const float* ring_dones, const int64_t* batch_inds, const int64_t* env_inds,
+                                                         int64_t slots, int n_envs, uint8_t* frames_out, int64_t* actions_out, float* rewards_out,
+                                                         float* dones_out, int M) {
+    const char* fn = "mi355ppo_replay_gather_u8_cpu";
+    MI355_REQUIRE(ring_frames && ring_actions && ring_rewards && ring_dones && batch_inds && env_inds && frames_out && actions_out && rewards_out &&
+                      dones_out, MI355PPO_EINVAL, "%s: null pointer", fn);
+    if (int rc = da_ring_shape(fn, slots, n_envs)) return rc;
+    MI355_REQUIRE(M >= 1 && M <= kDaMaxRows, MI355PPO_EINVAL, "%s: rows=%d: 1 <= rows <= %d", fn, M, kDaMaxRows);
+    const size_t fb = (size_t)4 * kDaPix;
+    for (int m = 0; m < M; ++m) {
+        const int64_t slot = op_clamp(batch_inds[m], slots);
+        const int e = (int)op_clamp(env_inds[m], n_envs);
+        memcpy(frames_out + (size_t)m * fb, ring_frames + 4 * da_frame(slot, e, n_envs), fb);
+        memcpy(frames_out + (size_t)(M + m) * fb, ring_frames + 4 * da_frame(da_next_slot(slot, slots), e, n_envs), fb);
+        actions_out[m] = ring_actions[slot * n_envs + e];
+        rewards_out[m] = ring_rewards[slot * n_envs + e];
+        dones_out[m] = ring_dones[slot * n_envs + e];
+    }
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_dqn_head_act_f32_cpu(const float* h, const float* w, const float* b, const float* atoms, int64_t* actions_out,
+                                                         float* q_out, int N, int hidden, int n_actions, int n_atoms) {
+    const char* fn = "mi355ppo_dqn_head_act_f32_cpu";
+    MI355_REQUIRE(h && w && b && actions_out, MI355PPO_EINVAL, "%s: null pointer", fn);
+    if (int rc = da_shape(fn, N, hidden, n_actions, n_atoms)) return rc;
+    MI355_REQUIRE(n_atoms == 1 || atoms, MI355PPO_EINVAL, "%s: n_atoms=%d needs the atoms", fn, n_atoms);
+    const int J = n_actions * n_atoms;
+    std::vector<float> z((size_t)N * J);
+    da_forward_host(h, w, b, N, J, z.data());
+    float q[kDqMaxAct];
+    for (int r = 0; r < N; ++r) {
+        da_qvalues_host(z.data() + (size_t)r * J, n_actions, n_atoms, atoms, q);
+        if (q_out)
+            for (int a = 0; a < n_actions; ++a) q_out[(int64_t)r * n_actions + a] = q[a];
+        actions_out[r] = (int64_t)dq_argmax(q, n_actions);
+    }
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_dqn_head_td_fwd_bwd_f32_cpu(const float* h, const float* h_next, const float* w, const float* b,
+                                                                const float* w_target, const float* b_target, const int64_t* actions,
+                                                                const float* rewards, const float* dones, double gamma, float* dh, float* dw,
+                                                                float* db, float* scalars_out, float* target_q_out, float* td_target_out, int M,
+                                                                int hidden, int n_actions) {
+    const char* fn = "mi355ppo_dqn_head_td_fwd_bwd_f32_cpu";
+    MI355_REQUIRE(h && h_next && w && b && w_target && b_target && actions && rewards && dones && dh && dw && db && scalars_out, MI355PPO_EINVAL,
+                  "%s: null pointer", fn);
+    if (int rc = da_shape(fn, M, hidden, n_actions, 1)) return rc;
+    return da_update_cpu<false>(h, h_next, w, b, w_target, b_target, nullptr, actions, rewards, dones, (float)gamma, 0.0f, 0.0f,
+                                (float)(2.0 / (double)M), dh, dw, db, scalars_out, target_q_out, td_target_out, M, n_actions, 1);
+}
+
+extern "C" MI355PPO_API int mi355ppo_c51_head_fwd_bwd_f32_cpu(const float* h, const float* h_next, const float* w, const float* b,
+                                                             const float* w_target, const float* b_target, const float* atoms,
+                                                             const int64_t* actions, const float* rewards, const float* dones, double gamma,
+                                                             double v_min, double v_max, float* dh, float* dw, float* db, float* scalars_out,
+                                                             float* next_pmfs_out, float* target_pmfs_out, int M, int hidden, int n_actions,
+                                                             int n_atoms) {
+    const char* fn = "mi355ppo_c51_head_fwd_bwd_f32_cpu";
+    MI355_REQUIRE(h && h_next && w && b && w_target && b_target && actions && rewards && dones && dh && dw && db && scalars_out, MI355PPO_EINVAL,
+                  "%s: null pointer", fn);
+    if (int rc = da_shape(fn, M, hidden, n_actions, n_atoms)) return rc;
+    MI355_REQUIRE(n_atoms >= 2 && atoms, MI355PPO_EINVAL, "%s: n_atoms=%d: the projection needs the atoms, at least two (delta_z = atoms[1] - atoms[0])",
+                  fn, n_atoms);
+    return da_update_cpu<true>(h, h_next, w, b, w_target, b_target, atoms, actions, rewards, dones, (float)gamma, (float)v_min, (float)v_max,
+                               (float)(1.0 / (double)M), dh, dw, db, scalars_out, next_pmfs_out, target_pmfs_out, M, n_actions, n_atoms);
 }

@@ -749,3 +749,41 @@ class CartPoleReplayVecEnv(CartPoleVecEnv):
             infos["final_observation"] = final
             infos["_final_observation"] = terminated | truncated
         return obs, reward, terminated, truncated, infos
+
+
+class AtariReplayVecEnv(SyntheticAtariVecEnv):
+    """The Atari stand-in of dqn_atari.py / c51_atari.py: ``SyntheticAtariVecEnv``'s byte stream with a seeded
+    ``single_action_space.sample()``, an optional truncation ``horizon`` (steps per episode) and gymnasium's ``final_observation`` in
+    ``infos`` when an episode ends (the returned observation is then the next episode's first)."""
+
+    def __init__(self, num_envs: int, seed: int = 0, n_actions: int = 4, horizon=None, pool_planes: int = 2048):
+        super().__init__(num_envs, seed=seed, n_actions=n_actions, pool_planes=pool_planes)
+        self.horizon = None if horizon is None else int(horizon)
+        self.single_action_space = self.action_space = SamplingDiscrete(n_actions)
+        self.single_action_space.seed(seed)
+        self.steps = np.zeros(num_envs, np.int64)
+
+    def reset(self, seed: Optional[int] = None, out=None):
+        self.steps[:] = 0
+        return super().reset(seed, out)
+
+    def step(self, action, out=None):
+        n = self.num_envs
+        reward = self.rng.choice(np.array([-1.0, 0.0, 1.0]), size=n, p=[0.05, 0.9, 0.05])
+        terminated = self.rng.random_sample(n) < self.done_p
+        jump = self.rng.randint(0, len(self.planes), size=n)
+        self.cursor += 1
+        self.steps += 1
+        truncated = ~terminated & (self.steps >= self.horizon) if self.horizon is not None else np.zeros(n, bool)
+        done = terminated | truncated
+        infos = _final_info(done, *self.stats.update(reward.astype(np.float32), done))
+        if done.any():
+            last = self._obs()                                    # the ending episodes' last stacks, before the cursor jumps
+            final = np.empty(n, dtype=object)
+            for i in np.flatnonzero(done):
+                final[i] = last[i].copy()
+            infos["final_observation"] = final
+            infos["_final_observation"] = done.copy()
+        self.cursor = np.where(done, jump, self.cursor)
+        self.steps[done] = 0
+        return self._obs(out), reward, terminated, truncated, infos

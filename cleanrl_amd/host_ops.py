@@ -17,7 +17,7 @@ import ctypes
 import torch
 
 from . import _lib
-from .ops import IMPALA_CHANNELS, _lstm_dims, _ptr_array, dqn_counts, dqn_limits_ok, offpolicy_counts, pqn_param_count, radam_schedule, sac_actor_count, trxl_dims  # noqa: F401  (one definition for both modules)
+from .ops import ATARI_FRAME, IMPALA_CHANNELS, _lstm_dims, _ptr_array, dqn_counts, dqn_head_limits_ok, dqn_limits_ok, offpolicy_counts, pqn_param_count, radam_schedule, sac_actor_count, trxl_dims  # noqa: F401  (one definition for both modules)
 
 LOSS_SCALARS = 7
 
@@ -621,4 +621,75 @@ def c51_fwd_bwd(ring, batch_inds, env_inds, online, target, atoms, n_actions, ga
               _in(target, torch.float32, (P,), "target"), _in(atoms, torch.float32, (na,), "atoms"), float(gamma), float(v_min), float(v_max),
               _out(grads, torch.float32, P, "grads"), _out(scalars, torch.float32, 2, "scalars"),
               _opt_out(next_pmfs_out, M * na, "next_pmfs_out"), _opt_out(target_pmfs_out, M * na, "target_pmfs_out"), M, O, int(n_actions), na)
+    return scalars
+
+
+# ------------------------------------------------------------------------------------------- Atari DQN / C51 twins (csrc/dqn_atari.hip)
+def _frame_ring(ring):
+    frames, act, rew, done = ring
+    slots, N = frames.shape[:2]
+    specs = ((frames, torch.uint8, (slots, N) + ATARI_FRAME, "ring frames"), (act, torch.int64, (slots, N), "ring actions"),
+             (rew, torch.float32, (slots, N), "ring rewards"), (done, torch.float32, (slots, N), "ring dones"))
+    return slots, N, [_in(t, dt, shape, nm) for t, dt, shape, nm in specs]
+
+
+def replay_add_u8(ring, pos, obs, next_obs, actions, rewards, dones):
+    slots, N, rp = _frame_ring(ring)
+    H, W, C = ATARI_FRAME
+    _lib.call("mi355ppo_replay_add_u8_cpu", _in(obs, torch.uint8, (N, C, H, W), "obs"), _in(next_obs, torch.uint8, (N, C, H, W), "next_obs"),
+              _in(actions, torch.int64, (N,), "actions"), _in(rewards, torch.float32, (N,), "rewards"), _in(dones, torch.float32, (N,), "dones"),
+              *rp, int(pos), slots, N)
+
+
+def replay_gather_u8(ring, batch_inds, env_inds, frames_out, actions_out, rewards_out, dones_out):
+    slots, N, rp = _frame_ring(ring)
+    (M,) = batch_inds.shape
+    H, W, C = ATARI_FRAME
+    _lib.call("mi355ppo_replay_gather_u8_cpu", *rp, _in(batch_inds, torch.int64, (M,), "batch_inds"), _in(env_inds, torch.int64, (M,), "env_inds"),
+              slots, N, _out(frames_out, torch.uint8, 2 * M * H * W * C, "frames_out"), _out(actions_out, torch.int64, M, "actions_out"),
+              _out(rewards_out, torch.float32, M, "rewards_out"), _out(dones_out, torch.float32, M, "dones_out"), M)
+    return frames_out
+
+
+def dqn_head_act(h, w, b, n_actions, actions_out, atoms=None, q_out=None):
+    N, hidden = h.shape
+    na = 1 if atoms is None else atoms.numel()
+    J = int(n_actions) * na
+    _lib.call("mi355ppo_dqn_head_act_f32_cpu", _in(h, torch.float32, (N, hidden), "h"), _in(w, torch.float32, (J, hidden), "w"),
+              _in(b, torch.float32, (J,), "b"), None if atoms is None else _in(atoms, torch.float32, (na,), "atoms"),
+              _out(actions_out, torch.int64, N, "actions_out"), _opt_out(q_out, N * n_actions, "q_out"), N, hidden, int(n_actions), na)
+    return actions_out
+
+
+def _head_update_ptrs(h, h_next, w, b, w_target, b_target, actions, rewards, dones, J):
+    M, hidden = h.shape
+    return M, hidden, [_in(h, torch.float32, (M, hidden), "h"), _in(h_next, torch.float32, (M, hidden), "h_next"),
+                       _in(w, torch.float32, (J, hidden), "w"), _in(b, torch.float32, (J,), "b"),
+                       _in(w_target, torch.float32, (J, hidden), "w_target"), _in(b_target, torch.float32, (J,), "b_target")], [
+                       _in(actions, torch.int64, (M,), "actions"), _in(rewards, torch.float32, (M,), "rewards"),
+                       _in(dones, torch.float32, (M,), "dones")]
+
+
+def _head_grads(dh, dw, db, scalars, M, hidden, J):
+    return [_out(dh, torch.float32, M * hidden, "dh"), _out(dw, torch.float32, J * hidden, "dw"), _out(db, torch.float32, J, "db"),
+            _out(scalars, torch.float32, 2, "scalars")]
+
+
+def dqn_head_td_fwd_bwd(h, h_next, w, b, w_target, b_target, actions, rewards, dones, n_actions, gamma, dh, dw, db, scalars,
+                        target_q_out=None, td_target_out=None):
+    J = int(n_actions)
+    M, hidden, nets, batch = _head_update_ptrs(h, h_next, w, b, w_target, b_target, actions, rewards, dones, J)
+    _lib.call("mi355ppo_dqn_head_td_fwd_bwd_f32_cpu", *nets, *batch, float(gamma), *_head_grads(dh, dw, db, scalars, M, hidden, J),
+              _opt_out(target_q_out, M * J, "target_q_out"), _opt_out(td_target_out, M, "td_target_out"), M, hidden, J)
+    return scalars
+
+
+def c51_head_fwd_bwd(h, h_next, w, b, w_target, b_target, atoms, actions, rewards, dones, n_actions, gamma, v_min, v_max, dh, dw, db, scalars,
+                     next_pmfs_out=None, target_pmfs_out=None):
+    na = atoms.numel()
+    J = int(n_actions) * na
+    M, hidden, nets, batch = _head_update_ptrs(h, h_next, w, b, w_target, b_target, actions, rewards, dones, J)
+    _lib.call("mi355ppo_c51_head_fwd_bwd_f32_cpu", *nets, _in(atoms, torch.float32, (na,), "atoms"), *batch, float(gamma), float(v_min),
+              float(v_max), *_head_grads(dh, dw, db, scalars, M, hidden, J), _opt_out(next_pmfs_out, M * na, "next_pmfs_out"),
+              _opt_out(target_pmfs_out, M * na, "target_pmfs_out"), M, hidden, int(n_actions), na)
     return scalars

@@ -1,0 +1,308 @@
+"""The replay buffer, action logic and training step of ``dqn_atari.py`` and ``c51_atari.py`` (reference: cleanrl/dqn_atari.py,
+cleanrl/c51_atari.py and ``ReplayBuffer(..., optimize_memory_usage=True, handle_timeout_termination=False)`` of cleanrl_utils/buffers.py).
+
+====================================================  ==============================================================
+reference                                              here
+====================================================  ==============================================================
+``ReplayBuffer(optimize_memory_usage=True)``           ``torch`` -- ``HostFrameBuffer`` (one u8 array, the reference's add / sample rules);
+                                                       ``fused`` -- the u8 frame ring in device memory, channels-last, pinned staging
+``random.random() < epsilon``, then ``sample()``       ``act``: the same two draws in the same order; greedy on ``fused``: the trunk and
+per env or ``argmax(q_network(obs))`` /                ``Linear(3136, 512)`` on this library's kernels, then ``mi355ppo_dqn_head_act_f32``
+``get_action(obs)``
+``rb.add(obs, real_next_obs, ...)``                    ``store``: one staged copy + ``mi355ppo_replay_add_u8``
+``rb.sample`` (skips ``pos`` when full)                ``sample_indices``
+the update up to ``optimizer.step``                    ``train_step``: ``mi355ppo_replay_gather_u8``, target trunk + FC under ``no_grad``, online
+                                                       trunk + FC under autograd, ``mi355ppo_dqn_head_td_fwd_bwd_f32`` /
+                                                       ``mi355ppo_c51_head_fwd_bwd_f32`` (3 launches), ``h.backward(dh)`` into the flat gradient,
+                                                       ``mi355ppo_clip_adam_f32`` (eps 1e-8 / ``0.01 / batch_size``)
+the ``tau`` loop / ``load_state_dict``                 ``sync_target``: ``mi355ppo_polyak_f32`` / one flat copy
+====================================================  ==============================================================
+
+Backend: ``MI355PPO_OFFPOLICY=torch|fused``, default ``torch``.  Both backends draw ``random``, ``np.random`` and
+the action space's stream in the reference's order.  On the CPU ``fused`` runs the host twins around torch's convolutions.
+"""
+from __future__ import annotations
+
+import random
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+import torch.optim as optim
+
+from . import ops
+from .learner_offpolicy import DeviceRing, advance
+
+FRAME = (4, 84, 84)
+
+
+class HostFrameBuffer:
+    """The memory-optimised ``ReplayBuffer``: ONE u8 observation array; ``add`` writes obs to ``pos`` and next_obs to
+    ``(pos + 1) % slots``; a sample's next_obs is the frame one slot on."""
+
+    def __init__(self, buffer_size: int, device, n_envs: int = 1):
+        self.slots, self.n_envs, self.device = max(int(buffer_size) // n_envs, 1), n_envs, device
+        self.observations = np.zeros((self.slots, n_envs) + FRAME, np.uint8)
+        self.actions = np.zeros((self.slots, n_envs, 1), np.int64)
+        self.rewards = np.zeros((self.slots, n_envs), np.float32)
+        self.dones = np.zeros((self.slots, n_envs), np.float32)
+        self.pos, self.full = 0, False
+
+    def add(self, obs, next_obs, action, reward, done):
+        self.observations[self.pos] = np.array(obs)
+        self.observations[(self.pos + 1) % self.slots] = np.array(next_obs)
+        self.actions[self.pos] = np.array(action).reshape(self.n_envs, 1)
+        self.rewards[self.pos] = np.array(reward)
+        self.dones[self.pos] = np.array(done)
+        advance(self)
+
+    def gather(self, bi, ei):
+        t = lambda a: torch.tensor(a, device=self.device)  # noqa: E731
+        return (t(self.observations[bi, ei, :]), t(self.actions[bi, ei, :]), t(self.observations[(bi + 1) % self.slots, ei, :]),
+                t(self.dones[bi, ei].reshape(-1, 1)), t(self.rewards[bi, ei].reshape(-1, 1)))
+
+
+class AtariDQNLearner(DeviceRing):
+    """``c51``: the networks are ``AtariC51Network`` (atoms, ``get_action``) and the update is the categorical one."""
+
+    def __init__(self, q_network, target_network, args, envs, device, c51: bool, backend=None):
+        self.c51 = bool(c51)
+        self.n = int(envs.single_action_space.n)
+        self.n_atoms = int(args.n_atoms) if self.c51 else 1
+        if tuple(envs.single_observation_space.shape) != FRAME:
+            raise ValueError(f"the Atari learners take {FRAME} uint8 frame stacks, not {tuple(envs.single_observation_space.shape)}")
+        super().__init__(args, envs, device, backend, 1, act_dtype=np.int64)
+        self.q_network, self.target_network = q_network, target_network
+        self.eps = 0.01 / args.batch_size if self.c51 else 1e-8
+        self.step = 0
+        if not self.fused:
+            self.optimizer = optim.Adam(q_network.parameters(), lr=args.learning_rate, eps=self.eps)
+            return
+        dev = self.device
+        total = sum(p.numel() for p in q_network.parameters())
+        self._alloc_flat(total)
+        self.target = torch.zeros(total, dtype=torch.float32, device=dev)
+        self._adopt([q_network], self.online)
+        self._adopt([target_network], self.target)
+        for p, off in self._param_offsets(q_network):                       # autograd accumulates into the flat gradient
+            p.grad = self.grads[off:off + p.numel()].view(p.shape)
+        J = self.n * self.n_atoms
+        self.head_off = total - J * ops.DQN_HEAD_HIDDEN - J
+        self.atoms = q_network.atoms.detach().to(dev).contiguous() if self.c51 else None
+        M = int(args.batch_size)
+        self._greedy = torch.zeros(self.N, dtype=torch.int64, device=dev)
+        self._sc = torch.zeros(2, dtype=torch.float32, device=dev)
+        self._dh = torch.zeros((M, ops.DQN_HEAD_HIDDEN), dtype=torch.float32, device=dev)
+        self._trunks = {}
+
+    @staticmethod
+    def _param_offsets(net):
+        off = 0
+        for p in net.parameters():
+            yield p, off
+            off += p.numel()
+
+    def _host_buffer(self, act_dtype):
+        return HostFrameBuffer(self.args.buffer_size, self.device, n_envs=self.N)
+
+    def _check_sizes(self):
+        if not ops.dqn_head_limits_ok(self.n, self.n_atoms, int(self.args.batch_size)) or (self.c51 and self.n_atoms < 2):
+            raise ValueError(f"MI355PPO_OFFPOLICY=fused: the fused Q heads take 2 <= n_actions <= {ops.DQN_MAX_ACT}, n_atoms <= "
+                             f"{ops.DQN_MAX_ATOMS} (at least 2 for c51), n_actions * n_atoms <= {ops.DQN_HEAD_MAX_OUT} and batch_size <= "
+                             f"{ops.DQN_HEAD_MAX_ROWS}, not {self.n} / {self.n_atoms} / {self.args.batch_size}; use MI355PPO_OFFPOLICY=torch")
+
+    def _alloc_ring(self, M: int):
+        dev, N = self.device, self.N
+        H, W, C = ops.ATARI_FRAME
+        try:
+            frames = torch.zeros((self.slots, N, H, W, C), dtype=torch.uint8, device=dev)
+        except (RuntimeError, MemoryError) as e:
+            raise ValueError(f"MI355PPO_OFFPOLICY=fused: a frame ring of {self.slots} slots x {N} envs ({self.slots * N * H * W * C / 1e9:.1f} GB) "
+                             f"cannot be allocated on {dev}; lower --buffer-size or use MI355PPO_OFFPOLICY=torch") from e
+        self.ring = (frames, torch.zeros((self.slots, N), dtype=torch.int64, device=dev), torch.zeros((self.slots, N), device=dev),
+                     torch.zeros((self.slots, N), device=dev))
+        pin = (lambda t: t.pin_memory()) if dev.type == "cuda" else (lambda t: t)
+        self._frames_host = pin(torch.zeros((2, N, C, H, W), dtype=torch.uint8))      # obs | next_obs as the env gives them
+        self._act_host = pin(torch.zeros(N, dtype=torch.int64))
+        self._rd_host = pin(torch.zeros((2, N), dtype=torch.float32))
+        self._idx_host = pin(torch.zeros((2, M), dtype=torch.int64))
+        self._frames_dev = torch.zeros_like(self._frames_host, device=dev)
+        self._act_dev = torch.zeros(N, dtype=torch.int64, device=dev)
+        self._rd_dev = torch.zeros((2, N), dtype=torch.float32, device=dev)
+        self._idx = torch.zeros((2, M), dtype=torch.int64, device=dev)
+        self._obs_hwc = torch.zeros((N, H, W, C), dtype=torch.uint8, device=dev)
+        self._batch = (torch.zeros((2 * M, H, W, C), dtype=torch.uint8, device=dev), torch.zeros(M, dtype=torch.int64, device=dev),
+                       torch.zeros(M, device=dev), torch.zeros(M, device=dev))
+        self._norm = torch.zeros(1, dtype=torch.float32, device=dev)
+
+    # ------------------------------------------------------------------ the networks below the head
+    def _hidden(self, net, frames_hwc):
+        """``Linear(3136, 512)``'s ReLU output on (rows, 84, 84, 4) u8 rows: this library's trunk and FC on a GPU, torch's on the CPU."""
+        seq = net.network
+        if self.device.type != "cuda":
+            return seq[:9](frames_hwc.permute(0, 3, 1, 2).float() / 255.0)
+        from . import cnn
+
+        trunk = self._trunks.get(id(net))
+        if trunk is None:
+            trunk = self._trunks[id(net)] = cnn.NatureTrunk()
+        feats = trunk(frames_hwc, None, seq[0], seq[2], seq[4])
+        return cnn.LinearReLUHwcFn.apply(feats, seq[7].weight, seq[7].bias, trunk.bufs)
+
+    def _head(self, flat):
+        J = self.n * self.n_atoms
+        w = flat[self.head_off:self.head_off + J * ops.DQN_HEAD_HIDDEN].view(J, ops.DQN_HEAD_HIDDEN)
+        return w, flat[self.head_off + J * ops.DQN_HEAD_HIDDEN:]
+
+    # ------------------------------------------------------------------ rollout
+    def act(self, obs, global_step: int, epsilon: float):
+        """The step's actions (N,) int64: ``random.random() < epsilon`` first, then ``sample()`` per env or the greedy action."""
+        if random.random() < epsilon:
+            return np.array([self.space.sample() for _ in range(self.N)])
+        with torch.no_grad():
+            if not self.fused:
+                x = torch.Tensor(obs).to(self.device)
+                if self.c51:
+                    actions, _ = self.q_network.get_action(x)
+                else:
+                    actions = torch.argmax(self.q_network(x), dim=1)
+                return actions.cpu().numpy()
+            self._frames_host[0].copy_(torch.from_numpy(np.ascontiguousarray(obs, np.uint8)).reshape(self._frames_host[0].shape))
+            if self.device.type == "cuda":
+                self._frames_dev[0].copy_(self._frames_host[0], non_blocking=True)
+                rows = ops.obs_nchw_to_nhwc_u8(self._frames_dev[0], out=self._obs_hwc)
+            else:
+                rows = self._frames_host[0].permute(0, 2, 3, 1).contiguous()
+            w, b = self._head(self.online)
+            self.g.dqn_head_act(self._hidden(self.q_network, rows).contiguous(), w, b, self.n, self._greedy, atoms=self.atoms)
+            return self._copy_out(self._greedy)
+
+    def store(self, obs, real_next_obs, actions, rewards, terminations):
+        """``rb.add(obs, real_next_obs, actions, rewards, terminations, infos)``."""
+        if not self.fused:
+            self.rb.add(obs, real_next_obs, actions, rewards, terminations)
+            self.pos, self.full = self.rb.pos, self.rb.full
+            return
+        fh, ah, rh = self._frames_host, self._act_host, self._rd_host
+        fh[0].copy_(torch.from_numpy(np.ascontiguousarray(obs, np.uint8)).reshape(fh[0].shape))
+        fh[1].copy_(torch.from_numpy(np.ascontiguousarray(real_next_obs, np.uint8)).reshape(fh[1].shape))
+        ah.copy_(torch.from_numpy(np.asarray(actions, np.int64).reshape(-1)))
+        rh[0].copy_(torch.from_numpy(np.asarray(rewards, np.float32).reshape(-1)))
+        rh[1].copy_(torch.from_numpy(np.asarray(terminations, np.float32).reshape(-1)))
+        if self.device.type == "cuda":
+            self._frames_dev.copy_(fh, non_blocking=True)
+            self._act_dev.copy_(ah, non_blocking=True)
+            self._rd_dev.copy_(rh, non_blocking=True)
+            fh, ah, rh = self._frames_dev, self._act_dev, self._rd_dev
+        self.g.replay_add_u8(self.ring, self.pos, fh[0], fh[1], ah, rh[0], rh[1])
+        advance(self)
+
+    def sample_indices(self, batch_size: int):
+        """The memory-optimised ``ReplayBuffer.sample``: never slot ``pos`` once full; then ``env_indices``."""
+        if self.full:
+            batch_inds = (np.random.randint(1, self.slots, size=batch_size) + self.pos) % self.slots
+        else:
+            batch_inds = np.random.randint(0, self.pos, size=batch_size)
+        env_indices = np.random.randint(0, high=self.N, size=(len(batch_inds),))
+        return batch_inds, env_indices
+
+    # ------------------------------------------------------------------ training
+    def train_step(self, indices=None):
+        """One ``# ALGO LOGIC: training.`` block up to the optimizer step.  ``indices`` replaces the draws (teacher forcing)."""
+        M = int(self.args.batch_size)
+        bi, ei = self.sample_indices(M) if indices is None else indices
+        if not self.fused:
+            return self._train_torch(np.asarray(bi), np.asarray(ei))
+        idx = self._stage_indices(bi, ei)
+        self.update_kernels(idx[0], idx[1])
+        self.last = ("fused",)
+        return self
+
+    def update_kernels(self, bi, ei, adam: bool = True, aux=None):
+        """The update on device-resident indices: gather, both trunks, the head kernels, the backward below the head, Adam.  ``aux``:
+        an optional pair of tensors for the target side's outputs (tests)."""
+        a, g = self.args, self.g
+        M = bi.numel()
+        frames, actions, rewards, dones = self._batch
+        g.replay_gather_u8(self.ring, bi, ei, frames, actions, rewards, dones)
+        with torch.no_grad():
+            h_next = self._hidden(self.target_network, frames[M:]).contiguous()
+        h = self._hidden(self.q_network, frames[:M])
+        hd = h.detach().contiguous()
+        (w, b), (wt, bt), (dw, db) = self._head(self.online), self._head(self.target), self._head(self.grads)
+        self.grads[:self.head_off].zero_()
+        aux = aux or (None, None)
+        if self.c51:
+            g.c51_head_fwd_bwd(hd, h_next, w, b, wt, bt, self.atoms, actions, rewards, dones, self.n, a.gamma, a.v_min, a.v_max, self._dh, dw, db,
+                               self._sc, *aux)
+        else:
+            g.dqn_head_td_fwd_bwd(hd, h_next, w, b, wt, bt, actions, rewards, dones, self.n, a.gamma, self._dh, dw, db, self._sc, *aux)
+        h.backward(self._dh)
+        if adam:
+            self.step += 1
+            self._adam(self._flats, self.step, a.learning_rate, self.eps)
+            for trunk in self._trunks.values():
+                trunk.bufs.weights_version += 1
+
+    def _train_torch(self, bi, ei):
+        a = self.args
+        observations, actions, next_observations, dones, rewards = self.rb.gather(bi, ei)
+        q_network, target_network = self.q_network, self.target_network
+        if self.c51:
+            with torch.no_grad():
+                _, next_pmfs = target_network.get_action(next_observations)
+                next_atoms = rewards + a.gamma * target_network.atoms * (1 - dones)
+                delta_z = target_network.atoms[1] - target_network.atoms[0]
+                tz = next_atoms.clamp(a.v_min, a.v_max)
+                b = (tz - a.v_min) / delta_z
+                l = b.floor().clamp(0, a.n_atoms - 1)  # noqa: E741
+                u = b.ceil().clamp(0, a.n_atoms - 1)
+                d_m_l = (u + (l == u).float() - b) * next_pmfs
+                d_m_u = (b - l) * next_pmfs
+                target_pmfs = torch.zeros_like(next_pmfs)
+                for i in range(target_pmfs.size(0)):
+                    target_pmfs[i].index_add_(0, l[i].long(), d_m_l[i])
+                    target_pmfs[i].index_add_(0, u[i].long(), d_m_u[i])
+            _, old_pmfs = q_network.get_action(observations, actions.flatten())
+            loss = (-(target_pmfs * old_pmfs.clamp(min=1e-5, max=1 - 1e-5).log()).sum(-1)).mean()
+            old_val = (old_pmfs * q_network.atoms).sum(1)
+        else:
+            with torch.no_grad():
+                target_max, _ = target_network(next_observations).max(dim=1)
+                td_target = rewards.flatten() + a.gamma * target_max * (1 - dones.flatten())
+            old_val = q_network(observations).gather(1, actions).squeeze()
+            loss = F.mse_loss(td_target, old_val)
+        self.optimizer.zero_grad()
+        loss.backward()
+        self.optimizer.step()
+        self.step += 1
+        self.last = ("torch", loss.detach(), old_val.detach())
+        return self
+
+    def sync_target(self):
+        """The target update: dqn_atari.py's ``tau`` loop, c51_atari.py's ``load_state_dict``."""
+        if self.fused:
+            if self.c51:
+                self.target.copy_(self.online)
+            else:
+                self.g.polyak_(self.online, self.target, self.args.tau)
+            for trunk in self._trunks.values():
+                trunk.bufs.weights_version += 1
+            return
+        if self.c51:
+            self.target_network.load_state_dict(self.q_network.state_dict())
+            return
+        tau = self.args.tau
+        for target_network_param, q_network_param in zip(self.target_network.parameters(), self.q_network.parameters()):
+            target_network_param.data.copy_(tau * q_network_param.data + (1.0 - tau) * target_network_param.data)
+
+    def metrics(self) -> dict:
+        """The last update's scalars as Python floats: ``loss`` (``losses/td_loss`` or ``losses/loss``) and ``q_values``."""
+        if self.last[0] == "torch":
+            return {"loss": self.last[1].item(), "q_values": self.last[2].mean().item()}
+        sc = self._sc.tolist()
+        return {"loss": sc[0], "q_values": sc[1]}
+
+    def flat_params(self):
+        """(online, target) flat parameters, detached copies (tests)."""
+        return self._flat([self.q_network]), self._flat([self.target_network])

@@ -107,10 +107,14 @@ class DeviceRing:
         self.slots = max(int(args.buffer_size) // self.N, 1)
         self.last = None
         if not self.fused:
-            self.rb = HostReplayBuffer(args.buffer_size, self.O, self.A, self.device, n_envs=self.N, act_dtype=act_dtype)
+            self.rb = self._host_buffer(act_dtype)
             return
         self._check_sizes()                                      # before anything of the ring's size is allocated
         self._alloc_ring(int(args.batch_size))
+
+    def _host_buffer(self, act_dtype):
+        """The ``torch`` backend's buffer (``learner_dqn_atari.AtariDQNLearner`` keeps frames as bytes instead)."""
+        return HostReplayBuffer(self.args.buffer_size, self.O, self.A, self.device, n_envs=self.N, act_dtype=act_dtype)
 
     def _check_sizes(self):
         """The refusal of sizes the fused networks do not take: the continuous families' (``DQNLearner`` has its own limits)."""

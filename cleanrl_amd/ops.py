@@ -29,6 +29,7 @@ __all__ = [
     "clip_radam_", "clip_radam_sched_", "pqn_lstm_act", "pqn_lstm_td_fwd_bwd", "offpolicy_counts", "replay_add", "ddpg_act", "td3_target",
     "td3_critic_fwd_bwd", "td3_actor_fwd_bwd", "polyak_", "sac_actor_count", "sac_policy", "sac_target", "sac_actor_fwd_bwd", "sac_alpha_",
     "dqn_counts", "dqn_limits_ok", "dqn_act", "dqn_td_fwd_bwd", "c51_fwd_bwd",
+    "dqn_head_limits_ok", "replay_add_u8", "replay_gather_u8", "dqn_head_act", "dqn_head_td_fwd_bwd", "c51_head_fwd_bwd",
 ]
 
 LOSS_SCALAR_NAMES = ("loss", "pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac")
@@ -1589,4 +1590,127 @@ def c51_fwd_bwd(ring, batch_inds, env_inds, online, target, atoms, n_actions: in
     _launch("mi355ppo_c51_fwd_bwd_f32", dev, *[_ptr(t) for t in ring], _ptr(batch_inds), _ptr(env_inds), slots, N, _ptr(online), _ptr(target),
             _ptr(atoms), float(gamma), float(v_min), float(v_max), _ptr(grads), _ptr(scalars), _ptr(next_pmfs_out), _ptr(target_pmfs_out), M, O,
             int(n_actions), na, _ptr(ws), ws.numel())
+    return scalars
+
+
+# ------------------------------------------------------------------------------------------- Atari DQN / C51 (csrc/dqn_atari.hip)
+DQN_HEAD_HIDDEN, DQN_HEAD_MAX_OUT, DQN_HEAD_MAX_ROWS, ATARI_FRAME = 512, 1024, 1024, (84, 84, 4)
+
+
+def dqn_head_limits_ok(n_actions: int, n_atoms: int = 1, rows: int = 1) -> bool:
+    """What the fused Q heads take (anything else is ``MI355PPO_EINVAL`` from the C ABI)."""
+    return (2 <= n_actions <= DQN_MAX_ACT and 1 <= n_atoms <= DQN_MAX_ATOMS and n_actions * n_atoms <= DQN_HEAD_MAX_OUT
+            and 1 <= rows <= DQN_HEAD_MAX_ROWS)
+
+
+def _frame_ring(ring):
+    """ring = (frames (slots, n_envs, 84, 84, 4) u8, actions (slots, n_envs) int64, rewards, dones (slots, n_envs) f32) -> (slots, N)."""
+    frames, act, rew, done = ring
+    slots, N = frames.shape[:2]
+    _chk(frames, torch.uint8, "ring frames", (slots, N) + ATARI_FRAME)
+    _chk(act, torch.int64, "ring actions", (slots, N))
+    _chk(rew, torch.float32, "ring rewards", (slots, N))
+    _chk(done, torch.float32, "ring dones", (slots, N))
+    return slots, N
+
+
+def replay_add_u8(ring, pos: int, obs, next_obs, actions, rewards, dones):
+    """The memory-optimised ``ReplayBuffer.add``: ``obs`` / ``next_obs`` (N, 4, 84, 84) u8 channels-last into slot ``pos`` and slot
+    ``(pos + 1) % slots`` of the device frame ring, actions / rewards / dones into slot ``pos`` (one launch)."""
+    slots, N = _frame_ring(ring)
+    H, W, C = ATARI_FRAME
+    _chk(obs, torch.uint8, "obs", (N, C, H, W))
+    _chk(next_obs, torch.uint8, "next_obs", (N, C, H, W))
+    _chk(actions, torch.int64, "actions", (N,))
+    _chk(rewards, torch.float32, "rewards", (N,))
+    _chk(dones, torch.float32, "dones", (N,))
+    _launch("mi355ppo_replay_add_u8", obs.device, _ptr(obs), _ptr(next_obs), _ptr(actions), _ptr(rewards), _ptr(dones), *[_ptr(t) for t in ring],
+            int(pos), slots, N)
+
+
+def replay_gather_u8(ring, batch_inds, env_inds, frames_out, actions_out, rewards_out, dones_out):
+    """A batch out of the frame ring in one launch: frames_out (2M, 84, 84, 4) u8 = the M observation stacks, then the M stacks at
+    ``(batch_inds + 1) % slots``; actions_out (M,) int64, rewards_out / dones_out (M,) f32."""
+    slots, N = _frame_ring(ring)
+    M = _batch_inds(batch_inds, env_inds)
+    _chk(frames_out, torch.uint8, "frames_out", (2 * M,) + ATARI_FRAME)
+    _chk(actions_out, torch.int64, "actions_out", (M,))
+    _chk(rewards_out, torch.float32, "rewards_out", (M,))
+    _chk(dones_out, torch.float32, "dones_out", (M,))
+    _launch("mi355ppo_replay_gather_u8", batch_inds.device, *[_ptr(t) for t in ring], _ptr(batch_inds), _ptr(env_inds), slots, N,
+            _ptr(frames_out), _ptr(actions_out), _ptr(rewards_out), _ptr(dones_out), M)
+    return frames_out
+
+
+def _head(h, w, b, nm=""):
+    M, hidden = h.shape
+    J = b.numel()
+    _chk(h, torch.float32, nm + "h", (M, hidden))
+    _chk(w, torch.float32, nm + "w", (J, hidden))
+    _chk(b, torch.float32, nm + "b", (J,))
+    return M, hidden, J
+
+
+def dqn_head_act(h, w, b, n_actions: int, actions_out, atoms=None, q_out=None):
+    """The greedy action on ``h`` (N, 512): ``Linear(512, n_actions * n_atoms)`` and ``dqn_act``'s argmax -> actions_out (N,) int64."""
+    N, hidden, J = _head(h, w, b)
+    na = 1 if atoms is None else atoms.numel()
+    if J != n_actions * na:
+        raise ValueError(f"w: expected {n_actions * na} output rows, got {J}")
+    if atoms is not None:
+        _chk(atoms, torch.float32, "atoms", (na,))
+    _chk(actions_out, torch.int64, "actions_out", (N,))
+    if q_out is not None:
+        _chk(q_out, torch.float32, "q_out", (N, n_actions))
+    ws = _workspace(h.device, _lib.load().mi355ppo_dqn_head_act_workspace_bytes(N, int(n_actions), na))
+    _launch("mi355ppo_dqn_head_act_f32", h.device, _ptr(h), _ptr(w), _ptr(b), _ptr(atoms), _ptr(actions_out), _ptr(q_out), N, hidden,
+            int(n_actions), na, _ptr(ws), ws.numel())
+    return actions_out
+
+
+def _head_update_args(h, h_next, w, b, w_target, b_target, actions, rewards, dones, dh, dw, db, scalars, n_actions, na, aux):
+    M, hidden, J = _head(h, w, b)
+    if J != n_actions * na:
+        raise ValueError(f"w: expected {n_actions * na} output rows, got {J}")
+    _chk(h_next, torch.float32, "h_next", (M, hidden))
+    _chk(w_target, torch.float32, "w_target", (J, hidden))
+    _chk(b_target, torch.float32, "b_target", (J,))
+    _chk(actions, torch.int64, "actions", (M,))
+    _chk(rewards, torch.float32, "rewards", (M,))
+    _chk(dones, torch.float32, "dones", (M,))
+    _chk(dh, torch.float32, "dh", (M, hidden))
+    _chk(dw, torch.float32, "dw", (J, hidden))
+    _chk(db, torch.float32, "db", (J,))
+    _chk(scalars, torch.float32, "scalars", (2,))
+    for t, nm, shape in aux:
+        if t is not None:
+            _chk(t, torch.float32, nm, shape(M))
+    return M, hidden
+
+
+def dqn_head_td_fwd_bwd(h, h_next, w, b, w_target, b_target, actions, rewards, dones, n_actions: int, gamma: float, dh, dw, db, scalars,
+                        target_q_out=None, td_target_out=None):
+    """dqn_atari.py's update behind the trunks in three launches.  OVERWRITES ``dh`` (M, 512), ``dw`` / ``db`` (the head's gradient,
+    e.g. views of the flat gradient); scalars (2,) = {td_loss, mean old_val}."""
+    M, hidden = _head_update_args(h, h_next, w, b, w_target, b_target, actions, rewards, dones, dh, dw, db, scalars, n_actions, 1,
+                                  ((target_q_out, "target_q_out", lambda M: (M, n_actions)), (td_target_out, "td_target_out", lambda M: (M,))))
+    ws = _workspace(h.device, _lib.load().mi355ppo_dqn_head_workspace_bytes(M, int(n_actions), 1))
+    _launch("mi355ppo_dqn_head_td_fwd_bwd_f32", h.device, _ptr(h), _ptr(h_next), _ptr(w), _ptr(b), _ptr(w_target), _ptr(b_target), _ptr(actions),
+            _ptr(rewards), _ptr(dones), float(gamma), _ptr(dh), _ptr(dw), _ptr(db), _ptr(scalars), _ptr(target_q_out), _ptr(td_target_out), M,
+            hidden, int(n_actions), _ptr(ws), ws.numel())
+    return scalars
+
+
+def c51_head_fwd_bwd(h, h_next, w, b, w_target, b_target, atoms, actions, rewards, dones, n_actions: int, gamma: float, v_min: float,
+                     v_max: float, dh, dw, db, scalars, next_pmfs_out=None, target_pmfs_out=None):
+    """c51_atari.py's update behind the trunks in three launches (target ``get_action``, projection, loss, the head's backward).
+    OVERWRITES ``dh``, ``dw`` / ``db``; scalars (2,) = {loss, mean (old_pmfs * atoms).sum(1)}."""
+    na = atoms.numel()
+    _chk(atoms, torch.float32, "atoms", (na,))
+    M, hidden = _head_update_args(h, h_next, w, b, w_target, b_target, actions, rewards, dones, dh, dw, db, scalars, n_actions, na,
+                                  ((next_pmfs_out, "next_pmfs_out", lambda M: (M, na)), (target_pmfs_out, "target_pmfs_out", lambda M: (M, na))))
+    ws = _workspace(h.device, _lib.load().mi355ppo_dqn_head_workspace_bytes(M, int(n_actions), na))
+    _launch("mi355ppo_c51_head_fwd_bwd_f32", h.device, _ptr(h), _ptr(h_next), _ptr(w), _ptr(b), _ptr(w_target), _ptr(b_target), _ptr(atoms),
+            _ptr(actions), _ptr(rewards), _ptr(dones), float(gamma), float(v_min), float(v_max), _ptr(dh), _ptr(dw), _ptr(db), _ptr(scalars),
+            _ptr(next_pmfs_out), _ptr(target_pmfs_out), M, hidden, int(n_actions), na, _ptr(ws), ws.numel())
     return scalars

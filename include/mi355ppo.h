@@ -1110,6 +1110,72 @@ MI355PPO_API int mi355ppo_c51_fwd_bwd_f32_cpu(const float* ring_obs, const float
                                               float* scalars_out, float* next_pmfs_out, float* target_pmfs_out, int M, int O, int n_actions,
                                               int n_atoms);
 
+/* ---- Atari DQN / C51 (added under ABI 2.7.1, csrc/dqn_atari.hip; reference: cleanrl/dqn_atari.py, cleanrl/c51_atari.py and
+ * ReplayBuffer(optimize_memory_usage=True) of cleanrl_utils/buffers.py) ----
+ * The frame ring is ONE u8 array (slots, n_envs, 84, 84, 4), channels-last and 4-byte aligned, beside ring_actions (slots, n_envs) int64,
+ * ring_rewards and ring_dones (slots, n_envs) f32.  Every offset into it is 64-bit.  The head is Linear(512, n_actions * n_atoms) on the
+ * post-ReLU output h of Linear(3136, 512): w (n_actions * n_atoms, 512) and b as torch keeps them; n_atoms = 1 is dqn_atari.py's head.
+ * hidden == 512, 2 <= n_actions <= 18, 1 <= n_atoms <= 101, n_actions * n_atoms <= 1024, 1 <= rows <= 1024 (the C51 update needs
+ * n_atoms >= 2); anything else is MI355PPO_EINVAL before any launch.  td_target, the projection, exp / log and every accumulation order
+ * are those of the DQN / C51 section above.  No entry point allocates or synchronises, none uses atomics, all can be captured; every
+ * *_cpu twin returns the device's bits (csrc/dqn_atari_rows.h).
+ *
+ * replay_add: the memory-optimised add.  obs / next_obs (n_envs, 4, 84, 84) u8 as the env gives them -> slot pos and slot
+ * (pos + 1) % slots, one 4-byte store per pixel; with slots == 1 next_obs alone is written (it is what the reference leaves).  actions
+ * (n_envs) int64, rewards, dones (n_envs) f32 -> slot pos.  One launch. */
+MI355PPO_API int mi355ppo_replay_add_u8(const uint8_t* obs, const uint8_t* next_obs, const int64_t* actions, const float* rewards,
+                                        const float* dones, uint8_t* ring_frames, int64_t* ring_actions, float* ring_rewards,
+                                        float* ring_dones, int64_t pos, int64_t slots, int n_envs, void* stream);
+MI355PPO_API int mi355ppo_replay_add_u8_cpu(const uint8_t* obs, const uint8_t* next_obs, const int64_t* actions, const float* rewards,
+                                            const float* dones, uint8_t* ring_frames, int64_t* ring_actions, float* ring_rewards,
+                                            float* ring_dones, int64_t pos, int64_t slots, int n_envs);
+/* replay_gather: frames_out (2M, 84, 84, 4) u8, 4-byte aligned: rows m < M the frames (batch_inds[m], env_inds[m]), rows M + m the frames
+ * ((batch_inds[m] + 1) % slots, env_inds[m]); actions_out (M) int64, rewards_out, dones_out (M) f32.  Indices are clamped into the
+ * ring.  One launch. */
+MI355PPO_API int mi355ppo_replay_gather_u8(const uint8_t* ring_frames, const int64_t* ring_actions, const float* ring_rewards,
+                                           const float* ring_dones, const int64_t* batch_inds, const int64_t* env_inds, int64_t slots,
+                                           int n_envs, uint8_t* frames_out, int64_t* actions_out, float* rewards_out, float* dones_out, int M,
+                                           void* stream);
+MI355PPO_API int mi355ppo_replay_gather_u8_cpu(const uint8_t* ring_frames, const int64_t* ring_actions, const float* ring_rewards,
+                                               const float* ring_dones, const int64_t* batch_inds, const int64_t* env_inds, int64_t slots,
+                                               int n_envs, uint8_t* frames_out, int64_t* actions_out, float* rewards_out, float* dones_out,
+                                               int M);
+/* head_act: actions_out (N, int64) = argmax_a q(h)[a] with mi355ppo_dqn_act_f32's semantics (a tie to the lowest index, a NaN is the
+ * maximum, n_atoms > 1: C51's get_action in ascending atom order); q_out (N, n_actions) may be NULL.  Two launches (the product spread
+ * over rows x output tiles, then the argmax). */
+MI355PPO_API size_t mi355ppo_dqn_head_act_workspace_bytes(int N, int n_actions, int n_atoms);
+MI355PPO_API int mi355ppo_dqn_head_act_f32(const float* h, const float* w, const float* b, const float* atoms, int64_t* actions_out,
+                                           float* q_out, int N, int hidden, int n_actions, int n_atoms, void* workspace,
+                                           size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_dqn_head_act_f32_cpu(const float* h, const float* w, const float* b, const float* atoms, int64_t* actions_out,
+                                               float* q_out, int N, int hidden, int n_actions, int n_atoms);
+/* The updates given h = online trunk(obs) and h_next = target trunk(next_obs), both (M, 512) post-ReLU, and the gathered actions (int64,
+ * clamped into [0, n_actions)), rewards and dones.  dh (M, 512) is d loss / d h; dw (n_actions * n_atoms, 512) and db are OVERWRITTEN:
+ * the taken actions' rows summed over the batch rows in ascending order, every other row zero.  scalars_out (2) = {loss, mean q}.
+ * The optional outputs are the target side's: target_q_out (M, n_actions) and td_target_out (M), or next_pmfs_out and
+ * target_pmfs_out (M, n_atoms).  Three launches; mi355ppo_dqn_head_workspace_bytes serves both (n_atoms = 1 for the TD update). */
+MI355PPO_API size_t mi355ppo_dqn_head_workspace_bytes(int M, int n_actions, int n_atoms);
+MI355PPO_API int mi355ppo_dqn_head_td_fwd_bwd_f32(const float* h, const float* h_next, const float* w, const float* b, const float* w_target,
+                                                  const float* b_target, const int64_t* actions, const float* rewards, const float* dones,
+                                                  double gamma, float* dh, float* dw, float* db, float* scalars_out, float* target_q_out,
+                                                  float* td_target_out, int M, int hidden, int n_actions, void* workspace,
+                                                  size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_dqn_head_td_fwd_bwd_f32_cpu(const float* h, const float* h_next, const float* w, const float* b,
+                                                      const float* w_target, const float* b_target, const int64_t* actions,
+                                                      const float* rewards, const float* dones, double gamma, float* dh, float* dw, float* db,
+                                                      float* scalars_out, float* target_q_out, float* td_target_out, int M, int hidden,
+                                                      int n_actions);
+MI355PPO_API int mi355ppo_c51_head_fwd_bwd_f32(const float* h, const float* h_next, const float* w, const float* b, const float* w_target,
+                                               const float* b_target, const float* atoms, const int64_t* actions, const float* rewards,
+                                               const float* dones, double gamma, double v_min, double v_max, float* dh, float* dw, float* db,
+                                               float* scalars_out, float* next_pmfs_out, float* target_pmfs_out, int M, int hidden,
+                                               int n_actions, int n_atoms, void* workspace, size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_c51_head_fwd_bwd_f32_cpu(const float* h, const float* h_next, const float* w, const float* b, const float* w_target,
+                                                   const float* b_target, const float* atoms, const int64_t* actions, const float* rewards,
+                                                   const float* dones, double gamma, double v_min, double v_max, float* dh, float* dw,
+                                                   float* db, float* scalars_out, float* next_pmfs_out, float* target_pmfs_out, int M,
+                                                   int hidden, int n_actions, int n_atoms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 """ddpg_continuous_action.py / td3_continuous_action.py / sac_continuous_action.py with both ``MI355PPO_OFFPOLICY`` backends, in one
 process, alternating.
 
-    python tools/offpolicybench.py [--reps 20] [--scripts td3 ddpg sac dqn]
+    python tools/offpolicybench.py [--reps 20] [--scripts td3 ddpg sac dqn dqn_atari]
 
 Times, at each script's defaults (batch 256) on a HalfCheetah-shaped (obs 17 / act 6) and a Humanoid-shaped (376 / 17) task:
 one rollout step including the action's copy to the host, one critic-only training step and one step with the delayed policy
@@ -75,6 +75,45 @@ def bench_dqn(a, dev):
         print(json.dumps(row), flush=True)
 
 
+ATARI_SHAPES = {"4-action": 4, "18-action": 18}
+
+
+def make_dqn_atari(c51, n, backend, dev, fill=256):
+    from cleanrl_amd.agents import AtariC51Network, AtariDQNNetwork
+    from cleanrl_amd.learner_dqn_atari import AtariDQNLearner
+
+    torch.manual_seed(1)
+    np.random.seed(1)
+    envs = E.AtariReplayVecEnv(1, seed=1, n_actions=n)
+    mk = (lambda: AtariC51Network(envs).to(dev)) if c51 else (lambda: AtariDQNNetwork(envs).to(dev))
+    q, t = mk(), mk()
+    t.load_state_dict(q.state_dict())
+    args = SimpleNamespace(buffer_size=fill * 2, batch_size=32, learning_rate=1e-4, gamma=0.99, tau=1.0, n_atoms=51, v_min=-10, v_max=10)
+    return fill_ring(AtariDQNLearner(q, t, args, envs, dev, c51=c51, backend=backend), envs, fill)
+
+
+def bench_dqn_atari(a, dev):
+    """dqn_atari.py / c51_atari.py at batch 32: one greedy rollout step, one DQN update, one C51 update (51 atoms)."""
+    for shape, n in ATARI_SHAPES.items():
+        learners = {(alg, b): make_dqn_atari(alg == "c51", n, b, dev) for alg in ("dqn", "c51") for b in ("torch", "fused")}
+        legs = {"rollout_step": ("dqn", lambda L, obs: L.act(obs, 1, 0.0)), "dqn_update": ("dqn", lambda L, obs: L.train_step()),
+                "c51_update": ("c51", lambda L, obs: L.train_step())}
+        times = {leg: {b: [] for b in ("torch", "fused")} for leg in legs}
+        for rep in range(a.warmup + a.reps):
+            for leg, (alg, fn) in legs.items():
+                for b in ("torch", "fused"):                             # alternating: both backends see the same box state
+                    L, obs = learners[(alg, b)]
+                    us = timed(lambda: fn(L, obs), dev)
+                    if rep >= a.warmup:
+                        times[leg][b].append(us)
+        row = {"script": "dqn_atari", "shape": shape, "n_actions": n, "n_atoms": 51, "batch": 32, "device": str(dev), "reps": a.reps}
+        for leg in legs:
+            for b in ("torch", "fused"):
+                row[f"{leg}_{b}_us"] = round(statistics.median(times[leg][b]), 1)
+            row[f"{leg}_speedup"] = round(row[f"{leg}_torch_us"] / row[f"{leg}_fused_us"], 2)
+        print(json.dumps(row), flush=True)
+
+
 def make(script, O, A, backend, dev, fill=4096):
     td3 = script == "td3"
     torch.manual_seed(1)
@@ -126,6 +165,9 @@ def main():
     for script in a.scripts:
         if script == "dqn":
             bench_dqn(a, dev)
+            continue
+        if script == "dqn_atari":
+            bench_dqn_atari(a, dev)
             continue
         for shape, (O, A) in SHAPES.items():
             learners = {b: make(script, O, A, b, dev) for b in ("torch", "fused")}
