@@ -263,9 +263,9 @@ extern "C" MI355PPO_API int mi355ppo_normal_logprob_entropy_bwd_f32_cpu(const fl
 namespace {
 
 int loss_params(const char* fn, int M, double clip_coef, double ent_coef, double vf_coef, int norm_adv, int clip_vloss,
-                LossParams* P) {
+                const float* adv_mean_den, LossParams* P) {
     MI355_REQUIRE(M > 0, MI355PPO_EINVAL, "%s: M=%d must be positive", fn, M);
-    MI355_REQUIRE(!norm_adv || M > 1, MI355PPO_EINVAL, "%s: norm_adv needs M > 1 (unbiased std)", fn);
+    MI355_REQUIRE(!norm_adv || adv_mean_den || M > 1, MI355PPO_EINVAL, "%s: norm_adv needs M > 1 (unbiased std)", fn);
     P->lo = (float)(1.0 - clip_coef);
     P->hi = (float)(1.0 + clip_coef);
     P->clip = (float)clip_coef;
@@ -319,7 +319,7 @@ extern "C" MI355PPO_API int mi355ppo_loss_categorical_fwd_bwd_f32_cpu(
                   MI355PPO_EINVAL, "%s: null pointer", fn);
     MI355_REQUIRE(A > 0 && A <= kAMax, MI355PPO_EINVAL, "%s: A=%d must be in 1..64", fn, A);
     LossParams P;
-    if (int rc = loss_params(fn, M, clip_coef, ent_coef, vf_coef, norm_adv, clip_vloss, &P)) return rc;
+    if (int rc = loss_params(fn, M, clip_coef, ent_coef, vf_coef, norm_adv, clip_vloss, adv_mean_den, &P)) return rc;
     float mean = 0.0f, den = 1.0f;
     if (norm_adv) adv_mean_den_host(b_advantages, mb_inds, M, adv_mean_den, &mean, &den);
     double tot[kNumSums] = {0, 0, 0, 0, 0, 0};
@@ -357,7 +357,7 @@ extern "C" MI355PPO_API int mi355ppo_loss_normal_fwd_bwd_f32_cpu(
                   MI355PPO_EINVAL, "%s: null pointer", fn);
     MI355_REQUIRE(D > 0 && D <= 64, MI355PPO_EINVAL, "%s: D=%d must be in 1..64", fn, D);
     LossParams P;
-    if (int rc = loss_params(fn, M, clip_coef, ent_coef, vf_coef, norm_adv, clip_vloss, &P)) return rc;
+    if (int rc = loss_params(fn, M, clip_coef, ent_coef, vf_coef, norm_adv, clip_vloss, adv_mean_den, &P)) return rc;
     float amean = 0.0f, den = 1.0f;
     if (norm_adv) adv_mean_den_host(b_advantages, mb_inds, M, adv_mean_den, &amean, &den);
     double tot[kNumSums] = {0, 0, 0, 0, 0, 0};

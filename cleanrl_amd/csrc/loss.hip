@@ -574,6 +574,7 @@ extern "C" MI355PPO_API int mi355ppo_loss_categorical_fwd_bwd_f32(const float* n
                           scalars7, dlogits, dvalue, workspace, workspace_bytes, 0);
     if (rc) return rc;
     MI355_REQUIRE(A > 0 && A <= 64, MI355PPO_EINVAL, "%s: A=%d must be in 1..64", fn, A);
+    MI355_REQUIRE(!norm_adv || adv_mean_den || M > 1, MI355PPO_EINVAL, "%s: norm_adv needs M > 1 (unbiased std)", fn);
     MI355_REQUIRE(aligned(mb_inds, 8) && aligned(adv_mean_den, 4), MI355PPO_EALIGN, "%s: misaligned pointer", fn);
     hipStream_t s = as_stream(stream);
     const LossParams P = make_params(M, clip_coef, ent_coef, vf_coef, norm_adv, clip_vloss, adv_mean_den != nullptr);
@@ -614,6 +615,7 @@ extern "C" MI355PPO_API int mi355ppo_loss_categorical_packed_fwd_bwd_f32(const f
                           workspace_bytes, 0);
     if (rc) return rc;
     MI355_REQUIRE(A > 0 && A <= 64, MI355PPO_EINVAL, "%s: A=%d must be in 1..64", fn, A);
+    MI355_REQUIRE(!norm_adv || adv_mean_den || M > 1, MI355PPO_EINVAL, "%s: norm_adv needs M > 1 (unbiased std)", fn);
     MI355_REQUIRE(aligned(pack, 32) && aligned(mb_inds, 8) && aligned(adv_mean_den, 4), MI355PPO_EALIGN,
                   "%s: misaligned pointer (pack rows are 32-byte aligned)", fn);
     MI355_REQUIRE(!norm_adv || adv_mean_den, MI355PPO_EINVAL,
@@ -654,6 +656,7 @@ extern "C" MI355PPO_API int mi355ppo_loss_normal_fwd_bwd_f32(const float* new_me
     int rc = check_common(fn, new_mean, new_value, b_actions, b_logprobs, b_advantages, b_returns, b_values, M, scalars7,
                           dmean, dvalue, workspace, workspace_bytes, D);
     if (rc) return rc;
+    MI355_REQUIRE(!norm_adv || adv_mean_den || M > 1, MI355PPO_EINVAL, "%s: norm_adv needs M > 1 (unbiased std)", fn);
     MI355_REQUIRE(aligned(mb_inds, 8) && aligned(logstd, 4) && aligned(dlogstd, 4) && aligned(adv_mean_den, 4), MI355PPO_EALIGN,
                   "%s: misaligned pointer", fn);
     hipStream_t s = as_stream(stream);

@@ -294,7 +294,9 @@ class LossSlots:
 def adv_stats(b_advantages, inds, minibatch_size: int, out=None):
     """``(mean, unbiased std + 1e-8)`` of ``b_advantages[inds[j*M:(j+1)*M]]`` for every minibatch j of one epoch's permutation,
     in one launch (ppo_atari_multigpu.py:337-338).  Returns a ``(ceil(len/M), 2)`` f32 tensor whose rows are the
-    ``adv_mean_den`` argument of the loss entry points."""
+    ``adv_mean_den`` argument of the loss entry points.  A minibatch of one row (``minibatch_size == 1`` or a ragged last one)
+    gets ``(that advantage, NaN)``, as ``torch.std`` of one element is NaN; the loss calls refuse ``norm_adv`` on a one-row
+    minibatch unless they are handed ``adv_mean_den``."""
     lib = _lib.load()
     flat = _chk(b_advantages.reshape(-1), torch.float32, "b_advantages")
     total = flat.numel() if inds is None else inds.numel()
@@ -357,7 +359,7 @@ def ppo_loss_categorical_packed(new_logits, new_value, mb_inds, pack, clip_coef:
     _chk(pack, torch.float32, "pack")
     if pack.dim() != 2 or pack.shape[1] != PACK_FLOATS:
         raise ValueError(f"pack: expected (B, {PACK_FLOATS}), got {tuple(pack.shape)}")
-    if norm_adv and adv_mean_den is None:
+    if norm_adv and adv_mean_den is None and M > 1:          # (M == 1 has no unbiased std: the library refuses the call below)
         adv_mean_den = adv_stats_packed(pack, mb_inds, M)[0] if mb_inds is not None else adv_stats_packed(pack[:M], None, M)[0]
     if adv_mean_den is not None:
         _chk(adv_mean_den, torch.float32, "adv_mean_den", (2,))

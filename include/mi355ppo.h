@@ -181,6 +181,9 @@ MI355PPO_API int mi355ppo_normal_logprob_entropy_bwd_f32(const float* mean, cons
  *                  mi355ppo_adv_stats_f32 (then no statistics launch happens here)        [in]
  * Reductions are computed in a fixed order (deterministic); advantage mean / unbiased std are
  * accumulated in f64.  Tolerances vs the reference are stated in tests/test_gpu_kernels.py.
+ * One row has no unbiased std: norm_adv with M == 1 and adv_mean_den == NULL is refused (MI355PPO_EINVAL, nothing
+ * launched) by every loss entry point, the packed and the continuous-action ones and the *_cpu twins included; with a
+ * caller-supplied adv_mean_den the call is valid.
  * Launches per call: statistics (only if norm_adv and adv_mean_den == NULL), row pass, scalar fold
  * (only if scalars7 != NULL).  scalars7 == NULL defers the fold: the call's partial sums stay in
  * its workspace, which then must be a slot no other call overwrites until
@@ -208,7 +211,10 @@ MI355PPO_API int mi355ppo_loss_scalars_f32(const void* workspaces, size_t slot_s
  * epoch's permutation and the GAE output, not on anything the network produces, so the learner
  * computes them when it uploads the permutation and K3 runs without its statistics launch.
  *   inds (total) int64 or NULL (= identity); minibatch j = rows [j*M, min((j+1)*M, total));
- *   mean_den : (ceil(total / M), 2) f32                                                  [out] */
+ *   mean_den : (ceil(total / M), 2) f32                                                  [out]
+ * A minibatch of ONE row (M == 1, or a ragged last minibatch of one row) gets (that row's advantage, NaN): the unbiased
+ * variance is 0 / 0, as torch's `std()` of one element is NaN.  The statistics calls do not refuse it (the other rows
+ * of the table are valid); a loss call that is handed such a row normalises with NaN. */
 MI355PPO_API size_t mi355ppo_adv_stats_workspace_bytes(int64_t total, int M);
 MI355PPO_API int mi355ppo_adv_stats_f32(const float* b_advantages, const int64_t* inds, int64_t total, int M,
                                         float* mean_den, void* workspace, size_t workspace_bytes, void* stream);

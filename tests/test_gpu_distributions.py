@@ -1,5 +1,5 @@
-"""The distribution kernels (K2 / K2': Categorical and Normal log-prob / entropy, forward and backward) and the Normal K3 loss
-against float64 autograd of the reference's lines, at the C ABI and through the ``ops`` wrappers and the agents.
+"""The distribution kernels (K2 / K2': Categorical and Normal log-prob / entropy, forward and backward), the Normal and the
+Categorical K3 loss and the advantage statistics against float64 autograd of the reference's lines, at the C ABI and through the ``ops`` wrappers and the agents.
 
 One reference everywhere: the f32 inputs cast up to float64 and run through oracle/torch_oracle.py (pinned to the reference-line
 goldens by tests/test_oracle_golden.py), on the device so the large sizes stay fast.  Cases and bars live in tests/dist_cases.py,
@@ -267,7 +267,8 @@ def _loss_cases():
                 continue                                 # bounds memory and time
             for norm_adv, clip_vloss in FLAGS:
                 if norm_adv and M == 1:
-                    continue                             # one row has no unbiased std (the library refuses it, as torch gives NaN)
+                    continue                             # one row has no unbiased std (the library refuses it, as torch gives NaN:
+                    #                                      test_losses_refuse_norm_adv_on_one_row)
                 yield M, D, norm_adv, clip_vloss
 
 
@@ -365,3 +366,235 @@ def test_loss_normal_autograd_function_matches_float64_autograd_under_a_network(
                             (logstd.grad, ls64.grad, "logstd")):
         w = want.cpu().numpy()
         np.testing.assert_allclose(got.double().cpu().numpy(), w, rtol=1e-4, atol=1e-5 * np.abs(w).max(), err_msg=name)
+
+
+# ============================================================================== K3  Categorical loss
+def _cat_loss_args(c):
+    return tuple(c[k] for k in C.LOSS_CAT_KEYS)
+
+
+def _cat_loss_small():
+    for regime in C.REGIMES:
+        for A in C.LOSS_CAT_A:
+            if regime == "masked" and A == 1:
+                continue                                 # no distribution (see _cat_small)
+            yield regime, A
+
+
+@pytest.mark.parametrize("regime,A", list(_cat_loss_small()))
+def test_loss_categorical_float64(regime, A):
+    """Every logit regime x both sides of every A bucket of the dispatch (4 / 8 / 18 / 64) x M in {1, 2, 255, 257, 1025} (one
+    lane, one workgroup +- 1, the statistics' second partial) x the four flag pairs x ent_coef in {0, 0.01}."""
+    for M in (1, 2, 255, 257, 1025):
+        c = C.loss_categorical_case(M, A, regime, seed=1, device=DEV)
+        for norm_adv, clip_vloss in FLAGS:
+            if norm_adv and M == 1:
+                continue                                 # refused: test_losses_refuse_norm_adv_on_one_row
+            for ent_coef in (0.0, 0.01):
+                ref = C.loss_categorical_ref(c, ent_coef, norm_adv, clip_vloss)
+                out = ops.ppo_loss_categorical(*_cat_loss_args(c), C.CLIP, ent_coef, C.VF, norm_adv, clip_vloss)
+                C.check_loss_categorical(*out, ref, f"{regime} A={A} M={M} flags=({norm_adv}, {clip_vloss}) ent={ent_coef}")
+
+
+@pytest.mark.parametrize("A", [4, 18])
+@pytest.mark.parametrize("regime", ["randn", "masked"])
+@pytest.mark.parametrize("M", [524288, 524289, 1048577, 1200007])
+def test_loss_categorical_float64_large(M, regime, A):
+    """Across the second sweep of the persistent pass (2,048 x 256 rows) and the 1,024-partial cap of the statistics."""
+    c = C.loss_categorical_case(M, A, regime, seed=2, device=DEV)
+    ref = C.loss_categorical_ref(c, 0.01, True, True)
+    out = ops.ppo_loss_categorical(*_cat_loss_args(c), C.CLIP, 0.01, C.VF, True, True)
+    C.check_loss_categorical(*out, ref, f"{regime} A={A} M={M}")
+
+
+@pytest.mark.parametrize("regime", ["masked", "randn_x40"])
+@pytest.mark.parametrize("M,A", [(257, 4), (1025, 4), (1025, 9), (300, 19)])
+def test_loss_categorical_every_route_meets_the_float64_bar(M, A, regime):
+    """The five-array call, the packed call (batch_pack + adv_stats_packed), a caller-supplied adv_mean_den, the deferred fold
+    through LossSlots at a non-zero slot and, at A = 4, logits and dlogits on views at storage offset 1 (4-byte aligned: the
+    scalar route instead of the float4 one): each meets the float64 bar, and all give the same bits."""
+    c = C.loss_categorical_case(M, A, regime, seed=3, device=DEV)
+    ref = C.loss_categorical_ref(c, 0.01, True, True)
+    args, kw = _cat_loss_args(c), dict(clip_coef=C.CLIP, ent_coef=0.01, vf_coef=C.VF, norm_adv=True, clip_vloss=True)
+    base = ops.ppo_loss_categorical(*args, **kw)
+    routes = {"five arrays": base}
+    pack = ops.batch_pack(*args[3:])
+    md = ops.adv_stats(c["b_advantages"], c["mb_inds"], M)
+    mdp = ops.adv_stats_packed(pack, c["mb_inds"], M)
+    assert torch.equal(md, mdp)
+    routes["packed"] = ops.ppo_loss_categorical_packed(*args[:3], pack, adv_mean_den=mdp[0], **kw)
+    routes["packed, own statistics"] = ops.ppo_loss_categorical_packed(*args[:3], pack, **kw)
+    routes["adv_mean_den"] = ops.ppo_loss_categorical(*args, adv_mean_den=md[0], **kw)
+    slots = ops.LossSlots(3, torch.device(DEV))
+    none, dl_s, dv_s = ops.ppo_loss_categorical(*args, slot=(slots, 2), **kw)
+    table = torch.zeros(3, 7, device=DEV)
+    slots.fold(1, table, first=2)
+    assert none is None and not table[:2].any()
+    routes["deferred fold"] = (table[2], dl_s, dv_s)
+    if A == 4:
+        buf, obuf = torch.empty(M * A + 1, device=DEV), torch.empty(M * A + 1, device=DEV)
+        buf[1:] = c["new_logits"].reshape(-1)
+        view, oview = buf[1:].view(M, A), obuf[1:].view(M, A)
+        assert view.is_contiguous() and view.data_ptr() % 16 == 4 and c["new_logits"].data_ptr() % 16 == 0
+        routes["misaligned"] = ops.ppo_loss_categorical(view, *args[1:], dlogits_out=oview, **kw)
+    for name, out in routes.items():
+        C.check_loss_categorical(*out, ref, f"{regime} A={A} M={M} {name}")
+        assert all(torch.equal(a, b) for a, b in zip(out, base)), name
+
+
+def _device_loss(clip, norm_adv, clip_vloss):
+    def run(c, ent_coef=0.0):
+        return ops.ppo_loss_categorical(*_cat_loss_args(c), clip, ent_coef, C.VF, norm_adv, clip_vloss)
+    return run
+
+
+@pytest.mark.parametrize("clip_vloss", [True, False])
+def test_loss_categorical_exact_convention_rows(clip_vloss):
+    """dist_cases.EXACT_ROWS: dv == +-clip (torch.clamp passes gradient on the closed interval), u == c inside and outside the
+    clip (torch.max splits a tie 1/2 + 1/2), a zero gradient, an advantage of exactly 0.  Every value-loss quantity is dyadic:
+    dvalue and v_loss are bit-equal to float64 autograd rounded to f32."""
+    C.check_exact_rows(_device_loss(C.EXACT_CLIP, False, clip_vloss), DEV, clip_vloss)
+
+
+def test_loss_categorical_policy_tie_rows_device_equals_twin():
+    """The policy-side tie pg1 == pg2 cannot be placed exactly against float64 on a general row: the f32 and the float64
+    log-probability differ, so one of the two runs is off the tie.  It is pinned on the rows of dist_cases.loss_tie_case, whose
+    exp / log are exact in every arithmetic, with clip_coef = 0 and b_logprobs = the kernel's own categorical_logprob_entropy
+    output: the device and the twin give the same bits, which are the bits of float64 autograd."""
+    from cleanrl_amd import host_ops as H
+    dev = C.check_tie_rows(_device_loss(0.0, False, True), ops.categorical_logprob_entropy, DEV)
+
+    def twin(c):
+        lg, vl = c["new_logits"].clone().requires_grad_(True), c["new_value"].clone().requires_grad_(True)
+        loss, sc = H.ppo_loss_categorical(lg, vl, *(c[k] for k in C.LOSS_CAT_KEYS[2:]), 0.0, 0.0, C.VF, False, True)
+        loss.backward()
+        return sc, lg.grad, vl.grad
+    host = C.check_tie_rows(twin, H.categorical_logprob_entropy, "cpu")
+    assert all(torch.equal(a, b) for a, b in zip(dev, host))
+
+
+def test_loss_categorical_autograd_function_matches_float64_autograd_under_a_network():
+    """PPOLossCategorical under a tiny network == the reference's discrete loss lines differentiated by float64 autograd."""
+    torch.manual_seed(0)
+    M, A, Bf, O = 512, 6, 2048, 16
+    net = torch.nn.Linear(O, A + 1).to(DEV)
+    x = torch.randn(M, O, device=DEV)
+    inds = torch.randperm(Bf, device=DEV)[:M]
+    b_actions = torch.randint(0, A, (Bf,), device=DEV).float()
+    b_logprobs = -np.log(A) + 0.3 * torch.randn(Bf, device=DEV)
+    b_adv = torch.randn(Bf, device=DEV)
+    b_val = torch.randn(Bf, device=DEV)
+    b_ret = b_val + b_adv
+    out = net(x)
+    loss, _ = ops.PPOLossCategorical.apply(out[:, :A].contiguous(), out[:, A].contiguous(), inds, b_actions, b_logprobs, b_adv,
+                                           b_ret, b_val, 0.2, 0.01, 0.5, True, True)
+    loss.backward()
+    net64 = copy.deepcopy(net).double()
+    net64.zero_grad(set_to_none=True)
+    o = net64(x.double())
+    lp, ent = TO.categorical_logprob_entropy(o[:, :A], b_actions.long()[inds])
+    ref = TO.ppo_loss(lp, ent, o[:, A], b_logprobs.double()[inds], b_adv.double()[inds], b_ret.double()[inds], b_val.double()[inds],
+                      0.2, 0.01, 0.5, True, True)
+    ref["loss"].backward()
+    np.testing.assert_allclose(loss.item(), ref["loss"].item(), rtol=1e-5)
+    for got, want, name in ((net.weight.grad, net64.weight.grad, "weight"), (net.bias.grad, net64.bias.grad, "bias")):
+        w = want.cpu().numpy()
+        np.testing.assert_allclose(got.double().cpu().numpy(), w, rtol=1e-4, atol=1e-5 * np.abs(w).max(), err_msg=name)
+
+
+def test_losses_refuse_norm_adv_on_one_row():
+    """One row has no unbiased std (torch gives NaN): norm_adv with M == 1 and no caller-supplied adv_mean_den is refused with
+    MI355PPO_EINVAL before anything is launched, by the five-array, the packed and the Normal entry points and by their ops
+    wrappers, as by the twins; with adv_mean_den the call is valid."""
+    lib = _lib.load()
+    c = C.loss_categorical_case(1, 4, "randn", seed=2, device=DEV)
+    args = _cat_loss_args(c)
+    f = lambda *s: torch.full(s, 7.0, device=DEV)       # noqa: E731
+    sc, dl, dv, dm, dls = f(7), f(1, 4), f(1), f(1, 4), f(4)
+    ws = torch.zeros(lib.mi355ppo_loss_workspace_bytes(1, 4), dtype=torch.uint8, device=DEV)
+    pack = ops.batch_pack(*args[3:])
+    hp = (C.CLIP, 0.01, C.VF, 1, 1)
+    tail = (_p(ws), ws.numel(), _stream())
+    md = torch.tensor([0.25, 2.0], device=DEV)
+
+    def five(given):
+        return lib.mi355ppo_loss_categorical_fwd_bwd_f32(*(_p(t) for t in args), 1, 4, *hp, _p(given), _p(sc), _p(dl), _p(dv), *tail)
+
+    def packed(given):
+        return lib.mi355ppo_loss_categorical_packed_fwd_bwd_f32(*(_p(t) for t in args[:3]), _p(pack), 1, 4, *hp, _p(given), _p(sc),
+                                                                _p(dl), _p(dv), *tail)
+    cn = C.loss_normal_case(1, 4, seed=5, device=DEV)
+    nargs = _loss_args(cn)
+
+    def normal(given):
+        return lib.mi355ppo_loss_normal_fwd_bwd_f32(*(_p(t) for t in nargs), 1, 4, *hp, _p(given), _p(sc), _p(dm), _p(dls), _p(dv),
+                                                    *tail)
+    for call in (five, packed, normal):
+        assert call(None) == EINVAL
+        assert b"norm_adv needs M > 1" in lib.mi355ppo_last_error()
+    torch.cuda.synchronize()
+    for t in (sc, dl, dv, dm, dls):
+        assert (t == 7.0).all()                                     # refused before any launch
+    kw = dict(clip_coef=C.CLIP, ent_coef=0.01, vf_coef=C.VF, norm_adv=True, clip_vloss=True)
+    with pytest.raises(_lib.Mi355PpoError, match="norm_adv needs M > 1"):
+        ops.ppo_loss_categorical(*args, **kw)
+    with pytest.raises(_lib.Mi355PpoError, match="norm_adv needs M > 1"):
+        ops.ppo_loss_categorical_packed(*args[:3], pack, **kw)
+    with pytest.raises(_lib.Mi355PpoError, match="norm_adv needs M > 1"):
+        ops.ppo_loss_normal(*nargs, **kw)
+    # with the statistics supplied the one-row call is valid: == the un-normalised loss of the advantage (a - 0.25) / 2
+    c2 = dict(c, b_advantages=(c["b_advantages"] - 0.25) / 2.0)
+    ref = C.loss_categorical_ref(c2, 0.01, False, True)
+    assert five(md) == 0
+    C.check_loss_categorical(sc, dl, dv, ref, "five arrays, given statistics")
+    out = ops.ppo_loss_categorical_packed(*args[:3], pack, adv_mean_den=md, **kw)
+    C.check_loss_categorical(*out, ref, "packed, given statistics")
+    cn2 = dict(cn, b_advantages=(cn["b_advantages"] - 0.25) / 2.0)
+    assert normal(md) == 0
+    C.check_loss_normal(sc, dm, dls, dv, C.loss_normal_ref(cn2, 0.01, False, True), 1, 4, "Normal, given statistics")
+
+
+# ============================================================================== advantage statistics
+@pytest.mark.parametrize("kind", C.ADV_KINDS)
+@pytest.mark.parametrize("total,M", C.ADV_SEGMENTS + [(64, 2)])
+def test_adv_stats_float64(total, M, kind):
+    """Every minibatch of an epoch in one call: more than one segment, a ragged last one (of two rows, and of ONE row at
+    (2049, 1024): NaN, as torch), more than one partial per segment above M = 1,024 and their cap of 1,024; well conditioned,
+    a large mean with a small spread (the one-pass variance) and a constant (the variance is exactly 0); with a permutation
+    and with identity indices; packed and unpacked routes give the same bits."""
+    adv = C.adv_values(total, kind, seed=1, device=DEV)
+    perm = torch.randperm(adv.numel(), device=DEV)[:total]
+    zeros = torch.zeros_like(adv)
+    pack = ops.batch_pack(zeros, zeros, adv, zeros, zeros)
+    for inds, flat, rows in ((perm, adv, pack), (None, adv[:total].contiguous(), pack[:total])):
+        got = ops.adv_stats(flat, inds, M)
+        C.check_adv_stats(got, flat, inds, M, f"total={total} M={M} {kind} {'perm' if inds is not None else 'identity'}")
+        packed = ops.adv_stats_packed(rows, inds, M)
+        assert torch.equal(torch.isnan(packed), torch.isnan(got)) and torch.equal(packed.nan_to_num(), got.nan_to_num())
+
+
+def test_adv_stats_constant_segments_clamp_a_negative_variance_residue():
+    """Constant advantages that are not dyadic: s = n a and mu = a are exact, but n a^2 outgrows 53 bits and rounds, so the
+    one-pass ss - s mu is a rounding residue of either sign where float64's two-pass variance is exactly 0.  Every segment's
+    den stays inside [1e-8f, 1e-8 + sqrt(E)] -- a negative residue clamps to exactly 1e-8f instead of a NaN.  Over three
+    constants x segments of 900, 1,024, 1,025 and 1,200,007 rows (thirteen independent residues; the reductions run in a fixed
+    order, so each sign is the same on every run) at least one is negative or zero: the clamp is on the path."""
+    clamped = 0
+    for a in C.ADV_CONSTANTS:
+        for total, M in C.ADV_SEGMENTS[1:]:
+            adv = C.adv_values(total, a, device=DEV)
+            got = ops.adv_stats(adv[:total].contiguous(), None, M)
+            clamped += C.check_adv_stats(got, adv[:total], None, M, f"constant {a} total={total} M={M}", exact_constant=False)
+    assert clamped > 0
+
+
+def test_adv_stats_of_one_row_minibatches_is_the_row_and_nan():
+    """M == 1 as a whole call: every row of the table is (that advantage, NaN), as torch.std of one element; not refused."""
+    adv = C.adv_values(5, "n(0.5,2)", seed=3, device=DEV)
+    perm = torch.randperm(adv.numel(), device=DEV)[:5]
+    got = ops.adv_stats(adv, perm, 1)
+    assert got.shape == (5, 2) and torch.equal(got[:, 0], adv[perm]) and torch.isnan(got[:, 1]).all()
+    C.check_adv_stats(got, adv, perm, 1, "M=1")
+    zeros = torch.zeros_like(adv)
+    packed = ops.adv_stats_packed(ops.batch_pack(zeros, zeros, adv, zeros, zeros), perm, 1)
+    assert torch.equal(packed[:, 0], got[:, 0]) and torch.isnan(packed[:, 1]).all()
