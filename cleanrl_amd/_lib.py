@@ -243,6 +243,26 @@ SIGNATURES = {
     "mi355ppo_dqn_head_td_fwd_bwd_f32_cpu": (c_int, [_P] * 9 + [c_double] + [_P] * 6 + [c_int] * 3),
     "mi355ppo_c51_head_fwd_bwd_f32": (c_int, [_P] * 10 + [c_double] * 3 + [_P] * 6 + [c_int] * 4 + [_P, c_size_t, _P]),
     "mi355ppo_c51_head_fwd_bwd_f32_cpu": (c_int, [_P] * 10 + [c_double] * 3 + [_P] * 6 + [c_int] * 4),
+    # Rainbow: prioritized replay and noisy layers (added under ABI 2.7.1, csrc/rainbow.hip)
+    "mi355ppo_rainbow_per_add_u8": (c_int, [_P] * 13 + [c_int64, c_int64, c_double, _P]),
+    "mi355ppo_rainbow_per_add_u8_cpu": (c_int, [_P] * 13 + [c_int64, c_int64, c_double]),
+    "mi355ppo_rainbow_per_sample": (c_int, [_P] * 4 + [c_int64, _P, _P, c_int, _P]),
+    "mi355ppo_rainbow_per_sample_cpu": (c_int, [_P] * 4 + [c_int64, _P, _P, c_int]),
+    "mi355ppo_rainbow_per_gather_u8": (c_int, [_P] * 6 + [c_int64] + [_P] * 4 + [c_int, _P]),
+    "mi355ppo_rainbow_per_gather_u8_cpu": (c_int, [_P] * 6 + [c_int64] + [_P] * 4 + [c_int]),
+    "mi355ppo_rainbow_per_update": (c_int, [_P] * 4 + [c_int64, c_double, c_double, c_int, _P]),
+    "mi355ppo_rainbow_per_update_cpu": (c_int, [_P] * 4 + [c_int64, c_double, c_double, c_int]),
+    "mi355ppo_rainbow_noisy_count": (c_int64, [c_int, c_int, c_int]),
+    "mi355ppo_rainbow_noisy_compose_f32": (c_int, [_P, _P, _P, c_int, c_int, _P]),
+    "mi355ppo_rainbow_noisy_compose_f32_cpu": (c_int, [_P, _P, _P, c_int, c_int]),
+    "mi355ppo_rainbow_noisy_grad_f32": (c_int, [_P, _P, _P, c_int, c_int, _P]),
+    "mi355ppo_rainbow_noisy_grad_f32_cpu": (c_int, [_P, _P, _P, c_int, c_int]),
+    "mi355ppo_rainbow_head_act_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mi355ppo_rainbow_head_act_f32": (c_int, [_P] * 6 + [c_int] * 3 + [_P, c_size_t, _P]),
+    "mi355ppo_rainbow_head_act_f32_cpu": (c_int, [_P] * 6 + [c_int] * 3),
+    "mi355ppo_rainbow_head_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mi355ppo_rainbow_head_fwd_bwd_f32": (c_int, [_P] * 12 + [c_double] * 3 + [_P] * 8 + [c_int] * 3 + [_P, c_size_t, _P]),
+    "mi355ppo_rainbow_head_fwd_bwd_f32_cpu": (c_int, [_P] * 12 + [c_double] * 3 + [_P] * 8 + [c_int] * 3),
 }
 
 ABI_VERSION = 271       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)

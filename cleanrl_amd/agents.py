@@ -13,11 +13,13 @@ fused loss kernel (``heads``/``dist_params`` below are the seam).
 """
 from __future__ import annotations
 
+import math
 import os
 
 import numpy as np
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 from torch.distributions.categorical import Categorical
 from torch.distributions.normal import Normal
 
@@ -1359,3 +1361,79 @@ class AtariC51Network(nn.Module):
         if action is None:
             action = torch.argmax(q_values, 1)
         return action, pmfs[torch.arange(len(x)), action]
+
+
+class NoisyLinear(nn.Module):
+    """rainbow_atari.py's ``NoisyLinear``: ``W = weight_mu + weight_sigma * weight_epsilon`` in training mode, independent Gaussian noise
+    per weight.  Names, registration order and the construction's draws (``uniform_`` on weight_mu, ``uniform_`` on bias_mu, then the
+    two ``normal_()``) are the reference's, so a seeded construction gives its tensors."""
+
+    def __init__(self, in_features, out_features, std_init=0.5):
+        super().__init__()
+        self.in_features = in_features
+        self.out_features = out_features
+        self.std_init = std_init
+        self.weight_mu = nn.Parameter(torch.empty(out_features, in_features))
+        self.weight_sigma = nn.Parameter(torch.empty(out_features, in_features))
+        self.register_buffer("weight_epsilon", torch.empty(out_features, in_features))
+        self.bias_mu = nn.Parameter(torch.empty(out_features))
+        self.bias_sigma = nn.Parameter(torch.empty(out_features))
+        self.register_buffer("bias_epsilon", torch.empty(out_features))
+        self.reset_parameters()
+        self.reset_noise()
+
+    def reset_parameters(self):
+        mu_range = 1 / math.sqrt(self.in_features)
+        self.weight_mu.data.uniform_(-mu_range, mu_range)
+        self.weight_sigma.data.fill_(self.std_init / math.sqrt(self.in_features))
+        self.bias_mu.data.uniform_(-mu_range, mu_range)
+        self.bias_sigma.data.fill_(self.std_init / math.sqrt(self.out_features))
+
+    def reset_noise(self):
+        self.weight_epsilon.normal_()
+        self.bias_epsilon.normal_()
+
+    def forward(self, input):
+        if self.training:
+            return F.linear(input, self.weight_mu + self.weight_sigma * self.weight_epsilon, self.bias_mu + self.bias_sigma * self.bias_epsilon)
+        return F.linear(input, self.weight_mu, self.bias_mu)
+
+
+class NoisyDuelingDistributionalNetwork(nn.Module):
+    """rainbow_atari.py's network: the NatureCNN trunk, then a value and an advantage stream of two ``NoisyLinear`` layers each, the
+    dueling combine per atom and a softmax over the atoms -> (B, n_actions, n_atoms).  ``x / 255.0`` is part of the network."""
+
+    def __init__(self, env, n_atoms, v_min, v_max):
+        super().__init__()
+        self.n_atoms = n_atoms
+        self.v_min = v_min
+        self.v_max = v_max
+        self.delta_z = (v_max - v_min) / (n_atoms - 1)
+        self.n_actions = env.single_action_space.n
+        self.register_buffer("support", torch.linspace(v_min, v_max, n_atoms))
+        self.network = nn.Sequential(
+            nn.Conv2d(4, 32, 8, stride=4),
+            nn.ReLU(),
+            nn.Conv2d(32, 64, 4, stride=2),
+            nn.ReLU(),
+            nn.Conv2d(64, 64, 3, stride=1),
+            nn.ReLU(),
+            nn.Flatten(),
+        )
+        self.value_head = nn.Sequential(NoisyLinear(3136, 512), nn.ReLU(), NoisyLinear(512, n_atoms))
+        self.advantage_head = nn.Sequential(NoisyLinear(3136, 512), nn.ReLU(), NoisyLinear(512, n_atoms * self.n_actions))
+
+    def forward(self, x):
+        h = self.network(x / 255.0)
+        value = self.value_head(h).view(-1, 1, self.n_atoms)
+        advantage = self.advantage_head(h).view(-1, self.n_actions, self.n_atoms)
+        q_atoms = value + advantage - advantage.mean(dim=1, keepdim=True)
+        return F.softmax(q_atoms, dim=2)
+
+    def noisy_layers(self):
+        """The four NoisyLinear layers in ``reset_noise``'s order: value_head.0, value_head.2, advantage_head.0, advantage_head.2."""
+        return [m for head in (self.value_head, self.advantage_head) for m in head if isinstance(m, NoisyLinear)]
+
+    def reset_noise(self):
+        for layer in self.noisy_layers():
+            layer.reset_noise()

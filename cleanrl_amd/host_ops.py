@@ -17,7 +17,7 @@ import ctypes
 import torch
 
 from . import _lib
-from .ops import ATARI_FRAME, IMPALA_CHANNELS, _lstm_dims, _ptr_array, dqn_counts, dqn_head_limits_ok, dqn_limits_ok, offpolicy_counts, pqn_param_count, radam_schedule, sac_actor_count, trxl_dims  # noqa: F401  (one definition for both modules)
+from .ops import ATARI_FRAME, IMPALA_CHANNELS, _lstm_dims, _ptr_array, dqn_counts, dqn_head_limits_ok, dqn_limits_ok, offpolicy_counts, pqn_param_count, radam_schedule, rainbow_head_limits_ok, rainbow_new_buffer, rainbow_noisy_counts, rainbow_noisy_limits_ok, _rainbow_head, _rainbow_head_update_args, sac_actor_count, trxl_dims  # noqa: F401  (one definition for both modules)
 
 LOSS_SCALARS = 7
 
@@ -692,4 +692,85 @@ def c51_head_fwd_bwd(h, h_next, w, b, w_target, b_target, atoms, actions, reward
     _lib.call("mi355ppo_c51_head_fwd_bwd_f32_cpu", *nets, _in(atoms, torch.float32, (na,), "atoms"), *batch, float(gamma), float(v_min),
               float(v_max), *_head_grads(dh, dw, db, scalars, M, hidden, J), _opt_out(next_pmfs_out, M * na, "next_pmfs_out"),
               _opt_out(target_pmfs_out, M * na, "target_pmfs_out"), M, hidden, int(n_actions), na)
+    return scalars
+
+
+# ------------------------------------------------------------------------------------------- Rainbow twins (csrc/rainbow_twins.hip)
+def _per_buffer(buf):
+    ring_obs, ring_next, act, rew, done, tree, state, size = buf
+    slots = ring_obs.shape[0]
+    specs = ((ring_obs, torch.uint8, (slots,) + ATARI_FRAME, "ring obs"), (ring_next, torch.uint8, (slots,) + ATARI_FRAME, "ring next_obs"),
+             (act, torch.int64, (slots,), "ring actions"), (rew, torch.float32, (slots,), "ring rewards"),
+             (done, torch.float32, (slots,), "ring dones"), (tree, torch.float32, (2 * slots - 1,), "tree"), (state, torch.float32, (2,), "state"),
+             (size, torch.int64, (1,), "size"))
+    return slots, [_in(t, dt, shape, nm) for t, dt, shape, nm in specs]
+
+
+def rainbow_per_add_u8(buf, pos, obs, next_obs, action, reward, done, alpha):
+    slots, bp = _per_buffer(buf)
+    H, W, C = ATARI_FRAME
+    _lib.call("mi355ppo_rainbow_per_add_u8_cpu", _in(obs, torch.uint8, (1, C, H, W), "obs"), _in(next_obs, torch.uint8, (1, C, H, W), "next_obs"),
+              _in(action, torch.int64, (1,), "action"), _in(reward, torch.float32, (1,), "reward"), _in(done, torch.float32, (1,), "done"),
+              *bp, int(pos), slots, float(alpha))
+
+
+def rainbow_per_sample(buf, u, indices_out, weights_out):
+    slots, bp = _per_buffer(buf)
+    (B,) = u.shape
+    _lib.call("mi355ppo_rainbow_per_sample_cpu", _in(u, torch.float64, (B,), "u"), bp[5], bp[6], bp[7], slots,
+              _out(indices_out, torch.int64, B, "indices_out"), _out(weights_out, torch.float32, B, "weights_out"), B)
+    return indices_out, weights_out
+
+
+def rainbow_per_gather_u8(buf, indices, frames_out, actions_out, rewards_out, dones_out):
+    slots, bp = _per_buffer(buf)
+    (M,) = indices.shape
+    H, W, C = ATARI_FRAME
+    _lib.call("mi355ppo_rainbow_per_gather_u8_cpu", *bp[:5], _in(indices, torch.int64, (M,), "indices"), slots,
+              _out(frames_out, torch.uint8, 2 * M * H * W * C, "frames_out"), _out(actions_out, torch.int64, M, "actions_out"),
+              _out(rewards_out, torch.float32, M, "rewards_out"), _out(dones_out, torch.float32, M, "dones_out"), M)
+    return frames_out
+
+
+def rainbow_per_update(buf, indices, loss_per_sample, alpha, eps):
+    slots, bp = _per_buffer(buf)
+    (B,) = indices.shape
+    _lib.call("mi355ppo_rainbow_per_update_cpu", _in(indices, torch.int64, (B,), "indices"),
+              _in(loss_per_sample, torch.float32, (B,), "loss_per_sample"), bp[5], bp[6], slots, float(alpha), float(eps), B)
+
+
+def rainbow_noisy_compose(params, eps, effective, n_actions, n_atoms):
+    E, P = rainbow_noisy_counts(n_actions, n_atoms)
+    _lib.call("mi355ppo_rainbow_noisy_compose_f32_cpu", _in(params, torch.float32, (P,), "params"), _in(eps, torch.float32, (E,), "eps"),
+              _out(effective, torch.float32, E, "effective"), int(n_actions), int(n_atoms))
+    return effective
+
+
+def rainbow_noisy_grad(effective_grad, eps, grads, n_actions, n_atoms):
+    E, P = rainbow_noisy_counts(n_actions, n_atoms)
+    _lib.call("mi355ppo_rainbow_noisy_grad_f32_cpu", _in(effective_grad, torch.float32, (E,), "effective_grad"),
+              _in(eps, torch.float32, (E,), "eps"), _out(grads, torch.float32, P, "grads"), int(n_actions), int(n_atoms))
+    return grads
+
+
+def _host_chk(t, dtype, name, shape):
+    return _in(t, dtype, shape, name)
+
+
+def rainbow_head_act(h, w_out, b_out, support, n_actions, actions_out, q_out=None):
+    N, na, J = _rainbow_head(h, w_out, b_out, support, n_actions, _host_chk)
+    _lib.call("mi355ppo_rainbow_head_act_f32_cpu", _p(h), _p(w_out), _p(b_out), _p(support), _out(actions_out, torch.int64, N, "actions_out"),
+              _opt_out(q_out, N * n_actions, "q_out"), N, int(n_actions), na)
+    return actions_out
+
+
+def rainbow_head_fwd_bwd(h, h_next, h_next_target, w_out, b_out, w_out_target, b_out_target, support, actions, rewards, dones, weights,
+                         n_actions, gamma_n, v_min, v_max, dh, dw_out, db_out, scalars, loss_per_sample, best_actions_out=None,
+                         next_pmfs_out=None, target_pmfs_out=None):
+    M, na = _rainbow_head_update_args(h, h_next, h_next_target, w_out, b_out, w_out_target, b_out_target, support, actions, rewards, dones, weights,
+                                      n_actions, dh, dw_out, db_out, scalars, loss_per_sample, best_actions_out, next_pmfs_out, target_pmfs_out,
+                                      _host_chk)
+    _lib.call("mi355ppo_rainbow_head_fwd_bwd_f32_cpu", _p(h), _p(h_next), _p(h_next_target), _p(w_out), _p(b_out), _p(w_out_target), _p(b_out_target),
+              _p(support), _p(actions), _p(rewards), _p(dones), _p(weights), float(gamma_n), float(v_min), float(v_max), _p(dh), _p(dw_out),
+              _p(db_out), _p(scalars), _p(loss_per_sample), _p(best_actions_out), _p(next_pmfs_out), _p(target_pmfs_out), M, int(n_actions), na)
     return scalars

@@ -30,6 +30,8 @@ __all__ = [
     "td3_critic_fwd_bwd", "td3_actor_fwd_bwd", "polyak_", "sac_actor_count", "sac_policy", "sac_target", "sac_actor_fwd_bwd", "sac_alpha_",
     "dqn_counts", "dqn_limits_ok", "dqn_act", "dqn_td_fwd_bwd", "c51_fwd_bwd",
     "dqn_head_limits_ok", "replay_add_u8", "replay_gather_u8", "dqn_head_act", "dqn_head_td_fwd_bwd", "c51_head_fwd_bwd",
+    "rainbow_noisy_limits_ok", "rainbow_noisy_counts", "rainbow_new_buffer", "rainbow_per_add_u8", "rainbow_per_sample", "rainbow_per_gather_u8",
+    "rainbow_per_update", "rainbow_noisy_compose", "rainbow_noisy_grad", "rainbow_head_limits_ok", "rainbow_head_act", "rainbow_head_fwd_bwd",
 ]
 
 LOSS_SCALAR_NAMES = ("loss", "pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac")
@@ -1715,4 +1717,187 @@ def c51_head_fwd_bwd(h, h_next, w, b, w_target, b_target, atoms, actions, reward
     _launch("mi355ppo_c51_head_fwd_bwd_f32", h.device, _ptr(h), _ptr(h_next), _ptr(w), _ptr(b), _ptr(w_target), _ptr(b_target), _ptr(atoms),
             _ptr(actions), _ptr(rewards), _ptr(dones), float(gamma), float(v_min), float(v_max), _ptr(dh), _ptr(dw), _ptr(db), _ptr(scalars),
             _ptr(next_pmfs_out), _ptr(target_pmfs_out), M, hidden, int(n_actions), na, _ptr(ws), ws.numel())
+    return scalars
+
+
+# ------------------------------------------------------------------------------------------- Rainbow (csrc/rainbow.hip)
+RAINBOW_MAX_BATCH = 1024
+
+
+def rainbow_noisy_limits_ok(n_actions: int, n_atoms: int) -> bool:
+    """What the noisy dueling head's compose / grad kernels take (anything else is ``MI355PPO_EINVAL`` from the C ABI)."""
+    return 2 <= n_actions <= DQN_MAX_ACT and 2 <= n_atoms <= DQN_MAX_ATOMS and (n_actions + 1) * n_atoms <= DQN_HEAD_MAX_OUT
+
+
+def rainbow_noisy_counts(n_actions: int, n_atoms: int):
+    """(elements of the effective buffer and of eps, elements of the head's flat parameters) of the four NoisyLinear layers."""
+    if not rainbow_noisy_limits_ok(n_actions, n_atoms):
+        raise ValueError(f"n_actions={n_actions} n_atoms={n_atoms}: 2 <= n_actions <= {DQN_MAX_ACT}, 2 <= n_atoms <= {DQN_MAX_ATOMS}, "
+                         f"(n_actions + 1) * n_atoms <= {DQN_HEAD_MAX_OUT}")
+    hid, fc_in, J = DQN_HEAD_HIDDEN, 3136, (n_actions + 1) * n_atoms
+    E = 2 * hid * fc_in + 2 * hid + J * hid + J
+    return E, 2 * E
+
+
+def rainbow_new_buffer(slots: int, device, beta: float = 0.4):
+    """The prioritized buffer's tensors on ``device``: (ring_obs, ring_next_obs (slots, 84, 84, 4) u8, actions (slots,) int64, rewards,
+    dones (slots,) f32, tree (2 * slots - 1,) f32, state (2,) f32 = {max_priority = 1, beta}, size (1,) int64)."""
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)  # noqa: E731
+    state = torch.tensor([1.0, beta], dtype=torch.float32, device=device)
+    return (z((slots,) + ATARI_FRAME, torch.uint8), z((slots,) + ATARI_FRAME, torch.uint8), z((slots,), torch.int64), z((slots,), torch.float32),
+            z((slots,), torch.float32), z((2 * slots - 1,), torch.float32), state, z((1,), torch.int64))
+
+
+def _per_buffer(buf, chk):
+    ring_obs, ring_next, act, rew, done, tree, state, size = buf
+    slots = ring_obs.shape[0]
+    chk(ring_obs, torch.uint8, "ring obs", (slots,) + ATARI_FRAME)
+    chk(ring_next, torch.uint8, "ring next_obs", (slots,) + ATARI_FRAME)
+    chk(act, torch.int64, "ring actions", (slots,))
+    chk(rew, torch.float32, "ring rewards", (slots,))
+    chk(done, torch.float32, "ring dones", (slots,))
+    chk(tree, torch.float32, "tree", (2 * slots - 1,))
+    chk(state, torch.float32, "state", (2,))
+    chk(size, torch.int64, "size", (1,))
+    return slots
+
+
+def rainbow_per_add_u8(buf, pos: int, obs, next_obs, action, reward, done, alpha: float):
+    """``PrioritizedReplayBuffer.add`` behind the n-step accumulator: one transition into slot ``pos`` of both frame rings, its leaf at
+    ``max_priority ** alpha`` and the leaf's ancestors (one launch)."""
+    slots = _per_buffer(buf, _chk)
+    H, W, C = ATARI_FRAME
+    _chk(obs, torch.uint8, "obs", (1, C, H, W))
+    _chk(next_obs, torch.uint8, "next_obs", (1, C, H, W))
+    _chk(action, torch.int64, "action", (1,))
+    _chk(reward, torch.float32, "reward", (1,))
+    _chk(done, torch.float32, "done", (1,))
+    _launch("mi355ppo_rainbow_per_add_u8", obs.device, _ptr(obs), _ptr(next_obs), _ptr(action), _ptr(reward), _ptr(done), *[_ptr(t) for t in buf],
+            int(pos), slots, float(alpha))
+
+
+def rainbow_per_sample(buf, u, indices_out, weights_out):
+    """``PrioritizedReplayBuffer.sample``'s indices (B,) int64 and weights (B,) f32 from the draws ``u`` (B,) f64; the tree, ``size``
+    and ``beta`` are read from device memory (one launch)."""
+    slots = _per_buffer(buf, _chk)
+    (B,) = u.shape
+    _chk(u, torch.float64, "u", (B,))
+    _chk(indices_out, torch.int64, "indices_out", (B,))
+    _chk(weights_out, torch.float32, "weights_out", (B,))
+    _launch("mi355ppo_rainbow_per_sample", u.device, _ptr(u), _ptr(buf[5]), _ptr(buf[6]), _ptr(buf[7]), slots, _ptr(indices_out),
+            _ptr(weights_out), B)
+    return indices_out, weights_out
+
+
+def rainbow_per_gather_u8(buf, indices, frames_out, actions_out, rewards_out, dones_out):
+    """A batch out of the two frame rings in one launch: frames_out (2M, 84, 84, 4) u8 = the M obs frames, then the M next_obs frames;
+    actions_out (M,) int64, rewards_out / dones_out (M,) f32."""
+    slots = _per_buffer(buf, _chk)
+    (M,) = indices.shape
+    _chk(indices, torch.int64, "indices", (M,))
+    _chk(frames_out, torch.uint8, "frames_out", (2 * M,) + ATARI_FRAME)
+    _chk(actions_out, torch.int64, "actions_out", (M,))
+    _chk(rewards_out, torch.float32, "rewards_out", (M,))
+    _chk(dones_out, torch.float32, "dones_out", (M,))
+    _launch("mi355ppo_rainbow_per_gather_u8", indices.device, *[_ptr(t) for t in buf[:5]], _ptr(indices), slots, _ptr(frames_out),
+            _ptr(actions_out), _ptr(rewards_out), _ptr(dones_out), M)
+    return frames_out
+
+
+def rainbow_per_update(buf, indices, loss_per_sample, alpha: float, eps: float):
+    """``PrioritizedReplayBuffer.update_priorities`` on device tensors: the running maximum, the leaves and their ancestors (one
+    launch, no read-back of ``loss_per_sample``)."""
+    slots = _per_buffer(buf, _chk)
+    (B,) = indices.shape
+    _chk(indices, torch.int64, "indices", (B,))
+    _chk(loss_per_sample, torch.float32, "loss_per_sample", (B,))
+    _launch("mi355ppo_rainbow_per_update", indices.device, _ptr(indices), _ptr(loss_per_sample), _ptr(buf[5]), _ptr(buf[6]), slots, float(alpha),
+            float(eps), B)
+
+
+def rainbow_noisy_compose(params, eps, effective, n_actions: int, n_atoms: int):
+    """``mu + sigma * eps`` of the four NoisyLinear layers into the effective buffer (layouts: include/mi355ppo.h), one launch."""
+    E, P = rainbow_noisy_counts(n_actions, n_atoms)
+    _chk(params, torch.float32, "params", (P,))
+    _chk(eps, torch.float32, "eps", (E,))
+    _chk(effective, torch.float32, "effective", (E,))
+    _launch("mi355ppo_rainbow_noisy_compose_f32", params.device, _ptr(params), _ptr(eps), _ptr(effective), int(n_actions), int(n_atoms))
+    return effective
+
+
+def rainbow_noisy_grad(effective_grad, eps, grads, n_actions: int, n_atoms: int):
+    """The effective buffer's gradient back onto the parameters: ``dmu = g``, ``dsigma = g * eps``; OVERWRITES ``grads``, one launch."""
+    E, P = rainbow_noisy_counts(n_actions, n_atoms)
+    _chk(effective_grad, torch.float32, "effective_grad", (E,))
+    _chk(eps, torch.float32, "eps", (E,))
+    _chk(grads, torch.float32, "grads", (P,))
+    _launch("mi355ppo_rainbow_noisy_grad_f32", grads.device, _ptr(effective_grad), _ptr(eps), _ptr(grads), int(n_actions), int(n_atoms))
+    return grads
+
+
+RAINBOW_HEAD_IN = 2 * DQN_HEAD_HIDDEN            # h (rows, 1024): the value stream's 512 hidden columns, then the advantage stream's
+
+
+def rainbow_head_limits_ok(n_actions: int, n_atoms: int, rows: int = 1) -> bool:
+    """What the fused dueling distributional head takes (anything else is ``MI355PPO_EINVAL`` from the C ABI)."""
+    return rainbow_noisy_limits_ok(n_actions, n_atoms) and 1 <= rows <= DQN_HEAD_MAX_ROWS
+
+
+def _rainbow_head(h, w_out, b_out, support, n_actions, chk, nm=""):
+    M = h.shape[0]
+    na = support.numel()
+    J = (int(n_actions) + 1) * na
+    chk(h, torch.float32, nm + "h", (M, RAINBOW_HEAD_IN))
+    chk(w_out, torch.float32, nm + "w_out", (J, DQN_HEAD_HIDDEN))
+    chk(b_out, torch.float32, nm + "b_out", (J,))
+    chk(support, torch.float32, "support", (na,))
+    return M, na, J
+
+
+def rainbow_head_act(h, w_out, b_out, support, n_actions: int, actions_out, q_out=None):
+    """The greedy action of the noisy dueling head on ``h`` (N, 1024) -> actions_out (N,) int64 (two launches)."""
+    N, na, J = _rainbow_head(h, w_out, b_out, support, n_actions, _chk)
+    _chk(actions_out, torch.int64, "actions_out", (N,))
+    if q_out is not None:
+        _chk(q_out, torch.float32, "q_out", (N, n_actions))
+    ws = _workspace(h.device, _lib.load().mi355ppo_rainbow_head_act_workspace_bytes(N, int(n_actions), na))
+    _launch("mi355ppo_rainbow_head_act_f32", h.device, _ptr(h), _ptr(w_out), _ptr(b_out), _ptr(support), _ptr(actions_out), _ptr(q_out), N,
+            int(n_actions), na, _ptr(ws), ws.numel())
+    return actions_out
+
+
+def _rainbow_head_update_args(h, h_next, h_next_target, w_out, b_out, w_out_target, b_out_target, support, actions, rewards, dones, weights,
+                              n_actions, dh, dw_out, db_out, scalars, loss_per_sample, best_actions_out, next_pmfs_out, target_pmfs_out, chk):
+    M, na, J = _rainbow_head(h, w_out, b_out, support, n_actions, chk)
+    _rainbow_head(h_next, w_out_target, b_out_target, support, n_actions, chk, "target ")
+    chk(h_next_target, torch.float32, "h_next_target", (M, RAINBOW_HEAD_IN))
+    chk(h_next, torch.float32, "h_next", (M, RAINBOW_HEAD_IN))
+    chk(actions, torch.int64, "actions", (M,))
+    for t, nm in ((rewards, "rewards"), (dones, "dones"), (weights, "weights"), (loss_per_sample, "loss_per_sample")):
+        chk(t, torch.float32, nm, (M,))
+    chk(dh, torch.float32, "dh", (M, RAINBOW_HEAD_IN))
+    chk(dw_out, torch.float32, "dw_out", (J, DQN_HEAD_HIDDEN))
+    chk(db_out, torch.float32, "db_out", (J,))
+    chk(scalars, torch.float32, "scalars", (2,))
+    if best_actions_out is not None:
+        chk(best_actions_out, torch.int64, "best_actions_out", (M,))
+    for t, nm in ((next_pmfs_out, "next_pmfs_out"), (target_pmfs_out, "target_pmfs_out")):
+        if t is not None:
+            chk(t, torch.float32, nm, (M, na))
+    return M, na
+
+
+def rainbow_head_fwd_bwd(h, h_next, h_next_target, w_out, b_out, w_out_target, b_out_target, support, actions, rewards, dones, weights,
+                         n_actions: int, gamma_n: float, v_min: float, v_max: float, dh, dw_out, db_out, scalars, loss_per_sample,
+                         best_actions_out=None, next_pmfs_out=None, target_pmfs_out=None):
+    """rainbow_atari.py's update behind the trunks in three launches: online(obs), online(next_obs) and target(next_obs) through the
+    effective output layers, double-Q selection, the n-step projection (``gamma_n = gamma ** n_step``), the importance-weighted loss and
+    the head's backward.  OVERWRITES ``dh`` (M, 1024), ``dw_out`` / ``db_out``, ``loss_per_sample`` (M,); scalars (2,) = {loss, q_values}."""
+    M, na = _rainbow_head_update_args(h, h_next, h_next_target, w_out, b_out, w_out_target, b_out_target, support, actions, rewards, dones, weights,
+                                      n_actions, dh, dw_out, db_out, scalars, loss_per_sample, best_actions_out, next_pmfs_out, target_pmfs_out, _chk)
+    ws = _workspace(h.device, _lib.load().mi355ppo_rainbow_head_workspace_bytes(M, int(n_actions), na))
+    _launch("mi355ppo_rainbow_head_fwd_bwd_f32", h.device, _ptr(h), _ptr(h_next), _ptr(h_next_target), _ptr(w_out), _ptr(b_out), _ptr(w_out_target),
+            _ptr(b_out_target), _ptr(support), _ptr(actions), _ptr(rewards), _ptr(dones), _ptr(weights), float(gamma_n), float(v_min), float(v_max),
+            _ptr(dh), _ptr(dw_out), _ptr(db_out), _ptr(scalars), _ptr(loss_per_sample), _ptr(best_actions_out), _ptr(next_pmfs_out),
+            _ptr(target_pmfs_out), M, int(n_actions), na, _ptr(ws), ws.numel())
     return scalars

@@ -1182,6 +1182,107 @@ MI355PPO_API int mi355ppo_c51_head_fwd_bwd_f32_cpu(const float* h, const float* 
                                                    float* db, float* scalars_out, float* next_pmfs_out, float* target_pmfs_out, int M,
                                                    int hidden, int n_actions, int n_atoms);
 
+/* ---- Rainbow: prioritized n-step replay and noisy layers (added under ABI 2.7.1, csrc/rainbow.hip; reference: cleanrl/rainbow_atari.py's
+ * PrioritizedReplayBuffer, SumSegmentTree and NoisyLinear) ----
+ * The buffer in device memory: ring_obs and ring_next_obs (slots, 84, 84, 4) u8, channels-last and 4-byte aligned, two separate rings;
+ * ring_actions (slots) int64, ring_rewards and ring_dones (slots) f32; tree (2 * slots - 1) f32 in the reference's heap layout (node p has
+ * the children 2p + 1 and 2p + 2, leaf i is word slots - 1 + i; an inner node is the f32 sum of its two children); state (2) f32 =
+ * {max_priority, beta}; size (1) int64.  The caller initialises state to {1, beta} and zeroes the rest.  Every offset is 64-bit.
+ * x ** alpha and x ** -beta are pow((double)x, (double)(float)exponent) rounded once to f32: NumPy raises a float32 to a Python float
+ * with powf(x, (float)exponent), and the exact power is within 1 ulp of both.  Everything that does not pass through a power is
+ * bit-equal between device, twin and reference.  1 <= rows <= 1024; anything else is MI355PPO_EINVAL before any launch.  No entry point
+ * allocates or synchronises, none uses atomics, all can be captured.
+ *
+ * per_add: one n-step transition into slot pos: obs / next_obs (1, 4, 84, 84) u8 as the env gives them, action (1) int64, reward (1)
+ * (the n-step return) and done (1) f32, all in device memory.  Leaf pos becomes max_priority ** alpha, its ancestors are recomputed,
+ * size becomes min(size + 1, slots).  One launch. */
+MI355PPO_API int mi355ppo_rainbow_per_add_u8(const uint8_t* obs, const uint8_t* next_obs, const int64_t* action, const float* reward,
+                                             const float* done, uint8_t* ring_obs, uint8_t* ring_next_obs, int64_t* ring_actions,
+                                             float* ring_rewards, float* ring_dones, float* tree, float* state, int64_t* size, int64_t pos,
+                                             int64_t slots, double alpha, void* stream);
+MI355PPO_API int mi355ppo_rainbow_per_add_u8_cpu(const uint8_t* obs, const uint8_t* next_obs, const int64_t* action, const float* reward,
+                                                 const float* done, uint8_t* ring_obs, uint8_t* ring_next_obs, int64_t* ring_actions,
+                                                 float* ring_rewards, float* ring_dones, float* tree, float* state, int64_t* size,
+                                                 int64_t pos, int64_t slots, double alpha);
+/* per_sample: PrioritizedReplayBuffer.sample's indices and weights.  u (B) f64: one np.random.random_sample() per sample, which is what
+ * each of the reference's np.random.uniform(a, b) draws.  segment = tree[0] / B, a = segment * i, b = segment * (i + 1) in f32; value =
+ * a + (b - a) * u in f64, rounded to f32 (NumPy compares and subtracts a Python float against a float32 in float32); the walk takes
+ * the left child while value <= tree[left], else subtracts it and goes right.  weights = (size * p / tree[0]) ** -beta / their maximum
+ * (a NaN wins).  indices_out (B) int64, weights_out (B) f32.  One launch of one workgroup. */
+MI355PPO_API int mi355ppo_rainbow_per_sample(const double* u, const float* tree, const float* state, const int64_t* size, int64_t slots,
+                                             int64_t* indices_out, float* weights_out, int B, void* stream);
+MI355PPO_API int mi355ppo_rainbow_per_sample_cpu(const double* u, const float* tree, const float* state, const int64_t* size, int64_t slots,
+                                                 int64_t* indices_out, float* weights_out, int B);
+/* per_gather: frames_out (2M, 84, 84, 4) u8, 4-byte aligned: rows m < M the obs frames of slots indices[m], rows M + m their next_obs
+ * frames; actions_out (M) int64, rewards_out, dones_out (M) f32.  Indices are clamped into the ring.  One launch. */
+MI355PPO_API int mi355ppo_rainbow_per_gather_u8(const uint8_t* ring_obs, const uint8_t* ring_next_obs, const int64_t* ring_actions,
+                                                const float* ring_rewards, const float* ring_dones, const int64_t* indices, int64_t slots,
+                                                uint8_t* frames_out, int64_t* actions_out, float* rewards_out, float* dones_out, int M,
+                                                void* stream);
+MI355PPO_API int mi355ppo_rainbow_per_gather_u8_cpu(const uint8_t* ring_obs, const uint8_t* ring_next_obs, const int64_t* ring_actions,
+                                                    const float* ring_rewards, const float* ring_dones, const int64_t* indices,
+                                                    int64_t slots, uint8_t* frames_out, int64_t* actions_out, float* rewards_out,
+                                                    float* dones_out, int M);
+/* per_update: update_priorities.  p = |loss_per_sample| + (float)eps; max_priority = max(max_priority, max p) (a NaN maximum leaves it);
+ * leaf indices[i] (clamped into the ring) becomes p[i] ** alpha, of duplicate indices the highest batch position stays, as the
+ * reference's serial loop leaves it; every ancestor of a written leaf is recomputed, level by level from the deepest tree level.  One
+ * launch of one workgroup. */
+MI355PPO_API int mi355ppo_rainbow_per_update(const int64_t* indices, const float* loss_per_sample, float* tree, float* state, int64_t slots,
+                                             double alpha, double eps, int B, void* stream);
+MI355PPO_API int mi355ppo_rainbow_per_update_cpu(const int64_t* indices, const float* loss_per_sample, float* tree, float* state,
+                                                 int64_t slots, double alpha, double eps, int B);
+/* The four NoisyLinear layers of NoisyDuelingDistributionalNetwork in one launch.  params / grads: the head's parameters (gradients) as
+ * one flat buffer in torch's registration order: per layer weight_mu, weight_sigma, bias_mu, bias_sigma; layers value_head.0 (512, 3136),
+ * value_head.2 (n_atoms, 512), advantage_head.0 (512, 3136), advantage_head.2 (n_actions * n_atoms, 512).  eps: per layer
+ * weight_epsilon, bias_epsilon in the same layer order (reset_noise()'s).  effective: W_fc (1024, 3136) | b_fc (1024) |
+ * W_out ((n_actions + 1) * n_atoms, 512) | b_out, the value stream's rows first.  noisy_count(which = 0): the elements of eps and of
+ * effective; (which = 1): of params; 0 outside 2 <= n_actions <= 18, 2 <= n_atoms <= 101, (n_actions + 1) * n_atoms <= 1024.
+ * compose: effective = mu + sigma * eps (an f32 multiply, then an add: torch's bits).  grad: dmu = g, dsigma = g * eps of the effective
+ * buffer's gradient g, OVERWRITING grads (autograd's bits). */
+MI355PPO_API int64_t mi355ppo_rainbow_noisy_count(int n_actions, int n_atoms, int which);
+MI355PPO_API int mi355ppo_rainbow_noisy_compose_f32(const float* params, const float* eps, float* effective, int n_actions, int n_atoms,
+                                                    void* stream);
+MI355PPO_API int mi355ppo_rainbow_noisy_compose_f32_cpu(const float* params, const float* eps, float* effective, int n_actions, int n_atoms);
+MI355PPO_API int mi355ppo_rainbow_noisy_grad_f32(const float* effective_grad, const float* eps, float* grads, int n_actions, int n_atoms,
+                                                 void* stream);
+MI355PPO_API int mi355ppo_rainbow_noisy_grad_f32_cpu(const float* effective_grad, const float* eps, float* grads, int n_actions, int n_atoms);
+/* The noisy dueling distributional head behind the trunk.  h (rows, 1024): the post-ReLU output of ONE Linear(3136, 1024) that holds both
+ * streams' hidden layers (the effective W_fc / b_fc above), the value stream's 512 columns first.  w_out ((n_actions + 1) * n_atoms, 512)
+ * and b_out: the effective output layer, the value stream's n_atoms rows first; they read h[:, :512], the advantage rows h[:, 512:].
+ * Every dot product starts at 0.0f and adds in ascending index, then the bias.  q_atoms = (v + adv) - mean_a adv (ascending sum / n), a
+ * softmax over each action's atoms, expectations against support, argmax under mi355ppo_dqn_act_f32's tie and NaN rules.
+ * 1 <= rows <= 1024, 2 <= n_actions <= 18, 2 <= n_atoms <= 101, (n_actions + 1) * n_atoms <= 1024; anything else is MI355PPO_EINVAL.
+ * head_act: actions_out (N) int64; q_out (N, n_actions) may be NULL.  Two launches. */
+MI355PPO_API size_t mi355ppo_rainbow_head_act_workspace_bytes(int N, int n_actions, int n_atoms);
+MI355PPO_API int mi355ppo_rainbow_head_act_f32(const float* h, const float* w_out, const float* b_out, const float* support,
+                                               int64_t* actions_out, float* q_out, int N, int n_actions, int n_atoms, void* workspace,
+                                               size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_rainbow_head_act_f32_cpu(const float* h, const float* w_out, const float* b_out, const float* support,
+                                                   int64_t* actions_out, float* q_out, int N, int n_actions, int n_atoms);
+/* head_fwd_bwd: rainbow_atari.py's update behind the trunks in three launches.  Three passes: online on h (obs), online on h_next
+ * (next_obs), target on h_next_target (next_obs).  The online expectations on next_obs pick best_actions, next_pmfs is the target's
+ * distribution there; the projection is the script's own: next_atoms = r + (gamma_n * support) * (1 - d) with gamma_n =
+ * (float)(gamma ** n_step), b = (clamp(next_atoms) - v_min) / (float)((v_max - v_min) / (n_atoms - 1)), d_m_l = (u + (l == b) - b) * p,
+ * d_m_u = (b - l) * p, added in index_add_'s serial order.  loss_per_sample (M) = -sum target * log(clamp(pred, 1e-5, 1 - 1e-5));
+ * scalars_out (2) = {mean(loss_per_sample * weights), mean sum pred * support}.  dh (M, 1024) is d loss / d h; dw_out and db_out are
+ * OVERWRITTEN with the effective output layer's gradient (every row: the advantage mean reaches every action).  The optional outputs:
+ * best_actions_out (M) int64, next_pmfs_out and target_pmfs_out (M, n_atoms). */
+MI355PPO_API size_t mi355ppo_rainbow_head_workspace_bytes(int M, int n_actions, int n_atoms);
+MI355PPO_API int mi355ppo_rainbow_head_fwd_bwd_f32(const float* h, const float* h_next, const float* h_next_target, const float* w_out,
+                                                   const float* b_out, const float* w_out_target, const float* b_out_target,
+                                                   const float* support, const int64_t* actions, const float* rewards, const float* dones,
+                                                   const float* weights, double gamma_n, double v_min, double v_max, float* dh, float* dw_out,
+                                                   float* db_out, float* scalars_out, float* loss_per_sample, int64_t* best_actions_out,
+                                                   float* next_pmfs_out, float* target_pmfs_out, int M, int n_actions, int n_atoms,
+                                                   void* workspace, size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_rainbow_head_fwd_bwd_f32_cpu(const float* h, const float* h_next, const float* h_next_target, const float* w_out,
+                                                       const float* b_out, const float* w_out_target, const float* b_out_target,
+                                                       const float* support, const int64_t* actions, const float* rewards,
+                                                       const float* dones, const float* weights, double gamma_n, double v_min, double v_max,
+                                                       float* dh, float* dw_out, float* db_out, float* scalars_out, float* loss_per_sample,
+                                                       int64_t* best_actions_out, float* next_pmfs_out, float* target_pmfs_out, int M,
+                                                       int n_actions, int n_atoms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,13 +1,18 @@
 """ddpg_continuous_action.py / td3_continuous_action.py / sac_continuous_action.py with both ``MI355PPO_OFFPOLICY`` backends, in one
 process, alternating.
 
-    python tools/offpolicybench.py [--reps 20] [--scripts td3 ddpg sac dqn dqn_atari]
+    python tools/offpolicybench.py [--reps 20] [--scripts td3 ddpg sac dqn dqn_atari rainbow rainbow_buffer]
 
 Times, at each script's defaults (batch 256) on a HalfCheetah-shaped (obs 17 / act 6) and a Humanoid-shaped (376 / 17) task:
 one rollout step including the action's copy to the host, one critic-only training step and one step with the delayed policy
 update.  The comparison is the ``torch`` backend on the same box in the same process; medians of ``--reps`` after a warm-up.
 Prints one JSON line per (script, shape).  ``--scripts dqn`` times dqn.py and c51.py (batch 128) at a CartPole-shaped (obs 4 / 2
 actions) and a LunarLander-shaped (8 / 4) task: one greedy rollout step, one DQN update and one C51 update (101 atoms).
+``--scripts rainbow`` times rainbow_atari.py (batch 32, 51 atoms) for a 4-action and an 18-action game: one rollout step, one update
+and the three noise compositions.  ``--scripts rainbow_buffer`` times rainbow_atari.py's prioritized replay at batch 32 (cleanrl_amd/rainbow_replay.py): the host buffer
+by the reference's rules (NumPy tree walk, batch upload, ``loss_per_sample`` read back) against the device buffer, per add, per
+sample and per priority update; and the four NoisyLinear layers' ``mu + sigma * eps`` by torch against the one-launch compose, for a
+4-action and an 18-action game.
 """
 from __future__ import annotations
 
@@ -114,6 +119,126 @@ def bench_dqn_atari(a, dev):
         print(json.dumps(row), flush=True)
 
 
+def make_rainbow(n, backend, dev, fill=256):
+    from cleanrl_amd.agents import NoisyDuelingDistributionalNetwork
+    from cleanrl_amd.learner_rainbow import RainbowLearner
+
+    torch.manual_seed(1)
+    np.random.seed(1)
+    envs = E.AtariReplayVecEnv(1, seed=1, n_actions=n)
+    q, t = (NoisyDuelingDistributionalNetwork(envs, 51, -10, 10).to(dev) for _ in range(2))
+    t.load_state_dict(q.state_dict())
+    args = SimpleNamespace(buffer_size=fill * 2, batch_size=32, learning_rate=6.25e-5, gamma=0.99, tau=1.0, n_step=3, n_atoms=51, v_min=-10,
+                           v_max=10, prioritized_replay_alpha=0.5, prioritized_replay_beta=0.4, prioritized_replay_eps=1e-6)
+    L = RainbowLearner(q, t, args, envs, dev, backend=backend)
+    obs, _ = envs.reset(seed=1)
+    for _ in range(fill):
+        act = np.array([envs.single_action_space.sample()])
+        nxt, r, term, trunc, _ = envs.step(act)
+        L.store(obs, act, r, nxt, term)
+        obs = nxt
+    return L, obs
+
+
+def bench_rainbow(a, dev):
+    """rainbow_atari.py at batch 32: one rollout step, one update, and the three noise compositions (after ``reset_noise``: both
+    networks; after Adam: online; after ``sync_target``: target).  The ``torch`` side of a compose leg is what its forward passes
+    pay instead: ``mu + sigma * eps`` of the same layers by torch's ops."""
+    for shape, n in ATARI_SHAPES.items():
+        learners = {b: make_rainbow(n, b, dev) for b in ("torch", "fused")}
+
+        def composes(L, online, target):
+            if L.fused:
+                return L.compose(online, target)
+            with torch.no_grad():
+                nets = [net for net, on in ((L.q_network, online), (L.target_network, target)) if on]
+                return [t for net in nets for l in net.noisy_layers()
+                        for t in (l.weight_mu + l.weight_sigma * l.weight_epsilon, l.bias_mu + l.bias_sigma * l.bias_epsilon)]
+
+        legs = {"rollout_step": lambda L, obs: L.act(obs), "update": lambda L, obs: L.train_step(),
+                "compose_both": lambda L, obs: composes(L, True, True), "compose_online": lambda L, obs: composes(L, True, False),
+                "compose_target": lambda L, obs: composes(L, False, True)}
+        times = {leg: {b: [] for b in learners} for leg in legs}
+        for rep in range(a.warmup + a.reps):
+            for leg, fn in legs.items():
+                for b, (L, obs) in learners.items():                     # alternating: both backends see the same box state
+                    us = timed(lambda: fn(L, obs), dev)
+                    if rep >= a.warmup:
+                        times[leg][b].append(us)
+        row = {"script": "rainbow", "shape": shape, "n_actions": n, "n_atoms": 51, "batch": 32, "device": str(dev), "reps": a.reps}
+        for leg in legs:
+            for b in learners:
+                row[f"{leg}_{b}_us"] = round(statistics.median(times[leg][b]), 1)
+            row[f"{leg}_speedup"] = round(row[f"{leg}_torch_us"] / row[f"{leg}_fused_us"], 2)
+        print(json.dumps(row), flush=True)
+
+
+def bench_rainbow_buffer(a, dev, slots=4096, B=32):
+    from cleanrl_amd import ops
+    from cleanrl_amd.agents import NoisyDuelingDistributionalNetwork
+    from cleanrl_amd.rainbow_replay import DevicePrioritizedReplay, HostPrioritizedReplay
+
+    g = ops.twins(dev)
+    for shape, n in ATARI_SHAPES.items():
+        torch.manual_seed(1)
+        np.random.seed(1)
+        envs = E.AtariReplayVecEnv(1, seed=1, n_actions=n)
+        bufs = {"torch": HostPrioritizedReplay(slots, (4, 84, 84), 3, 0.99, 0.5, 0.4, 1e-6), "fused": DevicePrioritizedReplay(slots, dev, 3, 0.99, 0.5)}
+        obs, _ = envs.reset(seed=1)
+        steps = []
+        for _ in range(slots // 4):
+            act = np.array([envs.single_action_space.sample()])
+            nxt, r, term, trunc, _ = envs.step(act)
+            steps.append((obs, act, r, nxt, term))
+            for rb in bufs.values():
+                rb.add(*steps[-1])
+            obs = nxt
+        net = NoisyDuelingDistributionalNetwork(envs, 51, -10, 10).to(dev)
+        layers = net.noisy_layers()
+        params = torch.cat([p.detach().reshape(-1) for l in layers for p in (l.weight_mu, l.weight_sigma, l.bias_mu, l.bias_sigma)])
+        eps = torch.cat([b.reshape(-1) for l in layers for b in (l.weight_epsilon, l.bias_epsilon)])
+        eff = torch.zeros_like(eps)
+        loss = torch.rand(B, device=dev)
+        last = {}
+
+        def host_sample(rb):
+            b = rb.sample(B)
+            last["torch"] = b["indices"]
+            return [torch.from_numpy(b[k]).to(dev) for k in ("observations", "next_observations", "actions", "rewards", "dones", "weights")]
+
+        def dev_sample(rb):
+            last["fused"] = rb.sample(B)["indices"]
+
+        k = [0]
+
+        def add(rb):
+            k[0] += 1
+            rb.add(*steps[k[0] % len(steps)])
+
+        def torch_compose():
+            with torch.no_grad():
+                return [t for l in layers for t in (l.weight_mu + l.weight_sigma * l.weight_epsilon, l.bias_mu + l.bias_sigma * l.bias_epsilon)]
+
+        legs = {"add": {"torch": lambda: add(bufs["torch"]), "fused": lambda: add(bufs["fused"])},
+                "sample": {"torch": lambda: host_sample(bufs["torch"]), "fused": lambda: dev_sample(bufs["fused"])},
+                "priority_update": {"torch": lambda: bufs["torch"].update_priorities(last["torch"], loss.cpu().numpy()),
+                                    "fused": lambda: bufs["fused"].update_priorities(last["fused"], loss)},
+                "compose": {"torch": torch_compose, "fused": lambda: g.rainbow_noisy_compose(params, eps, eff, n, 51)}}
+        times = {leg: {b: [] for b in ("torch", "fused")} for leg in legs}
+        for rep in range(a.warmup + a.reps):
+            for leg, fns in legs.items():
+                for b in ("torch", "fused"):                             # alternating: both see the same box state
+                    us = timed(fns[b], dev)
+                    if rep >= a.warmup:
+                        times[leg][b].append(us)
+        row = {"script": "rainbow_buffer", "shape": shape, "n_actions": n, "n_atoms": 51, "batch": B, "slots": slots, "device": str(dev), "reps": a.reps}
+        for leg in legs:
+            for b in ("torch", "fused"):
+                row[f"{leg}_{b}_us"] = round(statistics.median(times[leg][b]), 1)
+            row[f"{leg}_speedup"] = round(row[f"{leg}_torch_us"] / row[f"{leg}_fused_us"], 2)
+        print(json.dumps(row), flush=True)
+
+
 def make(script, O, A, backend, dev, fill=4096):
     td3 = script == "td3"
     torch.manual_seed(1)
@@ -168,6 +293,12 @@ def main():
             continue
         if script == "dqn_atari":
             bench_dqn_atari(a, dev)
+            continue
+        if script == "rainbow":
+            bench_rainbow(a, dev)
+            continue
+        if script == "rainbow_buffer":
+            bench_rainbow_buffer(a, dev)
             continue
         for shape, (O, A) in SHAPES.items():
             learners = {b: make(script, O, A, b, dev) for b in ("torch", "fused")}
