@@ -156,7 +156,7 @@ __global__ __launch_bounds__(256) void dq_update_kernel(OpRing R, const float* _
                 if (r < nr) {
                     const int64_t row = ring_row(R, r0 + r);
                     const float p = z[r * kDqZS + act[r] * na + j];
-                    e = c51_proj_elem(R.rewards[row], R.dones[row], gamma, atoms[j], vmin, vmax, delta_z, na, p);
+                    e = c51_proj_elem(R.rewards[row], R.dones[row], gamma, atoms[j], vmin, vmax, delta_z, na, p, false);
                     if (aux_a) aux_a[(int64_t)(r0 + r) * na + j] = p;
                 }
                 pl[r * kDqPS + j] = e.l;

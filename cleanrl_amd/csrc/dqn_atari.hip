@@ -4,11 +4,13 @@
 //
 //   add      one thread per pixel: the four planes of an (4, 84, 84) stack become one 4-byte store into the channels-last ring.  obs goes
 //            to slot pos, next_obs to (pos + 1) % slots; with one slot only next_obs is written (it would win), so no two threads share a word.
-//   gather   one thread per pixel word: frames (batch_inds, env_inds) and ((batch_inds + 1) % slots, env_inds) into (2M, 84, 84, 4).
+//   gather   one thread per pixel word: frames (batch_inds, env_inds) and ((batch_inds + 1) % slots, env_inds) into (2M, 84, 84, 4)
+//            (qh_gather_kernel<true>, qhead_wg.h).
 //   forward  both heads in one launch, spread over 8-row tiles x 32-output tiles x {online, target}: h's rows sit in LDS, W streams from
-//            L2 through a 32 x 64 LDS tile; thread (row, output) runs its dot product in ascending k.
+//            L2 through a 32 x 64 LDS tile; thread (row, output) runs its dot product in ascending k (qh_fwd_kernel<kDaH>, qhead_wg.h).
 //   row      one workgroup per batch row: the softmax of each action's atoms (one thread per action and network), the target's argmax,
-//            td_target or the projection (one thread per atom), the loss terms, dz of the taken action's atoms and dh (two columns a thread).
+//            td_target or the categorical row (wg_c51_row, qhead_wg.h: one thread per atom), dz of the taken action's atoms and dh (two
+//            columns a thread).
 //   wgrad    one workgroup per output row j: dW[j, :] and db[j] over the batch rows that took j's action, ascending; zeros elsewhere.  One
 //            more workgroup folds the two row scalars in f64 slots (wg_fold_mean).
 //
@@ -16,15 +18,11 @@
 // none uses atomics; every one validates before its first HIP call and takes the stream last.
 #include "common.h"
 #include "dqn_atari_rows.h"
-#include "offpolicy_wg.h"
+#include "qhead_wg.h"
 
 #pragma clang fp contract(off)
 
 namespace mi355ppo {
-
-constexpr int kDaTJ = 32;            // outputs per forward tile
-constexpr int kDaTK = 64;            // k-depth of the staged weight tile
-constexpr int kDaTLd = kDaTK + 1;    // padded: lane j reads word j * 65 + k, 32 different banks
 
 // ---------------------------------------------------------------------------------------------------------------- the ring
 // grid (ceil(N * 7056 / 256), 2 or 1): y + first selects obs (0) / next_obs (1)
@@ -48,54 +46,7 @@ __global__ __launch_bounds__(256) void da_add_kernel(const uint8_t* __restrict__
     }
 }
 
-// grid (ceil(7056 / 256), 2M): frame y < M is the observation, y >= M the next observation of sample y - M
-__global__ __launch_bounds__(256) void da_gather_kernel(const uint32_t* __restrict__ ring, const int64_t* __restrict__ ring_actions,
-                                                        const float* __restrict__ ring_rewards, const float* __restrict__ ring_dones,
-                                                        const int64_t* __restrict__ bi, const int64_t* __restrict__ ei, int64_t slots, int N,
-                                                        uint32_t* __restrict__ frames, int64_t* __restrict__ actions, float* __restrict__ rewards,
-                                                        float* __restrict__ dones, int M) {
-    const int f = blockIdx.y, m = f < M ? f : f - M;
-    const int64_t slot = op_clamp(bi[m], slots);
-    const int e = (int)op_clamp(ei[m], N);
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p < kDaPix) frames[(int64_t)f * kDaPix + p] = ring[da_frame(f < M ? slot : da_next_slot(slot, slots), e, N) + p];
-    if (f < M && p == 0) {
-        actions[m] = ring_actions[slot * N + e];
-        rewards[m] = ring_rewards[slot * N + e];
-        dones[m] = ring_dones[slot * N + e];
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------- the heads
-struct DaHeads {
-    const float *h[2], *w[2], *b[2];           // 0: online on obs, 1: target on next_obs
-};
-
-// z[net][r, j] = b[j] + sum_k h[r, k] * W[j, k].  grid (ceil(J / 32), ceil(M / 8), nets); z: nets x M x J
-__global__ __launch_bounds__(256) void da_fwd_kernel(DaHeads H, float* __restrict__ z, int M, int J) {
-    __shared__ float hs[kOpRows * kDaH], wt[kDaTJ * kDaTLd];
-    const int t = threadIdx.x, net = blockIdx.z, j0 = blockIdx.x * kDaTJ, r0 = blockIdx.y * kOpRows;
-    const float* __restrict__ h = H.h[net];
-    const float* __restrict__ W = H.w[net];
-    for (int i = t; i < kOpRows * kDaH; i += 256) {
-        const int r = i / kDaH;
-        hs[i] = (r0 + r < M) ? h[(int64_t)r0 * kDaH + i] : 0.0f;
-    }
-    const int jj = t & (kDaTJ - 1), r = t / kDaTJ;
-    const float* x = hs + r * kDaH;
-    float acc = 0.0f;
-    for (int k0 = 0; k0 < kDaH; k0 += kDaTK) {
-        __syncthreads();                                    // hs is complete (first pass); the previous tile has been read
-        for (int i = t; i < kDaTJ * kDaTK; i += 256) {
-            const int wj = i / kDaTK, wk = i - wj * kDaTK;
-            wt[wj * kDaTLd + wk] = (j0 + wj < J) ? W[(int64_t)(j0 + wj) * kDaH + k0 + wk] : 0.0f;
-        }
-        __syncthreads();
-        for (int kk = 0; kk < kDaTK; ++kk) acc = op_mac(acc, x[k0 + kk], wt[jj * kDaTLd + kk]);
-    }
-    if (r0 + r < M && j0 + jj < J) z[((int64_t)net * M + r0 + r) * J + j0 + jj] = acc + H.b[net][j0 + jj];
-}
-
 // ws layout (floats): z (2 x M x J) | rows (2 x Mp: loss term | q) | dz (M x na) | act (M ints)
 struct DaWs {
     float *z, *rows, *dz;
@@ -133,45 +84,13 @@ __global__ __launch_bounds__(256) void da_row_kernel(DaWs S, const float* __rest
     const int act = (int)op_clamp(actions[r], n);
     const float rew = rewards[r], done = dones[r];
     if constexpr (C51) {
-        const float delta_z = atoms[1] - atoms[0];
-        if (t < na) {
-            const float p = zt[best * na + t];
-            const C51Proj e = c51_proj_elem(rew, done, gamma, atoms[t], vmin, vmax, delta_z, na, p);
-            pl[t] = e.l;
-            pu[t] = e.u;
-            pdl[t] = e.dml;
-            pdu[t] = e.dmu;
-            if (aux_a) aux_a[(int64_t)r * na + t] = p;
-        }
-        __syncthreads();
-        if (t < na) {
-            const float v = c51_proj_atom(t, pl, pu, pdl, pdu, na);
-            tp[t] = v;
-            if (aux_b) aux_b[(int64_t)r * na + t] = v;
-        }
-        __syncthreads();
-        if (t < na) {
-            const C51Loss e = c51_loss_elem(tp[t], zo[act * na + t], norm);
-            pl[t] = e.term;
-            pdl[t] = e.g;
-            pdu[t] = e.gp;
-        }
-        __syncthreads();
+        const float ns = wg_c51_row({pl, pu, pdl, pdu, tp, dzs, &dotv}, zt + best * na, zo + act * na, atoms, rew, done, gamma, vmin, vmax,
+                                    atoms[1] - atoms[0], na, norm, false, aux_a ? aux_a + (int64_t)r * na : nullptr,
+                                    aux_b ? aux_b + (int64_t)r * na : nullptr);
+        if (t < na) S.dz[(int64_t)r * na + t] = dzs[t];
         if (t == 0) {
-            float s = 0.0f, dot = 0.0f;
-            for (int k = 0; k < na; ++k) {
-                s = s + pl[k];
-                dot = dot + pdu[k];
-            }
-            dotv = dot;
-            S.rows[r] = -s;
+            S.rows[r] = ns;
             S.rows[Mp + r] = qo[act];
-        }
-        __syncthreads();
-        if (t < na) {
-            const float d = c51_dlogit(zo[act * na + t], pdl[t], dotv);
-            dzs[t] = d;
-            S.dz[(int64_t)r * na + t] = d;
         }
     } else {
         if (aux_a && t < n) aux_a[(int64_t)r * n + t] = qt[t];
@@ -200,10 +119,7 @@ __global__ __launch_bounds__(256) void da_wgrad_kernel(DaWs S, const float* __re
     __shared__ float dzj[kDaMaxRows];
     const int t = threadIdx.x, j = blockIdx.x;
     if (j == J) {
-        for (int s = 0; s < 2; ++s) {
-            const float m = wg_fold_mean(S.rows + (int64_t)s * Mp, M, red);
-            if (t == 0) scalars[s] = m;
-        }
+        wg_fold_scalars(S.rows, Mp, M, red, scalars);
         return;
     }
     const int a = j / na, k0 = j - a * na;
@@ -217,7 +133,7 @@ __global__ __launch_bounds__(256) void da_wgrad_kernel(DaWs S, const float* __re
     if (t == 0) db[j] = da_wgrad(acts, dzj, 1, M, a, 0, nullptr, 0);
 }
 
-// actions[r] = argmax_a q[r, a]; z: N x J from da_fwd_kernel.  One workgroup of 64 per row: thread a takes action a's atoms.
+// actions[r] = argmax_a q[r, a]; z: N x J from qh_fwd_kernel.  One workgroup of 64 per row: thread a takes action a's atoms.
 __global__ __launch_bounds__(64) void da_argmax_kernel(float* __restrict__ z, const float* __restrict__ atoms, int64_t* __restrict__ actions,
                                                        float* __restrict__ q_out, int n, int na) {
     __shared__ float qv[kDqMaxAct];
@@ -252,11 +168,8 @@ static int da_update_launch(bool c51, const char* fn, const float* h, const floa
     hipStream_t s = as_stream(stream);
     const int J = n * na, Mp = (int)op_mp(M);
     const DaWs S = da_ws(workspace, M, J, na);
-    DaHeads H;
-    H.h[0] = h, H.w[0] = w, H.b[0] = b;
-    H.h[1] = h_next, H.w[1] = w_target, H.b[1] = b_target;
-    hipLaunchKernelGGL(da_fwd_kernel, dim3((J + kDaTJ - 1) / kDaTJ, op_tiles(M), 2), dim3(256), 0, s, H, S.z, M, J);
-    if (int rc = check_launch("da_fwd_kernel")) return rc;
+    const QhPasses H{{h, h_next}, {w, w_target}, {b, b_target}};              // 0: online on obs, 1: target on next_obs
+    if (int rc = qh_fwd_launch<kDaH>(s, H, 2, S.z, M, J, na)) return rc;
     if (c51)
         hipLaunchKernelGGL(da_row_kernel<true>, dim3(M), dim3(256), 0, s, S, w, atoms, actions, rewards, dones, dh, aux_a, aux_b, M, Mp, n, na,
                            (float)gamma, (float)v_min, (float)v_max, (float)(1.0 / (double)M));
@@ -300,10 +213,8 @@ extern "C" MI355PPO_API int mi355ppo_replay_gather_u8(const uint8_t* ring_frames
     if (int rc = da_ring_shape(fn, slots, n_envs)) return rc;
     MI355_REQUIRE(M >= 1 && M <= kDaMaxRows, MI355PPO_EINVAL, "%s: rows=%d: 1 <= rows <= %d", fn, M, kDaMaxRows);
     MI355_REQUIRE(aligned(ring_frames, 4) && aligned(frames_out, 4), MI355PPO_EALIGN, "%s: the ring and the batch must be 4-byte aligned", fn);
-    hipLaunchKernelGGL(da_gather_kernel, dim3((kDaPix + 255) / 256, 2 * M), dim3(256), 0, as_stream(stream),
-                       reinterpret_cast<const uint32_t*>(ring_frames), ring_actions, ring_rewards, ring_dones, batch_inds, env_inds, slots, n_envs,
-                       reinterpret_cast<uint32_t*>(frames_out), actions_out, rewards_out, dones_out, M);
-    return check_launch("da_gather_kernel");
+    return qh_gather_launch<true>(as_stream(stream), ring_frames, nullptr, ring_actions, ring_rewards, ring_dones, batch_inds, env_inds, slots,
+                                  n_envs, frames_out, actions_out, rewards_out, dones_out, M);
 }
 
 extern "C" MI355PPO_API size_t mi355ppo_dqn_head_act_workspace_bytes(int N, int n_actions, int n_atoms) {
@@ -322,10 +233,7 @@ extern "C" MI355PPO_API int mi355ppo_dqn_head_act_f32(const float* h, const floa
     hipStream_t s = as_stream(stream);
     const int J = n_actions * n_atoms;
     float* z = static_cast<float*>(workspace);
-    DaHeads H;
-    H.h[0] = H.h[1] = h, H.w[0] = H.w[1] = w, H.b[0] = H.b[1] = b;
-    hipLaunchKernelGGL(da_fwd_kernel, dim3((J + kDaTJ - 1) / kDaTJ, op_tiles(N), 1), dim3(256), 0, s, H, z, N, J);
-    if (int rc = check_launch("da_fwd_kernel")) return rc;
+    if (int rc = qh_fwd_launch<kDaH>(s, QhPasses{{h}, {w}, {b}}, 1, z, N, J, n_atoms)) return rc;
     hipLaunchKernelGGL(da_argmax_kernel, dim3(N), dim3(64), 0, s, z, atoms, actions_out, q_out, n_actions, n_atoms);
     return check_launch("da_argmax_kernel");
 }

@@ -1,6 +1,7 @@
 // Row / element math of the Atari DQN / C51 kernels (dqn_atari.hip: dqn_atari.py, c51_atari.py) and their host twins
 // (host_twins.hip): one definition compiled for both sides, so a twin returns the device's bits.  td_target, the softmax, the
-// projection, the loss elements and the argmax are dqn_rows.h's; op_mac / op_clamp are offpolicy_rows.h's.
+// projection, the loss elements, the categorical row and the argmax are dqn_rows.h's; op_mac / op_clamp are offpolicy_rows.h's.  The
+// frame words and the host gather serve Rainbow's two rings too (rainbow_rows.h, rainbow_twins.hip).
 //
 // * The frame ring is ONE u8 array (slots, n_envs, 84, 84, 4), channels-last, as the reference's memory-optimised ReplayBuffer keeps
 //   one observation array: a step's obs goes to slot pos, its next_obs to slot (pos + 1) % slots; a sample's next_obs is the frame at
@@ -11,6 +12,8 @@
 //   over ascending j; dW[a * n_atoms + j, k] adds dz[r, j] * h[r, k] over the rows r with a_r == a in ascending r, db likewise; the rows
 //   of an action no batch row took are zeros.
 #pragma once
+#include <string.h>
+
 #include "dqn_rows.h"
 
 namespace mi355ppo {
@@ -44,6 +47,23 @@ MI355_HD int64_t da_next_slot(int64_t slot, int64_t slots) { return (slot + 1) %
 // one pixel channels-last: plane c of an (4, 84, 84) stack becomes byte c of the word
 MI355_HD uint32_t da_pack(const uint8_t* stack, int p) {
     return (uint32_t)stack[p] | ((uint32_t)stack[kDaPix + p] << 8) | ((uint32_t)stack[2 * kDaPix + p] << 16) | ((uint32_t)stack[3 * kDaPix + p] << 24);
+}
+
+// qh_gather_kernel (qhead_wg.h) on the host: sample m's frame to row m, its next frame to row M + m, and the row's scalars.  aliased:
+// the next frame is ring_a's at da_next_slot; otherwise ring_b's at the same slot.  ei == nullptr: env 0.
+inline void da_gather_host(const uint8_t* ring_a, const uint8_t* ring_b, const int64_t* ring_actions, const float* ring_rewards,
+                           const float* ring_dones, const int64_t* bi, const int64_t* ei, int64_t slots, int N, bool aliased, uint8_t* frames,
+                           int64_t* actions, float* rewards, float* dones, int M) {
+    const size_t fb = (size_t)4 * kDaPix;
+    for (int m = 0; m < M; ++m) {
+        const int64_t slot = op_clamp(bi[m], slots);
+        const int e = ei ? (int)op_clamp(ei[m], N) : 0;
+        memcpy(frames + (size_t)m * fb, ring_a + 4 * da_frame(slot, e, N), fb);
+        memcpy(frames + (size_t)(M + m) * fb, aliased ? ring_a + 4 * da_frame(da_next_slot(slot, slots), e, N) : ring_b + 4 * da_frame(slot, e, N), fb);
+        actions[m] = ring_actions[slot * N + e];
+        rewards[m] = ring_rewards[slot * N + e];
+        dones[m] = ring_dones[slot * N + e];
+    }
 }
 
 // z[j] = b[j] + sum_k h[k] * W[j, k]

@@ -1,6 +1,7 @@
 // Row / element math of the DQN / C51 kernels (dqn.hip: dqn.py, c51.py) and their host twins (host_twins.hip): one definition
 // compiled for both sides, so a twin returns the device's bits.  Tiles, groups, op_mac, op_relu, op_clamp and op_mse_row are
-// offpolicy_rows.h's; op_exp / op_log are sac_rows.h's.
+// offpolicy_rows.h's; op_exp / op_log are sac_rows.h's.  The projection, the loss elements and c51_row_host also serve the Atari heads
+// and Rainbow's (dqn_atari.hip, rainbow.hip and their twins).
 //
 // * QNetwork of both scripts is Linear(O, 120) - ReLU - Linear(120, 84) - ReLU - Linear(84, J), J = n (dqn.py) or n * n_atoms
 //   (c51.py, viewed as (n, n_atoms)); parameters in .parameters() order.
@@ -100,11 +101,14 @@ MI355_HD float dq_softmax_q(const float* z, int na, const float* atoms, float* p
     return q;
 }
 
-// c51.py's projection on one (row, atom j): next_atoms, tz, b, l, u, d_m_l, d_m_u
+// c51.py's projection on one (row, atom j): next_atoms, tz, b, l, u, d_m_l, d_m_u.  l_eq_b: rainbow_atari.py's own (l == b) in place
+// of c51.py's (l == u); the two differ where b rounds to just above n_atoms - 1 (l == u after the clamp, l != b), and gamma is its
+// gamma ** n_step.
 struct C51Proj {
     float l, u, dml, dmu;
 };
-MI355_HD C51Proj c51_proj_elem(float rew, float done, float gamma, float atom, float vmin, float vmax, float delta_z, int na, float p) {
+MI355_HD C51Proj c51_proj_elem(float rew, float done, float gamma, float atom, float vmin, float vmax, float delta_z, int na, float p,
+                               bool l_eq_b) {
     C51Proj e;
     const float next = rew + (gamma * atom) * (1.0f - done);
     const float tz = op_clamp_f(next, vmin, vmax);
@@ -112,7 +116,7 @@ MI355_HD C51Proj c51_proj_elem(float rew, float done, float gamma, float atom, f
     const float top = (float)(na - 1);
     e.l = op_clamp_f(__builtin_floorf(b), 0.0f, top);
     e.u = op_clamp_f(__builtin_ceilf(b), 0.0f, top);
-    e.dml = ((e.u + ((e.l == e.u) ? 1.0f : 0.0f)) - b) * p;
+    e.dml = ((e.u + ((l_eq_b ? e.l == b : e.l == e.u) ? 1.0f : 0.0f)) - b) * p;
     e.dmu = (b - e.l) * p;
     return e;
 }
@@ -142,5 +146,31 @@ MI355_HD C51Loss c51_loss_elem(float tp, float p, float inv_m) {
 }
 // softmax backward on the taken action's atoms
 MI355_HD float c51_dlogit(float p, float g, float dot) { return p * (g - dot); }
+
+// The categorical update of one row in serial form (wg_c51_row of qhead_wg.h on the host): the projection of pnext (the target's
+// pmf at the chosen action) through next_row / target_row (optional outputs), the loss against pred (the online pmf at the taken
+// action) and dq[k] = d loss / d logit k.  scale multiplies the row's gradient; tmp holds 5 * na floats.  Returns the row's loss.
+inline float c51_row_host(const float* pnext, const float* pred, const float* atoms, float rew, float done, float gamma, float vmin, float vmax,
+                          float delta_z, int na, float scale, bool l_eq_b, float* next_row, float* target_row, float* tmp, float* dq) {
+    float *pl = tmp, *pu = pl + na, *pdl = pu + na, *pdu = pdl + na, *tp = pdu + na;
+    for (int j = 0; j < na; ++j) {
+        const C51Proj e = c51_proj_elem(rew, done, gamma, atoms[j], vmin, vmax, delta_z, na, pnext[j], l_eq_b);
+        pl[j] = e.l, pu[j] = e.u, pdl[j] = e.dml, pdu[j] = e.dmu;
+        if (next_row) next_row[j] = pnext[j];
+    }
+    for (int k = 0; k < na; ++k) {
+        tp[k] = c51_proj_atom(k, pl, pu, pdl, pdu, na);
+        if (target_row) target_row[k] = tp[k];
+    }
+    float s = 0.0f, dot = 0.0f;
+    for (int k = 0; k < na; ++k) {
+        const C51Loss e = c51_loss_elem(tp[k], pred[k], scale);
+        pdl[k] = e.g;
+        s = s + e.term;
+        dot = dot + e.gp;
+    }
+    for (int k = 0; k < na; ++k) dq[k] = c51_dlogit(pred[k], pdl[k], dot);
+    return -s;
+}
 
 }  // namespace mi355ppo

@@ -1348,16 +1348,6 @@ void op_wgrad_host(const float* dz, int ds, const float* in, int is, int J, int 
     }
 }
 
-float op_fold_mean_host(const float* v, int M) {
-    double tot = 0.0;
-    for (int t = 0; t < kOpFold; ++t) {
-        double s = 0.0;
-        for (int k = t; k < M; k += kOpFold) s += (double)v[k];
-        tot += s;
-    }
-    return (float)(tot / (double)M);
-}
-
 void op_fold_host(const float* part, int G, int64_t P, float* grads) {
     for (int64_t e = 0; e < P; ++e) {
         float acc = 0.0f;
@@ -1904,7 +1894,7 @@ int dq_update_cpu(const float* ring_obs, const float* ring_next_obs, const float
                     if (r < nr) {
                         const int64_t row = ring(r0 + r);
                         const float pj = T.z[r * ZS + a * na + j];
-                        e = c51_proj_elem(ring_rewards[row], ring_dones[row], gamma, atoms[j], vmin, vmax, delta_z, na, pj);
+                        e = c51_proj_elem(ring_rewards[row], ring_dones[row], gamma, atoms[j], vmin, vmax, delta_z, na, pj, false);
                         if (aux_a) aux_a[(int64_t)(r0 + r) * na + j] = pj;
                     }
                     T.pl[r * PS + j] = e.l;
@@ -2044,7 +2034,7 @@ void da_qvalues_host(float* z, int n, int na, const float* atoms, float* q) {
     for (int a = 0; a < n; ++a) q[a] = (na > 1) ? dq_softmax_q(z + a * na, na, atoms, z + a * na) : z[a];
 }
 
-// da_fwd_kernel, da_row_kernel<C51> and da_wgrad_kernel on the host
+// qh_fwd_kernel<kDaH>, da_row_kernel<C51> and da_wgrad_kernel on the host
 template <bool C51>
 int da_update_cpu(const float* h, const float* h_next, const float* w, const float* b, const float* w_target, const float* b_target,
                   const float* atoms, const int64_t* actions, const float* rewards, const float* dones, float gamma, float vmin, float vmax,
@@ -2062,27 +2052,8 @@ int da_update_cpu(const float* h, const float* h_next, const float* w, const flo
         const int best = dq_argmax(qt, n), a = (int)op_clamp(actions[r], n);
         act[r] = a;
         if constexpr (C51) {
-            float *pl = tmp.data(), *pu = pl + na, *pdl = pu + na, *pdu = pdl + na, *tp = pdu + na;
-            const float delta_z = atoms[1] - atoms[0];
-            for (int j = 0; j < na; ++j) {
-                const float p = t[best * na + j];
-                const C51Proj e = c51_proj_elem(rewards[r], dones[r], gamma, atoms[j], vmin, vmax, delta_z, na, p);
-                pl[j] = e.l, pu[j] = e.u, pdl[j] = e.dml, pdu[j] = e.dmu;
-                if (aux_a) aux_a[(int64_t)r * na + j] = p;
-            }
-            for (int k = 0; k < na; ++k) {
-                tp[k] = c51_proj_atom(k, pl, pu, pdl, pdu, na);
-                if (aux_b) aux_b[(int64_t)r * na + k] = tp[k];
-            }
-            float s = 0.0f, dot = 0.0f;
-            for (int k = 0; k < na; ++k) {
-                const C51Loss e = c51_loss_elem(tp[k], o[a * na + k], norm);
-                pdl[k] = e.g;
-                s = s + e.term;
-                dot = dot + e.gp;
-            }
-            for (int k = 0; k < na; ++k) d[k] = c51_dlogit(o[a * na + k], pdl[k], dot);
-            rows[r] = -s;
+            rows[r] = c51_row_host(t + best * na, o + a * na, atoms, rewards[r], dones[r], gamma, vmin, vmax, atoms[1] - atoms[0], na, norm, false,
+                                   aux_a ? aux_a + (int64_t)r * na : nullptr, aux_b ? aux_b + (int64_t)r * na : nullptr, tmp.data(), d);
         } else {
             if (aux_a)
                 for (int k = 0; k < n; ++k) aux_a[(int64_t)r * n + k] = qt[k];
@@ -2141,16 +2112,8 @@ extern "C" MI355PPO_API int mi355ppo_replay_gather_u8_cpu(const uint8_t* ring_fr
                       dones_out, MI355PPO_EINVAL, "%s: null pointer", fn);
     if (int rc = da_ring_shape(fn, slots, n_envs)) return rc;
     MI355_REQUIRE(M >= 1 && M <= kDaMaxRows, MI355PPO_EINVAL, "%s: rows=%d: 1 <= rows <= %d", fn, M, kDaMaxRows);
-    const size_t fb = (size_t)4 * kDaPix;
-    for (int m = 0; m < M; ++m) {
-        const int64_t slot = op_clamp(batch_inds[m], slots);
-        const int e = (int)op_clamp(env_inds[m], n_envs);
-        memcpy(frames_out + (size_t)m * fb, ring_frames + 4 * da_frame(slot, e, n_envs), fb);
-        memcpy(frames_out + (size_t)(M + m) * fb, ring_frames + 4 * da_frame(da_next_slot(slot, slots), e, n_envs), fb);
-        actions_out[m] = ring_actions[slot * n_envs + e];
-        rewards_out[m] = ring_rewards[slot * n_envs + e];
-        dones_out[m] = ring_dones[slot * n_envs + e];
-    }
+    da_gather_host(ring_frames, nullptr, ring_actions, ring_rewards, ring_dones, batch_inds, env_inds, slots, n_envs, true, frames_out, actions_out,
+                   rewards_out, dones_out, M);
     return MI355PPO_OK;
 }
 

@@ -127,6 +127,17 @@ MI355_HD float op_dmu(float dact, float scale, float t) { return (dact * scale) 
 // args.tau * param + (1 - args.tau) * target_param
 MI355_HD float op_polyak(float p, float t, float tau, float omt) { return tau * p + omt * t; }
 
+// wg_fold_mean (offpolicy_wg.h) on the host, in its order: kOpFold f64 slots, then the slots in order
+inline float op_fold_mean_host(const float* v, int M) {
+    double tot = 0.0;
+    for (int t = 0; t < kOpFold; ++t) {
+        double s = 0.0;
+        for (int k = t; k < M; k += kOpFold) s += (double)v[k];
+        tot += s;
+    }
+    return (float)(tot / (double)M);
+}
+
 // host-side argument check of the device entry points and of their twins
 inline int op_shape(const char* fn, int M, int O, int A) {
     MI355_REQUIRE(M > 0 && O > 0 && O <= kOpMaxObs && A > 0 && A <= kOpMaxAct, MI355PPO_EINVAL,

@@ -1,6 +1,6 @@
 // Workgroup-level device helpers of the off-policy kernels (offpolicy.hip: DDPG / TD3, sac.hip: SAC): one tile of kOpRows rows
-// through a 256-wide layer (forward, head, masked data gradient, weight gradient), the f64 slot fold, the ring gather and the
-// host-side argument checks of the device entry points.  Included by the kernel files only; the row math and the shape check both
+// through a 256-wide layer (forward, head, masked data gradient, weight gradient), the f64 slot fold (wg_fold_scalars: the two row
+// scalars of the Q heads in dqn_atari.hip / rainbow.hip), the ring gather and the host-side argument checks of the device entry points.  Included by the kernel files only; the row math and the shape check both
 // sides share are in offpolicy_rows.h.
 #pragma once
 #include "common.h"
@@ -121,6 +121,14 @@ __device__ float wg_fold_mean(const float* __restrict__ v, int M, double* red) {
         for (int t = 0; t < kOpFold; ++t) tot += red[t];
     __syncthreads();
     return (float)(tot / (double)M);
+}
+
+// scalars[s] = the mean of rows[s * Mp .. s * Mp + M) for the two row scalars of a head update (the extra workgroup of its wgrad kernel)
+__device__ void wg_fold_scalars(const float* __restrict__ rows, int Mp, int M, double* red, float* __restrict__ scalars) {
+    for (int s = 0; s < 2; ++s) {
+        const float m = wg_fold_mean(rows + (int64_t)s * Mp, M, red);
+        if (threadIdx.x == 0) scalars[s] = m;
+    }
 }
 
 // The value of a uniform int behind an empty statement the optimiser cannot see through.  A network's six pointers derived from it

@@ -1,12 +1,13 @@
 // Rainbow (cleanrl/rainbow_atari.py): the prioritized n-step replay buffer in device memory and the noise composition of the four
-// NoisyLinear layers (gfx950).  Row math: rainbow_rows.h.
+// NoisyLinear layers (gfx950).  Row math: rainbow_rows.h.  The gather, the head's forward kernel and its categorical row are the
+// ones dqn_atari.hip uses (qhead_wg.h).
 //
 //   add      one thread per pixel of obs and of next_obs: the four planes of a (4, 84, 84) stack become one 4-byte store into slot
 //            pos of their ring.  Thread 0 of workgroup (0, 0) writes the action, the n-step reward and the done flag, sets the
 //            leaf to max_priority ** alpha, walks its ancestors and bumps size.
 //   sample   ONE workgroup: lane i draws its stratum's value from u[i], walks the tree and computes its weight; the weights' maximum is
 //            folded through LDS and divided out.
-//   gather   one thread per pixel word: the M obs frames, then the M next_obs frames, into (2M, 84, 84, 4).
+//   gather   one thread per pixel word: the M obs frames, then the M next_obs frames, into (2M, 84, 84, 4) (qh_gather_kernel<false>).
 //   update   ONE workgroup: the priorities and the running maximum; the leaves (of duplicate indices the highest batch position
 //            writes); then the ancestors level by level from the deepest tree level, a barrier between levels.  Lanes that share a
 //            parent compute the same sum from the same two words, so the level needs no atomics.
@@ -16,7 +17,7 @@
 // No entry point allocates or synchronises, none uses atomics; every one validates before its first HIP call and takes the stream last.
 #include "common.h"
 #include "rainbow_rows.h"
-#include "offpolicy_wg.h"
+#include "qhead_wg.h"
 
 #pragma clang fp contract(off)
 
@@ -43,23 +44,6 @@ __global__ __launch_bounds__(256) void rb_add_kernel(const uint8_t* __restrict__
         rb_propagate(tree, leaf);
         const int64_t s = size[0] + 1;
         size[0] = s < slots ? s : slots;
-    }
-}
-
-// grid (ceil(7056 / 256), 2M): frame y < M is the observation, y >= M the next observation of sample y - M
-__global__ __launch_bounds__(256) void rb_gather_kernel(const uint32_t* __restrict__ ring_obs, const uint32_t* __restrict__ ring_next,
-                                                        const int64_t* __restrict__ ring_actions, const float* __restrict__ ring_rewards,
-                                                        const float* __restrict__ ring_dones, const int64_t* __restrict__ indices, int64_t slots,
-                                                        uint32_t* __restrict__ frames, int64_t* __restrict__ actions, float* __restrict__ rewards,
-                                                        float* __restrict__ dones, int M) {
-    const int f = blockIdx.y, m = f < M ? f : f - M;
-    const int64_t slot = op_clamp(indices[m], slots);
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p < kDaPix) frames[(int64_t)f * kDaPix + p] = (f < M ? ring_obs : ring_next)[da_frame(slot, 0, 1) + p];
-    if (f < M && p == 0) {
-        actions[m] = ring_actions[slot];
-        rewards[m] = ring_rewards[slot];
-        dones[m] = ring_dones[slot];
     }
 }
 
@@ -147,39 +131,7 @@ __global__ __launch_bounds__(256) void rb_noisy_kernel(RbSegs S, const float* __
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the head
-constexpr int kRbTJ = 32;            // outputs per forward tile
-constexpr int kRbTK = 64;            // k-depth of the staged weight tile
-constexpr int kRbTLd = kRbTK + 1;    // padded: lane j reads word j * 65 + k, 32 different banks
-
-struct RbHeads {
-    const float *h[3], *w[3], *b[3];           // 0: online on obs, 1: online on next_obs, 2: target on next_obs
-};
-
-// z[pass][r, j] = b[j] + sum_k h[r, col0(j) + k] * W[j, k].  grid (ceil(J / 32), ceil(M / 8), passes); z: passes x M x J.  As
-// da_fwd_kernel, with both streams' 512 hidden columns of the 8 rows in LDS (32 KB) and the weight tile beside them (8.3 KB).
-__global__ __launch_bounds__(256) void rb_fwd_kernel(RbHeads H, float* __restrict__ z, int M, int J, int na) {
-    __shared__ float hs[kOpRows * kRbH2], wt[kRbTJ * kRbTLd];
-    const int t = threadIdx.x, pass = blockIdx.z, j0 = blockIdx.x * kRbTJ, r0 = blockIdx.y * kOpRows;
-    const float* __restrict__ h = H.h[pass];
-    const float* __restrict__ W = H.w[pass];
-    for (int i = t; i < kOpRows * kRbH2; i += 256) {
-        const int r = i / kRbH2;
-        hs[i] = (r0 + r < M) ? h[(int64_t)r0 * kRbH2 + i] : 0.0f;
-    }
-    const int jj = t & (kRbTJ - 1), r = t / kRbTJ;
-    const float* x = hs + r * kRbH2 + rb_col0(j0 + jj, na);
-    float acc = 0.0f;
-    for (int k0 = 0; k0 < kRbHid; k0 += kRbTK) {
-        __syncthreads();                                    // hs is complete (first pass); the previous tile has been read
-        for (int i = t; i < kRbTJ * kRbTK; i += 256) {
-            const int wj = i / kRbTK, wk = i - wj * kRbTK;
-            wt[wj * kRbTLd + wk] = (j0 + wj < J) ? W[(int64_t)(j0 + wj) * kRbHid + k0 + wk] : 0.0f;
-        }
-        __syncthreads();
-        for (int kk = 0; kk < kRbTK; ++kk) acc = op_mac(acc, x[k0 + kk], wt[jj * kRbTLd + kk]);
-    }
-    if (r0 + r < M && j0 + jj < J) z[((int64_t)pass * M + r0 + r) * J + j0 + jj] = acc + H.b[pass][j0 + jj];
-}
+// forward: qh_fwd_kernel<kRbH2> (qhead_wg.h); passes 0: online on obs, 1: online on next_obs, 2: target on next_obs
 
 // ws layout (floats): z (3 x M x J) | rows (2 x Mp: weighted loss | q) | dz (M x J)
 struct RbWs {
@@ -222,46 +174,15 @@ __global__ __launch_bounds__(256) void rb_row_kernel(RbWs S, const float* __rest
     const int act = (int)op_clamp(actions[r], n);
     const float rew = rewards[r], done = dones[r], wr = weights[r];
     const float* pred = zs + na + act * na;                                    // online(obs) at the taken action
-    if (t < na) {
-        const float p = zs[2 * kDaMaxOut + na + best * na + t];                // the target's distribution at best
-        const C51Proj e = rb_proj_elem(rew, done, gamma_n, support[t], vmin, vmax, delta_z, na, p);
-        pl[t] = e.l;
-        pu[t] = e.u;
-        pdl[t] = e.dml;
-        pdu[t] = e.dmu;
-        if (next_pmfs) next_pmfs[(int64_t)r * na + t] = p;
-    }
-    __syncthreads();
-    if (t < na) {
-        const float v = c51_proj_atom(t, pl, pu, pdl, pdu, na);
-        tp[t] = v;
-        if (target_pmfs) target_pmfs[(int64_t)r * na + t] = v;
-    }
-    __syncthreads();
-    if (t < na) {
-        const C51Loss e = c51_loss_elem(tp[t], pred[t], wr * inv_m);
-        pl[t] = e.term;
-        pdl[t] = e.g;
-        pdu[t] = e.gp;
-    }
-    __syncthreads();
+    const float ns = wg_c51_row({pl, pu, pdl, pdu, tp, dq, &dotv}, zs + 2 * kDaMaxOut + na + best * na, pred, support, rew, done, gamma_n, vmin,
+                                vmax, delta_z, na, wr * inv_m, true, next_pmfs ? next_pmfs + (int64_t)r * na : nullptr,
+                                target_pmfs ? target_pmfs + (int64_t)r * na : nullptr);      // the target's distribution at best
+    if (t < na) dqn[t] = dq[t] / (float)n;
     if (t == 0) {
-        float s = 0.0f, dot = 0.0f;
-        for (int k = 0; k < na; ++k) {
-            s = s + pl[k];
-            dot = dot + pdu[k];
-        }
-        dotv = dot;
-        loss_per_sample[r] = -s;
-        S.rows[r] = (-s) * wr;
+        loss_per_sample[r] = ns;
+        S.rows[r] = ns * wr;
         S.rows[Mp + r] = qe[act];
         if (best_out) best_out[r] = best;
-    }
-    __syncthreads();
-    if (t < na) {
-        const float d = c51_dlogit(pred[t], pdl[t], dotv);
-        dq[t] = d;
-        dqn[t] = d / (float)n;
     }
     __syncthreads();
     for (int j = t; j < J; j += 256) S.dz[(int64_t)r * J + j] = j < na ? dq[j] : rb_dz_adv(dq, dqn, (j - na) / na, act, (j - na) % na);
@@ -274,17 +195,14 @@ __global__ __launch_bounds__(256) void rb_wgrad_kernel(RbWs S, const float* __re
     __shared__ double red[kOpFold];
     const int t = threadIdx.x, j = blockIdx.x;
     if (j == J) {
-        for (int s = 0; s < 2; ++s) {
-            const float m = wg_fold_mean(S.rows + (int64_t)s * Mp, M, red);
-            if (t == 0) scalars[s] = m;
-        }
+        wg_fold_scalars(S.rows, Mp, M, red, scalars);
         return;
     }
     for (int c = t; c < kRbHid; c += 256) dw[(int64_t)j * kRbHid + c] = rb_wgrad(S.dz, M, J, j, na, h, c);
     if (t == 0) db[j] = rb_wgrad(S.dz, M, J, j, na, nullptr, 0);
 }
 
-// actions[r] = argmax_a sum_k p[r, a, k] * support[k]; z: N x J from rb_fwd_kernel.  One workgroup of 128 per row.
+// actions[r] = argmax_a sum_k p[r, a, k] * support[k]; z: N x J from qh_fwd_kernel.  One workgroup of 128 per row.
 __global__ __launch_bounds__(128) void rb_act_kernel(const float* __restrict__ z, const float* __restrict__ support, int64_t* __restrict__ actions,
                                                      float* __restrict__ q_out, int n, int na) {
     __shared__ float zs[kDaMaxOut], qe[kDqMaxAct];
@@ -338,10 +256,8 @@ extern "C" MI355PPO_API int mi355ppo_rainbow_per_gather_u8(const uint8_t* ring_o
     if (int rc = rb_batch_shape(fn, M)) return rc;
     MI355_REQUIRE(aligned(ring_obs, 4) && aligned(ring_next_obs, 4) && aligned(frames_out, 4), MI355PPO_EALIGN,
                   "%s: the rings and the batch must be 4-byte aligned", fn);
-    hipLaunchKernelGGL(rb_gather_kernel, dim3((kDaPix + 255) / 256, 2 * M), dim3(256), 0, as_stream(stream),
-                       reinterpret_cast<const uint32_t*>(ring_obs), reinterpret_cast<const uint32_t*>(ring_next_obs), ring_actions, ring_rewards,
-                       ring_dones, indices, slots, reinterpret_cast<uint32_t*>(frames_out), actions_out, rewards_out, dones_out, M);
-    return check_launch("rb_gather_kernel");
+    return qh_gather_launch<false>(as_stream(stream), ring_obs, ring_next_obs, ring_actions, ring_rewards, ring_dones, indices, nullptr, slots, 1,
+                                   frames_out, actions_out, rewards_out, dones_out, M);
 }
 
 extern "C" MI355PPO_API int mi355ppo_rainbow_per_update(const int64_t* indices, const float* loss_per_sample, float* tree, float* state,
@@ -392,10 +308,7 @@ extern "C" MI355PPO_API int mi355ppo_rainbow_head_act_f32(const float* h, const 
     hipStream_t s = as_stream(stream);
     const int J = (n_actions + 1) * n_atoms;
     float* z = static_cast<float*>(workspace);
-    RbHeads H;
-    for (int p = 0; p < 3; ++p) H.h[p] = h, H.w[p] = w_out, H.b[p] = b_out;
-    hipLaunchKernelGGL(rb_fwd_kernel, dim3((J + kRbTJ - 1) / kRbTJ, op_tiles(N), 1), dim3(256), 0, s, H, z, N, J, n_atoms);
-    if (int rc = check_launch("rb_fwd_kernel")) return rc;
+    if (int rc = qh_fwd_launch<kRbH2>(s, QhPasses{{h}, {w_out}, {b_out}}, 1, z, N, J, n_atoms)) return rc;
     hipLaunchKernelGGL(rb_act_kernel, dim3(N), dim3(128), 0, s, z, support, actions_out, q_out, n_actions, n_atoms);
     return check_launch("rb_act_kernel");
 }
@@ -420,12 +333,8 @@ extern "C" MI355PPO_API int mi355ppo_rainbow_head_fwd_bwd_f32(const float* h, co
     hipStream_t s = as_stream(stream);
     const int J = (n_actions + 1) * n_atoms, Mp = (int)op_mp(M);
     const RbWs S = rb_ws(workspace, M, J);
-    RbHeads H;
-    H.h[0] = h, H.w[0] = w_out, H.b[0] = b_out;
-    H.h[1] = h_next, H.w[1] = w_out, H.b[1] = b_out;
-    H.h[2] = h_next_target, H.w[2] = w_out_target, H.b[2] = b_out_target;
-    hipLaunchKernelGGL(rb_fwd_kernel, dim3((J + kRbTJ - 1) / kRbTJ, op_tiles(M), 3), dim3(256), 0, s, H, S.z, M, J, n_atoms);
-    if (int rc = check_launch("rb_fwd_kernel")) return rc;
+    const QhPasses H{{h, h_next, h_next_target}, {w_out, w_out, w_out_target}, {b_out, b_out, b_out_target}};
+    if (int rc = qh_fwd_launch<kRbH2>(s, H, 3, S.z, M, J, n_atoms)) return rc;
     hipLaunchKernelGGL(rb_row_kernel, dim3(M), dim3(256), 0, s, S, w_out, support, actions, rewards, dones, weights, dh, loss_per_sample,
                        best_actions_out, next_pmfs_out, target_pmfs_out, M, Mp, n_actions, n_atoms, (float)gamma_n, (float)v_min, (float)v_max,
                        (float)((v_max - v_min) / (double)(n_atoms - 1)), (float)(1.0 / (double)M));

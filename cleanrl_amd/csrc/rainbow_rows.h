@@ -1,5 +1,6 @@
 // Row / element math of the Rainbow kernels (rainbow.hip: rainbow_atari.py's PrioritizedReplayBuffer and NoisyLinear) and their host
-// twins (rainbow_twins.hip): one definition compiled for both sides.  The frame words (da_pack, da_frame) are dqn_atari_rows.h's.
+// twins (rainbow_twins.hip): one definition compiled for both sides.  The frame words (da_pack, da_frame) and the host gather are
+// dqn_atari_rows.h's, the projection (c51_proj_elem with l_eq_b) and the categorical row dqn_rows.h's.
 //
 // * Two u8 frame rings (slots, 84, 84, 4), channels-last: obs and next_obs of the n-step transition, no aliasing between them.
 // * The sum tree is the reference's heap of 2 * slots - 1 f32 words: node p has the children 2p + 1 and 2p + 2, leaf i is node
@@ -125,19 +126,6 @@ MI355_HD void rb_combine_col(float* z, int n, int na, int k) {
     for (int a = 0; a < n; ++a) s = s + z[na + a * na + k];
     const float mean = s / (float)n;
     for (int a = 0; a < n; ++a) z[na + a * na + k] = (z[k] + z[na + a * na + k]) - mean;
-}
-// rainbow_atari.py's projection on one (row, atom j): as c51_proj_elem, with the script's own (l == b) and gamma ** n_step
-MI355_HD C51Proj rb_proj_elem(float rew, float done, float gamma_n, float atom, float vmin, float vmax, float delta_z, int na, float p) {
-    C51Proj e;
-    const float next = rew + (gamma_n * atom) * (1.0f - done);
-    const float tz = op_clamp_f(next, vmin, vmax);
-    const float b = (tz - vmin) / delta_z;
-    const float top = (float)(na - 1);
-    e.l = op_clamp_f(__builtin_floorf(b), 0.0f, top);
-    e.u = op_clamp_f(__builtin_ceilf(b), 0.0f, top);
-    e.dml = ((e.u + ((e.l == b) ? 1.0f : 0.0f)) - b) * p;
-    e.dmu = (b - e.l) * p;
-    return e;
 }
 // d loss / d (advantage logit of action a, atom k): the taken action carries dq, every action -dq / n (the mean's backward)
 MI355_HD float rb_dz_adv(const float* dq, const float* dqn, int a, int act, int k) { return ((a == act) ? dq[k] : 0.0f) - dqn[k]; }

@@ -1,4 +1,5 @@
-// Host-pointer twins of rainbow.hip's entry points: the same row functions (rainbow_rows.h) in plain serial C++.  They live in a
+// Host-pointer twins of rainbow.hip's entry points: the same row functions (rainbow_rows.h; the gather, the categorical row and the
+// f64 slot fold are the headers' da_gather_host, c51_row_host and op_fold_mean_host) in plain serial C++.  They live in a
 // file of their own, beside host_twins.hip, so that the stand-alone sanitizer driver (tools/rainbow_host_check.cpp) links them
 // with api.hip alone.  The tree's ancestors are rebuilt the reference's way here, one _propagate per written leaf; the device
 // rebuilds them level by level, and both leave every inner node equal to the f32 sum of its children's final values.
@@ -69,15 +70,8 @@ extern "C" MI355PPO_API int mi355ppo_rainbow_per_gather_u8_cpu(const uint8_t* ri
                       dones_out, MI355PPO_EINVAL, "%s: null pointer", fn);
     if (int rc = rb_ring_shape(fn, slots)) return rc;
     if (int rc = rb_batch_shape(fn, M)) return rc;
-    const size_t fb = (size_t)4 * kDaPix;
-    for (int m = 0; m < M; ++m) {
-        const int64_t slot = op_clamp(indices[m], slots);
-        memcpy(frames_out + (size_t)m * fb, ring_obs + 4 * da_frame(slot, 0, 1), fb);
-        memcpy(frames_out + (size_t)(M + m) * fb, ring_next_obs + 4 * da_frame(slot, 0, 1), fb);
-        actions_out[m] = ring_actions[slot];
-        rewards_out[m] = ring_rewards[slot];
-        dones_out[m] = ring_dones[slot];
-    }
+    da_gather_host(ring_obs, ring_next_obs, ring_actions, ring_rewards, ring_dones, indices, nullptr, slots, 1, false, frames_out, actions_out,
+                   rewards_out, dones_out, M);
     return MI355PPO_OK;
 }
 
@@ -143,16 +137,6 @@ void rb_row_dists(const float* hrow, const float* w, const float* b, const float
     for (int a = 0; a < n; ++a) qe[a] = dq_softmax_q(z + na + a * na, na, support, z + na + a * na);
 }
 
-float rb_fold_mean_host(const float* v, int M) {                 // wg_fold_mean's order: 256 f64 slots, then the slots in order
-    double tot = 0.0;
-    for (int t = 0; t < kOpFold; ++t) {
-        double s = 0.0;
-        for (int k = t; k < M; k += kOpFold) s += (double)v[k];
-        tot += s;
-    }
-    return (float)(tot / (double)M);
-}
-
 }  // namespace
 
 extern "C" MI355PPO_API int mi355ppo_rainbow_head_act_f32_cpu(const float* h, const float* w_out, const float* b_out, const float* support,
@@ -185,8 +169,7 @@ extern "C" MI355PPO_API int mi355ppo_rainbow_head_fwd_bwd_f32_cpu(const float* h
     const int n = n_actions, na = n_atoms, J = (n + 1) * na;
     const float gn = (float)gamma_n, vmin = (float)v_min, vmax = (float)v_max, delta_z = (float)((v_max - v_min) / (double)(na - 1)),
                 inv_m = (float)(1.0 / (double)M);
-    std::vector<float> zo(J), zn(J), zt(J), qo(n), qn(n), qt(n), pl(na), pu(na), pdl(na), pdu(na), tp(na), dq(na), dqn(na), dz((size_t)M * J),
-        rows((size_t)2 * M);
+    std::vector<float> zo(J), zn(J), zt(J), qo(n), qn(n), qt(n), tmp((size_t)5 * na), dq(na), dqn(na), dz((size_t)M * J), rows((size_t)2 * M);
     for (int r = 0; r < M; ++r) {
         rb_row_dists(h + (size_t)r * kRbH2, w_out, b_out, support, n, na, zo.data(), qo.data());
         rb_row_dists(h_next + (size_t)r * kRbH2, w_out, b_out, support, n, na, zn.data(), qn.data());
@@ -194,31 +177,14 @@ extern "C" MI355PPO_API int mi355ppo_rainbow_head_fwd_bwd_f32_cpu(const float* h
         const int best = dq_argmax(qn.data(), n), act = (int)op_clamp(actions[r], n);
         const float wr = weights[r];
         const float* pred = zo.data() + na + act * na;
-        for (int k = 0; k < na; ++k) {
-            const float p = zt[na + best * na + k];
-            const C51Proj e = rb_proj_elem(rewards[r], dones[r], gn, support[k], vmin, vmax, delta_z, na, p);
-            pl[k] = e.l, pu[k] = e.u, pdl[k] = e.dml, pdu[k] = e.dmu;
-            if (next_pmfs_out) next_pmfs_out[(size_t)r * na + k] = p;
-        }
-        for (int k = 0; k < na; ++k) {
-            tp[k] = c51_proj_atom(k, pl.data(), pu.data(), pdl.data(), pdu.data(), na);
-            if (target_pmfs_out) target_pmfs_out[(size_t)r * na + k] = tp[k];
-        }
-        float s = 0.0f, dot = 0.0f;
-        for (int k = 0; k < na; ++k) {
-            const C51Loss e = c51_loss_elem(tp[k], pred[k], wr * inv_m);
-            pdl[k] = e.g;
-            s = s + e.term;
-            dot = dot + e.gp;
-        }
-        loss_per_sample[r] = -s;
-        rows[r] = (-s) * wr;
+        const float ns = c51_row_host(zt.data() + na + best * na, pred, support, rewards[r], dones[r], gn, vmin, vmax, delta_z, na, wr * inv_m, true,
+                                      next_pmfs_out ? next_pmfs_out + (size_t)r * na : nullptr,
+                                      target_pmfs_out ? target_pmfs_out + (size_t)r * na : nullptr, tmp.data(), dq.data());
+        loss_per_sample[r] = ns;
+        rows[r] = ns * wr;
         rows[(size_t)M + r] = qo[act];
         if (best_actions_out) best_actions_out[r] = best;
-        for (int k = 0; k < na; ++k) {
-            dq[k] = c51_dlogit(pred[k], pdl[k], dot);
-            dqn[k] = dq[k] / (float)n;
-        }
+        for (int k = 0; k < na; ++k) dqn[k] = dq[k] / (float)n;
         for (int j = 0; j < J; ++j) dz[(size_t)r * J + j] = j < na ? dq[j] : rb_dz_adv(dq.data(), dqn.data(), (j - na) / na, act, (j - na) % na);
         for (int c = 0; c < kRbH2; ++c) dh[(size_t)r * kRbH2 + c] = rb_dh(dq.data(), dqn.data(), n, na, act, w_out, c);
     }
@@ -226,6 +192,6 @@ extern "C" MI355PPO_API int mi355ppo_rainbow_head_fwd_bwd_f32_cpu(const float* h
         for (int c = 0; c < kRbHid; ++c) dw_out[(size_t)j * kRbHid + c] = rb_wgrad(dz.data(), M, J, j, na, h, c);
         db_out[j] = rb_wgrad(dz.data(), M, J, j, na, nullptr, 0);
     }
-    for (int s = 0; s < 2; ++s) scalars_out[s] = rb_fold_mean_host(rows.data() + (size_t)s * M, M);
+    for (int s = 0; s < 2; ++s) scalars_out[s] = op_fold_mean_host(rows.data() + (size_t)s * M, M);
     return MI355PPO_OK;
 }

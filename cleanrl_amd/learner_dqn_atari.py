@@ -20,6 +20,9 @@ the ``tau`` loop / ``load_state_dict``                 ``sync_target``: ``mi355p
 
 Backend: ``MI355PPO_OFFPOLICY=torch|fused``, default ``torch``.  Both backends draw ``random``, ``np.random`` and
 the action space's stream in the reference's order.  On the CPU ``fused`` runs the host twins around torch's convolutions.
+
+The flat buffers, the target update, the torch update and the logged scalars are ``learner_dqn.QLearner``'s.  ``check_frames`` and
+``Trunks`` serve ``learner_rainbow.RainbowLearner`` too.
 """
 from __future__ import annotations
 
@@ -27,13 +30,33 @@ import random
 
 import numpy as np
 import torch
-import torch.nn.functional as F
-import torch.optim as optim
 
 from . import ops
-from .learner_offpolicy import DeviceRing, advance
+from .learner_dqn import QLearner
+from .learner_offpolicy import advance
 
 FRAME = (4, 84, 84)
+
+
+def check_frames(envs):
+    if tuple(envs.single_observation_space.shape) != FRAME:
+        raise ValueError(f"the Atari learners take {FRAME} uint8 frame stacks, not {tuple(envs.single_observation_space.shape)}")
+
+
+class Trunks(dict):
+    """One ``cnn.NatureTrunk`` per key, made on first use.  A trunk keeps packed copies of its convolutions' weights: ``bump`` after
+    every write to them."""
+
+    def of(self, key):
+        from . import cnn
+
+        if key not in self:
+            self[key] = cnn.NatureTrunk()
+        return self[key]
+
+    def bump(self):
+        for trunk in self.values():
+            trunk.bufs.weights_version += 1
 
 
 class HostFrameBuffer:
@@ -62,45 +85,24 @@ class HostFrameBuffer:
                 t(self.dones[bi, ei].reshape(-1, 1)), t(self.rewards[bi, ei].reshape(-1, 1)))
 
 
-class AtariDQNLearner(DeviceRing):
+class AtariDQNLearner(QLearner):
     """``c51``: the networks are ``AtariC51Network`` (atoms, ``get_action``) and the update is the categorical one."""
 
     def __init__(self, q_network, target_network, args, envs, device, c51: bool, backend=None):
         self.c51 = bool(c51)
         self.n = int(envs.single_action_space.n)
         self.n_atoms = int(args.n_atoms) if self.c51 else 1
-        if tuple(envs.single_observation_space.shape) != FRAME:
-            raise ValueError(f"the Atari learners take {FRAME} uint8 frame stacks, not {tuple(envs.single_observation_space.shape)}")
-        super().__init__(args, envs, device, backend, 1, act_dtype=np.int64)
-        self.q_network, self.target_network = q_network, target_network
-        self.eps = 0.01 / args.batch_size if self.c51 else 1e-8
-        self.step = 0
+        check_frames(envs)
+        super().__init__(q_network, target_network, args, envs, device, backend, 0.01 / args.batch_size if self.c51 else 1e-8)
         if not self.fused:
-            self.optimizer = optim.Adam(q_network.parameters(), lr=args.learning_rate, eps=self.eps)
             return
-        dev = self.device
-        total = sum(p.numel() for p in q_network.parameters())
-        self._alloc_flat(total)
-        self.target = torch.zeros(total, dtype=torch.float32, device=dev)
-        self._adopt([q_network], self.online)
-        self._adopt([target_network], self.target)
         for p, off in self._param_offsets(q_network):                       # autograd accumulates into the flat gradient
             p.grad = self.grads[off:off + p.numel()].view(p.shape)
         J = self.n * self.n_atoms
-        self.head_off = total - J * ops.DQN_HEAD_HIDDEN - J
-        self.atoms = q_network.atoms.detach().to(dev).contiguous() if self.c51 else None
-        M = int(args.batch_size)
-        self._greedy = torch.zeros(self.N, dtype=torch.int64, device=dev)
-        self._sc = torch.zeros(2, dtype=torch.float32, device=dev)
-        self._dh = torch.zeros((M, ops.DQN_HEAD_HIDDEN), dtype=torch.float32, device=dev)
-        self._trunks = {}
-
-    @staticmethod
-    def _param_offsets(net):
-        off = 0
-        for p in net.parameters():
-            yield p, off
-            off += p.numel()
+        self.head_off = self.online.numel() - J * ops.DQN_HEAD_HIDDEN - J
+        self.atoms = q_network.atoms.detach().to(self.device).contiguous() if self.c51 else None
+        self._dh = torch.zeros((int(args.batch_size), ops.DQN_HEAD_HIDDEN), dtype=torch.float32, device=self.device)
+        self._trunks = Trunks()
 
     def _host_buffer(self, act_dtype):
         return HostFrameBuffer(self.args.buffer_size, self.device, n_envs=self.N)
@@ -143,9 +145,7 @@ class AtariDQNLearner(DeviceRing):
             return seq[:9](frames_hwc.permute(0, 3, 1, 2).float() / 255.0)
         from . import cnn
 
-        trunk = self._trunks.get(id(net))
-        if trunk is None:
-            trunk = self._trunks[id(net)] = cnn.NatureTrunk()
+        trunk = self._trunks.of(id(net))
         feats = trunk(frames_hwc, None, seq[0], seq[2], seq[4])
         return cnn.LinearReLUHwcFn.apply(feats, seq[7].weight, seq[7].bias, trunk.bufs)
 
@@ -241,68 +241,7 @@ class AtariDQNLearner(DeviceRing):
         if adam:
             self.step += 1
             self._adam(self._flats, self.step, a.learning_rate, self.eps)
-            for trunk in self._trunks.values():
-                trunk.bufs.weights_version += 1
+            self._weights_changed(True, False)
 
-    def _train_torch(self, bi, ei):
-        a = self.args
-        observations, actions, next_observations, dones, rewards = self.rb.gather(bi, ei)
-        q_network, target_network = self.q_network, self.target_network
-        if self.c51:
-            with torch.no_grad():
-                _, next_pmfs = target_network.get_action(next_observations)
-                next_atoms = rewards + a.gamma * target_network.atoms * (1 - dones)
-                delta_z = target_network.atoms[1] - target_network.atoms[0]
-                tz = next_atoms.clamp(a.v_min, a.v_max)
-                b = (tz - a.v_min) / delta_z
-                l = b.floor().clamp(0, a.n_atoms - 1)  # noqa: E741
-                u = b.ceil().clamp(0, a.n_atoms - 1)
-                d_m_l = (u + (l == u).float() - b) * next_pmfs
-                d_m_u = (b - l) * next_pmfs
-                target_pmfs = torch.zeros_like(next_pmfs)
-                for i in range(target_pmfs.size(0)):
-                    target_pmfs[i].index_add_(0, l[i].long(), d_m_l[i])
-                    target_pmfs[i].index_add_(0, u[i].long(), d_m_u[i])
-            _, old_pmfs = q_network.get_action(observations, actions.flatten())
-            loss = (-(target_pmfs * old_pmfs.clamp(min=1e-5, max=1 - 1e-5).log()).sum(-1)).mean()
-            old_val = (old_pmfs * q_network.atoms).sum(1)
-        else:
-            with torch.no_grad():
-                target_max, _ = target_network(next_observations).max(dim=1)
-                td_target = rewards.flatten() + a.gamma * target_max * (1 - dones.flatten())
-            old_val = q_network(observations).gather(1, actions).squeeze()
-            loss = F.mse_loss(td_target, old_val)
-        self.optimizer.zero_grad()
-        loss.backward()
-        self.optimizer.step()
-        self.step += 1
-        self.last = ("torch", loss.detach(), old_val.detach())
-        return self
-
-    def sync_target(self):
-        """The target update: dqn_atari.py's ``tau`` loop, c51_atari.py's ``load_state_dict``."""
-        if self.fused:
-            if self.c51:
-                self.target.copy_(self.online)
-            else:
-                self.g.polyak_(self.online, self.target, self.args.tau)
-            for trunk in self._trunks.values():
-                trunk.bufs.weights_version += 1
-            return
-        if self.c51:
-            self.target_network.load_state_dict(self.q_network.state_dict())
-            return
-        tau = self.args.tau
-        for target_network_param, q_network_param in zip(self.target_network.parameters(), self.q_network.parameters()):
-            target_network_param.data.copy_(tau * q_network_param.data + (1.0 - tau) * target_network_param.data)
-
-    def metrics(self) -> dict:
-        """The last update's scalars as Python floats: ``loss`` (``losses/td_loss`` or ``losses/loss``) and ``q_values``."""
-        if self.last[0] == "torch":
-            return {"loss": self.last[1].item(), "q_values": self.last[2].mean().item()}
-        sc = self._sc.tolist()
-        return {"loss": sc[0], "q_values": sc[1]}
-
-    def flat_params(self):
-        """(online, target) flat parameters, detached copies (tests)."""
-        return self._flat([self.q_network]), self._flat([self.target_network])
+    def _weights_changed(self, online: bool, target: bool):
+        self._trunks.bump()

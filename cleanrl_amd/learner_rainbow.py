@@ -17,44 +17,35 @@ the ``tau`` loop                             ``sync_target`` (``polyak_`` on the
 ``MI355PPO_OFFPOLICY`` selects the backend, default ``torch`` (the reference's ops around ``rainbow_replay.HostPrioritizedReplay``).  Both
 consume ``random``, ``np.random`` and torch's generators in the reference's order: two ``reset_noise`` (online, then target: eight
 ``normal_()`` each) and then ``batch_size`` uniform draws per update.  On ``fused`` nothing between the sample and Adam reads the device
-back.
+back.  The flat buffers, the target update and the logged scalars are ``learner_dqn.QLearner``'s, the projection
+is ``learner_dqn.project``, the frame check and the trunk cache ``learner_dqn_atari``'s.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
-import torch.optim as optim
 
 from . import ops
-from .learner_offpolicy import DeviceRing
+from .learner_dqn import QLearner, project
+from .learner_dqn_atari import FRAME, Trunks, check_frames
 from .rainbow_replay import DevicePrioritizedReplay, HostPrioritizedReplay
 
-FRAME = (4, 84, 84)
 ADAM_EPS = 1.5e-4
 FC_OUT, FC_IN = ops.RAINBOW_HEAD_IN, 3136
 
 
-class RainbowLearner(DeviceRing):
+class RainbowLearner(QLearner):
     def __init__(self, q_network, target_network, args, envs, device, backend=None):
         self.n, self.n_atoms = int(envs.single_action_space.n), int(args.n_atoms)
-        if tuple(envs.single_observation_space.shape) != FRAME:
-            raise ValueError(f"the Atari learners take {FRAME} uint8 frame stacks, not {tuple(envs.single_observation_space.shape)}")
+        check_frames(envs)
         self._beta = float(args.prioritized_replay_beta)
-        super().__init__(args, envs, device, backend, 1, act_dtype=np.int64)
-        self.q_network, self.target_network = q_network, target_network
         self.gamma_n = args.gamma**args.n_step
-        self.step = 0
+        super().__init__(q_network, target_network, args, envs, device, backend, ADAM_EPS)
         if not self.fused:
-            self.optimizer = optim.Adam(q_network.parameters(), lr=args.learning_rate, eps=ADAM_EPS)
             return
         dev, n, na = self.device, self.n, self.n_atoms
-        total = sum(p.numel() for p in q_network.parameters())
         self.E, self.P = ops.rainbow_noisy_counts(n, na)
-        self.head_off = total - self.P
-        self._alloc_flat(total)
-        self.target = torch.zeros(total, dtype=torch.float32, device=dev)
-        self._adopt([q_network], self.online)
-        self._adopt([target_network], self.target)
+        self.head_off = self.online.numel() - self.P
         for p, off in self._param_offsets(q_network):                       # the trunk's autograd accumulates into the flat gradient
             if off < self.head_off:
                 p.grad = self.grads[off:off + p.numel()].view(p.shape)
@@ -69,17 +60,10 @@ class RainbowLearner(DeviceRing):
         self.support = q_network.support.detach().to(dev).contiguous()
         M, J = int(args.batch_size), (n + 1) * na
         z = lambda shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
-        self._greedy, self._sc, self._dh, self.loss_per_sample = z(self.N, torch.int64), z(2), z((M, FC_OUT)), z(M)
+        self._dh, self.loss_per_sample = z((M, FC_OUT)), z(M)
         self._J = J
-        self._trunks = {}
+        self._trunks = Trunks()
         self.compose(True, True)
-
-    @staticmethod
-    def _param_offsets(net):
-        off = 0
-        for p in net.parameters():
-            yield p, off
-            off += p.numel()
 
     def _adopt_noise(self, net):
         """The network's noise buffers become views of one flat buffer, in ``reset_noise()``'s order."""
@@ -119,8 +103,9 @@ class RainbowLearner(DeviceRing):
             self.g.rainbow_noisy_compose(self.online[self.head_off:], self.eps_online, self.eff_online, self.n, self.n_atoms)
         if target:
             self.g.rainbow_noisy_compose(self.target[self.head_off:], self.eps_target, self.eff_target, self.n, self.n_atoms)
-        for trunk in self._trunks.values():
-            trunk.bufs.weights_version += 1
+        self._trunks.bump()
+
+    _weights_changed = compose
 
     def _out(self, eff):
         a = FC_OUT * FC_IN + FC_OUT
@@ -133,9 +118,7 @@ class RainbowLearner(DeviceRing):
             return torch.relu(torch.nn.functional.linear(seq(frames_hwc.permute(0, 3, 1, 2).float() / 255.0), W, b))
         from . import cnn
 
-        trunk = self._trunks.get(key)
-        if trunk is None:
-            trunk = self._trunks[key] = cnn.NatureTrunk()
+        trunk = self._trunks.of(key)
         return cnn.LinearReLUHwcFn.apply(trunk(frames_hwc, None, seq[0], seq[2], seq[4]), W, b, trunk.bufs)
 
     # ------------------------------------------------------------------ rollout
@@ -202,7 +185,7 @@ class RainbowLearner(DeviceRing):
         if adam:
             self.step += 1
             self._adam(self._flats, self.step, a.learning_rate, ADAM_EPS)
-            self.compose(True, False)
+            self._weights_changed(True, False)
 
     def _train_torch(self, M, u):
         a, q_network, target_network, dev = self.args, self.q_network, self.target_network, self.device
@@ -218,17 +201,8 @@ class RainbowLearner(DeviceRing):
             next_q_online = torch.sum(next_dist_online * support, dim=2)
             best_actions = torch.argmax(next_q_online, dim=1)
             next_pmfs = next_dist[torch.arange(M), best_actions]
-            next_atoms = rewards + self.gamma_n * support * (1 - dones.float())
-            tz = next_atoms.clamp(q_network.v_min, q_network.v_max)
-            b = (tz - q_network.v_min) / q_network.delta_z
-            l = b.floor().clamp(0, a.n_atoms - 1)  # noqa: E741
-            u_ = b.ceil().clamp(0, a.n_atoms - 1)
-            d_m_l = (u_.float() + (l == b).float() - b) * next_pmfs
-            d_m_u = (b - l) * next_pmfs
-            target_pmfs = torch.zeros_like(next_pmfs)
-            for i in range(target_pmfs.size(0)):
-                target_pmfs[i].index_add_(0, l[i].long(), d_m_l[i])
-                target_pmfs[i].index_add_(0, u_[i].long(), d_m_u[i])
+            target_pmfs = project(next_pmfs, rewards, dones, support, q_network.delta_z, self.gamma_n, q_network.v_min, q_network.v_max, a.n_atoms,
+                                  True)
         dist = q_network(observations)
         pred_dist = dist.gather(1, actions.unsqueeze(-1).expand(-1, -1, a.n_atoms)).squeeze(1)
         log_pred = torch.log(pred_dist.clamp(min=1e-5, max=1 - 1e-5))
@@ -243,24 +217,3 @@ class RainbowLearner(DeviceRing):
         self.loss_per_sample = loss_per_sample.detach()
         self.last = ("torch", loss.detach(), q_values.detach(), data["indices"], data["weights"])
         return self
-
-    def sync_target(self):
-        """The reference's ``tau`` loop over the parameters (the noise buffers are not parameters and stay)."""
-        tau = self.args.tau
-        if self.fused:
-            self.g.polyak_(self.online, self.target, tau)
-            self.compose(False, True)
-            return
-        for target_param, param in zip(self.target_network.parameters(), self.q_network.parameters()):
-            target_param.data.copy_(tau * param.data + (1.0 - tau) * target_param.data)
-
-    def metrics(self) -> dict:
-        """The last update's scalars as Python floats: ``loss`` (``losses/td_loss``) and ``q_values``."""
-        if self.last[0] == "torch":
-            return {"loss": self.last[1].item(), "q_values": self.last[2].mean().item()}
-        sc = self._sc.tolist()
-        return {"loss": sc[0], "q_values": sc[1]}
-
-    def flat_params(self):
-        """(online, target) flat parameters, detached copies (tests)."""
-        return self._flat([self.q_network]), self._flat([self.target_network])

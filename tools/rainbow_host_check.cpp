@@ -2,13 +2,15 @@
 // sanitizers: its own main, every buffer a heap allocation of exactly the size the C ABI names, capacities 1, 3 and 37 (no level,
 // leaves at two depths, several levels), batches 1, 5 and 32 with duplicate and out-of-range indices.  It checks what it can without a
 // reference: the rings hold the last transition written to each slot, every inner node is the f32 sum of its children, sampled
-// indices lie in the ring, the largest weight is 1.
+// indices lie in the ring, the largest weight is 1.  Then the noisy layers, the dueling head at (rows, actions, atoms) = (5, 6, 5) -- both
+// pmfs of every row sum to 1 -- and the gather on its own.
 //
 //   hipcc -x hip --cuda-host-only -std=c++20 -ffp-contract=off -g -O1 -Xarch_host -fsanitize=address,undefined \
 //       -Xarch_host -fno-sanitize-recover=undefined -Iinclude -Icleanrl_amd/csrc tools/rainbow_host_check.cpp \
 //       cleanrl_amd/csrc/rainbow_twins.hip cleanrl_amd/csrc/api.hip -o tools/rainbow_host_check && tools/rainbow_host_check
 //
 // (without the three -Xarch_host flags: the plain build that tests/test_rainbow_twins.py runs).  Never loaded into python.
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -103,6 +105,53 @@ int run_noisy(int n, int na) {
     return 0;
 }
 
+// the dueling head's twins on heap buffers of exactly the ABI's sizes: rows that are done and not, rewards past both clamps
+int run_head(int M, int n, int na) {
+    const int64_t slots = 0;
+    const int B = M;
+    const int J = (n + 1) * na, H2 = 1024, HID = 512;
+    std::vector<float> h((size_t)M * H2), hn(h.size()), hnt(h.size()), w((size_t)J * HID), b(J), wt(w.size()), bt(J), support(na), rew(M), done(M),
+        wts(M), dh(h.size()), dw(w.size()), db(J), sc(2), lps(M), npm((size_t)M * na), tpm((size_t)M * na), q((size_t)M * n);
+    std::vector<int64_t> actions(M), best(M), greedy(M);
+    for (auto* v : {&h, &hn, &hnt}) for (auto& x : *v) x = (float)rnd01();
+    for (auto* v : {&w, &b, &wt, &bt}) for (auto& x : *v) x = (float)(rnd01() - 0.5) * 0.1f;
+    for (int k = 0; k < na; ++k) support[k] = -10.0f + 20.0f * k / (na - 1);
+    for (int r = 0; r < M; ++r) actions[r] = r == 0 ? n + 2 : rnd() % n, rew[r] = (float)(rnd01() - 0.5) * 60.0f, done[r] = (float)(r & 1), wts[r] = 0.1f + (float)rnd01();
+    CHECK(mi355ppo_rainbow_head_act_f32_cpu(h.data(), w.data(), b.data(), support.data(), greedy.data(), q.data(), M, n, na) == 0);
+    CHECK(mi355ppo_rainbow_head_fwd_bwd_f32_cpu(h.data(), hn.data(), hnt.data(), w.data(), b.data(), wt.data(), bt.data(), support.data(), actions.data(),
+                                                rew.data(), done.data(), wts.data(), 0.970299, -10.0, 10.0, dh.data(), dw.data(), db.data(), sc.data(),
+                                                lps.data(), best.data(), npm.data(), tpm.data(), M, n, na) == 0);
+    for (int r = 0; r < M; ++r) {
+        float sn = 0.0f, st = 0.0f;
+        for (int k = 0; k < na; ++k) sn += npm[(size_t)r * na + k], st += tpm[(size_t)r * na + k];
+        CHECK(sn > 0.9999f && sn < 1.0001f && st > 0.9999f && st < 1.0001f);       // the projection keeps the mass
+        CHECK(greedy[r] >= 0 && greedy[r] < n && best[r] >= 0 && best[r] < n && lps[r] > 0.0f);
+    }
+    CHECK(sc[0] > 0.0f && sc[1] == sc[1]);
+    return 0;
+}
+
+// the gather twin on its own: two slots, indices on both sides of the ring
+int run_gather() {
+    const int64_t slots = 2;
+    const int B = 3;
+    std::vector<uint8_t> ring_obs((size_t)slots * kFrame), ring_next(ring_obs.size()), frames((size_t)2 * B * kFrame);
+    for (auto& v : ring_obs) v = (uint8_t)rnd();
+    for (auto& v : ring_next) v = (uint8_t)rnd();
+    std::vector<int64_t> ring_act{3, 7}, idx{1, 5, -3}, act_out(B);
+    std::vector<float> ring_rew{0.5f, -1.0f}, ring_done{0.0f, 1.0f}, rew_out(B), done_out(B);
+    CHECK(mi355ppo_rainbow_per_gather_u8_cpu(ring_obs.data(), ring_next.data(), ring_act.data(), ring_rew.data(), ring_done.data(), idx.data(), slots,
+                                             frames.data(), act_out.data(), rew_out.data(), done_out.data(), B) == 0);
+    const int64_t want[3] = {1, 1, 0};
+    for (int m = 0; m < B; ++m) {
+        CHECK(std::equal(frames.begin() + (size_t)m * kFrame, frames.begin() + (size_t)(m + 1) * kFrame, ring_obs.begin() + (size_t)want[m] * kFrame));
+        CHECK(std::equal(frames.begin() + (size_t)(B + m) * kFrame, frames.begin() + (size_t)(B + m + 1) * kFrame,
+                         ring_next.begin() + (size_t)want[m] * kFrame));
+        CHECK(act_out[m] == ring_act[want[m]] && rew_out[m] == ring_rew[want[m]] && done_out[m] == ring_done[want[m]]);
+    }
+    return 0;
+}
+
 }  // namespace
 
 int main() {
@@ -113,6 +162,7 @@ int main() {
             for (double alpha : {0.5, 0.6})
                 if (run(slots, B, alpha)) return 1;
     if (run_noisy(2, 2) || run_noisy(6, 5) || run_noisy(9, 101)) return 1;
+    if (run_head(5, 6, 5) || run_gather()) return 1;
     printf("rainbow host check: ok\n");
     return 0;
 }
