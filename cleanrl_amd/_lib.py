@@ -263,6 +263,20 @@ SIGNATURES = {
     "mi355ppo_rainbow_head_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mi355ppo_rainbow_head_fwd_bwd_f32": (c_int, [_P] * 12 + [c_double] * 3 + [_P] * 8 + [c_int] * 3 + [_P, c_size_t, _P]),
     "mi355ppo_rainbow_head_fwd_bwd_f32_cpu": (c_int, [_P] * 12 + [c_double] * 3 + [_P] * 8 + [c_int] * 3),
+    # Discrete SAC on Atari (added under ABI 2.7.1, csrc/sac_atari.hip)
+    "mi355ppo_replay_add2_u8": (c_int, [_P] * 10 + [c_int64, c_int64, c_int, _P]),
+    "mi355ppo_replay_add2_u8_cpu": (c_int, [_P] * 10 + [c_int64, c_int64, c_int]),
+    "mi355ppo_replay_gather2_u8": (c_int, [_P] * 7 + [c_int64, c_int] + [_P] * 4 + [c_int, _P]),
+    "mi355ppo_replay_gather2_u8_cpu": (c_int, [_P] * 7 + [c_int64, c_int] + [_P] * 4 + [c_int]),
+    "mi355ppo_sacd_head_act_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "mi355ppo_sacd_head_act_f32": (c_int, [_P] * 6 + [c_int] * 3 + [_P, c_size_t, _P]),
+    "mi355ppo_sacd_head_act_f32_cpu": (c_int, [_P] * 6 + [c_int] * 3),
+    "mi355ppo_sacd_critic_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "mi355ppo_sacd_critic_fwd_bwd_f32": (c_int, [_P] * 19 + [c_double] + [_P] * 9 + [c_int] * 3 + [_P, c_size_t, _P]),
+    "mi355ppo_sacd_critic_fwd_bwd_f32_cpu": (c_int, [_P] * 19 + [c_double] + [_P] * 9 + [c_int] * 3),
+    "mi355ppo_sacd_actor_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "mi355ppo_sacd_actor_fwd_bwd_f32": (c_int, [_P] * 10 + [c_double] + [_P] * 5 + [c_int] * 3 + [_P, c_size_t, _P]),
+    "mi355ppo_sacd_actor_fwd_bwd_f32_cpu": (c_int, [_P] * 10 + [c_double] + [_P] * 5 + [c_int] * 3),
 }
 
 ABI_VERSION = 271       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)

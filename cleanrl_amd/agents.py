@@ -1437,3 +1437,66 @@ class NoisyDuelingDistributionalNetwork(nn.Module):
     def reset_noise(self):
         for layer in self.noisy_layers():
             layer.reset_noise()
+
+
+def _kaiming_init(layer, bias_const=0.0):
+    """sac_atari.py's ``layer_init``: ``kaiming_normal_`` weights, constant biases."""
+    nn.init.kaiming_normal_(layer.weight)
+    torch.nn.init.constant_(layer.bias, bias_const)
+    return layer
+
+
+def _sac_atari_conv(channels):
+    """The convolutions of sac_atari.py's two network classes: the third ReLU is a functional call after ``Flatten``, not a module."""
+    return nn.Sequential(
+        _kaiming_init(nn.Conv2d(channels, 32, kernel_size=8, stride=4)),
+        nn.ReLU(),
+        _kaiming_init(nn.Conv2d(32, 64, kernel_size=4, stride=2)),
+        nn.ReLU(),
+        _kaiming_init(nn.Conv2d(64, 64, kernel_size=3, stride=1)),
+        nn.Flatten(),
+    )
+
+
+class AtariSoftQNetwork(nn.Module):
+    """sac_atari.py's ``SoftQNetwork``: ``conv`` / ``fc1`` / ``fc_q``; ``x / 255.0`` is part of the network."""
+
+    def __init__(self, envs):
+        super().__init__()
+        obs_shape = envs.single_observation_space.shape
+        self.conv = _sac_atari_conv(obs_shape[0])
+        with torch.inference_mode():
+            output_dim = self.conv(torch.zeros(1, *obs_shape)).shape[1]
+        self.fc1 = _kaiming_init(nn.Linear(output_dim, 512))
+        self.fc_q = _kaiming_init(nn.Linear(512, envs.single_action_space.n))
+
+    def forward(self, x):
+        x = F.relu(self.conv(x / 255.0))
+        x = F.relu(self.fc1(x))
+        return self.fc_q(x)
+
+
+class AtariSACActor(nn.Module):
+    """sac_atari.py's ``Actor``: ``conv`` / ``fc1`` / ``fc_logits``; ``get_action`` divides by 255, ``forward`` does not."""
+
+    def __init__(self, envs):
+        super().__init__()
+        obs_shape = envs.single_observation_space.shape
+        self.conv = _sac_atari_conv(obs_shape[0])
+        with torch.inference_mode():
+            output_dim = self.conv(torch.zeros(1, *obs_shape)).shape[1]
+        self.fc1 = _kaiming_init(nn.Linear(output_dim, 512))
+        self.fc_logits = _kaiming_init(nn.Linear(512, envs.single_action_space.n))
+
+    def forward(self, x):
+        x = F.relu(self.conv(x))
+        x = F.relu(self.fc1(x))
+        return self.fc_logits(x)
+
+    def get_action(self, x):
+        logits = self(x / 255.0)
+        policy_dist = Categorical(logits=logits)
+        action = policy_dist.sample()
+        action_probs = policy_dist.probs
+        log_prob = F.log_softmax(logits, dim=1)
+        return action, log_prob, action_probs

@@ -17,7 +17,7 @@ import ctypes
 import torch
 
 from . import _lib
-from .ops import ATARI_FRAME, IMPALA_CHANNELS, _lstm_dims, _ptr_array, dqn_counts, dqn_head_limits_ok, dqn_limits_ok, offpolicy_counts, pqn_param_count, radam_schedule, rainbow_head_limits_ok, rainbow_new_buffer, rainbow_noisy_counts, rainbow_noisy_limits_ok, _rainbow_head, _rainbow_head_update_args, sac_actor_count, trxl_dims  # noqa: F401  (one definition for both modules)
+from .ops import ATARI_FRAME, IMPALA_CHANNELS, _lstm_dims, _ptr_array, dqn_counts, dqn_head_limits_ok, dqn_limits_ok, offpolicy_counts, pqn_param_count, radam_schedule, rainbow_head_limits_ok, rainbow_new_buffer, rainbow_noisy_counts, rainbow_noisy_limits_ok, _rainbow_head, _rainbow_head_update_args, sac_actor_count, sacd_limits_ok, _frame_ring2, _sacd_heads, trxl_dims  # noqa: F401  (one definition for both modules)
 
 LOSS_SCALARS = 7
 
@@ -774,3 +774,55 @@ def rainbow_head_fwd_bwd(h, h_next, h_next_target, w_out, b_out, w_out_target, b
               _p(support), _p(actions), _p(rewards), _p(dones), _p(weights), float(gamma_n), float(v_min), float(v_max), _p(dh), _p(dw_out),
               _p(db_out), _p(scalars), _p(loss_per_sample), _p(best_actions_out), _p(next_pmfs_out), _p(target_pmfs_out), M, int(n_actions), na)
     return scalars
+
+
+# ------------------------------------------------------------------------------------------- discrete SAC on Atari twins (csrc/sac_atari_twins.hip)
+def replay_add2_u8(ring, pos, obs, next_obs, actions, rewards, dones):
+    slots, N = _frame_ring2(ring, _host_chk)
+    H, W, C = ATARI_FRAME
+    _lib.call("mi355ppo_replay_add2_u8_cpu", _in(obs, torch.uint8, (N, C, H, W), "obs"), _in(next_obs, torch.uint8, (N, C, H, W), "next_obs"),
+              _in(actions, torch.int64, (N,), "actions"), _in(rewards, torch.float32, (N,), "rewards"), _in(dones, torch.float32, (N,), "dones"),
+              *[_p(t) for t in ring], int(pos), slots, N)
+
+
+def replay_gather2_u8(ring, batch_inds, env_inds, frames_out, actions_out, rewards_out, dones_out):
+    slots, N = _frame_ring2(ring, _host_chk)
+    (M,) = batch_inds.shape
+    H, W, C = ATARI_FRAME
+    _lib.call("mi355ppo_replay_gather2_u8_cpu", *[_p(t) for t in ring], _in(batch_inds, torch.int64, (M,), "batch_inds"),
+              _in(env_inds, torch.int64, (M,), "env_inds"), slots, N, _out(frames_out, torch.uint8, 2 * M * H * W * C, "frames_out"),
+              _out(actions_out, torch.int64, M, "actions_out"), _out(rewards_out, torch.float32, M, "rewards_out"),
+              _out(dones_out, torch.float32, M, "dones_out"), M)
+    return frames_out
+
+
+def sacd_head_act(h, w, b, noise_exp1, actions_out, probs_out=None):
+    N, hidden, n = _sacd_heads((h,), ((w, b),), _host_chk)
+    _lib.call("mi355ppo_sacd_head_act_f32_cpu", _p(h), _p(w), _p(b), _in(noise_exp1, torch.float32, (N, n), "noise_exp1"),
+              _out(actions_out, torch.int64, N, "actions_out"), _opt_out(probs_out, N * n, "probs_out"), N, hidden, n)
+    return actions_out
+
+
+def sacd_critic_fwd_bwd(hs, heads, actions, rewards, dones, alpha, gamma, dhs, grads, scalars, v_out=None, y_out=None):
+    M, hidden, n = _sacd_heads(hs, heads, _host_chk)
+    if len(hs) != 5:
+        raise ValueError(f"the critic update takes five heads, got {len(hs)}")
+    outs = [_out(dhs[0], torch.float32, M * hidden, "dh1"), _out(dhs[1], torch.float32, M * hidden, "dh2")]
+    for i in range(2):
+        outs += [_out(grads[i][0], torch.float32, n * hidden, f"dw{i + 1}"), _out(grads[i][1], torch.float32, n, f"db{i + 1}")]
+    _lib.call("mi355ppo_sacd_critic_fwd_bwd_f32_cpu", *[_p(h) for h in hs], *[_p(t) for wb in heads for t in wb],
+              _in(actions, torch.int64, (M,), "actions"), _in(rewards, torch.float32, (M,), "rewards"), _in(dones, torch.float32, (M,), "dones"),
+              _in(alpha, torch.float32, (1,), "alpha"), float(gamma), *outs, _out(scalars, torch.float32, 4, "scalars"),
+              _opt_out(v_out, M, "v_out"), _opt_out(y_out, M, "y_out"), M, hidden, n)
+    return scalars
+
+
+def sacd_actor_fwd_bwd(hs, heads, alpha, target_entropy, dh, dw, db, entropy_rows, actor_loss):
+    M, hidden, n = _sacd_heads(hs, heads, _host_chk)
+    if len(hs) != 3:
+        raise ValueError(f"the actor update takes three heads, got {len(hs)}")
+    _lib.call("mi355ppo_sacd_actor_fwd_bwd_f32_cpu", *[_p(h) for h in hs], *[_p(t) for wb in heads for t in wb],
+              _in(alpha, torch.float32, (1,), "alpha"), float(target_entropy), _out(dh, torch.float32, M * hidden, "dh"),
+              _out(dw, torch.float32, n * hidden, "dw"), _out(db, torch.float32, n, "db"), _out(entropy_rows, torch.float32, M, "entropy_rows"),
+              _out(actor_loss, torch.float32, 1, "actor_loss"), M, hidden, n)
+    return actor_loss

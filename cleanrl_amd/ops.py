@@ -32,6 +32,7 @@ __all__ = [
     "dqn_head_limits_ok", "replay_add_u8", "replay_gather_u8", "dqn_head_act", "dqn_head_td_fwd_bwd", "c51_head_fwd_bwd",
     "rainbow_noisy_limits_ok", "rainbow_noisy_counts", "rainbow_new_buffer", "rainbow_per_add_u8", "rainbow_per_sample", "rainbow_per_gather_u8",
     "rainbow_per_update", "rainbow_noisy_compose", "rainbow_noisy_grad", "rainbow_head_limits_ok", "rainbow_head_act", "rainbow_head_fwd_bwd",
+    "sacd_limits_ok", "replay_add2_u8", "replay_gather2_u8", "sacd_head_act", "sacd_critic_fwd_bwd", "sacd_actor_fwd_bwd",
 ]
 
 LOSS_SCALAR_NAMES = ("loss", "pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac")
@@ -1901,3 +1902,124 @@ def rainbow_head_fwd_bwd(h, h_next, h_next_target, w_out, b_out, w_out_target, b
             _ptr(dh), _ptr(dw_out), _ptr(db_out), _ptr(scalars), _ptr(loss_per_sample), _ptr(best_actions_out), _ptr(next_pmfs_out),
             _ptr(target_pmfs_out), M, int(n_actions), na, _ptr(ws), ws.numel())
     return scalars
+
+
+# ------------------------------------------------------------------------------------------- discrete SAC on Atari (csrc/sac_atari.hip)
+def sacd_limits_ok(n_actions: int, rows: int = 1) -> bool:
+    """What the fused discrete-SAC heads take (anything else is ``MI355PPO_EINVAL`` from the C ABI)."""
+    return dqn_head_limits_ok(n_actions, 1, rows)
+
+
+def _frame_ring2(ring, chk=None):
+    """ring = (obs frames, next_obs frames (slots, n_envs, 84, 84, 4) u8, actions (slots, n_envs) int64, rewards, dones (slots, n_envs)
+    f32) -> (slots, N)."""
+    chk = chk or _chk
+    obs, nxt, act, rew, done = ring
+    slots, N = obs.shape[:2]
+    chk(obs, torch.uint8, "ring obs", (slots, N) + ATARI_FRAME)
+    chk(nxt, torch.uint8, "ring next_obs", (slots, N) + ATARI_FRAME)
+    chk(act, torch.int64, "ring actions", (slots, N))
+    chk(rew, torch.float32, "ring rewards", (slots, N))
+    chk(done, torch.float32, "ring dones", (slots, N))
+    return slots, N
+
+
+def replay_add2_u8(ring, pos: int, obs, next_obs, actions, rewards, dones):
+    """The plain ``ReplayBuffer.add`` of sac_atari.py: ``obs`` / ``next_obs`` (N, 4, 84, 84) u8 channels-last into slot ``pos`` of the
+    obs ring and of the next_obs ring, actions / rewards / dones into slot ``pos`` (one launch)."""
+    slots, N = _frame_ring2(ring)
+    H, W, C = ATARI_FRAME
+    _chk(obs, torch.uint8, "obs", (N, C, H, W))
+    _chk(next_obs, torch.uint8, "next_obs", (N, C, H, W))
+    _chk(actions, torch.int64, "actions", (N,))
+    _chk(rewards, torch.float32, "rewards", (N,))
+    _chk(dones, torch.float32, "dones", (N,))
+    _launch("mi355ppo_replay_add2_u8", obs.device, _ptr(obs), _ptr(next_obs), _ptr(actions), _ptr(rewards), _ptr(dones), *[_ptr(t) for t in ring],
+            int(pos), slots, N)
+
+
+def replay_gather2_u8(ring, batch_inds, env_inds, frames_out, actions_out, rewards_out, dones_out):
+    """A batch out of the two frame rings in one launch: frames_out (2M, 84, 84, 4) u8 = the M observation stacks, then the M next
+    observation stacks of the same slots; actions_out (M,) int64, rewards_out / dones_out (M,) f32."""
+    slots, N = _frame_ring2(ring)
+    M = _batch_inds(batch_inds, env_inds)
+    _chk(frames_out, torch.uint8, "frames_out", (2 * M,) + ATARI_FRAME)
+    _chk(actions_out, torch.int64, "actions_out", (M,))
+    _chk(rewards_out, torch.float32, "rewards_out", (M,))
+    _chk(dones_out, torch.float32, "dones_out", (M,))
+    _launch("mi355ppo_replay_gather2_u8", batch_inds.device, *[_ptr(t) for t in ring], _ptr(batch_inds), _ptr(env_inds), slots, N,
+            _ptr(frames_out), _ptr(actions_out), _ptr(rewards_out), _ptr(dones_out), M)
+    return frames_out
+
+
+def _sacd_heads(hs, heads, chk=None):
+    """``hs``: the heads' inputs (rows, 512); ``heads``: one (w (n, 512), b (n,)) per input -> (rows, hidden, n)."""
+    chk = chk or _chk
+    M, hidden = hs[0].shape
+    n = heads[0][1].numel()
+    if len(hs) != len(heads):
+        raise ValueError(f"{len(hs)} inputs for {len(heads)} heads")
+    for i, (h, (w, b)) in enumerate(zip(hs, heads)):
+        chk(h, torch.float32, f"h[{i}]", (M, hidden))
+        chk(w, torch.float32, f"w[{i}]", (n, hidden))
+        chk(b, torch.float32, f"b[{i}]", (n,))
+    return M, hidden, n
+
+
+def sacd_head_act(h, w, b, noise_exp1, actions_out, probs_out=None):
+    """``Actor.get_action``'s sample on ``h`` (N, 512): ``Linear(512, n)``, the softmax and argmax ``probs / noise_exp1`` (the caller's
+    Exp(1) draws (N, n)) -> actions_out (N,) int64; probs_out (N, n) optional."""
+    N, hidden, n = _sacd_heads((h,), ((w, b),))
+    _chk(noise_exp1, torch.float32, "noise_exp1", (N, n))
+    _chk(actions_out, torch.int64, "actions_out", (N,))
+    if probs_out is not None:
+        _chk(probs_out, torch.float32, "probs_out", (N, n))
+    ws = _workspace(h.device, _lib.load().mi355ppo_sacd_head_act_workspace_bytes(N, n))
+    _launch("mi355ppo_sacd_head_act_f32", h.device, _ptr(h), _ptr(w), _ptr(b), _ptr(noise_exp1), _ptr(actions_out), _ptr(probs_out), N, hidden, n,
+            _ptr(ws), ws.numel())
+    return actions_out
+
+
+def sacd_critic_fwd_bwd(hs, heads, actions, rewards, dones, alpha, gamma: float, dhs, grads, scalars, v_out=None, y_out=None):
+    """sac_atari.py's critic update behind the trunks in four launches.  ``hs`` = (qf1, qf2 on obs; actor, qf1_target, qf2_target on
+    next_obs), ``heads`` their (w, b) in that order; ``alpha`` (1,) in device memory.  OVERWRITES ``dhs`` = (dh1, dh2) (M, 512) and
+    ``grads`` = ((dw1, db1), (dw2, db2)); scalars (4,) = {qf1_loss, qf2_loss, mean qf1_a_values, mean qf2_a_values}."""
+    M, hidden, n = _sacd_heads(hs, heads)
+    if len(hs) != 5:
+        raise ValueError(f"the critic update takes five heads, got {len(hs)}")
+    _chk(actions, torch.int64, "actions", (M,))
+    _chk(rewards, torch.float32, "rewards", (M,))
+    _chk(dones, torch.float32, "dones", (M,))
+    _chk(alpha, torch.float32, "alpha", (1,))
+    for i in range(2):
+        _chk(dhs[i], torch.float32, f"dh{i + 1}", (M, hidden))
+        _chk(grads[i][0], torch.float32, f"dw{i + 1}", (n, hidden))
+        _chk(grads[i][1], torch.float32, f"db{i + 1}", (n,))
+    _chk(scalars, torch.float32, "scalars", (4,))
+    for t, nm in ((v_out, "v_out"), (y_out, "y_out")):
+        if t is not None:
+            _chk(t, torch.float32, nm, (M,))
+    ws = _workspace(hs[0].device, _lib.load().mi355ppo_sacd_critic_workspace_bytes(M, n))
+    _launch("mi355ppo_sacd_critic_fwd_bwd_f32", hs[0].device, *[_ptr(h) for h in hs], *[_ptr(t) for wb in heads for t in wb], _ptr(actions),
+            _ptr(rewards), _ptr(dones), _ptr(alpha), float(gamma), _ptr(dhs[0]), _ptr(dhs[1]), *[_ptr(t) for wb in grads for t in wb],
+            _ptr(scalars), _ptr(v_out), _ptr(y_out), M, hidden, n, _ptr(ws), ws.numel())
+    return scalars
+
+
+def sacd_actor_fwd_bwd(hs, heads, alpha, target_entropy: float, dh, dw, db, entropy_rows, actor_loss):
+    """sac_atari.py's actor update behind the trunks in three launches.  ``hs`` = (actor, qf1, qf2 on obs), ``heads`` their (w, b).
+    OVERWRITES ``dh`` (M, 512), ``dw`` / ``db`` (the actor head's gradient), ``entropy_rows`` (M,) (what ``sac_alpha_`` takes with a
+    target entropy of 0) and ``actor_loss`` (1,)."""
+    M, hidden, n = _sacd_heads(hs, heads)
+    if len(hs) != 3:
+        raise ValueError(f"the actor update takes three heads, got {len(hs)}")
+    _chk(alpha, torch.float32, "alpha", (1,))
+    _chk(dh, torch.float32, "dh", (M, hidden))
+    _chk(dw, torch.float32, "dw", (n, hidden))
+    _chk(db, torch.float32, "db", (n,))
+    _chk(entropy_rows, torch.float32, "entropy_rows", (M,))
+    _chk(actor_loss, torch.float32, "actor_loss", (1,))
+    ws = _workspace(hs[0].device, _lib.load().mi355ppo_sacd_actor_workspace_bytes(M, n))
+    _launch("mi355ppo_sacd_actor_fwd_bwd_f32", hs[0].device, *[_ptr(h) for h in hs], *[_ptr(t) for wb in heads for t in wb], _ptr(alpha),
+            float(target_entropy), _ptr(dh), _ptr(dw), _ptr(db), _ptr(entropy_rows), _ptr(actor_loss), M, hidden, n, _ptr(ws), ws.numel())
+    return actor_loss

@@ -51,6 +51,8 @@ extern "C" {
                                   DQN / C51 -- mi355ppo_dqn_act_f32, mi355ppo_dqn_td_fwd_bwd_f32, mi355ppo_c51_fwd_bwd_f32 (+ workspace sizes) and
                                   their *_cpu twins were added the same way: no existing signature moved, and the number stays at 2.7.1 (a
                                   binding finds out whether they are there by looking the symbols up);
+                                  the Atari DQN / C51 heads, Rainbow and discrete SAC on Atari (mi355ppo_replay_add2_u8, mi355ppo_replay_gather2_u8,
+                                  mi355ppo_sacd_*) likewise;
                                   a binding must check major AND minor (cleanrl_amd/_lib.py does) */
 
 #if defined(__GNUC__)
@@ -1282,6 +1284,87 @@ MI355PPO_API int mi355ppo_rainbow_head_fwd_bwd_f32_cpu(const float* h, const flo
                                                        float* dh, float* dw_out, float* db_out, float* scalars_out, float* loss_per_sample,
                                                        int64_t* best_actions_out, float* next_pmfs_out, float* target_pmfs_out, int M,
                                                        int n_actions, int n_atoms);
+
+/* ---- Discrete SAC on Atari (added under ABI 2.7.1, csrc/sac_atari.hip; reference: cleanrl/sac_atari.py and the plain ReplayBuffer of
+ * cleanrl_utils/buffers.py, which sac_atari.py builds without optimize_memory_usage) ----
+ * The buffer is TWO u8 rings ring_obs and ring_next_obs (slots, n_envs, 84, 84, 4), channels-last and 4-byte aligned, beside
+ * ring_actions (slots, n_envs) int64, ring_rewards and ring_dones (slots, n_envs) f32.  Every offset into a ring is 64-bit.  Five heads
+ * Linear(512, n_actions) sit on the post-ReLU outputs h of five Linear(3136, 512): the actor's fc_logits, fc_q of qf1 / qf2 and of their
+ * targets; every w is (n_actions, 512) and every b (n_actions) as torch keeps them.  hidden == 512, 2 <= n_actions <= 18, 1 <= rows <=
+ * 1024; anything else is MI355PPO_EINVAL before any launch.  alpha is ONE f32 in the caller's memory (device memory for the device entry
+ * points: exp(log_alpha) as mi355ppo_sac_alpha_f32 leaves it, or args.alpha).  Every dot product starts at 0.0f and adds in ascending
+ * index, then the bias; the softmax is exp(z - max) / sum and logp = (z - max) - log(sum) with the exp / log of the SAC section, sums in
+ * ascending action order.  No entry point allocates or synchronises, none uses atomics, all can be captured; every *_cpu twin returns
+ * the device's bits (csrc/sac_atari_rows.h).
+ *
+ * replay_add2: `rb.add(obs, real_next_obs, actions, rewards, terminations, infos)`.  obs / next_obs (n_envs, 4, 84, 84) u8 as the env
+ * gives them -> ring_obs and ring_next_obs at slot pos, one 4-byte store per pixel; actions (n_envs) int64, rewards, dones (n_envs) f32
+ * -> slot pos.  One launch. */
+MI355PPO_API int mi355ppo_replay_add2_u8(const uint8_t* obs, const uint8_t* next_obs, const int64_t* actions, const float* rewards,
+                                         const float* dones, uint8_t* ring_obs, uint8_t* ring_next_obs, int64_t* ring_actions,
+                                         float* ring_rewards, float* ring_dones, int64_t pos, int64_t slots, int n_envs, void* stream);
+MI355PPO_API int mi355ppo_replay_add2_u8_cpu(const uint8_t* obs, const uint8_t* next_obs, const int64_t* actions, const float* rewards,
+                                             const float* dones, uint8_t* ring_obs, uint8_t* ring_next_obs, int64_t* ring_actions,
+                                             float* ring_rewards, float* ring_dones, int64_t pos, int64_t slots, int n_envs);
+/* replay_gather2: `rb.sample`'s `_get_samples`.  frames_out (2M, 84, 84, 4) u8, 4-byte aligned: rows m < M the ring_obs frames
+ * (batch_inds[m], env_inds[m]), rows M + m the ring_next_obs frames at the same place; actions_out (M) int64, rewards_out, dones_out
+ * (M) f32.  Indices are clamped into the ring.  One launch. */
+MI355PPO_API int mi355ppo_replay_gather2_u8(const uint8_t* ring_obs, const uint8_t* ring_next_obs, const int64_t* ring_actions,
+                                            const float* ring_rewards, const float* ring_dones, const int64_t* batch_inds,
+                                            const int64_t* env_inds, int64_t slots, int n_envs, uint8_t* frames_out, int64_t* actions_out,
+                                            float* rewards_out, float* dones_out, int M, void* stream);
+MI355PPO_API int mi355ppo_replay_gather2_u8_cpu(const uint8_t* ring_obs, const uint8_t* ring_next_obs, const int64_t* ring_actions,
+                                                const float* ring_rewards, const float* ring_dones, const int64_t* batch_inds,
+                                                const int64_t* env_inds, int64_t slots, int n_envs, uint8_t* frames_out,
+                                                int64_t* actions_out, float* rewards_out, float* dones_out, int M);
+/* sacd_head_act: `Actor.get_action`'s `policy_dist.sample()` on h (N, 512).  actions_out (N) int64 = argmax_a probs[a] / noise_exp1[a]
+ * (noise_exp1 (N, n_actions): the caller's Exp(1) draws; the first maximum wins, a NaN never does): one draw of torch.multinomial's
+ * rule, as mi355ppo_categorical_sample_f32 draws it.  probs_out (N, n_actions) may be NULL.  Two launches. */
+MI355PPO_API size_t mi355ppo_sacd_head_act_workspace_bytes(int N, int n_actions);
+MI355PPO_API int mi355ppo_sacd_head_act_f32(const float* h, const float* w, const float* b, const float* noise_exp1, int64_t* actions_out,
+                                            float* probs_out, int N, int hidden, int n_actions, void* workspace, size_t workspace_bytes,
+                                            void* stream);
+MI355PPO_API int mi355ppo_sacd_head_act_f32_cpu(const float* h, const float* w, const float* b, const float* noise_exp1, int64_t* actions_out,
+                                                float* probs_out, int N, int hidden, int n_actions);
+/* sacd_critic_fwd_bwd: `# CRITIC training` behind the trunks.  h_q1 / h_q2: qf1 / qf2 on obs; h_pi_next / h_q1t_next / h_q2t_next: the
+ * actor and the two target critics on next_obs; all (M, 512).  Per row: p, logp of the actor's next logits; V = sum_a p_a *
+ * (min(q1t_a, q2t_a) - alpha * logp_a) (torch.min: a NaN wins); y = rewards + ((1 - dones) * gamma) * V; both critics' q at the taken
+ * action (int64, clamped into [0, n_actions)); F.mse_loss rows with the gradient (2 / M) * (q - y).  dh1 / dh2 (M, 512) are d qf_loss /
+ * d h_q1, d h_q2; dw1 / db1 / dw2 / db2 are OVERWRITTEN: the taken actions' rows summed over the batch rows in ascending order, every
+ * other row zero.  scalars_out (4) = {qf1_loss, qf2_loss, mean qf1_a_values, mean qf2_a_values} (f64 folds).  v_out, y_out (M): V and y,
+ * optional.  Four launches (two forwards of three and two heads, the rows, the weight gradients with the scalars). */
+MI355PPO_API size_t mi355ppo_sacd_critic_workspace_bytes(int M, int n_actions);
+MI355PPO_API int mi355ppo_sacd_critic_fwd_bwd_f32(const float* h_q1, const float* h_q2, const float* h_pi_next, const float* h_q1t_next,
+                                                  const float* h_q2t_next, const float* w_q1, const float* b_q1, const float* w_q2,
+                                                  const float* b_q2, const float* w_pi, const float* b_pi, const float* w_q1t,
+                                                  const float* b_q1t, const float* w_q2t, const float* b_q2t, const int64_t* actions,
+                                                  const float* rewards, const float* dones, const float* alpha, double gamma, float* dh1,
+                                                  float* dh2, float* dw1, float* db1, float* dw2, float* db2, float* scalars_out, float* v_out,
+                                                  float* y_out, int M, int hidden, int n_actions, void* workspace, size_t workspace_bytes,
+                                                  void* stream);
+MI355PPO_API int mi355ppo_sacd_critic_fwd_bwd_f32_cpu(const float* h_q1, const float* h_q2, const float* h_pi_next, const float* h_q1t_next,
+                                                      const float* h_q2t_next, const float* w_q1, const float* b_q1, const float* w_q2,
+                                                      const float* b_q2, const float* w_pi, const float* b_pi, const float* w_q1t,
+                                                      const float* b_q1t, const float* w_q2t, const float* b_q2t, const int64_t* actions,
+                                                      const float* rewards, const float* dones, const float* alpha, double gamma, float* dh1,
+                                                      float* dh2, float* dw1, float* db1, float* dw2, float* db2, float* scalars_out,
+                                                      float* v_out, float* y_out, int M, int hidden, int n_actions);
+/* sacd_actor_fwd_bwd: `# ACTOR training` behind the trunks.  h_pi / h_q1 / h_q2: the actor and the two critics (after their Adam step)
+ * on obs.  Per row: t_a = alpha * logp_a - min(q1_a, q2_a), s = sum_a p_a * t_a; actor_loss_out (1) = sum_r s_r / (M n) (an f64 fold);
+ * dz_j = p_j * (t_j - s) / (M n); dh (M, 512) = dz w_pi; dw (n_actions, 512) and db are OVERWRITTEN with the dense gradient, batch rows
+ * ascending.  entropy_rows_out (M): e_r = sum_a p_a * (logp_a + target_entropy) / n_actions, so that mi355ppo_sac_alpha_f32 on it with
+ * target_entropy 0 is the script's alpha_loss, its gradient and its Adam step.  Three launches. */
+MI355PPO_API size_t mi355ppo_sacd_actor_workspace_bytes(int M, int n_actions);
+MI355PPO_API int mi355ppo_sacd_actor_fwd_bwd_f32(const float* h_pi, const float* h_q1, const float* h_q2, const float* w_pi, const float* b_pi,
+                                                 const float* w_q1, const float* b_q1, const float* w_q2, const float* b_q2, const float* alpha,
+                                                 double target_entropy, float* dh, float* dw, float* db, float* entropy_rows_out,
+                                                 float* actor_loss_out, int M, int hidden, int n_actions, void* workspace,
+                                                 size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_sacd_actor_fwd_bwd_f32_cpu(const float* h_pi, const float* h_q1, const float* h_q2, const float* w_pi,
+                                                     const float* b_pi, const float* w_q1, const float* b_q1, const float* w_q2,
+                                                     const float* b_q2, const float* alpha, double target_entropy, float* dh, float* dw,
+                                                     float* db, float* entropy_rows_out, float* actor_loss_out, int M, int hidden,
+                                                     int n_actions);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 """ddpg_continuous_action.py / td3_continuous_action.py / sac_continuous_action.py with both ``MI355PPO_OFFPOLICY`` backends, in one
 process, alternating.
 
-    python tools/offpolicybench.py [--reps 20] [--scripts td3 ddpg sac dqn dqn_atari rainbow rainbow_buffer]
+    python tools/offpolicybench.py [--reps 20] [--scripts td3 ddpg sac dqn dqn_atari rainbow rainbow_buffer sac_atari]
 
 Times, at each script's defaults (batch 256) on a HalfCheetah-shaped (obs 17 / act 6) and a Humanoid-shaped (376 / 17) task:
 one rollout step including the action's copy to the host, one critic-only training step and one step with the delayed policy
@@ -12,7 +12,8 @@ actions) and a LunarLander-shaped (8 / 4) task: one greedy rollout step, one DQN
 and the three noise compositions.  ``--scripts rainbow_buffer`` times rainbow_atari.py's prioritized replay at batch 32 (cleanrl_amd/rainbow_replay.py): the host buffer
 by the reference's rules (NumPy tree walk, batch upload, ``loss_per_sample`` read back) against the device buffer, per add, per
 sample and per priority update; and the four NoisyLinear layers' ``mu + sigma * eps`` by torch against the one-launch compose, for a
-4-action and an 18-action game.
+4-action and an 18-action game.  ``--scripts sac_atari`` times sac_atari.py at its batch of 64 for a 4-action and an 18-action game: one rollout
+step (the policy's sample) and one update (critics, actor, temperature).
 """
 from __future__ import annotations
 
@@ -239,6 +240,41 @@ def bench_rainbow_buffer(a, dev, slots=4096, B=32):
         print(json.dumps(row), flush=True)
 
 
+def make_sac_atari(n, backend, dev, fill=256):
+    from cleanrl_amd.agents import AtariSACActor, AtariSoftQNetwork
+    from cleanrl_amd.learner_sac_atari import SACAtariLearner
+
+    torch.manual_seed(1)
+    np.random.seed(1)
+    envs = E.AtariReplayVecEnv(1, seed=1, n_actions=n)
+    actor = AtariSACActor(envs).to(dev)
+    qs = [AtariSoftQNetwork(envs).to(dev) for _ in range(4)]
+    qs[2].load_state_dict(qs[0].state_dict()), qs[3].load_state_dict(qs[1].state_dict())
+    args = SimpleNamespace(buffer_size=fill * 2, batch_size=64, q_lr=3e-4, policy_lr=3e-4, gamma=0.99, tau=1.0, learning_starts=0, alpha=0.2,
+                           autotune=True, target_entropy_scale=0.89)
+    return fill_ring(SACAtariLearner(actor, *qs, args, envs, dev, backend=backend), envs, fill)
+
+
+def bench_sac_atari(a, dev):
+    """sac_atari.py at batch 64: one rollout step (``get_action``'s sample, with its copy to the host) and one update."""
+    for shape, n in ATARI_SHAPES.items():
+        learners = {b: make_sac_atari(n, b, dev) for b in ("torch", "fused")}
+        legs = {"rollout_step": lambda L, obs: L.act(obs, 1), "update": lambda L, obs: L.train_step()}
+        times = {leg: {b: [] for b in learners} for leg in legs}
+        for rep in range(a.warmup + a.reps):
+            for leg, fn in legs.items():
+                for b, (L, obs) in learners.items():                     # alternating: both backends see the same box state
+                    us = timed(lambda: fn(L, obs), dev)
+                    if rep >= a.warmup:
+                        times[leg][b].append(us)
+        row = {"script": "sac_atari", "shape": shape, "n_actions": n, "batch": 64, "device": str(dev), "reps": a.reps}
+        for leg in legs:
+            for b in learners:
+                row[f"{leg}_{b}_us"] = round(statistics.median(times[leg][b]), 1)
+            row[f"{leg}_speedup"] = round(row[f"{leg}_torch_us"] / row[f"{leg}_fused_us"], 2)
+        print(json.dumps(row), flush=True)
+
+
 def make(script, O, A, backend, dev, fill=4096):
     td3 = script == "td3"
     torch.manual_seed(1)
@@ -299,6 +335,9 @@ def main():
             continue
         if script == "rainbow_buffer":
             bench_rainbow_buffer(a, dev)
+            continue
+        if script == "sac_atari":
+            bench_sac_atari(a, dev)
             continue
         for shape, (O, A) in SHAPES.items():
             learners = {b: make(script, O, A, b, dev) for b in ("torch", "fused")}
