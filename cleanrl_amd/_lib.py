@@ -142,6 +142,11 @@ SIGNATURES = {
     "mi355ppo_impala_workspace_bytes": (c_size_t, [c_int, c_int]),
     "mi355ppo_impala_fwd_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     "mi355ppo_impala_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "mi355ppo_impala84_saved_floats": (c_int64, [c_int]),
+    "mi355ppo_impala84_argmax_bytes": (c_int64, [c_int]),
+    "mi355ppo_impala84_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "mi355ppo_impala84_fwd_u8": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "mi355ppo_impala84_bwd_u8": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     "mi355ppo_impala_maxpool_fwd_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "mi355ppo_impala_maxpool_bwd_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     # host-pointer twins (csrc/host_twins.hip): the device signatures minus stream / workspace
@@ -167,6 +172,8 @@ SIGNATURES = {
                                                _P, _P, _P, _P, c_int, c_int, c_int, c_int]),
     "mi355ppo_impala_fwd_f32_cpu": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "mi355ppo_impala_bwd_f32_cpu": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "mi355ppo_impala84_fwd_u8_cpu": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "mi355ppo_impala84_bwd_u8_cpu": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "mi355ppo_impala_maxpool_fwd_f32_cpu": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int]),
     "mi355ppo_impala_maxpool_bwd_f32_cpu": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int]),
     # PQN (ABI 2.5)
@@ -235,6 +242,13 @@ SIGNATURES = {
     "mi355ppo_replay_add_u8_cpu": (c_int, [_P] * 9 + [c_int64, c_int64, c_int]),
     "mi355ppo_replay_gather_u8": (c_int, [_P] * 6 + [c_int64, c_int] + [_P] * 4 + [c_int, _P]),
     "mi355ppo_replay_gather_u8_cpu": (c_int, [_P] * 6 + [c_int64, c_int] + [_P] * 4 + [c_int]),
+    # the QDagger head (csrc/qdagger.hip)
+    "mi355ppo_qdagger_head_act_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "mi355ppo_qdagger_head_act_f32": (c_int, [_P] * 5 + [c_int] * 3 + [_P, c_size_t, _P]),
+    "mi355ppo_qdagger_head_act_f32_cpu": (c_int, [_P] * 5 + [c_int] * 3),
+    "mi355ppo_qdagger_head_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "mi355ppo_qdagger_head_fwd_bwd_f32": (c_int, [_P] * 10 + [c_double] * 3 + [_P] * 6 + [c_int] * 3 + [_P, c_size_t, _P]),
+    "mi355ppo_qdagger_head_fwd_bwd_f32_cpu": (c_int, [_P] * 10 + [c_double] * 3 + [_P] * 6 + [c_int] * 3),
     "mi355ppo_dqn_head_act_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "mi355ppo_dqn_head_act_f32": (c_int, [_P] * 6 + [c_int] * 4 + [_P, c_size_t, _P]),
     "mi355ppo_dqn_head_act_f32_cpu": (c_int, [_P] * 6 + [c_int] * 4),

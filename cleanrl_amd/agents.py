@@ -474,6 +474,49 @@ class ConvSequence(nn.Module):
         return (self._out_channels, (h + 1) // 2, (w + 1) // 2)
 
 
+class AtariImpalaQNetwork(nn.Module):
+    """qdagger_dqn_atari_impalacnn.py:164-184 (the QDagger student's ``QNetwork``): IMPALA-CNN [16, 32, 32] on (4, 84, 84) frame
+    stacks, then Flatten -> ReLU -> Linear(3872, 256) -> ReLU -> Linear(256, n).  Same ``state_dict`` keys and default
+    initialisation as the reference.  ``forward`` takes the reference's (B, 4, 84, 84) stacks; ``forward_hwc`` takes the
+    channels-last (B, 84, 84, 4) uint8 rows of the frame ring, which with ``impala_backend == "fused"`` (MI355PPO_IMPALA) go
+    to ``ops.impala84_trunk`` as bytes (csrc/impala.hip) while the tail runs on the NCHW view of its output."""
+
+    def __init__(self, env, obs_shape=(4, 84, 84)):
+        super().__init__()
+        n_actions = env if isinstance(env, int) else env.single_action_space.n        # the reference takes ``envs``
+        self.n = int(n_actions)
+        shape = tuple(obs_shape) if isinstance(env, int) else tuple(env.single_observation_space.shape)
+        conv_seqs = []
+        for out_channels in [16, 32, 32]:
+            conv_seq = ConvSequence(shape, out_channels)
+            shape = conv_seq.get_output_shape()
+            conv_seqs.append(conv_seq)
+        conv_seqs += [
+            nn.Flatten(),
+            nn.ReLU(),
+            nn.Linear(in_features=shape[0] * shape[1] * shape[2], out_features=256),
+            nn.ReLU(),
+            nn.Linear(in_features=256, out_features=int(n_actions)),
+        ]
+        self.network = nn.Sequential(*conv_seqs)
+        self.impala_backend = impala_backend_from_env()
+
+    def hidden_hwc(self, x_hwc):
+        """(B, 84, 84, 4) uint8 channels-last rows -> the 256-wide hidden layer (the input of the Q head)."""
+        if self.impala_backend != "fused":
+            return self.network[:-1](x_hwc.permute(0, 3, 1, 2) / 255.0)
+        y = ops.impala84_trunk(x_hwc, ops.impala84_params(self))
+        return self.network[3:-1](y.permute(0, 3, 1, 2))
+
+    def forward_hwc(self, x_hwc):
+        return self.network[-1](self.hidden_hwc(x_hwc))
+
+    def forward(self, x):
+        if self.impala_backend == "fused" and x.dtype == torch.uint8:      # the fused trunk reads bytes; float stacks take the reference's ops
+            return self.forward_hwc(x.permute(0, 2, 3, 1).contiguous())
+        return self.network(x / 255.0)
+
+
 class ProcgenAgent(_DiscreteMixin, nn.Module):
     """ppo_procgen.py:127-158: IMPALA-CNN [16, 32, 32] on (64, 64, 3) frames that arrive pixel-interleaved ("bhwc") --
     which is how the rollout buffer stores images anyway, so no relayout kernel runs for this script.  The conv layers

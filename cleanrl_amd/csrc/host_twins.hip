@@ -18,6 +18,7 @@
 #include "lstm_rows.h"
 #include "trxl_rows.h"
 #include "impala_rows.h"
+#include "qdagger_rows.h"
 #include "pqn_rows.h"
 #include "pqn_lstm_rows.h"
 #include "offpolicy_rows.h"
@@ -753,6 +754,7 @@ struct ImpConvHost {
     const float* res;
     float* out;
     int B;
+    const uint8_t* in8 = nullptr;   // the 84 family's layer 0: the frames as bytes (in NULL), read through imp_u8
 };
 
 template <int V>
@@ -767,7 +769,8 @@ __attribute__((always_inline)) inline void imp_conv_host_impl(const ImpConvHost&
                     const int yy = y - 1, xx = x - 1;
                     float v = 0.0f;
                     if (yy >= 0 && yy < a.h && xx >= 0 && xx < a.h && c < a.ci) {
-                        v = a.in[(((size_t)img * a.h + yy) * a.h + xx) * a.ci + c];
+                        const size_t e = (((size_t)img * a.h + yy) * a.h + xx) * a.ci + c;
+                        v = a.in8 ? imp_u8(a.in8[e]) : a.in[e];
                         if (a.relu) v = imp_relu(v);
                     }
                     pad[((size_t)y * hp + x) * cp + c] = v;
@@ -797,6 +800,7 @@ struct ImpWgradHost {
     float* gw;
     float* gb;
     int B;
+    const uint8_t* in8 = nullptr;   // as in ImpConvHost
 };
 
 template <int V>
@@ -815,14 +819,15 @@ __attribute__((always_inline)) inline void imp_wgrad_host_impl(const ImpWgradHos
             int y0;
             imp_band(g, a.h, b, &img0, &y0);
             for (int64_t img = img0; img < img0 + g.NI && img < a.B; ++img)
-                for (int y = y0; y < y0 + g.R; ++y)
+                for (int y = y0; y < y0 + g.R && y < a.h; ++y)
                     for (int x = 0; x < a.h; ++x) {
                         for (int j = 0; j < jp; ++j) {
                             float v = j == g.KP ? 1.0f : 0.0f;
                             if (j < g.KP) {
                                 const int tap = j / g.CP, c = j % g.CP, yy = y + tap / 3 - 1, xx = x + tap % 3 - 1;
                                 if (yy >= 0 && yy < a.h && xx >= 0 && xx < a.h && c < a.ci) {
-                                    v = a.in[(((size_t)img * a.h + yy) * a.h + xx) * a.ci + c];
+                                    const size_t e = (((size_t)img * a.h + yy) * a.h + xx) * a.ci + c;
+                                    v = a.in8 ? imp_u8(a.in8[e]) : a.in[e];
                                     if (a.relu) v = imp_relu(v);
                                 }
                             }
@@ -834,6 +839,9 @@ __attribute__((always_inline)) inline void imp_wgrad_host_impl(const ImpWgradHos
                             for (int j = 0; j < jp; ++j) r[j] = fmaf(d[n], row[j], r[j]);
                         }
                     }
+            // the dead steps that complete the band's last MFMA (impala_rows.h): 0 * 0 into every chain
+            for (int dead = (4 - imp_band_pixels(g, a.h, img0, y0, a.B) % 4) % 4; dead > 0; --dead)
+                for (int i = 0; i < a.co * jp; ++i) acc[i] = fmaf(0.0f, 0.0f, acc[i]);
         }
     }
     for (int n = 0; n < a.co; ++n)
@@ -867,8 +875,8 @@ void imp_conv_host(const ImpConvHost& a) { imp_host_has_fma() ? imp_conv_host_fm
 void imp_wgrad_host(const ImpWgradHost& a) { imp_host_has_fma() ? imp_wgrad_host_fma(a) : imp_wgrad_host_plain(a); }
 
 // Dense Wt[k][n] of layer l: the forward's (dgrad = false) or the data gradient's.
-std::vector<float> imp_wt_host(const float* w, int l, bool dgrad) {
-    const int ci = imp_layer_cin(l), co = imp_layer_cout(l);
+std::vector<float> imp_wt_host(int f, const float* w, int l, bool dgrad) {
+    const int ci = imp_layer_cin(f, l), co = imp_layer_cout(l);
     const int kp = dgrad ? 9 * co : 9 * imp_cpad(ci), nn = dgrad ? ci : co;
     std::vector<float> wt((size_t)kp * nn);
     for (int k = 0; k < kp; ++k)
@@ -877,7 +885,7 @@ std::vector<float> imp_wt_host(const float* w, int l, bool dgrad) {
 }
 
 void imp_pool_fwd_host(const float* x, float* y, uint8_t* arg, int B, int h, int c) {
-    const int ho = h / 2;
+    const int ho = imp_half(h);
     for (int64_t img = 0; img < B; ++img)
         for (int oy = 0; oy < ho; ++oy)
             for (int ox = 0; ox < ho; ++ox)
@@ -888,7 +896,7 @@ void imp_pool_fwd_host(const float* x, float* y, uint8_t* arg, int B, int h, int
 }
 
 void imp_pool_bwd_host(const float* g, const uint8_t* arg, float* dx, int B, int h, int c) {
-    const int ho = h / 2;
+    const int ho = imp_half(h);
     for (int64_t img = 0; img < B; ++img)
         for (int iy = 0; iy < h; ++iy)
             for (int ix = 0; ix < h; ++ix)
@@ -898,43 +906,45 @@ void imp_pool_bwd_host(const float* g, const uint8_t* arg, float* dx, int B, int
                 }
 }
 
-int imp_check_host(const char* fn, int B, int H, int W, int C, int ch0, int ch1, int ch2) {
+int imp_check_host(int f, const char* fn, int B, int H, int W, int C, int ch0, int ch1, int ch2) {
     MI355_REQUIRE(B > 0, MI355PPO_EINVAL, "%s: B=%d must be positive", fn, B);
-    MI355_REQUIRE(H == kImpH && W == kImpH && C == kImpC, MI355PPO_EINVAL, "%s: frames %dx%dx%d (only 64x64x3)", fn, H, W, C);
+    MI355_REQUIRE(H == imp_fam_h(f) && W == imp_fam_h(f) && C == imp_fam_c(f), MI355PPO_EINVAL, "%s: frames %dx%dx%d (only %dx%dx%d)", fn,
+                  H, W, C, imp_fam_h(f), imp_fam_h(f), imp_fam_c(f));
     MI355_REQUIRE(ch0 == 16 && ch1 == 32 && ch2 == 32, MI355PPO_EINVAL, "%s: channels [%d, %d, %d] (only [16, 32, 32])", fn, ch0, ch1,
                   ch2);
     return MI355PPO_OK;
 }
 
 bool imp_pool_shape_ok(int B, int H, int W, int C) {
-    return B > 0 && H == W && ((H == 64 && C == 16) || (H == 32 && C == 32) || (H == 16 && C == 32));
+    for (int f : {kImpFam64, kImpFam84})
+        for (int s = 0; s < kImpSeqs; ++s)
+            if (B > 0 && H == W && H == imp_seq_h(f, s) && C == imp_seq_cout(s)) return true;
+    return false;
 }
 
-}  // namespace
-
-extern "C" MI355PPO_API int mi355ppo_impala_fwd_f32_cpu(const float* x, const float* const* params, float* y, float* saved,
-                                                        uint8_t* argmax, int B, int H, int W, int C, int ch0, int ch1, int ch2) {
-    const char* fn = "mi355ppo_impala_fwd_f32_cpu";
-    MI355_REQUIRE(x && params && y && saved && argmax, MI355PPO_EINVAL, "%s: null pointer", fn);
-    if (int st = imp_check_host(fn, B, H, W, C, ch0, ch1, ch2)) return st;
+// Family f's forward / backward; the frames are x (f32, the 64 family) or x8 (bytes, the 84 family).
+int imp_fwd_host(int f, const char* fn, const float* x, const uint8_t* x8, const float* const* params, float* y, float* saved,
+                 uint8_t* argmax, int B, int H, int W, int C, int ch0, int ch1, int ch2) {
+    MI355_REQUIRE((x || x8) && params && y && saved && argmax, MI355PPO_EINVAL, "%s: null pointer", fn);
+    if (int st = imp_check_host(f, fn, B, H, W, C, ch0, ch1, ch2)) return st;
     for (int i = 0; i < kImpParams; ++i) MI355_REQUIRE(params[i], MI355PPO_EINVAL, "%s: null pointer (params[%d])", fn, i);
-    std::vector<float> big((size_t)B * kImpH * kImpH * 16);
+    std::vector<float> big((size_t)B * imp_fam_h(f) * imp_fam_h(f) * 16);
     const float* xin = x;
     for (int s = 0; s < kImpSeqs; ++s) {
-        const int ci = imp_seq_cin(s), c = imp_seq_cout(s), h = imp_seq_h(s), hp = h / 2, L = 5 * s;
-        float* P = saved + imp_saved_offset(B, s, 0);
-        float* h0 = saved + imp_saved_offset(B, s, 1);
-        float* x1 = saved + imp_saved_offset(B, s, 2);
-        float* h1 = saved + imp_saved_offset(B, s, 3);
-        float* yo = s < 2 ? saved + imp_saved_offset(B, s, 4) : y;
-        std::vector<float> wt = imp_wt_host(params[2 * L], L, false);
-        imp_conv_host({xin, ci, c, h, false, wt.data(), params[2 * L + 1], nullptr, nullptr, big.data(), B});
-        imp_pool_fwd_host(big.data(), P, argmax + imp_argmax_offset(B, s), B, h, c);
+        const int ci = imp_seq_cin(f, s), c = imp_seq_cout(s), h = imp_seq_h(f, s), hp = imp_half(h), L = 5 * s;
+        float* P = saved + imp_saved_offset(f, B, s, 0);
+        float* h0 = saved + imp_saved_offset(f, B, s, 1);
+        float* x1 = saved + imp_saved_offset(f, B, s, 2);
+        float* h1 = saved + imp_saved_offset(f, B, s, 3);
+        float* yo = s < 2 ? saved + imp_saved_offset(f, B, s, 4) : y;
+        std::vector<float> wt = imp_wt_host(f, params[2 * L], L, false);
+        imp_conv_host({xin, ci, c, h, false, wt.data(), params[2 * L + 1], nullptr, nullptr, big.data(), B, s == 0 ? x8 : nullptr});
+        imp_pool_fwd_host(big.data(), P, argmax + imp_argmax_offset(f, B, s), B, h, c);
         const float* ins[4] = {P, h0, x1, h1};
         float* outs[4] = {h0, x1, h1, yo};
         const float* ress[4] = {nullptr, P, nullptr, x1};
         for (int i = 0; i < 4; ++i) {
-            wt = imp_wt_host(params[2 * (L + 1 + i)], L + 1 + i, false);
+            wt = imp_wt_host(f, params[2 * (L + 1 + i)], L + 1 + i, false);
             imp_conv_host({ins[i], c, c, hp, true, wt.data(), params[2 * (L + 1 + i) + 1], nullptr, ress[i], outs[i], B});
         }
         xin = yo;
@@ -942,46 +952,44 @@ extern "C" MI355PPO_API int mi355ppo_impala_fwd_f32_cpu(const float* x, const fl
     return MI355PPO_OK;
 }
 
-extern "C" MI355PPO_API int mi355ppo_impala_bwd_f32_cpu(const float* x, const float* const* params, const float* saved,
-                                                        const uint8_t* argmax, const float* dy, float* const* grads, int B, int H, int W,
-                                                        int C, int ch0, int ch1, int ch2) {
-    const char* fn = "mi355ppo_impala_bwd_f32_cpu";
-    MI355_REQUIRE(x && params && saved && argmax && dy && grads, MI355PPO_EINVAL, "%s: null pointer", fn);
-    if (int st = imp_check_host(fn, B, H, W, C, ch0, ch1, ch2)) return st;
+int imp_bwd_host(int f, const char* fn, const float* x, const uint8_t* x8, const float* const* params, const float* saved,
+                 const uint8_t* argmax, const float* dy, float* const* grads, int B, int H, int W, int C, int ch0, int ch1, int ch2) {
+    MI355_REQUIRE((x || x8) && params && saved && argmax && dy && grads, MI355PPO_EINVAL, "%s: null pointer", fn);
+    if (int st = imp_check_host(f, fn, B, H, W, C, ch0, ch1, ch2)) return st;
     for (int i = 0; i < kImpParams; ++i)
         MI355_REQUIRE(params[i] && grads[i], MI355PPO_EINVAL, "%s: null pointer (params / grads[%d])", fn, i);
-    const size_t plane = (size_t)B * 32 * 32 * 16;
-    std::vector<float> ga(plane), gb(plane), t(plane), big((size_t)B * kImpH * kImpH * 16);
+    const size_t plane = (size_t)B * imp_plane(f, 0);
+    std::vector<float> ga(plane), gb(plane), t(plane), big((size_t)B * imp_fam_h(f) * imp_fam_h(f) * 16);
     const float* g_in = dy;
     for (int s = kImpSeqs - 1; s >= 0; --s) {
-        const int ci = imp_seq_cin(s), c = imp_seq_cout(s), h = imp_seq_h(s), hp = h / 2, L = 5 * s;
-        const float* P = saved + imp_saved_offset(B, s, 0);
-        const float* h0 = saved + imp_saved_offset(B, s, 1);
-        const float* x1 = saved + imp_saved_offset(B, s, 2);
-        const float* h1 = saved + imp_saved_offset(B, s, 3);
-        const float* xin = s == 0 ? x : saved + imp_saved_offset(B, s - 1, 4);
+        const int ci = imp_seq_cin(f, s), c = imp_seq_cout(s), h = imp_seq_h(f, s), hp = imp_half(h), L = 5 * s;
+        const float* P = saved + imp_saved_offset(f, B, s, 0);
+        const float* h0 = saved + imp_saved_offset(f, B, s, 1);
+        const float* x1 = saved + imp_saved_offset(f, B, s, 2);
+        const float* h1 = saved + imp_saved_offset(f, B, s, 3);
+        const float* xin = s == 0 ? x : saved + imp_saved_offset(f, B, s - 1, 4);
         auto other = [&](const float* g) { return g == ga.data() ? gb.data() : ga.data(); };
         float* g1 = other(g_in);
         float* g2 = other(g1);
         std::vector<float> wt;
         // res_block1, then res_block0 (the order of bwd_seq in impala.hip)
         imp_wgrad_host({h1, c, c, hp, true, g_in, grads[2 * L + 8], grads[2 * L + 9], B});
-        wt = imp_wt_host(params[2 * (L + 4)], L + 4, true);
+        wt = imp_wt_host(f, params[2 * (L + 4)], L + 4, true);
         imp_conv_host({g_in, c, c, hp, false, wt.data(), nullptr, h1, nullptr, t.data(), B});
         imp_wgrad_host({x1, c, c, hp, true, t.data(), grads[2 * L + 6], grads[2 * L + 7], B});
-        wt = imp_wt_host(params[2 * (L + 3)], L + 3, true);
+        wt = imp_wt_host(f, params[2 * (L + 3)], L + 3, true);
         imp_conv_host({t.data(), c, c, hp, false, wt.data(), nullptr, x1, g_in, g1, B});
         imp_wgrad_host({h0, c, c, hp, true, g1, grads[2 * L + 4], grads[2 * L + 5], B});
-        wt = imp_wt_host(params[2 * (L + 2)], L + 2, true);
+        wt = imp_wt_host(f, params[2 * (L + 2)], L + 2, true);
         imp_conv_host({g1, c, c, hp, false, wt.data(), nullptr, h0, nullptr, t.data(), B});
         imp_wgrad_host({P, c, c, hp, true, t.data(), grads[2 * L + 2], grads[2 * L + 3], B});
-        wt = imp_wt_host(params[2 * (L + 1)], L + 1, true);
+        wt = imp_wt_host(f, params[2 * (L + 1)], L + 1, true);
         imp_conv_host({t.data(), c, c, hp, false, wt.data(), nullptr, P, g1, g2, B});
-        imp_pool_bwd_host(g2, argmax + imp_argmax_offset(B, s), big.data(), B, h, c);
-        imp_wgrad_host({xin, ci, c, h, false, big.data(), grads[2 * L], grads[2 * L + 1], B});
+        imp_pool_bwd_host(g2, argmax + imp_argmax_offset(f, B, s), big.data(), B, h, c);
+        imp_wgrad_host({xin, ci, c, h, false, big.data(), grads[2 * L], grads[2 * L + 1], B, s == 0 ? x8 : nullptr});
         if (s > 0) {
             float* gx = other(g2);
-            wt = imp_wt_host(params[2 * L], L, true);
+            wt = imp_wt_host(f, params[2 * L], L, true);
             imp_conv_host({big.data(), c, ci, h, false, wt.data(), nullptr, nullptr, nullptr, gx, B});
             g_in = gx;
         }
@@ -989,10 +997,36 @@ extern "C" MI355PPO_API int mi355ppo_impala_bwd_f32_cpu(const float* x, const fl
     return MI355PPO_OK;
 }
 
+}  // namespace
+
+extern "C" MI355PPO_API int mi355ppo_impala_fwd_f32_cpu(const float* x, const float* const* params, float* y, float* saved,
+                                                        uint8_t* argmax, int B, int H, int W, int C, int ch0, int ch1, int ch2) {
+    return imp_fwd_host(kImpFam64, "mi355ppo_impala_fwd_f32_cpu", x, nullptr, params, y, saved, argmax, B, H, W, C, ch0, ch1, ch2);
+}
+
+extern "C" MI355PPO_API int mi355ppo_impala_bwd_f32_cpu(const float* x, const float* const* params, const float* saved,
+                                                        const uint8_t* argmax, const float* dy, float* const* grads, int B, int H, int W,
+                                                        int C, int ch0, int ch1, int ch2) {
+    return imp_bwd_host(kImpFam64, "mi355ppo_impala_bwd_f32_cpu", x, nullptr, params, saved, argmax, dy, grads, B, H, W, C, ch0, ch1,
+                        ch2);
+}
+
+extern "C" MI355PPO_API int mi355ppo_impala84_fwd_u8_cpu(const uint8_t* x, const float* const* params, float* y, float* saved,
+                                                         uint8_t* argmax, int B, int H, int W, int C, int ch0, int ch1, int ch2) {
+    return imp_fwd_host(kImpFam84, "mi355ppo_impala84_fwd_u8_cpu", nullptr, x, params, y, saved, argmax, B, H, W, C, ch0, ch1, ch2);
+}
+
+extern "C" MI355PPO_API int mi355ppo_impala84_bwd_u8_cpu(const uint8_t* x, const float* const* params, const float* saved,
+                                                         const uint8_t* argmax, const float* dy, float* const* grads, int B, int H,
+                                                         int W, int C, int ch0, int ch1, int ch2) {
+    return imp_bwd_host(kImpFam84, "mi355ppo_impala84_bwd_u8_cpu", nullptr, x, params, saved, argmax, dy, grads, B, H, W, C, ch0, ch1,
+                        ch2);
+}
+
 extern "C" MI355PPO_API int mi355ppo_impala_maxpool_fwd_f32_cpu(const float* x, float* y, uint8_t* argmax, int B, int H, int W, int C) {
     const char* fn = "mi355ppo_impala_maxpool_fwd_f32_cpu";
     MI355_REQUIRE(x && y && argmax, MI355PPO_EINVAL, "%s: null pointer", fn);
-    MI355_REQUIRE(imp_pool_shape_ok(B, H, W, C), MI355PPO_EINVAL, "%s: B=%d %dx%dx%d (only the trunk's 64x64x16, 32x32x32, 16x16x32)",
+    MI355_REQUIRE(imp_pool_shape_ok(B, H, W, C), MI355PPO_EINVAL, "%s: B=%d %dx%dx%d (only the trunks' 64x64x16, 32x32x32, 16x16x32, 84x84x16, 42x42x32, 21x21x32)",
                   fn, B, H, W, C);
     imp_pool_fwd_host(x, y, argmax, B, H, C);
     return MI355PPO_OK;
@@ -1002,7 +1036,7 @@ extern "C" MI355PPO_API int mi355ppo_impala_maxpool_bwd_f32_cpu(const float* dy,
                                                                 int C) {
     const char* fn = "mi355ppo_impala_maxpool_bwd_f32_cpu";
     MI355_REQUIRE(dy && argmax && dx, MI355PPO_EINVAL, "%s: null pointer", fn);
-    MI355_REQUIRE(imp_pool_shape_ok(B, H, W, C), MI355PPO_EINVAL, "%s: B=%d %dx%dx%d (only the trunk's 64x64x16, 32x32x32, 16x16x32)",
+    MI355_REQUIRE(imp_pool_shape_ok(B, H, W, C), MI355PPO_EINVAL, "%s: B=%d %dx%dx%d (only the trunks' 64x64x16, 32x32x32, 16x16x32, 84x84x16, 42x42x32, 21x21x32)",
                   fn, B, H, W, C);
     imp_pool_bwd_host(dy, argmax, dx, B, H, C);
     return MI355PPO_OK;
@@ -2163,4 +2197,64 @@ extern "C" MI355PPO_API int mi355ppo_c51_head_fwd_bwd_f32_cpu(const float* h, co
                   fn, n_atoms);
     return da_update_cpu<true>(h, h_next, w, b, w_target, b_target, atoms, actions, rewards, dones, (float)gamma, (float)v_min, (float)v_max,
                                (float)(1.0 / (double)M), dh, dw, db, scalars_out, next_pmfs_out, target_pmfs_out, M, n_actions, n_atoms);
+}
+
+// ------------------------------------------------------------------------------------------------ QDagger head (qdagger.hip)
+// qh_fwd_kernel<256, 256>, qd_row_kernel and qd_wgrad_kernel on the host, from qdagger_rows.h in the device's orders.
+extern "C" MI355PPO_API int mi355ppo_qdagger_head_act_f32_cpu(const float* h, const float* w, const float* b, int64_t* actions_out, float* q_out,
+                                                             int N, int hidden, int n_actions) {
+    const char* fn = "mi355ppo_qdagger_head_act_f32_cpu";
+    MI355_REQUIRE(h && w && b && actions_out, MI355PPO_EINVAL, "%s: null pointer", fn);
+    if (int rc = qd_shape(fn, N, hidden, n_actions)) return rc;
+    float q[kDqMaxAct];
+    for (int r = 0; r < N; ++r) {
+        for (int j = 0; j < n_actions; ++j) {
+            q[j] = qd_dot(h + (int64_t)r * kQdH, w + (int64_t)j * kQdH, b[j]);
+            if (q_out) q_out[(int64_t)r * n_actions + j] = q[j];
+        }
+        actions_out[r] = (int64_t)dq_argmax(q, n_actions);
+    }
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_qdagger_head_fwd_bwd_f32_cpu(const float* h, const float* h_next, const float* w, const float* b,
+                                                                 const float* w_target, const float* b_target, const float* teacher_q,
+                                                                 const int64_t* actions, const float* rewards, const float* dones, double gamma,
+                                                                 double temperature, double distill_coeff, float* dh, float* dw, float* db,
+                                                                 float* scalars_out, float* target_q_out, float* td_target_out, int M,
+                                                                 int hidden, int n_actions) {
+    const char* fn = "mi355ppo_qdagger_head_fwd_bwd_f32_cpu";
+    MI355_REQUIRE(h && h_next && w && b && w_target && b_target && teacher_q && actions && rewards && dones && dh && dw && db && scalars_out,
+                  MI355PPO_EINVAL, "%s: null pointer", fn);
+    if (int rc = qd_shape(fn, M, hidden, n_actions)) return rc;
+    MI355_REQUIRE(temperature > 0.0, MI355PPO_EINVAL, "%s: temperature=%g must be positive", fn, temperature);
+    const int n = n_actions;
+    const float norm = (float)(2.0 / (double)M), ck = (float)(distill_coeff / temperature);
+    std::vector<float> dq((size_t)M * n), rows((size_t)3 * M);
+    float qo[kDqMaxAct], qt[kDqMaxAct];
+    for (int r = 0; r < M; ++r) {
+        for (int j = 0; j < n; ++j) {
+            qo[j] = qd_dot(h + (int64_t)r * kQdH, w + (int64_t)j * kQdH, b[j]);
+            qt[j] = qd_dot(h_next + (int64_t)r * kQdH, w_target + (int64_t)j * kQdH, b_target[j]);
+            if (target_q_out) target_q_out[(int64_t)r * n + j] = qt[j];
+        }
+        float* d = dq.data() + (size_t)r * n;
+        const QdRow R = qd_row(qo, qt, teacher_q + (int64_t)r * n, n, (int)op_clamp(actions[r], n), rewards[r], dones[r], (float)gamma,
+                               (float)temperature, norm, ck, d);
+        if (td_target_out) td_target_out[r] = R.y;
+        rows[r] = R.sq;
+        rows[(size_t)M + r] = R.qa;
+        rows[(size_t)2 * M + r] = R.kl;
+        for (int k = 0; k < kQdH; ++k) dh[(int64_t)r * kQdH + k] = qd_dh(d, n, w, k);
+    }
+    for (int j = 0; j < n; ++j) {
+        for (int k = 0; k < kQdH; ++k) dw[(int64_t)j * kQdH + k] = qd_wgrad(dq.data() + j, n, M, h, k);
+        db[j] = qd_wgrad(dq.data() + j, n, M, nullptr, 0);
+    }
+    const float q_loss = op_fold_mean_host(rows.data(), M), distill = qd_fold_sum_host(rows.data() + (size_t)2 * M, M);
+    scalars_out[0] = qd_loss(q_loss, (float)distill_coeff, distill);
+    scalars_out[1] = q_loss;
+    scalars_out[2] = distill;
+    scalars_out[3] = op_fold_mean_host(rows.data() + (size_t)M, M);
+    return MI355PPO_OK;
 }

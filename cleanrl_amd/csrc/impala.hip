@@ -9,6 +9,10 @@
 //     kernel IF (imp_fold_kernel) adds the partials in order.  No atomics: deterministic;
 //   * max pool forward (value + argmax byte) and backward are separate element-wise launches.
 // One launch per layer and pass: 19 forward, 47 backward.
+// The geometry is a function of (C_in, C_out, H) alone, so the same kernels serve two frame families (impala_rows.h): 64x64x3
+// f32 frames (ppo_procgen / ppg_procgen) and 84x84x4 u8 Atari stacks (qdagger_dqn_atari_impalacnn.py:164-184), whose planes
+// 84 / 42 / 21 / 11 tile into ragged bands with dead slots.  The 84 family's layer 0 stages the ring's bytes directly (one
+// 4-byte pixel = four channels byte / 255.0f); no f32 copy of the frames exists.
 #include "common.h"
 #include "impala_rows.h"
 
@@ -24,6 +28,7 @@ struct ImpParams {
 };
 
 // ---------------------------------------------------------------------------------------------------------- weight packing
+template <int F>
 __global__ __launch_bounds__(256) void imp_pack_kernel(ImpParams prm, float* __restrict__ wp) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= kImpPackFloats) return;
@@ -36,7 +41,7 @@ __global__ __launch_bounds__(256) void imp_pack_kernel(ImpParams prm, float* __r
     }
     const bool dg = piece >= kImpLayers;
     const int l = dg ? piece - kImpLayers + 1 : piece;
-    const int cin = imp_layer_cin(l), cout = imp_layer_cout(l);
+    const int cin = imp_layer_cin(F, l), cout = imp_layer_cout(l);
     const int nt_count = (dg ? cin : cout) / 16;
     const int i = e - imp_pack_offset(l, dg);
     const int ks = i / (nt_count * 64), nt = (i / 64) % nt_count, lane = i % 64;
@@ -45,8 +50,11 @@ __global__ __launch_bounds__(256) void imp_pack_kernel(ImpParams prm, float* __r
 }
 
 // Stage band (img0, y0)'s input rows into LDS: NI x (R + 2) rows x (H + 2) columns x CP channels, zero outside the image.
-template <int CI, int CO, int H, bool RELU_IN>
-__device__ __forceinline__ void imp_stage(float* s_in, const float* __restrict__ in, int64_t img0, int y0, int B) {
+// TIN = uint8_t (the 84 family's frames, CI = 4): the pixel's four bytes in one load, each imp_u8'd.
+template <int CI, int CO, int H, bool RELU_IN, typename TIN>
+__device__ __forceinline__ void imp_stage(float* s_in, const TIN* __restrict__ in, int64_t img0, int y0, int B) {
+    constexpr bool U8 = sizeof(TIN) == 1;
+    static_assert(!U8 || (CI == 4 && !RELU_IN), "u8 frames: four channels, layer 0");
     constexpr ImpGeom G = imp_geom(CI, CO, H);
     constexpr int Q = G.CP / 4;
     for (int e = threadIdx.x; e < G.ROWS * G.COLS * Q; e += kImpThreads) {
@@ -55,8 +63,12 @@ __device__ __forceinline__ void imp_stage(float* s_in, const float* __restrict__
         const int64_t img = img0 + li;
         f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
         if (img < B && y >= 0 && y < H && x >= 0 && x < H) {
-            const float* src = in + ((img * H + y) * H + x) * CI + 4 * q;
-            if constexpr (CI % 4 == 0) {
+            const TIN* src = in + ((img * H + y) * H + x) * CI + 4 * q;
+            if constexpr (U8) {
+                const uint32_t w = *reinterpret_cast<const uint32_t*>(src);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = imp_u8((uint8_t)(w >> (8 * j)));
+            } else if constexpr (CI % 4 == 0) {
                 v = *reinterpret_cast<const f32x4*>(src);
             } else {
 #pragma unroll
@@ -73,12 +85,13 @@ __device__ __forceinline__ void imp_stage(float* s_in, const float* __restrict__
 
 // ------------------------------------------------------------------------------------------------- kernel IC: convolution
 // DGRAD = false: out = conv(relu?(in)) + bias (+ res).  DGRAD = true: out = (mask > 0 ? conv(in) : 0) (+ res), in = dY.
-template <int CI, int CO, int H, bool RELU_IN, bool DGRAD>
-__global__ __launch_bounds__(kImpThreads) void imp_conv_kernel(const float* __restrict__ in, const float* __restrict__ wp,
+template <int CI, int CO, int H, bool RELU_IN, bool DGRAD, typename TIN>
+__global__ __launch_bounds__(kImpThreads) void imp_conv_kernel(const TIN* __restrict__ in, const float* __restrict__ wp,
                                                                const float* __restrict__ bias, const float* __restrict__ mask,
                                                                const float* __restrict__ res, float* __restrict__ out, int B) {
     constexpr ImpGeom G = imp_geom(CI, CO, H);
-    static_assert(G.NI * G.R * H == G.PIX && G.MT * G.NT == 4 && G.KP % 4 == 0, "tiling");
+    static_assert(G.LIVE <= G.PIX && (G.NI == 1 || (G.R == H && G.LIVE == G.PIX)) && G.MT * G.NT == 4 && G.KP % 4 == 0, "tiling");
+    constexpr bool RAGGED = G.LIVE < G.PIX || H % G.R != 0;          // false for the 64 family: no dead slots, no dead rows
     __shared__ __attribute__((aligned(16))) float s_in[G.LDS_IN];
     __shared__ __attribute__((aligned(16))) float s_w[G.LDS_W];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lrow = lane & 15, kq = lane >> 4;
@@ -94,7 +107,9 @@ __global__ __launch_bounds__(kImpThreads) void imp_conv_kernel(const float* __re
     int abase[G.MT];
 #pragma unroll
     for (int mt = 0; mt < G.MT; ++mt) {
-        const int p = wave * 16 * G.MT + mt * 16 + lrow, li = p / (G.R * H), q = p % (G.R * H);
+        int p = wave * 16 * G.MT + mt * 16 + lrow;
+        if constexpr (RAGGED) p = p < G.LIVE ? p : 0;                 // a dead slot reads slot 0's cells
+        const int li = p / (G.R * H), q = p % (G.R * H);
         abase[mt] = ((li * (G.R + 2) + q / H) * G.COLS + q % H) * G.S + kq;
     }
     f32x4 acc[G.MT][G.NT];
@@ -124,6 +139,8 @@ __global__ __launch_bounds__(kImpThreads) void imp_conv_kernel(const float* __re
         for (int r = 0; r < 4; ++r) {
             const int p = wave * 16 * G.MT + mt * 16 + kq * 4 + r;
             if (img0 + p / (G.R * H) >= B) continue;
+            if constexpr (RAGGED)
+                if (p >= G.LIVE || y0 + p / H >= H) continue;         // dead slot / dead row of the image's last band
 #pragma unroll
             for (int nt = 0; nt < G.NT; ++nt) {
                 const int n = nt * 16 + lrow;
@@ -140,8 +157,8 @@ __global__ __launch_bounds__(kImpThreads) void imp_conv_kernel(const float* __re
 
 // ---------------------------------------------------------------------------------------- kernel IW: weight + bias gradient
 // part[q][co][j] = sum over the pixels of part q's bands of dy[p][co] * a[p][j] (a: the conv's input columns, 1 at j = KP).
-template <int CI, int CO, int H, bool RELU_IN>
-__global__ __launch_bounds__(kImpThreads) void imp_wgrad_kernel(const float* __restrict__ in, const float* __restrict__ dy,
+template <int CI, int CO, int H, bool RELU_IN, typename TIN>
+__global__ __launch_bounds__(kImpThreads) void imp_wgrad_kernel(const TIN* __restrict__ in, const float* __restrict__ dy,
                                                                 float* __restrict__ part, int B, int64_t bands, int parts) {
     constexpr ImpGeom G = imp_geom(CI, CO, H);
     constexpr int CT = CO / 16, JT = G.JP / 16, TILES = CT * JT, TPW = (TILES + 3) / 4;
@@ -172,24 +189,35 @@ __global__ __launch_bounds__(kImpThreads) void imp_wgrad_kernel(const float* __r
         int64_t img0;
         int y0;
         imp_band(G, H, b, &img0, &y0);
-        const int64_t nimg = B - img0 < G.NI ? B - img0 : G.NI;
-        const int npix = (int)nimg * G.R * H;
+        const int npix = imp_band_pixels(G, H, img0, y0, B);
         const int64_t pix0 = (img0 * H + y0) * H;
         __syncthreads();                                              // the previous band's reads are done
         for (int e = tid; e < npix * CO / 4; e += kImpThreads)
             reinterpret_cast<f32x4*>(s_dy)[e] = reinterpret_cast<const f32x4*>(dy + pix0 * CO)[e];
         imp_stage<CI, CO, H, RELU_IN>(s_in, in, img0, y0, B);
         __syncthreads();
-        for (int pg = 0; pg < npix / 4; ++pg) {
-            const int p = 4 * pg + kq, li = p / (G.R * H), q = p % (G.R * H);
+        constexpr bool TAIL = (G.R * H) % 4 != 0 || H % 4 != 0;       // a band's pixel count may be no multiple of 4
+        for (int pg = 0; pg < (npix + 3) / 4; ++pg) {
+            int p = 4 * pg + kq;
+            bool dead = false;
+            if constexpr (TAIL) {
+                dead = p >= npix;                                     // enters the chain as 0 * 0 (impala_rows.h)
+                p = dead ? 0 : p;
+            }
+            const int li = p / (G.R * H), q = p % (G.R * H);
             const int pb = ((li * (G.R + 2) + q / H) * G.COLS + q % H) * G.S;
-            const float a0 = s_dy[p * CO + lrow];
-            const float a1 = CT > 1 ? s_dy[p * CO + 16 + lrow] : 0.0f;
+            float a0 = s_dy[p * CO + lrow];
+            float a1 = CT > 1 ? s_dy[p * CO + 16 + lrow] : 0.0f;
+            if constexpr (TAIL) {
+                a0 = dead ? 0.0f : a0;
+                a1 = dead ? 0.0f : a1;
+            }
 #pragma unroll
             for (int i = 0; i < TPW; ++i) {
                 if (wave + 4 * i >= TILES) continue;                  // wave-uniform
                 float bv = s_in[pb + boff[i]];
                 bv = bload[i] ? bv : bconst[i];
+                if constexpr (TAIL) bv = dead ? 0.0f : bv;
                 acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(bhi[i] ? a1 : a0, bv, acc[i], 0, 0, 0);
             }
         }
@@ -246,7 +274,7 @@ __global__ __launch_bounds__(256) void imp_pool_fwd_kernel(const float* __restri
                                                            uint8_t* __restrict__ arg, int64_t total, int h, int c) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
-    const int ho = h / 2;
+    const int ho = imp_half(h);
     const int ch = (int)(i % c);
     const int64_t o = i / c;
     const int ox = (int)(o % ho), oy = (int)((o / ho) % ho);
@@ -260,7 +288,7 @@ __global__ __launch_bounds__(256) void imp_pool_bwd_kernel(const float* __restri
                                                            float* __restrict__ dx, int64_t total, int h, int c) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
-    const int ho = h / 2;
+    const int ho = imp_half(h);
     const int ch = (int)(i % c);
     const int64_t o = i / c;
     const int ix = (int)(o % h), iy = (int)((o / h) % h);
@@ -272,24 +300,24 @@ __global__ __launch_bounds__(256) void imp_pool_bwd_kernel(const float* __restri
 // ---------------------------------------------------------------------------------------------------------------- launches
 unsigned blocks256(int64_t n) { return (unsigned)((n + 255) / 256); }
 
-template <int CI, int CO, int H, bool RELU_IN, bool DGRAD>
-void conv(const float* in, const float* wp, const float* bias, const float* mask, const float* res, float* out, int B, hipStream_t s) {
+template <int CI, int CO, int H, bool RELU_IN, bool DGRAD, typename TIN>
+void conv(const TIN* in, const float* wp, const float* bias, const float* mask, const float* res, float* out, int B, hipStream_t s) {
     constexpr ImpGeom G = imp_geom(CI, CO, H);
-    hipLaunchKernelGGL((imp_conv_kernel<CI, CO, H, RELU_IN, DGRAD>), dim3((unsigned)imp_bands(G, H, B)), dim3(kImpThreads), 0, s, in, wp,
+    hipLaunchKernelGGL((imp_conv_kernel<CI, CO, H, RELU_IN, DGRAD, TIN>), dim3((unsigned)imp_bands(G, H, B)), dim3(kImpThreads), 0, s, in, wp,
                        bias, mask, res, out, B);
 }
 
-template <int CI, int CO, int H, bool RELU_IN>
-void wgrad(const float* in, const float* dy, float* part, float* gw, float* gb, int B, hipStream_t s) {
+template <int CI, int CO, int H, bool RELU_IN, typename TIN>
+void wgrad(const TIN* in, const float* dy, float* part, float* gw, float* gb, int B, hipStream_t s) {
     constexpr ImpGeom G = imp_geom(CI, CO, H);
     const int64_t bands = imp_bands(G, H, B);
     const int parts = imp_parts(bands);
-    hipLaunchKernelGGL((imp_wgrad_kernel<CI, CO, H, RELU_IN>), dim3(parts), dim3(kImpThreads), 0, s, in, dy, part, B, bands, parts);
+    hipLaunchKernelGGL((imp_wgrad_kernel<CI, CO, H, RELU_IN, TIN>), dim3(parts), dim3(kImpThreads), 0, s, in, dy, part, B, bands, parts);
     hipLaunchKernelGGL(imp_fold_kernel, dim3((CO * G.JP + 15) / 16), dim3(256), 0, s, part, parts, CI, CO, G.CP, G.JP, gw, gb);
 }
 
 void pool_fwd(const float* x, float* y, uint8_t* arg, int B, int h, int c, hipStream_t s) {
-    const int64_t total = (int64_t)B * (h / 2) * (h / 2) * c;
+    const int64_t total = (int64_t)B * imp_half(h) * imp_half(h) * c;
     hipLaunchKernelGGL(imp_pool_fwd_kernel, dim3(blocks256(total)), dim3(256), 0, s, x, y, arg, total, h, c);
 }
 
@@ -301,19 +329,21 @@ void pool_bwd(const float* g, const uint8_t* arg, float* dx, int B, int h, int c
 // Workspace regions (bytes, 256-aligned): packed weights | conv / pool scratch of the largest plane | (backward) two
 // gradient planes and a temporary of the residual size | weight-gradient partials.
 size_t al256(size_t n) { return (n + 255) / 256 * 256; }
-constexpr int64_t kImpConv0Plane = (int64_t)kImpH * kImpH * 16;         // sequence 0's conv output, per image
-constexpr int64_t kImpResPlane = (int64_t)32 * 32 * 16;                 // the largest residual-block tensor, per image
+constexpr int64_t imp_conv0_plane(int f) { return (int64_t)imp_fam_h(f) * imp_fam_h(f) * 16; }   // sequence 0's conv output, per image
+constexpr int64_t imp_res_plane(int f) { return imp_plane(f, 0); }      // the largest residual-block tensor, per image
+static_assert(imp_res_plane(kImpFam64) == 32 * 32 * 16 && imp_plane(kImpFam84, 0) >= imp_plane(kImpFam84, 1), "workspace planes");
 constexpr int64_t kImpPartFloats = (int64_t)kImpMaxParts * 32 * imp_geom(32, 32, 16).JP;
 
 struct ImpWs {
     float *wp, *big, *ga, *gb, *t, *part;
 };
-size_t imp_ws_bytes(int B, bool backward) {
-    size_t n = al256(sizeof(float) * kImpPackFloats) + al256(sizeof(float) * kImpConv0Plane * B);
-    if (backward) n += 3 * al256(sizeof(float) * kImpResPlane * B) + al256(sizeof(float) * kImpPartFloats);
+size_t imp_ws_bytes(int f, int B, bool backward) {
+    size_t n = al256(sizeof(float) * kImpPackFloats) + al256(sizeof(float) * imp_conv0_plane(f) * B);
+    if (backward) n += 3 * al256(sizeof(float) * imp_res_plane(f) * B) + al256(sizeof(float) * kImpPartFloats);
     return n;
 }
-ImpWs imp_ws(void* ws, int B, bool backward) {
+ImpWs imp_ws(int f, void* ws, int B, bool backward) {
+    const int64_t kImpConv0Plane = imp_conv0_plane(f), kImpResPlane = imp_res_plane(f);
     char* p = static_cast<char*>(ws);
     ImpWs w{};
     w.wp = reinterpret_cast<float*>(p);
@@ -332,17 +362,17 @@ ImpWs imp_ws(void* ws, int B, bool backward) {
     return w;
 }
 
-template <int S>
-void fwd_seq(const float* xin, const ImpParams& prm, const float* wp, float* saved, uint8_t* argmax, float* big, float* yout, int B,
+template <int F, int S, typename TIN>
+void fwd_seq(const TIN* xin, const ImpParams& prm, const float* wp, float* saved, uint8_t* argmax, float* big, float* yout, int B,
              hipStream_t s) {
-    constexpr int CI = imp_seq_cin(S), C = imp_seq_cout(S), H = imp_seq_h(S), HP = H / 2, L = 5 * S;
-    float* P = saved + imp_saved_offset(B, S, 0);
-    float* h0 = saved + imp_saved_offset(B, S, 1);
-    float* x1 = saved + imp_saved_offset(B, S, 2);
-    float* h1 = saved + imp_saved_offset(B, S, 3);
+    constexpr int CI = imp_seq_cin(F, S), C = imp_seq_cout(S), H = imp_seq_h(F, S), HP = imp_half(H), L = 5 * S;
+    float* P = saved + imp_saved_offset(F, B, S, 0);
+    float* h0 = saved + imp_saved_offset(F, B, S, 1);
+    float* x1 = saved + imp_saved_offset(F, B, S, 2);
+    float* h1 = saved + imp_saved_offset(F, B, S, 3);
     const float* const* p = prm.p;
     conv<CI, C, H, false, false>(xin, wp + imp_pack_offset(L, false), p[2 * L + 1], nullptr, nullptr, big, B, s);
-    pool_fwd(big, P, argmax + imp_argmax_offset(B, S), B, H, C, s);
+    pool_fwd(big, P, argmax + imp_argmax_offset(F, B, S), B, H, C, s);
     conv<C, C, HP, true, false>(P, wp + imp_pack_offset(L + 1, false), p[2 * L + 3], nullptr, nullptr, h0, B, s);
     conv<C, C, HP, true, false>(h0, wp + imp_pack_offset(L + 2, false), p[2 * L + 5], nullptr, P, x1, B, s);
     conv<C, C, HP, true, false>(x1, wp + imp_pack_offset(L + 3, false), p[2 * L + 7], nullptr, nullptr, h1, B, s);
@@ -350,14 +380,14 @@ void fwd_seq(const float* xin, const ImpParams& prm, const float* wp, float* sav
 }
 
 // Backward of sequence S from g_in = dL/d(its output); returns dL/d(its input) (S > 0) in a workspace plane.
-template <int S>
-const float* bwd_seq(const float* xin, const float* wp, const float* saved, const uint8_t* argmax, const float* g_in, float* const* gr,
+template <int F, int S, typename TIN>
+const float* bwd_seq(const TIN* xin, const float* wp, const float* saved, const uint8_t* argmax, const float* g_in, float* const* gr,
                      const ImpWs& w, int B, hipStream_t s) {
-    constexpr int CI = imp_seq_cin(S), C = imp_seq_cout(S), H = imp_seq_h(S), HP = H / 2, L = 5 * S;
-    const float* P = saved + imp_saved_offset(B, S, 0);
-    const float* h0 = saved + imp_saved_offset(B, S, 1);
-    const float* x1 = saved + imp_saved_offset(B, S, 2);
-    const float* h1 = saved + imp_saved_offset(B, S, 3);
+    constexpr int CI = imp_seq_cin(F, S), C = imp_seq_cout(S), H = imp_seq_h(F, S), HP = imp_half(H), L = 5 * S;
+    const float* P = saved + imp_saved_offset(F, B, S, 0);
+    const float* h0 = saved + imp_saved_offset(F, B, S, 1);
+    const float* x1 = saved + imp_saved_offset(F, B, S, 2);
+    const float* h1 = saved + imp_saved_offset(F, B, S, 3);
     auto other = [&](const float* g) { return g == w.ga ? w.gb : w.ga; };
     float* g1 = other(g_in);
     float* g2 = other(g1);
@@ -372,7 +402,7 @@ const float* bwd_seq(const float* xin, const float* wp, const float* saved, cons
     wgrad<C, C, HP, true>(P, w.t, w.part, gr[2 * L + 2], gr[2 * L + 3], B, s);
     conv<C, C, HP, false, true>(w.t, wp + imp_pack_offset(L + 1, true), nullptr, P, g1, g2, B, s);
     // max pool, then the sequence's conv
-    pool_bwd(g2, argmax + imp_argmax_offset(B, S), w.big, B, H, C, s);
+    pool_bwd(g2, argmax + imp_argmax_offset(F, B, S), w.big, B, H, C, s);
     wgrad<CI, C, H, false>(xin, w.big, w.part, gr[2 * L], gr[2 * L + 1], B, s);
     if constexpr (S == 0) {
         return nullptr;
@@ -383,12 +413,69 @@ const float* bwd_seq(const float* xin, const float* wp, const float* saved, cons
     }
 }
 
-int imp_check(const char* fn, int B, int H, int W, int C, int ch0, int ch1, int ch2) {
+int imp_check(int f, const char* fn, int B, int H, int W, int C, int ch0, int ch1, int ch2) {
     MI355_REQUIRE(B > 0, MI355PPO_EINVAL, "%s: B=%d must be positive", fn, B);
-    MI355_REQUIRE(H == kImpH && W == kImpH && C == kImpC, MI355PPO_EINVAL, "%s: frames %dx%dx%d (only 64x64x3)", fn, H, W, C);
+    MI355_REQUIRE(H == imp_fam_h(f) && W == imp_fam_h(f) && C == imp_fam_c(f), MI355PPO_EINVAL, "%s: frames %dx%dx%d (only %dx%dx%d)", fn,
+                  H, W, C, imp_fam_h(f), imp_fam_h(f), imp_fam_c(f));
     MI355_REQUIRE(ch0 == 16 && ch1 == 32 && ch2 == 32, MI355PPO_EINVAL, "%s: channels [%d, %d, %d] (only [16, 32, 32])", fn, ch0, ch1,
                   ch2);
     return MI355PPO_OK;
+}
+
+// The forward / backward of family F on frames of type TIN (f32 for the 64 family, the ring's bytes for the 84 family).
+template <int F, typename TIN>
+int imp_fwd(const char* fn, const TIN* x, const float* const* params, float* y, float* saved, uint8_t* argmax, int B, int H, int W,
+            int C, int ch0, int ch1, int ch2, void* workspace, size_t workspace_bytes, void* stream) {
+    MI355_REQUIRE(x && params && y && saved && argmax, MI355PPO_EINVAL, "%s: null pointer", fn);
+    if (int st = imp_check(F, fn, B, H, W, C, ch0, ch1, ch2)) return st;
+    for (int i = 0; i < kImpParams; ++i) MI355_REQUIRE(params[i], MI355PPO_EINVAL, "%s: null pointer (params[%d])", fn, i);
+    MI355_REQUIRE(aligned(x, 4) && aligned(y, 16) && aligned(saved, 16), MI355PPO_EALIGN, "%s: x must be 4-, y / saved 16-byte aligned",
+                  fn);
+    MI355_REQUIRE(workspace && workspace_bytes >= imp_ws_bytes(F, B, false), MI355PPO_EWORKSPACE, "%s: workspace NULL or < %zu bytes", fn,
+                  imp_ws_bytes(F, B, false));
+    MI355_REQUIRE(aligned(workspace, 256), MI355PPO_EALIGN, "%s: workspace must be 256-byte aligned", fn);
+    hipStream_t s = as_stream(stream);
+    ImpParams prm;
+    for (int i = 0; i < kImpParams; ++i) prm.p[i] = params[i];
+    const ImpWs w = imp_ws(F, workspace, B, false);
+    hipLaunchKernelGGL(imp_pack_kernel<F>, dim3(blocks256(kImpPackFloats)), dim3(256), 0, s, prm, w.wp);
+    float* y0 = saved + imp_saved_offset(F, B, 0, 4);
+    float* y1 = saved + imp_saved_offset(F, B, 1, 4);
+    fwd_seq<F, 0>(x, prm, w.wp, saved, argmax, w.big, y0, B, s);
+    fwd_seq<F, 1>((const float*)y0, prm, w.wp, saved, argmax, w.big, y1, B, s);
+    fwd_seq<F, 2>((const float*)y1, prm, w.wp, saved, argmax, w.big, y, B, s);
+    return check_launch(fn);
+}
+
+template <int F, typename TIN>
+int imp_bwd(const char* fn, const TIN* x, const float* const* params, const float* saved, const uint8_t* argmax, const float* dy,
+            float* const* grads, int B, int H, int W, int C, int ch0, int ch1, int ch2, void* workspace, size_t workspace_bytes,
+            void* stream) {
+    MI355_REQUIRE(x && params && saved && argmax && dy && grads, MI355PPO_EINVAL, "%s: null pointer", fn);
+    if (int st = imp_check(F, fn, B, H, W, C, ch0, ch1, ch2)) return st;
+    for (int i = 0; i < kImpParams; ++i)
+        MI355_REQUIRE(params[i] && grads[i], MI355PPO_EINVAL, "%s: null pointer (params / grads[%d])", fn, i);
+    MI355_REQUIRE(aligned(x, 4) && aligned(dy, 16) && aligned(saved, 16), MI355PPO_EALIGN, "%s: x must be 4-, dy / saved 16-byte aligned",
+                  fn);
+    MI355_REQUIRE(workspace && workspace_bytes >= imp_ws_bytes(F, B, true), MI355PPO_EWORKSPACE, "%s: workspace NULL or < %zu bytes", fn,
+                  imp_ws_bytes(F, B, true));
+    MI355_REQUIRE(aligned(workspace, 256), MI355PPO_EALIGN, "%s: workspace must be 256-byte aligned", fn);
+    hipStream_t s = as_stream(stream);
+    ImpParams prm;
+    for (int i = 0; i < kImpParams; ++i) prm.p[i] = params[i];
+    const ImpWs w = imp_ws(F, workspace, B, true);
+    hipLaunchKernelGGL(imp_pack_kernel<F>, dim3(blocks256(kImpPackFloats)), dim3(256), 0, s, prm, w.wp);
+    const float* g = bwd_seq<F, 2>(saved + imp_saved_offset(F, B, 1, 4), w.wp, saved, argmax, dy, grads, w, B, s);
+    g = bwd_seq<F, 1>(saved + imp_saved_offset(F, B, 0, 4), w.wp, saved, argmax, g, grads, w, B, s);
+    bwd_seq<F, 0>(x, w.wp, saved, argmax, g, grads, w, B, s);
+    return check_launch(fn);
+}
+
+bool imp_pool_shape(int B, int H, int W, int C) {
+    for (int f : {kImpFam64, kImpFam84})
+        for (int s = 0; s < kImpSeqs; ++s)
+            if (B > 0 && H == W && H == imp_seq_h(f, s) && C == imp_seq_cout(s)) return true;
+    return false;
 }
 
 }  // namespace
@@ -396,65 +483,52 @@ int imp_check(const char* fn, int B, int H, int W, int C, int ch0, int ch1, int 
 
 using namespace mi355ppo;
 
-extern "C" MI355PPO_API int64_t mi355ppo_impala_saved_floats(int B) { return B > 0 ? imp_saved_floats(B) : 0; }
-extern "C" MI355PPO_API int64_t mi355ppo_impala_argmax_bytes(int B) { return B > 0 ? imp_argmax_bytes(B) : 0; }
-extern "C" MI355PPO_API size_t mi355ppo_impala_workspace_bytes(int B, int backward) { return B > 0 ? imp_ws_bytes(B, backward != 0) : 0; }
+extern "C" MI355PPO_API int64_t mi355ppo_impala_saved_floats(int B) { return B > 0 ? imp_saved_floats(kImpFam64, B) : 0; }
+extern "C" MI355PPO_API int64_t mi355ppo_impala_argmax_bytes(int B) { return B > 0 ? imp_argmax_bytes(kImpFam64, B) : 0; }
+extern "C" MI355PPO_API size_t mi355ppo_impala_workspace_bytes(int B, int backward) {
+    return B > 0 ? imp_ws_bytes(kImpFam64, B, backward != 0) : 0;
+}
+extern "C" MI355PPO_API int64_t mi355ppo_impala84_saved_floats(int B) { return B > 0 ? imp_saved_floats(kImpFam84, B) : 0; }
+extern "C" MI355PPO_API int64_t mi355ppo_impala84_argmax_bytes(int B) { return B > 0 ? imp_argmax_bytes(kImpFam84, B) : 0; }
+extern "C" MI355PPO_API size_t mi355ppo_impala84_workspace_bytes(int B, int backward) {
+    return B > 0 ? imp_ws_bytes(kImpFam84, B, backward != 0) : 0;
+}
 
 extern "C" MI355PPO_API int mi355ppo_impala_fwd_f32(const float* x, const float* const* params, float* y, float* saved, uint8_t* argmax,
                                                     int B, int H, int W, int C, int ch0, int ch1, int ch2, void* workspace,
                                                     size_t workspace_bytes, void* stream) {
-    const char* fn = "mi355ppo_impala_fwd_f32";
-    MI355_REQUIRE(x && params && y && saved && argmax, MI355PPO_EINVAL, "%s: null pointer", fn);
-    if (int st = imp_check(fn, B, H, W, C, ch0, ch1, ch2)) return st;
-    for (int i = 0; i < kImpParams; ++i) MI355_REQUIRE(params[i], MI355PPO_EINVAL, "%s: null pointer (params[%d])", fn, i);
-    MI355_REQUIRE(aligned(x, 4) && aligned(y, 16) && aligned(saved, 16), MI355PPO_EALIGN, "%s: x must be 4-, y / saved 16-byte aligned",
-                  fn);
-    MI355_REQUIRE(workspace && workspace_bytes >= imp_ws_bytes(B, false), MI355PPO_EWORKSPACE, "%s: workspace NULL or < %zu bytes", fn,
-                  imp_ws_bytes(B, false));
-    MI355_REQUIRE(aligned(workspace, 256), MI355PPO_EALIGN, "%s: workspace must be 256-byte aligned", fn);
-    hipStream_t s = as_stream(stream);
-    ImpParams prm;
-    for (int i = 0; i < kImpParams; ++i) prm.p[i] = params[i];
-    const ImpWs w = imp_ws(workspace, B, false);
-    hipLaunchKernelGGL(imp_pack_kernel, dim3(blocks256(kImpPackFloats)), dim3(256), 0, s, prm, w.wp);
-    float* y0 = saved + imp_saved_offset(B, 0, 4);
-    float* y1 = saved + imp_saved_offset(B, 1, 4);
-    fwd_seq<0>(x, prm, w.wp, saved, argmax, w.big, y0, B, s);
-    fwd_seq<1>(y0, prm, w.wp, saved, argmax, w.big, y1, B, s);
-    fwd_seq<2>(y1, prm, w.wp, saved, argmax, w.big, y, B, s);
-    return check_launch(fn);
+    return imp_fwd<kImpFam64>("mi355ppo_impala_fwd_f32", x, params, y, saved, argmax, B, H, W, C, ch0, ch1, ch2, workspace,
+                              workspace_bytes, stream);
 }
 
 extern "C" MI355PPO_API int mi355ppo_impala_bwd_f32(const float* x, const float* const* params, const float* saved, const uint8_t* argmax,
                                                     const float* dy, float* const* grads, int B, int H, int W, int C, int ch0, int ch1,
                                                     int ch2, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* fn = "mi355ppo_impala_bwd_f32";
-    MI355_REQUIRE(x && params && saved && argmax && dy && grads, MI355PPO_EINVAL, "%s: null pointer", fn);
-    if (int st = imp_check(fn, B, H, W, C, ch0, ch1, ch2)) return st;
-    for (int i = 0; i < kImpParams; ++i)
-        MI355_REQUIRE(params[i] && grads[i], MI355PPO_EINVAL, "%s: null pointer (params / grads[%d])", fn, i);
-    MI355_REQUIRE(aligned(x, 4) && aligned(dy, 16) && aligned(saved, 16), MI355PPO_EALIGN, "%s: x must be 4-, dy / saved 16-byte aligned",
-                  fn);
-    MI355_REQUIRE(workspace && workspace_bytes >= imp_ws_bytes(B, true), MI355PPO_EWORKSPACE, "%s: workspace NULL or < %zu bytes", fn,
-                  imp_ws_bytes(B, true));
-    MI355_REQUIRE(aligned(workspace, 256), MI355PPO_EALIGN, "%s: workspace must be 256-byte aligned", fn);
-    hipStream_t s = as_stream(stream);
-    ImpParams prm;
-    for (int i = 0; i < kImpParams; ++i) prm.p[i] = params[i];
-    const ImpWs w = imp_ws(workspace, B, true);
-    hipLaunchKernelGGL(imp_pack_kernel, dim3(blocks256(kImpPackFloats)), dim3(256), 0, s, prm, w.wp);
-    const float* g = bwd_seq<2>(saved + imp_saved_offset(B, 1, 4), w.wp, saved, argmax, dy, grads, w, B, s);
-    g = bwd_seq<1>(saved + imp_saved_offset(B, 0, 4), w.wp, saved, argmax, g, grads, w, B, s);
-    bwd_seq<0>(x, w.wp, saved, argmax, g, grads, w, B, s);
-    return check_launch(fn);
+    return imp_bwd<kImpFam64>("mi355ppo_impala_bwd_f32", x, params, saved, argmax, dy, grads, B, H, W, C, ch0, ch1, ch2, workspace,
+                              workspace_bytes, stream);
+}
+
+extern "C" MI355PPO_API int mi355ppo_impala84_fwd_u8(const uint8_t* x, const float* const* params, float* y, float* saved,
+                                                     uint8_t* argmax, int B, int H, int W, int C, int ch0, int ch1, int ch2,
+                                                     void* workspace, size_t workspace_bytes, void* stream) {
+    return imp_fwd<kImpFam84>("mi355ppo_impala84_fwd_u8", x, params, y, saved, argmax, B, H, W, C, ch0, ch1, ch2, workspace,
+                              workspace_bytes, stream);
+}
+
+extern "C" MI355PPO_API int mi355ppo_impala84_bwd_u8(const uint8_t* x, const float* const* params, const float* saved,
+                                                     const uint8_t* argmax, const float* dy, float* const* grads, int B, int H, int W,
+                                                     int C, int ch0, int ch1, int ch2, void* workspace, size_t workspace_bytes,
+                                                     void* stream) {
+    return imp_bwd<kImpFam84>("mi355ppo_impala84_bwd_u8", x, params, saved, argmax, dy, grads, B, H, W, C, ch0, ch1, ch2, workspace,
+                              workspace_bytes, stream);
 }
 
 extern "C" MI355PPO_API int mi355ppo_impala_maxpool_fwd_f32(const float* x, float* y, uint8_t* argmax, int B, int H, int W, int C,
                                                             void* stream) {
     const char* fn = "mi355ppo_impala_maxpool_fwd_f32";
     MI355_REQUIRE(x && y && argmax, MI355PPO_EINVAL, "%s: null pointer", fn);
-    MI355_REQUIRE(B > 0 && H == W && ((H == 64 && C == 16) || (H == 32 && C == 32) || (H == 16 && C == 32)), MI355PPO_EINVAL,
-                  "%s: B=%d %dx%dx%d (only the trunk's 64x64x16, 32x32x32, 16x16x32)", fn, B, H, W, C);
+    MI355_REQUIRE(imp_pool_shape(B, H, W, C), MI355PPO_EINVAL,
+                  "%s: B=%d %dx%dx%d (only the trunks' 64x64x16, 32x32x32, 16x16x32, 84x84x16, 42x42x32, 21x21x32)", fn, B, H, W, C);
     pool_fwd(x, y, argmax, B, H, C, as_stream(stream));
     return check_launch(fn);
 }
@@ -463,8 +537,8 @@ extern "C" MI355PPO_API int mi355ppo_impala_maxpool_bwd_f32(const float* dy, con
                                                             void* stream) {
     const char* fn = "mi355ppo_impala_maxpool_bwd_f32";
     MI355_REQUIRE(dy && argmax && dx, MI355PPO_EINVAL, "%s: null pointer", fn);
-    MI355_REQUIRE(B > 0 && H == W && ((H == 64 && C == 16) || (H == 32 && C == 32) || (H == 16 && C == 32)), MI355PPO_EINVAL,
-                  "%s: B=%d %dx%dx%d (only the trunk's 64x64x16, 32x32x32, 16x16x32)", fn, B, H, W, C);
+    MI355_REQUIRE(imp_pool_shape(B, H, W, C), MI355PPO_EINVAL,
+                  "%s: B=%d %dx%dx%d (only the trunks' 64x64x16, 32x32x32, 16x16x32, 84x84x16, 42x42x32, 21x21x32)", fn, B, H, W, C);
     pool_bwd(dy, argmax, dx, B, H, C, as_stream(stream));
     return check_launch(fn);
 }

@@ -38,28 +38,43 @@
 
 namespace mi355ppo {
 
-constexpr int kImpH = 64;                 // procgen frames: 64 x 64 x 3
+constexpr int kImpH = 64;                 // procgen frames: 64 x 64 x 3 (the 64 family)
 constexpr int kImpC = 3;
+constexpr int kImpFam64 = 0;              // frame family of a trunk: 64 x 64 x 3 f32 frames, planes 64 -> 32 -> 16 -> 8
+constexpr int kImpFam84 = 1;              // 84 x 84 x 4 u8 Atari stacks, planes 84 -> 42 -> 21 -> 11 (the pool's (h + 1) / 2)
 constexpr int kImpSeqs = 3;
 constexpr int kImpLayers = 15;
 constexpr int kImpParams = 30;
 constexpr int kImpThreads = 256;          // 4 waves per workgroup in every conv launch
 constexpr int kImpMaxParts = 512;         // weight-gradient partials per layer (fewer when there are fewer bands)
 
-MI355_HD constexpr int imp_seq_cin(int s) { return s == 0 ? 3 : (s == 1 ? 16 : 32); }
+MI355_HD constexpr int imp_fam_h(int f) { return f == kImpFam84 ? 84 : kImpH; }
+MI355_HD constexpr int imp_fam_c(int f) { return f == kImpFam84 ? 4 : kImpC; }
+MI355_HD constexpr int imp_half(int h) { return (h + 1) / 2; }                  // max_pool2d(3, stride 2, pad 1)'s output size
+MI355_HD constexpr int imp_seq_cin(int f, int s) { return s == 0 ? imp_fam_c(f) : (s == 1 ? 16 : 32); }
 MI355_HD constexpr int imp_seq_cout(int s) { return s == 0 ? 16 : 32; }
-MI355_HD constexpr int imp_seq_h(int s) { return kImpH >> s; }                  // input size of sequence s
-MI355_HD constexpr int imp_layer_cin(int l) { return l % 5 == 0 ? imp_seq_cin(l / 5) : imp_seq_cout(l / 5); }
+MI355_HD constexpr int imp_seq_h(int f, int s) {                                // input size of sequence s
+    int h = imp_fam_h(f);
+    for (int i = 0; i < s; ++i) h = imp_half(h);
+    return h;
+}
+MI355_HD constexpr int imp_layer_cin(int f, int l) { return l % 5 == 0 ? imp_seq_cin(f, l / 5) : imp_seq_cout(l / 5); }
 MI355_HD constexpr int imp_layer_cout(int l) { return imp_seq_cout(l / 5); }
-MI355_HD constexpr int imp_layer_h(int l) { return l % 5 == 0 ? imp_seq_h(l / 5) : imp_seq_h(l / 5) / 2; }
 MI355_HD constexpr int imp_cpad(int c) { return (c + 3) & ~3; }
 
 // One conv launch's tiling for (input channels CI, output channels CO, size H = W):
 //   a wave owns MT 16-pixel tiles x NT 16-channel tiles (4 accumulators); a workgroup (4 waves) owns PIX = 64 MT consecutive
-//   output pixels: R rows of NI images (NI > 1 only at 8 x 8).  The LDS input tile holds NI x (R + 2) rows x (H + 2) columns
-//   with a zero halo, S floats per pixel (CP + 4: the 16 pixels x 4 channels of one MFMA operand fall in 64 distinct banks).
+//   output pixel SLOTS: a band of R = min(h, PIX / h) whole rows of NI images (NI > 1 only at 8 x 8, where R = h).  The LDS
+//   input tile holds NI x (R + 2) rows x (H + 2) columns with a zero halo, S floats per pixel (CP + 4: the 16 pixels x 4
+//   channels of one MFMA operand fall in 64 distinct banks).  An image has BPI = ceil(h / R) bands.
+// Ragged bands (the 84 family; in the 64 family R h NI = PIX and R divides h, so nothing below is ever dead): slots at or
+//   beyond LIVE = NI R h, and rows at or beyond h in an image's last band, are DEAD.  A dead slot reads a valid LDS cell (slot
+//   0's, or the zero rows staged below the image) and is never stored.  In the weight gradient a band's live pixels are its
+//   first npix = (live rows) h slots; the chain advances four pixels per MFMA, so a band whose npix is no multiple of 4 ends
+//   with 4 - npix % 4 dead steps that enter every chain of the part as fmaf(0.0f, 0.0f, acc) (NOT skipped: the twin adds the
+//   same steps; their only effect is that a -0.0f sum becomes +0.0f).
 struct ImpGeom {
-    int CP, S, KP, KS, NT, MT, PIX, R, NI, COLS, ROWS, LDS_IN, LDS_W, JP;
+    int CP, S, KP, KS, NT, MT, PIX, R, NI, COLS, ROWS, LDS_IN, LDS_W, JP, BPI, LIVE;
 };
 MI355_HD constexpr ImpGeom imp_geom(int ci, int co, int h) {
     ImpGeom g{};
@@ -77,21 +92,28 @@ MI355_HD constexpr ImpGeom imp_geom(int ci, int co, int h) {
     g.LDS_IN = g.ROWS * g.COLS * g.S;
     g.LDS_W = g.KP * co;
     g.JP = (g.KP + 1 + 15) / 16 * 16;     // weight-gradient columns: KP taps x channels, the bias column, zero padding
+    g.BPI = (h + g.R - 1) / g.R;
+    g.LIVE = g.NI * g.R * h;
     return g;
 }
 
 // Bands (one workgroup's PIX pixels) of a batch, and band b's first image / first row.
 MI355_HD int64_t imp_bands(const ImpGeom& g, int h, int B) {
-    return g.NI == 1 ? (int64_t)B * (h / g.R) : ((int64_t)B + g.NI - 1) / g.NI;
+    return g.NI == 1 ? (int64_t)B * g.BPI : ((int64_t)B + g.NI - 1) / g.NI;
 }
 MI355_HD void imp_band(const ImpGeom& g, int h, int64_t b, int64_t* img0, int* y0) {
     if (g.NI == 1) {
-        *img0 = b / (h / g.R);
-        *y0 = (int)(b % (h / g.R)) * g.R;
+        *img0 = b / g.BPI;
+        *y0 = (int)(b % g.BPI) * g.R;
     } else {
         *img0 = b * g.NI;
         *y0 = 0;
     }
+}
+// Live pixels of the band at (img0, y0): whole rows, of the images that exist.
+MI355_HD int imp_band_pixels(const ImpGeom& g, int h, int64_t img0, int y0, int B) {
+    if (g.NI > 1) return (int)(B - img0 < g.NI ? B - img0 : g.NI) * g.R * h;
+    return (h - y0 < g.R ? h - y0 : g.R) * h;
 }
 MI355_HD int imp_parts(int64_t bands) { return bands < kImpMaxParts ? (int)bands : kImpMaxParts; }
 constexpr int kImpFoldGroups = 16;       // runs of consecutive parts folded side by side, then in order
@@ -106,6 +128,8 @@ MI355_HD void imp_part_range(int64_t bands, int parts, int q, int64_t* b0, int64
 
 // The layer input as the convolution reads it.
 MI355_HD float imp_relu(float v) { return v > 0.0f ? v : 0.0f; }
+// A frame byte of the 84 family as layer 0 reads it: torch's ``x / 255.0`` on a u8 tensor (an f32 division, rounded once).
+MI355_HD float imp_u8(uint8_t b) { return (float)b / 255.0f; }
 
 // Wt[k][n] of the forward: W (co, ci, 3, 3) with ci < cin, zero for the padded channels.
 MI355_HD float imp_wt_fwd(const float* w, int cin, int k, int n) {
@@ -145,7 +169,7 @@ MI355_HD float imp_pool_window(const float* src, int h, int c_stride, int oy, in
     return best;
 }
 
-// Max-pool backward of input pixel (iy, ix) of one channel: g / arg point at channel c of output pixel (0, 0), ho = h / 2.
+// Max-pool backward of input pixel (iy, ix) of one channel: g / arg point at channel c of output pixel (0, 0), ho = imp_half(h).
 MI355_HD float imp_pool_grad(const float* g, const uint8_t* arg, int ho, int c_stride, int iy, int ix) {
     float s = 0.0f;
     const int oya = iy / 2, oyb = (iy + 1) / 2 < ho - 1 ? (iy + 1) / 2 : ho - 1;
@@ -161,23 +185,25 @@ MI355_HD float imp_pool_grad(const float* g, const uint8_t* arg, int ho, int c_s
 // Saved-activation layout (floats, one plane of B images each, in this order): per sequence s the pooled output P (= res
 // block 0's input), res block 0's conv0 output h0, its output x1, res block 1's conv0 output h1, and for s < 2 its output y
 // (the next sequence's input; the last sequence's output is the caller's y).  Argmax bytes: one plane per sequence.
-MI355_HD int64_t imp_plane(int s) { const int hp = imp_seq_h(s) / 2; return (int64_t)hp * hp * imp_seq_cout(s); }
-MI355_HD int64_t imp_saved_floats(int B) {
+// Every plane of both families is a multiple of 4 floats, so each starts 16-byte aligned for any B.
+MI355_HD constexpr int64_t imp_plane(int f, int s) { const int hp = imp_half(imp_seq_h(f, s)); return (int64_t)hp * hp * imp_seq_cout(s); }
+MI355_HD constexpr int64_t imp_saved_floats(int f, int B) {
     int64_t n = 0;
-    for (int s = 0; s < kImpSeqs; ++s) n += (s < 2 ? 5 : 4) * imp_plane(s);
+    for (int s = 0; s < kImpSeqs; ++s) n += (s < 2 ? 5 : 4) * imp_plane(f, s);
     return n * B;
 }
-MI355_HD int64_t imp_saved_offset(int B, int s, int which) {    // which: 0 P, 1 h0, 2 x1, 3 h1, 4 y
+MI355_HD constexpr int64_t imp_saved_offset(int f, int B, int s, int which) {    // which: 0 P, 1 h0, 2 x1, 3 h1, 4 y
     int64_t n = 0;
-    for (int t = 0; t < s; ++t) n += (t < 2 ? 5 : 4) * imp_plane(t);
-    return (n + which * imp_plane(s)) * B;
+    for (int t = 0; t < s; ++t) n += (t < 2 ? 5 : 4) * imp_plane(f, t);
+    return (n + which * imp_plane(f, s)) * B;
 }
-MI355_HD int64_t imp_argmax_bytes(int B) { return (imp_plane(0) + imp_plane(1) + imp_plane(2)) * B; }
-MI355_HD int64_t imp_argmax_offset(int B, int s) {
+MI355_HD constexpr int64_t imp_argmax_bytes(int f, int B) { return (imp_plane(f, 0) + imp_plane(f, 1) + imp_plane(f, 2)) * B; }
+MI355_HD constexpr int64_t imp_argmax_offset(int f, int B, int s) {
     int64_t n = 0;
-    for (int t = 0; t < s; ++t) n += imp_plane(t);
+    for (int t = 0; t < s; ++t) n += imp_plane(f, t);
     return n * B;
 }
+static_assert(imp_saved_floats(kImpFam84, 1) == 227168 && imp_argmax_bytes(kImpFam84, 1) == 46208, "84 family: 887 KiB saved per image");
 
 }  // namespace mi355ppo
 
@@ -186,8 +212,9 @@ namespace mi355ppo {
 // Packed conv weights (the workspace's first region): one piece per launch that reads weights -- the 15 forward convolutions,
 // then the data gradients of layers 1 .. 14 (layer 0's input, the frames, needs none).  A piece is in MFMA fragment order:
 // float (ks NT + nt) 64 + lane = Wt[4 ks + lane / 16][16 nt + lane % 16], so a lane's B operand is one linear LDS read.
+// The pieces do not depend on the frame family: 3 and 4 frame channels both pad to CP = 4, and layer 0 has no data gradient.
 MI355_HD constexpr int imp_pack_floats(int l, bool dgrad) {
-    return dgrad ? 9 * imp_layer_cout(l) * imp_layer_cin(l) : 9 * imp_cpad(imp_layer_cin(l)) * imp_layer_cout(l);
+    return dgrad ? 9 * imp_layer_cout(l) * imp_layer_cin(kImpFam64, l) : 9 * imp_cpad(imp_layer_cin(kImpFam64, l)) * imp_layer_cout(l);
 }
 MI355_HD constexpr int imp_pack_offset(int l, bool dgrad) {
     int n = 0;

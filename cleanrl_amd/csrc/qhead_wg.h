@@ -19,10 +19,10 @@ struct QhPasses {
     const float *h[3], *w[3], *b[3];           // one {h, W, b} per pass (grid z), up to three
 };
 
-// z[pass][r, j] = b[j] + sum_k h[r, col0(j) + k] * W[j, k], k < 512.  ROW: the row width of h -- kDaH (col0 = 0) or kRbH2 (both
-// streams' hidden columns, col0 = rb_col0(j, na)).  grid (ceil(J / 32), ceil(M / 8), passes); z: passes x M x J.  h's 8 rows sit in
+// z[pass][r, j] = b[j] + sum_k h[r, col0(j) + k] * W[j, k], k < K (512; 256 for the QDagger head).  ROW: the row width of h -- K
+// (col0 = 0) or kRbH2 (both streams' hidden columns, col0 = rb_col0(j, na)).  grid (ceil(J / 32), ceil(M / 8), passes); z: passes x M x J.  h's 8 rows sit in
 // LDS (16 | 32 KB), W streams from L2 through a 32 x 64 LDS tile (8.3 KB); thread (row, output) runs its dot product in ascending k.
-template <int ROW>
+template <int ROW, int K = kDaH>
 __global__ __launch_bounds__(256) void qh_fwd_kernel(QhPasses H, float* __restrict__ z, int M, int J, int na) {
     __shared__ float hs[kOpRows * ROW], wt[kQhTJ * kQhTLd];
     const int t = threadIdx.x, pass = blockIdx.z, j0 = blockIdx.x * kQhTJ, r0 = blockIdx.y * kOpRows;
@@ -33,13 +33,13 @@ __global__ __launch_bounds__(256) void qh_fwd_kernel(QhPasses H, float* __restri
         hs[i] = (r0 + r < M) ? h[(int64_t)r0 * ROW + i] : 0.0f;
     }
     const int jj = t & (kQhTJ - 1), r = t / kQhTJ;
-    const float* x = hs + r * ROW + (ROW == kDaH ? 0 : rb_col0(j0 + jj, na));
+    const float* x = hs + r * ROW + (ROW == K ? 0 : rb_col0(j0 + jj, na));
     float acc = 0.0f;
-    for (int k0 = 0; k0 < kDaH; k0 += kQhTK) {
+    for (int k0 = 0; k0 < K; k0 += kQhTK) {
         __syncthreads();                                    // hs is complete (first pass); the previous tile has been read
         for (int i = t; i < kQhTJ * kQhTK; i += 256) {
             const int wj = i / kQhTK, wk = i - wj * kQhTK;
-            wt[wj * kQhTLd + wk] = (j0 + wj < J) ? W[(int64_t)(j0 + wj) * kDaH + k0 + wk] : 0.0f;
+            wt[wj * kQhTLd + wk] = (j0 + wj < J) ? W[(int64_t)(j0 + wj) * K + k0 + wk] : 0.0f;
         }
         __syncthreads();
         for (int kk = 0; kk < kQhTK; ++kk) acc = op_mac(acc, x[k0 + kk], wt[jj * kQhTLd + kk]);
@@ -47,9 +47,9 @@ __global__ __launch_bounds__(256) void qh_fwd_kernel(QhPasses H, float* __restri
     if (r0 + r < M && j0 + jj < J) z[((int64_t)pass * M + r0 + r) * J + j0 + jj] = acc + H.b[pass][j0 + jj];
 }
 
-template <int ROW>
+template <int ROW, int K = kDaH>
 static int qh_fwd_launch(hipStream_t s, const QhPasses& H, int passes, float* z, int M, int J, int na) {
-    hipLaunchKernelGGL(qh_fwd_kernel<ROW>, dim3((J + kQhTJ - 1) / kQhTJ, op_tiles(M), passes), dim3(256), 0, s, H, z, M, J, na);
+    hipLaunchKernelGGL((qh_fwd_kernel<ROW, K>), dim3((J + kQhTJ - 1) / kQhTJ, op_tiles(M), passes), dim3(256), 0, s, H, z, M, J, na);
     return check_launch("qh_fwd_kernel");
 }
 

@@ -17,7 +17,7 @@ import ctypes
 import torch
 
 from . import _lib
-from .ops import ATARI_FRAME, IMPALA_CHANNELS, _lstm_dims, _ptr_array, dqn_counts, dqn_head_limits_ok, dqn_limits_ok, offpolicy_counts, pqn_param_count, radam_schedule, rainbow_head_limits_ok, rainbow_new_buffer, rainbow_noisy_counts, rainbow_noisy_limits_ok, _rainbow_head, _rainbow_head_update_args, sac_actor_count, sacd_limits_ok, _frame_ring2, _sacd_heads, trxl_dims  # noqa: F401  (one definition for both modules)
+from .ops import ATARI_FRAME, IMPALA84_OUT, IMPALA_CHANNELS, _lstm_dims, _ptr_array, dqn_counts, dqn_head_limits_ok, dqn_limits_ok, offpolicy_counts, pqn_param_count, radam_schedule, rainbow_head_limits_ok, rainbow_new_buffer, rainbow_noisy_counts, rainbow_noisy_limits_ok, _rainbow_head, _rainbow_head_update_args, sac_actor_count, sacd_limits_ok, _frame_ring2, _sacd_heads, trxl_dims  # noqa: F401  (one definition for both modules)
 
 LOSS_SCALARS = 7
 
@@ -289,22 +289,50 @@ def impala_backward(x, params, saved, arg, dy):
     return grads
 
 
+def impala84_forward(x, params):
+    """The Atari IMPALA-CNN trunk through ``mi355ppo_impala84_fwd_u8_cpu``: x (B,84,84,4) u8 channels-last stacks -> (y (B,11,11,32)
+    channels-last, saved, argmax).  Same arithmetic as the device kernels (csrc/impala_rows.h)."""
+    lib = _lib.load()
+    if x.dtype != torch.uint8:
+        raise TypeError(f"x: expected uint8 frame stacks, got {x.dtype}")
+    B, H, W, C = x.shape
+    xs, ps = x.contiguous(), [_f32(p) for p in params]
+    y = torch.empty((B, *IMPALA84_OUT))
+    saved = torch.empty(max(int(lib.mi355ppo_impala84_saved_floats(B)), 1))
+    arg = torch.empty(max(int(lib.mi355ppo_impala84_argmax_bytes(B)), 1), dtype=torch.uint8)
+    _lib.call("mi355ppo_impala84_fwd_u8_cpu", _p(xs), _ptr_array([_p_t(p) for p in ps]), _p(y), _p(saved), _p(arg), B, H, W, C, *IMPALA_CHANNELS)
+    return y, saved, arg
+
+
+def impala84_backward(x, params, saved, arg, dy):
+    """Backward of ``impala84_forward`` through ``mi355ppo_impala84_bwd_u8_cpu`` -> the 30 parameter gradients (none for the frames)."""
+    if x.dtype != torch.uint8:
+        raise TypeError(f"x: expected uint8 frame stacks, got {x.dtype}")
+    B, H, W, C = x.shape
+    xs, ps, g = x.contiguous(), [_f32(p) for p in params], _f32(dy)
+    grads = [torch.empty(p.shape) for p in ps]
+    _lib.call("mi355ppo_impala84_bwd_u8_cpu", _p(xs), _ptr_array([_p_t(p) for p in ps]), _p(saved), _p(arg), _p(g),
+              _ptr_array([_p_t(t) for t in grads]), B, H, W, C, *IMPALA_CHANNELS)
+    return grads
+
+
 def impala_maxpool_forward(x):
-    """The trunk's max pool (3, stride 2, pad 1) on channels-last x (B,H,W,C) -> (y (B,H/2,W/2,C), argmax bytes)."""
+    """The trunks' max pool (3, stride 2, pad 1) on channels-last x (B,H,W,C) -> (y (B,(H+1)/2,(W+1)/2,C), argmax bytes)."""
     B, H, W, C = x.shape
     xs = _f32(x)
-    y = torch.empty((B, H // 2, W // 2, C))
-    arg = torch.empty((B, H // 2, W // 2, C), dtype=torch.uint8)
+    y = torch.empty((B, (H + 1) // 2, (W + 1) // 2, C))
+    arg = torch.empty((B, (H + 1) // 2, (W + 1) // 2, C), dtype=torch.uint8)
     _lib.call("mi355ppo_impala_maxpool_fwd_f32_cpu", _p(xs), _p(y), _p(arg), B, H, W, C)
     return y, arg
 
 
-def impala_maxpool_backward(dy, arg):
-    """Backward of ``impala_maxpool_forward``: dx (B,H,W,C) from dy and the argmax."""
+def impala_maxpool_backward(dy, arg, size=None):
+    """Backward of ``impala_maxpool_forward``: dx (B,H,H,C) from dy and the argmax, H = ``size`` (default 2 Ho)."""
     B, Ho, Wo, C = dy.shape
     g = _f32(dy)
-    dx = torch.empty((B, 2 * Ho, 2 * Wo, C))
-    _lib.call("mi355ppo_impala_maxpool_bwd_f32_cpu", _p(g), _p(arg.contiguous()), _p(dx), B, 2 * Ho, 2 * Wo, C)
+    H = 2 * Ho if size is None else int(size)
+    dx = torch.empty((B, H, H, C))
+    _lib.call("mi355ppo_impala_maxpool_bwd_f32_cpu", _p(g), _p(arg.contiguous()), _p(dx), B, H, H, C)
     return dx
 
 
@@ -692,6 +720,26 @@ def c51_head_fwd_bwd(h, h_next, w, b, w_target, b_target, atoms, actions, reward
     _lib.call("mi355ppo_c51_head_fwd_bwd_f32_cpu", *nets, _in(atoms, torch.float32, (na,), "atoms"), *batch, float(gamma), float(v_min),
               float(v_max), *_head_grads(dh, dw, db, scalars, M, hidden, J), _opt_out(next_pmfs_out, M * na, "next_pmfs_out"),
               _opt_out(target_pmfs_out, M * na, "target_pmfs_out"), M, hidden, int(n_actions), na)
+    return scalars
+
+
+# ------------------------------------------------------------------------------------------- QDagger head twins (csrc/qdagger.hip)
+def qdagger_head_act(h, w, b, actions_out, q_out=None):
+    N, hidden = h.shape
+    n = b.numel()
+    _lib.call("mi355ppo_qdagger_head_act_f32_cpu", _in(h, torch.float32, (N, hidden), "h"), _in(w, torch.float32, (n, hidden), "w"),
+              _in(b, torch.float32, (n,), "b"), _out(actions_out, torch.int64, N, "actions_out"), _opt_out(q_out, N * n, "q_out"), N, hidden, n)
+    return actions_out
+
+
+def qdagger_head_fwd_bwd(h, h_next, w, b, w_target, b_target, teacher_q, actions, rewards, dones, gamma, temperature, distill_coeff, dh, dw, db,
+                         scalars, target_q_out=None, td_target_out=None):
+    n = b.numel()
+    M, hidden, nets, batch = _head_update_ptrs(h, h_next, w, b, w_target, b_target, actions, rewards, dones, n)
+    _lib.call("mi355ppo_qdagger_head_fwd_bwd_f32_cpu", *nets, _in(teacher_q, torch.float32, (M, n), "teacher_q"), *batch, float(gamma),
+              float(temperature), float(distill_coeff), _out(dh, torch.float32, M * hidden, "dh"), _out(dw, torch.float32, n * hidden, "dw"),
+              _out(db, torch.float32, n, "db"), _out(scalars, torch.float32, 4, "scalars"), _opt_out(target_q_out, M * n, "target_q_out"),
+              _opt_out(td_target_out, M, "td_target_out"), M, hidden, n)
     return scalars
 
 

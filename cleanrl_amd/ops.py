@@ -24,7 +24,8 @@ __all__ = [
     "ppo_loss_categorical", "ppo_loss_normal", "obs_u8_to_f32", "obs_nchw_to_nhwc_u8", "clip_adam_", "PPOLossCategorical", "PPOLossNormal",
     "CategoricalLogProbEntropy", "NormalLogProbEntropy", "LOSS_SCALAR_NAMES", "lstm_seq_forward", "lstm_seq_backward", "LSTMSeq",
     "lstm_seq", "lstm_seq_dw_hh", "impala_forward", "impala_backward", "impala_maxpool_forward", "impala_maxpool_backward",
-    "ImpalaTrunk", "impala_trunk", "impala_param_shapes", "trxl_attn_forward", "trxl_attn_backward", "TrXLMemoryAttention", "trxl_memory_attention",
+    "ImpalaTrunk", "impala_trunk", "impala_param_shapes", "impala84_forward", "impala84_backward", "Impala84Trunk", "impala84_trunk",
+    "impala84_param_shapes", "impala84_params", "qdagger_head_limits_ok", "qdagger_head_act", "qdagger_head_fwd_bwd", "trxl_attn_forward", "trxl_attn_backward", "TrXLMemoryAttention", "trxl_memory_attention",
     "pqn_param_count", "pqn_egreedy", "pqn_qlambda", "pqn_td_loss", "pqn_mlp_forward", "pqn_mlp_act", "pqn_mlp_td_fwd_bwd", "radam_schedule",
     "clip_radam_", "clip_radam_sched_", "pqn_lstm_act", "pqn_lstm_td_fwd_bwd", "offpolicy_counts", "replay_add", "ddpg_act", "td3_target",
     "td3_critic_fwd_bwd", "td3_actor_fwd_bwd", "polyak_", "sac_actor_count", "sac_policy", "sac_target", "sac_actor_fwd_bwd", "sac_alpha_",
@@ -1011,22 +1012,23 @@ def impala_backward(x, params, saved, arg, dy):
 
 
 def impala_maxpool_forward(x):
-    """The trunk's max pool (3, stride 2, pad 1) alone on channels-last x (B,H,W,C) -> (y, argmax bytes (B,H/2,W/2,C))."""
+    """The trunks' max pool (3, stride 2, pad 1) alone on channels-last x (B,H,W,C) -> (y, argmax bytes (B,(H+1)/2,(W+1)/2,C))."""
     _chk(x, torch.float32, "x")
     B, H, W, C = x.shape
-    y = torch.empty((B, H // 2, W // 2, C), device=x.device)
-    arg = torch.empty((B, H // 2, W // 2, C), dtype=torch.uint8, device=x.device)
+    y = torch.empty((B, (H + 1) // 2, (W + 1) // 2, C), device=x.device)
+    arg = torch.empty((B, (H + 1) // 2, (W + 1) // 2, C), dtype=torch.uint8, device=x.device)
     _launch("mi355ppo_impala_maxpool_fwd_f32", x.device, _ptr(x), _ptr(y), _ptr(arg), B, H, W, C)
     return y, arg
 
 
-def impala_maxpool_backward(dy, arg):
-    """Backward of ``impala_maxpool_forward``: dx (B,2Ho,2Wo,C)."""
+def impala_maxpool_backward(dy, arg, size=None):
+    """Backward of ``impala_maxpool_forward``: dx (B,H,H,C), H = ``size`` (default 2 Ho; the 21 -> 11 pool needs it said)."""
     _chk(dy, torch.float32, "dy")
     B, Ho, Wo, C = dy.shape
     _chk(arg, torch.uint8, "argmax", tuple(dy.shape))
-    dx = torch.empty((B, 2 * Ho, 2 * Wo, C), device=dy.device)
-    _launch("mi355ppo_impala_maxpool_bwd_f32", dy.device, _ptr(dy), _ptr(arg), _ptr(dx), B, 2 * Ho, 2 * Wo, C)
+    H = 2 * Ho if size is None else int(size)
+    dx = torch.empty((B, H, H, C), device=dy.device)
+    _launch("mi355ppo_impala_maxpool_bwd_f32", dy.device, _ptr(dy), _ptr(arg), _ptr(dx), B, H, H, C)
     return dx
 
 
@@ -1063,6 +1065,118 @@ def impala_trunk(x, params):
     fwd, _ = twins(x, *_IMPALA)
     ps = [p.detach().contiguous() for p in params]
     _impala_check(x, ps)
+    return fwd(x.contiguous(), ps)[0]
+
+
+# ----------------------------------------------------------------- IMPALA-CNN trunk on Atari stacks (the 84 family)
+IMPALA84_FRAME = (84, 84, 4)
+IMPALA84_OUT = (11, 11, 32)
+
+
+def impala84_param_shapes():
+    """The 30 trunk parameters' shapes of the Atari IMPALA-CNN (qdagger_dqn_atari_impalacnn.py:164-181) in state_dict order."""
+    shapes, cin = [], IMPALA84_FRAME[2]
+    for c in IMPALA_CHANNELS:
+        for i in range(5):
+            shapes += [(c, cin if i == 0 else c, 3, 3), (c,)]
+        cin = c
+    return shapes
+
+
+def impala84_params(net):
+    """The trunk's 30 parameters of a module whose ``network[0..2]`` are the three ConvSequences."""
+    return [p for i in range(3) for p in net.network[i].parameters()]
+
+
+def _impala84_check(x, params):
+    if x.dim() != 4 or tuple(x.shape[1:]) != IMPALA84_FRAME or x.shape[0] < 1:
+        raise ValueError(f"x: expected channels-last frame stacks (B, 84, 84, 4), got {tuple(x.shape)}")
+    if x.dtype != torch.uint8:
+        raise TypeError(f"x: expected the ring's uint8 rows, got {x.dtype} (the trunk reads bytes; no f32 copy of the frames is made)")
+    if len(params) != 30:
+        raise ValueError(f"params: expected the trunk's 30 weights and biases, got {len(params)}")
+    for i, (p, shp) in enumerate(zip(params, impala84_param_shapes())):
+        if tuple(p.shape) != shp:
+            raise ValueError(f"params[{i}]: expected shape {shp}, got {tuple(p.shape)} (channels must be {list(IMPALA_CHANNELS)})")
+
+
+def impala84_forward(x, params):
+    """The IMPALA-CNN trunk of the QDagger student on the HIP kernels of csrc/impala.hip: x (B,84,84,4) u8 channels-last rows
+    (what ``replay_gather_u8`` writes), read as byte / 255; params the 30 conv weights / biases in state_dict order.  Returns
+    ``(y (B,11,11,32) channels-last, saved, argmax)``; the last two feed ``impala84_backward``."""
+    lib = _lib.load()
+    _impala84_check(x, params)
+    _chk(x, torch.uint8, "x")
+    for i, p in enumerate(params):
+        _chk(p, torch.float32, f"params[{i}]")
+    B, dev = x.shape[0], x.device
+    y = torch.empty((B, *IMPALA84_OUT), device=dev)
+    saved = torch.empty(int(lib.mi355ppo_impala84_saved_floats(B)), device=dev)
+    arg = torch.empty(int(lib.mi355ppo_impala84_argmax_bytes(B)), dtype=torch.uint8, device=dev)
+    nws = int(lib.mi355ppo_impala84_workspace_bytes(B, 0))
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    _launch("mi355ppo_impala84_fwd_u8", dev, _ptr(x), _ptr_array(params), _ptr(y), _ptr(saved), _ptr(arg), B, *IMPALA84_FRAME,
+            *IMPALA_CHANNELS, _ptr(ws), nws)
+    return y, saved, arg
+
+
+def impala84_backward(x, params, saved, arg, dy):
+    """Backward of ``impala84_forward``: dy (B,11,11,32) channels-last -> the 30 parameter gradients (one flat buffer's views,
+    written by deterministic fixed-order folds); no gradient for the frames."""
+    lib = _lib.load()
+    _impala84_check(x, params)
+    B, dev = x.shape[0], x.device
+    _chk(x, torch.uint8, "x")
+    _chk(dy, torch.float32, "dy", (B, *IMPALA84_OUT))
+    _chk(saved, torch.float32, "saved", (int(lib.mi355ppo_impala84_saved_floats(B)),))
+    _chk(arg, torch.uint8, "argmax", (int(lib.mi355ppo_impala84_argmax_bytes(B)),))
+    for i, p in enumerate(params):
+        _chk(p, torch.float32, f"params[{i}]")
+    flat = torch.empty(sum(p.numel() for p in params), device=dev)
+    grads, o = [], 0
+    for p in params:
+        grads.append(flat[o:o + p.numel()].view(p.shape))
+        o += p.numel()
+    nws = int(lib.mi355ppo_impala84_workspace_bytes(B, 1))
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    _launch("mi355ppo_impala84_bwd_u8", dev, _ptr(x), _ptr_array(params), _ptr(saved), _ptr(arg), _ptr(dy), _ptr_array(grads), B,
+            *IMPALA84_FRAME, *IMPALA_CHANNELS, _ptr(ws), nws)
+    return grads
+
+
+_IMPALA84 = ("impala84_forward", "impala84_backward")
+
+
+class Impala84Trunk(torch.autograd.Function):
+    """Differentiable ``(x, *params) -> y``: the three ConvSequences of the Atari IMPALA-CNN on u8 channels-last stacks x
+    (B,84,84,4), y (B,11,11,32) channels-last.  The backward returns the 30 parameter gradients and None for the frames.  The
+    HIP kernels run for CUDA tensors, the host twins for CPU ones (same arithmetic)."""
+
+    @staticmethod
+    def forward(ctx, x, *params):
+        fwd, _ = twins(x, *_IMPALA84)
+        xs = x.detach().contiguous()
+        ps = [p.detach().contiguous() for p in params]
+        _impala84_check(xs, ps)
+        y, saved, arg = fwd(xs, ps)
+        ctx.save_for_backward(xs, saved, arg, *ps)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xs, saved, arg, *ps = ctx.saved_tensors
+        _, bwd = twins(xs, *_IMPALA84)
+        grads = bwd(xs, ps, saved, arg, dy.contiguous())
+        return (None, *grads)
+
+
+def impala84_trunk(x, params):
+    """``Impala84Trunk.apply`` when a gradient is wanted, else the forward alone (acting, the target network)."""
+    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        return Impala84Trunk.apply(x, *params)
+    fwd, _ = twins(x, *_IMPALA84)
+    ps = [p.detach().contiguous() for p in params]
+    _impala84_check(x, ps)
     return fwd(x.contiguous(), ps)[0]
 
 
@@ -1718,6 +1832,56 @@ def c51_head_fwd_bwd(h, h_next, w, b, w_target, b_target, atoms, actions, reward
     _launch("mi355ppo_c51_head_fwd_bwd_f32", h.device, _ptr(h), _ptr(h_next), _ptr(w), _ptr(b), _ptr(w_target), _ptr(b_target), _ptr(atoms),
             _ptr(actions), _ptr(rewards), _ptr(dones), float(gamma), float(v_min), float(v_max), _ptr(dh), _ptr(dw), _ptr(db), _ptr(scalars),
             _ptr(next_pmfs_out), _ptr(target_pmfs_out), M, hidden, int(n_actions), na, _ptr(ws), ws.numel())
+    return scalars
+
+
+# ------------------------------------------------------------------------------------------- QDagger head (csrc/qdagger.hip)
+QDAGGER_HIDDEN = 256
+QDAGGER_MAX_ROWS = 1024
+
+
+def qdagger_head_limits_ok(n_actions: int, rows: int = 1, hidden: int = QDAGGER_HIDDEN) -> bool:
+    """What the QDagger head kernels take (anything else is ``MI355PPO_EINVAL`` from the C ABI)."""
+    return hidden == QDAGGER_HIDDEN and 2 <= n_actions <= DQN_MAX_ACT and 1 <= rows <= QDAGGER_MAX_ROWS
+
+
+def qdagger_head_act(h, w, b, actions_out, q_out=None):
+    """The student's greedy action on ``h`` (N, 256): ``Linear(256, n)`` and ``dqn_act``'s argmax -> actions_out (N,) int64."""
+    N, hidden, n = _head(h, w, b)
+    _chk(actions_out, torch.int64, "actions_out", (N,))
+    if q_out is not None:
+        _chk(q_out, torch.float32, "q_out", (N, n))
+    ws = _workspace(h.device, _lib.load().mi355ppo_qdagger_head_act_workspace_bytes(N, n))
+    _launch("mi355ppo_qdagger_head_act_f32", h.device, _ptr(h), _ptr(w), _ptr(b), _ptr(actions_out), _ptr(q_out), N, hidden, n, _ptr(ws), ws.numel())
+    return actions_out
+
+
+def qdagger_head_fwd_bwd(h, h_next, w, b, w_target, b_target, teacher_q, actions, rewards, dones, gamma: float, temperature: float,
+                         distill_coeff: float, dh, dw, db, scalars, target_q_out=None, td_target_out=None):
+    """qdagger_dqn_atari_impalacnn.py's update behind the student's hidden layer in three launches: the TD loss against the target
+    network plus ``distill_coeff`` x the KL against the teacher's softmax (``teacher_q`` (M, n): its raw Q values), summed over the
+    batch.  OVERWRITES ``dh`` (M, 256), ``dw`` / ``db`` (e.g. views of the flat gradient); scalars (4,) = {loss, q_loss, distill_loss,
+    mean old_val}."""
+    M, hidden, n = _head(h, w, b)
+    _chk(h_next, torch.float32, "h_next", (M, hidden))
+    _chk(w_target, torch.float32, "w_target", (n, hidden))
+    _chk(b_target, torch.float32, "b_target", (n,))
+    _chk(teacher_q, torch.float32, "teacher_q", (M, n))
+    _chk(actions, torch.int64, "actions", (M,))
+    _chk(rewards, torch.float32, "rewards", (M,))
+    _chk(dones, torch.float32, "dones", (M,))
+    _chk(dh, torch.float32, "dh", (M, hidden))
+    _chk(dw, torch.float32, "dw", (n, hidden))
+    _chk(db, torch.float32, "db", (n,))
+    _chk(scalars, torch.float32, "scalars", (4,))
+    if target_q_out is not None:
+        _chk(target_q_out, torch.float32, "target_q_out", (M, n))
+    if td_target_out is not None:
+        _chk(td_target_out, torch.float32, "td_target_out", (M,))
+    ws = _workspace(h.device, _lib.load().mi355ppo_qdagger_head_workspace_bytes(M, n))
+    _launch("mi355ppo_qdagger_head_fwd_bwd_f32", h.device, _ptr(h), _ptr(h_next), _ptr(w), _ptr(b), _ptr(w_target), _ptr(b_target), _ptr(teacher_q),
+            _ptr(actions), _ptr(rewards), _ptr(dones), float(gamma), float(temperature), float(distill_coeff), _ptr(dh), _ptr(dw), _ptr(db),
+            _ptr(scalars), _ptr(target_q_out), _ptr(td_target_out), M, hidden, n, _ptr(ws), ws.numel())
     return scalars
 
 

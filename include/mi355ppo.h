@@ -474,8 +474,22 @@ MI355PPO_API int mi355ppo_impala_fwd_f32(const float* x, const float* const* par
 MI355PPO_API int mi355ppo_impala_bwd_f32(const float* x, const float* const* params, const float* saved, const uint8_t* argmax,
                                          const float* dy, float* const* grads, int B, int H, int W, int C, int ch0, int ch1, int ch2,
                                          void* workspace, size_t workspace_bytes, void* stream);
-/* The trunk's max pool alone (channels-last; only its three shapes: 64x64x16, 32x32x32, 16x16x32): y (B, H/2, W/2, C) and the
- * argmax byte per output; the backward writes dx (B, H, W, C) from dy and the argmax. */
+/* The same trunk on Atari frame stacks (the student of qdagger_dqn_atari_impalacnn.py:164-184): x is (B, 84, 84, 4) u8
+ * channels-last rows as mi355ppo_replay_gather_u8 writes them, read by layer 0 as byte / 255.0f (no f32 copy of the frames is
+ * made, no gradient for them); planes 84 -> 42 -> 21 -> 11 (the pool's (h + 1) / 2), y (B, 11, 11, 32).  Same kernels, orders and
+ * tie rule as the 64x64x3 family on ragged bands (csrc/impala_rows.h); sizes from the mi355ppo_impala84_* functions.  Only
+ * B > 0, H = W = 84, C = 4 and channels (16, 32, 32); anything else returns MI355PPO_EINVAL before any launch. */
+MI355PPO_API int64_t mi355ppo_impala84_saved_floats(int B);
+MI355PPO_API int64_t mi355ppo_impala84_argmax_bytes(int B);
+MI355PPO_API size_t mi355ppo_impala84_workspace_bytes(int B, int backward);
+MI355PPO_API int mi355ppo_impala84_fwd_u8(const uint8_t* x, const float* const* params, float* y, float* saved, uint8_t* argmax, int B,
+                                          int H, int W, int C, int ch0, int ch1, int ch2, void* workspace, size_t workspace_bytes,
+                                          void* stream);
+MI355PPO_API int mi355ppo_impala84_bwd_u8(const uint8_t* x, const float* const* params, const float* saved, const uint8_t* argmax,
+                                          const float* dy, float* const* grads, int B, int H, int W, int C, int ch0, int ch1, int ch2,
+                                          void* workspace, size_t workspace_bytes, void* stream);
+/* The trunks' max pool alone (channels-last; only their shapes: 64x64x16, 32x32x32, 16x16x32 and 84x84x16, 42x42x32, 21x21x32):
+ * y (B, (H+1)/2, (W+1)/2, C) and the argmax byte per output; the backward writes dx (B, H, W, C) from dy and the argmax. */
 MI355PPO_API int mi355ppo_impala_maxpool_fwd_f32(const float* x, float* y, uint8_t* argmax, int B, int H, int W, int C, void* stream);
 MI355PPO_API int mi355ppo_impala_maxpool_bwd_f32(const float* dy, const uint8_t* argmax, float* dx, int B, int H, int W, int C,
                                                  void* stream);
@@ -549,6 +563,11 @@ MI355PPO_API int mi355ppo_impala_fwd_f32_cpu(const float* x, const float* const*
 MI355PPO_API int mi355ppo_impala_bwd_f32_cpu(const float* x, const float* const* params, const float* saved, const uint8_t* argmax,
                                              const float* dy, float* const* grads, int B, int H, int W, int C, int ch0, int ch1,
                                              int ch2);
+MI355PPO_API int mi355ppo_impala84_fwd_u8_cpu(const uint8_t* x, const float* const* params, float* y, float* saved, uint8_t* argmax,
+                                              int B, int H, int W, int C, int ch0, int ch1, int ch2);
+MI355PPO_API int mi355ppo_impala84_bwd_u8_cpu(const uint8_t* x, const float* const* params, const float* saved, const uint8_t* argmax,
+                                              const float* dy, float* const* grads, int B, int H, int W, int C, int ch0, int ch1,
+                                              int ch2);
 MI355PPO_API int mi355ppo_impala_maxpool_fwd_f32_cpu(const float* x, float* y, uint8_t* argmax, int B, int H, int W, int C);
 MI355PPO_API int mi355ppo_impala_maxpool_bwd_f32_cpu(const float* dy, const uint8_t* argmax, float* dx, int B, int H, int W, int C);
 
@@ -1365,6 +1384,35 @@ MI355PPO_API int mi355ppo_sacd_actor_fwd_bwd_f32_cpu(const float* h_pi, const fl
                                                      const float* b_q2, const float* alpha, double target_entropy, float* dh, float* dw,
                                                      float* db, float* entropy_rows_out, float* actor_loss_out, int M, int hidden,
                                                      int n_actions);
+
+/* ---------------------------------------------------------------------------------------------
+ * QDagger head (cleanrl/qdagger_dqn_atari_impalacnn.py:294-306, 403-415; csrc/qdagger.hip, row math csrc/qdagger_rows.h): Linear(256, n)
+ * of the IMPALA student behind mi355ppo_impala84_fwd_u8 and the torch Linear(3872, 256).
+ *   act      actions_out[r] = argmax_a q[r, a] (ties to the lowest index, NaN is the maximum); q_out (N, n) optional.  Two launches.
+ *   fwd_bwd  td_target = r + gamma max_j q_target(h_next)[j] (1 - d);  q_loss = mean (td_target - q[r, a_r])^2;  with t = teacher_q / T,
+ *            s = q / T:  distill = SUM over rows and actions of -softmax(t) (log_softmax(s) - log_softmax(t));
+ *            loss = q_loss + distill_coeff * distill.  OVERWRITES dh (M, 256), dw (n, 256), db (n) with the gradient of loss
+ *            (dq is dense over the actions: dW[j, k] sums all rows in ascending r); scalars_out (4) = {loss, q_loss, distill,
+ *            mean q[r, a_r]}; target_q_out (M, n) / td_target_out (M) optional.  Three launches, plain f32, no atomics.
+ * Limits: hidden == 256, 2 <= n_actions <= 18, 1 <= rows <= 1024, temperature > 0; anything else returns MI355PPO_EINVAL before any
+ * launch.  workspace: the *_workspace_bytes functions' size, 16-byte aligned. */
+MI355PPO_API size_t mi355ppo_qdagger_head_act_workspace_bytes(int N, int n_actions);
+MI355PPO_API int mi355ppo_qdagger_head_act_f32(const float* h, const float* w, const float* b, int64_t* actions_out, float* q_out, int N,
+                                               int hidden, int n_actions, void* workspace, size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_qdagger_head_act_f32_cpu(const float* h, const float* w, const float* b, int64_t* actions_out, float* q_out, int N,
+                                                   int hidden, int n_actions);
+MI355PPO_API size_t mi355ppo_qdagger_head_workspace_bytes(int M, int n_actions);
+MI355PPO_API int mi355ppo_qdagger_head_fwd_bwd_f32(const float* h, const float* h_next, const float* w, const float* b, const float* w_target,
+                                                   const float* b_target, const float* teacher_q, const int64_t* actions, const float* rewards,
+                                                   const float* dones, double gamma, double temperature, double distill_coeff, float* dh,
+                                                   float* dw, float* db, float* scalars_out, float* target_q_out, float* td_target_out, int M,
+                                                   int hidden, int n_actions, void* workspace, size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_qdagger_head_fwd_bwd_f32_cpu(const float* h, const float* h_next, const float* w, const float* b,
+                                                       const float* w_target, const float* b_target, const float* teacher_q,
+                                                       const int64_t* actions, const float* rewards, const float* dones, double gamma,
+                                                       double temperature, double distill_coeff, float* dh, float* dw, float* db,
+                                                       float* scalars_out, float* target_q_out, float* td_target_out, int M, int hidden,
+                                                       int n_actions);
 
 #ifdef __cplusplus
 }

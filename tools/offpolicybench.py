@@ -1,7 +1,7 @@
 """ddpg_continuous_action.py / td3_continuous_action.py / sac_continuous_action.py with both ``MI355PPO_OFFPOLICY`` backends, in one
 process, alternating.
 
-    python tools/offpolicybench.py [--reps 20] [--scripts td3 ddpg sac dqn dqn_atari rainbow rainbow_buffer sac_atari]
+    python tools/offpolicybench.py [--reps 20] [--scripts td3 ddpg sac dqn dqn_atari rainbow rainbow_buffer sac_atari qdagger]
 
 Times, at each script's defaults (batch 256) on a HalfCheetah-shaped (obs 17 / act 6) and a Humanoid-shaped (376 / 17) task:
 one rollout step including the action's copy to the host, one critic-only training step and one step with the delayed policy
@@ -13,7 +13,9 @@ and the three noise compositions.  ``--scripts rainbow_buffer`` times rainbow_at
 by the reference's rules (NumPy tree walk, batch upload, ``loss_per_sample`` read back) against the device buffer, per add, per
 sample and per priority update; and the four NoisyLinear layers' ``mu + sigma * eps`` by torch against the one-launch compose, for a
 4-action and an 18-action game.  ``--scripts sac_atari`` times sac_atari.py at its batch of 64 for a 4-action and an 18-action game: one rollout
-step (the policy's sample) and one update (critics, actor, temperature).
+step (the policy's sample) and one update (critics, actor, temperature).  ``--scripts qdagger`` times qdagger_dqn_atari_impalacnn.py at batch 32
+for a 4-action and an 18-action game: one greedy step of the student, one offline update (``distill_coeff`` 1) and one online update
+(``distill_coeff`` 0.37); the ``fused`` side runs the IMPALA trunk kernels too (``impala_backend`` fused).
 """
 from __future__ import annotations
 
@@ -275,6 +277,41 @@ def bench_sac_atari(a, dev):
         print(json.dumps(row), flush=True)
 
 
+def make_qdagger(n, backend, dev, fill=256):
+    from cleanrl_amd.agents import AtariDQNNetwork, AtariImpalaQNetwork
+    from cleanrl_amd.learner_qdagger import QDaggerLearner
+
+    torch.manual_seed(1)
+    np.random.seed(1)
+    envs = E.AtariReplayVecEnv(1, seed=1, n_actions=n)
+    q, t = AtariImpalaQNetwork(envs).to(dev), AtariImpalaQNetwork(envs).to(dev)
+    q.impala_backend = t.impala_backend = backend
+    t.load_state_dict(q.state_dict())
+    args = SimpleNamespace(buffer_size=fill * 2, batch_size=32, learning_rate=1e-4, gamma=0.99, tau=1.0, temperature=1.0)
+    return fill_ring(QDaggerLearner(q, t, AtariDQNNetwork(envs).to(dev), args, envs, dev, backend=backend), envs, fill)
+
+
+def bench_qdagger(a, dev):
+    """qdagger_dqn_atari_impalacnn.py at batch 32: one greedy step of the student, one offline and one online update."""
+    for shape, n in ATARI_SHAPES.items():
+        learners = {b: make_qdagger(n, b, dev) for b in ("torch", "fused")}
+        legs = {"greedy_step": lambda L, obs: L.act(obs, 1, 0.0), "offline_update": lambda L, obs: L.train_step(1.0),
+                "online_update": lambda L, obs: L.train_step(0.37)}
+        times = {leg: {b: [] for b in learners} for leg in legs}
+        for rep in range(a.warmup + a.reps):
+            for leg, fn in legs.items():
+                for b, (L, obs) in learners.items():                     # alternating: both backends see the same box state
+                    us = timed(lambda: fn(L, obs), dev)
+                    if rep >= a.warmup:
+                        times[leg][b].append(us)
+        row = {"script": "qdagger", "shape": shape, "n_actions": n, "batch": 32, "device": str(dev), "reps": a.reps}
+        for leg in legs:
+            for b in learners:
+                row[f"{leg}_{b}_us"] = round(statistics.median(times[leg][b]), 1)
+            row[f"{leg}_speedup"] = round(row[f"{leg}_torch_us"] / row[f"{leg}_fused_us"], 2)
+        print(json.dumps(row), flush=True)
+
+
 def make(script, O, A, backend, dev, fill=4096):
     td3 = script == "td3"
     torch.manual_seed(1)
@@ -338,6 +375,9 @@ def main():
             continue
         if script == "sac_atari":
             bench_sac_atari(a, dev)
+            continue
+        if script == "qdagger":
+            bench_qdagger(a, dev)
             continue
         for shape, (O, A) in SHAPES.items():
             learners = {b: make(script, O, A, b, dev) for b in ("torch", "fused")}
