@@ -22,7 +22,8 @@ Backend: ``MI355PPO_OFFPOLICY=torch|fused``, default ``torch`` (DESIGN.md sectio
 the action space's stream in the reference's order.  On the CPU ``fused`` runs the host twins around torch's convolutions.
 
 The flat buffers, the target update, the torch update and the logged scalars are ``learner_dqn.QLearner``'s.  ``check_frames`` and
-``Trunks`` serve ``learner_rainbow.RainbowLearner`` too.
+``Trunks`` serve ``learner_rainbow.RainbowLearner`` too; ``FrameRing`` (the ring's allocation, its pinned staging through
+``staging.Staging``, ``store``) serves ``learner_sac_atari.SACAtariLearner`` and ``learner_qdagger.QDaggerLearner`` too.
 """
 from __future__ import annotations
 
@@ -34,6 +35,7 @@ import torch
 from . import ops
 from .learner_dqn import QLearner
 from .learner_offpolicy import advance
+from .staging import Staging
 
 FRAME = (4, 84, 84)
 
@@ -85,7 +87,61 @@ class HostFrameBuffer:
                 t(self.dones[bi, ei].reshape(-1, 1)), t(self.rewards[bi, ei].reshape(-1, 1)))
 
 
-class AtariDQNLearner(QLearner):
+class FrameRing:
+    """What the learners on u8 frame rings share, mixed in in front of a ``DeviceRing``: the ``fused`` ring with ``FRAME_ARRAYS`` frame
+    arrays (1: the memory-optimised ring, next_obs one slot on; 2: ``observations`` and ``next_observations``), its staging groups
+    (``staging.Staging``), the batch buffers, ``store`` and the staging of the rollout's frames."""
+
+    FRAME_ARRAYS = 1
+
+    def _alloc_ring(self, M: int):
+        dev, N, K = self.device, self.N, self.FRAME_ARRAYS
+        H, W, C = ops.ATARI_FRAME
+        try:
+            frames = tuple(torch.zeros((self.slots, N, H, W, C), dtype=torch.uint8, device=dev) for _ in range(K))
+        except (RuntimeError, MemoryError) as e:
+            raise ValueError(f"MI355PPO_OFFPOLICY=fused: {'a frame ring' if K == 1 else 'two frame rings'} of {self.slots} slots x {N} envs "
+                             f"({K * self.slots * N * H * W * C / 1e9:.1f} GB) cannot be allocated on {dev}; lower --buffer-size or use "
+                             f"MI355PPO_OFFPOLICY=torch") from e
+        self.ring = frames + (torch.zeros((self.slots, N), dtype=torch.int64, device=dev), torch.zeros((self.slots, N), device=dev),
+                              torch.zeros((self.slots, N), device=dev))
+        # obs | next_obs as the env gives them, the actions, rewards | dones; the rollout's frames; the batch's draws
+        self._step_stage = Staging(dev, frames=((2, N, C, H, W), torch.uint8), act=((N,), torch.int64), rd=((2, N), torch.float32))
+        self._obs_stage = Staging(dev, frames=((N, C, H, W), torch.uint8))
+        self._idx_stage = Staging(dev, idx=((2, M), torch.int64))
+        self._obs_hwc = torch.zeros((N, H, W, C), dtype=torch.uint8, device=dev)
+        self._batch = (torch.zeros((2 * M, H, W, C), dtype=torch.uint8, device=dev), torch.zeros(M, dtype=torch.int64, device=dev),
+                       torch.zeros(M, device=dev), torch.zeros(M, device=dev))
+        self._norm = torch.zeros(1, dtype=torch.float32, device=dev)
+
+    def _stage_frames(self, obs):
+        """The rollout's frames as (N, 84, 84, 4) u8 rows where the trunks read them."""
+        self._obs_stage.begin()["frames"].copy_(torch.from_numpy(np.ascontiguousarray(obs, np.uint8)).reshape((self.N,) + FRAME))
+        frames = self._obs_stage.push()["frames"]
+        if self.device.type == "cuda":
+            return ops.obs_nchw_to_nhwc_u8(frames, out=self._obs_hwc)
+        return frames.permute(0, 2, 3, 1).contiguous()
+
+    def store(self, obs, real_next_obs, actions, rewards, terminations):
+        """``rb.add(obs, real_next_obs, actions, rewards, terminations, infos)``."""
+        if not self.fused:
+            self.rb.add(obs, real_next_obs, actions, rewards, terminations)
+            self.pos, self.full = self.rb.pos, self.rb.full
+            return
+        h = self._step_stage.begin()
+        fh, rh = h["frames"], h["rd"]
+        fh[0].copy_(torch.from_numpy(np.ascontiguousarray(obs, np.uint8)).reshape(fh[0].shape))
+        fh[1].copy_(torch.from_numpy(np.ascontiguousarray(real_next_obs, np.uint8)).reshape(fh[1].shape))
+        h["act"].copy_(torch.from_numpy(np.asarray(actions, np.int64).reshape(-1)))
+        rh[0].copy_(torch.from_numpy(np.asarray(rewards, np.float32).reshape(-1)))
+        rh[1].copy_(torch.from_numpy(np.asarray(terminations, np.float32).reshape(-1)))
+        d = self._step_stage.push()
+        add = self.g.replay_add_u8 if self.FRAME_ARRAYS == 1 else self.g.replay_add2_u8
+        add(self.ring, self.pos, d["frames"][0], d["frames"][1], d["act"], d["rd"][0], d["rd"][1])
+        advance(self)
+
+
+class AtariDQNLearner(FrameRing, QLearner):
     """``c51``: the networks are ``AtariC51Network`` (atoms, ``get_action``) and the update is the categorical one."""
 
     def __init__(self, q_network, target_network, args, envs, device, c51: bool, backend=None):
@@ -112,30 +168,6 @@ class AtariDQNLearner(QLearner):
             raise ValueError(f"MI355PPO_OFFPOLICY=fused: the fused Q heads take 2 <= n_actions <= {ops.DQN_MAX_ACT}, n_atoms <= "
                              f"{ops.DQN_MAX_ATOMS} (at least 2 for c51), n_actions * n_atoms <= {ops.DQN_HEAD_MAX_OUT} and batch_size <= "
                              f"{ops.DQN_HEAD_MAX_ROWS}, not {self.n} / {self.n_atoms} / {self.args.batch_size}; use MI355PPO_OFFPOLICY=torch")
-
-    def _alloc_ring(self, M: int):
-        dev, N = self.device, self.N
-        H, W, C = ops.ATARI_FRAME
-        try:
-            frames = torch.zeros((self.slots, N, H, W, C), dtype=torch.uint8, device=dev)
-        except (RuntimeError, MemoryError) as e:
-            raise ValueError(f"MI355PPO_OFFPOLICY=fused: a frame ring of {self.slots} slots x {N} envs ({self.slots * N * H * W * C / 1e9:.1f} GB) "
-                             f"cannot be allocated on {dev}; lower --buffer-size or use MI355PPO_OFFPOLICY=torch") from e
-        self.ring = (frames, torch.zeros((self.slots, N), dtype=torch.int64, device=dev), torch.zeros((self.slots, N), device=dev),
-                     torch.zeros((self.slots, N), device=dev))
-        pin = (lambda t: t.pin_memory()) if dev.type == "cuda" else (lambda t: t)
-        self._frames_host = pin(torch.zeros((2, N, C, H, W), dtype=torch.uint8))      # obs | next_obs as the env gives them
-        self._act_host = pin(torch.zeros(N, dtype=torch.int64))
-        self._rd_host = pin(torch.zeros((2, N), dtype=torch.float32))
-        self._idx_host = pin(torch.zeros((2, M), dtype=torch.int64))
-        self._frames_dev = torch.zeros_like(self._frames_host, device=dev)
-        self._act_dev = torch.zeros(N, dtype=torch.int64, device=dev)
-        self._rd_dev = torch.zeros((2, N), dtype=torch.float32, device=dev)
-        self._idx = torch.zeros((2, M), dtype=torch.int64, device=dev)
-        self._obs_hwc = torch.zeros((N, H, W, C), dtype=torch.uint8, device=dev)
-        self._batch = (torch.zeros((2 * M, H, W, C), dtype=torch.uint8, device=dev), torch.zeros(M, dtype=torch.int64, device=dev),
-                       torch.zeros(M, device=dev), torch.zeros(M, device=dev))
-        self._norm = torch.zeros(1, dtype=torch.float32, device=dev)
 
     # ------------------------------------------------------------------ the networks below the head
     def _hidden(self, net, frames_hwc):
@@ -167,35 +199,9 @@ class AtariDQNLearner(QLearner):
                 else:
                     actions = torch.argmax(self.q_network(x), dim=1)
                 return actions.cpu().numpy()
-            self._frames_host[0].copy_(torch.from_numpy(np.ascontiguousarray(obs, np.uint8)).reshape(self._frames_host[0].shape))
-            if self.device.type == "cuda":
-                self._frames_dev[0].copy_(self._frames_host[0], non_blocking=True)
-                rows = ops.obs_nchw_to_nhwc_u8(self._frames_dev[0], out=self._obs_hwc)
-            else:
-                rows = self._frames_host[0].permute(0, 2, 3, 1).contiguous()
             w, b = self._head(self.online)
-            self.g.dqn_head_act(self._hidden(self.q_network, rows).contiguous(), w, b, self.n, self._greedy, atoms=self.atoms)
+            self.g.dqn_head_act(self._hidden(self.q_network, self._stage_frames(obs)).contiguous(), w, b, self.n, self._greedy, atoms=self.atoms)
             return self._copy_out(self._greedy)
-
-    def store(self, obs, real_next_obs, actions, rewards, terminations):
-        """``rb.add(obs, real_next_obs, actions, rewards, terminations, infos)``."""
-        if not self.fused:
-            self.rb.add(obs, real_next_obs, actions, rewards, terminations)
-            self.pos, self.full = self.rb.pos, self.rb.full
-            return
-        fh, ah, rh = self._frames_host, self._act_host, self._rd_host
-        fh[0].copy_(torch.from_numpy(np.ascontiguousarray(obs, np.uint8)).reshape(fh[0].shape))
-        fh[1].copy_(torch.from_numpy(np.ascontiguousarray(real_next_obs, np.uint8)).reshape(fh[1].shape))
-        ah.copy_(torch.from_numpy(np.asarray(actions, np.int64).reshape(-1)))
-        rh[0].copy_(torch.from_numpy(np.asarray(rewards, np.float32).reshape(-1)))
-        rh[1].copy_(torch.from_numpy(np.asarray(terminations, np.float32).reshape(-1)))
-        if self.device.type == "cuda":
-            self._frames_dev.copy_(fh, non_blocking=True)
-            self._act_dev.copy_(ah, non_blocking=True)
-            self._rd_dev.copy_(rh, non_blocking=True)
-            fh, ah, rh = self._frames_dev, self._act_dev, self._rd_dev
-        self.g.replay_add_u8(self.ring, self.pos, fh[0], fh[1], ah, rh[0], rh[1])
-        advance(self)
 
     def sample_indices(self, batch_size: int):
         """The memory-optimised ``ReplayBuffer.sample``: never slot ``pos`` once full; then ``env_indices``."""

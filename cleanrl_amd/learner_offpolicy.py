@@ -37,6 +37,7 @@ import torch.nn.functional as F
 import torch.optim as optim
 
 from . import ops
+from .staging import Staging
 
 BACKENDS = ("torch", "fused")
 
@@ -86,7 +87,8 @@ def advance(ring):
 class DeviceRing:
     """What the learners on the replay ring share.  ``__init__`` resolves the backend (``fused``), reads ``N`` / ``O`` from ``envs`` and
     sets ``space``, ``g`` (``ops.twins``), ``slots`` and ``pos`` / ``full``; then ``torch`` gets ``rb`` (a ``HostReplayBuffer``) and
-    ``fused`` the ring: the five device arrays and the pinned staging of a step's transitions, indices and observations.  ``act_width``
+    ``fused`` the ring: the five device arrays and three ``staging.Staging`` groups (a step's transition, its observations, a batch's
+    indices; pinned and guarded on a GPU).  ``act_width``
     is the ring's action width ``A`` and ``act_dtype`` the host buffer's action dtype: ``prod(space.shape)`` / float32 for the
     continuous families, ``1`` / int64 for a Discrete space.  ``store``, ``sample_indices`` and the helpers of the flat parameter
     buffers (``_alloc_flat``, ``_adopt``, ``_adam``, ``_copy_out``, ``_flat``) are here once.  Base of ``OffPolicyLearner``,
@@ -127,16 +129,10 @@ class DeviceRing:
         self.ring = (torch.zeros((self.slots, N, O), device=dev), torch.zeros((self.slots, N, O), device=dev),
                      torch.zeros((self.slots, N, A), device=dev), torch.zeros((self.slots, N), device=dev),
                      torch.zeros((self.slots, N), device=dev))
-        pin = dev.type == "cuda"
-        width = 2 * O + A + 2
-        self._stage_host = torch.zeros(N * width, dtype=torch.float32)
-        self._idx_host = torch.zeros((2, M), dtype=torch.int64)
-        self._obs_host = torch.zeros((N, O), dtype=torch.float32)
-        if pin:                                                  # the step's data and draws reach the device through pinned staging
-            self._stage_host, self._idx_host, self._obs_host = (t.pin_memory() for t in (self._stage_host, self._idx_host, self._obs_host))
-        self._stage = torch.zeros(N * width, dtype=torch.float32, device=dev)
-        self._idx = torch.zeros((2, M), dtype=torch.int64, device=dev)
-        self._obs = torch.zeros((N, O), dtype=torch.float32, device=dev)
+        # the step's transition (obs | next_obs | actions | rewards | dones), the rollout's observations and the batch's draws
+        self._step_stage = Staging(dev, step=((N * (2 * O + A + 2),), torch.float32))
+        self._obs_stage = Staging(dev, obs=((N, O), torch.float32))
+        self._idx_stage = Staging(dev, idx=((2, M), torch.int64))
         self._act = torch.zeros((N, A), dtype=torch.float32, device=dev)
         self._norm = torch.zeros(1, dtype=torch.float32, device=dev)
 
@@ -181,20 +177,15 @@ class DeviceRing:
 
     def _stage_obs(self, obs):
         """The rollout's observations (N, O) where the action kernel reads them."""
-        self._obs_host.copy_(torch.from_numpy(np.ascontiguousarray(obs, np.float32)).reshape(self.N, self.O))
-        if self.device.type != "cuda":
-            return self._obs_host
-        self._obs.copy_(self._obs_host, non_blocking=True)
-        return self._obs
+        self._obs_stage.begin()["obs"].copy_(torch.from_numpy(np.ascontiguousarray(obs, np.float32)).reshape(self.N, self.O))
+        return self._obs_stage.push()["obs"]
 
     def _stage_indices(self, bi, ei):
         """The batch's (batch_inds, env_inds) as two int64 rows on the learner's device."""
-        self._idx_host[0].copy_(torch.from_numpy(np.asarray(bi, np.int64)))
-        self._idx_host[1].copy_(torch.from_numpy(np.asarray(ei, np.int64)))
-        if self.device.type != "cuda":
-            return self._idx_host
-        self._idx.copy_(self._idx_host, non_blocking=True)
-        return self._idx
+        h = self._idx_stage.begin()["idx"]
+        h[0].copy_(torch.from_numpy(np.asarray(bi, np.int64)))
+        h[1].copy_(torch.from_numpy(np.asarray(ei, np.int64)))
+        return self._idx_stage.push()["idx"]
 
     def store(self, obs, real_next_obs, actions, rewards, terminations):
         """``rb.add(obs, real_next_obs, actions, rewards, terminations, infos)``."""
@@ -203,16 +194,13 @@ class DeviceRing:
             self.pos, self.full = self.rb.pos, self.rb.full
             return
         N, O, A = self.N, self.O, self.A
-        h = self._stage_host
+        h = self._step_stage.begin()["step"]
         parts, off = [], 0
         for src, n in ((obs, N * O), (real_next_obs, N * O), (actions, N * A), (rewards, N), (terminations, N)):
             h[off:off + n].copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(src).reshape(-1).astype(np.float32))))
             parts.append((off, n))
             off += n
-        buf = h
-        if self.device.type == "cuda":
-            self._stage.copy_(h, non_blocking=True)
-            buf = self._stage
+        buf = self._step_stage.push()["step"]
         v = [buf[o:o + n] for o, n in parts]
         self.g.replay_add(self.ring, self.pos, v[0].view(N, O), v[1].view(N, O), v[2].view(N, A), v[3], v[4])
         advance(self)

@@ -75,28 +75,6 @@ class QDaggerLearner(AtariDQNLearner):
         if not self.fused:
             self.rb = self._host_buffer(np.int64)
 
-    # ------------------------------------------------------------------ pinned staging
-    # The base class stages a step's frames and a batch's indices in pinned host buffers and copies them with ``non_blocking``.  The
-    # stream orders the copies, but nothing orders the HOST's next write to the same pinned buffer behind a copy still in flight.  The
-    # Atari DQN loop synchronises somewhere in nearly every step (a greedy action or a logged scalar comes back); this script's teacher
-    # phase starts with epsilon 1 and its offline phase logs every 100th update, so many stores and updates run back to back with no
-    # synchronisation at all.  An event recorded behind each staged copy is waited for before the buffers are written again.
-    def _staging_free(self):
-        ev = getattr(self, "_staged", None)
-        if ev is not None:
-            ev.synchronize()
-
-    def _staging_used(self):
-        if self.fused and self.device.type == "cuda":
-            if getattr(self, "_staged", None) is None:
-                self._staged = torch.cuda.Event()
-            self._staged.record(torch.cuda.current_stream(self.device))
-
-    def store(self, obs, real_next_obs, actions, rewards, terminations):
-        self._staging_free()
-        super().store(obs, real_next_obs, actions, rewards, terminations)
-        self._staging_used()
-
     # ------------------------------------------------------------------ the networks below the heads
     def _hidden(self, net, frames_hwc):
         """The student's ``Linear(3872, 256)`` ReLU output on (rows, 84, 84, 4) u8 rows (the trunk per ``net.impala_backend``); the
@@ -124,13 +102,7 @@ class QDaggerLearner(AtariDQNLearner):
             if not self.fused:
                 q_values = (self.teacher if teacher else self.q_network)(torch.Tensor(obs).to(self.device))
                 return torch.argmax(q_values, dim=1).cpu().numpy()
-            self._staging_free()
-            self._frames_host[0].copy_(torch.from_numpy(np.ascontiguousarray(obs, np.uint8)).reshape(self._frames_host[0].shape))
-            if self.device.type == "cuda":
-                self._frames_dev[0].copy_(self._frames_host[0], non_blocking=True)
-                rows = ops.obs_nchw_to_nhwc_u8(self._frames_dev[0], out=self._obs_hwc)
-            else:
-                rows = self._frames_host[0].permute(0, 2, 3, 1).contiguous()
+            rows = self._stage_frames(obs)
             if teacher:
                 self._teacher_head(rows, self._greedy)
             else:
@@ -146,9 +118,7 @@ class QDaggerLearner(AtariDQNLearner):
         bi, ei = self.sample_indices(M) if indices is None else indices
         if not self.fused:
             return self._train_qdagger_torch(np.asarray(bi), np.asarray(ei), distill_coeff)
-        self._staging_free()
         idx = self._stage_indices(bi, ei)
-        self._staging_used()
         self.update_kernels(idx[0], idx[1], distill_coeff=distill_coeff)
         self.last = ("fused",)
         return self

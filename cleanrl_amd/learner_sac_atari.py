@@ -41,7 +41,7 @@ import torch.nn.functional as F
 import torch.optim as optim
 
 from . import ops
-from .learner_dqn_atari import FRAME, Trunks, check_frames
+from .learner_dqn_atari import FRAME, FrameRing, Trunks, check_frames
 from .learner_offpolicy import DeviceRing, advance
 
 ADAM_EPS = 1e-4          # "TRY NOT TO MODIFY: eps=1e-4 increases numerical stability"
@@ -73,10 +73,12 @@ class HostFrameBuffer2:
                 t(self.dones[bi, ei].reshape(-1, 1)), t(self.rewards[bi, ei].reshape(-1, 1)))
 
 
-class SACAtariLearner(DeviceRing):
-    """``sample_indices`` (``rb.sample``'s two ``np.random`` draws) is the base class's."""
+class SACAtariLearner(FrameRing, DeviceRing):
+    """``sample_indices`` (``rb.sample``'s two ``np.random`` draws) is ``DeviceRing``'s; the two rings, their staging and ``store`` are
+    ``FrameRing``'s."""
 
     NETS = ("actor", "qf1", "qf2")
+    FRAME_ARRAYS = 2
 
     def __init__(self, actor, qf1, qf2, qf1_target, qf2_target, args, envs, device, backend=None):
         self.n = int(envs.single_action_space.n)
@@ -130,31 +132,6 @@ class SACAtariLearner(DeviceRing):
             raise ValueError(f"MI355PPO_OFFPOLICY=fused: the fused discrete-SAC heads take 2 <= n_actions <= {ops.DQN_MAX_ACT} and batch_size <= "
                              f"{ops.DQN_HEAD_MAX_ROWS}, not {self.n} / {self.args.batch_size}; use MI355PPO_OFFPOLICY=torch")
 
-    def _alloc_ring(self, M: int):
-        dev, N = self.device, self.N
-        H, W, C = ops.ATARI_FRAME
-        try:
-            frames = tuple(torch.zeros((self.slots, N, H, W, C), dtype=torch.uint8, device=dev) for _ in range(2))
-        except (RuntimeError, MemoryError) as e:
-            raise ValueError(f"MI355PPO_OFFPOLICY=fused: two frame rings of {self.slots} slots x {N} envs "
-                             f"({2 * self.slots * N * H * W * C / 1e9:.1f} GB) cannot be allocated on {dev}; lower --buffer-size or use "
-                             f"MI355PPO_OFFPOLICY=torch") from e
-        self.ring = frames + (torch.zeros((self.slots, N), dtype=torch.int64, device=dev), torch.zeros((self.slots, N), device=dev),
-                              torch.zeros((self.slots, N), device=dev))
-        pin = (lambda t: t.pin_memory()) if dev.type == "cuda" else (lambda t: t)
-        self._frames_host = pin(torch.zeros((2, N, C, H, W), dtype=torch.uint8))      # obs | next_obs as the env gives them
-        self._act_host = pin(torch.zeros(N, dtype=torch.int64))
-        self._rd_host = pin(torch.zeros((2, N), dtype=torch.float32))
-        self._idx_host = pin(torch.zeros((2, M), dtype=torch.int64))
-        self._frames_dev = torch.zeros_like(self._frames_host, device=dev)
-        self._act_dev = torch.zeros(N, dtype=torch.int64, device=dev)
-        self._rd_dev = torch.zeros((2, N), dtype=torch.float32, device=dev)
-        self._idx = torch.zeros((2, M), dtype=torch.int64, device=dev)
-        self._obs_hwc = torch.zeros((N, H, W, C), dtype=torch.uint8, device=dev)
-        self._batch = (torch.zeros((2 * M, H, W, C), dtype=torch.uint8, device=dev), torch.zeros(M, dtype=torch.int64, device=dev),
-                       torch.zeros(M, device=dev), torch.zeros(M, device=dev))
-        self._norm = torch.zeros(1, dtype=torch.float32, device=dev)
-
     # ------------------------------------------------------------------ views of the flat buffers
     def _seg(self, flat, which):
         """``actor``: the first network's floats; ``critics``: ``qf1 | qf2`` with the padding between them."""
@@ -186,36 +163,11 @@ class SACAtariLearner(DeviceRing):
             if not self.fused:
                 actions, _, _ = self.actor.get_action(torch.Tensor(obs).to(self.device))
                 return actions.detach().cpu().numpy()
-            self._frames_host[0].copy_(torch.from_numpy(np.ascontiguousarray(obs, np.uint8)).reshape(self._frames_host[0].shape))
-            if self.device.type == "cuda":
-                self._frames_dev[0].copy_(self._frames_host[0], non_blocking=True)
-                rows = ops.obs_nchw_to_nhwc_u8(self._frames_dev[0], out=self._obs_hwc)
-            else:
-                rows = self._frames_host[0].permute(0, 2, 3, 1).contiguous()
+            rows = self._stage_frames(obs)
             noise = torch.empty((self.N, self.n), dtype=torch.float32, device=self.device).exponential_()
             w, b = self._head(self.online, 0)
             self.g.sacd_head_act(self._hidden(self.actor, rows).contiguous(), w, b, noise, self._sampled)
             return self._copy_out(self._sampled)
-
-    def store(self, obs, real_next_obs, actions, rewards, terminations):
-        """``rb.add(obs, real_next_obs, actions, rewards, terminations, infos)``."""
-        if not self.fused:
-            self.rb.add(obs, real_next_obs, actions, rewards, terminations)
-            self.pos, self.full = self.rb.pos, self.rb.full
-            return
-        fh, ah, rh = self._frames_host, self._act_host, self._rd_host
-        fh[0].copy_(torch.from_numpy(np.ascontiguousarray(obs, np.uint8)).reshape(fh[0].shape))
-        fh[1].copy_(torch.from_numpy(np.ascontiguousarray(real_next_obs, np.uint8)).reshape(fh[1].shape))
-        ah.copy_(torch.from_numpy(np.asarray(actions, np.int64).reshape(-1)))
-        rh[0].copy_(torch.from_numpy(np.asarray(rewards, np.float32).reshape(-1)))
-        rh[1].copy_(torch.from_numpy(np.asarray(terminations, np.float32).reshape(-1)))
-        if self.device.type == "cuda":
-            self._frames_dev.copy_(fh, non_blocking=True)
-            self._act_dev.copy_(ah, non_blocking=True)
-            self._rd_dev.copy_(rh, non_blocking=True)
-            fh, ah, rh = self._frames_dev, self._act_dev, self._rd_dev
-        self.g.replay_add2_u8(self.ring, self.pos, fh[0], fh[1], ah, rh[0], rh[1])
-        advance(self)
 
     # ------------------------------------------------------------------ training
     def train_step(self, indices=None):

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .staging import Staging
 
 __all__ = ["NStepAccumulator", "SumTree", "HostPrioritizedReplay", "DevicePrioritizedReplay"]
 
@@ -163,12 +164,7 @@ class DevicePrioritizedReplay(_Replay):
             raise ValueError(f"buffer_size={capacity}: the two device frame rings need {gb:.1f} GB and could not be allocated ({e}); lower "
                              "--buffer-size or keep MI355PPO_OFFPOLICY=torch") from e
         self._batch = None
-        cuda = self.device.type == "cuda"
-        stage = lambda **kw: (torch.zeros((2, 1, 4, 84, 84), dtype=torch.uint8, **kw), torch.zeros(1, dtype=torch.int64, **kw),  # noqa: E731
-                              torch.zeros(2, dtype=torch.float32, **kw))
-        self._host = [stage(pin_memory=cuda) + (torch.cuda.Event() if cuda else None,) for _ in range(2)]
-        self._dev = stage(device=self.device) if cuda else None
-        self._turn = 0
+        self._stage = Staging(self.device, frames=((2, 1, 4, 84, 84), torch.uint8), act=((1,), torch.int64), rd=((2,), torch.float32))
 
     @property
     def beta(self):
@@ -180,22 +176,15 @@ class DevicePrioritizedReplay(_Replay):
         self.buf[6][1:2].fill_(float(v))                  # read by the sample kernel from device memory
 
     def _store(self, obs, action, reward, next_obs, done):
-        """One staged transition: two pinned host sets used in turn (a set is rewritten only after its copies have left it), three
-        asynchronous copies and one launch; on a CPU device the twins read the host set itself."""
-        self._turn = 1 - self._turn
-        fh, ah, rh, ev = self._host[self._turn]
-        if ev is not None:
-            ev.synchronize()
+        """One staged transition (``staging.Staging``: on a GPU three asynchronous copies) and one launch."""
+        h = self._stage.begin()
+        fh, rh = h["frames"], h["rd"]
         fh[0].copy_(torch.from_numpy(np.ascontiguousarray(obs, np.uint8)).reshape(fh[0].shape))
         fh[1].copy_(torch.from_numpy(np.ascontiguousarray(next_obs, np.uint8)).reshape(fh[1].shape))
-        ah[0] = int(np.asarray(action).reshape(-1)[0])
+        h["act"][0] = int(np.asarray(action).reshape(-1)[0])
         rh[0], rh[1] = float(np.float32(np.asarray(reward).reshape(-1)[0])), float(bool(np.asarray(done).reshape(-1)[0]))
-        if ev is not None:
-            fd, ad, rd = self._dev
-            fd.copy_(fh, non_blocking=True), ad.copy_(ah, non_blocking=True), rd.copy_(rh, non_blocking=True)
-            ev.record()
-            fh, ah, rh = fd, ad, rd
-        self.g.rainbow_per_add_u8(self.buf, self.pos, fh[0], fh[1], ah, rh[0:1], rh[1:2], self.alpha)
+        d = self._stage.push()
+        self.g.rainbow_per_add_u8(self.buf, self.pos, d["frames"][0], d["frames"][1], d["act"], d["rd"][0:1], d["rd"][1:2], self.alpha)
 
     def _outputs(self, B):
         if self._batch is None or self._batch["indices"].numel() != B:

@@ -15,7 +15,9 @@ sample and per priority update; and the four NoisyLinear layers' ``mu + sigma * 
 4-action and an 18-action game.  ``--scripts sac_atari`` times sac_atari.py at its batch of 64 for a 4-action and an 18-action game: one rollout
 step (the policy's sample) and one update (critics, actor, temperature).  ``--scripts qdagger`` times qdagger_dqn_atari_impalacnn.py at batch 32
 for a 4-action and an 18-action game: one greedy step of the student, one offline update (``distill_coeff`` 1) and one online update
-(``distill_coeff`` 0.37); the ``fused`` side runs the IMPALA trunk kernels too (``impala_backend`` fused).
+(``distill_coeff`` 0.37); the ``fused`` side runs the IMPALA trunk kernels too (``impala_backend`` fused).  Every family but
+``rainbow_buffer`` also has a ``store`` leg: 64 back-to-back ``store``s with one synchronisation behind them, in microseconds per store
+(the other legs synchronise around every call, so a wait inside ``store`` for an earlier copy would not show in them).
 """
 from __future__ import annotations
 
@@ -66,7 +68,7 @@ def bench_dqn(a, dev):
     for shape, (O, n) in DQN_SHAPES.items():
         learners = {(alg, b): make_dqn(alg == "c51", O, n, b, dev) for alg in ("dqn", "c51") for b in ("torch", "fused")}
         legs = {"rollout_step": ("dqn", lambda L, obs: L.act(obs, 1, 0.0)), "dqn_update": ("dqn", lambda L, obs: L.train_step()),
-                "c51_update": ("c51", lambda L, obs: L.train_step())}
+                "c51_update": ("c51", lambda L, obs: L.train_step()), "store": ("dqn", store_leg(*learners[("dqn", "torch")]))}
         times = {leg: {b: [] for b in ("torch", "fused")} for leg in legs}
         for rep in range(a.warmup + a.reps):
             for leg, (alg, fn) in legs.items():
@@ -80,7 +82,7 @@ def bench_dqn(a, dev):
             for b in ("torch", "fused"):
                 row[f"{leg}_{b}_us"] = round(statistics.median(times[leg][b]), 1)
             row[f"{leg}_speedup"] = round(row[f"{leg}_torch_us"] / row[f"{leg}_fused_us"], 2)
-        print(json.dumps(row), flush=True)
+        emit(row)
 
 
 ATARI_SHAPES = {"4-action": 4, "18-action": 18}
@@ -105,7 +107,7 @@ def bench_dqn_atari(a, dev):
     for shape, n in ATARI_SHAPES.items():
         learners = {(alg, b): make_dqn_atari(alg == "c51", n, b, dev) for alg in ("dqn", "c51") for b in ("torch", "fused")}
         legs = {"rollout_step": ("dqn", lambda L, obs: L.act(obs, 1, 0.0)), "dqn_update": ("dqn", lambda L, obs: L.train_step()),
-                "c51_update": ("c51", lambda L, obs: L.train_step())}
+                "c51_update": ("c51", lambda L, obs: L.train_step()), "store": ("dqn", store_leg(*learners[("dqn", "torch")]))}
         times = {leg: {b: [] for b in ("torch", "fused")} for leg in legs}
         for rep in range(a.warmup + a.reps):
             for leg, (alg, fn) in legs.items():
@@ -119,7 +121,7 @@ def bench_dqn_atari(a, dev):
             for b in ("torch", "fused"):
                 row[f"{leg}_{b}_us"] = round(statistics.median(times[leg][b]), 1)
             row[f"{leg}_speedup"] = round(row[f"{leg}_torch_us"] / row[f"{leg}_fused_us"], 2)
-        print(json.dumps(row), flush=True)
+        emit(row)
 
 
 def make_rainbow(n, backend, dev, fill=256):
@@ -160,7 +162,7 @@ def bench_rainbow(a, dev):
 
         legs = {"rollout_step": lambda L, obs: L.act(obs), "update": lambda L, obs: L.train_step(),
                 "compose_both": lambda L, obs: composes(L, True, True), "compose_online": lambda L, obs: composes(L, True, False),
-                "compose_target": lambda L, obs: composes(L, False, True)}
+                "compose_target": lambda L, obs: composes(L, False, True), "store": store_leg(*learners["torch"], rainbow=True)}
         times = {leg: {b: [] for b in learners} for leg in legs}
         for rep in range(a.warmup + a.reps):
             for leg, fn in legs.items():
@@ -173,7 +175,7 @@ def bench_rainbow(a, dev):
             for b in learners:
                 row[f"{leg}_{b}_us"] = round(statistics.median(times[leg][b]), 1)
             row[f"{leg}_speedup"] = round(row[f"{leg}_torch_us"] / row[f"{leg}_fused_us"], 2)
-        print(json.dumps(row), flush=True)
+        emit(row)
 
 
 def bench_rainbow_buffer(a, dev, slots=4096, B=32):
@@ -239,7 +241,7 @@ def bench_rainbow_buffer(a, dev, slots=4096, B=32):
             for b in ("torch", "fused"):
                 row[f"{leg}_{b}_us"] = round(statistics.median(times[leg][b]), 1)
             row[f"{leg}_speedup"] = round(row[f"{leg}_torch_us"] / row[f"{leg}_fused_us"], 2)
-        print(json.dumps(row), flush=True)
+        emit(row)
 
 
 def make_sac_atari(n, backend, dev, fill=256):
@@ -261,7 +263,7 @@ def bench_sac_atari(a, dev):
     """sac_atari.py at batch 64: one rollout step (``get_action``'s sample, with its copy to the host) and one update."""
     for shape, n in ATARI_SHAPES.items():
         learners = {b: make_sac_atari(n, b, dev) for b in ("torch", "fused")}
-        legs = {"rollout_step": lambda L, obs: L.act(obs, 1), "update": lambda L, obs: L.train_step()}
+        legs = {"rollout_step": lambda L, obs: L.act(obs, 1), "update": lambda L, obs: L.train_step(), "store": store_leg(*learners["torch"])}
         times = {leg: {b: [] for b in learners} for leg in legs}
         for rep in range(a.warmup + a.reps):
             for leg, fn in legs.items():
@@ -274,7 +276,7 @@ def bench_sac_atari(a, dev):
             for b in learners:
                 row[f"{leg}_{b}_us"] = round(statistics.median(times[leg][b]), 1)
             row[f"{leg}_speedup"] = round(row[f"{leg}_torch_us"] / row[f"{leg}_fused_us"], 2)
-        print(json.dumps(row), flush=True)
+        emit(row)
 
 
 def make_qdagger(n, backend, dev, fill=256):
@@ -296,7 +298,7 @@ def bench_qdagger(a, dev):
     for shape, n in ATARI_SHAPES.items():
         learners = {b: make_qdagger(n, b, dev) for b in ("torch", "fused")}
         legs = {"greedy_step": lambda L, obs: L.act(obs, 1, 0.0), "offline_update": lambda L, obs: L.train_step(1.0),
-                "online_update": lambda L, obs: L.train_step(0.37)}
+                "online_update": lambda L, obs: L.train_step(0.37), "store": store_leg(*learners["torch"])}
         times = {leg: {b: [] for b in learners} for leg in legs}
         for rep in range(a.warmup + a.reps):
             for leg, fn in legs.items():
@@ -309,7 +311,7 @@ def bench_qdagger(a, dev):
             for b in learners:
                 row[f"{leg}_{b}_us"] = round(statistics.median(times[leg][b]), 1)
             row[f"{leg}_speedup"] = round(row[f"{leg}_torch_us"] / row[f"{leg}_fused_us"], 2)
-        print(json.dumps(row), flush=True)
+        emit(row)
 
 
 def make(script, O, A, backend, dev, fill=4096):
@@ -340,6 +342,34 @@ def fill_ring(L, envs, fill):
         L.store(obs, nxt, a, r, term)
         obs = nxt
     return L, obs
+
+
+STORES = 64
+
+
+def store_leg(L, obs, rainbow=False):
+    """The ``store`` leg of ``L``'s family: 64 back-to-back ``store``s of pre-generated transitions shaped like ``obs``, with no
+    synchronisation but the one ``timed`` puts behind them, so whatever a ``store`` waits for is in the time."""
+    rng = np.random.RandomState(2)
+    obs = np.asarray(obs)
+    new = (lambda: rng.randint(0, 256, obs.shape).astype(np.uint8)) if obs.dtype == np.uint8 else (lambda: rng.standard_normal(obs.shape).astype(np.float32))
+    steps = [(new(), new(), np.array([L.space.sample()]), rng.standard_normal(1).astype(np.float32), np.array([i % 20 == 19])) for i in range(STORES)]
+    if rainbow:                                                  # RainbowLearner.store(obs, actions, rewards, real_next_obs, terminations)
+        steps = [(o, a, r, nxt, d) for o, nxt, a, r, d in steps]
+
+    def run(L, obs):
+        for step in steps:
+            L.store(*step)
+
+    return run
+
+
+def emit(row):
+    """Prints the row; the ``store`` leg's medians become microseconds per store."""
+    for k in ("store_torch_us", "store_fused_us"):
+        if k in row:
+            row[k] = round(row[k] / STORES, 2)
+    print(json.dumps(row), flush=True)
 
 
 def timed(fn, dev):
@@ -383,7 +413,7 @@ def main():
             learners = {b: make(script, O, A, b, dev) for b in ("torch", "fused")}
             extra = (True,) if script == "sac" else ()          # SAC's target update runs every step (target_network_frequency 1)
             legs = {"rollout_step": lambda L, obs: L.act(obs, 1), "critic_step": lambda L, obs: L.train_step(False, *extra),
-                    "policy_step": lambda L, obs: L.train_step(True, *extra)}
+                    "policy_step": lambda L, obs: L.train_step(True, *extra), "store": store_leg(*learners["torch"])}
             times = {leg: {b: [] for b in learners} for leg in legs}
             for rep in range(a.warmup + a.reps):
                 for leg, fn in legs.items():
@@ -396,7 +426,7 @@ def main():
                 for b in learners:
                     row[f"{leg}_{b}_us"] = round(statistics.median(times[leg][b]), 1)
                 row[f"{leg}_speedup"] = round(row[f"{leg}_torch_us"] / row[f"{leg}_fused_us"], 2)
-            print(json.dumps(row), flush=True)
+            emit(row)
 
 
 if __name__ == "__main__":
