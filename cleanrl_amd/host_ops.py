@@ -8,7 +8,9 @@ kernels' own row / element functions compiled for the host, so the CPU loop cros
 as the GPU loop: GAE (ppo.py:218-231), the fused loss forward + backward (ppo.py:250-285 and its autograd),
 the LSTM sequence scans of ppo_atari_lstm.py (opt-in: ``MI355PPO_LSTM=fused``), the TrXL memory attention of ppo_trxl.py
 (opt-in: ``MI355PPO_TRXL=fused``) and, for tests, sampling and clip + Adam.  The learners whose loss has extra terms (LSTM state, RND's second value
-head and distillation loss) cross the same twin on their logits / value and add their terms outside.
+head and distillation loss) cross the same twin on their logits / value and add their terms outside.  The twins of the replay-ring
+families (``replay_add`` .. ``sacd_actor_fwd_bwd``) are not written here: cleanrl_amd/replay_ops.py defines each operator
+once, and the end of this file binds them to the host side, which checks like ``ops`` (nothing coerced) and calls ``name + "_cpu"``.
 """
 from __future__ import annotations
 
@@ -17,7 +19,13 @@ import ctypes
 import torch
 
 from . import _lib
-from .ops import ATARI_FRAME, IMPALA84_OUT, IMPALA_CHANNELS, _lstm_dims, _ptr_array, dqn_counts, dqn_head_limits_ok, dqn_limits_ok, offpolicy_counts, pqn_param_count, radam_schedule, rainbow_head_limits_ok, rainbow_new_buffer, rainbow_noisy_counts, rainbow_noisy_limits_ok, _rainbow_head, _rainbow_head_update_args, sac_actor_count, sacd_limits_ok, _frame_ring2, _sacd_heads, trxl_dims  # noqa: F401  (one definition for both modules)
+from . import replay_ops
+from .ops import IMPALA84_OUT, IMPALA_CHANNELS, _lstm_dims, _ptr_array, pqn_param_count, radam_schedule, trxl_dims  # noqa: F401
+from .replay_ops import (ATARI_FRAME, DQN_HEAD_HIDDEN, DQN_HEAD_MAX_OUT, DQN_HEAD_MAX_ROWS, DQN_HIDDEN, DQN_MAX_ACT, DQN_MAX_ATOMS,  # noqa: F401
+                         DQN_MAX_OBS, DQN_MAX_OUT, OFFPOLICY_HIDDEN, OFFPOLICY_MAX_ACT, OFFPOLICY_MAX_OBS, QDAGGER_HIDDEN, QDAGGER_MAX_ROWS,
+                         RAINBOW_HEAD_IN, RAINBOW_MAX_BATCH, dqn_counts, dqn_head_limits_ok, dqn_limits_ok, offpolicy_counts,
+                         qdagger_head_limits_ok, rainbow_head_limits_ok, rainbow_new_buffer, rainbow_noisy_counts, rainbow_noisy_limits_ok,
+                         sac_actor_count, sacd_limits_ok)
 
 LOSS_SCALARS = 7
 
@@ -455,89 +463,6 @@ def pqn_lstm_td_fwd_bwd(h, mb_inds, b_actions, b_returns, wq, bq, dwq, dbq, dh=N
     return dh, scalars
 
 
-# ------------------------------------------------------------------------------------------- DDPG / TD3 twins (csrc/offpolicy.hip)
-def _in(t, dtype, shape, name):
-    """An input the twin reads ``prod(shape)`` elements of: taken as it is (the ring is never copied)."""
-    _p(t)
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name}: expected {dtype} {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _ring_dims(ring):
-    obs, nxt, act, rew, done = ring
-    slots, N, O = obs.shape
-    A = act.shape[-1]
-    ptrs = [_in(t, torch.float32, shape, nm) for t, nm, shape in (
-        (obs, "ring obs", (slots, N, O)), (nxt, "ring next_obs", (slots, N, O)), (act, "ring actions", (slots, N, A)),
-        (rew, "ring rewards", (slots, N)), (done, "ring dones", (slots, N)))]
-    return slots, N, O, A, ptrs
-
-
-def replay_add(ring, pos, obs, next_obs, actions, rewards, dones):
-    slots, N, O, A, rp = _ring_dims(ring)
-    _lib.call("mi355ppo_replay_add_f32_cpu", _in(obs, torch.float32, (N, O), "obs"), _in(next_obs, torch.float32, (N, O), "next_obs"),
-              _in(actions, torch.float32, (N, A), "actions"), _in(rewards, torch.float32, (N,), "rewards"),
-              _in(dones, torch.float32, (N,), "dones"), *rp, int(pos), slots, N, O, A)
-
-
-def ddpg_act(obs, actor_params, action_scale, action_bias, noise_row, low, high, actions_out):
-    N, O = obs.shape
-    (A,) = action_scale.shape
-    nz = None if noise_row is None else _in(noise_row, torch.float32, (A,), "noise_row")
-    _lib.call("mi355ppo_ddpg_act_f32_cpu", _in(obs, torch.float32, (N, O), "obs"),
-              _in(actor_params, torch.float32, (offpolicy_counts(O, A)[0],), "actor_params"), _in(action_scale, torch.float32, (A,), "action_scale"),
-              _in(action_bias, torch.float32, (A,), "action_bias"), nz, _in(low, torch.float32, (A,), "low"), _in(high, torch.float32, (A,), "high"),
-              _out(actions_out, torch.float32, N * A, "actions_out"), N, O, A)
-    return actions_out
-
-
-def td3_target(ring, batch_inds, env_inds, target_actor, target_critics, n_critics, action_scale, action_bias, noise, policy_noise,
-               noise_clip, low0, high0, gamma, next_q_value, next_actions_out=None):
-    slots, N, O, A, rp = _ring_dims(ring)
-    (M,) = batch_inds.shape
-    pa, pq = offpolicy_counts(O, A)
-    nz = None if noise is None else _in(noise, torch.float32, (M, A), "noise")
-    _lib.call("mi355ppo_td3_target_f32_cpu", rp[1], rp[3], rp[4], _in(batch_inds, torch.int64, (M,), "batch_inds"),
-              _in(env_inds, torch.int64, (M,), "env_inds"), slots, N, _in(target_actor, torch.float32, (pa,), "target_actor"),
-              _in(target_critics, torch.float32, (int(n_critics) * pq,), "target_critics"), int(n_critics),
-              _in(action_scale, torch.float32, (A,), "action_scale"), _in(action_bias, torch.float32, (A,), "action_bias"), nz,
-              float(policy_noise), float(noise_clip), float(low0), float(high0), float(gamma),
-              _out(next_q_value, torch.float32, M, "next_q_value"), _out(next_actions_out, torch.float32, M * A, "next_actions_out"), M, O, A)
-    return next_q_value
-
-
-def td3_critic_fwd_bwd(ring, batch_inds, env_inds, critics, n_critics, next_q_value, grads, scalars):
-    slots, N, O, A, rp = _ring_dims(ring)
-    (M,) = batch_inds.shape
-    P = int(n_critics) * offpolicy_counts(O, A)[1]
-    _lib.call("mi355ppo_td3_critic_fwd_bwd_f32_cpu", rp[0], rp[2], _in(batch_inds, torch.int64, (M,), "batch_inds"),
-              _in(env_inds, torch.int64, (M,), "env_inds"), slots, N, _in(critics, torch.float32, (P,), "critics"), int(n_critics),
-              _in(next_q_value, torch.float32, (M,), "next_q_value"), _out(grads, torch.float32, P, "grads"),
-              _out(scalars, torch.float32, 2 * int(n_critics), "scalars"), M, O, A)
-    return scalars
-
-
-def td3_actor_fwd_bwd(ring, batch_inds, env_inds, actor, qf1, action_scale, action_bias, grads, actor_loss, dq_daction_out=None):
-    slots, N, O, A, rp = _ring_dims(ring)
-    (M,) = batch_inds.shape
-    pa, pq = offpolicy_counts(O, A)
-    _lib.call("mi355ppo_td3_actor_fwd_bwd_f32_cpu", rp[0], _in(batch_inds, torch.int64, (M,), "batch_inds"),
-              _in(env_inds, torch.int64, (M,), "env_inds"), slots, N, _in(actor, torch.float32, (pa,), "actor"),
-              _in(qf1, torch.float32, (pq,), "qf1"), _in(action_scale, torch.float32, (A,), "action_scale"),
-              _in(action_bias, torch.float32, (A,), "action_bias"), _out(grads, torch.float32, pa, "grads"),
-              _out(actor_loss, torch.float32, 1, "actor_loss"), _out(dq_daction_out, torch.float32, M * A, "dq_daction_out"), M, O, A)
-    return actor_loss
-
-
-def polyak_(params, target_params, tau):
-    n = params.numel()
-    _lib.call("mi355ppo_polyak_f32_cpu", _in(params, torch.float32, (n,), "params"), _out(target_params, torch.float32, n, "target_params"),
-              n, float(tau))
-    return target_params
-
-
-# ------------------------------------------------------------------------------------------- SAC twins (csrc/sac.hip)
 def sac_exp_log(x):
     """The library's own exp and log (csrc/sac_rows.h) on a float32 CPU tensor -> (exp, log)."""
     x = _f32(x).reshape(-1)
@@ -546,331 +471,28 @@ def sac_exp_log(x):
     return e, l
 
 
-def sac_policy(obs, actor, action_scale, action_bias, eps, actions_out=None, log_pi_out=None, batch_inds=None, env_inds=None):
-    rows, A = eps.shape
-    if batch_inds is None:
-        slots, N, O = 0, 0, obs.shape[-1]
-        op, bi, ei = _in(obs, torch.float32, (rows, O), "obs"), None, None
-    else:
-        slots, N, O = obs.shape
-        op = _in(obs, torch.float32, (slots, N, O), "obs")
-        bi, ei = _in(batch_inds, torch.int64, (rows,), "batch_inds"), _in(env_inds, torch.int64, (rows,), "env_inds")
-    _lib.call("mi355ppo_sac_policy_f32_cpu", op, bi, ei, slots, N, _in(actor, torch.float32, (sac_actor_count(O, A),), "actor"),
-              _in(action_scale, torch.float32, (A,), "action_scale"), _in(action_bias, torch.float32, (A,), "action_bias"),
-              _in(eps, torch.float32, (rows, A), "eps"), _out(actions_out, torch.float32, rows * A, "actions_out"),
-              _out(log_pi_out, torch.float32, rows, "log_pi_out"), rows, O, A)
-    return actions_out, log_pi_out
-
-
-def sac_target(ring, batch_inds, env_inds, actor, target_critics, action_scale, action_bias, eps, alpha, gamma, next_q_value,
-               next_actions_out=None, log_pi_out=None):
-    slots, N, O, A, rp = _ring_dims(ring)
-    (M,) = batch_inds.shape
-    _lib.call("mi355ppo_sac_target_f32_cpu", rp[1], rp[3], rp[4], _in(batch_inds, torch.int64, (M,), "batch_inds"),
-              _in(env_inds, torch.int64, (M,), "env_inds"), slots, N, _in(actor, torch.float32, (sac_actor_count(O, A),), "actor"),
-              _in(target_critics, torch.float32, (2 * offpolicy_counts(O, A)[1],), "target_critics"),
-              _in(action_scale, torch.float32, (A,), "action_scale"), _in(action_bias, torch.float32, (A,), "action_bias"),
-              _in(eps, torch.float32, (M, A), "eps"), _in(alpha, torch.float32, (1,), "alpha"), float(gamma),
-              _out(next_q_value, torch.float32, M, "next_q_value"), _out(next_actions_out, torch.float32, M * A, "next_actions_out"),
-              _out(log_pi_out, torch.float32, M, "log_pi_out"), M, O, A)
-    return next_q_value
-
-
-def sac_actor_fwd_bwd(ring, batch_inds, env_inds, actor, critics, action_scale, action_bias, eps, alpha, grads, actor_loss,
-                      log_pi_out=None, dmean_out=None, du_out=None):
-    slots, N, O, A, rp = _ring_dims(ring)
-    (M,) = batch_inds.shape
-    pa = sac_actor_count(O, A)
-    _lib.call("mi355ppo_sac_actor_fwd_bwd_f32_cpu", rp[0], _in(batch_inds, torch.int64, (M,), "batch_inds"),
-              _in(env_inds, torch.int64, (M,), "env_inds"), slots, N, _in(actor, torch.float32, (pa,), "actor"),
-              _in(critics, torch.float32, (2 * offpolicy_counts(O, A)[1],), "critics"), _in(action_scale, torch.float32, (A,), "action_scale"),
-              _in(action_bias, torch.float32, (A,), "action_bias"), _in(eps, torch.float32, (M, A), "eps"),
-              _in(alpha, torch.float32, (1,), "alpha"), _out(grads, torch.float32, pa, "grads"), _out(actor_loss, torch.float32, 1, "actor_loss"),
-              _out(log_pi_out, torch.float32, M, "log_pi_out"), _out(dmean_out, torch.float32, M * A, "dmean_out"),
-              _out(du_out, torch.float32, M * A, "du_out"), M, O, A)
-    return actor_loss
-
-
-def sac_alpha_(log_pi, target_entropy, log_alpha, exp_avg, exp_avg_sq, step, lr, alpha_out, alpha_loss_out, sched2=None, beta1=0.9,
-               beta2=0.999, eps=1e-8):
-    """The twin takes the Adam step count by value; ``sched2`` (the device path's schedule in device memory) is refused."""
-    if sched2 is not None:
-        raise ValueError("sac_alpha_: the host twin takes `step` and `lr`; a schedule tensor is the device path's (cleanrl_amd.ops)")
-    (M,) = log_pi.shape
-    _lib.call("mi355ppo_sac_alpha_f32_cpu", _in(log_pi, torch.float32, (M,), "log_pi"), M, float(target_entropy),
-              _out(log_alpha, torch.float32, 1, "log_alpha"), _out(exp_avg, torch.float32, 1, "exp_avg"),
-              _out(exp_avg_sq, torch.float32, 1, "exp_avg_sq"), float(lr), float(beta1), float(beta2), float(eps), int(step),
-              _out(alpha_out, torch.float32, 1, "alpha_out"), _out(alpha_loss_out, torch.float32, 1, "alpha_loss_out"))
-    return alpha_out
-
-
-# ------------------------------------------------------------------------------------------- DQN / C51 twins (csrc/dqn.hip)
-def _opt_out(t, numel, name):
-    return None if t is None else _out(t, torch.float32, numel, name)
-
-
-def dqn_act(obs, params, n_actions, actions_out, atoms=None, q_out=None):
-    N, O = obs.shape
-    na = 1 if atoms is None else atoms.numel()
-    _lib.call("mi355ppo_dqn_act_f32_cpu", _in(obs, torch.float32, (N, O), "obs"),
-              _in(params, torch.float32, (dqn_counts(O, n_actions, na),), "params"),
-              None if atoms is None else _in(atoms, torch.float32, (na,), "atoms"), _out(actions_out, torch.int64, N, "actions_out"),
-              _opt_out(q_out, N * n_actions, "q_out"), N, O, int(n_actions), na)
-    return actions_out
-
-
-def _dqn_ring(ring):
-    slots, N, O, A, rp = _ring_dims(ring)
-    if A != 1:
-        raise ValueError(f"ring actions: the DQN / C51 ring stores one action index per env, got width {A}")
-    return slots, N, O, rp
-
-
-def dqn_td_fwd_bwd(ring, batch_inds, env_inds, online, target, n_actions, gamma, grads, scalars, target_q_out=None, td_target_out=None):
-    slots, N, O, rp = _dqn_ring(ring)
-    (M,) = batch_inds.shape
-    P = dqn_counts(O, n_actions)
-    _lib.call("mi355ppo_dqn_td_fwd_bwd_f32_cpu", *rp, _in(batch_inds, torch.int64, (M,), "batch_inds"),
-              _in(env_inds, torch.int64, (M,), "env_inds"), slots, N, _in(online, torch.float32, (P,), "online"),
-              _in(target, torch.float32, (P,), "target"), float(gamma), _out(grads, torch.float32, P, "grads"),
-              _out(scalars, torch.float32, 2, "scalars"), _opt_out(target_q_out, M * n_actions, "target_q_out"),
-              _opt_out(td_target_out, M, "td_target_out"), M, O, int(n_actions))
-    return scalars
-
-
-def c51_fwd_bwd(ring, batch_inds, env_inds, online, target, atoms, n_actions, gamma, v_min, v_max, grads, scalars, next_pmfs_out=None,
-                target_pmfs_out=None):
-    slots, N, O, rp = _dqn_ring(ring)
-    (M,) = batch_inds.shape
-    na = atoms.numel()
-    P = dqn_counts(O, n_actions, na)
-    _lib.call("mi355ppo_c51_fwd_bwd_f32_cpu", *rp, _in(batch_inds, torch.int64, (M,), "batch_inds"),
-              _in(env_inds, torch.int64, (M,), "env_inds"), slots, N, _in(online, torch.float32, (P,), "online"),
-              _in(target, torch.float32, (P,), "target"), _in(atoms, torch.float32, (na,), "atoms"), float(gamma), float(v_min), float(v_max),
-              _out(grads, torch.float32, P, "grads"), _out(scalars, torch.float32, 2, "scalars"),
-              _opt_out(next_pmfs_out, M * na, "next_pmfs_out"), _opt_out(target_pmfs_out, M * na, "target_pmfs_out"), M, O, int(n_actions), na)
-    return scalars
-
-
-# ------------------------------------------------------------------------------------------- Atari DQN / C51 twins (csrc/dqn_atari.hip)
-def _frame_ring(ring):
-    frames, act, rew, done = ring
-    slots, N = frames.shape[:2]
-    specs = ((frames, torch.uint8, (slots, N) + ATARI_FRAME, "ring frames"), (act, torch.int64, (slots, N), "ring actions"),
-             (rew, torch.float32, (slots, N), "ring rewards"), (done, torch.float32, (slots, N), "ring dones"))
-    return slots, N, [_in(t, dt, shape, nm) for t, dt, shape, nm in specs]
-
-
-def replay_add_u8(ring, pos, obs, next_obs, actions, rewards, dones):
-    slots, N, rp = _frame_ring(ring)
-    H, W, C = ATARI_FRAME
-    _lib.call("mi355ppo_replay_add_u8_cpu", _in(obs, torch.uint8, (N, C, H, W), "obs"), _in(next_obs, torch.uint8, (N, C, H, W), "next_obs"),
-              _in(actions, torch.int64, (N,), "actions"), _in(rewards, torch.float32, (N,), "rewards"), _in(dones, torch.float32, (N,), "dones"),
-              *rp, int(pos), slots, N)
-
-
-def replay_gather_u8(ring, batch_inds, env_inds, frames_out, actions_out, rewards_out, dones_out):
-    slots, N, rp = _frame_ring(ring)
-    (M,) = batch_inds.shape
-    H, W, C = ATARI_FRAME
-    _lib.call("mi355ppo_replay_gather_u8_cpu", *rp, _in(batch_inds, torch.int64, (M,), "batch_inds"), _in(env_inds, torch.int64, (M,), "env_inds"),
-              slots, N, _out(frames_out, torch.uint8, 2 * M * H * W * C, "frames_out"), _out(actions_out, torch.int64, M, "actions_out"),
-              _out(rewards_out, torch.float32, M, "rewards_out"), _out(dones_out, torch.float32, M, "dones_out"), M)
-    return frames_out
-
-
-def dqn_head_act(h, w, b, n_actions, actions_out, atoms=None, q_out=None):
-    N, hidden = h.shape
-    na = 1 if atoms is None else atoms.numel()
-    J = int(n_actions) * na
-    _lib.call("mi355ppo_dqn_head_act_f32_cpu", _in(h, torch.float32, (N, hidden), "h"), _in(w, torch.float32, (J, hidden), "w"),
-              _in(b, torch.float32, (J,), "b"), None if atoms is None else _in(atoms, torch.float32, (na,), "atoms"),
-              _out(actions_out, torch.int64, N, "actions_out"), _opt_out(q_out, N * n_actions, "q_out"), N, hidden, int(n_actions), na)
-    return actions_out
-
-
-def _head_update_ptrs(h, h_next, w, b, w_target, b_target, actions, rewards, dones, J):
-    M, hidden = h.shape
-    return M, hidden, [_in(h, torch.float32, (M, hidden), "h"), _in(h_next, torch.float32, (M, hidden), "h_next"),
-                       _in(w, torch.float32, (J, hidden), "w"), _in(b, torch.float32, (J,), "b"),
-                       _in(w_target, torch.float32, (J, hidden), "w_target"), _in(b_target, torch.float32, (J,), "b_target")], [
-                       _in(actions, torch.int64, (M,), "actions"), _in(rewards, torch.float32, (M,), "rewards"),
-                       _in(dones, torch.float32, (M,), "dones")]
-
-
-def _head_grads(dh, dw, db, scalars, M, hidden, J):
-    return [_out(dh, torch.float32, M * hidden, "dh"), _out(dw, torch.float32, J * hidden, "dw"), _out(db, torch.float32, J, "db"),
-            _out(scalars, torch.float32, 2, "scalars")]
-
-
-def dqn_head_td_fwd_bwd(h, h_next, w, b, w_target, b_target, actions, rewards, dones, n_actions, gamma, dh, dw, db, scalars,
-                        target_q_out=None, td_target_out=None):
-    J = int(n_actions)
-    M, hidden, nets, batch = _head_update_ptrs(h, h_next, w, b, w_target, b_target, actions, rewards, dones, J)
-    _lib.call("mi355ppo_dqn_head_td_fwd_bwd_f32_cpu", *nets, *batch, float(gamma), *_head_grads(dh, dw, db, scalars, M, hidden, J),
-              _opt_out(target_q_out, M * J, "target_q_out"), _opt_out(td_target_out, M, "td_target_out"), M, hidden, J)
-    return scalars
-
-
-def c51_head_fwd_bwd(h, h_next, w, b, w_target, b_target, atoms, actions, rewards, dones, n_actions, gamma, v_min, v_max, dh, dw, db, scalars,
-                     next_pmfs_out=None, target_pmfs_out=None):
-    na = atoms.numel()
-    J = int(n_actions) * na
-    M, hidden, nets, batch = _head_update_ptrs(h, h_next, w, b, w_target, b_target, actions, rewards, dones, J)
-    _lib.call("mi355ppo_c51_head_fwd_bwd_f32_cpu", *nets, _in(atoms, torch.float32, (na,), "atoms"), *batch, float(gamma), float(v_min),
-              float(v_max), *_head_grads(dh, dw, db, scalars, M, hidden, J), _opt_out(next_pmfs_out, M * na, "next_pmfs_out"),
-              _opt_out(target_pmfs_out, M * na, "target_pmfs_out"), M, hidden, int(n_actions), na)
-    return scalars
-
-
-# ------------------------------------------------------------------------------------------- QDagger head twins (csrc/qdagger.hip)
-def qdagger_head_act(h, w, b, actions_out, q_out=None):
-    N, hidden = h.shape
-    n = b.numel()
-    _lib.call("mi355ppo_qdagger_head_act_f32_cpu", _in(h, torch.float32, (N, hidden), "h"), _in(w, torch.float32, (n, hidden), "w"),
-              _in(b, torch.float32, (n,), "b"), _out(actions_out, torch.int64, N, "actions_out"), _opt_out(q_out, N * n, "q_out"), N, hidden, n)
-    return actions_out
-
-
-def qdagger_head_fwd_bwd(h, h_next, w, b, w_target, b_target, teacher_q, actions, rewards, dones, gamma, temperature, distill_coeff, dh, dw, db,
-                         scalars, target_q_out=None, td_target_out=None):
-    n = b.numel()
-    M, hidden, nets, batch = _head_update_ptrs(h, h_next, w, b, w_target, b_target, actions, rewards, dones, n)
-    _lib.call("mi355ppo_qdagger_head_fwd_bwd_f32_cpu", *nets, _in(teacher_q, torch.float32, (M, n), "teacher_q"), *batch, float(gamma),
-              float(temperature), float(distill_coeff), _out(dh, torch.float32, M * hidden, "dh"), _out(dw, torch.float32, n * hidden, "dw"),
-              _out(db, torch.float32, n, "db"), _out(scalars, torch.float32, 4, "scalars"), _opt_out(target_q_out, M * n, "target_q_out"),
-              _opt_out(td_target_out, M, "td_target_out"), M, hidden, n)
-    return scalars
-
-
-# ------------------------------------------------------------------------------------------- Rainbow twins (csrc/rainbow_twins.hip)
-def _per_buffer(buf):
-    ring_obs, ring_next, act, rew, done, tree, state, size = buf
-    slots = ring_obs.shape[0]
-    specs = ((ring_obs, torch.uint8, (slots,) + ATARI_FRAME, "ring obs"), (ring_next, torch.uint8, (slots,) + ATARI_FRAME, "ring next_obs"),
-             (act, torch.int64, (slots,), "ring actions"), (rew, torch.float32, (slots,), "ring rewards"),
-             (done, torch.float32, (slots,), "ring dones"), (tree, torch.float32, (2 * slots - 1,), "tree"), (state, torch.float32, (2,), "state"),
-             (size, torch.int64, (1,), "size"))
-    return slots, [_in(t, dt, shape, nm) for t, dt, shape, nm in specs]
-
-
-def rainbow_per_add_u8(buf, pos, obs, next_obs, action, reward, done, alpha):
-    slots, bp = _per_buffer(buf)
-    H, W, C = ATARI_FRAME
-    _lib.call("mi355ppo_rainbow_per_add_u8_cpu", _in(obs, torch.uint8, (1, C, H, W), "obs"), _in(next_obs, torch.uint8, (1, C, H, W), "next_obs"),
-              _in(action, torch.int64, (1,), "action"), _in(reward, torch.float32, (1,), "reward"), _in(done, torch.float32, (1,), "done"),
-              *bp, int(pos), slots, float(alpha))
-
-
-def rainbow_per_sample(buf, u, indices_out, weights_out):
-    slots, bp = _per_buffer(buf)
-    (B,) = u.shape
-    _lib.call("mi355ppo_rainbow_per_sample_cpu", _in(u, torch.float64, (B,), "u"), bp[5], bp[6], bp[7], slots,
-              _out(indices_out, torch.int64, B, "indices_out"), _out(weights_out, torch.float32, B, "weights_out"), B)
-    return indices_out, weights_out
-
-
-def rainbow_per_gather_u8(buf, indices, frames_out, actions_out, rewards_out, dones_out):
-    slots, bp = _per_buffer(buf)
-    (M,) = indices.shape
-    H, W, C = ATARI_FRAME
-    _lib.call("mi355ppo_rainbow_per_gather_u8_cpu", *bp[:5], _in(indices, torch.int64, (M,), "indices"), slots,
-              _out(frames_out, torch.uint8, 2 * M * H * W * C, "frames_out"), _out(actions_out, torch.int64, M, "actions_out"),
-              _out(rewards_out, torch.float32, M, "rewards_out"), _out(dones_out, torch.float32, M, "dones_out"), M)
-    return frames_out
-
-
-def rainbow_per_update(buf, indices, loss_per_sample, alpha, eps):
-    slots, bp = _per_buffer(buf)
-    (B,) = indices.shape
-    _lib.call("mi355ppo_rainbow_per_update_cpu", _in(indices, torch.int64, (B,), "indices"),
-              _in(loss_per_sample, torch.float32, (B,), "loss_per_sample"), bp[5], bp[6], slots, float(alpha), float(eps), B)
-
-
-def rainbow_noisy_compose(params, eps, effective, n_actions, n_atoms):
-    E, P = rainbow_noisy_counts(n_actions, n_atoms)
-    _lib.call("mi355ppo_rainbow_noisy_compose_f32_cpu", _in(params, torch.float32, (P,), "params"), _in(eps, torch.float32, (E,), "eps"),
-              _out(effective, torch.float32, E, "effective"), int(n_actions), int(n_atoms))
-    return effective
-
-
-def rainbow_noisy_grad(effective_grad, eps, grads, n_actions, n_atoms):
-    E, P = rainbow_noisy_counts(n_actions, n_atoms)
-    _lib.call("mi355ppo_rainbow_noisy_grad_f32_cpu", _in(effective_grad, torch.float32, (E,), "effective_grad"),
-              _in(eps, torch.float32, (E,), "eps"), _out(grads, torch.float32, P, "grads"), int(n_actions), int(n_atoms))
-    return grads
-
-
-def _host_chk(t, dtype, name, shape):
-    return _in(t, dtype, shape, name)
-
-
-def rainbow_head_act(h, w_out, b_out, support, n_actions, actions_out, q_out=None):
-    N, na, J = _rainbow_head(h, w_out, b_out, support, n_actions, _host_chk)
-    _lib.call("mi355ppo_rainbow_head_act_f32_cpu", _p(h), _p(w_out), _p(b_out), _p(support), _out(actions_out, torch.int64, N, "actions_out"),
-              _opt_out(q_out, N * n_actions, "q_out"), N, int(n_actions), na)
-    return actions_out
-
-
-def rainbow_head_fwd_bwd(h, h_next, h_next_target, w_out, b_out, w_out_target, b_out_target, support, actions, rewards, dones, weights,
-                         n_actions, gamma_n, v_min, v_max, dh, dw_out, db_out, scalars, loss_per_sample, best_actions_out=None,
-                         next_pmfs_out=None, target_pmfs_out=None):
-    M, na = _rainbow_head_update_args(h, h_next, h_next_target, w_out, b_out, w_out_target, b_out_target, support, actions, rewards, dones, weights,
-                                      n_actions, dh, dw_out, db_out, scalars, loss_per_sample, best_actions_out, next_pmfs_out, target_pmfs_out,
-                                      _host_chk)
-    _lib.call("mi355ppo_rainbow_head_fwd_bwd_f32_cpu", _p(h), _p(h_next), _p(h_next_target), _p(w_out), _p(b_out), _p(w_out_target), _p(b_out_target),
-              _p(support), _p(actions), _p(rewards), _p(dones), _p(weights), float(gamma_n), float(v_min), float(v_max), _p(dh), _p(dw_out),
-              _p(db_out), _p(scalars), _p(loss_per_sample), _p(best_actions_out), _p(next_pmfs_out), _p(target_pmfs_out), M, int(n_actions), na)
-    return scalars
-
-
-# ------------------------------------------------------------------------------------------- discrete SAC on Atari twins (csrc/sac_atari_twins.hip)
-def replay_add2_u8(ring, pos, obs, next_obs, actions, rewards, dones):
-    slots, N = _frame_ring2(ring, _host_chk)
-    H, W, C = ATARI_FRAME
-    _lib.call("mi355ppo_replay_add2_u8_cpu", _in(obs, torch.uint8, (N, C, H, W), "obs"), _in(next_obs, torch.uint8, (N, C, H, W), "next_obs"),
-              _in(actions, torch.int64, (N,), "actions"), _in(rewards, torch.float32, (N,), "rewards"), _in(dones, torch.float32, (N,), "dones"),
-              *[_p(t) for t in ring], int(pos), slots, N)
-
-
-def replay_gather2_u8(ring, batch_inds, env_inds, frames_out, actions_out, rewards_out, dones_out):
-    slots, N = _frame_ring2(ring, _host_chk)
-    (M,) = batch_inds.shape
-    H, W, C = ATARI_FRAME
-    _lib.call("mi355ppo_replay_gather2_u8_cpu", *[_p(t) for t in ring], _in(batch_inds, torch.int64, (M,), "batch_inds"),
-              _in(env_inds, torch.int64, (M,), "env_inds"), slots, N, _out(frames_out, torch.uint8, 2 * M * H * W * C, "frames_out"),
-              _out(actions_out, torch.int64, M, "actions_out"), _out(rewards_out, torch.float32, M, "rewards_out"),
-              _out(dones_out, torch.float32, M, "dones_out"), M)
-    return frames_out
-
-
-def sacd_head_act(h, w, b, noise_exp1, actions_out, probs_out=None):
-    N, hidden, n = _sacd_heads((h,), ((w, b),), _host_chk)
-    _lib.call("mi355ppo_sacd_head_act_f32_cpu", _p(h), _p(w), _p(b), _in(noise_exp1, torch.float32, (N, n), "noise_exp1"),
-              _out(actions_out, torch.int64, N, "actions_out"), _opt_out(probs_out, N * n, "probs_out"), N, hidden, n)
-    return actions_out
-
-
-def sacd_critic_fwd_bwd(hs, heads, actions, rewards, dones, alpha, gamma, dhs, grads, scalars, v_out=None, y_out=None):
-    M, hidden, n = _sacd_heads(hs, heads, _host_chk)
-    if len(hs) != 5:
-        raise ValueError(f"the critic update takes five heads, got {len(hs)}")
-    outs = [_out(dhs[0], torch.float32, M * hidden, "dh1"), _out(dhs[1], torch.float32, M * hidden, "dh2")]
-    for i in range(2):
-        outs += [_out(grads[i][0], torch.float32, n * hidden, f"dw{i + 1}"), _out(grads[i][1], torch.float32, n, f"db{i + 1}")]
-    _lib.call("mi355ppo_sacd_critic_fwd_bwd_f32_cpu", *[_p(h) for h in hs], *[_p(t) for wb in heads for t in wb],
-              _in(actions, torch.int64, (M,), "actions"), _in(rewards, torch.float32, (M,), "rewards"), _in(dones, torch.float32, (M,), "dones"),
-              _in(alpha, torch.float32, (1,), "alpha"), float(gamma), *outs, _out(scalars, torch.float32, 4, "scalars"),
-              _opt_out(v_out, M, "v_out"), _opt_out(y_out, M, "y_out"), M, hidden, n)
-    return scalars
-
-
-def sacd_actor_fwd_bwd(hs, heads, alpha, target_entropy, dh, dw, db, entropy_rows, actor_loss):
-    M, hidden, n = _sacd_heads(hs, heads, _host_chk)
-    if len(hs) != 3:
-        raise ValueError(f"the actor update takes three heads, got {len(hs)}")
-    _lib.call("mi355ppo_sacd_actor_fwd_bwd_f32_cpu", *[_p(h) for h in hs], *[_p(t) for wb in heads for t in wb],
-              _in(alpha, torch.float32, (1,), "alpha"), float(target_entropy), _out(dh, torch.float32, M * hidden, "dh"),
-              _out(dw, torch.float32, n * hidden, "dw"), _out(db, torch.float32, n, "db"), _out(entropy_rows, torch.float32, M, "entropy_rows"),
-              _out(actor_loss, torch.float32, 1, "actor_loss"), M, hidden, n)
-    return actor_loss
+# ------------------------------------------------------------------------------------------- the replay-ring families
+# The host side of cleanrl_amd/replay_ops.py: ``ops._chk`` for CPU tensors, and the ``*_cpu`` twin, which takes neither workspace nor stream.
+def _chk(t, dtype, name, shape=None):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a CPU tensor, got {type(t).__name__}")
+    if t.device.type != "cpu":
+        raise TypeError("cleanrl_amd.host_ops works on CPU tensors only (CUDA tensors run the HIP kernels: cleanrl_amd.ops)")
+    if t.dtype != dtype:
+        raise TypeError(f"{name}: expected dtype {dtype}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: must be contiguous")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def _twin(name, dev, *args):
+    _lib.call(name + "_cpu", *args)
+
+
+def _twin_ws(name, dev, ws_bytes, dims, *args):
+    _lib.call(name + "_cpu", *args)
+
+
+replay_ops.bind(replay_ops.Side(True, _chk, _twin, _twin_ws), globals())
