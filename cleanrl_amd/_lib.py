@@ -291,6 +291,19 @@ SIGNATURES = {
     "mi355ppo_sacd_actor_workspace_bytes": (c_size_t, [c_int, c_int]),
     "mi355ppo_sacd_actor_fwd_bwd_f32": (c_int, [_P] * 10 + [c_double] + [_P] * 5 + [c_int] * 3 + [_P, c_size_t, _P]),
     "mi355ppo_sacd_actor_fwd_bwd_f32_cpu": (c_int, [_P] * 10 + [c_double] + [_P] * 5 + [c_int] * 3),
+    # RND (added under ABI 2.7.1, csrc/rnd.hip)
+    "mi355ppo_rnd_normalize_u8_f32": (c_int, [_P, c_int64, c_int64, c_int, c_int64, _P, _P, _P, _P, c_int, _P]),
+    "mi355ppo_rnd_normalize_u8_f32_cpu": (c_int, [_P, c_int64, c_int64, c_int, c_int64, _P, _P, _P, _P, c_int]),
+    "mi355ppo_rnd_obs_moments_workspace_bytes": (c_size_t, [c_int64]),
+    "mi355ppo_rnd_obs_moments_u8": (c_int, [_P, c_int64, c_int64, c_int, c_int64, _P, _P, c_size_t, _P]),
+    "mi355ppo_rnd_obs_moments_u8_cpu": (c_int, [_P, c_int64, c_int64, c_int, c_int64, _P]),
+    "mi355ppo_rnd_intrinsic_reward_f32": (c_int, [_P, _P, _P, c_int, c_int, _P]),
+    "mi355ppo_rnd_intrinsic_reward_f32_cpu": (c_int, [_P, _P, _P, c_int, c_int]),
+    "mi355ppo_rnd_reward_filter_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_double, _P]),
+    "mi355ppo_rnd_reward_filter_f32_cpu": (c_int, [_P, _P, _P, _P, c_int, c_int, c_double]),
+    "mi355ppo_rnd_loss_workspace_bytes": (c_size_t, [c_int]),
+    "mi355ppo_rnd_loss_fwd_bwd_f32": (c_int, [_P, _P, _P, c_double, _P, _P, _P, c_int64, c_double, _P, _P, _P, c_int, c_int, _P, c_size_t, _P]),
+    "mi355ppo_rnd_loss_fwd_bwd_f32_cpu": (c_int, [_P, _P, _P, c_double, _P, _P, _P, c_int64, c_double, _P, _P, _P, c_int, c_int]),
 }
 
 ABI_VERSION = 271       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)

@@ -19,7 +19,7 @@ import ctypes
 import torch
 
 from . import _lib
-from . import replay_ops
+from . import replay_ops, rnd_ops
 from .ops import IMPALA84_OUT, IMPALA_CHANNELS, _lstm_dims, _ptr_array, pqn_param_count, radam_schedule, trxl_dims  # noqa: F401
 from .replay_ops import (ATARI_FRAME, DQN_HEAD_HIDDEN, DQN_HEAD_MAX_OUT, DQN_HEAD_MAX_ROWS, DQN_HIDDEN, DQN_MAX_ACT, DQN_MAX_ATOMS,  # noqa: F401
                          DQN_MAX_OBS, DQN_MAX_OUT, OFFPOLICY_HIDDEN, OFFPOLICY_MAX_ACT, OFFPOLICY_MAX_OBS, QDAGGER_HIDDEN, QDAGGER_MAX_ROWS,
@@ -495,4 +495,10 @@ def _twin_ws(name, dev, ws_bytes, dims, *args):
     _lib.call(name + "_cpu", *args)
 
 
-replay_ops.bind(replay_ops.Side(True, _chk, _twin, _twin_ws), globals())
+_SIDE = replay_ops.Side(True, _chk, _twin, _twin_ws)
+replay_ops.bind(_SIDE, globals())
+
+# ------------------------------------------------------------------------------------------- RND (csrc/rnd.hip)
+from .rnd_ops import RND_FEATURES, RND_MAX_BATCH, RND_MAX_STEPS, RND_PIXELS, rnd_mean_var  # noqa: E402,F401
+
+rnd_ops.bind(_SIDE, globals())

@@ -21,8 +21,16 @@ reference                              here
                                                                two small torch terms; autograd; fused clip + Adam over
                                                                agent + predictor parameters in one flat buffer)
 ====================================  ==========================================================
+
+``MI355PPO_RND=fused`` (HIP learner only; the default ``torch`` is the table above) moves what surrounds the two RND networks onto
+the kernels of csrc/rnd.hip: ``curiosity`` = normalise kernel + networks + intrinsic-reward kernel with device copies
+of the observation statistics; ``finish_rollout`` = one reward-filter launch on a device (mean, var, count) triple, no host round
+trip; ``update`` = exact integer observation moments of the u8 batch (one 113 KB read-back), the RND input of each minibatch
+normalised straight from the u8 rollout rows, and one loss kernel for the distillation and intrinsic-value terms.
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
@@ -33,6 +41,7 @@ import torch.optim as optim
 
 from . import host_ops
 from .learner import PPOLearner
+from .rnd_ops import RND_PIXELS, rnd_mean_var
 
 
 class RunningMeanStd:
@@ -70,6 +79,46 @@ class RewardForwardFilter:
         return self.rewems
 
 
+def rnd_backend() -> str:
+    """``MI355PPO_RND``: ``torch`` (the default) or ``fused`` (csrc/rnd.hip, HIP learner only); read when a learner is built."""
+    v = os.environ.get("MI355PPO_RND", "torch").strip().lower() or "torch"
+    if v not in ("torch", "fused"):
+        raise ValueError(f"MI355PPO_RND={v!r}: expected 'torch' or 'fused'")
+    return v
+
+
+class DeviceRunningMeanStd:
+    """``reward_rms`` of the fused backend: the (mean, var, count) float64 triple lives on the device, where the reward-filter
+    kernel updates it.  Reading an attribute synchronises (only then); assigning one writes the device triple."""
+
+    def __init__(self, device, epsilon=1e-4):
+        self.stats = torch.tensor([0.0, 1.0, epsilon], dtype=torch.float64, device=device)
+
+    @property
+    def mean(self):
+        return float(self.stats[0].item())
+
+    @mean.setter
+    def mean(self, value):
+        self.stats[0].fill_(float(value))
+
+    @property
+    def var(self):
+        return float(self.stats[1].item())
+
+    @var.setter
+    def var(self, value):
+        self.stats[1].fill_(float(value))
+
+    @property
+    def count(self):
+        return float(self.stats[2].item())
+
+    @count.setter
+    def count(self, value):
+        self.stats[2].fill_(float(value))
+
+
 class _Combined(nn.Module):
     """agent parameters followed by the predictor's: the order of ``combined_parameters`` (:295)."""
 
@@ -104,6 +153,31 @@ class RNDPPOLearner(PPOLearner):
         self.obs_rms = RunningMeanStd(shape=(1, 1, 84, 84))
         self.discounted_reward = RewardForwardFilter(args.int_gamma)
         self.last_fwd_loss = float("nan")
+        self.rnd_fused = False
+        if self.hip and rnd_backend() == "fused":
+            self.init_rnd_fused()
+
+    def init_rnd_fused(self) -> None:
+        """The state of ``MI355PPO_RND=fused``: device copies of the observation statistics, the filter state and the reward
+        statistics on the device (``discounted_reward`` is not used), the buffers the kernels write."""
+        assert self.hip and self.nhwc, "MI355PPO_RND=fused runs on the HIP learner's u8 NHWC rollout storage"
+        dev, P = self.device, RND_PIXELS
+        self.rnd_fused = True
+        self._rnd_mean = torch.zeros(P, dtype=torch.float64, device=dev)
+        self._rnd_sd = torch.ones(P, dtype=torch.float64, device=dev)
+        self._rnd_sums = torch.zeros((2, P), dtype=torch.int64, device=dev)
+        self._rnd_rewems = torch.zeros(self.T, device=dev)              # all zero == the reference's "first call returns rews"
+        self._rnd_x_step = torch.empty((self.N, 1, 84, 84), device=dev)
+        self._rnd_x_mb = None
+        self.reward_rms = DeviceRunningMeanStd(dev)
+        self.refresh_obs_stats()
+
+    def refresh_obs_stats(self) -> None:
+        """Upload ``obs_rms.mean`` and ``sqrt(obs_rms.var)`` (float64, formed once here) to the device copies the normalise kernel
+        reads.  Runs by itself at the first ``curiosity`` of a rollout and in ``update``; call it after overwriting ``obs_rms``
+        anywhere else."""
+        self._rnd_mean.copy_(torch.from_numpy(np.ascontiguousarray(self.obs_rms.mean, dtype=np.float64).reshape(-1)))
+        self._rnd_sd.copy_(torch.from_numpy(np.sqrt(np.asarray(self.obs_rms.var, dtype=np.float64)).reshape(-1)))
 
     # ------------------------------------------------------------------ rollout
     def _newest_frame(self, rows):
@@ -140,6 +214,13 @@ class RNDPPOLearner(PPOLearner):
     def curiosity(self, step: int):
         """Intrinsic reward of the transition into the observation stored in slot ``step + 1`` (:363-371)."""
         rows, _ = self._slot(step + 1)
+        if self.rnd_fused:
+            if step == 0:
+                self.refresh_obs_stats()
+            x = self.ops.rnd_normalize(rows, self._rnd_mean, self._rnd_sd, out=self._rnd_x_step)
+            self.ops.rnd_intrinsic_reward(self.rnd_model.target(x).contiguous(), self.rnd_model.predictor(x).contiguous(),
+                                          out=self.curiosity_rewards[step])
+            return self.curiosity_rewards[step]
         rnd_next_obs = self._rnd_input(rows)
         target_next_feature = self.rnd_model.target(rnd_next_obs)
         predict_next_feature = self.rnd_model.predictor(rnd_next_obs)
@@ -149,12 +230,15 @@ class RNDPPOLearner(PPOLearner):
     @torch.no_grad()
     def finish_rollout(self) -> None:
         a = self.args
-        # :390-400 intrinsic-reward scaling -- (T, N) floats through the host, as the reference
-        curiosity_reward_per_env = np.array(
-            [self.discounted_reward.update(reward_per_step) for reward_per_step in self.curiosity_rewards.cpu().data.numpy().T])
-        mean, std, count = (np.mean(curiosity_reward_per_env), np.std(curiosity_reward_per_env), len(curiosity_reward_per_env))
-        self.reward_rms.update_from_moments(mean, std**2, count)
-        self.curiosity_rewards /= np.sqrt(self.reward_rms.var)
+        if self.rnd_fused:  # :390-400 in one launch: filter along the env axis, running variance, division -- nothing leaves the device
+            self.ops.rnd_reward_filter_(self.curiosity_rewards, self._rnd_rewems, self.reward_rms.stats, a.int_gamma)
+        else:
+            # :390-400 intrinsic-reward scaling -- (T, N) floats through the host, as the reference
+            curiosity_reward_per_env = np.array(
+                [self.discounted_reward.update(reward_per_step) for reward_per_step in self.curiosity_rewards.cpu().data.numpy().T])
+            mean, std, count = (np.mean(curiosity_reward_per_env), np.std(curiosity_reward_per_env), len(curiosity_reward_per_env))
+            self.reward_rms.update_from_moments(mean, std**2, count)
+            self.curiosity_rewards /= np.sqrt(self.reward_rms.var)
         if self.hip:
             _, v_ext, v_int = self.agent.heads3(self._features(self.boot_obs))
             self.ops.gae(self.rewards, self.dones, self.values, self.boot_done, v_ext.reshape(-1).contiguous(),
@@ -185,17 +269,23 @@ class RNDPPOLearner(PPOLearner):
         b_ext_returns, b_int_returns = self.returns.reshape(-1), self.int_returns.reshape(-1)
         b_ext_values = self.values.reshape(-1)
         b_advantages = self.int_advantages.reshape(-1) * a.int_coef + self.advantages.reshape(-1) * a.ext_coef     # :444
-        newest = self._newest_frame(b_obs)
-        if self.hip:        # statistics of np.mean / np.var over the batch axis, on the device in f64
-            d = newest.double()
-            self.obs_rms.update_from_moments(d.mean(0).cpu().numpy(), d.var(0, unbiased=False).cpu().numpy(), d.shape[0])
-            del d
+        if self.rnd_fused:  # :446 from exact integer moments of the u8 rows; :453-458 per minibatch, straight from the rollout rows
+            mean, var = rnd_mean_var(self.ops.rnd_obs_moments(b_obs, self._rnd_sums), B)
+            self.obs_rms.update_from_moments(mean.reshape(1, 1, 84, 84), var.reshape(1, 1, 84, 84), B)
+            self.refresh_obs_stats()
+            rnd_next_obs = None
         else:
-            self.obs_rms.update(newest.cpu().numpy())                                                          # :446
-        mean = torch.from_numpy(self.obs_rms.mean).to(self.device)
-        var = torch.from_numpy(self.obs_rms.var).to(self.device)
-        rnd_next_obs = ((newest - mean) / torch.sqrt(var)).clip(-5, 5).float()                                   # :453-458
-        del newest
+            newest = self._newest_frame(b_obs)
+            if self.hip:        # statistics of np.mean / np.var over the batch axis, on the device in f64
+                d = newest.double()
+                self.obs_rms.update_from_moments(d.mean(0).cpu().numpy(), d.var(0, unbiased=False).cpu().numpy(), d.shape[0])
+                del d
+            else:
+                self.obs_rms.update(newest.cpu().numpy())                                                          # :446
+            mean = torch.from_numpy(self.obs_rms.mean).to(self.device)
+            var = torch.from_numpy(self.obs_rms.var).to(self.device)
+            rnd_next_obs = ((newest - mean) / torch.sqrt(var)).clip(-5, 5).float()                                   # :453-458
+            del newest
         k = 0
         clipfracs = []
         last = None
@@ -241,6 +331,9 @@ class RNDPPOLearner(PPOLearner):
     def _minibatch_rnd_hip(self, idx, b_obs, rnd_next_obs, b_actions, b_logprobs, b_advantages, b_ext_returns, b_int_returns,
                            b_ext_values, lr, k):
         a, ops = self.args, self.ops
+        if self.rnd_fused:
+            return self._minibatch_rnd_fused(idx, b_obs, b_actions, b_logprobs, b_advantages, b_ext_returns, b_int_returns, b_ext_values,
+                                             lr, k)
         forward_loss = self._forward_loss(rnd_next_obs.index_select(0, idx))
         if self._x_mb is None or self._x_mb.shape[0] != idx.numel():
             self._x_mb = torch.empty((idx.numel(),) + self.obs_shape, device=self.device)
@@ -256,6 +349,30 @@ class RNDPPOLearner(PPOLearner):
         self._extra[k, 0], self._extra[k, 1] = int_v_loss.detach(), forward_loss.detach().view(())
         rest = int_v_loss * a.vf_coef + forward_loss.view(())
         torch.autograd.backward([logits, v_ext, rest], [dlogits, dv_ext, None])                               # :518
+        if self.world_size > 1:
+            dist.all_reduce(self.flat.grads, op=dist.ReduceOp.SUM)
+        self.optimizer_step_hip(lr)                                                                           # :519-524
+
+    def _minibatch_rnd_fused(self, idx, b_obs, b_actions, b_logprobs, b_advantages, b_ext_returns, b_int_returns, b_ext_values, lr, k):
+        """``_minibatch_rnd_hip`` with the RND input normalised from the u8 rows and the two extra loss terms in one kernel."""
+        a, ops = self.args, self.ops
+        M = idx.numel()
+        if self._rnd_x_mb is None or self._rnd_x_mb.shape[0] != M:
+            self._rnd_x_mb = torch.empty((M, 1, 84, 84), device=self.device)
+        predict, target = self.rnd_model(ops.rnd_normalize(b_obs, self._rnd_mean, self._rnd_sd, idx=idx, out=self._rnd_x_mb))   # :453-458, :463
+        u = torch.rand(M, device=self.device)                                                                 # :467
+        if self._x_mb is None or self._x_mb.shape[0] != M:
+            self._x_mb = torch.empty((M,) + self.obs_shape, device=self.device)
+        x = ops.obs_u8_to_f32(b_obs, idx, self._x_mb).permute(0, 3, 1, 2)
+        logits, v_ext, v_int = self.agent.heads3(x)
+        v_ext, v_int = v_ext.view(-1), v_int.view(-1)
+        _, dlogits, dv_ext = ops.ppo_loss_categorical(logits.detach().contiguous(), v_ext.detach().contiguous(), idx, b_actions,
+                                                      b_logprobs, b_advantages, b_ext_returns, b_ext_values, a.clip_coef,
+                                                      a.ent_coef, a.vf_coef, a.norm_adv, a.clip_vloss,
+                                                      scalars_out=self._scalars[k])
+        _, d_predict, d_v_int = ops.rnd_loss_fwd_bwd(predict.detach().contiguous(), target.detach().contiguous(), u, a.update_proportion,
+                                                     v_int.detach().contiguous(), b_int_returns, idx, a.vf_coef, scalars=self._extra[k])
+        torch.autograd.backward([logits, v_ext, v_int, predict], [dlogits, dv_ext, d_v_int, d_predict])       # :518
         if self.world_size > 1:
             dist.all_reduce(self.flat.grads, op=dist.ReduceOp.SUM)
         self.optimizer_step_hip(lr)                                                                           # :519-524

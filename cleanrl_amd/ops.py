@@ -17,7 +17,7 @@ import sys
 
 import torch
 
-from . import _lib, replay_ops
+from . import _lib, replay_ops, rnd_ops
 from .replay_ops import _ptr
 
 __all__ = [
@@ -35,6 +35,7 @@ __all__ = [
     "rainbow_noisy_limits_ok", "rainbow_noisy_counts", "rainbow_new_buffer", "rainbow_per_add_u8", "rainbow_per_sample", "rainbow_per_gather_u8",
     "rainbow_per_update", "rainbow_noisy_compose", "rainbow_noisy_grad", "rainbow_head_limits_ok", "rainbow_head_act", "rainbow_head_fwd_bwd",
     "sacd_limits_ok", "replay_add2_u8", "replay_gather2_u8", "sacd_head_act", "sacd_critic_fwd_bwd", "sacd_actor_fwd_bwd",
+    "rnd_normalize", "rnd_obs_moments", "rnd_mean_var", "rnd_intrinsic_reward", "rnd_reward_filter_", "rnd_loss_fwd_bwd",
 ]
 
 LOSS_SCALAR_NAMES = ("loss", "pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac")
@@ -1421,4 +1422,10 @@ def _device_launch_ws(name: str, dev: torch.device, ws_bytes: str, dims, *args) 
     _launch(name, dev, *args, _ptr(ws), ws.numel())
 
 
-replay_ops.bind(replay_ops.Side(False, _chk, _device_launch, _device_launch_ws), globals())
+_SIDE = replay_ops.Side(False, _chk, _device_launch, _device_launch_ws)
+replay_ops.bind(_SIDE, globals())
+
+# ------------------------------------------------------------------------------------------- RND (csrc/rnd.hip)
+from .rnd_ops import RND_FEATURES, RND_MAX_BATCH, RND_MAX_STEPS, RND_PIXELS, rnd_mean_var  # noqa: E402,F401
+
+rnd_ops.bind(_SIDE, globals())

@@ -53,6 +53,9 @@ extern "C" {
                                   binding finds out whether they are there by looking the symbols up);
                                   the Atari DQN / C51 heads, Rainbow and discrete SAC on Atari (mi355ppo_replay_add2_u8, mi355ppo_replay_gather2_u8,
                                   mi355ppo_sacd_*) likewise;
+                                  RND -- mi355ppo_rnd_* (newest-frame normalisation, exact observation moments, intrinsic reward, the
+                                  env-axis reward filter, the distillation / intrinsic-value loss) and their *_cpu twins likewise: only
+                                  added, the number stays at 2.7.1;
                                   a binding must check major AND minor (cleanrl_amd/_lib.py does) */
 
 #if defined(__GNUC__)
@@ -1413,6 +1416,62 @@ MI355PPO_API int mi355ppo_qdagger_head_fwd_bwd_f32_cpu(const float* h, const flo
                                                        double temperature, double distill_coeff, float* dh, float* dw, float* db,
                                                        float* scalars_out, float* target_q_out, float* td_target_out, int M, int hidden,
                                                        int n_actions);
+
+/* ---------------------------------------------------------------------------------------------
+ * Random Network Distillation (cleanrl/ppo_rnd_envpool.py; csrc/rnd.hip, row math in csrc/rnd_rows.h): what the learner does around
+ * the two RND networks.  Every *_cpu twin takes host pointers and returns the device's bits.  No entry point allocates or synchronises
+ * (all are capturable); no atomics: every result is a pure function of the inputs.
+ *
+ * A FRAME is the 84 x 84 = 7056 newest-frame bytes of an observation row of row_bytes bytes (B rows at src), pixel p at byte
+ * byte_offset + pixel_stride * p of the row: pixel_stride 4 (the learner's NHWC rows of 4 stacked frames, byte_offset 3: whole 4-byte
+ * pixels are read, src 4-byte aligned, row_bytes a multiple of 4) or 1 (planar NCHW rows, byte_offset 3 * 7056).
+ *
+ * normalize (ppo_rnd_envpool.py:365-370, :449-454): out (M, 1, 84, 84) f32, out[r, p] = (float)clip(((double)x - mean[p]) / sd[p], -5, 5)
+ * with x the frame pixel of row idx[r] (idx NULL: row r; an index out of range is clamped): the reference's float64 arithmetic with
+ * one rounding to f32.  mean / sd: float64[7056], sd = sqrt(var) formed once by the caller. */
+MI355PPO_API int mi355ppo_rnd_normalize_u8_f32(const unsigned char* src, int64_t B, int64_t row_bytes, int pixel_stride, int64_t byte_offset,
+                                               const int64_t* idx, const double* mean, const double* sd, float* out, int M, void* stream);
+MI355PPO_API int mi355ppo_rnd_normalize_u8_f32_cpu(const unsigned char* src, int64_t B, int64_t row_bytes, int pixel_stride, int64_t byte_offset,
+                                                   const int64_t* idx, const double* mean, const double* sd, float* out, int M);
+/* Per-pixel batch moments of the frame over all B rows, exact: sums (uint64[2][7056]) is OVERWRITTEN with S1[p] = sum x and
+ * S2[p] = sum x^2 (32-bit partials over slabs of 256 rows, 255^2 * 256 < 2^32, folded in 64 bits).  The caller forms mean = S1 / B and
+ * var = (B S2 - S1^2) / B^2; the numerator is exact in 64-bit integers for B < 2^24 -- a larger B returns MI355PPO_EINVAL.
+ * workspace: mi355ppo_rnd_obs_moments_workspace_bytes(B) bytes, 16-byte aligned.  Two launches. */
+MI355PPO_API size_t mi355ppo_rnd_obs_moments_workspace_bytes(int64_t B);
+MI355PPO_API int mi355ppo_rnd_obs_moments_u8(const unsigned char* src, int64_t B, int64_t row_bytes, int pixel_stride, int64_t byte_offset,
+                                             uint64_t* sums, void* workspace, size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_rnd_obs_moments_u8_cpu(const unsigned char* src, int64_t B, int64_t row_bytes, int pixel_stride, int64_t byte_offset,
+                                                 uint64_t* sums);
+/* Intrinsic reward (:373): out[n] = sum_f (target[n, f] - predict[n, f])^2 / 2 over F == 512 features (any other F: MI355PPO_EINVAL), in
+ * one fixed order (per lane 8 terms, then a 64-lane butterfly).  Feature rows 16-byte aligned. */
+MI355PPO_API int mi355ppo_rnd_intrinsic_reward_f32(const float* target, const float* predict, float* out, int N, int F, void* stream);
+MI355PPO_API int mi355ppo_rnd_intrinsic_reward_f32_cpu(const float* target, const float* predict, float* out, int N, int F);
+/* Intrinsic-reward scaling (:390-400) in one call.  The reference iterates over curiosity_rewards.T, so its RewardForwardFilter runs
+ * ALONG THE ENV AXIS with a T-vector of state that persists across rollouts; reproduced as written: for n = 0 .. N-1,
+ * rewems[t] = fl32(fl32(rewems[t] * (float)gamma) + curiosity[t][n]) (T independent scans; an all-zero rewems is the reference's first
+ * call).  Over the N x T filtered values: mean and population variance in float64 (per scan in ascending n, the scans in ascending t),
+ * RunningMeanStd.update_from_moments(mean, var, N) on stats3 = (mean, var, count) in float64 in the host class's operation order, then
+ * curiosity (T, N) is OVERWRITTEN with curiosity / (float)sqrt(var_new).  filtered_out (T, N), optional: the filtered values.
+ * 1 <= T <= 1024.  One launch of one workgroup. */
+MI355PPO_API int mi355ppo_rnd_reward_filter_f32(float* curiosity, float* rewems, double* stats3, float* filtered_out, int T, int N, double gamma,
+                                                void* stream);
+MI355PPO_API int mi355ppo_rnd_reward_filter_f32_cpu(float* curiosity, float* rewems, double* stats3, float* filtered_out, int T, int N,
+                                                    double gamma);
+/* The two loss terms of a minibatch that the fused PPO loss does not cover (:463-472, :512), forward and backward, on predict / target
+ * (M, 512), uniform draws u (M), v_int (M) and int_returns (B rows) gathered by mb_inds (M; clamped):
+ *   mask_m = u_m < (float)update_proportion, c = max(sum mask, 1)
+ *   scalars_out[0] = 0.5 * mean_m (v_int - R)^2                 scalars_out[1] = sum_m mask_m mean_f (predict - target)^2 / c
+ *   d_v_int[m] = (v_int - R) * (float)(vf_coef / M)             d_predict[m, f] = mask_m * 2 (predict - target) * (float)(1 / (512 c))
+ * (the gradients of vf_coef * scalars_out[0] + scalars_out[1]); the scalars are summed in f64 in a fixed order.  F == 512.
+ * workspace: mi355ppo_rnd_loss_workspace_bytes(M) bytes, 16-byte aligned.  Three launches. */
+MI355PPO_API size_t mi355ppo_rnd_loss_workspace_bytes(int M);
+MI355PPO_API int mi355ppo_rnd_loss_fwd_bwd_f32(const float* predict, const float* target, const float* u, double update_proportion,
+                                               const float* v_int, const float* int_returns, const int64_t* mb_inds, int64_t B, double vf_coef,
+                                               float* scalars_out, float* d_predict, float* d_v_int, int M, int F, void* workspace,
+                                               size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_rnd_loss_fwd_bwd_f32_cpu(const float* predict, const float* target, const float* u, double update_proportion,
+                                                   const float* v_int, const float* int_returns, const int64_t* mb_inds, int64_t B,
+                                                   double vf_coef, float* scalars_out, float* d_predict, float* d_v_int, int M, int F);
 
 #ifdef __cplusplus
 }
