@@ -304,6 +304,18 @@ SIGNATURES = {
     "mi355ppo_rnd_loss_workspace_bytes": (c_size_t, [c_int]),
     "mi355ppo_rnd_loss_fwd_bwd_f32": (c_int, [_P, _P, _P, c_double, _P, _P, _P, c_int64, c_double, _P, _P, _P, c_int, c_int, _P, c_size_t, _P]),
     "mi355ppo_rnd_loss_fwd_bwd_f32_cpu": (c_int, [_P, _P, _P, c_double, _P, _P, _P, c_int64, c_double, _P, _P, _P, c_int, c_int]),
+    # PPG's auxiliary phase (added under ABI 2.7.1, csrc/ppg.hip, csrc/optim.hip)
+    "mi355ppo_ppg_aux_gather_u8_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int64, c_int64, _P]),
+    "mi355ppo_ppg_aux_gather_u8_f32_cpu": (c_int, [_P, _P, _P, c_int, c_int, c_int64, c_int64]),
+    "mi355ppo_ppg_old_logits_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int64, c_int, c_int, _P]),
+    "mi355ppo_ppg_old_logits_f32_cpu": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int64, c_int, c_int]),
+    "mi355ppo_ppg_aux_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "mi355ppo_ppg_aux_fwd_bwd_f32": (c_int, [_P] * 10 + [c_int, c_int, c_int64, c_int, c_int, c_double, c_double] + [_P] * 8 + [c_int, _P, c_size_t, _P]),
+    "mi355ppo_ppg_aux_fwd_bwd_f32_cpu": (c_int, [_P] * 10 + [c_int, c_int, c_int64, c_int, c_int, c_double, c_double] + [_P] * 8 + [c_int]),
+    "mi355ppo_clip_adam_split_f32": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_double, c_double, c_double, c_double, c_double, c_double, c_int64,
+                                             c_int64, _P, _P, c_size_t, _P]),
+    "mi355ppo_clip_adam_split_f32_cpu": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_double, c_double, c_double, c_double, c_double, c_double, c_int64,
+                                                 c_int64, _P]),
 }
 
 ABI_VERSION = 271       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)

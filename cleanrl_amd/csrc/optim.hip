@@ -80,6 +80,35 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ p, f
     }
 }
 
+// clip_adam_kernel with two step counts: elements [0, n_split) take A's bias corrections, [n_split, n) the tail's (neg_step_tail,
+// bc2_sqrt_tail) -- torch.optim.Adam keeps a step count per parameter, and PPG's auxiliary value head only steps in the auxiliary
+// phase.  One global norm and one clip coefficient for both ranges; the same partials, fold and element update as clip_adam_kernel.
+__global__ __launch_bounds__(256) void clip_adam_split_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                              float* __restrict__ v, int64_t n, int64_t n_split, AdamParams A,
+                                                              float neg_step_tail, float bc2_sqrt_tail, const double* __restrict__ partials,
+                                                              float* __restrict__ total_norm_out) {
+    __shared__ float s_coef;
+    if (threadIdx.x < 64) {
+        double s = 0.0;
+        for (int b = threadIdx.x; b < A.nblocks; b += 64) s += partials[b];
+        s = wave_sum(s);
+        if (threadIdx.x == 0) {
+            const float total = (float)sqrt(s);
+            float coef = A.max_norm / (total + 1e-6f);
+            coef = fminf(coef, 1.0f);
+            s_coef = coef;
+            if (blockIdx.x == 0 && total_norm_out) *total_norm_out = total;
+        }
+    }
+    __syncthreads();
+    const float coef = s_coef;
+    AdamParams B = A;
+    B.neg_step = neg_step_tail;
+    B.bc2_sqrt = bc2_sqrt_tail;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+        adam_elem(p[i], g[i], m[i], v[i], coef, i < n_split ? A : B);
+}
+
 }  // namespace mi355ppo
 
 using namespace mi355ppo;
@@ -158,4 +187,49 @@ extern "C" MI355PPO_API int mi355ppo_clip_adam_sched_f32(float* params, float* g
     MI355_REQUIRE(sched2, MI355PPO_EINVAL, "mi355ppo_clip_adam_sched_f32: null pointer");
     return clip_adam_impl("mi355ppo_clip_adam_sched_f32", params, grads, exp_avg, exp_avg_sq, n, grad_scale, max_grad_norm, 0.0, beta1, beta2,
                           eps, 1, sched2, total_norm_out, workspace, workspace_bytes, stream);
+}
+
+// PPG's auxiliary-phase step (cleanrl/ppg_procgen.py:466-468) in two launches and no host round trip: one global norm over all n
+// gradients times grad_scale by grad_sumsq_kernel (the grid and f64 partials of mi355ppo_clip_adam_f32), then clip + Adam with
+// step_head's bias corrections on [0, n_split) and step_tail's on [n_split, n); gradients are zeroed.
+extern "C" MI355PPO_API int mi355ppo_clip_adam_split_f32(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int64_t n_split,
+                                                        double grad_scale, double max_grad_norm, double lr, double beta1, double beta2, double eps,
+                                                        int64_t step_head, int64_t step_tail, float* total_norm_out, void* workspace,
+                                                        size_t workspace_bytes, void* stream) {
+    const char* fn = "mi355ppo_clip_adam_split_f32";
+    MI355_REQUIRE(params && grads && exp_avg && exp_avg_sq, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(n > 0 && n_split >= 0 && n_split <= n && step_head >= 1 && step_tail >= 1, MI355PPO_EINVAL,
+                  "%s: n=%lld n_split=%lld step_head=%lld step_tail=%lld: n > 0, 0 <= n_split <= n, steps >= 1", fn, (long long)n, (long long)n_split,
+                  (long long)step_head, (long long)step_tail);
+    MI355_REQUIRE(workspace && workspace_bytes >= (size_t)kNormMaxBlocks * sizeof(double), MI355PPO_EWORKSPACE,
+                  "%s: workspace %zu bytes < required %zu", fn, workspace ? workspace_bytes : (size_t)0, (size_t)kNormMaxBlocks * sizeof(double));
+    MI355_REQUIRE(aligned(params, 16) && aligned(grads, 16) && aligned(exp_avg, 16) && aligned(exp_avg_sq, 16) && aligned(workspace, 8) &&
+                      aligned(total_norm_out, 4),
+                  MI355PPO_EALIGN, "%s: flat buffers must be 16-byte aligned", fn);
+    hipStream_t s = as_stream(stream);
+    const int64_t n4 = (n + 3) / 4;
+    int64_t blocks = (n4 + 255) / 256;
+    if (blocks > kNormMaxBlocks) blocks = kNormMaxBlocks;
+    double* partials = static_cast<double*>(workspace);
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)blocks), dim3(256), 0, s, grads, n, (float)grad_scale, partials);
+    if (int rc = check_launch("grad_sumsq_kernel")) return rc;
+    AdamParams A;
+    A.scale = (float)grad_scale;
+    A.max_norm = (float)max_grad_norm;
+    A.w1 = (float)(1.0 - beta1);
+    A.beta2 = (float)beta2;
+    A.w2 = (float)(1.0 - beta2);
+    float head[2], tail[2];
+    mi355ppo_adam_schedule_f32(lr, beta1, beta2, step_head, head);
+    mi355ppo_adam_schedule_f32(lr, beta1, beta2, step_tail, tail);
+    A.neg_step = head[0];
+    A.bc2_sqrt = head[1];
+    A.eps = (float)eps;
+    A.nblocks = (int)blocks;
+    A.zero_grads = 1;
+    int64_t ublocks = (n + 255) / 256;
+    if (ublocks > 2048) ublocks = 2048;
+    hipLaunchKernelGGL(clip_adam_split_kernel, dim3((unsigned)ublocks), dim3(256), 0, s, params, grads, exp_avg, exp_avg_sq, n, n_split, A, tail[0],
+                       tail[1], partials, total_norm_out);
+    return check_launch("clip_adam_split_kernel");
 }

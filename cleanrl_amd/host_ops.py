@@ -19,7 +19,7 @@ import ctypes
 import torch
 
 from . import _lib
-from . import replay_ops, rnd_ops
+from . import ppg_ops, replay_ops, rnd_ops
 from .ops import IMPALA84_OUT, IMPALA_CHANNELS, _lstm_dims, _ptr_array, pqn_param_count, radam_schedule, trxl_dims  # noqa: F401
 from .replay_ops import (ATARI_FRAME, DQN_HEAD_HIDDEN, DQN_HEAD_MAX_OUT, DQN_HEAD_MAX_ROWS, DQN_HIDDEN, DQN_MAX_ACT, DQN_MAX_ATOMS,  # noqa: F401
                          DQN_MAX_OBS, DQN_MAX_OUT, OFFPOLICY_HIDDEN, OFFPOLICY_MAX_ACT, OFFPOLICY_MAX_OBS, QDAGGER_HIDDEN, QDAGGER_MAX_ROWS,
@@ -502,3 +502,8 @@ replay_ops.bind(_SIDE, globals())
 from .rnd_ops import RND_FEATURES, RND_MAX_BATCH, RND_MAX_STEPS, RND_PIXELS, rnd_mean_var  # noqa: E402,F401
 
 rnd_ops.bind(_SIDE, globals())
+
+# ------------------------------------------------------------------------------------------- PPG's auxiliary phase (csrc/ppg.hip)
+from .ppg_ops import PPG_HIDDEN, PPG_MAX_ACT, PPG_MAX_ROWS, PPG_MIN_ACT  # noqa: E402,F401
+
+ppg_ops.bind(_SIDE, globals())

@@ -15,8 +15,12 @@ reference (ppg_procgen.py)             here
                                        = aux value + beta_clone * KL(old || new), plus the real value loss; gradient
                                        accumulation, clip, Adam
 ====================================  ==========================================================
+
+``MI355PPO_PPG=fused`` (HIP learner only) runs the auxiliary phase on csrc/ppg.hip: ``_aux_phase_fused``.
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
@@ -26,6 +30,7 @@ import torch.nn as nn
 import torch.optim as optim
 from torch.distributions.categorical import Categorical
 
+from .agents import _impala_features
 from .learner import PPOLearner
 
 
@@ -35,6 +40,14 @@ def flatten01(arr):
 
 def unflatten01(arr, targetshape):
     return arr.reshape((*targetshape, *arr.shape[1:]))
+
+
+def ppg_backend() -> str:
+    """``MI355PPO_PPG``: ``torch`` (the default) or ``fused`` (csrc/ppg.hip, HIP learner only); read when a learner is built."""
+    v = os.environ.get("MI355PPO_PPG", "torch").strip().lower() or "torch"
+    if v not in ("torch", "fused"):
+        raise ValueError(f"MI355PPO_PPG={v!r}: expected 'torch' or 'fused'")
+    return v
 
 
 class PPGLearner(PPOLearner):
@@ -54,6 +67,7 @@ class PPGLearner(PPOLearner):
         self._aux_tail_step = 0                         # Adam step count of the auxiliary value head (see _aux_step_hip)
         self._last_lr = float(args.learning_rate)
         self.last_aux = {}
+        self.ppg_fused = ppg_backend() == "fused" and self.hip
 
     # ------------------------------------------------------------------ policy phase
     def optimizer_step_hip(self, lr: float) -> None:
@@ -115,7 +129,70 @@ class PPGLearner(PPOLearner):
             return self.agent.heads_aux(x)
         return self.agent.heads_aux(self.agent._normalise(rows))
 
+    def _aux_step_fused(self, lr: float) -> None:
+        """``_aux_step_hip`` in one call and without its device->host read of the norm: the global-norm clip and both step counts
+        inside ``clip_adam_split_`` (the clip coefficient is formed in f32 on the device, as ``clip_adam_`` forms it)."""
+        f, a = self.flat, self.args
+        tail = sum(p.numel() for p in self.agent.aux_critic.parameters())
+        assert f._params_list[-1] is self.agent.aux_critic.bias
+        f.step += 1
+        self._aux_tail_step += 1
+        self.ops.clip_adam_split_(f.params, f.grads, f.exp_avg, f.exp_avg_sq, f.numel - tail, f.step, self._aux_tail_step, lr,
+                                  a.max_grad_norm, grad_scale=1.0 / self.world_size, eps=self.adam_eps, total_norm_out=self._total_norm)
+
+    def _aux_hidden(self, cols):
+        """The 256 features of the whole rollouts ``cols`` (a device int64 tensor): one gather + u8 -> f32 launch, then the trunk."""
+        x = self.ops.ppg_aux_gather(self.aux_obs, cols)
+        return _impala_features(self.agent, x.permute(0, 3, 1, 2))
+
+    def _aux_phase_fused(self) -> dict:
+        """``aux_phase`` on csrc/ppg.hip (``MI355PPO_PPG=fused``): ``aux_pi`` stays on the device, an epoch's shuffled rollouts are
+        uploaded once, a minibatch is gather -> trunk -> heads + loss + backward -> trunk backward -> clip + Adam, and nothing is
+        read back until the last minibatch is done."""
+        a, ag, ops = self.args, self.agent, self.ops
+        R, nr, A, accum = int(a.aux_batch_rollouts), int(a.num_aux_rollouts), ag.n_actions, int(a.n_aux_grad_accum)
+        assert self._aux_update * self.N == R, "the auxiliary phase follows n_iteration policy updates"
+        dev = self.aux_obs.device
+        aux_inds = np.arange(R)
+        aux_pi = torch.zeros((self.T, R, A), device=dev)
+        inds_dev = torch.from_numpy(aux_inds.copy()).to(dev)
+        with torch.no_grad():                                                                # :417-431
+            for start in range(0, R, nr):
+                cols = inds_dev[start:start + nr]
+                ops.ppg_old_logits_(self._aux_hidden(cols).contiguous(), ag.actor.weight.data, ag.actor.bias.data, cols, aux_pi)
+        heads = [p for m in (ag.actor, ag.critic, ag.aux_critic) for p in (m.weight, m.bias)]
+        head_grads = [p.grad for p in heads]
+        heads = [p.data for p in heads]
+        stale = self._stale_grads is not None                # the reference quirk (see aux_phase): the first backward lands on it
+        if stale:
+            self.flat.grads.copy_(self._stale_grads)
+            self._stale_grads = None
+        scalars = torch.zeros(3, device=dev)
+        for auxiliary_update in range(1, int(a.e_auxiliary) + 1):                           # :433-471
+            print(f"aux epoch {auxiliary_update}")
+            np.random.shuffle(aux_inds)
+            inds_dev = torch.from_numpy(aux_inds.copy()).to(dev)
+            for i, start in enumerate(range(0, R, nr)):
+                cols = inds_dev[start:start + nr]
+                hidden = self._aux_hidden(cols)
+                # the flat gradient is zero after a step, so the heads' gradients are only added to what is there on the stale
+                # first step and on the later minibatches of an accumulation group
+                _, dh = ops.ppg_aux_fwd_bwd(hidden.detach(), heads, aux_pi, self.aux_returns, cols, float(a.beta_clone), 1.0 / accum,
+                                            head_grads, stale or i % accum != 0, scalars=scalars)
+                hidden.backward(dh)
+                if (i + 1) % accum == 0:
+                    if self.world_size > 1:
+                        dist.all_reduce(self.flat.grads, op=dist.ReduceOp.SUM)
+                    self._aux_step_fused(self._last_lr)
+                    stale = False
+        self._aux_update = 0
+        kl_loss, aux_value_loss, real_value_loss = scalars.tolist()
+        self.last_aux = dict(kl_loss=kl_loss, aux_value_loss=aux_value_loss, real_value_loss=real_value_loss)
+        return self.last_aux
+
     def aux_phase(self) -> dict:
+        if self.ppg_fused:
+            return self._aux_phase_fused()
         a = self.args
         R, nr, A = int(a.aux_batch_rollouts), int(a.num_aux_rollouts), self.agent.n_actions
         assert self._aux_update * self.N == R, "the auxiliary phase follows n_iteration policy updates"

@@ -17,7 +17,7 @@ import sys
 
 import torch
 
-from . import _lib, replay_ops, rnd_ops
+from . import _lib, ppg_ops, replay_ops, rnd_ops
 from .replay_ops import _ptr
 
 __all__ = [
@@ -36,6 +36,7 @@ __all__ = [
     "rainbow_per_update", "rainbow_noisy_compose", "rainbow_noisy_grad", "rainbow_head_limits_ok", "rainbow_head_act", "rainbow_head_fwd_bwd",
     "sacd_limits_ok", "replay_add2_u8", "replay_gather2_u8", "sacd_head_act", "sacd_critic_fwd_bwd", "sacd_actor_fwd_bwd",
     "rnd_normalize", "rnd_obs_moments", "rnd_mean_var", "rnd_intrinsic_reward", "rnd_reward_filter_", "rnd_loss_fwd_bwd",
+    "ppg_aux_gather", "ppg_old_logits_", "ppg_aux_fwd_bwd", "clip_adam_split_",
 ]
 
 LOSS_SCALAR_NAMES = ("loss", "pg_loss", "v_loss", "entropy", "old_approx_kl", "approx_kl", "clipfrac")
@@ -1429,3 +1430,8 @@ replay_ops.bind(_SIDE, globals())
 from .rnd_ops import RND_FEATURES, RND_MAX_BATCH, RND_MAX_STEPS, RND_PIXELS, rnd_mean_var  # noqa: E402,F401
 
 rnd_ops.bind(_SIDE, globals())
+
+# ------------------------------------------------------------------------------------------- PPG's auxiliary phase (csrc/ppg.hip)
+from .ppg_ops import PPG_HIDDEN, PPG_MAX_ACT, PPG_MAX_ROWS, PPG_MIN_ACT  # noqa: E402,F401
+
+ppg_ops.bind(_SIDE, globals())

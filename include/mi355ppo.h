@@ -56,6 +56,9 @@ extern "C" {
                                   RND -- mi355ppo_rnd_* (newest-frame normalisation, exact observation moments, intrinsic reward, the
                                   env-axis reward filter, the distillation / intrinsic-value loss) and their *_cpu twins likewise: only
                                   added, the number stays at 2.7.1;
+                                  PPG's auxiliary phase -- mi355ppo_ppg_* (the rollout gather, the old policy's normalised logits, the three
+                                  heads with the joint loss and its backward), mi355ppo_clip_adam_split_f32 and their *_cpu twins likewise:
+                                  only added, the number stays at 2.7.1;
                                   a binding must check major AND minor (cleanrl_amd/_lib.py does) */
 
 #if defined(__GNUC__)
@@ -1472,6 +1475,62 @@ MI355PPO_API int mi355ppo_rnd_loss_fwd_bwd_f32(const float* predict, const float
 MI355PPO_API int mi355ppo_rnd_loss_fwd_bwd_f32_cpu(const float* predict, const float* target, const float* u, double update_proportion,
                                                    const float* v_int, const float* int_returns, const int64_t* mb_inds, int64_t B,
                                                    double vf_coef, float* scalars_out, float* d_predict, float* d_v_int, int M, int F);
+
+/* ---------------------------------------------------------------------------------------------
+ * Phasic Policy Gradient, the auxiliary phase (cleanrl/ppg_procgen.py:421-474; csrc/ppg.hip, row math in csrc/ppg_rows.h).  Every
+ * *_cpu twin takes host pointers and returns the device's bits.  No entry point allocates or synchronises (all are capturable); no
+ * atomics: every dot product and every sum over rows runs in one fixed order.
+ *
+ * The auxiliary buffers are aux_obs (T, R, row_bytes) u8, aux_pi (T, R, A) f32 and aux_returns (T, R) f32; a minibatch is the n whole
+ * rollouts cols (int64[n], distinct; an entry outside [0, R) is clamped), and its FLAT ROW t * n + i is (t, cols[i]) -- flatten01 over
+ * (T, n).  All offsets into the three buffers are 64-bit.  hidden must be 256 and 2 <= A <= 30 (A + 2 outputs fit one 32-output tile):
+ * anything else returns MI355PPO_EINVAL before any launch.
+ *
+ * gather: out (T * n, row_bytes) f32 = byte / 255 (correctly rounded: mi355ppo_obs_u8_to_f32's expression).  row_bytes a multiple of 4,
+ * aux_obs 4-byte and out 16-byte aligned.  One launch. */
+MI355PPO_API int mi355ppo_ppg_aux_gather_u8_f32(const unsigned char* aux_obs, const int64_t* cols, float* out, int T, int n, int64_t R,
+                                                int64_t row_bytes, void* stream);
+MI355PPO_API int mi355ppo_ppg_aux_gather_u8_f32_cpu(const unsigned char* aux_obs, const int64_t* cols, float* out, int T, int n, int64_t R,
+                                                    int64_t row_bytes);
+/* The old policy (:424-433): z = h w^T + b on h (T * n, 256), then (z - max) - log sum exp(z - max), written into aux_pi[t, cols[i], :].
+ * T * n <= 65,536.  One launch. */
+MI355PPO_API int mi355ppo_ppg_old_logits_f32(const float* h, const float* w, const float* b, const int64_t* cols, float* aux_pi, int T, int n,
+                                             int64_t R, int A, int hidden, void* stream);
+MI355PPO_API int mi355ppo_ppg_old_logits_f32_cpu(const float* h, const float* w, const float* b, const int64_t* cols, float* aux_pi, int T, int n,
+                                                 int64_t R, int A, int hidden);
+/* The auxiliary minibatch (:449-462) on the hidden rows h (M = T * n <= 65,536, 256): the actor (wa (A, 256), ba), the critic (wc (256),
+ * bc) and the auxiliary critic (wx, bx), forward and backward.  Per row: the old row is renormalised, p_old = exp(logp_old),
+ * kl_row = sum_j p_old (logp_old - logp_new) with a term inf where p_new == 0 and then 0 where p_old == 0 (torch's rules),
+ * d kl_row / d z_j = softmax(z)_j - p_old[j]; both value losses are 0.5 (v - ret)^2.
+ *   scalars_out[3] = {mean kl_row, 0.5 mean (v_aux - ret)^2, 0.5 mean (v - ret)^2}: the un-divided means the reference logs
+ *   dh (M, 256)    = the gradient of (aux_value_loss + beta_clone kl + real_value_loss) inv_accum through the actor and the auxiliary
+ *                    critic (the critic reads detached features)
+ *   dwa .. dbx     = the six head gradients of the same loss; accumulate 0 overwrites, 1 adds the folded value to what is there (one add
+ *                    per element)
+ * Rows are dealt to tiles of 8 whose partials are added in ascending tile order; the loss sums are f64.
+ * workspace: mi355ppo_ppg_aux_workspace_bytes(M, A) bytes, 16-byte aligned.  Two launches. */
+MI355PPO_API size_t mi355ppo_ppg_aux_workspace_bytes(int M, int A);
+MI355PPO_API int mi355ppo_ppg_aux_fwd_bwd_f32(const float* h, const float* wa, const float* ba, const float* wc, const float* bc, const float* wx,
+                                              const float* bx, const float* aux_pi, const float* aux_returns, const int64_t* cols, int T, int n,
+                                              int64_t R, int A, int hidden, double beta_clone, double inv_accum, float* scalars_out, float* dh,
+                                              float* dwa, float* dba, float* dwc, float* dbc, float* dwx, float* dbx, int accumulate,
+                                              void* workspace, size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_ppg_aux_fwd_bwd_f32_cpu(const float* h, const float* wa, const float* ba, const float* wc, const float* bc,
+                                                  const float* wx, const float* bx, const float* aux_pi, const float* aux_returns,
+                                                  const int64_t* cols, int T, int n, int64_t R, int A, int hidden, double beta_clone,
+                                                  double inv_accum, float* scalars_out, float* dh, float* dwa, float* dba, float* dwc, float* dbc,
+                                                  float* dwx, float* dbx, int accumulate);
+/* The auxiliary phase's optimiser step (:466-468) without a host round trip: mi355ppo_clip_adam_f32 (same norm reduction, clip
+ * coefficient and element update) with step_head's bias corrections on [0, n_split) and step_tail's on [n_split, n) -- torch.optim.Adam
+ * counts steps per parameter and the auxiliary value head only steps in this phase.  Gradients are zeroed.
+ * workspace: mi355ppo_clip_adam_workspace_bytes(n).  Two launches. */
+MI355PPO_API int mi355ppo_clip_adam_split_f32(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int64_t n_split,
+                                              double grad_scale, double max_grad_norm, double lr, double beta1, double beta2, double eps,
+                                              int64_t step_head, int64_t step_tail, float* total_norm_out, void* workspace, size_t workspace_bytes,
+                                              void* stream);
+MI355PPO_API int mi355ppo_clip_adam_split_f32_cpu(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int64_t n_split,
+                                                  double grad_scale, double max_grad_norm, double lr, double beta1, double beta2, double eps,
+                                                  int64_t step_head, int64_t step_tail, float* total_norm_out);
 
 #ifdef __cplusplus
 }
