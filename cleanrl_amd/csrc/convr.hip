@@ -17,7 +17,8 @@
 //     instructions of step v, and the loop is 2 MT + 2 NT reads per 3 MT NT matrix instructions;
 //   * requests the NEXT group's source two 16-byte loads per k-step into registers (one workgroup per CU holds the LDS), splits and stores
 //     it at the top of the next group.
-// Eight or twelve waves per CU (the instances below RGeom); which row sits in which lane is a compile-time table that keeps the 16-lane groups of a
+// Eight or twelve waves per CU (the instances below RGeom; the layer-2 forward's twelve-wave, two-image instance serves launches below MI355_RS_MIN_IMAGES = 512 images
+// since round 7 -- from there on kernel RS, convrs.hip, streams the source by stride-parity class); which row sits in which lane is a compile-time table that keeps the 16-lane groups of a
 // fragment read on 16 different bank slots (RRowTable).  What was measured on the way (each step bit-identical): profiles/
 // r05_tile_shape_experiments.txt (the s_memtime stamps of round 5's MI355PPO_R_TRACE builds: profiles/r05_kernel_r_trace.txt; the stamp code is gone since round 6).
 // Accumulator layout and epilogue are kernel Z's (lane = channel, accumulator e = row (e & 3) + 8 (e >> 2) + 4 (lane >> 5) of the tile):
@@ -457,7 +458,8 @@ static int r_launch(const RArgs& a0, hipStream_t s, const char* what) {
 
 // Which launches kernel R takes (profiles/r05_kernel_r_sizes.txt: same-box A/B at 256 .. 32,768 images): both forwards and the layer-3 data
 // gradient at every size (at or below kernel Z's time everywhere; at 32,768 images 0.72 x for the layer-3 forward, 0.90 x for the layer-2
-// forward -- its 51-KB source allows two images = 162 of 192 row slots per workgroup), the layer-2 data gradient from `min_images` = 512 on
+// forward -- its 51-KB source allows two images = 162 of 192 row slots per workgroup; conv_fwd_packed_impl hands the layer-2 forward of 512 images
+// and more to kernel RS, convrs.hip), the layer-2 data gradient from `min_images` = 512 on
 // (0.76 x at 32,768; 1.13 x at 256: one persistent workgroup per CU with two images each leaves half the chip idle there).
 // MI355PPO_CONV_R=0: never (A/B runs; the results are bit-identical either way); =min:<n>: every layer from n images on (common.h::kernel_switch).
 bool convr_on(long long images, long long min_images) { return kernel_switch("MI355PPO_CONV_R", images, min_images); }

@@ -1340,8 +1340,10 @@ static int conv_fwd_packed_impl(const char* fn, const float* src, const void* pa
     // profiles/r04_small_tiles_ab.txt).
     const bool small = !bits && images < 768;
     if (layer == 2) {
-        if (src_amax && conv_r_takes(images, 2, false))
+        if (src_amax && conv_r_takes(images, 2, false)) {      // kernel R's layer-2 forward: from MI355_RS_MIN_IMAGES images on its streamed instance, kernel RS (convrs.hip)
+            if (convrs_takes(images)) return convrs_fwd2(fn, src, (unsigned)srcb, pack, bias, dst, (unsigned)((long long)images * 81 * 64 * 4), bits, images, src_amax, dst_amax, st);
             return convr_fwd2(fn, src, (unsigned)srcb, pack, bias, dst, (unsigned)((long long)images * 81 * 64 * 4), bits, images, src_amax, dst_amax, st);
+        }
         ZArgs za = zargs(src, srcb, 0, pack, bias, nullptr, dst, (long long)images * 81 * 64 * 4, 64, (long long)images * 81, 64, ZConv2::K);
         za.bits_out = bits;
         za.a_amax = src_amax; za.c_amax = dst_amax;

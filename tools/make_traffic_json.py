@@ -16,7 +16,7 @@ IMAGES = 32768
 FETCH_CSV, WRITE_CSV = "r06_pmc_fetch.csv", "r06_pmc_write.csv"      # round 6: tools/gpu/r6_final.sh (kernels G / H on the FC layer)
 KEYS = {   # bench key -> (kernel-name substring, geometry substring) in rocpd_pmc.py's (truncated) kernel names
     "conv1_fwd": ("conv1q_fwd_kernel", ""),
-    "conv2_fwd": [("z_kernel", "ZRowsConv<20, 20, 32, 4, 4, 9, 9, 2, 0,"), ("r_kernel", "RGeom<20, 20, 0, 4, 4, 9, 9,")],
+    "conv2_fwd": [("z_kernel", "ZRowsConv<20, 20, 32, 4, 4, 9, 9, 2, 0,"), ("r_kernel", "RGeom<20, 20, 0, 4, 4, 9, 9,"), ("rs_kernel", "")],
     # (at 32,768 images kernel R runs the layer-3 forward and the layer-2 data gradient: csrc/convr.hip; one of the two names appears in a pass)
     "conv3_fwd": [("z_kernel", "ZRowsConv<9, 9, 64, 3, 3, 7, 7, 1, 0,"), ("r_kernel", "RGeom<9, 9, 0, 3, 3, 7, 7,")],
     "conv2_dgrad": [("z_kernel", "ZRowsConv<9, 9, 64, 2, 2, 10, 10, 1, -1,"), ("r_kernel", "RGeom<9, 9, 1, 2, 2, 10, 10,"), ("rb_kernel", "")],

@@ -15,7 +15,7 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = [("conv1q_fwd_kernel", "", "Q conv1 fwd"), ("z_kernel", "ZRowsConv<20, 20, 32, 4, 4, 9, 9, 2, 0,", "Z conv2 fwd"), ("r_kernel", "RGeom<20, 20, 0, 4, 4, 9, 9,", "R conv2 fwd"),
+NAMES = [("conv1q_fwd_kernel", "", "Q conv1 fwd"), ("z_kernel", "ZRowsConv<20, 20, 32, 4, 4, 9, 9, 2, 0,", "Z conv2 fwd"), ("r_kernel", "RGeom<20, 20, 0, 4, 4, 9, 9,", "R conv2 fwd"), ("rs_kernel", "", "RS conv2 fwd"),
          ("z_kernel", "ZRowsConv<9, 9, 64, 3, 3, 7, 7, 1, 0,", "Z conv3 fwd"), ("r_kernel", "RGeom<9, 9, 0, 3, 3, 7, 7,", "R conv3 fwd"), ("z_kernel", "ZRowsLinear, 2, 4, 4, 0, true", "Z FC fwd"), ("g_kernel<0>", "", "G FC fwd"), ("g_kernel<1>", "", "G FC dgrad"), ("h_kernel", "", "H FC wgrad"),
          ("z_kernel", "ZRowsLinear, 2, 4, 4, 3, false", "Z FC dgrad"), ("fcw_bf16_kernel", "", "W FC wgrad"),
          ("convw_bf16_kernel", "VGeom<9, 9, 64,", "V conv3 wgrad"), ("convu_kernel", "UGeom<9, 9, 64,", "U conv3 wgrad"), ("z_kernel", "ZRowsConv<7, 7, 64, 3, 3, 9, 9, 1, -2,", "Z conv3 dgrad"), ("r_kernel", "RGeom<7, 7, 2, 3, 3, 9, 9,", "R conv3 dgrad"),
