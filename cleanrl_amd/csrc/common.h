@@ -75,6 +75,14 @@ int convrb_dgrad2(const char* fn, const float* dz, unsigned dz_bytes, const void
 bool convrs_takes(long long images);
 int convrs_fwd2(const char* fn, const float* src, unsigned src_bytes, const void* pack, const float* bias, float* dst, unsigned dst_bytes, unsigned* bits,
                 long long images, const unsigned* src_amax, unsigned* dst_amax, hipStream_t st);
+// convrv.hip: kernel RV, the layer-3 data gradient with seven images per group and the rows dealt to tiles by vertical border class (three quarters of kernel
+// R's matrix instructions, bit-identical results); conv_dgrad_packed_impl (gemmz.hip) hands over from MI355_RV_MIN_IMAGES images on (MI355PPO_CONV_RV: 0 = never, min:<n>)
+#ifndef MI355_RV_MIN_IMAGES
+#define MI355_RV_MIN_IMAGES 4096
+#endif
+bool convrv_takes(long long images);
+int convrv_dgrad3(const char* fn, const float* dz, unsigned dz_bytes, const void* pack, const unsigned* bits, float* dsrc, unsigned dsrc_bytes,
+                  long long images, const unsigned* dz_amax, unsigned* dsrc_amax, hipStream_t st);
 // convu.hip: kernel U, the layer-3 weight gradient on the f16 split with both operands of an image group resident in LDS (-> 0 launched, 1 not applicable)
 int convu_max_parts();
 bool convu_takes(int64_t images, int layer);       // the f16x2 weight gradient of this size and layer (1, 2, 3) runs on kernel U

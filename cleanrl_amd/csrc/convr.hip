@@ -459,7 +459,8 @@ static int r_launch(const RArgs& a0, hipStream_t s, const char* what) {
 // Which launches kernel R takes (profiles/r05_kernel_r_sizes.txt: same-box A/B at 256 .. 32,768 images): both forwards and the layer-3 data
 // gradient at every size (at or below kernel Z's time everywhere; at 32,768 images 0.72 x for the layer-3 forward, 0.90 x for the layer-2
 // forward -- its 51-KB source allows two images = 162 of 192 row slots per workgroup; conv_fwd_packed_impl hands the layer-2 forward of 512 images
-// and more to kernel RS, convrs.hip), the layer-2 data gradient from `min_images` = 512 on
+// and more to kernel RS, convrs.hip, and conv_dgrad_packed_impl the layer-3 data gradient of MI355_RV_MIN_IMAGES = 4,096 images and more to kernel RV,
+// convrv.hip: seven images per group, tiles by vertical border class), the layer-2 data gradient from `min_images` = 512 on
 // (0.76 x at 32,768; 1.13 x at 256: one persistent workgroup per CU with two images each leaves half the chip idle there).
 // MI355PPO_CONV_R=0: never (A/B runs; the results are bit-identical either way); =min:<n>: every layer from n images on (common.h::kernel_switch).
 bool convr_on(long long images, long long min_images) { return kernel_switch("MI355PPO_CONV_R", images, min_images); }

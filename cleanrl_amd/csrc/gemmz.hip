@@ -1389,7 +1389,10 @@ static int conv_dgrad_packed_impl(const char* fn, const float* dz, const void* p
                   "%s: dz (%lld bytes) and dsrc (%lld bytes) must stay below 4 GiB (32-bit buffer offsets)", fn, srcb, dstb);
     hipStream_t st = as_stream(stream);
     if (layer == 3) {      // da2 (images, 9, 9, 64) = full correlation of dz3 with the flipped taps, masked by a2 > 0
-        if (dz_amax && bits && conv_r_takes(images, 3, true)) return convr_dgrad3(fn, dz, (unsigned)srcb, pack, bits, dsrc, (unsigned)dstb, images, dz_amax, dsrc_amax, st);
+        if (dz_amax && bits && conv_r_takes(images, 3, true)) {      // kernel R's layer-3 data gradient: from MI355_RV_MIN_IMAGES images on its border-class form, kernel RV (convrv.hip)
+            if (convrv_takes(images)) return convrv_dgrad3(fn, dz, (unsigned)srcb, pack, bits, dsrc, (unsigned)dstb, images, dz_amax, dsrc_amax, st);
+            return convr_dgrad3(fn, dz, (unsigned)srcb, pack, bits, dsrc, (unsigned)dstb, images, dz_amax, dsrc_amax, st);
+        }
         ZArgs za = zargs(dz, srcb, 0, pack, nullptr, act_in, dsrc, (long long)images * 81 * 64 * 4, 64, (long long)images * 81, 64, ZDgrad3::K, images);
         za.bits_in = bits;
         za.a_amax = dz_amax; za.c_amax = dsrc_amax;
