@@ -316,6 +316,19 @@ SIGNATURES = {
                                              c_int64, _P, _P, c_size_t, _P]),
     "mi355ppo_clip_adam_split_f32_cpu": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_double, c_double, c_double, c_double, c_double, c_double, c_int64,
                                                  c_int64, _P]),
+    # ppo_pettingzoo_ma_atari on the NatureCNN trunk kernels (added under ABI 2.7.1, csrc/ma_atari.hip, csrc/conv1q.hip)
+    "mi355ppo_ma_atari_split_u8": (c_int, [_P, _P, _P, _P, c_int64, _P]),
+    "mi355ppo_ma_atari_split_u8_cpu": (c_int, [_P, _P, _P, _P, c_int64]),
+    "mi355ppo_ma_atari_conv1_pack_f32": (c_int, [_P, _P, _P, _P]),
+    "mi355ppo_ma_atari_conv1_pack_f32_cpu": (c_int, [_P, _P, _P]),
+    "mi355ppo_cnn_conv1q_pack_cpu": (c_int, [_P, _P]),
+    "mi355ppo_ma_atari_conv1_fwd_bits": (c_int, [_P] * 8 + [c_int64, _P]),
+    "mi355ppo_ma_atari_conv1_fwd_amax": (c_int, [_P] * 8 + [c_int64, _P, _P]),
+    "mi355ppo_ma_atari_conv1_fwd_cpu": (c_int, [_P] * 8 + [c_int64]),
+    "mi355ppo_cnn_conv1q_fwd_cpu": (c_int, [_P] * 6 + [c_int64]),
+    "mi355ppo_ma_atari_conv1_wgrad_fold_workspace_bytes": (c_size_t, [c_int64]),
+    "mi355ppo_ma_atari_conv1_wgrad_fold_f32": (c_int, [_P] * 5 + [c_int64, _P, c_size_t, _P]),
+    "mi355ppo_ma_atari_conv1_wgrad_fold_f32_cpu": (c_int, [_P] * 5 + [c_int64]),
 }
 
 ABI_VERSION = 271       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)

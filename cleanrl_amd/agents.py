@@ -790,6 +790,19 @@ class PPGAgent(_DiscreteMixin, nn.Module):
         return Categorical(logits=self.actor(_impala_features(self, self._normalise(x))))
 
 
+MA_ATARI_BACKENDS = ("torch", "fused")
+
+
+def ma_atari_backend() -> str:
+    """``MI355PPO_MA_ATARI``: ``torch`` (the default: K5 + MIOpen convolutions + library GEMMs on the six-channel rows) or ``fused`` (the
+    NatureCNN trunk kernels on four-channel rows with the indicator planes as a per-row bias; HIP learner only); read when a learner is
+    built."""
+    v = os.environ.get("MI355PPO_MA_ATARI", "torch").strip().lower() or "torch"
+    if v not in MA_ATARI_BACKENDS:
+        raise ValueError(f"MI355PPO_MA_ATARI={v!r}: expected 'torch' or 'fused'")
+    return v
+
+
 class MAAtariAgent(_DiscreteMixin, nn.Module):
     """ppo_pettingzoo_ma_atari.py:86-118: NatureCNN on (84, 84, 6) pixel-interleaved observations -- four stacked frames plus
     two agent-indicator planes.  Only the four frame channels are divided by 255 (:104,109)."""
@@ -797,6 +810,8 @@ class MAAtariAgent(_DiscreteMixin, nn.Module):
     obs_is_image = True
     obs_layout = "hwc"
     frame_channels = 4            # channels [0, 4) are pixels; the rest pass through unscaled
+    indicator_planes = 2          # channels [4, 6): constant over an observation (supersuit's agent_indicator_v0)
+    _trunk = None                 # MI355PPO_MA_ATARI=fused: the trunk kernels' buffers (cnn.NatureTrunk), created by the learner
 
     def __init__(self, envs):
         super().__init__()
@@ -832,6 +847,41 @@ class MAAtariAgent(_DiscreteMixin, nn.Module):
         """xn: normalised (B, 6, 84, 84) -> (logits, value)."""
         hidden = self.network(xn)
         return self.actor(hidden), self.critic(hidden)
+
+    def heads_u8(self, obs_rows, inds=None, ind=None):
+        """``MI355PPO_MA_ATARI=fused``: ``obs_rows`` are the (rows, 84, 84, 4) u8 frame channels, ``ind`` (rows, 2) the two indicator bytes of
+        each row, ``inds`` optionally gathers rows.  Same function as ``heads`` on the six-channel observation whose planes 4 / 5 hold
+        ``ind`` everywhere: conv1 on kernel Q with the planes' contribution as a per-row bias, the rest as ``AtariAgent.heads_u8``."""
+        from . import cnn
+
+        if self._trunk is None:
+            self._trunk = cnn.NatureTrunk()
+        net = self.network
+        self._trunk.bufs.pack_params = (net[0].weight, net[2].weight, net[4].weight, net[7].weight)
+        feats = self._trunk(obs_rows, inds, net[0], net[2], net[4], ind=ind)
+        hidden = cnn.LinearReLUHwcFn.apply(feats, net[7].weight, net[7].bias, self._trunk.bufs)
+        if cnn.heads_supported(self.actor, self.critic):
+            return cnn.HeadsFn.apply(hidden, self.actor.weight, self.actor.bias, self.critic.weight, self.critic.bias, self._trunk.bufs)
+        return self.actor(hidden), self.critic(hidden)      # > 18 actions: library GEMMs
+
+    def act_u8(self, obs_rows, ind, seed, offset, offset_base=None, action_f32_out=None, logprob_out=None, value_out=None, want_i64=True):
+        """The fused rollout step on the four-channel rows and their indicator bytes (``AtariAgent.act_u8``); None when it does not apply."""
+        from . import cnn
+
+        if self._trunk is None:
+            self._trunk = cnn.NatureTrunk()
+        net = self.network
+        if torch.is_grad_enabled() or not cnn.heads_supported(self.actor, self.critic) or not cnn.fc_heads_act_supported_rows(obs_rows.shape[0]):
+            return None
+        self._trunk.bufs.pack_params = (net[0].weight, net[2].weight, net[4].weight, net[7].weight)
+        feats = self._trunk(obs_rows, None, net[0], net[2], net[4], ind=ind)
+        if not cnn.fc_heads_act_supported(feats):
+            return None
+        bufs = self._trunk.bufs
+        return cnn.fc_heads_act_categorical(feats, bufs.fc_pack_fwd(net[7].weight), net[7].bias.detach().contiguous(),
+                                            self.actor.weight.detach(), self.actor.bias.detach(), self.critic.weight.detach(),
+                                            self.critic.bias.detach(), seed, offset, offset_base, action_f32_out, logprob_out, value_out,
+                                            want_i64=want_i64, amax=bufs.rec_of(cnn.REC_A3, feats) if bufs.f16(feats) else None)
 
     def get_value(self, x):
         return self.critic(self.network(self._normalise(x)))

@@ -370,6 +370,90 @@ def conv1q_fwd_bits(obs_u8: torch.Tensor, pack: torch.Tensor, bias: torch.Tensor
     return out
 
 
+# ---- ppo_pettingzoo_ma_atari.py on the trunk kernels (csrc/ma_atari.hip, csrc/ma_atari_rows.h): (84, 84, 6) observations = four frame
+# channels stored as (84, 84, 4) rows + two indicator bytes per row; the constant indicator planes are a per-row bias of conv1
+MA_TAPSUM_NUMEL = 32 * 2
+
+
+def ma_split(frames6: torch.Tensor, rows4: torch.Tensor, ind: torch.Tensor, flag: torch.Tensor) -> None:
+    """Incoming (n, 84, 84, 6) u8 frames -> ``rows4`` (n, 84, 84, 4), ``ind`` (n, 2) = planes 4 / 5 at pixel (0, 0); ``flag`` (one int32
+    word) gets bit 0 OR-ed in when a plane is not constant (sticky)."""
+    n = frames6.shape[0]
+    _chk(frames6, torch.uint8, "frames6", (n, 84, 84, 6))
+    _chk(rows4, torch.uint8, "rows4", (n, 84, 84, 4))
+    _chk(ind, torch.uint8, "ind", (n, 2))
+    _chk(flag, torch.int32, "flag", (1,))
+    _launch("mi355ppo_ma_atari_split_u8", frames6.device, _ptr(frames6), _ptr(rows4), _ptr(ind), _ptr(flag), n)
+
+
+def ma_conv1_pack(W6: torch.Tensor, pack: torch.Tensor | None = None, tapsum: torch.Tensor | None = None):
+    """(32, 6, 8, 8) weight -> (kernel Q's pack of channels 0 - 3, the (32, 2) tap sums of channels 4 / 5): one launch."""
+    _chk(W6, torch.float32, "W1", (32, 6, 8, 8))
+    if pack is None:
+        pack = torch.empty(QPACK_NUMEL, dtype=torch.float32, device=W6.device)
+    if tapsum is None:
+        tapsum = torch.empty(MA_TAPSUM_NUMEL, dtype=torch.float32, device=W6.device)
+    _chk(pack, torch.float32, "Bt", (QPACK_NUMEL,))
+    _chk(tapsum, torch.float32, "tapsum", (MA_TAPSUM_NUMEL,))
+    _launch("mi355ppo_ma_atari_conv1_pack_f32", W6.device, _ptr(W6), _ptr(pack), _ptr(tapsum))
+    return pack, tapsum
+
+
+def _ma_fwd_args(obs_u8, ind, pack, tapsum, bias, inds, out, bits):
+    _chk(obs_u8, torch.uint8, "src")
+    assert tuple(obs_u8.shape[1:]) == (84, 84, 4), f"source rows must be (84,84,4) uint8, got {tuple(obs_u8.shape)}"
+    _chk(ind, torch.uint8, "ind", (obs_u8.shape[0], 2))
+    images = obs_u8.shape[0] if inds is None else inds.numel()
+    if inds is not None:
+        _chk(inds, torch.int64, "inds")
+    _chk(pack, torch.float32, "Bt", (QPACK_NUMEL,))
+    _chk(tapsum, torch.float32, "tapsum", (MA_TAPSUM_NUMEL,))
+    _chk(bias, torch.float32, "bias", (32,))
+    _chk(out, torch.float32, "out", (images, 20, 20, 32))
+    if bits is not None:
+        _chk(bits, torch.int32, "bits", (mask_words(out.numel()),))
+    return images
+
+
+def ma_conv1_fwd_amax(obs_u8, ind, pack, tapsum, bias, inds, out, bits, dst_amax) -> torch.Tensor:
+    """``conv1q_fwd_amax`` with the per-row bias ``fmaf(v5, S[n][1], fmaf(v4, S[n][0], bias[n]))``, (v4, v5) = ``ind[row]``."""
+    images = _ma_fwd_args(obs_u8, ind, pack, tapsum, bias, inds, out, bits)
+    _launch("mi355ppo_ma_atari_conv1_fwd_amax", obs_u8.device, _ptr(obs_u8), _ptr(inds), _ptr(ind), _ptr(pack), _ptr(tapsum), _ptr(bias),
+            _ptr(out), _ptr(bits), images, _rec(dst_amax, "dst_amax"))
+    return out
+
+
+def ma_conv1_fwd_bits(obs_u8, ind, pack, tapsum, bias, inds, out, bits) -> torch.Tensor:
+    """``conv1q_fwd_bits`` with the per-row bias."""
+    images = _ma_fwd_args(obs_u8, ind, pack, tapsum, bias, inds, out, bits)
+    assert bits is not None
+    _launch("mi355ppo_ma_atari_conv1_fwd_bits", obs_u8.device, _ptr(obs_u8), _ptr(inds), _ptr(ind), _ptr(pack), _ptr(tapsum), _ptr(bias),
+            _ptr(out), _ptr(bits), images)
+    return out
+
+
+def ma_conv1_wgrad_fold(dz1: torch.Tensor, ind: torch.Tensor, inds: torch.Tensor | None, dW4: torch.Tensor,
+                        out: torch.Tensor | None = None) -> torch.Tensor:
+    """The (32, 6, 8, 8) weight gradient (overwritten, like ``conv_wgrad(out=)``): channels 0 - 3 = ``dW4``, kernel P's result on the rows;
+    every tap of channel 4 + j = ``sum_i v_j(i) sum_p dz1[i][p][n]`` in one fixed order (the same input gives the same bits)."""
+    lib = _lib.load()
+    images = dz1.shape[0]
+    _chk(dz1, torch.float32, "dz", (images, 20, 20, 32))
+    _chk(ind, torch.uint8, "ind")
+    if inds is not None:
+        _chk(inds, torch.int64, "inds", (images,))
+    else:
+        assert ind.shape[0] == images
+    _chk(dW4, torch.float32, "dW4", (32, 4, 8, 8))
+    if out is None:
+        out = torch.empty((32, 6, 8, 8), dtype=torch.float32, device=dz1.device)
+    _chk(out, torch.float32, "dW", (32, 6, 8, 8))
+    ws = _workspace(dz1.device, lib.mi355ppo_ma_atari_conv1_wgrad_fold_workspace_bytes(images))
+    _launch("mi355ppo_ma_atari_conv1_wgrad_fold_f32", dz1.device, _ptr(dz1), _ptr(inds), _ptr(ind), _ptr(dW4), _ptr(out), images, _ptr(ws),
+            ws.numel())
+    return out
+
+
 def conv_fwd_packed(src: torch.Tensor, pack: torch.Tensor, bias: torch.Tensor, layer: int, out: torch.Tensor | None = None,
                     bits: torch.Tensor | None = None, amax=None) -> torch.Tensor:
     """``relu(conv(src) + bias)`` of layer 2 / 3 on kernel Z (csrc/gemmz.hip); ``pack = conv_zpack(W, layer, MODE_FWD)``.
@@ -573,15 +657,35 @@ class _Buffers:
                 buf = hit[1]
             outs.append(buf)
         W1, W2, W3, Wfc = (w.detach() for w in self.pack_params)
+        ma = W1.shape[1] == 6          # ppo_pettingzoo_ma_atari's conv1: the all-packs launch skips kernel Q's piece, ma_conv1_pack reads W1 in place
+        q_args = (None, _ptr(W2), _ptr(W3), _ptr(Wfc), None, *[_ptr(o) for o in outs[1:]]) if ma else (_ptr(W1), _ptr(W2), _ptr(W3), _ptr(Wfc), *[_ptr(o) for o in outs])
         if f16:
             if self.w_amax is None:
                 self.w_amax = new_amax(3, dev)
-            _launch("mi355ppo_nature_packs_f16x2_f32", dev, _ptr(W1), _ptr(W2), _ptr(W3), _ptr(Wfc), *[_ptr(o) for o in outs], _ptr(self.w_amax))
+            _launch("mi355ppo_nature_packs_f16x2_f32", dev, *q_args, _ptr(self.w_amax))
         else:
-            _launch("mi355ppo_nature_packs_f32", dev, _ptr(W1), _ptr(W2), _ptr(W3), _ptr(Wfc), *[_ptr(o) for o in outs])
+            _launch("mi355ppo_nature_packs_f32", dev, *q_args)
         for (k, w, _), buf in zip(keys, outs):
             self._bt[k] = ((self.weights_version, w._version, w.data_ptr()), buf)
+        if ma:
+            hit = self._bt.get("ma_tapsum")
+            _, tapsum = ma_conv1_pack(W1, outs[0], hit[1] if hit is not None else None)
+            self._bt["ma_tapsum"] = (self._bt[keys[0][0]][0], tapsum)
         return True
+
+    def ma_pack(self, W: torch.Tensor):
+        """(kernel Q's pack of channels 0 - 3, the tap sums of channels 4 / 5) of ppo_pettingzoo_ma_atari's (32, 6, 8, 8) conv1 weight, cached
+        like the other packs (re-derived into the same buffers; with the other packs stale too, behind the all-packs launch)."""
+        if not self.cache_weights:
+            return ma_conv1_pack(W.detach())
+        key = (1, MODE_FWD_Q)
+        tag = (self.weights_version, W._version, W.data_ptr())
+        hit, ts = self._bt.get(key), self._bt.get("ma_tapsum")
+        if hit is None or ts is None or hit[0] != tag or ts[0] != tag:
+            if not self._repack_all(key, W):
+                pack, tapsum = ma_conv1_pack(W.detach(), hit[1] if hit is not None else None, ts[1] if ts is not None else None)
+                self._bt[key], self._bt["ma_tapsum"] = (tag, pack), (tag, tapsum)
+        return self._bt[key][1], self._bt["ma_tapsum"][1]
 
     def fc_weight(self, W: torch.Tensor) -> torch.Tensor:
         """Linear(3136,512) weight with (h,w,c)-ordered input features, cached like the conv matrices (re-derived INTO the
@@ -685,9 +789,43 @@ class NatureTrunkFn(torch.autograd.Function):
     """a3 = relu(conv3(relu(conv2(relu(conv1(obs[inds] / 255)))))) as one autograd node; a3 is (M, 7, 7, 64)."""
 
     @staticmethod
-    def forward(ctx, obs_u8, inds, W1, b1, W2, b2, W3, b3, bufs, want_bits=False):
+    def forward(ctx, obs_u8, inds, W1, b1, W2, b2, W3, b3, bufs, want_bits=False, ind=None):
+        """``ind`` (rows, 2) u8: ppo_pettingzoo_ma_atari's indicator bytes of the rows -- W1 then is (32, 6, 8, 8), its channels 4 / 5 a bias
+        per row (csrc/ma_atari_rows.h); None for the four-channel agents."""
         m = obs_u8.shape[0] if inds is None else inds.numel()
         a1, a2, a3 = bufs.get(m, obs_u8.device, False)
+        ctx.ind = ind
+        if ind is not None:
+            if not _CONV_Z or a1.numel() * 4 >= BUF_LIMIT:
+                raise NotImplementedError("the row-bias conv1 exists on kernel Q with layers 2 / 3 on kernel Z only (MI355PPO_CONV=f / more "
+                                          "than 83,000 images are not covered)")
+            bt1, tapsum = bufs.ma_pack(W1)
+            ctx.bits = None
+            bufs.last_a3_bits = None
+            ctx.f16 = f16 = bufs.f16(obs_u8)
+            grads = _MASK_BITS and want_bits and any(ctx.needs_input_grad)
+            if f16:
+                rec = bufs.begin_pass(m, obs_u8.device)
+                mb1 = mb2 = mb3 = None
+                if grads:
+                    mb1, mb2, mb3 = ctx.bits = bufs.get_bits(m, obs_u8.device)
+                    bufs.last_a3_bits = mb3
+                ma_conv1_fwd_amax(obs_u8, ind, bt1, tapsum, b1.detach(), inds, a1, mb1, bufs.owns(REC_A1, a1))
+                conv_fwd_packed(a1, bufs.conv_zpack(W2, 2, MODE_FWD), b2.detach(), 2, a2, bits=mb2, amax=(rec[REC_A1], bufs.owns(REC_A2, a2)))
+                conv_fwd_packed(a2, bufs.conv_zpack(W3, 3, MODE_FWD), b3.detach(), 3, a3, bits=mb3, amax=(rec[REC_A2], bufs.owns(REC_A3, a3)))
+            else:
+                mb1, mb2, mb3 = bufs.get_bits(m, obs_u8.device)
+                ma_conv1_fwd_bits(obs_u8, ind, bt1, tapsum, b1.detach(), inds, a1, mb1)
+                conv_fwd_packed(a1, bufs.conv_zpack(W2, 2, MODE_FWD), b2.detach(), 2, a2, bits=mb2 if grads else None)
+                conv_fwd_packed(a2, bufs.conv_zpack(W3, 3, MODE_FWD), b3.detach(), 3, a3, bits=mb3 if grads else None)
+                if grads:
+                    ctx.bits = (mb1, mb2, mb3)
+                    bufs.last_a3_bits = mb3
+            ctx.obs, ctx.inds, ctx.acts, ctx.bufs = obs_u8, inds, (a1, a2, a3), bufs
+            ctx.params = (W1, b1, W2, b2, W3, b3)
+            bufs.last_a3_ptr = a3.data_ptr()
+            ctx.save_for_backward(W2, W3)
+            return a3
         if a1.numel() * 4 >= BUF_LIMIT:     # beyond 32-bit buffer offsets: the f32-pipe kernels with 64-bit pointers (kernel S) throughout
             conv_fwd(obs_u8, bufs.weights(W1, 1, MODE_FWD), b1.detach(), 1, inds, a1)
             conv_fwd(a1, bufs.weights(W2, 2, MODE_FWD), b2.detach(), 2, None, a2)
@@ -752,6 +890,21 @@ class NatureTrunkFn(torch.autograd.Function):
             dz3 = torch.ops.aten.threshold_backward(da3.contiguous(), a3, 0.0)    # ReLU backward of the last conv
         direct = ctx.bufs.direct_grads and all(p.grad is not None for p in ctx.params)
         gout = (lambda l: (ctx.params[2 * l - 2].grad, ctx.params[2 * l - 1].grad)) if direct else (lambda l: None)
+        none = (None,) * (10 if ctx.ind is None else 11)
+        if ctx.ind is not None:
+            # kernel P runs unchanged on the four-channel rows into a (32, 4, 8, 8) temporary (one address per trunk: captured slots replay it) and
+            # writes db1 where it belongs; the fold writes all six channels of the gradient
+            W1, key = ctx.params[0], ("ma_dw4", a3.device)
+            dW4 = ctx.bufs.by_m.get(key)
+            if dW4 is None:
+                dW4 = ctx.bufs.by_m[key] = torch.empty((32, 4, 8, 8), dtype=torch.float32, device=a3.device)
+            db1 = ctx.params[1].grad if direct else torch.empty(32, dtype=torch.float32, device=a3.device)
+
+            def wgrad1(amax):
+                conv_wgrad(ctx.obs, dz1, 1, ctx.inds, out=(dW4, db1), amax=amax)
+                return ma_conv1_wgrad_fold(dz1, ctx.ind, ctx.inds, dW4, out=W1.grad if direct else None), db1
+        else:
+            wgrad1 = lambda amax: conv_wgrad(ctx.obs, dz1, 1, ctx.inds, out=gout(1), amax=amax)
         if ctx.bufs.f16(dz3) and a1.numel() * 4 < BUF_LIMIT:      # the two-term f16 split (records: from the producers, else computed here)
             bufs, bits = ctx.bufs, ctx.bits
             r3 = bufs.rec_of(REC_DZ3, dz3)          # filled by the FC data gradient's epilogue when it produced dz3
@@ -762,10 +915,10 @@ class NatureTrunkFn(torch.autograd.Function):
             dW2, db2 = conv_wgrad(a1, dz2, 2, out=gout(2), amax=(bufs.rec_of(REC_A1, a1), r2))
             conv_dgrad_packed(dz2, bufs.conv_zpack(W2, 2, MODE_DGRAD_S2), a1, 2, dz1, bits=bits[0] if bits else None,
                               amax=(r2, bufs.owns(REC_DZ1, dz1)))
-            dW1, db1 = conv_wgrad(ctx.obs, dz1, 1, ctx.inds, out=gout(1), amax=(None, bufs.rec_of(REC_DZ1, dz1)))      # kernel P, dz in two f16 terms
+            dW1, db1 = wgrad1((None, bufs.rec_of(REC_DZ1, dz1)))      # kernel P, dz in two f16 terms
             if direct:
-                return (None,) * 10
-            return None, None, dW1, db1, dW2, db2, dW3, db3, None, None
+                return none
+            return (None, None, dW1, db1, dW2, db2, dW3, db3) + none[8:]
         dW3, db3 = conv_wgrad(a2, dz3, 3, out=gout(3))
         # (layer-3 data gradient: kernel Z multiplies the padding taps, 1.65 x the MFMAs, and still beats kernel F's nine
         # border-class launches at every size measured: profiles/r03_conv_traffic_ab_same_box.jsonl)
@@ -785,10 +938,10 @@ class NatureTrunkFn(torch.autograd.Function):
             conv_dgrad(dz2, ctx.bufs.weights(W2, 2, MODE_DGRAD_S2_CLASSES), a1, 2, dz1, variant=VARIANT_DGRAD2_CLASSES)   # no padding zeros
         else:
             conv_dgrad(dz2, ctx.bufs.weights(W2, 2, MODE_DGRAD_S2), a1, 2, dz1)
-        dW1, db1 = conv_wgrad(ctx.obs, dz1, 1, ctx.inds, out=gout(1))
+        dW1, db1 = wgrad1(None)
         if direct:
-            return (None,) * 10
-        return None, None, dW1, db1, dW2, db2, dW3, db3, None, None
+            return none
+        return (None, None, dW1, db1, dW2, db2, dW3, db3) + none[8:]
 
 
 class NatureTrunk:
@@ -798,9 +951,10 @@ class NatureTrunk:
     def __init__(self):
         self.bufs = _Buffers()
 
-    def __call__(self, obs_u8, inds, conv1, conv2, conv3):
+    def __call__(self, obs_u8, inds, conv1, conv2, conv3, ind=None):
+        extra = () if ind is None else (ind,)         # (ppo_pettingzoo_ma_atari: the rows' indicator bytes, see NatureTrunkFn.forward)
         a3 = NatureTrunkFn.apply(obs_u8, inds, conv1.weight, conv1.bias, conv2.weight, conv2.bias, conv3.weight,
-                                 conv3.bias, self.bufs, torch.is_grad_enabled())
+                                 conv3.bias, self.bufs, torch.is_grad_enabled(), *extra)
         return a3.reshape(a3.shape[0], -1)
 
 

@@ -29,6 +29,7 @@
 #include "common.h"
 #include "conv1q_pack.h"
 #include "f16split.h"
+#include "ma_atari_rows.h"
 
 #pragma clang fp contract(off)
 
@@ -42,6 +43,14 @@ __global__ __launch_bounds__(256) void conv1q_pack_kernel(const float* __restric
     conv1q_pack_body(W, pack);
 }
 
+// The pack of channels 0 - 3 of a (32, 6, 8, 8) weight read in place (ppo_pettingzoo_ma_atari.py's conv1: the same bytes as the pack of its
+// [:, :4] slice), and the tap sums of channels 4 / 5 -- S[n][j] = sum_{kh,kw} W[n][4 + j][kh][kw], 64 terms added in double in tap order,
+// rounded once -- that the row-bias instance below multiplies the two indicator bytes of an observation by.
+__global__ __launch_bounds__(256) void conv1q_pack6_kernel(const float* __restrict__ W, unsigned char* __restrict__ pack, float* __restrict__ tapsum) {
+    conv1q_pack_body<kMaInC>(W, pack);
+    if (threadIdx.x < 64) tapsum[threadIdx.x] = conv1q_tapsum(W, threadIdx.x >> 1, threadIdx.x & 1);
+}
+
 // lane `l` of w := the wave-uniform value x
 __device__ __forceinline__ int q_writelane(int w, unsigned x, int l) {
     asm("s_nop 1\n\tv_writelane_b32 %0, %1, %2" : "+v"(w) : "s"(x), "i"(l));      // (s_nop: two wait states behind the v_cmp that wrote x -- see gemmz.hip's z_writelane)
@@ -53,11 +62,15 @@ __device__ __forceinline__ int q_writelane(int w, unsigned x, int l) {
 // WPS: waves per SIMD the instance is compiled for = 4-wave workgroups per CU.  3 (168 VGPRs) at rollout sizes; 4 (128 VGPRs: 122 used, the epilogue's
 // per-channel constants read from LDS at the top of every epilogue instead of living in six registers across the matrix phase) from 4,096 images on:
 // -2.6 % at 32,768 images, +6 % at 1,024, where a fourth workgroup per CU is a fourth 32-KB digit copy for a quarter fewer tiles (profiles/r06_nt_ab.txt).
-template <int NW, bool BITS, int WPS>
+// ROWB: the bias is one per IMAGE and channel (ma_atari_rows.h): ma_rowbias of `bias`, the tap sums `tapsum` (32, 2) and the two indicator bytes
+// `ind[2 s], ind[2 s + 1]` of the image's source row s.  A tile touches at most two images, so the epilogue holds two biases per lane and picks by
+// the pixel's position in the tile; the four bytes travel with the tile's address (one scalar load per image: the aligned word that holds the pair).
+template <int NW, bool BITS, int WPS, bool ROWB = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPS, WPS))) void conv1q_fwd_kernel(const unsigned char* __restrict__ src, const int64_t* __restrict__ inds,
                                                              const unsigned char* __restrict__ pack, const float* __restrict__ bias,
                                                              float* __restrict__ dst, unsigned* __restrict__ bits, unsigned P, int ntiles, unsigned dst_bytes,
-                                                             unsigned* __restrict__ amax) {
+                                                             unsigned* __restrict__ amax, const unsigned char* __restrict__ ind = nullptr,
+                                                             const float* __restrict__ tapsum = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (wave-uniform: the tile index lives in an SGPR)
     const int li = lane & 31, lh = lane >> 5;
     // digit matrices, in operand layout, -> LDS [row][digit][lane]
@@ -73,6 +86,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPS, WP
         Cl[kQDigits][tid] = reinterpret_cast<const int*>(pack + kQScaleOff)[tid];
         Cl[kQDigits + 1][tid] = __float_as_int(bias[tid]);
     }
+    const float* sl = nullptr;
+    if constexpr (ROWB) {
+        __shared__ float Sl[2][32];                // tap sums of the two indicator channels, per output channel
+        if (tid < 64) Sl[tid & 1][tid >> 1] = tapsum[tid];
+        sl = &Sl[0][0];
+    }
     __syncthreads();
     const __amdgpu_buffer_rsrc_t rsrc_dst = __builtin_amdgcn_make_buffer_rsrc(dst, 0, (int)dst_bytes, kQRsrcWord3);
     const __amdgpu_buffer_rsrc_t rsrc_bits = __builtin_amdgcn_make_buffer_rsrc(bits, 0, BITS ? (int)(dst_bytes >> 5) : 0, kQRsrcWord3);
@@ -81,7 +100,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPS, WP
     // pointer to byte 16*lh of tap row 0 of the lane's pixel of `tile` (pixels past P read pixel 0: results dropped).
     // A 32-pixel tile touches at most two images: their rollout rows are looked up with SCALAR loads (lgkmcnt), so the
     // address of the next tile never waits behind this tile's vector stores (vmcnt).
-    auto setup = [&](int tile) -> const unsigned char* {
+    auto setup = [&](int tile, unsigned& iw) -> const unsigned char* {
         const int tu = __builtin_amdgcn_readfirstlane(tile);
         const bool live = tu < ntiles;
         const unsigned p0 = live ? (unsigned)tu * 32u : 0u;
@@ -90,6 +109,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPS, WP
         const unsigned img1 = img0 < last ? img0 + 1u : img0;
         const long long s0 = inds ? inds[img0] : (long long)img0;
         const long long s1 = inds ? inds[img1] : (long long)img1;
+        if constexpr (ROWB) {                      // (v4, v5) of img0 in the low half, of img1 in the high half
+            const uintptr_t a0 = reinterpret_cast<uintptr_t>(ind) + 2 * (uintptr_t)s0, a1 = reinterpret_cast<uintptr_t>(ind) + 2 * (uintptr_t)s1;
+            const unsigned w0 = *reinterpret_cast<const unsigned*>(a0 & ~(uintptr_t)3) >> (8 * (unsigned)(a0 & 2));
+            const unsigned w1 = *reinterpret_cast<const unsigned*>(a1 & ~(uintptr_t)3) >> (8 * (unsigned)(a1 & 2));
+            iw = (w0 & 0xffffu) | (w1 << 16);
+        }
         const unsigned p = p0 + (unsigned)li;
         const unsigned pp = (live && p < P) ? p : p0;
         const unsigned img = pp / (unsigned)kQPerImg, rem = pp - img * (unsigned)kQPerImg;
@@ -105,8 +130,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPS, WP
     int wg = blockIdx.x;
     if ((gridDim.x & 7u) == 0u) wg = (int)((blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3));
     int tile = wg * NW + wave;
-    const unsigned char* cur = setup(tile);
-    const unsigned char* nxt = setup(tile + nwv);
+    unsigned iw_cur = 0u, iw_nxt = 0u;             // ROWB: the indicator bytes of the tile in flight / of the wave's next tile
+    const unsigned char* cur = setup(tile, iw_cur);
+    const unsigned char* nxt = setup(tile + nwv, iw_nxt);
 #pragma unroll
     for (int r = 0; r < kQRows; ++r) ring[r] = *reinterpret_cast<const u32x4q*>(cur + r * kQPitch);
     // vmcnt counts loads and stores in ONE in-order queue.  A tile's ring loads are issued in FRONT of the previous tile's 17 epilogue stores, so the
@@ -149,6 +175,16 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPS, WP
         // 8 (e >> 2)) (the instruction's immediate).  Pixels past P lie past dst_bytes = 128 P: the buffer drops their stores -- which is why the tile's
         // base travels in the VECTOR offset: a buffer instruction's scalar offset is not part of its range check.
         const unsigned tl = (unsigned)__builtin_amdgcn_readfirstlane(tile) * 4096u + lanebase;
+        float rb0 = 0.0f, rb1 = 0.0f;
+        unsigned cut = 0u, span = 0u;              // pixels [cut, cut + span) of the tile belong to the tile's second image
+        if constexpr (ROWB) {
+            const float s4 = sl[li], s5 = sl[32 + li];
+            rb0 = ma_rowbias(bias_r, s4, s5, iw_cur & 255u, (iw_cur >> 8) & 255u);
+            rb1 = ma_rowbias(bias_r, s4, s5, (iw_cur >> 16) & 255u, iw_cur >> 24);
+            const unsigned p0 = (unsigned)__builtin_amdgcn_readfirstlane(tile) * 32u;
+            cut = (p0 / (unsigned)kQPerImg + 1u) * (unsigned)kQPerImg - p0;
+            span = P - p0 > cut ? P - p0 - cut : 0u;      // (pixels past P re-read the tile's first pixel: the first image's bias)
+        }
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const unsigned off = tl + (unsigned)(128 * ((e & 3) + 8 * (e >> 2)));
@@ -159,7 +195,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPS, WP
             t = __builtin_fmaf(t, 0.00390625f, (float)(acc[1][e] + acc0[1]));
             t = __builtin_fmaf(t, 0.00390625f, (float)(acc[0][e] + acc0[0]));
             float v = t * scale;
-            v = v + bias_r;
+            if constexpr (ROWB) v = v + (((unsigned)((e & 3) + 8 * (e >> 2) + 4 * lh) - cut) < span ? rb1 : rb0);
+            else v = v + bias_r;
             v = v > 0.0f ? v : 0.0f;
             vmax = __float_as_uint(v) > vmax ? __float_as_uint(v) : vmax;     // (pixels past P re-read pixel 0: real values)
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rsrc_dst, off, 0, MI355_AUX_STREAM_ST);   // dropped when out of range
@@ -172,7 +209,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPS, WP
         if constexpr (BITS)            // myoff = 128 p (or out of range): word p sits at byte 4 p
             __builtin_amdgcn_raw_buffer_store_b32((unsigned)wv, rsrc_bits, (lh == 0 && myoff != kQOob) ? myoff >> 5 : kQOob, 0, 0);
         cur = nxt;
-        nxt = setup(tile + 2 * nwv);
+        iw_cur = iw_nxt;
+        nxt = setup(tile + 2 * nwv, iw_nxt);
     }
     if (amax) amax_commit(amax, vmax, blockIdx.x * NW + wave, lane);      // (uniform; one atomic per wave of the persistent grid)
 }
@@ -198,8 +236,11 @@ extern "C" MI355PPO_API int mi355ppo_cnn_conv1q_pack(const float* W, void* pack,
 }
 
 static int conv1q_fwd_impl(const char* fn, const void* src_u8, const int64_t* inds, const void* pack, const float* bias, float* dst,
-                           unsigned* bits, int64_t images, void* stream, unsigned* amax = nullptr) {
+                           unsigned* bits, int64_t images, void* stream, unsigned* amax = nullptr, const unsigned char* ind = nullptr,
+                           const float* tapsum = nullptr) {
     MI355_REQUIRE(src_u8 && pack && bias && dst, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE((ind == nullptr) == (tapsum == nullptr) && aligned(ind, 2) && aligned(tapsum, 4), MI355PPO_EINVAL,
+                  "%s: the indicator bytes (2-byte aligned) and the tap sums come together", fn);
     MI355_REQUIRE(images > 0 && images <= (1 << 22), MI355PPO_EINVAL, "%s: images=%lld out of range (1..4194304)", fn,
                   (long long)images);
     MI355_REQUIRE(aligned(src_u8, 16) && aligned(pack, 16) && aligned(dst, 128) && aligned(inds, 8) && aligned(bias, 4) && aligned(bits, 4),
@@ -223,8 +264,16 @@ static int conv1q_fwd_impl(const char* fn, const void* src_u8, const int64_t* in
     hipLaunchKernelGGL((conv1q_fwd_kernel<NW, BITS_, WPS_>), dim3((unsigned)wgs), dim3(64 * NW), 0, as_stream(stream),                         \
                        static_cast<const unsigned char*>(src_u8), inds, static_cast<const unsigned char*>(pack), bias, dst, bits, (unsigned)P, \
                        ntiles, (unsigned)dstb, amax)
-    if (bits) { if (wps == 4) MI355_Q_LAUNCH(true, 4); else MI355_Q_LAUNCH(true, 3); }
+#define MI355_Q_LAUNCH_ROWB(BITS_, WPS_)                                                                                                       \
+    hipLaunchKernelGGL((conv1q_fwd_kernel<NW, BITS_, WPS_, true>), dim3((unsigned)wgs), dim3(64 * NW), 0, as_stream(stream),                   \
+                       static_cast<const unsigned char*>(src_u8), inds, static_cast<const unsigned char*>(pack), bias, dst, bits, (unsigned)P, \
+                       ntiles, (unsigned)dstb, amax, ind, tapsum)
+    if (ind) {
+        if (bits) { if (wps == 4) MI355_Q_LAUNCH_ROWB(true, 4); else MI355_Q_LAUNCH_ROWB(true, 3); }
+        else { if (wps == 4) MI355_Q_LAUNCH_ROWB(false, 4); else MI355_Q_LAUNCH_ROWB(false, 3); }
+    } else if (bits) { if (wps == 4) MI355_Q_LAUNCH(true, 4); else MI355_Q_LAUNCH(true, 3); }
     else { if (wps == 4) MI355_Q_LAUNCH(false, 4); else MI355_Q_LAUNCH(false, 3); }
+#undef MI355_Q_LAUNCH_ROWB
 #undef MI355_Q_LAUNCH
     return check_launch(fn);
 }
@@ -248,4 +297,32 @@ extern "C" MI355PPO_API int mi355ppo_cnn_conv1q_fwd_amax(const void* src_u8, con
     const char* fn = "mi355ppo_cnn_conv1q_fwd_amax";
     MI355_REQUIRE(dst_amax && aligned(dst_amax, 64), MI355PPO_EINVAL, "%s: amax record missing or not 64-byte aligned", fn);
     return conv1q_fwd_impl(fn, src_u8, inds, pack, bias, dst, mask_bits, images, stream, dst_amax);
+}
+
+// ppo_pettingzoo_ma_atari.py's conv1 on the stored (84, 84, 4) rows: kernel Q's pack of channels 0 - 3 of the (32, 6, 8, 8) weight and the
+// (32, 2) tap sums of channels 4 / 5 in one launch ...
+extern "C" MI355PPO_API int mi355ppo_ma_atari_conv1_pack_f32(const float* W6, void* pack, float* tapsum, void* stream) {
+    const char* fn = "mi355ppo_ma_atari_conv1_pack_f32";
+    MI355_REQUIRE(W6 && pack && tapsum, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(aligned(W6, 4) && aligned(pack, 16) && aligned(tapsum, 4), MI355PPO_EALIGN, "%s: pack must be 16-byte aligned", fn);
+    hipLaunchKernelGGL(conv1q_pack6_kernel, dim3(1), dim3(256), 0, as_stream(stream), W6, static_cast<unsigned char*>(pack), tapsum);
+    return check_launch(fn);
+}
+
+// ... and kernel Q with the per-observation bias ma_rowbias(bias, tapsum, ind[2 s], ind[2 s + 1]), s the image's source row (inds[i] or i).
+extern "C" MI355PPO_API int mi355ppo_ma_atari_conv1_fwd_bits(const void* src_u8, const int64_t* inds, const uint8_t* ind, const void* pack,
+                                                             const float* tapsum, const float* bias, float* dst, uint32_t* mask_bits,
+                                                             int64_t images, void* stream) {
+    const char* fn = "mi355ppo_ma_atari_conv1_fwd_bits";
+    MI355_REQUIRE(mask_bits && ind && tapsum, MI355PPO_EINVAL, "%s: null pointer", fn);
+    return conv1q_fwd_impl(fn, src_u8, inds, pack, bias, dst, mask_bits, images, stream, nullptr, ind, tapsum);
+}
+
+extern "C" MI355PPO_API int mi355ppo_ma_atari_conv1_fwd_amax(const void* src_u8, const int64_t* inds, const uint8_t* ind, const void* pack,
+                                                             const float* tapsum, const float* bias, float* dst, uint32_t* mask_bits,
+                                                             int64_t images, uint32_t* dst_amax, void* stream) {
+    const char* fn = "mi355ppo_ma_atari_conv1_fwd_amax";
+    MI355_REQUIRE(ind && tapsum, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(dst_amax && aligned(dst_amax, 64), MI355PPO_EINVAL, "%s: amax record missing or not 64-byte aligned", fn);
+    return conv1q_fwd_impl(fn, src_u8, inds, pack, bias, dst, mask_bits, images, stream, dst_amax, ind, tapsum);
 }

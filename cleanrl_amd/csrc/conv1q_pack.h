@@ -14,7 +14,9 @@ constexpr int kQH = 84, kQW = 84, kQC = 4, kQG = 20, kQPitch = kQW * kQC, kQPerI
 constexpr unsigned kQOob = 0xFFFFF000u;
 constexpr int kQRsrcWord3 = 0x00020000;
 
-// One workgroup: W (32,4,8,8) f32 as torch stores it -> the pack.
+// One workgroup: W (32,4,8,8) f32 as torch stores it -> the pack.  CS: channels of the weight tensor W is read from -- its first four enter
+// the pack (CS = 6: conv1 of ppo_pettingzoo_ma_atari.py read in place; the bytes are those of the contiguous [:, :4] slice).
+template <int CS = kQC>
 __device__ __forceinline__ void conv1q_pack_body(const float* __restrict__ W, unsigned char* __restrict__ pack) {
     __shared__ int s_E[32];
     __shared__ float s_max[32][8];
@@ -23,7 +25,7 @@ __device__ __forceinline__ void conv1q_pack_body(const float* __restrict__ W, un
     {   // per-channel largest magnitude: thread (n, r) scans its 32 weights, 8 partial maxima per channel
         const int n = tid >> 3, r = tid & 7;
         float m = 0.0f;
-        for (int e32 = 0; e32 < 32; ++e32) m = fmaxf(m, fabsf(W[((n * kQC + (e32 & 3)) * 8 + r) * 8 + (e32 >> 2)]));
+        for (int e32 = 0; e32 < 32; ++e32) m = fmaxf(m, fabsf(W[((n * CS + (e32 & 3)) * 8 + r) * 8 + (e32 >> 2)]));
         s_max[n][r] = m;
     }
     __syncthreads();
@@ -43,7 +45,7 @@ __device__ __forceinline__ void conv1q_pack_body(const float* __restrict__ W, un
     int sums[kQDigits] = {0, 0, 0, 0};
     for (int e32 = 0; e32 < 32; ++e32) {         // byte e32 of the pixel's tap row: column kw = e32 / 4, channel c = e32 % 4
         const int kw = e32 >> 2, c = e32 & 3;
-        const float w = W[((n * kQC + c) * 8 + r) * 8 + kw];
+        const float w = W[((n * CS + c) * 8 + r) * 8 + kw];
         long long q = llrint(ldexp((double)w, 30 - E));
         int dig[kQDigits];
         for (int d = kQDigits - 1; d >= 0; --d) {
@@ -66,6 +68,13 @@ __device__ __forceinline__ void conv1q_pack_body(const float* __restrict__ W, un
         reinterpret_cast<int*>(pack + kQAccOff)[d * 32 + nn] = 128 * s;
     }
     if (tid < 32) reinterpret_cast<float*>(pack + kQScaleOff)[tid] = (float)(ldexp(1.0, s_E[tid] - 6) / 255.0);
+}
+
+// S[n][j] of a (32, 6, 8, 8) weight: the 64 taps of channel 4 + j added in double in (kh, kw) order, rounded once
+MI355_HD float conv1q_tapsum(const float* W6, int n, int j) {
+    double s = 0.0;
+    for (int t = 0; t < 64; ++t) s = s + (double)W6[(n * 6 + 4 + j) * 64 + t];
+    return (float)s;
 }
 
 }  // namespace mi355ppo

@@ -176,7 +176,15 @@ class PPOLearner:
         self.nhwc = self.image and self.hip
         # NatureCNN convolutions on the f32-MFMA kernels (cnn.py); MI355PPO_CNN=miopen keeps torch's Conv2d (MIOpen)
         # behind the K5 gather+convert kernel -- same results within f32 round-off, used for A/B timing.
-        self.fused_cnn = (self.nhwc and hasattr(agent, "heads_u8") and tuple(obs_space.shape) == (4, 84, 84)
+        # MI355PPO_MA_ATARI=fused (HIP learner only, default torch): ppo_pettingzoo_ma_atari's (84, 84, 6) observations are stored as
+        # (84, 84, 4) rows + two indicator bytes per row and take the trunk kernels, the constant indicator planes as a per-row bias of conv1
+        self.ma_fused = False
+        if self.image and getattr(agent, "indicator_planes", 0):
+            from .agents import ma_atari_backend
+
+            self.ma_fused = (ma_atari_backend() == "fused" and self.hip and tuple(obs_space.shape) == (84, 84, 6)
+                             and os.environ.get("MI355PPO_CNN", "mfma") != "miopen")
+        self.fused_cnn = (self.nhwc and hasattr(agent, "heads_u8") and (tuple(obs_space.shape) == (4, 84, 84) or self.ma_fused)
                           and os.environ.get("MI355PPO_CNN", "mfma") != "miopen")
         self.frame_shape = self.obs_shape                                   # what the env delivers: (C,H,W) ...
         # ... unless the agent declares pixel-interleaved frames (procgen's "bhwc", ppo_procgen.py:147): then the frames
@@ -188,7 +196,13 @@ class PPOLearner:
                 self.obs_shape = (h, w, c)                                  # how rollout rows are laid out
             os.environ.setdefault("PYTORCH_MIOPEN_SUGGEST_NHWC", "1")
         self.relayout = self.nhwc and not self.hwc_frames
-        self.partial_scale = self.image and hasattr(agent, "scale_frames_")
+        self.partial_scale = self.image and hasattr(agent, "scale_frames_") and not self.ma_fused
+        self.ind = self.boot_ind = self._ma_flag = None
+        if self.ma_fused:
+            self.obs_shape = (84, 84, 4)                                    # the frame channels; frame_shape stays what the env delivers
+            self.ind = torch.zeros((T, N, 2), dtype=torch.uint8, device=device)      # planes 4 / 5 of every stored row
+            self.boot_ind = torch.zeros((N, 2), dtype=torch.uint8, device=device)
+            self._ma_flag = torch.zeros(1, dtype=torch.int32, device=device)         # sticky: set by a store that saw a non-constant plane
         self.obs = torch.zeros((T, N) + self.obs_shape, dtype=obs_dtype, device=device)
         self.actions = torch.zeros((T, N) + self.act_shape, device=device)
         self.logprobs = torch.zeros((T, N), device=device)
@@ -207,7 +221,7 @@ class PPOLearner:
             self._stage_free = torch.cuda.Event()    # compute stream: the staging / rollout buffers may be overwritten by the copy stream
             self._pin_obs = torch.zeros((N,) + self.frame_shape, dtype=obs_dtype).pin_memory()
             # device staging for incoming channel-planar frames (H2D target / device-env output)
-            self.stage_obs = torch.zeros((N,) + self.frame_shape, dtype=obs_dtype, device=device) if self.relayout else None
+            self.stage_obs = torch.zeros((N,) + self.frame_shape, dtype=obs_dtype, device=device) if (self.relayout or self.ma_fused) else None
             self._pin_rd = torch.zeros((2, N), dtype=torch.float32).pin_memory()
             self._pin_obs_np, self._pin_rd_np = self._pin_obs.numpy(), self._pin_rd.numpy()   # views of the pinned buffers
             self._x_roll = torch.empty((N,) + self.obs_shape, device=device) if (self.image and not self.fused_cnn) else None
@@ -287,7 +301,9 @@ class PPOLearner:
         and are re-laid out to the buffer's (H,W,C) rows by the uint8 relayout kernel."""
         obs_dst, done_dst = self._slot(step)
         if isinstance(next_obs, torch.Tensor):
-            if self.relayout:
+            if self.ma_fused:
+                self._ma_store(next_obs, step)
+            elif self.relayout:
                 self.ops.obs_nchw_to_nhwc_u8(next_obs, obs_dst)
             elif next_obs.data_ptr() != obs_dst.data_ptr():
                 obs_dst.copy_(next_obs)
@@ -301,7 +317,7 @@ class PPOLearner:
         self._h2d_evt.synchronize()                    # the pinned staging buffers are free again
         np.copyto(self._pin_obs_np, next_obs, casting="unsafe")      # one host memcpy straight into pinned memory
         np.copyto(self._pin_rd_np[0], next_done, casting="unsafe")
-        h2d_dst = self.stage_obs if self.relayout else obs_dst
+        h2d_dst = self.stage_obs if (self.relayout or self.ma_fused) else obs_dst
         # the copy stream must not overtake the compute stream's last use of its target: the zero fill at construction, the
         # relayout kernel of the previous step
         self._h2d.wait_event(self._stage_free)
@@ -310,25 +326,48 @@ class PPOLearner:
             done_dst.copy_(self._pin_rd[0], non_blocking=True)
             self._h2d_evt.record(self._h2d)
         torch.cuda.current_stream(self.device).wait_event(self._h2d_evt)
-        if self.relayout:
+        if self.ma_fused:
+            self._ma_store(self.stage_obs, step)
+        elif self.relayout:
             self.ops.obs_nchw_to_nhwc_u8(self.stage_obs, obs_dst)
         self._stage_free.record(torch.cuda.current_stream(self.device))
+
+    def _ma_store(self, frames6, step: int) -> None:
+        """MI355PPO_MA_ATARI=fused: (N, 84, 84, 6) u8 device frames -> the slot's (84, 84, 4) rows and indicator bytes; a plane that is not
+        constant sets the flag word on the device (read with the next update's diagnostics: no copy to the host per step)."""
+        from . import cnn
+
+        cnn.ma_split(frames6.contiguous(), self.obs[step] if step < self.T else self.boot_obs, self._ind_slot(step), self._ma_flag)
+
+    def _ind_slot(self, step: int):
+        return self.ind[step] if step < self.T else self.boot_ind
+
+    def _ma_flag_check(self, flag_host):
+        """-> the check ``PendingMetrics.result`` runs once the diagnostics (``flag_host`` among them) have arrived."""
+        def check():
+            if int(flag_host.reshape(-1)[0]) != 0:
+                raise RuntimeError("MI355PPO_MA_ATARI=fused: the agent-indicator planes (channels 4 and 5) of this environment's observations "
+                                   "are not constant over an observation, so they are not a per-observation bias of the first convolution; "
+                                   "leave MI355PPO_MA_ATARI unset for this environment")
+        return check
 
     def start_iteration(self) -> None:
         """Carry the bootstrap observation of the previous rollout into slot 0 (the reference keeps it in
         ``next_obs`` across iterations, :245-247,272)."""
         self.obs[0].copy_(self.boot_obs)
         self.dones[0].copy_(self.boot_done)
+        if self.ma_fused:
+            self.ind[0].copy_(self.boot_ind)
 
-    def _heads_rollout(self, obs_rows):
-        """Policy/value heads on one slot of the rollout buffer (HIP path)."""
+    def _heads_rollout(self, obs_rows, ind=None):
+        """Policy/value heads on one slot of the rollout buffer (HIP path); ``ind``: the slot's indicator bytes (MI355PPO_MA_ATARI=fused)."""
         if self.image and self.fused_cnn:
             if self.agent._trunk is None:
                 from . import cnn
 
                 self.agent._trunk = cnn.NatureTrunk()
             self._own_trunk_buffers()
-            return self.agent.heads_u8(obs_rows)
+            return self.agent.heads_u8(obs_rows, None, ind) if self.ma_fused else self.agent.heads_u8(obs_rows)
         return self.agent.heads(self._features(obs_rows))
 
     def _own_trunk_buffers(self) -> None:
@@ -356,7 +395,11 @@ class PPOLearner:
             self.agent._trunk = cnn.NatureTrunk()
         bufs, net = self.agent._trunk.bufs, self.agent.network
         self._own_trunk_buffers()
-        bufs.weights(net[0].weight, 1, cnn.MODE_FWD_Q)
+        if self.ma_fused:
+            bufs.pack_params = (net[0].weight, net[2].weight, net[4].weight, net[7].weight)
+            bufs.ma_pack(net[0].weight)
+        else:
+            bufs.weights(net[0].weight, 1, cnn.MODE_FWD_Q)
         bufs.weights(net[2].weight, 2, cnn.MODE_FWD)
         bufs.weights(net[4].weight, 3, cnn.MODE_FWD)
         cnn.warm_forward_packs(bufs, net)                # kernel Z's packs: what NatureTrunkFn / LinearReLUHwcFn.forward ask for
@@ -399,14 +442,15 @@ class PPOLearner:
                 self.agent._trunk = cnn.NatureTrunk()
             self._own_trunk_buffers()
             seed, off = (self.agent.rng.seed, self.agent.rng.offset + 1) if rng_offset is None else (self.agent.rng.seed, int(rng_offset))
-            r = self.agent.act_u8(self.obs[step][lo:hi], seed, off, rng_base, self.actions[step][lo:hi], self.logprobs[step][lo:hi],
+            ind = (self.ind[step][lo:hi],) if self.ma_fused else ()
+            r = self.agent.act_u8(self.obs[step][lo:hi], *ind, seed, off, rng_base, self.actions[step][lo:hi], self.logprobs[step][lo:hi],
                                   self.values[step][lo:hi], want_i64=rng_base is None)
             if r is not None:
                 if rng_offset is None:
                     self.agent.rng.next()
                 return r[0] if r[0] is not None else r[1]
         if self.hip:
-            p, value = self._heads_rollout(self.obs[step][lo:hi])
+            p, value = self._heads_rollout(self.obs[step][lo:hi], self.ind[step][lo:hi] if self.ma_fused else None)
             seed, off = self.agent.rng.next() if rng_offset is None else (self.agent.rng.seed, int(rng_offset))
             if self.discrete:
                 a64, _, _, _ = self.ops.categorical_sample(p.contiguous(), seed=seed, offset=off, offset_base=rng_base,
@@ -517,7 +561,7 @@ class PPOLearner:
             if self.mlp is not None:
                 next_value = self.ops.mlp_forward(self.boot_obs, *self.mlp)[1]
             else:
-                _, next_value = self._heads_rollout(self.boot_obs)
+                _, next_value = self._heads_rollout(self.boot_obs, self.boot_ind)
             self.ops.gae(self.rewards, self.dones, self.values, self.boot_done, next_value.reshape(-1).contiguous(),
                          a.gamma, a.gae_lambda, self.advantages, self.returns)
         else:
@@ -624,8 +668,9 @@ class PPOLearner:
             # :382-384 and the logged scalars: async D2H into pinned memory (the caching host allocator keeps a block out of
             # reuse until the copy that used it has executed), one event behind them
             on_gpu = b_values.is_cuda              # (the HIP branches also run on CPU tensors under the tests' stand-in ops)
-            host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=on_gpu) for t in (b_values, b_returns, self._scalars[:k])]
-            for h, t in zip(host, (b_values, b_returns, self._scalars[:k])):
+            diag = (b_values, b_returns, self._scalars[:k]) + ((self._ma_flag,) if self.ma_fused else ())
+            host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=on_gpu) for t in diag]
+            for h, t in zip(host, diag):
                 h.copy_(t, non_blocking=True)
             ev = None
             if on_gpu:
@@ -634,6 +679,9 @@ class PPOLearner:
             pm = PendingMetrics(ev, host[0], host[1], host[2], None, k)
             if self._peer is not None:
                 pm.after_sync = self._peer.check
+            if self.ma_fused:                       # the store-time flag of this iteration's observations travels with the diagnostics
+                peer_check, flag_check = pm.after_sync, self._ma_flag_check(host[3])
+                pm.after_sync = flag_check if peer_check is None else (lambda: (peer_check(), flag_check()))
             return pm
         pm = PendingMetrics(None, b_values, b_returns, None, (last, clipfracs), k)
         pm.result()                     # CPU path: resolved at once (the handle holds views of buffers the next rollout overwrites)
@@ -1006,7 +1054,10 @@ class PPOLearner:
                                 logstd_grad=None if ls is None else ls.grad, mean_shift=shift)
             return
         if self.image and self.fused_cnn:
-            p, value = self.agent.heads_u8(b_obs, idx)                    # :320 gather + /255 fused into conv1
+            if self.ma_fused:
+                p, value = self.agent.heads_u8(b_obs, idx, self.ind.reshape(-1, 2))
+            else:
+                p, value = self.agent.heads_u8(b_obs, idx)                # :320 gather + /255 fused into conv1
         else:
             if self.image:
                 if self._x_mb is None or self._x_mb.shape[0] != idx.numel():

@@ -60,6 +60,8 @@ class _Lane:
         L = self.L = learner
         self.g, self.lo, self.hi, self.n = g, lo, hi, hi - lo
         self.hip = L.hip
+        if getattr(L, "ma_fused", False):       # the lanes store rows themselves; the store-time split of that backend lives in PPOLearner.observe
+            raise NotImplementedError("MI355PPO_MA_ATARI=fused does not cover env groups (--env-groups): leave one of the two unset")
         self.delta = bool(frame_delta and L.hip and L.relayout and tuple(L.frame_shape) == (4, 84, 84))
         if not self.hip:
             return

@@ -1532,6 +1532,49 @@ MI355PPO_API int mi355ppo_clip_adam_split_f32_cpu(float* params, float* grads, f
                                                   double grad_scale, double max_grad_norm, double lr, double beta1, double beta2, double eps,
                                                   int64_t step_head, int64_t step_tail, float* total_norm_out);
 
+/* ---- ppo_pettingzoo_ma_atari.py on the NatureCNN trunk kernels (added under ABI 2.7.1; csrc/ma_atari.hip, csrc/conv1q.hip) -------------
+ * The script's observations are (84, 84, 6) u8, pixel-interleaved: four stacked frames and two agent-indicator planes that are constant
+ * over an observation and are NOT divided by 255 (:104).  A constant plane of value v adds v * sum_taps W1[n][c] to every output pixel of
+ * conv1's channel n -- a bias per observation -- and its weight gradient is one number for all 64 taps.  So the rollout keeps the four
+ * frame channels as (84, 84, 4) rows (what kernels Q and P read) and two indicator bytes per row.
+ *
+ * split: `frames` incoming (84, 84, 6) frames -> rows4 (frames, 84, 84, 4) and ind (frames, 2) = planes 4 / 5 at pixel (0, 0).  *flag gets
+ * bit 0 OR-ed in when any byte of plane 4 / 5 differs from that plane's pixel (0, 0); it is never cleared here.  frames6 8-byte, rows4
+ * 16-byte aligned.  One launch. */
+MI355PPO_API int mi355ppo_ma_atari_split_u8(const uint8_t* frames6, uint8_t* rows4, uint8_t* ind, uint32_t* flag, int64_t frames, void* stream);
+MI355PPO_API int mi355ppo_ma_atari_split_u8_cpu(const uint8_t* frames6, uint8_t* rows4, uint8_t* ind, uint32_t* flag, int64_t frames);
+/* pack: W6 (32, 6, 8, 8) read in place -> kernel Q's pack of its channels 0 - 3 (mi355ppo_cnn_conv1q_pack_bytes(); the bytes of
+ * mi355ppo_cnn_conv1q_pack on the contiguous [:, :4] slice) and tapsum (32, 2): S[n][j] = sum_{kh,kw} W6[n][4 + j][kh][kw], added in
+ * double in tap order, rounded once.  One launch.  mi355ppo_cnn_conv1q_pack_cpu: the twin of mi355ppo_cnn_conv1q_pack. */
+MI355PPO_API int mi355ppo_ma_atari_conv1_pack_f32(const float* W6, void* pack, float* tapsum, void* stream);
+MI355PPO_API int mi355ppo_ma_atari_conv1_pack_f32_cpu(const float* W6, void* pack, float* tapsum);
+MI355PPO_API int mi355ppo_cnn_conv1q_pack_cpu(const float* W, void* pack);
+/* forward: mi355ppo_cnn_conv1q_fwd_bits / _amax on the (84, 84, 4) rows with the bias of image i and channel n
+ *   fmaf(v5, S[n][1], fmaf(v4, S[n][0], bias[n])),  (v4, v5) = ind[2 s], ind[2 s + 1] as f32,  s = inds ? inds[i] : i
+ * (all indicator bytes 0: the bits of the plain entry points).  ind: 2-byte aligned.  The twin serves both forms (mask_bits may be null;
+ * it keeps no amax record); mi355ppo_cnn_conv1q_fwd_cpu is the twin of the plain kernel Q forward. */
+MI355PPO_API int mi355ppo_ma_atari_conv1_fwd_bits(const void* src_u8, const int64_t* inds, const uint8_t* ind, const void* pack,
+                                                  const float* tapsum, const float* bias, float* dst, uint32_t* mask_bits, int64_t images,
+                                                  void* stream);
+MI355PPO_API int mi355ppo_ma_atari_conv1_fwd_amax(const void* src_u8, const int64_t* inds, const uint8_t* ind, const void* pack,
+                                                  const float* tapsum, const float* bias, float* dst, uint32_t* mask_bits, int64_t images,
+                                                  uint32_t* dst_amax, void* stream);
+MI355PPO_API int mi355ppo_ma_atari_conv1_fwd_cpu(const void* src_u8, const int64_t* inds, const uint8_t* ind, const void* pack,
+                                                 const float* tapsum, const float* bias, float* dst, uint32_t* mask_bits, int64_t images);
+MI355PPO_API int mi355ppo_cnn_conv1q_fwd_cpu(const void* src_u8, const int64_t* inds, const void* pack, const float* bias, float* dst,
+                                             uint32_t* mask_bits, int64_t images);
+/* weight-gradient fold: dW6 (32, 6, 8, 8) is OVERWRITTEN: channels 0 - 3 = dW4 (32, 4, 8, 8), the layer-1 weight gradient of the rows
+ * (mi355ppo_cnn_conv1_wgrad_f16x2 / mi355ppo_cnn_conv_wgrad_f32), every tap of channel 4 + j of output channel n =
+ *   sum_i v_j(i) * sum_p dz1[i][p][n]
+ * over dz1 (images, 20, 20, 32), accumulated in double in one fixed order (four images per partial, the partials in four interleaved
+ * chains; no floating-point atomics: the same input gives the same bits; the twin follows the same order).
+ * workspace: mi355ppo_ma_atari_conv1_wgrad_fold_workspace_bytes(images) bytes, 8-byte aligned.  Two launches. */
+MI355PPO_API size_t mi355ppo_ma_atari_conv1_wgrad_fold_workspace_bytes(int64_t images);
+MI355PPO_API int mi355ppo_ma_atari_conv1_wgrad_fold_f32(const float* dz1, const int64_t* inds, const uint8_t* ind, const float* dW4, float* dW6,
+                                                        int64_t images, void* workspace, size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_ma_atari_conv1_wgrad_fold_f32_cpu(const float* dz1, const int64_t* inds, const uint8_t* ind, const float* dW4,
+                                                            float* dW6, int64_t images);
+
 #ifdef __cplusplus
 }
 #endif
