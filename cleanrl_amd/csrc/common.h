@@ -53,14 +53,10 @@ int convr_dgrad3(const char* fn, const float* dz, unsigned dz_bytes, const void*
                  long long images, const unsigned* dz_amax, unsigned* dsrc_amax, hipStream_t st);
 int convr_dgrad2(const char* fn, const float* dz, unsigned dz_bytes, const void* pack, const unsigned* bits, float* dsrc, unsigned dsrc_bytes,
                  long long images, const unsigned* dz_amax, unsigned* dsrc_amax, hipStream_t st);
-// Kernels R / RB: the weights' LDS ring filled by LDS-DMA (buffer_load_dwordx4 ... lds, one slot ahead, hand-counted vmcnt waits) instead of global -> registers ->
-// ds_write (two slots ahead): bit-identical, layer-3 forward / data gradient -5 %, layer-2 launches -1.5 % at 32,768 images (profiles/r06_ring_dma_ab.txt).
-// -DMI355_RING_DMA=0 (tools/build_variant.py) builds the register ring for A/Bs.
-#ifndef MI355_RING_DMA
-#define MI355_RING_DMA 1
-#endif
+// (The family's shared device layer and launcher: conv_resident.h.  The weights' LDS ring is filled by LDS-DMA -- buffer_load_dwordx4 ... lds, one slot ahead,
+// counted vmcnt waits; the A/B against round 5's register ring -- global -> registers -> ds_write, two slots ahead --, which is gone: profiles/r06_ring_dma_ab.txt.)
 // convrb.hip: kernel RB, the layer-2 data gradient with a group's rows dealt to tiles by border class (three images per group, two thirds of
-// kernel R's matrix instructions, bit-identical results); convr_dgrad2 hands over from MI355_RB_MIN_IMAGES images on
+// kernel R's matrix instructions, bit-identical results); conv_dgrad_packed_impl (gemmz.hip) hands over from MI355_RB_MIN_IMAGES images on (MI355PPO_CONV_RB: 0 = never, min:<n>)
 #ifndef MI355_RB_MIN_IMAGES
 #define MI355_RB_MIN_IMAGES 3072
 #endif
@@ -124,6 +120,16 @@ inline bool kernel_switch(const char* name, long long size, long long default_mi
     if (e[0] == '0' && !e[1]) return false;
     if (e[0] == 'm' && e[1] == 'i' && e[2] == 'n' && e[3] == ':') return size >= atoll(e + 4);
     return size >= default_min;
+}
+
+// The CU count of the CURRENT device, asked at every call: an attribute query, no synchronisation -- the library keeps no per-process state.
+inline int cu_count() {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
+        (void)hipGetLastError();
+        n = 256;
+    }
+    return n;
 }
 
 inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }

@@ -4,11 +4,7 @@
 // conflict-free 16-lane sets, the k-step orders are permutations, (window origin) + (tap) is additive in the record index, LDS budgets).
 #pragma once
 
-#if defined(__HIPCC__)
-#define R_GEOM_FN __device__ __forceinline__ constexpr
-#else
-#define R_GEOM_FN inline constexpr
-#endif
+#include "conv_resident_geom.h"
 
 namespace mi355ppo {
 
@@ -52,16 +48,14 @@ using RConv3 = RGeom<9, 9, 0, 3, 3, 7, 7, 2, 5, 8, 1, 1, 6, 1>;          // a2 (
 using RDgrad3 = RGeom<7, 7, 2, 3, 3, 9, 9, 2, 3, 8, 1, 0, 6, 1>;         // dz3 (7, 7, 64) -> da2 (9, 9, 64): 243 rows of 256
 using RDgrad2 = RGeom<9, 9, 1, 2, 2, 10, 10, 4, 2, 8, 2, 0, 4, 1, 2>;       // dz2 (9, 9, 64) -> da1 (20, 20, 32), four stride-parity classes = four column tiles: 200 rows of 256
 
-// Which row of the group sits in which lane.  A fragment read (ds_read_b128, lane = row) is served in groups of 16 lanes -- {0-3, 12-15,
-// 20-27} and {4-11, 16-19, 28-31} of each wave half -- and is conflict-free when the 16 records start in 16 different sixteen-byte slots of
+// Which row of the group sits in which lane.  A fragment read (ds_read_b128, lane = row) is served in sets of 16 lanes (ResRowSets)
+// and is conflict-free when the 16 records start in 16 different sixteen-byte slots of
 // the 256-byte bank row, i.e. (record pitch = 17 slots) when the 16 window origins differ mod 16.  Raster order does not give that (a
 // line of 7 or 9 outputs, then a jump); any order of the rows is as good as any other for everything else, so the table deals the rows
 // to the 16-lane sets by the residue of their window origin: set s never gets a residue twice while another set can still take it.
-// Slot = (wave MT + tile) 32 + lane % 32.  `row`: the group's row in the slot, -1 = none; `src`: the row a slot computes -- its own, or
-// (empty slots) a row of the SAME sixteen-lane set: the same address as that lane's, a broadcast, where row 0 would be one more record on
-// some bank; an empty slot computes and stores that row's values a second time.
+// Slot = (wave MT + tile) 32 + lane % 32.  `row`: the group's row in the slot, -1 = none; `src`: the row a slot computes (ResRowSets::fill_empty).
 template <class RG>
-struct RRowTable {
+struct RRowTable : ResRowSets {
     short row[RG::SLOTS], src[RG::SLOTS];
     constexpr RRowTable() : row{}, src{} {
         constexpr int NSET = RG::SLOTS / 16;
@@ -70,10 +64,8 @@ struct RRowTable {
         int slot_of[NSET][16] = {};                        // k-th lane (0..15) of set s -> slot
         for (int s = 0; s < NSET; ++s) {
             int k = 0;
-            for (int l = 0; l < 32; ++l) {
-                const bool first = l < 4 || (l >= 12 && l < 16) || (l >= 20 && l < 28);
-                if (first == ((s & 1) == 0)) slot_of[s][k++] = (s >> 1) * 32 + l;
-            }
+            for (int l = 0; l < 32; ++l)
+                if (first_set(l) == ((s & 1) == 0)) slot_of[s][k++] = (s >> 1) * 32 + l;
         }
         for (int i = 0; i < RG::SLOTS; ++i) row[i] = -1;
         int next = 0;
@@ -93,18 +85,13 @@ struct RRowTable {
                     }
                 }
             }
-        for (int s = 0; s < NSET; ++s) {
-            int have = 0;                                   // (a set without any row: all sixteen lanes on row 0, one address)
-            for (int k = 0; k < 16; ++k)
-                if (row[slot_of[s][k]] >= 0) { have = row[slot_of[s][k]]; break; }
-            for (int k = 0; k < 16; ++k) src[slot_of[s][k]] = row[slot_of[s][k]] >= 0 ? row[slot_of[s][k]] : (short)have;
-        }
+        fill_empty(row, src);
     }
 };
 
 // visited index v -> (k-step of the pack, byte offset of the step's hi fragment from the lane's window origin)
 template <class RG>
-R_GEOM_FN int r_kstep(int v) {
+RES_GEOM_FN int r_kstep(int v) {
     if constexpr (RG::ORDER == 1) {                       // kernel Z's phase order of the 3 x 3 / 64-channel forward (z_kstep)
         const int lp = v >= 18 ? 1 : 0, w = v - 18 * lp, combo = w >> 1;
         const int ty = combo / 3, tx = combo - 3 * ty;
@@ -118,7 +105,7 @@ R_GEOM_FN int r_kstep(int v) {
     }
 }
 template <class RG>
-R_GEOM_FN int r_tapoff(int ks) {
+RES_GEOM_FN int r_tapoff(int ks) {
     const int ty = ks / RG::SPR, us = ks - ty * RG::SPR, tx = us / RG::C16, chunk = us - tx * RG::C16;
     return RG::pidx(ty, tx) * RG::PIX + chunk * 32;
 }

@@ -17,11 +17,7 @@
 // -- four tiles x one column tile x three products = the 12 matrix instructions per k-step kernel R issues, every wave, every step.
 #pragma once
 
-#if defined(__HIPCC__)
-#define RB_GEOM_FN __device__ __forceinline__ constexpr
-#else
-#define RB_GEOM_FN inline constexpr
-#endif
+#include "conv_resident_geom.h"
 
 namespace mi355ppo {
 
@@ -49,21 +45,19 @@ struct RBGeom {
 static_assert(RBGeom::pidx(RBGeom::IH + 1, RBGeom::IW + 1) < RBGeom::IPIX && RBGeom::LDSB <= 160 * 1024 && (RBGeom::PIX / 16) % 2 == 1 && RBGeom::ROWS <= RBGeom::SLOTS,
               "records, LDS, odd pitch, row slots");
 
-RB_GEOM_FN int rb_tapoff(int ks) {                         // byte offset of k-step ks' hi fragment from the lane's window origin
+RES_GEOM_FN int rb_tapoff(int ks) {                         // byte offset of k-step ks' hi fragment from the lane's window origin
     const int ty = ks / RBGeom::SPR, us = ks - ty * RBGeom::SPR, tx = us / RBGeom::C16, chunk = us - tx * RBGeom::C16;
     return RBGeom::pidx(ty, tx) * RBGeom::PIX + chunk * 32;
 }
 
 // Which row of the group sits in which lane: slot (row-wave MT + tile) 32 + lane % 32 -> row id = image 100 + gy 10 + gx (`row`: -1 = an empty
-// slot; `src`: the row the slot computes -- its own, or for an empty slot a row of the same sixteen-lane set, i.e. the same LDS address: a
-// broadcast; its values are stored a second time).  A fragment read (ds_read_b128, lane = row) is served in sets of 16 lanes and is
+// slot; `src`: the row the slot computes, ResRowSets::fill_empty).  A fragment read (ds_read_b128, lane = row) is served in sets of 16 lanes and is
 // conflict-free when the 16 window origins differ mod 16 (record pitch 17 slots).  Interior rows: the residue of image 117 + 10 gy + gx over
 // gy, gx in 1 .. 8 takes every value 12 times per group = once per set of the six interior tiles: the k-th row of a residue goes to set k.
 // Rim tiles: 27 rows in two sets; a residue occurs at most twice in the line tiles (conflict-free) and three times for two residues of
 // each column tile (two two-way conflicts per column tile: 4 extra LDS cycles per 40 fragment reads of a rim tile).
-struct RBRowTable {
+struct RBRowTable : ResRowSets {
     short row[RBGeom::SLOTS], src[RBGeom::SLOTS];
-    static constexpr bool first_set(int l) { return l < 4 || (l >= 12 && l < 16) || (l >= 20 && l < 28); }
     static constexpr int residue(int gi, int gy, int gx) { return (gi * RBGeom::IPIX + RBGeom::pidx(gy, gx)) & 15; }
     constexpr RBRowTable() : row{}, src{} {
         using RG = RBGeom;
@@ -109,17 +103,7 @@ struct RBRowTable {
                             }
                     }
         }
-        // ---- empty slots compute a row of their own set
-        for (int t = 0; t < RG::SLOTS / 32; ++t)
-            for (int h = 0; h < 2; ++h) {
-                int have = -1;
-                for (int k = 0; k < 16; ++k)
-                    if (row[t * 32 + lane_of[h][k]] >= 0) { have = row[t * 32 + lane_of[h][k]]; break; }
-                for (int k = 0; k < 16; ++k) {
-                    const int s = t * 32 + lane_of[h][k];
-                    src[s] = row[s] >= 0 ? row[s] : (short)have;
-                }
-            }
+        fill_empty(row, src);
     }
 };
 

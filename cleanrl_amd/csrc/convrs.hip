@@ -14,32 +14,12 @@
 // Arithmetic: kernel R's, i.e. kernel Z's SPLIT = 1 instance's -- every output element sees the same k-steps in the same order, per step hi hi, hi lo,
 // lo hi into one accumulator, the same split under the same scale, the same epilogue: bit-identical output, mask words and amax record
 // (tests/test_gpu_conv2_stream.py).  Which slot a row sits in does not enter the result.
-#include "common.h"
-#include "f16split.h"
+#include "conv_resident.h"
 #include "convrs_geom.h"
 
 #pragma clang fp contract(off)
 
 namespace mi355ppo {
-
-typedef float rs_f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr unsigned kRSOob = 0xFFFFF000u;              // buffer offset out of range for every tensor < 4 GiB - 4 KiB
-constexpr int kRSRsrcWord3 = 0x00020000;              // raw buffer, 32-bit elements
-constexpr int kRSWaitVm0 = 0x0F70;                    // s_waitcnt vmcnt(0) (gfx9 encoding: expcnt 7, lgkmcnt 15 = no wait)
-
-// lane `l` of w := the wave-uniform value x (convr.hip's r_writelane: the s_nop covers the wait states a VALU read of an SGPR needs behind a VALU
-// write the compiler cannot see inside the asm)
-__device__ __forceinline__ int rs_writelane(int w, unsigned x, int l) {
-    asm("s_nop 1\n\tv_writelane_b32 %0, %1, %2" : "+v"(w) : "s"(x), "i"(l));
-    return w;
-}
-
-// one LDS-DMA piece: 16 bytes per lane from the buffer (per-lane offset `voff`, wave-uniform `soff`) to LDS at `dst` + 16 lane (buffer_load_dwordx4 ... lds).
-// (A plain function on purpose, as in convr.hip: with the builtin inside a kernel template the host pass drops the launch stubs without a diagnostic.)
-__device__ __forceinline__ void rs_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned char* dst, unsigned voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)dst, 16, voff, soff, 0, 0);
-}
 
 // one unit of a class into its record: hi half at `addr`, lo half 64 bytes on (ds_write2_b64).  In assembly on purpose: behind a compiler-visible LDS store the
 // compiler waits for every LDS-DMA piece in flight (it cannot tell the ring from the class buffers) -- the weight ring's one slot of distance would be gone.  The
@@ -127,7 +107,7 @@ __global__ __launch_bounds__(RSGeom::THREADS) __attribute__((amdgpu_waves_per_eu
         const int u = r * THREADS + tid;
         const int c4 = u % RG::UPP, j = (u / RG::UPP) % RG::CW, i = (u / (RG::UPP * RG::CW)) % RG::CH, img = u / (RG::UPP * RG::CW * RG::CH);
         const bool ok = u < RG::CUNITS;
-        usrc[r] = ok ? (unsigned)(img * RG::IMG_SRC + (2 * i * RG::IW + 2 * j) * (RG::IC * 4) + c4 * 16) : kRSOob;
+        usrc[r] = ok ? (unsigned)(img * RG::IMG_SRC + (2 * i * RG::IW + 2 * j) * (RG::IC * 4) + c4 * 16) : kResOob;
         udst[r] = ok ? (unsigned)((img * RG::IP + i * RG::RP + j) * RG::PIX + c4 * 8) : (unsigned)(RG::SPARE * RG::PIX + c4 * 8);
     }
     // a1's descriptor of a group starts AT the group: the per-unit offsets are then lane constants + an immediate; the range shrinks with the base, so units of
@@ -136,7 +116,7 @@ __global__ __launch_bounds__(RSGeom::THREADS) __attribute__((amdgpu_waves_per_eu
     auto rsrc_a_of = [&](int g) __attribute__((always_inline)) {
         const bool ok = g < a.groups;
         const unsigned gb = (unsigned)g * (unsigned)RG::GROUP_SRC;
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<unsigned char*>(const_cast<float*>(a.A)) + (ok ? gb : 0u), 0, ok ? (int)(a.a_bytes - gb) : 0, kRSRsrcWord3);
+        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<unsigned char*>(const_cast<float*>(a.A)) + (ok ? gb : 0u), 0, ok ? (int)(a.a_bytes - gb) : 0, kResRsrcWord3);
     };
     const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds;      // LDS byte address of class buffer 0
     static_assert(RG::LO == 64, "rs_put16: the lo half one ds_write2_b64 stride (8 x 8 bytes) behind the hi half");
@@ -154,9 +134,9 @@ __global__ __launch_bounds__(RSGeom::THREADS) __attribute__((amdgpu_waves_per_eu
     // C's descriptor of a group starts AT the group: the per-value offsets are lane constants + an immediate, and rows of images past the batch fall out of its
     // range -- stores dropped (a scalar offset would not be checked)
     auto rsrc_c_of = [&](unsigned gbase) __attribute__((always_inline)) {
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<unsigned char*>(a.C) + gbase, 0, (int)(a.c_bytes - gbase), kRSRsrcWord3);
+        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<unsigned char*>(a.C) + gbase, 0, (int)(a.c_bytes - gbase), kResRsrcWord3);
     };
-    const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(BITS ? a.bits_out : nullptr, 0, BITS ? (int)(a.c_bytes >> 5) : 0, kRSRsrcWord3);
+    const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(BITS ? a.bits_out : nullptr, 0, BITS ? (int)(a.c_bytes >> 5) : 0, kResRsrcWord3);
     float bj[NT];                                         // the lane's bias element per column tile
 #pragma unroll
     for (int j = 0; j < NT; ++j) bj[j] = a.bias[32 * j + li];
@@ -166,27 +146,16 @@ __global__ __launch_bounds__(RSGeom::THREADS) __attribute__((amdgpu_waves_per_eu
     // step of slot s into the buffer every wave read for the last time before the barrier of slot s - 1; slot NSLOT = the next group's slot 0.  The issuing wave
     // waits for ITS pieces in front of the barrier at the last step of slot s (the last slot: in front of the epilogue; the barrier is the next group's first):
     // vmcnt counts in order, so "all but the rs_dma_younger(s) source rounds issued behind the pieces".
-    const __amdgpu_buffer_rsrc_t rsrc_p = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.pack), 0, kF16PackHeader + RG::KSTEPS * RG::STEPB, kRSRsrcWord3);
+    const __amdgpu_buffer_rsrc_t rsrc_p = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.pack), 0, kF16PackHeader + RG::KSTEPS * RG::STEPB, kResRsrcWord3);
     auto dma_slot = [&](int slot) __attribute__((always_inline)) {                       // -> buffer slot & 1
 #pragma unroll
         for (int u = 0; u < kShare; ++u) {
             const int x = wave * kShare + u, h = x / (NT * 2), jt = x - h * (NT * 2);
-            rs_dma16(rsrc_p, ring + (slot & 1) * RG::SLOTB + x * 1024, 16u * (unsigned)lane, kF16PackHeader + r_kstep<RG>(SS * (slot % NSLOT) + h) * RG::STEPB + jt * 1024);
+            res_dma16(rsrc_p, ring + (slot & 1) * RG::SLOTB + x * 1024, 16u * (unsigned)lane, kF16PackHeader + r_kstep<RG>(SS * (slot % NSLOT) + h) * RG::STEPB + jt * 1024);
         }
     };
-    auto dma_wait = [&](int slot) __attribute__((always_inline)) {       // s_waitcnt vmcnt(rs_dma_younger(slot)): an immediate -- the chain folds once the k-loop is unrolled
-        const int n = rs_dma_younger(slot);
-#define RS_VMCNT_CASE(k) if (n == k) asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory");
-        RS_VMCNT_CASE(0) RS_VMCNT_CASE(1) RS_VMCNT_CASE(2) RS_VMCNT_CASE(3) RS_VMCNT_CASE(4)
-#undef RS_VMCNT_CASE
-        static_assert(RG::NI <= 5, "at most NI - 1 rounds behind a slot's pieces");
-    };
-    auto ring_barrier = [&]() __attribute__((always_inline)) {      // (a bare s_barrier: __syncthreads' fence would drain vmcnt -- source rounds, the previous group's stores)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-    };
 
-    rs_f32x16 acc[NT];
+    res_f32x16 acc[NT];
     int wv = 0;                                           // BITS: lane L (< 32) collects the mask word of slot row L of the tile in flight
     s_u32x4 pa[2][2], wb[2][NT][2];                       // [k-step parity]: pixel fragment [hi, lo]; weight fragments [tile][hi, lo]
     auto read_a = [&](int par, int v) __attribute__((always_inline)) {
@@ -214,9 +183,9 @@ __global__ __launch_bounds__(RSGeom::THREADS) __attribute__((amdgpu_waves_per_eu
         if constexpr (BITS) {                             // lanes 0..31 of the ballot: the 32 channels of slot row (e & 3) + 8 (e >> 2); 32..63: of that row + 4
             if (e == 0) wv = 0;
             const unsigned long long bal = __builtin_amdgcn_ballot_w64(v > 0.0f);
-            wv = rs_writelane(wv, (unsigned)bal, (e & 3) + 8 * (e >> 2));
-            wv = rs_writelane(wv, (unsigned)(bal >> 32), (e & 3) + 8 * (e >> 2) + 4);
-            if (e == 15) __builtin_amdgcn_raw_buffer_store_b32((unsigned)wv, rsrc_b, lh == 0 ? (gbase + rword + (unsigned)(128 * j)) >> 5 : kRSOob, 0, 0);
+            wv = res_writelane(wv, (unsigned)bal, (e & 3) + 8 * (e >> 2));
+            wv = res_writelane(wv, (unsigned)(bal >> 32), (e & 3) + 8 * (e >> 2) + 4);
+            if (e == 15) __builtin_amdgcn_raw_buffer_store_b32((unsigned)wv, rsrc_b, lh == 0 ? (gbase + rword + (unsigned)(128 * j)) >> 5 : kResOob, 0, 0);
         }
     };
     static_assert(RG::round_step(NI - 1) < PSTEPS - 1, "a class is written before the barrier at its phase's last step");
@@ -224,16 +193,16 @@ __global__ __launch_bounds__(RSGeom::THREADS) __attribute__((amdgpu_waves_per_eu
         const unsigned gbase = (unsigned)grp * kGroupC;
         const __amdgpu_buffer_rsrc_t ra_cur = rsrc_a_of(grp), ra_next = rsrc_a_of(grp + (int)gridDim.x);
         // every wave is done with the previous group's last class buffer and ring slot; class 0 and ring slot 0 of this group have been written
-        ring_barrier();
+        res_ring_barrier();
         read_a(0, 0);
         read_b(0, 0);
 #pragma unroll
         for (int v = 0; v < RG::KSTEPS; ++v) {
             const int q = v & 1, slot = v / SS, h = v % SS, g = v / PSTEPS, w = v % PSTEPS;
             // the operands of step v + 1 are requested before the matrix instructions of step v go out
-            if (h == SS - 1) dma_wait(slot);              // this wave's pieces of slot + 1 have landed
+            if (h == SS - 1) res_wait_vmcnt(rs_dma_younger(slot));      // this wave's pieces of slot + 1 have landed
             if (v + 1 < RG::KSTEPS) {
-                if (h == SS - 1) ring_barrier();          // ... everybody's; phase ends (w == PSTEPS - 1): class g + 1 is written, nobody reads class g - 1's buffer any more
+                if (h == SS - 1) res_ring_barrier();          // ... everybody's; phase ends (w == PSTEPS - 1): class g + 1 is written, nobody reads class g - 1's buffer any more
                 read_b(q ^ 1, v + 1);
                 read_a(q ^ 1, v + 1);
             }
@@ -279,7 +248,7 @@ __global__ __launch_bounds__(RSGeom::THREADS) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
         for (int r = 0; r < NI; ++r) get(ra, 0, r);
         dma_slot(0);
-        __builtin_amdgcn_s_waitcnt(kRSWaitVm0);
+        __builtin_amdgcn_s_waitcnt(kResWaitVm0);
 #pragma unroll
         for (int r = 0; r < NI; ++r) {
             put(0, r);
@@ -288,7 +257,7 @@ __global__ __launch_bounds__(RSGeom::THREADS) __attribute__((amdgpu_waves_per_eu
         // (the loop is entered as the back edge enters it in one respect: no round is in flight that has FEWER loads and stores behind it than on the back edge --
         //  the compiler's wait for a round is counted for the worse of the two entries, and "five loads behind class 1's first round" there would make every group
         //  wait at its first step until all but five of the previous group's stores are acknowledged.  One trip to memory per workgroup and launch.)
-        __builtin_amdgcn_s_waitcnt(kRSWaitVm0);
+        __builtin_amdgcn_s_waitcnt(kResWaitVm0);
     }
     for (; grp < a.groups; grp += gridDim.x) group(grp);
     if (a.c_amax) amax_commit(a.c_amax, __float_as_uint(cmax), blockIdx.x * NW + (unsigned)wave, lane);
@@ -299,23 +268,9 @@ bool convrs_takes(long long images) { return kernel_switch("MI355PPO_CONV_RS", i
 
 int convrs_fwd2(const char* fn, const float* src, unsigned src_bytes, const void* pack, const float* bias, float* dst, unsigned dst_bytes, unsigned* bits,
                 long long images, const unsigned* src_amax, unsigned* dst_amax, hipStream_t st) {
-    RSArgs a{};
-    a.A = src; a.a_bytes = src_bytes; a.pack = static_cast<const unsigned char*>(pack); a.bias = bias; a.bits_out = bits; a.C = dst; a.c_bytes = dst_bytes;
-    a.images = images; a.a_amax = src_amax; a.c_amax = dst_amax;
-    a.groups = (int)((images + RSGeom::G - 1) / RSGeom::G);
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
-            (void)hipGetLastError();
-            n = 256;
-        }
-        cus = n;
-    }
-    const int grid = a.groups < cus ? a.groups : cus;
-    if (bits) hipLaunchKernelGGL(rs_kernel<true>, dim3((unsigned)grid), dim3(RSGeom::THREADS), 0, st, a);
-    else hipLaunchKernelGGL(rs_kernel<false>, dim3((unsigned)grid), dim3(RSGeom::THREADS), 0, st, a);
-    return check_launch(fn);
+    RSArgs a = res_args<RSArgs>(src, src_bytes, pack, dst, dst_bytes, images, src_amax, dst_amax);
+    a.bias = bias; a.bits_out = bits;
+    return res_launch(bits ? rs_kernel<true> : rs_kernel<false>, a, RSGeom::G, 1, RSGeom::THREADS, st, fn);
 }
 
 }  // namespace mi355ppo

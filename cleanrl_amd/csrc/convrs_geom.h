@@ -54,8 +54,8 @@ struct RSGeom {
 };
 
 // visited step v -> the class buffer it reads (= its phase's class, mod 2) and the byte offset of the step's hi fragment from the lane's window origin
-R_GEOM_FN int rs_class(int v) { return v / RSGeom::PSTEPS; }
-R_GEOM_FN int rs_tapoff(int ks) {
+RES_GEOM_FN int rs_class(int v) { return v / RSGeom::PSTEPS; }
+RES_GEOM_FN int rs_tapoff(int ks) {
     const int ty = ks / RSGeom::SPR, us = ks - ty * RSGeom::SPR, tx = us / RSGeom::C16, chunk = us - tx * RSGeom::C16;
     return ((ty >> 1) * RSGeom::RP + (tx >> 1)) * RSGeom::PIX + chunk * 32;
 }

@@ -20,33 +20,12 @@
 // products of tap rows outside the image (zero operands): bit-identical results (tests/test_gpu_conv3_dgrad_classes.py).
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): 216 VGPRs, no AGPRs, 80 SGPRs, no scratch, no spills, 155,568 B of LDS, two waves per SIMD.
 // Measured: profiles/r08_conv3_dgrad_classes_ab.txt (479 -> 403 us per launch at 32,768 images).
-#include "common.h"
-#include "f16split.h"
+#include "conv_resident.h"
 #include "convrv_geom.h"
 
 #pragma clang fp contract(off)
 
 namespace mi355ppo {
-
-typedef float rv_f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr unsigned kRVOob = 0xFFFFF000u;              // buffer offset out of range for every tensor < 4 GiB - 4 KiB
-constexpr int kRVRsrcWord3 = 0x00020000;              // raw buffer, 32-bit elements
-constexpr int kRVWaitVm0 = 0x0F70;                    // s_waitcnt vmcnt(0) (gfx9 encoding: expcnt 7, lgkmcnt 15 = no wait)
-
-// x where bit (lane) of {hi, lo} is set, else 0 (convr.hip's r_keep_where: the s_nop covers the wait states a VALU read of an SGPR needs
-// behind a VALU write the compiler cannot see inside the asm)
-__device__ __forceinline__ float rv_keep_where(float x, unsigned lo, unsigned hi) {
-    const unsigned long long m = ((unsigned long long)hi << 32) | lo;
-    float r;
-    asm("s_nop 1\n\tv_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(x), "s"(m));
-    return r;
-}
-
-// one LDS-DMA piece: 16 bytes per lane from the buffer to LDS at `dst` + 16 lane (a plain function, as convr.hip's r_dma16)
-__device__ __forceinline__ void rv_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned char* dst, unsigned voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)dst, 16, voff, soff, 0, 0);
-}
 
 struct RVArgs {
     const float* A;             // dz3 (images, 7, 7, 64)
@@ -70,7 +49,7 @@ __device__ __forceinline__ void rv_wave(const RVArgs& a, unsigned char* const ld
     constexpr int MT = 4 + XC, NWM = (MT + 1) / 2;        // accumulator tiles; registers of mask words (64 wave rows each)
     constexpr int kPieces = SS * NT * 2;                  // KiB pieces of a ring slot: (step h of the slot, column tile j, term t), x = (h NT + j) 2 + t
     constexpr int kShare = kPieces / NW;                  // every wave moves kShare pieces of a slot
-    static_assert(kPieces % NW == 0 && MI355_RING_DMA, "whole pieces per wave; the ring by LDS-DMA only");
+    static_assert(kPieces % NW == 0, "whole pieces per wave");
     unsigned char* const ring = lds + RG::ABYTES;
     unsigned* const rofft = reinterpret_cast<unsigned*>(lds + RG::ABYTES + 2 * RG::SLOTB);
     const int lane = tid & 63, li = lane & 31, lh = lane >> 5;
@@ -101,7 +80,7 @@ __device__ __forceinline__ void rv_wave(const RVArgs& a, unsigned char* const ld
     winb[2] = origin(14 + simd, 2);
 
     // ---- the group's source: unit u = 16 bytes = 4 channels of a pixel; thread tid takes units it * THREADS + tid
-    const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.A), 0, (int)a.a_bytes, kRVRsrcWord3);
+    const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.A), 0, (int)a.a_bytes, kResRsrcWord3);
     unsigned udst[(NI + 1) / 2];                          // LDS byte address / 8 of two units' hi halves (lo: + LO), 16 bits each; 0xffff: no such unit
 #pragma unroll
     for (int it = 0; it < NI; ++it) {
@@ -110,50 +89,19 @@ __device__ __forceinline__ void rv_wave(const RVArgs& a, unsigned char* const ld
         const unsigned d = u < RG::UNITS ? (unsigned)(RG::rec(img, qy, qx) * RG::PIX + c4 * 8) >> 3 : 0xffffu;
         udst[it >> 1] = (it & 1) ? (udst[it >> 1] | (d << 16)) : d;
     }
-    // the next group's source: two loads per k-step from the second step on (unconditional: past the last group with out-of-range offsets, which
-    // load zeros without touching memory -- see convr.hip)
+    // the next group's source: two loads per k-step from the second step on (res_prefetch), filled at the top of the group (res_fill_packed)
     static_assert(rv_pre_lo(RG::KSTEPS) == NI, "the next group's source is requested inside one k-loop");
     s_u32x4 pre[NI];
-    auto prefetch = [&](int grp, int it0, int n) __attribute__((always_inline)) {
-        const bool any = grp < a.groups;
-        const unsigned base = (unsigned)grp * (unsigned)(RG::UNITS * 16);
-#pragma unroll
-        for (int it = it0; it < it0 + n && it < NI; ++it) {
-            const int u = it * THREADS + tid;
-            pre[it] = __builtin_bit_cast(s_u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_a, (any && u < RG::UNITS) ? base + (unsigned)u * 16u : kRVOob, 0, MI355_AUX_STREAM_LD));
-        }
-    };
-    auto fill = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int it = 0; it < NI; ++it) {
-            unsigned hi[2], lo[2];
-            f16_split4(pre[it], sa, hi, lo);
-            // (the packed word is made opaque in place, as in kernel RB: unpacked outside the group loop the addresses cost registers the k-loop does not have)
-            if ((it & 1) == 0) asm volatile("" : "+v"(udst[it >> 1]));
-            const unsigned d = (it & 1) ? udst[it >> 1] >> 16 : udst[it >> 1] & 0xffffu;
-            if ((it + 1) * THREADS <= RG::UNITS || d != 0xffffu) {
-                *reinterpret_cast<uint2*>(lds + 8u * d) = make_uint2(hi[0], hi[1]);
-                *reinterpret_cast<uint2*>(lds + 8u * d + RG::LO) = make_uint2(lo[0], lo[1]);
-            }
-        }
-    };
 
     // ---- epilogue constants: C's descriptor of a group starts AT the group (+ the wave's column tile): offsets are table words + the lane's channel
     const unsigned col_off = (unsigned)(jc * 32 * 4);
-    auto rsrc_c_of = [&](int g, unsigned gbase) __attribute__((always_inline)) {
-        const bool ok = g >= 0 && g < a.groups;
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<unsigned char*>(a.C) + (ok ? gbase : 0u), 0, ok ? (int)(a.c_bytes - gbase) : 0, kRVRsrcWord3);
-    };
-    auto rsrc_b_of = [&](int g) __attribute__((always_inline)) {
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned*>(a.bits_in), 0, (g >= 0 && g < a.groups) ? (int)(a.c_bytes >> 5) : 0, kRVRsrcWord3);
-    };
     float cmax = 0.0f;
 
     // ---- the weights' ring by LDS-DMA (kernel R's): slot s = k-steps SS s .. SS s + SS - 1 = one tap, two buffers.  Slot s + 1 is requested at the first step of
     // slot s into the buffer every wave read for the last time before the barrier of slot s - 1; the issuing wave waits for ITS pieces (vmcnt counts in order:
     // rv_dma_younger = the vector loads it issued behind them) in front of the barrier at the last step of slot s.  NSLOT is odd: slot s of a group lives in
     // buffer (s & 1) ^ gpar, gpar alternating from group to group (slot NSLOT = the next group's slot 0 goes where slot NSLOT - 2 was).
-    const __amdgpu_buffer_rsrc_t rsrc_p = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.pack), 0, kF16PackHeader + RG::KSTEPS * RG::STEPB, kRVRsrcWord3);
+    const __amdgpu_buffer_rsrc_t rsrc_p = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(a.pack), 0, kF16PackHeader + RG::KSTEPS * RG::STEPB, kResRsrcWord3);
     const unsigned lane16 = 16u * (unsigned)lane;
     int gpar = 0;
     unsigned rbuf[2] = {(unsigned)(RG::ABYTES + 16 * lane + jc * 2048), (unsigned)(RG::ABYTES + RG::SLOTB + 16 * lane + jc * 2048)};      // the lane's address in the buffer of this group's even / odd slots
@@ -161,22 +109,11 @@ __device__ __forceinline__ void rv_wave(const RVArgs& a, unsigned char* const ld
 #pragma unroll
         for (int u = 0; u < kShare; ++u) {
             const int x = wave * kShare + u, h = x / (NT * 2), jt = x - h * (NT * 2);
-            rv_dma16(rsrc_p, ring + ((slot & 1) ^ gpar) * RG::SLOTB + x * 1024, lane16, kF16PackHeader + (SS * (slot % NSLOT) + h) * RG::STEPB + jt * 1024);
+            res_dma16(rsrc_p, ring + ((slot & 1) ^ gpar) * RG::SLOTB + x * 1024, lane16, kF16PackHeader + (SS * (slot % NSLOT) + h) * RG::STEPB + jt * 1024);
         }
     };
-    auto dma_wait = [&](int slot) __attribute__((always_inline)) {       // s_waitcnt vmcnt(rv_dma_younger(slot)): an immediate once the k-loop is unrolled
-        const int n = rv_dma_younger(slot);
-#define RV_VMCNT_CASE(k) if (n == k) asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory");
-        RV_VMCNT_CASE(1) RV_VMCNT_CASE(2) RV_VMCNT_CASE(3) RV_VMCNT_CASE(4) RV_VMCNT_CASE(5) RV_VMCNT_CASE(6)
-#undef RV_VMCNT_CASE
-        if (n < 1 || n > 6) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (a full wait is always correct)
-    };
-    auto ring_barrier = [&]() __attribute__((always_inline)) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-    };
 
-    rv_f32x16 acc[MT];
+    res_f32x16 acc[MT];
     unsigned wm[NWM];                                     // lane L of wm[k]: the mask word of wave row 64 k + L = slot L % 32 of the wave's tile 2 k + L / 32 (this wave's column tile)
     s_u32x4 pa[4][2], wb[2][2];                           // pixel fragments of the step's tiles [position][hi, lo]; weight fragments [k-step parity][hi, lo]
     auto read_a = [&](int pos, unsigned w, int off) __attribute__((always_inline)) {
@@ -202,10 +139,9 @@ __device__ __forceinline__ void rv_wave(const RVArgs& a, unsigned char* const ld
         for (int k = 0; k < NWM; ++k) {
             const bool have = 2 * k + 1 < MT || lh == 0;   // (an odd number of tiles: lanes 32 .. 63 of the last register hold nothing)
             const unsigned ro = rofft[mword[k]];
-            wm[k] = __builtin_amdgcn_raw_buffer_load_b32(rb, have ? (gbase + ro) >> 5 : kRVOob, 0, 0);
+            wm[k] = __builtin_amdgcn_raw_buffer_load_b32(rb, have ? (gbase + ro) >> 5 : kResOob, 0, 0);
         }
     };
-    // three matrix instructions of a tile (hi hi, hi lo, lo hi: dependent); of a pair of tiles, interleaved
     auto mfma3 = [&](int q, int t, int p, int pi, bool z) __attribute__((always_inline)) {
         if (pi == 0 && z) {
 #pragma unroll
@@ -223,12 +159,12 @@ __device__ __forceinline__ void rv_wave(const RVArgs& a, unsigned char* const ld
 
     auto group = [&](int grp) __attribute__((always_inline)) {
         const unsigned gbase = (unsigned)grp * (unsigned)RG::GROUPC + col_off;
-        const __amdgpu_buffer_rsrc_t rb_cur = rsrc_b_of(grp);
+        const __amdgpu_buffer_rsrc_t rb_cur = res_rsrc_b_of(a.bits_in, a.c_bytes, grp >= 0 && grp < a.groups);
         // every wave is done with the previous group's records and ring slots
-        ring_barrier();                                   // (a bare s_barrier: __syncthreads' fence drains vmcnt -- the previous group's stores -- while an LDS-DMA may be pending)
-        fill();
+        res_ring_barrier();
+        res_fill_packed<RG>(lds, pre, udst, sa);
         __builtin_amdgcn_sched_barrier(0);
-        ring_barrier();                                   // the records are written (slot 0 landed before the previous epilogue / the prologue's wait)
+        res_ring_barrier();                               // the records are written (slot 0 landed before the previous epilogue / the prologue's wait)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[3][e] = 0.0f;
         read_b(0, 0);
@@ -239,8 +175,8 @@ __device__ __forceinline__ void rv_wave(const RVArgs& a, unsigned char* const ld
             const int q = v & 1, slot = v / SS, h = v % SS;
             if (v + 1 < RG::KSTEPS) {
                 if (h == SS - 1) {
-                    dma_wait(slot);                       // this wave's pieces of slot + 1 have landed
-                    ring_barrier();
+                    res_wait_vmcnt(rv_dma_younger(slot));      // this wave's pieces of slot + 1 have landed
+                    res_ring_barrier();
                 }
                 read_b(q ^ 1, v + 1);
             }
@@ -248,10 +184,10 @@ __device__ __forceinline__ void rv_wave(const RVArgs& a, unsigned char* const ld
                 dma_slot(slot + 1);                       // (slot NSLOT = the next group's slot 0; the last group fetches it for nobody)
                 __builtin_amdgcn_sched_barrier(0);        // (rv_dma_younger assumes the pieces are issued in front of this step's round)
             }
-            if (rv_pre_lo(v + 1) > rv_pre_lo(v)) prefetch(grp + a.grid, rv_pre_lo(v), rv_pre_lo(v + 1) - rv_pre_lo(v));
+            if (rv_pre_lo(v + 1) > rv_pre_lo(v)) res_prefetch<RG>(pre, rsrc_a, a.groups, tid, grp + a.grid, rv_pre_lo(v), rv_pre_lo(v + 1) - rv_pre_lo(v));
             if (v == RG::KSTEPS - 3) load_masks(gbase, rb_cur);          // (inside the last slot, behind its first step: no ring wait follows)
             if (h == 0 && (slot == 3 || slot == 6) && eb_pair) {          // {e, b}: the border accumulators change places
-                const rv_f32x16 t = acc[2];
+                const res_f32x16 t = acc[2];
                 acc[2] = acc[3];
                 acc[3] = t;
             }
@@ -271,29 +207,11 @@ __device__ __forceinline__ void rv_wave(const RVArgs& a, unsigned char* const ld
         }
         // every load in flight -- the next group's source, its first ring slot, this group's mask words -- is waited for in front of the
         // epilogue's stores (vmcnt counts loads and stores in one in-order queue: convr.hip)
-        __builtin_amdgcn_s_waitcnt(kRVWaitVm0);
+        __builtin_amdgcn_s_waitcnt(kResWaitVm0);
         __builtin_amdgcn_sched_barrier(0);
-        const __amdgpu_buffer_rsrc_t rc = rsrc_c_of(grp, gbase);
+        const __amdgpu_buffer_rsrc_t rc = res_rsrc_c_of(a.C, a.c_bytes, grp >= 0 && grp < a.groups, gbase);
 #pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            const unsigned* const rt = rofft + (tile_of(i) * 2 + lh) * 16;
-            unsigned ro[16];
-#pragma unroll
-            for (int e4 = 0; e4 < 4; ++e4) {
-                const s_u32x4 w = *reinterpret_cast<const s_u32x4*>(rt + 4 * e4);
-                ro[4 * e4] = w[0]; ro[4 * e4 + 1] = w[1]; ro[4 * e4 + 2] = w[2]; ro[4 * e4 + 3] = w[3];
-            }
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int wr = 32 * i + (e & 3) + 8 * (e >> 2);                 // wave row of lanes 0 .. 31's value; lanes 32 .. 63: + 4
-                const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)wm[wr >> 6], wr & 63);
-                const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)wm[(wr + 4) >> 6], (wr + 4) & 63);
-                const float v = rv_keep_where(acc[i][e] * un, lo, hi);
-                cmax = __builtin_fmaxf(cmax, __builtin_fabsf(v));
-                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rc, ro[e] + 4u * (unsigned)li, 0, MI355_AUX_STREAM_ST);
-            }
-            __builtin_amdgcn_sched_barrier(0);            // (one tile's offsets in registers at a time)
-        }
+        for (int i = 0; i < MT; ++i) res_masked_tile(acc[i], i, rofft + (tile_of(i) * 2 + lh) * 16, wm, un, cmax, rc, li);
         // the ring's buffers change places for the next group (nine slots)
         gpar ^= 1;
         const unsigned t = rbuf[0];
@@ -303,9 +221,9 @@ __device__ __forceinline__ void rv_wave(const RVArgs& a, unsigned char* const ld
 
     int grp = blockIdx.x;
     if (grp < a.groups) {
-        prefetch(grp, 0, NI);
+        res_prefetch<RG>(pre, rsrc_a, a.groups, tid, grp, 0, NI);
         dma_slot(0);
-        __builtin_amdgcn_s_waitcnt(kRVWaitVm0);
+        __builtin_amdgcn_s_waitcnt(kResWaitVm0);
     }
     for (; grp < a.groups; grp += a.grid) group(grp);
     if (a.c_amax) amax_commit(a.c_amax, __float_as_uint(cmax), blockIdx.x * NW + (unsigned)wave, lane);
@@ -333,19 +251,9 @@ bool convrv_takes(long long images) { return kernel_switch("MI355PPO_CONV_RV", i
 
 int convrv_dgrad3(const char* fn, const float* dz, unsigned dz_bytes, const void* pack, const unsigned* bits, float* dsrc, unsigned dsrc_bytes,
                   long long images, const unsigned* dz_amax, unsigned* dsrc_amax, hipStream_t st) {
-    RVArgs a{};
-    a.A = dz; a.a_bytes = dz_bytes; a.pack = static_cast<const unsigned char*>(pack); a.bits_in = bits; a.C = dsrc; a.c_bytes = dsrc_bytes;
-    a.images = images; a.a_amax = dz_amax; a.c_amax = dsrc_amax;
-    a.groups = (int)((images + RVGeom::G - 1) / RVGeom::G);
-    // (the CU count of the CURRENT device, asked at every call: an attribute query, no synchronisation -- the library keeps no per-process state)
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-        (void)hipGetLastError();
-        cus = 256;
-    }
-    a.grid = a.groups < cus ? a.groups : cus;
-    hipLaunchKernelGGL(rv_kernel, dim3((unsigned)a.grid), dim3(RVGeom::THREADS), 0, st, a);
-    return check_launch(fn);
+    RVArgs a = res_args<RVArgs>(dz, dz_bytes, pack, dsrc, dsrc_bytes, images, dz_amax, dsrc_amax);
+    a.bits_in = bits;
+    return res_launch(rv_kernel, a, RVGeom::G, 1, RVGeom::THREADS, st, fn);
 }
 
 }  // namespace mi355ppo

@@ -20,11 +20,7 @@
 //     waves (s and s + 4) take column tile 0 and column tile 1 of those, and ONE of the two also takes its column half of c tile 8 + s / 2.
 #pragma once
 
-#if defined(__HIPCC__)
-#define RV_GEOM_FN __device__ __forceinline__ constexpr
-#else
-#define RV_GEOM_FN inline constexpr
-#endif
+#include "conv_resident_geom.h"
 
 namespace mi355ppo {
 
@@ -69,26 +65,24 @@ static_assert(RVGeom::ABYTES / 8 < 0xffff, "two 16-bit record offsets per regist
 // Byte offset of k-step ks' hi fragment from the lane's window origin.  c tiles: the origin is the record of dz3 pixel (y - 2, x - 2) -- tap row 0;
 // border tiles keep one origin PER TAP ROW (the record of pixel (y + ty - 2, x - 2): a class's first valid tap row is folded into the origin), so
 // their offsets carry the tap column only and no immediate is negative.
-RV_GEOM_FN int rv_tapoff_c(int ks) {
+RES_GEOM_FN int rv_tapoff_c(int ks) {
     const int ty = ks / RVGeom::SPR, us = ks - ty * RVGeom::SPR, tx = us / RVGeom::C16, chunk = us - tx * RVGeom::C16;
     return (ty * RVGeom::RP + tx) * RVGeom::PIX + chunk * 32;
 }
-RV_GEOM_FN int rv_tapoff_b(int ks) {
+RES_GEOM_FN int rv_tapoff_b(int ks) {
     const int us = ks % RVGeom::SPR, tx = us / RVGeom::C16, chunk = us - tx * RVGeom::C16;
     return tx * RVGeom::PIX + chunk * 32;
 }
 // record of the window origin of row (gi, y, x) for tap row ty (pixel (y + ty - 2, x - 2): a zero record of line y + ty - 2 when x < 2)
-RV_GEOM_FN int rv_origin(int gi, int y, int x, int ty) { return RVGeom::rec(gi, y + ty - RVGeom::HL, x - RVGeom::HL); }
+RES_GEOM_FN int rv_origin(int gi, int y, int x, int ty) { return RVGeom::rec(gi, y + ty - RVGeom::HL, x - RVGeom::HL); }
 
 // Which row of the group sits in which lane: slot tile 32 + lane % 32 -> row id = image 81 + y 9 + x (`row`: -1 = an empty slot; `src`: the row the
-// slot computes -- its own, or for an empty slot a row of the same sixteen-lane set, i.e. the same LDS address: a broadcast; its values are
-// stored a second time).  A fragment read (ds_read_b128, lane = row) is served in sets of 16 lanes and is conflict-free when the 16 window
+// slot computes, ResRowSets::fill_empty).  A fragment read (ds_read_b128, lane = row) is served in sets of 16 lanes and is conflict-free when the 16 window
 // origins differ mod 16 (record pitch 17 slots).  As RRowTable does, the rows of a class are dealt to the sets of the class's tiles by the
 // residue of their window origin -- a set takes a residue twice only when no other set of the class can take it (the border classes: a
 // class's 63 origins 63 gi + x fall on 15 residues, up to seven rows each, for four sets).
-struct RVRowTable {
+struct RVRowTable : ResRowSets {
     short row[RVGeom::SLOTS], src[RVGeom::SLOTS];
-    static constexpr bool first_set(int l) { return l < 4 || (l >= 12 && l < 16) || (l >= 20 && l < 28); }
     constexpr RVRowTable() : row{}, src{} {
         using RG = RVGeom;
         constexpr int NSET = RG::SLOTS / 16;
@@ -125,22 +119,12 @@ struct RVRowTable {
                     }
                 }
         }
-        for (int s = 0; s < NSET; ++s) {
-            int have = -1;
-            for (int k = 0; k < 16; ++k)
-                if (row[slot_of[s][k]] >= 0) { have = row[slot_of[s][k]]; break; }
-            for (int k = 0; k < 16; ++k) src[slot_of[s][k]] = row[slot_of[s][k]] >= 0 ? row[slot_of[s][k]] : (short)have;
-        }
+        fill_empty(row, src);
     }
 };
 
-// vector loads a wave issues behind the LDS-DMA pieces of ring slot `slot` + 1 (requested at the slot's first step, in front of that step's round of the
-// next group's source) and in front of its wait (top of the slot's last step): the rounds of the slot's steps but the last -- two 16-byte loads per k-step
-// from the second step on, NI in all
-RV_GEOM_FN int rv_pre_lo(int v) {
-    const int n = (v - 1) * 2;
-    return v < 1 ? 0 : (n > RVGeom::NI ? RVGeom::NI : n);
-}
-RV_GEOM_FN int rv_dma_younger(int slot) { return rv_pre_lo(RVGeom::SS * slot + RVGeom::SS - 1) - rv_pre_lo(RVGeom::SS * slot); }
+// the next group's source: two 16-byte loads per k-step from the second step on, NI in all; those a wave issues behind a ring slot's LDS-DMA pieces
+RES_GEOM_FN int rv_pre_lo(int v) { return res_pre_lo(v, RVGeom::NI); }
+RES_GEOM_FN int rv_dma_younger(int slot) { return res_pre_younger(slot, RVGeom::SS, RVGeom::NI); }
 
 }  // namespace mi355ppo

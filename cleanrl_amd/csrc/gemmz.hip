@@ -1400,7 +1400,10 @@ static int conv_dgrad_packed_impl(const char* fn, const float* dz, const void* p
         return z_blds(images) ? z_launch<ZDgrad3, 2, 2, 4, Z_MASK, false, 2, true>(za, st, fn) : z_launch<ZDgrad3, 2, 2, 4, Z_MASK, false, 2>(za, st, fn);
     }
     // da1 (images, 20, 20, 32): the four stride-parity classes are the four column tiles of one 128-column GEMM over the 10 x 10 grid
-    if (dz_amax && bits && conv_r_takes(images, 2, true)) return convr_dgrad2(fn, dz, (unsigned)srcb, pack, bits, dsrc, (unsigned)dstb, images, dz_amax, dsrc_amax, st);
+    if (dz_amax && bits && conv_r_takes(images, 2, true)) {      // kernel R's layer-2 data gradient: from MI355_RB_MIN_IMAGES images on its border-class form, kernel RB (convrb.hip)
+        if (convrb_takes(images)) return convrb_dgrad2(fn, dz, (unsigned)srcb, pack, bits, dsrc, (unsigned)dstb, images, dz_amax, dsrc_amax, st);
+        return convr_dgrad2(fn, dz, (unsigned)srcb, pack, bits, dsrc, (unsigned)dstb, images, dz_amax, dsrc_amax, st);
+    }
     ZArgs za = zargs(dz, srcb, 0, pack, nullptr, act_in, dsrc, (long long)images * 400 * 32 * 4, 0, (long long)images * 100, 128, ZDgrad2::K, images);
     za.bits_in = bits;
     za.a_amax = dz_amax; za.c_amax = dsrc_amax;

@@ -196,11 +196,17 @@ def test_which_kernel_a_packed_f16x2_convolution_takes_is_a_host_side_decision(m
     layer-2 data gradient below 512 images; the switches of DESIGN 3.7 are read at every call."""
     lib = _lib.load()
     monkeypatch.delenv("MI355PPO_CONV_R", raising=False)
+    monkeypatch.delenv("MI355PPO_CONV_RB", raising=False)
     k = lambda images, layer, dgrad: chr(lib.mi355ppo_cnn_conv_packed_kernel_f16x2(images, layer, dgrad))
     assert [k(n, 2, 0) for n in (1, 256, 32768)] == ["R"] * 3 and [k(n, 3, 0) for n in (1, 256, 32768)] == ["R"] * 3
     assert [k(n, 3, 1) for n in (1, 32768)] == ["R", "R"]
     assert [k(n, 2, 1) for n in (1, 511, 512, 3071, 3072, 32768)] == ["Z", "Z", "R", "R", "B", "B"]      # ('B': kernel RB, convrb.hip)
     assert k(0, 2, 0) == "Z" and k(64, 1, 0) == "Z" and k(64, 4, 1) == "Z"          # nothing kernel R could take
+    monkeypatch.setenv("MI355PPO_CONV_RB", "0")                     # kernel RB's own switch: kernel R keeps the layer-2 data gradient
+    assert k(32768, 2, 1) == "R"
+    monkeypatch.setenv("MI355PPO_CONV_RB", "min:512")
+    assert k(512, 2, 1) == "B" and k(511, 2, 1) == "Z"
+    monkeypatch.delenv("MI355PPO_CONV_RB")
     monkeypatch.setenv("MI355PPO_CONV_R", "min:8192")
     assert k(4096, 3, 0) == "Z" and k(8192, 3, 0) == "R" and k(8192, 2, 1) == "B"
     monkeypatch.setenv("MI355PPO_CONV_R", "0")
