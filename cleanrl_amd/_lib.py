@@ -329,6 +329,16 @@ SIGNATURES = {
     "mi355ppo_ma_atari_conv1_wgrad_fold_workspace_bytes": (c_size_t, [c_int64]),
     "mi355ppo_ma_atari_conv1_wgrad_fold_f32": (c_int, [_P] * 5 + [c_int64, _P, c_size_t, _P]),
     "mi355ppo_ma_atari_conv1_wgrad_fold_f32_cpu": (c_int, [_P] * 5 + [c_int64]),
+    # the LayerNorm NatureCNN of pqn_atari_envpool (added under ABI 2.7.1, csrc/layernorm.hip, csrc/conv1q.hip, csrc/gemmz.hip)
+    "mi355ppo_cnn_conv1q_pre_fwd": (c_int, [_P] * 5 + [c_int64, _P]),
+    "mi355ppo_cnn_conv1q_pre_fwd_cpu": (c_int, [_P] * 5 + [c_int64]),
+    "mi355ppo_cnn_conv_pre_packed_f16x2_f32": (c_int, [_P] * 4 + [c_int64, c_int, _P, _P]),
+    "mi355ppo_fc_pre_packed_f16x2_f32": (c_int, [_P, c_int, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P, _P]),
+    "mi355ppo_layernorm_relu_fwd_f32": (c_int, [_P] * 8 + [c_int64, c_int, c_int, c_double, _P]),
+    "mi355ppo_layernorm_relu_fwd_f32_cpu": (c_int, [_P] * 8 + [c_int64, c_int, c_int, c_double]),
+    "mi355ppo_layernorm_bwd_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "mi355ppo_layernorm_relu_bwd_f32": (c_int, [_P] * 10 + [c_int64, c_int, c_int, _P, c_size_t, _P]),
+    "mi355ppo_layernorm_relu_bwd_f32_cpu": (c_int, [_P] * 10 + [c_int64, c_int, c_int]),
 }
 
 ABI_VERSION = 271       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)

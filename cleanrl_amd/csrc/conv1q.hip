@@ -65,12 +65,15 @@ __device__ __forceinline__ int q_writelane(int w, unsigned x, int l) {
 // ROWB: the bias is one per IMAGE and channel (ma_atari_rows.h): ma_rowbias of `bias`, the tap sums `tapsum` (32, 2) and the two indicator bytes
 // `ind[2 s], ind[2 s + 1]` of the image's source row s.  A tile touches at most two images, so the epilogue holds two biases per lane and picks by
 // the pixel's position in the tile; the four bytes travel with the tile's address (one scalar load per image: the aligned word that holds the pair).
-template <int NW, bool BITS, int WPS, bool ROWB = false>
+// PRE: the pre-activation acc * scale + bias without the ReLU -- what the LayerNorm of pqn_atari_envpool.py's network normalises (layernorm.hip);
+// no mask bits (BITS = false) and no amax record: only the LayerNorm kernel reads it.
+template <int NW, bool BITS, int WPS, bool ROWB = false, bool PRE = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPS, WPS))) void conv1q_fwd_kernel(const unsigned char* __restrict__ src, const int64_t* __restrict__ inds,
                                                              const unsigned char* __restrict__ pack, const float* __restrict__ bias,
                                                              float* __restrict__ dst, unsigned* __restrict__ bits, unsigned P, int ntiles, unsigned dst_bytes,
                                                              unsigned* __restrict__ amax, const unsigned char* __restrict__ ind = nullptr,
                                                              const float* __restrict__ tapsum = nullptr) {
+    static_assert(!PRE || !BITS, "the pre-activation has no ReLU mask");
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (wave-uniform: the tile index lives in an SGPR)
     const int li = lane & 31, lh = lane >> 5;
     // digit matrices, in operand layout, -> LDS [row][digit][lane]
@@ -197,8 +200,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPS, WP
             float v = t * scale;
             if constexpr (ROWB) v = v + (((unsigned)((e & 3) + 8 * (e >> 2) + 4 * lh) - cut) < span ? rb1 : rb0);
             else v = v + bias_r;
-            v = v > 0.0f ? v : 0.0f;
-            vmax = __float_as_uint(v) > vmax ? __float_as_uint(v) : vmax;     // (pixels past P re-read pixel 0: real values)
+            if constexpr (!PRE) {
+                v = v > 0.0f ? v : 0.0f;
+                vmax = __float_as_uint(v) > vmax ? __float_as_uint(v) : vmax;     // (pixels past P re-read pixel 0: real values)
+            }
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rsrc_dst, off, 0, MI355_AUX_STREAM_ST);   // dropped when out of range
             if constexpr (BITS) {      // ballot lanes 0..31: the 32 channels of pixel (e & 3) + 8 (e >> 2); lanes 32..63: of that pixel + 4
                 const unsigned long long bal = __builtin_amdgcn_ballot_w64(v > 0.0f);
@@ -212,7 +217,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPS, WP
         iw_cur = iw_nxt;
         nxt = setup(tile + 2 * nwv, iw_nxt);
     }
-    if (amax) amax_commit(amax, vmax, blockIdx.x * NW + wave, lane);      // (uniform; one atomic per wave of the persistent grid)
+    if constexpr (!PRE)
+        if (amax) amax_commit(amax, vmax, blockIdx.x * NW + wave, lane);      // (uniform; one atomic per wave of the persistent grid)
 }
 
 static int g_q_cus = 0;
@@ -237,7 +243,7 @@ extern "C" MI355PPO_API int mi355ppo_cnn_conv1q_pack(const float* W, void* pack,
 
 static int conv1q_fwd_impl(const char* fn, const void* src_u8, const int64_t* inds, const void* pack, const float* bias, float* dst,
                            unsigned* bits, int64_t images, void* stream, unsigned* amax = nullptr, const unsigned char* ind = nullptr,
-                           const float* tapsum = nullptr) {
+                           const float* tapsum = nullptr, bool pre = false) {
     MI355_REQUIRE(src_u8 && pack && bias && dst, MI355PPO_EINVAL, "%s: null pointer", fn);
     MI355_REQUIRE((ind == nullptr) == (tapsum == nullptr) && aligned(ind, 2) && aligned(tapsum, 4), MI355PPO_EINVAL,
                   "%s: the indicator bytes (2-byte aligned) and the tap sums come together", fn);
@@ -268,11 +274,17 @@ static int conv1q_fwd_impl(const char* fn, const void* src_u8, const int64_t* in
     hipLaunchKernelGGL((conv1q_fwd_kernel<NW, BITS_, WPS_, true>), dim3((unsigned)wgs), dim3(64 * NW), 0, as_stream(stream),                   \
                        static_cast<const unsigned char*>(src_u8), inds, static_cast<const unsigned char*>(pack), bias, dst, bits, (unsigned)P, \
                        ntiles, (unsigned)dstb, amax, ind, tapsum)
-    if (ind) {
+#define MI355_Q_LAUNCH_PRE(WPS_)                                                                                                               \
+    hipLaunchKernelGGL((conv1q_fwd_kernel<NW, false, WPS_, false, true>), dim3((unsigned)wgs), dim3(64 * NW), 0, as_stream(stream),            \
+                       static_cast<const unsigned char*>(src_u8), inds, static_cast<const unsigned char*>(pack), bias, dst, bits, (unsigned)P, \
+                       ntiles, (unsigned)dstb, amax)
+    if (pre) { if (wps == 4) MI355_Q_LAUNCH_PRE(4); else MI355_Q_LAUNCH_PRE(3); }
+    else if (ind) {
         if (bits) { if (wps == 4) MI355_Q_LAUNCH_ROWB(true, 4); else MI355_Q_LAUNCH_ROWB(true, 3); }
         else { if (wps == 4) MI355_Q_LAUNCH_ROWB(false, 4); else MI355_Q_LAUNCH_ROWB(false, 3); }
     } else if (bits) { if (wps == 4) MI355_Q_LAUNCH(true, 4); else MI355_Q_LAUNCH(true, 3); }
     else { if (wps == 4) MI355_Q_LAUNCH(false, 4); else MI355_Q_LAUNCH(false, 3); }
+#undef MI355_Q_LAUNCH_PRE
 #undef MI355_Q_LAUNCH_ROWB
 #undef MI355_Q_LAUNCH
     return check_launch(fn);
@@ -297,6 +309,13 @@ extern "C" MI355PPO_API int mi355ppo_cnn_conv1q_fwd_amax(const void* src_u8, con
     const char* fn = "mi355ppo_cnn_conv1q_fwd_amax";
     MI355_REQUIRE(dst_amax && aligned(dst_amax, 64), MI355PPO_EINVAL, "%s: amax record missing or not 64-byte aligned", fn);
     return conv1q_fwd_impl(fn, src_u8, inds, pack, bias, dst, mask_bits, images, stream, dst_amax);
+}
+
+// The pre-activation conv1(obs[inds] / 255) + bias (no ReLU, no mask bits, no amax record): the input of the first LayerNorm of
+// pqn_atari_envpool.py's network.  relu() of it is mi355ppo_cnn_conv1q_fwd's result bit for bit.
+extern "C" MI355PPO_API int mi355ppo_cnn_conv1q_pre_fwd(const void* src_u8, const int64_t* inds, const void* pack, const float* bias,
+                                                        float* dst, int64_t images, void* stream) {
+    return conv1q_fwd_impl("mi355ppo_cnn_conv1q_pre_fwd", src_u8, inds, pack, bias, dst, nullptr, images, stream, nullptr, nullptr, nullptr, true);
 }
 
 // ppo_pettingzoo_ma_atari.py's conv1 on the stored (84, 84, 4) rows: kernel Q's pack of channels 0 - 3 of the (32, 6, 8, 8) weight and the

@@ -55,7 +55,8 @@ __device__ __forceinline__ int z_writelane(int w, unsigned x, int l) {
 // Z_RAW (GEMM rows, split K): blockIdx.z owns `steps_per` k-steps and stores its raw f32 partial of C into slab z of a workspace;
 // zsplit_reduce_kernel adds the slabs in order, then bias + ReLU (rollout-sized batches: M / 64 x N / 64 wave tiles alone cannot fill
 // the chip and each would walk all K / 16 = 196 k-steps in a row).
-enum { Z_BIAS_RELU = 0, Z_MASK = 1, Z_MASK_CLS4 = 2, Z_MASKB = 3, Z_MASKB_CLS4 = 4, Z_BIAS_RELU_BITS = 5, Z_RAW = 6 };
+enum { Z_BIAS_RELU = 0, Z_MASK = 1, Z_MASK_CLS4 = 2, Z_MASKB = 3, Z_MASKB_CLS4 = 4, Z_BIAS_RELU_BITS = 5, Z_RAW = 6,
+       Z_BIAS = 7 };      // Z_BIAS: C = acc + bias, the pre-activation a LayerNorm follows (layernorm.hip); the same accumulation as Z_BIAS_RELU
 
 // x where bit (lane) of the 64-bit lane mask {hi, lo} is set, else 0: one v_cndmask with the mask in an SGPR pair.
 __device__ __forceinline__ float z_keep_where(float x, unsigned lo, unsigned hi) {
@@ -980,7 +981,8 @@ __global__ __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(OCC
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
                     float v = fin(acc[i][j][e]) + bj[j];
-                    if constexpr (SPLIT) v = v < 0.0f ? 0.0f : v;      // (a NaN from an overflowed f16 operand -- an understated amax record -- stays a NaN)
+                    if constexpr (EPI == Z_BIAS) {}                    // (the pre-activation: no ReLU)
+                    else if constexpr (SPLIT) v = v < 0.0f ? 0.0f : v;      // (a NaN from an overflowed f16 operand -- an understated amax record -- stays a NaN)
                     else v = v > 0.0f ? v : 0.0f;
                     seen(v);
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rsrc_c, at(ro, j), 0, 0);
@@ -1166,6 +1168,20 @@ __global__ __launch_bounds__(256) void zsplit_reduce_kernel(const float4* __rest
     const float* const b = bias + 4 * (i % (size_t)n4);
     acc.x += b[0]; acc.y += b[1]; acc.z += b[2]; acc.w += b[3];
     h[i] = make_float4(acc.x > 0.0f ? acc.x : 0.0f, acc.y > 0.0f ? acc.y : 0.0f, acc.z > 0.0f ? acc.z : 0.0f, acc.w > 0.0f ? acc.w : 0.0f);
+}
+
+// The same fold without the ReLU: the pre-activation of the FC layer (mi355ppo_fc_pre_packed_f16x2_f32), the additions in zsplit_reduce_kernel's order
+__global__ __launch_bounds__(256) void zsplit_reduce_pre_kernel(const float4* __restrict__ part, int splits, size_t slab4, const float* __restrict__ bias,
+                                                                int n4, float4* __restrict__ h, size_t total4) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total4) return;
+    float4 acc = part[i];
+    for (int z = 1; z < splits; ++z) {
+        const float4 p = part[(size_t)z * slab4 + i];
+        acc.x += p.x; acc.y += p.y; acc.z += p.z; acc.w += p.w;
+    }
+    const float* const b = bias + 4 * (i % (size_t)n4);
+    h[i] = make_float4(acc.x + b[0], acc.y + b[1], acc.z + b[2], acc.w + b[3]);
 }
 
 // K splits of the small-batch forward: (row tile, column tile, split) wave tiles for ONE wave per SIMD (1,024: measured 30.8 us at
@@ -1501,4 +1517,59 @@ extern "C" MI355PPO_API int mi355ppo_cnn_conv_dgrad_packed_f16x2_f32(const float
     const char* fn = "mi355ppo_cnn_conv_dgrad_packed_f16x2_f32";
     MI355_REQUIRE(dz_amax && aligned(dz_amax, 64) && aligned(dsrc_amax, 64), MI355PPO_EINVAL, "%s: dz's amax record missing, or a record not 64-byte aligned", fn);
     return conv_dgrad_packed_impl(fn, dz, pack, mask_bits ? nullptr : act_in, mask_bits, dsrc, images, layer, stream, dz_amax, dsrc_amax);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- pre-activation forwards
+// z = conv(src) + bias / a @ B^T + bias WITHOUT the ReLU (Z_BIAS): what the LayerNorm + ReLU of pqn_atari_envpool.py's network normalises
+// (layernorm.hip).  f16x2 split only; always kernel Z, at the tile shapes -- and, for the FC layer, the K split -- of the ReLU forwards of
+// the same size, so relu(z) is the ReLU forward's result bit for bit.  No amax record for z: only the LayerNorm kernel reads it.
+extern "C" MI355PPO_API int mi355ppo_cnn_conv_pre_packed_f16x2_f32(const float* src, const void* pack, const float* bias, float* dst,
+                                                                   int64_t images, int layer, const uint32_t* src_amax, void* stream) {
+    const char* fn = "mi355ppo_cnn_conv_pre_packed_f16x2_f32";
+    MI355_REQUIRE(src && pack && bias && dst, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(src_amax && aligned(src_amax, 64), MI355PPO_EINVAL, "%s: src's amax record missing or not 64-byte aligned", fn);
+    MI355_REQUIRE(layer == 2 || layer == 3, MI355PPO_EINVAL, "%s: layer=%d must be 2 or 3", fn, layer);
+    MI355_REQUIRE(images > 0, MI355PPO_EINVAL, "%s: images=%lld must be positive", fn, (long long)images);
+    MI355_REQUIRE(aligned(src, 16) && aligned(pack, 16) && aligned(dst, 128) && aligned(bias, 4), MI355PPO_EALIGN,
+                  "%s: src / pack must be 16-byte aligned, dst 128-byte aligned", fn);
+    const long long srcb = (long long)images * (layer == 2 ? 20 * 20 * 32 : 9 * 9 * 64) * 4;
+    MI355_REQUIRE(srcb < (1LL << 32) - 8192, MI355PPO_EINVAL, "%s: the source (%lld bytes) must stay below 4 GiB (32-bit buffer offsets)", fn, srcb);
+    hipStream_t st = as_stream(stream);
+    const bool small = images < 768;
+    if (layer == 2) {
+        ZArgs za = zargs(src, srcb, 0, pack, bias, nullptr, dst, (long long)images * 81 * 64 * 4, 64, (long long)images * 81, 64, ZConv2::K);
+        za.a_amax = src_amax;
+        if (small) return z_launch<ZConv2, 1, 2, 4, Z_BIAS, false, 2>(za, st, fn);
+        return z_blds(images) ? z_launch<ZConv2, 2, 2, 4, Z_BIAS, false, 2, true>(za, st, fn) : z_launch<ZConv2, 2, 2, 4, Z_BIAS, false, 2>(za, st, fn);
+    }
+    ZArgs za = zargs(src, srcb, 0, pack, bias, nullptr, dst, (long long)images * 49 * 64 * 4, 64, (long long)images * 49, 64, ZConv3::K);
+    za.a_amax = src_amax;
+    if (small) return z_launch<ZConv3, 1, 2, 4, Z_BIAS, false, 2>(za, st, fn);
+    return z_blds(images) ? z_launch<ZConv3, 2, 2, 4, Z_BIAS, false, 2, true>(za, st, fn) : z_launch<ZConv3, 2, 2, 4, Z_BIAS, false, 2>(za, st, fn);
+}
+
+// a @ B^T + bias; `ws`: mi355ppo_fc_fwd_workspace_bytes(M, N, K) bytes (below 8,192 rows: K split over the grid, as the ReLU forward splits it)
+extern "C" MI355PPO_API int mi355ppo_fc_pre_packed_f16x2_f32(const float* a, int lda, const void* pack, const float* bias, float* h, int M, int N,
+                                                             int K, void* ws, size_t ws_bytes, const uint32_t* a_amax, void* stream) {
+    const char* fn = "mi355ppo_fc_pre_packed_f16x2_f32";
+    MI355_REQUIRE(a_amax && aligned(a_amax, 64), MI355PPO_EINVAL, "%s: a's amax record missing or not 64-byte aligned", fn);
+    int rc = zgemm_check(fn, a, pack, h, M, N, K, lda, N);
+    if (rc) return rc;
+    MI355_REQUIRE(bias && aligned(bias, 4), MI355PPO_EINVAL, "%s: bias missing or misaligned", fn);
+    const size_t need = mi355ppo_fc_fwd_workspace_bytes(M, N, K);
+    if (need == 0 || N % 4) {
+        ZArgs za = zargs(a, (long long)M * lda * 4, lda, pack, bias, nullptr, h, (long long)M * N * 4, N, M, N, K);
+        za.a_amax = a_amax;
+        if (M < 16384) return z_launch<ZRowsLinear, 2, 2, 4, Z_BIAS, true, 2>(za, as_stream(stream), fn);
+        return z_launch<ZRowsLinear, 2, 4, 4, Z_BIAS, true>(za, as_stream(stream), fn);
+    }
+    MI355_REQUIRE(ws && aligned(h, 16) && aligned(ws, 16), MI355PPO_EWORKSPACE, "%s: M=%d rows split K: a 16-byte aligned workspace is needed (h too)", fn, M);
+    MI355_REQUIRE(ws_bytes >= need, MI355PPO_EWORKSPACE, "%s: workspace of %zu bytes, %zu needed (mi355ppo_fc_fwd_workspace_bytes)", fn, ws_bytes, need);
+    int splits = 0;
+    rc = z_fc_raw_launch(fn, a, lda, pack, M, N, K, ws, ws_bytes, &splits, as_stream(stream), a_amax);
+    if (rc) return rc;
+    const size_t total4 = (size_t)M * N / 4;
+    hipLaunchKernelGGL(zsplit_reduce_pre_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, as_stream(stream),
+                       static_cast<const float4*>(ws), splits, total4, bias, N / 4, reinterpret_cast<float4*>(h), total4);
+    return check_launch(fn);
 }

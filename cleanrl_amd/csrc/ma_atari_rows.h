@@ -59,6 +59,16 @@ MI355_HD float ma_q_finish(const int D[4], float scale, float bias) {
     return v > 0.0f ? v : 0.0f;
 }
 
+// the same without the ReLU (kernel Q's PRE instance: the pre-activation a LayerNorm follows)
+MI355_HD float ma_q_finish_pre(const int D[4], float scale, float bias) {
+    float t = (float)D[3];
+    t = __builtin_fmaf(t, 0.00390625f, (float)D[2]);
+    t = __builtin_fmaf(t, 0.00390625f, (float)D[1]);
+    t = __builtin_fmaf(t, 0.00390625f, (float)D[0]);
+    float v = t * scale;
+    return v + bias;
+}
+
 // strip q of channel n of one image's dz1 (400, 32), ascending pixels
 MI355_HD double ma_fold_strip(const float* dz_img, int n, int q) {
     double s = 0.0;

@@ -53,7 +53,7 @@ void q_pack_host(const float* W, int cs, unsigned char* pack) {
 
 // kernel Q, serial: exact integer dot products of the bytes with the pack's digits, then its epilogue; ind == nullptr: the plain bias
 int q_fwd_host(const char* fn, const uint8_t* src, const int64_t* inds, const uint8_t* ind, const unsigned char* pack, const float* tapsum,
-               const float* bias, float* dst, uint32_t* bits, int64_t images) {
+               const float* bias, float* dst, uint32_t* bits, int64_t images, bool pre = false) {
     MI355_REQUIRE(src && pack && bias && dst && (ind == nullptr) == (tapsum == nullptr), MI355PPO_EINVAL, "%s: null pointer", fn);
     MI355_REQUIRE(images > 0, MI355PPO_EINVAL, "%s: images=%lld must be positive", fn, (long long)images);
     const signed char* dig = reinterpret_cast<const signed char*>(pack);
@@ -74,7 +74,7 @@ int q_fwd_host(const char* fn, const uint8_t* src, const int64_t* inds, const ui
                 float sc;
                 memcpy(&sc, pack + kQScaleOff + n * 4, 4);
                 const float b = ind ? ma_rowbias(bias[n], tapsum[2 * n], tapsum[2 * n + 1], ind[2 * row], ind[2 * row + 1]) : bias[n];
-                const float v = ma_q_finish(D, sc, b);
+                const float v = pre ? ma_q_finish_pre(D, sc, b) : ma_q_finish(D, sc, b);
                 dst[((size_t)img * kQPerImg + p) * 32 + n] = v;
                 if (v > 0.0f) word |= 1u << n;
             }
@@ -122,6 +122,12 @@ extern "C" MI355PPO_API int mi355ppo_cnn_conv1q_fwd_cpu(const void* src_u8, cons
                                                         uint32_t* mask_bits, int64_t images) {
     return q_fwd_host("mi355ppo_cnn_conv1q_fwd_cpu", static_cast<const uint8_t*>(src_u8), inds, nullptr, static_cast<const unsigned char*>(pack),
                       nullptr, bias, dst, mask_bits, images);
+}
+
+extern "C" MI355PPO_API int mi355ppo_cnn_conv1q_pre_fwd_cpu(const void* src_u8, const int64_t* inds, const void* pack, const float* bias, float* dst,
+                                                            int64_t images) {
+    return q_fwd_host("mi355ppo_cnn_conv1q_pre_fwd_cpu", static_cast<const uint8_t*>(src_u8), inds, nullptr, static_cast<const unsigned char*>(pack),
+                      nullptr, bias, dst, nullptr, images, true);
 }
 
 extern "C" MI355PPO_API int mi355ppo_ma_atari_conv1_fwd_cpu(const void* src_u8, const int64_t* inds, const uint8_t* ind, const void* pack,

@@ -387,6 +387,59 @@ def pqn_td_loss(q, mb_inds, b_actions, b_returns, dq=None, scalars=None):
     return dq, scalars
 
 
+def layernorm_relu_fwd(z, gamma, beta, C, HW, eps=1e-5, out=None, mean=None, rstd=None, bits=None, amax=None):
+    """``mi355ppo_layernorm_relu_fwd_f32_cpu`` (see ops.layernorm_relu_fwd): the device's bits; an amax record's value lands in its word 0."""
+    rows, D = z.shape[0], int(C) * int(HW)
+    zz, g, b = _f32(z), _f32(gamma), _f32(beta)
+    if zz.numel() != rows * D or g.numel() != D or b.numel() != D:
+        raise ValueError(f"layernorm: rows of {D} floats with {D} gamma / beta, got {tuple(z.shape)}, {g.numel()}, {b.numel()}")
+    out = torch.empty_like(zz) if out is None else out
+    mean = torch.empty(rows) if mean is None else mean
+    rstd = torch.empty(rows) if rstd is None else rstd
+    _lib.call("mi355ppo_layernorm_relu_fwd_f32_cpu", _p(zz), _p(g), _p(b), _out(out, torch.float32, rows * D, "out"),
+              _out(mean, torch.float32, rows, "mean"), _out(rstd, torch.float32, rows, "rstd"),
+              _out(bits, torch.int32, rows * D // 32 if D % 32 == 0 else rows * D, "bits"), _out(amax, torch.int32, 256, "amax"), rows, int(C), int(HW),
+              float(eps))
+    return out, mean, rstd
+
+
+def layernorm_relu_bwd(dy, z, mean, rstd, gamma, C, HW, act=None, dz=None, dgamma=None, dbeta=None, amax=None):
+    """``mi355ppo_layernorm_relu_bwd_f32_cpu`` (see ops.layernorm_relu_bwd)."""
+    rows, D = z.shape[0], int(C) * int(HW)
+    zz, dd, g, m, r = _f32(z), _f32(dy), _f32(gamma), _f32(mean), _f32(rstd)
+    aa = None if act is None else _f32(act)
+    if zz.numel() != rows * D or dd.numel() != rows * D or g.numel() != D or m.numel() != rows or r.numel() != rows or (aa is not None and aa.numel() != rows * D):
+        raise ValueError(f"layernorm: rows of {D} floats, got z {tuple(z.shape)}, dy {tuple(dy.shape)}, gamma {g.numel()}")
+    dz = torch.empty_like(zz) if dz is None else dz
+    dgamma = torch.empty_like(g) if dgamma is None else dgamma
+    dbeta = torch.empty_like(g) if dbeta is None else dbeta
+    _lib.call("mi355ppo_layernorm_relu_bwd_f32_cpu", _p(dd), _p(aa), _p(zz), _p(m), _p(r), _p(g), _out(dz, torch.float32, rows * D, "dz"),
+              _out(dgamma, torch.float32, D, "dgamma"), _out(dbeta, torch.float32, D, "dbeta"), _out(amax, torch.int32, 256, "amax"), rows, int(C),
+              int(HW))
+    return dz, dgamma, dbeta
+
+
+def conv1q_pack(W):
+    """``mi355ppo_cnn_conv1q_pack_cpu``: kernel Q's pack of a (32, 4, 8, 8) weight, as f32 storage."""
+    pack = torch.empty(_lib.load().mi355ppo_cnn_conv1q_pack_bytes() // 4, dtype=torch.float32)
+    _lib.call("mi355ppo_cnn_conv1q_pack_cpu", _p(_f32(W)), _p(pack))
+    return pack
+
+
+def conv1q_pre_fwd(obs_u8, pack, bias, inds=None, out=None):
+    """``mi355ppo_cnn_conv1q_pre_fwd_cpu`` (see ops.conv1q_pre_fwd)."""
+    if obs_u8.dtype != torch.uint8 or tuple(obs_u8.shape[1:]) != (84, 84, 4):
+        raise ValueError(f"conv1q_pre_fwd: source rows must be (84, 84, 4) uint8, got {tuple(obs_u8.shape)} {obs_u8.dtype}")
+    ii = None if inds is None else _i64(inds)
+    if ii is not None and ii.numel() and (int(ii.min()) < 0 or int(ii.max()) >= obs_u8.shape[0]):
+        raise ValueError("conv1q_pre_fwd: inds out of range")
+    images = obs_u8.shape[0] if ii is None else ii.numel()
+    out = torch.empty((images, 20, 20, 32)) if out is None else out
+    _lib.call("mi355ppo_cnn_conv1q_pre_fwd_cpu", _p(obs_u8.contiguous()), _p(ii), _p(pack), _p(_f32(bias)),
+              _out(out, torch.float32, images * 12800, "out"), images)
+    return out
+
+
 def pqn_mlp_forward(obs, params, n_actions, q_out=None):
     N, O = obs.shape
     x, p = _f32(obs), _pqn_params(params, O, n_actions)

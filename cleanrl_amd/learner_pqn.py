@@ -25,6 +25,12 @@ Backend: ``MI355PPO_PQN=torch|fused``; the default is ``fused`` on a CUDA device
 host twins (cleanrl_amd/host_ops.py).  Both draw the reference's random stream: ``torch.randint(0, A, (N,))`` and then
 ``torch.rand((N,))`` on the CPU default generator every step, and ``np.random.shuffle`` for the minibatches, so a fused run takes
 the reference's actions for a seed as long as the greedy actions agree.
+
+Trunk of the Atari network: ``MI355PPO_PQN_TRUNK=torch|fused`` (or the ``trunk`` keyword), default ``torch``.  ``fused`` -- only with the
+Atari network, ``MI355PPO_PQN=fused`` and a HIP device, anything else is refused -- keeps the rollout frames as ``(T, N, 84, 84, 4)`` uint8
+rows (a quarter of the f32 storage's bytes; ``reset`` / ``observe`` convert the incoming ``(N, 4, 84, 84)`` uint8 frames once per step) and
+runs ``network[0:13]`` on the LayerNorm NatureCNN node of ``cleanrl_amd/ln_cnn.py`` in ``act``, ``finish_rollout`` and ``update``; the
+minibatch gather ``b_obs[mb_inds]`` rides in conv1's loader.  The head ``Linear(512, A)``, the TD loss and the random streams are unchanged.
 """
 from __future__ import annotations
 
@@ -38,8 +44,17 @@ import torch.optim as optim
 
 from . import ops
 from .flat import FlatParams
+from .learner_dqn_atari import FRAME
 
 BACKENDS = ("torch", "fused")
+TRUNKS = ("torch", "fused")
+
+
+def pqn_trunk() -> str:
+    t = os.environ.get("MI355PPO_PQN_TRUNK", "").strip().lower() or "torch"
+    if t not in TRUNKS:
+        raise ValueError(f"MI355PPO_PQN_TRUNK={t!r}: expected one of {TRUNKS}")
+    return t
 
 
 def pqn_backend(device) -> str:
@@ -58,7 +73,10 @@ def linear_schedule(start_e: float, end_e: float, duration: int, t: int):
 
 
 class PQNLearner:
-    def __init__(self, q_network: nn.Module, args, obs_shape, n_actions: int, num_envs: int, device, mlp: bool = True, backend=None):
+    def __init__(self, q_network: nn.Module, args, obs_shape, n_actions: int, num_envs: int, device, mlp: bool = True, backend=None,
+                 trunk=None, obs_space=None):
+        """``trunk``: ``"torch"`` / ``"fused"`` (None: ``MI355PPO_PQN_TRUNK``, read for the Atari network only); ``obs_space``: the env's
+        ``single_observation_space``, checked by the fused trunk (uint8 frame stacks only)."""
         self.net, self.args, self.device = q_network, args, torch.device(device)
         self.backend = pqn_backend(self.device) if backend is None else backend
         if self.backend not in BACKENDS:
@@ -72,6 +90,21 @@ class PQNLearner:
             if not (1 <= O <= ops.PQN_MAX_OBS and 1 <= self.A <= ops.PQN_MAX_ACTIONS):
                 raise ValueError(f"MI355PPO_PQN=fused: the fused QNetwork takes obs_dim <= {ops.PQN_MAX_OBS} and <= {ops.PQN_MAX_ACTIONS} "
                                  f"actions, not {O} / {self.A}; use MI355PPO_PQN=torch")
+        self.trunk = ("torch" if self.mlp else pqn_trunk()) if trunk is None else trunk
+        if self.trunk not in TRUNKS:
+            raise ValueError(f"PQN trunk {self.trunk!r}: expected one of {TRUNKS}")
+        self.fused_trunk = self.trunk == "fused"
+        self._ln = None
+        if self.fused_trunk:
+            if self.mlp:
+                raise ValueError("MI355PPO_PQN_TRUNK=fused is the LayerNorm NatureCNN of pqn_atari_envpool.py; pqn.py's MLP has no trunk")
+            if not self.fused:
+                raise ValueError(f"MI355PPO_PQN_TRUNK=fused needs MI355PPO_PQN=fused (the backend is {self.backend!r})")
+            if self.obs_shape != FRAME or (obs_space is not None and np.dtype(obs_space.dtype) != np.uint8):
+                raise ValueError(f"MI355PPO_PQN_TRUNK=fused takes {FRAME} uint8 frame stacks, not {self.obs_shape} "
+                                 f"{getattr(obs_space, 'dtype', '')}".rstrip())
+            if self.device.type != "cuda":
+                raise ValueError(f"MI355PPO_PQN_TRUNK=fused runs HIP kernels only: the device is {self.device} (use MI355PPO_PQN_TRUNK=torch)")
         if self.fused:
             self.flat = FlatParams(q_network)
             self.optimizer = None
@@ -79,7 +112,13 @@ class PQNLearner:
             self.flat = None
             self.optimizer = optim.RAdam(q_network.parameters(), lr=args.learning_rate)
         dev, T, N = self.device, self.T, self.N
-        self.obs = torch.zeros((T, N) + self.obs_shape).to(dev)
+        if self.fused_trunk:
+            from .ln_cnn import LnNatureTrunk
+
+            self._ln = LnNatureTrunk(q_network.network)             # (after FlatParams: the packs are cached by the parameters' addresses)
+            self.obs = torch.zeros((T, N, 84, 84, 4), dtype=torch.uint8, device=dev)
+        else:
+            self.obs = torch.zeros((T, N) + self.obs_shape).to(dev)
         self.actions = torch.zeros((T, N)).to(dev)
         self.rewards = torch.zeros((T, N)).to(dev)
         self.dones = torch.zeros((T, N)).to(dev)
@@ -100,8 +139,19 @@ class PQNLearner:
             self._act = torch.zeros(N, dtype=torch.int64, device=dev)
 
     # ------------------------------------------------------------------ rollout
+    def _rows(self, frames):
+        """Incoming (N, 4, 84, 84) uint8 frames -> (N, 84, 84, 4) uint8 rows on the device (the fused trunk's storage layout)."""
+        f = torch.as_tensor(np.asarray(frames) if not isinstance(frames, torch.Tensor) else frames)
+        if f.dtype != torch.uint8 or tuple(f.shape) != (self.N,) + FRAME:
+            raise ValueError(f"MI355PPO_PQN_TRUNK=fused takes ({self.N}, 4, 84, 84) uint8 frames, got {tuple(f.shape)} {f.dtype}")
+        return ops.obs_nchw_to_nhwc_u8(f.to(self.device).contiguous())
+
+    def _q(self, rows_u8, inds=None):
+        """``q_network(obs)`` on the fused trunk: ``network[0:13]`` on the kernels, the head in torch."""
+        return self.net.network[13](self._ln(rows_u8, inds, self.net.network))
+
     def reset(self, next_obs):
-        self.next_obs = torch.Tensor(next_obs).to(self.device)
+        self.next_obs = self._rows(next_obs) if self.fused_trunk else torch.Tensor(next_obs).to(self.device)
         self.next_done = torch.zeros(self.N).to(self.device)
 
     def start_iteration(self, iteration: int):
@@ -149,7 +199,7 @@ class PQNLearner:
             self.obs[step] = self.next_obs
             self.dones[step] = self.next_done
             with torch.no_grad():
-                q = self.net(self.next_obs)
+                q = self._q(self.next_obs) if self.fused_trunk else self.net(self.next_obs)
             self.g.pqn_egreedy(q, rnd, u, epsilon, self.actions[step], self.values[step], self._act)
         if force_action is not None:
             self._act.copy_(force_action.to(torch.int64))
@@ -158,7 +208,8 @@ class PQNLearner:
 
     def observe(self, step: int, next_obs, reward, next_done):
         self.rewards[step] = torch.tensor(reward).to(self.device).view(-1)
-        self.next_obs, self.next_done = torch.Tensor(next_obs).to(self.device), torch.Tensor(next_done).to(self.device)
+        self.next_obs = self._rows(next_obs) if self.fused_trunk else torch.Tensor(next_obs).to(self.device)
+        self.next_done = torch.Tensor(next_done).to(self.device)
 
     @torch.no_grad()
     def finish_rollout(self):
@@ -167,6 +218,8 @@ class PQNLearner:
         if self.fused:
             if self.mlp:
                 next_q = self.g.pqn_mlp_forward(self.next_obs, self.flat.params, self.A)
+            elif self.fused_trunk:
+                next_q = self._q(self.next_obs).contiguous()
             else:
                 next_q = self.net(self.next_obs).contiguous()
             self.returns = self.g.pqn_qlambda(self.rewards, self.dones, self.values, self.next_done, next_q, a.gamma, a.q_lambda)
@@ -189,7 +242,7 @@ class PQNLearner:
         a = self.args
         batch_size = self.T * self.N
         minibatch_size = batch_size // int(a.num_minibatches)
-        b_obs = self.obs.reshape((-1,) + self.obs_shape)
+        b_obs = self.obs.view(-1, 84, 84, 4) if self.fused_trunk else self.obs.reshape((-1,) + self.obs_shape)
         b_actions = self.actions.reshape(-1)
         b_returns = self.returns.reshape(-1)
         b_inds = np.arange(batch_size)
@@ -212,12 +265,14 @@ class PQNLearner:
                     scalars = self.g.pqn_mlp_td_fwd_bwd(b_obs.view(batch_size, -1), mb, self.flat.params, b_actions, b_returns,
                                                         self.flat.grads, self.A, scalars)
                 else:
-                    q = self.net(b_obs[mb])
+                    q = self._q(b_obs, mb) if self.fused_trunk else self.net(b_obs[mb])
                     dq, scalars = self.g.pqn_td_loss(q.detach().contiguous(), mb, b_actions, b_returns, scalars=scalars)
                     q.backward(dq)
                 self.flat.step += 1
                 self.g.clip_radam_(self.flat.params, self.flat.grads, self.flat.exp_avg, self.flat.exp_avg_sq, self.flat.step, self.lr,
                                    a.max_grad_norm)
+                if self.fused_trunk:
+                    self._ln.bufs.weights_version += 1              # the step wrote the flat buffer through raw pointers: re-derive the packs
         if not self.fused:
             return {"td_loss": loss.item(), "q_values": old_val.mean().item()}
         td_loss, q_values = scalars.tolist()

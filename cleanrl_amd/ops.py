@@ -1252,6 +1252,86 @@ def pqn_td_loss(q, mb_inds, b_actions, b_returns, dq=None, scalars=None):
     return dq, scalars
 
 
+# ---- the LayerNorm NatureCNN of pqn_atari_envpool.py (csrc/layernorm.hip; the pre-activation forwards: cleanrl_amd/ln_cnn.py)
+AMAX_WORDS = 256      # MI355PPO_AMAX_WORDS: uint32 words of an amax record (csrc/f16split.h)
+LN_MAX_D = 16384
+
+
+def _ln_dims(z, C: int, HW: int):
+    rows, D = z.shape[0], int(C) * int(HW)
+    if rows <= 0 or C <= 0 or HW <= 0 or C % 4 or D > LN_MAX_D or z.numel() != rows * D:
+        raise ValueError(f"layernorm: rows of C * HW = {C} * {HW} floats (C a multiple of 4, at most {LN_MAX_D}), got {tuple(z.shape)}")
+    return rows, D
+
+
+def layernorm_relu_fwd(z, gamma, beta, C: int, HW: int, eps: float = 1e-5, out=None, mean=None, rstd=None, bits=None, amax=None):
+    """``relu(layer_norm(z))`` over rows ``z`` (rows, ..) of C * HW floats in (H, W, C) order, ``gamma`` / ``beta`` in torch's (C, H, W)
+    order -> ``(a, mean (rows,), rstd (rows,))``.  ``bits`` (int32, ``z.numel() // 32`` words) receives ``a > 0`` in the layout of the
+    ``*_bits`` forwards, ``amax`` (one zeroed row of ``cnn.new_amax``) a's amax record."""
+    rows, D = _ln_dims(z, C, HW)
+    _chk(z, torch.float32, "z")
+    _chk(gamma, torch.float32, "gamma")
+    _chk(beta, torch.float32, "beta")
+    if gamma.numel() != D or beta.numel() != D:
+        raise ValueError(f"layernorm: gamma / beta must hold {D} floats, got {gamma.numel()} / {beta.numel()}")
+    dev = z.device
+    out = torch.empty_like(z) if out is None else _chk(out, torch.float32, "out", z.shape)
+    mean = torch.empty(rows, dtype=torch.float32, device=dev) if mean is None else _chk(mean, torch.float32, "mean", (rows,))
+    rstd = torch.empty(rows, dtype=torch.float32, device=dev) if rstd is None else _chk(rstd, torch.float32, "rstd", (rows,))
+    if bits is not None:
+        if D % 32:
+            raise ValueError(f"layernorm: mask bits need C * HW % 32 == 0, got {D}")
+        _chk(bits, torch.int32, "bits", (rows * D // 32,))
+    if amax is not None:
+        _chk(amax, torch.int32, "amax", (AMAX_WORDS,))
+    _launch("mi355ppo_layernorm_relu_fwd_f32", dev, _ptr(z), _ptr(gamma), _ptr(beta), _ptr(out), _ptr(mean), _ptr(rstd), _ptr(bits), _ptr(amax),
+            rows, int(C), int(HW), float(eps))
+    return out, mean, rstd
+
+
+def layernorm_relu_bwd(dy, z, mean, rstd, gamma, C: int, HW: int, act=None, dz=None, dgamma=None, dbeta=None, amax=None):
+    """Backward of ``layernorm_relu_fwd``: ``dy`` is the gradient at ``a`` already under the mask ``a > 0`` -- or, with ``act`` given, is
+    masked here by ``act > 0`` -> ``(dz, dgamma, dbeta)`` (the parameter gradients in torch's (C, H, W) order, overwritten; ``amax``
+    receives dz's amax record).  The same input gives the same bits on every call."""
+    rows, D = _ln_dims(z, C, HW)
+    _chk(z, torch.float32, "z")
+    _chk(dy, torch.float32, "dy", z.shape)
+    if act is not None:
+        _chk(act, torch.float32, "act", z.shape)
+    _chk(mean, torch.float32, "mean", (rows,))
+    _chk(rstd, torch.float32, "rstd", (rows,))
+    _chk(gamma, torch.float32, "gamma")
+    if gamma.numel() != D:
+        raise ValueError(f"layernorm: gamma must hold {D} floats, got {gamma.numel()}")
+    dev = z.device
+    dz = torch.empty_like(z) if dz is None else _chk(dz, torch.float32, "dz", z.shape)
+    dgamma = torch.empty_like(gamma) if dgamma is None else _chk(dgamma, torch.float32, "dgamma", gamma.shape)
+    dbeta = torch.empty_like(gamma) if dbeta is None else _chk(dbeta, torch.float32, "dbeta", gamma.shape)
+    if amax is not None:
+        _chk(amax, torch.int32, "amax", (AMAX_WORDS,))
+    ws = _workspace(dev, _lib.load().mi355ppo_layernorm_bwd_workspace_bytes(rows, int(C), int(HW)))
+    _launch("mi355ppo_layernorm_relu_bwd_f32", dev, _ptr(dy), _ptr(act), _ptr(z), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(dz), _ptr(dgamma),
+            _ptr(dbeta), _ptr(amax), rows, int(C), int(HW), _ptr(ws), ws.numel())
+    return dz, dgamma, dbeta
+
+
+def conv1q_pre_fwd(obs_u8, pack, bias, inds=None, out=None):
+    """``conv1(obs_u8[inds] / 255) + bias`` WITHOUT the ReLU on kernel Q -- the input of the network's first LayerNorm; ``pack`` = kernel Q's
+    pack of the weight (``cnn.repack_weights(W, 1, cnn.MODE_FWD_Q)``).  ``relu`` of the result is the ReLU forward's, bit for bit."""
+    _chk(obs_u8, torch.uint8, "src")
+    if tuple(obs_u8.shape[1:]) != (84, 84, 4):
+        raise ValueError(f"conv1q_pre_fwd: source rows must be (84, 84, 4) uint8, got {tuple(obs_u8.shape)}")
+    images = obs_u8.shape[0] if inds is None else inds.numel()
+    if inds is not None:
+        _chk(inds, torch.int64, "inds")
+    _chk(pack, torch.float32, "Bt", (_lib.load().mi355ppo_cnn_conv1q_pack_bytes() // 4,))
+    _chk(bias, torch.float32, "bias", (32,))
+    out = torch.empty((images, 20, 20, 32), dtype=torch.float32, device=obs_u8.device) if out is None else _chk(out, torch.float32, "out",
+                                                                                                               (images, 20, 20, 32))
+    _launch("mi355ppo_cnn_conv1q_pre_fwd", obs_u8.device, _ptr(obs_u8), _ptr(inds), _ptr(pack), _ptr(bias), _ptr(out), images)
+    return out
+
+
 def _pqn_net(obs, params, n_actions):
     N, O = obs.shape
     _chk(obs, torch.float32, "obs")

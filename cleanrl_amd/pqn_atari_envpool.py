@@ -4,7 +4,9 @@
 
 Same flags, defaults, stdout lines and scalar tags as the reference.  ``AtariQNetwork`` (cleanrl_amd/agents.py) is the reference's
 network and stays torch on every backend; with ``MI355PPO_PQN=fused`` (the default on a GPU) the library takes its ``q`` for
-e-greedy, Q(lambda) and the TD loss (``q.backward(dq)``), and clip + RAdam runs on flat buffers (csrc/pqn.hip).  Without envpool
+e-greedy, Q(lambda) and the TD loss (``q.backward(dq)``), and clip + RAdam runs on flat buffers (csrc/pqn.hip).  The opt-in
+``MI355PPO_PQN_TRUNK=fused`` (GPU, ``MI355PPO_PQN=fused``) moves ``network[0:13]`` onto the library's LayerNorm NatureCNN kernels and
+keeps the rollout frames as uint8 rows (cleanrl_amd/ln_cnn.py, cleanrl_amd/learner_pqn.py).  Without envpool
 the synthetic (N, 4, 84, 84) uint8 Atari stand-in (gym API, ``lives`` in ``info``) is used.
 """
 from __future__ import annotations
@@ -109,7 +111,7 @@ def main(argv=None):
     envs = make_envs(args)
     q_network = AtariQNetwork(envs).to(device)
     learner = PQNLearner(q_network, args, envs.single_observation_space.shape, envs.single_action_space.n, args.num_envs, device,
-                         mlp=False)
+                         mlp=False, obs_space=envs.single_observation_space)
 
     avg_returns = deque(maxlen=20)
     start_time = time.time()

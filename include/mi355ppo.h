@@ -59,6 +59,9 @@ extern "C" {
                                   PPG's auxiliary phase -- mi355ppo_ppg_* (the rollout gather, the old policy's normalised logits, the three
                                   heads with the joint loss and its backward), mi355ppo_clip_adam_split_f32 and their *_cpu twins likewise:
                                   only added, the number stays at 2.7.1;
+                                  the LayerNorm NatureCNN of pqn_atari_envpool.py -- mi355ppo_layernorm_relu_* (+ workspace size, *_cpu twins) and the
+                                  pre-activation forwards mi355ppo_cnn_conv1q_pre_fwd (+ twin), mi355ppo_cnn_conv_pre_packed_f16x2_f32,
+                                  mi355ppo_fc_pre_packed_f16x2_f32 likewise: only added, the number stays at 2.7.1;
                                   a binding must check major AND minor (cleanrl_amd/_lib.py does) */
 
 #if defined(__GNUC__)
@@ -1574,6 +1577,53 @@ MI355PPO_API int mi355ppo_ma_atari_conv1_wgrad_fold_f32(const float* dz1, const 
                                                         int64_t images, void* workspace, size_t workspace_bytes, void* stream);
 MI355PPO_API int mi355ppo_ma_atari_conv1_wgrad_fold_f32_cpu(const float* dz1, const int64_t* inds, const uint8_t* ind, const float* dW4,
                                                             float* dW6, int64_t images);
+
+/* ---- The LayerNorm NatureCNN of pqn_atari_envpool.py (added under ABI 2.7.1; csrc/layernorm.hip, csrc/conv1q.hip, csrc/gemmz.hip) ------
+ * The network is Conv -> LayerNorm -> ReLU three times, then Linear(3136, 512) -> LayerNorm(512) -> ReLU -> Linear(512, A)
+ * (cleanrl/pqn_atari_envpool.py, QNetwork).  Every forward kernel above fuses bias + ReLU; these are the same kernels WITHOUT the ReLU,
+ * a LayerNorm + ReLU kernel pair for what sits between, and nothing else: the data- and weight-gradient kernels above are used unchanged
+ * (with a = relu(LN(z)), "the gradient under the mask a > 0" is the gradient at the LayerNorm's output).
+ *
+ * pre-activation forwards: the accumulation, tile shapes and (FC) K split of the ReLU forward of the same size, so relu(z) equals that
+ * forward's result bit for bit; no mask bits, no amax record for z (only the LayerNorm reads it).
+ *   conv1q_pre_fwd: src_u8 (rows, 84, 84, 4) u8 + optional int64 gather -> dst (images, 20, 20, 32); kernel Q, pack =
+ *     mi355ppo_cnn_conv1q_pack.  Alignments of mi355ppo_cnn_conv1q_fwd.
+ *   conv_pre_packed_f16x2: layer 2 / 3, src (images, 20, 20, 32) / (images, 9, 9, 64) with its amax record -> dst (images, 9, 9, 64) /
+ *     (images, 7, 7, 64); always kernel Z; pack = the layer's f16x2 forward pack.
+ *   fc_pre_packed_f16x2: a (M, K) pitch lda with its amax record -> h (M, N) dense; workspace: mi355ppo_fc_fwd_workspace_bytes(M, N, K)
+ *     bytes, 16-byte aligned (below 8,192 rows the K split of mi355ppo_fc_fwd_relu_packed_f16x2_f32; two launches). */
+MI355PPO_API int mi355ppo_cnn_conv1q_pre_fwd(const void* src_u8, const int64_t* inds, const void* pack, const float* bias, float* dst,
+                                             int64_t images, void* stream);
+MI355PPO_API int mi355ppo_cnn_conv1q_pre_fwd_cpu(const void* src_u8, const int64_t* inds, const void* pack, const float* bias, float* dst,
+                                                 int64_t images);
+MI355PPO_API int mi355ppo_cnn_conv_pre_packed_f16x2_f32(const float* src, const void* pack, const float* bias, float* dst, int64_t images,
+                                                        int layer, const uint32_t* src_amax, void* stream);
+MI355PPO_API int mi355ppo_fc_pre_packed_f16x2_f32(const float* a, int lda, const void* pack, const float* bias, float* h, int M, int N, int K,
+                                                  void* workspace, size_t workspace_bytes, const uint32_t* a_amax, void* stream);
+/* LayerNorm + ReLU over rows of D = C * HW floats in (H, W, C) order; gamma / beta / dgamma / dbeta (D) in torch's (C, H, W) order
+ * (element p * C + c of a row <-> parameter c * HW + p; the FC layer: C = 512, HW = 1).  C % 4 == 0, D <= 16,384.
+ * forward:  mean = sum z / D, var = sum (z - mean)^2 / D (biased, two passes, double partials in an order that depends on D alone),
+ *   rstd = 1 / sqrt(var + eps), a = max((z - mean) * rstd * gamma + beta, 0).  z, a (rows, D) 16-byte aligned (may not alias); mean, rstd
+ *   (rows).  mask_bits (optional, D % 32 == 0): rows * D / 32 words, word w bit b <-> flat element 32 w + b of a -- the layout of the
+ *   *_bits forwards.  a_amax (optional): a's amax record (MI355PPO_AMAX_WORDS uint32, 64-byte aligned, zeroed by the caller).  One launch.
+ * backward: dy (rows, D) the gradient at a -- already under the mask a > 0 (what the *_dgrad_* kernels write), or, with act != NULL,
+ *   masked here by act > 0 (the FC layer, whose dh comes from the head).  With g = dy * gamma, xh = (z - mean) * rstd:
+ *     dz = rstd * ((g - mean_j g) - xh * mean_j (g * xh)),  dgamma[j] = sum_r dy * xh,  dbeta[j] = sum_r dy  (both OVERWRITTEN).
+ *   dz_amax (optional): dz's amax record.  No atomics on floats: slabs of rows write partial column sums into the workspace
+ *   (mi355ppo_layernorm_bwd_workspace_bytes(rows, C, HW) bytes, 16-byte aligned), a second launch adds them in slab order in double; the
+ *   order depends on (rows, D) alone, so the same input gives the same bits, eager or replayed from a graph.  Two launches.
+ * The twins follow the same orders and return the device's bits; they fold an amax record's value into its word 0. */
+MI355PPO_API int mi355ppo_layernorm_relu_fwd_f32(const float* z, const float* gamma, const float* beta, float* a, float* mean, float* rstd,
+                                                 uint32_t* mask_bits, uint32_t* a_amax, int64_t rows, int C, int HW, double eps, void* stream);
+MI355PPO_API int mi355ppo_layernorm_relu_fwd_f32_cpu(const float* z, const float* gamma, const float* beta, float* a, float* mean, float* rstd,
+                                                     uint32_t* mask_bits, uint32_t* a_amax, int64_t rows, int C, int HW, double eps);
+MI355PPO_API size_t mi355ppo_layernorm_bwd_workspace_bytes(int64_t rows, int C, int HW);
+MI355PPO_API int mi355ppo_layernorm_relu_bwd_f32(const float* dy, const float* act, const float* z, const float* mean, const float* rstd,
+                                                 const float* gamma, float* dz, float* dgamma, float* dbeta, uint32_t* dz_amax, int64_t rows,
+                                                 int C, int HW, void* workspace, size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_layernorm_relu_bwd_f32_cpu(const float* dy, const float* act, const float* z, const float* mean, const float* rstd,
+                                                     const float* gamma, float* dz, float* dgamma, float* dbeta, uint32_t* dz_amax,
+                                                     int64_t rows, int C, int HW);
 
 #ifdef __cplusplus
 }

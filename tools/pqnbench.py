@@ -1,10 +1,14 @@
 """Time both PQN backends (MI355PPO_PQN=torch | fused) on one GPU: one rollout step, the Q(lambda) scan, one minibatch and one
 ``update()`` of PQNLearner / LSTMPQNLearner, at each script's defaults and at a larger env count.
 
-    python tools/pqnbench.py [--reps 20] [--scripts pqn,atari,lstm] [--json out.json]
+    python tools/pqnbench.py [--reps 20] [--scripts pqn,atari,lstm,trunk] [--json out.json] [--leg-seconds 60] [--breakdown]
 
 The recurrent script (``lstm``) builds both learners in one process and times them in alternation (torch, fused, torch, ...), so
-that a drift of the machine falls on both sides.
+that a drift of the machine falls on both sides.  ``trunk`` is the Atari script's trunk axis (MI355PPO_PQN=fused with
+MI355PPO_PQN_TRUNK=torch | fused): both learners in one process, alternating, every leg (rollout step, Q(lambda), update) under its own
+time limit of ``--leg-seconds`` -- a leg that runs out stops repeating and reports the medians of what it has; the rows also carry the
+bytes of ``learner.obs``.  ``--breakdown`` adds, per env count, the synchronised median time of every library call of one fused-trunk
+minibatch (forward + backward), in call order.
 
 A rollout step here is the learner's ``act`` plus the action's copy to the host (the env is left out); ``minibatch_us`` is one
 ``update()`` (update_epochs x num_minibatches of forward + TD loss + backward + clip + RAdam, plus the shuffles) divided by its
@@ -89,6 +93,109 @@ def _alternate(fns, reps):
     return [statistics.median(t) for t in ts]
 
 
+def _alternate_limited(fns, reps, limit_s):
+    """``_alternate`` that stops repeating once the leg has used ``limit_s`` seconds (always one warm-up and one timed round)."""
+    t_leg = time.perf_counter()
+    for fn in fns:
+        fn()
+    torch.cuda.synchronize()
+    ts = [[] for _ in fns]
+    for _ in range(reps):
+        for i, fn in enumerate(fns):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts[i].append((time.perf_counter() - t0) * 1e6)
+        if time.perf_counter() - t_leg > limit_s:
+            break
+    return [statistics.median(t) for t in ts], len(ts[0])
+
+
+def _atari_learner(N, trunk, dev):
+    from cleanrl_amd.pqn_atari_envpool import Args
+
+    args = Args(num_envs=N)
+    args.batch_size = N * args.num_steps
+    args.minibatch_size = args.batch_size // args.num_minibatches
+    args.num_iterations = args.total_timesteps // args.batch_size
+    torch.manual_seed(1)
+    np.random.seed(1)
+    env = E.SyntheticAtariVecEnv(N, seed=1, api="gym")
+    obs = env.reset()
+    L = PQNLearner(AtariQNetwork(env).to(dev), args, env.single_observation_space.shape, env.single_action_space.n, N, dev, mlp=False,
+                   backend="fused", trunk=trunk, obs_space=env.single_observation_space)
+    L.reset(obs)
+    L.start_iteration(1)
+    for step in range(args.num_steps):                       # fill the storage once (random rewards / dones)
+        L.act(step)
+        L.observe(step, obs, np.random.randn(N), np.random.rand(N) < 0.02)
+    return L, args
+
+
+def bench_atari_trunks(N, reps, dev, leg_seconds):
+    """pqn_atari_envpool.py at N envs on MI355PPO_PQN=fused: the torch trunk and the fused trunk in this process, alternating ->
+    [torch-trunk row, fused-trunk row]."""
+    learners = [_atari_learner(N, trunk, dev) for trunk in ("torch", "fused")]
+    args = learners[0][1]
+    learners = [L for L, _ in learners]
+    rows = [{"script": "atari", "N": N, "backend": "fused", "trunk": L.trunk, "obs_bytes": L.obs.numel() * L.obs.element_size()} for L in learners]
+    for key, fns, r in (("rollout_step_us", [lambda L=L: L.act(1).cpu() for L in learners], reps),
+                        ("qlambda_us", [L.finish_rollout for L in learners], reps),
+                        ("update_us", [L.update for L in learners], max(3, reps // 4))):
+        meds, n = _alternate_limited(fns, r, leg_seconds)
+        for row, t in zip(rows, meds):
+            row[key] = t
+            row[key[:-3] + "_reps"] = n
+    for row in rows:
+        row["minibatch_us"] = row["update_us"] / (args.update_epochs * args.num_minibatches)
+        row["batch"], row["minibatch_rows"] = args.batch_size, args.minibatch_size
+    return rows, learners[1], args
+
+
+def trunk_breakdown(L, args, reps):
+    """The library calls of ONE fused-trunk minibatch (forward, TD loss, backward) of learner ``L``, each synchronised and timed: ->
+    [(call, median us)] in call order.  The calls are timed in place of the node's own bindings, which are restored afterwards."""
+    from cleanrl_amd import cnn, ln_cnn
+
+    spots = [(ln_cnn, n) for n in ("conv1q_pre_fwd", "layernorm_relu_fwd", "conv_pre_packed", "fc_pre", "layernorm_relu_bwd")] + \
+            [(cnn, n) for n in ("fc_wgrad", "fc_dgrad_mask_packed", "conv_wgrad", "conv_dgrad_packed")]
+    log = []
+
+    def timed(name, fn):
+        def call(*a, **k):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn(*a, **k)
+            torch.cuda.synchronize()
+            log.append((name, (time.perf_counter() - t0) * 1e6))
+            return out
+        return call
+
+    mb = torch.randperm(args.batch_size)[:args.minibatch_size].to(L.device)
+    b_obs = L.obs.view(-1, 84, 84, 4)
+
+    def minibatch():
+        q = L._q(b_obs, mb)
+        dq, _ = L.g.pqn_td_loss(q.detach().contiguous(), mb, L.actions.reshape(-1), L.returns.reshape(-1))
+        q.backward(dq)
+        L.flat.grads.zero_()
+
+    minibatch()
+    saved = [(m, n, getattr(m, n)) for m, n in spots]
+    try:
+        for m, n, fn in saved:
+            setattr(m, n, timed(n, fn))
+        runs = []
+        for _ in range(reps):
+            log.clear()
+            minibatch()
+            runs.append(list(log))
+    finally:
+        for m, n, fn in saved:
+            setattr(m, n, fn)
+    return [(runs[0][i][0], statistics.median(r[i][1] for r in runs)) for i in range(len(runs[0]))]
+
+
 def bench_lstm(N, reps, dev):
     """pqn_atari_envpool_lstm.py at N envs: both backends in this process, alternating -> [torch row, fused row]."""
     from cleanrl_amd.pqn_atari_envpool_lstm import Args
@@ -128,6 +235,8 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--scripts", default="pqn,atari,lstm")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--leg-seconds", type=float, default=60.0, help="time limit of each leg of the trunk axis")
+    ap.add_argument("--breakdown", action="store_true", help="trunk axis: also time every library call of one fused-trunk minibatch")
     a = ap.parse_args()
     dev = torch.device("cuda")
     rows = []
@@ -143,6 +252,19 @@ def main():
                 r = bench(script, N, backend, a.reps, dev)
                 rows.append(r)
                 show(r)
+    if "trunk" in scripts:
+        for N in (8, 128):
+            trunk_rows, fused_learner, targs = bench_atari_trunks(N, a.reps, dev, a.leg_seconds)
+            for r in trunk_rows:
+                rows.append(r)
+                show(r)
+            if a.breakdown:
+                r = {"script": "atari", "N": N, "trunk": "fused", "minibatch_rows": targs.minibatch_size,
+                     "calls_us": [[n, round(t, 1)] for n, t in trunk_breakdown(fused_learner, targs, max(3, a.reps // 2))]}
+                rows.append(r)
+                show(r)
+            del trunk_rows, fused_learner
+            torch.cuda.empty_cache()
     if "lstm" in scripts:
         for N in (8, 64):
             for r in bench_lstm(N, a.reps, dev):
