@@ -339,6 +339,14 @@ SIGNATURES = {
     "mi355ppo_layernorm_bwd_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "mi355ppo_layernorm_relu_bwd_f32": (c_int, [_P] * 10 + [c_int64, c_int, c_int, _P, c_size_t, _P]),
     "mi355ppo_layernorm_relu_bwd_f32_cpu": (c_int, [_P] * 10 + [c_int64, c_int, c_int]),
+    # the same network on one frame: pqn_atari_envpool_lstm (added under ABI 2.7.1, csrc/conv1q1.hip, csrc/conv1p1.hip)
+    "mi355ppo_cnn_conv1q1_pack_bytes": (c_size_t, []),
+    "mi355ppo_cnn_conv1q1_pack": (c_int, [_P, _P, _P]),
+    "mi355ppo_cnn_conv1q1_pack_cpu": (c_int, [_P, _P]),
+    "mi355ppo_cnn_conv1q1_pre_fwd": (c_int, [_P] * 5 + [c_int64, _P]),
+    "mi355ppo_cnn_conv1q1_pre_fwd_cpu": (c_int, [_P] * 5 + [c_int64]),
+    "mi355ppo_cnn_conv1p1_wgrad_workspace_bytes": (c_size_t, [c_int64]),
+    "mi355ppo_cnn_conv1p1_wgrad_f16x2": (c_int, [_P, _P, _P, _P, _P, c_int64, _P, c_size_t, _P, _P]),
 }
 
 ABI_VERSION = 271       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)

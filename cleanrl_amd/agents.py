@@ -1207,7 +1207,9 @@ class AtariLSTMQNetwork(nn.Module):
     torch seed gives the reference's weights.  ``forward`` / ``get_states`` are the reference's per-step loop (the ``torch``
     backend).  The fused backend of ``LSTMPQNLearner`` uses the seams below: ``gates`` (trunk + the gx GEMM, both torch) and
     ``states_fused`` (``ops.lstm_seq``: all T steps in one scan, HIP kernels on the GPU and their host twins on the CPU); the cell of
-    a rollout step, ``q_func``, e-greedy and the TD loss run in csrc/pqn_lstm.hip on this module's parameters."""
+    a rollout step, ``q_func``, e-greedy and the TD loss run in csrc/pqn_lstm.hip on this module's parameters.  With
+    ``MI355PPO_PQN_TRUNK=fused`` the learner takes ``gates_fused`` / ``states_from_gates`` instead: the same two with ``network`` on the
+    kernels of ``ln_cnn`` (uint8 frames, the one-frame conv1 of csrc/conv1q1.hip / conv1p1.hip)."""
 
     def __init__(self, env):
         super().__init__()
@@ -1268,6 +1270,19 @@ class AtariLSTMQNetwork(nn.Module):
         act kernel take it."""
         lstm = self.lstm
         return nn.functional.linear(self.network(x / 255.0), lstm.weight_ih_l0, lstm.bias_ih_l0 + lstm.bias_hh_l0)
+
+    def gates_fused(self, trunk, rows_u8, inds=None):
+        """``gates`` with ``network`` on the LayerNorm NatureCNN node (``ln_cnn.LnNatureTrunk``): ``rows_u8`` (R, 84, 84) uint8 frames,
+        ``inds`` an optional int64 row gather that rides in conv1's loader; the ``/ 255`` is the kernel's."""
+        lstm = self.lstm
+        return nn.functional.linear(trunk(rows_u8, inds, self.network), lstm.weight_ih_l0, lstm.bias_ih_l0 + lstm.bias_hh_l0)
+
+    def states_from_gates(self, gx, lstm_state, done):
+        """``states_fused`` behind the gx GEMM: ``gx`` (T*B, 4H) time-major."""
+        batch_size, H = lstm_state[0].shape[1], self.lstm.hidden_size
+        h, hT, cT = ops.lstm_seq(gx.reshape(-1, batch_size, 4 * H), self.lstm.weight_hh_l0, lstm_state[0][0], lstm_state[1][0],
+                                 done.reshape(-1, batch_size))
+        return h.reshape(-1, H), (hT.unsqueeze(0), cT.unsqueeze(0))
 
     def states_fused(self, x, lstm_state, done):
         """``get_states`` as one scan over the T time-major steps of the B envs of ``lstm_state`` -> (h (T*B, H), new state)."""

@@ -632,9 +632,10 @@ class _Buffers:
 
     def _pack_keys(self):
         W1, W2, W3, Wfc = self.pack_params
-        return [((1, MODE_FWD_Q), W1, None), (("zpack", 2, MODE_FWD), W2, (64, 512)), (("zpack", 3, MODE_FWD), W3, (64, 576)),
-                (("zpack", 3, MODE_DGRAD_S1), W3, (64, 576)), (("zpack", 2, MODE_DGRAD_S2), W2, (128, 256)),
-                ("fc_pack_fwd", Wfc, (512, 3136)), ("fc_pack_dgrad", Wfc, (3136, 512))]
+        q = [] if W1.shape[1] == 1 else [((1, MODE_FWD_Q), W1, None)]     # (one frame: kernel Q1's pack is ln_cnn.LnNatureTrunk's own launch)
+        return q + [(("zpack", 2, MODE_FWD), W2, (64, 512)), (("zpack", 3, MODE_FWD), W3, (64, 576)),
+                    (("zpack", 3, MODE_DGRAD_S1), W3, (64, 576)), (("zpack", 2, MODE_DGRAD_S2), W2, (128, 256)),
+                    ("fc_pack_fwd", Wfc, (512, 3136)), ("fc_pack_dgrad", Wfc, (3136, 512))]
 
     def _repack_all(self, key, W) -> bool:
         """Rebuild every cached pack in one launch when ``key`` (stale) is one of them and ``W`` its parameter.  -> done?"""
@@ -658,7 +659,9 @@ class _Buffers:
             outs.append(buf)
         W1, W2, W3, Wfc = (w.detach() for w in self.pack_params)
         ma = W1.shape[1] == 6          # ppo_pettingzoo_ma_atari's conv1: the all-packs launch skips kernel Q's piece, ma_conv1_pack reads W1 in place
-        q_args = (None, _ptr(W2), _ptr(W3), _ptr(Wfc), None, *[_ptr(o) for o in outs[1:]]) if ma else (_ptr(W1), _ptr(W2), _ptr(W3), _ptr(Wfc), *[_ptr(o) for o in outs])
+        one = W1.shape[1] == 1         # pqn_atari_envpool_lstm's one-frame conv1: no kernel Q pack among the keys, the launch skips that piece likewise
+        q_args = ((None, _ptr(W2), _ptr(W3), _ptr(Wfc), None, *[_ptr(o) for o in (outs if one else outs[1:])]) if ma or one
+                  else (_ptr(W1), _ptr(W2), _ptr(W3), _ptr(Wfc), *[_ptr(o) for o in outs]))
         if f16:
             if self.w_amax is None:
                 self.w_amax = new_amax(3, dev)

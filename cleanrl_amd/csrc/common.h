@@ -36,6 +36,9 @@ void set_error(const char* fmt, ...);
 // kernel P (conv1p.hip): layer-1 weight gradient on the bf16 matrix pipe; one partial per wave (conv.hip reduces them)
 int conv1p_launch(const unsigned char* src, const int64_t* inds, const float* dz, float* part_w, float* part_b, int images, int grid,
                   hipStream_t s, const unsigned* dz_amax, float* partial_scale);
+// kernel P1 (conv1p1.hip): the same gradient of Conv2d(1, 32, 8, stride=4) on one-channel frames, f16 split of dz; one (32 x 64) partial per wave
+int conv1p1_launch(const unsigned char* src, const int64_t* inds, const float* dz, float* part_w, float* part_b, int images, int grid,
+                   hipStream_t s, const unsigned* dz_amax);
 // kernel V (convw.hip): layers 2 / 3 weight + bias gradient on the bf16 pipe; returns 1 when the batch does not qualify
 bool convw_applies(int64_t images, int layer, bool f16 = false);      // (f16: the two-tile shape of the f16 split -- 227 instead of 170 slabs on layer 3)
 int convw_parts(int64_t images, int layer);

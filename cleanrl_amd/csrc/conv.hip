@@ -1318,3 +1318,48 @@ extern "C" MI355PPO_API int mi355ppo_cnn_conv1_wgrad_f16x2(const void* src_u8, c
     MI355_REQUIRE(dz_amax && aligned(dz_amax, 64), MI355PPO_EINVAL, "%s: dz's amax record missing or not 64-byte aligned", fn);
     return conv_wgrad_impl(fn, src_u8, inds, dz, dW, db, images, 1, workspace, workspace_bytes, nullptr, dz_amax, stream);
 }
+
+// Kernel P1 (conv1p1.hip): the weight + bias gradient of Conv2d(1, 32, 8, stride=4) on one-channel uint8 frames (pqn_atari_envpool_lstm.py's conv1), dz in
+// two f16 terms under its amax record.  One partial per wave of min(images, 512) workgroups, folded by the reductions above in their fixed order.
+static int wgrad1c_grid(int64_t images) { return images < 512 ? (int)images : 512; }
+
+extern "C" MI355PPO_API size_t mi355ppo_cnn_conv1p1_wgrad_workspace_bytes(int64_t images) {
+    if (images <= 0) return 0;
+    const size_t wparts = (size_t)wgrad1c_grid(images) * 4;
+    const size_t nchunks = (wparts + kRedChunk - 1) / kRedChunk;
+    return ((wparts + nchunks) * (size_t)(32 * 64) + (wparts + nchunks) * 32) * sizeof(float);
+}
+
+extern "C" MI355PPO_API int mi355ppo_cnn_conv1p1_wgrad_f16x2(const void* src_u8, const int64_t* inds, const float* dz, float* dW, float* db,
+                                                             int64_t images, void* workspace, size_t workspace_bytes, const uint32_t* dz_amax,
+                                                             void* stream) {
+    const char* fn = "mi355ppo_cnn_conv1p1_wgrad_f16x2";
+    MI355_REQUIRE(src_u8 && dz && dW && db, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(dz_amax && aligned(dz_amax, 64), MI355PPO_EINVAL, "%s: dz's amax record missing or not 64-byte aligned", fn);
+    MI355_REQUIRE(images > 0 && images <= (1 << 22), MI355PPO_EINVAL, "%s: images=%lld out of range (1..4194304)", fn, (long long)images);
+    const size_t need = mi355ppo_cnn_conv1p1_wgrad_workspace_bytes(images);
+    MI355_REQUIRE(workspace && workspace_bytes >= need, MI355PPO_EWORKSPACE, "%s: workspace %zu bytes < required %zu", fn,
+                  workspace ? workspace_bytes : (size_t)0, need);
+    MI355_REQUIRE(aligned(src_u8, 4) && aligned(dz, 16) && aligned(dW, 4) && aligned(db, 4) && aligned(workspace, 16) && aligned(inds, 8),
+                  MI355PPO_EALIGN, "%s: src must be 4-byte aligned, dz/workspace 16-byte aligned", fn);
+    // Workspace layout: part_w [parts][2048] | part_b [parts][32] | mid [ceil(parts/32)][2048] | mid_b [ceil(parts/32)][32]
+    const int grid = wgrad1c_grid(images), wparts = grid * 4, total_w = 32 * 64;
+    const int nchunks = (wparts + kRedChunk - 1) / kRedChunk;
+    float* part_w = static_cast<float*>(workspace);
+    float* part_b = part_w + (size_t)wparts * total_w;
+    float* mid = part_b + (size_t)wparts * 32;
+    float* mid_b = mid + (size_t)nchunks * total_w;
+    hipStream_t s = as_stream(stream);
+    int rc = conv1p1_launch(static_cast<const unsigned char*>(src_u8), inds, dz, part_w, part_b, (int)images, grid, s, dz_amax);
+    if (rc) return rc;
+    if (nchunks <= 8) {                // both stages in one launch, the same additions in the same order (as layer 1 of the four-frame network)
+        hipLaunchKernelGGL(conv_wgrad_reduce12, dim3(total_w / 32 + 1), dim3(256), 0, s, part_w, wparts, total_w, part_b, 32, 1, 8, 8, kInv255, dW, db);
+        return check_launch("conv_wgrad_reduce12");
+    }
+    hipLaunchKernelGGL(conv_wgrad_reduce1, dim3((total_w + 255) / 256 + 1, nchunks), dim3(256), 0, s, part_w, wparts, total_w, mid, part_b, wparts, 32,
+                       mid_b);
+    rc = check_launch("conv_wgrad_reduce1");
+    if (rc) return rc;
+    hipLaunchKernelGGL(conv_wgrad_reduce2, dim3((total_w + 255) / 256), dim3(256), 0, s, mid, nchunks, mid_b, nchunks, 32, 1, 8, 8, kInv255, dW, db);
+    return check_launch("conv_wgrad_reduce2");
+}

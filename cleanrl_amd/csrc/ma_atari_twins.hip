@@ -3,6 +3,7 @@
 // of its own (as ppg_twins.hip), so that tools/ma_atari_host_check.cpp builds it stand-alone for the sanitizers.  Serial.
 #include "common.h"
 #include "conv1q_pack.h"
+#include "conv1q1_pack.h"
 #include "ma_atari_rows.h"
 
 #include <math.h>
@@ -84,7 +85,71 @@ int q_fwd_host(const char* fn, const uint8_t* src, const int64_t* inds, const ui
     return MI355PPO_OK;
 }
 
+// conv1q1_pack_body, serial: W (32, 1, 8, 8) -> kernel Q1's pack (conv1q1_pack.h's element functions)
+void q1_pack_host(const float* W, unsigned char* pack) {
+    for (int n = 0; n < 32; ++n) {
+        float m = 0.0f;
+        for (int t = 0; t < 64; ++t) m = fmaxf(m, fabsf(W[n * 64 + t]));
+        const int E = q1_exp(m);
+        int sums[kQDigits] = {0, 0, 0, 0};
+        for (int r = 0; r < 8; ++r)
+            for (int kw = 0; kw < 8; ++kw) {
+                int dig[kQDigits];
+                q1_digits(W[(n * 8 + r) * 8 + kw], E, dig);
+                for (int d = 0; d < kQDigits; ++d) {
+                    pack[q1_pack_index(n, r, kw, d)] = (unsigned char)(signed char)dig[d];
+                    sums[d] += dig[d];
+                }
+            }
+        for (int d = 0; d < kQDigits; ++d) {
+            const int v = 128 * sums[d];
+            memcpy(pack + kQ1AccOff + (d * 32 + n) * 4, &v, 4);
+        }
+        const float sc = q1_scale(E);
+        memcpy(pack + kQ1ScaleOff + n * 4, &sc, 4);
+    }
+}
+
+// kernel Q1, serial: exact integer dot products of the frame's bytes with the pack's digits, then kernel Q's pre-activation epilogue
+int q1_pre_fwd_host(const char* fn, const uint8_t* src, const int64_t* inds, const unsigned char* pack, const float* bias, float* dst,
+                    int64_t images) {
+    MI355_REQUIRE(src && pack && bias && dst, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(images > 0, MI355PPO_EINVAL, "%s: images=%lld must be positive", fn, (long long)images);
+    const signed char* dig = reinterpret_cast<const signed char*>(pack);
+    for (int64_t img = 0; img < images; ++img) {
+        const int64_t row = inds ? inds[img] : img;
+        const uint8_t* frame = src + (size_t)row * kQ1Img;
+        for (int p = 0; p < kQPerImg; ++p) {
+            const int gy = p / kQG, gx = p - gy * kQG;
+            for (int n = 0; n < 32; ++n) {
+                int D[kQDigits] = {0, 0, 0, 0};
+                for (int r = 0; r < 8; ++r) {
+                    const uint8_t* taps = frame + (size_t)(gy * 4 + r) * kQ1Pitch + gx * 4;
+                    for (int kw = 0; kw < 8; ++kw)
+                        for (int d = 0; d < kQDigits; ++d) D[d] += (int)taps[kw] * (int)dig[q1_pack_index(n, r, kw, d)];
+                }
+                float sc;
+                memcpy(&sc, pack + kQ1ScaleOff + n * 4, 4);
+                dst[((size_t)img * kQPerImg + p) * 32 + n] = ma_q_finish_pre(D, sc, bias[n]);
+            }
+        }
+    }
+    return MI355PPO_OK;
+}
+
 }  // namespace
+
+extern "C" MI355PPO_API int mi355ppo_cnn_conv1q1_pack_cpu(const float* W, void* pack) {
+    MI355_REQUIRE(W && pack, MI355PPO_EINVAL, "mi355ppo_cnn_conv1q1_pack_cpu: null pointer");
+    q1_pack_host(W, static_cast<unsigned char*>(pack));
+    return MI355PPO_OK;
+}
+
+extern "C" MI355PPO_API int mi355ppo_cnn_conv1q1_pre_fwd_cpu(const void* src_u8, const int64_t* inds, const void* pack, const float* bias,
+                                                             float* dst, int64_t images) {
+    return q1_pre_fwd_host("mi355ppo_cnn_conv1q1_pre_fwd_cpu", static_cast<const uint8_t*>(src_u8), inds, static_cast<const unsigned char*>(pack),
+                           bias, dst, images);
+}
 
 extern "C" MI355PPO_API int mi355ppo_ma_atari_split_u8_cpu(const uint8_t* frames6, uint8_t* rows4, uint8_t* ind, uint32_t* flag, int64_t frames) {
     const char* fn = "mi355ppo_ma_atari_split_u8_cpu";

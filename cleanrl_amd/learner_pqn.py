@@ -73,6 +73,10 @@ def linear_schedule(start_e: float, end_e: float, duration: int, t: int):
 
 
 class PQNLearner:
+    # the fused trunk's observation shape and its storage rows: pqn_atari_envpool.py's four-frame stacks (LSTMPQNLearner: one frame)
+    TRUNK_FRAME = FRAME
+    TRUNK_ROWS = (84, 84, 4)
+
     def __init__(self, q_network: nn.Module, args, obs_shape, n_actions: int, num_envs: int, device, mlp: bool = True, backend=None,
                  trunk=None, obs_space=None):
         """``trunk``: ``"torch"`` / ``"fused"`` (None: ``MI355PPO_PQN_TRUNK``, read for the Atari network only); ``obs_space``: the env's
@@ -100,8 +104,8 @@ class PQNLearner:
                 raise ValueError("MI355PPO_PQN_TRUNK=fused is the LayerNorm NatureCNN of pqn_atari_envpool.py; pqn.py's MLP has no trunk")
             if not self.fused:
                 raise ValueError(f"MI355PPO_PQN_TRUNK=fused needs MI355PPO_PQN=fused (the backend is {self.backend!r})")
-            if self.obs_shape != FRAME or (obs_space is not None and np.dtype(obs_space.dtype) != np.uint8):
-                raise ValueError(f"MI355PPO_PQN_TRUNK=fused takes {FRAME} uint8 frame stacks, not {self.obs_shape} "
+            if self.obs_shape != self.TRUNK_FRAME or (obs_space is not None and np.dtype(obs_space.dtype) != np.uint8):
+                raise ValueError(f"MI355PPO_PQN_TRUNK=fused takes {self.TRUNK_FRAME} uint8 frame stacks, not {self.obs_shape} "
                                  f"{getattr(obs_space, 'dtype', '')}".rstrip())
             if self.device.type != "cuda":
                 raise ValueError(f"MI355PPO_PQN_TRUNK=fused runs HIP kernels only: the device is {self.device} (use MI355PPO_PQN_TRUNK=torch)")
@@ -116,7 +120,7 @@ class PQNLearner:
             from .ln_cnn import LnNatureTrunk
 
             self._ln = LnNatureTrunk(q_network.network)             # (after FlatParams: the packs are cached by the parameters' addresses)
-            self.obs = torch.zeros((T, N, 84, 84, 4), dtype=torch.uint8, device=dev)
+            self.obs = torch.zeros((T, N) + self.TRUNK_ROWS, dtype=torch.uint8, device=dev)
         else:
             self.obs = torch.zeros((T, N) + self.obs_shape).to(dev)
         self.actions = torch.zeros((T, N)).to(dev)

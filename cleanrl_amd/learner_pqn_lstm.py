@@ -24,6 +24,13 @@ state per env, ``mse_loss``, ``backward``,             (one scan forward, one ba
 Backend: ``MI355PPO_PQN=torch|fused`` alone, as for the other PQN scripts (``fused`` on a CUDA device by default, ``torch`` on the
 CPU, where ``fused`` runs the host twins); ``MI355PPO_LSTM`` is not read here.  Both backends draw the reference's random stream:
 ``torch.randint`` then ``torch.rand`` on the CPU generator every step, ``np.random.shuffle(envinds)`` every epoch.
+
+Trunk: ``MI355PPO_PQN_TRUNK=torch|fused`` (or the ``trunk`` keyword), default ``torch``, read as ``PQNLearner`` reads it.  ``fused`` -- only
+with ``MI355PPO_PQN=fused``, a HIP device and ``(1, 84, 84)`` uint8 observations -- keeps the rollout frames as ``(T, N, 84, 84)`` uint8 (a
+quarter of the f32 storage's bytes; ``reset`` / ``observe`` copy the incoming bytes, no conversion) and runs ``network`` on the LayerNorm
+NatureCNN node of ``cleanrl_amd/ln_cnn.py`` with the one-frame conv1 kernels (csrc/conv1q1.hip, csrc/conv1p1.hip) in ``act``,
+``finish_rollout`` and ``update``: gx = ``AtariLSTMQNetwork.gates_fused``, the time-major ``mb_inds`` gather rides in conv1's loader.  The LSTM
+scan, the act kernel, the TD kernel, clip + RAdam and the random streams are the same calls.
 """
 from __future__ import annotations
 
@@ -37,8 +44,11 @@ from .learner_pqn import PQNLearner
 
 
 class LSTMPQNLearner(PQNLearner):
-    def __init__(self, q_network: nn.Module, args, obs_shape, n_actions: int, num_envs: int, device, backend=None):
-        super().__init__(q_network, args, obs_shape, n_actions, num_envs, device, mlp=False, backend=backend)
+    TRUNK_FRAME = (1, 84, 84)
+    TRUNK_ROWS = (84, 84)            # (N, 1, 84, 84) and (N, 84, 84, 1) are the same bytes: no transposition
+
+    def __init__(self, q_network: nn.Module, args, obs_shape, n_actions: int, num_envs: int, device, backend=None, trunk=None, obs_space=None):
+        super().__init__(q_network, args, obs_shape, n_actions, num_envs, device, mlp=False, backend=backend, trunk=trunk, obs_space=obs_space)
         assert self.N % int(args.num_minibatches) == 0
         if self.fused and not (q_network.lstm.hidden_size == 128 and 1 <= self.A <= ops.PQN_MAX_ACTIONS):
             raise ValueError(f"MI355PPO_PQN=fused: the recurrent Q head takes LSTM(512, 128) and <= {ops.PQN_MAX_ACTIONS} actions, not "
@@ -49,6 +59,19 @@ class LSTMPQNLearner(PQNLearner):
             self._next_q = torch.zeros((self.N, self.A), dtype=torch.float32, device=self.device)
 
     # ------------------------------------------------------------------ rollout
+    def _rows(self, frames):
+        """Incoming (N, 1, 84, 84) uint8 frames -> (N, 84, 84) uint8 rows on the device: the same bytes, copied."""
+        f = torch.as_tensor(np.asarray(frames) if not isinstance(frames, torch.Tensor) else frames)
+        if f.dtype != torch.uint8 or tuple(f.shape) != (self.N,) + self.TRUNK_FRAME:
+            raise ValueError(f"MI355PPO_PQN_TRUNK=fused takes ({self.N}, 1, 84, 84) uint8 frames, got {tuple(f.shape)} {f.dtype}")
+        return f.to(self.device).contiguous().view(self.N, 84, 84)
+
+    def _gates(self, obs, inds=None):
+        """gx of ``obs`` (of ``obs[inds]``): the fused trunk on the uint8 rows, or the torch trunk on the f32 frames."""
+        if self.fused_trunk:
+            return self.net.gates_fused(self._ln, obs, inds)
+        return self.net.gates(obs if inds is None else obs[inds])
+
     def act(self, step: int, force_action=None):
         """One step's action logic with the recurrent state; see ``PQNLearner.act`` for ``force_action``."""
         if step == 0:
@@ -79,7 +102,7 @@ class LSTMPQNLearner(PQNLearner):
         self.obs[step] = self.next_obs
         net = self.net
         with torch.no_grad():
-            gx = net.gates(self.next_obs)
+            gx = self._gates(self.next_obs)
         h, c = self.next_lstm_state[0][0], self.next_lstm_state[1][0]         # (N, H) views: the state is advanced in place
         self.g.pqn_lstm_act(gx, net.lstm.weight_hh_l0.detach(), h, c, self.next_done, net.q_func.weight.detach(), net.q_func.bias.detach(),
                             rnd, u, epsilon, h_out=h, c_out=c, actions_out=self.actions[step], values_out=self.values[step],
@@ -95,7 +118,7 @@ class LSTMPQNLearner(PQNLearner):
         a, net = self.args, self.net
         if self.fused:
             h, c = self.next_lstm_state[0][0], self.next_lstm_state[1][0]
-            self.g.pqn_lstm_act(net.gates(self.next_obs), net.lstm.weight_hh_l0, h, c, self.next_done, net.q_func.weight, net.q_func.bias,
+            self.g.pqn_lstm_act(self._gates(self.next_obs), net.lstm.weight_hh_l0, h, c, self.next_done, net.q_func.weight, net.q_func.bias,
                                 q_out=self._next_q)
             self.returns = self.g.pqn_qlambda(self.rewards, self.dones, self.values, self.next_done, self._next_q, a.gamma, a.q_lambda)
             return self.returns
@@ -116,7 +139,7 @@ class LSTMPQNLearner(PQNLearner):
     def update(self):
         a, net = self.args, self.net
         batch_size = self.T * self.N
-        b_obs = self.obs.reshape((-1,) + self.obs_shape)
+        b_obs = self.obs.view(-1, 84, 84) if self.fused_trunk else self.obs.reshape((-1,) + self.obs_shape)
         b_actions = self.actions.reshape(-1)
         b_returns = self.returns.reshape(-1)
         b_dones = self.dones.reshape(-1)
@@ -142,7 +165,10 @@ class LSTMPQNLearner(PQNLearner):
                     continue
                 mb = torch.from_numpy(mb_inds).to(self.device)
                 env = torch.from_numpy(mbenvinds).to(self.device)
-                h, _ = net.states_fused(b_obs[mb], (initial[0][:, env], initial[1][:, env]), b_dones[mb])
+                if self.fused_trunk:
+                    h, _ = net.states_from_gates(self._gates(b_obs, mb), (initial[0][:, env], initial[1][:, env]), b_dones[mb])
+                else:
+                    h, _ = net.states_fused(b_obs[mb], (initial[0][:, env], initial[1][:, env]), b_dones[mb])
                 dh, scalars = self.g.pqn_lstm_td_fwd_bwd(h.detach(), mb, b_actions, b_returns, net.q_func.weight.detach(),
                                                          net.q_func.bias.detach(), net.q_func.weight.grad, net.q_func.bias.grad,
                                                          scalars=scalars)
@@ -150,6 +176,8 @@ class LSTMPQNLearner(PQNLearner):
                 self.flat.step += 1
                 self.g.clip_radam_(self.flat.params, self.flat.grads, self.flat.exp_avg, self.flat.exp_avg_sq, self.flat.step, self.lr,
                                    a.max_grad_norm)
+                if self.fused_trunk:
+                    self._ln.bufs.weights_version += 1              # the step wrote the flat buffer through raw pointers: re-derive the packs
         if not self.fused:
             return {"td_loss": loss.item(), "q_values": old_val.mean().item()}
         td_loss, q_values = scalars.tolist()

@@ -9,6 +9,10 @@ chain is LN backward -> ``cnn.conv_wgrad`` / ``cnn.fc_wgrad`` -> ``cnn.conv_dgra
 kernels exactly as ``cnn.NatureTrunkFn.backward`` / ``cnn.LinearReLUHwcFn.backward`` use them.  The minibatch gather ``b_obs[mb_inds]``
 and ``x / 255.0`` ride in kernel Q's loader.  The head ``Linear(512, A)`` stays torch.
 
+The frame count comes from ``network[0].weight.shape[1]``: 4 (pqn_atari_envpool.py, rows (84, 84, 4)) or 1 (pqn_atari_envpool_lstm.py, rows
+(84, 84) -- ``(N, 1, 84, 84)`` and ``(N, 84, 84, 1)`` are the same bytes).  With one channel conv1's forward, pack and weight gradient are
+kernels Q1 / P1 (csrc/conv1q1.hip, csrc/conv1p1.hip); everything from the first LayerNorm on is the same code.
+
 f16x2 split only: with ``MI355PPO_SPLIT=bf16x3``, ``MI355PPO_CONV=f`` or tensors beyond ``cnn.BUF_LIMIT`` the node raises
 ``NotImplementedError`` -- there is no fallback.
 """
@@ -19,7 +23,7 @@ import torch
 from . import _lib, cnn
 from .cnn import (BUF_LIMIT, MODE_DGRAD_S1, MODE_DGRAD_S2, MODE_FWD, MODE_FWD_Q, REC_A1, REC_A2, REC_A3, REC_DH, REC_DZ1, REC_DZ2, REC_DZ3,
                   _rec, _row_major)
-from .ops import _chk, _launch, _ptr, _workspace, conv1q_pre_fwd, layernorm_relu_bwd, layernorm_relu_fwd
+from .ops import _chk, _launch, _ptr, _workspace, conv1p1_wgrad, conv1q1_pack, conv1q1_pre_fwd, conv1q_pre_fwd, layernorm_relu_bwd, layernorm_relu_fwd
 
 LN_EPS = 1e-5                 # nn.LayerNorm's default
 # (C, HW) of the four LayerNorms: conv1 (20 x 20 x 32), conv2 (9 x 9 x 64), conv3 (7 x 7 x 64), Linear (512)
@@ -91,7 +95,10 @@ class LnNatureFn(torch.autograd.Function):
         rec = bufs.begin_pass(m, dev)         # one fill zeroes the records of this forward and of the backward that may follow
         grads = bool(want_grads)
         mb1, mb2, mb3 = bufs.get_bits(m, dev) if grads else (None, None, None)
-        conv1q_pre_fwd(obs_u8, bufs.weights(W1, 1, MODE_FWD_Q), b1.detach(), inds, z1)
+        if W1.shape[1] == 1:
+            conv1q1_pre_fwd(obs_u8, trunk.q1_pack(W1), b1.detach(), inds, z1)
+        else:
+            conv1q_pre_fwd(obs_u8, bufs.weights(W1, 1, MODE_FWD_Q), b1.detach(), inds, z1)
         layernorm_relu_fwd(z1, g1.detach(), e1.detach(), 32, 400, LN_EPS, a1, stats[0], stats[1], mb1, bufs.owns(REC_A1, a1))
         conv_pre_packed(a1, bufs.conv_zpack(W2, 2, MODE_FWD), b2.detach(), 2, rec[REC_A1], z2)
         layernorm_relu_fwd(z2, g2.detach(), e2.detach(), 64, 81, LN_EPS, a2, stats[2], stats[3], mb2, bufs.owns(REC_A2, a2))
@@ -137,7 +144,10 @@ class LnNatureFn(torch.autograd.Function):
         cnn.conv_dgrad_packed(dz2, bufs.conv_zpack(W2, 2, MODE_DGRAD_S2), a1, 2, dy1, bits=mb1, amax=(r2, None))
         # layer 1 (kernel P, dz in two f16 terms; the uint8 frames are exact)
         _, dg1, de1 = layernorm_relu_bwd(dy1, z1, stats[0], stats[1], g1.detach(), 32, 400, dz=dz1, amax=bufs.owns(REC_DZ1, dz1))
-        dW1, db1 = cnn.conv_wgrad(ctx.obs, dz1, 1, ctx.inds, amax=(None, bufs.rec_of(REC_DZ1, dz1)))
+        if W1.shape[1] == 1:
+            dW1, db1 = conv1p1_wgrad(ctx.obs, dz1, bufs.rec_of(REC_DZ1, dz1), ctx.inds)
+        else:
+            dW1, db1 = cnn.conv_wgrad(ctx.obs, dz1, 1, ctx.inds, amax=(None, bufs.rec_of(REC_DZ1, dz1)))
         return (None, None, None, None, dW1, db1, dg1, de1, dW2, db2, dg2, de2, dW3, db3, dg3, de3, dWf, dbf, dgf, def_)
 
 
@@ -154,6 +164,17 @@ class LnNatureTrunk:
         if network is not None:
             self.bufs.cache_weights = True
             self.bufs.pack_params = (network[0].weight, network[3].weight, network[6].weight, network[10].weight)
+
+    def q1_pack(self, W: torch.Tensor) -> torch.Tensor:
+        """Kernel Q1's pack of the one-frame conv1 weight, cached like ``bufs``' packs (re-derived INTO the same buffer, keyed by
+        ``bufs.weights_version``, the tensor's version counter and its address)."""
+        if not self.bufs.cache_weights:
+            return conv1q1_pack(W.detach())
+        tag = (self.bufs.weights_version, W._version, W.data_ptr())
+        hit = self._own.get("q1_pack")
+        if hit is None or hit[0] != tag:
+            hit = self._own["q1_pack"] = (tag, conv1q1_pack(W.detach(), hit[1] if hit is not None else None))
+        return hit[1]
 
     def _key(self, kind, m, dev):
         return (kind, m, dev, torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0)

@@ -1332,6 +1332,61 @@ def conv1q_pre_fwd(obs_u8, pack, bias, inds=None, out=None):
     return out
 
 
+def _frames_u8(obs_u8, what):
+    """(rows, 84, 84) uint8 frames: ``(N, 1, 84, 84)`` and ``(N, 84, 84, 1)`` are the same bytes -> the (rows, 84, 84) view."""
+    _chk(obs_u8, torch.uint8, "src")
+    if tuple(obs_u8.shape[1:]) not in ((84, 84), (1, 84, 84), (84, 84, 1)):
+        raise ValueError(f"{what}: source rows must be (84, 84) uint8 frames, got {tuple(obs_u8.shape)}")
+    return obs_u8.view(-1, 84, 84)
+
+
+def conv1q1_pack(W, out=None):
+    """Kernel Q1's pack of a ``Conv2d(1, 32, 8, stride=4)`` weight (32, 1, 8, 8), as f32 storage (kernel Q's digits in the one-channel layout)."""
+    _chk(W, torch.float32, "W", (32, 1, 8, 8))
+    n = _lib.load().mi355ppo_cnn_conv1q1_pack_bytes() // 4
+    out = torch.empty(n, dtype=torch.float32, device=W.device) if out is None else _chk(out, torch.float32, "pack", (n,))
+    _launch("mi355ppo_cnn_conv1q1_pack", W.device, _ptr(W), _ptr(out))
+    return out
+
+
+def conv1q1_pre_fwd(obs_u8, pack, bias, inds=None, out=None):
+    """``conv1(obs_u8[inds] / 255) + bias`` WITHOUT the ReLU for ONE-channel frames (rows, 84, 84) uint8 on kernel Q1 -- the input of the first
+    LayerNorm of pqn_atari_envpool_lstm.py's network; ``pack = conv1q1_pack(W)``.  (M, 20, 20, 32) f32, kernel Q's arithmetic: exact."""
+    frames = _frames_u8(obs_u8, "conv1q1_pre_fwd")
+    images = frames.shape[0] if inds is None else inds.numel()
+    if inds is not None:
+        _chk(inds, torch.int64, "inds")
+    _chk(pack, torch.float32, "pack", (_lib.load().mi355ppo_cnn_conv1q1_pack_bytes() // 4,))
+    _chk(bias, torch.float32, "bias", (32,))
+    out = torch.empty((images, 20, 20, 32), dtype=torch.float32, device=frames.device) if out is None else _chk(out, torch.float32, "out",
+                                                                                                               (images, 20, 20, 32))
+    _launch("mi355ppo_cnn_conv1q1_pre_fwd", frames.device, _ptr(frames), _ptr(inds), _ptr(pack), _ptr(bias), _ptr(out), images)
+    return out
+
+
+def conv1p1_wgrad(obs_u8, dz, dz_amax, inds=None, out=None):
+    """``(dW (32, 1, 8, 8), db (32,))`` of ``Conv2d(1, 32, 8, stride=4)`` from the uint8 frames (rows, 84, 84) through ``inds`` and the
+    pre-activation gradient ``dz`` (M, 20, 20, 32) with its amax record (kernel P1: dz in two f16 terms, exact frame operand, fixed-order
+    fold -- the same input gives the same bits)."""
+    frames = _frames_u8(obs_u8, "conv1p1_wgrad")
+    images = dz.shape[0]
+    _chk(dz, torch.float32, "dz", (images, 20, 20, 32))
+    if inds is not None:
+        _chk(inds, torch.int64, "inds", (images,))
+    elif frames.shape[0] != images:
+        raise ValueError(f"conv1p1_wgrad: {frames.shape[0]} frames for {images} rows of dz")
+    _chk(dz_amax, torch.int32, "dz_amax", (AMAX_WORDS,))
+    dev = dz.device
+    if out is not None:
+        dW, db = _chk(out[0], torch.float32, "dW", (32, 1, 8, 8)), _chk(out[1], torch.float32, "db", (32,))
+    else:
+        dW, db = torch.empty((32, 1, 8, 8), dtype=torch.float32, device=dev), torch.empty(32, dtype=torch.float32, device=dev)
+    ws = _workspace(dev, _lib.load().mi355ppo_cnn_conv1p1_wgrad_workspace_bytes(images))
+    _launch("mi355ppo_cnn_conv1p1_wgrad_f16x2", dev, _ptr(frames), _ptr(inds), _ptr(dz), _ptr(dW), _ptr(db), images, _ptr(ws), ws.numel(),
+            _ptr(dz_amax))
+    return dW, db
+
+
 def _pqn_net(obs, params, n_actions):
     N, O = obs.shape
     _chk(obs, torch.float32, "obs")

@@ -111,7 +111,8 @@ def main(argv=None):
 
     envs = make_envs(args)
     q_network = AtariLSTMQNetwork(envs).to(device)
-    learner = LSTMPQNLearner(q_network, args, envs.single_observation_space.shape, envs.single_action_space.n, args.num_envs, device)
+    learner = LSTMPQNLearner(q_network, args, envs.single_observation_space.shape, envs.single_action_space.n, args.num_envs, device,
+                             obs_space=envs.single_observation_space)
 
     avg_returns = deque(maxlen=20)
     start_time = time.time()

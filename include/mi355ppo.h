@@ -62,6 +62,9 @@ extern "C" {
                                   the LayerNorm NatureCNN of pqn_atari_envpool.py -- mi355ppo_layernorm_relu_* (+ workspace size, *_cpu twins) and the
                                   pre-activation forwards mi355ppo_cnn_conv1q_pre_fwd (+ twin), mi355ppo_cnn_conv_pre_packed_f16x2_f32,
                                   mi355ppo_fc_pre_packed_f16x2_f32 likewise: only added, the number stays at 2.7.1;
+                                  the same network on one frame (pqn_atari_envpool_lstm.py) -- mi355ppo_cnn_conv1q1_pack (+ size, twin),
+                                  mi355ppo_cnn_conv1q1_pre_fwd (+ twin), mi355ppo_cnn_conv1p1_wgrad_f16x2 (+ workspace size) likewise:
+                                  only added, the number stays at 2.7.1;
                                   a binding must check major AND minor (cleanrl_amd/_lib.py does) */
 
 #if defined(__GNUC__)
@@ -1624,6 +1627,30 @@ MI355PPO_API int mi355ppo_layernorm_relu_bwd_f32(const float* dy, const float* a
 MI355PPO_API int mi355ppo_layernorm_relu_bwd_f32_cpu(const float* dy, const float* act, const float* z, const float* mean, const float* rstd,
                                                      const float* gamma, float* dz, float* dgamma, float* dbeta, uint32_t* dz_amax,
                                                      int64_t rows, int C, int HW);
+
+/* ---- The same network on ONE frame: pqn_atari_envpool_lstm.py (added under ABI 2.7.1; csrc/conv1q1.hip, csrc/conv1p1.hip) ---------------
+ * Conv2d(1, 32, 8, stride=4) on uint8 frames (rows, 84, 84): (N, 1, 84, 84) and (N, 84, 84, 1) are the same bytes.  Everything behind
+ * conv1 -- layers 2 / 3, the FC layer, the LayerNorm pair, every data and weight gradient -- is the four-frame network's, unchanged.
+ *   conv1q1_pack: W (32, 1, 8, 8) -> kernel Q1's pack, mi355ppo_cnn_conv1q1_pack_bytes() = 8,832 bytes, 16-byte aligned.  Kernel Q's
+ *     arithmetic (31-bit fixed point per output channel, four signed radix-256 digits) in this kernel's own layout.  One launch.
+ *   conv1q1_pre_fwd: conv1(src[inds] / 255) + bias -> dst (images, 20, 20, 32) f32, 128-byte aligned; src 4-byte aligned, every load inside
+ *     [src, src + rows * 7,056); inds int64 or NULL; images in 1 .. 1 << 22, the destination inside the 32-bit buffer range.  Exact int32
+ *     accumulation and kernel Q's epilogue: the twin returns the device's bits.  One launch.
+ *   conv1p1_wgrad_f16x2: dW (32, 1, 8, 8) and db (32), OVERWRITTEN, from the frames (through inds) and dz (images, 20, 20, 32) with its amax
+ *     record: dz in two f16 terms under the record's scale, the bytes as exact f16 operands, f32 accumulation, one partial per wave folded in a
+ *     fixed order (no atomics on floats: the same input gives the same bits).  workspace: mi355ppo_cnn_conv1p1_wgrad_workspace_bytes(images)
+ *     bytes, 16-byte aligned.  Two or three launches. */
+MI355PPO_API size_t mi355ppo_cnn_conv1q1_pack_bytes(void);
+MI355PPO_API int mi355ppo_cnn_conv1q1_pack(const float* W, void* pack, void* stream);
+MI355PPO_API int mi355ppo_cnn_conv1q1_pack_cpu(const float* W, void* pack);
+MI355PPO_API int mi355ppo_cnn_conv1q1_pre_fwd(const void* src_u8, const int64_t* inds, const void* pack, const float* bias, float* dst,
+                                              int64_t images, void* stream);
+MI355PPO_API int mi355ppo_cnn_conv1q1_pre_fwd_cpu(const void* src_u8, const int64_t* inds, const void* pack, const float* bias, float* dst,
+                                                  int64_t images);
+MI355PPO_API size_t mi355ppo_cnn_conv1p1_wgrad_workspace_bytes(int64_t images);
+MI355PPO_API int mi355ppo_cnn_conv1p1_wgrad_f16x2(const void* src_u8, const int64_t* inds, const float* dz, float* dW, float* db,
+                                                  int64_t images, void* workspace, size_t workspace_bytes, const uint32_t* dz_amax,
+                                                  void* stream);
 
 #ifdef __cplusplus
 }

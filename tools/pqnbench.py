@@ -1,14 +1,16 @@
 """Time both PQN backends (MI355PPO_PQN=torch | fused) on one GPU: one rollout step, the Q(lambda) scan, one minibatch and one
 ``update()`` of PQNLearner / LSTMPQNLearner, at each script's defaults and at a larger env count.
 
-    python tools/pqnbench.py [--reps 20] [--scripts pqn,atari,lstm,trunk] [--json out.json] [--leg-seconds 60] [--breakdown]
+    python tools/pqnbench.py [--reps 20] [--scripts pqn,atari,lstm,trunk,lstm_trunk] [--json out.json] [--leg-seconds 60] [--breakdown]
 
 The recurrent script (``lstm``) builds both learners in one process and times them in alternation (torch, fused, torch, ...), so
 that a drift of the machine falls on both sides.  ``trunk`` is the Atari script's trunk axis (MI355PPO_PQN=fused with
 MI355PPO_PQN_TRUNK=torch | fused): both learners in one process, alternating, every leg (rollout step, Q(lambda), update) under its own
 time limit of ``--leg-seconds`` -- a leg that runs out stops repeating and reports the medians of what it has; the rows also carry the
 bytes of ``learner.obs``.  ``--breakdown`` adds, per env count, the synchronised median time of every library call of one fused-trunk
-minibatch (forward + backward), in call order.
+minibatch (forward + backward), in call order.  ``lstm_trunk`` is the same axis for the recurrent script (LSTMPQNLearner on one-frame
+observations; the rows add ``minibatch_us`` of one minibatch timed on its own); it asserts that the fused trunk's ``learner.obs`` is exactly
+a quarter of the f32 storage's bytes.
 
 A rollout step here is the learner's ``act`` plus the action's copy to the host (the env is left out); ``minibatch_us`` is one
 ``update()`` (update_epochs x num_minibatches of forward + TD loss + backward + clip + RAdam, plus the shuffles) divided by its
@@ -152,12 +154,14 @@ def bench_atari_trunks(N, reps, dev, leg_seconds):
     return rows, learners[1], args
 
 
-def trunk_breakdown(L, args, reps):
+def trunk_breakdown(L, args, reps, minibatch=None):
     """The library calls of ONE fused-trunk minibatch (forward, TD loss, backward) of learner ``L``, each synchronised and timed: ->
-    [(call, median us)] in call order.  The calls are timed in place of the node's own bindings, which are restored afterwards."""
+    [(call, median us)] in call order.  The calls are timed in place of the node's own bindings, which are restored afterwards.
+    ``minibatch``: the minibatch to run (default: PQNLearner's)."""
     from cleanrl_amd import cnn, ln_cnn
 
-    spots = [(ln_cnn, n) for n in ("conv1q_pre_fwd", "layernorm_relu_fwd", "conv_pre_packed", "fc_pre", "layernorm_relu_bwd")] + \
+    spots = [(ln_cnn, n) for n in ("conv1q_pre_fwd", "conv1q1_pre_fwd", "layernorm_relu_fwd", "conv_pre_packed", "fc_pre", "layernorm_relu_bwd",
+                                   "conv1p1_wgrad")] + \
             [(cnn, n) for n in ("fc_wgrad", "fc_dgrad_mask_packed", "conv_wgrad", "conv_dgrad_packed")]
     log = []
 
@@ -172,14 +176,14 @@ def trunk_breakdown(L, args, reps):
         return call
 
     mb = torch.randperm(args.batch_size)[:args.minibatch_size].to(L.device)
-    b_obs = L.obs.view(-1, 84, 84, 4)
 
-    def minibatch():
-        q = L._q(b_obs, mb)
+    def own_minibatch():
+        q = L._q(L.obs.view(-1, 84, 84, 4), mb)
         dq, _ = L.g.pqn_td_loss(q.detach().contiguous(), mb, L.actions.reshape(-1), L.returns.reshape(-1))
         q.backward(dq)
         L.flat.grads.zero_()
 
+    minibatch = own_minibatch if minibatch is None else minibatch
     minibatch()
     saved = [(m, n, getattr(m, n)) for m, n in spots]
     try:
@@ -194,6 +198,72 @@ def trunk_breakdown(L, args, reps):
         for m, n, fn in saved:
             setattr(m, n, fn)
     return [(runs[0][i][0], statistics.median(r[i][1] for r in runs)) for i in range(len(runs[0]))]
+
+
+def _lstm_learner(N, trunk, dev):
+    from cleanrl_amd.pqn_atari_envpool_lstm import Args
+
+    args = Args(num_envs=N)
+    args.batch_size = N * args.num_steps
+    args.minibatch_size = args.batch_size // args.num_minibatches
+    args.num_iterations = args.total_timesteps // args.batch_size
+    torch.manual_seed(1)
+    np.random.seed(1)
+    env = E.SyntheticAtariVecEnv(N, seed=1, api="gym", frames=1)
+    obs = env.reset()
+    L = LSTMPQNLearner(AtariLSTMQNetwork(env).to(dev), args, env.single_observation_space.shape, env.single_action_space.n, N, dev,
+                       backend="fused", trunk=trunk, obs_space=env.single_observation_space)
+    L.reset(obs)
+    L.start_iteration(1)
+    for step in range(args.num_steps):                       # fill the storage once (random rewards / dones)
+        L.act(step)
+        L.observe(step, obs, np.random.randn(N), np.random.rand(N) < 0.02)
+    L.finish_rollout()
+    return L, args
+
+
+def _lstm_minibatch(L, args):
+    """One minibatch of ``LSTMPQNLearner.update`` (the first ``N / num_minibatches`` envs, time-major rows): trunk + gx, the scan, the TD
+    kernel, the backward; the gradients are zeroed instead of stepped."""
+    envs = np.arange(L.N // int(args.num_minibatches))
+    mb = torch.from_numpy(np.arange(L.T * L.N).reshape(L.T, L.N)[:, envs].ravel().copy()).to(L.device)
+    env = torch.from_numpy(envs).to(L.device)
+    net, b_dones = L.net, L.dones.reshape(-1)
+    b_obs = L.obs.view(-1, 84, 84) if L.fused_trunk else L.obs.reshape((-1,) + L.obs_shape)
+
+    def minibatch():
+        state = (L.initial_lstm_state[0][:, env], L.initial_lstm_state[1][:, env])
+        if L.fused_trunk:
+            h, _ = net.states_from_gates(L._gates(b_obs, mb), state, b_dones[mb])
+        else:
+            h, _ = net.states_fused(b_obs[mb], state, b_dones[mb])
+        dh, _ = L.g.pqn_lstm_td_fwd_bwd(h.detach(), mb, L.actions.reshape(-1), L.returns.reshape(-1), net.q_func.weight.detach(),
+                                        net.q_func.bias.detach(), net.q_func.weight.grad, net.q_func.bias.grad)
+        h.backward(dh)
+        L.flat.grads.zero_()
+
+    return minibatch
+
+
+def bench_lstm_trunks(N, reps, dev, leg_seconds):
+    """pqn_atari_envpool_lstm.py at N envs on MI355PPO_PQN=fused: the torch trunk and the fused trunk in this process, alternating ->
+    ([torch-trunk row, fused-trunk row], the fused learner, args)."""
+    learners = [_lstm_learner(N, trunk, dev) for trunk in ("torch", "fused")]
+    args = learners[0][1]
+    learners = [L for L, _ in learners]
+    rows = [{"script": "lstm", "N": N, "backend": "fused", "trunk": L.trunk, "obs_bytes": L.obs.numel() * L.obs.element_size()} for L in learners]
+    assert learners[1].obs.dtype == torch.uint8 and 4 * rows[1]["obs_bytes"] == rows[0]["obs_bytes"], rows      # a quarter of the f32 storage
+    for key, fns, r in (("rollout_step_us", [lambda L=L: L.act(1).cpu() for L in learners], reps),
+                        ("qlambda_us", [L.finish_rollout for L in learners], reps),
+                        ("minibatch_us", [_lstm_minibatch(L, args) for L in learners], reps),
+                        ("update_us", [L.update for L in learners], max(3, reps // 4))):
+        meds, n = _alternate_limited(fns, r, leg_seconds)
+        for row, t in zip(rows, meds):
+            row[key] = t
+            row[key[:-3] + "_reps"] = n
+    for row in rows:
+        row["batch"], row["minibatch_rows"] = args.batch_size, args.minibatch_size
+    return rows, learners[1], args
 
 
 def bench_lstm(N, reps, dev):
@@ -261,6 +331,19 @@ def main():
             if a.breakdown:
                 r = {"script": "atari", "N": N, "trunk": "fused", "minibatch_rows": targs.minibatch_size,
                      "calls_us": [[n, round(t, 1)] for n, t in trunk_breakdown(fused_learner, targs, max(3, a.reps // 2))]}
+                rows.append(r)
+                show(r)
+            del trunk_rows, fused_learner
+            torch.cuda.empty_cache()
+    if "lstm_trunk" in scripts:
+        for N in (8, 128):
+            trunk_rows, fused_learner, targs = bench_lstm_trunks(N, a.reps, dev, a.leg_seconds)
+            for r in trunk_rows:
+                rows.append(r)
+                show(r)
+            if a.breakdown:
+                calls = trunk_breakdown(fused_learner, targs, max(3, a.reps // 2), _lstm_minibatch(fused_learner, targs))
+                r = {"script": "lstm", "N": N, "trunk": "fused", "minibatch_rows": targs.minibatch_size, "calls_us": [[n, round(t, 1)] for n, t in calls]}
                 rows.append(r)
                 show(r)
             del trunk_rows, fused_learner
