@@ -347,6 +347,10 @@ SIGNATURES = {
     "mi355ppo_cnn_conv1q1_pre_fwd_cpu": (c_int, [_P] * 5 + [c_int64]),
     "mi355ppo_cnn_conv1p1_wgrad_workspace_bytes": (c_size_t, [c_int64]),
     "mi355ppo_cnn_conv1p1_wgrad_f16x2": (c_int, [_P, _P, _P, _P, _P, c_int64, _P, c_size_t, _P, _P]),
+    # kernel Q1's ReLU instances: conv1 of ppo_atari_lstm's network (added under ABI 2.7.1, csrc/conv1q1.hip)
+    "mi355ppo_cnn_conv1q1_fwd_bits": (c_int, [_P] * 6 + [c_int64, _P]),
+    "mi355ppo_cnn_conv1q1_fwd_amax": (c_int, [_P] * 6 + [c_int64, _P, _P]),
+    "mi355ppo_cnn_conv1q1_fwd_cpu": (c_int, [_P] * 7 + [c_int64]),
 }
 
 ABI_VERSION = 271       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)

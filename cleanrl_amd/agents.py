@@ -321,6 +321,18 @@ def lstm_backend_from_env() -> str:
     return v
 
 
+LSTM_TRUNKS = ("torch", "fused")
+
+
+def lstm_trunk_backend_from_env() -> str:
+    """``MI355PPO_LSTM_TRUNK``: ``torch`` (default: ``AtariLSTMAgent.network`` on torch's Conv2d / Linear behind the K5 gather + convert
+    kernel) or ``fused`` (HIP learner only: the one-frame NatureCNN kernels of ``cnn.NatureTrunkFn`` on the uint8 rollout rows)."""
+    v = os.environ.get("MI355PPO_LSTM_TRUNK", "torch")
+    if v not in LSTM_TRUNKS:
+        raise ValueError(f"MI355PPO_LSTM_TRUNK={v!r}: expected torch or fused")
+    return v
+
+
 class AtariLSTMAgent(_DiscreteMixin, nn.Module):
     """ppo_atari_lstm.py:117-165: NatureCNN on ONE 84x84 frame -> Linear(3136,512) -> LSTM(512,128) -> actor / critic.
     Same construction order as the reference (network layers, ``nn.LSTM`` default init, then bias := 0 and orthogonal
@@ -356,11 +368,27 @@ class AtariLSTMAgent(_DiscreteMixin, nn.Module):
         self.n_actions = envs.single_action_space.n
         self.rng = _SampleCounter()
         self.lstm_backend = lstm_backend_from_env()
+        self._trunk = None                  # cnn.NatureTrunk of heads_seq_u8 (MI355PPO_LSTM_TRUNK=fused), made on first use
 
     def _normalise(self, x):
         if x.dtype == torch.uint8:
             return ops.obs_u8_to_f32(x.contiguous()) if x.is_cuda else x.float() / 255.0
         return x / 255.0
+
+    def heads_seq_u8(self, obs_rows, inds, lstm_state, done):
+        """``heads_seq`` on the uint8 rollout rows (rows, 84, 84, 1), ``inds`` optionally gathering them time-major (``b_obs[mb_inds]``):
+        the three convolutions and Linear(3136,512) on the libmi355ppo kernels (gather, /255, bias, ReLU and their backward fused;
+        conv1 on kernels Q1 / P1, cleanrl_amd/cnn.py), then the same LSTM seam (either ``lstm_backend``) and the torch heads."""
+        from . import cnn
+
+        if self._trunk is None:
+            self._trunk = cnn.NatureTrunk()
+        net = self.network
+        self._trunk.bufs.pack_params = (net[0].weight, net[2].weight, net[4].weight, net[7].weight)
+        feats = self._trunk(obs_rows, inds, net[0], net[2], net[4])
+        hidden = cnn.LinearReLUHwcFn.apply(feats, net[7].weight, net[7].bias, self._trunk.bufs)
+        hidden, lstm_state = self.states_from_features(hidden, lstm_state, done)
+        return self.actor(hidden), self.critic(hidden), lstm_state
 
     def initial_state(self, num_envs: int, device):
         """(:225-228) zero hidden and cell state, (num_layers, N, hidden)."""

@@ -18,7 +18,7 @@ import weakref
 import torch
 
 from . import _lib
-from .ops import _chk, _launch, _ptr, _workspace
+from .ops import _chk, _launch, _ptr, _workspace, conv1p1_wgrad, conv1q1_fwd_amax, conv1q1_fwd_bits, conv1q1_pack
 
 # layer -> (Cin, Cout, K, stride, Hin, Hout)
 LAYERS = {1: (4, 32, 8, 4, 84, 20), 2: (32, 64, 4, 2, 20, 9), 3: (64, 64, 3, 1, 9, 7)}
@@ -690,6 +690,18 @@ class _Buffers:
                 self._bt[key], self._bt["ma_tapsum"] = (tag, pack), (tag, tapsum)
         return self._bt[key][1], self._bt["ma_tapsum"][1]
 
+    def q1_pack(self, W: torch.Tensor) -> torch.Tensor:
+        """Kernel Q1's pack of a one-frame (32, 1, 8, 8) conv1 weight (``NatureTrunkFn`` and ``ln_cnn.LnNatureTrunk.q1_pack``), cached like the
+        other packs: keyed by ``weights_version``, the tensor's version counter and its address, re-derived INTO the same buffer (a launch
+        of its own: the all-packs launch skips conv1 for one frame)."""
+        if not self.cache_weights:
+            return conv1q1_pack(W.detach())
+        tag = (self.weights_version, W._version, W.data_ptr())
+        hit = self._bt.get("q1_pack")
+        if hit is None or hit[0] != tag:
+            hit = self._bt["q1_pack"] = (tag, conv1q1_pack(W.detach(), hit[1] if hit is not None else None))
+        return hit[1]
+
     def fc_weight(self, W: torch.Tensor) -> torch.Tensor:
         """Linear(3136,512) weight with (h,w,c)-ordered input features, cached like the conv matrices (re-derived INTO the
         same buffer: captured rollout steps keep reading one address)."""
@@ -798,6 +810,40 @@ class NatureTrunkFn(torch.autograd.Function):
         m = obs_u8.shape[0] if inds is None else inds.numel()
         a1, a2, a3 = bufs.get(m, obs_u8.device, False)
         ctx.ind = ind
+        if W1.shape[1] == 1:
+            # ppo_atari_lstm.py's conv1 on ONE frame: kernel Q1's ReLU instances (csrc/conv1q1.hip) on (rows, 84, 84) u8 frames, kernel P1 in the
+            # backward; layers 2 / 3 as for the four-frame agents.  The f16x2 split of kernel Z only, as ln_cnn's one-frame node.
+            if ind is not None or not _CONV_Z or bufs.split != "f16x2" or a1.numel() * 4 >= BUF_LIMIT:
+                raise NotImplementedError("MI355PPO_LSTM_TRUNK=fused runs on the f16x2 split of kernel Z only: MI355PPO_SPLIT=bf16x3, MI355PPO_CONV=f "
+                                          f"and batches of {BUF_LIMIT // 51200} images or more (32-bit buffer offsets) are not covered -- use "
+                                          "MI355PPO_LSTM_TRUNK=torch")
+            bt1 = bufs.q1_pack(W1)
+            ctx.bits = None
+            bufs.last_a3_bits = None
+            ctx.f16 = f16 = bufs.f16(obs_u8)
+            grads = _MASK_BITS and want_bits and any(ctx.needs_input_grad)
+            if f16:
+                rec = bufs.begin_pass(m, obs_u8.device)
+                mb1 = mb2 = mb3 = None
+                if grads:
+                    mb1, mb2, mb3 = ctx.bits = bufs.get_bits(m, obs_u8.device)
+                    bufs.last_a3_bits = mb3
+                conv1q1_fwd_amax(obs_u8, bt1, b1.detach(), inds, a1, mb1, bufs.owns(REC_A1, a1))
+                conv_fwd_packed(a1, bufs.conv_zpack(W2, 2, MODE_FWD), b2.detach(), 2, a2, bits=mb2, amax=(rec[REC_A1], bufs.owns(REC_A2, a2)))
+                conv_fwd_packed(a2, bufs.conv_zpack(W3, 3, MODE_FWD), b3.detach(), 3, a3, bits=mb3, amax=(rec[REC_A2], bufs.owns(REC_A3, a3)))
+            else:
+                mb1, mb2, mb3 = bufs.get_bits(m, obs_u8.device)
+                conv1q1_fwd_bits(obs_u8, bt1, b1.detach(), inds, a1, mb1)
+                conv_fwd_packed(a1, bufs.conv_zpack(W2, 2, MODE_FWD), b2.detach(), 2, a2, bits=mb2 if grads else None)
+                conv_fwd_packed(a2, bufs.conv_zpack(W3, 3, MODE_FWD), b3.detach(), 3, a3, bits=mb3 if grads else None)
+                if grads:
+                    ctx.bits = (mb1, mb2, mb3)
+                    bufs.last_a3_bits = mb3
+            ctx.obs, ctx.inds, ctx.acts, ctx.bufs = obs_u8, inds, (a1, a2, a3), bufs
+            ctx.params = (W1, b1, W2, b2, W3, b3)
+            bufs.last_a3_ptr = a3.data_ptr()
+            ctx.save_for_backward(W2, W3)
+            return a3
         if ind is not None:
             if not _CONV_Z or a1.numel() * 4 >= BUF_LIMIT:
                 raise NotImplementedError("the row-bias conv1 exists on kernel Q with layers 2 / 3 on kernel Z only (MI355PPO_CONV=f / more "
@@ -906,6 +952,8 @@ class NatureTrunkFn(torch.autograd.Function):
             def wgrad1(amax):
                 conv_wgrad(ctx.obs, dz1, 1, ctx.inds, out=(dW4, db1), amax=amax)
                 return ma_conv1_wgrad_fold(dz1, ctx.ind, ctx.inds, dW4, out=W1.grad if direct else None), db1
+        elif ctx.params[0].shape[1] == 1:       # one frame: kernel P1 (dz in two f16 terms under its record, whichever path produced dz1)
+            wgrad1 = lambda amax: conv1p1_wgrad(ctx.obs, dz1, ctx.bufs.rec_of(REC_DZ1, dz1), ctx.inds, out=gout(1))
         else:
             wgrad1 = lambda amax: conv_wgrad(ctx.obs, dz1, 1, ctx.inds, out=gout(1), amax=amax)
         if ctx.bufs.f16(dz3) and a1.numel() * 4 < BUF_LIMIT:      # the two-term f16 split (records: from the producers, else computed here)

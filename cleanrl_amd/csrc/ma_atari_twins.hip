@@ -110,17 +110,20 @@ void q1_pack_host(const float* W, unsigned char* pack) {
     }
 }
 
-// kernel Q1, serial: exact integer dot products of the frame's bytes with the pack's digits, then kernel Q's pre-activation epilogue
-int q1_pre_fwd_host(const char* fn, const uint8_t* src, const int64_t* inds, const unsigned char* pack, const float* bias, float* dst,
-                    int64_t images) {
+// kernel Q1, serial: exact integer dot products of the frame's bytes with the pack's digits, then kernel Q's epilogue -- pre: the
+// pre-activation; otherwise the ReLU, with the mask words (bits) and the maximum folded into slot 0 of the amax record when given
+int q1_fwd_host(const char* fn, const uint8_t* src, const int64_t* inds, const unsigned char* pack, const float* bias, float* dst,
+                uint32_t* bits, uint32_t* amax, int64_t images, bool pre) {
     MI355_REQUIRE(src && pack && bias && dst, MI355PPO_EINVAL, "%s: null pointer", fn);
     MI355_REQUIRE(images > 0, MI355PPO_EINVAL, "%s: images=%lld must be positive", fn, (long long)images);
     const signed char* dig = reinterpret_cast<const signed char*>(pack);
+    float vmax = 0.0f;
     for (int64_t img = 0; img < images; ++img) {
         const int64_t row = inds ? inds[img] : img;
         const uint8_t* frame = src + (size_t)row * kQ1Img;
         for (int p = 0; p < kQPerImg; ++p) {
             const int gy = p / kQG, gx = p - gy * kQG;
+            uint32_t word = 0;
             for (int n = 0; n < 32; ++n) {
                 int D[kQDigits] = {0, 0, 0, 0};
                 for (int r = 0; r < 8; ++r) {
@@ -130,9 +133,18 @@ int q1_pre_fwd_host(const char* fn, const uint8_t* src, const int64_t* inds, con
                 }
                 float sc;
                 memcpy(&sc, pack + kQ1ScaleOff + n * 4, 4);
-                dst[((size_t)img * kQPerImg + p) * 32 + n] = ma_q_finish_pre(D, sc, bias[n]);
+                const float v = pre ? ma_q_finish_pre(D, sc, bias[n]) : ma_q_finish(D, sc, bias[n]);
+                dst[((size_t)img * kQPerImg + p) * 32 + n] = v;
+                if (v > 0.0f) word |= 1u << n;
+                if (!pre) vmax = fmaxf(vmax, v);
             }
+            if (bits) bits[(size_t)img * kQPerImg + p] = word;
         }
+    }
+    if (amax) {                 // (as the LayerNorm twins: the device spreads its waves' maxima over the 16 slots, the record's value is their maximum)
+        uint32_t b;
+        memcpy(&b, &vmax, 4);
+        if (b > amax[0]) amax[0] = b;
     }
     return MI355PPO_OK;
 }
@@ -147,8 +159,15 @@ extern "C" MI355PPO_API int mi355ppo_cnn_conv1q1_pack_cpu(const float* W, void* 
 
 extern "C" MI355PPO_API int mi355ppo_cnn_conv1q1_pre_fwd_cpu(const void* src_u8, const int64_t* inds, const void* pack, const float* bias,
                                                              float* dst, int64_t images) {
-    return q1_pre_fwd_host("mi355ppo_cnn_conv1q1_pre_fwd_cpu", static_cast<const uint8_t*>(src_u8), inds, static_cast<const unsigned char*>(pack),
-                           bias, dst, images);
+    return q1_fwd_host("mi355ppo_cnn_conv1q1_pre_fwd_cpu", static_cast<const uint8_t*>(src_u8), inds, static_cast<const unsigned char*>(pack),
+                       bias, dst, nullptr, nullptr, images, true);
+}
+
+// kernel Q1's ReLU forward (mi355ppo_cnn_conv1q1_fwd_bits / _fwd_amax): mask_bits and dst_amax may each be null
+extern "C" MI355PPO_API int mi355ppo_cnn_conv1q1_fwd_cpu(const void* src_u8, const int64_t* inds, const void* pack, const float* bias, float* dst,
+                                                         uint32_t* mask_bits, uint32_t* dst_amax, int64_t images) {
+    return q1_fwd_host("mi355ppo_cnn_conv1q1_fwd_cpu", static_cast<const uint8_t*>(src_u8), inds, static_cast<const unsigned char*>(pack), bias,
+                       dst, mask_bits, dst_amax, images, false);
 }
 
 extern "C" MI355PPO_API int mi355ppo_ma_atari_split_u8_cpu(const uint8_t* frames6, uint8_t* rows4, uint8_t* ind, uint32_t* flag, int64_t frames) {

@@ -465,6 +465,22 @@ def conv1q1_pre_fwd(obs_u8, pack, bias, inds=None, out=None):
     return out
 
 
+def conv1q1_fwd(obs_u8, pack, bias, inds=None, out=None, bits=None, amax=None):
+    """``mi355ppo_cnn_conv1q1_fwd_cpu`` (see ops.conv1q1_fwd_amax / ops.conv1q1_fwd_bits): the ReLU forward, the device's bits; ``bits``
+    (int32, 400 words per image) and ``amax`` (a record: its value lands in word 0) are optional."""
+    if obs_u8.dtype != torch.uint8 or tuple(obs_u8.shape[1:]) not in ((84, 84), (1, 84, 84), (84, 84, 1)):
+        raise ValueError(f"conv1q1_fwd: source rows must be (84, 84) uint8 frames, got {tuple(obs_u8.shape)} {obs_u8.dtype}")
+    frames = obs_u8.contiguous().view(-1, 84, 84)
+    ii = None if inds is None else _i64(inds)
+    if ii is not None and ii.numel() and (int(ii.min()) < 0 or int(ii.max()) >= frames.shape[0]):
+        raise ValueError("conv1q1_fwd: inds out of range")
+    images = frames.shape[0] if ii is None else ii.numel()
+    out = torch.empty((images, 20, 20, 32)) if out is None else out
+    _lib.call("mi355ppo_cnn_conv1q1_fwd_cpu", _p(frames), _p(ii), _p(pack), _p(_f32(bias)), _out(out, torch.float32, images * 12800, "out"),
+              _out(bits, torch.int32, images * 400, "bits"), _out(amax, torch.int32, 256, "amax"), images)
+    return out
+
+
 def pqn_mlp_forward(obs, params, n_actions, q_out=None):
     N, O = obs.shape
     x, p = _f32(obs), _pqn_params(params, O, n_actions)

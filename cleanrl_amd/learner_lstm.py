@@ -26,6 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import host_ops
+from .agents import lstm_trunk_backend_from_env
 from .learner import PPOLearner
 
 
@@ -35,19 +36,46 @@ class LSTMPPOLearner(PPOLearner):
         assert self.N % int(args.num_minibatches) == 0, "num_envs must be divisible by num_minibatches"   # :296
         self.next_lstm_state = agent.initial_state(self.N, device)
         self.initial_lstm_state = (self.next_lstm_state[0].clone(), self.next_lstm_state[1].clone())
+        # MI355PPO_LSTM_TRUNK=fused (HIP learner only, default torch): the network's convolutions and Linear(3136,512) run on the
+        # one-frame NatureCNN kernels straight from the uint8 rollout rows -- no f32 copy of a rollout slot or of the gathered minibatch
+        self.trunk = lstm_trunk_backend_from_env()
+        self.fused_trunk = self.trunk == "fused"
+        if self.fused_trunk:
+            if not self.hip:
+                raise ValueError("MI355PPO_LSTM_TRUNK=fused runs on the HIP kernels only (the CPU path keeps the reference's torch ops): use a "
+                                 "cuda device or MI355PPO_LSTM_TRUNK=torch")
+            if tuple(obs_space.shape) != (1, 84, 84) or self.obs.dtype != torch.uint8 or not hasattr(agent, "heads_seq_u8"):
+                raise ValueError(f"MI355PPO_LSTM_TRUNK=fused takes (1, 84, 84) uint8 frames, got {tuple(obs_space.shape)}")
+            self._x_roll = None                                             # (the K5 convert of a rollout slot is gone)
         if self.hip:
             E = int(args.update_epochs)
             self._env_dev = torch.empty((E, self.N), dtype=torch.int64, device=device)
             self._env_pin = torch.empty((E, self.N), dtype=torch.int64).pin_memory()
 
     # ------------------------------------------------------------------ rollout
+    def _heads_seq(self, obs_rows, inds, lstm_state, done):
+        """``agent.heads_seq`` on uint8 rows (HIP path): through K5 (gather + convert) and torch's layers, or -- MI355PPO_LSTM_TRUNK=fused --
+        straight into the trunk kernels, whose packs follow the optimizer through ``weights_version`` (``_own_trunk_buffers``)."""
+        if self.fused_trunk:
+            if self.agent._trunk is None:
+                from . import cnn
+
+                self.agent._trunk = cnn.NatureTrunk()
+            self._own_trunk_buffers()
+            return self.agent.heads_seq_u8(obs_rows, inds, lstm_state, done)
+        if inds is None:
+            return self.agent.heads_seq(self._features(obs_rows), lstm_state, done)
+        if self._x_mb is None or self._x_mb.shape[0] != inds.numel():
+            self._x_mb = torch.empty((inds.numel(),) + self.obs_shape, device=self.device)
+        x = self.ops.obs_u8_to_f32(obs_rows, inds, self._x_mb).permute(0, 3, 1, 2)   # b_obs[mb_inds] ; x / 255.0
+        return self.agent.heads_seq(x, lstm_state, done)
+
     @torch.no_grad()
     def act(self, step: int):
         if step == 0:                                                      # :231
             self.initial_lstm_state = (self.next_lstm_state[0].clone(), self.next_lstm_state[1].clone())
         if self.hip:
-            logits, value, self.next_lstm_state = self.agent.heads_seq(self._features(self.obs[step]), self.next_lstm_state,
-                                                                       self.dones[step])
+            logits, value, self.next_lstm_state = self._heads_seq(self.obs[step], None, self.next_lstm_state, self.dones[step])
             seed, off = self.agent.rng.next()
             a64, _, _, _ = self.ops.categorical_sample(logits.contiguous(), seed=seed, offset=off,
                                                        action_f32_out=self.actions[step], logprob_out=self.logprobs[step],
@@ -65,7 +93,7 @@ class LSTMPPOLearner(PPOLearner):
     def finish_rollout(self) -> None:
         a = self.args
         if self.hip:
-            _, next_value, _ = self.agent.heads_seq(self._features(self.boot_obs), self.next_lstm_state, self.boot_done)
+            _, next_value, _ = self._heads_seq(self.boot_obs, None, self.next_lstm_state, self.boot_done)
             self.ops.gae(self.rewards, self.dones, self.values, self.boot_done, next_value.reshape(-1).contiguous(),
                          a.gamma, a.gae_lambda, self.advantages, self.returns)
         else:
@@ -130,13 +158,10 @@ class LSTMPPOLearner(PPOLearner):
                     clipfrac=clipfrac, explained_variance=float(explained_var), num_updates=k)
 
     def forward_backward_hip(self, idx, b_obs, b_actions, b_logprobs, b_advantages, b_returns, b_values, scalars_out):
-        """K5 gather of the minibatch's (T x envs) rows -> conv stack -> T LSTM steps from the minibatch's initial state ->
-        K3 fused loss fwd+bwd -> autograd through LSTM and conv stack (:304-352)."""
+        """K5 gather of the minibatch's (T x envs) rows (MI355PPO_LSTM_TRUNK=fused: inside conv1) -> conv stack -> T LSTM steps from the
+        minibatch's initial state -> K3 fused loss fwd+bwd -> autograd through LSTM and conv stack (:304-352)."""
         a, ops = self.args, self.ops
-        if self._x_mb is None or self._x_mb.shape[0] != idx.numel():
-            self._x_mb = torch.empty((idx.numel(),) + self.obs_shape, device=self.device)
-        x = ops.obs_u8_to_f32(b_obs, idx, self._x_mb).permute(0, 3, 1, 2)           # b_obs[mb_inds] ; x / 255.0
-        logits, value, _ = self.agent.heads_seq(x, self._mb_state, self._mb_dones)
+        logits, value, _ = self._heads_seq(b_obs, idx, self._mb_state, self._mb_dones)      # (fused trunk: the gather rides in conv1's loader)
         value = value.view(-1)
         _, dlogits, dvalue = ops.ppo_loss_categorical(logits.detach().contiguous(), value.detach().contiguous(), idx,
                                                       b_actions, b_logprobs, b_advantages, b_returns, b_values,

@@ -23,7 +23,7 @@ import torch
 from . import _lib, cnn
 from .cnn import (BUF_LIMIT, MODE_DGRAD_S1, MODE_DGRAD_S2, MODE_FWD, MODE_FWD_Q, REC_A1, REC_A2, REC_A3, REC_DH, REC_DZ1, REC_DZ2, REC_DZ3,
                   _rec, _row_major)
-from .ops import _chk, _launch, _ptr, _workspace, conv1p1_wgrad, conv1q1_pack, conv1q1_pre_fwd, conv1q_pre_fwd, layernorm_relu_bwd, layernorm_relu_fwd
+from .ops import _chk, _launch, _ptr, _workspace, conv1p1_wgrad, conv1q1_pre_fwd, conv1q_pre_fwd, layernorm_relu_bwd, layernorm_relu_fwd
 
 LN_EPS = 1e-5                 # nn.LayerNorm's default
 # (C, HW) of the four LayerNorms: conv1 (20 x 20 x 32), conv2 (9 x 9 x 64), conv3 (7 x 7 x 64), Linear (512)
@@ -166,15 +166,9 @@ class LnNatureTrunk:
             self.bufs.pack_params = (network[0].weight, network[3].weight, network[6].weight, network[10].weight)
 
     def q1_pack(self, W: torch.Tensor) -> torch.Tensor:
-        """Kernel Q1's pack of the one-frame conv1 weight, cached like ``bufs``' packs (re-derived INTO the same buffer, keyed by
-        ``bufs.weights_version``, the tensor's version counter and its address)."""
-        if not self.bufs.cache_weights:
-            return conv1q1_pack(W.detach())
-        tag = (self.bufs.weights_version, W._version, W.data_ptr())
-        hit = self._own.get("q1_pack")
-        if hit is None or hit[0] != tag:
-            hit = self._own["q1_pack"] = (tag, conv1q1_pack(W.detach(), hit[1] if hit is not None else None))
-        return hit[1]
+        """Kernel Q1's pack of the one-frame conv1 weight, cached like ``bufs``' packs (``cnn._Buffers.q1_pack``: re-derived INTO the same
+        buffer, keyed by ``bufs.weights_version``, the tensor's version counter and its address)."""
+        return self.bufs.q1_pack(W)
 
     def _key(self, kind, m, dev):
         return (kind, m, dev, torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0)

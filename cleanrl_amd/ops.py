@@ -1364,6 +1364,39 @@ def conv1q1_pre_fwd(obs_u8, pack, bias, inds=None, out=None):
     return out
 
 
+def _conv1q1_relu_args(obs_u8, pack, bias, inds, out, bits, what):
+    frames = _frames_u8(obs_u8, what)
+    images = frames.shape[0] if inds is None else inds.numel()
+    if inds is not None:
+        _chk(inds, torch.int64, "inds")
+    _chk(pack, torch.float32, "pack", (_lib.load().mi355ppo_cnn_conv1q1_pack_bytes() // 4,))
+    _chk(bias, torch.float32, "bias", (32,))
+    _chk(out, torch.float32, "out", (images, 20, 20, 32))
+    if bits is not None:
+        _chk(bits, torch.int32, "bits", (images * 400,))
+    return frames, images
+
+
+def conv1q1_fwd_amax(obs_u8, pack, bias, inds, out, bits, dst_amax):
+    """``relu(conv1(obs_u8[inds] / 255) + bias)`` for ONE-channel frames (rows, 84, 84) uint8 on kernel Q1 -- conv1 of ppo_atari_lstm.py's
+    network; ``pack = conv1q1_pack(W)``.  Folds ``max(out)`` into the amax record ``dst_amax`` and, when ``bits`` is given, writes
+    ``out > 0`` as bits (int32, ``out.numel() // 32`` words: word w, bit b <-> flat element 32 w + b)."""
+    frames, images = _conv1q1_relu_args(obs_u8, pack, bias, inds, out, bits, "conv1q1_fwd_amax")
+    _chk(dst_amax, torch.int32, "dst_amax", (AMAX_WORDS,))
+    _launch("mi355ppo_cnn_conv1q1_fwd_amax", frames.device, _ptr(frames), _ptr(inds), _ptr(pack), _ptr(bias), _ptr(out), _ptr(bits), images,
+            _ptr(dst_amax))
+    return out
+
+
+def conv1q1_fwd_bits(obs_u8, pack, bias, inds, out, bits):
+    """The same without the amax record; ``bits`` is required."""
+    if bits is None:
+        raise ValueError("conv1q1_fwd_bits: the mask words are required")
+    frames, images = _conv1q1_relu_args(obs_u8, pack, bias, inds, out, bits, "conv1q1_fwd_bits")
+    _launch("mi355ppo_cnn_conv1q1_fwd_bits", frames.device, _ptr(frames), _ptr(inds), _ptr(pack), _ptr(bias), _ptr(out), _ptr(bits), images)
+    return out
+
+
 def conv1p1_wgrad(obs_u8, dz, dz_amax, inds=None, out=None):
     """``(dW (32, 1, 8, 8), db (32,))`` of ``Conv2d(1, 32, 8, stride=4)`` from the uint8 frames (rows, 84, 84) through ``inds`` and the
     pre-activation gradient ``dz`` (M, 20, 20, 32) with its amax record (kernel P1: dz in two f16 terms, exact frame operand, fixed-order

@@ -65,6 +65,8 @@ extern "C" {
                                   the same network on one frame (pqn_atari_envpool_lstm.py) -- mi355ppo_cnn_conv1q1_pack (+ size, twin),
                                   mi355ppo_cnn_conv1q1_pre_fwd (+ twin), mi355ppo_cnn_conv1p1_wgrad_f16x2 (+ workspace size) likewise:
                                   only added, the number stays at 2.7.1;
+                                  the plain ReLU network on one frame (ppo_atari_lstm.py) -- mi355ppo_cnn_conv1q1_fwd_bits, _fwd_amax and the
+                                  twin mi355ppo_cnn_conv1q1_fwd_cpu likewise: only added, the number stays at 2.7.1;
                                   a binding must check major AND minor (cleanrl_amd/_lib.py does) */
 
 #if defined(__GNUC__)
@@ -1651,6 +1653,20 @@ MI355PPO_API size_t mi355ppo_cnn_conv1p1_wgrad_workspace_bytes(int64_t images);
 MI355PPO_API int mi355ppo_cnn_conv1p1_wgrad_f16x2(const void* src_u8, const int64_t* inds, const float* dz, float* dW, float* db,
                                                   int64_t images, void* workspace, size_t workspace_bytes, const uint32_t* dz_amax,
                                                   void* stream);
+
+/* ---- Kernel Q1's ReLU instances: conv1 of ppo_atari_lstm.py's plain NatureCNN on one frame (added under ABI 2.7.1; csrc/conv1q1.hip) -------
+ * relu(conv1(src[inds] / 255) + bias) -> dst (images, 20, 20, 32) f32: mi355ppo_cnn_conv1q_fwd_bits / _fwd_amax on (rows, 84, 84) frames, with
+ * the pack, the pointer and range checks of mi355ppo_cnn_conv1q1_pre_fwd.  relu() of that entry point's result is this one's, bit for bit.
+ *   mask_bits: images * 400 uint32, word p = (dst > 0) of the 32 channels of pixel p (bit b of word w <-> flat element 32 w + b); required by
+ *     _fwd_bits, may be NULL in _fwd_amax and the twin.
+ *   dst_amax: dst's amax record (zeroed by the caller), 64-byte aligned; the twin folds its maximum into slot 0 and takes NULL.
+ * One launch each. */
+MI355PPO_API int mi355ppo_cnn_conv1q1_fwd_bits(const void* src_u8, const int64_t* inds, const void* pack, const float* bias, float* dst,
+                                               uint32_t* mask_bits, int64_t images, void* stream);
+MI355PPO_API int mi355ppo_cnn_conv1q1_fwd_amax(const void* src_u8, const int64_t* inds, const void* pack, const float* bias, float* dst,
+                                               uint32_t* mask_bits, int64_t images, uint32_t* dst_amax, void* stream);
+MI355PPO_API int mi355ppo_cnn_conv1q1_fwd_cpu(const void* src_u8, const int64_t* inds, const void* pack, const float* bias, float* dst,
+                                              uint32_t* mask_bits, uint32_t* dst_amax, int64_t images);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,4 @@
-// Stand-alone driver of the host twins of the one-frame conv1 kernels (kernel Q1's pack and pre-activation forward,
+// Stand-alone driver of the host twins of the one-frame conv1 kernels (kernel Q1's pack, pre-activation forward and ReLU forward,
 // cleanrl_amd/csrc/ma_atari_twins.hip) for the address and undefined-behaviour sanitizers: its own main, every buffer a heap allocation of
 // exactly the size the C ABI names -- the frames exactly rows x 7,056 bytes, so a load past the last tap row of the last pixel is a report.
 // 1 image, 3 images gathered with inds = {3, 0, 3} from 4 stored frames, and 5 images in place.  It checks what it can without a library
@@ -63,6 +63,25 @@ int run(int images, int stored, const int64_t* inds) {
             }
     }
     CHECK(negative);
+    {   // the ReLU twin: max(pre-activation, 0) to the bit, mask words of exactly images x 400 words, the maximum folded into slot 0 of a record
+        std::vector<float> a((size_t)images * kOut);
+        std::vector<uint32_t> bits((size_t)images * 400, 0xFFFFFFFFu), rec(256, 0u);
+        CHECK(mi355ppo_cnn_conv1q1_fwd_cpu(frames.data(), inds, pack.data(), bias.data(), a.data(), bits.data(), rec.data(), images) == 0);
+        float amax = 0.0f;
+        for (size_t e = 0; e < a.size(); ++e) {
+            const float want = z[e] > 0.0f ? z[e] : 0.0f;
+            CHECK(memcmp(&a[e], &want, 4) == 0);
+            CHECK(((bits[e >> 5] >> (e & 31)) & 1u) == (want > 0.0f ? 1u : 0u));
+            amax = want > amax ? want : amax;
+        }
+        CHECK(amax > 0.0f && memcmp(&rec[0], &amax, 4) == 0);
+        for (int w = 1; w < 256; ++w) CHECK(rec[w] == 0u);
+        std::vector<float> again((size_t)images * kOut);                          // neither mask words nor a record
+        CHECK(mi355ppo_cnn_conv1q1_fwd_cpu(frames.data(), inds, pack.data(), bias.data(), again.data(), nullptr, nullptr, images) == 0);
+        CHECK(memcmp(again.data(), a.data(), a.size() * 4) == 0);
+        CHECK(mi355ppo_cnn_conv1q1_fwd_cpu(frames.data(), inds, pack.data(), bias.data(), a.data(), nullptr, nullptr, 0) == MI355PPO_EINVAL);
+        CHECK(mi355ppo_cnn_conv1q1_fwd_cpu(frames.data(), inds, nullptr, bias.data(), a.data(), nullptr, nullptr, images) == MI355PPO_EINVAL);
+    }
     if (inds)
         for (int i = 1; i < images; ++i)
             if (inds[i] == inds[0]) CHECK(memcmp(z.data(), z.data() + (size_t)i * kOut, (size_t)kOut * 4) == 0);
