@@ -102,7 +102,56 @@ class _DiscreteMixin:
         return action, probs.log_prob(action), probs.entropy()
 
 
-class AtariAgent(_DiscreteMixin, nn.Module):
+class _NatureTrunkMixin:
+    """The fast path of the agents whose ``network`` is the NatureCNN (three Conv2d + ReLU, Flatten, Linear(3136, 512) + ReLU): uint8 rollout
+    rows straight into the libmi355ppo kernels (cleanrl_amd/cnn.py: gather, /255, bias, ReLU and their backward fused)."""
+
+    _trunk = None                 # cnn.NatureTrunk: made on first use, or by the learner that owns its buffers (PPOLearner._owned_trunk)
+
+    def _nature_trunk(self):
+        from . import cnn
+
+        if self._trunk is None:
+            self._trunk = cnn.NatureTrunk()
+        net = self.network
+        self._trunk.bufs.pack_params = (net[0].weight, net[2].weight, net[4].weight, net[7].weight)
+        return self._trunk
+
+    def _hidden_u8(self, obs_rows, inds=None, ind=None):
+        """``network`` on the rows ``obs_rows[inds]`` (``ind``: ``MAAtariAgent.heads_u8``) -> (M, 512)."""
+        from . import cnn
+
+        trunk, net = self._nature_trunk(), self.network
+        feats = trunk(obs_rows, inds, net[0], net[2], net[4], ind=ind)
+        return cnn.LinearReLUHwcFn.apply(feats, net[7].weight, net[7].bias, trunk.bufs)
+
+    def _heads_u8(self, obs_rows, inds=None, ind=None):
+        from . import cnn
+
+        hidden = self._hidden_u8(obs_rows, inds, ind)
+        if cnn.heads_supported(self.actor, self.critic):
+            return cnn.HeadsFn.apply(hidden, self.actor.weight, self.actor.bias, self.critic.weight, self.critic.bias, self._trunk.bufs)
+        return self.actor(hidden), self.critic(hidden)      # > 18 actions: library GEMMs
+
+    def _act_u8(self, obs_rows, ind, seed, offset, offset_base, action_f32_out, logprob_out, value_out, want_i64):
+        """The rollout step on uint8 rows (no autograd graph): trunk, then Linear(3136,512) + heads + Categorical draw in two launches
+        (``cnn.fc_heads_act_categorical``).  None when the fused step does not apply (wide action spaces, huge batches)."""
+        from . import cnn
+
+        trunk, net = self._nature_trunk(), self.network
+        if torch.is_grad_enabled() or not cnn.heads_supported(self.actor, self.critic) or not cnn.fc_heads_act_supported_rows(obs_rows.shape[0]):
+            return None                                   # (decided before the trunk runs: the caller's fallback computes it)
+        feats = trunk(obs_rows, None, net[0], net[2], net[4], ind=ind)
+        if not cnn.fc_heads_act_supported(feats):
+            return None
+        bufs = trunk.bufs
+        return cnn.fc_heads_act_categorical(feats, bufs.fc_pack_fwd(net[7].weight), net[7].bias.detach().contiguous(),
+                                            self.actor.weight.detach(), self.actor.bias.detach(), self.critic.weight.detach(),
+                                            self.critic.bias.detach(), seed, offset, offset_base, action_f32_out, logprob_out, value_out,
+                                            want_i64=want_i64, amax=bufs.rec_of(cnn.REC_A3, feats) if bufs.f16(feats) else None)
+
+
+class AtariAgent(_NatureTrunkMixin, _DiscreteMixin, nn.Module):
     obs_is_image = True
 
     def __init__(self, envs):
@@ -122,7 +171,6 @@ class AtariAgent(_DiscreteMixin, nn.Module):
         self.critic = layer_init(nn.Linear(512, 1), std=1)
         self.n_actions = envs.single_action_space.n
         self.rng = _SampleCounter()
-        self._trunk = None
 
     def _normalise(self, x):
         if x.dtype == torch.uint8:
@@ -139,37 +187,11 @@ class AtariAgent(_DiscreteMixin, nn.Module):
         (rows, 84, 84, 4) and ``inds`` optionally gathers rows (``b_obs[mb_inds]``).  Same function as
         ``heads(obs / 255.0)`` with the three convolutions on the libmi355ppo f32-MFMA kernels (gather, /255, bias,
         ReLU and the ReLU / bias backward fused; cleanrl_amd/cnn.py); the two Linear layers stay on hipBLASLt."""
-        from . import cnn
-
-        if self._trunk is None:
-            self._trunk = cnn.NatureTrunk()
-        net = self.network
-        self._trunk.bufs.pack_params = (net[0].weight, net[2].weight, net[4].weight, net[7].weight)
-        feats = self._trunk(obs_rows, inds, net[0], net[2], net[4])
-        hidden = cnn.LinearReLUHwcFn.apply(feats, net[7].weight, net[7].bias, self._trunk.bufs)
-        if cnn.heads_supported(self.actor, self.critic):
-            return cnn.HeadsFn.apply(hidden, self.actor.weight, self.actor.bias, self.critic.weight, self.critic.bias, self._trunk.bufs)
-        return self.actor(hidden), self.critic(hidden)      # > 18 actions: library GEMMs
+        return self._heads_u8(obs_rows, inds)
 
     def act_u8(self, obs_rows, seed, offset, offset_base=None, action_f32_out=None, logprob_out=None, value_out=None, want_i64=True):
-        """The learner's rollout step on uint8 rows (no autograd graph): trunk, then Linear(3136,512) + heads + Categorical draw in two
-        launches (``cnn.fc_heads_act_categorical``).  None when the fused step does not apply (wide action spaces, huge batches)."""
-        from . import cnn
-
-        if self._trunk is None:
-            self._trunk = cnn.NatureTrunk()
-        net = self.network
-        if torch.is_grad_enabled() or not cnn.heads_supported(self.actor, self.critic) or not cnn.fc_heads_act_supported_rows(obs_rows.shape[0]):
-            return None                                   # (decided before the trunk runs: the caller's fallback computes it)
-        self._trunk.bufs.pack_params = (net[0].weight, net[2].weight, net[4].weight, net[7].weight)
-        feats = self._trunk(obs_rows, None, net[0], net[2], net[4])
-        if not cnn.fc_heads_act_supported(feats):
-            return None
-        bufs = self._trunk.bufs
-        return cnn.fc_heads_act_categorical(feats, bufs.fc_pack_fwd(net[7].weight), net[7].bias.detach().contiguous(),
-                                            self.actor.weight.detach(), self.actor.bias.detach(), self.critic.weight.detach(),
-                                            self.critic.bias.detach(), seed, offset, offset_base, action_f32_out, logprob_out, value_out,
-                                            want_i64=want_i64, amax=bufs.rec_of(cnn.REC_A3, feats) if bufs.f16(feats) else None)
+        """The learner's rollout step on uint8 rows (``_act_u8``)."""
+        return self._act_u8(obs_rows, None, seed, offset, offset_base, action_f32_out, logprob_out, value_out, want_i64)
 
     def get_value(self, x):
         return self.critic(self.network(self._normalise(x)))
@@ -333,7 +355,7 @@ def lstm_trunk_backend_from_env() -> str:
     return v
 
 
-class AtariLSTMAgent(_DiscreteMixin, nn.Module):
+class AtariLSTMAgent(_NatureTrunkMixin, _DiscreteMixin, nn.Module):
     """ppo_atari_lstm.py:117-165: NatureCNN on ONE 84x84 frame -> Linear(3136,512) -> LSTM(512,128) -> actor / critic.
     Same construction order as the reference (network layers, ``nn.LSTM`` default init, then bias := 0 and orthogonal
     weights in ``named_parameters`` order, then actor, critic), hence the same weights for the same torch seed.
@@ -368,7 +390,6 @@ class AtariLSTMAgent(_DiscreteMixin, nn.Module):
         self.n_actions = envs.single_action_space.n
         self.rng = _SampleCounter()
         self.lstm_backend = lstm_backend_from_env()
-        self._trunk = None                  # cnn.NatureTrunk of heads_seq_u8 (MI355PPO_LSTM_TRUNK=fused), made on first use
 
     def _normalise(self, x):
         if x.dtype == torch.uint8:
@@ -379,15 +400,7 @@ class AtariLSTMAgent(_DiscreteMixin, nn.Module):
         """``heads_seq`` on the uint8 rollout rows (rows, 84, 84, 1), ``inds`` optionally gathering them time-major (``b_obs[mb_inds]``):
         the three convolutions and Linear(3136,512) on the libmi355ppo kernels (gather, /255, bias, ReLU and their backward fused;
         conv1 on kernels Q1 / P1, cleanrl_amd/cnn.py), then the same LSTM seam (either ``lstm_backend``) and the torch heads."""
-        from . import cnn
-
-        if self._trunk is None:
-            self._trunk = cnn.NatureTrunk()
-        net = self.network
-        self._trunk.bufs.pack_params = (net[0].weight, net[2].weight, net[4].weight, net[7].weight)
-        feats = self._trunk(obs_rows, inds, net[0], net[2], net[4])
-        hidden = cnn.LinearReLUHwcFn.apply(feats, net[7].weight, net[7].bias, self._trunk.bufs)
-        hidden, lstm_state = self.states_from_features(hidden, lstm_state, done)
+        hidden, lstm_state = self.states_from_features(self._hidden_u8(obs_rows, inds), lstm_state, done)
         return self.actor(hidden), self.critic(hidden), lstm_state
 
     def initial_state(self, num_envs: int, device):
@@ -831,7 +844,7 @@ def ma_atari_backend() -> str:
     return v
 
 
-class MAAtariAgent(_DiscreteMixin, nn.Module):
+class MAAtariAgent(_NatureTrunkMixin, _DiscreteMixin, nn.Module):
     """ppo_pettingzoo_ma_atari.py:86-118: NatureCNN on (84, 84, 6) pixel-interleaved observations -- four stacked frames plus
     two agent-indicator planes.  Only the four frame channels are divided by 255 (:104,109)."""
 
@@ -839,7 +852,6 @@ class MAAtariAgent(_DiscreteMixin, nn.Module):
     obs_layout = "hwc"
     frame_channels = 4            # channels [0, 4) are pixels; the rest pass through unscaled
     indicator_planes = 2          # channels [4, 6): constant over an observation (supersuit's agent_indicator_v0)
-    _trunk = None                 # MI355PPO_MA_ATARI=fused: the trunk kernels' buffers (cnn.NatureTrunk), created by the learner
 
     def __init__(self, envs):
         super().__init__()
@@ -880,36 +892,11 @@ class MAAtariAgent(_DiscreteMixin, nn.Module):
         """``MI355PPO_MA_ATARI=fused``: ``obs_rows`` are the (rows, 84, 84, 4) u8 frame channels, ``ind`` (rows, 2) the two indicator bytes of
         each row, ``inds`` optionally gathers rows.  Same function as ``heads`` on the six-channel observation whose planes 4 / 5 hold
         ``ind`` everywhere: conv1 on kernel Q with the planes' contribution as a per-row bias, the rest as ``AtariAgent.heads_u8``."""
-        from . import cnn
-
-        if self._trunk is None:
-            self._trunk = cnn.NatureTrunk()
-        net = self.network
-        self._trunk.bufs.pack_params = (net[0].weight, net[2].weight, net[4].weight, net[7].weight)
-        feats = self._trunk(obs_rows, inds, net[0], net[2], net[4], ind=ind)
-        hidden = cnn.LinearReLUHwcFn.apply(feats, net[7].weight, net[7].bias, self._trunk.bufs)
-        if cnn.heads_supported(self.actor, self.critic):
-            return cnn.HeadsFn.apply(hidden, self.actor.weight, self.actor.bias, self.critic.weight, self.critic.bias, self._trunk.bufs)
-        return self.actor(hidden), self.critic(hidden)      # > 18 actions: library GEMMs
+        return self._heads_u8(obs_rows, inds, ind)
 
     def act_u8(self, obs_rows, ind, seed, offset, offset_base=None, action_f32_out=None, logprob_out=None, value_out=None, want_i64=True):
-        """The fused rollout step on the four-channel rows and their indicator bytes (``AtariAgent.act_u8``); None when it does not apply."""
-        from . import cnn
-
-        if self._trunk is None:
-            self._trunk = cnn.NatureTrunk()
-        net = self.network
-        if torch.is_grad_enabled() or not cnn.heads_supported(self.actor, self.critic) or not cnn.fc_heads_act_supported_rows(obs_rows.shape[0]):
-            return None
-        self._trunk.bufs.pack_params = (net[0].weight, net[2].weight, net[4].weight, net[7].weight)
-        feats = self._trunk(obs_rows, None, net[0], net[2], net[4], ind=ind)
-        if not cnn.fc_heads_act_supported(feats):
-            return None
-        bufs = self._trunk.bufs
-        return cnn.fc_heads_act_categorical(feats, bufs.fc_pack_fwd(net[7].weight), net[7].bias.detach().contiguous(),
-                                            self.actor.weight.detach(), self.actor.bias.detach(), self.critic.weight.detach(),
-                                            self.critic.bias.detach(), seed, offset, offset_base, action_f32_out, logprob_out, value_out,
-                                            want_i64=want_i64, amax=bufs.rec_of(cnn.REC_A3, feats) if bufs.f16(feats) else None)
+        """The fused rollout step on the four-channel rows and their indicator bytes (``_act_u8``); None when it does not apply."""
+        return self._act_u8(obs_rows, ind, seed, offset, offset_base, action_f32_out, logprob_out, value_out, want_i64)
 
     def get_value(self, x):
         return self.critic(self.network(self._normalise(x)))

@@ -5,6 +5,9 @@ Host side of ``mi355ppo_cnn_*``: tensor-level wrappers, and ``NatureTrunk`` -- t
 rows.  Everything the reference runs as separate passes around the convolutions is fused into them:
 ``b_obs[mb_inds]`` and ``x / 255.0`` (:320,154) into conv1's loader, bias + ReLU into every forward epilogue, ReLU
 backward into the data-gradient epilogues, bias gradients into the weight-gradient kernels.
+``NatureTrunkFn`` has one forward body for three conv1 families -- four stacked frames (kernel Q), ppo_pettingzoo_ma_atari's four frames + two
+indicator planes as a per-row bias, ppo_atari_lstm's single frame (kernel Q1) -- chosen by ``_conv1_family``; ``_Buffers`` keeps every derived
+weight matrix behind ``_derived`` and every per-stream buffer set behind ``_stream_key``.
 
 Activations are (images, H, W, C) f32; parameters keep torch's (Cout, Cin, KH, KW) layout (they are views of the
 flat parameter buffer) and are repacked into the kernels' matrix layouts on use (<= 147 KB each).
@@ -29,8 +32,6 @@ VARIANT_DGRAD2_CLASSES = 6
 QPACK_NUMEL = 33408 // 4            # mi355ppo_cnn_conv1q_pack_bytes() as f32 storage elements (kernel Q's integer-digit pack)
 VARIANT_Q = 6                       # layer-1 forward on the integer matrix pipe (csrc/conv1q.hip); Bt = the mode-4 pack
 _CONV_Z = os.environ.get("MI355PPO_CONV", "z") != "f"    # layers 2 / 3 forward + data gradients: kernel Z, or the f32-pipe kernel F
-_MASK_BITS = True    # ReLU masks travel to the data gradients as bits (the A/B switch MI355PPO_MASK_BITS is gone since round 6: profiles/r03_mask_bits_ab.jsonl)
-_FUSED_PACKS = True   # all weight packs of the NatureCNN agent in one launch (the A/B switch MI355PPO_FUSED_PACKS is gone since round 6)
 BUF_LIMIT = (1 << 32) - 8192     # kernels Z / F address a tensor with 32-bit buffer offsets: larger tensors take kernel S (64-bit pointers)
 # Operand split of kernels Z / V / W (round 5): "f16x2" = two f16 terms per f32 under per-tensor power-of-two scales, three matrix
 # instructions per product (csrc/f16split.h); "bf16x3" = round 3's three bf16 terms, six instructions.  Read once per process.
@@ -552,6 +553,21 @@ def fc_wgrad(dz: torch.Tensor, a: torch.Tensor, hwc_channels: int = 0, out: torc
 FCZ_MIN_ROWS = 1             # kernel Z at every batch size: from 8,192 rows whole-K wave tiles, below (a rollout step, config B's minibatch) K split over the grid
 
 
+def _stream_key(dev, *head):
+    """``head`` + the current stream of ``dev``: one buffer set per (kind, batch size, device, stream) -- the env-group lanes of a rollout
+    (pipeline.py) run the same batch size side by side, one stream each."""
+    return (*head, torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0)
+
+
+def _per_stream(store: dict, dev, head: tuple, make):
+    """``store``'s buffers under ``_stream_key(dev, *head)``, made by ``make()`` on first use."""
+    key = _stream_key(dev, *head)
+    b = store.get(key)
+    if b is None:
+        b = store[key] = make()
+    return b
+
+
 class _Buffers:
     """Activation / gradient buffers reused across calls of one batch size (no allocator traffic in the loop), and the
     repacked weight matrices.  The matrices are re-derived from the parameters on every use unless the owner opts in to
@@ -589,7 +605,7 @@ class _Buffers:
 
     @staticmethod
     def _amax_key(m: int, dev):
-        return ("amax", m, dev, torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0)
+        return _stream_key(dev, "amax", m, dev)
 
     def has_pass(self, m: int, dev) -> bool:
         return self._amax_key(m, dev) in self.by_m
@@ -632,14 +648,14 @@ class _Buffers:
 
     def _pack_keys(self):
         W1, W2, W3, Wfc = self.pack_params
-        q = [] if W1.shape[1] == 1 else [((1, MODE_FWD_Q), W1, None)]     # (one frame: kernel Q1's pack is ln_cnn.LnNatureTrunk's own launch)
+        q = [] if W1.shape[1] == 1 else [((1, MODE_FWD_Q), W1, None)]     # (one frame: kernel Q1's pack is ``q1_pack``'s own launch)
         return q + [(("zpack", 2, MODE_FWD), W2, (64, 512)), (("zpack", 3, MODE_FWD), W3, (64, 576)),
                     (("zpack", 3, MODE_DGRAD_S1), W3, (64, 576)), (("zpack", 2, MODE_DGRAD_S2), W2, (128, 256)),
                     ("fc_pack_fwd", Wfc, (512, 3136)), ("fc_pack_dgrad", Wfc, (3136, 512))]
 
     def _repack_all(self, key, W) -> bool:
         """Rebuild every cached pack in one launch when ``key`` (stale) is one of them and ``W`` its parameter.  -> done?"""
-        if self.pack_params is None or not self.cache_weights or not _FUSED_PACKS:
+        if self.pack_params is None or not self.cache_weights:
             return False
         keys = self._pack_keys()
         if not any(k == key and w.data_ptr() == W.data_ptr() for k, w, _ in keys) or not all(w.is_cuda and w.dtype == torch.float32 and w.is_contiguous() for _, w, _ in keys):
@@ -669,54 +685,62 @@ class _Buffers:
         else:
             _launch("mi355ppo_nature_packs_f32", dev, *q_args)
         for (k, w, _), buf in zip(keys, outs):
-            self._bt[k] = ((self.weights_version, w._version, w.data_ptr()), buf)
+            self._bt[k] = (self._tag(w), buf)
         if ma:
             hit = self._bt.get("ma_tapsum")
             _, tapsum = ma_conv1_pack(W1, outs[0], hit[1] if hit is not None else None)
             self._bt["ma_tapsum"] = (self._bt[keys[0][0]][0], tapsum)
         return True
 
+    def _tag(self, W: torch.Tensor):
+        """What a cached derivation of ``W`` is valid for: the owner's ``weights_version``, the tensor's own version counter, its address."""
+        return (self.weights_version, W._version, W.data_ptr())
+
+    def _derived(self, key, W: torch.Tensor, derive, all_packs: bool = False) -> torch.Tensor:
+        """``derive(out | None) -> tensor`` of the parameter ``W``, cached under ``key`` while ``_tag(W)`` holds and re-derived INTO the same
+        buffer when it does not (captured rollout steps and updates keep reading one address).  ``all_packs``: a stale entry first tries the
+        all-packs launch (``_repack_all``).  Without ``cache_weights``: derived on every use."""
+        if not self.cache_weights:
+            return derive(None)
+        tag = self._tag(W)
+        hit = self._bt.get(key)
+        if hit is None or hit[0] != tag:
+            if all_packs and self._repack_all(key, W):
+                return self._bt[key][1]
+            hit = self._bt[key] = (tag, derive(hit[1] if hit is not None else None))
+        return hit[1]
+
     def ma_pack(self, W: torch.Tensor):
         """(kernel Q's pack of channels 0 - 3, the tap sums of channels 4 / 5) of ppo_pettingzoo_ma_atari's (32, 6, 8, 8) conv1 weight, cached
-        like the other packs (re-derived into the same buffers; with the other packs stale too, behind the all-packs launch)."""
+        like the other packs (with the other packs stale too, behind the all-packs launch): one launch derives both, the tap sums follow
+        the pack's entry under a key of their own."""
         if not self.cache_weights:
             return ma_conv1_pack(W.detach())
-        key = (1, MODE_FWD_Q)
-        tag = (self.weights_version, W._version, W.data_ptr())
-        hit, ts = self._bt.get(key), self._bt.get("ma_tapsum")
-        if hit is None or ts is None or hit[0] != tag or ts[0] != tag:
-            if not self._repack_all(key, W):
-                pack, tapsum = ma_conv1_pack(W.detach(), hit[1] if hit is not None else None, ts[1] if ts is not None else None)
-                self._bt[key], self._bt["ma_tapsum"] = (tag, pack), (tag, tapsum)
-        return self._bt[key][1], self._bt["ma_tapsum"][1]
+
+        def derive(out):
+            ts = self._bt.get("ma_tapsum")
+            pack, tapsum = ma_conv1_pack(W.detach(), out, ts[1] if ts is not None else None)
+            self._bt["ma_tapsum"] = (self._tag(W), tapsum)
+            return pack
+
+        return self._derived((1, MODE_FWD_Q), W, derive, all_packs=True), self._bt["ma_tapsum"][1]
 
     def q1_pack(self, W: torch.Tensor) -> torch.Tensor:
-        """Kernel Q1's pack of a one-frame (32, 1, 8, 8) conv1 weight (``NatureTrunkFn`` and ``ln_cnn.LnNatureTrunk.q1_pack``), cached like the
-        other packs: keyed by ``weights_version``, the tensor's version counter and its address, re-derived INTO the same buffer (a launch
-        of its own: the all-packs launch skips conv1 for one frame)."""
-        if not self.cache_weights:
-            return conv1q1_pack(W.detach())
-        tag = (self.weights_version, W._version, W.data_ptr())
-        hit = self._bt.get("q1_pack")
-        if hit is None or hit[0] != tag:
-            hit = self._bt["q1_pack"] = (tag, conv1q1_pack(W.detach(), hit[1] if hit is not None else None))
-        return hit[1]
+        """Kernel Q1's pack of a one-frame (32, 1, 8, 8) conv1 weight (``NatureTrunkFn`` and ``ln_cnn.LnNatureFn``), cached like the other
+        packs (a launch of its own: the all-packs launch skips conv1 for one frame)."""
+        return self._derived("q1_pack", W, lambda out: conv1q1_pack(W.detach(), out))
 
     def fc_weight(self, W: torch.Tensor) -> torch.Tensor:
-        """Linear(3136,512) weight with (h,w,c)-ordered input features, cached like the conv matrices (re-derived INTO the
-        same buffer: captured rollout steps keep reading one address)."""
-        if not self.cache_weights:
-            return fc_weight_hwc(W.detach()).contiguous()
-        tag = (self.weights_version, W._version, W.data_ptr())
-        hit = self._bt.get("fc")
-        if hit is None or hit[0] != tag:
-            if hit is None:
-                hit = (tag, fc_weight_hwc(W.detach()).contiguous())
-            else:
-                hit[1].copy_(fc_weight_hwc(W.detach()))
-                hit = (tag, hit[1])
-            self._bt["fc"] = hit
-        return hit[1]
+        """Linear(3136,512) weight with (h,w,c)-ordered input features, cached like the conv matrices."""
+        def derive(out):
+            hwc = fc_weight_hwc(W.detach())
+            return hwc.contiguous() if out is None else out.copy_(hwc)
+
+        return self._derived("fc", W, derive)
+
+    def fc_weight_t(self, W: torch.Tensor) -> torch.Tensor:
+        """``fc_weight(W).T`` as a (3136, 512) matrix of pitch 516 (the B operand of the FC data gradient), cached likewise."""
+        return self._derived("fc_t", W, lambda out: (padded_rows(W.shape[1], W.shape[0], W.device) if out is None else out).copy_(self.fc_weight(W).t()))
 
     def fc_pack_fwd(self, W: torch.Tensor) -> torch.Tensor:
         """Kernel Z's pack of the (h,w,c)-ordered Linear(3136,512) weight (the forward's B operand), cached like the matrices."""
@@ -732,72 +756,62 @@ class _Buffers:
 
     def _pack_cached(self, key, W, source):
         pack = (lambda B, out=None: fc_pack_f16x2(B, None, out)) if self.f16(W) else fc_pack      # (looked up per call: the tests patch cnn.fc_pack)
-        if not self.cache_weights:
-            return pack(source())
-        tag = (self.weights_version, W._version, W.data_ptr())
-        hit = self._bt.get(key)
-        if hit is None or hit[0] != tag:
-            if self._repack_all(key, W):
-                return self._bt[key][1]
-            hit = (tag, pack(source(), hit[1] if hit is not None else None))
-            self._bt[key] = hit
-        return hit[1]
+        return self._derived(key, W, lambda out: pack(source(), out), all_packs=True)
+
+    def weights(self, W: torch.Tensor, layer: int, mode: int) -> torch.Tensor:
+        return self._derived((layer, mode), W, lambda out: repack_weights(W.detach(), layer, mode, out), all_packs=mode == MODE_FWD_Q)
 
     def fc_dz(self, m: int, n: int, dev) -> torch.Tensor:
         """Reusable (m, n) buffer with a padded row pitch for the FC layer's pre-activation gradient."""
-        key = ("fc_dz", m, n, dev, torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0)
-        b = self.by_m.get(key)
-        if b is None:
-            b = padded_rows(m, n, dev)
-            self.by_m[key] = b
-        return b
-
-    def fc_weight_t(self, W: torch.Tensor) -> torch.Tensor:
-        """``fc_weight(W).T`` as a dense (3136, 512) matrix (the B operand of the FC data gradient), cached likewise."""
-        if not self.cache_weights:
-            wt = padded_rows(W.shape[1], W.shape[0], W.device)
-            wt.copy_(fc_weight_hwc(W.detach()).t())
-            return wt
-        tag = (self.weights_version, W._version, W.data_ptr())
-        hit = self._bt.get("fc_t")
-        if hit is None or hit[0] != tag:
-            wt = hit[1] if hit is not None else padded_rows(W.shape[1], W.shape[0], W.device)     # (3136, 512), pitch 516
-            wt.copy_(self.fc_weight(W).t())
-            hit = (tag, wt)
-            self._bt["fc_t"] = hit
-        return hit[1]
-
-    def weights(self, W: torch.Tensor, layer: int, mode: int) -> torch.Tensor:
-        if not self.cache_weights:
-            return repack_weights(W.detach(), layer, mode)
-        key = (layer, mode)
-        tag = (self.weights_version, W._version, W.data_ptr())
-        hit = self._bt.get(key)
-        if hit is None or hit[0] != tag:
-            if mode == MODE_FWD_Q and self._repack_all(key, W):
-                return self._bt[key][1]
-            hit = (tag, repack_weights(W.detach(), layer, mode, hit[1] if hit is not None else None))
-            self._bt[key] = hit
-        return hit[1]
+        return _per_stream(self.by_m, dev, ("fc_dz", m, n, dev), lambda: padded_rows(m, n, dev))
 
     def get_bits(self, m: int, dev):
         """ReLU masks of a1, a2, a3 as bits (int32 words; one set per batch size and stream, like the activations)."""
-        key = ("bits", m, dev, torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0)
-        b = self.by_m.get(key)
-        if b is None:
-            b = [torch.empty(mask_words(m * n), dtype=torch.int32, device=dev) for n in (20 * 20 * 32, 9 * 9 * 64, 7 * 7 * 64)]
-            self.by_m[key] = b
-        return b
+        return _per_stream(self.by_m, dev, ("bits", m, dev), lambda: [torch.empty(mask_words(m * n), dtype=torch.int32, device=dev)
+                                                                      for n in (20 * 20 * 32, 9 * 9 * 64, 7 * 7 * 64)])
 
     def get(self, m: int, dev, grads: bool):
-        # one set per (batch size, stream): the env-group lanes of a rollout (pipeline.py) run the same batch size concurrently
-        key = (m, dev, grads, torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0)
-        b = self.by_m.get(key)
-        if b is None:
-            shapes = [(m, 20, 20, 32), (m, 9, 9, 64), (m, 7, 7, 64)]
-            b = [torch.empty(s, dtype=torch.float32, device=dev) for s in shapes]
-            self.by_m[key] = b
-        return b
+        """a1, a2, a3 (``grads``: the same shapes for their gradients)."""
+        return _per_stream(self.by_m, dev, (m, dev, grads), lambda: [torch.empty(s, dtype=torch.float32, device=dev)
+                                                                     for s in ((m, 20, 20, 32), (m, 9, 9, 64), (m, 7, 7, 64))])
+
+
+def _wgrad1_four(ctx, dz1, direct, gout, amax):
+    return conv_wgrad(ctx.obs, dz1, 1, ctx.inds, out=gout(1), amax=amax)
+
+
+def _wgrad1_one(ctx, dz1, direct, gout, amax):
+    # kernel P1 (dz in two f16 terms under its record, whichever path produced dz1)
+    return conv1p1_wgrad(ctx.obs, dz1, ctx.bufs.rec_of(REC_DZ1, dz1), ctx.inds, out=gout(1))
+
+
+def _wgrad1_ma(ctx, dz1, direct, gout, amax):
+    # kernel P runs unchanged on the four-channel rows into a (32, 4, 8, 8) temporary (one address per trunk: captured slots replay it) and
+    # writes db1 where it belongs; the fold writes all six channels of the gradient
+    dev, by_m = dz1.device, ctx.bufs.by_m
+    dW4 = by_m.get(("ma_dw4", dev))
+    if dW4 is None:
+        dW4 = by_m[("ma_dw4", dev)] = torch.empty((32, 4, 8, 8), dtype=torch.float32, device=dev)
+    W1, b1 = ctx.params[:2]
+    db1 = b1.grad if direct else torch.empty(32, dtype=torch.float32, device=dev)
+    conv_wgrad(ctx.obs, dz1, 1, ctx.inds, out=(dW4, db1), amax=amax)
+    return ma_conv1_wgrad_fold(dz1, ctx.ind, ctx.inds, dW4, out=W1.grad if direct else None), db1
+
+
+def _conv1_family(W1, ind):
+    """conv1 of the three agents, by ``(W1.shape[1], ind is not None)`` -> ``(packs, fwd_amax, fwd_bits, wgrad1)``: ``packs(bufs)`` = the
+    weight operands as a tuple, ``fwd_amax(obs, *packs, bias, inds, out, bits | None, record)`` and ``fwd_bits(obs, *packs, bias, inds, out,
+    bits)`` the ReLU forwards, ``wgrad1(ctx, dz1, direct, gout, amax) -> (dW1, db1)``.  The entry points are this module's attributes at
+    CALL time (the tests' stand-ins replace them).
+    - one frame (ppo_atari_lstm.py): kernel Q1's ReLU instances (csrc/conv1q1.hip) on (rows, 84, 84) u8 frames, kernel P1 in the backward;
+    - ``ind`` (ppo_pettingzoo_ma_atari.py): W1 is (32, 6, 8, 8), its channels 4 / 5 a bias per row (csrc/ma_atari_rows.h);
+    - four frames: the integer matrix pipe (kernel Q) -- uint8 taps are exact int8 operands, weights four int8 digits."""
+    if W1.shape[1] == 1:
+        return (lambda bufs: (bufs.q1_pack(W1),), lambda *a: conv1q1_fwd_amax(*a), lambda *a: conv1q1_fwd_bits(*a), _wgrad1_one)
+    if ind is not None:
+        return (lambda bufs: bufs.ma_pack(W1), lambda obs, *a: ma_conv1_fwd_amax(obs, ind, *a), lambda obs, *a: ma_conv1_fwd_bits(obs, ind, *a),
+                _wgrad1_ma)
+    return (lambda bufs: (bufs.weights(W1, 1, MODE_FWD_Q),), lambda *a: conv1q_fwd_amax(*a), lambda *a: conv1q_fwd_bits(*a), _wgrad1_four)
 
 
 class NatureTrunkFn(torch.autograd.Function):
@@ -805,124 +819,65 @@ class NatureTrunkFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, obs_u8, inds, W1, b1, W2, b2, W3, b3, bufs, want_bits=False, ind=None):
-        """``ind`` (rows, 2) u8: ppo_pettingzoo_ma_atari's indicator bytes of the rows -- W1 then is (32, 6, 8, 8), its channels 4 / 5 a bias
-        per row (csrc/ma_atari_rows.h); None for the four-channel agents."""
+        """``ind`` (rows, 2) u8: ppo_pettingzoo_ma_atari's indicator bytes of the rows; None for the other agents (``_conv1_family``)."""
         m = obs_u8.shape[0] if inds is None else inds.numel()
-        a1, a2, a3 = bufs.get(m, obs_u8.device, False)
-        ctx.ind = ind
-        if W1.shape[1] == 1:
-            # ppo_atari_lstm.py's conv1 on ONE frame: kernel Q1's ReLU instances (csrc/conv1q1.hip) on (rows, 84, 84) u8 frames, kernel P1 in the
-            # backward; layers 2 / 3 as for the four-frame agents.  The f16x2 split of kernel Z only, as ln_cnn's one-frame node.
-            if ind is not None or not _CONV_Z or bufs.split != "f16x2" or a1.numel() * 4 >= BUF_LIMIT:
-                raise NotImplementedError("MI355PPO_LSTM_TRUNK=fused runs on the f16x2 split of kernel Z only: MI355PPO_SPLIT=bf16x3, MI355PPO_CONV=f "
-                                          f"and batches of {BUF_LIMIT // 51200} images or more (32-bit buffer offsets) are not covered -- use "
-                                          "MI355PPO_LSTM_TRUNK=torch")
-            bt1 = bufs.q1_pack(W1)
-            ctx.bits = None
-            bufs.last_a3_bits = None
-            ctx.f16 = f16 = bufs.f16(obs_u8)
-            grads = _MASK_BITS and want_bits and any(ctx.needs_input_grad)
-            if f16:
-                rec = bufs.begin_pass(m, obs_u8.device)
-                mb1 = mb2 = mb3 = None
-                if grads:
-                    mb1, mb2, mb3 = ctx.bits = bufs.get_bits(m, obs_u8.device)
-                    bufs.last_a3_bits = mb3
-                conv1q1_fwd_amax(obs_u8, bt1, b1.detach(), inds, a1, mb1, bufs.owns(REC_A1, a1))
-                conv_fwd_packed(a1, bufs.conv_zpack(W2, 2, MODE_FWD), b2.detach(), 2, a2, bits=mb2, amax=(rec[REC_A1], bufs.owns(REC_A2, a2)))
-                conv_fwd_packed(a2, bufs.conv_zpack(W3, 3, MODE_FWD), b3.detach(), 3, a3, bits=mb3, amax=(rec[REC_A2], bufs.owns(REC_A3, a3)))
-            else:
-                mb1, mb2, mb3 = bufs.get_bits(m, obs_u8.device)
-                conv1q1_fwd_bits(obs_u8, bt1, b1.detach(), inds, a1, mb1)
-                conv_fwd_packed(a1, bufs.conv_zpack(W2, 2, MODE_FWD), b2.detach(), 2, a2, bits=mb2 if grads else None)
-                conv_fwd_packed(a2, bufs.conv_zpack(W3, 3, MODE_FWD), b3.detach(), 3, a3, bits=mb3 if grads else None)
-                if grads:
-                    ctx.bits = (mb1, mb2, mb3)
-                    bufs.last_a3_bits = mb3
-            ctx.obs, ctx.inds, ctx.acts, ctx.bufs = obs_u8, inds, (a1, a2, a3), bufs
-            ctx.params = (W1, b1, W2, b2, W3, b3)
-            bufs.last_a3_ptr = a3.data_ptr()
-            ctx.save_for_backward(W2, W3)
-            return a3
-        if ind is not None:
-            if not _CONV_Z or a1.numel() * 4 >= BUF_LIMIT:
-                raise NotImplementedError("the row-bias conv1 exists on kernel Q with layers 2 / 3 on kernel Z only (MI355PPO_CONV=f / more "
-                                          "than 83,000 images are not covered)")
-            bt1, tapsum = bufs.ma_pack(W1)
-            ctx.bits = None
-            bufs.last_a3_bits = None
-            ctx.f16 = f16 = bufs.f16(obs_u8)
-            grads = _MASK_BITS and want_bits and any(ctx.needs_input_grad)
-            if f16:
-                rec = bufs.begin_pass(m, obs_u8.device)
-                mb1 = mb2 = mb3 = None
-                if grads:
-                    mb1, mb2, mb3 = ctx.bits = bufs.get_bits(m, obs_u8.device)
-                    bufs.last_a3_bits = mb3
-                ma_conv1_fwd_amax(obs_u8, ind, bt1, tapsum, b1.detach(), inds, a1, mb1, bufs.owns(REC_A1, a1))
-                conv_fwd_packed(a1, bufs.conv_zpack(W2, 2, MODE_FWD), b2.detach(), 2, a2, bits=mb2, amax=(rec[REC_A1], bufs.owns(REC_A2, a2)))
-                conv_fwd_packed(a2, bufs.conv_zpack(W3, 3, MODE_FWD), b3.detach(), 3, a3, bits=mb3, amax=(rec[REC_A2], bufs.owns(REC_A3, a3)))
-            else:
-                mb1, mb2, mb3 = bufs.get_bits(m, obs_u8.device)
-                ma_conv1_fwd_bits(obs_u8, ind, bt1, tapsum, b1.detach(), inds, a1, mb1)
-                conv_fwd_packed(a1, bufs.conv_zpack(W2, 2, MODE_FWD), b2.detach(), 2, a2, bits=mb2 if grads else None)
-                conv_fwd_packed(a2, bufs.conv_zpack(W3, 3, MODE_FWD), b3.detach(), 3, a3, bits=mb3 if grads else None)
-                if grads:
-                    ctx.bits = (mb1, mb2, mb3)
-                    bufs.last_a3_bits = mb3
-            ctx.obs, ctx.inds, ctx.acts, ctx.bufs = obs_u8, inds, (a1, a2, a3), bufs
-            ctx.params = (W1, b1, W2, b2, W3, b3)
-            bufs.last_a3_ptr = a3.data_ptr()
-            ctx.save_for_backward(W2, W3)
-            return a3
-        if a1.numel() * 4 >= BUF_LIMIT:     # beyond 32-bit buffer offsets: the f32-pipe kernels with 64-bit pointers (kernel S) throughout
+        dev = obs_u8.device
+        a1, a2, a3 = bufs.get(m, dev, False)
+        beyond = a1.numel() * 4 >= BUF_LIMIT     # kernels Z / F address a tensor with 32-bit buffer offsets
+        four = W1.shape[1] != 1 and ind is None   # only the four-frame conv1 has the legacy routes (bf16x3 without bits, kernel F, kernel S)
+        if W1.shape[1] == 1 and (ind is not None or not _CONV_Z or bufs.split != "f16x2" or beyond):
+            raise NotImplementedError("MI355PPO_LSTM_TRUNK=fused runs on the f16x2 split of kernel Z only: MI355PPO_SPLIT=bf16x3, MI355PPO_CONV=f "
+                                      f"and batches of {BUF_LIMIT // 51200} images or more (32-bit buffer offsets) are not covered -- use "
+                                      "MI355PPO_LSTM_TRUNK=torch")
+        if not four and (not _CONV_Z or beyond):
+            raise NotImplementedError("the row-bias conv1 exists on kernel Q with layers 2 / 3 on kernel Z only (MI355PPO_CONV=f / more "
+                                      "than 83,000 images are not covered)")
+        packs, fwd_amax, fwd_bits, _ = _conv1_family(W1, ind)
+        # a backward will follow (the caller saw gradients enabled; inside forward() they never are): every forward also writes its ReLU mask
+        # as bits -- the data gradients then read 1/32 of the mask bytes (the f32 activations stay: the weight gradients read them)
+        grads = want_bits and any(ctx.needs_input_grad)
+        ctx.ind, ctx.bits = ind, None
+        if beyond:                              # the f32-pipe kernels with 64-bit pointers (kernel S) throughout
             conv_fwd(obs_u8, bufs.weights(W1, 1, MODE_FWD), b1.detach(), 1, inds, a1)
             conv_fwd(a1, bufs.weights(W2, 2, MODE_FWD), b2.detach(), 2, None, a2)
             conv_fwd(a2, bufs.weights(W3, 3, MODE_FWD), b3.detach(), 3, None, a3)
-            ctx.obs, ctx.inds, ctx.acts, ctx.bufs, ctx.bits = obs_u8, inds, (a1, a2, a3), bufs, None
-            ctx.params = (W1, b1, W2, b2, W3, b3)
-            bufs.last_a3_ptr, bufs.last_a3_bits = a3.data_ptr(), None
-            ctx.save_for_backward(W2, W3)
-            return a3
-        # layer 1 runs on the integer matrix pipe (kernel Q): uint8 taps are exact int8 operands, weights four int8 digits
-        bt1 = bufs.weights(W1, 1, MODE_FWD_Q)
-        ctx.bits = None
-        bufs.last_a3_bits = None
-        ctx.f16 = f16 = bufs.f16(obs_u8)
-        if f16:
+        elif bufs.f16(obs_u8):
             # the two-term f16 split (csrc/f16split.h): every forward folds its output's maximum into the tensor's amax record, the
             # next layer scales its A operand by it; one fill zeroes the records of this forward and of the backward that may follow
-            rec = bufs.begin_pass(m, obs_u8.device)
+            bt1 = packs(bufs)
+            rec = bufs.begin_pass(m, dev)
             mb1 = mb2 = mb3 = None
-            if _MASK_BITS and want_bits and any(ctx.needs_input_grad):
-                mb1, mb2, mb3 = ctx.bits = bufs.get_bits(m, obs_u8.device)
-                bufs.last_a3_bits = mb3
-            conv1q_fwd_amax(obs_u8, bt1, b1.detach(), inds, a1, mb1, bufs.owns(REC_A1, a1))
+            if grads:
+                mb1, mb2, mb3 = ctx.bits = bufs.get_bits(m, dev)
+            fwd_amax(obs_u8, *bt1, b1.detach(), inds, a1, mb1, bufs.owns(REC_A1, a1))
             conv_fwd_packed(a1, bufs.conv_zpack(W2, 2, MODE_FWD), b2.detach(), 2, a2, bits=mb2, amax=(rec[REC_A1], bufs.owns(REC_A2, a2)))
             conv_fwd_packed(a2, bufs.conv_zpack(W3, 3, MODE_FWD), b3.detach(), 3, a3, bits=mb3, amax=(rec[REC_A2], bufs.owns(REC_A3, a3)))
-        elif _CONV_Z and _MASK_BITS and want_bits and any(ctx.needs_input_grad):
-            # a backward will follow (the caller saw gradients enabled; inside forward() they never are): every forward also writes its ReLU mask as bits -- the data gradients then read 1/32 of the
-            # mask bytes (the f32 activations stay: the weight gradients read them)
-            mb1, mb2, mb3 = bufs.get_bits(m, obs_u8.device)
-            conv1q_fwd_bits(obs_u8, bt1, b1.detach(), inds, a1, mb1)
-            conv_fwd_packed(a1, bufs.conv_zpack(W2, 2, MODE_FWD), b2.detach(), 2, a2, bits=mb2)
-            conv_fwd_packed(a2, bufs.conv_zpack(W3, 3, MODE_FWD), b3.detach(), 3, a3, bits=mb3)
-            ctx.bits = (mb1, mb2, mb3)
-            bufs.last_a3_bits = mb3
-        elif _CONV_Z:               # layers 2 and 3 on kernel Z (bf16 pipe, pre-split weights, coalesced window loads)
-            conv_fwd(obs_u8, bt1, b1.detach(), 1, inds, a1, variant=VARIANT_Q)
-            conv_fwd_packed(a1, bufs.conv_zpack(W2, 2, MODE_FWD), b2.detach(), 2, a2)
-            conv_fwd_packed(a2, bufs.conv_zpack(W3, 3, MODE_FWD), b3.detach(), 3, a3)
-        elif m <= 4096 and obs_u8.is_contiguous() and tuple(obs_u8.shape[1:]) == (84, 84, 4):     # inference-sized: one call
-            bt2, bt3 = bufs.weights(W2, 2, MODE_FWD), bufs.weights(W3, 3, MODE_FWD)
-            trunk_fwd(obs_u8, inds, bt1, b1.detach(), bt2, b2.detach(), bt3, b3.detach(), a1, a2, a3, conv1_variant=VARIANT_Q)
+        elif _CONV_Z and (grads or not four):
+            # kernel Z on the bf16 split.  The ma and one-frame conv1 have no instance without mask words: they always get theirs (reachable
+            # with the tests' CPU stand-ins only -- on a device f16x2 and kernel Z imply the branch above)
+            bt1 = packs(bufs)
+            mb1, mb2, mb3 = bufs.get_bits(m, dev)
+            fwd_bits(obs_u8, *bt1, b1.detach(), inds, a1, mb1)
+            conv_fwd_packed(a1, bufs.conv_zpack(W2, 2, MODE_FWD), b2.detach(), 2, a2, bits=mb2 if grads else None)
+            conv_fwd_packed(a2, bufs.conv_zpack(W3, 3, MODE_FWD), b3.detach(), 3, a3, bits=mb3 if grads else None)
+            if grads:
+                ctx.bits = (mb1, mb2, mb3)
         else:
-            conv_fwd(obs_u8, bt1, b1.detach(), 1, inds, a1, variant=VARIANT_Q)
-            conv_fwd(a1, bufs.weights(W2, 2, MODE_FWD), b2.detach(), 2, None, a2)
-            conv_fwd(a2, bufs.weights(W3, 3, MODE_FWD), b3.detach(), 3, None, a3)
+            bt1, = packs(bufs)
+            if _CONV_Z:             # layers 2 and 3 on kernel Z (bf16 pipe, pre-split weights, coalesced window loads)
+                conv_fwd(obs_u8, bt1, b1.detach(), 1, inds, a1, variant=VARIANT_Q)
+                conv_fwd_packed(a1, bufs.conv_zpack(W2, 2, MODE_FWD), b2.detach(), 2, a2)
+                conv_fwd_packed(a2, bufs.conv_zpack(W3, 3, MODE_FWD), b3.detach(), 3, a3)
+            elif m <= 4096 and obs_u8.is_contiguous() and tuple(obs_u8.shape[1:]) == (84, 84, 4):     # inference-sized: one call
+                bt2, bt3 = bufs.weights(W2, 2, MODE_FWD), bufs.weights(W3, 3, MODE_FWD)
+                trunk_fwd(obs_u8, inds, bt1, b1.detach(), bt2, b2.detach(), bt3, b3.detach(), a1, a2, a3, conv1_variant=VARIANT_Q)
+            else:
+                conv_fwd(obs_u8, bt1, b1.detach(), 1, inds, a1, variant=VARIANT_Q)
+                conv_fwd(a1, bufs.weights(W2, 2, MODE_FWD), b2.detach(), 2, None, a2)
+                conv_fwd(a2, bufs.weights(W3, 3, MODE_FWD), b3.detach(), 3, None, a3)
         ctx.obs, ctx.inds, ctx.acts, ctx.bufs = obs_u8, inds, (a1, a2, a3), bufs
         ctx.params = (W1, b1, W2, b2, W3, b3)
-        bufs.last_a3_ptr = a3.data_ptr()
+        bufs.last_a3_ptr, bufs.last_a3_bits = a3.data_ptr(), ctx.bits[2] if ctx.bits else None
         ctx.save_for_backward(W2, W3)
         return a3
 
@@ -940,22 +895,7 @@ class NatureTrunkFn(torch.autograd.Function):
         direct = ctx.bufs.direct_grads and all(p.grad is not None for p in ctx.params)
         gout = (lambda l: (ctx.params[2 * l - 2].grad, ctx.params[2 * l - 1].grad)) if direct else (lambda l: None)
         none = (None,) * (10 if ctx.ind is None else 11)
-        if ctx.ind is not None:
-            # kernel P runs unchanged on the four-channel rows into a (32, 4, 8, 8) temporary (one address per trunk: captured slots replay it) and
-            # writes db1 where it belongs; the fold writes all six channels of the gradient
-            W1, key = ctx.params[0], ("ma_dw4", a3.device)
-            dW4 = ctx.bufs.by_m.get(key)
-            if dW4 is None:
-                dW4 = ctx.bufs.by_m[key] = torch.empty((32, 4, 8, 8), dtype=torch.float32, device=a3.device)
-            db1 = ctx.params[1].grad if direct else torch.empty(32, dtype=torch.float32, device=a3.device)
-
-            def wgrad1(amax):
-                conv_wgrad(ctx.obs, dz1, 1, ctx.inds, out=(dW4, db1), amax=amax)
-                return ma_conv1_wgrad_fold(dz1, ctx.ind, ctx.inds, dW4, out=W1.grad if direct else None), db1
-        elif ctx.params[0].shape[1] == 1:       # one frame: kernel P1 (dz in two f16 terms under its record, whichever path produced dz1)
-            wgrad1 = lambda amax: conv1p1_wgrad(ctx.obs, dz1, ctx.bufs.rec_of(REC_DZ1, dz1), ctx.inds, out=gout(1))
-        else:
-            wgrad1 = lambda amax: conv_wgrad(ctx.obs, dz1, 1, ctx.inds, out=gout(1), amax=amax)
+        wgrad1 = lambda amax: _conv1_family(ctx.params[0], ctx.ind)[3](ctx, dz1, direct, gout, amax)
         if ctx.bufs.f16(dz3) and a1.numel() * 4 < BUF_LIMIT:      # the two-term f16 split (records: from the producers, else computed here)
             bufs, bits = ctx.bufs, ctx.bits
             r3 = bufs.rec_of(REC_DZ3, dz3)          # filled by the FC data gradient's epilogue when it produced dz3

@@ -362,18 +362,18 @@ class PPOLearner:
     def _heads_rollout(self, obs_rows, ind=None):
         """Policy/value heads on one slot of the rollout buffer (HIP path); ``ind``: the slot's indicator bytes (MI355PPO_MA_ATARI=fused)."""
         if self.image and self.fused_cnn:
-            if self.agent._trunk is None:
-                from . import cnn
-
-                self.agent._trunk = cnn.NatureTrunk()
-            self._own_trunk_buffers()
+            self._owned_trunk()
             return self.agent.heads_u8(obs_rows, None, ind) if self.ma_fused else self.agent.heads_u8(obs_rows)
         return self.agent.heads(self._features(obs_rows))
 
-    def _own_trunk_buffers(self) -> None:
-        """This learner owns the trunk's buffers: it bumps ``weights_version`` after every optimiser step (cached packs), and its
-        flat gradient buffer is zeroed by the optimizer kernel before every backward, so the backward nodes may write parameter
-        gradients straight into the ``.grad`` views (``direct_grads``)."""
+    def _owned_trunk(self):
+        """The agent's ``cnn.NatureTrunk`` (made here when the agent has not run yet), its buffers owned by this learner: it bumps
+        ``weights_version`` after every optimiser step (cached packs), and its flat gradient buffer is zeroed by the optimizer kernel
+        before every backward, so the backward nodes may write parameter gradients straight into the ``.grad`` views (``direct_grads``)."""
+        if self.agent._trunk is None:
+            from . import cnn
+
+            self.agent._trunk = cnn.NatureTrunk()
         bufs = self.agent._trunk.bufs
         bufs.cache_weights = True
         if not getattr(bufs, "_owned", False):
@@ -383,6 +383,7 @@ class PPOLearner:
             bufs.direct_grads = type(self).forward_backward_hip is PPOLearner.forward_backward_hip
             if self._ar_early is not None:              # world > 1: the early bucket's all-reduce starts when its gradient is final
                 bufs.after_fc_wgrad = self._early_all_reduce
+        return self.agent._trunk
 
     def warm_rollout_caches(self) -> None:
         """Re-derive the cached forward matrices on the current stream, so that the env-group lanes of a rollout
@@ -391,10 +392,7 @@ class PPOLearner:
             return
         from . import cnn
 
-        if self.agent._trunk is None:
-            self.agent._trunk = cnn.NatureTrunk()
-        bufs, net = self.agent._trunk.bufs, self.agent.network
-        self._own_trunk_buffers()
+        bufs, net = self._owned_trunk().bufs, self.agent.network
         if self.ma_fused:
             bufs.pack_params = (net[0].weight, net[2].weight, net[4].weight, net[7].weight)
             bufs.ma_pack(net[0].weight)
@@ -436,11 +434,7 @@ class PPOLearner:
                                            logprob_out=self.logprobs[step][lo:hi], value_out=self.values[step][lo:hi])[0]
         if self.hip and self.discrete and self.image and self.fused_cnn and hasattr(self.agent, "act_u8") and _FUSED_ACT:
             # trunk, then Linear(3136,512) + heads + Categorical draw in two launches; action / log-prob / value written in place
-            if self.agent._trunk is None:
-                from . import cnn
-
-                self.agent._trunk = cnn.NatureTrunk()
-            self._own_trunk_buffers()
+            self._owned_trunk()
             seed, off = (self.agent.rng.seed, self.agent.rng.offset + 1) if rng_offset is None else (self.agent.rng.seed, int(rng_offset))
             ind = (self.ind[step][lo:hi],) if self.ma_fused else ()
             r = self.agent.act_u8(self.obs[step][lo:hi], *ind, seed, off, rng_base, self.actions[step][lo:hi], self.logprobs[step][lo:hi],
@@ -590,11 +584,7 @@ class PPOLearner:
         a = self.args
         B, M = self.batch_size, self.minibatch_size
         if self.hip and self.image and self.fused_cnn:
-            if self.agent._trunk is None:
-                from . import cnn
-
-                self.agent._trunk = cnn.NatureTrunk()
-            self._own_trunk_buffers()
+            self._owned_trunk()
         b_inds = np.arange(B)                                             # :312
         b_obs = self.obs.reshape((-1,) + self.obs_shape)                  # :304-309, views
         b_actions = self.actions.reshape((-1,) + self.act_shape)

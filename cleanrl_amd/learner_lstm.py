@@ -55,13 +55,9 @@ class LSTMPPOLearner(PPOLearner):
     # ------------------------------------------------------------------ rollout
     def _heads_seq(self, obs_rows, inds, lstm_state, done):
         """``agent.heads_seq`` on uint8 rows (HIP path): through K5 (gather + convert) and torch's layers, or -- MI355PPO_LSTM_TRUNK=fused --
-        straight into the trunk kernels, whose packs follow the optimizer through ``weights_version`` (``_own_trunk_buffers``)."""
+        straight into the trunk kernels, whose packs follow the optimizer through ``weights_version`` (``_owned_trunk``)."""
         if self.fused_trunk:
-            if self.agent._trunk is None:
-                from . import cnn
-
-                self.agent._trunk = cnn.NatureTrunk()
-            self._own_trunk_buffers()
+            self._owned_trunk()
             return self.agent.heads_seq_u8(obs_rows, inds, lstm_state, done)
         if inds is None:
             return self.agent.heads_seq(self._features(obs_rows), lstm_state, done)

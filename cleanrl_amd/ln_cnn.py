@@ -76,6 +76,16 @@ def fc_pre(a: torch.Tensor, W: torch.Tensor, b: torch.Tensor, bufs, a_rec: torch
     return torch.addmm(b.detach(), a, bufs.fc_weight(W).t(), out=out)
 
 
+def _conv1(W1, bufs):
+    """conv1 by its frame count -> ``(pack getter, pre-activation forward, weight gradient)``: kernels Q1 / P1 on one channel, kernel Q's PRE
+    instance and kernel P on four (``cnn._conv1_family``'s idea for this node; dz1 in two f16 terms under its record, the uint8 frames are
+    exact)."""
+    if W1.shape[1] == 1:
+        return bufs.q1_pack, conv1q1_pre_fwd, conv1p1_wgrad
+    return (lambda W: bufs.weights(W, 1, MODE_FWD_Q), conv1q_pre_fwd,
+            lambda obs, dz1, rec, inds: cnn.conv_wgrad(obs, dz1, 1, inds, amax=(None, rec)))
+
+
 class LnNatureFn(torch.autograd.Function):
     """``h = relu(LN(fc(relu(LN(conv3(relu(LN(conv2(relu(LN(conv1(obs[inds] / 255))))))))))))`` as one autograd node; h is (M, 512)."""
 
@@ -95,10 +105,8 @@ class LnNatureFn(torch.autograd.Function):
         rec = bufs.begin_pass(m, dev)         # one fill zeroes the records of this forward and of the backward that may follow
         grads = bool(want_grads)
         mb1, mb2, mb3 = bufs.get_bits(m, dev) if grads else (None, None, None)
-        if W1.shape[1] == 1:
-            conv1q1_pre_fwd(obs_u8, trunk.q1_pack(W1), b1.detach(), inds, z1)
-        else:
-            conv1q_pre_fwd(obs_u8, bufs.weights(W1, 1, MODE_FWD_Q), b1.detach(), inds, z1)
+        pack1, pre_fwd1, _ = _conv1(W1, bufs)
+        pre_fwd1(obs_u8, pack1(W1), b1.detach(), inds, z1)
         layernorm_relu_fwd(z1, g1.detach(), e1.detach(), 32, 400, LN_EPS, a1, stats[0], stats[1], mb1, bufs.owns(REC_A1, a1))
         conv_pre_packed(a1, bufs.conv_zpack(W2, 2, MODE_FWD), b2.detach(), 2, rec[REC_A1], z2)
         layernorm_relu_fwd(z2, g2.detach(), e2.detach(), 64, 81, LN_EPS, a2, stats[2], stats[3], mb2, bufs.owns(REC_A2, a2))
@@ -142,12 +150,9 @@ class LnNatureFn(torch.autograd.Function):
         r2 = bufs.rec_of(REC_DZ2, dz2)
         dW2, db2 = cnn.conv_wgrad(a1, dz2, 2, amax=(bufs.rec_of(REC_A1, a1), r2))
         cnn.conv_dgrad_packed(dz2, bufs.conv_zpack(W2, 2, MODE_DGRAD_S2), a1, 2, dy1, bits=mb1, amax=(r2, None))
-        # layer 1 (kernel P, dz in two f16 terms; the uint8 frames are exact)
+        # layer 1
         _, dg1, de1 = layernorm_relu_bwd(dy1, z1, stats[0], stats[1], g1.detach(), 32, 400, dz=dz1, amax=bufs.owns(REC_DZ1, dz1))
-        if W1.shape[1] == 1:
-            dW1, db1 = conv1p1_wgrad(ctx.obs, dz1, bufs.rec_of(REC_DZ1, dz1), ctx.inds)
-        else:
-            dW1, db1 = cnn.conv_wgrad(ctx.obs, dz1, 1, ctx.inds, amax=(None, bufs.rec_of(REC_DZ1, dz1)))
+        dW1, db1 = _conv1(W1, bufs)[2](ctx.obs, dz1, bufs.rec_of(REC_DZ1, dz1), ctx.inds)
         return (None, None, None, None, dW1, db1, dg1, de1, dW2, db2, dg2, de2, dW3, db3, dg3, de3, dWf, dbf, dgf, def_)
 
 
@@ -165,31 +170,16 @@ class LnNatureTrunk:
             self.bufs.cache_weights = True
             self.bufs.pack_params = (network[0].weight, network[3].weight, network[6].weight, network[10].weight)
 
-    def q1_pack(self, W: torch.Tensor) -> torch.Tensor:
-        """Kernel Q1's pack of the one-frame conv1 weight, cached like ``bufs``' packs (``cnn._Buffers.q1_pack``: re-derived INTO the same
-        buffer, keyed by ``bufs.weights_version``, the tensor's version counter and its address)."""
-        return self.bufs.q1_pack(W)
-
-    def _key(self, kind, m, dev):
-        return (kind, m, dev, torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0)
-
     def buffers(self, m: int, dev):
         """The pre-activations z1..z3, zf, the output h and the rows' (mean, rstd) of the four LayerNorms, one set per batch size."""
-        key = self._key("fwd", m, dev)
-        b = self._own.get(key)
-        if b is None:
-            f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)      # noqa: E731
-            b = self._own[key] = {"z1": f(m, 20, 20, 32), "z2": f(m, 9, 9, 64), "z3": f(m, 7, 7, 64), "zf": f(m, 512), "h": f(m, 512),
-                                  "stats": f(8, m)}
-        return b
+        shapes = {"z1": (m, 20, 20, 32), "z2": (m, 9, 9, 64), "z3": (m, 7, 7, 64), "zf": (m, 512), "h": (m, 512), "stats": (8, m)}
+        return self._f32("fwd", m, dev, shapes)
 
     def grad_buffers(self, m: int, dev):
-        key = self._key("bwd", m, dev)
-        b = self._own.get(key)
-        if b is None:
-            f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)      # noqa: E731
-            b = self._own[key] = {"dz1": f(m, 20, 20, 32), "dz2": f(m, 9, 9, 64), "dz3": f(m, 7, 7, 64), "dzf": f(m, 512)}
-        return b
+        return self._f32("bwd", m, dev, {"dz1": (m, 20, 20, 32), "dz2": (m, 9, 9, 64), "dz3": (m, 7, 7, 64), "dzf": (m, 512)})
+
+    def _f32(self, kind, m, dev, shapes):
+        return cnn._per_stream(self._own, dev, (kind, m, dev), lambda: {k: torch.empty(s, dtype=torch.float32, device=dev) for k, s in shapes.items()})
 
     def __call__(self, obs_u8, inds, network):
         params = []

@@ -869,3 +869,155 @@ def test_tensors_beyond_4GiB_take_the_64bit_pointer_kernel():
     # sizes -- a routing check, not an accuracy bar: a dropped or doubled image shows as an O(1e-2) difference)
     for i in range(3):
         _close(g_all[i], g0[i] + g1[i], f"trunk dW{i + 1} beyond 4 GiB", tol=2e-3)
+
+
+# ---- which entry points a pass of each trunk node launches, in order: the fence around the host-side dispatch of cnn.py / ln_cnn.py ------
+def _launch_names(kind, cached):
+    """The entry points (without their ``mi355ppo_`` prefix) that pass through ``_launch`` during forward + backward of one node on 5 rollout
+    rows gathered to 3: ``four`` / ``ma`` / ``one`` = ``cnn.NatureTrunkFn``'s conv1 families, then ``LinearReLUHwcFn`` and ``HeadsFn``;
+    ``ln4`` / ``ln1`` = ``ln_cnn.LnNatureFn`` at 4 channels and at 1.  Uncached: one pass on fresh buffers.  Cached (``pack_params`` set as
+    the agents set it): the first pass, which derives every pack, and the second, which must derive none."""
+    import contextlib
+
+    from cleanrl_amd import ln_cnn, ops
+
+    names = []
+
+    def recording(name, dev, *args):
+        names.append(name.removeprefix("mi355ppo_"))
+        return launch(name, dev, *args)
+
+    launch = ops._launch
+    g = torch.Generator().manual_seed(77)
+    channels = {"four": 4, "ma": 6, "one": 1, "ln4": 4, "ln1": 1}[kind]
+    obs = torch.randint(0, 256, (5, 84, 84) if channels == 1 else (5, 84, 84, 4), generator=g, dtype=torch.uint8).to(DEV)
+    ind = torch.tensor([[0, 255], [255, 0], [7, 0], [0, 0], [3, 255]], dtype=torch.uint8).to(DEV) if kind == "ma" else None
+    inds = torch.tensor([4, 1, 1]).to(DEV)
+    torch.manual_seed(78)
+    nn = torch.nn
+    if kind in ("ln4", "ln1"):
+        net = nn.Sequential(nn.Conv2d(channels, 32, 8, stride=4), nn.LayerNorm([32, 20, 20]), nn.ReLU(), nn.Conv2d(32, 64, 4, stride=2),
+                            nn.LayerNorm([64, 9, 9]), nn.ReLU(), nn.Conv2d(64, 64, 3, stride=1), nn.LayerNorm([64, 7, 7]), nn.ReLU(),
+                            nn.Flatten(), nn.Linear(3136, 512), nn.LayerNorm(512), nn.ReLU()).to(DEV)
+        trunk = ln_cnn.LnNatureTrunk(net if cached else None)
+
+        def one_pass():
+            trunk(obs, inds, net).sum().backward()
+    else:
+        net = nn.Sequential(nn.Conv2d(channels, 32, 8, stride=4), nn.ReLU(), nn.Conv2d(32, 64, 4, stride=2), nn.ReLU(),
+                            nn.Conv2d(64, 64, 3, stride=1), nn.ReLU(), nn.Flatten(), nn.Linear(64 * 7 * 7, 512), nn.ReLU()).to(DEV)
+        actor, critic = nn.Linear(512, 6).to(DEV), nn.Linear(512, 1).to(DEV)
+        trunk = cnn.NatureTrunk()
+        if cached:
+            trunk.bufs.cache_weights = True
+            trunk.bufs.pack_params = (net[0].weight, net[2].weight, net[4].weight, net[7].weight)
+
+        def one_pass():
+            feats = trunk(obs, inds, net[0], net[2], net[4], ind=ind)
+            hidden = cnn.LinearReLUHwcFn.apply(feats, net[7].weight, net[7].bias, trunk.bufs)
+            logits, value = cnn.HeadsFn.apply(hidden, actor.weight, actor.bias, critic.weight, critic.bias, trunk.bufs)
+            (logits.sum() + value.sum()).backward()
+
+    passes = []
+    with contextlib.ExitStack() as stack:
+        for mod in (cnn, ops, ln_cnn):               # each bound ``_launch`` at import
+            stack.enter_context(pytest.MonkeyPatch.context()).setattr(mod, "_launch", recording)
+        for _ in range(2 if cached else 1):
+            names.clear()
+            one_pass()
+            passes.append(list(names))
+    torch.cuda.synchronize()
+    return passes
+
+
+# recorded on the tree before the dispatch was folded onto one body (f16x2 split, kernel Z): one string per pass
+LAUNCHES = {
+    ('four', False): [
+        ("cnn_repack_weights_f32 cnn_conv1q_fwd_amax cnn_repack_weights_f32 absmax_f32 fc_pack_f16x2_f32 cnn_conv_fwd_packed_f16x2_f32 "
+         "cnn_repack_weights_f32 absmax_f32 fc_pack_f16x2_f32 cnn_conv_fwd_packed_f16x2_f32 absmax_f32 fc_pack_f16x2_f32 fc_fwd_relu_packed_f16x2_f32 "
+         "heads_fwd_f32 heads_bwd_relu_amax_f32 absmax_f32 fc_pack_f16x2_f32 fc_dgrad_packed_f16x2_f32 fc_wgrad_f16x2_f32 cnn_conv_wgrad_f16x2_f32 "
+         "cnn_repack_weights_f32 absmax_f32 fc_pack_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 cnn_conv_wgrad_f16x2_f32 cnn_repack_weights_f32 "
+         "absmax_f32 fc_pack_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 cnn_conv1_wgrad_f16x2").split(),
+    ],
+    ('four', True): [
+        ("nature_packs_f16x2_f32 cnn_conv1q_fwd_amax cnn_conv_fwd_packed_f16x2_f32 cnn_conv_fwd_packed_f16x2_f32 fc_fwd_relu_packed_f16x2_f32 "
+         "heads_fwd_f32 heads_bwd_relu_amax_f32 fc_dgrad_packed_f16x2_f32 fc_wgrad_f16x2_f32 cnn_conv_wgrad_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 "
+         "cnn_conv_wgrad_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 cnn_conv1_wgrad_f16x2").split(),
+        ("cnn_conv1q_fwd_amax cnn_conv_fwd_packed_f16x2_f32 cnn_conv_fwd_packed_f16x2_f32 fc_fwd_relu_packed_f16x2_f32 heads_fwd_f32 "
+         "heads_bwd_relu_amax_f32 fc_dgrad_packed_f16x2_f32 fc_wgrad_f16x2_f32 cnn_conv_wgrad_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 "
+         "cnn_conv_wgrad_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 cnn_conv1_wgrad_f16x2").split(),
+    ],
+    ('ma', False): [
+        ("ma_atari_conv1_pack_f32 ma_atari_conv1_fwd_amax cnn_repack_weights_f32 absmax_f32 fc_pack_f16x2_f32 cnn_conv_fwd_packed_f16x2_f32 "
+         "cnn_repack_weights_f32 absmax_f32 fc_pack_f16x2_f32 cnn_conv_fwd_packed_f16x2_f32 absmax_f32 fc_pack_f16x2_f32 fc_fwd_relu_packed_f16x2_f32 "
+         "heads_fwd_f32 heads_bwd_relu_amax_f32 absmax_f32 fc_pack_f16x2_f32 fc_dgrad_packed_f16x2_f32 fc_wgrad_f16x2_f32 cnn_conv_wgrad_f16x2_f32 "
+         "cnn_repack_weights_f32 absmax_f32 fc_pack_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 cnn_conv_wgrad_f16x2_f32 cnn_repack_weights_f32 "
+         "absmax_f32 fc_pack_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 cnn_conv1_wgrad_f16x2 ma_atari_conv1_wgrad_fold_f32").split(),
+    ],
+    ('ma', True): [
+        ("nature_packs_f16x2_f32 ma_atari_conv1_pack_f32 ma_atari_conv1_fwd_amax cnn_conv_fwd_packed_f16x2_f32 cnn_conv_fwd_packed_f16x2_f32 "
+         "fc_fwd_relu_packed_f16x2_f32 heads_fwd_f32 heads_bwd_relu_amax_f32 fc_dgrad_packed_f16x2_f32 fc_wgrad_f16x2_f32 cnn_conv_wgrad_f16x2_f32 "
+         "cnn_conv_dgrad_packed_f16x2_f32 cnn_conv_wgrad_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 cnn_conv1_wgrad_f16x2 ma_atari_conv1_wgrad_fold_f32").split(),
+        ("ma_atari_conv1_fwd_amax cnn_conv_fwd_packed_f16x2_f32 cnn_conv_fwd_packed_f16x2_f32 fc_fwd_relu_packed_f16x2_f32 heads_fwd_f32 "
+         "heads_bwd_relu_amax_f32 fc_dgrad_packed_f16x2_f32 fc_wgrad_f16x2_f32 cnn_conv_wgrad_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 "
+         "cnn_conv_wgrad_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 cnn_conv1_wgrad_f16x2 ma_atari_conv1_wgrad_fold_f32").split(),
+    ],
+    ('one', False): [
+        ("cnn_conv1q1_pack cnn_conv1q1_fwd_amax cnn_repack_weights_f32 absmax_f32 fc_pack_f16x2_f32 cnn_conv_fwd_packed_f16x2_f32 "
+         "cnn_repack_weights_f32 absmax_f32 fc_pack_f16x2_f32 cnn_conv_fwd_packed_f16x2_f32 absmax_f32 fc_pack_f16x2_f32 fc_fwd_relu_packed_f16x2_f32 "
+         "heads_fwd_f32 heads_bwd_relu_amax_f32 absmax_f32 fc_pack_f16x2_f32 fc_dgrad_packed_f16x2_f32 fc_wgrad_f16x2_f32 cnn_conv_wgrad_f16x2_f32 "
+         "cnn_repack_weights_f32 absmax_f32 fc_pack_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 cnn_conv_wgrad_f16x2_f32 cnn_repack_weights_f32 "
+         "absmax_f32 fc_pack_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 cnn_conv1p1_wgrad_f16x2").split(),
+    ],
+    ('one', True): [
+        ("cnn_conv1q1_pack cnn_conv1q1_fwd_amax nature_packs_f16x2_f32 cnn_conv_fwd_packed_f16x2_f32 cnn_conv_fwd_packed_f16x2_f32 "
+         "fc_fwd_relu_packed_f16x2_f32 heads_fwd_f32 heads_bwd_relu_amax_f32 fc_dgrad_packed_f16x2_f32 fc_wgrad_f16x2_f32 cnn_conv_wgrad_f16x2_f32 "
+         "cnn_conv_dgrad_packed_f16x2_f32 cnn_conv_wgrad_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 cnn_conv1p1_wgrad_f16x2").split(),
+        ("cnn_conv1q1_fwd_amax cnn_conv_fwd_packed_f16x2_f32 cnn_conv_fwd_packed_f16x2_f32 fc_fwd_relu_packed_f16x2_f32 heads_fwd_f32 "
+         "heads_bwd_relu_amax_f32 fc_dgrad_packed_f16x2_f32 fc_wgrad_f16x2_f32 cnn_conv_wgrad_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 "
+         "cnn_conv_wgrad_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 cnn_conv1p1_wgrad_f16x2").split(),
+    ],
+    ('ln4', False): [
+        ("cnn_repack_weights_f32 cnn_conv1q_pre_fwd layernorm_relu_fwd_f32 cnn_repack_weights_f32 absmax_f32 fc_pack_f16x2_f32 "
+         "cnn_conv_pre_packed_f16x2_f32 layernorm_relu_fwd_f32 cnn_repack_weights_f32 absmax_f32 fc_pack_f16x2_f32 cnn_conv_pre_packed_f16x2_f32 "
+         "layernorm_relu_fwd_f32 absmax_f32 fc_pack_f16x2_f32 fc_pre_packed_f16x2_f32 layernorm_relu_fwd_f32 layernorm_relu_bwd_f32 fc_wgrad_f16x2_f32 "
+         "absmax_f32 fc_pack_f16x2_f32 fc_dgrad_packed_f16x2_f32 layernorm_relu_bwd_f32 cnn_conv_wgrad_f16x2_f32 cnn_repack_weights_f32 absmax_f32 "
+         "fc_pack_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 layernorm_relu_bwd_f32 cnn_conv_wgrad_f16x2_f32 cnn_repack_weights_f32 absmax_f32 "
+         "fc_pack_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 layernorm_relu_bwd_f32 cnn_conv1_wgrad_f16x2").split(),
+    ],
+    ('ln4', True): [
+        ("nature_packs_f16x2_f32 cnn_conv1q_pre_fwd layernorm_relu_fwd_f32 cnn_conv_pre_packed_f16x2_f32 layernorm_relu_fwd_f32 "
+         "cnn_conv_pre_packed_f16x2_f32 layernorm_relu_fwd_f32 fc_pre_packed_f16x2_f32 layernorm_relu_fwd_f32 layernorm_relu_bwd_f32 "
+         "fc_wgrad_f16x2_f32 fc_dgrad_packed_f16x2_f32 layernorm_relu_bwd_f32 cnn_conv_wgrad_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 "
+         "layernorm_relu_bwd_f32 cnn_conv_wgrad_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 layernorm_relu_bwd_f32 cnn_conv1_wgrad_f16x2").split(),
+        ("cnn_conv1q_pre_fwd layernorm_relu_fwd_f32 cnn_conv_pre_packed_f16x2_f32 layernorm_relu_fwd_f32 cnn_conv_pre_packed_f16x2_f32 "
+         "layernorm_relu_fwd_f32 fc_pre_packed_f16x2_f32 layernorm_relu_fwd_f32 layernorm_relu_bwd_f32 fc_wgrad_f16x2_f32 fc_dgrad_packed_f16x2_f32 "
+         "layernorm_relu_bwd_f32 cnn_conv_wgrad_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 layernorm_relu_bwd_f32 cnn_conv_wgrad_f16x2_f32 "
+         "cnn_conv_dgrad_packed_f16x2_f32 layernorm_relu_bwd_f32 cnn_conv1_wgrad_f16x2").split(),
+    ],
+    ('ln1', False): [
+        ("cnn_conv1q1_pack cnn_conv1q1_pre_fwd layernorm_relu_fwd_f32 cnn_repack_weights_f32 absmax_f32 fc_pack_f16x2_f32 "
+         "cnn_conv_pre_packed_f16x2_f32 layernorm_relu_fwd_f32 cnn_repack_weights_f32 absmax_f32 fc_pack_f16x2_f32 cnn_conv_pre_packed_f16x2_f32 "
+         "layernorm_relu_fwd_f32 absmax_f32 fc_pack_f16x2_f32 fc_pre_packed_f16x2_f32 layernorm_relu_fwd_f32 layernorm_relu_bwd_f32 fc_wgrad_f16x2_f32 "
+         "absmax_f32 fc_pack_f16x2_f32 fc_dgrad_packed_f16x2_f32 layernorm_relu_bwd_f32 cnn_conv_wgrad_f16x2_f32 cnn_repack_weights_f32 absmax_f32 "
+         "fc_pack_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 layernorm_relu_bwd_f32 cnn_conv_wgrad_f16x2_f32 cnn_repack_weights_f32 absmax_f32 "
+         "fc_pack_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 layernorm_relu_bwd_f32 cnn_conv1p1_wgrad_f16x2").split(),
+    ],
+    ('ln1', True): [
+        ("cnn_conv1q1_pack cnn_conv1q1_pre_fwd layernorm_relu_fwd_f32 nature_packs_f16x2_f32 cnn_conv_pre_packed_f16x2_f32 layernorm_relu_fwd_f32 "
+         "cnn_conv_pre_packed_f16x2_f32 layernorm_relu_fwd_f32 fc_pre_packed_f16x2_f32 layernorm_relu_fwd_f32 layernorm_relu_bwd_f32 "
+         "fc_wgrad_f16x2_f32 fc_dgrad_packed_f16x2_f32 layernorm_relu_bwd_f32 cnn_conv_wgrad_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 "
+         "layernorm_relu_bwd_f32 cnn_conv_wgrad_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 layernorm_relu_bwd_f32 cnn_conv1p1_wgrad_f16x2").split(),
+        ("cnn_conv1q1_pre_fwd layernorm_relu_fwd_f32 cnn_conv_pre_packed_f16x2_f32 layernorm_relu_fwd_f32 cnn_conv_pre_packed_f16x2_f32 "
+         "layernorm_relu_fwd_f32 fc_pre_packed_f16x2_f32 layernorm_relu_fwd_f32 layernorm_relu_bwd_f32 fc_wgrad_f16x2_f32 fc_dgrad_packed_f16x2_f32 "
+         "layernorm_relu_bwd_f32 cnn_conv_wgrad_f16x2_f32 cnn_conv_dgrad_packed_f16x2_f32 layernorm_relu_bwd_f32 cnn_conv_wgrad_f16x2_f32 "
+         "cnn_conv_dgrad_packed_f16x2_f32 layernorm_relu_bwd_f32 cnn_conv1p1_wgrad_f16x2").split(),
+    ],
+}
+
+
+@pytest.mark.parametrize("cached", [False, True], ids=["uncached", "cached"])
+@pytest.mark.parametrize("kind", ["four", "ma", "one", "ln4", "ln1"])
+def test_the_trunk_nodes_launch_exactly_these_entry_points_in_this_order(kind, cached):
+    got = _launch_names(kind, cached)
+    assert got == LAUNCHES[kind, cached], got

@@ -852,3 +852,258 @@ def test_ppg_hip_branch_world_size_two_allreduce(capsys, monkeypatch):
     assert d <= 1e-7, d
     for k in one.last_aux:
         assert abs(two.last_aux[k] - one.last_aux[k]) <= 1e-6 * max(1.0, abs(one.last_aux[k]))
+
+
+# ---- the conv1 families beside the four-frame one, and the trunk node on its own (no learner) ------------------------------------------
+class FakeCnnFlavours(FakeCnn):
+    """``FakeCnn`` plus CPU stand-ins for the two other conv1 families of ``cnn.NatureTrunkFn``: the row-bias conv1 of
+    ppo_pettingzoo_ma_atari (``ma_conv1_*``: six channels in ``MAAtariAgent._normalise``'s convention -- channels 0 - 3 divided by 255, the
+    two indicator planes constant over a row and unscaled) and the one-frame conv1 of ppo_atari_lstm (``conv1q1_*`` / ``conv1p1_wgrad``:
+    frames (rows, 84, 84) u8, weight (32, 1, 8, 8)).  A pack is again its buffer's address -> the weights AT PACK TIME."""
+
+    def ma_conv1_pack(self, W6, pack=None, tapsum=None):
+        from cleanrl_amd import cnn
+
+        _chk(W6, torch.float32, "W1", (32, 6, 8, 8))
+        pack = torch.empty(cnn.QPACK_NUMEL) if pack is None else pack
+        tapsum = torch.empty(cnn.MA_TAPSUM_NUMEL) if tapsum is None else tapsum
+        _chk(pack, torch.float32, "Bt", (cnn.QPACK_NUMEL,))
+        _chk(tapsum, torch.float32, "tapsum", (cnn.MA_TAPSUM_NUMEL,))
+        snap = W6.detach().clone()
+        self.reg[pack.data_ptr()], self.reg[tapsum.data_ptr()] = (snap, 1, "ma_pack"), (snap, 1, "ma_tapsum")
+        self.repacks += 1
+        return pack, tapsum
+
+    def _ma_fwd(self, obs_u8, ind, pack, tapsum, bias, inds, out):
+        W6, Wt = self._w(pack, 1, ("ma_pack",)), self._w(tapsum, 1, ("ma_tapsum",))
+        assert W6 is Wt, "the pack and the tap sums come from different weights"
+        _chk(obs_u8, torch.uint8, "src")
+        assert tuple(obs_u8.shape[1:]) == (84, 84, 4)
+        _chk(ind, torch.uint8, "ind", (obs_u8.shape[0], 2))
+        if inds is not None:
+            _chk(inds, torch.int64, "inds")
+            obs_u8, ind = obs_u8[inds], ind[inds]
+        planes = ind.float()[:, None, None, :].expand(-1, 84, 84, 2)
+        x = torch.cat([obs_u8.float() / 255.0, planes], dim=3)
+        y = torch.relu(torch.nn.functional.conv2d(x.permute(0, 3, 1, 2), W6, _chk(bias, torch.float32, "bias", (32,)), stride=4)).permute(0, 2, 3, 1)
+        return _chk(out, torch.float32, "out", tuple(y.shape)).copy_(y)
+
+    def ma_conv1_fwd_amax(self, obs_u8, ind, pack, tapsum, bias, inds, out, bits, dst_amax):
+        y = self._ma_fwd(obs_u8, ind, pack, tapsum, bias, inds, out)
+        if bits is not None:
+            self._write_bits(bits, y)
+        self._put(dst_amax, y)
+        return y
+
+    def ma_conv1_fwd_bits(self, obs_u8, ind, pack, tapsum, bias, inds, out, bits):
+        assert bits is not None
+        y = self._ma_fwd(obs_u8, ind, pack, tapsum, bias, inds, out)
+        self._write_bits(bits, y)
+        return y
+
+    def ma_conv1_wgrad_fold(self, dz1, ind, inds, dW4, out=None):
+        images = dz1.shape[0]
+        _chk(dz1, torch.float32, "dz", (images, 20, 20, 32))
+        _chk(ind, torch.uint8, "ind")
+        if inds is not None:
+            _chk(inds, torch.int64, "inds", (images,))
+            ind = ind[inds]
+        assert ind.shape[0] == images
+        _chk(dW4, torch.float32, "dW4", (32, 4, 8, 8))
+        out = torch.empty((32, 6, 8, 8)) if out is None else out
+        _chk(out, torch.float32, "dW", (32, 6, 8, 8))
+        out[:, :4] = dW4
+        out[:, 4:] = (dz1.sum((1, 2)).t() @ ind.float())[:, :, None, None]        # every tap of a constant plane sees the same sum
+        return out
+
+    @staticmethod
+    def _frames(obs_u8, inds):
+        _chk(obs_u8, torch.uint8, "src")
+        assert tuple(obs_u8.shape[1:]) in ((84, 84), (1, 84, 84), (84, 84, 1))
+        frames = obs_u8.view(-1, 84, 84)
+        if inds is not None:
+            frames = frames[_chk(inds, torch.int64, "inds")]
+        return frames.float().unsqueeze(1) / 255.0
+
+    def conv1q1_pack(self, W, out=None):
+        from cleanrl_amd import _lib
+
+        _chk(W, torch.float32, "W", (32, 1, 8, 8))
+        n = _lib.load().mi355ppo_cnn_conv1q1_pack_bytes() // 4
+        out = torch.empty(n) if out is None else out
+        self.reg[_chk(out, torch.float32, "pack", (n,)).data_ptr()] = (W.detach().clone(), 1, "q1_pack")
+        self.repacks += 1
+        return out
+
+    def _q1_fwd(self, obs_u8, pack, bias, inds, out):
+        W = self._w(pack, 1, ("q1_pack",))
+        y = torch.relu(torch.nn.functional.conv2d(self._frames(obs_u8, inds), W, _chk(bias, torch.float32, "bias", (32,)), stride=4))
+        y = y.permute(0, 2, 3, 1)
+        return _chk(out, torch.float32, "out", tuple(y.shape)).copy_(y)
+
+    def conv1q1_fwd_amax(self, obs_u8, pack, bias, inds, out, bits, dst_amax):
+        y = self._q1_fwd(obs_u8, pack, bias, inds, out)
+        if bits is not None:
+            self._write_bits(bits, y)
+        self._put(dst_amax, y)
+        return y
+
+    def conv1q1_fwd_bits(self, obs_u8, pack, bias, inds, out, bits):
+        assert bits is not None, "conv1q1_fwd_bits: the mask words are required"
+        y = self._q1_fwd(obs_u8, pack, bias, inds, out)
+        self._write_bits(bits, y)
+        return y
+
+    def conv1p1_wgrad(self, obs_u8, dz, dz_amax, inds=None, out=None):
+        images = dz.shape[0]
+        _chk(dz, torch.float32, "dz", (images, 20, 20, 32))
+        self._holds(dz_amax, dz, "conv1 (one frame) weight gradient's dz")
+        x = self._frames(obs_u8, inds)
+        assert x.shape[0] == images
+        dW = torch.nn.grad.conv2d_weight(x, (32, 1, 8, 8), dz.permute(0, 3, 1, 2), stride=4)
+        if out is not None:
+            _chk(out[0], torch.float32, "dW", (32, 1, 8, 8)).copy_(dW)
+            _chk(out[1], torch.float32, "db", (32,)).copy_(dz.sum((0, 1, 2)))
+            return out
+        return dW, dz.sum((0, 1, 2))
+
+
+_NODE_STANDINS = ("repack_weights", "conv_fwd", "conv_dgrad", "conv_wgrad", "trunk_fwd", "fc_pack", "fc_pack_f16x2", "conv_fwd_packed",
+                  "conv_dgrad_packed", "conv1q_fwd_bits", "conv1q_fwd_amax", "absmax", "ma_conv1_pack", "ma_conv1_fwd_amax", "ma_conv1_fwd_bits",
+                  "ma_conv1_wgrad_fold", "conv1q1_pack", "conv1q1_fwd_amax", "conv1q1_fwd_bits", "conv1p1_wgrad")
+_NODE_COUNTERS = ("bits_written", "bits_read", "recs_written", "recs_checked", "absmax_calls")
+_NODE_CHANNELS = {"four": 4, "ma": 6, "one": 1}
+
+
+def _node_counts(flavour, f16, grads):
+    """What ONE pass (forward, plus backward with gradients) asks of the stand-ins, read off ``cnn.NatureTrunkFn``:
+    - bits: with gradients the three forwards write their masks and the two conv data gradients read them.  Without: nothing is written on
+      the f16 route or by the four-frame conv1; the other two families' ``*_fwd_bits`` need their words, so conv1 alone writes.
+    - records (f16 route): each forward writes its output's (3) and conv2 / conv3 check their input's (2); backward, the two data
+      gradients write (2) and wgrad3 (2), dgrad3 (1), wgrad2 (2), dgrad2 (1), wgrad1 (1) check.  dz3 comes from torch's
+      threshold_backward: one ``absmax``.  Off the f16 route only kernel P1 (one frame) splits dz1: one ``absmax`` and one check.
+    - matrices, nothing cached: conv1's pack + two forward matrices with their kernel Z packs, two more of each for the data gradients."""
+    return {"bits_written": 3 if grads else 0 if f16 or flavour == "four" else 1,
+            "bits_read": 2 if grads else 0,
+            "recs_written": (5 if grads else 3) if f16 else 0,
+            "recs_checked": (9 if grads else 2) if f16 else 1 if grads and flavour == "one" else 0,
+            "absmax_calls": 1 if grads and (f16 or flavour == "one") else 0,
+            "repacks": 5 if grads else 3,
+            "packs": 4 if grads else 2}
+
+
+def _node_inputs(flavour, gathered):
+    g = torch.Generator().manual_seed(2300 + 10 * _NODE_CHANNELS[flavour] + gathered)
+    obs = torch.randint(0, 256, (5, 84, 84) if flavour == "one" else (5, 84, 84, 4), generator=g, dtype=torch.uint8)
+    ind = torch.tensor([[0, 255], [255, 0], [7, 0], [0, 0], [3, 255]], dtype=torch.uint8) if flavour == "ma" else None
+    inds = torch.tensor([4, 1, 1]) if gathered else None          # a repeated row: the weight gradients must count it twice
+    gh = torch.randn((3 if gathered else 5, 512), generator=g)
+    torch.manual_seed(2400 + _NODE_CHANNELS[flavour])
+    nn = torch.nn
+    net = nn.Sequential(nn.Conv2d(_NODE_CHANNELS[flavour], 32, 8, stride=4), nn.ReLU(), nn.Conv2d(32, 64, 4, stride=2), nn.ReLU(),
+                        nn.Conv2d(64, 64, 3, stride=1), nn.ReLU(), nn.Flatten(), nn.Linear(64 * 7 * 7, 512), nn.ReLU())
+    if flavour == "ma":
+        # the planes hold raw bytes up to 255: at the frame channels' weight scale they put the activations -- and with them the rounding of
+        # two correct f32 sums in different orders, eps x the largest term -- a hundred times above the other families', past atol = 1e-5
+        # (and their weight gradient multiplies every dz1 by up to 255: a smaller upstream gradient keeps that sum's rounding below it too)
+        with torch.no_grad():
+            net[0].weight[:, 4:] /= 255.0
+        gh = gh * 0.05
+    return obs, ind, inds, gh, net
+
+
+def _node_reference(net, flavour, obs, ind, inds, gh, grads):
+    """(a3 in the trunk's (m, 7, 7, 64) layout, h, parameter gradients) of the same ``nn.Sequential`` on the normalised f32 input."""
+    rows = obs if inds is None else obs[inds]
+    if flavour == "one":
+        x = rows.float().unsqueeze(1) / 255.0
+    else:
+        x = rows.float().permute(0, 3, 1, 2) / 255.0
+    if flavour == "ma":
+        v = (ind if inds is None else ind[inds]).float()
+        x = torch.cat([x, v[:, :, None, None].expand(-1, 2, 84, 84)], dim=1)
+    with torch.enable_grad() if grads else torch.no_grad():
+        a3 = net[:6](x)
+        h = net[6:](a3)
+        if grads:
+            (h * gh).sum().backward()
+    g = [p.grad for p in net.parameters()]
+    for p in net.parameters():
+        p.grad = None
+    return a3.detach().permute(0, 2, 3, 1), h.detach(), g
+
+
+def _node_pass(trunk, net, obs, ind, inds, gh, grads):
+    from cleanrl_amd import cnn
+
+    with torch.enable_grad() if grads else torch.no_grad():
+        feats = trunk(obs, inds, net[0], net[2], net[4], ind=ind)
+        a3 = feats.detach().clone().view(-1, 7, 7, 64)
+        assert trunk.bufs.last_a3_ptr == feats.data_ptr() and (trunk.bufs.last_a3_bits is not None) == grads
+        h = cnn.LinearReLUHwcFn.apply(feats, net[7].weight, net[7].bias, trunk.bufs)
+        if grads:
+            (h * gh).sum().backward()
+    g = [p.grad for p in net.parameters()]
+    for p in net.parameters():
+        p.grad = None
+    return a3, h.detach(), g
+
+
+def _node_agrees(got, want, grads, what):
+    names = ("a3", "h") + tuple(f"grad[{i}]" for i in range(8))
+    tensors = [(got[0], want[0]), (got[1], want[1])] + (list(zip(got[2], want[2])) if grads else [])
+    for name, (a, b) in zip(names, tensors):
+        assert a is not None and torch.allclose(a, b, atol=1e-5), f"{what}: {name} differs by {(a - b).abs().max().item()}"
+
+
+def _node_delta(fk, before):
+    now = {k: getattr(FakeCnn, k) for k in _NODE_COUNTERS}
+    now.update(repacks=fk.repacks, packs=getattr(fk, "packs", 0))
+    return {k: now[k] - before.get(k, 0) for k in now}, now
+
+
+@pytest.mark.parametrize("gathered", [True, False], ids=["inds", "all_rows"])
+@pytest.mark.parametrize("cached", [False, True], ids=["uncached", "cached"])
+@pytest.mark.parametrize("grads", [True, False], ids=["grads", "no_grads"])
+@pytest.mark.parametrize("f16", [True, False], ids=["f16", "no_f16"])
+@pytest.mark.parametrize("flavour", ["four", "ma", "one"])
+def test_trunk_node_flavours_on_the_stand_ins(monkeypatch, flavour, f16, grads, cached, gathered):
+    """``cnn.NatureTrunk`` + ``LinearReLUHwcFn`` alone, for each conv1 family: a3, h and every parameter gradient against torch's layers,
+    and exactly the records, mask words and matrices ``_node_counts`` derives.  ``cached``: a second pass re-derives nothing; after an
+    in-place change of every weight and a ``weights_version`` bump a third re-derives everything INTO the same buffers (a stale pack would
+    compute with the snapshot it was made from and miss the comparison)."""
+    from cleanrl_amd import cnn
+
+    fk = FakeCnnFlavours()
+    for name in _NODE_STANDINS:
+        monkeypatch.setattr(cnn, name, getattr(fk, name))
+    for k in _NODE_COUNTERS:
+        setattr(FakeCnn, k, 0)
+    obs, ind, inds, gh, net = _node_inputs(flavour, gathered)
+    trunk = cnn.NatureTrunk()
+    trunk.bufs.split = "f16x2"
+    trunk.bufs.f16_on_cpu = f16
+    trunk.bufs.cache_weights = cached
+    want = _node_counts(flavour, f16, grads)
+    _node_agrees(_node_pass(trunk, net, obs, ind, inds, gh, grads), _node_reference(net, flavour, obs, ind, inds, gh, grads), grads, "first pass")
+    delta, seen = _node_delta(fk, {})
+    assert delta == want, (delta, want)
+    if not cached:
+        assert not trunk.bufs._bt
+        return
+    addresses = {k: v[1].data_ptr() for k, v in trunk.bufs._bt.items()}
+    conv1_keys = {"four": {(1, cnn.MODE_FWD_Q)}, "ma": {(1, cnn.MODE_FWD_Q), "ma_tapsum"}, "one": {"q1_pack"}}[flavour]
+    fwd_keys = conv1_keys | {(2, cnn.MODE_FWD), (3, cnn.MODE_FWD), ("zpack", 2, cnn.MODE_FWD), ("zpack", 3, cnn.MODE_FWD), "fc"}
+    bwd_keys = {(3, cnn.MODE_DGRAD_S1), (2, cnn.MODE_DGRAD_S2), ("zpack", 3, cnn.MODE_DGRAD_S1), ("zpack", 2, cnn.MODE_DGRAD_S2)}
+    assert set(addresses) == fwd_keys | (bwd_keys if grads else set())
+    _node_pass(trunk, net, obs, ind, inds, gh, grads)                      # nothing changed: nothing is derived again
+    delta, seen = _node_delta(fk, seen)
+    assert delta == dict(want, repacks=0, packs=0), (delta, want)
+    with torch.no_grad():
+        for i in (0, 2, 4, 7):
+            net[i].weight.mul_(0.75)
+    trunk.bufs.weights_version += 1
+    _node_agrees(_node_pass(trunk, net, obs, ind, inds, gh, grads), _node_reference(net, flavour, obs, ind, inds, gh, grads), grads, "after the step")
+    delta, seen = _node_delta(fk, seen)
+    assert delta == want, (delta, want)
+    assert {k: v[1].data_ptr() for k, v in trunk.bufs._bt.items()} == addresses      # captured graphs replay these addresses

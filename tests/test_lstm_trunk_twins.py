@@ -2,8 +2,9 @@
 on one uint8 frame -- against float64, against the pre-activation twin, its mask words and amax record; the MI355PPO_LSTM_TRUNK switch; the
 new C ABI symbols.  Runs without a GPU.
 
-The one-frame branch of ``cnn.NatureTrunkFn`` is not run here: layers 2 / 3 and the FC layer have no host twins (the node runs on device
-tensors only), so that path is covered on the GPU (tests/test_gpu_lstm_trunk.py)."""
+The one-frame family of ``cnn.NatureTrunkFn`` is not run here: layers 2 / 3 and the FC layer have no host twins (the node runs on device
+tensors only), so its arithmetic is covered on the GPU (tests/test_gpu_lstm_trunk.py) and its dispatch on CPU stand-ins
+(tests/test_hip_branches_on_fake_ops.py)."""
 import os
 import re
 from types import SimpleNamespace
