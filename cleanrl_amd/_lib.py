@@ -351,6 +351,15 @@ SIGNATURES = {
     "mi355ppo_cnn_conv1q1_fwd_bits": (c_int, [_P] * 6 + [c_int64, _P]),
     "mi355ppo_cnn_conv1q1_fwd_amax": (c_int, [_P] * 6 + [c_int64, _P, _P]),
     "mi355ppo_cnn_conv1q1_fwd_cpu": (c_int, [_P] * 7 + [c_int64]),
+    # LeakyReLU of RNDModel's stacks (added under ABI 2.7.1, csrc/leaky.hip)
+    "mi355ppo_leaky_relu_fwd_f32": (c_int, [_P] * 4 + [c_int64, c_double, _P]),
+    "mi355ppo_leaky_relu_fwd_f32_cpu": (c_int, [_P] * 4 + [c_int64, c_double]),
+    "mi355ppo_leaky_relu_bwd_f32": (c_int, [_P] * 4 + [c_int64, c_double, _P]),
+    "mi355ppo_leaky_relu_bwd_f32_cpu": (c_int, [_P] * 4 + [c_int64, c_double]),
+    # the normalising one-frame conv1 of RNDModel's stacks (added under ABI 2.7.1, csrc/rnd_conv1.hip)
+    "mi355ppo_rnd_conv1_fwd_f16x2": (c_int, [_P, c_int64, c_int64, c_int, c_int64] + [_P] * 8 + [c_int, c_double, _P]),
+    "mi355ppo_rnd_conv1_wgrad_workspace_bytes": (c_size_t, [c_int64]),
+    "mi355ppo_rnd_conv1_wgrad_f16x2": (c_int, [_P, c_int64, c_int64, c_int, c_int64] + [_P] * 6 + [c_int64, _P, c_size_t, _P, _P]),
 }
 
 ABI_VERSION = 271       # == MI355PPO_VERSION of include/mi355ppo.h this binding was written against (major*100 + minor*10 + patch)

@@ -114,7 +114,8 @@ class _NatureTrunkMixin:
         if self._trunk is None:
             self._trunk = cnn.NatureTrunk()
         net = self.network
-        self._trunk.bufs.pack_params = (net[0].weight, net[2].weight, net[4].weight, net[7].weight)
+        if net[7].out_features == 512:      # the all-packs launch is sized for Linear(3136, 512); RNDAgent's 256 rows derive pack by pack
+            self._trunk.bufs.pack_params = (net[0].weight, net[2].weight, net[4].weight, net[7].weight)
         return self._trunk
 
     def _hidden_u8(self, obs_rows, inds=None, ind=None):
@@ -610,7 +611,7 @@ class ProcgenAgent(_DiscreteMixin, nn.Module):
         return action, lp, ent, value
 
 
-class RNDAgent(_DiscreteMixin, nn.Module):
+class RNDAgent(_NatureTrunkMixin, _DiscreteMixin, nn.Module):
     """ppo_rnd_envpool.py:139-185: NatureCNN -> Linear(3136,256) -> Linear(256,448), a 448-448 "extra" layer feeding two
     value heads (extrinsic / intrinsic) through a residual sum, and a two-layer actor.  Same construction order as the
     reference."""
@@ -651,10 +652,19 @@ class RNDAgent(_DiscreteMixin, nn.Module):
 
     def heads3(self, xn):
         """xn: normalised f32 observations (B,4,84,84) -> (logits, extrinsic value, intrinsic value)."""
-        hidden = self.network(xn)
+        return self._heads3(self.network(xn))
+
+    def _heads3(self, hidden):
         logits = self.actor(hidden)
         features = self.extra_layer(hidden)
         return logits, self.critic_ext(features + hidden), self.critic_int(features + hidden)
+
+    def heads3_u8(self, obs_rows, inds=None):
+        """``heads3(obs_rows[inds] / 255.0)`` on the uint8 (rows, 84, 84, 4) rollout rows (MI355PPO_RND_TRUNK=fused): ``network[0:9]`` --
+        the three convolutions and Linear(3136, 256) + ReLU -- on the trunk kernels (``_hidden_u8``: gather and /255 inside conv1);
+        ``network[9:]``, the extra layer, the actor and the two critics stay torch modules."""
+        net = self.network
+        return self._heads3(net[10](net[9](self._hidden_u8(obs_rows, inds))))
 
     def get_action_and_value(self, x, action=None):
         logits, v_ext, v_int = self.heads3(self._normalise(x))

@@ -14,8 +14,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libmi355ppo.so")
-SOURCES = ["api.hip", "gae.hip", "distributions.hip", "loss.hip", "obs.hip", "optim.hip", "conv.hip", "convw.hip", "conv1q.hip", "conv1q1.hip", "conv1p.hip", "conv1p1.hip", "gemmz.hip", "gemmg.hip", "gemmh.hip", "convr.hip", "convrb.hip", "convrs.hip", "convrv.hip", "convu.hip", "fcw.hip", "heads.hip", "mlp.hip", "synth_env.hip", "dpcomm.hip", "lstm.hip", "trxl_attn.hip", "impala.hip", "pqn.hip", "pqn_lstm.hip", "offpolicy.hip", "sac.hip", "dqn.hip", "dqn_atari.hip", "rainbow.hip", "rainbow_twins.hip", "sac_atari.hip", "sac_atari_twins.hip", "qdagger.hip", "rnd.hip", "ppg.hip", "ppg_twins.hip", "ma_atari.hip", "ma_atari_twins.hip", "layernorm.hip", "layernorm_twins.hip", "host_twins.hip"]
-HEADERS = ["common.h", "catrow.h", "ppo_rows.h", "lstm_rows.h", "trxl_rows.h", "impala_rows.h", "pqn_rows.h", "pqn_lstm_rows.h", "offpolicy_rows.h", "offpolicy_wg.h", "qhead_wg.h", "sac_rows.h", "dqn_rows.h", "dqn_atari_rows.h", "rainbow_rows.h", "sac_atari_rows.h", "qdagger_rows.h", "rnd_rows.h", "ppg_rows.h", "ma_atari_rows.h", "layernorm_rows.h", "conv1q_pack.h", "conv1q1_pack.h", "bf16split.h", "f16split.h", "conv_resident.h", "conv_resident_geom.h", "convr_geom.h", "convrb_geom.h", "convrs_geom.h", "convrv_geom.h", os.path.join("..", "..", "include", "mi355ppo.h")]
+SOURCES = ["api.hip", "gae.hip", "distributions.hip", "loss.hip", "obs.hip", "optim.hip", "conv.hip", "convw.hip", "conv1q.hip", "conv1q1.hip", "conv1p.hip", "conv1p1.hip", "gemmz.hip", "gemmg.hip", "gemmh.hip", "convr.hip", "convrb.hip", "convrs.hip", "convrv.hip", "convu.hip", "fcw.hip", "heads.hip", "mlp.hip", "synth_env.hip", "dpcomm.hip", "lstm.hip", "trxl_attn.hip", "impala.hip", "pqn.hip", "pqn_lstm.hip", "offpolicy.hip", "sac.hip", "dqn.hip", "dqn_atari.hip", "rainbow.hip", "rainbow_twins.hip", "sac_atari.hip", "sac_atari_twins.hip", "qdagger.hip", "rnd.hip", "rnd_conv1.hip", "ppg.hip", "ppg_twins.hip", "ma_atari.hip", "ma_atari_twins.hip", "layernorm.hip", "layernorm_twins.hip", "leaky.hip", "leaky_twins.hip", "host_twins.hip"]
+HEADERS = ["common.h", "catrow.h", "ppo_rows.h", "lstm_rows.h", "trxl_rows.h", "impala_rows.h", "pqn_rows.h", "pqn_lstm_rows.h", "offpolicy_rows.h", "offpolicy_wg.h", "qhead_wg.h", "sac_rows.h", "dqn_rows.h", "dqn_atari_rows.h", "rainbow_rows.h", "sac_atari_rows.h", "qdagger_rows.h", "rnd_rows.h", "ppg_rows.h", "ma_atari_rows.h", "layernorm_rows.h", "leaky_rows.h", "conv1q_pack.h", "conv1q1_pack.h", "bf16split.h", "f16split.h", "conv_resident.h", "conv_resident_geom.h", "convr_geom.h", "convrb_geom.h", "convrs_geom.h", "convrv_geom.h", os.path.join("..", "..", "include", "mi355ppo.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: every f32 multiply/add rounds separately, as the reference's un-fused torch ops do.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]

@@ -39,6 +39,12 @@ int conv1p_launch(const unsigned char* src, const int64_t* inds, const float* dz
 // kernel P1 (conv1p1.hip): the same gradient of Conv2d(1, 32, 8, stride=4) on one-channel frames, f16 split of dz; one (32 x 64) partial per wave
 int conv1p1_launch(const unsigned char* src, const int64_t* inds, const float* dz, float* part_w, float* part_b, int images, int grid,
                    hipStream_t s, const unsigned* dz_amax);
+// rnd_conv1.hip: that gradient with the normalised newest frame of RND's observation rows as the staged operand (two f16 terms of x)
+int rnd_conv1_wgrad_launch(const unsigned char* src, int64_t B, int64_t row_bytes, int pixel_stride, int off, const int64_t* idx, const double* mean,
+                           const double* sd, const float* dz, float* part_w, float* part_b, int images, int grid, hipStream_t s,
+                           const unsigned* dz_amax);
+// rnd.hip: the frame addressing every RND entry point checks (row_bytes, pixel_stride, byte_offset)
+int rnd_frame_args(const char* fn, const void* src, int64_t B, int64_t row_bytes, int pixel_stride, int64_t byte_offset);
 // kernel V (convw.hip): layers 2 / 3 weight + bias gradient on the bf16 pipe; returns 1 when the batch does not qualify
 bool convw_applies(int64_t images, int layer, bool f16 = false);      // (f16: the two-tile shape of the f16 split -- 227 instead of 170 slabs on layer 3)
 int convw_parts(int64_t images, int layer);

@@ -1363,3 +1363,44 @@ extern "C" MI355PPO_API int mi355ppo_cnn_conv1p1_wgrad_f16x2(const void* src_u8,
     hipLaunchKernelGGL(conv_wgrad_reduce2, dim3((total_w + 255) / 256), dim3(256), 0, s, mid, nchunks, mid_b, nchunks, 32, 1, 8, 8, kInv255, dW, db);
     return check_launch("conv_wgrad_reduce2");
 }
+
+// The same gradient for RNDModel's conv1 (rnd_conv1.hip): the operand is the normalised newest frame of the observation rows, x in two f16 terms
+// under its static scale, so no factor is left for the reduction.  Kernel P1's grid, partials, workspace layout and folds.
+extern "C" MI355PPO_API size_t mi355ppo_rnd_conv1_wgrad_workspace_bytes(int64_t images) { return mi355ppo_cnn_conv1p1_wgrad_workspace_bytes(images); }
+
+extern "C" MI355PPO_API int mi355ppo_rnd_conv1_wgrad_f16x2(const unsigned char* src, int64_t B, int64_t row_bytes, int pixel_stride,
+                                                           int64_t byte_offset, const int64_t* idx, const double* mean, const double* sd,
+                                                           const float* dz, float* dW, float* db, int64_t images, void* workspace,
+                                                           size_t workspace_bytes, const uint32_t* dz_amax, void* stream) {
+    const char* fn = "mi355ppo_rnd_conv1_wgrad_f16x2";
+    if (int rc = rnd_frame_args(fn, src, B, row_bytes, pixel_stride, byte_offset)) return rc;
+    MI355_REQUIRE(mean && sd && dz && dW && db, MI355PPO_EINVAL, "%s: null pointer", fn);
+    MI355_REQUIRE(dz_amax && aligned(dz_amax, 64), MI355PPO_EINVAL, "%s: dz's amax record missing or not 64-byte aligned", fn);
+    MI355_REQUIRE(images > 0 && images <= (1 << 22) && (idx || images <= B), MI355PPO_EINVAL,
+                  "%s: images=%lld must be in 1..4194304 and, without an index, at most B=%lld", fn, (long long)images, (long long)B);
+    const size_t need = mi355ppo_rnd_conv1_wgrad_workspace_bytes(images);
+    MI355_REQUIRE(workspace && workspace_bytes >= need, MI355PPO_EWORKSPACE, "%s: workspace %zu bytes < required %zu", fn,
+                  workspace ? workspace_bytes : (size_t)0, need);
+    MI355_REQUIRE(aligned(mean, 8) && aligned(sd, 8) && aligned(idx, 8) && aligned(dz, 16) && aligned(dW, 4) && aligned(db, 4) && aligned(workspace, 16),
+                  MI355PPO_EALIGN, "%s: mean / sd / idx must be 8-byte aligned, dz / workspace 16-byte aligned", fn);
+    // Workspace layout: part_w [parts][2048] | part_b [parts][32] | mid [ceil(parts/32)][2048] | mid_b [ceil(parts/32)][32]
+    const int grid = wgrad1c_grid(images), wparts = grid * 4, total_w = 32 * 64;
+    const int nchunks = (wparts + kRedChunk - 1) / kRedChunk;
+    float* part_w = static_cast<float*>(workspace);
+    float* part_b = part_w + (size_t)wparts * total_w;
+    float* mid = part_b + (size_t)wparts * 32;
+    float* mid_b = mid + (size_t)nchunks * total_w;
+    hipStream_t s = as_stream(stream);
+    int rc = rnd_conv1_wgrad_launch(src, B, row_bytes, pixel_stride, (int)byte_offset, idx, mean, sd, dz, part_w, part_b, (int)images, grid, s, dz_amax);
+    if (rc) return rc;
+    if (nchunks <= 8) {
+        hipLaunchKernelGGL(conv_wgrad_reduce12, dim3(total_w / 32 + 1), dim3(256), 0, s, part_w, wparts, total_w, part_b, 32, 1, 8, 8, 1.0f, dW, db);
+        return check_launch("conv_wgrad_reduce12");
+    }
+    hipLaunchKernelGGL(conv_wgrad_reduce1, dim3((total_w + 255) / 256 + 1, nchunks), dim3(256), 0, s, part_w, wparts, total_w, mid, part_b, wparts, 32,
+                       mid_b);
+    rc = check_launch("conv_wgrad_reduce1");
+    if (rc) return rc;
+    hipLaunchKernelGGL(conv_wgrad_reduce2, dim3((total_w + 255) / 256), dim3(256), 0, s, mid, nchunks, mid_b, nchunks, 32, 1, 8, 8, 1.0f, dW, db);
+    return check_launch("conv_wgrad_reduce2");
+}

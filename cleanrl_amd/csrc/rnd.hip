@@ -193,9 +193,7 @@ __global__ __launch_bounds__(kRndFold) void rnd_loss_fold_kernel(const float* __
     }
 }
 
-namespace {
-
-// Shared argument checks of the device entry points and their twins (before any HIP call).
+// Shared argument checks of the device entry points and their twins (before any HIP call).  The frame check is also rnd_conv1.hip's.
 int rnd_frame_args(const char* fn, const void* src, int64_t B, int64_t row_bytes, int pixel_stride, int64_t byte_offset) {
     MI355_REQUIRE(src, MI355PPO_EINVAL, "%s: null pointer", fn);
     MI355_REQUIRE(B > 0, MI355PPO_EINVAL, "%s: B=%lld must be positive", fn, (long long)B);
@@ -212,6 +210,8 @@ int rnd_frame_args(const char* fn, const void* src, int64_t B, int64_t row_bytes
     }
     return MI355PPO_OK;
 }
+
+namespace {
 
 int rnd_normalize_args(const char* fn, const void* src, int64_t B, int64_t row_bytes, int pixel_stride, int64_t byte_offset, const int64_t* idx,
                        const double* mean, const double* sd, float* out, int M) {

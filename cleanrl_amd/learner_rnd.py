@@ -27,6 +27,11 @@ the kernels of csrc/rnd.hip: ``curiosity`` = normalise kernel + 
 of the observation statistics; ``finish_rollout`` = one reward-filter launch on a device (mean, var, count) triple, no host round
 trip; ``update`` = exact integer observation moments of the u8 batch (one 113 KB read-back), the RND input of each minibatch
 normalised straight from the u8 rollout rows, and one loss kernel for the distillation and intrinsic-value terms.
+
+``MI355PPO_RND_TRUNK=fused`` (with ``MI355PPO_RND=fused`` only; default ``torch``) moves the three NatureCNN stacks of a
+minibatch onto the library as well: the agent's trunk through ``RNDAgent.heads3_u8``, the predictor's and the target's one-frame
+LeakyReLU stacks through ``leaky_cnn.LeakyNatureTrunk`` -- all three read the u8 rollout rows, so neither the K5 conversion nor the
+``rnd_normalize`` launch runs and no f32 frame tensor is allocated.
 """
 from __future__ import annotations
 
@@ -84,6 +89,17 @@ def rnd_backend() -> str:
     v = os.environ.get("MI355PPO_RND", "torch").strip().lower() or "torch"
     if v not in ("torch", "fused"):
         raise ValueError(f"MI355PPO_RND={v!r}: expected 'torch' or 'fused'")
+    return v
+
+
+def rnd_trunk_backend() -> str:
+    """``MI355PPO_RND_TRUNK``: ``torch`` (the default) or ``fused`` -- the three NatureCNN stacks of a minibatch straight from the u8
+    rollout rows: the agent's trunk on the kernels of cleanrl_amd/cnn.py (``RNDAgent.heads3_u8``), the predictor's and the target's
+    one-frame LeakyReLU stacks on cleanrl_amd/leaky_cnn.py (csrc/rnd_conv1.hip, csrc/leaky.hip).  HIP learner with
+    ``MI355PPO_RND=fused`` only; read when a learner is built."""
+    v = os.environ.get("MI355PPO_RND_TRUNK", "torch").strip().lower() or "torch"
+    if v not in ("torch", "fused"):
+        raise ValueError(f"MI355PPO_RND_TRUNK={v!r}: expected 'torch' or 'fused'")
     return v
 
 
@@ -156,6 +172,50 @@ class RNDPPOLearner(PPOLearner):
         self.rnd_fused = False
         if self.hip and rnd_backend() == "fused":
             self.init_rnd_fused()
+        self.rnd_trunk_fused = False
+        self.select_rnd_trunk()
+
+    def select_rnd_trunk(self) -> None:
+        """``MI355PPO_RND_TRUNK`` on the HIP learner (the host learner ignores it, as it ignores ``MI355PPO_RND``)."""
+        if self.hip and rnd_trunk_backend() == "fused":
+            if not self.rnd_fused:
+                raise ValueError("MI355PPO_RND_TRUNK=fused needs MI355PPO_RND=fused: it reads the u8 NHWC rollout rows and the device "
+                                 "copies of the observation statistics that backend keeps")
+            self.init_rnd_trunk_fused()
+
+    def init_rnd_trunk_fused(self) -> None:
+        """The state of ``MI355PPO_RND_TRUNK=fused``: the agent's ``cnn.NatureTrunk`` and the predictor's / target's
+        ``leaky_cnn.LeakyNatureTrunk``, each with cached weight packs.  ``optimizer_step_hip`` bumps the ``weights_version`` of the two
+        trained ones after every step, which writes the parameters through raw pointers; the target's packs are derived once."""
+        assert self.rnd_fused and self.nhwc, "MI355PPO_RND_TRUNK=fused runs on the u8 NHWC rollout rows of MI355PPO_RND=fused"
+        from .leaky_cnn import LeakyNatureTrunk
+
+        self.agent._nature_trunk().bufs.cache_weights = True
+        self._rnd_pred = LeakyNatureTrunk(self.rnd_model.predictor, head=True)
+        self._rnd_pred_tail = self.rnd_model.predictor[9:]              # Linear, ReLU, Linear: torch modules on the node's (M, 512)
+        self._rnd_targ = LeakyNatureTrunk(self.rnd_model.target, head=False)
+        self._rnd_x_step = None                                         # no normalised f32 frames under the switch
+        self.rnd_trunk_fused = True
+
+    def _rnd_features(self, rows, idx=None):
+        """(predictor, target) features of the newest frame of ``rows[idx]``, from the u8 rows (``MI355PPO_RND_TRUNK=fused``)."""
+        predict = self._rnd_pred_tail(self._rnd_pred(rows, idx, self._rnd_mean, self._rnd_sd))
+        return predict, self._rnd_targ(rows, idx, self._rnd_mean, self._rnd_sd)
+
+    def optimizer_step_hip(self, lr: float) -> None:
+        super().optimizer_step_hip(lr)
+        if self.rnd_trunk_fused:                    # the kernel rewrote the predictor's parameters through raw pointers too
+            self._rnd_pred.bufs.weights_version += 1
+
+    def _heads3_rows(self, rows, idx=None):
+        """``agent.heads3`` of the u8 rollout rows ``rows[idx]``: the trunk kernels under ``MI355PPO_RND_TRUNK=fused``, else K5 + torch."""
+        if self.rnd_trunk_fused:
+            return self.agent.heads3_u8(rows, idx)
+        if idx is None:
+            return self.agent.heads3(self._features(rows))
+        if self._x_mb is None or self._x_mb.shape[0] != idx.numel():
+            self._x_mb = torch.empty((idx.numel(),) + self.obs_shape, device=self.device)
+        return self.agent.heads3(self.ops.obs_u8_to_f32(rows, idx, self._x_mb).permute(0, 3, 1, 2))
 
     def init_rnd_fused(self) -> None:
         """The state of ``MI355PPO_RND=fused``: device copies of the observation statistics, the filter state and the reward
@@ -195,7 +255,7 @@ class RNDPPOLearner(PPOLearner):
     @torch.no_grad()
     def act(self, step: int):
         if self.hip:
-            logits, v_ext, v_int = self.agent.heads3(self._features(self.obs[step]))
+            logits, v_ext, v_int = self._heads3_rows(self.obs[step])
             seed, off = self.agent.rng.next()
             a64, _, _, _ = self.ops.categorical_sample(logits.contiguous(), seed=seed, offset=off,
                                                        action_f32_out=self.actions[step], logprob_out=self.logprobs[step],
@@ -217,6 +277,10 @@ class RNDPPOLearner(PPOLearner):
         if self.rnd_fused:
             if step == 0:
                 self.refresh_obs_stats()
+            if self.rnd_trunk_fused:
+                predict, target = self._rnd_features(rows)
+                self.ops.rnd_intrinsic_reward(target.contiguous(), predict.contiguous(), out=self.curiosity_rewards[step])
+                return self.curiosity_rewards[step]
             x = self.ops.rnd_normalize(rows, self._rnd_mean, self._rnd_sd, out=self._rnd_x_step)
             self.ops.rnd_intrinsic_reward(self.rnd_model.target(x).contiguous(), self.rnd_model.predictor(x).contiguous(),
                                           out=self.curiosity_rewards[step])
@@ -240,7 +304,7 @@ class RNDPPOLearner(PPOLearner):
             self.reward_rms.update_from_moments(mean, std**2, count)
             self.curiosity_rewards /= np.sqrt(self.reward_rms.var)
         if self.hip:
-            _, v_ext, v_int = self.agent.heads3(self._features(self.boot_obs))
+            _, v_ext, v_int = self._heads3_rows(self.boot_obs)
             self.ops.gae(self.rewards, self.dones, self.values, self.boot_done, v_ext.reshape(-1).contiguous(),
                          a.gamma, a.gae_lambda, self.advantages, self.returns)
             # the intrinsic stream is non-episodic (int_nextnonterminal = 1.0, :413,418): K1 with all-zero dones
@@ -357,14 +421,14 @@ class RNDPPOLearner(PPOLearner):
         """``_minibatch_rnd_hip`` with the RND input normalised from the u8 rows and the two extra loss terms in one kernel."""
         a, ops = self.args, self.ops
         M = idx.numel()
-        if self._rnd_x_mb is None or self._rnd_x_mb.shape[0] != M:
-            self._rnd_x_mb = torch.empty((M, 1, 84, 84), device=self.device)
-        predict, target = self.rnd_model(ops.rnd_normalize(b_obs, self._rnd_mean, self._rnd_sd, idx=idx, out=self._rnd_x_mb))   # :453-458, :463
+        if self.rnd_trunk_fused:
+            predict, target = self._rnd_features(b_obs, idx)                                                  # :453-458, :463 from the u8 rows
+        else:
+            if self._rnd_x_mb is None or self._rnd_x_mb.shape[0] != M:
+                self._rnd_x_mb = torch.empty((M, 1, 84, 84), device=self.device)
+            predict, target = self.rnd_model(ops.rnd_normalize(b_obs, self._rnd_mean, self._rnd_sd, idx=idx, out=self._rnd_x_mb))   # :453-458, :463
         u = torch.rand(M, device=self.device)                                                                 # :467
-        if self._x_mb is None or self._x_mb.shape[0] != M:
-            self._x_mb = torch.empty((M,) + self.obs_shape, device=self.device)
-        x = ops.obs_u8_to_f32(b_obs, idx, self._x_mb).permute(0, 3, 1, 2)
-        logits, v_ext, v_int = self.agent.heads3(x)
+        logits, v_ext, v_int = self._heads3_rows(b_obs, idx)               # K5 gather + torch, or the trunk kernels on the u8 rows
         v_ext, v_int = v_ext.view(-1), v_int.view(-1)
         _, dlogits, dv_ext = ops.ppo_loss_categorical(logits.detach().contiguous(), v_ext.detach().contiguous(), idx, b_actions,
                                                       b_logprobs, b_advantages, b_ext_returns, b_ext_values, a.clip_coef,

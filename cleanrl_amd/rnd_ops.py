@@ -11,9 +11,12 @@ import torch
 
 from .replay_ops import _ptr
 
-OPERATORS = ("rnd_normalize", "rnd_obs_moments", "rnd_intrinsic_reward", "rnd_reward_filter_", "rnd_loss_fwd_bwd")
+OPERATORS = ("rnd_normalize", "rnd_obs_moments", "rnd_intrinsic_reward", "rnd_reward_filter_", "rnd_loss_fwd_bwd",
+             "leaky_relu_fwd", "leaky_relu_bwd")
 
 RND_PIXELS, RND_FEATURES, RND_MAX_BATCH, RND_MAX_STEPS = 84 * 84, 512, 1 << 24, 1024
+LEAKY_SLOPE = 0.01             # nn.LeakyReLU's default negative_slope (RNDModel's predictor / target)
+_AMAX_WORDS = 256              # MI355PPO_AMAX_WORDS: uint32 words of an amax record (csrc/f16split.h)
 
 
 def bind(side, namespace: dict) -> None:
@@ -129,3 +132,42 @@ def rnd_loss_fwd_bwd(s, predict, target, u, update_proportion: float, v_int, int
                 float(update_proportion), _ptr(v_int), _ptr(int_returns), _ptr(mb_inds), B, float(vf_coef), _ptr(scalars), _ptr(d_predict),
                 _ptr(d_v_int), M, F)
     return scalars, d_predict, d_v_int
+
+
+# ------------------------------------------------------------------------------------------- LeakyReLU (csrc/leaky.hip)
+def _leaky_tail(s, n, bits, amax):
+    if bits is not None:
+        s.chk(bits, torch.int32, "bits", ((n + 31) // 32,))
+    if amax is not None:
+        s.chk(amax, torch.int32, "amax record", (_AMAX_WORDS,))
+
+
+def leaky_relu_fwd(s, z, out=None, bits=None, amax=None, slope: float = LEAKY_SLOPE):
+    """``torch.nn.functional.leaky_relu(z, slope)`` in f32, bit for bit -> ``out`` (``z``'s shape; may be ``z`` itself).  ``bits``
+    (optional, int32, ``(n + 31) // 32`` words): bit b of word w = ``z > 0`` of flat element 32 w + b.  ``amax`` (optional): ``out``'s
+    amax record, zeroed by the caller; ``max |out|`` is folded into it."""
+    n = z.numel()
+    s.chk(z, torch.float32, "z")
+    if n == 0:
+        raise ValueError("leaky_relu_fwd: empty tensor")
+    out = torch.empty_like(z) if out is None else out
+    s.chk(out, torch.float32, "out", z.shape)
+    _leaky_tail(s, n, bits, amax)
+    s.launch("mi355ppo_leaky_relu_fwd_f32", z.device, _ptr(z), _ptr(out), _ptr(bits), _ptr(amax), n, float(slope))
+    return out
+
+
+def leaky_relu_bwd(s, da, bits, out=None, amax=None, slope: float = LEAKY_SLOPE):
+    """``dz = bit ? da : da * (float)slope`` with the forward's ``bits`` -> ``out`` (``da``'s shape; may be ``da`` itself): the gradient
+    of ``leaky_relu_fwd``, torch's bits.  ``amax`` (optional): ``out``'s amax record."""
+    n = da.numel()
+    s.chk(da, torch.float32, "da")
+    if n == 0:
+        raise ValueError("leaky_relu_bwd: empty tensor")
+    if bits is None:
+        raise TypeError("leaky_relu_bwd: the forward's mask bits are required")
+    out = torch.empty_like(da) if out is None else out
+    s.chk(out, torch.float32, "out", da.shape)
+    _leaky_tail(s, n, bits, amax)
+    s.launch("mi355ppo_leaky_relu_bwd_f32", da.device, _ptr(da), _ptr(bits), _ptr(out), _ptr(amax), n, float(slope))
+    return out

@@ -1668,6 +1668,44 @@ MI355PPO_API int mi355ppo_cnn_conv1q1_fwd_amax(const void* src_u8, const int64_t
 MI355PPO_API int mi355ppo_cnn_conv1q1_fwd_cpu(const void* src_u8, const int64_t* inds, const void* pack, const float* bias, float* dst,
                                               uint32_t* mask_bits, uint32_t* dst_amax, int64_t images);
 
+/* ---- LeakyReLU over a flat f32 tensor (added under ABI 2.7.1; csrc/leaky.hip, element math in csrc/leaky_rows.h) --------------------------
+ * The activation of RNDModel's predictor / target stacks (cleanrl/ppo_rnd_envpool.py:188-233), behind a pre-activation forward and behind a
+ * data gradient called with an all-ones mask.  n > 0 elements, any n; z / a / da / dz 16-byte aligned, each pair may be the same buffer.
+ *   forward:  a = z > 0 ? z : z * (float)slope, as torch.nn.functional.leaky_relu in f32 (-0 stays -0).  mask_bits (optional): (n + 31) / 32
+ *     words, word w bit b <-> (z > 0) of flat element 32 w + b, the bits past n zero.  a_amax (optional): a's amax record (max |a|;
+ *     MI355PPO_AMAX_WORDS uint32, 64-byte aligned, zeroed by the caller).
+ *   backward: dz = bit ? da : da * (float)slope with the forward's mask_bits (required).  dz_amax (optional): dz's amax record.
+ * One launch each; no atomics on floats (a record takes integer maxima): the same input gives the same bits.  The twins return the device's
+ * bits and fold an amax record's value into its word 0. */
+MI355PPO_API int mi355ppo_leaky_relu_fwd_f32(const float* z, float* a, uint32_t* mask_bits, uint32_t* a_amax, int64_t n, double slope,
+                                             void* stream);
+MI355PPO_API int mi355ppo_leaky_relu_fwd_f32_cpu(const float* z, float* a, uint32_t* mask_bits, uint32_t* a_amax, int64_t n, double slope);
+MI355PPO_API int mi355ppo_leaky_relu_bwd_f32(const float* da, const uint32_t* mask_bits, float* dz, uint32_t* dz_amax, int64_t n, double slope,
+                                             void* stream);
+MI355PPO_API int mi355ppo_leaky_relu_bwd_f32_cpu(const float* da, const uint32_t* mask_bits, float* dz, uint32_t* dz_amax, int64_t n,
+                                                 double slope);
+
+/* ---- The normalising one-frame conv1 of RNDModel's predictor / target (added under ABI 2.7.1; csrc/rnd_conv1.hip) ------------------------
+ * Conv2d(1, 32, 8, stride=4) on x[r, p] = the value of mi355ppo_rnd_normalize_u8_f32 (the same row function), straight from the u8
+ * observation rows: FRAME addressing, idx (clamped) and mean / sd as there; x never goes to global memory and nothing outside the frames is
+ * read.  Arithmetic: the two-term f16 split, x under the static scale 2^12 (|x| <= 5: no amax record, a row's bits do not depend on the
+ * rest of its batch), the products hi hi, hi lo, lo hi with f32 accumulation.  Device only; capturable, no allocation, no float atomics.
+ *   forward: dst (M, 20, 20, 32) f32 = leaky(conv(x, W1) + bias), leaky(z) = z > 0 ? z : z * (float)slope.  pack: W1 viewed as a (32, 64)
+ *     matrix through mi355ppo_fc_pack_f16x2_f32 (mi355ppo_fc_pack_f16x2_bytes(32, 64) bytes, 16-byte aligned).  mask_bits (optional): M * 400
+ *     words, word p = (z > 0) of the 32 channels of pixel p (bit b of word w <-> flat element 32 w + b).  dst_amax (optional): dst's amax
+ *     record (max |dst|; zeroed by the caller, 64-byte aligned).  M in 1 .. 1 << 22.  One launch.
+ *   gradient: dW (32, 1, 8, 8) and db (32), OVERWRITTEN: dW[n][kh][kw] = sum dz[p][n] * x[4 oy + kh][4 ox + kw], db[n] = sum dz[p][n], from
+ *     dz (images, 20, 20, 32; 16-byte aligned) in two f16 terms under its amax record (required).  One partial per wave, folded in a fixed
+ *     order: the same input gives the same bits.  workspace: mi355ppo_rnd_conv1_wgrad_workspace_bytes(images) bytes, 16-byte aligned.  Two or
+ *     three launches. */
+MI355PPO_API int mi355ppo_rnd_conv1_fwd_f16x2(const unsigned char* src, int64_t B, int64_t row_bytes, int pixel_stride, int64_t byte_offset,
+                                              const int64_t* idx, const double* mean, const double* sd, const void* pack, const float* bias,
+                                              float* dst, uint32_t* mask_bits, uint32_t* dst_amax, int M, double slope, void* stream);
+MI355PPO_API size_t mi355ppo_rnd_conv1_wgrad_workspace_bytes(int64_t images);
+MI355PPO_API int mi355ppo_rnd_conv1_wgrad_f16x2(const unsigned char* src, int64_t B, int64_t row_bytes, int pixel_stride, int64_t byte_offset,
+                                                const int64_t* idx, const double* mean, const double* sd, const float* dz, float* dW, float* db,
+                                                int64_t images, void* workspace, size_t workspace_bytes, const uint32_t* dz_amax, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,13 @@ Legs, per size (envs x steps, 4 minibatches, 4 epochs as the script):
     peak_mem_mb        ``torch.cuda.max_memory_allocated`` over the backend's ``update`` (reset before it)
 
 Times are medians over ``--reps`` runs, synchronised, in microseconds.
+
+    python tools/rndbench.py --trunk [--reps 20] [--sizes 128x128,32x32] [--leg-timeout 300] [--breakdown] [--json out.json]
+
+The trunk axis: ``MI355PPO_RND=fused`` on both sides, ``MI355PPO_RND_TRUNK=torch | fused`` in alternation.  Every leg is a child process
+under its own time limit; the first leg that fails or runs out of time ends the run.  Legs, per size: ``act_us`` (one ``act(step)``),
+``curiosity_us``, ``minibatch_us``, ``update_us`` and, from the update's child, ``peak_mem_mb``.  ``--breakdown`` adds one child that times
+every library call of one fused-trunk minibatch (synchronised around each launch: what a call costs alone, not what it costs in the queue).
 """
 from __future__ import annotations
 
@@ -21,6 +28,7 @@ import argparse
 import json
 import os
 import statistics
+import subprocess
 import sys
 import time
 
@@ -51,8 +59,9 @@ def _alternate(fns, reps):
     return [statistics.median(t) for t in ts]
 
 
-def _learner(backend, N, T, dev):
+def _learner(backend, N, T, dev, trunk="torch"):
     os.environ["MI355PPO_RND"] = backend                      # read when the learner is built
+    os.environ["MI355PPO_RND_TRUNK"] = trunk
     torch.manual_seed(1)
     np.random.seed(1)
     envs = type("S", (), dict(single_observation_space=E.Box(0, 255, (4, 84, 84), np.uint8), single_action_space=E.Discrete(6)))
@@ -60,7 +69,7 @@ def _learner(backend, N, T, dev):
     args = default_args(num_steps=T, num_minibatches=4, update_epochs=4, gamma=0.999, int_gamma=0.99, clip_coef=0.1, ent_coef=0.001,
                         update_proportion=0.25, int_coef=1.0, ext_coef=2.0, learning_rate=1e-4)
     L = RNDPPOLearner(agent, rnd, args, envs.single_observation_space, envs.single_action_space, N, dev, sample_seed=1)
-    assert L.rnd_fused == (backend == "fused")
+    assert L.rnd_fused == (backend == "fused") and L.rnd_trunk_fused == (trunk == "fused")
     rs = np.random.RandomState(2)
     L.obs_rms.update(rs.randint(0, 256, size=(64, 1, 84, 84)).astype(np.float64))
     if L.rnd_fused:
@@ -147,12 +156,105 @@ def bench(N, T, reps, dev):
     return rows
 
 
+TRUNK_LEGS = ("act_us", "curiosity_us", "minibatch_us", "update_us")
+
+
+def _peak(L, dev):
+    L.__dict__.pop("_bench_mb", None)
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats(dev)
+    L.update(1e-4)
+    torch.cuda.synchronize()
+    return torch.cuda.max_memory_allocated(dev) / 2**20
+
+
+def trunk_child(leg, N, T, reps):
+    """One leg of the trunk axis: both learners under ``MI355PPO_RND=fused``, the two trunks timed in alternation."""
+    dev = torch.device("cuda")
+    sides = [_learner("fused", N, T, dev, trunk) for trunk in ("torch", "fused")]
+    base = {"envs": N, "steps": T, "minibatch_rows": sides[0].minibatch_size, "leg": leg}
+    if leg == "breakdown":
+        for row in _breakdown(sides[1], reps):
+            print(json.dumps({**base, "trunk": "fused", **row}), flush=True)
+        return
+    run = {"act_us": lambda L: L.act(1), "curiosity_us": lambda L: L.curiosity(1), "minibatch_us": _one_minibatch,
+           "update_us": lambda L: L.update(1e-4)}[leg]
+    r = max(3, reps // 4) if leg == "update_us" else reps
+    for L, t in zip(sides, _alternate([lambda L=L: run(L) for L in sides], r)):
+        row = {**base, "trunk": "fused" if L.rnd_trunk_fused else "torch", "us": round(t, 1), "reps": r}
+        if leg == "update_us":
+            row["peak_mem_mb"] = round(_peak(L, dev), 1)
+        print(json.dumps(row), flush=True)
+
+
+def _breakdown(L, reps):
+    """Median time of every library call of one minibatch of ``L``, in call order, each launch synchronised on both sides."""
+    from cleanrl_amd import ops
+
+    real = ops._launch
+    mods = [m for n, m in sorted(sys.modules.items()) if n.startswith("cleanrl_amd") and m is not None and getattr(m, "_launch", None) is real]
+    calls = []
+
+    def timed(name, dev, *args):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        real(name, dev, *args)
+        torch.cuda.synchronize()
+        calls.append((name, (time.perf_counter() - t0) * 1e6))
+
+    _one_minibatch(L)
+    torch.cuda.synchronize()
+    runs = []
+    for m in mods:
+        m._launch = timed
+    try:
+        for _ in range(max(3, reps // 4)):
+            calls.clear()
+            _one_minibatch(L)
+            runs.append(list(calls))
+    finally:
+        for m in mods:
+            m._launch = real
+    assert all([n for n, _ in r] == [n for n, _ in runs[0]] for r in runs), "the minibatch's launches changed between runs"
+    return [{"call": k, "entry": name, "us": round(statistics.median(r[k][1] for r in runs), 1)} for k, (name, _) in enumerate(runs[0])]
+
+
+def trunk_main(a):
+    rows = []
+    for size in a.sizes.split(","):
+        N, T = (int(v) for v in size.split("x"))
+        for leg in TRUNK_LEGS + (("breakdown",) if a.breakdown else ()):
+            cmd = ["timeout", "-k", "10", str(a.leg_timeout), sys.executable, os.path.abspath(__file__), "--reps", str(a.reps), "--trunk-child", leg,
+                   str(N), str(T)]
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            sys.stdout.write(r.stdout)
+            sys.stdout.flush()
+            if r.returncode != 0:                              # a failed or hung leg ends the run: nothing more is started on the GPU
+                sys.stderr.write(r.stderr[-4000:])
+                print(json.dumps({"leg": leg, "envs": N, "failed": r.returncode}), flush=True)
+                return 1
+            rows += [json.loads(line) for line in r.stdout.splitlines() if line.startswith("{")]
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump(rows, fh, indent=1)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--sizes", default="128x128,32x32", help="envs x steps, comma separated")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--trunk", action="store_true", help="the MI355PPO_RND_TRUNK axis under MI355PPO_RND=fused, one child process per leg")
+    ap.add_argument("--breakdown", action="store_true", help="with --trunk: the time per library call of one fused-trunk minibatch")
+    ap.add_argument("--leg-timeout", type=int, default=300, help="with --trunk: seconds one leg (one child process) may take")
+    ap.add_argument("--trunk-child", nargs=3, metavar=("LEG", "N", "T"), default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.trunk_child:
+        trunk_child(a.trunk_child[0], int(a.trunk_child[1]), int(a.trunk_child[2]), a.reps)
+        return 0
+    if a.trunk:
+        return trunk_main(a)
     dev = torch.device("cuda")
     rows = []
     for size in a.sizes.split(","):
@@ -166,4 +268,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())
