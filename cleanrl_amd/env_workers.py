@@ -22,7 +22,9 @@ can build it itself (nothing but that tuple is pickled).
 """
 from __future__ import annotations
 
+import functools
 import importlib
+import mmap
 import multiprocessing as mp
 from multiprocessing import shared_memory
 from typing import Optional
@@ -108,6 +110,36 @@ def _worker(spec, names, n, obs_shape, obs_dtype, act_shape, act_dtype, conn):
             s.close()
 
 
+def _host_register(ptr: int, nbytes: int) -> bool:
+    """``hipHostRegister`` through torch's runtime binding.  A refusal is taken off the calling thread's HIP error state
+    (``hipGetLastError``): left there, the next kernel launch of this thread -- anybody's -- would report it as its own."""
+    import torch
+
+    if int(torch.cuda.cudart().cudaHostRegister(ptr, nbytes, 0)) == 0:
+        return True
+    from . import _lib
+
+    _lib.load().hipGetLastError()       # (looked up through libmi355ppo.so's handle: the HIP runtime it is linked to, the one torch loaded)
+    return False
+
+
+@functools.lru_cache(maxsize=None)
+def host_register_supported() -> bool:
+    """Whether the HIP runtime here pins memory the process already has (one page is tried, once).  Where it does not -- a GPU
+    passed through to a virtual machine, for one -- ``ProcessVecEnv.pin()`` answers False and the lanes stage the frames
+    through their own pinned buffers."""
+    import torch
+
+    if not torch.cuda.is_available():
+        return False
+    page = mmap.mmap(-1, mmap.PAGESIZE)
+    t = torch.frombuffer(page, dtype=torch.uint8)
+    ok = _host_register(t.data_ptr(), t.numel())
+    if ok:
+        torch.cuda.cudart().cudaHostUnregister(t.data_ptr())
+    return ok
+
+
 class ProcessVecEnv:
     """``ProcessVecEnv(("cleanrl_amd.envs", "SyntheticAtariVecEnv", dict(num_envs=256, seed=1, api="gym")))``."""
 
@@ -145,16 +177,17 @@ class ProcessVecEnv:
     def pin(self) -> bool:
         """Register the observation segments as pinned host memory (``hipHostRegister`` through torch's runtime binding) and expose
         them as uint8 tensors ``obs_t`` / ``newest_t``: H2D copies from them are asynchronous DMA.  False when the runtime refuses
-        (the caller then stages through its own pinned buffers)."""
+        (the caller then stages through its own pinned buffers); a refusal leaves no HIP error behind."""
         import torch
 
         try:
-            rt = torch.cuda.cudart()
+            if not host_register_supported():
+                return False
             for key in ("obs", "newest"):
                 if key not in self._segs:
                     continue
                 t = torch.frombuffer(self._segs[key].buf, dtype=torch.uint8)
-                if int(rt.cudaHostRegister(t.data_ptr(), t.numel(), 0)) != 0:
+                if not _host_register(t.data_ptr(), t.numel()):
                     raise RuntimeError("cudaHostRegister")
                 self._registered.append(t.data_ptr())
                 setattr(self, key + "_t", t.view(self._v[key].shape))

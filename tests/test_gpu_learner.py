@@ -614,14 +614,32 @@ def test_captured_lane_steps_match_the_eager_lanes(K):
     assert not torch.equal(out[0][0]["logprobs"], out[0][1]["logprobs"])          # the update changed the policy between the rollouts
 
 
-@pytest.mark.parametrize("K,pin", [(2, True), (4, True), (2, False)])
+def test_a_refused_host_registration_leaves_no_hip_error_for_the_next_launch():
+    """``env_workers.host_register_supported``: where the runtime refuses ``hipHostRegister`` the answer is False and the refusal is
+    off the thread's HIP error state -- the next launch (which would report a pending error as its own) runs; either way the answer
+    is stable."""
+    from cleanrl_amd import env_workers
+
+    env_workers.host_register_supported.cache_clear()
+    ok = env_workers.host_register_supported()
+    z = torch.zeros(64, device=DEV)
+    torch.cuda.synchronize()
+    assert float(z.sum()) == 0.0
+    env_workers.host_register_supported.cache_clear()
+    assert env_workers.host_register_supported() == ok
+
+
+@pytest.mark.parametrize("K,pin", [(2, True), (4, True), (2, False), (4, False)])
 def test_one_thread_driver_over_worker_process_envs_matches_the_threaded_lanes(K, pin):
     """``GroupedRollout.run_async``: envs stepped in worker processes (cleanrl_amd/env_workers.py), captured lane steps, ONE host
     thread polling every lane, frames DMA'd straight from the workers' registered shared memory (``pin``) -- against the threaded
-    eager lanes over in-process envs: every rollout buffer bit for bit, over two rollouts with an update in between."""
-    from cleanrl_amd.env_workers import ProcessVecEnv
+    eager lanes over in-process envs: every rollout buffer bit for bit, over two rollouts with an update in between.  The ``pin``
+    cases are about ``hipHostRegister`` and skip where the runtime does not have it (a GPU inside a virtual machine)."""
+    from cleanrl_amd.env_workers import ProcessVecEnv, host_register_supported
     from cleanrl_amd.pipeline import GroupedRollout, split_env_groups
 
+    if pin and not host_register_supported():
+        pytest.skip("hipHostRegister is not supported here")
     N, T = 16, 8
     space = SimpleNamespace(single_observation_space=E.Box(0, 255, (4, 84, 84), np.uint8), single_action_space=E.Discrete(4))
     kw = lambda g, n: dict(num_envs=n, seed=41 + g * n, api="gym", done_p=0.1)
