@@ -7,8 +7,6 @@ The host side also checks ``0 <= cols < R``; the device side cannot without a de
 """
 from __future__ import annotations
 
-import types
-
 import torch
 
 from .replay_ops import _ptr
@@ -16,11 +14,6 @@ from .replay_ops import _ptr
 OPERATORS = ("ppg_aux_gather", "ppg_old_logits_", "ppg_aux_fwd_bwd", "clip_adam_split_")
 
 PPG_HIDDEN, PPG_MIN_ACT, PPG_MAX_ACT, PPG_MAX_ROWS = 256, 2, 30, 1 << 16
-
-
-def bind(side, namespace: dict) -> None:
-    for name in OPERATORS:
-        namespace[name] = types.MethodType(globals()[name], side)
 
 
 def _cols(s, cols, R: int, fn: str) -> int:

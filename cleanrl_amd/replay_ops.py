@@ -2,7 +2,7 @@
 
 The C ABI makes one definition enough: a ``*_cpu`` twin takes its device entry point's arguments minus the tail ``(stream)`` or
 ``(workspace, workspace_bytes, stream)``.  So every operator below validates its arguments once and makes one call through its first
-parameter ``s``, a ``Side``, which holds the only two differences between the paths:
+parameter ``s``, a ``Side``, which holds the only differences between the paths:
 
 * ``s.chk(t, dtype, name, shape=None)`` -- a tensor on this side's kind of device, of that dtype, contiguous, of exactly that shape:
   ``TypeError`` for a non-tensor, the wrong kind of device or a wrong dtype, ``ValueError`` for a non-contiguous tensor or a wrong
@@ -10,6 +10,8 @@ parameter ``s``, a ``Side``, which holds the only two differences between the pa
 * ``s.launch(name, dev, *args)`` / ``s.launch_ws(name, dev, ws_bytes, dims, *args)`` -- the device side calls ``name`` with ``args``,
   then (``launch_ws``) the workspace of ``ws_bytes(*dims)`` bytes and its size, then ``dev``'s current stream; the host side calls
   ``name + "_cpu"`` with ``args`` alone and never asks for the workspace's size.
+* ``s.empty(shape, dtype, dev)`` -- ``torch.empty`` as the side's own module sees it, for the buffers an operator allocates itself
+  (cleanrl_amd/twin_ops.py): the guard-band tests carve a wrapper's allocations by patching ``torch`` in ``ops`` / ``host_ops``.
 
 ``cleanrl_amd.ops`` and ``cleanrl_amd.host_ops`` each build their side and ``bind`` it once at import: ``ops.X`` and ``host_ops.X``
 are the function ``X`` below bound to that side, under one name, signature and docstring.  ``sac_alpha_`` holds the one entry point
@@ -23,7 +25,7 @@ from collections import namedtuple
 
 import torch
 
-Side = namedtuple("Side", "host chk launch launch_ws")
+Side = namedtuple("Side", "host chk launch launch_ws empty")
 
 OPERATORS = (
     "replay_add", "ddpg_act", "td3_target", "td3_critic_fwd_bwd", "td3_actor_fwd_bwd", "polyak_",
@@ -37,10 +39,11 @@ OPERATORS = (
 )
 
 
-def bind(side: Side, namespace: dict) -> None:
-    """Put every operator, bound to ``side``, into ``namespace`` (a module's globals) under its own name."""
-    for name in OPERATORS:
-        namespace[name] = types.MethodType(globals()[name], side)
+def bind(module, side: Side, namespace: dict) -> None:
+    """Put every operator of ``module.OPERATORS`` (this module, rnd_ops, ppg_ops, twin_ops), bound to ``side``, into ``namespace`` (a
+    module's globals) under its own name."""
+    for name in module.OPERATORS:
+        namespace[name] = types.MethodType(getattr(module, name), side)
 
 
 def _ptr(t):

@@ -4,8 +4,6 @@ them to their side at import.  Nothing is coerced or copied; every check runs be
 """
 from __future__ import annotations
 
-import types
-
 import numpy as np
 import torch
 
@@ -17,11 +15,6 @@ OPERATORS = ("rnd_normalize", "rnd_obs_moments", "rnd_intrinsic_reward", "rnd_re
 RND_PIXELS, RND_FEATURES, RND_MAX_BATCH, RND_MAX_STEPS = 84 * 84, 512, 1 << 24, 1024
 LEAKY_SLOPE = 0.01             # nn.LeakyReLU's default negative_slope (RNDModel's predictor / target)
 _AMAX_WORDS = 256              # MI355PPO_AMAX_WORDS: uint32 words of an amax record (csrc/f16split.h)
-
-
-def bind(side, namespace: dict) -> None:
-    for name in OPERATORS:
-        namespace[name] = types.MethodType(globals()[name], side)
 
 
 def _frame(s, rows, nhwc: bool):

@@ -1,13 +1,14 @@
 """cleanrl_amd/replay_ops.py: one definition per replay-ring operator, bound once to the device side (``ops``) and once to the host
 side (``host_ops``).  The ABI rule that makes this possible, the bindings, and for one operator per family which side refuses what,
-which symbol is called with how many arguments, and that every refusal precedes the C call."""
+which symbol is called with how many arguments, and that every refusal precedes the C call.  The same binding holds
+for cleanrl_amd/twin_ops.py (LSTM, TrXL, IMPALA, PQN, the LayerNorm trunk pieces); its host side is held to the device side's strictness."""
 import ctypes
 import inspect
 
 import pytest
 import torch
 
-from cleanrl_amd import _lib, host_ops, ops
+from cleanrl_amd import _lib, host_ops, ops, twin_ops
 from cleanrl_amd.replay_ops import ATARI_FRAME, OPERATORS, dqn_counts, offpolicy_counts, sac_actor_count
 
 SYMBOLS = {
@@ -44,10 +45,11 @@ def test_twin_takes_the_device_arguments_minus_workspace_and_stream(op):
     assert dev_args[:len(cpu_args)] == cpu_args and tail in ([P], [P, Z, P])
 
 
-@pytest.mark.parametrize("op", sorted(SYMBOLS))
+@pytest.mark.parametrize("op", sorted(SYMBOLS) + sorted(twin_ops.OPERATORS))
 def test_both_modules_bind_the_one_definition(op):
     d, h = getattr(ops, op), getattr(host_ops, op)
     assert d is not h and d.__func__ is h.__func__ and d.__self__ is not h.__self__
+    assert d.__self__.host is False and h.__self__.host is True
     assert inspect.signature(d) == inspect.signature(h) and d.__doc__ and h.__doc__ and d.__name__ == op
     assert op in ops.__all__
 
@@ -156,3 +158,51 @@ def test_the_host_side_refuses_cuda_tensors(family, calls):
     with pytest.raises(TypeError, match="CPU tensors only"):
         getattr(host_ops, op)(*make("cuda", torch.full(shape, SENTINEL, dtype=dtype, device="cuda")))
     assert calls == []
+
+
+# ---------------------------------------------------------------------------------------------- cleanrl_amd/twin_ops.py, one operator per family
+def _z(*shape, dtype=torch.float32):
+    return torch.zeros(shape, dtype=dtype)
+
+
+def _trxl_smallest():
+    import trxl_cases
+
+    c = trxl_cases.make_case(64, 4, 7, 3, "random", "absolute")
+    return [c["memory"], c["layer"], c["ep"], c["rows"], c["pos"], c["mask"].to(torch.uint8), c["pe"], c["gamma"], c["beta"], c["q"]]
+
+
+# family: (operator, its arguments at the smallest shapes the twin takes, the index of the argument that is made wrong)
+TWIN_FAMILIES = {
+    "lstm": ("lstm_seq_forward", lambda: [_z(2, 2, 16), _z(16, 4), _z(2, 4), _z(2, 4), _z(2, 2)], 4),                                  # T=2, B=2, H=4: done
+    "trxl": ("trxl_attn_forward", _trxl_smallest, 5),                                                                                    # mask
+    "impala": ("impala_forward", lambda: [_z(1, 64, 64, 3), [_z(*s) for s in ops.impala_param_shapes()]], 0),                           # B=1: x
+    "impala84": ("impala84_forward", lambda: [_z(1, 84, 84, 4, dtype=torch.uint8), [_z(*s) for s in ops.impala84_param_shapes()]], 0),
+    "pqn": ("pqn_mlp_act", lambda: [_z(2, 3), _z(ops.pqn_param_count(3, 2)), 2, _z(2, dtype=torch.int64), _z(2), 0.1, _z(2), _z(2)], 3),  # N=2, obs 3, 2 actions: random_actions
+    "layernorm": ("layernorm_relu_fwd", lambda: [_z(2, 32), _z(32), _z(32), 2, 16], 1),                                                # rows=2, C=2, HW=16: gamma
+    "conv1q1": ("conv1q1_pre_fwd", lambda: [_z(2, 84, 84, dtype=torch.uint8), _z(_lib.load().mi355ppo_cnn_conv1q1_pack_bytes() // 4), _z(32)], 2),  # 2 frames: bias
+}
+
+
+@pytest.mark.parametrize("family", sorted(TWIN_FAMILIES))
+def test_the_host_side_of_twin_ops_is_as_strict_as_the_device_side(family, calls):
+    """A wrong dtype, a non-contiguous tensor and a wrong shape are refused with ``ops._chk``'s exception types before any C call (the
+    host copies of these operators used to coerce and copy); the exact arguments reach the twin in one call."""
+    op, make, k = TWIN_FAMILIES[family]
+    good = make()[k]
+    last = good.shape[-1]
+    bad = ((TypeError, good.to(torch.float64 if good.dtype == torch.float32 else torch.float32)),
+           (ValueError, torch.zeros(tuple(good.shape[:-1]) + (2 * last,), dtype=good.dtype)[..., ::2]),
+           (ValueError, torch.zeros(tuple(good.shape[:-1]) + (last + 1,), dtype=good.dtype)))
+    assert bad[1][1].shape == good.shape and not bad[1][1].is_contiguous()
+    for error, t in bad:
+        args = make()
+        args[k] = t
+        with pytest.raises(error):
+            getattr(host_ops, op)(*args)
+        assert calls == []
+    with pytest.raises(TypeError, match="CUDA/HIP tensor"):
+        getattr(ops, op)(*make())
+    assert calls == []
+    getattr(host_ops, op)(*make())
+    assert len(calls) == 1 and calls[0][0].endswith("_cpu") and len(calls[0][1]) == len(_lib.SIGNATURES[calls[0][0]][1])
