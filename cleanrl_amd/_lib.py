@@ -110,6 +110,13 @@ SIGNATURES = {
     "mi355ppo_mlp_ppo_normal_fwd_bwd_f32": (
         c_int, [_P, _P, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, c_double, c_double, c_double, c_int, c_int, _P, _P, _P, _P,
                 _P, c_int, _P, c_size_t, _P]),
+    # K8: the 256-wide tanh MLP family on the matrix pipe (csrc/mlp256.hip)
+    "mi355ppo_mlp256_pack_bytes": (c_size_t, [c_int, c_int]),
+    "mi355ppo_mlp256_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mi355ppo_mlp256_pack_f32": (c_int, [_P, _P, c_int, c_int, _P, c_size_t, _P]),
+    "mi355ppo_mlp256_fwd_f32": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "mi355ppo_mlp256_dgrad_f32": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "mi355ppo_mlp256_wgrad_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, _P, c_int, _P, c_size_t, _P]),
     "mi355ppo_synth_continuous_step_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_uint64, _P, _P, c_double, _P, _P, _P, _P, c_int, c_int,
                                                    c_int, _P]),
     # round 5: the NatureCNN GEMMs on the two-term f16 split (csrc/f16split.h): amax records in, amax records out

@@ -332,6 +332,70 @@ class ContinuousAgent(nn.Module):
         return action, probs.log_prob(action).sum(1), probs.entropy().sum(1), value
 
 
+MLP256_BACKENDS = ("torch", "fused")
+
+
+def mlp256_backend() -> str:
+    """``MI355PPO_MLP256``: ``torch`` (default: the two networks on library GEMMs behind the HIP sampling / loss kernels) or ``fused``
+    (the K8 kernels of csrc/mlp256.hip; HIP learner only).  DESIGN 3.7 / 3.25."""
+    v = os.environ.get("MI355PPO_MLP256", "torch")
+    if v not in MLP256_BACKENDS:
+        raise ValueError(f"MI355PPO_MLP256={v!r}: expected torch or fused")
+    return v
+
+
+def fused_mlp256(agent):
+    """``ops.Mlp256Nets`` of an agent whose two networks the K8 kernels cover (O-256-256-n_out tanh, O <= 256, n_out <= 32, f32 on a HIP
+    device) under ``MI355PPO_MLP256=fused``, else None -- said once on stderr when the backend was asked for and the shape is outside."""
+    if mlp256_backend() != "fused":
+        return None
+    actor, critic = agent.mlp256_nets()
+    w = actor[0].weight
+    if not w.is_cuda or w.dtype != torch.float32:
+        return None
+    try:
+        return ops.Mlp256Nets(actor, critic)
+    except AssertionError:
+        import sys
+
+        print(f"cleanrl_amd: this MLP agent (observation width {actor[0].in_features}, {actor[-1].out_features} actor outputs) is outside the K8 "
+              f"kernels' shapes (256-256 tanh, observation width <= {ops.MLP256_MAX_OBS}, <= {ops.MLP256_MAX_OUT} outputs): its networks run on "
+              "library GEMMs behind the HIP sampling / loss kernels", file=sys.stderr, flush=True)
+        return None
+
+
+class IsaacGymAgent(ContinuousAgent):
+    """ppo_continuous_action_isaacgym.py:155-184: two 256-256 tanh networks and a state-independent ``actor_logstd``; the reference's module
+    tree, parameter names and initialisation order.  Method surface as ``ContinuousAgent``; ``mlp256_nets`` is the seam of the K8 kernels."""
+
+    def __init__(self, envs):
+        nn.Module.__init__(self)
+        self.rpo_alpha = None
+        obs_dim = int(np.array(envs.single_observation_space.shape).prod())
+        act_dim = int(np.prod(envs.single_action_space.shape))
+        self.critic = nn.Sequential(
+            layer_init(nn.Linear(obs_dim, 256)),
+            nn.Tanh(),
+            layer_init(nn.Linear(256, 256)),
+            nn.Tanh(),
+            layer_init(nn.Linear(256, 1), std=1.0),
+        )
+        self.actor_mean = nn.Sequential(
+            layer_init(nn.Linear(obs_dim, 256)),
+            nn.Tanh(),
+            layer_init(nn.Linear(256, 256)),
+            nn.Tanh(),
+            layer_init(nn.Linear(256, act_dim), std=0.01),
+        )
+        self.actor_logstd = nn.Parameter(torch.zeros(1, act_dim))
+        self.act_dim = act_dim
+        self.rng = _SampleCounter()
+        self._fused = None
+
+    def mlp256_nets(self):
+        return self.actor_mean, self.critic
+
+
 LSTM_BACKENDS = ("torch", "fused")
 
 

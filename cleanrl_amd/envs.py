@@ -366,6 +366,46 @@ class DeviceSyntheticContinuousVecEnv:
         pass
 
 
+class DeviceLinearContinuousVecEnv:
+    """``SyntheticContinuousVecEnv``'s task (a stable random linear system driven by the clipped action, reward = a velocity proxy minus an
+    action cost, truncation after ``horizon`` steps) for any ``obs_dim``, stepped by torch operations on ``device`` tensors: the step kernel
+    of ``DeviceSyntheticContinuousVecEnv`` takes observations of at most 32 values, Ant's 60 (ppo_continuous_action_isaacgym.py) do not fit
+    it.  ``step`` -> (obs, reward, done) tensors.  A stand-in env (plumbing), not part of the hot path."""
+
+    def __init__(self, num_envs: int, device, seed: int = 0, obs_dim: int = 60, act_dim: int = 8, horizon: int = 1000):
+        import torch
+
+        self.torch, self.num_envs, self.horizon = torch, num_envs, horizon
+        self.single_observation_space = Box(-np.inf, np.inf, (obs_dim,))
+        self.single_action_space = Box(-1.0, 1.0, (act_dim,))
+        g = torch.Generator().manual_seed(seed + 777)
+        a = torch.randn(obs_dim, obs_dim, generator=g) / math.sqrt(obs_dim)
+        self.At = (0.9 * a / max(1.0, float(torch.linalg.eigvals(a).abs().max()))).t().contiguous().to(device)
+        self.B = (0.3 * torch.randn(act_dim, obs_dim, generator=g)).to(device)
+        self.w = (torch.randn(obs_dim, generator=g) / math.sqrt(obs_dim)).to(device)
+        self.gen = torch.Generator(device=device).manual_seed(seed)
+        self.state = 0.1 * torch.randn(num_envs, obs_dim, generator=self.gen, device=device)
+        self.steps = torch.zeros(num_envs, device=device)
+
+    def obs(self):
+        return self.state
+
+    def step(self, action):
+        torch = self.torch
+        a = action.clamp(-1.0, 1.0)
+        state = self.state @ self.At + a @ self.B + 0.01 * torch.randn(self.state.shape, generator=self.gen, device=self.state.device)
+        reward = state @ self.w - 0.1 * (a * a).sum(1)
+        self.steps += 1
+        done = (self.steps >= self.horizon).float()
+        fresh = 0.1 * torch.randn(self.state.shape, generator=self.gen, device=self.state.device)
+        self.state = torch.where(done.bool().unsqueeze(1), fresh, state)
+        self.steps *= 1 - done
+        return self.state, reward, done
+
+    def close(self):
+        pass
+
+
 def have_gymnasium() -> bool:
     try:
         import gymnasium  # noqa: F401

@@ -245,7 +245,7 @@ class PPOLearner:
             from .agents import fused_mlp_ptrs
 
             self.mlp = fused_mlp_ptrs(agent)            # after FlatParams: the parameters sit at their final addresses
-            if self.mlp is None and os.environ.get("MI355PPO_MLP", "fused") != "torch":
+            if self.mlp is None and os.environ.get("MI355PPO_MLP", "fused") != "torch" and not hasattr(agent, "mlp256_nets"):
                 # said once, not silently: which kernel family runs is part of what a drop-in user measures (round-5 review, weak #11)
                 import sys
 
@@ -253,6 +253,14 @@ class PPOLearner:
                 print(f"cleanrl_amd: this MLP agent (observation width {nets[0][0].in_features}, {nets[0][-1].out_features} actor outputs) is outside the fused "
                       "MLP kernels' shapes (64-64 tanh, observation width <= 512, <= 20 outputs): its networks run on library GEMMs behind the HIP sampling / "
                       "loss kernels", file=sys.stderr, flush=True)
+        # the 256-256 tanh agent of ppo_continuous_action_isaacgym.py on the K8 kernels (csrc/mlp256.hip; MI355PPO_MLP256=fused, default torch:
+        # DESIGN 3.25): rollout step = forward chain + K2', minibatch = forward (save) -> K3 -> data-gradient chain -> weight gradients + fold
+        self.mlp256 = None
+        if self.hip and not self.image and hasattr(agent, "mlp256_nets") and type(self).forward_backward_hip is PPOLearner.forward_backward_hip:
+            from .agents import fused_mlp256
+
+            self.mlp256 = fused_mlp256(agent)          # after FlatParams: the parameters sit at their final addresses
+        self.device_randperm = False    # True: the epoch permutation is torch.randperm on the learner's device (ppo_continuous_action_isaacgym.py:331)
         self._pack = None           # (B, 8) packed behaviour rows (ops.batch_pack) of the current update, or None
         self._pack_buf = None       # their storage, allocated by the first update()
         self._mb_adv_md = None      # the current minibatch's (mean, std + 1e-8) row of ops.adv_stats, or None
@@ -443,6 +451,11 @@ class PPOLearner:
                 if rng_offset is None:
                     self.agent.rng.next()
                 return r[0] if r[0] is not None else r[1]
+        if self.hip and self.mlp256 is not None:
+            seed, off = self.agent.rng.next() if rng_offset is None else (self.agent.rng.seed, int(rng_offset))
+            mean, _ = self.ops.mlp256_forward(self.obs[step][lo:hi], self.mlp256, value_out=self.values[step][lo:hi])
+            return self.ops.normal_sample(mean, self.agent.actor_logstd.detach(), seed=seed, offset=off, action_out=self.actions[step][lo:hi],
+                                          logprob_out=self.logprobs[step][lo:hi])[0]
         if self.hip:
             p, value = self._heads_rollout(self.obs[step][lo:hi], self.ind[step][lo:hi] if self.ma_fused else None)
             seed, off = self.agent.rng.next() if rng_offset is None else (self.agent.rng.seed, int(rng_offset))
@@ -554,6 +567,8 @@ class PPOLearner:
         if self.hip:
             if self.mlp is not None:
                 next_value = self.ops.mlp_forward(self.boot_obs, *self.mlp)[1]
+            elif self.mlp256 is not None:
+                next_value = self.ops.mlp256_forward(self.boot_obs, self.mlp256)[1]
             else:
                 _, next_value = self._heads_rollout(self.boot_obs, self.boot_ind)
             self.ops.gae(self.rewards, self.dones, self.values, self.boot_done, next_value.reshape(-1).contiguous(),
@@ -607,9 +622,14 @@ class PPOLearner:
         if replayed:
             k = self._replay_update(lr, b_inds, b_advantages, use_pack)
         for epoch in range(0 if replayed else int(a.update_epochs)):
-            np.random.shuffle(b_inds)                                     # :315 host MT19937, per-rank seed
+            if self.device_randperm:
+                inds_dev = torch.randperm(B, device=self.device)
+                b_inds = inds_dev if self.hip else inds_dev.numpy()
+            else:
+                np.random.shuffle(b_inds)                                 # :315 host MT19937, per-rank seed
             if self.hip:
-                inds_dev = self.upload_permutation(epoch, b_inds)
+                if not self.device_randperm:
+                    inds_dev = self.upload_permutation(epoch, b_inds)
                 # :337-338 hoisted: (mean, std + 1e-8) of every minibatch of this epoch depend only on the permutation and
                 # the GAE output -> one launch per epoch, and K3 runs without its statistics launch
                 if not a.norm_adv:
@@ -1043,6 +1063,16 @@ class PPOLearner:
                                 scalars_out=scalars_out, logstd=None if ls is None else ls.detach(),
                                 logstd_grad=None if ls is None else ls.grad, mean_shift=shift)
             return
+        if self.mlp256 is not None:
+            # K8: gather + both forward chains (h1 / h2 saved), K3's Normal loss, the data-gradient chain, the weight gradients + fold
+            nets, ls = self.mlp256, self.agent.actor_logstd
+            mean, value = ops.mlp256_forward(b_obs, nets, inds=idx, save=True)
+            _, dmean, dlogstd, dvalue = ops.ppo_loss_normal(mean, ls.detach(), value, idx, b_actions, b_logprobs, b_advantages, b_returns,
+                                                            b_values, a.clip_coef, a.ent_coef, a.vf_coef, a.norm_adv, a.clip_vloss,
+                                                            scalars_out=scalars_out, adv_mean_den=self._mb_adv_md)
+            ops.mlp256_backward(b_obs, nets, dmean, dvalue, inds=idx)
+            ls.grad.add_(dlogstd.view_as(ls))
+            return
         if self.image and self.fused_cnn:
             if self.ma_fused:
                 p, value = self.agent.heads_u8(b_obs, idx, self.ind.reshape(-1, 2))
@@ -1097,6 +1127,8 @@ class PPOLearner:
         trunk = getattr(self.agent, "_trunk", None)
         if trunk is not None:                       # the kernel rewrote the parameters through raw pointers
             trunk.bufs.weights_version += 1
+        if self.mlp256 is not None:
+            self.mlp256.weights_version += 1
 
     def _minibatch_host(self, mb_inds, b_obs, b_actions, b_logprobs, b_advantages, b_returns, b_values, lr):
         """The reference's minibatch body on CPU tensors (ppo.py:250-290; multigpu :360-374 when world_size>1)."""

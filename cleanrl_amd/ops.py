@@ -718,6 +718,114 @@ def mlp_ppo_fwd_bwd(b_obs, mb_inds, actor: MlpNetPtrs, critic: MlpNetPtrs, b_act
     return sc
 
 
+# ------------------------------------------------------------------------------------------- K8: the 256-wide tanh MLP agents
+MLP256_MAX_OBS, MLP256_MAX_OUT, MLP256_HIDDEN, MLP256_TILE = 256, 32, 256, 64
+
+
+def mlp256_supported(obs_dim: int, n_out: int) -> bool:
+    return 1 <= obs_dim <= MLP256_MAX_OBS and 1 <= n_out <= MLP256_MAX_OUT
+
+
+class Mlp256Nets:
+    """Actor-mean and critic ``nn.Sequential(Linear(O, 256), Tanh, Linear(256, 256), Tanh, Linear(256, n_out))`` for the K8 kernels
+    (csrc/mlp256.hip): the parameter / gradient pointer blocks, the weight pack and the workspace.  The pack is a derived weight in the
+    sense of ``cnn.TrunkBuffers._derived``: valid for ``(weights_version, the tensors' version counters, their addresses)`` and re-derived
+    INTO the same buffer when that tag moved -- whoever rewrites the parameters through raw pointers bumps ``weights_version``.  (The rule is
+    stated here again, not shared: ``_derived`` tags ONE tensor per entry and lives on the NatureCNN trunk's buffer object with its all-packs
+    launch; this pack is one buffer derived from twelve tensors of an agent that has no trunk.)  The
+    workspace is this object's own (the loss kernel between forward and backward uses the shared per-stream one); an outgrown
+    one is kept, never freed: a captured graph may have baked its address in."""
+
+    def __init__(self, actor, critic):
+        self.nets = [[m for m in seq if isinstance(m, torch.nn.Linear)] for seq in (actor, critic)]
+        a, c = self.nets
+        assert len(a) == 3 and len(c) == 3, "three Linear layers per network"
+        self.obs_dim, self.n_out = a[0].in_features, a[2].out_features
+        for lin, no in ((a, self.n_out), (c, 1)):
+            assert (lin[0].in_features, lin[0].out_features) == (self.obs_dim, MLP256_HIDDEN) and lin[2].out_features == no and \
+                (lin[1].in_features, lin[1].out_features, lin[2].in_features) == (MLP256_HIDDEN,) * 3, "the K8 kernels are O-256-256-n_out networks"
+        assert mlp256_supported(self.obs_dim, self.n_out), "outside the K8 kernels' shapes"
+        self.tensors = [[t for m in lin for t in (m.weight, m.bias)] for lin in self.nets]
+        for t in self.tensors[0] + self.tensors[1]:
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        self.device = self.tensors[0][0].device
+        self.weights_version = 0
+        self._pack = None            # (tag, uint8 tensor)
+        self._ws, self._old_ws = None, []
+
+    def _ptrs(self, tensors):
+        return (ctypes.c_void_p * 6)(*[t.data_ptr() for t in tensors])
+
+    def pack(self):
+        ts = self.tensors[0] + self.tensors[1]
+        tag = (self.weights_version, tuple(t._version for t in ts), tuple(t.data_ptr() for t in ts))
+        if self._pack is None or self._pack[0] != tag:
+            nbytes = _lib.load().mi355ppo_mlp256_pack_bytes(self.obs_dim, self.n_out)
+            buf = self._pack[1] if self._pack is not None else torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            _launch("mi355ppo_mlp256_pack_f32", self.device, self._ptrs(self.tensors[0]), self._ptrs(self.tensors[1]), self.obs_dim, self.n_out,
+                    _ptr(buf), buf.numel())
+            self._pack = (tag, buf)
+        return self._pack[1]
+
+    def workspace(self, M: int):
+        nbytes = _lib.load().mi355ppo_mlp256_workspace_bytes(int(M), self.obs_dim, self.n_out)
+        if self._ws is None or self._ws.numel() < nbytes:
+            if self._ws is not None:
+                self._old_ws.append(self._ws)
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def saved(self, M: int):
+        """Views of the workspace after a saving forward / the data gradient: ``(h1, h2, dz2, dz1)``, each (2 networks, M, 256)."""
+        f = self.workspace(M).view(torch.float32)
+        n = 2 * M * MLP256_HIDDEN
+        return tuple(f[i * n:(i + 1) * n].view(2, M, MLP256_HIDDEN) for i in range(4))
+
+    def grads(self):
+        out = []
+        for ts in self.tensors:
+            g = [t.grad for t in ts]
+            assert all(x is not None and x.is_contiguous() for x in g), "the K8 backward needs allocated .grad tensors (flat buffers)"
+            out.append(self._ptrs(g))
+        return out
+
+
+def mlp256_forward(obs, nets: Mlp256Nets, inds=None, save: bool = False, mean_out=None, value_out=None):
+    """Both networks' forward chain on ``obs[inds]`` (``inds`` None: ``obs``) in one launch -> ``(mean (M, n_out), value (M))``.
+    ``save``: h1 / h2 of both networks stay in ``nets``' workspace for ``mlp256_backward``."""
+    Bf, O = obs.shape
+    _chk(obs, torch.float32, "obs", (Bf, nets.obs_dim))
+    dev = obs.device
+    M = Bf
+    if inds is not None:
+        _chk(inds, torch.int64, "inds")
+        M = inds.numel()
+    mean = mean_out if mean_out is not None else torch.empty((M, nets.n_out), dtype=torch.float32, device=dev)
+    value = value_out if value_out is not None else torch.empty(M, dtype=torch.float32, device=dev)
+    _chk(mean, torch.float32, "mean_out", (M, nets.n_out))
+    _chk(value, torch.float32, "value_out", (M,))
+    ws = nets.workspace(M) if save else None
+    _launch("mi355ppo_mlp256_fwd_f32", dev, _ptr(obs), _ptr(inds), M, O, nets.n_out, _ptr(nets.pack()), _ptr(mean), _ptr(value), _ptr(ws),
+            ws.numel() if save else 0)
+    return mean, value
+
+
+def mlp256_backward(obs, nets: Mlp256Nets, dmean, dvalue, inds=None, slabs: int = 0):
+    """The backward of ``mlp256_forward(..., save=True)``: the data-gradient chain (one launch), then the six weight and six bias
+    gradients over row slabs and their fold in slab order (two launches).  The gradients are ADDED to the parameters' ``.grad``."""
+    M = dmean.shape[0]
+    _chk(obs, torch.float32, "obs", (obs.shape[0], nets.obs_dim))
+    _chk(dmean, torch.float32, "dmean", (M, nets.n_out))
+    dvalue = _chk(dvalue.reshape(-1), torch.float32, "dvalue", (M,))
+    if inds is not None:
+        _chk(inds, torch.int64, "inds", (M,))
+    dev, ws = obs.device, nets.workspace(M)
+    _launch("mi355ppo_mlp256_dgrad_f32", dev, _ptr(dmean), _ptr(dvalue), M, nets.obs_dim, nets.n_out, _ptr(nets.pack()), _ptr(ws), ws.numel())
+    ga, gc = nets.grads()
+    _launch("mi355ppo_mlp256_wgrad_f32", dev, _ptr(obs), _ptr(inds), _ptr(dmean), _ptr(dvalue), M, nets.obs_dim, nets.n_out, ga, gc, int(slabs),
+            _ptr(ws), ws.numel())
+
+
 # ------------------------------------------------------------------------------------------- LSTM
 def lstm_seq_dw_hh(dgx, record):
     """d W_hh = sum_t dgx[t]^T hk_t (hk: the record's plane 5), as the reference's per-step graphs accumulate it: one product of

@@ -67,6 +67,7 @@ extern "C" {
                                   only added, the number stays at 2.7.1;
                                   the plain ReLU network on one frame (ppo_atari_lstm.py) -- mi355ppo_cnn_conv1q1_fwd_bits, _fwd_amax and the
                                   twin mi355ppo_cnn_conv1q1_fwd_cpu likewise: only added, the number stays at 2.7.1;
+                                  the 256-wide tanh MLP family K8 -- mi355ppo_mlp256_* (no twins) likewise: only added, the number stays at 2.7.1;
                                   a binding must check major AND minor (cleanrl_amd/_lib.py does) */
 
 #if defined(__GNUC__)
@@ -395,6 +396,37 @@ MI355PPO_API int mi355ppo_mlp_ppo_normal_fwd_bwd_f32(
     const float* b_values, double clip_coef, double ent_coef, double vf_coef, int norm_adv, int clip_vloss, const float* adv_mean_den,
     void* const* actor_grads, void* const* critic_grads, float* dlogstd, float* scalars7, int rows_per_block, void* workspace,
     size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * K8  Two independent O -> 256 -> 256 -> n_out tanh networks (actor mean and critic of ppo_continuous_action_isaacgym.py) on the matrix
+ * pipe (csrc/mlp256.hip): a workgroup walks the whole layer chain for a tile of 64 rows with the hidden activations resident in LDS; the
+ * arithmetic is the two-term f16 split with one scale per weight matrix, 2^14 for tanh activations and one scale PER ROW TILE for the
+ * observation and gradient tiles.  1 <= O <= 256, 1 <= n_out <= 32, M >= 1; anything else returns MI355PPO_EINVAL before any launch.
+ * A network is a HOST array of six DEVICE pointers {W1 (256, O), b1, W2 (256, 256), b2, W3 (n_out, 256), b3}; the critic has one output.
+ *   mi355ppo_mlp256_pack_f32   both networks' matrices as hi / lo f16 terms in fragment order (forward and data-gradient orders), their
+ *                              scale exponents and the biases -> pack (mi355ppo_mlp256_pack_bytes, 16-byte aligned).  Two launches; once
+ *                              per optimizer step.
+ *   mi355ppo_mlp256_fwd_f32    rows obs[inds[i]] (inds NULL: obs[i]) -> mean (M, n_out), value (M).  One launch.  workspace non-NULL: h1, h2 of
+ *                              both networks are saved in it for the backward pass (rollout step / bootstrap value: NULL).
+ *   mi355ppo_mlp256_dgrad_f32  dmean (M, n_out), dvalue (M) and the saved h1, h2 -> dz2, dz1 in the workspace.  One launch.
+ *   mi355ppo_mlp256_wgrad_f32  the six weight and six bias gradients from the workspace, obs (gathered again) and dmean / dvalue: one launch
+ *                              over row slabs (slabs: 1..8, 0 = default) and a fold in slab order; the sums are ADDED to actor_grads /
+ *                              critic_grads (host arrays of six device pointers, the parameters' layouts).  No atomics: same inputs and
+ *                              slabs, same bits.
+ * The workspace (mi355ppo_mlp256_workspace_bytes, 16-byte aligned, the caller's) holds the saved activations, dz and the partials; NULL or
+ * short is MI355PPO_EWORKSPACE.  No allocation, no synchronisation, everything on `stream`: a minibatch is capturable.
+ */
+MI355PPO_API size_t mi355ppo_mlp256_pack_bytes(int O, int n_out);
+MI355PPO_API size_t mi355ppo_mlp256_workspace_bytes(int M, int O, int n_out);
+MI355PPO_API int mi355ppo_mlp256_pack_f32(const void* const* actor, const void* const* critic, int O, int n_out, void* pack, size_t pack_bytes,
+                                          void* stream);
+MI355PPO_API int mi355ppo_mlp256_fwd_f32(const float* obs, const int64_t* inds, int M, int O, int n_out, const void* pack, float* mean,
+                                         float* value, void* workspace, size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_mlp256_dgrad_f32(const float* dmean, const float* dvalue, int M, int O, int n_out, const void* pack, void* workspace,
+                                           size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_mlp256_wgrad_f32(const float* obs, const int64_t* inds, const float* dmean, const float* dvalue, int M, int O, int n_out,
+                                           void* const* actor_grads, void* const* critic_grads, int slabs, void* workspace,
+                                           size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * LSTM  The recurrence of ppo_atari_lstm.py's get_states (cleanrl/ppo_atari_lstm.py:140-158): one layer of nn.LSTM(512, 128)
