@@ -143,6 +143,15 @@ SIGNATURES = {
                                            c_int, c_int, c_int, c_int, _P]),
     "mi355ppo_trxl_attn_bwd_f32": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P,
                                            _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    # the TrXL layer's dense half on the matrix pipe (csrc/trxl_layer.hip)
+    "mi355ppo_trxl_layer_pack_bytes": (c_size_t, [c_int, c_int]),
+    "mi355ppo_trxl_layer_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mi355ppo_trxl_layer_pack_f32": (c_int, [_P, c_int, c_int, _P, c_size_t, _P]),
+    "mi355ppo_trxl_layer_pre_fwd_f32": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "mi355ppo_trxl_layer_post_fwd_f32": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "mi355ppo_trxl_layer_post_bwd_f32": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "mi355ppo_trxl_layer_pre_bwd_f32": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "mi355ppo_trxl_layer_wgrad_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     # the IMPALA-CNN trunk (csrc/impala.hip)
     "mi355ppo_impala_saved_floats": (c_int64, [c_int]),
     "mi355ppo_impala_argmax_bytes": (c_int64, [c_int]),

@@ -982,15 +982,16 @@ class MAAtariAgent(_NatureTrunkMixin, _DiscreteMixin, nn.Module):
 
 
 # ------------------------------------------------------------------------------------------- TrXL (ppo_trxl.py)
-TRXL_BACKENDS = ("torch", "fused")
+TRXL_BACKENDS = ("torch", "fused", "layer")
 
 
 def trxl_backend_from_env() -> str:
     """``MI355PPO_TRXL``: ``torch`` (default: the reference's window gather and attention ops) or ``fused`` (the episodic-memory
-    attention of csrc/trxl_attn.hip, ``ops.TrXLMemoryAttention``)."""
+    attention of csrc/trxl_attn.hip, ``ops.TrXLMemoryAttention``) or ``layer`` (that attention inside ``ops.TrXLLayer``: the rest of every
+    transformer layer on the MFMA kernels of csrc/trxl_layer.hip)."""
     v = os.environ.get("MI355PPO_TRXL", "torch")
     if v not in TRXL_BACKENDS:
-        raise ValueError(f"MI355PPO_TRXL={v!r}: expected torch or fused")
+        raise ValueError(f"MI355PPO_TRXL={v!r}: expected torch, fused or layer")
     return v
 
 
@@ -1077,6 +1078,7 @@ class TrXLTransformerLayer(nn.Module):
         self.norm_kv = nn.LayerNorm(dim)
         self.layer_norm_attn = nn.LayerNorm(dim)
         self.fc_projection = nn.Sequential(nn.Linear(dim, dim), nn.ReLU())
+        self._layer_pack = None                                   # ops.TrXLLayerPack of the ``layer`` backend, made on first use
 
     def forward(self, value, key, query, mask):
         query_ = self.layer_norm_q(query)
@@ -1099,6 +1101,15 @@ class TrXLTransformerLayer(nn.Module):
         x = att.fc_out(att.values(u).reshape(B, att.embed_dim)) + x
         return self.fc_projection(self.layer_norm_attn(x)) + x
 
+    def forward_layer(self, x, window, layer, pos, mask, pe):
+        """The whole layer as one autograd node on the kernels of csrc/trxl_layer.hip around the attention kernel (``ops.TrXLLayer``).
+        CPU tensors take ``forward_fused``: torch dense ops around the attention's host twins."""
+        if not x.is_cuda:
+            return self.forward_fused(x, window, layer, pos, mask, pe)
+        if self._layer_pack is None or self._layer_pack.device != x.device:
+            self._layer_pack = ops.TrXLLayerPack(self.attention.embed_dim, self.attention.num_heads, x.device)
+        return ops.trxl_layer(x, list(self.parameters()), self._layer_pack, window.pool, layer, window.ep, window.rows, pos, mask, pe)
+
 
 class TrXLTransformer(nn.Module):
     """ppo_trxl.py ``Transformer``: positional encoding (``absolute``, ``learned`` or none) added to the memory window, then the
@@ -1116,7 +1127,7 @@ class TrXLTransformer(nn.Module):
         self.backend = backend
 
     def forward(self, x, memories, mask, memory_indices):
-        if self.backend == "fused":
+        if self.backend in ("fused", "layer"):
             return self._forward_fused(x, memories, mask, memory_indices)
         if isinstance(memories, MemoryWindow):
             memories = memories.gather()
@@ -1143,7 +1154,8 @@ class TrXLTransformer(nn.Module):
         out_memories = []
         for i, layer in enumerate(self.transformer_layers):
             out_memories.append(x.detach())
-            x = layer.forward_fused(x, memories, i, memory_indices, mask, pe)
+            step = layer.forward_layer if self.backend == "layer" else layer.forward_fused
+            x = step(x, memories, i, memory_indices, mask, pe)
         return x, torch.stack(out_memories, dim=1)
 
 
@@ -1154,7 +1166,8 @@ class TrXLAgent(nn.Module):
     seeded construction gives the reference's weights.
 
     ``trxl_backend`` (from ``MI355PPO_TRXL`` at construction): ``torch`` runs the reference's ops; ``fused`` routes each layer's
-    window path through ``ops.TrXLMemoryAttention`` (HIP kernels on the GPU, their host twins on CPU).  ``fused`` refuses a
+    window path through ``ops.TrXLMemoryAttention`` (HIP kernels on the GPU, their host twins on CPU); ``layer`` runs every whole
+    transformer layer as ``ops.TrXLLayer`` (csrc/trxl_layer.hip around the same attention kernels; on CPU it is ``fused``).  Both refuse a
     ``learned`` positional encoding, whose gradient would be a scatter-add into the table.  The ``memory`` argument of the methods
     is a gathered window (B, L, layers, D), as in the reference, or a ``MemoryWindow`` into an episode pool."""
 
@@ -1163,8 +1176,8 @@ class TrXLAgent(nn.Module):
         self.obs_shape = observation_space.shape
         self.max_episode_steps = max_episode_steps
         self.trxl_backend = trxl_backend_from_env()
-        if self.trxl_backend == "fused" and args.trxl_positional_encoding == "learned":
-            raise ValueError("MI355PPO_TRXL=fused does not support --trxl-positional-encoding learned (use torch)")
+        if self.trxl_backend != "torch" and args.trxl_positional_encoding == "learned":
+            raise ValueError(f"MI355PPO_TRXL={self.trxl_backend} does not support --trxl-positional-encoding learned (use torch)")
 
         if len(self.obs_shape) > 1:
             self.encoder = nn.Sequential(
@@ -1208,7 +1221,7 @@ class TrXLAgent(nn.Module):
     @trxl_backend.setter
     def trxl_backend(self, v):
         if v not in TRXL_BACKENDS:
-            raise ValueError(f"trxl_backend={v!r}: expected torch or fused")
+            raise ValueError(f"trxl_backend={v!r}: expected torch, fused or layer")
         self._trxl_backend = v
         if "transformer" in self._modules:
             self.transformer.backend = v

@@ -21,7 +21,7 @@ minibatch loss, AdamW, ``clip_grad_norm_``,
 
 The episode memories live in one pool tensor (``self.pool``, (episodes, T_ep, layers, D)) instead of a Python list of views
 stacked before the update: the slot of an episode is the reference's ``stored_memory_index``.  With the ``torch`` backend the
-minibatch windows are gathered as the reference gathers them; with ``fused`` the kernel reads the rows straight from the pool.
+minibatch windows are gathered as the reference gathers them; with ``fused`` and ``layer`` the kernel reads the rows straight from the pool.
 The loss and the optimizer stay torch ops (the loss has one policy term per action branch).
 """
 from __future__ import annotations
@@ -121,7 +121,7 @@ class TrXLLearner:
 
     # ------------------------------------------------------------------ rollout
     def _window(self, memory, rows):
-        if self.agent.trxl_backend == "fused":
+        if self.agent.trxl_backend in ("fused", "layer"):
             return MemoryWindow(memory, self.env_ids, rows)
         return batched_index_select(memory, 1, rows)
 
@@ -172,7 +172,7 @@ class TrXLLearner:
         b_memory_indices = self.stored_memory_indices.reshape(-1, *self.stored_memory_indices.shape[2:])
         b_memory_mask = self.stored_memory_masks.reshape(-1, *self.stored_memory_masks.shape[2:])
         stored_memories = self.pool
-        fused = self.agent.trxl_backend == "fused"
+        fused = self.agent.trxl_backend in ("fused", "layer")
 
         actual_max_episode_steps = (self.stored_memory_indices * self.stored_memory_masks).max().item() + 1
         self.trimmed = actual_max_episode_steps < self.L

@@ -32,7 +32,7 @@ __all__ = [
     "ppo_loss_categorical", "ppo_loss_normal", "obs_u8_to_f32", "obs_nchw_to_nhwc_u8", "clip_adam_", "PPOLossCategorical", "PPOLossNormal",
     "CategoricalLogProbEntropy", "NormalLogProbEntropy", "LOSS_SCALAR_NAMES", "LSTMSeq", "lstm_seq", "lstm_seq_dw_hh",
     "ImpalaTrunk", "impala_trunk", "impala_param_shapes", "Impala84Trunk", "impala84_trunk", "impala84_param_shapes", "impala84_params",
-    "TrXLMemoryAttention", "trxl_memory_attention", "pqn_param_count", "radam_schedule", "clip_radam_sched_",
+    "TrXLMemoryAttention", "trxl_memory_attention", "TrXLLayer", "TrXLLayerPack", "trxl_layer", "trxl_layer_supported", "pqn_param_count", "radam_schedule", "clip_radam_sched_",
     "offpolicy_counts", "sac_actor_count", "dqn_counts", "dqn_limits_ok", "dqn_head_limits_ok", "qdagger_head_limits_ok",
     "rainbow_noisy_limits_ok", "rainbow_noisy_counts", "rainbow_new_buffer", "rainbow_head_limits_ok", "sacd_limits_ok", "rnd_mean_var",
     *replay_ops.OPERATORS, *rnd_ops.OPERATORS, *ppg_ops.OPERATORS, *twin_ops.OPERATORS,
@@ -922,6 +922,150 @@ def trxl_memory_attention(q, gamma, beta, memory, layer: int, ep, rows, pos, mas
     memory, ep, rows, pos, mask, pe = _trxl_inputs(memory, ep, rows, pos, mask, pe)
     u, _ = fwd(memory, layer, ep, rows, pos, mask, pe, gamma.detach().contiguous(), beta.detach().contiguous(), q.detach().contiguous())
     return u
+
+
+# ------------------------------------------------------------------------------------------- TrXL: a whole layer (csrc/trxl_layer.hip)
+# the 13 parameters of agents.TrXLTransformerLayer in module order; norm_kv's two belong to the attention kernel
+TRXL_LAYER_PARAMS = ("attention.values.weight", "attention.keys.weight", "attention.queries.weight", "attention.fc_out.weight",
+                     "attention.fc_out.bias", "layer_norm_q.weight", "layer_norm_q.bias", "norm_kv.weight", "norm_kv.bias",
+                     "layer_norm_attn.weight", "layer_norm_attn.bias", "fc_projection.0.weight", "fc_projection.0.bias")
+_TRXL_NORM_KV = (7, 8)
+TRXL_LAYER_SAVED = ("x1", "f", "n1", "n2", "df", "dx1")
+
+
+def trxl_layer_supported(D: int, H: int) -> bool:
+    return _lib.load().mi355ppo_trxl_layer_pack_bytes(int(D), int(H)) > 0
+
+
+class TrXLLayerPack:
+    """The derived weights of one TransformerLayer for the ``layer`` kernels: A = blockdiag(Wq^T Wk), Wvo = blockdiag(Wv^T) Wo^T and Wp as
+    split f16 fragments, with the biases and LayerNorm vectors.  Valid for ``(the 13 tensors' version counters, their addresses)`` and
+    re-derived INTO the same buffer when that tag moved (``Mlp256Nets.pack``'s rule): an optimizer's in-place step advances the counters.
+    ``slabs``: the weight gradient's slab count (0: the library's default)."""
+
+    def __init__(self, D: int, H: int, device, slabs: int = 0):
+        if not trxl_layer_supported(D, H):
+            raise ValueError(f"TrXL layer kernels: D={D} H={H} (need D % 64 == 0, D <= 512, H dividing 64)")
+        self.D, self.H, self.device, self.slabs = int(D), int(H), torch.device(device), int(slabs)
+        self._pack = None            # (tag, uint8 tensor)
+
+    def _check(self, params):
+        D, d = self.D, self.D // self.H
+        shapes = [(d, d)] * 3 + [(D, D)] + [(D,)] * 7 + [(D, D), (D,)]
+        assert len(params) == len(shapes), "a TransformerLayer has 13 parameters"
+        return [_chk(p, torch.float32, n, s) for p, n, s in zip(params, TRXL_LAYER_PARAMS, shapes)]
+
+    def pack(self, params, out=None):
+        params = self._check([p.detach() for p in params])
+        tag = (tuple(p._version for p in params), tuple(p.data_ptr() for p in params))
+        if out is not None or self._pack is None or self._pack[0] != tag:
+            nbytes = _lib.load().mi355ppo_trxl_layer_pack_bytes(self.D, self.H)
+            buf = out if out is not None else self._pack[1] if self._pack is not None else torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            _launch("mi355ppo_trxl_layer_pack_f32", self.device, twin_ops._ptr_array(params), self.D, self.H, _ptr(buf), buf.numel())
+            self._pack = (tag, buf)
+        return self._pack[1]
+
+    def workspace(self, B: int):
+        """A fresh workspace for one forward / backward pair of ``B`` rows (the autograd node keeps it until its backward ran)."""
+        return torch.empty(_lib.load().mi355ppo_trxl_layer_workspace_bytes(int(B), self.D, self.H), dtype=torch.uint8, device=self.device)
+
+    def saved(self, ws, B: int):
+        """Views of a workspace's (B, D) planes by name (``TRXL_LAYER_SAVED``)."""
+        f, n = ws.view(torch.float32), B * self.D
+        return {k: f[i * n:(i + 1) * n].view(B, self.D) for i, k in enumerate(TRXL_LAYER_SAVED)}
+
+
+def _trxl_layer_call(name, pk: TrXLLayerPack, pack, ws, out, *ins):
+    B = ins[0].shape[0]
+    for i, t in enumerate(ins):
+        _chk(t, torch.float32, f"{name} input {i}", (B, pk.D))
+    out = torch.empty((B, pk.D), dtype=torch.float32, device=pk.device) if out is None else _chk(out, torch.float32, "out", (B, pk.D))
+    _launch(name, pk.device, *[_ptr(t) for t in ins], B, pk.D, pk.H, _ptr(pack), _ptr(out), _ptr(ws), 0 if ws is None else ws.numel())
+    return out
+
+
+def trxl_layer_pre_forward(x, pk, pack, ws=None, out=None):
+    """q~ = LN_q(x) A (B, D); with ``ws`` the backward's LN_q(x) and statistics are saved."""
+    return _trxl_layer_call("mi355ppo_trxl_layer_pre_fwd_f32", pk, pack, ws, out, x)
+
+
+def trxl_layer_post_forward(x, u, pk, pack, ws=None, out=None):
+    """y = relu(LN_attn(x1) Wp^T + b_p) + x1, x1 = (u Wvo + b_o) + x; with ``ws`` x1, the ReLU output and LN_attn(x1) are saved."""
+    return _trxl_layer_call("mi355ppo_trxl_layer_post_fwd_f32", pk, pack, ws, out, x, u)
+
+
+def trxl_layer_post_backward(dy, pk, pack, ws, out=None):
+    """du of the attention's output from dy; df and dx1 stay in ``ws``."""
+    return _trxl_layer_call("mi355ppo_trxl_layer_post_bwd_f32", pk, pack, ws, out, dy)
+
+
+def trxl_layer_pre_backward(dqt, x, pk, pack, ws, out=None):
+    """dx from the attention backward's dq~ and the skip's dx1 in ``ws``."""
+    return _trxl_layer_call("mi355ppo_trxl_layer_pre_bwd_f32", pk, pack, ws, out, dqt, x)
+
+
+def trxl_layer_wgrad(u, dqt, params, grads, pk, ws, slabs: int = 0):
+    """The eleven parameter gradients of the dense half, ADDED into ``grads`` (13 tensors in ``TRXL_LAYER_PARAMS`` order; norm_kv's are
+    left alone)."""
+    B = u.shape[0]
+    _chk(u, torch.float32, "u", (B, pk.D))
+    _chk(dqt, torch.float32, "dqt", (B, pk.D))
+    params = pk._check([p.detach() for p in params])
+    for g, p in zip(grads, params):
+        _chk(g, torch.float32, "grad", p.shape)
+    _launch("mi355ppo_trxl_layer_wgrad_f32", pk.device, _ptr(u), _ptr(dqt), twin_ops._ptr_array(params), twin_ops._ptr_array(list(grads)), B, pk.D, pk.H,
+            int(slabs), _ptr(ws), ws.numel())
+
+
+def _trxl_layer_forward(x, params, pk, memory, layer, ep, rows, pos, mask, pe, ws):
+    B, D, H = x.shape[0], pk.D, pk.H
+    pack = pk.pack(params)
+    qt = trxl_layer_pre_forward(x, pk, pack, ws)
+    u, stats = trxl_attn_forward(memory, layer, ep, rows, pos, mask, pe, params[7].detach().contiguous(), params[8].detach().contiguous(),  # noqa: F821
+                                 qt.view(B, H, D // H))
+    return pack, qt, u, stats, trxl_layer_post_forward(x, u.view(B, D), pk, pack, ws)
+
+
+class TrXLLayer(torch.autograd.Function):
+    """Differentiable ``(x, the layer's 13 parameters; memory, layer, ep, rows, pos, mask, pe, pack holder) -> y``: one whole
+    TransformerLayer of ppo_trxl.py -- pre (LN_q, q~) -> ``TrXLMemoryAttention``'s kernels -> post (values / fc_out, skip, LN_attn,
+    fc_projection, skip) -- and the same in reverse, on csrc/trxl_layer.hip and csrc/trxl_attn.hip.  CUDA tensors only."""
+
+    @staticmethod
+    def forward(ctx, x, *rest):
+        params, (memory, layer, ep, rows, pos, mask, pe, pk) = rest[:13], rest[13:]
+        memory, ep, rows, pos, mask, pe = _trxl_inputs(memory, ep, rows, pos, mask, pe)
+        x = x.detach().contiguous()
+        ws = pk.workspace(x.shape[0])
+        pack, qt, u, stats, y = _trxl_layer_forward(x, params, pk, memory, layer, ep, rows, pos, mask, pe, ws)
+        ctx.layer, ctx.pk, ctx.pack, ctx.has_pe = layer, pk, pack, pe is not None
+        ctx.save_for_backward(x, qt, u, stats, ws, memory, ep, rows, mask, *(() if pe is None else (pos, pe)), *params)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, qt, u, stats, ws, memory, ep, rows, mask, *tail = ctx.saved_tensors
+        (pos, pe), params = (tail[:2], tail[2:]) if ctx.has_pe else ((None, None), tail)
+        pk, pack = ctx.pk, ctx.pack
+        B, D, H = x.shape[0], pk.D, pk.H
+        du = trxl_layer_post_backward(dy.contiguous(), pk, pack, ws)
+        gkv, bkv = params[7].detach().contiguous(), params[8].detach().contiguous()
+        dqt, dgkv, dbkv = trxl_attn_backward(memory, ctx.layer, ep, rows, pos, mask, pe, gkv, bkv, qt.view(B, H, D // H), u, stats,  # noqa: F821
+                                             du.view(B, H, D // H))
+        dqt = dqt.view(B, D)
+        dx = trxl_layer_pre_backward(dqt, x, pk, pack, ws)
+        grads = [dgkv if i == 7 else dbkv if i == 8 else torch.zeros_like(p) for i, p in enumerate(params)]
+        trxl_layer_wgrad(u.view(B, D), dqt, params, grads, pk, ws, pk.slabs)
+        return (dx, *grads, None, None, None, None, None, None, None, None)
+
+
+def trxl_layer(x, params, pk: TrXLLayerPack, memory, layer: int, ep, rows, pos, mask, pe):
+    """``TrXLLayer.apply`` when a gradient is wanted, else the two forward launches around the attention forward with nothing saved (the
+    rollout step, the bootstrap value)."""
+    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+        return TrXLLayer.apply(x, *params, memory, layer, ep, rows, pos, mask, pe, pk)
+    memory, ep, rows, pos, mask, pe = _trxl_inputs(memory, ep, rows, pos, mask, pe)
+    return _trxl_layer_forward(x.detach().contiguous(), params, pk, memory, layer, ep, rows, pos, mask, pe, None)[4]
 
 
 # ------------------------------------------------------------------------------------------- IMPALA-CNN trunks

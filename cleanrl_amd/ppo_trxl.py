@@ -5,7 +5,8 @@
 The network, rollout, episodic-memory bookkeeping and update are the reference's (``TrXLAgent`` in cleanrl_amd/agents.py,
 ``TrXLLearner`` in cleanrl_amd/learner_trxl.py).  ``MI355PPO_TRXL=fused`` runs each layer's memory-window attention -- the
 window gather, positional encoding, ``norm_kv``, keys, masked softmax and weighted sum -- as one HIP kernel that streams the
-rows from the episode pool (csrc/trxl_attn.hip); the default ``torch`` runs the reference's ops.  GAE runs in the K1 kernel on
+rows from the episode pool (csrc/trxl_attn.hip); ``MI355PPO_TRXL=layer`` runs the rest of every transformer layer around that
+kernel on MFMA kernels as well (csrc/trxl_layer.hip); the default ``torch`` runs the reference's ops.  GAE runs in the K1 kernel on
 the GPU.  Without ``gymnasium`` / ``memory_gym`` the synthetic memory task of cleanrl_amd/envs.py stands in
 (``SyntheticMemoryVecEnv``: vector or (84, 84, 3) image observations, Discrete or MultiDiscrete actions, by env id).
 

@@ -68,6 +68,7 @@ extern "C" {
                                   the plain ReLU network on one frame (ppo_atari_lstm.py) -- mi355ppo_cnn_conv1q1_fwd_bits, _fwd_amax and the
                                   twin mi355ppo_cnn_conv1q1_fwd_cpu likewise: only added, the number stays at 2.7.1;
                                   the 256-wide tanh MLP family K8 -- mi355ppo_mlp256_* (no twins) likewise: only added, the number stays at 2.7.1;
+                                  the TrXL layer's dense half -- mi355ppo_trxl_layer_* (no twins) likewise: only added, the number stays at 2.7.1;
                                   a binding must check major AND minor (cleanrl_amd/_lib.py does) */
 
 #if defined(__GNUC__)
@@ -492,6 +493,45 @@ MI355PPO_API int mi355ppo_trxl_attn_bwd_f32(const float* memory, int E, int T_ep
                                             const float* gamma, const float* beta, const float* q, const float* u, const float* stats,
                                             const float* du, float* dq, float* dln_rows, float* dgamma, float* dbeta, int* err, int B,
                                             int L, int D, int H, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * TRXL LAYER  The dense half of ppo_trxl.py's TransformerLayer around the attention above, on the matrix pipe (csrc/trxl_layer.hip;
+ * MI355PPO_TRXL=layer).  With d = D / H and the per-head (d, d) matrices expanded to block-diagonal (D, D) ones:
+ *   pre   q~ = LN_q(x) A,  A = blockdiag(Wq^T Wk)                                 (then mi355ppo_trxl_attn_fwd_f32: q~ -> u)
+ *   post  x1 = (u Wvo + b_o) + x,  Wvo = blockdiag(Wv^T) Wo^T;  y = relu(LN_attn(x1) Wp^T + b_p) + x1
+ * and their backwards; two-term f16 split with one scale per packed matrix and one per activation / gradient row, exact f32 LayerNorms.
+ * `params` / `grads` are HOST arrays of the layer's 13 DEVICE pointers in module order: values.weight (d, d), keys.weight, queries.weight,
+ * fc_out.weight (D, D), fc_out.bias, layer_norm_q.weight, .bias, norm_kv.weight, .bias (unused here: may be NULL), layer_norm_attn.weight,
+ * .bias, fc_projection.0.weight (D, D), .bias.  Shapes as the attention's: D % 64 == 0, D <= 512, H dividing 64; B >= 1; else
+ * MI355PPO_EINVAL before any launch.  x, u, q~, y and every gradient of them are (B, D) f32.
+ *   mi355ppo_trxl_layer_pack_f32      A, Wvo (f64 accumulation, rounded once) and Wp as hi / lo f16 terms in MFMA B-fragment order, forward
+ *                                     and transposed, with their scale exponents, the biases and the LayerNorm vectors -> pack
+ *                                     (mi355ppo_trxl_layer_pack_bytes, 16-byte aligned).  Three launches; once per optimizer step.
+ *   mi355ppo_trxl_layer_pre_fwd_f32   x -> q~.                       workspace non-NULL: LN_q(x) and its (mean, rstd) are saved.
+ *   mi355ppo_trxl_layer_post_fwd_f32  x, u -> y.                     workspace non-NULL: x1, the ReLU output, LN_attn(x1), (mean, rstd) are saved.
+ *   mi355ppo_trxl_layer_post_bwd_f32  dy -> du (for mi355ppo_trxl_attn_bwd_f32); df and dx1 stay in the workspace.
+ *   mi355ppo_trxl_layer_pre_bwd_f32   dq~ (the attention backward's dq), x -> dx (the skip's dx1 added).
+ *   mi355ppo_trxl_layer_wgrad_f32     the eleven parameter gradients (all but norm_kv's) from the workspace, u and dq~: reductions over
+ *                                     slabs of rows (slabs: 1..8, 0 = default), a fold in slab order and a parameter-sized launch that maps
+ *                                     dA, dWvo to dWq, dWk, dWv, dWo; the sums are ADDED to `grads`.  No atomics: same inputs and slabs,
+ *                                     same bits.
+ * One workspace (mi355ppo_trxl_layer_workspace_bytes, 16-byte aligned, the caller's) serves one forward / backward pair of one layer; the
+ * forwards accept NULL (nothing saved: the rollout step, the bootstrap value), the others return MI355PPO_EWORKSPACE for NULL or short.
+ * No allocation, no synchronisation, everything on `stream`.
+ */
+MI355PPO_API size_t mi355ppo_trxl_layer_pack_bytes(int D, int H);
+MI355PPO_API size_t mi355ppo_trxl_layer_workspace_bytes(int B, int D, int H);
+MI355PPO_API int mi355ppo_trxl_layer_pack_f32(const void* const* params, int D, int H, void* pack, size_t pack_bytes, void* stream);
+MI355PPO_API int mi355ppo_trxl_layer_pre_fwd_f32(const float* x, int B, int D, int H, const void* pack, float* qt, void* workspace,
+                                                 size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_trxl_layer_post_fwd_f32(const float* x, const float* u, int B, int D, int H, const void* pack, float* y,
+                                                  void* workspace, size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_trxl_layer_post_bwd_f32(const float* dy, int B, int D, int H, const void* pack, float* du, void* workspace,
+                                                  size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_trxl_layer_pre_bwd_f32(const float* dqt, const float* x, int B, int D, int H, const void* pack, float* dx,
+                                                 void* workspace, size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_trxl_layer_wgrad_f32(const float* u, const float* dqt, const void* const* params, void* const* grads, int B, int D,
+                                               int H, int slabs, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * IMPALA  The IMPALA-CNN trunk of ppo_procgen.py / ppg_procgen.py (cleanrl/ppo_procgen.py:86-124, cleanrl/ppg_procgen.py:123-165):

@@ -1,5 +1,6 @@
-"""ppo_trxl.py's memory attention on one MI355X with both TrXL backends (``torch``: the reference's whole-episode gather and
-attention ops, ``fused``: the episodic-memory attention of csrc/trxl_attn.hip); JSON lines to stdout and to --out.
+"""ppo_trxl.py's transformer on one MI355X with the three TrXL backends (``torch``: the reference's whole-episode gather and
+attention ops, ``fused``: the episodic-memory attention of csrc/trxl_attn.hip, ``layer``: that attention inside whole-layer MFMA kernels,
+csrc/trxl_layer.hip), all in one process; JSON lines to stdout and to --out.
 
     python tools/trxlbench.py [--minibatch] [--update] [--kernel] [--out FILE]
 
@@ -8,7 +9,8 @@ attention ops, ``fused``: the episodic-memory attention of csrc/trxl_attn.hip); 
   --update     one TrXLLearner.update() (3 epochs x 8 minibatches of 32 envs x 512 steps, T_ep = 1024: a Memory Gym env
                without a step limit) on a synthetic rollout; host wall time ending in the metrics' device -> host copies,
                median of --reps
-  --kernel     the attention kernels alone (forward, backward) at the update size (B = 2,048) and the rollout size (B = 32)
+  --kernel     the attention kernels alone (forward, backward) at the update size (B = 2,048) and the rollout size (B = 32), and the
+               ``layer`` backend's launches of one layer (pack, pre / post forward, post / pre backward, weight gradients) at B = 2,048
 """
 import argparse
 import json
@@ -26,6 +28,7 @@ from cleanrl_amd.learner_trxl import TrXLLearner  # noqa: E402
 from cleanrl_amd.ppo_trxl import Args  # noqa: E402
 
 DEV = torch.device("cuda:0")
+BACKENDS = ("torch", "fused", "layer")
 
 
 def _emit(rec, out):
@@ -71,7 +74,7 @@ def _windows(args, T_ep, E_, B, g):
 
 def bench_minibatch(reps, out, T_ep=512, E_=64, B=2048):
     g = torch.Generator().manual_seed(0)
-    for backend in ("torch", "fused"):
+    for backend in BACKENDS:
         args, agent = _agent(backend, T_ep)
         pool = torch.randn((E_, T_ep, args.trxl_num_layers, args.trxl_dim), generator=g).to(DEV)
         ep, idx, mask = _windows(args, T_ep, E_, B, g)
@@ -79,7 +82,7 @@ def bench_minibatch(reps, out, T_ep=512, E_=64, B=2048):
         act = torch.randint(0, 4, (B, 1), generator=g).to(DEV)
 
         def step():
-            if backend == "fused":
+            if backend != "torch":
                 win = MemoryWindow(pool, ep, idx)
             else:                                                # the reference's minibatch: whole episodes, then the windows
                 from cleanrl_amd.agents import batched_index_select
@@ -96,7 +99,7 @@ def bench_minibatch(reps, out, T_ep=512, E_=64, B=2048):
 
 def bench_update(reps, out, T_ep=1024):
     g = torch.Generator().manual_seed(1)
-    for backend in ("torch", "fused"):
+    for backend in BACKENDS:
         args, agent = _agent(backend, T_ep)
         N, T = args.num_envs, args.num_steps
         L = TrXLLearner(agent, args, E.Box(0, 255, (84, 84, 3), np.uint8), (4,), N, T_ep, DEV)
@@ -145,6 +148,33 @@ def bench_kernel(reps, out, T_ep=512, E_=64):
                "bwd_ms_median": bwd[0], "fwd_ms_min": fwd[1], "bwd_ms_min": bwd[1]}, out)
 
 
+def bench_layer_kernels(reps, out, B=2048):
+    """The ``layer`` backend's own launches for one transformer layer at the script's D and H."""
+    from cleanrl_amd.agents import TrXLTransformerLayer
+
+    args = Args()
+    D, H = args.trxl_dim, args.trxl_num_heads
+    torch.manual_seed(3)
+    params = [p.detach() for p in TrXLTransformerLayer(D, H).to(DEV).parameters()]
+    grads = [torch.zeros_like(p) for p in params]
+    pk = ops.TrXLLayerPack(D, H, DEV)
+    pack, ws = pk.pack(params), pk.workspace(B)
+    x, u, dy = (torch.randn((B, D), device=DEV) for _ in range(3))
+    o = torch.empty((B, D), device=DEV)
+    ops.trxl_layer_pre_forward(x, pk, pack, ws, o)
+    ops.trxl_layer_post_forward(x, u, pk, pack, ws, o)
+    ops.trxl_layer_post_backward(dy, pk, pack, ws, o)
+    steps = {"pack": lambda: pk.pack(params, out=pack), "pre_fwd": lambda: ops.trxl_layer_pre_forward(x, pk, pack, ws, o),
+             "post_fwd": lambda: ops.trxl_layer_post_forward(x, u, pk, pack, ws, o),
+             "post_bwd": lambda: ops.trxl_layer_post_backward(dy, pk, pack, ws, o),
+             "pre_bwd": lambda: ops.trxl_layer_pre_backward(dy, x, pk, pack, ws, o),
+             "wgrad": lambda: ops.trxl_layer_wgrad(u, dy, params, grads, pk, ws)}
+    rec = {"bench": "trxl_layer_kernels", "B": B, "D": D, "H": H}
+    for name, fn in steps.items():
+        rec[name + "_ms_median"], rec[name + "_ms_min"] = _event_time(fn, reps)
+    _emit(rec, out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--minibatch", action="store_true")
@@ -156,6 +186,7 @@ def main():
     everything = not (a.minibatch or a.update or a.kernel)
     if a.kernel or everything:
         bench_kernel(max(a.reps, 20), a.out)
+        bench_layer_kernels(max(a.reps, 20), a.out)
     if a.minibatch or everything:
         bench_minibatch(a.reps, a.out)
     if a.update or everything:
