@@ -158,6 +158,8 @@ SIGNATURES = {
     "mi355ppo_impala_workspace_bytes": (c_size_t, [c_int, c_int]),
     "mi355ppo_impala_fwd_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     "mi355ppo_impala_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "mi355ppo_impala_fwd_pooled_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "mi355ppo_impala_bwd_pooled_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     "mi355ppo_impala84_saved_floats": (c_int64, [c_int]),
     "mi355ppo_impala84_argmax_bytes": (c_int64, [c_int]),
     "mi355ppo_impala84_workspace_bytes": (c_size_t, [c_int, c_int]),

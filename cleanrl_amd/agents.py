@@ -514,28 +514,29 @@ class AtariLSTMAgent(_NatureTrunkMixin, _DiscreteMixin, nn.Module):
         return action, lp, ent, self.critic(hidden), lstm_state
 
 
-IMPALA_BACKENDS = ("torch", "fused")
+IMPALA_BACKENDS = ("torch", "fused", "pooled")
 
 
 def impala_backend_from_env() -> str:
-    """``MI355PPO_IMPALA``: ``torch`` (default: the reference's ConvSequence modules) or ``fused`` (the trunk kernels of
-    csrc/impala.hip, ``ops.impala_trunk``)."""
+    """``MI355PPO_IMPALA``: ``torch`` (default: the reference's ConvSequence modules), ``fused`` (the trunk kernels of
+    csrc/impala.hip, ``ops.impala_trunk``) or ``pooled`` (the same trunk with each max pool inside its conv launches; 64x64x3 frames
+    only, same bits as ``fused``)."""
     v = os.environ.get("MI355PPO_IMPALA", "torch")
     if v not in IMPALA_BACKENDS:
-        raise ValueError(f"MI355PPO_IMPALA={v!r}: expected torch or fused")
+        raise ValueError(f"MI355PPO_IMPALA={v!r}: expected torch, fused or pooled")
     return v
 
 
 def _impala_features(agent, xn):
     """The IMPALA network (conv sequences, then Flatten -> ReLU -> Linear -> ReLU) on normalised (B, C, H, W) frames.  With the
-    ``fused`` backend the three conv sequences run as ``ops.impala_trunk`` on the channels-last frames (``xn`` is a permuted
-    view of them, so the permute back is free) and the tail runs on the NCHW view of the trunk's output, so ``Flatten`` sees
-    the reference's (C, H, W) order."""
-    if agent.impala_backend != "fused":
+    ``fused`` and ``pooled`` backends the three conv sequences run as ``ops.impala_trunk`` on the channels-last frames (``xn`` is a
+    permuted view of them, so the permute back is free) and the tail runs on the NCHW view of the trunk's output, so ``Flatten``
+    sees the reference's (C, H, W) order.  The one place that turns the backend into ``ops.impala_trunk``'s ``pooled`` flag."""
+    if agent.impala_backend == "torch":
         return agent.network(xn)
     net = agent.network
     params = [p for i in range(3) for p in net[i].parameters()]
-    y = ops.impala_trunk(xn.permute(0, 2, 3, 1), params)
+    y = ops.impala_trunk(xn.permute(0, 2, 3, 1), params, pooled=agent.impala_backend == "pooled")
     return net[3:](y.permute(0, 3, 1, 2))
 
 
@@ -606,6 +607,9 @@ class AtariImpalaQNetwork(nn.Module):
         ]
         self.network = nn.Sequential(*conv_seqs)
         self.impala_backend = impala_backend_from_env()
+        if self.impala_backend == "pooled":
+            raise NotImplementedError("MI355PPO_IMPALA=pooled serves the 64x64x3 trunk (ppo_procgen / ppg_procgen) only: the 84 / 42 / 21 planes "
+                                      "of Atari stacks need a band geometry of their own; use MI355PPO_IMPALA=fused")
 
     def hidden_hwc(self, x_hwc):
         """(B, 84, 84, 4) uint8 channels-last rows -> the 256-wide hidden layer (the input of the Q head)."""

@@ -891,7 +891,7 @@ void imp_pool_fwd_host(const float* x, float* y, uint8_t* arg, int B, int h, int
             for (int ox = 0; ox < ho; ++ox)
                 for (int ch = 0; ch < c; ++ch) {
                     const int64_t i = ((img * ho + oy) * ho + ox) * c + ch;
-                    y[i] = imp_pool_window(x + img * h * h * c + ch, h, c, oy, ox, arg + i);
+                    y[i] = imp_pool_window(x + img * h * h * c + ch, h, 0, h, c, oy, ox, arg + i);
                 }
 }
 

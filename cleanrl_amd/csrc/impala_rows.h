@@ -150,8 +150,10 @@ MI355_HD float imp_epi_dgrad(float acc, const float* mask, const float* res) {
     return res ? v + *res : v;
 }
 
-// Max pool of output (oy, ox) of one channel: src points at channel c of pixel (0, 0) of the image, pixels C floats apart.
-MI355_HD float imp_pool_window(const float* src, int h, int c_stride, int oy, int ox, uint8_t* arg) {
+// Max pool of output (oy, ox) of one channel of an h x h image.  src points at channel c of pixel (row0, 0) of wherever the image's
+// rows are held -- the whole image in global memory (row0 = 0, pitch = h), or a band of rows in LDS --: pixel (y, x) is
+// src[((y - row0) * pitch + x) * c_stride].  One definition for the global-memory kernel, the twin and the fused conv + pool kernel.
+MI355_HD float imp_pool_window(const float* src, int h, int row0, int pitch, int c_stride, int oy, int ox, uint8_t* arg) {
     const int y0 = 2 * oy - 1, x0 = 2 * ox - 1;
     const int ya = y0 < 0 ? 0 : y0, yb = y0 + 3 < h ? y0 + 3 : h;
     const int xa = x0 < 0 ? 0 : x0, xb = x0 + 3 < h ? x0 + 3 : h;
@@ -159,7 +161,7 @@ MI355_HD float imp_pool_window(const float* src, int h, int c_stride, int oy, in
     int bi = (ya - y0) * 3 + (xa - x0);
     for (int y = ya; y < yb; ++y)
         for (int x = xa; x < xb; ++x) {
-            const float v = src[((size_t)y * h + x) * c_stride];
+            const float v = src[((size_t)(y - row0) * pitch + x) * c_stride];
             if (v > best || v != v) {
                 best = v;
                 bi = (y - y0) * 3 + (x - x0);
@@ -169,14 +171,15 @@ MI355_HD float imp_pool_window(const float* src, int h, int c_stride, int oy, in
     return best;
 }
 
-// Max-pool backward of input pixel (iy, ix) of one channel: g / arg point at channel c of output pixel (0, 0), ho = imp_half(h).
-MI355_HD float imp_pool_grad(const float* g, const uint8_t* arg, int ho, int c_stride, int iy, int ix) {
+// Max-pool backward of input pixel (iy, ix) of one channel: g / arg point at channel c of output pixel (orow, 0) (orow > 0: a
+// run of output rows staged in LDS), ho = imp_half(h).
+MI355_HD float imp_pool_grad(const float* g, const uint8_t* arg, int ho, int c_stride, int iy, int ix, int orow = 0) {
     float s = 0.0f;
     const int oya = iy / 2, oyb = (iy + 1) / 2 < ho - 1 ? (iy + 1) / 2 : ho - 1;
     const int oxa = ix / 2, oxb = (ix + 1) / 2 < ho - 1 ? (ix + 1) / 2 : ho - 1;
     for (int oy = oya; oy <= oyb; ++oy)
         for (int ox = oxa; ox <= oxb; ++ox) {
-            const size_t o = ((size_t)oy * ho + ox) * c_stride;
+            const size_t o = ((size_t)(oy - orow) * ho + ox) * c_stride;
             if (arg[o] == (iy - (2 * oy - 1)) * 3 + (ix - (2 * ox - 1))) s = s + g[o];
         }
     return s;

@@ -1075,36 +1075,43 @@ def _impala_trunk(f: ImpalaFamily, name: str, what: str):
     H, W, C = f.frame
 
     def forward(ctx, x, *params):
+        ctx.flagged = bool(params) and isinstance(params[-1], bool)              # ``(x, *params, pooled)``: the 64 family's trailing flag
+        if ctx.flagged:
+            *params, pooled = params
+        kw = {"pooled": True} if ctx.flagged and pooled else {}
         fwd, _ = twins(x, *names)
         xs = x.detach().contiguous()
         ps = [p.detach().contiguous() for p in params]
         impala_check(f, xs, ps)
-        y, saved, arg = fwd(xs, ps)
+        y, saved, arg = fwd(xs, ps, **kw)
         ctx.save_for_backward(xs, saved, arg, *ps)
+        ctx.kw = kw
         return y
 
     def backward(ctx, dy):
         xs, saved, arg, *ps = ctx.saved_tensors
         _, bwd = twins(xs, *names)
-        return (None, *bwd(xs, ps, saved, arg, dy.contiguous()))
+        return (None, *bwd(xs, ps, saved, arg, dy.contiguous(), **ctx.kw), *((None,) if ctx.flagged else ()))
 
     doc = (f"Differentiable ``(x, *params) -> y``: the three ConvSequences of {what} on channels-last {f.frames} x (B,{H},{W},{C}) "
            f"{f.suffix}, y (B,{','.join(map(str, f.out))}) channels-last.  The backward returns the 30 parameter gradients and None "
            f"for the frames (no input gradient is computed).  The HIP kernels run for CUDA tensors, the host twins for CPU ones "
-           f"(same arithmetic).")
+           f"(same arithmetic).  The 64x64x3 family also takes ``(x, *params, pooled)``: a trailing bool that picks the kernels with "
+           f"the max pools fused into the conv launches (same bits; one more None from the backward).")
     # created under its own name: autograd names the backward node (``ImpalaTrunkBackward``) when the class is made
     Trunk = type(name.capitalize() + "Trunk", (torch.autograd.Function,),
                  {"__doc__": doc, "__module__": __name__, "forward": staticmethod(forward), "backward": staticmethod(backward)})
 
-    def trunk(x, params):
+    def trunk(x, params, pooled: bool = False):
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return Trunk.apply(x, *params)
+            return Trunk.apply(x, *params, True) if pooled else Trunk.apply(x, *params)
         fwd, _ = twins(x, *names)
         ps = [p.detach().contiguous() for p in params]
         impala_check(f, x, ps)
-        return fwd(x.contiguous(), ps)[0]
+        return fwd(x.contiguous(), ps, **({"pooled": True} if pooled else {}))[0]
 
-    trunk.__doc__ = f"``{name.capitalize()}Trunk.apply`` when a gradient is wanted, else the forward alone (acting, an old-policy or target pass)."
+    trunk.__doc__ = (f"``{name.capitalize()}Trunk.apply`` when a gradient is wanted, else the forward alone (acting, an old-policy or target pass).  "
+                     f"``pooled`` (the 64x64x3 family): the kernels with the max pools fused into the conv launches, same bits.")
     trunk.__name__ = trunk.__qualname__ = name + "_trunk"
     return Trunk, trunk
 

@@ -200,11 +200,15 @@ def impala_check(f: ImpalaFamily, x, params):
             raise ValueError(f"params[{i}]: expected shape {shp}, got {tuple(p.shape)} (channels must be {list(IMPALA_CHANNELS)})")
 
 
-def _impala_launch(s, f, backward: bool, x, *args) -> None:
-    """The device entry point also takes a workspace, this call's own allocation (not the stream's shared one); the twin takes none."""
+def _impala_launch(s, f, backward: bool, pooled: bool, x, *args) -> None:
+    """The device entry point also takes a workspace, this call's own allocation (not the stream's shared one); the twin takes none.
+    ``pooled`` picks the device side's ``{stem}_fwd_pooled_{suffix}`` / ``_bwd_pooled_`` (the 64x64x3 family's only; same arguments, same
+    bits); the host side ignores it: the plain pair's twins are theirs too."""
     name, B = f.bwd if backward else f.fwd, x.shape[0]
     if s.host:
         return s.launch(name, x.device, *args, B, *f.frame, *IMPALA_CHANNELS)
+    if pooled:
+        name = name.replace("_fwd_", "_fwd_pooled_").replace("_bwd_", "_bwd_pooled_")
     ws = s.empty(int(getattr(_lib.load(), f.workspace_bytes)(B, int(backward))), torch.uint8, x.device)
     s.launch(name, x.device, *args, B, *f.frame, *IMPALA_CHANNELS, _ptr(ws), ws.numel())
 
@@ -218,16 +222,16 @@ def _impala_args(s, f, x, params):
     return int(getattr(lib, f.saved_floats)(x.shape[0])), int(getattr(lib, f.argmax_bytes)(x.shape[0]))
 
 
-def impala_family_forward(s, f: ImpalaFamily, x, params):
+def impala_family_forward(s, f: ImpalaFamily, x, params, pooled: bool = False):
     B = x.shape[0]
     n_saved, n_arg = _impala_args(s, f, x, params)
     dev = x.device
     y, saved, arg = s.empty((B, *f.out), torch.float32, dev), s.empty(n_saved, torch.float32, dev), s.empty(n_arg, torch.uint8, dev)
-    _impala_launch(s, f, False, x, _ptr(x), _ptr_array(params), _ptr(y), _ptr(saved), _ptr(arg))
+    _impala_launch(s, f, False, pooled, x, _ptr(x), _ptr_array(params), _ptr(y), _ptr(saved), _ptr(arg))
     return y, saved, arg
 
 
-def impala_family_backward(s, f: ImpalaFamily, x, params, saved, arg, dy):
+def impala_family_backward(s, f: ImpalaFamily, x, params, saved, arg, dy, pooled: bool = False):
     B = x.shape[0]
     n_saved, n_arg = _impala_args(s, f, x, params)
     s.chk(dy, torch.float32, "dy", (B, *f.out))
@@ -238,21 +242,23 @@ def impala_family_backward(s, f: ImpalaFamily, x, params, saved, arg, dy):
     for p in params:
         grads.append(flat[o:o + p.numel()].view(p.shape))
         o += p.numel()
-    _impala_launch(s, f, True, x, _ptr(x), _ptr_array(params), _ptr(saved), _ptr(arg), _ptr(dy), _ptr_array(grads))
+    _impala_launch(s, f, True, pooled, x, _ptr(x), _ptr_array(params), _ptr(saved), _ptr(arg), _ptr(dy), _ptr_array(grads))
     return grads
 
 
-def impala_forward(s, x, params):
+def impala_forward(s, x, params, pooled: bool = False):
     """The IMPALA-CNN trunk (ppo_procgen.py:86-124 / ppg_procgen.py:123-165, three ConvSequences; csrc/impala.hip, the twin the same
     arithmetic: csrc/impala_rows.h): x (B,64,64,3) f32 channels-last frames, params the 30 conv weights / biases in state_dict order.
-    Returns ``(y (B,8,8,32) channels-last, saved, argmax)``; the last two feed ``impala_backward``."""
-    return impala_family_forward(s, IMPALA64, x, params)
+    Returns ``(y (B,8,8,32) channels-last, saved, argmax)``; the last two feed ``impala_backward``.  ``pooled``: on the device, each
+    sequence's conv + max pool as one kernel (the pre-pool plane stays in LDS); the same bits."""
+    return impala_family_forward(s, IMPALA64, x, params, pooled)
 
 
-def impala_backward(s, x, params, saved, arg, dy):
+def impala_backward(s, x, params, saved, arg, dy, pooled: bool = False):
     """Backward of ``impala_forward``: dy (B,8,8,32) channels-last -> the 30 parameter gradients (one flat buffer's views, written
-    by deterministic fixed-order folds); no input gradient."""
-    return impala_family_backward(s, IMPALA64, x, params, saved, arg, dy)
+    by deterministic fixed-order folds); no input gradient.  ``pooled``: on the device, the pools' backward inside the staging of the
+    conv gradient kernels; the same bits, from either forward's ``saved`` / ``argmax``."""
+    return impala_family_backward(s, IMPALA64, x, params, saved, arg, dy, pooled)
 
 
 def impala84_forward(s, x, params):

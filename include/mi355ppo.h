@@ -560,6 +560,18 @@ MI355PPO_API int mi355ppo_impala_fwd_f32(const float* x, const float* const* par
 MI355PPO_API int mi355ppo_impala_bwd_f32(const float* x, const float* const* params, const float* saved, const uint8_t* argmax,
                                          const float* dy, float* const* grads, int B, int H, int W, int C, int ch0, int ch1, int ch2,
                                          void* workspace, size_t workspace_bytes, void* stream);
+/* The same pair with each sequence's max pool inside its conv launches (MI355PPO_IMPALA=pooled): the forward's conv + bias + pool
+ * is one kernel that keeps the pre-pool plane in LDS, the backward un-pools the pooled gradient inside the staging of the conv's
+ * weight- and data-gradient kernels, so no pre-pool plane is written to or read from HBM.  Same arguments, layouts, sizes
+ * (the workspace's pre-pool region stays unused) and validation; additionally the backward wants argmax 16-byte aligned.  y,
+ * saved, argmax and all 30 gradients equal the plain pair's bit for bit (same k-ordered chains, same tie rule, same folds), so
+ * either forward feeds either backward and the *_cpu twins of the plain pair are these entry points' twins too. */
+MI355PPO_API int mi355ppo_impala_fwd_pooled_f32(const float* x, const float* const* params, float* y, float* saved, uint8_t* argmax,
+                                                int B, int H, int W, int C, int ch0, int ch1, int ch2, void* workspace,
+                                                size_t workspace_bytes, void* stream);
+MI355PPO_API int mi355ppo_impala_bwd_pooled_f32(const float* x, const float* const* params, const float* saved, const uint8_t* argmax,
+                                                const float* dy, float* const* grads, int B, int H, int W, int C, int ch0, int ch1,
+                                                int ch2, void* workspace, size_t workspace_bytes, void* stream);
 /* The same trunk on Atari frame stacks (the student of qdagger_dqn_atari_impalacnn.py:164-184): x is (B, 84, 84, 4) u8
  * channels-last rows as mi355ppo_replay_gather_u8 writes them, read by layer 0 as byte / 255.0f (no f32 copy of the frames is
  * made, no gradient for them); planes 84 -> 42 -> 21 -> 11 (the pool's (h + 1) / 2), y (B, 11, 11, 32).  Same kernels, orders and

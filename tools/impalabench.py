@@ -1,6 +1,6 @@
-"""The IMPALA-CNN trunk of ppo_procgen.py / ppg_procgen.py on one MI355X with both backends (``torch``: the reference's
-ConvSequence modules on MIOpen, ``fused``: the trunk kernels of csrc/impala.hip), timed in one process, alternating the two;
-JSON lines to stdout and to --out.
+"""The IMPALA-CNN trunk of ppo_procgen.py / ppg_procgen.py on one MI355X with the three backends (``torch``: the reference's
+ConvSequence modules on MIOpen, ``fused``: the trunk kernels of csrc/impala.hip, ``pooled``: the same with each max pool inside its
+conv launches), timed in one process, alternating the three; JSON lines to stdout and to --out.
 
     python tools/impalabench.py [--trunk] [--update] [--reps N] [--out FILE]
 
@@ -41,16 +41,20 @@ def flop(B, backward):
     return f * B
 
 
-def hbm_bytes(B, backward):
+def hbm_bytes(B, backward, pooled=False):
     """Minimum traffic of the fused path: frames in, every saved activation written once (and read back once by the
-    backward, which also writes and reads its gradient planes), the pre-pool planes through the pool."""
+    backward, which also writes and reads its gradient planes), the pre-pool planes through the pool: written and read by the
+    forward; the backward writes their gradient once and reads it twice (weight gradient; data gradient of sequences 1 and 2,
+    counted for all three as before).  The pooled path has no pre-pool plane in HBM: instead the argmax bytes (one per pooled
+    value, written once, read by the two gradient launches) and one more read of the pooled gradient."""
     frames = 64 * 64 * 3 * 4
     saved = 4 * (5 * 32 * 32 * 16 + 5 * 16 * 16 * 32 + 4 * 8 * 8 * 32)
     prepool = 4 * (64 * 64 * 16 + 32 * 32 * 32 + 16 * 16 * 32)
-    fwd = frames + saved + 2 * prepool
+    pooled_vals = 32 * 32 * 16 + 16 * 16 * 32 + 8 * 8 * 32
+    fwd = frames + saved + (pooled_vals if pooled else 2 * prepool)
     if not backward:
         return fwd * B
-    return (fwd + frames + 2 * saved + 4 * prepool) * B
+    return (fwd + frames + 2 * saved + (2 * pooled_vals + 4 * pooled_vals if pooled else 4 * prepool)) * B
 
 
 def _emit(rec, out):
@@ -97,30 +101,32 @@ def bench_trunk(reps, out):
             y = agent.network[:3](x.permute(0, 3, 1, 2))
             torch.autograd.grad(y, params, dy.permute(0, 3, 1, 2))
 
-        def run_fused():
+        def run_fused(pooled=False):
             if not backward:
                 with torch.no_grad():
-                    ops.impala_trunk(x, params)
+                    ops.impala_trunk(x, params, pooled=pooled)
                 return
-            y = ops.ImpalaTrunk.apply(x, *params)
+            y = ops.ImpalaTrunk.apply(x, *params, pooled)
             torch.autograd.grad(y, params, dy)
 
-        ts = {"torch": [], "fused": []}
+        legs = [("torch", run_torch), ("fused", run_fused), ("pooled", lambda: run_fused(True))]
+        ts = {name: [] for name, _ in legs}
         for rnd in range(4):                                   # alternate the backends in rounds
-            for name, fn in (("torch", run_torch), ("fused", run_fused)) if rnd % 2 == 0 else (("fused", run_fused), ("torch", run_torch)):
+            for name, fn in legs if rnd % 2 == 0 else legs[::-1]:
                 ts[name] += _events(fn, max(1, reps // 4))
-        for name in ("torch", "fused"):
+        for name, _ in legs:
             ms = float(np.median(ts[name]))
             rec = {"bench": "impala_trunk", "pass": "fwd+bwd" if backward else "fwd", "B": B, "backend": name, "ms": round(ms, 4),
                    "min_ms": round(float(np.min(ts[name])), 4), "n": len(ts[name]), "gflop": round(flop(B, backward) / 1e9, 3),
-                   "tflops": round(flop(B, backward) / ms / 1e9, 2), "min_hbm_mb": round(hbm_bytes(B, backward) / 1e6, 1)}
+                   "tflops": round(flop(B, backward) / ms / 1e9, 2),
+                   "min_hbm_mb": round(hbm_bytes(B, backward, name == "pooled") / 1e6, 1)}
             _emit(rec, out)
 
 
 def bench_update(reps, out):
     res = {}
     for rnd in range(2):
-        for backend in ("torch", "fused") if rnd == 0 else ("fused", "torch"):
+        for backend in ("torch", "fused", "pooled") if rnd == 0 else ("pooled", "fused", "torch"):
             agent, envs = _agent()
             agent.impala_backend = backend
             args = default_args(num_steps=256, num_minibatches=8, update_epochs=3, clip_coef=0.2, learning_rate=5e-4)
